@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- proveSignatureList throughput of the MI355X engine (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...)
 
 A "step" is one zk_prove_batch_device call over one batch of B synthetic proofs (default B = 65536, ring = 2^16:
@@ -9,8 +9,11 @@ BASELINE.json configs[2]) with every input already resident in HBM and the proof
 scaling: proofs are independent given (params, ring), so every rank proves its own B proofs; the only collective is
 the RCCL broadcast of the key ring at set-up (outside the timed region), as the north star prescribes.
 
-The JSON line carries `roofline` for the dominant kernel (k_tom_commit: integer VALU bound)
-and `cpu_baseline` (the C restatement in oracle/, timed on this box's host cores on a bounded sample).
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds everything else the bench measures or
+checks: the verify half, `roofline` for the dominant kernel (k_tom_commit: integer VALU bound)
+from a serial pass of its own, `cpu_baseline` (the C restatement in oracle/, timed on the host cores on a bounded sample)
+with the byte-for-byte check of the last step against it, the host-buffer, JSON and small-batch latency figures, and
+--device-stream.  --dump-outputs DIR writes what the last timed step computed (dump_outputs below).
 """
 import argparse
 import ctypes as C
@@ -73,20 +76,31 @@ def main():
     ap.add_argument('--json-sample', type=int, default=2048, help='proofs converted to the JSON wire format and back by the batch converters, on one host thread and on all of them (toJson / fromJson of the reference bench; 0 = skip)')
     ap.add_argument('--latency', type=int, default=1, help='small-batch latency table (B = 1 .. 4096 proofs per zk_prove_batch / zk_verify_batch call, two ring sizes) in the bench line; 0 = skip')
     ap.add_argument('--check', type=int, default=1 << 30, help='proofs of the last step diffed against the oracle on rank 0 (at most the CPU sample)')
+    ap.add_argument('--full', action='store_true', help='also run the measurements and checks beyond the timed steps (verify half, roofline pass, CPU baseline and oracle check, '
+                    'host-buffer, JSON and latency figures, --device-stream) in the default prove mode; the options that tune them apply only with --full')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write what the last timed step computed to DIR/<name>.npy (rank 0; see dump_outputs)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.dump_outputs and (args.pool or args.mode != 'prove'):
+        ap.error('--dump-outputs covers the default prove step only')
 
+    if not (args.full or args.pool):   # a plain run: set-up, warm-up, the timed steps, the dump, the line (--pool, like --mode verify, runs only when asked for)
+        args.device_stream = args.roofline_steps = args.verify_steps = args.host_io = args.json_sample = args.latency = 0
+        args.no_cpu_baseline = True
     if args.verify_steps < 0:
         args.verify_steps = max(5, args.steps)
     # A bare `python3 bench.py --gpus N` (N > 1, no launcher in the environment) starts its own ranks: the documented launch line, one rank per GPU.
     if args.gpus > 1 and not args.pool and 'WORLD_SIZE' not in os.environ:
         import socket
+        import subprocess
         with socket.socket() as sk:
             sk.bind(('127.0.0.1', 0))
             port = sk.getsockname()[1]
         cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(args.gpus), '--master-addr', '127.0.0.1', '--master-port', str(port),
                os.path.abspath(__file__)] + sys.argv[1:]
         print('bench.py: --gpus %d without WORLD_SIZE: re-executing as `%s`' % (args.gpus, ' '.join(cmd[1:])), file=sys.stderr, flush=True)
-        os.execv(sys.executable, cmd)
+        return subprocess.call(cmd)
     import zkp_ecdsa_amd as Z
     if args.pool:
         return run_pool_mode(args, Z)
@@ -162,6 +176,8 @@ def main():
         step()
     barrier()
     dt = time.time() - t0
+    if args.dump_outputs and rank == 0:   # before the passes of --full write into the same buffers
+        dump_outputs(args.dump_outputs, torch, d_out, d_off, d_st, B, args.seed)
     # the same steps as jobs in flight on the context: submit(0) .. submit(n-1); wait(0); submit(n); wait(1); ...
     dstream = None
     if args.device_stream >= 2:
@@ -271,96 +287,98 @@ def main():
     hbm_used = total_b - free_b
     if rank == 0:
         n_log2 = max(1, (nkeys - 1).bit_length())
-        # --- roofline of the dominant kernel, from HIP events recorded on the engine's stream around every launch
-        off_l = off.tolist()
-        zeros_total = sum(((off_l[i + 1] - off_l[i]) - (304 + 336 * sec + (4 * 72 + 96) * n_log2 + 32)) // 3392 for i in range(B) if off_l[i + 1] > off_l[i])
-        commits_per_step = B * (2 + 2 * sec) + zeros_total * 34 + B * 4 * n_log2
-        tom_ms = fam.get('tom_commit', 0.0) / max(1, args.roofline_steps)
-        launches_per_step = 4 * ((B + eng_chunk(args, B) - 1) // eng_chunk(args, B))   # lists A, B (unpaired + paired slots), C
-        # executed additions: 2 * nwin per commitment, except, per PointAdd item, the 9 pairs that share v*g (3 * nwin per pair) and
-        # C4 of pi8, whose value is i7 * i8 = 1: its g-windows above the first are skipped wave-wide on unsigned combs (k_tom.hip)
-        nwin = (256 + args.comb_bits - 1) // args.comb_bits
-        skipped = nwin - 1 if args.comb_bits <= 24 else 0
-        adds = (commits_per_step - 34 * zeros_total) * 2 * nwin + zeros_total * ((16 * 2 + 9 * 3) * nwin - skipped)
-        # 8 modmuls per addition; the first one of a comb is 1 (identity + entry), the last one 7 (no T coordinate)
-        modmuls = adds * 8 - (commits_per_step - 34 * zeros_total) * 8 - zeros_total * (16 * 8 + 9 * 9)
-        modmuls_per_commit = round(modmuls / commits_per_step, 2)
-        pmc_bytes = TOM_COMMIT_PMC_BYTES.get(args.comb_bits)
-        macs = modmuls * MACS_PER_MODMUL
-        achieved_tmacs = macs / (tom_ms * 1e-3) / 1e12 if tom_ms > 0 else 0.0
-        hbm_gbps = commits_per_step * TOM_COMMIT_BYTES / (tom_ms * 1e-3) / 1e9 if tom_ms > 0 else 0.0
-        wt, wq, wring = nominal_modmuls(n_log2)
-        roofline = {
-            'bound': 'valu_int32',
-            'kernel': 'k_tom_commit',
-            'achieved': round(achieved_tmacs, 3), 'peak': VALU_MAD_PEAK_TOPS, 'unit': 'T multiplier-instr/s (v_mad_u64_u32 + v_mul_lo_u32 lane-ops, peak measured by tools/valu_peak.hip)',
-            'frac': round(achieved_tmacs / VALU_MAD_PEAK_TOPS, 4),
-            'frac_of_rate_at_kernel_ilp': round(achieved_tmacs / VALU_MAD_8CHAIN_TOPS, 4),
-            'rate_at_kernel_ilp': {'value': VALU_MAD_8CHAIN_TOPS, 'note': 'v_mad_u64_u32 microbenchmark at 8 independent chains per SIMD (4 per wave x 2 waves: what 212 VGPRs allow); '
-                                   'the kernel issues 1.39 VALU instructions per multiplier instruction on top (profiles/r03_valu_peak_microbench.txt, DESIGN.md section 8)'},
-            'traffic': int(commits_per_step / max(1, launches_per_step) * pmc_bytes) if pmc_bytes else None,
-            'traffic_note': ('bytes per launch = units per launch x %d B (FETCH_SIZE + WRITE_SIZE per commitment, separate rocprofv3 --pmc passes, '
-                             'profiles/r05_pmc_summary.txt); table gathers, not the 180 algorithmic bytes, dominate' % pmc_bytes) if pmc_bytes
-                            else 'no PMC pass recorded for this comb width',
-            'valu_active_per_wave': TOM_COMMIT_VALU_ACTIVE_PER_WAVE.get(args.comb_bits),
-            'pmc_source': PMC_SOURCE,
-            'comb_bits': args.comb_bits,
-            'avg_launch_ms': round(tom_ms / max(1, launches_per_step), 3),
-            'launches_per_step': launches_per_step,
-            'units_per_step': commits_per_step,
-            'executed_modmuls_per_unit': modmuls_per_commit, 'nominal_modmuls_per_unit': TOM_COMMIT_NOMINAL,
-            'hbm': {'achieved': round(hbm_gbps, 2), 'peak': HBM_PEAK_GBPS, 'unit': 'GB/s', 'frac': round(hbm_gbps / HBM_PEAK_GBPS, 5),
-                    'algorithmic_bytes_per_unit': TOM_COMMIT_BYTES},
-            'share_of_gpu_time': round(fam.get('tom_commit', 0.0) / gpu_ms, 3) if gpu_ms else None,
-            'nominal_modmuls_per_proof': {'F_t': wt, 'F_q_ec': wq, 'F_q_ring': wring},
-        }
-        # ---- the two next-largest arithmetic kernels, priced the same way (multiplier instructions of the shipped ISA / measured peak)
-        others = {}
-        exp_ms = fam.get('p256_exp_commit', 0.0) / max(1, args.roofline_steps)
-        if exp_ms > 0:
-            lanes = B * (sec + 1)
-            adds = EXP_KT_ADDS if kt_count else EXP_RTAB_ADDS
-            ops = lanes * adds * EXP_ADD_MACS
-            others['k_exp_commit_kt' if kt_count else 'k_exp_commit'] = {
-                'units': lanes, 'unit': 'T_i = alpha_i R, A_i = T_i + r_i h (one lane each; exp.ts:144-149)', 'mixed_additions_per_unit': adds,
-                'multiplier_instr_per_addition': EXP_ADD_MACS, 'ms_per_step': round(exp_ms, 2), 'achieved': round(ops / (exp_ms * 1e-3) / 1e12, 3),
-                'peak': VALU_MAD_PEAK_TOPS, 'frac': round(ops / (exp_ms * 1e-3) / 1e12 / VALU_MAD_PEAK_TOPS, 4),
-                'note': 'ISA count of the loop body (tools/isa_blocks.py: 1872 v_mad_u64_u32 + 99 v_mul_lo_u32 per mixed complete addition of 11 products); 13 + 33 + 13 gathered '
-                        'table entries per lane minus the first (no addition)'}
-        if verify and verify.get('msm_live_terms'):
-            bms = verify['gpu_ms_by_family_per_step'].get('+v_msm_bucket', 0.0)
-            terms = verify['msm_live_terms']
-            # a 256-bit term has a digit in all 16 windows, a 128-bit one in 8; per proof 135 of the former and 312 of the latter are expected at n = 16
-            # (10 zero-bit slots x (10 + 26), 10 one-bit slots x 2, 8 membership groups x (4 + 4), 3 per proof); a bucket's first term is a copy
-            nq = (n_log2 + 1) // 2
-            t256, t128 = 10 * 10 + nq * 4 + 3, 10 * 26 + 10 * 2 + nq * 4
-            adds = terms * (16 * t256 + 8 * t128) / (t256 + t128) - 2 * 16 * 8 * 65535 * ((B + vchunk - 1) // vchunk) / 2
-            ops = adds * 8 * MACS_PER_MODMUL
-            if bms > 0:
-                others['k_msm_bucket'] = {'units': int(adds), 'unit': 'niels additions into (window, group, digit) buckets, 8 products each (estimate from the live-term count)',
-                                          'live_terms': terms, 'ms_per_step': round(bms, 2), 'achieved': round(ops / (bms * 1e-3) / 1e12, 3), 'peak': VALU_MAD_PEAK_TOPS,
-                                          'frac': round(ops / (bms * 1e-3) / 1e12 / VALU_MAD_PEAK_TOPS, 4),
-                                          'note': 'one lane per bucket, lanes of a wave walk lists of equal length (buckets ordered by size); gathers of 128-byte entries'}
-        roofline['others'] = others
-        if verify and 'k_msm_bucket' in others:
-            # the verify half priced like the prove half: its largest arithmetic kernel against the multiplier peak, and how much of the (serial) verify step is
-            # not modular arithmetic at all -- SHA-256 (challenges, sampler), the grouping of the bucket pass's keys, packing, parsing
-            vf = verify['gpu_ms_by_family_per_step']
-            vsum = sum(v for k, v in vf.items() if not k.startswith('+'))
-            non_arith = {k: vf[k] for k in ('v_hash', '+v_msm_group') if k in vf}
-            verify['roofline'] = {'bound': 'valu_int32', 'kernel': 'k_msm_bucket', 'achieved': others['k_msm_bucket']['achieved'], 'peak': VALU_MAD_PEAK_TOPS,
-                                  'unit': roofline['unit'], 'frac': others['k_msm_bucket']['frac'], 'ms_per_step': others['k_msm_bucket']['ms_per_step'],
-                                  'share_of_gpu_time': round(others['k_msm_bucket']['ms_per_step'] / vsum, 3) if vsum else None,
-                                  'traffic': 19015000000, 'traffic_note': 'bytes fetched per launch of a 32 768-proof chunk (FETCH_SIZE, its own rocprofv3 --pmc pass, raw: '
-                                  'profiles/r05_pmc_verify.txt; a constant of bench.py, NOT measured in this run): the 137 M gathered 128-byte entries and their ids (18.2 GB), nothing re-read; '
-                                  'SIMD busy 0.945',
-                                  'family_sum_ms_per_step': round(vsum, 2), 'single_lane_wall_ms_per_step': verify.get('gpu_ms_single_lane_wall'),
-                                  'overlapped_families': ['v_msm_p256'],   # on an auxiliary stream beside v_msm_tom even with one lane: the family sum exceeds the wall time by that overlap
-                                  'whole_step_simd_busy': VERIFY_WHOLE_STEP_SIMD_BUSY, 'whole_step_source': VERIFY_PMC_SOURCE,
-                                  'non_arithmetic_ms': non_arith,
-                                  'non_arithmetic_share': round(sum(non_arith.values()) / vsum, 3) if vsum else None,
-                                  'note': 'non_arithmetic = SHA-256 (both challenges, the sampler\'s fills) and the hand-written grouping of the bucket pass\'s keys '
-                                          '(k_msm_hist / _scatter / _binsort); v_parse_validate is arithmetic (one curve check per point)'}
+        roofline = None
+        if fam:   # the serial pass of --full ran
+            # --- roofline of the dominant kernel, from HIP events recorded on the engine's stream around every launch
+            off_l = off.tolist()
+            zeros_total = sum(((off_l[i + 1] - off_l[i]) - (304 + 336 * sec + (4 * 72 + 96) * n_log2 + 32)) // 3392 for i in range(B) if off_l[i + 1] > off_l[i])
+            commits_per_step = B * (2 + 2 * sec) + zeros_total * 34 + B * 4 * n_log2
+            tom_ms = fam.get('tom_commit', 0.0) / max(1, args.roofline_steps)
+            launches_per_step = 4 * ((B + eng_chunk(args, B) - 1) // eng_chunk(args, B))   # lists A, B (unpaired + paired slots), C
+            # executed additions: 2 * nwin per commitment, except, per PointAdd item, the 9 pairs that share v*g (3 * nwin per pair) and
+            # C4 of pi8, whose value is i7 * i8 = 1: its g-windows above the first are skipped wave-wide on unsigned combs (k_tom.hip)
+            nwin = (256 + args.comb_bits - 1) // args.comb_bits
+            skipped = nwin - 1 if args.comb_bits <= 24 else 0
+            adds = (commits_per_step - 34 * zeros_total) * 2 * nwin + zeros_total * ((16 * 2 + 9 * 3) * nwin - skipped)
+            # 8 modmuls per addition; the first one of a comb is 1 (identity + entry), the last one 7 (no T coordinate)
+            modmuls = adds * 8 - (commits_per_step - 34 * zeros_total) * 8 - zeros_total * (16 * 8 + 9 * 9)
+            modmuls_per_commit = round(modmuls / commits_per_step, 2)
+            pmc_bytes = TOM_COMMIT_PMC_BYTES.get(args.comb_bits)
+            macs = modmuls * MACS_PER_MODMUL
+            achieved_tmacs = macs / (tom_ms * 1e-3) / 1e12 if tom_ms > 0 else 0.0
+            hbm_gbps = commits_per_step * TOM_COMMIT_BYTES / (tom_ms * 1e-3) / 1e9 if tom_ms > 0 else 0.0
+            wt, wq, wring = nominal_modmuls(n_log2)
+            roofline = {
+                'bound': 'valu_int32',
+                'kernel': 'k_tom_commit',
+                'achieved': round(achieved_tmacs, 3), 'peak': VALU_MAD_PEAK_TOPS, 'unit': 'T multiplier-instr/s (v_mad_u64_u32 + v_mul_lo_u32 lane-ops, peak measured by tools/valu_peak.hip)',
+                'frac': round(achieved_tmacs / VALU_MAD_PEAK_TOPS, 4),
+                'frac_of_rate_at_kernel_ilp': round(achieved_tmacs / VALU_MAD_8CHAIN_TOPS, 4),
+                'rate_at_kernel_ilp': {'value': VALU_MAD_8CHAIN_TOPS, 'note': 'v_mad_u64_u32 microbenchmark at 8 independent chains per SIMD (4 per wave x 2 waves: what 212 VGPRs allow); '
+                                       'the kernel issues 1.39 VALU instructions per multiplier instruction on top (profiles/r03_valu_peak_microbench.txt, DESIGN.md section 8)'},
+                'traffic': int(commits_per_step / max(1, launches_per_step) * pmc_bytes) if pmc_bytes else None,
+                'traffic_note': ('bytes per launch = units per launch x %d B (FETCH_SIZE + WRITE_SIZE per commitment, separate rocprofv3 --pmc passes, '
+                                 'profiles/r05_pmc_summary.txt); table gathers, not the 180 algorithmic bytes, dominate' % pmc_bytes) if pmc_bytes
+                                else 'no PMC pass recorded for this comb width',
+                'valu_active_per_wave': TOM_COMMIT_VALU_ACTIVE_PER_WAVE.get(args.comb_bits),
+                'pmc_source': PMC_SOURCE,
+                'comb_bits': args.comb_bits,
+                'avg_launch_ms': round(tom_ms / max(1, launches_per_step), 3),
+                'launches_per_step': launches_per_step,
+                'units_per_step': commits_per_step,
+                'executed_modmuls_per_unit': modmuls_per_commit, 'nominal_modmuls_per_unit': TOM_COMMIT_NOMINAL,
+                'hbm': {'achieved': round(hbm_gbps, 2), 'peak': HBM_PEAK_GBPS, 'unit': 'GB/s', 'frac': round(hbm_gbps / HBM_PEAK_GBPS, 5),
+                        'algorithmic_bytes_per_unit': TOM_COMMIT_BYTES},
+                'share_of_gpu_time': round(fam.get('tom_commit', 0.0) / gpu_ms, 3) if gpu_ms else None,
+                'nominal_modmuls_per_proof': {'F_t': wt, 'F_q_ec': wq, 'F_q_ring': wring},
+            }
+            # ---- the two next-largest arithmetic kernels, priced the same way (multiplier instructions of the shipped ISA / measured peak)
+            others = {}
+            exp_ms = fam.get('p256_exp_commit', 0.0) / max(1, args.roofline_steps)
+            if exp_ms > 0:
+                lanes = B * (sec + 1)
+                adds = EXP_KT_ADDS if kt_count else EXP_RTAB_ADDS
+                ops = lanes * adds * EXP_ADD_MACS
+                others['k_exp_commit_kt' if kt_count else 'k_exp_commit'] = {
+                    'units': lanes, 'unit': 'T_i = alpha_i R, A_i = T_i + r_i h (one lane each; exp.ts:144-149)', 'mixed_additions_per_unit': adds,
+                    'multiplier_instr_per_addition': EXP_ADD_MACS, 'ms_per_step': round(exp_ms, 2), 'achieved': round(ops / (exp_ms * 1e-3) / 1e12, 3),
+                    'peak': VALU_MAD_PEAK_TOPS, 'frac': round(ops / (exp_ms * 1e-3) / 1e12 / VALU_MAD_PEAK_TOPS, 4),
+                    'note': 'ISA count of the loop body (tools/isa_blocks.py: 1872 v_mad_u64_u32 + 99 v_mul_lo_u32 per mixed complete addition of 11 products); 13 + 33 + 13 gathered '
+                            'table entries per lane minus the first (no addition)'}
+            if verify and verify.get('msm_live_terms'):
+                bms = verify['gpu_ms_by_family_per_step'].get('+v_msm_bucket', 0.0)
+                terms = verify['msm_live_terms']
+                # a 256-bit term has a digit in all 16 windows, a 128-bit one in 8; per proof 135 of the former and 312 of the latter are expected at n = 16
+                # (10 zero-bit slots x (10 + 26), 10 one-bit slots x 2, 8 membership groups x (4 + 4), 3 per proof); a bucket's first term is a copy
+                nq = (n_log2 + 1) // 2
+                t256, t128 = 10 * 10 + nq * 4 + 3, 10 * 26 + 10 * 2 + nq * 4
+                adds = terms * (16 * t256 + 8 * t128) / (t256 + t128) - 2 * 16 * 8 * 65535 * ((B + vchunk - 1) // vchunk) / 2
+                ops = adds * 8 * MACS_PER_MODMUL
+                if bms > 0:
+                    others['k_msm_bucket'] = {'units': int(adds), 'unit': 'niels additions into (window, group, digit) buckets, 8 products each (estimate from the live-term count)',
+                                              'live_terms': terms, 'ms_per_step': round(bms, 2), 'achieved': round(ops / (bms * 1e-3) / 1e12, 3), 'peak': VALU_MAD_PEAK_TOPS,
+                                              'frac': round(ops / (bms * 1e-3) / 1e12 / VALU_MAD_PEAK_TOPS, 4),
+                                              'note': 'one lane per bucket, lanes of a wave walk lists of equal length (buckets ordered by size); gathers of 128-byte entries'}
+            roofline['others'] = others
+            if verify and 'k_msm_bucket' in others:
+                # the verify half priced like the prove half: its largest arithmetic kernel against the multiplier peak, and how much of the (serial) verify step is
+                # not modular arithmetic at all -- SHA-256 (challenges, sampler), the grouping of the bucket pass's keys, packing, parsing
+                vf = verify['gpu_ms_by_family_per_step']
+                vsum = sum(v for k, v in vf.items() if not k.startswith('+'))
+                non_arith = {k: vf[k] for k in ('v_hash', '+v_msm_group') if k in vf}
+                verify['roofline'] = {'bound': 'valu_int32', 'kernel': 'k_msm_bucket', 'achieved': others['k_msm_bucket']['achieved'], 'peak': VALU_MAD_PEAK_TOPS,
+                                      'unit': roofline['unit'], 'frac': others['k_msm_bucket']['frac'], 'ms_per_step': others['k_msm_bucket']['ms_per_step'],
+                                      'share_of_gpu_time': round(others['k_msm_bucket']['ms_per_step'] / vsum, 3) if vsum else None,
+                                      'traffic': 19015000000, 'traffic_note': 'bytes fetched per launch of a 32 768-proof chunk (FETCH_SIZE, its own rocprofv3 --pmc pass, raw: '
+                                      'profiles/r05_pmc_verify.txt; a constant of bench.py, NOT measured in this run): the 137 M gathered 128-byte entries and their ids (18.2 GB), nothing re-read; '
+                                      'SIMD busy 0.945',
+                                      'family_sum_ms_per_step': round(vsum, 2), 'single_lane_wall_ms_per_step': verify.get('gpu_ms_single_lane_wall'),
+                                      'overlapped_families': ['v_msm_p256'],   # on an auxiliary stream beside v_msm_tom even with one lane: the family sum exceeds the wall time by that overlap
+                                      'whole_step_simd_busy': VERIFY_WHOLE_STEP_SIMD_BUSY, 'whole_step_source': VERIFY_PMC_SOURCE,
+                                      'non_arithmetic_ms': non_arith,
+                                      'non_arithmetic_share': round(sum(non_arith.values()) / vsum, 3) if vsum else None,
+                                      'note': 'non_arithmetic = SHA-256 (both challenges, the sampler\'s fills) and the hand-written grouping of the bucket pass\'s keys '
+                                              '(k_msm_hist / _scatter / _binsort); v_parse_validate is arithmetic (one curve check per point)'}
         cpu = None
         if not args.no_cpu_baseline:   # rank 0, at every N (the other ranks wait at the final barrier)
             sample = args.cpu_sample or 4 * host_cores()
@@ -411,10 +429,11 @@ def main():
                        'parallelism': 'proofs sharded per GPU; ring broadcast over RCCL at set-up' if world > 1 else 'single GPU'},
             'set_params_s': round(t_tab, 3),
             'key_table_proofs_last_chunk': kt_count,   # zk_test_counter(ctx, 1): proofs of the last chunk whose multiples of the signer's key came from the per-key tables
-            'hbm_used_gb': round(hbm_used / 2**30, 1),   # tables + both lanes' prover and verifier workspaces + this step's proofs
+            'hbm_used_gb': round(hbm_used / 2**30, 1),   # tables + the lanes' prover workspaces (+ the verifier's with --full) + this step's proofs
             'proof_bytes_per_step': total_bytes, 'failed_proofs': nbad,
-            'gpu_ms_by_family_per_step': {k: round(v / max(1, args.roofline_steps), 2) for k, v in sorted(fam.items(), key=lambda kv: -kv[1])},
-            'gpu_ms_note': 'serial single-lane pass (sum = %.1f ms); the timed steps overlap %d chunks on %d streams' % (gpu_ms / max(1, args.roofline_steps), args.lanes, args.lanes),
+            'gpu_ms_by_family_per_step': {k: round(v / max(1, args.roofline_steps), 2) for k, v in sorted(fam.items(), key=lambda kv: -kv[1])} if fam else None,
+            'gpu_ms_note': 'serial single-lane pass (sum = %.1f ms); the timed steps overlap %d chunks on %d streams' % (gpu_ms / max(1, args.roofline_steps), args.lanes, args.lanes)
+                           if fam else None,
             'roofline': roofline, 'cpu_baseline': cpu, 'verify': verify, 'host_io': host_io, 'json': json_rates, 'latency': latency,
         }
         if latency and 'rings' in latency:   # one proof per call is the reference's only shape (src/zkpAttestList.ts:104-145)
@@ -452,5 +471,37 @@ def eng_chunk(args, B):
     return min(args.chunk, B)
 
 
+DUMP_LIMIT = 64 * 10**6        # bytes of all files of one --dump-outputs
+DUMP_TAIL = 64                 # last bytes of every proof: its final responses, which depend on every challenge before them
+DUMP_SAMPLE_BYTES = 8 << 20    # proof bytes in the seeded sample of whole proofs (32 MiB as float32)
+
+
+def dump_outputs(path, torch, d_out, d_off, d_st, B, seed):
+    """--dump-outputs: what a prove step hands its caller -- the status of every proof, the offsets of the proofs in the output buffer
+    and the proof bytes.  The bytes are ~11 GB at the default shape, so of them: the last DUMP_TAIL bytes of every proof (-1 where a
+    proof is shorter; fewer bytes when B is large) and whole proofs drawn in an order fixed by `seed`.  One value per element,
+    float32 (statuses, bytes) or float64 (offsets, indices), at most DUMP_LIMIT bytes in all."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    off = d_off.cpu().numpy()
+    tail_len = max(1, min(DUMP_TAIL, (16 << 20) // (4 * B)))
+    pos = d_off[1:, None] - tail_len + torch.arange(tail_len, device=d_off.device)
+    tail = torch.where(pos >= d_off[:-1, None], d_out[pos.clamp(0, d_out.numel() - 1)].to(torch.int32), -1)
+    budget = min(DUMP_SAMPLE_BYTES, (DUMP_LIMIT - 4 * B - 8 * (B + 1) - 4 * B * tail_len - 4096) // 4)   # what the other arrays and the .npy headers leave
+    pick, nbytes = [], 0
+    for i in np.random.default_rng(seed).permutation(B):
+        n = int(off[i + 1] - off[i])
+        if nbytes + n > budget:
+            break
+        pick.append(int(i))
+        nbytes += n
+    pick.sort()
+    sample = torch.cat([d_out[int(off[i]):int(off[i + 1])] for i in pick]) if pick else d_out[:0]
+    out = {'status': d_st.cpu().numpy().astype(np.float32), 'proof_offsets': off.astype(np.float64), 'proof_tail_bytes': tail.cpu().numpy().astype(np.float32),
+           'proof_sample_index': np.array(pick, dtype=np.float64), 'proof_sample_bytes': sample.cpu().numpy().astype(np.float32)}
+    for name, a in out.items():
+        np.save(os.path.join(path, name + '.npy'), a)
+
+
 if __name__ == '__main__':
-    main()
+    sys.exit(main())

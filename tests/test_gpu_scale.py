@@ -341,7 +341,7 @@ def test_the_references_own_bench_ring_of_100001_keys_runs_on_the_key_tables():
     that ring too (35 GB at 2^17 keys; they stopped at 2^16 until round 4), every proof of the CPU sample is diffed byte for byte against
     the oracle inside bench.py, every proof verifies, and the line carries the small-batch latency table."""
     line = _bench(['--ring', '100001', '--batch', '8192', '--chunk', '4096', '--lanes', '2', '--verify-chunk', '4096', '--steps', '1', '--warmup', '1',
-                   '--cpu-sample', '8', '--host-io', '0', '--json-sample', '0'], timeout=1500)
+                   '--cpu-sample', '8', '--host-io', '0', '--json-sample', '0', '--full'], timeout=1500)
     assert 'ring=100001 keys (n=17)' in line['config']['workload'] and 'per-key tables' in line['config']['workload']
     assert line['key_table_proofs_last_chunk'] == 4096          # zk_test_counter(ctx, 1): every proof of the last chunk went through them
     assert line['failed_proofs'] == 0 and line['cpu_baseline']['checked_bit_exact'] == 8
@@ -349,6 +349,29 @@ def test_the_references_own_bench_ring_of_100001_keys_runs_on_the_key_tables():
     lat = line['latency']['rings']
     assert set(lat) == {'100001', '1024'} and set(lat['1024']) == {'1', '8', '64', '512'} and set(lat['100001']) == {'1', '8', '64', '512', '4096'}
     assert line['latency_ms_b1'] == lat['100001']['1']['prove_ms'] > 0
+
+
+def test_plain_bench_run_times_the_steps_and_dumps_the_last_steps_outputs(tmp_path):
+    """bench.py without --full: the line carries the timed steps and none of the --full measurements, and --dump-outputs writes what
+    the last timed step computed -- statuses, offsets, the tail of every proof and a seeded sample of whole proofs -- which must be
+    the proofs the engine makes for the same seeded workload."""
+    import numpy as np
+    B, nkeys, S = 2048, 4096, 2024
+    line = _bench(['--batch', str(B), '--ring', str(nkeys), '--chunk', '1024', '--lanes', '2', '--comb-bits', '16', '--steps', '3', '--warmup', '1',
+                   '--seed', str(S), '--dump-outputs', str(tmp_path)])
+    assert line['steps'] == 3 and line['ms_per_step'] > 0 and line['value'] > 0 and line['failed_proofs'] == 0
+    assert all(line[k] is None for k in ('verify', 'cpu_baseline', 'roofline', 'host_io', 'json', 'latency', 'gpu_ms_by_family_per_step'))
+    d = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert set(d) == {'status', 'proof_offsets', 'proof_tail_bytes', 'proof_sample_index', 'proof_sample_bytes'}
+    assert all(a.dtype in (np.float32, np.float64) for a in d.values()) and sum(a.nbytes for a in d.values()) <= 64 * 10**6
+    eng, _, (ring, msg, sig, pk, which, seeds) = _engine(S, nkeys, B, comb_bits=16)
+    proofs, st = eng.prove_batch(msg, sig, pk, which, seeds=seeds)
+    eng.close()
+    assert not any(st) and not d['status'].any()
+    assert list(np.diff(d['proof_offsets'].astype(np.int64))) == [len(p) for p in proofs]
+    assert all(bytes(d['proof_tail_bytes'][i].astype(np.uint8)) == proofs[i][-64:] for i in range(B))
+    pick = d['proof_sample_index'].astype(np.int64)
+    assert len(pick) > 0 and bytes(d['proof_sample_bytes'].astype(np.uint8)) == b''.join(proofs[i] for i in pick)
 
 
 def test_pool_prove_with_device_resident_output_equals_the_host_buffer_call():
@@ -466,7 +489,7 @@ def test_bench_starts_its_own_ranks_from_a_bare_gpus_line():
     import subprocess
     import sys
     res = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '1', '--warmup', '1', '--batch', '2048', '--ring', '4096', '--chunk', '1024', '--lanes', '2',
-                          '--verify-chunk', '1024', '--comb-bits', '16', '--host-io', '0', '--cpu-sample', '2', '--json-sample', '0', '--latency', '0'],
+                          '--verify-chunk', '1024', '--comb-bits', '16', '--host-io', '0', '--cpu-sample', '2', '--json-sample', '0', '--latency', '0', '--full'],
                          cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     lines = [l for l in res.stdout.splitlines() if l.startswith('{"metric"')]
     assert res.returncode == 0 and len(lines) == 1, res.stdout[-2000:] + res.stderr[-3000:]

@@ -5,7 +5,7 @@ export GPU_MAX_HW_QUEUES=8
 O=gpurun_out/r06ab
 mkdir -p $O
 timeout 600 python -m pytest tests/test_gpu_primitives.py tests/test_gpu_prove.py -q -m gpu -k "sha or rng or golden or config2 or cooperative" > $O/bitop_tests.log 2>&1; echo "tests rc=$?"; tail -3 $O/bitop_tests.log
-ARGS="--steps 4 --warmup 1 --verify-steps 5 --roofline-steps 1 --host-io 0 --json-sample 0 --latency 1 --no-cpu-baseline"
+ARGS="--full --steps 4 --warmup 1 --verify-steps 5 --roofline-steps 1 --host-io 0 --json-sample 0 --latency 1 --no-cpu-baseline"
 for rep in 1 2; do
   for v in prebitop main; do
     lib=$PWD/zkp-ecdsa_amd/build_ab/lib_$v.so; [ $v = main ] && lib=$PWD/zkp-ecdsa_amd/lib/libzkattest_hip.so

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Compare bench.py JSON lines of library variants (tools/ab_variants.sh): per-family GPU ms of the serial pass."""
 import json, sys, glob, os
-files = sys.argv[1:] or sorted(glob.glob('gpurun_out/ab/*.json'))
+files = sys.argv[1:] or sorted(glob.glob(os.path.join(os.environ.get('OUT_DIR', 'out'), 'ab', '*.json')))
 rows = {}
 names = []
 for f in files:

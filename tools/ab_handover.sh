@@ -6,7 +6,7 @@
 export GPU_MAX_HW_QUEUES=8
 O=gpurun_out/r06ab
 mkdir -p $O
-ARGS="--steps 6 --warmup 2 --verify-steps 5 --roofline-steps 0 --host-io 0 --json-sample 0 --latency 0 --no-cpu-baseline"
+ARGS="--full --steps 6 --warmup 2 --verify-steps 5 --roofline-steps 0 --host-io 0 --json-sample 0 --latency 0 --no-cpu-baseline"
 for rep in 1 2 3; do
   for v in main cachedscan; do
     lib=$PWD/zkp-ecdsa_amd/build_ab/lib_$v.so; [ $v = main ] && lib=$PWD/zkp-ecdsa_amd/lib/libzkattest_hip.so

@@ -4,7 +4,7 @@
 export GPU_MAX_HW_QUEUES=8
 O=gpurun_out/r06ab
 mkdir -p $O
-ARGS="--steps 3 --warmup 1 --verify-steps 5 --roofline-steps 1 --host-io 0 --json-sample 0 --latency 0 --no-cpu-baseline"
+ARGS="--full --steps 3 --warmup 1 --verify-steps 5 --roofline-steps 1 --host-io 0 --json-sample 0 --latency 0 --no-cpu-baseline"
 for rep in 1 2; do
   for v in main norm32 norm16 norm8; do
     lib=$PWD/zkp-ecdsa_amd/build_ab/lib_$v.so; [ $v = main ] && lib=$PWD/zkp-ecdsa_amd/lib/libzkattest_hip.so

@@ -1,6 +1,6 @@
 # same-box A/B of the verifier's cross-proof P-256 pass (k_pmsm.hip): on (default threshold), off (ZKATTEST_P256_BATCH=0), on again; then a serial kernel trace
 mkdir -p gpurun_out
-ARGS="--steps 1 --warmup 1 --roofline-steps 0 --verify-steps 3 --host-io 0 --json-sample 0 --latency 0 --no-cpu-baseline"
+ARGS="--full --steps 1 --warmup 1 --roofline-steps 0 --verify-steps 3 --host-io 0 --json-sample 0 --latency 0 --no-cpu-baseline"
 for v in on off on2; do
   e=8192; [ $v = off ] && e=0
   ZKATTEST_P256_BATCH=$e timeout 300 python bench.py $ARGS 2>gpurun_out/p256_$v.err | grep '"metric"' > gpurun_out/p256_$v.json

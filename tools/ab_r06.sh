@@ -27,7 +27,7 @@ if sys.argv[2]=='1': print('   prove fam', d['prove_families_ms']); print('   ve
 PY
   done
 done
-BARGS="--steps 2 --warmup 1 --verify-steps 5 --roofline-steps 1 --host-io 0 --json-sample 0 --latency 0 --no-cpu-baseline"
+BARGS="--full --steps 2 --warmup 1 --verify-steps 5 --roofline-steps 1 --host-io 0 --json-sample 0 --latency 0 --no-cpu-baseline"
 for rep in 1 2; do
   for v in "main $MAIN 0" "onelane $MAIN 1" "r5 $R5 1"; do
     set -- $v
@@ -48,7 +48,7 @@ for v in "main $MAIN 0" "onelane $MAIN 1"; do
   set -- $v
   run $1 $2 $3 timeout 600 rocprofv3 --kernel-trace -d $ROOT/$O/prof_b1_$1 -o r -- python $ROOT/tools/b1_timeline.py run > $ROOT/$O/b1_$1.log 2>&1
   python $ROOT/tools/b1_timeline.py parse $ROOT/$O/prof_b1_$1/r_results.db > $ROOT/$O/b1_timeline_$1.txt 2>&1
-  run $1 $2 $3 timeout 600 rocprofv3 --kernel-trace -d $ROOT/$O/prof_v_$1 -o r -- python $ROOT/bench.py --steps 1 --warmup 0 --verify-steps 2 --roofline-steps 0 --host-io 0 --json-sample 0 --latency 0 --no-cpu-baseline > $ROOT/$O/v_$1.log 2>&1
+  run $1 $2 $3 timeout 600 rocprofv3 --kernel-trace -d $ROOT/$O/prof_v_$1 -o r -- python $ROOT/bench.py --full --steps 1 --warmup 0 --verify-steps 2 --roofline-steps 0 --host-io 0 --json-sample 0 --latency 0 --no-cpu-baseline > $ROOT/$O/v_$1.log 2>&1
   python $ROOT/tools/rocpd_stats.py $ROOT/$O/prof_v_$1/r_results.db | grep -E "Name|k_msm_red|k_pm_final|k_pm_reduce|k_msm_final" > $ROOT/$O/vkern_$1.csv
   rm -rf $ROOT/$O/prof_b1_$1 $ROOT/$O/prof_v_$1
 done

@@ -1,5 +1,5 @@
 # same-box A/B of the PCIe-inclusive one-call rates for library variants under zkp-ecdsa_amd/lib_exp (lib_noside.so: -DV_SIDE_MAXP=0; lib_sideall.so: auxiliary streams for every small chunk)
-F="--steps 1 --warmup 0 --no-cpu-baseline --json-sample 0 --latency 0 --roofline-steps 0 --verify-steps 0 --host-io-stream 0 --host-io-packed 0"
+F="--full --steps 1 --warmup 0 --no-cpu-baseline --json-sample 0 --latency 0 --roofline-steps 0 --verify-steps 0 --host-io-stream 0 --host-io-packed 0"
 for rep in 1 2; do
 for lib in main noside sideall; do
   if [ $lib = main ]; then unset ZKATTEST_LIB; else export ZKATTEST_LIB=zkp-ecdsa_amd/build_ab/lib_$lib.so; fi

@@ -5,7 +5,7 @@ set -e
 export GPU_MAX_HW_QUEUES=8
 mkdir -p gpurun_out
 ROOT=$PWD
-ARGS="--steps 1 --warmup 0 --no-cpu-baseline --verify-steps 1 --verify-warmup 1 --roofline-steps 0 --host-io 0 --json-sample 0 --latency 0 --lanes 1 --verify-lanes 1"
+ARGS="--full --steps 1 --warmup 0 --no-cpu-baseline --verify-steps 1 --verify-warmup 1 --roofline-steps 0 --host-io 0 --json-sample 0 --latency 0 --lanes 1 --verify-lanes 1"
 cd /tmp && export TMPDIR=/tmp
 for c in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY GRBM_GUI_ACTIVE" FETCH_SIZE WRITE_SIZE; do
     n=$(echo $c | cut -d" " -f1)

@@ -13,4 +13,4 @@ elif [ "$mode" = prove8 ]; then
 else
   extra="--batch 4096 --chunk 2048 --lanes 2 --verify-chunk 2048 --comb-bits 16 --host-io 1024 --host-io-chunk 512 --host-io-verify-chunk 512 --cpu-sample 4 --json-sample 2"
 fi
-python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus $n --steps 2 --warmup 1 $extra
+python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus $n --steps 2 --warmup 1 --full $extra
