@@ -48,7 +48,7 @@ export class Engine {
     constructor(devices?: number | number[])
     close(): void
     info(): { devices: number; ringTransport: string; proofMaxSize: number }
-    setOption(name: 'chunk' | 'lanes' | 'combBits' | 'hostTaper' | 'batchVerify' | 'mode' | 'slice' | 'ringFold' | 'verifyGroups' | 'wire' | 'inflight', value: number): void
+    setOption(name: 'chunk' | 'lanes' | 'combBits' | 'hostTaper' | 'batchVerify' | 'mode' | 'slice' | 'ringFold' | 'verifyGroups' | 'wire' | 'verifyLevel' | 'inflight', value: number): void
     /** zero the witness-derived device memory (prover workspaces, staged signatures and seeds) of every device now; close() and a failed prove do it by themselves */
     wipe(): void
     setParams(p: EngineParams): void
@@ -67,3 +67,7 @@ export class Engine {
  *  verifySignatureList / ...Batch accept either layout per proof; writeJson gives the same text for both. */
 export function setWireLayout(name: 'zka1' | 'zka1p'): void
 export function getWireLayout(): 'zka1' | 'zka1p'
+/** The level verifySignatureList / ...Batch verify a proof at: 'context' (default; the params' SecLevel, a proof of another count is 'error deserializing')
+ *  or 'proof' (the proof's own repetition count, as the reference's verifier does).  Applies to every engine, cached ones included. */
+export function setVerifyLevel(name: 'context' | 'proof'): void
+export function getVerifyLevel(): 'context' | 'proof'

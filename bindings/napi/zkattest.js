@@ -300,7 +300,7 @@ class Engine {
     }
     close() { if (this.h) native.destroyPool(this.h); this.h = null }
     info() { return native.poolInfo(this.h) }
-    setOption(name, value) { native.setOption(this.h, name, value) }   // chunk, lanes, combBits (before setParams), hostTaper, batchVerify, mode, slice, ringFold, verifyGroups, wire (0 ZKA1, 1 ZKA1P), inflight
+    setOption(name, value) { native.setOption(this.h, name, value) }   // chunk, lanes, combBits (before setParams), hostTaper, batchVerify, mode, slice, ringFold, verifyGroups, wire (0 ZKA1, 1 ZKA1P), verifyLevel (0 context, 1 per proof), inflight
     wipe() { native.setOption(this.h, 'wipe', 0) }   // zk_ctx_wipe on every device: prover workspaces and staged inputs zeroed (also done by close() and after a failed prove)
     // params: { nistH: 64 B, tomG: 72 B, tomH: 72 B, secLevel } -- SystemParametersList as affine big-endian coordinates
     setParams(p) { native.setParams(this.h, p.nistH, p.tomG, p.tomH, p.secLevel || 80); this.params = p }
@@ -413,6 +413,18 @@ function getWireLayout() { return wireLayout ? 'zka1p' : 'zka1' }
 function useWire(slotEngine, wire) {   // inside a queued unit of the engine (nothing of it is in flight)
     if (slotEngine._wire !== wire) { slotEngine.setOption('wire', wire); slotEngine._wire = wire }
 }
+// The level verifySignatureList verifies a proof at: 'context' (default) = the SecLevel of the params it is called with -- a proof made under
+// another SecLevel is 'error deserializing' --, or 'proof' = the proof's own repetition count, as the reference's verifier does
+// (src/zkpAttestList.ts:147-184, src/exp/exp.ts:233-262; include/zkattest.h zk_ctx_set_verify_level).  Applies to every engine, cached ones included.
+let verifyLevel = 0
+function setVerifyLevel(name) {
+    if (name !== 'context' && name !== 'proof') throw new TypeError("verify level: 'context' or 'proof'")
+    verifyLevel = name === 'proof' ? 1 : 0
+}
+function getVerifyLevel() { return verifyLevel ? 'proof' : 'context' }
+function useVerifyLevel(slotEngine, level) {   // inside a queued unit of the engine (nothing of it is in flight)
+    if ((slotEngine._verifyLevel || 0) !== level) { slotEngine.setOption('verifyLevel', level); slotEngine._verifyLevel = level }
+}
 const isPacked = (b) => Buffer.isBuffer(b) && b.length >= 4 && b.slice(0, 4).toString('latin1') === 'ZK1P'
 
 // ---------------------------------------------------------------- the reference's API
@@ -461,13 +473,14 @@ async function verifySignatureListBatch(params, msgHashes, keys, proofs) {
         const sel = idx[wire]
         if (!sel.length) continue
         const m = sel.length === raw.length ? msg : Buffer.concat(sel.map((i) => msg.slice(32 * i, 32 * i + 32)))
-        const r = await engineFor(params, keys).withRing((engine) => { useWire(engine, wire); return engine._verifyNow(m, sel.map((i) => raw[i])) })
+        const level = verifyLevel
+        const r = await engineFor(params, keys).withRing((engine) => { useWire(engine, wire); useVerifyLevel(engine, level); return engine._verifyNow(m, sel.map((i) => raw[i])) })
         sel.forEach((i, k) => { out[i] = r[k]; errors[i] = r.errors[k] })
     }
     Object.defineProperty(out, 'errors', { value: errors })
     return out
 }
 
-module.exports = { generateParamsList, generateParamsListHardened, keyToInt, proveSignatureList, verifySignatureList, proveSignatureListBatch, verifySignatureListBatch,
+module.exports = { setVerifyLevel, getVerifyLevel, generateParamsList, generateParamsListHardened, keyToInt, proveSignatureList, verifySignatureList, proveSignatureListBatch, verifySignatureListBatch,
     writeJson, readJson, writeJsonBatch, readJsonBatch, SignatureProofList, SystemParametersList, PedersenParams, generatePedersenParams, p256, tomEdwards256, ALL_GROUPS,
     Group, Point, Scalar, Engine, shutdown, setWireLayout, getWireLayout, native }

@@ -224,14 +224,37 @@ zk_status zk_prove_batch_device(zk_ctx *ctx, uint64_t B, const void *d_msg_hash,
  * curve, also inside a GKProof of the wrong length --; ok = 0 with status 0 where the reference returns false (membership, a GKProof
  * whose length is not the ring's, gk.ts:208-218, a failed relation); otherwise the exception verifyExp throws FIRST when it walks
  * the 20 sampled repetitions in order (exp.ts:265-346): ZK_E_PARAMS_NOT_FOUND, ZK_E_T_INF or ZK_E_T1_INF.  ZK_E_R_INF cannot occur (R
- * travels in affine form).  One restriction: a batch is homogeneous in secLevel -- a proof whose header announces another repetition
- * count than the context's gets ZK_E_BAD_ENCODING, where the reference would verify it with its own count (exp.ts:243-260); a context
- * with secLevel < 20 refuses the call with ZK_E_SECLEVEL. */
+ * travels in affine form).  One restriction in the default mode (ZK_VERIFY_LEVEL_CONTEXT): a batch is homogeneous in secLevel -- a proof
+ * whose header announces another repetition count than the context's gets ZK_E_BAD_ENCODING, where the reference would verify it with
+ * its own count (exp.ts:243-260); a context with secLevel < 20 refuses the call with ZK_E_SECLEVEL.  zk_ctx_set_verify_level below lifts
+ * it: in ZK_VERIFY_LEVEL_PER_PROOF every proof is verified at its own header's count, as the reference does. */
 zk_status zk_verify_batch(zk_ctx *ctx, uint64_t B, const uint8_t *msg_hash /*Bx32*/, const uint8_t *proofs,
                           const uint64_t *proof_off /*B+1*/, const uint8_t *verifier_seeds /*Bx32 or NULL*/,
                           uint8_t *ok /*B*/, int32_t *per_proof_status /*B*/);
 zk_status zk_verify_batch_device(zk_ctx *ctx, uint64_t B, const void *d_msg_hash, const void *d_proofs,
                                  const void *d_proof_off, const void *d_verifier_seeds, void *d_ok, void *d_per_proof_status);
+
+/* Verify levels.  ZK_VERIFY_LEVEL_CONTEXT (default): every proof is verified at the context's secLevel (zk_verify_batch above).
+ * ZK_VERIFY_LEVEL_PER_PROOF: the reference's verifySignatureList never reads the caller's SecLevel -- verifyExp(..., 20, Q) hashes every
+ * repetition the proof holds and samples generateIndices(20, count) (src/zkpAttestList.ts:147-184, src/exp/exp.ts:233-262) -- and neither
+ * does the engine in this mode: a proof's level is its header's secLevel field, 0..128 (above 128: ZK_E_BAD_ENCODING, the header holds 128
+ * challenge bits), and everything checked in the default mode is checked against that count.  Per proof, in the reference's order:
+ * ZK_E_BAD_ENCODING for a structural error; ok 0 / status 0 where membership fails; ZK_E_SECLEVEL for fewer than 20 repetitions (only the
+ * membership proof of such a proof is verified); otherwise verifyExp's verdict and exceptions at the proof's count.  The verifier-seed
+ * contract is unchanged, per proof (2n+1 fills for membership, then count - 2 for generateIndices(20, count)).  Every verify entry point
+ * (host, page-locked, HBM and device-pointer proofs, submit / wait, the pool calls) and both wire layouts and protocol modes follow it.
+ * How: a census of the batch's levels -- the headers read on the host for host-pointer calls; for zk_verify_batch_device one kernel and
+ * ONE read-back of 130 counters per call.  A batch whose well-formed proofs share one level runs the usual pipeline planned at that level
+ * (workspaces grow to it and are never shrunk; the next prove call plans at the context's level again).  A batch of several levels is
+ * split: the proofs of each level are gathered on the device into a window of at most 2 x chunk x lanes proofs (zk_ctx_set_chunk,
+ * zk_ctx_set_lanes), verified there, and their verdicts scattered back to their indices; host-pointer mixed batches first copy their
+ * bytes to HBM in one transfer.  A streamed job (zk_verify_submit) whose proofs are all at the level of the jobs already queued is
+ * queued as usual; any other job (several levels, a level below 20, another level) waits for the queue ahead of it to drain and runs at
+ * its zk_verify_wait like the synchronous call -- the results are the same.  The setter follows the rules of the other zk_ctx_set_*
+ * (takes effect with the next call; ZK_E_ARG while streamed jobs are queued, or for an unknown mode).  zk_pool_set_verify_level sets the
+ * mode of every shard context. */
+enum { ZK_VERIFY_LEVEL_CONTEXT = 0, ZK_VERIFY_LEVEL_PER_PROOF = 1 };
+zk_status zk_ctx_set_verify_level(zk_ctx *ctx, uint32_t mode);
 
 /* ---- two (or more) batches in flight on one context.  zk_prove_batch / zk_verify_batch are synchronous: each call pays its own head
  * (no byte of a chunk exists before its stage 1 is over) and its own tail (the copies of the last slices, with nothing left to
@@ -291,6 +314,7 @@ const char *zk_pool_rccl_library(const zk_pool *pool);
 void zk_pool_shard(const zk_pool *pool, uint64_t B, int i, uint64_t *first, uint64_t *count);
 zk_status zk_pool_set_params(zk_pool *pool, const uint8_t nist_h[64], const uint8_t tom_g[72], const uint8_t tom_h[72], uint32_t sec_level);
 zk_status zk_pool_set_ring(zk_pool *pool, const uint8_t *keys_be32, uint64_t n_keys);
+zk_status zk_pool_set_verify_level(zk_pool *pool, uint32_t mode);   /* zk_ctx_set_verify_level on every shard context */
 /* zk_prove_batch over all devices.  Shard i writes its proofs back to back from out + i * ((out_cap / G) & ~255): proof b lies
  * at out_off[b] .. out_off[b] + out_len[b] (its ZKA1 header carries the same length); there are gaps between shards, none
  * inside one.  ZK_E_BUFFER when a shard does not fit its region.  `out` from zk_host_alloc is filled by overlapped DMA. */

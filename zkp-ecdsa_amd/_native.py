@@ -21,6 +21,7 @@ SYMBOLS = [
     'zk_prove_submit', 'zk_prove_submit_device', 'zk_prove_wait', 'zk_verify_submit', 'zk_verify_wait', 'zk_test_counter', 'zk_ctx_set_key_tables',
     'zk_proofs_to_json_batch', 'zk_proofs_from_json_batch', 'zk_ctx_set_ring_fold',
     'zk_pool_prove_submit', 'zk_pool_prove_wait', 'zk_pool_verify_submit', 'zk_pool_verify_wait', 'zk_ctx_set_verify_groups',
+    'zk_ctx_set_verify_level', 'zk_pool_set_verify_level',
     'zk_test_field_op', 'zk_test_tom_commit', 'zk_test_p256_fixed_mul', 'zk_test_sha256', 'zk_test_rng_draws',
 ]
 
@@ -87,6 +88,8 @@ def lib():
         L.zk_ctx_set_host_taper.argtypes = [vp, u32]
         L.zk_ctx_set_slice.argtypes = [vp, u32]
         L.zk_ctx_set_mode.argtypes = [vp, u32]
+        L.zk_ctx_set_verify_level.argtypes = [vp, u32]
+        L.zk_pool_set_verify_level.argtypes = [vp, u32]
         L.zk_ring_digest.argtypes = [vp, vp]
         L.zk_hardened_h.argtypes = [C.c_char_p, u64, vp, vp]
         L.zk_pool_create.argtypes = [C.POINTER(C.c_int), i32, C.POINTER(vp)]
@@ -349,6 +352,11 @@ class Engine:
     def set_mode(self, mode):
         """MODE_REFERENCE (default, byte parity with the reference) or MODE_HARDENED (statement hashed into the GK challenge)."""
         self._chk(self.L.zk_ctx_set_mode(self.h, int(mode)))
+
+    def set_verify_level(self, per_proof):
+        """zk_ctx_set_verify_level: False / 0 = every proof at the context's secLevel (default), True / 1 = every proof at its own header's
+        secLevel, as the reference's verifySignatureList does."""
+        self._chk(self.L.zk_ctx_set_verify_level(self.h, 1 if per_proof else 0))
 
     def ring_digest(self):
         d = C.create_string_buffer(32)
@@ -641,6 +649,10 @@ class Pool:
 
     def set_params(self, nist_h64, tom_g72, tom_h72, sec_level=80):
         self._chk(self.L.zk_pool_set_params(self.h, bytes(nist_h64), bytes(tom_g72), bytes(tom_h72), sec_level))
+
+    def set_verify_level(self, per_proof):
+        """zk_pool_set_verify_level: Engine.set_verify_level on every shard context."""
+        self._chk(self.L.zk_pool_set_verify_level(self.h, 1 if per_proof else 0))
 
     def set_ring(self, keys_be32, nkeys=None):
         keys_be32 = bytes(keys_be32)

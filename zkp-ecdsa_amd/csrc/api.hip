@@ -174,7 +174,8 @@ extern "C" void zk_ctx_destroy(zk_ctx* c) {
     hipFree(c->P.tom_tab_g), hipFree(c->P.tom_tab_h), hipFree(c->tom_tab_gen), hipFree(c->P.pfix_G), hipFree(c->P.pfix_H);
     hipFree(c->gk_kdig), hipFree(c->gk_edig), hipFree(c->ktab), hipFree(c->ktab_ok);
     hipFree(c->tab_scratch), hipFree(c->gk_etab), hipFree(c->d_flag), hipFree(c->ring_mem), hipFree(c->ring_digest);
-    hipFree(c->io_buf), hipFree(c->in_buf), hipFree(c->unp_buf), hipFree(c->unp_off), hipFree(c->seed_buf);
+    hipFree(c->io_buf), hipFree(c->in_buf), hipFree(c->unp_buf), hipFree(c->unp_off), hipFree(c->seed_buf), hipFree(c->lv_buf), hipFree(c->lw_buf), hipFree(c->lb_buf);
+    if (c->h_lv) hipHostFree(c->h_lv);
     if (c->h_stage) hipHostFree(c->h_stage);
     if (c->in_ready) hipEventDestroy(c->in_ready);
     for (int l = 0; l < ZK_MAX_LANES; l++) {
@@ -396,6 +397,12 @@ extern "C" zk_status zk_ctx_set_mode(zk_ctx* c, uint32_t mode) {
     c->mode = mode;
     return ZK_OK;
 }
+extern "C" zk_status zk_ctx_set_verify_level(zk_ctx* c, uint32_t mode) {
+    if (!c || (mode != ZK_VERIFY_LEVEL_CONTEXT && mode != ZK_VERIFY_LEVEL_PER_PROOF)) return ZK_E_ARG;
+    if (c->stream_busy) return busy_refusal(c);
+    c->verify_level = mode;
+    return ZK_OK;
+}
 extern "C" zk_status zk_ring_digest(zk_ctx* c, uint8_t digest[32]) {
     if (!c || !digest) return ZK_E_ARG;
     if (!c->N || !c->ring_digest) return ZK_E_BUFFER;
@@ -517,7 +524,7 @@ hipError_t malloc_or_shed(zk_ctx* c, void** p, size_t bytes) {
     return hipMalloc(p, bytes);
 }
 zk_status ensure_workspace(zk_ctx* c, uint32_t C, uint32_t nlanes) {
-    uint32_t sec = c->P.sec, n = c->n;
+    uint32_t sec = plan_sec(c), n = c->n;
     if (!(c->ws_C == C && c->ws_sec == sec && c->ws_n == n)) {
         for (auto& L : c->pl) L.ready = false;
         c->ws_C = C, c->ws_sec = sec, c->ws_n = n;

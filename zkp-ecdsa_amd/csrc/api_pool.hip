@@ -346,6 +346,16 @@ extern "C" zk_status zk_pool_set_params(zk_pool* p, const uint8_t nist_h[64], co
     if (!p) return ZK_E_ARG;
     return pool_each(p, [&](int i) { return zk_ctx_set_params(p->ctx[i], nist_h, tom_g, tom_h, sec); });
 }
+// per-proof verify levels on every shard context (zk_ctx_set_verify_level: ZK_E_ARG while a shard has streamed jobs queued)
+extern "C" zk_status zk_pool_set_verify_level(zk_pool* p, uint32_t mode) {
+    if (!p) return ZK_E_ARG;
+    if (mode != ZK_VERIFY_LEVEL_CONTEXT && mode != ZK_VERIFY_LEVEL_PER_PROOF) return ZK_E_ARG;
+    for (size_t i = 0; i < p->ctx.size(); i++)
+        if (p->ctx[i]->stream_busy) return ZK_E_ARG;
+    for (size_t i = 0; i < p->ctx.size(); i++)
+        if (zk_status zs = zk_ctx_set_verify_level(p->ctx[i], mode)) return zs;
+    return ZK_OK;
+}
 
 extern "C" zk_status zk_pool_set_ring(zk_pool* p, const uint8_t* keys, uint64_t nkeys) {
     if (!p || !keys || nkeys < 2) return ZK_E_ARG;

@@ -35,6 +35,16 @@ struct zk_job {
     size_t res_a_off = 0, res_a_bytes = 0, res_b_off = 0, res_b_bytes = 0;
     void *user_a = nullptr, *user_b = nullptr;
     uint32_t nl = 1;                      // lanes the job was planned over (c->lanes at submit time; frozen while jobs are queued)
+    // per-proof verify levels: a verify job that cannot join the queued plan (several levels, a level below 20, another level than the queued jobs') is
+    // DEFERRED -- nothing of it is enqueued at submit; its wait runs it like the synchronous call once the jobs ahead of it are done
+    bool deferred = false;
+    struct {
+        uint64_t B;
+        const uint8_t *msg, *proofs, *vseeds;
+        const uint64_t* off;
+        uint8_t* ok;
+        int32_t* status;
+    } dargs{};
     bool all_enqueued = false, finisher_enqueued = false;
     zk_status result = ZK_OK;
     std::string err;
@@ -121,6 +131,7 @@ void stream_abandon_jobs(zk_ctx* c) {   // zk_ctx_destroy with jobs still queued
         job_free(j);
     }
     c->stream_busy = false;
+    c->v_sec_on = false;
 }
 static void unlink_job(zk_ctx* c, zk_job* j) {
     for (size_t i = 0; i < c->jobs.size(); i++)
@@ -129,6 +140,7 @@ static void unlink_job(zk_ctx* c, zk_job* j) {
             break;
         }
     c->stream_busy = !c->jobs.empty();
+    if (c->jobs.empty()) c->v_sec_on = false;   // (per-proof verify levels: the queue's plan level ends with the queue)
 }
 
 static zk_status stream_common(zk_ctx* c, int kind) {
@@ -141,7 +153,7 @@ static zk_status stream_common(zk_ctx* c, int kind) {
         c->err = "prove and verify jobs cannot be in flight together on one context";
         return ZK_E_ARG;
     }
-    if (!c->jobs.empty() && (!(c->ws_C == c->chunk && c->ws_sec == c->P.sec && c->ws_n == c->n) || (c->jobs[0]->kind ? c->jobs[0]->vj.NL : c->jobs[0]->pj.NL) != c->lanes ||
+    if (!c->jobs.empty() && (!(c->ws_C == c->chunk && c->ws_sec == plan_sec(c) && c->ws_n == c->n) || (c->jobs[0]->kind ? c->jobs[0]->vj.NL : c->jobs[0]->pj.NL) != c->lanes ||
                               (kind == 1 && c->vs_groups != c->verify_groups))) {
         c->err = "chunk / lanes / parameters / ring changed while streamed jobs are in flight";
         return ZK_E_ARG;
@@ -247,6 +259,16 @@ static zk_status wait_common(zk_ctx* c, zk_job* j) {
         return ZK_E_ARG;
     }
     HIPCHK(c, hipSetDevice(c->device));
+    if (j->deferred) {   // every job ahead of it is done, every job behind it is deferred too: nothing else runs on the context
+        const bool busy = c->stream_busy;
+        c->stream_busy = false;
+        const auto& a = j->dargs;
+        zk_status zs = a.ok ? verify_host(c, a.B, a.msg, a.proofs, a.off, a.vseeds, a.ok, a.status) : ZK_OK;
+        c->stream_busy = busy;
+        unlink_job(c, j);
+        job_free(j);
+        return zs;
+    }
     drive(c, j, j->nl - 1);
     hipError_t e = j->finisher_enqueued ? hipEventSynchronize(j->done) : hipSuccess;
     if (j->result != ZK_OK || e != hipSuccess) sync_every_stream(c);   // leave nothing of this job running: its buffers go back to the pool
@@ -274,6 +296,11 @@ static zk_status wait_common(zk_ctx* c, zk_job* j) {
 // zombie whose result pointers dangle.
 zk_status stream_cancel_job(zk_ctx* c, zk_job* j) {
     if (!c || !j || j->c != c || c->jobs.empty()) return ZK_E_ARG;
+    if (j->deferred && (c->jobs[0] == j || c->jobs.back() == j)) {   // nothing of it was enqueued
+        unlink_job(c, j);
+        job_free(j);
+        return ZK_OK;
+    }
     if (c->jobs[0] == j) {
         j->res_a_bytes = j->res_b_bytes = 0;   // nobody wants the results
         (void)wait_common(c, j);
@@ -401,12 +428,15 @@ extern "C" zk_status zk_prove_submit_device(zk_ctx* c, uint64_t B, const uint8_t
 }
 extern "C" zk_status zk_prove_wait(zk_ctx* c, zk_job* job) { return wait_common(c, job); }
 
+static zk_status verify_submit(zk_ctx* c, uint64_t B, const uint8_t* msg, const uint8_t* proofs, const uint64_t* off, const uint8_t* vseeds, uint8_t* ok, int32_t* status,
+                               zk_job** job);
 extern "C" zk_status zk_verify_submit(zk_ctx* c, uint64_t B, const uint8_t* msg, const uint8_t* proofs, const uint64_t* off, const uint8_t* vseeds, uint8_t* ok,
                                       int32_t* status, zk_job** job) {
     if (!c || !job || !B || !msg || !proofs || !off || !ok || !status) return ZK_E_ARG;
     *job = nullptr;
     HIPCHK(c, hipSetDevice(c->device));
-    if (c->params_set && c->P.sec < VK) return ZK_E_SECLEVEL;
+    const bool per_proof = c->verify_level == ZK_VERIFY_LEVEL_PER_PROOF;
+    if (!per_proof && c->params_set && c->P.sec < VK) return ZK_E_SECLEVEL;
     if (off[0] != 0) return ZK_E_ARG;
     for (uint64_t b = 0; b < B; b++)
         if (off[b + 1] < off[b]) return ZK_E_ARG;
@@ -414,6 +444,38 @@ extern "C" zk_status zk_verify_submit(zk_ctx* c, uint64_t B, const uint8_t* msg,
         c->err = "streamed calls need page-locked `proofs` (zk_host_alloc)";
         return ZK_E_ARG;
     }
+    if (!per_proof) return verify_submit(c, B, msg, proofs, off, vseeds, ok, status, job);
+    // per-proof verify levels: the headers, read here, decide whether the job joins the queued plan
+    if (!c->params_set || !c->N) return ZK_E_BUFFER;
+    const uint32_t lvl = host_level_census(c, B, proofs, off), L = lvl == LV_NONE ? c->P.sec : lvl;
+    bool defer = lvl == LV_MIXED || L < VK || (!c->jobs.empty() && (!c->v_sec_on || c->v_sec != L));
+    for (zk_job* q : c->jobs) defer = defer || q->deferred;
+    if (defer) {
+        if (c->jobs.size() >= ZK_MAX_JOBS) {
+            c->err = "too many streamed jobs in flight (wait for the oldest one first)";
+            return ZK_E_ARG;
+        }
+        if (!c->jobs.empty() && c->jobs[0]->kind != 1) {
+            c->err = "prove and verify jobs cannot be in flight together on one context";
+            return ZK_E_ARG;
+        }
+        zk_job* j = new zk_job();
+        j->kind = 1, j->c = c, j->deferred = true, j->nl = c->lanes;
+        j->all_enqueued = j->finisher_enqueued = true;
+        j->dargs.B = B, j->dargs.msg = msg, j->dargs.proofs = proofs, j->dargs.vseeds = vseeds, j->dargs.off = off, j->dargs.ok = ok, j->dargs.status = status;
+        c->jobs.push_back(j);
+        c->stream_busy = true;
+        *job = j;
+        return ZK_OK;
+    }
+    const bool first = c->jobs.empty();
+    if (first) c->v_sec = L, c->v_sec_on = true;   // the queue's plan level, until the queue is empty again (unlink_job)
+    zk_status zs = verify_submit(c, B, msg, proofs, off, vseeds, ok, status, job);
+    if (zs && c->jobs.empty()) c->v_sec_on = false;
+    return zs;
+}
+static zk_status verify_submit(zk_ctx* c, uint64_t B, const uint8_t* msg, const uint8_t* proofs, const uint64_t* off, const uint8_t* vseeds, uint8_t* ok, int32_t* status,
+                               zk_job** job) {
     zk_status zs = stream_common(c, 1);
     if (zs) return zs;
     const uint64_t total = off[B];

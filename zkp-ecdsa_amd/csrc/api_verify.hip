@@ -1,6 +1,7 @@
 // zk_verify_batch / zk_verify_batch_device: host-side phase pipeline of the verifier (kernels in k_verify.hip).
 #include "ctx.h"
 #include "jobs.h"
+#include <optional>
 
 static size_t vcarve(VWork& V, Soa& res, Soa& res2, MsmBuf& M, PMsmBuf& PM, uint8_t* base, uint32_t C, uint32_t sec, uint32_t n, uint64_t N, bool want_msm, bool want_pm,
                      uint32_t want_groups) {
@@ -86,7 +87,7 @@ static size_t vcarve(VWork& V, Soa& res, Soa& res2, MsmBuf& M, PMsmBuf& PM, uint
     return k.off + 256;
 }
 zk_status ensure_vworkspace(zk_ctx* c, uint32_t C, uint32_t nlanes) {
-    uint32_t sec = c->P.sec, n = c->n;
+    uint32_t sec = plan_sec(c), n = c->n;
     const bool want_msm = c->verify_batch_min && C >= c->verify_batch_min;   // the chunk-wide sums never run on smaller chunks
     const bool want_pm = want_msm && c->p256_batch_min && C >= c->p256_batch_min;
     if (!(c->vs_C == C && c->vs_sec == sec && c->vs_n == n && c->vs_msm == want_msm && c->vs_pm == want_pm && c->vs_groups == c->verify_groups)) {
@@ -206,6 +207,14 @@ zk_status VerifyJob::stage1(uint64_t chunk_no) {
         MaybeScope t(timed, c, "v_parse_validate", s);
         if (d_packed) launch_v_unpack(s, V.sec, cnt, d_packed, d_poff, first, ubase[chunk_no], (uint8_t*)d_proofs, d_uoff + first + chunk_no);
         launch_v_header_validate(s, V, cnt, d_proofs, d_off, first);
+    }
+    if (memb_only) {   // a level below VK: the membership proof's challenge, total and terms (stage 2b sums them per proof)
+        MaybeScope t(timed, c, "v_gk_total", s);
+        launch_v_challenges(s, V, cnt, d_proofs, d_off, d_msg, first, 2);
+        launch_v_gk_total(s, V, W.ring, W.gk_etab, W.gk_kdig, cnt, W.N, d_proofs, d_off, first, vres, vres2);
+        launch_v_proof_points(s, V, cnt, d_proofs, d_off, first, 1);
+        launch_v_proof_terms(s, W, V, cnt, d_proofs, d_off, d_vseeds, first);
+        return ZK_OK;
     }
     // A small chunk (per_proof_range below) is a chain of latencies: the two challenge hashes (one lane per proof, 16 KB each) and the membership
     // total need nothing from the P-256 front end (R's window table: 256 doublings in a row) and run beside it on an auxiliary stream.
@@ -448,6 +457,11 @@ static zk_status small_chunk_p256(zk_ctx* c, bool timed, uint32_t lane, uint32_t
     return ZK_OK;
 }
 zk_status VerifyJob::stage2a(uint64_t chunk_no) {
+    if (memb_only) {   // no batched pass
+        auto& A0 = c->vl[lane_of(chunk_no)];
+        A0.msm_pending = A0.pm_pending = A0.stage2_forked = A0.released_by_host = false;
+        return ZK_OK;
+    }
     const DevParams& P = c->P;
     const uint64_t first = plan[chunk_no].first;
     const uint32_t cnt = plan[chunk_no].cnt;
@@ -523,6 +537,15 @@ zk_status VerifyJob::stage2b(uint64_t chunk_no) {
     VWork& V = c->vl[lane].V;
     const MsmBuf& M = c->vl[lane].M;
     hipStream_t s = c->pl[lane].stream;
+    if (memb_only) {   // membership sums of every proof, one per proof, and the verdict
+        MaybeScope t(timed, c, "v_straus_tom", s);
+        const uint32_t nq = (c->n + 1) / 2;
+        launch_v_straus(s, V.gk_terms, cnt * nq, V.C * nq, 4, 4, V.gk_acc, nullptr, nullptr);
+        launch_v_straus(s, V.misc_terms, cnt, 3 * V.C, 1, 0, V.misc_acc, nullptr, nullptr);
+        launch_tom_commit(s, P, W.lc, cnt, 1, 4 * W.n);
+        launch_v_final_memb(s, W, V, cnt, d_ok, d_status, first);
+        return ZK_OK;
+    }
     const uint32_t G = c->vs_groups;
     auto& A = c->vl[lane];
     const bool wide_chunk = side_streams(cnt), pm = A.pm_pending;
@@ -629,7 +652,7 @@ zk_status make_default_vseeds(zk_ctx* c, uint64_t B, uint8_t* d_seeds /* 32 * B 
 static zk_status verify_device(zk_ctx* c, uint64_t B, const uint8_t* d_msg, const uint8_t* d_proofs, const uint64_t* d_off, const uint8_t* d_vseeds, uint8_t* d_ok,
                                int32_t* d_status, const uint8_t* host_src = nullptr, const uint64_t* host_off = nullptr, bool inputs_on_stream = false) {
     if (!c->params_set || !c->N) return ZK_E_BUFFER;
-    if (c->P.sec < VK) return ZK_E_SECLEVEL;
+    if (plan_sec(c) < VK && !c->v_sec_on) return ZK_E_SECLEVEL;   // (a per-proof-mode call at a level below VK verifies membership only)
     if (B == 0) return ZK_OK;
     if (c->stream_busy) {
         c->err = "streamed jobs are in flight on this context (zk_prove_wait / zk_verify_wait them first)";
@@ -643,7 +666,8 @@ static zk_status verify_device(zk_ctx* c, uint64_t B, const uint8_t* d_msg, cons
     J.NL = (uint32_t)std::min<size_t>(c->lanes, J.plan.size());   // chunks rotate over NL streams / workspaces
     {
         static const bool no_release = getenv("ZKATTEST_NO_HOST_RELEASE") != nullptr;   // A/B switch (tools/ab_release.sh)
-        J.host_release = J.plan.size() == 1 && B <= V_WIDE_MAXP && !no_release && !zk_one_lane_chains();
+        J.memb_only = plan_sec(c) < VK;
+        J.host_release = J.plan.size() == 1 && B <= V_WIDE_MAXP && !no_release && !zk_one_lane_chains() && !J.memb_only;
     }
     if (c->wire == ZK_WIRE_ZKA1P) {   // the proofs handed in are packed: every chunk is expanded into the context's staging first
         uint64_t total = 0;
@@ -727,10 +751,172 @@ static zk_status verify_device(zk_ctx* c, uint64_t B, const uint8_t* d_msg, cons
     return ZK_OK;
 }
 
+// ------------------------------------------------------------------ per-proof verify levels (include/zkattest.h: zk_ctx_set_verify_level)
+struct VLevel {   // the level the workspaces are planned for during one call (plan_sec); the context's own level again when it ends
+    zk_ctx* c;
+    VLevel(zk_ctx* c_, uint32_t sec) : c(c_) { c->v_sec = sec, c->v_sec_on = true; }
+    ~VLevel() { c->v_sec_on = false; }
+};
+uint32_t host_level_census(const zk_ctx* c, uint64_t B, const uint8_t* proofs, const uint64_t* off) {
+    const Wire w = wire_make(c->wire == ZK_WIRE_ZKA1P);
+    uint32_t lvl = LV_NONE;
+    for (uint64_t b = 0; b < B; b++) {
+        const uint32_t l = wire_level_class(proofs + off[b], off[b], off[b + 1], w);
+        if (l == ZK_LV_BAD) continue;   // ZK_E_BAD_ENCODING at whatever level the batch runs
+        if (lvl == LV_NONE) lvl = l;
+        else if (l != lvl) return LV_MIXED;
+    }
+    return lvl;
+}
+static zk_status grow(zk_ctx* c, void** buf, size_t* have, size_t need) {   // grow-only device buffer
+    if (need <= *have) return ZK_OK;
+    if (*buf) HIPCHK(c, hipFree(*buf));
+    *buf = nullptr, *have = 0;
+    HIPCHK(c, hipMalloc(buf, need));
+    *have = need;
+    return ZK_OK;
+}
+// A batch of device-resident proofs in per-proof mode.  The census (k_lv_census) classifies every proof and counts the classes; the host reads the
+// 130 counters back (the one read-back the mode adds to a call).  One level: the usual pipeline on the caller's buffers, planned at that level.
+// Several: a stable permutation by level, then per level windows of at most 2 x chunk x lanes proofs gathered into HBM (k_lv_gather_*), verified
+// like a batch of their own, their verdicts scattered back (k_lv_scatter); a proof whose header is malformed gets ZK_E_BAD_ENCODING directly.
+static zk_status verify_per_proof(zk_ctx* c, uint64_t B, const uint8_t* d_msg, const uint8_t* d_proofs, const uint64_t* d_off, const uint8_t* d_vseeds, uint8_t* d_ok,
+                                  int32_t* d_st, bool inputs_on_stream) {
+    if (!c->params_set || !c->N) return ZK_E_BUFFER;
+    if (B == 0) return ZK_OK;
+    if (c->stream_busy) {
+        c->err = "streamed jobs are in flight on this context (zk_prove_wait / zk_verify_wait them first)";
+        return ZK_E_ARG;
+    }
+    if (B > 0xffffffffull) return ZK_E_ARG;
+    const uint64_t nblk = (B + 1023) / 1024;
+    Carver k0(nullptr);
+    auto carve = [&](Carver& k, uint8_t*& cls, uint32_t*& blk, uint32_t*& out, uint32_t*& perm) {
+        cls = (uint8_t*)k.take(B), blk = (uint32_t*)k.take(4 * nblk * ZK_LV_CLASSES), out = (uint32_t*)k.take(8 * ZK_LV_CLASSES), perm = (uint32_t*)k.take(4 * B);
+    };
+    uint8_t* cls;
+    uint32_t *blk, *out, *perm;
+    carve(k0, cls, blk, out, perm);
+    if (zk_status zs = grow(c, &c->lv_buf, &c->lv_bytes, k0.off + 256)) return zs;
+    Carver k1((uint8_t*)c->lv_buf);
+    carve(k1, cls, blk, out, perm);
+    if (!c->h_lv) HIPCHK(c, hipHostMalloc((void**)&c->h_lv, 4096, hipHostMallocDefault));
+    hipStream_t s = c->stream;
+    const bool timed = zk_timed(c, B);
+    hipEvent_t ev[4] = {};
+    float lv_ms = 0;
+    auto lap = [&](int i, int j) {   // partition kernels between ev[i] and ev[j] (the stream has been synchronised behind ev[j])
+        float ms = 0;
+        if (timed && hipEventElapsedTime(&ms, ev[i], ev[j]) == hipSuccess) lv_ms += ms;
+    };
+    struct Events {
+        hipEvent_t* e;
+        ~Events() {
+            for (int i = 0; i < 4; i++)
+                if (e[i]) hipEventDestroy(e[i]);
+        }
+    } ev_guard{ev};
+    if (timed)
+        for (auto& e : ev) HIPCHK(c, hipEventCreate(&e));
+    if (timed) HIPCHK(c, hipEventRecord(ev[0], s));
+    launch_lv_census(s, B, d_proofs, d_off, c->wire == ZK_WIRE_ZKA1P, cls, blk, out);
+    if (timed) HIPCHK(c, hipEventRecord(ev[1], s));
+    HIPCHK(c, hipMemcpyAsync(c->h_lv, out, 8 * ZK_LV_CLASSES, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    lap(0, 1);
+    const uint32_t* cnt = c->h_lv;
+    uint32_t levels = 0, single = c->P.sec, most = 0;
+    uint32_t start[ZK_LV_CLASSES];
+    for (uint32_t l = 0; l < ZK_LV_CLASSES; l++) start[l] = c->h_lv[ZK_LV_CLASSES + l];
+    for (uint32_t l = 0; l <= ZK_MAXSEC; l++)
+        if (cnt[l]) levels++, single = l, most = std::max(most, cnt[l]);
+    if (levels <= 1) {   // the common case: the caller's buffers as they are (malformed headers get ZK_E_BAD_ENCODING from k_v_header at any level)
+        VLevel g(c, single);
+        return verify_device(c, B, d_msg, d_proofs, d_off, d_vseeds, d_ok, d_st, nullptr, nullptr, inputs_on_stream);
+    }
+    if (!d_vseeds) {   // the verifier's own seeds for the whole batch, gathered with the proofs (the window calls must not draw their own)
+        if (zk_status zs = grow(c, &c->seed_buf, &c->seed_bytes, 32 * B + 32 * B / 4 + 4096)) return zs;
+        if (zk_status zs = make_default_vseeds(c, B, (uint8_t*)c->seed_buf, s)) return zs;
+        d_vseeds = (const uint8_t*)c->seed_buf;
+    }
+    if (timed) HIPCHK(c, hipEventRecord(ev[0], s));
+    launch_lv_perm(s, B, cls, blk, out, perm);
+    launch_lv_scatter(s, cnt[ZK_LV_BAD], perm + start[ZK_LV_BAD], nullptr, nullptr, d_ok, d_st, ZK_E_BAD_ENCODING);
+    if (timed) HIPCHK(c, hipEventRecord(ev[1], s));
+    const uint32_t Wp = (uint32_t)std::min<uint64_t>(most, 2ull * c->chunk * c->lanes);
+    Carver w0(nullptr);
+    auto wcarve = [&](Carver& k, uint64_t*& w_off, uint8_t*& w_msg, uint8_t*& w_seeds, uint8_t*& w_ok, int32_t*& w_st) {
+        w_off = (uint64_t*)k.take(8 * ((size_t)Wp + 1)), w_msg = (uint8_t*)k.take(32 * (size_t)Wp), w_seeds = (uint8_t*)k.take(32 * (size_t)Wp);
+        w_ok = (uint8_t*)k.take(Wp), w_st = (int32_t*)k.take(4 * (size_t)Wp);
+    };
+    uint64_t* w_off;
+    uint8_t *w_msg, *w_seeds, *w_ok;
+    int32_t* w_st;
+    wcarve(w0, w_off, w_msg, w_seeds, w_ok, w_st);
+    if (zk_status zs = grow(c, &c->lw_buf, &c->lw_bytes, w0.off + 256)) return zs;
+    Carver w1((uint8_t*)c->lw_buf);
+    wcarve(w1, w_off, w_msg, w_seeds, w_ok, w_st);
+    // the windows' own calls record their families into the call's timing (the mode is the call's, whatever the window's size)
+    const int timing_mode = c->timing_mode;
+    c->timing_mode = timed ? ZK_TIMING_ON : ZK_TIMING_OFF;
+    std::vector<std::pair<const char*, float>> fam;
+    zk_status zs = ZK_OK;
+    for (uint32_t l = 0; l <= ZK_MAXSEC && !zs; l++) {
+        for (uint32_t w = 0; w < cnt[l] && !zs; w += Wp) {
+            const uint32_t n = std::min<uint32_t>(Wp, cnt[l] - w);
+            const uint32_t* sel = perm + start[l] + w;
+            if (timed) HIPCHK(c, hipEventRecord(ev[2], s));
+            launch_lv_gather_meta(s, n, sel, d_off, d_msg, d_vseeds, w_off, w_msg, w_seeds);
+            uint64_t* h_total = (uint64_t*)(c->h_lv + 2 * ZK_LV_CLASSES);
+            HIPCHK(c, hipMemcpyAsync(h_total, w_off + n, 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(c, hipStreamSynchronize(s));   // the window's bytes: every length is bounded by its level (wire_level_class)
+            if ((zs = grow(c, &c->lb_buf, &c->lb_bytes, *h_total + 64))) break;
+            launch_lv_gather_bytes(s, n, sel, d_off, d_proofs, w_off, (uint8_t*)c->lb_buf);
+            if (timed) HIPCHK(c, hipEventRecord(ev[3], s));
+            {
+                VLevel g(c, l);
+                zs = verify_device(c, n, w_msg, (const uint8_t*)c->lb_buf, w_off, w_seeds, w_ok, w_st, nullptr, nullptr, true);
+            }
+            if (zs) break;
+            lap(2, 3);
+            for (auto& f : c->last_timing) {
+                bool found = false;
+                for (auto& g : fam)
+                    if (g.first == f.first) g.second += f.second, found = true;
+                if (!found) fam.push_back(f);
+            }
+            if (timed) HIPCHK(c, hipEventRecord(ev[2], s));
+            launch_lv_scatter(s, n, sel, w_ok, w_st, d_ok, d_st, 0);
+            if (timed) HIPCHK(c, hipEventRecord(ev[3], s));
+            HIPCHK(c, hipStreamSynchronize(s));
+            lap(2, 3);
+        }
+    }
+    c->timing_mode = timing_mode;
+    if (zs) {
+        (void)hipStreamSynchronize(s);
+        return zs;
+    }
+    HIPCHK(c, hipStreamSynchronize(s));
+    lap(0, 1);
+    c->last_timing.clear(), c->last_total_ms = 0, c->last_wall_ms = 0;
+    if (timed) {   // the windows' families, summed, and the partition's kernels (census, permutation, gathers, scatters) as one family
+        c->last_timing = fam;
+        c->last_timing.push_back({"v_levels", lv_ms});
+        for (auto& f : c->last_timing)
+            if (f.first[0] != '+') c->last_total_ms += f.second;
+        c->last_wall_ms = c->last_total_ms;
+    }
+    return ZK_OK;
+}
+
 extern "C" zk_status zk_verify_batch_device(zk_ctx* c, uint64_t B, const void* d_msg, const void* d_proofs, const void* d_off, const void* d_vseeds, void* d_ok,
                                             void* d_status) {
     if (!c || (B && (!d_msg || !d_proofs || !d_off || !d_ok || !d_status))) return ZK_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
+    if (c->verify_level == ZK_VERIFY_LEVEL_PER_PROOF)
+        return verify_per_proof(c, B, (const uint8_t*)d_msg, (const uint8_t*)d_proofs, (const uint64_t*)d_off, (const uint8_t*)d_vseeds, (uint8_t*)d_ok, (int32_t*)d_status,
+                                false);
     return verify_device(c, B, (const uint8_t*)d_msg, (const uint8_t*)d_proofs, (const uint64_t*)d_off, (const uint8_t*)d_vseeds, (uint8_t*)d_ok, (int32_t*)d_status);
 }
 extern "C" zk_status zk_verify_batch(zk_ctx* c, uint64_t B, const uint8_t* msg, const uint8_t* proofs, const uint64_t* off, const uint8_t* vseeds, uint8_t* ok,
@@ -743,10 +929,23 @@ extern "C" zk_status zk_verify_batch(zk_ctx* c, uint64_t B, const uint8_t* msg, 
         c->err = "streamed jobs are in flight on this context (zk_prove_wait / zk_verify_wait them first)";
         return ZK_E_ARG;
     }
+    return verify_host(c, B, msg, proofs, off, vseeds, ok, status);
+}
+zk_status verify_host(zk_ctx* c, uint64_t B, const uint8_t* msg, const uint8_t* proofs, const uint64_t* off, const uint8_t* vseeds, uint8_t* ok, int32_t* status) {
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->params_set || !c->N) return ZK_E_BUFFER;
+    if (B == 0) return ZK_OK;
     if (off[0] != 0) return ZK_E_ARG;
     for (uint64_t b = 0; b < B; b++)
         if (off[b + 1] < off[b]) return ZK_E_ARG;  // every proof lies inside [0, off[B])
     uint64_t total = off[B];
+    // per-proof mode: the headers are read here; one level runs the usual pipeline planned at it, several go through the device partition
+    // (verify_per_proof) after ONE copy of the bytes to HBM
+    const bool per_proof = c->verify_level == ZK_VERIFY_LEVEL_PER_PROOF;
+    const uint32_t lvl = per_proof ? host_level_census(c, B, proofs, off) : LV_NONE;
+    const bool mixed = lvl == LV_MIXED;
+    std::optional<VLevel> level;
+    if (per_proof && !mixed) level.emplace(c, lvl == LV_NONE ? c->P.sec : lvl);
     // the small per-proof arrays live in the context's grow-only input buffer (no hipMalloc / hipFree per call)
     Carver k0(nullptr);
     auto carve_in = [&](Carver& kk, uint8_t*& m, uint64_t*& o, uint8_t*& okp, int32_t*& st_, uint8_t*& sd) {
@@ -765,7 +964,7 @@ extern "C" zk_status zk_verify_batch(zk_ctx* c, uint64_t B, const uint8_t* msg, 
     if (zs) return zs;
     uint8_t* d_proofs = (uint8_t*)c->io_buf;
     // page-locked `proofs` (zk_host_alloc): chunk-wise DMA under the kernels of the earlier chunks; pageable: one blocking copy
-    const bool pinned = host_ptr_is_pinned(proofs);
+    const bool pinned = !mixed && host_ptr_is_pinned(proofs);
     if (pinned) {
         zs = ensure_copy_stream(c);
         if (zs) return zs;
@@ -791,7 +990,8 @@ extern "C" zk_status zk_verify_batch(zk_ctx* c, uint64_t B, const uint8_t* msg, 
         if (vseeds) HIPCHK(c, hipMemcpyAsync(d_seeds, vseeds, 32 * B, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));   // both lanes read these arrays
     }
-    zs = verify_device(c, B, d_msg, d_proofs, d_off, vseeds ? d_seeds : nullptr, d_ok, d_st, pinned ? proofs : nullptr, pinned ? off : nullptr, staged);
+    zs = mixed ? verify_per_proof(c, B, d_msg, d_proofs, d_off, vseeds ? d_seeds : nullptr, d_ok, d_st, staged)
+               : verify_device(c, B, d_msg, d_proofs, d_off, vseeds ? d_seeds : nullptr, d_ok, d_st, pinned ? proofs : nullptr, pinned ? off : nullptr, staged);
     if (zs) {
         if (staged) (void)hipStreamSynchronize(c->stream);   // the mirror is reused by the next call
         return zs;

@@ -42,6 +42,18 @@ struct zk_ctx {
     uint32_t n = 0;
     uint32_t* ring_digest = nullptr;   // [8] SHA-256 words of the padded ring (hardened mode), computed by every zk_ctx_set_ring
     uint32_t mode = 0;                 // zk_ctx_set_mode: ZK_MODE_REFERENCE / ZK_MODE_HARDENED
+    uint32_t verify_level = 0;         // zk_ctx_set_verify_level: ZK_VERIFY_LEVEL_CONTEXT / ZK_VERIFY_LEVEL_PER_PROOF
+    // per-proof mode: the repetition count the verifier's workspaces are planned for during one call (or while streamed verify jobs are queued); the
+    // context's own P.sec otherwise (plan_sec below), so that the next prove call plans at the context's level again
+    uint32_t v_sec = 0;
+    bool v_sec_on = false;
+    void* lv_buf = nullptr;            // per-proof mode: census, permutation and counters of a mixed batch (grow-only)
+    size_t lv_bytes = 0;
+    void* lw_buf = nullptr;            // ... the offsets, message hashes, seeds and verdicts of the window one level's proofs are gathered into
+    size_t lw_bytes = 0;
+    void* lb_buf = nullptr;            // ... and the window's proof bytes (grow-only)
+    size_t lb_bytes = 0;
+    uint32_t* h_lv = nullptr;          // page-locked read-back of the per-level counters
     // workspace: up to ZK_MAX_LANES pipeline lanes, each with its own HIP stream and prover / verifier workspace; consecutive
     // chunks go to consecutive lanes, so the low-occupancy per-proof kernels, the scans the host waits for and (host-pointer
     // calls) the output phases of different chunks fall into each other's heavy phases.  Lane 0 runs on `stream`.
@@ -168,6 +180,8 @@ struct Scope {
 };
 // Per-family events of a blocking call of B proofs?  Two events per family and chunk cost a call of a few proofs 0.15-0.45 ms of idle GPU between kernels
 // (profiles/r06_ab_variants.txt (14)); a call of more than V_SIDE_MAXP proofs does not notice them.
+// the repetition count the workspaces are planned for: the context's secLevel, or the level of the proofs a per-proof-mode verify call is running
+static inline uint32_t plan_sec(const zk_ctx* c) { return c->v_sec_on ? c->v_sec : c->P.sec; }
 static inline bool zk_timed(const zk_ctx* c, uint64_t B) { return c->timing_mode == ZK_TIMING_ON || (c->timing_mode == ZK_TIMING_AUTO && B > V_SIDE_MAXP); }
 static inline void timing_begin(zk_ctx* c) { c->trecs.clear(), c->eused = 0, c->timing_forked = false; }
 static inline void timing_end(zk_ctx* c) {

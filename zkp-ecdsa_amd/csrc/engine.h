@@ -327,6 +327,14 @@ void launch_v_p256_total(hipStream_t s, const DevParams& P, const Workspace& W, 
 void launch_v_p256_total_fixed(hipStream_t s, const DevParams& P, const Workspace& W, const VWork& V, uint32_t count);
 void launch_v_p256_total_sum(hipStream_t s, const DevParams& P, const Workspace& W, const VWork& V, uint32_t count);
 void launch_v_final(hipStream_t s, const Workspace& W, const VWork& V, uint32_t count, uint8_t* ok, int32_t* status, uint64_t first, const VGroupFlags& gf, uint32_t gsz);
+void launch_v_final_memb(hipStream_t s, const Workspace& W, const VWork& V, uint32_t count, uint8_t* ok, int32_t* status, uint64_t first);   // levels below VK
+// per-proof verify levels (k_levels.hip)
+void launch_lv_census(hipStream_t s, uint64_t B, const uint8_t* proofs, const uint64_t* off, bool packed, uint8_t* cls, uint32_t* blk_cnt, uint32_t* out);
+void launch_lv_perm(hipStream_t s, uint64_t B, const uint8_t* cls, const uint32_t* blk_base, const uint32_t* out, uint32_t* perm);
+void launch_lv_gather_meta(hipStream_t s, uint32_t n, const uint32_t* sel, const uint64_t* off, const uint8_t* msg, const uint8_t* vseeds, uint64_t* w_off, uint8_t* w_msg,
+                           uint8_t* w_seeds);
+void launch_lv_gather_bytes(hipStream_t s, uint32_t n, const uint32_t* sel, const uint64_t* off, const uint8_t* proofs, const uint64_t* w_off, uint8_t* w_bytes);
+void launch_lv_scatter(hipStream_t s, uint32_t n, const uint32_t* sel, const uint8_t* w_ok, const int32_t* w_st, uint8_t* ok, int32_t* status, int32_t st);
 
 // chunk inputs (device pointers, already offset to the chunk's first proof)
 struct ChunkIn {

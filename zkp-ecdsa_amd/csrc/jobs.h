@@ -96,6 +96,9 @@ struct VerifyJob {
     // being queued early behind a wait for its event.  Two or more queues that hold a wait slow every OTHER queue of the device down by ~17 us per kernel boundary
     // (tools/sha_bench.hip: 21 -> 57 us per pair of small kernels), and stage 1's tail is a chain of ten small kernels on the main stream.
     bool host_release = false;
+    // per-proof verify levels (zk_ctx_set_verify_level): proofs of fewer than VK repetitions -- header, validation and the membership proof only, then
+    // 'security level not achieved' where membership holds (k_v_final_memb)
+    bool memb_only = false;
     hipEvent_t inputs_ready = nullptr;
     std::vector<ChunkPlan> plan;
     std::vector<hipEvent_t> arrived;     // host_src: one event per chunk, recorded on the copy stream behind the chunk's bytes
@@ -128,6 +131,12 @@ struct VerifyJob {
     uint64_t next_s2a = 0;
 };
 zk_status ensure_vworkspace(zk_ctx* c, uint32_t C, uint32_t nlanes);   // api_verify.hip
+// per-proof verify levels (api_verify.hip): the level every well-formed header of a host batch announces, LV_MIXED for several, LV_NONE for none
+#define LV_MIXED 0xfffffffeu
+#define LV_NONE 0xffffffffu
+uint32_t host_level_census(const zk_ctx* c, uint64_t B, const uint8_t* proofs, const uint64_t* off);
+// zk_verify_batch without the refusal while streamed jobs are queued: a deferred streamed job runs through it at its wait (api_stream.hip)
+zk_status verify_host(zk_ctx* c, uint64_t B, const uint8_t* msg, const uint8_t* proofs, const uint64_t* off, const uint8_t* vseeds, uint8_t* ok, int32_t* status);
 // bytes of the expansion staging and entries of the offset array for a ZKA1P batch of B proofs, `total` packed bytes, chunks of C proofs
 static inline size_t unpack_stage_bytes(uint64_t B, uint64_t total, uint32_t C) { return (size_t)((total * 12 + 10) / 11 + 32 * B + 256 * (B / (C ? C : 1) + 2) + 64); }
 static inline size_t unpack_off_entries(uint64_t B, uint32_t C) { return (size_t)(B + B / (C ? C : 1) + 4); }

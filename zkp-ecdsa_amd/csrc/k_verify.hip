@@ -1785,6 +1785,22 @@ __global__ void __launch_bounds__(64, 2) k_v_final(Workspace W, VWork V, uint32_
     ok_out[first + p] = ok;
     status_out[first + p] = st;
 }
+// A proof of fewer than VK repetitions (per-proof verify levels, include/zkattest.h): verifySignatureList checks membership first and verifyExp then
+// throws 'security level not achieved' (src/zkpAttestList.ts:165-183, src/exp/exp.ts:243-245).  Only the membership sum was computed (per proof).
+__global__ void __launch_bounds__(64, 2) k_v_final_memb(Workspace W, VWork V, uint32_t count, uint8_t* ok_out, int32_t* status_out, uint64_t first) {
+    uint32_t p = gtid();
+    if (p >= count) return;
+    int32_t st = V.st[p];
+    if (st == ZK_OK && !(V.okflags[p] & 8)) {   // (a GKProof of another length: the reference returns false)
+        const uint32_t n = V.n, nq = (n + 1) / 2;
+        TomPt m = ld_tom_proj3(W.lc.proj, p * 4 * n);
+        for (uint32_t q = 0; q < nq; q++) m = tom_add(m, ld_tom4(V.gk_acc, p * nq + q));
+        m = tom_add(m, ld_tom4(V.misc_acc, p));
+        if (tom_is_identity(m)) st = ZK_E_SECLEVEL;
+    }
+    ok_out[first + p] = 0;
+    status_out[first + p] = st;
+}
 // Clambda = comS1 from the proof (Montgomery affine), for k_v_final
 __global__ void k_v_clambda(VWork V, uint32_t count, const uint8_t* proofs, const uint64_t* off, uint64_t first) {
     uint32_t p = gtid();
@@ -1888,4 +1904,7 @@ void launch_v_p256_total_sum(hipStream_t s, const DevParams& P, const Workspace&
 }
 void launch_v_final(hipStream_t s, const Workspace& W, const VWork& V, uint32_t count, uint8_t* ok, int32_t* status, uint64_t first, const VGroupFlags& gf, uint32_t gsz) {
     L1(k_v_final, count, 64, W, V, count, ok, status, first, gf, gsz);
+}
+void launch_v_final_memb(hipStream_t s, const Workspace& W, const VWork& V, uint32_t count, uint8_t* ok, int32_t* status, uint64_t first) {
+    L1(k_v_final_memb, count, 64, W, V, count, ok, status, first);
 }

@@ -39,3 +39,17 @@ ZK_HD static inline Wire wire_make(bool packed) {
 ZK_HD static inline uint64_t wire_proof_size(const Wire& w, uint32_t sec, uint32_t n, uint32_t z) {
     return (uint64_t)w.fixed + (uint64_t)w.rep_head * sec + (uint64_t)w.padd * z + (uint64_t)w.gk_n * n + 32;
 }
+// Per-proof verify levels (zk_ctx_set_verify_level): the level a proof of o1 - o0 bytes at `pr` announces, 0..ZK_MAXSEC, or ZK_LV_BAD where the
+// header alone already makes it ZK_E_BAD_ENCODING in the pipeline at ANY level (short, misaligned, wrong magic, a length that is not the header's,
+// secLevel above 128, n above 63, or more bytes than the largest well-formed proof of that level) -- which also bounds the bytes a level's
+// window can receive.  Only the first 16 header bytes are read.
+#define ZK_LV_BAD (ZK_MAXSEC + 1)
+#define ZK_LV_CLASSES (ZK_MAXSEC + 2)
+ZK_HD static inline uint32_t wire_level_class(const uint8_t* pr, uint64_t o0, uint64_t o1, const Wire& w) {
+    if (o1 < o0 + ZK_HDR || (o0 & 3) || ((o1 - o0) & 3)) return ZK_LV_BAD;
+    uint32_t h[4];
+    __builtin_memcpy(h, pr, 16);
+    const uint32_t total = __builtin_bswap32(h[1]), sec = __builtin_bswap32(h[2]), n = __builtin_bswap32(h[3]);
+    if (h[0] != w.magic || total != o1 - o0 || sec > ZK_MAXSEC || n > 63 || total > wire_proof_size(w, sec, 63, sec)) return ZK_LV_BAD;
+    return sec;
+}
