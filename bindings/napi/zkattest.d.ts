@@ -35,6 +35,9 @@ export function proveSignatureListBatch(params: SystemParametersList, msgHashes:
 /** booleans per proof; `errors[b]` holds what verifySignatureList would have thrown for proof b (null otherwise) -- a malformed proof never affects its neighbours */
 export type Verdicts = boolean[] & { readonly errors: (Error | null)[] }
 export function verifySignatureListBatch(params: SystemParametersList, msgHashes: Uint8Array[], keys: bigint[] | Buffer, proofs: (SignatureProofList | Buffer)[]): Promise<Verdicts>
+/** one statement per proof over its own ring: keyLists[i] is proof i's ring.  The rings stay resident on the params' engine (Engine.setOption('residentRings')),
+ *  every call is one mixed-ring batch on the GPU (split only when it names more rings than are kept resident) */
+export function verifySignatureLists(params: SystemParametersList, msgHashes: Uint8Array[], keyLists: (bigint[] | Buffer)[], proofs: (SignatureProofList | Buffer)[]): Promise<Verdicts>
 type Newable<T> = new (...args: any[]) => T
 export function writeJson<T>(type: Newable<T>, object: T): string
 export function readJson<T>(type: Newable<T>, text: string): T
@@ -48,11 +51,20 @@ export class Engine {
     constructor(devices?: number | number[])
     close(): void
     info(): { devices: number; ringTransport: string; proofMaxSize: number }
-    setOption(name: 'chunk' | 'lanes' | 'combBits' | 'hostTaper' | 'batchVerify' | 'mode' | 'slice' | 'ringFold' | 'verifyGroups' | 'wire' | 'verifyLevel' | 'inflight', value: number): void
+    /** residentRings (1..16, default 4): key rings the facade's context cache keeps built on this engine, least recently used dropped first */
+    setOption(name: 'chunk' | 'lanes' | 'combBits' | 'hostTaper' | 'batchVerify' | 'mode' | 'slice' | 'ringFold' | 'verifyGroups' | 'wire' | 'verifyLevel' | 'inflight' | 'residentRings', value: number): void
     /** zero the witness-derived device memory (prover workspaces, staged signatures and seeds) of every device now; close() and a failed prove do it by themselves */
     wipe(): void
     setParams(p: EngineParams): void
     setRing(keys: Buffer | bigint[]): string
+    /** resident rings (zk_pool_add_ring): built once, then switched by id without a rebuild; the active ring cannot be dropped */
+    addRing(keys: Buffer | bigint[]): number
+    useRing(id: number): void
+    dropRing(id: number): void
+    ringInfo(id: number): { nKeys: number; logN: number; flags: number; generation: number }
+    /** one resident ring id per proof (zk_pool_verify_batch_rings) */
+    verifyBatchRings(msg: Buffer, proofs: Buffer[], ringIds: number[] | Uint32Array, seeds?: Buffer): Verdicts
+    verifyBatchRingsAsync(msg: Buffer, proofs: Buffer[], ringIds: number[] | Uint32Array, seeds?: Buffer): Promise<Verdicts>
     keysToInts(pkxy: Buffer): { keys: Buffer; status: Buffer }
     proveBatch(msg: Buffer, sig: Buffer, pk: Buffer, which: number[] | Buffer, seeds?: Buffer): Buffer[]
     verifyBatch(msg: Buffer, proofs: Buffer[], seeds?: Buffer): Verdicts

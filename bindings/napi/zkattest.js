@@ -286,6 +286,10 @@ function msgOf(msg, pk) {   // the message hashes of the packed proofs only
     for (let b = 0; b < pk.slot.length; b++) if (pk.slot[b] >= 0) parts.push(msg.slice(32 * b, 32 * b + 32))
     return Buffer.concat(parts)
 }
+function idsOf(ids, pk) {   // the ring ids of the packed proofs only, as u32
+    const all = Uint32Array.from(ids)
+    return Buffer.from(pk.n === pk.slot.length ? all.buffer : all.filter((_, b) => pk.slot[b] >= 0).buffer)
+}
 function seedsOf(seeds, pk) {
     if (!seeds || pk.n === pk.slot.length) return seeds || null
     const parts = []
@@ -300,11 +304,25 @@ class Engine {
     }
     close() { if (this.h) native.destroyPool(this.h); this.h = null }
     info() { return native.poolInfo(this.h) }
-    setOption(name, value) { native.setOption(this.h, name, value) }   // chunk, lanes, combBits (before setParams), hostTaper, batchVerify, mode, slice, ringFold, verifyGroups, wire (0 ZKA1, 1 ZKA1P), verifyLevel (0 context, 1 per proof), inflight
+    // chunk, lanes, combBits (before setParams), hostTaper, batchVerify, mode, slice, ringFold, verifyGroups, wire (0 ZKA1, 1 ZKA1P), verifyLevel (0 context, 1 per proof), inflight;
+    // residentRings (default 4): how many key rings the facade's context cache keeps built on this engine (engineFor: LRU by ring)
+    setOption(name, value) {
+        if (name === 'residentRings') {
+            if (!(Number.isInteger(value) && value >= 1 && value <= 16)) throw new RangeError('residentRings: 1 .. 16')
+            this.residentRings = value
+            return
+        }
+        native.setOption(this.h, name, value)
+    }
     wipe() { native.setOption(this.h, 'wipe', 0) }   // zk_ctx_wipe on every device: prover workspaces and staged inputs zeroed (also done by close() and after a failed prove)
     // params: { nistH: 64 B, tomG: 72 B, tomH: 72 B, secLevel } -- SystemParametersList as affine big-endian coordinates
     setParams(p) { native.setParams(this.h, p.nistH, p.tomG, p.tomH, p.secLevel || 80); this.params = p }
     setRing(keys) { return native.setRing(this.h, Buffer.isBuffer(keys) ? keys : Buffer.concat(keys.map(be32))) }
+    // resident rings (include/zkattest.h zk_ctx_add_ring): built once, switched by id without a rebuild
+    addRing(keys) { return native.addRing(this.h, Buffer.isBuffer(keys) ? keys : Buffer.concat(keys.map(be32))) }   // -> ring id (not made active)
+    useRing(id) { native.useRing(this.h, id) }
+    dropRing(id) { native.dropRing(this.h, id) }   // the active ring cannot be dropped
+    ringInfo(id) { return native.ringInfo(this.h, id) }   // -> { nKeys, logN, flags, generation }
     synthParams(seed) { return Object.assign(native.synthParams(this.h, seed), { secLevel: 80 }) }
     synthWorkload(seed, nKeys, B) { return native.synthWorkload(this.h, seed, nKeys, B) }
     keysToInts(pkxy) { return native.keysToInts(this.h, pkxy) }                       // keyToInt over a key set
@@ -333,6 +351,17 @@ class Engine {
         if (!pk.n) return Promise.resolve(verdicts(null, pk.slot))
         return native.verifyBatchAsync(this.h, msgOf(msg, pk), pk.blob, pk.off, pk.len, seedsOf(seeds, pk)).then((r) => verdicts(r, pk.slot))
     }
+    // one resident ring id per proof (zk_verify_batch_rings): -> array of booleans with .errors, like verifyBatch
+    verifyBatchRings(msg, proofs, ringIds, seeds) {
+        const pk = packProofs(proofs)
+        return verdicts(pk.n ? native.verifyBatchRings(this.h, msgOf(msg, pk), pk.blob, pk.off, pk.len, idsOf(ringIds, pk), seedsOf(seeds, pk)) : null, pk.slot)
+    }
+    _verifyRingsNow(msg, proofs, ringIds, seeds) {
+        const pk = packProofs(proofs)
+        if (!pk.n) return Promise.resolve(verdicts(null, pk.slot))
+        return native.verifyBatchRingsAsync(this.h, msgOf(msg, pk), pk.blob, pk.off, pk.len, idsOf(ringIds, pk), seedsOf(seeds, pk)).then((r) => verdicts(r, pk.slot))
+    }
+    verifyBatchRingsAsync(msg, proofs, ringIds, seeds) { return this._chain(() => this._verifyRingsNow(msg, proofs, ringIds, seeds)) }
     proveBatchAsync(msg, sig, pk, which, seeds) { return this._chain(() => this._proveNow(msg, sig, pk, which, seeds)) }
     verifyBatchAsync(msg, proofs, seeds) { return this._chain(() => this._verifyNow(msg, proofs, seeds)) }
     run(f) { return this._chain(f) }   // any other call on the handle, queued behind the running batches
@@ -385,20 +414,55 @@ function engineFor(params, keys) {
         if (process.env.ZKATTEST_COMB_BITS) engine.setOption('combBits', parseInt(process.env.ZKATTEST_COMB_BITS, 10))
         if (params.hardened) engine.setOption('mode', 1)
         engine.setParams(params._ep)           // builds the fixed-base tables: once per SystemParametersList
-        slot = { engine, ringTag: null }
+        slot = { engine, rings: new Map(), active: null }   // rings: ring tag -> resident ring id, least recently used first
         engines.set(key, slot)
     }
     const ring = ringOf(keys)
-    // one queued unit per call: (re)load the ring if the loaded one differs (table E: once per key ring), then run the batch;
-    // units of one engine run strictly one after the other, so interleaved callers with different rings cannot mix them up
+    // one queued unit per call: make the ring resident and active (table E and the rest: once per key ring while it stays among the engine's
+    // `residentRings` most recently used), then run the batch; units of one engine run strictly one after the other, so interleaved callers with
+    // different rings cannot mix them up
     const withRing = (job) => slot.engine.run(() => {
-        if (slot.ringTag !== ring.tag) {
-            slot.engine.setRing(ring.buf)
-            slot.ringTag = ring.tag
-        }
+        residentRing(slot, ring)
+        if (slot.active !== ring.tag) { slot.engine.useRing(slot.rings.get(ring.tag)); slot.active = ring.tag }
         return job(slot.engine)
     })
-    return { engine: slot.engine, withRing }
+    // several rings in one unit: every one resident (the caller names at most residentRings), -> their ids in the order given
+    const withRings = (rings, job) => slot.engine.run(() => job(slot.engine, rings.map((r) => residentRing(slot, r, rings))))
+    return { engine: slot.engine, withRing, withRings, capacity: () => slot.engine.residentRings || 4 }
+}
+// ring -> its resident id on the slot's engine: a hit moves it to the back of the LRU order; a miss adds it, dropping the least recently used ring
+// first when residentRings are built (never the active one, nor one of `keep`; with a single resident ring that is active, it is rebuilt in place)
+function residentRing(slot, ring, keep = []) {
+    const e = slot.engine, cap = e.residentRings || 4
+    let id = slot.rings.get(ring.tag)
+    if (id !== undefined) {
+        slot.rings.delete(ring.tag)
+        slot.rings.set(ring.tag, id)
+        return id
+    }
+    const busy = new Set(keep.map((r) => r.tag))
+    while (slot.rings.size >= cap) {
+        const victim = [...slot.rings.keys()].find((t) => t !== slot.active && !busy.has(t))
+        if (victim === undefined) break
+        e.dropRing(slot.rings.get(victim))
+        slot.rings.delete(victim)
+    }
+    if (slot.rings.size >= cap && slot.active !== null && !busy.has(slot.active)) {   // only the active ring is left: rebuilt in place under its id
+        id = slot.rings.get(slot.active)
+        slot.rings.delete(slot.active)
+        e.setRing(ring.buf)
+        slot.active = ring.tag
+    } else {
+        id = e.addRing(ring.buf)
+    }
+    slot.rings.set(ring.tag, id)
+    return id
+}
+function _ringGenerations(params) {   // (tests) ring tag -> build generation of every ring resident on the engine of `params`
+    const slot = params._tag0 && engines.get(params._tag0 + (params.hardened ? '|hardened' : ''))
+    const out = {}
+    if (slot) for (const [tag, id] of slot.rings) out[tag] = slot.engine.ringInfo(id).generation
+    return out
 }
 function shutdown() { for (const s of engines.values()) s.engine.close(); engines.clear() }
 // The wire layout of the proofs the reference-shaped calls below PRODUCE: 'zka1' (default; 36-byte Tom coordinates) or 'zka1p' (33-byte, 5.3 % fewer bytes
@@ -480,7 +544,41 @@ async function verifySignatureListBatch(params, msgHashes, keys, proofs) {
     Object.defineProperty(out, 'errors', { value: errors })
     return out
 }
+// B statements over several rings in one call: keyLists[i] is the ring of proof i.  The rings are made resident on the params' engine (residentRings at a
+// time: a call that names more rings than that is split by ring) and every wire layout's proofs go through ONE zk_verify_batch_rings.  -> booleans with
+// .errors, like verifySignatureListBatch.
+async function verifySignatureLists(params, msgHashes, keyLists, proofs) {
+    if (keyLists.length !== proofs.length || msgHashes.length !== proofs.length) throw new RangeError('verifySignatureLists: one message hash and one key list per proof')
+    const raw = proofs.map((p) => (p instanceof SignatureProofList ? p.bytes : p))
+    const rings = [], ringOfProof = new Array(raw.length), byTag = new Map()
+    keyLists.forEach((keys, i) => {
+        checkRingSize(Buffer.isBuffer(keys) ? keys.length / 32 : keys.length, false)
+        const r = ringOf(keys)
+        if (!byTag.has(r.tag)) { byTag.set(r.tag, rings.length); rings.push(r) }
+        ringOfProof[i] = byTag.get(r.tag)
+    })
+    const { withRings, capacity } = engineFor(params, keyLists[0] || [])
+    const out = new Array(raw.length), errors = new Array(raw.length), level = verifyLevel
+    const per = capacity()
+    for (let g = 0; g < rings.length; g += per) {   // groups of at most residentRings rings
+        const group = rings.slice(g, g + per)
+        for (const wire of [0, 1]) {
+            const sel = []
+            raw.forEach((b, i) => { if (ringOfProof[i] >= g && ringOfProof[i] < g + per && (isPacked(b) ? 1 : 0) === wire) sel.push(i) })
+            if (!sel.length) continue
+            const m = Buffer.concat(sel.map((i) => Buffer.from(msgHashes[i])))
+            const r = await withRings(group, (engine, ids) => {
+                useWire(engine, wire)
+                useVerifyLevel(engine, level)
+                return engine._verifyRingsNow(m, sel.map((i) => raw[i]), sel.map((i) => ids[ringOfProof[i] - g]))
+            })
+            sel.forEach((i, k) => { out[i] = r[k]; errors[i] = r.errors[k] })
+        }
+    }
+    Object.defineProperty(out, 'errors', { value: errors })
+    return out
+}
 
-module.exports = { setVerifyLevel, getVerifyLevel, generateParamsList, generateParamsListHardened, keyToInt, proveSignatureList, verifySignatureList, proveSignatureListBatch, verifySignatureListBatch,
+module.exports = { verifySignatureLists, _ringGenerations, setVerifyLevel, getVerifyLevel, generateParamsList, generateParamsListHardened, keyToInt, proveSignatureList, verifySignatureList, proveSignatureListBatch, verifySignatureListBatch,
     writeJson, readJson, writeJsonBatch, readJsonBatch, SignatureProofList, SystemParametersList, PedersenParams, generatePedersenParams, p256, tomEdwards256, ALL_GROUPS,
     Group, Point, Scalar, Engine, shutdown, setWireLayout, getWireLayout, native }

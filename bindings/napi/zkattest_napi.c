@@ -337,6 +337,7 @@ typedef struct Job {
     uint64_t worst_cap, *off, *len;
     int32_t *status;
     uint8_t *ok;
+    uint32_t *ring_ids; /* verifyBatchRings: one resident ring id per proof */
     zk_status rc;
     char err[384];
     napi_deferred deferred;
@@ -359,7 +360,7 @@ static void job_free(napi_env env, Job *j) {
     if (j->h_ref && env) napi_delete_reference(env, j->h_ref);
     if (j->out_ref && env) napi_delete_reference(env, j->out_ref);
     slab_free(&j->out);
-    free(j->msg), free(j->sig), free(j->pk), free(j->seeds), free(j->which), free(j->off), free(j->len), free(j->status), free(j->ok);
+    free(j->msg), free(j->sig), free(j->pk), free(j->seeds), free(j->which), free(j->off), free(j->len), free(j->status), free(j->ok), free(j->ring_ids);
     free(j);
 }
 /* output capacity for B proofs over G devices: mean + 8 sigma of the zero-bit repetitions per shard, at most the worst case */
@@ -374,7 +375,9 @@ static void prove_caps(Handle *h, size_t B, uint64_t *cap, uint64_t *worst) {
 static void job_execute(napi_env env, void *data) { /* worker thread (or inline for the synchronous calls): no N-API calls here */
     Job *j = data;
     zk_pool *p = j->h->pool;
-    if (j->verify) {
+    if (j->verify && j->ring_ids) {
+        j->rc = zk_pool_verify_batch_rings(p, j->B, j->msg, j->proofs_in, j->off, j->len, j->ring_ids, j->seeds, j->ok, j->status);
+    } else if (j->verify) {
         j->rc = zk_pool_verify_batch(p, j->B, j->msg, j->proofs_in, j->off, j->len, j->seeds, j->ok, j->status);
     } else {
         zk_rng rng = {ZK_RNG_SEED, j->seeds, 0};
@@ -485,10 +488,17 @@ static napi_value prove_common(napi_env env, napi_callback_info info, int async)
 }
 static napi_value ProveBatch(napi_env env, napi_callback_info info) { return prove_common(env, info, 0); }
 static napi_value ProveBatchAsync(napi_env env, napi_callback_info info) { return prove_common(env, info, 1); }
-/* (h, msg Bx32, proofs, offsets (B u64 LE), lengths (B u64 LE), seeds Bx32 | null) -> {ok: B bytes, status: B i32} */
-static napi_value verify_common(napi_env env, napi_callback_info info, int async) {
-    napi_value argv[6];
-    if (!get_args(env, info, 6, argv)) return NULL;
+/* (h, msg Bx32, proofs, offsets (B u64 LE), lengths (B u64 LE), seeds Bx32 | null) -> {ok: B bytes, status: B i32}
+ * rings: (h, msg, proofs, offsets, lengths, ringIds (B u32 LE), seeds | null) -- zk_pool_verify_batch_rings */
+static napi_value verify_common(napi_env env, napi_callback_info info, int async, int rings) {
+    napi_value argv[7];
+    if (!get_args(env, info, rings ? 7 : 6, argv)) return NULL;
+    uint8_t *ids = NULL;
+    size_t lid = 0;
+    if (rings) {
+        if (!get_bytes(env, argv[5], &ids, &lid)) return NULL;
+        argv[5] = argv[6];
+    }
     Handle *h = get_handle(env, argv[0], 0);
     uint8_t *msg, *proofs, *offs, *lens, *seeds;
     size_t lm, lp, lo, ll, ls;
@@ -496,7 +506,7 @@ static napi_value verify_common(napi_env env, napi_callback_info info, int async
         !get_bytes(env, argv[4], &lens, &ll) || !get_bytes(env, argv[5], &seeds, &ls))
         return NULL;
     size_t B = lm / 32;
-    if (!B || lm != 32 * B || lo != 8 * B || ll != 8 * B || (seeds && ls != 32 * B) || !proofs) {
+    if (!B || lm != 32 * B || lo != 8 * B || ll != 8 * B || (seeds && ls != 32 * B) || !proofs || (rings && lid != 4 * B)) {
         napi_throw_range_error(env, NULL, "verifyBatch: B message hashes, B offsets, B lengths, B seeds or null");
         return NULL;
     }
@@ -506,8 +516,9 @@ static napi_value verify_common(napi_env env, napi_callback_info info, int async
     j->msg = dup_bytes(msg, lm), j->off = (uint64_t *)dup_bytes(offs, lo), j->len = (uint64_t *)dup_bytes(lens, ll);
     j->seeds = seeds ? dup_bytes(seeds, ls) : NULL;
     j->ok = malloc(B), j->status = malloc(4 * B);
+    j->ring_ids = rings ? (uint32_t *)dup_bytes(ids, lid) : NULL;
     j->proofs_in = proofs;
-    int okk = j->msg && j->off && j->len && j->ok && j->status && (!seeds || j->seeds);
+    int okk = j->msg && j->off && j->len && j->ok && j->status && (!seeds || j->seeds) && (!rings || j->ring_ids);
     for (size_t b = 0; okk && b < B; b++) okk = j->off[b] <= lp && j->len[b] <= lp - j->off[b];
     if (okk && async) okk = napi_create_reference(env, argv[2], 1, &j->proofs_ref) == napi_ok && napi_create_reference(env, argv[0], 1, &j->h_ref) == napi_ok;
     if (!okk) {
@@ -517,8 +528,62 @@ static napi_value verify_common(napi_env env, napi_callback_info info, int async
     }
     return job_run(env, j, "zkattest.verifyBatch");
 }
-static napi_value VerifyBatch(napi_env env, napi_callback_info info) { return verify_common(env, info, 0); }
-static napi_value VerifyBatchAsync(napi_env env, napi_callback_info info) { return verify_common(env, info, 1); }
+static napi_value VerifyBatch(napi_env env, napi_callback_info info) { return verify_common(env, info, 0, 0); }
+static napi_value VerifyBatchAsync(napi_env env, napi_callback_info info) { return verify_common(env, info, 1, 0); }
+static napi_value VerifyBatchRings(napi_env env, napi_callback_info info) { return verify_common(env, info, 0, 1); }
+static napi_value VerifyBatchRingsAsync(napi_env env, napi_callback_info info) { return verify_common(env, info, 1, 1); }
+/* ---- resident rings (zk_pool_add_ring / use_ring / drop_ring, zk_ring_info of the first shard) */
+static napi_value AddRing(napi_env env, napi_callback_info info) { /* (h, keys: n x 32 bytes) -> ring id */
+    napi_value argv[2];
+    if (!get_args(env, info, 2, argv)) return NULL;
+    Handle *h = get_handle(env, argv[0], 0);
+    uint8_t *k;
+    size_t lk;
+    if (!h || !get_bytes(env, argv[1], &k, &lk)) return NULL;
+    uint32_t id = 0;
+    zk_status st = zk_pool_add_ring(h->pool, k, lk / 32, &id);
+    if (st != ZK_OK) return throw_status(env, h, st);
+    napi_value v;
+    NAPI_OK(napi_create_uint32(env, id, &v));
+    return v;
+}
+static napi_value ring_call(napi_env env, napi_callback_info info, zk_status (*f)(zk_pool *, uint32_t)) { /* (h, ring id) */
+    napi_value argv[2];
+    if (!get_args(env, info, 2, argv)) return NULL;
+    Handle *h = get_handle(env, argv[0], 0);
+    uint32_t id;
+    if (!h) return NULL;
+    if (napi_get_value_uint32(env, argv[1], &id) != napi_ok) {
+        napi_throw_type_error(env, NULL, "expected a ring id");
+        return NULL;
+    }
+    zk_status st = f(h->pool, id);
+    return st == ZK_OK ? NULL : throw_status(env, h, st);
+}
+static napi_value UseRing(napi_env env, napi_callback_info info) { return ring_call(env, info, zk_pool_use_ring); }
+static napi_value DropRing(napi_env env, napi_callback_info info) { return ring_call(env, info, zk_pool_drop_ring); }
+static napi_value RingInfo(napi_env env, napi_callback_info info) { /* (h, ring id) -> {nKeys, logN, flags, generation} */
+    napi_value argv[2];
+    if (!get_args(env, info, 2, argv)) return NULL;
+    Handle *h = get_handle(env, argv[0], 0);
+    uint32_t id, logn = 0, flags = 0;
+    uint64_t nk = 0, gen = 0;
+    if (!h) return NULL;
+    if (napi_get_value_uint32(env, argv[1], &id) != napi_ok) {
+        napi_throw_type_error(env, NULL, "expected a ring id");
+        return NULL;
+    }
+    zk_status st = zk_ring_info(zk_pool_ctx(h->pool, 0), id, &nk, &logn, &flags, &gen);
+    if (st != ZK_OK) return throw_text(env, st, "no resident ring has this id");
+    napi_value v, a, b, c, d;
+    NAPI_OK(napi_create_object(env, &v));
+    NAPI_OK(napi_create_double(env, (double)nk, &a));
+    NAPI_OK(napi_create_uint32(env, logn, &b));
+    NAPI_OK(napi_create_uint32(env, flags, &c));
+    NAPI_OK(napi_create_double(env, (double)gen, &d));
+    set_prop(env, v, "nKeys", a), set_prop(env, v, "logN", b), set_prop(env, v, "flags", c), set_prop(env, v, "generation", d);
+    return v;
+}
 
 /* ---- streamed batches: several jobs of one handle in flight (zk_pool_prove_submit / _wait).
  * proveSubmit / verifySubmit return a Promise at once and append the job to the handle's queue.  The engine wants one caller at a
@@ -907,7 +972,9 @@ static napi_value Init(napi_env env, napi_value exports) {
                {"verifyBatchAsync", VerifyBatchAsync}, {"proofToJson", ProofToJson}, {"proofFromJson", ProofFromJson},
                {"keysToInts", KeysToInts},       {"hostAlloc", HostAlloc},           {"hardenedH", HardenedH},
                {"proofsToJsonBatch", ProofsToJsonBatch}, {"proofsFromJsonBatch", ProofsFromJsonBatch},
-               {"proveSubmit", ProveSubmit},     {"verifySubmit", VerifySubmit}};
+               {"proveSubmit", ProveSubmit},     {"verifySubmit", VerifySubmit},
+               {"addRing", AddRing},             {"useRing", UseRing},               {"dropRing", DropRing},       {"ringInfo", RingInfo},
+               {"verifyBatchRings", VerifyBatchRings}, {"verifyBatchRingsAsync", VerifyBatchRingsAsync}};
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;
         if (napi_create_function(env, fns[i].name, NAPI_AUTO_LENGTH, fns[i].fn, NULL, &f) != napi_ok) return NULL;

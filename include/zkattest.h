@@ -256,6 +256,51 @@ zk_status zk_verify_batch_device(zk_ctx *ctx, uint64_t B, const void *d_msg_hash
 enum { ZK_VERIFY_LEVEL_CONTEXT = 0, ZK_VERIFY_LEVEL_PER_PROOF = 1 };
 zk_status zk_ctx_set_verify_level(zk_ctx *ctx, uint32_t mode);
 
+/* Resident rings.  The reference takes the ring as an argument of every call (proveSignatureList / verifySignatureList,
+ * src/zkpAttestList.ts:104-184); a context keeps up to ZK_MAX_RINGS rings built at once, so that a verifier serving several key sets
+ * never rebuilds one (a rebuild costs tens of milliseconds at 2^16 keys, a verification ~1.5 ms).  Exactly one of them, or none, is ACTIVE:
+ * every prove, verify, submit and pool entry point, zk_ring_digest and zk_proof_max_size work on the active ring, and a context whose
+ * rings are all inactive answers like a context without a ring.
+ * zk_ctx_add_ring[_device] builds a new ring (padding, the one-key refusal and the bounds of zk_ctx_set_ring) and returns its id in *ring;
+ * ids are never reused within a context.  It does not make the ring active.  Every table beyond the ring's limbs and digest is optional
+ * (table E, the digit planes, the per-key tables): what does not fit is skipped and zk_ring_info's flags say so; the call fails only where
+ * the limbs themselves cannot be allocated.  When a later workspace does not fit, the key tables of the rings the call does not use are
+ * given up first, then those of the ring it runs on -- same bytes and verdicts, slower proving.
+ * zk_ctx_use_ring makes a ring active: host work only, no allocation and no kernel.  zk_ctx_set_ring[_device] (re)builds the ACTIVE ring in
+ * place and keeps its id; on a context without an active ring it creates one (ring 0 on a fresh context) and makes it active.
+ * zk_ctx_drop_ring frees a ring; dropping the active ring is refused.  zk_ring_info: the ring's key count before padding, n = log2 of the
+ * padded size, ZK_RING_* flags and a generation counter that every build of the ring increments (use_ring does not).
+ * All four return ZK_E_ARG for an id that is not resident and while streamed jobs are queued on the context, like the zk_ctx_set_*.
+ * zk_pool_add_ring / use_ring / drop_ring do the same on every shard context with the same id (a shard that fails to add drops it again on
+ * the others). */
+#define ZK_MAX_RINGS 16
+enum {
+    ZK_RING_TABLE_E = 1,          /* table E of the GK block transform (rings of 2^8 .. 2^20 keys) */
+    ZK_RING_DIGIT_PLANES = 2,     /* the ring as int8 digit planes: the verifier's ring fold on the matrix pipe (rings of >= 2^12 keys) */
+    ZK_RING_TABLE_E_DIGITS = 4,   /* table E as digit planes: the prover's matrix-pipe table path */
+    ZK_RING_KEY_TABLES = 8,       /* per-key tables (zk_ctx_set_key_tables) */
+    ZK_RING_ACTIVE = 16           /* the context's active ring */
+};
+zk_status zk_ctx_add_ring(zk_ctx *ctx, const uint8_t *keys_be32, uint64_t n_keys, uint32_t *ring);
+zk_status zk_ctx_add_ring_device(zk_ctx *ctx, const void *d_keys_be32, uint64_t n_keys, uint32_t *ring);
+zk_status zk_ctx_use_ring(zk_ctx *ctx, uint32_t ring);
+zk_status zk_ctx_drop_ring(zk_ctx *ctx, uint32_t ring);
+zk_status zk_ring_info(zk_ctx *ctx, uint32_t ring, uint64_t *n_keys, uint32_t *log_n, uint32_t *flags, uint64_t *generation);
+
+/* Mixed-ring verification: zk_verify_batch[_device] with one resident ring id per proof.  A proof whose id is not resident gets ok 0 and
+ * ZK_E_ARG; every other proof gets exactly the (ok, status) zk_verify_batch gives it with that ring active -- both wire layouts, hardened
+ * mode with each ring's own digest, per-proof verify levels.  The active ring is neither read nor changed.  How: the proofs are classed by
+ * (ring, level) -- on the host for host-pointer calls, by one census kernel and ONE read-back of the per-class counters for the device
+ * call; a batch of one class runs the usual pipeline on the caller's buffers with that ring bound, several classes are gathered class by
+ * class into windows of at most 2 x chunk x lanes proofs, verified there and their verdicts scattered back (a host-pointer batch of several
+ * classes first copies its bytes to HBM in one transfer).  zk_pool_verify_batch_rings shards by contiguous proof ranges like
+ * zk_pool_verify_batch; the ids are those of zk_pool_add_ring. */
+zk_status zk_verify_batch_rings(zk_ctx *ctx, uint64_t B, const uint8_t *msg_hash /*Bx32*/, const uint8_t *proofs, const uint64_t *proof_off /*B+1*/,
+                                const uint32_t *ring_ids /*B*/, const uint8_t *verifier_seeds /*Bx32 or NULL*/, uint8_t *ok /*B*/,
+                                int32_t *per_proof_status /*B*/);
+zk_status zk_verify_batch_rings_device(zk_ctx *ctx, uint64_t B, const void *d_msg_hash, const void *d_proofs, const void *d_proof_off,
+                                       const void *d_ring_ids, const void *d_verifier_seeds, void *d_ok, void *d_per_proof_status);
+
 /* ---- two (or more) batches in flight on one context.  zk_prove_batch / zk_verify_batch are synchronous: each call pays its own head
  * (no byte of a chunk exists before its stage 1 is over) and its own tail (the copies of the last slices, with nothing left to
  * hide them).  The submit / wait pair splits a call so that the pipeline keeps running ACROSS calls: submit stages the inputs and
@@ -315,6 +360,9 @@ void zk_pool_shard(const zk_pool *pool, uint64_t B, int i, uint64_t *first, uint
 zk_status zk_pool_set_params(zk_pool *pool, const uint8_t nist_h[64], const uint8_t tom_g[72], const uint8_t tom_h[72], uint32_t sec_level);
 zk_status zk_pool_set_ring(zk_pool *pool, const uint8_t *keys_be32, uint64_t n_keys);
 zk_status zk_pool_set_verify_level(zk_pool *pool, uint32_t mode);   /* zk_ctx_set_verify_level on every shard context */
+zk_status zk_pool_add_ring(zk_pool *pool, const uint8_t *keys_be32, uint64_t n_keys, uint32_t *ring);   /* resident rings: see zk_ctx_add_ring */
+zk_status zk_pool_use_ring(zk_pool *pool, uint32_t ring);
+zk_status zk_pool_drop_ring(zk_pool *pool, uint32_t ring);
 /* zk_prove_batch over all devices.  Shard i writes its proofs back to back from out + i * ((out_cap / G) & ~255): proof b lies
  * at out_off[b] .. out_off[b] + out_len[b] (its ZKA1 header carries the same length); there are gaps between shards, none
  * inside one.  ZK_E_BUFFER when a shard does not fit its region.  `out` from zk_host_alloc is filled by overlapped DMA. */
@@ -336,6 +384,10 @@ void zk_pool_device_free(zk_pool *pool, int i, void *p);
 zk_status zk_pool_verify_batch(zk_pool *pool, uint64_t B, const uint8_t *msg_hash, const uint8_t *proofs, const uint64_t *proof_off /*B*/,
                                const uint64_t *proof_len /*B*/, const uint8_t *verifier_seeds /*Bx32 or NULL*/, uint8_t *ok /*B*/,
                                int32_t *per_proof_status /*B*/);
+/* zk_verify_batch_rings over all devices, with the packing rules of zk_pool_verify_batch */
+zk_status zk_pool_verify_batch_rings(zk_pool *pool, uint64_t B, const uint8_t *msg_hash, const uint8_t *proofs, const uint64_t *proof_off /*B*/,
+                                     const uint64_t *proof_len /*B*/, const uint32_t *ring_ids /*B*/, const uint8_t *verifier_seeds /*Bx32 or NULL*/,
+                                     uint8_t *ok /*B*/, int32_t *per_proof_status /*B*/);
 
 /* The streamed form of the two pool calls (see "two batches in flight"): every device's shard goes through zk_prove_submit / zk_prove_wait on
  * its own context, so a node keeps two or three batches in flight per GPU.  Same rules per device (waits in submission order, `out` /

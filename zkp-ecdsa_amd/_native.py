@@ -22,6 +22,8 @@ SYMBOLS = [
     'zk_proofs_to_json_batch', 'zk_proofs_from_json_batch', 'zk_ctx_set_ring_fold',
     'zk_pool_prove_submit', 'zk_pool_prove_wait', 'zk_pool_verify_submit', 'zk_pool_verify_wait', 'zk_ctx_set_verify_groups',
     'zk_ctx_set_verify_level', 'zk_pool_set_verify_level',
+    'zk_ctx_add_ring', 'zk_ctx_add_ring_device', 'zk_ctx_use_ring', 'zk_ctx_drop_ring', 'zk_ring_info', 'zk_verify_batch_rings', 'zk_verify_batch_rings_device',
+    'zk_pool_add_ring', 'zk_pool_use_ring', 'zk_pool_drop_ring', 'zk_pool_verify_batch_rings',
     'zk_test_field_op', 'zk_test_tom_commit', 'zk_test_p256_fixed_mul', 'zk_test_sha256', 'zk_test_rng_draws',
 ]
 
@@ -90,6 +92,17 @@ def lib():
         L.zk_ctx_set_mode.argtypes = [vp, u32]
         L.zk_ctx_set_verify_level.argtypes = [vp, u32]
         L.zk_pool_set_verify_level.argtypes = [vp, u32]
+        L.zk_ctx_add_ring.argtypes = [vp, C.c_char_p, u64, C.POINTER(u32)]
+        L.zk_ctx_add_ring_device.argtypes = [vp, vp, u64, C.POINTER(u32)]
+        L.zk_ctx_use_ring.argtypes = [vp, u32]
+        L.zk_ctx_drop_ring.argtypes = [vp, u32]
+        L.zk_ring_info.argtypes = [vp, u32, C.POINTER(u64), C.POINTER(u32), C.POINTER(u32), C.POINTER(u64)]
+        L.zk_verify_batch_rings.argtypes = [vp, u64, C.c_char_p, vp, vp, vp, C.c_char_p, vp, vp]
+        L.zk_verify_batch_rings_device.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp, vp]
+        L.zk_pool_add_ring.argtypes = [vp, C.c_char_p, u64, C.POINTER(u32)]
+        L.zk_pool_use_ring.argtypes = [vp, u32]
+        L.zk_pool_drop_ring.argtypes = [vp, u32]
+        L.zk_pool_verify_batch_rings.argtypes = [vp, u64, C.c_char_p, vp, vp, vp, vp, C.c_char_p, vp, vp]
         L.zk_ring_digest.argtypes = [vp, vp]
         L.zk_hardened_h.argtypes = [C.c_char_p, u64, vp, vp]
         L.zk_pool_create.argtypes = [C.POINTER(C.c_int), i32, C.POINTER(vp)]
@@ -183,6 +196,7 @@ class ZkError(RuntimeError):
 
 
 MODE_REFERENCE, MODE_HARDENED = 0, 1
+RING_TABLE_E, RING_DIGIT_PLANES, RING_TABLE_E_DIGITS, RING_KEY_TABLES, RING_ACTIVE = 1, 2, 4, 8, 16   # zk_ring_info flags
 
 
 def hardened_h(tag=b''):
@@ -362,6 +376,49 @@ class Engine:
         d = C.create_string_buffer(32)
         self._chk(self.L.zk_ring_digest(self.h, d))
         return d.raw
+
+    def add_ring(self, keys_be32, nkeys=None):
+        """zk_ctx_add_ring: builds a new resident ring (not made active) and returns its id."""
+        keys_be32 = bytes(keys_be32)
+        rid = C.c_uint32()
+        self._chk(self.L.zk_ctx_add_ring(self.h, keys_be32, nkeys if nkeys is not None else len(keys_be32) // 32, C.byref(rid)))
+        return rid.value
+
+    def add_ring_device(self, dev_ptr, nkeys):
+        rid = C.c_uint32()
+        self._chk(self.L.zk_ctx_add_ring_device(self.h, dev_ptr, nkeys, C.byref(rid)))
+        return rid.value
+
+    def use_ring(self, ring):
+        """zk_ctx_use_ring: makes a resident ring the active one (no rebuild)."""
+        self._chk(self.L.zk_ctx_use_ring(self.h, ring))
+
+    def drop_ring(self, ring):
+        self._chk(self.L.zk_ctx_drop_ring(self.h, ring))
+
+    def ring_info(self, ring):
+        """zk_ring_info: dict with n_keys, log_n, flags (RING_* bits) and generation."""
+        nk, ln, fl, gen = C.c_uint64(), C.c_uint32(), C.c_uint32(), C.c_uint64()
+        self._chk(self.L.zk_ring_info(self.h, ring, C.byref(nk), C.byref(ln), C.byref(fl), C.byref(gen)))
+        return {'n_keys': nk.value, 'log_n': ln.value, 'flags': fl.value, 'generation': gen.value}
+
+    def verify_batch_rings(self, msg, proofs, ring_ids, vseeds=None):
+        """zk_verify_batch_rings: verify_batch with one resident ring id per proof."""
+        B = len(proofs)
+        off = (C.c_uint64 * (B + 1))()
+        o = 0
+        for b, p in enumerate(proofs):
+            off[b] = o
+            o += len(p)
+        off[B] = o
+        ids = (C.c_uint32 * max(B, 1))(*ring_ids)
+        ok = (C.c_uint8 * B)()
+        st = (C.c_int32 * B)()
+        self._chk(self.L.zk_verify_batch_rings(self.h, B, bytes(msg), b''.join(proofs), off, ids, bytes(vseeds) if vseeds is not None else None, ok, st))
+        return list(ok), list(st)
+
+    def verify_batch_rings_device(self, B, d_msg, d_proofs, d_off, d_ring_ids, d_vseeds, d_ok, d_status):
+        self._chk(self.L.zk_verify_batch_rings_device(self.h, B, d_msg, d_proofs, d_off, d_ring_ids, d_vseeds, d_ok, d_status))
 
     def set_verify_groups(self, groups):
         self._chk(self.L.zk_ctx_set_verify_groups(self.h, groups))
@@ -658,6 +715,36 @@ class Pool:
         keys_be32 = bytes(keys_be32)
         self._chk(self.L.zk_pool_set_ring(self.h, keys_be32, nkeys if nkeys is not None else len(keys_be32) // 32))
         return self.L.zk_pool_ring_transport(self.h).decode()
+
+    def add_ring(self, keys_be32, nkeys=None):
+        """zk_pool_add_ring: the same resident ring (and id) on every shard context."""
+        keys_be32 = bytes(keys_be32)
+        rid = C.c_uint32()
+        self._chk(self.L.zk_pool_add_ring(self.h, keys_be32, nkeys if nkeys is not None else len(keys_be32) // 32, C.byref(rid)))
+        return rid.value
+
+    def use_ring(self, ring):
+        self._chk(self.L.zk_pool_use_ring(self.h, ring))
+
+    def drop_ring(self, ring):
+        self._chk(self.L.zk_pool_drop_ring(self.h, ring))
+
+    def ring_info(self, ring):
+        return self.engine(0).ring_info(ring)
+
+    def verify_batch_rings(self, msg, proofs, ring_ids, vseeds=None):
+        """zk_pool_verify_batch_rings: verify_batch with one resident ring id per proof, sharded by contiguous ranges."""
+        B = len(proofs)
+        off, ln = (C.c_uint64 * B)(), (C.c_uint64 * B)()
+        o = 0
+        for b, p in enumerate(proofs):
+            off[b], ln[b] = o, len(p)
+            o += len(p)
+        blob = (C.c_uint8 * max(o, 1)).from_buffer_copy(b''.join(proofs) or b'\0')
+        ids = (C.c_uint32 * max(B, 1))(*ring_ids)
+        ok, st = (C.c_uint8 * B)(), (C.c_int32 * B)()
+        self._chk(self.L.zk_pool_verify_batch_rings(self.h, B, bytes(msg), C.addressof(blob), off, ln, ids, bytes(vseeds) if vseeds is not None else None, ok, st))
+        return list(ok), list(st)
 
     def prove_batch_raw(self, msg, sig, pk, which, seeds, out, cap):
         """zk_pool_prove_batch into `out` (PinnedBuffer or ctypes array).  Returns (seconds, off, len, status)."""

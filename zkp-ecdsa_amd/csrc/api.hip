@@ -163,6 +163,7 @@ extern "C" zk_status zk_ctx_wipe(zk_ctx* c) {
     wipe_witness(c);
     return ZK_OK;
 }
+static void free_ring(Ring& R);
 extern "C" void zk_ctx_destroy(zk_ctx* c) {
     if (!c) return;
     hipSetDevice(c->device);
@@ -172,8 +173,9 @@ extern "C" void zk_ctx_destroy(zk_ctx* c) {
     wipe_witness(c);
     for (auto e : c->epool) hipEventDestroy(e);
     hipFree(c->P.tom_tab_g), hipFree(c->P.tom_tab_h), hipFree(c->tom_tab_gen), hipFree(c->P.pfix_G), hipFree(c->P.pfix_H);
-    hipFree(c->gk_kdig), hipFree(c->gk_edig), hipFree(c->ktab), hipFree(c->ktab_ok);
-    hipFree(c->tab_scratch), hipFree(c->gk_etab), hipFree(c->d_flag), hipFree(c->ring_mem), hipFree(c->ring_digest);
+    for (auto& R : c->rings) free_ring(R);
+    hipFree(c->tab_scratch), hipFree(c->d_flag), hipFree(c->rg_buf);
+    if (c->h_rg) hipHostFree(c->h_rg);
     hipFree(c->io_buf), hipFree(c->in_buf), hipFree(c->unp_buf), hipFree(c->unp_off), hipFree(c->seed_buf), hipFree(c->lv_buf), hipFree(c->lw_buf), hipFree(c->lb_buf);
     if (c->h_lv) hipHostFree(c->h_lv);
     if (c->h_stage) hipHostFree(c->h_stage);
@@ -260,52 +262,51 @@ extern "C" zk_status zk_ctx_set_params(zk_ctx* c, const uint8_t nist_h[64], cons
     return ZK_OK;
 }
 
-static zk_status set_ring_common(zk_ctx* c, const uint8_t* d_keys, uint64_t nkeys) {
-    if (c->stream_busy) {   // the queued jobs read the ring, table E and the key tables this call would free
-        c->err = "streamed jobs are in flight on this context (zk_prove_wait / zk_verify_wait them first)";
-        return ZK_E_ARG;
-    }
+static void free_ring(Ring& R) {   // (nothing in flight reads it: the callers synchronise or refuse while jobs are queued)
+    hipFree(R.ring_mem), hipFree(R.gk_etab), hipFree(R.gk_kdig), hipFree(R.gk_edig), hipFree(R.ktab), hipFree(R.ktab_ok), hipFree(R.ring_digest);
+    const uint32_t id = R.id;
+    const uint64_t gen = R.generation;
+    const bool live = R.live;
+    R = Ring{};
+    R.id = id, R.generation = gen, R.live = live;
+}
+// Builds ring R from nkeys device-resident keys: its limbs, table E, the digit planes, the per-key tables and the digest.  The previous contents of R are
+// freed first.  strict (zk_ctx_set_ring): a table E that cannot be allocated fails the call, as it always did; otherwise (zk_ctx_add_ring) only the limbs and
+// the digest are required and every other table is skipped where the HBM is not there (zk_ring_info's flags say which exist).
+static zk_status build_ring(zk_ctx* c, Ring& R, const uint8_t* d_keys, uint64_t nkeys, bool strict) {
     uint32_t n = 0;
     while (((uint64_t)1 << n) < nkeys) n++;
     if (n < 1 || n > ZK_MAXN - 4) return ZK_E_ARG;  // N = 1 is the reference's degenerate n = 0 case (untested there)
     uint64_t N = (uint64_t)1 << n;
-    if (c->ring_mem) HIPCHK(c, hipFree(c->ring_mem));
-    c->ring_mem = nullptr;
-    HIPCHK(c, hipMalloc(&c->ring_mem, sizeof(uint32_t) * 9 * N));
-    Soa ring = {c->ring_mem, (uint32_t)N};
+    free_ring(R);
+    R.generation++;
+    HIPCHK(c, hipMalloc(&R.ring_mem, sizeof(uint32_t) * 9 * N));
+    Soa ring = {R.ring_mem, (uint32_t)N};
     launch_ring_load(c->stream, d_keys, nkeys, N, ring);
-    if (c->gk_etab) HIPCHK(c, hipFree(c->gk_etab));
-    c->gk_etab = nullptr;
     if (c->gk_table && n >= GK_ETAB_MINN && n <= GK_ETAB_MAXN) {  // per-ring table of the 8 low fold levels (k_gk.hip)
-        HIPCHK(c, hipMalloc(&c->gk_etab, sizeof(uint32_t) * gk_etab_words(N)));
-        launch_gk_etab(c->stream, ring, (uint32_t)(N >> 8), c->gk_etab);
+        if (strict) HIPCHK(c, hipMalloc(&R.gk_etab, sizeof(uint32_t) * gk_etab_words(N)));
+        else if (hipMalloc(&R.gk_etab, sizeof(uint32_t) * gk_etab_words(N)) != hipSuccess) (void)hipGetLastError(), R.gk_etab = nullptr;   // plain fold for this ring
+        if (R.gk_etab) launch_gk_etab(c->stream, ring, (uint32_t)(N >> 8), R.gk_etab);
     }
-    if (c->gk_kdig) HIPCHK(c, hipFree(c->gk_kdig));
-    c->gk_kdig = nullptr;
     // the two digit-fragment tables and the per-key tables below are optimisations, not requirements: where the HBM is not there (several
     // contexts on one device, a ring of 2^20 keys next to other tenants) the allocation failure is cleared and the vector-ALU fold / the
     // per-proof tables of R serve every proof -- same bytes, same verdicts
-    if (c->gk_etab && n >= GKM_MINN) {   // 33 bytes per key: the verifier's ring fold on the matrix pipe (k_gk_mfma.hip)
-        if (hipMalloc(&c->gk_kdig, gkm_ring_frag_bytes(N)) == hipSuccess) launch_gkm_ring_digits(c->stream, ring, (uint32_t)(N >> 8), c->gk_kdig);
-        else (void)hipGetLastError(), c->gk_kdig = nullptr;
+    if (R.gk_etab && n >= GKM_MINN) {   // 33 bytes per key: the verifier's ring fold on the matrix pipe (k_gk_mfma.hip)
+        if (hipMalloc(&R.gk_kdig, gkm_ring_frag_bytes(N)) == hipSuccess) launch_gkm_ring_digits(c->stream, ring, (uint32_t)(N >> 8), R.gk_kdig);
+        else (void)hipGetLastError(), R.gk_kdig = nullptr;
     }
-    if (c->gk_edig) HIPCHK(c, hipFree(c->gk_edig));
-    c->gk_edig = nullptr;
-    if (c->gk_etab && n >= GKM_MINN && c->gk_mfma_prove) {   // table E's classes 2..6 as digit fragments: the prover's matrix-pipe path
-        if (hipMalloc(&c->gk_edig, gkm_etab_frag_bytes(N)) == hipSuccess) launch_gkm_etab_digits(c->stream, c->gk_etab, (uint32_t)(N >> 8), c->gk_edig);
-        else (void)hipGetLastError(), c->gk_edig = nullptr;
+    if (R.gk_etab && n >= GKM_MINN && c->gk_mfma_prove) {   // table E's classes 2..6 as digit fragments: the prover's matrix-pipe path
+        if (hipMalloc(&R.gk_edig, gkm_etab_frag_bytes(N)) == hipSuccess) launch_gkm_etab_digits(c->stream, R.gk_etab, (uint32_t)(N >> 8), R.gk_edig);
+        else (void)hipGetLastError(), R.gk_edig = nullptr;
     }
-    if (c->ktab) HIPCHK(c, hipFree(c->ktab));
-    if (c->ktab_ok) HIPCHK(c, hipFree(c->ktab_ok));
-    c->ktab = nullptr, c->ktab_ok = nullptr;
     if (c->key_tables && n <= KTAB_MAXN) {   // multiples of every ring key (k_ktab.hip): the prover's k * pk and alpha * R become table sums
         const uint32_t slab = (uint32_t)std::min<uint64_t>(N, 4096);
         void* tmp = nullptr;
         // an optimisation, not a requirement: where the HBM is not there (several contexts on one device, a small card) the per-proof
         // tables of R serve every proof
-        if (hipMalloc(&c->ktab, sizeof(uint32_t) * KTAB_KEY_WORDS * N) == hipSuccess && hipMalloc(&c->ktab_ok, N) == hipSuccess &&
+        if (hipMalloc(&R.ktab, sizeof(uint32_t) * KTAB_KEY_WORDS * N) == hipSuccess && hipMalloc(&R.ktab_ok, N) == hipSuccess &&
             hipMalloc(&tmp, ktab_temp_bytes(N, slab)) == hipSuccess) {
-            launch_ktab_build(c->stream, ring, N, c->ktab, c->ktab_ok, tmp, slab);
+            launch_ktab_build(c->stream, ring, N, R.ktab, R.ktab_ok, tmp, slab);
             hipError_t e = hipStreamSynchronize(c->stream);
             if (e != hipSuccess) {
                 hipFree(tmp);
@@ -313,23 +314,55 @@ static zk_status set_ring_common(zk_ctx* c, const uint8_t* d_keys, uint64_t nkey
             }
         } else {
             (void)hipGetLastError();
-            hipFree(c->ktab), hipFree(c->ktab_ok);
-            c->ktab = nullptr, c->ktab_ok = nullptr;
+            hipFree(R.ktab), hipFree(R.ktab_ok);
+            R.ktab = nullptr, R.ktab_ok = nullptr;
         }
         if (tmp) HIPCHK(c, hipFree(tmp));
     }
     {   // digest of the padded ring: what the hardened mode hashes into the membership challenge
-        if (!c->ring_digest) HIPCHK(c, hipMalloc(&c->ring_digest, 32));
+        HIPCHK(c, hipMalloc(&R.ring_digest, 32));
         uint32_t* leaves = nullptr;
         HIPCHK(c, hipMalloc(&leaves, 32 * ((N + 255) / 256)));
-        launch_ring_digest(c->stream, ring, N, leaves, c->ring_digest);
+        launch_ring_digest(c->stream, ring, N, leaves, R.ring_digest);
         HIPCHK(c, hipStreamSynchronize(c->stream));
         HIPCHK(c, hipFree(leaves));
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->N = N, c->n = n, c->nkeys = nkeys;
-    c->ws_C = 0;  // the workspace layout depends on the ring
+    R.N = N, R.n = n, R.nkeys = nkeys;
     return ZK_OK;
+}
+static Ring* find_ring(zk_ctx* c, uint32_t id) {
+    for (auto& R : c->rings)
+        if (R.live && R.id == id) return &R;
+    return nullptr;
+}
+Ring* zk_resident_ring(zk_ctx* c, uint32_t id) { return find_ring(c, id); }
+static Ring* free_slot(zk_ctx* c) {
+    for (auto& R : c->rings)
+        if (!R.live) return &R;
+    return nullptr;
+}
+// zk_ctx_set_ring: (re)builds the active ring in place (its id stays); a context without an active ring gets a new one and makes it active
+static zk_status set_ring_common(zk_ctx* c, const uint8_t* d_keys, uint64_t nkeys) {
+    if (c->stream_busy) {   // the queued jobs read the ring, table E and the key tables this call would free
+        c->err = "streamed jobs are in flight on this context (zk_prove_wait / zk_verify_wait them first)";
+        return ZK_E_ARG;
+    }
+    uint32_t n = 0;
+    while (((uint64_t)1 << n) < nkeys) n++;
+    if (n < 1 || n > ZK_MAXN - 4) return ZK_E_ARG;
+    Ring* R = c->active >= 0 ? &c->rings[c->active] : free_slot(c);
+    if (!R) {
+        c->err = "ZK_MAX_RINGS rings are resident and none is active (zk_ctx_drop_ring one first)";
+        return ZK_E_ARG;
+    }
+    if (c->active < 0) {
+        *R = Ring{};
+        R->id = c->next_ring_id++, R->live = true;
+        c->active = (int)(R - c->rings), c->ring = R;
+    }
+    c->ws_C = 0;  // the workspace layout depends on the ring
+    return build_ring(c, *R, d_keys, nkeys, true);
 }
 extern "C" zk_status zk_ctx_set_ring_device(zk_ctx* c, const void* d_keys, uint64_t nkeys) {
     if (!c || !d_keys || nkeys < 2) return ZK_E_ARG;
@@ -345,6 +378,85 @@ extern "C" zk_status zk_ctx_set_ring(zk_ctx* c, const uint8_t* keys, uint64_t nk
     zk_status s = set_ring_common(c, d, nkeys);
     hipFree(d);
     return s;
+}
+// ---- resident rings (include/zkattest.h: zk_ctx_add_ring)
+static zk_status add_ring_common(zk_ctx* c, const uint8_t* d_keys, uint64_t nkeys, uint32_t* id) {
+    if (c->stream_busy) return busy_refusal(c);
+    Ring* R = free_slot(c);
+    if (!R) {
+        c->err = "ZK_MAX_RINGS rings are resident already";
+        return ZK_E_ARG;
+    }
+    *R = Ring{};
+    const uint32_t new_id = c->next_ring_id++;   // (taken also when the build fails: the shard contexts of a pool stay in step)
+    zk_status zs = build_ring(c, *R, d_keys, nkeys, false);
+    if (zs) {
+        free_ring(*R);
+        *R = Ring{};
+        return zs;
+    }
+    R->id = new_id, R->live = true;
+    *id = R->id;
+    return ZK_OK;
+}
+extern "C" zk_status zk_ctx_add_ring_device(zk_ctx* c, const void* d_keys, uint64_t nkeys, uint32_t* ring) {
+    if (!c || !d_keys || !ring || nkeys < 2) return ZK_E_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    return add_ring_common(c, (const uint8_t*)d_keys, nkeys, ring);
+}
+extern "C" zk_status zk_ctx_add_ring(zk_ctx* c, const uint8_t* keys, uint64_t nkeys, uint32_t* ring) {
+    if (!c || !keys || !ring || nkeys < 2) return ZK_E_ARG;
+    if (c->stream_busy) return busy_refusal(c);
+    HIPCHK(c, hipSetDevice(c->device));
+    uint8_t* d;
+    HIPCHK(c, hipMalloc(&d, 32 * nkeys));
+    if (hipMemcpy(d, keys, 32 * nkeys, hipMemcpyHostToDevice) != hipSuccess) {
+        hipFree(d);
+        c->err = "ring upload failed";
+        return ZK_E_DEVICE;
+    }
+    zk_status s = add_ring_common(c, d, nkeys, ring);
+    hipFree(d);
+    return s;
+}
+extern "C" zk_status zk_ctx_use_ring(zk_ctx* c, uint32_t ring) {
+    if (!c) return ZK_E_ARG;
+    if (c->stream_busy) return busy_refusal(c);
+    Ring* R = find_ring(c, ring);
+    if (!R) {
+        c->err = "no resident ring has this id";
+        return ZK_E_ARG;
+    }
+    c->active = (int)(R - c->rings), c->ring = R;   // the workspaces are bound to it by the next call (ensure_workspace)
+    return ZK_OK;
+}
+extern "C" zk_status zk_ctx_drop_ring(zk_ctx* c, uint32_t ring) {
+    if (!c) return ZK_E_ARG;
+    if (c->stream_busy) return busy_refusal(c);
+    Ring* R = find_ring(c, ring);
+    if (!R || (c->active >= 0 && R == &c->rings[c->active])) {
+        c->err = R ? "the active ring cannot be dropped" : "no resident ring has this id";
+        return ZK_E_ARG;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    for (auto& L : c->pl)   // (no lane keeps a pointer into a ring it is not bound to past a call; cleared all the same)
+        if (L.W.ring.p == R->ring_mem) L.W.ring = Soa{nullptr, 0}, L.W.ktab = nullptr, L.W.ktab_ok = nullptr, L.W.gk_etab = nullptr, L.W.gk_kdig = nullptr, L.W.gk_edig = nullptr;
+    free_ring(*R);
+    *R = Ring{};
+    return ZK_OK;
+}
+extern "C" zk_status zk_ring_info(zk_ctx* c, uint32_t ring, uint64_t* n_keys, uint32_t* log_n, uint32_t* flags, uint64_t* generation) {
+    if (!c) return ZK_E_ARG;
+    if (c->stream_busy) return busy_refusal(c);
+    const Ring* R = find_ring(c, ring);
+    if (!R) return ZK_E_ARG;
+    if (n_keys) *n_keys = R->nkeys;
+    if (log_n) *log_n = R->n;
+    if (flags)
+        *flags = (R->gk_etab ? ZK_RING_TABLE_E : 0u) | (R->gk_kdig ? ZK_RING_DIGIT_PLANES : 0u) | (R->gk_edig ? ZK_RING_TABLE_E_DIGITS : 0u) |
+                 (R->ktab ? ZK_RING_KEY_TABLES : 0u) | (c->active >= 0 && R == &c->rings[c->active] ? ZK_RING_ACTIVE : 0u);
+    if (generation) *generation = R->generation;
+    return ZK_OK;
 }
 extern "C" zk_status zk_keys_to_ints(zk_ctx* c, uint64_t n, const uint8_t* pk, uint8_t* out, int32_t* st) {
     if (!c || !pk || !out || !st || !n) return ZK_E_ARG;
@@ -405,10 +517,10 @@ extern "C" zk_status zk_ctx_set_verify_level(zk_ctx* c, uint32_t mode) {
 }
 extern "C" zk_status zk_ring_digest(zk_ctx* c, uint8_t digest[32]) {
     if (!c || !digest) return ZK_E_ARG;
-    if (!c->N || !c->ring_digest) return ZK_E_BUFFER;
+    if (!c->ring->N || !c->ring->ring_digest) return ZK_E_BUFFER;
     HIPCHK(c, hipSetDevice(c->device));
     uint32_t w[8];
-    HIPCHK(c, hipMemcpy(w, c->ring_digest, 32, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(w, c->ring->ring_digest, 32, hipMemcpyDeviceToHost));
     for (int i = 0; i < 8; i++)
         for (int j = 0; j < 4; j++) digest[4 * i + j] = (uint8_t)(w[i] >> (24 - 8 * j));
     return ZK_OK;
@@ -439,8 +551,8 @@ extern "C" zk_status zk_ctx_set_lanes(zk_ctx* c, uint32_t lanes) {
     return ZK_OK;
 }
 extern "C" uint64_t zk_proof_max_size(const zk_ctx* c) {
-    if (!c || !c->params_set || !c->N) return 0;
-    return wire_proof_size(wire_make(c->wire == ZK_WIRE_ZKA1P), c->P.sec, c->n, c->P.sec);
+    if (!c || !c->params_set || !c->ring->N) return 0;
+    return wire_proof_size(wire_make(c->wire == ZK_WIRE_ZKA1P), c->P.sec, c->ring->n, c->P.sec);
 }
 
 // ------------------------------------------------------------------ workspace arena
@@ -453,7 +565,7 @@ static size_t carve(zk_ctx* c, Workspace& W, Soa& gk_am, uint8_t* base, uint32_t
     W.pkx = k.soa(C), W.pky = k.soa(C), W.pkxm = k.soa(C), W.pkym = k.soa(C);
     W.Rxm = k.soa(C), W.Rym = k.soa(C), W.Rx = k.soa(C), W.Ry = k.soa(C);
     W.Q = k.soa3(C), W.s1 = k.soa(C);
-    W.ktab = c->ktab, W.ktab_ok = c->ktab_ok;
+    W.ktab = c->ring->ktab, W.ktab_ok = c->ring->ktab_ok;
     W.kt_use = (uint8_t*)k.take((size_t)C), W.kt_key = (uint32_t*)k.take(4 * (size_t)C), W.r_zero = (uint8_t*)k.take((size_t)C);
     W.u1m = k.soa(C), W.u2m = k.soa(C);
     W.rtab = (uint32_t*)k.take(sizeof(uint32_t) * (size_t)std::max(rtab_words(RTAB_PROVE_BITS), rtab_words(RTAB_VERIFY_BITS)) * C);
@@ -481,14 +593,14 @@ static size_t carve(zk_ctx* c, Workspace& W, Soa& gk_am, uint8_t* base, uint32_t
     // fallback for tiny rings ping-pongs G*N elements between gk_bufA and gk_bufB
     uint64_t g = std::max<uint64_t>(1, std::min<uint64_t>(C, ((uint64_t)1 << 16) / N));
     W.gk_group = (uint32_t)g;
-    uint32_t T = c->gk_etab ? 8 : std::min<uint32_t>(n, 12);
+    uint32_t T = c->ring->gk_etab ? 8 : std::min<uint32_t>(n, 12);
     uint64_t tile_elems = (uint64_t)(T + 1) * C * (N >> T);
-    W.gk_etab = c->gk_etab;
-    W.gk_kdig = c->gk_mfma ? c->gk_kdig : nullptr;
-    W.gk_edig = c->gk_mfma ? c->gk_edig : nullptr;
-    W.gk_adig = c->gk_edig ? (int8_t*)k.take(gkm_asub_frag_bytes(C)) : nullptr;
+    W.gk_etab = c->ring->gk_etab;
+    W.gk_kdig = c->gk_mfma ? c->ring->gk_kdig : nullptr;
+    W.gk_edig = c->gk_mfma ? c->ring->gk_edig : nullptr;
+    W.gk_adig = c->ring->gk_edig ? (int8_t*)k.take(gkm_asub_frag_bytes(C)) : nullptr;
     W.gk_toff = (uint32_t*)k.take(4 * 264);
-    W.gk_asub = c->gk_etab ? (uint32_t*)k.take(36 * 256 * (size_t)C) : nullptr;
+    W.gk_asub = c->ring->gk_etab ? (uint32_t*)k.take(36 * 256 * (size_t)C) : nullptr;
     W.gk_order = (uint32_t*)k.take(4 * (size_t)C);
     W.gk_goff = (uint32_t*)k.take(4 * 264);
     W.gk_bufA = (uint32_t*)k.take(36 * std::max<uint64_t>(g * N, tile_elems));
@@ -507,39 +619,50 @@ static size_t carve(zk_ctx* c, Workspace& W, Soa& gk_am, uint8_t* base, uint32_t
         if (lb_bytes >= big_msg + (size_t)C * blocks * 256) W.exph_big_msg = lb_begin, W.exph_big_wk = (uint32_t*)(lb_begin ? lb_begin + big_msg : nullptr), W.exph_big_cap = C;
         else W.exph_big_msg = nullptr, W.exph_big_wk = nullptr, W.exph_big_cap = 0;
     }
-    W.ring = Soa{c->ring_mem, (uint32_t)N};
+    W.ring = Soa{c->ring->ring_mem, (uint32_t)N};
     return k.off + 256;
 }
 // hipMalloc for a workspace that gives up the OPTIONAL per-ring tables before it gives up itself: the per-key tables (35 GB at 2^17 keys)
-// are taken at zk_ctx_set_ring, before anybody knows how large the chunks will be; if a lane's arena no longer fits, the tables go and
-// every proof takes the per-proof tables of R -- slower, same bytes.
+// are taken when a ring is built, before anybody knows how large the chunks will be; if a lane's arena no longer fits, the tables go and
+// every proof takes the per-proof tables of R -- slower, same bytes.  Order: the key tables of the resident rings the running call is not bound to
+// first (slot order), then those of the bound ring; every lane workspace that pointed at a shed table is rebound to none.
 hipError_t malloc_or_shed(zk_ctx* c, void** p, size_t bytes) {
     hipError_t e = hipMalloc(p, bytes);
-    if (e == hipSuccess || !c->ktab) return e;
-    (void)hipGetLastError();
-    (void)hipDeviceSynchronize();
-    hipFree(c->ktab), hipFree(c->ktab_ok);
-    c->ktab = nullptr, c->ktab_ok = nullptr;
-    for (auto& L : c->pl) L.W.ktab = nullptr, L.W.ktab_ok = nullptr;
-    return hipMalloc(p, bytes);
+    if (e == hipSuccess) return e;
+    auto shed = [&](Ring& R) {
+        (void)hipGetLastError();
+        (void)hipDeviceSynchronize();
+        for (auto& L : c->pl)
+            if (L.W.ktab == R.ktab) L.W.ktab = nullptr, L.W.ktab_ok = nullptr;
+        hipFree(R.ktab), hipFree(R.ktab_ok);
+        R.ktab = nullptr, R.ktab_ok = nullptr;
+        return hipMalloc(p, bytes);
+    };
+    for (auto& R : c->rings)
+        if (R.live && R.ktab && &R != c->ring && (e = shed(R)) == hipSuccess) return e;
+    if (!c->ring->ktab) return e;
+    return shed(*c->ring);
 }
 zk_status ensure_workspace(zk_ctx* c, uint32_t C, uint32_t nlanes) {
-    uint32_t sec = plan_sec(c), n = c->n;
-    if (!(c->ws_C == C && c->ws_sec == sec && c->ws_n == n)) {
+    uint32_t sec = plan_sec(c), n = c->ring->n;
+    // the layout follows the bound ring's n and whether it has table E and its digit planes; two rings that agree on these share it as carved (the ring's
+    // pointers are bound below, on every call)
+    const bool etab = c->ring->gk_etab != nullptr, edig = c->ring->gk_edig != nullptr;
+    if (!(c->ws_C == C && c->ws_sec == sec && c->ws_n == n && c->ws_etab == etab && c->ws_edig == edig)) {
         for (auto& L : c->pl) L.ready = false;
-        c->ws_C = C, c->ws_sec = sec, c->ws_n = n;
+        c->ws_C = C, c->ws_sec = sec, c->ws_n = n, c->ws_etab = etab, c->ws_edig = edig;
     }
     for (uint32_t l = 0; l < nlanes && l < ZK_MAX_LANES; l++) {
         auto& L = c->pl[l];
         if (!L.ready) {
-            size_t need = carve(c, L.W, L.gk_am, nullptr, C, sec, n, c->N);
+            size_t need = carve(c, L.W, L.gk_am, nullptr, C, sec, n, c->ring->N);
             if (need > L.arena_bytes) {
                 if (L.arena) HIPCHK(c, hipFree(L.arena));
                 L.arena = nullptr, L.arena_bytes = 0;
                 HIPCHK(c, malloc_or_shed(c, &L.arena, need));
                 L.arena_bytes = need;
             }
-            carve(c, L.W, L.gk_am, (uint8_t*)L.arena, C, sec, n, c->N);
+            carve(c, L.W, L.gk_am, (uint8_t*)L.arena, C, sec, n, c->ring->N);
             if (!L.d_totals) HIPCHK(c, hipMalloc(&L.d_totals, 64));
             const size_t hs = 64 + 16 * ((size_t)C + 2);
             if (hs > L.h_scan_bytes) {
@@ -550,12 +673,13 @@ zk_status ensure_workspace(zk_ctx* c, uint32_t C, uint32_t nlanes) {
             }
             L.ready = true;
         }
-        L.W.ring = Soa{c->ring_mem, (uint32_t)c->N};
-        L.W.hardened = c->mode == ZK_MODE_HARDENED, L.W.ring_digest = c->ring_digest;
+        L.W.ring = Soa{c->ring->ring_mem, (uint32_t)c->ring->N};
+        L.W.hardened = c->mode == ZK_MODE_HARDENED, L.W.ring_digest = c->ring->ring_digest;
         L.W.wire = wire_make(c->wire == ZK_WIRE_ZKA1P);
-        L.W.ktab = c->ktab, L.W.ktab_ok = c->ktab_ok;
-        L.W.gk_kdig = c->gk_mfma ? c->gk_kdig : nullptr;
-        L.W.gk_edig = c->gk_mfma && L.W.gk_adig ? c->gk_edig : nullptr;
+        L.W.ktab = c->ring->ktab, L.W.ktab_ok = c->ring->ktab_ok;
+        L.W.gk_etab = c->ring->gk_etab;
+        L.W.gk_kdig = c->gk_mfma ? c->ring->gk_kdig : nullptr;
+        L.W.gk_edig = c->gk_mfma && L.W.gk_adig ? c->ring->gk_edig : nullptr;
     }
     return ZK_OK;
 }
@@ -1050,7 +1174,7 @@ zk_status ProveJob::stage2(uint64_t chunk_no) {
 static zk_status prove_device(zk_ctx* c, uint64_t B, const uint8_t* d_msg, const uint8_t* d_sig, const uint8_t* d_pk, const uint32_t* d_which,
                               int rng_mode, const uint8_t* d_rng, uint64_t stride, uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_off,
                               int32_t* d_status, uint8_t* host_sink = nullptr, hipEvent_t inputs_ready = nullptr) {
-    if (!c->params_set || !c->N) return ZK_E_BUFFER;
+    if (!c->params_set || !c->ring->N) return ZK_E_BUFFER;
     if (rng_mode != ZK_RNG_SEED && rng_mode != ZK_RNG_STREAM) return ZK_E_ARG;
     if (c->stream_busy) {
         c->err = "streamed jobs are in flight on this context (zk_prove_wait / zk_verify_wait them first)";
@@ -1123,7 +1247,7 @@ extern "C" zk_status zk_prove_batch(zk_ctx* c, uint64_t B, const uint8_t* msg, c
                                     const zk_rng* rng, uint8_t* out, uint64_t out_cap, uint64_t* out_off, int32_t* status) {
     if (!c || !rng || !out_off || !status || (B && (!msg || !sig || !pk || !which || !rng->data || !out))) return ZK_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->params_set || !c->N) return ZK_E_BUFFER;
+    if (!c->params_set || !c->ring->N) return ZK_E_BUFFER;
     if (c->stream_busy) {
         c->err = "streamed jobs are in flight on this context (zk_prove_wait / zk_verify_wait them first)";
         return ZK_E_ARG;

@@ -357,8 +357,10 @@ extern "C" zk_status zk_pool_set_verify_level(zk_pool* p, uint32_t mode) {
     return ZK_OK;
 }
 
-extern "C" zk_status zk_pool_set_ring(zk_pool* p, const uint8_t* keys, uint64_t nkeys) {
-    if (!p || !keys || nkeys < 2) return ZK_E_ARG;
+// The ring's keys on every shard device: one PCIe upload to device 0, then an RCCL broadcast or peer copies.  f(i, d_keys_i) runs on every shard
+// (pool_each) and the staging buffers are freed behind it; the calling thread's current device is restored on every exit path.
+template <class F>
+static zk_status pool_with_ring_keys(zk_pool* p, const uint8_t* keys, uint64_t nkeys, F f) {
     const int G = (int)p->ctx.size();
     const size_t bytes = 32 * (size_t)nkeys;
     std::vector<void*> d(G, nullptr);
@@ -441,9 +443,53 @@ extern "C" zk_status zk_pool_set_ring(zk_pool* p, const uint8_t* keys, uint64_t 
             p->transport = "peer-copy";
         }
     }
-    zk_status zs = pool_each(p, [&](int i) { return zk_ctx_set_ring_device(p->ctx[i], d[i], nkeys); });   // pad, limb conversion, table E
+    zk_status zs = pool_each(p, [&](int i) { return f(i, d[i]); });
     release();
     return zs;
+}
+extern "C" zk_status zk_pool_set_ring(zk_pool* p, const uint8_t* keys, uint64_t nkeys) {
+    if (!p || !keys || nkeys < 2) return ZK_E_ARG;
+    return pool_with_ring_keys(p, keys, nkeys, [&](int i, void* d) { return zk_ctx_set_ring_device(p->ctx[i], d, nkeys); });   // pad, limb conversion, table E
+}
+// ---- resident rings on every shard context, with the same id on each (zk_ctx_add_ring)
+extern "C" zk_status zk_pool_add_ring(zk_pool* p, const uint8_t* keys, uint64_t nkeys, uint32_t* ring) {
+    if (!p || !keys || !ring || nkeys < 2) return ZK_E_ARG;
+    const int G = (int)p->ctx.size();
+    for (int i = 0; i < G; i++)
+        if (p->ctx[i]->stream_busy) return ZK_E_ARG;
+    std::vector<uint32_t> id(G, 0);
+    std::vector<zk_status> st(G, ZK_E_ARG);
+    zk_status zs = pool_with_ring_keys(p, keys, nkeys, [&](int i, void* d) { return st[i] = zk_ctx_add_ring_device(p->ctx[i], d, nkeys, &id[i]); });
+    for (int i = 1; i < G && !zs; i++)
+        if (id[i] != id[0]) {   // (the shards' rings were added and dropped through the pool only: cannot happen)
+            p->err = "shard contexts disagree on the next ring id";
+            zs = ZK_E_ARG;
+        }
+    if (zs) {   // the shards that built the ring drop it again
+        for (int i = 0; i < G; i++)
+            if (st[i] == ZK_OK) (void)zk_ctx_drop_ring(p->ctx[i], id[i]);
+        return zs;
+    }
+    *ring = id[0];
+    return ZK_OK;
+}
+extern "C" zk_status zk_pool_use_ring(zk_pool* p, uint32_t ring) {
+    if (!p) return ZK_E_ARG;
+    for (auto c : p->ctx)   // every shard knows the id and has no job queued before any of them switches
+        if (c->stream_busy || zk_ring_info(c, ring, nullptr, nullptr, nullptr, nullptr)) return ZK_E_ARG;
+    for (auto c : p->ctx)
+        if (zk_status zs = zk_ctx_use_ring(c, ring)) return zs;
+    return ZK_OK;
+}
+extern "C" zk_status zk_pool_drop_ring(zk_pool* p, uint32_t ring) {
+    if (!p) return ZK_E_ARG;
+    for (auto c : p->ctx) {
+        uint32_t flags = 0;
+        if (c->stream_busy || zk_ring_info(c, ring, nullptr, nullptr, &flags, nullptr) || (flags & ZK_RING_ACTIVE)) return ZK_E_ARG;
+    }
+    for (auto c : p->ctx)
+        if (zk_status zs = zk_ctx_drop_ring(c, ring)) return zs;
+    return ZK_OK;
 }
 
 extern "C" zk_status zk_pool_prove_batch(zk_pool* p, uint64_t B, const uint8_t* msg, const uint8_t* sig, const uint8_t* pk, const uint32_t* which,
@@ -522,6 +568,26 @@ extern "C" zk_status zk_pool_verify_batch(zk_pool* p, uint64_t B, const uint8_t*
             off[j + 1] = off[j] + proof_len[first + j];
         }
         return zk_verify_batch(p->ctx[i], cnt, msg + 32 * first, proofs + base, off.data(), vseeds ? vseeds + 32 * first : nullptr, ok + first, status + first);
+    });
+}
+
+extern "C" zk_status zk_pool_verify_batch_rings(zk_pool* p, uint64_t B, const uint8_t* msg, const uint8_t* proofs, const uint64_t* proof_off, const uint64_t* proof_len,
+                                                const uint32_t* ring_ids, const uint8_t* vseeds, uint8_t* ok, int32_t* status) {
+    if (!p || (B && (!msg || !proofs || !proof_off || !proof_len || !ring_ids || !ok || !status))) return ZK_E_ARG;
+    return pool_each(p, [&](int i) -> zk_status {
+        uint64_t first, cnt;
+        zk_pool_shard(p, B, i, &first, &cnt);
+        if (!cnt) return ZK_OK;
+        std::vector<uint64_t> off(cnt + 1);   // (packing rules of zk_pool_verify_batch)
+        const uint64_t base = proof_off[first];
+        if (base & 3) return ZK_E_ARG;
+        for (uint64_t j = 0; j < cnt; j++) {
+            if (proof_off[first + j] - base != (j ? off[j] : 0)) return ZK_E_ARG;
+            off[j] = proof_off[first + j] - base;
+            off[j + 1] = off[j] + proof_len[first + j];
+        }
+        return zk_verify_batch_rings(p->ctx[i], cnt, msg + 32 * first, proofs + base, off.data(), ring_ids + first, vseeds ? vseeds + 32 * first : nullptr, ok + first,
+                                     status + first);
     });
 }
 

@@ -144,7 +144,7 @@ static void unlink_job(zk_ctx* c, zk_job* j) {
 }
 
 static zk_status stream_common(zk_ctx* c, int kind) {
-    if (!c->params_set || !c->N) return ZK_E_BUFFER;
+    if (!c->params_set || !c->ring->N) return ZK_E_BUFFER;
     if (c->jobs.size() >= ZK_MAX_JOBS) {
         c->err = "too many streamed jobs in flight (wait for the oldest one first)";
         return ZK_E_ARG;
@@ -153,7 +153,7 @@ static zk_status stream_common(zk_ctx* c, int kind) {
         c->err = "prove and verify jobs cannot be in flight together on one context";
         return ZK_E_ARG;
     }
-    if (!c->jobs.empty() && (!(c->ws_C == c->chunk && c->ws_sec == plan_sec(c) && c->ws_n == c->n) || (c->jobs[0]->kind ? c->jobs[0]->vj.NL : c->jobs[0]->pj.NL) != c->lanes ||
+    if (!c->jobs.empty() && (!(c->ws_C == c->chunk && c->ws_sec == plan_sec(c) && c->ws_n == c->ring->n) || (c->jobs[0]->kind ? c->jobs[0]->vj.NL : c->jobs[0]->pj.NL) != c->lanes ||
                               (kind == 1 && c->vs_groups != c->verify_groups))) {
         c->err = "chunk / lanes / parameters / ring changed while streamed jobs are in flight";
         return ZK_E_ARG;
@@ -446,7 +446,7 @@ extern "C" zk_status zk_verify_submit(zk_ctx* c, uint64_t B, const uint8_t* msg,
     }
     if (!per_proof) return verify_submit(c, B, msg, proofs, off, vseeds, ok, status, job);
     // per-proof verify levels: the headers, read here, decide whether the job joins the queued plan
-    if (!c->params_set || !c->N) return ZK_E_BUFFER;
+    if (!c->params_set || !c->ring->N) return ZK_E_BUFFER;
     const uint32_t lvl = host_level_census(c, B, proofs, off), L = lvl == LV_NONE ? c->P.sec : lvl;
     bool defer = lvl == LV_MIXED || L < VK || (!c->jobs.empty() && (!c->v_sec_on || c->v_sec != L));
     for (zk_job* q : c->jobs) defer = defer || q->deferred;

@@ -87,7 +87,7 @@ static size_t vcarve(VWork& V, Soa& res, Soa& res2, MsmBuf& M, PMsmBuf& PM, uint
     return k.off + 256;
 }
 zk_status ensure_vworkspace(zk_ctx* c, uint32_t C, uint32_t nlanes) {
-    uint32_t sec = plan_sec(c), n = c->n;
+    uint32_t sec = plan_sec(c), n = c->ring->n;
     const bool want_msm = c->verify_batch_min && C >= c->verify_batch_min;   // the chunk-wide sums never run on smaller chunks
     const bool want_pm = want_msm && c->p256_batch_min && C >= c->p256_batch_min;
     if (!(c->vs_C == C && c->vs_sec == sec && c->vs_n == n && c->vs_msm == want_msm && c->vs_pm == want_pm && c->vs_groups == c->verify_groups)) {
@@ -97,14 +97,14 @@ zk_status ensure_vworkspace(zk_ctx* c, uint32_t C, uint32_t nlanes) {
     for (uint32_t l = 0; l < nlanes && l < ZK_MAX_LANES; l++) {
         auto& L = c->vl[l];
         if (L.ready) continue;
-        size_t need = vcarve(L.V, L.res, L.res2, L.M, L.PM, nullptr, C, sec, n, c->N, want_msm, want_pm, c->verify_groups);
+        size_t need = vcarve(L.V, L.res, L.res2, L.M, L.PM, nullptr, C, sec, n, c->ring->N, want_msm, want_pm, c->verify_groups);
         if (need > L.arena_bytes) {
             if (L.arena) HIPCHK(c, hipFree(L.arena));
             L.arena = nullptr, L.arena_bytes = 0;
             HIPCHK(c, malloc_or_shed(c, &L.arena, need));
             L.arena_bytes = need;
         }
-        vcarve(L.V, L.res, L.res2, L.M, L.PM, (uint8_t*)L.arena, C, sec, n, c->N, want_msm, want_pm, c->verify_groups);
+        vcarve(L.V, L.res, L.res2, L.M, L.PM, (uint8_t*)L.arena, C, sec, n, c->ring->N, want_msm, want_pm, c->verify_groups);
         if (!L.h_msm) HIPCHK(c, hipHostMalloc((void**)&L.h_msm, 1024, hipHostMallocMapped | hipHostMallocCoherent));
         if (!L.aux_fork) HIPCHK(c, hipEventCreateWithFlags(&L.aux_fork, hipEventDisableTiming));
         for (int i = 0; i < V_AUX_STREAMS; i++) {
@@ -114,7 +114,7 @@ zk_status ensure_vworkspace(zk_ctx* c, uint32_t C, uint32_t nlanes) {
         L.M.host = L.h_msm;
         L.ready = true;
     }
-    for (uint32_t l = 0; l < nlanes && l < ZK_MAX_LANES; l++) c->vl[l].V.hardened = c->mode == ZK_MODE_HARDENED, c->vl[l].V.ring_digest = c->ring_digest;
+    for (uint32_t l = 0; l < nlanes && l < ZK_MAX_LANES; l++) c->vl[l].V.hardened = c->mode == ZK_MODE_HARDENED, c->vl[l].V.ring_digest = c->ring->ring_digest;
     return ZK_OK;
 }
 
@@ -357,7 +357,7 @@ static zk_status small_chunk_p256(zk_ctx* c, bool timed, uint32_t lane, uint32_t
 static zk_status per_proof_range(zk_ctx* c, bool timed, hipStream_t s, uint32_t lane, const Workspace& W, const VWork& V, uint32_t p0, uint32_t p1, uint32_t range_no, uint32_t tsplit,
                                  hipEvent_t release = nullptr, uint32_t chunk_cnt = 0) {
     const DevParams& P = c->P;
-    const uint32_t nq = (c->n + 1) / 2;
+    const uint32_t nq = (c->ring->n + 1) / 2;
     const uint32_t np = p1 - p0;
     auto terms_at = [](VTerms t, size_t o) {
         t.pts += o * VT_ENTRY_WORDS, t.sc.p += o, t.tab += o * 8 * 36, t.dig += o;
@@ -466,7 +466,7 @@ zk_status VerifyJob::stage2a(uint64_t chunk_no) {
     const uint64_t first = plan[chunk_no].first;
     const uint32_t cnt = plan[chunk_no].cnt;
     const uint32_t lane = lane_of(chunk_no);
-    const uint32_t nq = (c->n + 1) / 2;
+    const uint32_t nq = (c->ring->n + 1) / 2;
     Workspace& W = c->pl[lane].W;
     VWork& V = c->vl[lane].V;
     const MsmBuf& M = c->vl[lane].M;
@@ -539,7 +539,7 @@ zk_status VerifyJob::stage2b(uint64_t chunk_no) {
     hipStream_t s = c->pl[lane].stream;
     if (memb_only) {   // membership sums of every proof, one per proof, and the verdict
         MaybeScope t(timed, c, "v_straus_tom", s);
-        const uint32_t nq = (c->n + 1) / 2;
+        const uint32_t nq = (c->ring->n + 1) / 2;
         launch_v_straus(s, V.gk_terms, cnt * nq, V.C * nq, 4, 4, V.gk_acc, nullptr, nullptr);
         launch_v_straus(s, V.misc_terms, cnt, 3 * V.C, 1, 0, V.misc_acc, nullptr, nullptr);
         launch_tom_commit(s, P, W.lc, cnt, 1, 4 * W.n);
@@ -651,7 +651,7 @@ zk_status make_default_vseeds(zk_ctx* c, uint64_t B, uint8_t* d_seeds /* 32 * B 
 
 static zk_status verify_device(zk_ctx* c, uint64_t B, const uint8_t* d_msg, const uint8_t* d_proofs, const uint64_t* d_off, const uint8_t* d_vseeds, uint8_t* d_ok,
                                int32_t* d_status, const uint8_t* host_src = nullptr, const uint64_t* host_off = nullptr, bool inputs_on_stream = false) {
-    if (!c->params_set || !c->N) return ZK_E_BUFFER;
+    if (!c->params_set || !c->ring->N) return ZK_E_BUFFER;
     if (plan_sec(c) < VK && !c->v_sec_on) return ZK_E_SECLEVEL;   // (a per-proof-mode call at a level below VK verifies membership only)
     if (B == 0) return ZK_OK;
     if (c->stream_busy) {
@@ -776,13 +776,60 @@ static zk_status grow(zk_ctx* c, void** buf, size_t* have, size_t need) {   // g
     *have = need;
     return ZK_OK;
 }
+// One window of a partitioned batch: the n proofs sel[0 .. n) gathered into the window buffers (c->lb_buf for the bytes), verified as a batch of their
+// own with whatever ring and level the caller bound, their verdicts scattered back.  The partition's kernels are timed into *part_ms, the window's
+// families summed into *fam.
+struct WindowRun {
+    zk_ctx* c;
+    hipStream_t s;
+    bool timed;
+    hipEvent_t* ev;
+    float* part_ms;
+    std::vector<std::pair<const char*, float>>* fam;
+    const uint8_t *d_msg, *d_proofs;
+    const uint64_t* d_off;
+    const uint8_t* d_vseeds;
+    uint8_t* d_ok;
+    int32_t* d_st;
+    uint64_t* w_off;
+    uint8_t *w_msg, *w_seeds, *w_ok;
+    int32_t* w_st;
+    uint64_t* h_total;   // page-locked
+    void lap() {
+        float ms = 0;
+        if (timed && hipEventElapsedTime(&ms, ev[2], ev[3]) == hipSuccess) *part_ms += ms;
+    }
+    zk_status run(const uint32_t* sel, uint32_t n) {
+        if (timed) HIPCHK(c, hipEventRecord(ev[2], s));
+        launch_lv_gather_meta(s, n, sel, d_off, d_msg, d_vseeds, w_off, w_msg, w_seeds);
+        HIPCHK(c, hipMemcpyAsync(h_total, w_off + n, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));   // the window's bytes: every length is bounded by its level (wire_level_class)
+        if (zk_status zs = grow(c, &c->lb_buf, &c->lb_bytes, *h_total + 64)) return zs;
+        launch_lv_gather_bytes(s, n, sel, d_off, d_proofs, w_off, (uint8_t*)c->lb_buf);
+        if (timed) HIPCHK(c, hipEventRecord(ev[3], s));
+        if (zk_status zs = verify_device(c, n, w_msg, (const uint8_t*)c->lb_buf, w_off, w_seeds, w_ok, w_st, nullptr, nullptr, true)) return zs;
+        lap();
+        for (auto& f : c->last_timing) {
+            bool found = false;
+            for (auto& g : *fam)
+                if (g.first == f.first) g.second += f.second, found = true;
+            if (!found) fam->push_back(f);
+        }
+        if (timed) HIPCHK(c, hipEventRecord(ev[2], s));
+        launch_lv_scatter(s, n, sel, w_ok, w_st, d_ok, d_st, 0);
+        if (timed) HIPCHK(c, hipEventRecord(ev[3], s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        lap();
+        return ZK_OK;
+    }
+};
 // A batch of device-resident proofs in per-proof mode.  The census (k_lv_census) classifies every proof and counts the classes; the host reads the
 // 130 counters back (the one read-back the mode adds to a call).  One level: the usual pipeline on the caller's buffers, planned at that level.
 // Several: a stable permutation by level, then per level windows of at most 2 x chunk x lanes proofs gathered into HBM (k_lv_gather_*), verified
 // like a batch of their own, their verdicts scattered back (k_lv_scatter); a proof whose header is malformed gets ZK_E_BAD_ENCODING directly.
 static zk_status verify_per_proof(zk_ctx* c, uint64_t B, const uint8_t* d_msg, const uint8_t* d_proofs, const uint64_t* d_off, const uint8_t* d_vseeds, uint8_t* d_ok,
                                   int32_t* d_st, bool inputs_on_stream) {
-    if (!c->params_set || !c->N) return ZK_E_BUFFER;
+    if (!c->params_set || !c->ring->N) return ZK_E_BUFFER;
     if (B == 0) return ZK_OK;
     if (c->stream_busy) {
         c->err = "streamed jobs are in flight on this context (zk_prove_wait / zk_verify_wait them first)";
@@ -861,35 +908,11 @@ static zk_status verify_per_proof(zk_ctx* c, uint64_t B, const uint8_t* d_msg, c
     c->timing_mode = timed ? ZK_TIMING_ON : ZK_TIMING_OFF;
     std::vector<std::pair<const char*, float>> fam;
     zk_status zs = ZK_OK;
+    WindowRun R{c, s, timed, ev, &lv_ms, &fam, d_msg, d_proofs, d_off, d_vseeds, d_ok, d_st, w_off, w_msg, w_seeds, w_ok, w_st, (uint64_t*)(c->h_lv + 2 * ZK_LV_CLASSES)};
     for (uint32_t l = 0; l <= ZK_MAXSEC && !zs; l++) {
         for (uint32_t w = 0; w < cnt[l] && !zs; w += Wp) {
-            const uint32_t n = std::min<uint32_t>(Wp, cnt[l] - w);
-            const uint32_t* sel = perm + start[l] + w;
-            if (timed) HIPCHK(c, hipEventRecord(ev[2], s));
-            launch_lv_gather_meta(s, n, sel, d_off, d_msg, d_vseeds, w_off, w_msg, w_seeds);
-            uint64_t* h_total = (uint64_t*)(c->h_lv + 2 * ZK_LV_CLASSES);
-            HIPCHK(c, hipMemcpyAsync(h_total, w_off + n, 8, hipMemcpyDeviceToHost, s));
-            HIPCHK(c, hipStreamSynchronize(s));   // the window's bytes: every length is bounded by its level (wire_level_class)
-            if ((zs = grow(c, &c->lb_buf, &c->lb_bytes, *h_total + 64))) break;
-            launch_lv_gather_bytes(s, n, sel, d_off, d_proofs, w_off, (uint8_t*)c->lb_buf);
-            if (timed) HIPCHK(c, hipEventRecord(ev[3], s));
-            {
-                VLevel g(c, l);
-                zs = verify_device(c, n, w_msg, (const uint8_t*)c->lb_buf, w_off, w_seeds, w_ok, w_st, nullptr, nullptr, true);
-            }
-            if (zs) break;
-            lap(2, 3);
-            for (auto& f : c->last_timing) {
-                bool found = false;
-                for (auto& g : fam)
-                    if (g.first == f.first) g.second += f.second, found = true;
-                if (!found) fam.push_back(f);
-            }
-            if (timed) HIPCHK(c, hipEventRecord(ev[2], s));
-            launch_lv_scatter(s, n, sel, w_ok, w_st, d_ok, d_st, 0);
-            if (timed) HIPCHK(c, hipEventRecord(ev[3], s));
-            HIPCHK(c, hipStreamSynchronize(s));
-            lap(2, 3);
+            VLevel g(c, l);
+            zs = R.run(perm + start[l] + w, std::min<uint32_t>(Wp, cnt[l] - w));
         }
     }
     c->timing_mode = timing_mode;
@@ -910,6 +933,204 @@ static zk_status verify_per_proof(zk_ctx* c, uint64_t B, const uint8_t* d_msg, c
     return ZK_OK;
 }
 
+// ------------------------------------------------------------------ mixed-ring verification (include/zkattest.h: zk_verify_batch_rings)
+Ring* zk_resident_ring(zk_ctx* c, uint32_t id);   // api.hip
+// The resident rings in slot order: the census classes a proof by the place of its id in rs.id
+static uint32_t ring_slots(zk_ctx* c, RingSlots& rs, Ring** slot) {
+    rs = RingSlots{};
+    for (auto& R : c->rings)
+        if (R.live && R.N) slot[rs.count] = &R, rs.id[rs.count++] = R.id;
+    return rs.count;
+}
+// Device-resident proofs and ring ids.  The census (k_rg_census) classes every proof by (ring slot, level class) and counts the classes; the host reads
+// RG_CLASSES counters back (the one read-back the call adds).  One ring and one level: the usual pipeline on the caller's buffers with that ring
+// bound (and, per-proof mode, planned at that level).  Otherwise a stable permutation by class, then per class windows of at most 2 x chunk x lanes
+// proofs gathered into HBM, verified with the class's ring bound and its level planned, and their verdicts scattered back; a proof whose id is not
+// resident gets ZK_E_ARG and a malformed header ZK_E_BAD_ENCODING directly.  The level split of verify_per_proof never runs inside a window: one
+// census of (ring, level) gives one permutation and one gather per class.
+static zk_status verify_rings_device(zk_ctx* c, uint64_t B, const uint8_t* d_msg, const uint8_t* d_proofs, const uint64_t* d_off, const uint32_t* d_ids,
+                                     const uint8_t* d_vseeds, uint8_t* d_ok, int32_t* d_st, bool inputs_on_stream) {
+    if (!c->params_set) return ZK_E_BUFFER;
+    if (B == 0) return ZK_OK;
+    if (c->stream_busy) {
+        c->err = "streamed jobs are in flight on this context (zk_prove_wait / zk_verify_wait them first)";
+        return ZK_E_ARG;
+    }
+    if (B > 0xffffffffull) return ZK_E_ARG;
+    const bool per_proof = c->verify_level == ZK_VERIFY_LEVEL_PER_PROOF;
+    RingSlots rs;
+    Ring* slot[ZK_MAX_RINGS] = {};
+    ring_slots(c, rs, slot);
+    const uint64_t nblk = (B + LV_BLOCK - 1) / LV_BLOCK;
+    auto carve = [&](Carver& k, uint16_t*& cls, uint32_t*& blk, uint32_t*& out, uint32_t*& perm) {
+        cls = (uint16_t*)k.take(2 * B), blk = (uint32_t*)k.take(4 * nblk * RG_CLASSES), out = (uint32_t*)k.take(8 * RG_CLASSES), perm = (uint32_t*)k.take(4 * B);
+    };
+    uint16_t* cls;
+    uint32_t *blk, *out, *perm;
+    Carver k0(nullptr);
+    carve(k0, cls, blk, out, perm);
+    if (zk_status zs = grow(c, &c->rg_buf, &c->rg_bytes, k0.off + 256)) return zs;
+    Carver k1((uint8_t*)c->rg_buf);
+    carve(k1, cls, blk, out, perm);
+    if (!c->h_rg) HIPCHK(c, hipHostMalloc((void**)&c->h_rg, 4 * RG_CLASSES + 64, hipHostMallocDefault));
+    if (!c->h_lv) HIPCHK(c, hipHostMalloc((void**)&c->h_lv, 4096, hipHostMallocDefault));
+    hipStream_t s = c->stream;
+    const bool timed = zk_timed(c, B);
+    hipEvent_t ev[4] = {};
+    struct Events {
+        hipEvent_t* e;
+        ~Events() {
+            for (int i = 0; i < 4; i++)
+                if (e[i]) hipEventDestroy(e[i]);
+        }
+    } ev_guard{ev};
+    if (timed)
+        for (auto& e : ev) HIPCHK(c, hipEventCreate(&e));
+    float part_ms = 0;
+    auto lap = [&](int i, int j) {
+        float ms = 0;
+        if (timed && hipEventElapsedTime(&ms, ev[i], ev[j]) == hipSuccess) part_ms += ms;
+    };
+    if (timed) HIPCHK(c, hipEventRecord(ev[0], s));
+    launch_rg_census(s, B, d_ids, rs, d_proofs, d_off, c->wire == ZK_WIRE_ZKA1P, per_proof, cls, blk, out);
+    if (timed) HIPCHK(c, hipEventRecord(ev[1], s));
+    HIPCHK(c, hipMemcpyAsync(c->h_rg, out, 4 * RG_CLASSES, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    lap(0, 1);
+    uint32_t cnt[RG_CLASSES], start[RG_CLASSES];
+    memcpy(cnt, c->h_rg, sizeof cnt);
+    uint32_t most = 0, used_slots = 0, last_slot = 0, levels_last = 0, level_last = c->P.sec;
+    for (uint32_t k = 0, run = 0; k < RG_CLASSES; k++) start[k] = run, run += cnt[k];
+    for (uint32_t r = 0; r < rs.count; r++) {
+        uint32_t any = 0, lv = 0, lvl = c->P.sec;
+        for (uint32_t l = 0; l < ZK_LV_CLASSES; l++) {
+            const uint32_t n = cnt[r * ZK_LV_CLASSES + l];
+            any += n;
+            if (n && l != ZK_LV_BAD) lv++, lvl = l, most = std::max(most, n);
+        }
+        if (any) used_slots++, last_slot = r, levels_last = lv, level_last = lvl;
+    }
+    if (!cnt[RG_UNKNOWN] && used_slots == 1 && levels_last <= 1) {   // the common case: one ring, one level -- the caller's buffers as they are
+        RingBind rb(c, slot[last_slot]);
+        std::optional<VLevel> level;
+        if (per_proof) level.emplace(c, level_last);
+        return verify_device(c, B, d_msg, d_proofs, d_off, d_vseeds, d_ok, d_st, nullptr, nullptr, inputs_on_stream);
+    }
+    if (!d_vseeds) {   // the verifier's own seeds for the whole batch, gathered with the proofs (the window calls must not draw their own)
+        if (zk_status zs = grow(c, &c->seed_buf, &c->seed_bytes, 32 * B + 32 * B / 4 + 4096)) return zs;
+        if (zk_status zs = make_default_vseeds(c, B, (uint8_t*)c->seed_buf, s)) return zs;
+        d_vseeds = (const uint8_t*)c->seed_buf;
+    }
+    if (timed) HIPCHK(c, hipEventRecord(ev[0], s));
+    launch_rg_perm(s, B, cls, blk, out, perm);
+    launch_lv_scatter(s, cnt[RG_UNKNOWN], perm + start[RG_UNKNOWN], nullptr, nullptr, d_ok, d_st, ZK_E_ARG);
+    for (uint32_t r = 0; r < rs.count; r++) {
+        const uint32_t k = r * ZK_LV_CLASSES + ZK_LV_BAD;
+        launch_lv_scatter(s, cnt[k], perm + start[k], nullptr, nullptr, d_ok, d_st, ZK_E_BAD_ENCODING);
+    }
+    if (timed) HIPCHK(c, hipEventRecord(ev[1], s));
+    const uint32_t Wp = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(most, 2ull * c->chunk * c->lanes));
+    auto wcarve = [&](Carver& k, uint64_t*& w_off, uint8_t*& w_msg, uint8_t*& w_seeds, uint8_t*& w_ok, int32_t*& w_st) {
+        w_off = (uint64_t*)k.take(8 * ((size_t)Wp + 1)), w_msg = (uint8_t*)k.take(32 * (size_t)Wp), w_seeds = (uint8_t*)k.take(32 * (size_t)Wp);
+        w_ok = (uint8_t*)k.take(Wp), w_st = (int32_t*)k.take(4 * (size_t)Wp);
+    };
+    uint64_t* w_off;
+    uint8_t *w_msg, *w_seeds, *w_ok;
+    int32_t* w_st;
+    Carver w0(nullptr);
+    wcarve(w0, w_off, w_msg, w_seeds, w_ok, w_st);
+    // (the ring windows share lw_buf / lb_buf with the level windows: nothing below runs verify_per_proof, which would reuse them while they hold a window)
+    if (zk_status zs = grow(c, &c->lw_buf, &c->lw_bytes, w0.off + 256)) return zs;
+    Carver w1((uint8_t*)c->lw_buf);
+    wcarve(w1, w_off, w_msg, w_seeds, w_ok, w_st);
+    const int timing_mode = c->timing_mode;
+    c->timing_mode = timed ? ZK_TIMING_ON : ZK_TIMING_OFF;
+    std::vector<std::pair<const char*, float>> fam;
+    WindowRun R{c, s, timed, ev, &part_ms, &fam, d_msg, d_proofs, d_off, d_vseeds, d_ok, d_st, w_off, w_msg, w_seeds, w_ok, w_st, (uint64_t*)(c->h_lv + 2 * ZK_LV_CLASSES)};
+    zk_status zs = ZK_OK;
+    for (uint32_t r = 0; r < rs.count && !zs; r++) {
+        RingBind rb(c, slot[r]);
+        for (uint32_t l = 0; l <= ZK_MAXSEC && !zs; l++) {
+            const uint32_t k = r * ZK_LV_CLASSES + l;
+            for (uint32_t w = 0; w < cnt[k] && !zs; w += Wp) {
+                std::optional<VLevel> level;
+                if (per_proof) level.emplace(c, l);
+                zs = R.run(perm + start[k] + w, std::min<uint32_t>(Wp, cnt[k] - w));
+            }
+        }
+    }
+    c->timing_mode = timing_mode;
+    if (zs) {
+        (void)hipStreamSynchronize(s);
+        return zs;
+    }
+    HIPCHK(c, hipStreamSynchronize(s));
+    lap(0, 1);
+    c->last_timing.clear(), c->last_total_ms = 0, c->last_wall_ms = 0;
+    if (timed) {   // the windows' families, summed, and the partition's kernels (census, permutation, gathers, scatters) as one family
+        c->last_timing = fam;
+        c->last_timing.push_back({"v_rings", part_ms});
+        for (auto& f : c->last_timing)
+            if (f.first[0] != '+') c->last_total_ms += f.second;
+        c->last_wall_ms = c->last_total_ms;
+    }
+    return ZK_OK;
+}
+extern "C" zk_status zk_verify_batch_rings_device(zk_ctx* c, uint64_t B, const void* d_msg, const void* d_proofs, const void* d_off, const void* d_ids,
+                                                  const void* d_vseeds, void* d_ok, void* d_status) {
+    if (!c || (B && (!d_msg || !d_proofs || !d_off || !d_ids || !d_ok || !d_status))) return ZK_E_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    return verify_rings_device(c, B, (const uint8_t*)d_msg, (const uint8_t*)d_proofs, (const uint64_t*)d_off, (const uint32_t*)d_ids, (const uint8_t*)d_vseeds,
+                               (uint8_t*)d_ok, (int32_t*)d_status, false);
+}
+// Host-pointer proofs: the ids are classed here.  All of one resident ring: zk_verify_batch with that ring bound (its own level census, page-locked
+// DMA, staging: everything as with that ring active).  Anything else: the inputs cross to HBM in one transfer each and take the device path.
+extern "C" zk_status zk_verify_batch_rings(zk_ctx* c, uint64_t B, const uint8_t* msg, const uint8_t* proofs, const uint64_t* off, const uint32_t* ring_ids,
+                                           const uint8_t* vseeds, uint8_t* ok, int32_t* status) {
+    if (!c || (B && (!msg || !proofs || !off || !ring_ids || !ok || !status))) return ZK_E_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->params_set) return ZK_E_BUFFER;
+    if (B == 0) return ZK_OK;
+    if (c->stream_busy) {
+        c->err = "streamed jobs are in flight on this context (zk_prove_wait / zk_verify_wait them first)";
+        return ZK_E_ARG;
+    }
+    Ring* one = zk_resident_ring(c, ring_ids[0]);
+    for (uint64_t b = 1; b < B && one; b++)
+        if (ring_ids[b] != ring_ids[0]) one = nullptr;
+    if (one && one->N) {
+        RingBind rb(c, one);
+        return verify_host(c, B, msg, proofs, off, vseeds, ok, status);
+    }
+    if (off[0] != 0) return ZK_E_ARG;
+    for (uint64_t b = 0; b < B; b++)
+        if (off[b + 1] < off[b]) return ZK_E_ARG;  // every proof lies inside [0, off[B])
+    Carver k0(nullptr);
+    auto carve_in = [&](Carver& kk, uint8_t*& m, uint64_t*& o, uint32_t*& ids, uint8_t*& sd, uint8_t*& okp, int32_t*& st_) {
+        m = (uint8_t*)kk.take(32 * B), o = (uint64_t*)kk.take(8 * (B + 1)), ids = (uint32_t*)kk.take(4 * B), sd = (uint8_t*)kk.take(vseeds ? 32 * B : 32);
+        okp = (uint8_t*)kk.take(B), st_ = (int32_t*)kk.take(4 * B);
+    };
+    uint8_t *d_msg, *d_seeds, *d_ok;
+    uint64_t* d_off;
+    uint32_t* d_ids;
+    int32_t* d_st;
+    carve_in(k0, d_msg, d_off, d_ids, d_seeds, d_ok, d_st);
+    if (zk_status zs = ensure_in_buf(c, k0.off + 256)) return zs;
+    Carver k1((uint8_t*)c->in_buf);
+    carve_in(k1, d_msg, d_off, d_ids, d_seeds, d_ok, d_st);
+    if (zk_status zs = ensure_io_buf(c, off[B] + 64)) return zs;
+    HIPCHK(c, hipMemcpy(c->io_buf, proofs, off[B], hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d_msg, msg, 32 * B, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d_off, off, 8 * (B + 1), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d_ids, ring_ids, 4 * B, hipMemcpyHostToDevice));
+    if (vseeds) HIPCHK(c, hipMemcpy(d_seeds, vseeds, 32 * B, hipMemcpyHostToDevice));
+    zk_status zs = verify_rings_device(c, B, d_msg, (const uint8_t*)c->io_buf, d_off, d_ids, vseeds ? d_seeds : nullptr, d_ok, d_st, false);
+    if (zs) return zs;
+    HIPCHK(c, hipMemcpy(ok, d_ok, B, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(status, d_st, 4 * B, hipMemcpyDeviceToHost));
+    return ZK_OK;
+}
+
 extern "C" zk_status zk_verify_batch_device(zk_ctx* c, uint64_t B, const void* d_msg, const void* d_proofs, const void* d_off, const void* d_vseeds, void* d_ok,
                                             void* d_status) {
     if (!c || (B && (!d_msg || !d_proofs || !d_off || !d_ok || !d_status))) return ZK_E_ARG;
@@ -923,7 +1144,7 @@ extern "C" zk_status zk_verify_batch(zk_ctx* c, uint64_t B, const uint8_t* msg, 
                                      int32_t* status) {
     if (!c || (B && (!msg || !proofs || !off || !ok || !status))) return ZK_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->params_set || !c->N) return ZK_E_BUFFER;
+    if (!c->params_set || !c->ring->N) return ZK_E_BUFFER;
     if (B == 0) return ZK_OK;
     if (c->stream_busy) {
         c->err = "streamed jobs are in flight on this context (zk_prove_wait / zk_verify_wait them first)";
@@ -933,7 +1154,7 @@ extern "C" zk_status zk_verify_batch(zk_ctx* c, uint64_t B, const uint8_t* msg, 
 }
 zk_status verify_host(zk_ctx* c, uint64_t B, const uint8_t* msg, const uint8_t* proofs, const uint64_t* off, const uint8_t* vseeds, uint8_t* ok, int32_t* status) {
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->params_set || !c->N) return ZK_E_BUFFER;
+    if (!c->params_set || !c->ring->N) return ZK_E_BUFFER;
     if (B == 0) return ZK_OK;
     if (off[0] != 0) return ZK_E_ARG;
     for (uint64_t b = 0; b < B; b++)

@@ -14,6 +14,21 @@ struct TimerRec {
     hipEvent_t e0, e1;
 };
 #define ZK_MAX_LANES 4
+// One resident ring of a context: the padded ring's limbs and the tables built from it.  Every table but the limbs and the digest is optional.
+struct Ring {
+    uint32_t id = 0;
+    bool live = false;
+    uint64_t generation = 0;       // bumped by every build (zk_ring_info)
+    uint32_t* ring_mem = nullptr;
+    uint32_t* gk_etab = nullptr;   // table of the GK block transform (k_gk.hip); nullptr for small / huge rings
+    uint32_t* ktab = nullptr;      // per-key tables (k_ktab.hip): 264 KB per key (KTAB_KEY_WORDS), rings of up to 2^KTAB_MAXN keys
+    uint8_t* ktab_ok = nullptr;    // [N] which ring values are x-coordinates and own a table
+    int8_t* gk_kdig = nullptr;     // the ring as int8 digit fragments (k_gk_mfma.hip), built with table E for rings of >= 2^12 keys
+    int8_t* gk_edig = nullptr;     // table E's coefficient classes 2..6 as digit fragments: the prover's matrix-pipe table path (k_gk_mfma.hip)
+    uint64_t N = 0, nkeys = 0;
+    uint32_t n = 0;
+    uint32_t* ring_digest = nullptr;   // [8] SHA-256 words of the padded ring (hardened mode)
+};
 struct zk_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -27,20 +42,20 @@ struct zk_ctx {
     size_t scratch_words = 0;
     uint32_t* tab_scratch = nullptr;
     int32_t* d_flag = nullptr;
-    // ring
-    uint32_t* ring_mem = nullptr;
-    uint32_t* gk_etab = nullptr;   // per-ring table of the GK block transform (k_gk.hip); nullptr for small / huge rings
-    bool gk_table = true;          // ZKATTEST_GK_TABLE=0 disables it (plain fold for every ring)
-    uint32_t* ktab = nullptr;      // per-key tables of the ring (k_ktab.hip): 264 KB per key (KTAB_KEY_WORDS), rings of up to 2^KTAB_MAXN keys
-    uint8_t* ktab_ok = nullptr;    // [N] which ring values are x-coordinates and own a table
-    bool key_tables = true;        // ZKATTEST_KEYTAB=0 / zk_ctx_set_key_tables(ctx, 0): per-proof tables of R for every proof (read at zk_ctx_set_ring)
-    int8_t* gk_kdig = nullptr;     // the ring as int8 digit fragments (k_gk_mfma.hip), built with table E for rings of >= 2^12 keys
-    int8_t* gk_edig = nullptr;     // table E's coefficient classes 2..6 as digit fragments: the prover's matrix-pipe table path (k_gk_mfma.hip)
-    bool gk_mfma_prove = true;     // build gk_edig with the ring (ZKATTEST_GK_MFMA_PROVE; read at zk_ctx_set_ring)
+    // ring: the resident rings (zk_ctx_add_ring; zk_ctx_set_ring builds the active one) and the one the running call is bound to
+    Ring rings[ZK_MAX_RINGS];
+    Ring no_ring;                  // what `ring` points at while no ring is active: N = 0, every table nullptr
+    Ring* ring = &no_ring;         // the active ring between calls; a mixed-ring verify call binds each class's ring in turn (RingBind)
+    int active = -1;               // slot of the active ring in `rings`, -1 = none
+    uint32_t next_ring_id = 0;     // ids are never reused within a context
+    bool gk_table = true;          // ZKATTEST_GK_TABLE=0 disables table E (plain fold for every ring)
+    bool key_tables = true;        // ZKATTEST_KEYTAB=0 / zk_ctx_set_key_tables(ctx, 0): per-proof tables of R for every proof (read when a ring is built)
+    bool gk_mfma_prove = true;     // build gk_edig with the ring (ZKATTEST_GK_MFMA_PROVE; read when a ring is built)
     bool gk_mfma = true;           // verifier's ring fold on the matrix pipe where gk_kdig exists (zk_ctx_set_ring_fold, ZKATTEST_GK_MFMA)
-    uint64_t N = 0, nkeys = 0;
-    uint32_t n = 0;
-    uint32_t* ring_digest = nullptr;   // [8] SHA-256 words of the padded ring (hardened mode), computed by every zk_ctx_set_ring
+    void* rg_buf = nullptr;        // mixed-ring verify calls (api_verify.hip): census, permutation and counters (grow-only)
+    size_t rg_bytes = 0;
+    uint32_t* h_rg = nullptr;      // ... page-locked read-back of the per-class counters
+    size_t h_rg_bytes = 0;
     uint32_t mode = 0;                 // zk_ctx_set_mode: ZK_MODE_REFERENCE / ZK_MODE_HARDENED
     uint32_t verify_level = 0;         // zk_ctx_set_verify_level: ZK_VERIFY_LEVEL_CONTEXT / ZK_VERIFY_LEVEL_PER_PROOF
     // per-proof mode: the repetition count the verifier's workspaces are planned for during one call (or while streamed verify jobs are queued); the
@@ -59,6 +74,7 @@ struct zk_ctx {
     // calls) the output phases of different chunks fall into each other's heavy phases.  Lane 0 runs on `stream`.
     uint32_t chunk = 4096;
     uint32_t ws_C = 0, ws_sec = 0, ws_n = 0;
+    bool ws_etab = false, ws_edig = false;   // the prover workspaces' layout also follows which of the bound ring's tables E exist
     struct ProveLane {
         hipStream_t stream = nullptr;
         Workspace W{};
@@ -182,6 +198,13 @@ struct Scope {
 // (profiles/r06_ab_variants.txt (14)); a call of more than V_SIDE_MAXP proofs does not notice them.
 // the repetition count the workspaces are planned for: the context's secLevel, or the level of the proofs a per-proof-mode verify call is running
 static inline uint32_t plan_sec(const zk_ctx* c) { return c->v_sec_on ? c->v_sec : c->P.sec; }
+// binds `r` as the ring of the running call (mixed-ring verification) and puts the active ring back when the scope ends
+struct RingBind {
+    zk_ctx* c;
+    Ring* prev;
+    RingBind(zk_ctx* c_, Ring* r) : c(c_), prev(c_->ring) { c->ring = r; }
+    ~RingBind() { c->ring = prev; }
+};
 static inline bool zk_timed(const zk_ctx* c, uint64_t B) { return c->timing_mode == ZK_TIMING_ON || (c->timing_mode == ZK_TIMING_AUTO && B > V_SIDE_MAXP); }
 static inline void timing_begin(zk_ctx* c) { c->trecs.clear(), c->eused = 0, c->timing_forked = false; }
 static inline void timing_end(zk_ctx* c) {

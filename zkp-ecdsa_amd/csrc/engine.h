@@ -335,6 +335,17 @@ void launch_lv_gather_meta(hipStream_t s, uint32_t n, const uint32_t* sel, const
                            uint8_t* w_seeds);
 void launch_lv_gather_bytes(hipStream_t s, uint32_t n, const uint32_t* sel, const uint64_t* off, const uint8_t* proofs, const uint64_t* w_off, uint8_t* w_bytes);
 void launch_lv_scatter(hipStream_t s, uint32_t n, const uint32_t* sel, const uint8_t* w_ok, const int32_t* w_st, uint8_t* ok, int32_t* status, int32_t st);
+// mixed-ring verification (k_rings.hip): classes slot * ZK_LV_CLASSES + level class for up to ZK_MAX_RINGS resident rings, and one for ids that are not resident
+#define LV_BLOCK 1024   // proofs per workgroup of the census and the permutation (partition.h)
+#define RG_UNKNOWN (ZK_MAX_RINGS * ZK_LV_CLASSES)
+#define RG_CLASSES (RG_UNKNOWN + 1)
+struct RingSlots {   // (a kernel argument) the resident rings' ids in slot order
+    uint32_t id[ZK_MAX_RINGS];
+    uint32_t count;
+};
+void launch_rg_census(hipStream_t s, uint64_t B, const uint32_t* ring_ids, const RingSlots& rs, const uint8_t* proofs, const uint64_t* off, bool packed, bool per_proof,
+                      uint16_t* cls, uint32_t* blk_cnt, uint32_t* out);
+void launch_rg_perm(hipStream_t s, uint64_t B, const uint16_t* cls, const uint32_t* blk_base, const uint32_t* out, uint32_t* perm);
 
 // chunk inputs (device pointers, already offset to the chunk's first proof)
 struct ChunkIn {

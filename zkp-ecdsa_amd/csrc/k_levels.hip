@@ -1,9 +1,7 @@
 // Per-proof verify levels (include/zkattest.h: zk_ctx_set_verify_level): the census of a batch's header levels, the stable partition of its
 // proofs by level, the gather of one level's proofs into a contiguous window (bytes, offsets as prefix sums, message hashes, verifier seeds) and
 // the scatter of the window's verdicts back to the proofs' own indices.  The verifier's kernels run unchanged on the window (api_verify.hip).
-#include "engine.h"
-
-#define LV_BLOCK 1024   // proofs per workgroup of the census and the permutation
+#include "partition.h"
 
 // class of every proof (wire_level_class: 0..128, or ZK_LV_BAD) and, per workgroup, how many of its proofs fall into each class
 __global__ void __launch_bounds__(LV_BLOCK) k_lv_census(uint64_t B, const uint8_t* __restrict__ proofs, const uint64_t* __restrict__ off, uint32_t packed,
@@ -20,41 +18,6 @@ __global__ void __launch_bounds__(LV_BLOCK) k_lv_census(uint64_t B, const uint8_
     }
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < ZK_LV_CLASSES; i += LV_BLOCK) blk_cnt[(size_t)blockIdx.x * ZK_LV_CLASSES + i] = cnt[i];
-}
-// one workgroup: blk_cnt becomes, per class, the exclusive prefix over the workgroups; out[0 .. ZK_LV_CLASSES) = proofs per class (what the host
-// reads back), out[ZK_LV_CLASSES ..) = where each class starts in the permutation
-__global__ void __launch_bounds__(256) k_lv_scan(uint32_t blocks, uint32_t* __restrict__ blk_cnt, uint32_t* __restrict__ out) {
-    __shared__ uint32_t tot[ZK_LV_CLASSES];
-    const uint32_t l = threadIdx.x;
-    if (l < ZK_LV_CLASSES) {
-        uint32_t run = 0;
-#pragma unroll 8
-        for (uint32_t k = 0; k < blocks; k++) {
-            uint32_t* q = blk_cnt + (size_t)k * ZK_LV_CLASSES + l;
-            const uint32_t v = *q;
-            *q = run, run += v;
-        }
-        tot[l] = run;
-        out[l] = run;
-    }
-    __syncthreads();
-    if (l == 0) {
-        uint32_t run = 0;
-        for (uint32_t i = 0; i < ZK_LV_CLASSES; i++) out[ZK_LV_CLASSES + i] = run, run += tot[i];
-    }
-}
-// perm[start[class] + rank] = b, rank = the proof's place among the proofs of its class in index order (stable)
-__global__ void __launch_bounds__(LV_BLOCK) k_lv_perm(uint64_t B, const uint8_t* __restrict__ cls, const uint32_t* __restrict__ blk_base,
-                                                      const uint32_t* __restrict__ out, uint32_t* __restrict__ perm) {
-    __shared__ uint8_t sc[LV_BLOCK];
-    const uint64_t b = (uint64_t)blockIdx.x * LV_BLOCK + threadIdx.x;
-    const uint32_t l = b < B ? cls[b] : 0xffu;
-    sc[threadIdx.x] = (uint8_t)l;
-    __syncthreads();
-    if (b >= B) return;
-    uint32_t rank = 0;
-    for (uint32_t j = 0; j < threadIdx.x; j++) rank += sc[j] == l;   // (every lane of a wave reads the same byte: an LDS broadcast)
-    perm[out[ZK_LV_CLASSES + l] + blk_base[(size_t)blockIdx.x * ZK_LV_CLASSES + l] + rank] = (uint32_t)b;
 }
 // window entry j = proof sel[j]: its length (turned into offsets by k_lv_offsets), message hash and verifier seed
 __global__ void __launch_bounds__(256) k_lv_gather_meta(uint32_t n, const uint32_t* __restrict__ sel, const uint64_t* __restrict__ off, const uint8_t* __restrict__ msg,
@@ -129,10 +92,10 @@ __global__ void __launch_bounds__(256) k_lv_scatter(uint32_t n, const uint32_t* 
 void launch_lv_census(hipStream_t s, uint64_t B, const uint8_t* proofs, const uint64_t* off, bool packed, uint8_t* cls, uint32_t* blk_cnt, uint32_t* out) {
     const uint32_t blocks = (uint32_t)((B + LV_BLOCK - 1) / LV_BLOCK);
     hipLaunchKernelGGL(k_lv_census, dim3(blocks), dim3(LV_BLOCK), 0, s, B, proofs, off, packed ? 1u : 0u, cls, blk_cnt);
-    hipLaunchKernelGGL(k_lv_scan, dim3(1), dim3(256), 0, s, blocks, blk_cnt, out);
+    hipLaunchKernelGGL((k_part_scan<ZK_LV_CLASSES, 256>), dim3(1), dim3(256), 0, s, blocks, blk_cnt, out);
 }
 void launch_lv_perm(hipStream_t s, uint64_t B, const uint8_t* cls, const uint32_t* blk_base, const uint32_t* out, uint32_t* perm) {
-    hipLaunchKernelGGL(k_lv_perm, dim3((uint32_t)((B + LV_BLOCK - 1) / LV_BLOCK)), dim3(LV_BLOCK), 0, s, B, cls, blk_base, out, perm);
+    hipLaunchKernelGGL((k_part_perm<uint8_t, ZK_LV_CLASSES>), dim3((uint32_t)((B + LV_BLOCK - 1) / LV_BLOCK)), dim3(LV_BLOCK), 0, s, B, cls, blk_base, out, perm);
 }
 void launch_lv_gather_meta(hipStream_t s, uint32_t n, const uint32_t* sel, const uint64_t* off, const uint8_t* msg, const uint8_t* vseeds, uint64_t* w_off, uint8_t* w_msg,
                            uint8_t* w_seeds) {
