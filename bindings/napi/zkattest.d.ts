@@ -35,6 +35,9 @@ export function proveSignatureListBatch(params: SystemParametersList, msgHashes:
 /** booleans per proof; `errors[b]` holds what verifySignatureList would have thrown for proof b (null otherwise) -- a malformed proof never affects its neighbours */
 export type Verdicts = boolean[] & { readonly errors: (Error | null)[] }
 export function verifySignatureListBatch(params: SystemParametersList, msgHashes: Uint8Array[], keys: bigint[] | Buffer, proofs: (SignatureProofList | Buffer)[]): Promise<Verdicts>
+/** facade-wide options.  ringDelta (default 0 = off): a key list that is not resident but differs from a resident ring of the same length in at most `value`
+ *  32-byte entries updates that ring in place (Engine.updateRing) and re-tags it instead of building a new ring; Engine.setOption('ringDelta') overrides it per engine */
+export function setOption(name: 'ringDelta', value: number): void
 /** one statement per proof over its own ring: keyLists[i] is proof i's ring.  The rings stay resident on the params' engine (Engine.setOption('residentRings')),
  *  every call is one mixed-ring batch on the GPU (split only when it names more rings than are kept resident) */
 export function verifySignatureLists(params: SystemParametersList, msgHashes: Uint8Array[], keyLists: (bigint[] | Buffer)[], proofs: (SignatureProofList | Buffer)[]): Promise<Verdicts>
@@ -51,8 +54,10 @@ export class Engine {
     constructor(devices?: number | number[])
     close(): void
     info(): { devices: number; ringTransport: string; proofMaxSize: number }
-    /** residentRings (1..16, default 4): key rings the facade's context cache keeps built on this engine, least recently used dropped first */
-    setOption(name: 'chunk' | 'lanes' | 'combBits' | 'hostTaper' | 'batchVerify' | 'mode' | 'slice' | 'ringFold' | 'verifyGroups' | 'wire' | 'verifyLevel' | 'inflight' | 'residentRings', value: number): void
+    /** residentRings (1..16, default 4): key rings the facade's context cache keeps built on this engine, least recently used dropped first;
+     *  ringDelta (default 0 = off): a key list that misses the cache but differs from a resident ring of the same length in at most this many 32-byte entries
+     *  updates that ring in place (updateRing) instead of building a new one */
+    setOption(name: 'chunk' | 'lanes' | 'combBits' | 'hostTaper' | 'batchVerify' | 'mode' | 'slice' | 'ringFold' | 'verifyGroups' | 'wire' | 'verifyLevel' | 'inflight' | 'residentRings' | 'ringDelta', value: number): void
     /** zero the witness-derived device memory (prover workspaces, staged signatures and seeds) of every device now; close() and a failed prove do it by themselves */
     wipe(): void
     setParams(p: EngineParams): void
@@ -61,6 +66,9 @@ export class Engine {
     addRing(keys: Buffer | bigint[]): number
     useRing(id: number): void
     dropRing(id: number): void
+    /** zk_pool_update_ring: ring `id` becomes what setRing of the changed key list would build; indices[j] gets keys[j] (the last entry for an index wins),
+     *  nKeys is the new key count (default: unchanged).  The id, the active state and every other ring are untouched; the generation goes up by one. */
+    updateRing(id: number, indices: ArrayLike<number | bigint>, keys: Buffer | bigint[], nKeys?: number): void
     ringInfo(id: number): { nKeys: number; logN: number; flags: number; generation: number }
     /** one resident ring id per proof (zk_pool_verify_batch_rings) */
     verifyBatchRings(msg: Buffer, proofs: Buffer[], ringIds: number[] | Uint32Array, seeds?: Buffer): Verdicts

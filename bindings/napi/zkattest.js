@@ -312,6 +312,11 @@ class Engine {
             this.residentRings = value
             return
         }
+        if (name === 'ringDelta') {   // facade only: a key list that differs from a resident ring in at most this many entries updates that ring in place (0 = off)
+            if (!(Number.isInteger(value) && value >= 0)) throw new RangeError('ringDelta: an integer >= 0')
+            this.ringDelta = value
+            return
+        }
         native.setOption(this.h, name, value)
     }
     wipe() { native.setOption(this.h, 'wipe', 0) }   // zk_ctx_wipe on every device: prover workspaces and staged inputs zeroed (also done by close() and after a failed prove)
@@ -323,6 +328,13 @@ class Engine {
     useRing(id) { native.useRing(this.h, id) }
     dropRing(id) { native.dropRing(this.h, id) }   // the active ring cannot be dropped
     ringInfo(id) { return native.ringInfo(this.h, id) }   // -> { nKeys, logN, flags, generation }
+    // zk_pool_update_ring: the resident ring becomes what setRing of the changed key list would build, rewriting only what the change touches.
+    // indices[j] gets keys[j] (a Buffer of 32-byte entries or bigint[]; a later entry for the same index wins); nKeys: the new key count (default: unchanged)
+    updateRing(id, indices, keys, nKeys) {
+        const idx = Buffer.from(BigUint64Array.from(Array.from(indices, (i) => BigInt(i))).buffer)
+        const kb = Buffer.isBuffer(keys) ? keys : Buffer.concat(keys.map(be32))
+        native.updateRing(this.h, id, idx, kb, nKeys === undefined ? this.ringInfo(id).nKeys : nKeys)
+    }
     synthParams(seed) { return Object.assign(native.synthParams(this.h, seed), { secLevel: 80 }) }
     synthWorkload(seed, nKeys, B) { return native.synthWorkload(this.h, seed, nKeys, B) }
     keysToInts(pkxy) { return native.keysToInts(this.h, pkxy) }                       // keyToInt over a key set
@@ -414,7 +426,7 @@ function engineFor(params, keys) {
         if (process.env.ZKATTEST_COMB_BITS) engine.setOption('combBits', parseInt(process.env.ZKATTEST_COMB_BITS, 10))
         if (params.hardened) engine.setOption('mode', 1)
         engine.setParams(params._ep)           // builds the fixed-base tables: once per SystemParametersList
-        slot = { engine, rings: new Map(), active: null }   // rings: ring tag -> resident ring id, least recently used first
+        slot = { engine, rings: new Map(), active: null, bufs: new Map() }   // rings: ring tag -> resident ring id, least recently used first; bufs: ring tag -> key bytes (ringDelta)
         engines.set(key, slot)
     }
     const ring = ringOf(keys)
@@ -441,22 +453,67 @@ function residentRing(slot, ring, keep = []) {
         return id
     }
     const busy = new Set(keep.map((r) => r.tag))
+    const delta = e.ringDelta !== undefined ? e.ringDelta : facadeRingDelta
+    if (delta > 0) {   // opt-in: a resident ring of the same length that differs in a few entries is updated in place and re-tagged (Engine.updateRing)
+        for (const [tag, old] of slot.bufs) {
+            if (busy.has(tag) || old.length !== ring.buf.length || !slot.rings.has(tag)) continue
+            const diff = ringDiff(old, ring.buf, delta)
+            if (!diff || !diff.length) continue   // (no difference under another tag cannot be: never re-tag a ring without writing it)
+            id = slot.rings.get(tag)
+            const fresh = Buffer.from(ring.buf)   // a PRIVATE copy is the record of what is resident: the caller may overwrite its Buffer in place
+            try {
+                e.updateRing(id, diff, Buffer.concat(diff.map((i) => fresh.subarray(32 * i, 32 * i + 32))), fresh.length / 32)
+            } catch (err) {   // a failed update may have dropped the ring (and with it the active ring): the slot forgets it, the next call builds it anew
+                let resident = true
+                try { e.ringInfo(id) } catch (_) { resident = false }
+                if (!resident) {
+                    slot.rings.delete(tag), slot.bufs.delete(tag)
+                    if (slot.active === tag) slot.active = null
+                }
+                throw err
+            }
+            slot.rings.delete(tag), slot.bufs.delete(tag)
+            slot.rings.set(ring.tag, id), slot.bufs.set(ring.tag, fresh)
+            if (slot.active === tag) slot.active = ring.tag
+            return id
+        }
+    }
     while (slot.rings.size >= cap) {
         const victim = [...slot.rings.keys()].find((t) => t !== slot.active && !busy.has(t))
         if (victim === undefined) break
         e.dropRing(slot.rings.get(victim))
-        slot.rings.delete(victim)
+        slot.rings.delete(victim), slot.bufs.delete(victim)
     }
     if (slot.rings.size >= cap && slot.active !== null && !busy.has(slot.active)) {   // only the active ring is left: rebuilt in place under its id
         id = slot.rings.get(slot.active)
-        slot.rings.delete(slot.active)
+        slot.rings.delete(slot.active), slot.bufs.delete(slot.active)
         e.setRing(ring.buf)
         slot.active = ring.tag
     } else {
         id = e.addRing(ring.buf)
     }
     slot.rings.set(ring.tag, id)
+    if (delta > 0) slot.bufs.set(ring.tag, Buffer.from(ring.buf))   // a private copy (see above)
     return id
+}
+// Facade-wide options.  ringDelta (default 0 = off): when a call names a key list that is not resident but has the length of a resident ring of the same
+// engine and differs from it in at most `value` 32-byte entries, that ring is updated in place (Engine.updateRing: only the touched keys and blocks are
+// rebuilt) and re-tagged, instead of a new ring being built beside it.  An engine's own setOption('ringDelta') overrides it for that engine.
+let facadeRingDelta = 0
+function setOption(name, value) {
+    if (name !== 'ringDelta') throw new RangeError('setOption: unknown option ' + name)
+    if (!(Number.isInteger(value) && value >= 0)) throw new RangeError('ringDelta: an integer >= 0')
+    facadeRingDelta = value
+}
+// the 32-byte entries in which two key lists of one length differ (a linear comparison), or null when there are more than `max` of them
+function ringDiff(a, b, max) {
+    const out = []
+    for (let i = 0; 32 * i < a.length; i++)
+        if (a.compare(b, 32 * i, 32 * i + 32, 32 * i, 32 * i + 32) !== 0) {
+            if (out.length === max) return null
+            out.push(i)
+        }
+    return out
 }
 function _ringGenerations(params) {   // (tests) ring tag -> build generation of every ring resident on the engine of `params`
     const slot = params._tag0 && engines.get(params._tag0 + (params.hardened ? '|hardened' : ''))
@@ -581,4 +638,4 @@ async function verifySignatureLists(params, msgHashes, keyLists, proofs) {
 
 module.exports = { verifySignatureLists, _ringGenerations, setVerifyLevel, getVerifyLevel, generateParamsList, generateParamsListHardened, keyToInt, proveSignatureList, verifySignatureList, proveSignatureListBatch, verifySignatureListBatch,
     writeJson, readJson, writeJsonBatch, readJsonBatch, SignatureProofList, SystemParametersList, PedersenParams, generatePedersenParams, p256, tomEdwards256, ALL_GROUPS,
-    Group, Point, Scalar, Engine, shutdown, setWireLayout, getWireLayout, native }
+    Group, Point, Scalar, Engine, shutdown, setWireLayout, getWireLayout, setOption, native }

@@ -547,6 +547,34 @@ static napi_value AddRing(napi_env env, napi_callback_info info) { /* (h, keys: 
     NAPI_OK(napi_create_uint32(env, id, &v));
     return v;
 }
+static napi_value UpdateRing(napi_env env, napi_callback_info info) { /* (h, ring id, indices: count x u64 LE, keys: count x 32 bytes, nKeys): zk_pool_update_ring */
+    napi_value argv[5];
+    if (!get_args(env, info, 5, argv)) return NULL;
+    Handle *h = get_handle(env, argv[0], 0);
+    uint8_t *ib, *k;
+    size_t li, lk;
+    uint32_t id;
+    double nk;
+    if (!h || !get_bytes(env, argv[2], &ib, &li) || !get_bytes(env, argv[3], &k, &lk)) return NULL;
+    if (napi_get_value_uint32(env, argv[1], &id) != napi_ok || napi_get_value_double(env, argv[4], &nk) != napi_ok || nk < 0 || nk > 9007199254740992.0) {
+        napi_throw_type_error(env, NULL, "expected a ring id and a key count");
+        return NULL;
+    }
+    if (li % 8 || lk != li * 4) {
+        napi_throw_range_error(env, NULL, "updateRing: one 64-bit index and one 32-byte key per change");
+        return NULL;
+    }
+    const size_t count = li / 8;
+    uint64_t *idx = (uint64_t *)malloc(li ? li : 8); /* (a Buffer's bytes need not be 8-byte aligned) */
+    if (!idx) {
+        napi_throw_range_error(env, NULL, "updateRing: out of memory");
+        return NULL;
+    }
+    memcpy(idx, ib, li);
+    zk_status st = zk_pool_update_ring(h->pool, id, count, idx, k, (uint64_t)nk);
+    free(idx);
+    return st == ZK_OK ? NULL : throw_status(env, h, st);
+}
 static napi_value ring_call(napi_env env, napi_callback_info info, zk_status (*f)(zk_pool *, uint32_t)) { /* (h, ring id) */
     napi_value argv[2];
     if (!get_args(env, info, 2, argv)) return NULL;
@@ -973,7 +1001,7 @@ static napi_value Init(napi_env env, napi_value exports) {
                {"keysToInts", KeysToInts},       {"hostAlloc", HostAlloc},           {"hardenedH", HardenedH},
                {"proofsToJsonBatch", ProofsToJsonBatch}, {"proofsFromJsonBatch", ProofsFromJsonBatch},
                {"proveSubmit", ProveSubmit},     {"verifySubmit", VerifySubmit},
-               {"addRing", AddRing},             {"useRing", UseRing},               {"dropRing", DropRing},       {"ringInfo", RingInfo},
+               {"addRing", AddRing},             {"useRing", UseRing},               {"dropRing", DropRing},           {"updateRing", UpdateRing},       {"ringInfo", RingInfo},
                {"verifyBatchRings", VerifyBatchRings}, {"verifyBatchRingsAsync", VerifyBatchRingsAsync}};
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;

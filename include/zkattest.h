@@ -287,6 +287,26 @@ zk_status zk_ctx_use_ring(zk_ctx *ctx, uint32_t ring);
 zk_status zk_ctx_drop_ring(zk_ctx *ctx, uint32_t ring);
 zk_status zk_ring_info(zk_ctx *ctx, uint32_t ring, uint64_t *n_keys, uint32_t *log_n, uint32_t *flags, uint64_t *generation);
 
+/* Updating a resident ring in place.  A registry of attested keys gains a few keys, rotates one, revokes one; rebuilding the ring for that redoes every table
+ * of N keys.  Every table of a ring is indexed by key or by block of 256 keys, so zk_ctx_update_ring rewrites only what the change touches: k limbs, k per-key
+ * tables, the touched blocks of table E and of the two digit tables, their leaves of the digest and its root -- through the SAME kernels as the full build,
+ * handed an index list, so the result is bit for bit what zk_ctx_set_ring of the new list builds.  The reference has no counterpart (it takes `keys` with every
+ * call); it fixes the semantics: afterwards the context behaves exactly as if it had been given the new key list.
+ *   L = the ring's n_keys caller keys.  The new list L' has new_n_keys entries: L'[i] = the LAST keys_be32[j] with index[j] == i, else L[i].  new_n_keys > n_keys
+ *   appends (every index in [n_keys, new_n_keys) must be supplied); new_n_keys < n_keys truncates (the dropped tail becomes padding, copies of L'[0]).
+ *   The id and the active / inactive state stay, zk_ring_info reports new_n_keys, the generation goes up by one.  count == 0 with new_n_keys == n_keys is a
+ *   no-op (ZK_OK, generation unchanged).
+ * Same padded size (the next power of two): the tables are patched in place, no table is reallocated and none that was absent is created; the per-key tables of
+ * padding entries are copied from entry 0's.  The padded size changes: the ring is rebuilt from the assembled list like zk_ctx_add_ring builds it.
+ * ZK_E_ARG, nothing written, zk_last_error set: NULL arguments, an id that is not resident, new_n_keys < 2, an index >= new_n_keys, an appended position without
+ * a key, streamed jobs queued on the context.  A HIP failure after the first write returns ZK_E_DEVICE and DROPS the ring (a context whose active ring this was
+ * has none afterwards): a half-updated ring never stays resident.  A ZK_E_DEVICE from BEFORE the first write (the update's temporary memory, its upload) leaves
+ * the ring of a single context unchanged -- zk_last_error says which of the two happened, zk_ring_info whether the id is still resident.  All pointers are host pointers.
+ * zk_pool_update_ring: the same on every shard context, concurrently; if a shard fails on its device -- before or after its first write -- the ring is dropped on
+ * all of them, so that no shard serves a ring the others lost or did not update. */
+zk_status zk_ctx_update_ring(zk_ctx *ctx, uint32_t ring, uint64_t count, const uint64_t *index /*count*/, const uint8_t *keys_be32 /*count x 32*/,
+                             uint64_t new_n_keys);
+
 /* Mixed-ring verification: zk_verify_batch[_device] with one resident ring id per proof.  A proof whose id is not resident gets ok 0 and
  * ZK_E_ARG; every other proof gets exactly the (ok, status) zk_verify_batch gives it with that ring active -- both wire layouts, hardened
  * mode with each ring's own digest, per-proof verify levels.  The active ring is neither read nor changed.  How: the proofs are classed by
@@ -363,6 +383,8 @@ zk_status zk_pool_set_verify_level(zk_pool *pool, uint32_t mode);   /* zk_ctx_se
 zk_status zk_pool_add_ring(zk_pool *pool, const uint8_t *keys_be32, uint64_t n_keys, uint32_t *ring);   /* resident rings: see zk_ctx_add_ring */
 zk_status zk_pool_use_ring(zk_pool *pool, uint32_t ring);
 zk_status zk_pool_drop_ring(zk_pool *pool, uint32_t ring);
+zk_status zk_pool_update_ring(zk_pool *pool, uint32_t ring, uint64_t count, const uint64_t *index /*count*/, const uint8_t *keys_be32 /*count x 32*/,
+                              uint64_t new_n_keys);   /* see zk_ctx_update_ring */
 /* zk_prove_batch over all devices.  Shard i writes its proofs back to back from out + i * ((out_cap / G) & ~255): proof b lies
  * at out_off[b] .. out_off[b] + out_len[b] (its ZKA1 header carries the same length); there are gaps between shards, none
  * inside one.  ZK_E_BUFFER when a shard does not fit its region.  `out` from zk_host_alloc is filled by overlapped DMA. */
@@ -479,8 +501,17 @@ int zk_pool_test_locality(const char *pci_bus_id, int *numa_node, int *cpus, int
  * 2 = live terms that went through the verifier's batched Tom-256 check (bucket pass) since the context was created;
  * 3 = proofs whose P-256 relation was accepted by the cross-proof P-256 pass (chunks of at least ZKATTEST_P256_BATCH proofs, default 8192): every GROUP
  *     without a failing proof counts (a failing group, not its chunk, goes through the per-proof sums);
- * 4 = dependent chains of small calls handed to cooperating waves so far (k_coop.hip: Straus sums, the table of R), process-wide */
+ * 4 = dependent chains of small calls handed to cooperating waves so far (k_coop.hip: Straus sums, the table of R), process-wide;
+ * 5 = per-key tables COMPUTED by the ring builder since the context was created (a full build computes one per padded entry; the tables zk_ctx_update_ring
+ *     copies from entry 0 for padding entries do not count);
+ * 6 = 256-key blocks whose table E was built since the context was created */
 uint64_t zk_test_counter(const zk_ctx *ctx, int which);
+/* Only in the test build (lib/libzkattest_hip_testhooks.so, csrc/api_pool.hip under ZK_TEST_HOOKS); the product library exports neither:
+ *   void zk_test_pool_fail_next_submit, arguments (zk_pool *pool, int slot):
+ *       the next streamed pool submit fails at device slot `slot` (one shot)
+ *   zk_status zk_test_ring_checksum, arguments (zk_ctx *ctx, uint32_t ring, uint64_t sums[8]):
+ *       one order-independent 64-bit checksum per table of a resident ring -- limbs, table E, gk_kdig, gk_edig, ktab, ktab_ok, leaves, digest: the sum mod 2^64 of
+ *       a mix of (word index, word); 0 for a table the ring does not have.  Per-key tables of ring values that are no x-coordinate are never written and left out. */
 /*
  * which_field: 0 = F_q (p256.p), 1 = Z_n, 2 = F_t;  op: 0 mul, 1 add, 2 sub, 3 inverse, 4 a*b - a - b (fused double subtraction), 5 (a + b)^2 (dedicated squaring).  count x 40-byte BE operands. */
 zk_status zk_test_field_op(zk_ctx *ctx, int which_field, int op, uint64_t count, const uint8_t *a_be40, const uint8_t *b_be40, uint8_t *out_be40);

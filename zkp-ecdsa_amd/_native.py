@@ -24,6 +24,7 @@ SYMBOLS = [
     'zk_ctx_set_verify_level', 'zk_pool_set_verify_level',
     'zk_ctx_add_ring', 'zk_ctx_add_ring_device', 'zk_ctx_use_ring', 'zk_ctx_drop_ring', 'zk_ring_info', 'zk_verify_batch_rings', 'zk_verify_batch_rings_device',
     'zk_pool_add_ring', 'zk_pool_use_ring', 'zk_pool_drop_ring', 'zk_pool_verify_batch_rings',
+    'zk_ctx_update_ring', 'zk_pool_update_ring',
     'zk_test_field_op', 'zk_test_tom_commit', 'zk_test_p256_fixed_mul', 'zk_test_sha256', 'zk_test_rng_draws',
 ]
 
@@ -34,6 +35,17 @@ STATUS_TEXT = {
     12: 'buffer too small or context not configured', 13: 'incorrect interpolation', 14: 'invalid argument',
     15: 'HIP runtime failure',
 }
+
+
+def _ring_changes(changes):
+    """changes: a dict {index: key_bytes} or a list of (index, key_bytes), applied in order -> (count, u64 array or None, key bytes or None)"""
+    items = list(changes.items()) if isinstance(changes, dict) else list(changes)
+    if not items:
+        return 0, None, None
+    for _, k in items:
+        if len(k) != 32:
+            raise ValueError('a ring key is 32 bytes')
+    return len(items), (C.c_uint64 * len(items))(*[int(i) for i, _ in items]), b''.join(bytes(k) for _, k in items)
 
 
 class ZkRng(C.Structure):
@@ -101,6 +113,8 @@ def lib():
         L.zk_verify_batch_rings_device.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp, vp]
         L.zk_pool_add_ring.argtypes = [vp, C.c_char_p, u64, C.POINTER(u32)]
         L.zk_pool_use_ring.argtypes = [vp, u32]
+        L.zk_ctx_update_ring.argtypes = [vp, u32, u64, vp, C.c_char_p, u64]
+        L.zk_pool_update_ring.argtypes = [vp, u32, u64, vp, C.c_char_p, u64]
         L.zk_pool_drop_ring.argtypes = [vp, u32]
         L.zk_pool_verify_batch_rings.argtypes = [vp, u64, C.c_char_p, vp, vp, vp, vp, C.c_char_p, vp, vp]
         L.zk_ring_digest.argtypes = [vp, vp]
@@ -395,6 +409,14 @@ class Engine:
 
     def drop_ring(self, ring):
         self._chk(self.L.zk_ctx_drop_ring(self.h, ring))
+
+    def update_ring(self, ring, changes, nkeys=None):
+        """zk_ctx_update_ring: the resident ring becomes what set_ring of the changed key list would build, rewriting only what the change touches.
+        changes: dict {index: key} or list of (index, key) (a later entry for the same index wins); nkeys: the new key count (default: unchanged)."""
+        cnt, idx, keys = _ring_changes(changes)
+        if nkeys is None:
+            nkeys = self.ring_info(ring)['n_keys']
+        self._chk(self.L.zk_ctx_update_ring(self.h, ring, cnt, idx, keys, nkeys))
 
     def ring_info(self, ring):
         """zk_ring_info: dict with n_keys, log_n, flags (RING_* bits) and generation."""
@@ -731,6 +753,13 @@ class Pool:
 
     def ring_info(self, ring):
         return self.engine(0).ring_info(ring)
+
+    def update_ring(self, ring, changes, nkeys=None):
+        """zk_pool_update_ring: Engine.update_ring on every shard context."""
+        cnt, idx, keys = _ring_changes(changes)
+        if nkeys is None:
+            nkeys = self.ring_info(ring)['n_keys']
+        self._chk(self.L.zk_pool_update_ring(self.h, ring, cnt, idx, keys, nkeys))
 
     def verify_batch_rings(self, msg, proofs, ring_ids, vseeds=None):
         """zk_pool_verify_batch_rings: verify_batch with one resident ring id per proof, sharded by contiguous ranges."""

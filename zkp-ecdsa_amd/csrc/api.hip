@@ -263,7 +263,7 @@ extern "C" zk_status zk_ctx_set_params(zk_ctx* c, const uint8_t nist_h[64], cons
 }
 
 static void free_ring(Ring& R) {   // (nothing in flight reads it: the callers synchronise or refuse while jobs are queued)
-    hipFree(R.ring_mem), hipFree(R.gk_etab), hipFree(R.gk_kdig), hipFree(R.gk_edig), hipFree(R.ktab), hipFree(R.ktab_ok), hipFree(R.ring_digest);
+    hipFree(R.ring_mem), hipFree(R.gk_etab), hipFree(R.gk_kdig), hipFree(R.gk_edig), hipFree(R.ktab), hipFree(R.ktab_ok), hipFree(R.ring_digest), hipFree(R.leaves);
     const uint32_t id = R.id;
     const uint64_t gen = R.generation;
     const bool live = R.live;
@@ -286,7 +286,7 @@ static zk_status build_ring(zk_ctx* c, Ring& R, const uint8_t* d_keys, uint64_t 
     if (c->gk_table && n >= GK_ETAB_MINN && n <= GK_ETAB_MAXN) {  // per-ring table of the 8 low fold levels (k_gk.hip)
         if (strict) HIPCHK(c, hipMalloc(&R.gk_etab, sizeof(uint32_t) * gk_etab_words(N)));
         else if (hipMalloc(&R.gk_etab, sizeof(uint32_t) * gk_etab_words(N)) != hipSuccess) (void)hipGetLastError(), R.gk_etab = nullptr;   // plain fold for this ring
-        if (R.gk_etab) launch_gk_etab(c->stream, ring, (uint32_t)(N >> 8), R.gk_etab);
+        if (R.gk_etab) launch_gk_etab(c->stream, ring, (uint32_t)(N >> 8), R.gk_etab), c->dbg_etab_blocks += N >> 8;
     }
     // the two digit-fragment tables and the per-key tables below are optimisations, not requirements: where the HBM is not there (several
     // contexts on one device, a ring of 2^20 keys next to other tenants) the allocation failure is cleared and the vector-ALU fold / the
@@ -307,6 +307,7 @@ static zk_status build_ring(zk_ctx* c, Ring& R, const uint8_t* d_keys, uint64_t 
         if (hipMalloc(&R.ktab, sizeof(uint32_t) * KTAB_KEY_WORDS * N) == hipSuccess && hipMalloc(&R.ktab_ok, N) == hipSuccess &&
             hipMalloc(&tmp, ktab_temp_bytes(N, slab)) == hipSuccess) {
             launch_ktab_build(c->stream, ring, N, R.ktab, R.ktab_ok, tmp, slab);
+            c->dbg_ktab_keys += N;
             hipError_t e = hipStreamSynchronize(c->stream);
             if (e != hipSuccess) {
                 hipFree(tmp);
@@ -319,13 +320,11 @@ static zk_status build_ring(zk_ctx* c, Ring& R, const uint8_t* d_keys, uint64_t 
         }
         if (tmp) HIPCHK(c, hipFree(tmp));
     }
-    {   // digest of the padded ring: what the hardened mode hashes into the membership challenge
+    {   // digest of the padded ring: what the hardened mode hashes into the membership challenge; the leaves stay resident for zk_ctx_update_ring (32 B per block)
         HIPCHK(c, hipMalloc(&R.ring_digest, 32));
-        uint32_t* leaves = nullptr;
-        HIPCHK(c, hipMalloc(&leaves, 32 * ((N + 255) / 256)));
-        launch_ring_digest(c->stream, ring, N, leaves, R.ring_digest);
+        HIPCHK(c, hipMalloc(&R.leaves, 32 * ((N + 255) / 256)));
+        launch_ring_digest(c->stream, ring, N, R.leaves, R.ring_digest);
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipFree(leaves));
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     R.N = N, R.n = n, R.nkeys = nkeys;
@@ -430,6 +429,7 @@ extern "C" zk_status zk_ctx_use_ring(zk_ctx* c, uint32_t ring) {
     c->active = (int)(R - c->rings), c->ring = R;   // the workspaces are bound to it by the next call (ensure_workspace)
     return ZK_OK;
 }
+static void unbind_lanes(zk_ctx* c, const Ring* R);
 extern "C" zk_status zk_ctx_drop_ring(zk_ctx* c, uint32_t ring) {
     if (!c) return ZK_E_ARG;
     if (c->stream_busy) return busy_refusal(c);
@@ -439,11 +439,153 @@ extern "C" zk_status zk_ctx_drop_ring(zk_ctx* c, uint32_t ring) {
         return ZK_E_ARG;
     }
     HIPCHK(c, hipSetDevice(c->device));
-    for (auto& L : c->pl)   // (no lane keeps a pointer into a ring it is not bound to past a call; cleared all the same)
-        if (L.W.ring.p == R->ring_mem) L.W.ring = Soa{nullptr, 0}, L.W.ktab = nullptr, L.W.ktab_ok = nullptr, L.W.gk_etab = nullptr, L.W.gk_kdig = nullptr, L.W.gk_edig = nullptr;
+    unbind_lanes(c, R);   // (no lane keeps a pointer into a ring it is not bound to past a call; cleared all the same)
     free_ring(*R);
     *R = Ring{};
     return ZK_OK;
+}
+
+// ---- in-place update of a resident ring (include/zkattest.h: zk_ctx_update_ring; kernels: k_ring_update.hip and the builders' launch_*_list)
+static void unbind_lanes(zk_ctx* c, const Ring* R) {
+    for (auto& L : c->pl)
+        if (L.W.ring.p == R->ring_mem) L.W.ring = Soa{nullptr, 0}, L.W.ktab = nullptr, L.W.ktab_ok = nullptr, L.W.gk_etab = nullptr, L.W.gk_kdig = nullptr, L.W.gk_edig = nullptr;
+}
+// a device failure after the first write: the half-updated ring does not stay resident; if it was active the context has no active ring
+static void abandon_ring(zk_ctx* c, Ring* R) {
+    (void)hipGetLastError();
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipGetLastError();
+    unbind_lanes(c, R);
+    if (c->active >= 0 && R == &c->rings[c->active]) c->active = -1, c->ring = &c->no_ring, c->ws_C = 0;
+    free_ring(*R);
+    *R = Ring{};
+}
+void zk_abandon_resident_ring(zk_ctx* c, uint32_t id) {   // api_pool.hip: another shard's update failed
+    Ring* R = find_ring(c, id);
+    if (!R || hipSetDevice(c->device) != hipSuccess) return;
+    abandon_ring(c, R);
+}
+// the fast path: same padded size, every table patched in place.  `ent` = the touched padded entries (sorted, distinct), `src` = where each one's new value comes
+// from (index into `keys`, or ZK_RU_FROM_ENTRY0), `real` of them lie below new_nkeys (their key tables are computed), the rest are padding (copies of entry 0's)
+static zk_status patch_ring(zk_ctx* c, Ring& R, const std::vector<uint32_t>& ent, const std::vector<uint32_t>& src, const std::vector<uint8_t>& keys, uint64_t new_nkeys,
+                            bool& wrote) {
+    const uint32_t k = (uint32_t)ent.size();
+    const uint32_t real = (uint32_t)(std::lower_bound(ent.begin(), ent.end(), (uint32_t)new_nkeys) - ent.begin());
+    std::vector<uint32_t> blocks;   // sorted, distinct: blocks of 256 entries = leaves of the digest
+    for (uint32_t e : ent)
+        if (blocks.empty() || blocks.back() != e >> 8) blocks.push_back(e >> 8);
+    const uint32_t b = (uint32_t)blocks.size(), nblocks = (uint32_t)(R.N >> 8);
+    // one upload: entries | sources | blocks | keys
+    std::vector<uint32_t> h(2 * (size_t)k + b + keys.size() / 4);
+    memcpy(h.data(), ent.data(), 4 * (size_t)k), memcpy(h.data() + k, src.data(), 4 * (size_t)k), memcpy(h.data() + 2 * (size_t)k, blocks.data(), 4 * (size_t)b);
+    memcpy(h.data() + 2 * (size_t)k + b, keys.data(), keys.size());
+    DevBuf up, tmp;
+    const bool kt = R.ktab && R.ktab_ok;
+    const uint32_t slab = std::min<uint32_t>(std::max<uint32_t>(real, 1), 4096);
+    // nothing is written yet: a failure here leaves the ring as it was (ZK_E_DEVICE, and the text says so)
+    if (hipMalloc(&up.p, 4 * h.size()) != hipSuccess || (kt && real && hipMalloc(&tmp.p, ktab_temp_bytes(real, slab)) != hipSuccess) ||   // temp: indexed by touched key, not by ring entry
+        hipMemcpyAsync(up.p, h.data(), 4 * h.size(), hipMemcpyHostToDevice, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
+        (void)hipGetLastError();
+        c->err = "zk_ctx_update_ring: the update's temporary memory or its upload failed before anything was written; the ring is unchanged";
+        return ZK_E_DEVICE;
+    }
+    const uint32_t *d_ent = up.as<uint32_t>(), *d_src = d_ent + k, *d_blocks = d_ent + 2 * (size_t)k;
+    const uint8_t* d_keys = (const uint8_t*)(d_blocks + b);
+    Soa ring = {R.ring_mem, (uint32_t)R.N};
+    wrote = true;   // from here on the ring is written: a failure abandons it (the caller)
+    launch_ring_scatter(c->stream, d_keys, d_ent, d_src, k, ring);
+    if (R.gk_etab) launch_gk_etab_list(c->stream, ring, nblocks, d_blocks, b, R.gk_etab), c->dbg_etab_blocks += b;
+    if (R.gk_kdig) launch_gkm_ring_digits_list(c->stream, ring, d_blocks, b, R.gk_kdig);
+    if (R.gk_etab && R.gk_edig) launch_gkm_etab_digits_list(c->stream, R.gk_etab, nblocks, d_blocks, b, R.gk_edig);
+    if (kt) {
+        if (real) launch_ktab_build_list(c->stream, ring, d_ent, real, R.ktab, R.ktab_ok, tmp.p, slab), c->dbg_ktab_keys += real;
+        launch_ktab_copy_entry0(c->stream, d_ent + real, k - real, R.ktab, R.ktab_ok);   // behind the fill: entry 0's table is final
+    }
+    launch_ring_digest_list(c->stream, ring, R.N, R.N >= 256 ? d_blocks : nullptr, R.N >= 256 ? b : 1, R.leaves, R.ring_digest);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
+        c->err = "zk_ctx_update_ring: a kernel of the update failed; the ring was dropped";
+        return ZK_E_DEVICE;
+    }
+    R.nkeys = new_nkeys;
+    R.generation++;
+    return ZK_OK;
+}
+extern "C" zk_status zk_ctx_update_ring(zk_ctx* c, uint32_t ring_id, uint64_t count, const uint64_t* index, const uint8_t* keys, uint64_t new_nkeys) {
+    if (!c) return ZK_E_ARG;
+    if (count && (!index || !keys)) {
+        c->err = "zk_ctx_update_ring: index / keys_be32 is NULL";
+        return ZK_E_ARG;
+    }
+    if (c->stream_busy) return busy_refusal(c);
+    Ring* R = find_ring(c, ring_id);
+    if (!R) {
+        c->err = "no resident ring has this id";
+        return ZK_E_ARG;
+    }
+    if (new_nkeys < 2) {
+        c->err = "zk_ctx_update_ring: a ring has at least 2 keys";
+        return ZK_E_ARG;
+    }
+    if (new_nkeys > ((uint64_t)1 << (ZK_MAXN - 4))) {   // (before the loop below: it would shift past 63 bits)
+        c->err = "zk_ctx_update_ring: new_n_keys is beyond the largest ring";
+        return ZK_E_ARG;
+    }
+    uint32_t n = 0;
+    while (((uint64_t)1 << n) < new_nkeys) n++;
+    // last entry per index wins: (index, position) pairs sorted by index, position
+    std::vector<std::pair<uint64_t, uint64_t>> ch(count);
+    for (uint64_t j = 0; j < count; j++) {
+        if (index[j] >= new_nkeys) {
+            c->err = "zk_ctx_update_ring: an index is not below new_n_keys";
+            return ZK_E_ARG;
+        }
+        ch[j] = {index[j], j};
+    }
+    std::sort(ch.begin(), ch.end());
+    std::vector<uint32_t> ent, src;   // distinct supplied entries, ascending, and the position of each one's last key
+    for (uint64_t j = 0; j < count; j++)
+        if (j + 1 == count || ch[j + 1].first != ch[j].first) ent.push_back((uint32_t)ch[j].first), src.push_back((uint32_t)ch[j].second);
+    if (new_nkeys > R->nkeys) {   // every appended position must be supplied
+        const size_t lo = std::lower_bound(ent.begin(), ent.end(), (uint32_t)R->nkeys) - ent.begin();
+        if (ent.size() - lo != new_nkeys - R->nkeys) {
+            c->err = "zk_ctx_update_ring: an appended position has no key";
+            return ZK_E_ARG;
+        }
+    }
+    if (!count && new_nkeys == R->nkeys) return ZK_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const uint64_t N = (uint64_t)1 << n;
+    const bool was_active = c->active >= 0 && R == &c->rings[c->active];
+    if (N != R->N) {   // the padded size changes: a rebuild from the assembled list, as zk_ctx_add_ring would build it
+        DevBuf dk, up;
+        const uint64_t keep = std::min<uint64_t>(R->nkeys, new_nkeys);
+        HIPCHK(c, hipMalloc(&dk.p, 32 * new_nkeys));   // (a failure up to the rebuild below leaves the ring as it was)
+        std::vector<uint32_t> h(2 * ent.size() + 8 * (size_t)count);
+        if (!ent.empty()) {
+            memcpy(h.data(), ent.data(), 4 * ent.size()), memcpy(h.data() + ent.size(), src.data(), 4 * ent.size());
+            memcpy(h.data() + 2 * ent.size(), keys, 32 * (size_t)count);
+            HIPCHK(c, hipMalloc(&up.p, 4 * h.size()));
+            HIPCHK(c, hipMemcpyAsync(up.p, h.data(), 4 * h.size(), hipMemcpyHostToDevice, c->stream));
+        }
+        launch_ring_export(c->stream, Soa{R->ring_mem, (uint32_t)R->N}, keep, dk.as<uint8_t>());
+        launch_keys_scatter(c->stream, (const uint8_t*)(up.as<uint32_t>() + 2 * ent.size()), up.as<uint32_t>(), up.as<uint32_t>() + ent.size(), (uint32_t)ent.size(), dk.as<uint8_t>());
+        HIPCHK(c, hipStreamSynchronize(c->stream));   // (nothing of the ring is written yet)
+        unbind_lanes(c, R);
+        if (was_active) c->ws_C = 0;   // the workspace layout depends on the ring
+        zk_status zs = build_ring(c, *R, dk.as<uint8_t>(), new_nkeys, false);
+        if (zs) abandon_ring(c, R);
+        return zs;
+    }
+    // same padded size: the touched entries are the supplied ones, the tail a truncation turns into padding, and every padding entry when entry 0 is supplied
+    const bool key0 = !ent.empty() && ent[0] == 0;
+    const uint32_t pad_src = key0 ? src[0] : ZK_RU_FROM_ENTRY0;
+    const uint64_t pad_to = key0 ? N : std::max<uint64_t>(R->nkeys, new_nkeys);
+    for (uint64_t e = new_nkeys; e < pad_to; e++) ent.push_back((uint32_t)e), src.push_back(pad_src);   // (all above the supplied indices: the list stays sorted)
+    std::vector<uint8_t> kb(keys, keys + 32 * (size_t)count);
+    bool wrote = false;
+    zk_status zs = patch_ring(c, *R, ent, src, kb, new_nkeys, wrote);
+    if (zs && wrote) abandon_ring(c, R);
+    return zs;
 }
 extern "C" zk_status zk_ring_info(zk_ctx* c, uint32_t ring, uint64_t* n_keys, uint32_t* log_n, uint32_t* flags, uint64_t* generation) {
     if (!c) return ZK_E_ARG;

@@ -233,6 +233,48 @@ extern "C" void zk_test_pool_fail_next_submit(zk_pool* p, int slot) {
     if (p) p->test_fail_slot = slot;
 }
 #define POOL_INJECTED(p, i) ((int)(i) == (p)->test_fail_slot)
+// One order-independent checksum per table of a resident ring (tests/ring_update_checksum_check.py: an updated ring against a freshly built one), test build only:
+// the sum mod 2^64 of mix(word index, word) over the table's 32-bit words (ktab_ok: its bytes); 0 for a table the ring does not have.  The per-key tables of ring
+// values that are no x-coordinate (ktab_ok = 0) are never written by the builder and are left out.  sums: limbs, table E, gk_kdig, gk_edig, ktab, ktab_ok, leaves, digest.
+Ring* zk_resident_ring(zk_ctx* c, uint32_t id);   // api.hip
+__global__ void __launch_bounds__(256) k_test_ring_checksum(const uint32_t* __restrict__ words, const uint8_t* __restrict__ bytes, uint64_t count, const uint8_t* __restrict__ ok,
+                                                            uint64_t words_per_key, unsigned long long* sum) {
+    unsigned long long acc = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (uint64_t)gridDim.x * blockDim.x) {
+        if (ok && !ok[i / words_per_key]) continue;
+        uint64_t x = (i + 1) * 0x9e3779b97f4a7c15ull + (bytes ? bytes[i] : words[i]);
+        x ^= x >> 30, x *= 0xbf58476d1ce4e5b9ull, x ^= x >> 27, x *= 0x94d049bb133111ebull, x ^= x >> 31;
+        acc += x;
+    }
+    atomicAdd(sum, acc);
+}
+extern "C" zk_status zk_test_ring_checksum(zk_ctx* c, uint32_t ring, uint64_t sums[8]) {
+    if (!c || !sums) return ZK_E_ARG;
+    Ring* R = zk_resident_ring(c, ring);
+    if (!R) return ZK_E_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    DevBuf d;
+    HIPCHK(c, hipMalloc(&d.p, 64));
+    HIPCHK(c, hipMemsetAsync(d.p, 0, 64, c->stream));
+    const uint64_t N = R->N, nleaves = (N + 255) / 256;
+    auto run = [&](int slot, const void* p, uint64_t count, bool as_bytes, const uint8_t* ok, uint64_t per_key) {
+        if (!p || !count) return;
+        const uint32_t wgs = (uint32_t)std::min<uint64_t>((count + 255) / 256, 2048);
+        hipLaunchKernelGGL(k_test_ring_checksum, dim3(wgs), dim3(256), 0, c->stream, as_bytes ? nullptr : (const uint32_t*)p, as_bytes ? (const uint8_t*)p : nullptr, count, ok,
+                           per_key, d.as<unsigned long long>() + slot);
+    };
+    run(0, R->ring_mem, 9 * N, false, nullptr, 1);
+    run(1, R->gk_etab, (uint64_t)65536 * 9 * (N >> 8), false, nullptr, 1);
+    run(2, R->gk_kdig, gkm_ring_frag_bytes(N) / 4, false, nullptr, 1);
+    run(3, R->gk_edig, gkm_etab_frag_bytes(N) / 4, false, nullptr, 1);
+    if (R->ktab_ok) run(4, R->ktab, KTAB_KEY_WORDS * N, false, R->ktab_ok, KTAB_KEY_WORDS);
+    run(5, R->ktab_ok, N, true, nullptr, 1);
+    run(6, R->leaves, 8 * nleaves, false, nullptr, 1);
+    run(7, R->ring_digest, 8, false, nullptr, 1);
+    HIPCHK(c, hipMemcpyAsync(sums, d.p, 64, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ZK_OK;
+}
 #else
 #define POOL_INJECTED(p, i) false
 #endif
@@ -472,6 +514,26 @@ extern "C" zk_status zk_pool_add_ring(zk_pool* p, const uint8_t* keys, uint64_t 
     }
     *ring = id[0];
     return ZK_OK;
+}
+// zk_ctx_update_ring on every shard context, concurrently; a shard that fails on its device drops the ring on all of them (no shard serves a ring the others lost)
+void zk_abandon_resident_ring(zk_ctx* c, uint32_t id);   // api.hip
+extern "C" zk_status zk_pool_update_ring(zk_pool* p, uint32_t ring, uint64_t count, const uint64_t* index, const uint8_t* keys, uint64_t new_nkeys) {
+    if (!p || (count && (!index || !keys))) return ZK_E_ARG;
+    const int G = (int)p->ctx.size();
+    for (auto c : p->ctx)   // every shard knows the id and has no job queued before any of them writes
+        if (c->stream_busy || zk_ring_info(c, ring, nullptr, nullptr, nullptr, nullptr)) {
+            p->err = "zk_pool_update_ring: a shard has streamed jobs queued or does not hold this ring";
+            return ZK_E_ARG;
+        }
+    std::vector<zk_status> st(G, ZK_OK);
+    zk_status zs = pool_each(p, [&](int i) { return st[i] = zk_ctx_update_ring(p->ctx[i], ring, count, index, keys, new_nkeys); });
+    bool device_failure = false;
+    for (int i = 0; i < G; i++) device_failure = device_failure || (st[i] != ZK_OK && st[i] != ZK_E_ARG);   // (a refusal wrote nothing, and every shard refuses alike)
+    if (device_failure) {
+        for (auto c : p->ctx) zk_abandon_resident_ring(c, ring);
+        p->err = "zk_pool_update_ring: a shard failed; the ring was dropped on every shard";
+    }
+    return zs;
 }
 extern "C" zk_status zk_pool_use_ring(zk_pool* p, uint32_t ring) {
     if (!p) return ZK_E_ARG;

@@ -563,5 +563,7 @@ extern "C" uint64_t zk_test_counter(const zk_ctx* c, int which) {
         for (uint8_t v : u) n += v != 0;
         return n;
     }
+    if (which == 5) return c->dbg_ktab_keys;     // per-key tables computed by the ring builder (zk_ctx_update_ring's copies do not count)
+    if (which == 6) return c->dbg_etab_blocks;   // 256-key blocks whose table E was built
     return which == 0 ? c->dbg_recheck_proofs : which == 2 ? c->dbg_msm_terms : which == 3 ? c->dbg_p256_batched : 0;
 }

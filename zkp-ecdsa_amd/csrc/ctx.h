@@ -28,6 +28,7 @@ struct Ring {
     uint64_t N = 0, nkeys = 0;
     uint32_t n = 0;
     uint32_t* ring_digest = nullptr;   // [8] SHA-256 words of the padded ring (hardened mode)
+    uint32_t* leaves = nullptr;        // [8 x ceil(N / 256)] the digest's leaf hashes, kept so that zk_ctx_update_ring rehashes the touched leaves and the root only
 };
 struct zk_ctx {
     int device = 0;
@@ -152,6 +153,8 @@ struct zk_ctx {
     uint64_t dbg_recheck_proofs = 0;   // proofs that went through the verifier's per-proof sums since the context was created
     uint64_t dbg_p256_batched = 0;     // proofs whose P-256 relation was accepted by the cross-proof pass (k_pmsm.hip) since the context was created
     uint64_t dbg_msm_terms = 0;        // live terms that went through the batched Tom-256 check (k_msm.hip) since the context was created
+    uint64_t dbg_ktab_keys = 0;        // per-key tables computed by the builder (k_ktab.hip) since the context was created; copied tables do not count
+    uint64_t dbg_etab_blocks = 0;      // 256-key blocks whose table E was built (k_gk.hip) since the context was created
     // timing
     std::vector<TimerRec> trecs;
     std::vector<hipEvent_t> epool;

@@ -66,6 +66,8 @@ static inline size_t tom_tab_words(uint32_t bits) { return (size_t)tom_nwin(bits
 #include "ktab.h"   // layout of the per-key tables of the ring (KTAB_*) and the multiplication through them
 size_t ktab_temp_bytes(uint64_t N, uint32_t slab_keys);
 void launch_ktab_build(hipStream_t s, const Soa& ring, uint64_t N, uint32_t* ktab, uint8_t* ok, void* temp, uint32_t slab_keys);
+// the same kernels over a list of ring entries (zk_ctx_update_ring); temp: ktab_temp_bytes(count, slab_keys), indexed by position in the list
+void launch_ktab_build_list(hipStream_t s, const Soa& ring, const uint32_t* d_keys, uint64_t count, uint32_t* ktab, uint8_t* ok, void* temp, uint32_t slab_keys);
 // per-proof table of R (rtab.h): signed `bits`-bit comb, ceil(257/bits) windows x (2^(bits-1) + 1) entries of 28 words
 #define RTAB_ENTRY_WORDS 28
 #define RTAB_PROVE_BITS 6
@@ -291,12 +293,14 @@ void launch_v_gk_total(hipStream_t s, const VWork& V, const Soa& ring, const uin
 size_t gkm_ring_frag_bytes(uint64_t N);
 size_t gkm_coef_frag_bytes(uint32_t C);
 void launch_gkm_ring_digits(hipStream_t s, const Soa& ring, uint32_t nblocks, int8_t* frag);
+void launch_gkm_ring_digits_list(hipStream_t s, const Soa& ring, const uint32_t* d_blocks, uint32_t nb, int8_t* frag);   // only the listed blocks (zk_ctx_update_ring)
 void launch_v_gk_block_mfma(hipStream_t s, const VWork& V, const int8_t* ring_frag, uint32_t nblocks, uint32_t count, int8_t* coef_frag, const Soa& res);
 // prover: coefficients 2..6 of a block's polynomial (238 of its 255 products a_S * D_S) as int8 matrix products
 struct ChunkIn;
 size_t gkm_etab_frag_bytes(uint64_t N);
 size_t gkm_asub_frag_bytes(uint32_t C);
 void launch_gkm_etab_digits(hipStream_t s, const uint32_t* E, uint32_t nblocks, int8_t* edig);
+void launch_gkm_etab_digits_list(hipStream_t s, const uint32_t* E, uint32_t nblocks, const uint32_t* d_blocks, uint32_t nb, int8_t* edig);   // clears and refills the listed blocks' bytes
 void launch_gk_block_mfma(hipStream_t s, const Workspace& W, const ChunkIn& in, uint32_t nblocks, const Soa& res);
 void launch_v_slot_points(hipStream_t s, const VWork& V, uint32_t count, const uint8_t* proofs, const uint64_t* off, uint64_t first);
 void launch_v_slot_terms(hipStream_t s, const Workspace& W, const VWork& V, uint32_t count, const uint8_t* proofs, const uint64_t* off, const uint8_t* vseeds, uint64_t first);
@@ -419,6 +423,7 @@ static inline uint32_t gk_finish_gsz(uint32_t T, uint32_t ntiles) {
 #define GK_ETAB_MAXN 20
 size_t gk_etab_words(uint64_t N);
 void launch_gk_etab(hipStream_t s, const Soa& ring, uint32_t nblocks, uint32_t* E);
+void launch_gk_etab_list(hipStream_t s, const Soa& ring, uint32_t nblocks, const uint32_t* d_blocks, uint32_t nb, uint32_t* E);   // only the listed blocks' columns (zk_ctx_update_ring)
 void launch_gk_block_stage(hipStream_t s, const Workspace& W, const ChunkIn& in, const Soa& am, const Soa& res);
 struct VWork;
 void launch_v_gk_block_stage(hipStream_t s, const VWork& V, const uint32_t* E, uint32_t nblocks, uint32_t count, uint32_t* csub, const Soa& res);
@@ -447,6 +452,7 @@ void launch_exp_challenge(hipStream_t s, const Workspace& W, uint32_t count);
 void launch_padd_hash(hipStream_t s, const DevParams& P, const Workspace& W, uint32_t items);
 void launch_gk_hash(hipStream_t s, const Workspace& W, uint32_t count, const uint8_t* msg);
 void launch_ring_digest(hipStream_t s, const Soa& ring, uint64_t N, uint32_t* leaf_words /*[8 * ceil(N/256)]*/, uint32_t* digest8);
+void launch_ring_digest_list(hipStream_t s, const Soa& ring, uint64_t N, const uint32_t* d_leaves, uint32_t nl, uint32_t* leaf_words, uint32_t* digest8);   // the listed leaves, then the root
 void launch_test_sha256(hipStream_t s, uint64_t count, uint64_t len, const uint8_t* d_msgs, uint8_t* d_out);
 void launch_test_rng(hipStream_t s, const RngCtx& g, uint64_t B, uint32_t first_k, uint32_t n_k, uint8_t* d_out);
 // k_scalar.hip
@@ -465,6 +471,13 @@ void launch_gk_cd_scalars(hipStream_t s, const Workspace& W, uint32_t count);
 void launch_gk_respond(hipStream_t s, const Workspace& W, const ChunkIn& in, uint8_t* out);
 void launch_test_field(hipStream_t s, int which, int op, uint64_t count, const uint8_t* a, const uint8_t* b, uint8_t* out);
 void launch_ring_load(hipStream_t s, const uint8_t* d_keys_be32, uint64_t nkeys, uint64_t N, const Soa& ring);
+// k_ring_update.hip (zk_ctx_update_ring).  Scatter: ring[entry[i]] = keys[src[i]] reduced like k_ring_load, or ring[0] where src[i] == ZK_RU_FROM_ENTRY0 (padding entries of
+// a ring whose entry 0 is not in the list).  Key tables of padding entries: copies of entry 0's finished table.  Export: the first `count` ring entries as 32-byte integers.
+#define ZK_RU_FROM_ENTRY0 0xffffffffu
+void launch_ring_scatter(hipStream_t s, const uint8_t* d_keys_be32, const uint32_t* d_entry, const uint32_t* d_src, uint32_t count, const Soa& ring);
+void launch_ktab_copy_entry0(hipStream_t s, const uint32_t* d_entry, uint32_t count, uint32_t* ktab, uint8_t* ok);
+void launch_ring_export(hipStream_t s, const Soa& ring, uint64_t count, uint8_t* d_keys_be32);
+void launch_keys_scatter(hipStream_t s, const uint8_t* d_keys_be32, const uint32_t* d_entry, const uint32_t* d_src, uint32_t count, uint8_t* d_out_be32);
 void launch_keys_to_ints(hipStream_t s, const uint8_t* d_pk, uint64_t count, uint8_t* d_out, int32_t* d_st);
 void launch_bytes_to_scalars(hipStream_t s, const uint8_t* d_be32, uint64_t count, const Soa& out);
 void launch_affine_to_bytes(hipStream_t s, const Soa& ax, const Soa& ay, uint64_t count, int tom, uint8_t* d_out);

@@ -48,12 +48,14 @@ __device__ const GkRankTab GK_RT = gk_make_rank_tab();
 
 // ---------------------------------------------------------------- per-ring table E (zk_ctx_set_ring)
 // E[((l_low * 256 + rank(S)) * 9 + limb) * nblocks + block] = limb of D_S(l_low) for that block, canonical, 29-bit limbs.
-__global__ void __launch_bounds__(256) k_gk_etab(Soa ring, uint32_t nblocks, uint32_t* E) {
+// blist (zk_ctx_update_ring): only the nb listed blocks' columns are written; nullptr = every block (nb = nblocks), the full build.
+__global__ void __launch_bounds__(256) k_gk_etab(Soa ring, uint32_t nblocks, const uint32_t* __restrict__ blist, uint32_t nb, uint32_t* E) {
     uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint64_t total = (uint64_t)GKB_SIZE * GKB_SIZE * nblocks;
+    uint64_t total = (uint64_t)GKB_SIZE * GKB_SIZE * nb;
     if (t >= total) return;
-    uint32_t block = (uint32_t)(t % nblocks);
-    uint32_t lr = (uint32_t)(t / nblocks);
+    uint32_t block = (uint32_t)(t % nb);
+    if (blist) block = blist[block];
+    uint32_t lr = (uint32_t)(t / nb);
     uint32_t rank = lr & 255, llow = lr >> 8;
     uint32_t S = GK_RT.subset[rank];
     uint32_t fixed = llow & ~S;
@@ -70,10 +72,12 @@ __global__ void __launch_bounds__(256) k_gk_etab(Soa ring, uint32_t nblocks, uin
 #pragma unroll
     for (int l = 0; l < 9; l++) E[((size_t)lr * 9 + l) * nblocks + block] = o[l];
 }
-void launch_gk_etab(hipStream_t s, const Soa& ring, uint32_t nblocks, uint32_t* E) {
-    uint64_t total = (uint64_t)GKB_SIZE * GKB_SIZE * nblocks;
-    hipLaunchKernelGGL(k_gk_etab, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, s, ring, nblocks, E);
+void launch_gk_etab_list(hipStream_t s, const Soa& ring, uint32_t nblocks, const uint32_t* d_blocks, uint32_t nb, uint32_t* E) {
+    uint64_t total = (uint64_t)GKB_SIZE * GKB_SIZE * nb;
+    if (!total) return;
+    hipLaunchKernelGGL(k_gk_etab, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, s, ring, nblocks, d_blocks, nb, E);
 }
+void launch_gk_etab(hipStream_t s, const Soa& ring, uint32_t nblocks, uint32_t* E) { launch_gk_etab_list(s, ring, nblocks, nullptr, nblocks, E); }
 size_t gk_etab_words(uint64_t N) { return (size_t)GKB_SIZE * GKB_SIZE * 9 * (N / GKB_SIZE); }
 
 // ---------------------------------------------------------------- per chunk: sort by l_low, a_S

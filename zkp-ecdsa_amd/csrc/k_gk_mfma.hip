@@ -46,10 +46,11 @@ ZK_DEV size_t gkm_addr(uint32_t tile, uint32_t r, uint32_t i, uint32_t u) {
     return ((size_t)(tile * 4 + kc) * GKM_ND + u) * GKM_FRAG + (size_t)((g << 4) | r) * 16 + j;
 }
 // ring -> block-side fragments, once per ring (zk_ctx_set_ring): key(block, i), block = tile * 16 + r
-__global__ void __launch_bounds__(256) k_gkm_ring_digits(Soa ring, uint32_t nblocks, int8_t* frag) {
+// blist (zk_ctx_update_ring): workgroup b rewrites block blist[b]'s place inside its 16-block tile; nullptr = block b (nb = nblocks), the full build
+__global__ void __launch_bounds__(256) k_gkm_ring_digits(Soa ring, const uint32_t* __restrict__ blist, uint32_t nb, int8_t* frag) {
     uint32_t t = gtid();
-    if (t >= nblocks * 256) return;
-    uint32_t block = t >> 8, i = t & 255;
+    if (t >= nb * 256) return;
+    uint32_t block = blist ? blist[t >> 8] : t >> 8, i = t & 255;
     uint32_t w[8];
     words_from_limbs<8>(w, soa_ld<ModQ, 1>(ring, block * 256 + i).l);
     int8_t d[GKM_ND];
@@ -288,9 +289,10 @@ __global__ void __launch_bounds__(256, 1) k_v_gk_block_mfma(uint32_t count, cons
 
 size_t gkm_ring_frag_bytes(uint64_t N) { return (size_t)(N >> 12) * GKM_TILE_BYTES; }   // N / 256 blocks, 16 per tile
 size_t gkm_coef_frag_bytes(uint32_t C) { return (size_t)((C + 15) >> 4) * GKM_TILE_BYTES; }
-void launch_gkm_ring_digits(hipStream_t s, const Soa& ring, uint32_t nblocks, int8_t* frag) {
-    hipLaunchKernelGGL(k_gkm_ring_digits, dim3(nblocks), dim3(256), 0, s, ring, nblocks, frag);
+void launch_gkm_ring_digits_list(hipStream_t s, const Soa& ring, const uint32_t* d_blocks, uint32_t nb, int8_t* frag) {
+    if (nb) hipLaunchKernelGGL(k_gkm_ring_digits, dim3(nb), dim3(256), 0, s, ring, d_blocks, nb, frag);
 }
+void launch_gkm_ring_digits(hipStream_t s, const Soa& ring, uint32_t nblocks, int8_t* frag) { launch_gkm_ring_digits_list(s, ring, nullptr, nblocks, frag); }
 void launch_v_gk_block_mfma(hipStream_t s, const VWork& V, const int8_t* ring_frag, uint32_t nblocks, uint32_t count, int8_t* coef_frag, const Soa& res) {
     hipLaunchKernelGGL(k_gkm_coef_digits, dim3(count), dim3(256), 0, s, V, count, coef_frag);
     const uint32_t tiles_p = (count + 15) >> 4, tiles_b = nblocks >> 4;
@@ -321,12 +323,14 @@ ZK_DEV size_t gkp_addr(size_t tile, uint32_t r, uint32_t c, uint32_t kpos, uint3
     return ((tile * GKP_CHUNKS + c) * GKM_ND + u) * GKM_FRAG + (size_t)((((kpos >> 4) & 3) << 4) | r) * 16 + (kpos & 15);
 }
 // table E (29-bit limbs, [l_low][rank][limb][block]) -> digit fragments [l_low][block tile][chunk][digit]; the buffer is zeroed first
-__global__ void __launch_bounds__(256) k_gkm_etab_digits(const uint32_t* __restrict__ E, uint32_t nblocks, int8_t* edig) {
+// blist (zk_ctx_update_ring): only the nb listed blocks are converted (k_gkm_etab_clear zeroes their bytes first); nullptr = every block (nb = nblocks)
+__global__ void __launch_bounds__(256) k_gkm_etab_digits(const uint32_t* __restrict__ E, uint32_t nblocks, const uint32_t* __restrict__ blist, uint32_t nb, int8_t* edig) {
     uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;   // (l_low, rank - 9, block), block fastest
-    uint64_t total = (uint64_t)256 * 238 * nblocks;
+    uint64_t total = (uint64_t)256 * 238 * nb;
     if (t >= total) return;
-    uint32_t block = (uint32_t)(t % nblocks);
-    uint32_t lr = (uint32_t)(t / nblocks), rank = 9 + lr % 238, llow = lr / 238;
+    uint32_t block = (uint32_t)(t % nb);
+    if (blist) block = blist[block];
+    uint32_t lr = (uint32_t)(t / nb), rank = 9 + lr % 238, llow = lr / 238;
     uint32_t l29[9], l30[9], w[8];
 #pragma unroll
     for (int l = 0; l < 9; l++) l29[l] = E[(((size_t)llow * 256 + rank) * 9 + l) * nblocks + block];
@@ -441,7 +445,28 @@ size_t gkm_asub_frag_bytes(uint32_t C) { return (size_t)((C >> 4) + 256 + 1) * G
 void launch_gkm_etab_digits(hipStream_t s, const uint32_t* E, uint32_t nblocks, int8_t* edig) {
     hipMemsetAsync(edig, 0, gkm_etab_frag_bytes((uint64_t)nblocks << 8), s);
     uint64_t total = (uint64_t)256 * 238 * nblocks;
-    hipLaunchKernelGGL(k_gkm_etab_digits, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, s, E, nblocks, edig);
+    hipLaunchKernelGGL(k_gkm_etab_digits, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, s, E, nblocks, nullptr, nblocks, edig);
+}
+// The bytes of edig a block owns: gkp_addr with r = block & 15 fixed -- per (l_low, chunk, digit) four runs of 16 bytes (kpos >> 4 = 0..3), 256 x 6 x 33 x 64 bytes
+// = 3.2 MB per block.  The fill writes kpos < GKP_CNT[chunk] only; the rest is the zero padding of the classes, which the full build gets from its memset.
+__global__ void __launch_bounds__(256) k_gkm_etab_clear(uint32_t nblocks, const uint32_t* __restrict__ blist, uint32_t nb, int8_t* edig) {
+    uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;   // (l_low, chunk, digit, run, listed block), block fastest
+    uint64_t total = (uint64_t)256 * GKP_CHUNKS * GKM_ND * 4 * nb;
+    if (t >= total) return;
+    const uint32_t block = blist[(uint32_t)(t % nb)];
+    uint32_t q = (uint32_t)(t / nb);
+    const uint32_t g = q & 3;
+    q >>= 2;
+    const uint32_t u = q % GKM_ND, c = (q / GKM_ND) % GKP_CHUNKS, llow = q / (GKM_ND * GKP_CHUNKS);
+    const size_t tile = (size_t)llow * (nblocks >> 4) + (block >> 4);
+    *(uint4*)(edig + gkp_addr(tile, block & 15, c, g << 4, u)) = make_uint4(0, 0, 0, 0);   // 16-byte aligned: every term of gkp_addr is a multiple of 16 at kpos & 15 = 0
+}
+void launch_gkm_etab_digits_list(hipStream_t s, const uint32_t* E, uint32_t nblocks, const uint32_t* d_blocks, uint32_t nb, int8_t* edig) {
+    if (!nb) return;
+    uint64_t total = (uint64_t)256 * GKP_CHUNKS * GKM_ND * 4 * nb;
+    hipLaunchKernelGGL(k_gkm_etab_clear, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, s, nblocks, d_blocks, nb, edig);
+    total = (uint64_t)256 * 238 * nb;
+    hipLaunchKernelGGL(k_gkm_etab_digits, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, s, E, nblocks, d_blocks, nb, edig);
 }
 void launch_gk_block_mfma(hipStream_t s, const Workspace& W, const ChunkIn& in, uint32_t nblocks, const Soa& res) {
     const uint32_t tiles_max = (in.count >> 4) + 256;   // ceil(n_g / 16) summed over 256 groups

@@ -414,11 +414,13 @@ void launch_gk_hash(hipStream_t s, const Workspace& W, uint32_t count, const uin
 // ---------------------------------------------------------------- digest of the padded ring (hardened mode)
 // SHA-256("ZKAttest-ring-v1" || be64(N) || leaf_0 || leaf_1 || ...), leaf_i = SHA-256 of ring entries [256 i, 256 i + 256) as
 // 32-byte big-endian integers: one lane per leaf, then one lane over the leaf digests.
-__global__ void __launch_bounds__(64) k_ring_leaves(Soa ring, uint64_t N, uint32_t nleaves, uint32_t* leaf_words) {
+// llist (zk_ctx_update_ring): lane i rehashes leaf llist[i] of the resident leaves; nullptr = leaf i (nleaves of them), the full build
+__global__ void __launch_bounds__(64) k_ring_leaves(Soa ring, uint64_t N, const uint32_t* __restrict__ llist, uint32_t nleaves, uint32_t* leaf_words) {
     __shared__ uint32_t lds[16 * 64];
     uint32_t t = gtid();
     bool live = t < nleaves;
     if (!live) t = nleaves - 1;
+    if (llist) t = llist[t];
     ShaStream s;
     s.init(lds, threadIdx.x, 64);
     uint64_t e0 = (uint64_t)t * 256, e1 = e0 + 256 < N ? e0 + 256 : N;
@@ -450,10 +452,14 @@ __global__ void __launch_bounds__(64) k_ring_root(uint64_t N, uint32_t nleaves, 
     s.finish(h);
     for (int i = 0; i < 8; i++) digest8[i] = h[i];
 }
-void launch_ring_digest(hipStream_t s, const Soa& ring, uint64_t N, uint32_t* leaf_words, uint32_t* digest8) {
+// rehashes the nl leaves d_leaves[0..nl) (nullptr: all of them) into leaf_words, then the root over every leaf
+void launch_ring_digest_list(hipStream_t s, const Soa& ring, uint64_t N, const uint32_t* d_leaves, uint32_t nl, uint32_t* leaf_words, uint32_t* digest8) {
     uint32_t nleaves = (uint32_t)((N + 255) / 256);
-    hipLaunchKernelGGL(k_ring_leaves, dim3((nleaves + 63) / 64), dim3(64), 0, s, ring, N, nleaves, leaf_words);
+    if (nl) hipLaunchKernelGGL(k_ring_leaves, dim3((nl + 63) / 64), dim3(64), 0, s, ring, N, d_leaves, nl, leaf_words);
     hipLaunchKernelGGL(k_ring_root, dim3(1), dim3(64), 0, s, N, nleaves, leaf_words, digest8);
+}
+void launch_ring_digest(hipStream_t s, const Soa& ring, uint64_t N, uint32_t* leaf_words, uint32_t* digest8) {
+    launch_ring_digest_list(s, ring, N, nullptr, (uint32_t)((N + 255) / 256), leaf_words, digest8);
 }
 
 // ---------------------------------------------------------------- unit-test hooks

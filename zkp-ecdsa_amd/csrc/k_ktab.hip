@@ -15,17 +15,19 @@
 #define KTB_BASE_WORDS 28   // X, Y, Z (9 limbs each) + pad
 #define KTB_TMP_WORDS 36    // X, Y, Z, prefix product of the Z's before this entry
 
-__global__ void __launch_bounds__(64) k_ktab_base(Soa ring, uint32_t N, uint32_t* bases, uint8_t* ok) {
+// klist (zk_ctx_update_ring): slot i of the temp area belongs to ring entry klist[i]; nullptr = entry i (count = N), the full build
+__global__ void __launch_bounds__(64) k_ktab_base(Soa ring, uint32_t count, const uint32_t* __restrict__ klist, uint32_t* bases, uint8_t* ok) {
     uint32_t i = gtid();
-    if (i >= N) return;
+    if (i >= count) return;
+    const uint32_t key = klist ? klist[i] : i;
     const auto b = fe_const<ModQ, 1>(P256_B_M);
-    Fq2 x = fe_to_mont(soa_ld<ModQ, 1>(ring, i));
+    Fq2 x = fe_to_mont(soa_ld<ModQ, 1>(ring, key));
     auto x2 = x * x;
     auto x3 = x2 * x;
     Fq2 rhs = fe_reduce((x3 + b) - (x + x + x));
     Fq2 y = fe_pow_words<ModQ>(rhs, ModQ::exp_sqrt);
     bool good = fe_eq(y * y, rhs);
-    ok[i] = good ? 1 : 0;
+    ok[key] = good ? 1 : 0;
     if (!good) return;
     P256Aff a;
     a.x = x, a.y = y;
@@ -49,13 +51,14 @@ ZK_DEV Fe<ModQ, K> ktb_ld9(const uint32_t* e) {
     for (int k = 0; k < NLIMB; k++) r.l[k] = e[k];
     return r;
 }
-__global__ void __launch_bounds__(256) k_ktab_fill(const uint32_t* __restrict__ bases, const uint8_t* __restrict__ ok, uint32_t first, uint32_t count, uint32_t* tmp,
-                                                   uint32_t* ktab) {
+__global__ void __launch_bounds__(256) k_ktab_fill(const uint32_t* __restrict__ bases, const uint8_t* __restrict__ ok, const uint32_t* __restrict__ klist, uint32_t first,
+                                                   uint32_t count, uint32_t* tmp, uint32_t* ktab) {
     uint32_t t = gtid();
     if (t >= count * KTAB_NWIN) return;
-    const uint32_t key = first + t / KTAB_NWIN, w = t % KTAB_NWIN;
+    const uint32_t slot = first + t / KTAB_NWIN, w = t % KTAB_NWIN;   // slot: where the key's bases lie in the temp area
+    const uint32_t key = klist ? klist[slot] : slot;
     if (!ok[key]) return;
-    const P256Pt base = ld_rtab(bases + ((size_t)key * KTAB_NWIN + w) * KTB_BASE_WORDS);
+    const P256Pt base = ld_rtab(bases + ((size_t)slot * KTAB_NWIN + w) * KTB_BASE_WORDS);
     uint32_t* my = tmp + (size_t)t * KTAB_ENT * KTB_TMP_WORDS;
     uint32_t* out = ktab + ((size_t)key * KTAB_NWIN + w) * KTAB_ENT * KTAB_ENTRY_WORDS;
     P256Pt acc = base;
@@ -81,12 +84,17 @@ __global__ void __launch_bounds__(256) k_ktab_fill(const uint32_t* __restrict__ 
 size_t ktab_temp_bytes(uint64_t N, uint32_t slab_keys) {
     return sizeof(uint32_t) * ((size_t)N * KTAB_NWIN * KTB_BASE_WORDS + (size_t)slab_keys * KTAB_NWIN * KTAB_ENT * KTB_TMP_WORDS);
 }
-void launch_ktab_build(hipStream_t s, const Soa& ring, uint64_t N, uint32_t* ktab, uint8_t* ok, void* temp, uint32_t slab_keys) {
+// the tables of the `count` ring entries d_keys[0..count) (nullptr: entries 0..count); temp: ktab_temp_bytes(count, slab_keys), indexed by position in the list
+void launch_ktab_build_list(hipStream_t s, const Soa& ring, const uint32_t* d_keys, uint64_t count, uint32_t* ktab, uint8_t* ok, void* temp, uint32_t slab_keys) {
+    if (!count) return;
     uint32_t* bases = (uint32_t*)temp;
-    uint32_t* tmp = bases + (size_t)N * KTAB_NWIN * KTB_BASE_WORDS;
-    hipLaunchKernelGGL(k_ktab_base, dim3((uint32_t)((N + 63) / 64)), dim3(64), 0, s, ring, (uint32_t)N, bases, ok);
-    for (uint64_t first = 0; first < N; first += slab_keys) {
-        uint32_t cnt = (uint32_t)std::min<uint64_t>(slab_keys, N - first);
-        hipLaunchKernelGGL(k_ktab_fill, dim3((cnt * KTAB_NWIN + 255) / 256), dim3(256), 0, s, bases, ok, (uint32_t)first, cnt, tmp, ktab);
+    uint32_t* tmp = bases + (size_t)count * KTAB_NWIN * KTB_BASE_WORDS;
+    hipLaunchKernelGGL(k_ktab_base, dim3((uint32_t)((count + 63) / 64)), dim3(64), 0, s, ring, (uint32_t)count, d_keys, bases, ok);
+    for (uint64_t first = 0; first < count; first += slab_keys) {
+        uint32_t cnt = (uint32_t)std::min<uint64_t>(slab_keys, count - first);
+        hipLaunchKernelGGL(k_ktab_fill, dim3((cnt * KTAB_NWIN + 255) / 256), dim3(256), 0, s, bases, ok, d_keys, (uint32_t)first, cnt, tmp, ktab);
     }
+}
+void launch_ktab_build(hipStream_t s, const Soa& ring, uint64_t N, uint32_t* ktab, uint8_t* ok, void* temp, uint32_t slab_keys) {
+    launch_ktab_build_list(s, ring, nullptr, N, ktab, ok, temp, slab_keys);
 }
