@@ -41,6 +41,9 @@ export function setOption(name: 'ringDelta', value: number): void
 /** one statement per proof over its own ring: keyLists[i] is proof i's ring.  The rings stay resident on the params' engine (Engine.setOption('residentRings')),
  *  every call is one mixed-ring batch on the GPU (split only when it names more rings than are kept resident) */
 export function verifySignatureLists(params: SystemParametersList, msgHashes: Uint8Array[], keyLists: (bigint[] | Buffer)[], proofs: (SignatureProofList | Buffer)[]): Promise<Verdicts>
+/** B statements over several rings in one call, proved: keyLists[i] is the ring of proof i and whichs[i] indexes it (zk_prove_batch_rings).  The rings stay resident
+ *  through the cache verifySignatureLists uses; a call is split only when it names more rings than residentRings. */
+export function proveSignatureLists(params: SystemParametersList, msgHashes: Uint8Array[], sigs: Uint8Array[], publicKeys: PublicKey[], whichs: number[], keyLists: (bigint[] | Buffer)[]): Promise<SignatureProofList[]>
 type Newable<T> = new (...args: any[]) => T
 export function writeJson<T>(type: Newable<T>, object: T): string
 export function readJson<T>(type: Newable<T>, text: string): T
@@ -73,6 +76,9 @@ export class Engine {
     /** one resident ring id per proof (zk_pool_verify_batch_rings) */
     verifyBatchRings(msg: Buffer, proofs: Buffer[], ringIds: number[] | Uint32Array, seeds?: Buffer): Verdicts
     verifyBatchRingsAsync(msg: Buffer, proofs: Buffer[], ringIds: number[] | Uint32Array, seeds?: Buffer): Promise<Verdicts>
+    /** zk_prove_batch_rings: which[b] indexes resident ring ringIds[b]; the active ring plays no part */
+    proveBatchRings(msg: Buffer, sig: Buffer, pk: Buffer, which: number[] | Buffer, ringIds: number[] | Uint32Array, seeds?: Buffer): Buffer[]
+    proveBatchRingsAsync(msg: Buffer, sig: Buffer, pk: Buffer, which: number[] | Buffer, ringIds: number[] | Uint32Array, seeds?: Buffer): Promise<Buffer[]>
     keysToInts(pkxy: Buffer): { keys: Buffer; status: Buffer }
     proveBatch(msg: Buffer, sig: Buffer, pk: Buffer, which: number[] | Buffer, seeds?: Buffer): Buffer[]
     verifyBatch(msg: Buffer, proofs: Buffer[], seeds?: Buffer): Verdicts

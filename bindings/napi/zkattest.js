@@ -373,6 +373,16 @@ class Engine {
         if (!pk.n) return Promise.resolve(verdicts(null, pk.slot))
         return native.verifyBatchRingsAsync(this.h, msgOf(msg, pk), pk.blob, pk.off, pk.len, idsOf(ringIds, pk), seedsOf(seeds, pk)).then((r) => verdicts(r, pk.slot))
     }
+    // one resident ring id per proof (zk_prove_batch_rings): which[b] indexes ring ringIds[b]; the active ring plays no part.  -> array of proof Buffers
+    proveBatchRings(msg, sig, pk, which, ringIds, seeds) {
+        const [B, w, s] = this._proveArgs(msg, which, seeds)
+        return unpackProofs(native.proveBatchRings(this.h, msg, sig, pk, w, Buffer.from(Uint32Array.from(ringIds).buffer), s), B)
+    }
+    _proveRingsNow(msg, sig, pk, which, ringIds, seeds) {
+        const [B, w, s] = this._proveArgs(msg, which, seeds)
+        return native.proveBatchRingsAsync(this.h, msg, sig, pk, w, Buffer.from(Uint32Array.from(ringIds).buffer), s).then((r) => unpackProofs(r, B))
+    }
+    proveBatchRingsAsync(msg, sig, pk, which, ringIds, seeds) { return this._chain(() => this._proveRingsNow(msg, sig, pk, which, ringIds, seeds)) }
     verifyBatchRingsAsync(msg, proofs, ringIds, seeds) { return this._chain(() => this._verifyRingsNow(msg, proofs, ringIds, seeds)) }
     proveBatchAsync(msg, sig, pk, which, seeds) { return this._chain(() => this._proveNow(msg, sig, pk, which, seeds)) }
     verifyBatchAsync(msg, proofs, seeds) { return this._chain(() => this._verifyNow(msg, proofs, seeds)) }
@@ -601,6 +611,39 @@ async function verifySignatureListBatch(params, msgHashes, keys, proofs) {
     Object.defineProperty(out, 'errors', { value: errors })
     return out
 }
+// B statements over several rings in one call, proved: keyLists[i] is the ring of proof i and whichs[i] indexes it -- the reference's proveSignatureList takes
+// `keys` with every call (src/zkpAttestList.ts:104-145), this is that interface over a batch.  The rings are kept resident through the cache
+// verifySignatureLists uses; a call is split only when it names more rings than residentRings, and each part is ONE zk_prove_batch_rings.  -> SignatureProofList[]
+// in the order given; throws the reference's error text for the first proof that fails, like proveSignatureListBatch.
+async function proveSignatureLists(params, msgHashes, sigs, publicKeys, whichs, keyLists) {
+    const B = msgHashes.length
+    if (sigs.length !== B || publicKeys.length !== B || whichs.length !== B || keyLists.length !== B)
+        throw new RangeError('proveSignatureLists: one signature, one public key, one index and one key list per message hash')
+    const raws = await Promise.all(publicKeys.map(rawPublicKey))
+    for (const r of raws) if (r.length !== 65 || r[0] !== 4) throw new Error('invalid public key')
+    const rings = [], ringOfProof = new Array(B), byTag = new Map()
+    keyLists.forEach((keys, i) => {
+        checkRingSize(Buffer.isBuffer(keys) ? keys.length / 32 : keys.length, true)
+        const r = ringOf(keys)
+        if (!byTag.has(r.tag)) { byTag.set(r.tag, rings.length); rings.push(r) }
+        ringOfProof[i] = byTag.get(r.tag)
+    })
+    if (!B) return []
+    const { withRings, capacity } = engineFor(params, keyLists[0])
+    const out = new Array(B), wire = wireLayout, per = capacity()
+    for (let g = 0; g < rings.length; g += per) {   // groups of at most residentRings rings: one group unless the call names more
+        const sel = []
+        for (let i = 0; i < B; i++) if (ringOfProof[i] >= g && ringOfProof[i] < g + per) sel.push(i)
+        const cat = (f) => Buffer.concat(sel.map(f))
+        const proofs = await withRings(rings.slice(g, g + per), (engine, ids) => {
+            useWire(engine, wire)
+            return engine._proveRingsNow(cat((i) => Buffer.from(msgHashes[i])), cat((i) => Buffer.from(sigs[i])), cat((i) => raws[i].slice(1)), sel.map((i) => whichs[i]),
+                sel.map((i) => ids[ringOfProof[i] - g]))
+        })
+        sel.forEach((i, k) => { out[i] = new SignatureProofList(proofs[k]) })
+    }
+    return out
+}
 // B statements over several rings in one call: keyLists[i] is the ring of proof i.  The rings are made resident on the params' engine (residentRings at a
 // time: a call that names more rings than that is split by ring) and every wire layout's proofs go through ONE zk_verify_batch_rings.  -> booleans with
 // .errors, like verifySignatureListBatch.
@@ -636,6 +679,6 @@ async function verifySignatureLists(params, msgHashes, keyLists, proofs) {
     return out
 }
 
-module.exports = { verifySignatureLists, _ringGenerations, setVerifyLevel, getVerifyLevel, generateParamsList, generateParamsListHardened, keyToInt, proveSignatureList, verifySignatureList, proveSignatureListBatch, verifySignatureListBatch,
+module.exports = { verifySignatureLists, proveSignatureLists, _ringGenerations, setVerifyLevel, getVerifyLevel, generateParamsList, generateParamsListHardened, keyToInt, proveSignatureList, verifySignatureList, proveSignatureListBatch, verifySignatureListBatch,
     writeJson, readJson, writeJsonBatch, readJsonBatch, SignatureProofList, SystemParametersList, PedersenParams, generatePedersenParams, p256, tomEdwards256, ALL_GROUPS,
     Group, Point, Scalar, Engine, shutdown, setWireLayout, getWireLayout, setOption, native }

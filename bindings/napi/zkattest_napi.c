@@ -337,7 +337,7 @@ typedef struct Job {
     uint64_t worst_cap, *off, *len;
     int32_t *status;
     uint8_t *ok;
-    uint32_t *ring_ids; /* verifyBatchRings: one resident ring id per proof */
+    uint32_t *ring_ids; /* verifyBatchRings, proveBatchRings: one resident ring id per proof */
     zk_status rc;
     char err[384];
     napi_deferred deferred;
@@ -364,9 +364,8 @@ static void job_free(napi_env env, Job *j) {
     free(j);
 }
 /* output capacity for B proofs over G devices: mean + 8 sigma of the zero-bit repetitions per shard, at most the worst case */
-static void prove_caps(Handle *h, size_t B, uint64_t *cap, uint64_t *worst) {
+static void prove_caps(Handle *h, size_t B, uint64_t mx, uint64_t *cap, uint64_t *worst) {
     uint64_t G = (uint64_t)zk_pool_size(h->pool), m = (B + G - 1) / G;
-    uint64_t mx = zk_proof_max_size(zk_pool_ctx(h->pool, 0));
     uint64_t w = ((mx * (m ? m : 1) + 511) & ~(uint64_t)255) * G;
     double mean = (double)m * ((double)mx - 3392.0 * h->sec / 2.0), dev = 8.0 * 3392.0 * sqrt((double)m * h->sec / 4.0);
     uint64_t c = (((uint64_t)(mean + dev) + mx + 511) & ~(uint64_t)255) * G;
@@ -381,11 +380,13 @@ static void job_execute(napi_env env, void *data) { /* worker thread (or inline 
         j->rc = zk_pool_verify_batch(p, j->B, j->msg, j->proofs_in, j->off, j->len, j->seeds, j->ok, j->status);
     } else {
         zk_rng rng = {ZK_RNG_SEED, j->seeds, 0};
-        j->rc = zk_pool_prove_batch(p, j->B, j->msg, j->sig, j->pk, j->which, &rng, j->out.p, j->out.cap, j->off, j->len, j->status);
-        if (j->rc == ZK_E_BUFFER && j->out.cap < j->worst_cap) { /* 8 sigma were not enough: worst-case buffer */
-            slab_free(&j->out);
-            if (slab_alloc(&j->out, j->worst_cap))
-                j->rc = zk_pool_prove_batch(p, j->B, j->msg, j->sig, j->pk, j->which, &rng, j->out.p, j->out.cap, j->off, j->len, j->status);
+        for (int pass = 0; pass < 2; pass++) {
+            if (j->ring_ids)
+                j->rc = zk_pool_prove_batch_rings(p, j->B, j->msg, j->sig, j->pk, j->which, j->ring_ids, &rng, j->out.p, j->out.cap, j->off, j->len, j->status);
+            else j->rc = zk_pool_prove_batch(p, j->B, j->msg, j->sig, j->pk, j->which, &rng, j->out.p, j->out.cap, j->off, j->len, j->status);
+            if (j->rc != ZK_E_BUFFER || j->out.cap >= j->worst_cap) break;
+            slab_free(&j->out); /* 8 sigma were not enough: worst-case buffer */
+            if (!slab_alloc(&j->out, j->worst_cap)) break;
         }
     }
     if (j->rc != ZK_OK) snprintf(j->err, sizeof j->err, "%s: %s", zk_strerror(j->rc), zk_pool_last_error(p));
@@ -453,10 +454,17 @@ static napi_value job_run(napi_env env, Job *j, const char *name) {
     return promise;
 }
 /* (h, msg Bx32, sig Bx64, pk Bx64, which Bx4 (u32 LE), seeds Bx32)
- *   -> {proofs: Buffer, offsets: B u64 LE, lengths: B u64 LE, status: B i32}   proof b = proofs[offsets[b] .. offsets[b] + lengths[b]) */
-static napi_value prove_common(napi_env env, napi_callback_info info, int async) {
-    napi_value argv[6];
-    if (!get_args(env, info, 6, argv)) return NULL;
+ *   -> {proofs: Buffer, offsets: B u64 LE, lengths: B u64 LE, status: B i32}   proof b = proofs[offsets[b] .. offsets[b] + lengths[b])
+ * rings: (h, msg, sig, pk, which, ringIds (B u32 LE), seeds) -- zk_pool_prove_batch_rings: which[b] indexes ring ringIds[b] */
+static napi_value prove_common(napi_env env, napi_callback_info info, int async, int rings) {
+    napi_value argv[7];
+    if (!get_args(env, info, rings ? 7 : 6, argv)) return NULL;
+    uint8_t *ids = NULL;
+    size_t lid = 0;
+    if (rings) {
+        if (!get_bytes(env, argv[5], &ids, &lid)) return NULL;
+        argv[5] = argv[6];
+    }
     Handle *h = get_handle(env, argv[0], 0);
     uint8_t *msg, *sig, *pk, *which, *seeds;
     size_t lm, ls, lp, lw, lse;
@@ -464,7 +472,7 @@ static napi_value prove_common(napi_env env, napi_callback_info info, int async)
         !get_bytes(env, argv[4], &which, &lw) || !get_bytes(env, argv[5], &seeds, &lse))
         return NULL;
     size_t B = lm / 32;
-    if (!B || lm != 32 * B || ls != 64 * B || lp != 64 * B || lw != 4 * B || lse != 32 * B) {
+    if (!B || lm != 32 * B || ls != 64 * B || lp != 64 * B || lw != 4 * B || lse != 32 * B || (rings && (!ids || lid != 4 * B))) {
         napi_throw_range_error(env, NULL, "proveBatch: per proof 32-byte msgHash, 64-byte signature, 64-byte public key, u32 index, 32-byte seed");
         return NULL;
     }
@@ -473,10 +481,18 @@ static napi_value prove_common(napi_env env, napi_callback_info info, int async)
     j->h = h, j->B = B, j->async = async;
     j->msg = dup_bytes(msg, lm), j->sig = dup_bytes(sig, ls), j->pk = dup_bytes(pk, lp), j->seeds = dup_bytes(seeds, lse);
     j->which = (uint32_t *)dup_bytes(which, lw);
-    uint64_t cap;
-    prove_caps(h, B, &cap, &j->worst_cap);
+    j->ring_ids = rings ? (uint32_t *)dup_bytes(ids, lid) : NULL;
+    uint64_t cap, mx = zk_proof_max_size(zk_pool_ctx(h->pool, 0));
+    if (rings) { /* the largest proof over the resident rings the batch names; the active ring plays no part */
+        mx = 32;
+        for (size_t b = 0; j->ring_ids && b < B; b++) {
+            uint64_t m = !b || j->ring_ids[b] != j->ring_ids[b - 1] ? zk_ring_proof_max_size(zk_pool_ctx(h->pool, 0), j->ring_ids[b]) : 0;
+            if (m > mx) mx = m;
+        }
+    }
+    prove_caps(h, B, mx, &cap, &j->worst_cap);
     j->off = malloc(8 * B), j->len = malloc(8 * B), j->status = malloc(4 * B);
-    if (!j->msg || !j->sig || !j->pk || !j->seeds || !j->which || !j->off || !j->len || !j->status || !slab_alloc(&j->out, cap)) {
+    if (!j->msg || !j->sig || !j->pk || !j->seeds || !j->which || !j->off || !j->len || !j->status || (rings && !j->ring_ids) || !slab_alloc(&j->out, cap)) {
         job_free(env, j);
         return throw_text(env, ZK_E_BUFFER, "out of memory");
     }
@@ -486,8 +502,10 @@ static napi_value prove_common(napi_env env, napi_callback_info info, int async)
     }
     return job_run(env, j, "zkattest.proveBatch");
 }
-static napi_value ProveBatch(napi_env env, napi_callback_info info) { return prove_common(env, info, 0); }
-static napi_value ProveBatchAsync(napi_env env, napi_callback_info info) { return prove_common(env, info, 1); }
+static napi_value ProveBatch(napi_env env, napi_callback_info info) { return prove_common(env, info, 0, 0); }
+static napi_value ProveBatchAsync(napi_env env, napi_callback_info info) { return prove_common(env, info, 1, 0); }
+static napi_value ProveBatchRings(napi_env env, napi_callback_info info) { return prove_common(env, info, 0, 1); }
+static napi_value ProveBatchRingsAsync(napi_env env, napi_callback_info info) { return prove_common(env, info, 1, 1); }
 /* (h, msg Bx32, proofs, offsets (B u64 LE), lengths (B u64 LE), seeds Bx32 | null) -> {ok: B bytes, status: B i32}
  * rings: (h, msg, proofs, offsets, lengths, ringIds (B u32 LE), seeds | null) -- zk_pool_verify_batch_rings */
 static napi_value verify_common(napi_env env, napi_callback_info info, int async, int rings) {
@@ -1002,7 +1020,8 @@ static napi_value Init(napi_env env, napi_value exports) {
                {"proofsToJsonBatch", ProofsToJsonBatch}, {"proofsFromJsonBatch", ProofsFromJsonBatch},
                {"proveSubmit", ProveSubmit},     {"verifySubmit", VerifySubmit},
                {"addRing", AddRing},             {"useRing", UseRing},               {"dropRing", DropRing},           {"updateRing", UpdateRing},       {"ringInfo", RingInfo},
-               {"verifyBatchRings", VerifyBatchRings}, {"verifyBatchRingsAsync", VerifyBatchRingsAsync}};
+               {"verifyBatchRings", VerifyBatchRings}, {"verifyBatchRingsAsync", VerifyBatchRingsAsync},
+               {"proveBatchRings", ProveBatchRings},   {"proveBatchRingsAsync", ProveBatchRingsAsync}};
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;
         if (napi_create_function(env, fns[i].name, NAPI_AUTO_LENGTH, fns[i].fn, NULL, &f) != napi_ok) return NULL;

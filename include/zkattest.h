@@ -179,6 +179,9 @@ zk_status zk_proof_unpack(const uint8_t *zka1p, uint64_t len, uint8_t *out, uint
 /* Upper bound of one proof's size, in the context's wire layout, for the current params/ring. */
 uint64_t zk_proof_max_size(const zk_ctx *ctx);
 
+/* The same for a resident ring that need not be active (what zk_prove_batch_rings can write per proof of that ring); 0 for an id that is not resident. */
+uint64_t zk_ring_proof_max_size(const zk_ctx *ctx, uint32_t ring);
+
 /* Page-locked host memory for the big buffers of the host-pointer entry points (`out` of zk_prove_batch, `proofs` of
  * zk_verify_batch: ~169 KB per proof at secLevel 80).  With such a buffer the proof bytes move by DMA chunk by chunk while
  * the neighbouring chunks are being proved / verified; with ordinary (pageable) memory the runtime stages one blocking copy
@@ -321,6 +324,34 @@ zk_status zk_verify_batch_rings(zk_ctx *ctx, uint64_t B, const uint8_t *msg_hash
 zk_status zk_verify_batch_rings_device(zk_ctx *ctx, uint64_t B, const void *d_msg_hash, const void *d_proofs, const void *d_proof_off,
                                        const void *d_ring_ids, const void *d_verifier_seeds, void *d_ok, void *d_per_proof_status);
 
+/* Mixed-ring proving: zk_prove_batch[_device] with one resident ring id per proof -- the reference takes `keys` with every proveSignatureList call
+ * (src/zkpAttestList.ts:104-145); this is that interface over a batch.  Proof b and per_proof_status[b] are byte for byte what zk_prove_batch returns for
+ * input b with ring ring_ids[b] active, under the same randomness contract (fill k of proof b depends on b's own seed or stream only): which[b] indexes THAT
+ * ring's padded size, every per-proof status of the one-ring call appears unchanged and touches no neighbour, both wire layouts and hardened mode (each ring
+ * with its own digest) are honoured, and the per-key tables are used where the proof's ring has them.  A proof whose id is not resident gets ZK_E_ARG and an
+ * empty proof.  The proofs lie in `out` back to back in index order, out_off[0] = 0: the result can be handed to zk_verify_batch_rings with the same ring_ids
+ * as it is.  `out` may be pageable, page-locked or HBM of the context's device, as for zk_prove_batch; ZK_E_BUFFER when out_cap is too small (no proof is
+ * larger than zk_proof_max_size with the batch's largest ring active).  The active ring is neither read nor changed, and a context whose rings are all
+ * inactive can prove.  ZK_E_BUFFER before zk_ctx_set_params, ZK_E_ARG for NULL arguments and while streamed jobs are queued; there are no streamed variants.
+ * How: the ids are classed -- on the host for host-pointer calls, by one census kernel and ONE read-back of its counters for the device call.  A batch of one
+ * ring runs the usual pipeline on the caller's buffers with that ring bound and nothing else.  Otherwise the batch is cut into index-contiguous segments
+ * (multiples of 256 proofs) whose proofs fit a grow-only staging buffer in HBM (8 GiB of proofs at most; it is an optional workspace like the lanes': the
+ * per-key tables are given up before it); per segment and ring, windows of at most 2 x chunk x lanes proofs are gathered (inputs and seeds, or the
+ * proof's whole stream in ZK_RNG_STREAM mode), proved with their ring bound into the staging buffer, and -- a proof's size being known only once it is
+ * made -- one scan over the segment's lengths in index order writes out_off and one kernel moves the bytes to their final place behind the previous
+ * segment's; with a page-locked `out` a finished segment crosses the link while the next one is proved.  zk_test_counter 7 / 8 count the segments and
+ * windows.  The gathered signatures, seeds and streams are witness-derived: zk_ctx_wipe, zk_ctx_destroy and a failed call zero them.
+ * Memory of a mixed batch beyond the one-ring call's: the staging buffer (at most 8 GiB, or 256 of the largest proofs), the window's inputs (2 x chunk x lanes x
+ * 196 bytes; in ZK_RNG_STREAM mode 2 x chunk x lanes whole streams, 32 x stride_blocks bytes each -- 1.9 GB at the default chunk and lanes, secLevel 80), and, for
+ * host pointers, the whole batch's inputs in HBM at once (B streams in ZK_RNG_STREAM mode: callers of that mode bound B themselves); all grow-only.
+ * zk_pool_prove_batch_rings: zk_pool_prove_batch's contiguous shards and output regions with the ids of zk_pool_add_ring. */
+zk_status zk_prove_batch_rings(zk_ctx *ctx, uint64_t B, const uint8_t *msg_hash /*Bx32*/, const uint8_t *sig /*Bx64*/, const uint8_t *pk_xy /*Bx64*/,
+                               const uint32_t *which /*B*/, const uint32_t *ring_ids /*B*/, const zk_rng *rng, uint8_t *out, uint64_t out_cap,
+                               uint64_t *out_off /*B+1*/, int32_t *per_proof_status /*B*/);
+zk_status zk_prove_batch_rings_device(zk_ctx *ctx, uint64_t B, const void *d_msg_hash, const void *d_sig, const void *d_pk_xy, const void *d_which,
+                                      const void *d_ring_ids /*u32[B]*/, const zk_rng *rng_device, void *d_out, uint64_t out_cap,
+                                      void *d_out_off /*u64[B+1]*/, void *d_per_proof_status /*i32[B]*/);
+
 /* ---- two (or more) batches in flight on one context.  zk_prove_batch / zk_verify_batch are synchronous: each call pays its own head
  * (no byte of a chunk exists before its stage 1 is over) and its own tail (the copies of the last slices, with nothing left to
  * hide them).  The submit / wait pair splits a call so that the pipeline keeps running ACROSS calls: submit stages the inputs and
@@ -391,6 +422,10 @@ zk_status zk_pool_update_ring(zk_pool *pool, uint32_t ring, uint64_t count, cons
 zk_status zk_pool_prove_batch(zk_pool *pool, uint64_t B, const uint8_t *msg_hash, const uint8_t *sig, const uint8_t *pk_xy, const uint32_t *which,
                               const zk_rng *rng, uint8_t *out, uint64_t out_cap, uint64_t *out_off /*B*/, uint64_t *out_len /*B*/,
                               int32_t *per_proof_status /*B*/);
+/* zk_prove_batch_rings over all devices, with the output layout of zk_pool_prove_batch */
+zk_status zk_pool_prove_batch_rings(zk_pool *pool, uint64_t B, const uint8_t *msg_hash, const uint8_t *sig, const uint8_t *pk_xy, const uint32_t *which,
+                                    const uint32_t *ring_ids /*B*/, const zk_rng *rng, uint8_t *out, uint64_t out_cap, uint64_t *out_off /*B*/,
+                                    uint64_t *out_len /*B*/, int32_t *per_proof_status /*B*/);
 /* The same with the proofs left in HBM: shard i writes its proofs back to back from d_out[i], a buffer of out_cap[i] bytes on
  * device_ids[i] (zk_pool_device_alloc / zk_pool_device_free); out_off[b] is relative to the proof's own shard buffer.  Only the 160 bytes of
  * inputs per proof cross PCIe: through this entry point a multi-GPU run measures the GPUs and their host threads without the node's host
@@ -504,14 +539,20 @@ int zk_pool_test_locality(const char *pci_bus_id, int *numa_node, int *cpus, int
  * 4 = dependent chains of small calls handed to cooperating waves so far (k_coop.hip: Straus sums, the table of R), process-wide;
  * 5 = per-key tables COMPUTED by the ring builder since the context was created (a full build computes one per padded entry; the tables zk_ctx_update_ring
  *     copies from entry 0 for padding entries do not count);
- * 6 = 256-key blocks whose table E was built since the context was created */
+ * 6 = 256-key blocks whose table E was built since the context was created;
+ * 7 = segments that mixed-ring prove calls (zk_prove_batch_rings) staged since the context was created -- a call of one ring stages none;
+ * 8 = windows those calls proved;
+ * 9 = bytes of the staging buffer those calls have grown so far (grow-only) */
 uint64_t zk_test_counter(const zk_ctx *ctx, int which);
 /* Only in the test build (lib/libzkattest_hip_testhooks.so, csrc/api_pool.hip under ZK_TEST_HOOKS); the product library exports neither:
  *   void zk_test_pool_fail_next_submit, arguments (zk_pool *pool, int slot):
  *       the next streamed pool submit fails at device slot `slot` (one shot)
  *   zk_status zk_test_ring_checksum, arguments (zk_ctx *ctx, uint32_t ring, uint64_t sums[8]):
  *       one order-independent 64-bit checksum per table of a resident ring -- limbs, table E, gk_kdig, gk_edig, ktab, ktab_ok, leaves, digest: the sum mod 2^64 of
- *       a mix of (word index, word); 0 for a table the ring does not have.  Per-key tables of ring values that are no x-coordinate are never written and left out. */
+ *       a mix of (word index, word); 0 for a table the ring does not have.  Per-key tables of ring values that are no x-coordinate are never written and left out.
+ *   zk_status zk_test_set_prove_segment, arguments (zk_ctx *ctx, uint32_t proofs):
+ *       mixed-ring prove calls of this context cut their batch into segments of `proofs` proofs (rounded down to a multiple of 256, at least 256) instead of
+ *       what the staging buffer's default size holds; 0 = the default again */
 /*
  * which_field: 0 = F_q (p256.p), 1 = Z_n, 2 = F_t;  op: 0 mul, 1 add, 2 sub, 3 inverse, 4 a*b - a - b (fused double subtraction), 5 (a + b)^2 (dedicated squaring).  count x 40-byte BE operands. */
 zk_status zk_test_field_op(zk_ctx *ctx, int which_field, int op, uint64_t count, const uint8_t *a_be40, const uint8_t *b_be40, uint8_t *out_be40);

@@ -25,6 +25,7 @@ SYMBOLS = [
     'zk_ctx_add_ring', 'zk_ctx_add_ring_device', 'zk_ctx_use_ring', 'zk_ctx_drop_ring', 'zk_ring_info', 'zk_verify_batch_rings', 'zk_verify_batch_rings_device',
     'zk_pool_add_ring', 'zk_pool_use_ring', 'zk_pool_drop_ring', 'zk_pool_verify_batch_rings',
     'zk_ctx_update_ring', 'zk_pool_update_ring',
+    'zk_prove_batch_rings', 'zk_prove_batch_rings_device', 'zk_pool_prove_batch_rings', 'zk_ring_proof_max_size',
     'zk_test_field_op', 'zk_test_tom_commit', 'zk_test_p256_fixed_mul', 'zk_test_sha256', 'zk_test_rng_draws',
 ]
 
@@ -117,6 +118,11 @@ def lib():
         L.zk_pool_update_ring.argtypes = [vp, u32, u64, vp, C.c_char_p, u64]
         L.zk_pool_drop_ring.argtypes = [vp, u32]
         L.zk_pool_verify_batch_rings.argtypes = [vp, u64, C.c_char_p, vp, vp, vp, vp, C.c_char_p, vp, vp]
+        L.zk_prove_batch_rings.argtypes = [vp, u64, C.c_char_p, C.c_char_p, C.c_char_p, vp, vp, C.POINTER(ZkRng), vp, u64, vp, vp]
+        L.zk_prove_batch_rings_device.argtypes = [vp, u64, vp, vp, vp, vp, vp, C.POINTER(ZkRng), vp, u64, vp, vp]
+        L.zk_pool_prove_batch_rings.argtypes = [vp, u64, C.c_char_p, C.c_char_p, C.c_char_p, vp, vp, C.POINTER(ZkRng), vp, u64, vp, vp, vp]
+        L.zk_ring_proof_max_size.argtypes = [vp, u32]
+        L.zk_ring_proof_max_size.restype = u64
         L.zk_ring_digest.argtypes = [vp, vp]
         L.zk_hardened_h.argtypes = [C.c_char_p, u64, vp, vp]
         L.zk_pool_create.argtypes = [C.POINTER(C.c_int), i32, C.POINTER(vp)]
@@ -503,6 +509,59 @@ class Engine:
         proofs = [raw[off[b]:off[b + 1]] if st[b] == 0 else None for b in range(B)]
         return proofs, list(st)
 
+    def ring_proof_max_size(self, ring):
+        """zk_ring_proof_max_size: upper bound of one proof's size over a resident ring (0 for an id that is not resident)"""
+        return int(self.L.zk_ring_proof_max_size(self.h, ring))
+
+    def _rings_cap(self, B, ring_ids):
+        """bytes that hold B proofs over the resident rings among ring_ids (ids that are not resident give empty proofs)"""
+        return max([self.ring_proof_max_size(r) for r in set(ring_ids)] + [32]) * max(B, 1)
+
+    def prove_batch_rings(self, msg, sig, pk, which, ring_ids, seeds=None, streams=None, stream_blocks=0, cap=None, out=None):
+        """zk_prove_batch_rings: prove_batch with one resident ring id per proof (which[b] indexes ring ring_ids[b]); the active ring plays no part.
+        Returns (list of proof bytes or None, list of status); the proofs lie back to back in index order.  cap: the out_cap handed to the call
+        (default: room for every proof); out: a PinnedBuffer to prove into (default: a pageable buffer)."""
+        B = len(which)
+        if len(ring_ids) != B:
+            raise ValueError('one ring id per proof')
+        if seeds is None and streams is None:
+            seeds = os.urandom(32 * B)
+        if streams is None and len(seeds) != 32 * B:
+            raise ValueError('seeds must hold 32 bytes per proof')
+        if cap is None:
+            cap = self._rings_cap(B, ring_ids)
+        if out is None:
+            buf = C.create_string_buffer(max(cap, 1))
+            optr = C.cast(buf, C.c_void_p)
+        else:
+            cap, optr = min(cap, out.nbytes), out.ptr
+        off = (C.c_uint64 * (B + 1))()
+        st = (C.c_int32 * B)()
+        w = (C.c_uint32 * max(B, 1))(*which)
+        ids = (C.c_uint32 * max(B, 1))(*ring_ids)
+        if streams is None:
+            data = C.create_string_buffer(bytes(seeds), 32 * B)
+            rng = ZkRng(0, C.cast(data, C.c_void_p), 0)
+        else:
+            data = C.create_string_buffer(bytes(streams), 32 * B * stream_blocks)
+            rng = ZkRng(1, C.cast(data, C.c_void_p), stream_blocks)
+        self._chk(self.L.zk_prove_batch_rings(self.h, B, bytes(msg), bytes(sig), bytes(pk), w, ids, C.byref(rng), optr, cap, off, st))
+        assert off[0] == 0 and all(off[b] <= off[b + 1] for b in range(B))
+        raw = C.string_at(optr, off[B])
+        return [raw[off[b]:off[b + 1]] if st[b] == 0 else None for b in range(B)], list(st)
+
+    def prove_batch_rings_device(self, B, d_msg, d_sig, d_pk, d_which, d_ring_ids, d_seeds, d_out, out_cap, d_off, d_status, mode=0, stride_blocks=0):
+        """zk_prove_batch_rings_device: every pointer a device address"""
+        rng = ZkRng(mode, d_seeds, stride_blocks)
+        self._chk(self.L.zk_prove_batch_rings_device(self.h, B, d_msg, d_sig, d_pk, d_which, d_ring_ids, C.byref(rng), d_out, out_cap, d_off, d_status))
+
+    def test_set_prove_segment(self, proofs):
+        """test build only (lib/libzkattest_hip_testhooks.so through ZKATTEST_LIB): proofs per segment of the mixed-ring prove calls; 0 = the default"""
+        if not hasattr(self.L, 'zk_test_set_prove_segment'):
+            raise RuntimeError('this build has no test hooks (load lib/libzkattest_hip_testhooks.so through ZKATTEST_LIB)')
+        self.L.zk_test_set_prove_segment.argtypes = [C.c_void_p, C.c_uint32]
+        self._chk(self.L.zk_test_set_prove_segment(self.h, int(proofs)))
+
     def prove_batch_host_raw(self, msg, sig, pk, which, seeds, out=None):
         """zk_prove_batch on host buffers without slicing the output.  out: a PinnedBuffer (overlapped DMA), a ctypes byte array
         (pageable) or None (a pageable array is allocated).  Returns (wall seconds of the C call, out buffer, offsets, statuses)."""
@@ -774,6 +833,25 @@ class Pool:
         ok, st = (C.c_uint8 * B)(), (C.c_int32 * B)()
         self._chk(self.L.zk_pool_verify_batch_rings(self.h, B, bytes(msg), C.addressof(blob), off, ln, ids, bytes(vseeds) if vseeds is not None else None, ok, st))
         return list(ok), list(st)
+
+    def prove_batch_rings(self, msg, sig, pk, which, ring_ids, seeds=None):
+        """zk_pool_prove_batch_rings: prove_batch with one resident ring id per proof (ids of add_ring), sharded by contiguous ranges."""
+        B = len(which)
+        if len(ring_ids) != B:
+            raise ValueError('one ring id per proof')
+        if seeds is None:
+            seeds = os.urandom(32 * B)
+        per = self.engine(0)._rings_cap(1, ring_ids)
+        cap = (per * (B // self.n + 1) + 256) * self.n
+        out = (C.c_uint8 * cap)()
+        off, ln, st = (C.c_uint64 * B)(), (C.c_uint64 * B)(), (C.c_int32 * B)()
+        w = (C.c_uint32 * max(B, 1))(*which)
+        ids = (C.c_uint32 * max(B, 1))(*ring_ids)
+        data = C.create_string_buffer(bytes(seeds), 32 * B)
+        rng = ZkRng(0, C.cast(data, C.c_void_p), 0)
+        self._chk(self.L.zk_pool_prove_batch_rings(self.h, B, bytes(msg), bytes(sig), bytes(pk), w, ids, C.byref(rng), C.addressof(out), cap, off, ln, st))
+        raw = bytes(out)
+        return [raw[off[b]:off[b] + ln[b]] if st[b] == 0 else None for b in range(B)], list(st)
 
     def prove_batch_raw(self, msg, sig, pk, which, seeds, out, cap):
         """zk_pool_prove_batch into `out` (PinnedBuffer or ctypes array).  Returns (seconds, off, len, status)."""

@@ -142,9 +142,15 @@ void stream_abandon_jobs(zk_ctx* c);
 // prove call fails, and on request (zk_ctx_wipe); a successful call leaves them as they are -- the next call overwrites them, and wiping 2.5 GB of RNG
 // stream per 22 016-proof chunk would cost ~0.5 ms of every call.  (The reference leaves its BigInts to the garbage collector.)  Nothing may be in flight.
 static void wipe_witness(zk_ctx* c) {
+    // every stream a prove call puts work on is drained first: a kernel still running on a lane's side stream, or a gather of a mixed-ring call on the
+    // main stream, would write witness-derived data behind the memsets
+    for (int l = 0; l < ZK_MAX_LANES; l++)
+        for (hipStream_t st : {c->pl[l].stream, c->pl[l].side, c->pl[l].copy_stream})
+            if (st) (void)hipStreamSynchronize(st);
     for (int l = 0; l < ZK_MAX_LANES; l++)
         if (c->pl[l].arena && c->pl[l].stream) (void)hipMemsetAsync(c->pl[l].arena, 0, c->pl[l].arena_bytes, c->pl[l].stream);
     if (c->in_buf && c->stream) (void)hipMemsetAsync(c->in_buf, 0, c->in_bytes, c->stream);
+    if (c->pw_buf && c->stream) (void)hipMemsetAsync(c->pw_buf, 0, c->pw_bytes, c->stream);   // mixed-ring prove calls: the gathered signatures, seeds and RNG streams
     if (c->h_stage) {   // the page-locked mirror of the inputs (signatures, RNG blocks)
         volatile uint8_t* h = c->h_stage;
         for (size_t i = 0; i < c->h_stage_bytes; i++) h[i] = 0;
@@ -178,6 +184,9 @@ extern "C" void zk_ctx_destroy(zk_ctx* c) {
     if (c->h_rg) hipHostFree(c->h_rg);
     hipFree(c->io_buf), hipFree(c->in_buf), hipFree(c->unp_buf), hipFree(c->unp_off), hipFree(c->seed_buf), hipFree(c->lv_buf), hipFree(c->lw_buf), hipFree(c->lb_buf);
     if (c->h_lv) hipHostFree(c->h_lv);
+    hipFree(c->pr_buf), hipFree(c->pw_buf), hipFree(c->ps_buf);
+    if (c->h_pr) hipHostFree(c->h_pr);
+    if (c->pr_ready) hipEventDestroy(c->pr_ready);
     if (c->h_stage) hipHostFree(c->h_stage);
     if (c->in_ready) hipEventDestroy(c->in_ready);
     for (int l = 0; l < ZK_MAX_LANES; l++) {
@@ -1315,7 +1324,7 @@ zk_status ProveJob::stage2(uint64_t chunk_no) {
 
 static zk_status prove_device(zk_ctx* c, uint64_t B, const uint8_t* d_msg, const uint8_t* d_sig, const uint8_t* d_pk, const uint32_t* d_which,
                               int rng_mode, const uint8_t* d_rng, uint64_t stride, uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_off,
-                              int32_t* d_status, uint8_t* host_sink = nullptr, hipEvent_t inputs_ready = nullptr) {
+                              int32_t* d_status, uint8_t* host_sink = nullptr, hipEvent_t inputs_ready = nullptr, uint64_t* total_bytes = nullptr) {
     if (!c->params_set || !c->ring->N) return ZK_E_BUFFER;
     if (rng_mode != ZK_RNG_SEED && rng_mode != ZK_RNG_STREAM) return ZK_E_ARG;
     if (c->stream_busy) {
@@ -1374,6 +1383,7 @@ static zk_status prove_device(zk_ctx* c, uint64_t B, const uint8_t* d_msg, const
     HIPCHK(c, e_sync);
     HIPCHK(c, hipGetLastError());
     timing_end(c);
+    if (total_bytes) *total_bytes = J.cursor;   // (the host knows every chunk's bytes since its scan)
     return ZK_OK;
 }
 
@@ -1385,10 +1395,17 @@ extern "C" zk_status zk_prove_batch_device(zk_ctx* c, uint64_t B, const void* d_
                         rng->stride_blocks, (uint8_t*)d_out, out_cap, (uint64_t*)d_out_off, (int32_t*)d_status);
 }
 
+static zk_status prove_host(zk_ctx* c, uint64_t B, const uint8_t* msg, const uint8_t* sig, const uint8_t* pk, const uint32_t* which, const zk_rng* rng, uint8_t* out,
+                            uint64_t out_cap, uint64_t* out_off, int32_t* status);
 extern "C" zk_status zk_prove_batch(zk_ctx* c, uint64_t B, const uint8_t* msg, const uint8_t* sig, const uint8_t* pk, const uint32_t* which,
                                     const zk_rng* rng, uint8_t* out, uint64_t out_cap, uint64_t* out_off, int32_t* status) {
     if (!c || !rng || !out_off || !status || (B && (!msg || !sig || !pk || !which || !rng->data || !out))) return ZK_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
+    return prove_host(c, B, msg, sig, pk, which, rng, out, out_cap, out_off, status);
+}
+// zk_prove_batch on the ring the context is bound to: the active one, or the one ring of a zk_prove_batch_rings call (RingBind)
+static zk_status prove_host(zk_ctx* c, uint64_t B, const uint8_t* msg, const uint8_t* sig, const uint8_t* pk, const uint32_t* which, const zk_rng* rng, uint8_t* out,
+                            uint64_t out_cap, uint64_t* out_off, int32_t* status) {
     if (!c->params_set || !c->ring->N) return ZK_E_BUFFER;
     if (c->stream_busy) {
         c->err = "streamed jobs are in flight on this context (zk_prove_wait / zk_verify_wait them first)";
@@ -1465,6 +1482,248 @@ extern "C" zk_status zk_prove_batch(zk_ctx* c, uint64_t B, const uint8_t* msg, c
         if (B) HIPCHK(c, hipMemcpy(status, d_st, 4 * B, hipMemcpyDeviceToHost));
     }
     if (!sink && !out_on_device && out_off[B]) HIPCHK(c, hipMemcpy(out, d_out, out_off[B], hipMemcpyDeviceToHost));
+    return ZK_OK;
+}
+
+// ------------------------------------------------------------------ mixed-ring proving (include/zkattest.h: zk_prove_batch_rings)
+// One resident ring id per proof.  The census (k_pr_census) classes every proof by its ring's slot and counts the classes per workgroup of PR_BLOCK
+// proofs; the scan (partition.h) turns the counts into prefix sums over the workgroups, and the host reads all of them back ONCE: they tell how many
+// proofs of each ring lie in any index range that starts and ends at a multiple of PR_BLOCK, and where those proofs stand in the one stable
+// permutation by ring (k_part_perm) -- so a call needs no further census however it is cut.
+//   One ring, no unknown id: the usual pipeline on the caller's buffers with that ring bound.  Nothing else is launched.
+//   Otherwise the batch is cut into index-contiguous SEGMENTS whose proofs fit the staging buffer (c->ps_buf: ZK_PR_STAGE_BYTES, or one PR_BLOCK of the
+//   largest proofs if that is more).  Per segment and ring, WINDOWS of at most 2 x chunk x lanes proofs: the inputs are gathered into c->pw_buf, the
+//   window is proved with its ring bound (ensure_workspace re-binds, and re-carves only when n or the tables change) into the staging buffer behind the
+//   windows before it, and (staging offset, length, status) are recorded at every proof's own index.  A proof's size depends on its Exp challenge and its
+//   ring's n, so the final offsets exist only now: one scan over the segment's lengths in index order writes out_off, one byte mover (a workgroup
+//   per proof) writes `out` behind the previous segment's bytes.  A segment is finished before the next one starts; with a page-locked `out` its bytes
+//   cross the link on lane 0's copy stream under the next segment's kernels.
+#define ZK_PR_STAGE_BYTES (8ull << 30)
+static zk_status grow_dev(zk_ctx* c, void** buf, size_t* have, size_t need, bool shed) {   // grow-only device buffer
+    if (need <= *have) return ZK_OK;
+    if (*buf) HIPCHK(c, hipFree(*buf));
+    *buf = nullptr, *have = 0;
+    HIPCHK(c, shed ? malloc_or_shed(c, buf, need) : hipMalloc(buf, need));
+    *have = need;
+    return ZK_OK;
+}
+static uint64_t ring_proof_max_size(const zk_ctx* c, const Ring* R) { return wire_proof_size(wire_make(c->wire == ZK_WIRE_ZKA1P), c->P.sec, R->n, c->P.sec); }
+static zk_status prove_rings_device(zk_ctx* c, uint64_t B, const uint8_t* d_msg, const uint8_t* d_sig, const uint8_t* d_pk, const uint32_t* d_which, const uint32_t* d_ids,
+                                    int rng_mode, const uint8_t* d_rng, uint64_t stride, uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_off, int32_t* d_status,
+                                    uint8_t* host_sink) {
+    if (!c->params_set) return ZK_E_BUFFER;
+    if (rng_mode != ZK_RNG_SEED && rng_mode != ZK_RNG_STREAM) return ZK_E_ARG;
+    if (c->stream_busy) return busy_refusal(c);
+    if (B > 0xffffffffull) return ZK_E_ARG;
+    hipStream_t s = c->stream;
+    if (B == 0) {
+        HIPCHK(c, hipMemsetAsync(d_out_off, 0, 8, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        return ZK_OK;
+    }
+    RingSlots rs{};
+    Ring* slot[ZK_MAX_RINGS] = {};
+    uint64_t max_any = 0;
+    for (auto& R : c->rings)
+        if (R.live && R.N) slot[rs.count] = &R, rs.id[rs.count++] = R.id, max_any = std::max(max_any, ring_proof_max_size(c, &R));
+    // proofs per segment: what the staging buffer holds of the largest proof any resident ring can give, a multiple of PR_BLOCK
+    uint64_t seg = c->pr_seg_force ? c->pr_seg_force : ZK_PR_STAGE_BYTES / (max_any ? max_any : 1);
+    seg = std::max<uint64_t>(PR_BLOCK, seg & ~(uint64_t)(PR_BLOCK - 1));
+    const uint64_t nblk = (B + PR_BLOCK - 1) / PR_BLOCK, seg_max = std::min<uint64_t>(seg, nblk * PR_BLOCK);
+    const size_t ncnt = (size_t)(2 + nblk) * PR_CLASSES;
+    auto carve_pr = [&](Carver& k, uint8_t*& cls, uint32_t*& cnts, uint32_t*& perm, uint64_t*& rec_off, uint64_t*& rec_len) {
+        cls = (uint8_t*)k.take(B), cnts = (uint32_t*)k.take(4 * ncnt), perm = (uint32_t*)k.take(4 * B);
+        rec_off = (uint64_t*)k.take(8 * seg_max), rec_len = (uint64_t*)k.take(8 * seg_max);
+    };
+    uint8_t* cls;
+    uint32_t *cnts, *perm;
+    uint64_t *rec_off, *rec_len;
+    Carver k0(nullptr);
+    carve_pr(k0, cls, cnts, perm, rec_off, rec_len);
+    if (zk_status zs = grow_dev(c, &c->pr_buf, &c->pr_bytes, k0.off + 256, false)) return zs;
+    Carver k1((uint8_t*)c->pr_buf);
+    carve_pr(k1, cls, cnts, perm, rec_off, rec_len);
+    if (4 * ncnt > c->h_pr_bytes) {
+        if (c->h_pr) HIPCHK(c, hipHostFree(c->h_pr));
+        c->h_pr = nullptr, c->h_pr_bytes = 0;
+        HIPCHK(c, hipHostMalloc((void**)&c->h_pr, 8 * ncnt, hipHostMallocDefault));
+        c->h_pr_bytes = 8 * ncnt;
+    }
+    if (!c->pr_ready) HIPCHK(c, hipEventCreateWithFlags(&c->pr_ready, hipEventDisableTiming));
+    uint32_t *out = cnts, *blk = cnts + 2 * PR_CLASSES;   // totals and class starts, then the per-workgroup prefix sums
+    launch_pr_census(s, B, d_ids, rs, cls, blk, out);
+    HIPCHK(c, hipMemcpyAsync(c->h_pr, cnts, 4 * ncnt, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    const uint32_t *cnt = c->h_pr, *start = c->h_pr + PR_CLASSES;
+    auto before = [&](uint64_t b, uint32_t k) { return b < nblk ? c->h_pr[(2 + b) * PR_CLASSES + k] : cnt[k]; };   // proofs of class k in workgroups [0, b)
+    uint32_t used = 0, last = 0, most = 0;
+    uint64_t max_used = 0;
+    for (uint32_t r = 0; r < rs.count; r++)
+        if (cnt[r]) used++, last = r, most = std::max(most, cnt[r]), max_used = std::max(max_used, ring_proof_max_size(c, slot[r]));
+    if (!cnt[PR_UNKNOWN] && used == 1) {   // the common case: one ring -- the caller's buffers as they are
+        RingBind rb(c, slot[last]);
+        return prove_device(c, B, d_msg, d_sig, d_pk, d_which, rng_mode, d_rng, stride, d_out, out_cap, d_out_off, d_status, host_sink);
+    }
+    launch_pr_perm(s, B, cls, blk, out, perm);
+    const uint32_t Wp = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(most, 2ull * c->chunk * c->lanes));
+    const size_t rng_row = rng_mode == ZK_RNG_SEED ? 32 : 32 * (size_t)stride;
+    auto carve_pw = [&](Carver& k, uint8_t*& w_msg, uint8_t*& w_sig, uint8_t*& w_pk, uint32_t*& w_which, uint8_t*& w_rng, uint64_t*& w_off, int32_t*& w_st) {
+        w_msg = (uint8_t*)k.take(32 * (size_t)Wp), w_sig = (uint8_t*)k.take(64 * (size_t)Wp), w_pk = (uint8_t*)k.take(64 * (size_t)Wp), w_which = (uint32_t*)k.take(4 * (size_t)Wp);
+        w_rng = (uint8_t*)k.take(rng_row * Wp + 32), w_off = (uint64_t*)k.take(8 * ((size_t)Wp + 1)), w_st = (int32_t*)k.take(4 * (size_t)Wp);
+    };
+    uint8_t *w_msg, *w_sig, *w_pk, *w_rng;
+    uint32_t* w_which;
+    uint64_t* w_off;
+    int32_t* w_st;
+    Carver p0(nullptr);
+    carve_pw(p0, w_msg, w_sig, w_pk, w_which, w_rng, w_off, w_st);
+    if (zk_status zs = grow_dev(c, &c->pw_buf, &c->pw_bytes, p0.off + 256, true)) return zs;
+    Carver p1((uint8_t*)c->pw_buf);
+    carve_pw(p1, w_msg, w_sig, w_pk, w_which, w_rng, w_off, w_st);
+    if (zk_status zs = grow_dev(c, &c->ps_buf, &c->ps_bytes, (size_t)(std::min<uint64_t>(seg, B) * max_used + 256), true)) return zs;
+    uint8_t* stage = (uint8_t*)c->ps_buf;
+    zk_status zs = ZK_OK;
+    hipError_t he = hipSuccess;
+    auto hip = [&](hipError_t e) {
+        if (e != hipSuccess && he == hipSuccess) he = e;
+        return e == hipSuccess;
+    };
+    uint64_t base = 0;   // bytes of the finished segments: where this segment's proofs start in `out`
+    hipStream_t cs = c->pl[0].copy_stream;
+    for (uint64_t seg0 = 0; seg0 < B && !zs && he == hipSuccess; seg0 += seg) {
+        const uint64_t seg1 = std::min<uint64_t>(B, seg0 + seg), b0 = seg0 / PR_BLOCK, b1 = (seg1 + PR_BLOCK - 1) / PR_BLOCK;
+        c->dbg_pr_segments++;
+        uint64_t staged = 0;
+        for (uint32_t r = 0; r < rs.count && !zs && he == hipSuccess; r++) {
+            const uint32_t first = before(b0, r), n_r = before(b1, r) - first;
+            RingBind rb(c, slot[r]);
+            for (uint32_t w = 0; w < n_r && !zs && he == hipSuccess; w += Wp) {
+                const uint32_t n = std::min<uint32_t>(Wp, n_r - w);
+                const uint32_t* sel = perm + start[r] + first + w;
+                c->dbg_pr_windows++;
+                launch_pr_gather(s, n, sel, d_msg, d_sig, d_pk, d_which, rng_mode == ZK_RNG_SEED ? d_rng : nullptr, w_msg, w_sig, w_pk, w_which, w_rng);
+                if (rng_mode == ZK_RNG_STREAM) launch_pr_gather_rows(s, n, sel, d_rng, rng_row, w_rng);
+                if (!hip(hipEventRecord(c->pr_ready, s))) break;
+                uint64_t bytes = 0;
+                zs = prove_device(c, n, w_msg, w_sig, w_pk, w_which, rng_mode, w_rng, stride, stage + staged, c->ps_bytes - staged, w_off, w_st, nullptr, c->pr_ready, &bytes);
+                if (zs) break;
+                launch_pr_record(s, n, sel, seg0, w_off, w_st, staged, rec_off, rec_len, d_status, 0);
+                staged += bytes;
+            }
+        }
+        if (zs || he != hipSuccess) break;
+        {   // ids that are not resident: empty proofs, ZK_E_ARG
+            const uint32_t first = before(b0, PR_UNKNOWN), n_u = before(b1, PR_UNKNOWN) - first;
+            launch_pr_record(s, n_u, perm + start[PR_UNKNOWN] + first, seg0, nullptr, nullptr, 0, rec_off, rec_len, d_status, ZK_E_ARG);
+        }
+        if (base + staged > out_cap) {
+            c->err = "output buffer too small";
+            zs = ZK_E_BUFFER;
+            break;
+        }
+        launch_pr_offsets(s, (uint32_t)(seg1 - seg0), rec_len, base, d_out_off + seg0);
+        launch_pr_move(s, (uint32_t)(seg1 - seg0), rec_off, rec_len, stage, d_out_off + seg0, d_out);
+        if (host_sink && staged) {   // this segment's bytes are final: DMA them out behind the next segment's kernels
+            if (!hip(hipEventRecord(c->pl[0].copy_ev, s)) || !hip(hipStreamWaitEvent(cs, c->pl[0].copy_ev, 0))) break;
+            const uint64_t piece = 512ull << 20;   // one DMA command moves at most this much
+            for (uint64_t o = 0; o < staged && he == hipSuccess; o += piece)
+                hip(hipMemcpyAsync(host_sink + base + o, d_out + base + o, std::min<uint64_t>(piece, staged - o), hipMemcpyDeviceToHost, cs));
+        }
+        base += staged;
+    }
+    hip(hipStreamSynchronize(s));   // nothing of this call may still be running (or writing into the caller's buffers) when it returns
+    if (host_sink) hip(hipStreamSynchronize(cs));
+    if (!zs) hip(hipGetLastError());
+    if (zs || he != hipSuccess) wipe_witness(c);   // a failed call leaves no gathered signature, seed or RNG block behind (every stream it used is drained first)
+    if (zs) return zs;
+    HIPCHK(c, he);
+    c->last_timing.clear(), c->last_total_ms = 0, c->last_wall_ms = 0;   // (zk_last_timing reports no families after a mixed call: every window timed its own)
+    return ZK_OK;
+}
+// Upper bound of one proof's size over a resident ring, in the context's wire layout (zk_proof_max_size for a ring that need not be active); 0 when the id is
+// not resident or no params are set
+extern "C" uint64_t zk_ring_proof_max_size(const zk_ctx* c, uint32_t ring) {
+    if (!c || !c->params_set) return 0;
+    for (auto& R : c->rings)
+        if (R.live && R.id == ring && R.N) return ring_proof_max_size(c, &R);
+    return 0;
+}
+extern "C" zk_status zk_prove_batch_rings_device(zk_ctx* c, uint64_t B, const void* d_msg, const void* d_sig, const void* d_pk, const void* d_which, const void* d_ids,
+                                                 const zk_rng* rng, void* d_out, uint64_t out_cap, void* d_out_off, void* d_status) {
+    if (!c || !rng || (B && (!d_msg || !d_sig || !d_pk || !d_which || !d_ids || !rng->data || !d_out)) || !d_out_off || !d_status) return ZK_E_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    return prove_rings_device(c, B, (const uint8_t*)d_msg, (const uint8_t*)d_sig, (const uint8_t*)d_pk, (const uint32_t*)d_which, (const uint32_t*)d_ids, rng->mode, rng->data,
+                              rng->stride_blocks, (uint8_t*)d_out, out_cap, (uint64_t*)d_out_off, (int32_t*)d_status, nullptr);
+}
+// Host pointers: the ids are classed here.  All of one resident ring: zk_prove_batch with that ring bound (staging, page-locked DMA, slices: everything as
+// with that ring active).  Anything else: the inputs cross to HBM and take the device path; the proofs are put in order in the context's staging copy of
+// `out` (or in `out` itself where it lies in HBM) and cross the link segment by segment (page-locked `out`) or in one copy at the end.
+extern "C" zk_status zk_prove_batch_rings(zk_ctx* c, uint64_t B, const uint8_t* msg, const uint8_t* sig, const uint8_t* pk, const uint32_t* which, const uint32_t* ring_ids,
+                                          const zk_rng* rng, uint8_t* out, uint64_t out_cap, uint64_t* out_off, int32_t* status) {
+    if (!c || !rng || !out_off || !status || (B && (!msg || !sig || !pk || !which || !ring_ids || !rng->data || !out))) return ZK_E_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->params_set) return ZK_E_BUFFER;
+    if (rng->mode != ZK_RNG_SEED && rng->mode != ZK_RNG_STREAM) return ZK_E_ARG;
+    if (c->stream_busy) return busy_refusal(c);
+    if (B == 0) {
+        out_off[0] = 0;
+        return ZK_OK;
+    }
+    Ring* one = find_ring(c, ring_ids[0]);
+    for (uint64_t b = 1; b < B && one; b++)
+        if (ring_ids[b] != ring_ids[0]) one = nullptr;
+    if (one && one->N) {
+        RingBind rb(c, one);
+        return prove_host(c, B, msg, sig, pk, which, rng, out, out_cap, out_off, status);
+    }
+    const size_t rng_bytes = rng->mode == ZK_RNG_SEED ? 32 * B : 32 * B * rng->stride_blocks;
+    uint64_t bound = 0;   // no proof of the batch is larger than the largest resident ring's
+    for (auto& R : c->rings)
+        if (R.live && R.N) bound = std::max(bound, ring_proof_max_size(c, &R));
+    auto carve_in = [&](Carver& kk, uint8_t*& m, uint8_t*& sg, uint8_t*& p, uint32_t*& w, uint32_t*& ids, uint8_t*& r, uint64_t*& o, int32_t*& st_) {
+        m = (uint8_t*)kk.take(32 * B), sg = (uint8_t*)kk.take(64 * B), p = (uint8_t*)kk.take(64 * B), w = (uint32_t*)kk.take(4 * B), ids = (uint32_t*)kk.take(4 * B);
+        r = (uint8_t*)kk.take(rng_bytes ? rng_bytes : 32), o = (uint64_t*)kk.take(8 * (B + 1)), st_ = (int32_t*)kk.take(4 * B);
+    };
+    uint8_t *d_msg, *d_sig, *d_pk, *d_rng;
+    uint32_t *d_which, *d_ids;
+    uint64_t* d_off;
+    int32_t* d_st;
+    Carver k0(nullptr);
+    carve_in(k0, d_msg, d_sig, d_pk, d_which, d_ids, d_rng, d_off, d_st);
+    if (zk_status zs = ensure_in_buf(c, k0.off + 256)) return zs;
+    Carver k1((uint8_t*)c->in_buf);
+    carve_in(k1, d_msg, d_sig, d_pk, d_which, d_ids, d_rng, d_off, d_st);
+    bool out_on_device = false;
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, out) == hipSuccess) out_on_device = a.type == hipMemoryTypeDevice;
+    else (void)hipGetLastError();
+    if (out_on_device && a.device != c->device) {
+        c->err = "`out` lies on another device than this context's";
+        return ZK_E_ARG;
+    }
+    const uint64_t cap_dev = out_on_device ? out_cap : std::min<uint64_t>(out_cap, bound * B);
+    if (!out_on_device)
+        if (zk_status zs = ensure_io_buf(c, cap_dev ? cap_dev : 32)) return zs;
+    uint8_t* d_out = out_on_device ? out : (uint8_t*)c->io_buf;
+    uint8_t* sink = !out_on_device && host_ptr_is_pinned(out) ? out : nullptr;
+    if (sink)
+        if (zk_status zs = ensure_copy_stream(c)) return zs;
+    // from the first upload on, signatures and seeds lie in in_buf: every failure below zeroes them (prove_rings_device does so itself)
+    const struct { void* d; const void* h; size_t n; } up[] = {{d_msg, msg, 32 * B}, {d_sig, sig, 64 * B}, {d_pk, pk, 64 * B}, {d_which, which, 4 * B},
+                                                               {d_ids, ring_ids, 4 * B}, {d_rng, rng->data, rng_bytes}};
+    for (auto& u : up)
+        if (hipMemcpy(u.d, u.h, u.n, hipMemcpyHostToDevice) != hipSuccess) {
+            c->err = "upload of the inputs failed";
+            (void)hipGetLastError();
+            wipe_witness(c);
+            return ZK_E_DEVICE;
+        }
+    if (zk_status zs = prove_rings_device(c, B, d_msg, d_sig, d_pk, d_which, d_ids, rng->mode, d_rng, rng->stride_blocks, d_out, cap_dev, d_off, d_st, sink)) return zs;
+    hipError_t e = hipMemcpy(out_off, d_off, 8 * (B + 1), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(status, d_st, 4 * B, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && !sink && !out_on_device && out_off[B]) e = hipMemcpy(out, d_out, out_off[B], hipMemcpyDeviceToHost);
+    if (e != hipSuccess) wipe_witness(c);
+    HIPCHK(c, e);
     return ZK_OK;
 }
 

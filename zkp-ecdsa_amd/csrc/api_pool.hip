@@ -275,6 +275,13 @@ extern "C" zk_status zk_test_ring_checksum(zk_ctx* c, uint32_t ring, uint64_t su
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return ZK_OK;
 }
+// Mixed-ring prove calls of this context cut their batch into segments of `proofs` proofs (rounded down to a multiple of 256, at least 256) instead of what
+// the staging buffer's default size holds; 0 = the default again.  Test build only: tests/test_gpu_prove_rings.py watches the cutting happen on a small batch.
+extern "C" zk_status zk_test_set_prove_segment(zk_ctx* c, uint32_t proofs) {
+    if (!c) return ZK_E_ARG;
+    c->pr_seg_force = proofs;
+    return ZK_OK;
+}
 #else
 #define POOL_INJECTED(p, i) false
 #endif
@@ -568,6 +575,28 @@ extern "C" zk_status zk_pool_prove_batch(zk_pool* p, uint64_t B, const uint8_t* 
         std::vector<uint64_t> off(cnt + 1);
         zk_status zs = zk_prove_batch(p->ctx[i], cnt, msg + 32 * first, sig + 64 * first, pk + 64 * first, which + first, &r, out + region * i, region,
                                       off.data(), status + first);
+        if (zs) return zs;
+        for (uint64_t j = 0; j < cnt; j++) out_off[first + j] = region * i + off[j], out_len[first + j] = off[j + 1] - off[j];
+        return ZK_OK;
+    });
+}
+
+// zk_prove_batch_rings over all devices: zk_pool_prove_batch's shards and regions, every shard with its part of the ring ids (those of zk_pool_add_ring)
+extern "C" zk_status zk_pool_prove_batch_rings(zk_pool* p, uint64_t B, const uint8_t* msg, const uint8_t* sig, const uint8_t* pk, const uint32_t* which,
+                                               const uint32_t* ring_ids, const zk_rng* rng, uint8_t* out, uint64_t out_cap, uint64_t* out_off, uint64_t* out_len,
+                                               int32_t* status) {
+    if (!p || !rng || !out_off || !out_len || !status || (B && (!msg || !sig || !pk || !which || !ring_ids || !rng->data || !out))) return ZK_E_ARG;
+    const uint64_t G = p->ctx.size();
+    const uint64_t region = (out_cap / G) & ~(uint64_t)255;   // shard i writes into [i * region, (i+1) * region)
+    return pool_each(p, [&](int i) -> zk_status {
+        uint64_t first, cnt;
+        zk_pool_shard(p, B, i, &first, &cnt);
+        if (!cnt) return ZK_OK;
+        zk_rng r = *rng;
+        r.data = rng->data + (rng->mode == ZK_RNG_SEED ? 32 * first : 32 * first * rng->stride_blocks);
+        std::vector<uint64_t> off(cnt + 1);
+        zk_status zs = zk_prove_batch_rings(p->ctx[i], cnt, msg + 32 * first, sig + 64 * first, pk + 64 * first, which + first, ring_ids + first, &r, out + region * i,
+                                            region, off.data(), status + first);
         if (zs) return zs;
         for (uint64_t j = 0; j < cnt; j++) out_off[first + j] = region * i + off[j], out_len[first + j] = off[j + 1] - off[j];
         return ZK_OK;

@@ -565,5 +565,8 @@ extern "C" uint64_t zk_test_counter(const zk_ctx* c, int which) {
     }
     if (which == 5) return c->dbg_ktab_keys;     // per-key tables computed by the ring builder (zk_ctx_update_ring's copies do not count)
     if (which == 6) return c->dbg_etab_blocks;   // 256-key blocks whose table E was built
+    if (which == 7) return c->dbg_pr_segments;   // segments staged by mixed-ring prove calls
+    if (which == 8) return c->dbg_pr_windows;    // windows proved by mixed-ring prove calls
+    if (which == 9) return c->ps_bytes;          // bytes of the staging buffer mixed-ring prove calls have grown so far
     return which == 0 ? c->dbg_recheck_proofs : which == 2 ? c->dbg_msm_terms : which == 3 ? c->dbg_p256_batched : 0;
 }

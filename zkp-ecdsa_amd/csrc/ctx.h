@@ -57,6 +57,17 @@ struct zk_ctx {
     size_t rg_bytes = 0;
     uint32_t* h_rg = nullptr;      // ... page-locked read-back of the per-class counters
     size_t h_rg_bytes = 0;
+    // mixed-ring prove calls (api.hip: prove_rings_device), all grow-only
+    void* pr_buf = nullptr;        // classes, per-workgroup counters, permutation and the running segment's (staging offset, length) records
+    size_t pr_bytes = 0;
+    uint32_t* h_pr = nullptr;      // page-locked read-back of the counters
+    size_t h_pr_bytes = 0;
+    void* pw_buf = nullptr;        // the window one ring's inputs are gathered into: signatures, seeds or RNG streams -- witness-derived, wiped with the workspaces
+    size_t pw_bytes = 0;
+    void* ps_buf = nullptr;        // staging of a segment's proofs until their final offsets are known (malloc_or_shed)
+    size_t ps_bytes = 0;
+    hipEvent_t pr_ready = nullptr; // "the window is gathered": the lanes' stage 1 waits for it
+    uint32_t pr_seg_force = 0;     // test build only (zk_test_set_prove_segment): proofs per segment instead of what ZK_PR_STAGE_BYTES holds; 0 = off
     uint32_t mode = 0;                 // zk_ctx_set_mode: ZK_MODE_REFERENCE / ZK_MODE_HARDENED
     uint32_t verify_level = 0;         // zk_ctx_set_verify_level: ZK_VERIFY_LEVEL_CONTEXT / ZK_VERIFY_LEVEL_PER_PROOF
     // per-proof mode: the repetition count the verifier's workspaces are planned for during one call (or while streamed verify jobs are queued); the
@@ -155,6 +166,8 @@ struct zk_ctx {
     uint64_t dbg_msm_terms = 0;        // live terms that went through the batched Tom-256 check (k_msm.hip) since the context was created
     uint64_t dbg_ktab_keys = 0;        // per-key tables computed by the builder (k_ktab.hip) since the context was created; copied tables do not count
     uint64_t dbg_etab_blocks = 0;      // 256-key blocks whose table E was built (k_gk.hip) since the context was created
+    uint64_t dbg_pr_segments = 0;      // segments that mixed-ring prove calls staged since the context was created (a one-ring call stages none)
+    uint64_t dbg_pr_windows = 0;       // ... and the windows they proved
     // timing
     std::vector<TimerRec> trecs;
     std::vector<hipEvent_t> epool;
@@ -201,7 +214,7 @@ struct Scope {
 // (profiles/r06_ab_variants.txt (14)); a call of more than V_SIDE_MAXP proofs does not notice them.
 // the repetition count the workspaces are planned for: the context's secLevel, or the level of the proofs a per-proof-mode verify call is running
 static inline uint32_t plan_sec(const zk_ctx* c) { return c->v_sec_on ? c->v_sec : c->P.sec; }
-// binds `r` as the ring of the running call (mixed-ring verification) and puts the active ring back when the scope ends
+// binds `r` as the ring of the running call (mixed-ring verification and proving) and puts the active ring back when the scope ends
 struct RingBind {
     zk_ctx* c;
     Ring* prev;

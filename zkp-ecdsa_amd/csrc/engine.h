@@ -350,6 +350,21 @@ struct RingSlots {   // (a kernel argument) the resident rings' ids in slot orde
 void launch_rg_census(hipStream_t s, uint64_t B, const uint32_t* ring_ids, const RingSlots& rs, const uint8_t* proofs, const uint64_t* off, bool packed, bool per_proof,
                       uint16_t* cls, uint32_t* blk_cnt, uint32_t* out);
 void launch_rg_perm(hipStream_t s, uint64_t B, const uint16_t* cls, const uint32_t* blk_base, const uint32_t* out, uint32_t* perm);
+// mixed-ring proving (k_prove_rings.hip): one class per resident ring's slot and one for ids that are not resident; the census counts per workgroup of
+// PR_BLOCK proofs, which is also the granularity a call's index-contiguous segments are cut at
+#define PR_BLOCK 256
+#define PR_UNKNOWN ZK_MAX_RINGS
+#define PR_CLASSES (PR_UNKNOWN + 1)
+void launch_pr_census(hipStream_t s, uint64_t B, const uint32_t* ring_ids, const RingSlots& rs, uint8_t* cls, uint32_t* blk_cnt, uint32_t* out);
+void launch_pr_perm(hipStream_t s, uint64_t B, const uint8_t* cls, const uint32_t* blk_base, const uint32_t* out, uint32_t* perm);
+void launch_pr_gather(hipStream_t s, uint32_t n, const uint32_t* sel, const uint8_t* msg, const uint8_t* sig, const uint8_t* pk, const uint32_t* which, const uint8_t* seeds,
+                      uint8_t* w_msg, uint8_t* w_sig, uint8_t* w_pk, uint32_t* w_which, uint8_t* w_seeds);
+void launch_pr_gather_rows(hipStream_t s, uint32_t n, const uint32_t* sel, const uint8_t* src, uint64_t row_bytes, uint8_t* dst);
+// w_off == nullptr: empty proofs with status `st`
+void launch_pr_record(hipStream_t s, uint32_t n, const uint32_t* sel, uint64_t seg_first, const uint64_t* w_off, const int32_t* w_st, uint64_t stage_base, uint64_t* rec_off,
+                      uint64_t* rec_len, int32_t* status, int32_t st);
+void launch_pr_offsets(hipStream_t s, uint32_t n, const uint64_t* rec_len, uint64_t base, uint64_t* out_off);
+void launch_pr_move(hipStream_t s, uint32_t n, const uint64_t* rec_off, const uint64_t* rec_len, const uint8_t* stage, const uint64_t* out_off, uint8_t* out);
 
 // chunk inputs (device pointers, already offset to the chunk's first proof)
 struct ChunkIn {

@@ -19,7 +19,7 @@ __global__ void __launch_bounds__(LV_BLOCK) k_lv_census(uint64_t B, const uint8_
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < ZK_LV_CLASSES; i += LV_BLOCK) blk_cnt[(size_t)blockIdx.x * ZK_LV_CLASSES + i] = cnt[i];
 }
-// window entry j = proof sel[j]: its length (turned into offsets by k_lv_offsets), message hash and verifier seed
+// window entry j = proof sel[j]: its length (turned into offsets by k_part_offsets), message hash and verifier seed
 __global__ void __launch_bounds__(256) k_lv_gather_meta(uint32_t n, const uint32_t* __restrict__ sel, const uint64_t* __restrict__ off, const uint8_t* __restrict__ msg,
                                                         const uint8_t* __restrict__ vseeds, uint64_t* __restrict__ w_len, uint8_t* __restrict__ w_msg, uint8_t* __restrict__ w_seeds) {
     const uint32_t t = gtid();   // 8 threads per entry: one 16-byte piece of the message hash or of the seed each, and the length
@@ -29,28 +29,6 @@ __global__ void __launch_bounds__(256) k_lv_gather_meta(uint32_t n, const uint32
     if (q < 2) ((uint4*)(w_msg + 32 * (size_t)j))[q] = ((const uint4*)(msg + 32 * b))[q];
     else if (q < 4) ((uint4*)(w_seeds + 32 * (size_t)j))[q - 2] = ((const uint4*)(vseeds + 32 * b))[q - 2];
     else if (q == 4) w_len[j] = off[b + 1] - off[b];
-}
-// lengths -> exclusive prefix sums in place, w_off[n] = the window's bytes (one workgroup)
-__global__ void __launch_bounds__(1024) k_lv_offsets(uint32_t n, uint64_t* __restrict__ w_off) {
-    __shared__ uint64_t sb[1024];
-    const uint32_t t = threadIdx.x, per = (n + 1023) / 1024;
-    const uint32_t lo = t * per < n ? t * per : n, hi = lo + per < n ? lo + per : n;
-    uint64_t sum = 0;
-    for (uint32_t j = lo; j < hi; j++) sum += w_off[j];
-    sb[t] = sum;
-    __syncthreads();
-    for (uint32_t d = 1; d < 1024; d <<= 1) {   // inclusive Hillis-Steele scan of the 1024 partial sums
-        const uint64_t v = t >= d ? sb[t - d] : 0;
-        __syncthreads();
-        sb[t] += v;
-        __syncthreads();
-    }
-    uint64_t run = sb[t] - sum;
-    for (uint32_t j = lo; j < hi; j++) {
-        const uint64_t v = w_off[j];
-        w_off[j] = run, run += v;
-    }
-    if (t == 1023) w_off[n] = sb[1023];
 }
 // the bytes: one workgroup per window entry, 16-byte stores at 16-byte aligned destinations; the source is read with 16-byte loads where it has the same
 // alignment mod 16, as four dwords otherwise (offsets are 4-byte aligned, k_lv_census refused every other proof)
@@ -100,7 +78,7 @@ void launch_lv_perm(hipStream_t s, uint64_t B, const uint8_t* cls, const uint32_
 void launch_lv_gather_meta(hipStream_t s, uint32_t n, const uint32_t* sel, const uint64_t* off, const uint8_t* msg, const uint8_t* vseeds, uint64_t* w_off, uint8_t* w_msg,
                            uint8_t* w_seeds) {
     hipLaunchKernelGGL(k_lv_gather_meta, dim3((8 * n + 255) / 256), dim3(256), 0, s, n, sel, off, msg, vseeds, w_off, w_msg, w_seeds);
-    hipLaunchKernelGGL(k_lv_offsets, dim3(1), dim3(1024), 0, s, n, w_off);
+    hipLaunchKernelGGL(k_part_offsets<1024>, dim3(1), dim3(1024), 0, s, n, w_off, (uint64_t)0, w_off);   // lengths -> offsets in place, w_off[n] = the window's bytes
 }
 void launch_lv_gather_bytes(hipStream_t s, uint32_t n, const uint32_t* sel, const uint64_t* off, const uint8_t* proofs, const uint64_t* w_off, uint8_t* w_bytes) {
     hipLaunchKernelGGL(k_lv_gather_bytes, dim3(n), dim3(256), 0, s, n, sel, off, proofs, w_off, w_bytes);
