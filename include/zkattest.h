@@ -542,7 +542,9 @@ int zk_pool_test_locality(const char *pci_bus_id, int *numa_node, int *cpus, int
  * 6 = 256-key blocks whose table E was built since the context was created;
  * 7 = segments that mixed-ring prove calls (zk_prove_batch_rings) staged since the context was created -- a call of one ring stages none;
  * 8 = windows those calls proved;
- * 9 = bytes of the staging buffer those calls have grown so far (grow-only) */
+ * 9 = bytes of the staging buffer those calls have grown so far (grow-only);
+ * 10 = form of the context's comb tables of g and h: 1 = the a = -1 model (7 products per table addition; chosen by zk_ctx_set_params when q * g = q * h =
+ *     identity), 0 = the a = 1 image (any other pair of curve points); ~0 before zk_ctx_set_params.  Bytes and verdicts are the same. */
 uint64_t zk_test_counter(const zk_ctx *ctx, int which);
 /* Only in the test build (lib/libzkattest_hip_testhooks.so, csrc/api_pool.hip under ZK_TEST_HOOKS); the product library exports neither:
  *   void zk_test_pool_fail_next_submit, arguments (zk_pool *pool, int slot):
@@ -558,6 +560,11 @@ uint64_t zk_test_counter(const zk_ctx *ctx, int which);
 zk_status zk_test_field_op(zk_ctx *ctx, int which_field, int op, uint64_t count, const uint8_t *a_be40, const uint8_t *b_be40, uint8_t *out_be40);
 /* out[i] = v[i]*g + r[i]*h on Tom-256 (72-byte affine), through the fixed-base comb kernel */
 zk_status zk_test_tom_commit(zk_ctx *ctx, uint64_t count, const uint8_t *v_be32, const uint8_t *r_be32, uint8_t *out_xy72);
+/* the same through ONE named kernel of the comb sums whatever the count (shape 0: as zk_test_tom_commit, the launch wrapper chooses): 1 = one lane per commitment;
+ * 2 = the list is list B of count / 34 items, slot = k * items + item (unpaired slots one lane each, the nine pairs through the kernel that shares v * g: it takes v
+ * of a pair from its first slot); 3 = four lanes; 4 = four cooperating waves; 5 = the compacted-list kernel of the verifier.  ZK_E_ARG where a shape does not
+ * apply (3 and 4 with the signed comb widths 25 and 26; 2 with a count that is no multiple of 34). */
+zk_status zk_test_tom_commit_shape(zk_ctx *ctx, uint32_t shape, uint64_t count, const uint8_t *v_be32, const uint8_t *r_be32, uint8_t *out_xy72);
 /* out[i] = k[i]*G (base_sel 0) or k[i]*h_NIST (base_sel 1) on P-256 (64-byte affine; all-zero for the identity) */
 zk_status zk_test_p256_fixed_mul(zk_ctx *ctx, int base_sel, uint64_t count, const uint8_t *k_be32, uint8_t *out_xy64);
 /* digest[i] = SHA-256(msg[i]) for count messages of identical length len */

@@ -18,7 +18,7 @@ SYMBOLS = [
     'zk_pool_create', 'zk_pool_destroy', 'zk_pool_size', 'zk_pool_ctx', 'zk_pool_last_error', 'zk_pool_ring_transport', 'zk_pool_rccl_library', 'zk_pool_shard',
     'zk_pool_set_params', 'zk_pool_set_ring', 'zk_pool_prove_batch', 'zk_pool_verify_batch',
     'zk_pool_host_alloc', 'zk_pool_host_free', 'zk_pool_numa_node', 'zk_pool_test_locality', 'zk_pool_shard_ms', 'zk_ctx_copy_probe', 'zk_ctx_set_wire', 'zk_proof_pack', 'zk_proof_unpack', 'zk_pool_prove_batch_device', 'zk_pool_device_alloc', 'zk_pool_device_free',
-    'zk_prove_submit', 'zk_prove_submit_device', 'zk_prove_wait', 'zk_verify_submit', 'zk_verify_wait', 'zk_test_counter', 'zk_ctx_set_key_tables',
+    'zk_prove_submit', 'zk_prove_submit_device', 'zk_prove_wait', 'zk_verify_submit', 'zk_verify_wait', 'zk_test_counter', 'zk_test_tom_commit_shape', 'zk_ctx_set_key_tables',
     'zk_proofs_to_json_batch', 'zk_proofs_from_json_batch', 'zk_ctx_set_ring_fold',
     'zk_pool_prove_submit', 'zk_pool_prove_wait', 'zk_pool_verify_submit', 'zk_pool_verify_wait', 'zk_ctx_set_verify_groups',
     'zk_ctx_set_verify_level', 'zk_pool_set_verify_level',
@@ -177,6 +177,7 @@ def lib():
         L.zk_pool_test_locality.argtypes = [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), i32]
         L.zk_test_field_op.argtypes = [vp, i32, i32, u64, C.c_char_p, C.c_char_p, vp]
         L.zk_test_tom_commit.argtypes = [vp, u64, C.c_char_p, C.c_char_p, vp]
+        L.zk_test_tom_commit_shape.argtypes = [vp, u32, u64, C.c_char_p, C.c_char_p, vp]
         L.zk_test_p256_fixed_mul.argtypes = [vp, i32, u64, C.c_char_p, vp]
         L.zk_test_sha256.argtypes = [vp, u64, u64, C.c_char_p, vp]
         L.zk_test_rng_draws.argtypes = [vp, u64, C.POINTER(ZkRng), u32, u32, vp]
@@ -705,6 +706,14 @@ class Engine:
         out = C.create_string_buffer(72 * n)
         self._chk(self.L.zk_test_tom_commit(self.h, n, b''.join(x.to_bytes(32, 'big') for x in v_list),
                                             b''.join(x.to_bytes(32, 'big') for x in r_list), out))
+        return [out.raw[72 * i:72 * i + 72] for i in range(n)]
+
+    def test_tom_commit_shape(self, shape, v_list, r_list):
+        """zk_test_tom_commit_shape: the commitments through one named kernel (1 one lane, 2 list B with its pairs, 3 four lanes, 4 cooperating waves, 5 compacted list)"""
+        n = len(v_list)
+        out = C.create_string_buffer(72 * n)
+        self._chk(self.L.zk_test_tom_commit_shape(self.h, shape, n, b''.join(x.to_bytes(32, 'big') for x in v_list),
+                                                  b''.join(x.to_bytes(32, 'big') for x in r_list), out))
         return [out.raw[72 * i:72 * i + 72] for i in range(n)]
 
     def test_p256_fixed_mul(self, base_sel, k_list):

@@ -118,7 +118,7 @@ static zk_status ctx_init(zk_ctx* c, int device_id) {
     uint32_t* d_xy;
     HIPCHK(c, hipMalloc(&d_xy, 18 * 4));
     HIPCHK(c, hipMemcpyAsync(d_xy, genw, 72, hipMemcpyHostToDevice, c->stream));
-    launch_build_tom_table(c->stream, d_xy, 8, c->tom_tab_gen, c->tab_scratch, c->d_flag);
+    launch_build_tom_table(c->stream, d_xy, 8, TOM_MODEL_A1, c->tom_tab_gen, c->tab_scratch, c->d_flag);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipFree(d_xy));
     return ZK_OK;
@@ -255,8 +255,19 @@ extern "C" zk_status zk_ctx_set_params(zk_ctx* c, const uint8_t nist_h[64], cons
         c->tab_bits_alloc = c->P.tom_bits = c->tom_bits;
     }
     launch_build_pfix_table(c->stream, d, c->P.pfix_H, c->tab_scratch, c->d_flag);
-    launch_build_tom_table(c->stream, d + 16, c->tom_bits, c->P.tom_tab_g, c->tab_scratch, c->d_flag);
-    launch_build_tom_table(c->stream, d + 34, c->tom_bits, c->P.tom_tab_h, c->tab_scratch, c->d_flag);
+    // The comb tables of g and h take the a = -1 model (curve.h: 7 products per table addition) only where both bases have odd order, q * g = q * h = identity:
+    // its law is complete there and nowhere else.  Anything else the caller hands in -- the curve has order 4 q -- keeps the a = 1 tables and kernels.
+    int32_t odd[2] = {0, 0};
+    launch_tom_order_check(c->stream, d + 16, d + 34, (int32_t*)(d + 52));
+    {
+        hipError_t e = hipMemcpyAsync(odd, d + 52, 8, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) (void)hipFree(d);
+        HIPCHK(c, e);
+    }
+    c->P.tom_model = odd[0] && odd[1] ? TOM_MODEL_M1 : TOM_MODEL_A1;
+    launch_build_tom_table(c->stream, d + 16, c->tom_bits, c->P.tom_model, c->P.tom_tab_g, c->tab_scratch, c->d_flag);
+    launch_build_tom_table(c->stream, d + 34, c->tom_bits, c->P.tom_model, c->P.tom_tab_h, c->tab_scratch, c->d_flag);
     int32_t ok = 0;
     HIPCHK(c, hipMemcpyAsync(&ok, c->d_flag, 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1829,19 +1840,31 @@ extern "C" zk_status zk_synth_workload(zk_ctx* c, uint64_t seed, uint64_t nkeys,
     return ZK_OK;
 }
 
-static zk_status tom_commit_generic(zk_ctx* c, const uint32_t* tab_g, const uint32_t* tab_h, uint32_t bits, uint64_t count, const uint8_t* d_v, const uint8_t* d_r, uint8_t* d_out) {
+static zk_status tom_commit_generic(zk_ctx* c, const uint32_t* tab_g, const uint32_t* tab_h, uint32_t bits, uint32_t model, uint64_t count, const uint8_t* d_v, const uint8_t* d_r, uint8_t* d_out,
+                                    uint32_t shape = 0) {
     // temporary list
     TomList L;
     void* mem;
     size_t per = 36 * 7;
-    HIPCHK(c, hipMalloc(&mem, per * count + 4096));
+    HIPCHK(c, hipMalloc(&mem, per * count + 4096 + 4 * (count + 1)));
     Carver k((uint8_t*)mem);
     L = k.list(count);
+    uint32_t* d_list = (uint32_t*)((uint8_t*)mem + (per * count + 4096) / 4 * 4);   // shape 5 (k_tom_commit_list): the slots in reverse order, then their number
     launch_bytes_to_scalars(c->stream, d_v, count, L.v);
     launch_bytes_to_scalars(c->stream, d_r, count, L.r);
     DevParams P = c->P;
-    P.tom_tab_g = (uint32_t*)tab_g, P.tom_tab_h = (uint32_t*)tab_h, P.tom_bits = bits;
-    launch_tom_commit(c->stream, P, L, (uint32_t)count, 1, 1);
+    P.tom_tab_g = (uint32_t*)tab_g, P.tom_tab_h = (uint32_t*)tab_h, P.tom_bits = bits, P.tom_model = model;
+    if (shape) {
+        std::vector<uint32_t> lst(count + 1);
+        for (uint64_t i = 0; i < count; i++) lst[i] = (uint32_t)(count - 1 - i);
+        lst[count] = (uint32_t)count;
+        const bool up = hipMemcpyAsync(d_list, lst.data(), 4 * (count + 1), hipMemcpyHostToDevice, c->stream) == hipSuccess && hipStreamSynchronize(c->stream) == hipSuccess;
+        if (!up || !launch_tom_commit_shape(c->stream, P, L, (uint32_t)count, shape, d_list, d_list + count)) {
+            (void)hipFree(mem);
+            if (!up) c->err = "copy of the slot list failed";
+            return up ? ZK_E_ARG : ZK_E_DEVICE;
+        }
+    } else launch_tom_commit(c->stream, P, L, (uint32_t)count, 1, 1);
     launch_tom_normalize(c->stream, L, (uint32_t)count, 0, 1, 1);
     launch_affine_to_bytes(c->stream, L.ax, L.ay, count, 1, d_out);
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1856,7 +1879,7 @@ extern "C" zk_status zk_synth_params(zk_ctx* c, uint64_t seed, uint8_t nist_h[64
     HIPCHK(c, hipMemsetAsync(d, 0, 512, c->stream));
     launch_synth_param_scalars(c->stream, seed, d, d + 32);  // kn, kt (big-endian); d+64: zero scalar
     launch_test_pfix(c->stream, c->P.pfix_G, 1, d, d + 128);
-    zk_status zs = tom_commit_generic(c, c->tom_tab_gen, c->tom_tab_gen, 8, 1, d + 32, d + 64, d + 256);
+    zk_status zs = tom_commit_generic(c, c->tom_tab_gen, c->tom_tab_gen, 8, TOM_MODEL_A1, 1, d + 32, d + 64, d + 256);
     if (zs) return zs;
     HIPCHK(c, hipMemcpy(nist_h, d + 128, 64, hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemcpy(tom_h, d + 256, 72, hipMemcpyDeviceToHost));
@@ -1881,15 +1904,17 @@ extern "C" zk_status zk_test_field_op(zk_ctx* c, int which, int op, uint64_t cou
     HIPCHK(c, hipMemcpy(out, dout.p, 40 * count, hipMemcpyDeviceToHost));
     return ZK_OK;
 }
-extern "C" zk_status zk_test_tom_commit(zk_ctx* c, uint64_t count, const uint8_t* v, const uint8_t* r, uint8_t* out) {
-    if (!c || !v || !r || !out || !count) return ZK_E_ARG;
+extern "C" zk_status zk_test_tom_commit_shape(zk_ctx* c, uint32_t shape, uint64_t count, const uint8_t* v, const uint8_t* r, uint8_t* out);
+extern "C" zk_status zk_test_tom_commit(zk_ctx* c, uint64_t count, const uint8_t* v, const uint8_t* r, uint8_t* out) { return zk_test_tom_commit_shape(c, 0, count, v, r, out); }
+extern "C" zk_status zk_test_tom_commit_shape(zk_ctx* c, uint32_t shape, uint64_t count, const uint8_t* v, const uint8_t* r, uint8_t* out) {
+    if (!c || !v || !r || !out || !count || (shape && count > (1u << 24))) return ZK_E_ARG;   // a named shape builds a 32-bit slot list on the host
     if (!c->params_set) return ZK_E_BUFFER;
     HIPCHK(c, hipSetDevice(c->device));
     DevBuf dv, dr, dout;
     HIPCHK(c, hipMalloc(&dv.p, 32 * count)); HIPCHK(c, hipMalloc(&dr.p, 32 * count)); HIPCHK(c, hipMalloc(&dout.p, 72 * count));
     HIPCHK(c, hipMemcpy(dv.p, v, 32 * count, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(dr.p, r, 32 * count, hipMemcpyHostToDevice));
-    zk_status zs = tom_commit_generic(c, c->P.tom_tab_g, c->P.tom_tab_h, c->P.tom_bits, count, (uint8_t*)dv.p, (uint8_t*)dr.p, (uint8_t*)dout.p);
+    zk_status zs = tom_commit_generic(c, c->P.tom_tab_g, c->P.tom_tab_h, c->P.tom_bits, c->P.tom_model, count, (uint8_t*)dv.p, (uint8_t*)dr.p, (uint8_t*)dout.p, shape);
     if (zs) return zs;
     HIPCHK(c, hipMemcpy(out, dout.p, 72 * count, hipMemcpyDeviceToHost));
     return ZK_OK;

@@ -568,5 +568,6 @@ extern "C" uint64_t zk_test_counter(const zk_ctx* c, int which) {
     if (which == 7) return c->dbg_pr_segments;   // segments staged by mixed-ring prove calls
     if (which == 8) return c->dbg_pr_windows;    // windows proved by mixed-ring prove calls
     if (which == 9) return c->ps_bytes;          // bytes of the staging buffer mixed-ring prove calls have grown so far
+    if (which == 10) return c->params_set ? c->P.tom_model : ~0ull;   // form of the comb tables of g and h (curve.h): 1 = the a = -1 model (both bases of odd order), 0 = the a = 1 image
     return which == 0 ? c->dbg_recheck_proofs : which == 2 ? c->dbg_msm_terms : which == 3 ? c->dbg_p256_batched : 0;
 }

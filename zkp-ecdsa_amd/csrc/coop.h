@@ -384,6 +384,37 @@ ZK_DEV CoFe<M, 1> co_const(const uint32_t (&c)[NLIMB]) {   // the constant in ev
 }
 ZK_DEV CoU32 co_row_is(uint32_t r) { return co_eq(co_row_index(), r); }
 
+// ---- Tom-256 on the a = -1 model of the fixed-base comb tables (curve.h: TomM1Pt), rows X, Y, T, Z
+// E = B - A, F = D - C, G = D + C, H = B + A from rows A, B, C, D;  then E F, G H, E H, F G
+ZK_DEV CoTom co_tom_m1_tail(const CoFe<ModT, 2>& m, const CoU32& mj) {
+    const auto w = co_addsub(co_rows<1, 3, 3, 1>(m), co_rows<0, 2, 2, 0>(m), co_lt(co_row_index(), 2));
+    CoTom r;
+    r.v = co_mul(co_rows<0, 2, 0, 1>(w), co_rows<1, 3, 3, 2>(w), mj);
+    return r;
+}
+ZK_DEV CoFe<ModT, 6> co_tom_m1_lhs(const CoTom& p) {   // Y - X, Y + X, T, Z
+    return co_addsub(co_rows<1, 1, 2, 3>(p.v), co_rows<0, 0, 4, 4>(p.v), co_row_is(0));
+}
+// addition of a comb entry, rows y' - x'', y' + x'', 2 d2 x'' y' and the constant 2 (so that D = 2 Z comes out of the same pass): seven products in TWO passes
+ZK_DEV CoTom co_tom_m1_add_tab(const CoTom& p, const CoFe<ModT, 2>& ent, const CoU32& mj) {
+    return co_tom_m1_tail(co_mul(co_tom_m1_lhs(p), ent, mj), mj);
+}
+// general addition (curve.h: tom_m1_add_t): three passes, the second multiplies C0 by 2 d2 and D0 by 2
+ZK_DEV CoTom co_tom_m1_add(const CoTom& p, const CoTom& q, const CoU32& mj) {
+    const auto m1 = co_mul(co_tom_m1_lhs(p), co_tom_m1_lhs(q), mj);                              // A, B, C0 = t1 t2, D0 = z1 z2
+    CoFe<ModT, 1> k;
+    k.v = co_sel(co_lt(co_row_index(), 2), co_limbs(ModT::one), co_sel(co_row_is(2), co_limbs(TOM_M1_2D2_M), co_limbs(TOM_TWO_M)));
+    return co_tom_m1_tail(co_mul(m1, k, mj), mj);
+}
+// a finished sum back on the a = 1 image: x' = X / (s2 Z), y = Z / Y, i.e. the projective (T / s2 : Z : - : Y) in rows X, Y, T, Z (T is not carried over)
+ZK_DEV CoTom co_tom_m1_to_a1(const CoTom& p, const CoU32& mj) {
+    CoFe<ModT, 1> k;
+    k.v = co_sel(co_row_is(0), co_limbs(TOM_M1_SINV_M), co_limbs(ModT::one));
+    CoTom r;
+    r.v = co_mul(co_rows<2, 3, 4, 1>(p.v), k, mj);
+    return r;
+}
+
 // ---- P-256, homogeneous (X : Y : Z) in rows 0, 1, 2 (row 3 of a point register is ignored), the complete Renes-Costello-Batina laws of curve.h
 // (weier.ts:133-230) with their 14 / 13 products dealt to FOUR passes of at most four rows.
 struct CoP256 {

@@ -352,3 +352,147 @@ ZK_DEV bool tom_from_affine_words(TomPt& r, const uint32_t xw[9], const uint32_t
     r.z = fe_one_mont<ModT>().as<2>();
     return ok;
 }
+
+// ---------------------------------------------------------------- Tom-256 on the a = -1 model: the fixed-base comb tables of g and h ONLY
+// (x', y) on the a = 1 image  ->  (x'', y') = (s2 * x', 1 / y), s2^2 = -d/a:  -x''^2 + y'^2 = 1 + d2 x''^2 y'^2, d2 = -a/d.  A group isomorphism away from
+// the two points with y = 0 (order 4); it fixes the identity.  On this model E = X1 y2 + Y1 x2 and H = Y1 y2 + X1 x2 come out of (Y1 - X1)(y2 - x2) and
+// (Y1 + X1)(y2 + x2) alone ("madd-2008-hwcd-3"), so the addition of a table entry costs 7 products instead of 8.  -1 is a non-square and d2 a square mod t
+// (tools/gen_consts.py), so the law is complete only on points of ODD order: the exceptional pairs differ by a point of even order.  Multiples of bases
+// with q * g = q * h = identity (checked when the parameters are set, api.hip) never form such a pair; every sum over points taken from a proof stays
+// on the a = 1 law above.  The LAST step of a sum maps back -- x' = X3 / (s2 Z3), y = Z3 / Y3, i.e. the triple (E H / s2 : F G : G H) -- so the
+// normaliser and everything behind it see the a = 1 image as before.
+struct TomM1Pt {  // extended (X:Y:T:Z); the bounds are those of the first step of a sum (tom_m1_from_niels), every addition returns coordinates < 2t
+    Fe<ModT, 12> x;
+    Fe<ModT, 8> y;
+    Ft2 t, z;
+};
+template <int KT>
+struct TomM1NielsT {  // y' - x'', y' + x'', 2 d2 x'' y'; the identity entry is (1, 1, 0)
+    Ft2 ym, yp;
+    Fe<ModT, KT> t2;
+};
+// a loaded table entry (three field elements, in the slots of a TomNiels) as it is used; neg: -P swaps the first two and negates the third
+ZK_DEV TomM1NielsT<2> tom_m1_niels(const TomNiels& q) {
+    TomM1NielsT<2> r;
+    r.ym = q.x, r.yp = q.y, r.t2 = q.dt;
+    return r;
+}
+ZK_DEV TomM1NielsT<4> tom_m1_niels_neg_sel(const TomNiels& q, bool neg) {
+    TomM1NielsT<4> r;
+    r.ym = fe_select(neg, q.y, q.x);
+    r.yp = fe_select(neg, q.x, q.y);
+#pragma unroll
+    for (int i = 0; i < NLIMB; i++) r.t2.l[i] = neg ? ModT::sub4[i] - q.dt.l[i] : q.dt.l[i];
+    limbs_normalize(r.t2.l);
+    return r;
+}
+ZK_DEV TomM1Pt tom_m1_identity() {
+    TomM1Pt r;
+    r.x = fe_zero<ModT>().as<12>();
+    r.y = fe_one_mont<ModT>().as<8>();
+    r.t = fe_zero<ModT>().as<2>();
+    r.z = fe_one_mont<ModT>().as<2>();
+    return r;
+}
+// E F, G H, E H, F G
+template <int KE, int KF, int KG, int KH>
+ZK_DEV TomM1Pt tom_m1_finish(const Fe<ModT, KE>& E, const Fe<ModT, KF>& F, const Fe<ModT, KG>& G, const Fe<ModT, KH>& H) {
+    Ft2 x, y;
+    TomM1Pt r;
+    fe_mul4<ZK_BATCH_TOM != 0>(x, y, r.t, r.z, E, F, G, H, E, H, F, G);
+    r.x = x.as<12>(), r.y = y.as<8>();
+    return r;
+}
+// the sum is final: x, y, z of the result hold the a = 1 image's projective triple (E H / s2 : F G : G H), t is zero
+template <int KE, int KF, int KG, int KH>
+ZK_DEV TomM1Pt tom_m1_finish_last(const Fe<ModT, KE>& E, const Fe<ModT, KF>& F, const Fe<ModT, KG>& G, const Fe<ModT, KH>& H) {
+    Ft2 eh, y;
+    TomM1Pt r;
+    fe_mul3<ZK_BATCH_TOM != 0>(eh, y, r.z, E, H, F, G, G, H);
+    r.x = (eh * fe_const<ModT, 1>(TOM_M1_SINV_M)).as<12>();
+    r.y = y.as<8>();
+    r.t = fe_zero<ModT>().as<2>();
+    return r;
+}
+// mixed addition of a table entry: 3 + 4 lock-step products
+template <bool LAST, int KT>
+ZK_DEV TomM1Pt tom_m1_add_niels_t(const TomM1Pt& p, const TomM1NielsT<KT>& q) {
+    Ft2 A, B, C;
+    fe_mul3<ZK_BATCH_TOM != 0>(A, B, C, p.y - p.x, q.ym, p.y + p.x, q.yp, p.t, q.t2);
+    auto D = p.z + p.z;
+    auto E = B - A;
+    auto F = D - C;
+    auto G = D + C;
+    auto H = B + A;
+    if constexpr (LAST) return tom_m1_finish_last(E, F, G, H);
+    else return tom_m1_finish(E, F, G, H);
+}
+template <int KT>
+ZK_DEV TomM1Pt tom_m1_add_niels(const TomM1Pt& p, const TomM1NielsT<KT>& q) { return tom_m1_add_niels_t<false>(p, q); }
+template <int KT>
+ZK_DEV TomM1Pt tom_m1_add_niels_last(const TomM1Pt& p, const TomM1NielsT<KT>& q) { return tom_m1_add_niels_t<true>(p, q); }
+// identity + q, scaled by 4: X = 2 (yp - ym), Y = 2 (yp + ym), T = (yp - ym)(yp + ym), Z = 4: 1 product
+template <int KT>
+ZK_DEV TomM1Pt tom_m1_from_niels(const TomM1NielsT<KT>& q) {
+    auto dm = q.yp - q.ym;
+    auto dp = q.yp + q.ym;
+    TomM1Pt r;
+    r.x = dm + dm;
+    r.y = dp + dp;
+    r.t = dm * dp;
+    r.z = fe_const<ModT, 1>(TOM_FOUR_M).as<2>();
+    return r;
+}
+// general addition of two extended points (partial sums of the wide kernel): 8 products and one by 2 d2
+template <bool LAST>
+ZK_DEV TomM1Pt tom_m1_add_t(const TomM1Pt& p, const TomM1Pt& q) {
+    Ft2 A, B, C0, D0;
+    fe_mul4<ZK_BATCH_TOM != 0>(A, B, C0, D0, p.y - p.x, q.y - q.x, p.y + p.x, q.y + q.x, p.t, q.t, p.z, q.z);
+    Ft2 C = C0 * fe_const<ModT, 1>(TOM_M1_2D2_M);
+    auto D = D0 + D0;
+    auto E = B - A;
+    auto F = D - C;
+    auto G = D + C;
+    auto H = B + A;
+    if constexpr (LAST) return tom_m1_finish_last(E, F, G, H);
+    else return tom_m1_finish(E, F, G, H);
+}
+
+// The two models behind one interface: the comb kernels (k_tom.hip) and the table builder (k_tables.hip) are templates over MODEL.
+//   Pt: accumulator;  entry / entry_neg: a loaded table entry as used (signed combs negate it on load);  first: identity + entry;  add: + entry;
+//   add_last: + entry where the sum is final: x, y, z of the result are the a = 1 image's projective triple (what the lists and the normaliser take);
+//   add_pts / add_pts_last: the same for two accumulators.
+#define TOM_MODEL_A1 0
+#define TOM_MODEL_M1 1
+template <int MODEL>
+struct TomModel;
+template <>
+struct TomModel<TOM_MODEL_A1> {
+    typedef TomPt Pt;
+    static ZK_DEV Pt identity() { return tom_identity(); }
+    static ZK_DEV TomNiels entry(const TomNiels& q) { return q; }
+    static ZK_DEV TomNielsT<4> entry_neg(const TomNiels& q, bool neg) { return tom_niels_neg_sel(q, neg); }
+    template <class E>
+    static ZK_DEV Pt first(const E& e) { return tom_from_niels(e); }
+    template <class E>
+    static ZK_DEV Pt add(const Pt& p, const E& e) { return tom_add_niels(p, e); }
+    template <class E>
+    static ZK_DEV Pt add_last(const Pt& p, const E& e) { return tom_add_niels_last(p, e); }
+    static ZK_DEV Pt add_pts(const Pt& p, const Pt& q) { return tom_add(p, q); }
+    static ZK_DEV Pt add_pts_last(const Pt& p, const Pt& q) { return tom_add(p, q); }
+};
+template <>
+struct TomModel<TOM_MODEL_M1> {
+    typedef TomM1Pt Pt;
+    static ZK_DEV Pt identity() { return tom_m1_identity(); }
+    static ZK_DEV TomM1NielsT<2> entry(const TomNiels& q) { return tom_m1_niels(q); }
+    static ZK_DEV TomM1NielsT<4> entry_neg(const TomNiels& q, bool neg) { return tom_m1_niels_neg_sel(q, neg); }
+    template <class E>
+    static ZK_DEV Pt first(const E& e) { return tom_m1_from_niels(e); }
+    template <class E>
+    static ZK_DEV Pt add(const Pt& p, const E& e) { return tom_m1_add_niels(p, e); }
+    template <class E>
+    static ZK_DEV Pt add_last(const Pt& p, const E& e) { return tom_m1_add_niels_last(p, e); }
+    static ZK_DEV Pt add_pts(const Pt& p, const Pt& q) { return tom_m1_add_t<false>(p, q); }
+    static ZK_DEV Pt add_pts_last(const Pt& p, const Pt& q) { return tom_m1_add_t<true>(p, q); }
+};

@@ -104,6 +104,7 @@ struct DevParams {            // device-resident, built by zk_ctx_set_params
     uint32_t* tom_tab_g;      // tom_tab_words(tom_bits)
     uint32_t* tom_tab_h;
     uint32_t tom_bits;        // comb width of the two tables
+    uint32_t tom_model;       // form of their entries (curve.h): TOM_MODEL_M1 when q * g = q * h = identity, else TOM_MODEL_A1
     uint32_t* pfix_G;         // PFIX_TAB_WORDS
     uint32_t* pfix_H;
     uint32_t tom_g_aff[18];   // original-curve affine plain limbs of g (x, y) -- C_14 in pointAdd.ts:144
@@ -443,7 +444,8 @@ void launch_gk_block_stage(hipStream_t s, const Workspace& W, const ChunkIn& in,
 struct VWork;
 void launch_v_gk_block_stage(hipStream_t s, const VWork& V, const uint32_t* E, uint32_t nblocks, uint32_t count, uint32_t* csub, const Soa& res);
 // k_tables.hip
-void launch_build_tom_table(hipStream_t s, const uint32_t* aff_xy_words /*18 words on device*/, uint32_t bits, uint32_t* tab, uint32_t* scratch, int32_t* ok);
+void launch_build_tom_table(hipStream_t s, const uint32_t* aff_xy_words /*18 words on device*/, uint32_t bits, uint32_t model, uint32_t* tab, uint32_t* scratch, int32_t* ok);
+void launch_tom_order_check(hipStream_t s, const uint32_t* xy_g, const uint32_t* xy_h, int32_t* odd /* [2] */);   // odd[i] = (q * base_i == identity)
 size_t tom_table_scratch_words(uint32_t bits);
 void launch_build_pfix_table(hipStream_t s, const uint32_t* aff_xy_words /*16 words on device, or nullptr for G*/, uint32_t* tab, uint32_t* scratch, int32_t* ok);
 size_t pfix_table_scratch_words();
@@ -451,6 +453,7 @@ size_t pfix_table_scratch_words();
 void launch_tom_commit(hipStream_t s, const DevParams& P, const TomList& L, uint32_t count, uint32_t per_group, uint32_t slots_per_group, uint32_t kstride = 0);
 // the commitments of the listed slots only (`list[i]`, i < *count_dev <= max_count: the verifier's T1x / T1y exist for zero-bit repetitions only)
 void launch_tom_commit_list(hipStream_t s, const DevParams& P, const TomList& L, const uint32_t* list, const uint32_t* count_dev, uint32_t max_count);
+bool launch_tom_commit_shape(hipStream_t s, const DevParams& P, const TomList& L, uint32_t count, uint32_t shape, const uint32_t* list, const uint32_t* count_dev);   // test hook
 void launch_tom_commit_listb(hipStream_t s, const DevParams& P, const TomList& L, uint32_t items, uint32_t kstride);  // the 34 commitments of every PointAdd item
 void launch_tom_normalize(hipStream_t s, const TomList& L, uint32_t count, uint32_t first, uint32_t per_group, uint32_t slots_per_group, uint32_t kstride = 0);
 void launch_padd_derived(hipStream_t s, const Workspace& W, uint32_t items);

@@ -13,6 +13,9 @@
 //   3. k_tomtab_compose entry[w][d] = Lo[w][d mod 2^lo] + Hi[w][d >> lo]: one addition, then to affine with
 //                       Montgomery's trick over 8 entries per thread (prefix products parked in the entries
 //                       themselves, the sums recomputed on the way back: 2 x 9 + 3 + 4 modmuls + 1/8 inversion per entry).
+//                       The entries are written in the form of the chosen MODEL (curve.h: TomModel): (x, y, d' x y) of the a = 1 image, or
+//                       (y' - x'', y' + x'', 2 d2 x'' y') of the a = -1 model with x'' = s2 X / Z, y' = Z / Y -- there Y Z is what gets inverted
+//                       (no multiple of a base of odd order has Y = 0), four more products per entry.
 // scratch layout (words): window bases [nwin][36], then per window Lo [2^lo][36] and Hi [2^hi][36]
 // digits run over [0, E), E = tom_win_entries(bits) (2^bits, or 2^(bits-1) + 1 for the signed widths): split d = i + j * 2^lo
 static inline uint32_t tom_lo_bits(uint32_t bits) { return ((tom_signed(bits) ? bits - 1 : bits) + 1) / 2; }
@@ -66,6 +69,7 @@ __global__ void __launch_bounds__(64) k_tomtab_sub(uint32_t* scratch, uint32_t n
     st_tompt(scratch + (size_t)36 * nwin + (size_t)36 * t, acc);
 }
 #define TOMTAB_PER 8
+template <int MODEL>
 __global__ void __launch_bounds__(256) k_tomtab_compose(const uint32_t* scratch, uint32_t* tab, uint32_t ent, uint32_t nwin, uint32_t lo, uint32_t n_hi, uint32_t nthreads) {
     uint32_t t = gtid();
     if (t >= nthreads) return;
@@ -84,10 +88,11 @@ __global__ void __launch_bounds__(256) k_tomtab_compose(const uint32_t* scratch,
         uint32_t* pe = tab + (size_t)TOM_ENTRY_WORDS * e;  // the prefix product is parked in the entry it belongs to
 #pragma unroll
         for (int l = 0; l < 9; l++) pe[l] = acc.l[l];
-        acc = acc * entry_sum(e).z;
+        const TomPt s = entry_sum(e);
+        if constexpr (MODEL == TOM_MODEL_M1) acc = acc * (s.y * s.z);
+        else acc = acc * s.z;
     }
     Ft2 inv = fe_inv<ModT>(acc);
-    const auto d1 = fe_const<ModT, 1>(TOM_D1_M);
     for (int j = TOMTAB_PER - 1; j >= 0; j--) {
         uint64_t e = t + (uint64_t)j * nthreads;
         if (e >= total) continue;
@@ -95,27 +100,62 @@ __global__ void __launch_bounds__(256) k_tomtab_compose(const uint32_t* scratch,
         Ft2 pre;
 #pragma unroll
         for (int l = 0; l < 9; l++) pre.l[l] = tab[(size_t)TOM_ENTRY_WORDS * e + l];
-        Ft2 zi = inv * pre;
-        inv = inv * s.z;
-        Ft2 x = s.x * zi, y = s.y * zi;
-        Ft2 dt = (x * y) * d1;
+        Ft2 e0, e1, e2;
+        if constexpr (MODEL == TOM_MODEL_M1) {
+            Ft2 wi = inv * pre;   // 1 / (Y Z)
+            inv = inv * (s.y * s.z);
+            Ft2 zz = s.z * s.z, sxy = (s.x * s.y) * fe_const<ModT, 1>(TOM_M1_S_M);   // x'' = s2 X / Z = s2 X Y / (Y Z), y' = Z / Y = Z^2 / (Y Z)
+            e0 = (zz - sxy) * wi, e1 = (zz + sxy) * wi;
+            e2 = ((e1 - e0) * (e1 + e0)) * fe_const<ModT, 1>(TOM_M1_D2H_M);           // 2 d2 x'' y' = (d2 / 2) (yp - ym)(yp + ym)
+        } else {
+            Ft2 zi = inv * pre;
+            inv = inv * s.z;
+            e0 = s.x * zi, e1 = s.y * zi;
+            e2 = (e0 * e1) * fe_const<ModT, 1>(TOM_D1_M);
+        }
         uint4* q = (uint4*)(tab + (size_t)TOM_ENTRY_WORDS * e);
         uint32_t w[28];
 #pragma unroll
-        for (int l = 0; l < 9; l++) w[l] = x.l[l], w[9 + l] = y.l[l], w[18 + l] = dt.l[l];
+        for (int l = 0; l < 9; l++) w[l] = e0.l[l], w[9 + l] = e1.l[l], w[18 + l] = e2.l[l];
         w[27] = 0;
 #pragma unroll
         for (int i = 0; i < 7; i++) q[i] = make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
     }
 }
-void launch_build_tom_table(hipStream_t s, const uint32_t* xy, uint32_t bits, uint32_t* tab, uint32_t* scratch, int32_t* ok) {
+void launch_build_tom_table(hipStream_t s, const uint32_t* xy, uint32_t bits, uint32_t model, uint32_t* tab, uint32_t* scratch, int32_t* ok) {
     uint32_t nwin = tom_nwin(bits), lo = tom_lo_bits(bits), n_hi = tom_n_hi(bits), ent = tom_win_entries(bits);
     hipLaunchKernelGGL(k_tomtab_bases, dim3(1), dim3(64), 0, s, xy, scratch, ok, bits, nwin);
     uint32_t nsub = nwin * ((1u << lo) + n_hi);
     hipLaunchKernelGGL(k_tomtab_sub, dim3((nsub + 63) / 64), dim3(64), 0, s, scratch, nwin, lo, n_hi);
     uint64_t total = (uint64_t)nwin * ent;
     uint32_t nthreads = (uint32_t)((total + TOMTAB_PER - 1) / TOMTAB_PER);
-    hipLaunchKernelGGL(k_tomtab_compose, dim3((nthreads + 255) / 256), dim3(256), 0, s, scratch, tab, ent, nwin, lo, n_hi, nthreads);
+    if (model == TOM_MODEL_M1) hipLaunchKernelGGL(k_tomtab_compose<TOM_MODEL_M1>, dim3((nthreads + 255) / 256), dim3(256), 0, s, scratch, tab, ent, nwin, lo, n_hi, nthreads);
+    else hipLaunchKernelGGL(k_tomtab_compose<TOM_MODEL_A1>, dim3((nthreads + 255) / 256), dim3(256), 0, s, scratch, tab, ent, nwin, lo, n_hi, nthreads);
+}
+// q * P for the two bases of a parameter set (xy: 18 plain words each, lane 0 and lane 1), on the a = 1 law, which is complete for every point of the curve:
+// odd[i] = 1 where the result is the identity, i.e. where P lies in the subgroup of odd order q.  Only then may P's comb table live on the a = -1 model
+// (curve.h).  A point off the curve or with a coordinate >= t gives 0; the table builder reports it.
+__global__ void __launch_bounds__(64) k_tom_order_check(const uint32_t* xy_g, const uint32_t* xy_h, int32_t* odd) {
+    const uint32_t i = gtid();
+    if (i >= 2) return;
+    const uint32_t* xy = i ? xy_h : xy_g;
+    uint32_t xw[9], yw[9];
+    for (int k = 0; k < 9; k++) xw[k] = xy[k], yw[k] = xy[9 + k];
+    TomPt p;
+    const bool good = tom_from_affine_words(p, xw, yw);
+    TomPt acc = tom_identity();
+#pragma unroll 1
+    for (int b = ModQ::bits - 1; b >= 0; b--) {
+        acc = tom_dbl(acc);
+        const TomPt s = tom_add(acc, p);
+        const bool bit = (ModQ::mod32[b >> 5] >> (b & 31)) & 1;
+        acc.x = fe_select(bit, s.x, acc.x), acc.y = fe_select(bit, s.y, acc.y);
+        acc.t = fe_select(bit, s.t, acc.t), acc.z = fe_select(bit, s.z, acc.z);
+    }
+    odd[i] = good && fe_is_zero(fe_reduce(acc.x)) && fe_eq(acc.y, acc.z) ? 1 : 0;
+}
+void launch_tom_order_check(hipStream_t s, const uint32_t* xy_g, const uint32_t* xy_h, int32_t* odd) {
+    hipLaunchKernelGGL(k_tom_order_check, dim3(1), dim3(64), 0, s, xy_g, xy_h, odd);
 }
 
 // ---------------------------------------------------------------- P-256 fixed bases

@@ -41,19 +41,15 @@ ZK_DEV void niels_pin(TomNiels& n) {
 __device__ const uint8_t LB_SINGLE_K[16] = {0, 1, 2, 6, 7, 8, 11, 13, 14, 17, 19, 20, 23, 25, 26, 29};
 __device__ const uint8_t LB_PAIR_K0[9] = {9, 15, 21, 27, 30, 32, 3, 4, 5};
 __device__ const uint8_t LB_PAIR_K1[9] = {10, 16, 22, 28, 31, 33, 12, 18, 24};
-template <bool SGN>
-struct NielsSel;  // table entry as used by the addition: as loaded (unsigned combs) or conditionally negated (signed combs)
-template <>
-struct NielsSel<false> {
-    typedef TomNiels T;
-    static ZK_DEV T sel(const TomNiels& q, bool) { return q; }
-};
-template <>
-struct NielsSel<true> {
-    typedef TomNielsT<4> T;
-    static ZK_DEV T sel(const TomNiels& q, bool neg) { return tom_niels_neg_sel(q, neg); }
-};
-template <int OCC, bool SGN>
+// Every kernel that reads the comb tables is a template over the MODEL their entries are written in (curve.h: TomModel; DevParams::tom_model): the a = -1
+// model of bases of odd order (7 products per addition) or the a = 1 image (8).  Each emits the a = 1 image's projective triple at its last step.
+// table entry as used by the addition: as loaded (unsigned combs) or conditionally negated (signed combs)
+template <int MODEL, bool SGN>
+ZK_DEV auto niels_sel(const TomNiels& q, bool neg) {
+    if constexpr (SGN) return TomModel<MODEL>::entry_neg(q, neg);
+    else return TomModel<MODEL>::entry(q);
+}
+template <int OCC, bool SGN, int MODEL>
 __global__ void __launch_bounds__(256, OCC) k_tom_commit(const uint32_t* __restrict__ tab_g, const uint32_t* __restrict__ tab_h, TomList L,
                                                          uint32_t count, uint32_t per_group, uint32_t slots_per_group, uint32_t kstride,
                                                          uint32_t bits, uint32_t nwin, uint32_t lb_singles) {
@@ -72,7 +68,8 @@ __global__ void __launch_bounds__(256, OCC) k_tom_commit(const uint32_t* __restr
         words_from_limbs<8>(dgr.w, r.l);
     }
     const uint32_t ent = tom_win_entries(bits);
-    TomPt acc = tom_identity();
+    typedef TomModel<MODEL> TM;
+    typename TM::Pt acc = TM::identity();
     // software pipeline, one addition deep: the h-entry of window w is gathered during the g-addition of window w, the
     // g-entry of window w+1 during the h-addition (one entry in flight, one in use: 54 VGPRs instead of 108)
     // A g-window whose digit is 0 in EVERY lane of the wave is skipped (entry 0 is the identity): list B is item-fastest, so a wave
@@ -89,8 +86,8 @@ __global__ void __launch_bounds__(256, OCC) k_tom_commit(const uint32_t* __restr
         nh = ld_niels(tab_h + (size_t)TOM_ENTRY_WORDS * (base + dr));
         if (g_live) {
             niels_pin(ng);
-            typename NielsSel<SGN>::T cg = NielsSel<SGN>::sel(ng, sv);
-            acc = w == 0 ? tom_from_niels(cg) : tom_add_niels(acc, cg);                  // first step: identity + entry
+            const auto cg = niels_sel<MODEL, SGN>(ng, sv);
+            acc = w == 0 ? TM::first(cg) : TM::add(acc, cg);                             // first step: identity + entry
         }
         if (w + 1 < nwin) {
             dgv.next(dv, sv);
@@ -99,8 +96,8 @@ __global__ void __launch_bounds__(256, OCC) k_tom_commit(const uint32_t* __restr
         }
         niels_pin(nh);
         {
-            typename NielsSel<SGN>::T ch = NielsSel<SGN>::sel(nh, sr);
-            acc = w + 1 == nwin ? tom_add_niels_last(acc, ch) : tom_add_niels(acc, ch);  // last step: nobody reads T
+            const auto ch = niels_sel<MODEL, SGN>(nh, sr);
+            acc = w + 1 == nwin ? TM::add_last(acc, ch) : TM::add(acc, ch);              // last step: the a = 1 image's (X : Y : Z), nobody reads T
         }
     }
     soa_st(L.proj.x, slot, acc.x);
@@ -118,8 +115,9 @@ __global__ void __launch_bounds__(256, OCC) k_tom_commit(const uint32_t* __restr
 #define LB_UNITS_PAIR 9
 // acc += sum_w tab[w][digit_w(words)], gathers pipelined one window ahead.  FIRST: acc is the identity (the first entry is
 // taken as is); LAST: the result is final (no T coordinate).
-template <bool FIRST, bool LAST, bool SGN>
-ZK_DEV TomPt tom_comb_acc(TomPt acc, const uint32_t* __restrict__ tab, uint32_t* words, uint32_t bits, uint32_t nwin) {
+template <bool FIRST, bool LAST, bool SGN, int MODEL>
+ZK_DEV typename TomModel<MODEL>::Pt tom_comb_acc(typename TomModel<MODEL>::Pt acc, const uint32_t* __restrict__ tab, uint32_t* words, uint32_t bits, uint32_t nwin) {
+    typedef TomModel<MODEL> TM;
     CombDigits dg;
     dg.init(bits);
 #pragma unroll
@@ -132,19 +130,19 @@ ZK_DEV TomPt tom_comb_acc(TomPt acc, const uint32_t* __restrict__ tab, uint32_t*
 #pragma unroll 1
     for (uint32_t w = 0; w < nwin; w++) {
         niels_pin(nx);
-        typename NielsSel<SGN>::T cur = NielsSel<SGN>::sel(nx, sg);
+        const auto cur = niels_sel<MODEL, SGN>(nx, sg);
         if (w + 1 < nwin) {
             dg.next(d, nsg);
             nx = ld_niels(tab + (size_t)TOM_ENTRY_WORDS * ((size_t)(w + 1) * ent + d));
         }
         sg = nsg;
-        if (FIRST && w == 0) acc = tom_from_niels(cur);
-        else if (LAST && w + 1 == nwin) acc = tom_add_niels_last(acc, cur);
-        else acc = tom_add_niels(acc, cur);
+        if (FIRST && w == 0) acc = TM::first(cur);
+        else if (LAST && w + 1 == nwin) acc = TM::add_last(acc, cur);
+        else acc = TM::add(acc, cur);
     }
     return acc;
 }
-template <bool SGN>
+template <bool SGN, int MODEL>
 __global__ void __launch_bounds__(256, 2) k_tom_commit_pairs(const uint32_t* __restrict__ tab_g, const uint32_t* __restrict__ tab_h, TomList L,
                                                              uint32_t items, uint32_t kstride, uint32_t bits, uint32_t nwin) {
     uint32_t c = gtid();
@@ -152,20 +150,22 @@ __global__ void __launch_bounds__(256, 2) k_tom_commit_pairs(const uint32_t* __r
     uint32_t slot0 = LB_PAIR_K0[c / items] * kstride + c % items, slot1 = LB_PAIR_K1[c / items] * kstride + c % items;
     uint32_t w8[8];
     words_from_limbs<8>(w8, soa_ld<ModQ, 1>(L.v, slot0).l);
-    TomPt G = tom_comb_acc<true, false, SGN>(tom_identity(), tab_g, w8, bits, nwin);
+    typedef typename TomModel<MODEL>::Pt Pt;
+    Pt G = tom_comb_acc<true, false, SGN, MODEL>(TomModel<MODEL>::identity(), tab_g, w8, bits, nwin);
     words_from_limbs<8>(w8, soa_ld<ModQ, 1>(L.r, slot0).l);
-    TomPt A = tom_comb_acc<false, true, SGN>(G, tab_h, w8, bits, nwin);
+    Pt A = tom_comb_acc<false, true, SGN, MODEL>(G, tab_h, w8, bits, nwin);
     soa_st(L.proj.x, slot0, A.x), soa_st(L.proj.y, slot0, A.y), soa_st(L.proj.z, slot0, A.z);
     words_from_limbs<8>(w8, soa_ld<ModQ, 1>(L.r, slot1).l);
-    A = tom_comb_acc<false, true, SGN>(G, tab_h, w8, bits, nwin);
+    A = tom_comb_acc<false, true, SGN, MODEL>(G, tab_h, w8, bits, nwin);
     soa_st(L.proj.x, slot1, A.x), soa_st(L.proj.y, slot1, A.y), soa_st(L.proj.z, slot1, A.z);
 }
 // ---- the same commitments for a SMALL launch, four lanes each (engine.h: ZK_WIDE_MAX_UNITS).  The comb tables hold every window multiple, so lane `part`
 // takes windows [part * per, part * per + per) of v's g-part and r's h-part -- 3 + 3 table additions at 24 bits instead of 11 + 11 in a row -- and the four
 // partial points are added through the wave's cross-lane moves (two complete extended additions).  Same group element, hence the same affine
 // coordinates once the list is normalised.  Unsigned combs only (a signed comb's zero digit is not the identity entry; those widths keep one lane).
-ZK_DEV TomPt tom_shfl_xor(const TomPt& a, int m) {
-    TomPt r;
+template <class PT>
+ZK_DEV PT tom_shfl_xor(const PT& a, int m) {
+    PT r;
 #pragma unroll
     for (int l = 0; l < NLIMB; l++) {
         r.x.l[l] = (uint32_t)__shfl_xor((int)a.x.l[l], m), r.y.l[l] = (uint32_t)__shfl_xor((int)a.y.l[l], m);
@@ -174,7 +174,8 @@ ZK_DEV TomPt tom_shfl_xor(const TomPt& a, int m) {
     return r;
 }
 // acc + sum over windows [w0, w0 + per) of tab[w][digit_w(k)]; windows past the last one (and what the scalar has no bits for) add entry 0 of window 0, the identity
-ZK_DEV TomPt tom_comb_range(TomPt acc, const uint32_t* __restrict__ tab, const uint32_t kw[8], uint32_t bits, uint32_t nwin, uint32_t w0, uint32_t per) {
+template <int MODEL>
+ZK_DEV typename TomModel<MODEL>::Pt tom_comb_range(typename TomModel<MODEL>::Pt acc, const uint32_t* __restrict__ tab, const uint32_t kw[8], uint32_t bits, uint32_t nwin, uint32_t w0, uint32_t per) {
     CombDigits dg;
     dg.init(bits);
 #pragma unroll
@@ -191,10 +192,11 @@ ZK_DEV TomPt tom_comb_range(TomPt acc, const uint32_t* __restrict__ tab, const u
         const bool in = w < nwin;
         TomNiels e = ld_niels(tab + (size_t)TOM_ENTRY_WORDS * (in ? (size_t)w * ent + d : 0));
         niels_pin(e);
-        acc = tom_add_niels(acc, e);
+        acc = TomModel<MODEL>::add(acc, TomModel<MODEL>::entry(e));
     }
     return acc;
 }
+template <int MODEL>
 __global__ void __launch_bounds__(256) k_tom_commit_wide(const uint32_t* __restrict__ tab_g, const uint32_t* __restrict__ tab_h, TomList L, uint32_t count, uint32_t per_group,
                                                          uint32_t slots_per_group, uint32_t kstride, uint32_t bits, uint32_t nwin) {
     const uint32_t tt = gtid();
@@ -206,10 +208,11 @@ __global__ void __launch_bounds__(256) k_tom_commit_wide(const uint32_t* __restr
     words_from_limbs<8>(vw, soa_ld<ModQ, 1>(L.v, slot).l);
     words_from_limbs<8>(rw, soa_ld<ModQ, 1>(L.r, slot).l);
     const uint32_t per = (nwin + 3) / 4;
-    TomPt acc = tom_comb_range(tom_identity(), tab_g, vw, bits, nwin, part * per, per);
-    acc = tom_comb_range(acc, tab_h, rw, bits, nwin, part * per, per);
-    acc = tom_add(acc, tom_shfl_xor(acc, 1));
-    acc = tom_add(acc, tom_shfl_xor(acc, 2));
+    typedef TomModel<MODEL> TM;
+    typename TM::Pt acc = tom_comb_range<MODEL>(TM::identity(), tab_g, vw, bits, nwin, part * per, per);
+    acc = tom_comb_range<MODEL>(acc, tab_h, rw, bits, nwin, part * per, per);
+    acc = TM::add_pts(acc, tom_shfl_xor(acc, 1));
+    acc = TM::add_pts_last(acc, tom_shfl_xor(acc, 2));   // the a = 1 image's (X : Y : Z)
     if (!live || part) return;
     soa_st(L.proj.x, slot, acc.x);
     soa_st(L.proj.y, slot, acc.y);
@@ -218,6 +221,7 @@ __global__ void __launch_bounds__(256) k_tom_commit_wide(const uint32_t* __restr
 // ---- and for a call of a few proofs: one commitment per workgroup of four cooperating waves (coop.h).  Wave `part` adds the table entries of its quarter of the
 // windows (g-part, then h-part) at three passes an addition -- 0.9 us instead of one lane's 4.5 -- and the four partial points meet in LDS.  The same group
 // element again, hence the same bytes.  A zero digit's entry is the identity and is added like any other (no digit-dependent control flow here at all).
+template <int MODEL>
 ZK_DEV CoTom co_tom_comb_range(CoTom acc, const uint32_t* __restrict__ tab, const uint32_t kw[8], uint32_t bits, uint32_t nwin, uint32_t w0, uint32_t per, const CoU32& mj) {
     CombDigits dg;
     dg.init(bits);
@@ -231,12 +235,18 @@ ZK_DEV CoTom co_tom_comb_range(CoTom acc, const uint32_t* __restrict__ tab, cons
 #pragma unroll 1
     for (uint32_t w = w0; w < w0 + per && w < nwin; w++) {
         dg.next(d, sg);
-        CoFe<ModT, 2> e = co_load_aos<ModT, 2, 3>(tab + (size_t)TOM_ENTRY_WORDS * ((size_t)w * ent + d));   // rows x, y, d'T
-        if (co_row_index() == 3) e.v = co_limbs(ModT::one);                                              // Z = 1
-        acc = co_tom_add_tab(acc, e, false, mj);
+        CoFe<ModT, 2> e = co_load_aos<ModT, 2, 3>(tab + (size_t)TOM_ENTRY_WORDS * ((size_t)w * ent + d));   // rows x, y, d'T -- or y' - x'', y' + x'', 2 d2 x'' y'
+        if constexpr (MODEL == TOM_MODEL_M1) {
+            if (co_row_index() == 3) e.v = co_limbs(TOM_TWO_M);                                          // D = 2 Z comes out of the same pass
+            acc = co_tom_m1_add_tab(acc, e, mj);
+        } else {
+            if (co_row_index() == 3) e.v = co_limbs(ModT::one);                                          // Z = 1
+            acc = co_tom_add_tab(acc, e, false, mj);
+        }
     }
     return acc;
 }
+template <int MODEL>
 __global__ void __launch_bounds__(256) k_tom_commit_co(const uint32_t* __restrict__ tab_g, const uint32_t* __restrict__ tab_h, TomList L, uint32_t count, uint32_t per_group,
                                                        uint32_t slots_per_group, uint32_t kstride, uint32_t bits, uint32_t nwin) {
     __shared__ uint32_t partial[3][64];
@@ -248,8 +258,8 @@ __global__ void __launch_bounds__(256) k_tom_commit_co(const uint32_t* __restric
     words_from_limbs<8>(vw, soa_ld<ModQ, 1>(L.v, slot).l);
     words_from_limbs<8>(rw, soa_ld<ModQ, 1>(L.r, slot).l);
     const uint32_t per = (nwin + 3) / 4;
-    CoTom acc = co_tom_comb_range(co_tom_identity(), tab_g, vw, bits, nwin, part * per, per, mj);
-    acc = co_tom_comb_range(acc, tab_h, rw, bits, nwin, part * per, per, mj);
+    CoTom acc = co_tom_comb_range<MODEL>(co_tom_identity(), tab_g, vw, bits, nwin, part * per, per, mj);   // (0 : 1 : 0 : 1) is the identity of both models
+    acc = co_tom_comb_range<MODEL>(acc, tab_h, rw, bits, nwin, part * per, per, mj);
     if (part) partial[part - 1][lane] = acc.v.v;
     __syncthreads();
     if (part) return;
@@ -257,39 +267,48 @@ __global__ void __launch_bounds__(256) k_tom_commit_co(const uint32_t* __restric
     for (uint32_t k = 0; k < 3; k++) {
         CoTom o;
         o.v.v = partial[k][lane];
-        acc = co_tom_add(acc, o, mj);
+        if constexpr (MODEL == TOM_MODEL_M1) acc = co_tom_m1_add(acc, o, mj);
+        else acc = co_tom_add(acc, o, mj);
     }
+    if constexpr (MODEL == TOM_MODEL_M1) acc = co_tom_m1_to_a1(acc, mj);   // back to the a = 1 image
     co_store_soa(acc.v, slot, L.proj.x, L.proj.y, Soa{nullptr, 0}, L.proj.z);   // rows X, Y, T, Z
 }
 static bool tom_co(const DevParams& P, uint32_t count) { return !tom_signed(P.tom_bits) && (uint64_t)count * 4 <= ZK_COOP_MAX_CHAINS && !zk_one_lane_chains(); }
 static void launch_tom_commit_co(hipStream_t s, const DevParams& P, const TomList& L, uint32_t count, uint32_t per_group, uint32_t slots_per_group, uint32_t kstride) {
     g_coop_chains.fetch_add((uint64_t)count * 4, std::memory_order_relaxed);
-    hipLaunchKernelGGL(k_tom_commit_co, dim3(count), dim3(256), 0, s, P.tom_tab_g, P.tom_tab_h, L, count, per_group, slots_per_group, kstride, P.tom_bits, tom_nwin(P.tom_bits));
+    if (P.tom_model == TOM_MODEL_M1) hipLaunchKernelGGL(k_tom_commit_co<TOM_MODEL_M1>, dim3(count), dim3(256), 0, s, P.tom_tab_g, P.tom_tab_h, L, count, per_group, slots_per_group, kstride, P.tom_bits, tom_nwin(P.tom_bits));
+    else hipLaunchKernelGGL(k_tom_commit_co<TOM_MODEL_A1>, dim3(count), dim3(256), 0, s, P.tom_tab_g, P.tom_tab_h, L, count, per_group, slots_per_group, kstride, P.tom_bits, tom_nwin(P.tom_bits));
 }
 static bool tom_wide(const DevParams& P, uint32_t count) { return !tom_signed(P.tom_bits) && count <= ZK_WIDE_MAX_UNITS; }
-void launch_tom_commit_listb(hipStream_t s, const DevParams& P, const TomList& L, uint32_t items, uint32_t kstride) {
-    if (!items) return;
-    if (tom_co(P, items * LB_COMMITS)) {
-        launch_tom_commit_co(s, P, L, items * LB_COMMITS, items, 0u, kstride);
-        return;
-    }
-    if (tom_wide(P, items * LB_COMMITS)) {   // all 34 slots of every item as independent commitments (the pairs' shared v * g is recomputed: the GPU is idle anyway)
-        hipLaunchKernelGGL(k_tom_commit_wide, dim3((items * LB_COMMITS * 4 + 255) / 256), dim3(256), 0, s, P.tom_tab_g, P.tom_tab_h, L, items * LB_COMMITS, items, 0u, kstride,
+template <int MODEL>
+static void launch_tom_commit_listb_m(hipStream_t s, const DevParams& P, const TomList& L, uint32_t items, uint32_t kstride, bool wide) {
+    if (wide) {   // all 34 slots of every item as independent commitments (the pairs' shared v * g is recomputed: the GPU is idle anyway)
+        hipLaunchKernelGGL(k_tom_commit_wide<MODEL>, dim3((items * LB_COMMITS * 4 + 255) / 256), dim3(256), 0, s, P.tom_tab_g, P.tom_tab_h, L, items * LB_COMMITS, items, 0u, kstride,
                            P.tom_bits, tom_nwin(P.tom_bits));
         return;
     }
     uint32_t nwin = tom_nwin(P.tom_bits);
     uint32_t n1 = items * LB_UNITS_SINGLE, n2 = items * LB_UNITS_PAIR;
     if (tom_signed(P.tom_bits)) {
-        hipLaunchKernelGGL((k_tom_commit<2, true>), dim3((n1 + 255) / 256), dim3(256), 0, s, P.tom_tab_g, P.tom_tab_h, L, n1, items, 0u, kstride, P.tom_bits, nwin, 1u);
-        hipLaunchKernelGGL(k_tom_commit_pairs<true>, dim3((n2 + 255) / 256), dim3(256), 0, s, P.tom_tab_g, P.tom_tab_h, L, items, kstride, P.tom_bits, nwin);
+        hipLaunchKernelGGL((k_tom_commit<2, true, MODEL>), dim3((n1 + 255) / 256), dim3(256), 0, s, P.tom_tab_g, P.tom_tab_h, L, n1, items, 0u, kstride, P.tom_bits, nwin, 1u);
+        hipLaunchKernelGGL((k_tom_commit_pairs<true, MODEL>), dim3((n2 + 255) / 256), dim3(256), 0, s, P.tom_tab_g, P.tom_tab_h, L, items, kstride, P.tom_bits, nwin);
     } else {
-        hipLaunchKernelGGL((k_tom_commit<2, false>), dim3((n1 + 255) / 256), dim3(256), 0, s, P.tom_tab_g, P.tom_tab_h, L, n1, items, 0u, kstride, P.tom_bits, nwin, 1u);
-        hipLaunchKernelGGL(k_tom_commit_pairs<false>, dim3((n2 + 255) / 256), dim3(256), 0, s, P.tom_tab_g, P.tom_tab_h, L, items, kstride, P.tom_bits, nwin);
+        hipLaunchKernelGGL((k_tom_commit<2, false, MODEL>), dim3((n1 + 255) / 256), dim3(256), 0, s, P.tom_tab_g, P.tom_tab_h, L, n1, items, 0u, kstride, P.tom_bits, nwin, 1u);
+        hipLaunchKernelGGL((k_tom_commit_pairs<false, MODEL>), dim3((n2 + 255) / 256), dim3(256), 0, s, P.tom_tab_g, P.tom_tab_h, L, items, kstride, P.tom_bits, nwin);
     }
 }
+void launch_tom_commit_listb(hipStream_t s, const DevParams& P, const TomList& L, uint32_t items, uint32_t kstride) {
+    if (!items) return;
+    if (tom_co(P, items * LB_COMMITS)) {
+        launch_tom_commit_co(s, P, L, items * LB_COMMITS, items, 0u, kstride);
+        return;
+    }
+    const bool wide = tom_wide(P, items * LB_COMMITS);
+    if (P.tom_model == TOM_MODEL_M1) launch_tom_commit_listb_m<TOM_MODEL_M1>(s, P, L, items, kstride, wide);
+    else launch_tom_commit_listb_m<TOM_MODEL_A1>(s, P, L, items, kstride, wide);
+}
 // k_tom_commit over a compacted list of slots (see launch_tom_commit_list): the grid covers the largest possible list, lanes past *count_dev leave at once
-template <bool SGN>
+template <bool SGN, int MODEL>
 __global__ void __launch_bounds__(256, 2) k_tom_commit_list(const uint32_t* __restrict__ tab_g, const uint32_t* __restrict__ tab_h, TomList L, const uint32_t* __restrict__ list,
                                                             const uint32_t* __restrict__ count_dev, uint32_t bits, uint32_t nwin) {
     const uint32_t c = gtid();
@@ -298,15 +317,32 @@ __global__ void __launch_bounds__(256, 2) k_tom_commit_list(const uint32_t* __re
     uint32_t vw[8], rw[8];
     words_from_limbs<8>(vw, soa_ld<ModQ, 1>(L.v, slot).l);
     words_from_limbs<8>(rw, soa_ld<ModQ, 1>(L.r, slot).l);
-    TomPt G = tom_comb_acc<true, false, SGN>(tom_identity(), tab_g, vw, bits, nwin);
-    TomPt A = tom_comb_acc<false, true, SGN>(G, tab_h, rw, bits, nwin);
+    typedef typename TomModel<MODEL>::Pt Pt;
+    Pt G = tom_comb_acc<true, false, SGN, MODEL>(TomModel<MODEL>::identity(), tab_g, vw, bits, nwin);
+    Pt A = tom_comb_acc<false, true, SGN, MODEL>(G, tab_h, rw, bits, nwin);
     soa_st(L.proj.x, slot, A.x), soa_st(L.proj.y, slot, A.y), soa_st(L.proj.z, slot, A.z);
+}
+template <int MODEL>
+static void launch_tom_commit_list_m(hipStream_t s, const DevParams& P, const TomList& L, const uint32_t* list, const uint32_t* count_dev, uint32_t max_count) {
+    dim3 g((max_count + 255) / 256), b(256);
+    if (tom_signed(P.tom_bits)) hipLaunchKernelGGL((k_tom_commit_list<true, MODEL>), g, b, 0, s, P.tom_tab_g, P.tom_tab_h, L, list, count_dev, P.tom_bits, tom_nwin(P.tom_bits));
+    else hipLaunchKernelGGL((k_tom_commit_list<false, MODEL>), g, b, 0, s, P.tom_tab_g, P.tom_tab_h, L, list, count_dev, P.tom_bits, tom_nwin(P.tom_bits));
 }
 void launch_tom_commit_list(hipStream_t s, const DevParams& P, const TomList& L, const uint32_t* list, const uint32_t* count_dev, uint32_t max_count) {
     if (!max_count) return;
-    dim3 g((max_count + 255) / 256), b(256);
-    if (tom_signed(P.tom_bits)) hipLaunchKernelGGL(k_tom_commit_list<true>, g, b, 0, s, P.tom_tab_g, P.tom_tab_h, L, list, count_dev, P.tom_bits, tom_nwin(P.tom_bits));
-    else hipLaunchKernelGGL(k_tom_commit_list<false>, g, b, 0, s, P.tom_tab_g, P.tom_tab_h, L, list, count_dev, P.tom_bits, tom_nwin(P.tom_bits));
+    if (P.tom_model == TOM_MODEL_M1) launch_tom_commit_list_m<TOM_MODEL_M1>(s, P, L, list, count_dev, max_count);
+    else launch_tom_commit_list_m<TOM_MODEL_A1>(s, P, L, list, count_dev, max_count);
+}
+template <int MODEL>
+static void launch_tom_commit_m(hipStream_t s, const DevParams& P, const TomList& L, uint32_t count, uint32_t per_group, uint32_t slots_per_group, uint32_t kstride, bool wide) {
+    if (wide) {
+        hipLaunchKernelGGL(k_tom_commit_wide<MODEL>, dim3((count * 4 + 255) / 256), dim3(256), 0, s, P.tom_tab_g, P.tom_tab_h, L, count, per_group, slots_per_group, kstride, P.tom_bits,
+                           tom_nwin(P.tom_bits));
+        return;
+    }
+    dim3 g((count + 255) / 256), b(256);
+    if (tom_signed(P.tom_bits)) hipLaunchKernelGGL((k_tom_commit<2, true, MODEL>), g, b, 0, s, P.tom_tab_g, P.tom_tab_h, L, count, per_group, slots_per_group, kstride, P.tom_bits, tom_nwin(P.tom_bits), 0u);
+    else hipLaunchKernelGGL((k_tom_commit<2, false, MODEL>), g, b, 0, s, P.tom_tab_g, P.tom_tab_h, L, count, per_group, slots_per_group, kstride, P.tom_bits, tom_nwin(P.tom_bits), 0u);
 }
 void launch_tom_commit(hipStream_t s, const DevParams& P, const TomList& L, uint32_t count, uint32_t per_group, uint32_t slots_per_group, uint32_t kstride) {
     if (!count) return;
@@ -314,14 +350,26 @@ void launch_tom_commit(hipStream_t s, const DevParams& P, const TomList& L, uint
         launch_tom_commit_co(s, P, L, count, per_group, slots_per_group, kstride);
         return;
     }
-    if (tom_wide(P, count)) {
-        hipLaunchKernelGGL(k_tom_commit_wide, dim3((count * 4 + 255) / 256), dim3(256), 0, s, P.tom_tab_g, P.tom_tab_h, L, count, per_group, slots_per_group, kstride, P.tom_bits,
-                           tom_nwin(P.tom_bits));
-        return;
-    }
-    dim3 g((count + 255) / 256), b(256);
-    if (tom_signed(P.tom_bits)) hipLaunchKernelGGL((k_tom_commit<2, true>), g, b, 0, s, P.tom_tab_g, P.tom_tab_h, L, count, per_group, slots_per_group, kstride, P.tom_bits, tom_nwin(P.tom_bits), 0u);
-    else hipLaunchKernelGGL((k_tom_commit<2, false>), g, b, 0, s, P.tom_tab_g, P.tom_tab_h, L, count, per_group, slots_per_group, kstride, P.tom_bits, tom_nwin(P.tom_bits), 0u);
+    const bool wide = tom_wide(P, count);
+    if (P.tom_model == TOM_MODEL_M1) launch_tom_commit_m<TOM_MODEL_M1>(s, P, L, count, per_group, slots_per_group, kstride, wide);
+    else launch_tom_commit_m<TOM_MODEL_A1>(s, P, L, count, per_group, slots_per_group, kstride, wide);
+}
+// Unit-test hook (zk_test_tom_commit_shape): the commitments of a plain list (slot = index) through ONE kernel shape whatever the size of the launch.
+// shape 1: one lane (k_tom_commit);  2: the list is list B of count / 34 items, slot = k * items + item (k_tom_commit with lb_singles and k_tom_commit_pairs);
+// 3: four lanes (k_tom_commit_wide);  4: four cooperating waves (k_tom_commit_co);  5: k_tom_commit_list over `list` / `count_dev`.  Shapes 3 and 4 exist for
+// unsigned digits only; false: the shape does not apply.
+bool launch_tom_commit_shape(hipStream_t s, const DevParams& P, const TomList& L, uint32_t count, uint32_t shape, const uint32_t* list, const uint32_t* count_dev) {
+    const bool m1 = P.tom_model == TOM_MODEL_M1;
+    if (!count || shape < 1 || shape > 5 || ((shape == 3 || shape == 4) && tom_signed(P.tom_bits)) || (shape == 2 && count % LB_COMMITS)) return false;
+    if (shape == 1 || shape == 3) {
+        if (m1) launch_tom_commit_m<TOM_MODEL_M1>(s, P, L, count, 1, 1, 0, shape == 3);
+        else launch_tom_commit_m<TOM_MODEL_A1>(s, P, L, count, 1, 1, 0, shape == 3);
+    } else if (shape == 2) {
+        if (m1) launch_tom_commit_listb_m<TOM_MODEL_M1>(s, P, L, count / LB_COMMITS, count / LB_COMMITS, false);
+        else launch_tom_commit_listb_m<TOM_MODEL_A1>(s, P, L, count / LB_COMMITS, count / LB_COMMITS, false);
+    } else if (shape == 4) launch_tom_commit_co(s, P, L, count, 1, 1, 0);
+    else launch_tom_commit_list(s, P, L, list, count_dev, count);
+    return true;
 }
 
 // Batch normalisation: (X:Y:Z) on the a=1 image -> affine (x, y) of the ORIGINAL curve, plain canonical limbs
