@@ -44,6 +44,16 @@ export function verifySignatureLists(params: SystemParametersList, msgHashes: Ui
 /** B statements over several rings in one call, proved: keyLists[i] is the ring of proof i and whichs[i] indexes it (zk_prove_batch_rings).  The rings stay resident
  *  through the cache verifySignatureLists uses; a call is split only when it names more rings than residentRings. */
 export function proveSignatureLists(params: SystemParametersList, msgHashes: Uint8Array[], sigs: Uint8Array[], publicKeys: PublicKey[], whichs: number[], keyLists: (bigint[] | Buffer)[]): Promise<SignatureProofList[]>
+/** the witness screen (zk_screen_batch_rings): before a proof is paid for, where the signer's key stands in `keys` (`which` absent: the lowest index is found; given: that
+ *  index is checked) and whether the ECDSA signature verifies.  flags is a set of SCREEN bits; ok = (flags === 0) means proveSignatureList with `which` gives a proof that
+ *  verifies.  SCREEN.SIG_RANGE (r or s outside [1, n - 1]) is stricter than the prover, which reduces them mod n. */
+export interface ScreenStatement { msgHash: Uint8Array; sigBytes: Uint8Array; publicKey: PublicKey; keys: bigint[] | Buffer; which?: number }
+export interface ScreenVerdict { which: number; flags: number; ok: boolean }
+export const SCREEN: { readonly KEY_NOT_ON_CURVE: 1; readonly SIG_RANGE: 2; readonly SIG_INVALID: 4; readonly NOT_IN_RING: 8; readonly RING_NOT_RESIDENT: 16 }
+export const WHICH_NONE: number
+export function screenSignatureLists(params: SystemParametersList, statements: ScreenStatement[]): Promise<ScreenVerdict[]>
+/** the lookup alone: the lowest index of the key's x-coordinate among keys, or -1; params default to those the facade used last */
+export function findKey(publicKey: PublicKey, keys: bigint[] | Buffer, params?: SystemParametersList): Promise<number>
 type Newable<T> = new (...args: any[]) => T
 export function writeJson<T>(type: Newable<T>, object: T): string
 export function readJson<T>(type: Newable<T>, text: string): T

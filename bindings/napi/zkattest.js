@@ -382,6 +382,12 @@ class Engine {
         const [B, w, s] = this._proveArgs(msg, which, seeds)
         return native.proveBatchRingsAsync(this.h, msg, sig, pk, w, Buffer.from(Uint32Array.from(ringIds).buffer), s).then((r) => unpackProofs(r, B))
     }
+    // zk_screen_batch_rings: is each witness worth a proof?  which: indices to check, or null to find them; -> { which: number[] (WHICH_NONE where absent), flags: number[] (SCREEN_* bits) }
+    screenBatchRings(msg, sig, pk, which, ringIds) {
+        const r = native.screenBatchRings(this.h, msg, sig, pk, which ? Buffer.from(Uint32Array.from(which).buffer) : null, Buffer.from(Uint32Array.from(ringIds).buffer))
+        const u32 = (b) => Array.from({ length: b.length / 4 }, (_, i) => b.readUInt32LE(4 * i))
+        return { which: u32(r.which), flags: u32(r.flags) }
+    }
     proveBatchRingsAsync(msg, sig, pk, which, ringIds, seeds) { return this._chain(() => this._proveRingsNow(msg, sig, pk, which, ringIds, seeds)) }
     verifyBatchRingsAsync(msg, proofs, ringIds, seeds) { return this._chain(() => this._verifyRingsNow(msg, proofs, ringIds, seeds)) }
     proveBatchAsync(msg, sig, pk, which, seeds) { return this._chain(() => this._proveNow(msg, sig, pk, which, seeds)) }
@@ -429,6 +435,7 @@ function engineFor(params, keys) {
         Object.defineProperty(params, '_tag0', { value: tag })
         Object.defineProperty(params, '_ep', { value: ep })
     }
+    lastParams = params
     const key = params._tag0 + (params.hardened ? '|hardened' : '')
     let slot = engines.get(key)
     if (!slot) {
@@ -679,6 +686,49 @@ async function verifySignatureLists(params, msgHashes, keyLists, proofs) {
     return out
 }
 
-module.exports = { verifySignatureLists, proveSignatureLists, _ringGenerations, setVerifyLevel, getVerifyLevel, generateParamsList, generateParamsListHardened, keyToInt, proveSignatureList, verifySignatureList, proveSignatureListBatch, verifySignatureListBatch,
+// The witness screen (include/zkattest.h: zk_screen_batch_rings) behind the facade: before paying for proofs, ask for each statement { msgHash, sigBytes, publicKey,
+// keys, which? } where the signer's key stands in `keys` and whether the ECDSA signature verifies.  `which` given: that index is checked; absent: the lowest index of
+// the key among `keys` is found (WHICH_NONE when it is not there).  -> [{ which, flags, ok }] in the order given; flags is a set of SCREEN bits and ok = (flags === 0)
+// means that proveSignatureList with that `which` gives a proof that verifies.  SCREEN.SIG_RANGE is stricter than the prover, which reduces r and s mod n
+// (src/zkpAttestList.ts:119-127).  An unusable public key is flagged, not thrown.  Uses the engine and the resident rings of the prove / verify calls.
+const SCREEN = Object.freeze({ KEY_NOT_ON_CURVE: 1, SIG_RANGE: 2, SIG_INVALID: 4, NOT_IN_RING: 8, RING_NOT_RESIDENT: 16 })
+const WHICH_NONE = 0xFFFFFFFF
+async function screenSignatureLists(params, statements) {
+    const B = statements.length
+    if (!B) return []
+    const raws = await Promise.all(statements.map((s) => rawPublicKey(s.publicKey)))
+    for (const r of raws) if (r.length !== 65 || r[0] !== 4) throw new Error('invalid public key')
+    const check = statements[0].which !== undefined && statements[0].which !== null
+    if (statements.some((s) => (s.which !== undefined && s.which !== null) !== check)) throw new RangeError('screenSignatureLists: `which` in every statement or in none')
+    const rings = [], ringOfSt = new Array(B), byTag = new Map()
+    statements.forEach((s, i) => {
+        checkRingSize(Buffer.isBuffer(s.keys) ? s.keys.length / 32 : s.keys.length, true)
+        const r = ringOf(s.keys)
+        if (!byTag.has(r.tag)) { byTag.set(r.tag, rings.length); rings.push(r) }
+        ringOfSt[i] = byTag.get(r.tag)
+    })
+    const { withRings, capacity } = engineFor(params, statements[0].keys)
+    const out = new Array(B), per = capacity()
+    for (let g = 0; g < rings.length; g += per) {   // groups of at most residentRings rings: one group unless the call names more
+        const sel = []
+        for (let i = 0; i < B; i++) if (ringOfSt[i] >= g && ringOfSt[i] < g + per) sel.push(i)
+        const cat = (f) => Buffer.concat(sel.map(f))
+        const r = await withRings(rings.slice(g, g + per), (engine, ids) =>
+            engine.screenBatchRings(cat((i) => Buffer.from(statements[i].msgHash)), cat((i) => Buffer.from(statements[i].sigBytes)), cat((i) => raws[i].slice(1)),
+                check ? sel.map((i) => statements[i].which) : null, sel.map((i) => ids[ringOfSt[i] - g])))
+        sel.forEach((i, k) => { out[i] = { which: r.which[k], flags: r.flags[k], ok: r.flags[k] === 0 } })
+    }
+    return out
+}
+// the lookup alone: the lowest index of publicKey's x-coordinate among keys, or -1 (the engine compares integers: a key off the curve is looked up like any
+// other).  The ring lives on the engine of a SystemParametersList: `params`, or by default the one the facade used last.
+let lastParams = null
+async function findKey(publicKey, keys, params = lastParams) {
+    if (!params) throw new Error('findKey: no params given and none used yet')
+    const r = (await screenSignatureLists(params, [{ msgHash: Buffer.alloc(32), sigBytes: Buffer.alloc(64), publicKey, keys }]))[0]
+    return r.flags & SCREEN.NOT_IN_RING ? -1 : r.which
+}
+
+module.exports = { screenSignatureLists, findKey, SCREEN, WHICH_NONE, verifySignatureLists, proveSignatureLists, _ringGenerations, setVerifyLevel, getVerifyLevel, generateParamsList, generateParamsListHardened, keyToInt, proveSignatureList, verifySignatureList, proveSignatureListBatch, verifySignatureListBatch,
     writeJson, readJson, writeJsonBatch, readJsonBatch, SignatureProofList, SystemParametersList, PedersenParams, generatePedersenParams, p256, tomEdwards256, ALL_GROUPS,
     Group, Point, Scalar, Engine, shutdown, setWireLayout, getWireLayout, setOption, native }

@@ -1008,6 +1008,36 @@ static napi_value json_batch(napi_env env, napi_callback_info info, int to) {
 static napi_value ProofsToJsonBatch(napi_env env, napi_callback_info info) { return json_batch(env, info, 1); }
 static napi_value ProofsFromJsonBatch(napi_env env, napi_callback_info info) { return json_batch(env, info, 0); }
 
+/* (h, msg, sig, pk, which: B u32 LE or null, ringIds: B u32 LE) -> {which: B u32 LE, flags: B u32 LE}: zk_screen_batch_rings on the pool's first context (the
+ * screen has no pool form: it costs a few dozen point additions per witness and reads the resident rings, which every shard holds under the same ids) */
+static napi_value ScreenBatchRings(napi_env env, napi_callback_info info) {
+    napi_value argv[6];
+    if (!get_args(env, info, 6, argv)) return NULL;
+    Handle *h = get_handle(env, argv[0], 0);
+    uint8_t *msg, *sig, *pk, *wb, *ib;
+    size_t lm, ls, lp, lw, li;
+    if (!h || !get_bytes(env, argv[1], &msg, &lm) || !get_bytes(env, argv[2], &sig, &ls) || !get_bytes(env, argv[3], &pk, &lp) || !get_bytes(env, argv[4], &wb, &lw) ||
+        !get_bytes(env, argv[5], &ib, &li))
+        return NULL;
+    const size_t B = lm / 32;
+    if (lm % 32 || ls != 64 * B || lp != 64 * B || (wb && lw != 4 * B) || li != 4 * B) {
+        napi_throw_range_error(env, NULL, "screenBatchRings: 32 bytes of hash, 64 of signature, 64 of key and one ring id per witness (and one index each, or null)");
+        return NULL;
+    }
+    /* (a Buffer's bytes need not be 4-byte aligned) */
+    uint32_t *buf = (uint32_t *)xmalloc(env, 16 * B);
+    if (!buf) return NULL;
+    uint32_t *which = buf, *ids = buf + B, *wo = buf + 2 * B, *fl = buf + 3 * B;
+    if (wb) memcpy(which, wb, 4 * B);
+    if (B) memcpy(ids, ib, 4 * B);
+    zk_status st = zk_screen_batch_rings(zk_pool_ctx(h->pool, 0), B, msg, sig, pk, wb ? which : NULL, ids, wo, fl);
+    napi_value v = NULL;
+    if (st != ZK_OK) throw_text(env, st, zk_last_error(zk_pool_ctx(h->pool, 0)));
+    else if (napi_create_object(env, &v) == napi_ok) set_prop(env, v, "which", new_buffer(env, wo, 4 * B)), set_prop(env, v, "flags", new_buffer(env, fl, 4 * B));
+    free(buf);
+    return v;
+}
+
 static napi_value Init(napi_env env, napi_value exports) {
     static const struct {
         const char *name;
@@ -1021,7 +1051,8 @@ static napi_value Init(napi_env env, napi_value exports) {
                {"proveSubmit", ProveSubmit},     {"verifySubmit", VerifySubmit},
                {"addRing", AddRing},             {"useRing", UseRing},               {"dropRing", DropRing},           {"updateRing", UpdateRing},       {"ringInfo", RingInfo},
                {"verifyBatchRings", VerifyBatchRings}, {"verifyBatchRingsAsync", VerifyBatchRingsAsync},
-               {"proveBatchRings", ProveBatchRings},   {"proveBatchRingsAsync", ProveBatchRingsAsync}};
+               {"proveBatchRings", ProveBatchRings},   {"proveBatchRingsAsync", ProveBatchRingsAsync},
+               {"screenBatchRings", ScreenBatchRings}};
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;
         if (napi_create_function(env, fns[i].name, NAPI_AUTO_LENGTH, fns[i].fn, NULL, &f) != napi_ok) return NULL;

@@ -352,6 +352,56 @@ zk_status zk_prove_batch_rings_device(zk_ctx *ctx, uint64_t B, const void *d_msg
                                       const void *d_ring_ids /*u32[B]*/, const zk_rng *rng_device, void *d_out, uint64_t out_cap,
                                       void *d_out_off /*u64[B+1]*/, void *d_per_proof_status /*i32[B]*/);
 
+/* Witness screen: is a witness worth a proof?  The reference's prover starts with "a signature verification to recover R" (src/zkpAttestList.ts:124-131)
+ * but never compares R.x with r, takes `which` from the caller (zkpAttestList.ts:110) and finds out last whether keys[which] is the signer's key
+ * (proveMembership, src/proofGK/gk.ts:94-195); zk_prove_batch does the same, so a wrong signature, a wrong message, -pk for pk or a key that is not at
+ * `which` all return status 0 and a proof that zk_verify_batch rejects.  zk_screen_batch answers both questions for B witnesses at the cost of a few dozen
+ * point additions each, against the ring's resident limbs: which_out[b] is the signer's index, flags[b] a set of ZK_SCREEN_* bits, and flags[b] == 0 means
+ * that zk_prove_batch with which_out[b] gives a proof that verifies.
+ *   ZK_SCREEN_KEY_NOT_ON_CURVE   pk fails the prover's own key check: deserializePoint's rule (src/curves/weier.ts:74-89: the curve equation mod p, coordinates
+ *                                reduced and not range-checked), the condition of the prover's ZK_E_POINT_NOT_IN_GROUP.
+ *   ZK_SCREEN_SIG_RANGE          r or s is outside [1, n - 1] as a 256-bit integer (FIPS 186-5 section 6.4.2).  DELIBERATELY STRICTER THAN THE PROVER, which reduces
+ *                                r and s mod n (zkpAttestList.ts:119-127) and proves for r + n as it does for r: such a witness is flagged although its proof verifies.
+ *   ZK_SCREEN_SIG_INVALID        evaluated only when the two bits above are clear: R = (z / s) G + (r / s) pk is the identity or R.x mod n != r, with
+ *                                z = truncateToN(msg_hash) (zkpAttestList.ts:80-86) -- exactly where ECDSA verification of the in-range signature fails.
+ *   ZK_SCREEN_NOT_IN_RING        the lookup failed (below); evaluated whatever the other bits, it compares integers.
+ *   ZK_SCREEN_RING_NOT_RESIDENT  (_rings forms) ring_ids[b] is not resident: no other bit is evaluated and which_out[b] = ZK_WHICH_NONE.
+ * Lookup, with x = pk.x mod p, the value keyToInt (zkpAttestList.ts:94-102) / zk_keys_to_ints puts into a ring:
+ *   which == NULL (find): which_out[b] = the LOWEST i in [0, n_keys) with ring[i] == x -- never one of the padding copies of keys[0] at [n_keys, N) --, or
+ *                         ZK_WHICH_NONE and ZK_SCREEN_NOT_IN_RING when there is none;
+ *   which != NULL (check): which_out[b] = which[b]; ZK_SCREEN_NOT_IN_RING iff which[b] >= N or ring[which[b]] != x (padded indices are legal, as for the prover).
+ * The lookup reads the limbs zk_ctx_set_ring / add_ring / update_ring keep resident and stores nothing per ring, so a screen issued after zk_ctx_update_ring
+ * sees the updated ring.  The plain forms work on the active ring, the _rings forms take one resident ring id per witness like zk_prove_batch_rings and neither
+ * read nor change the active ring.  The _device forms take every pointer in this context's HBM; which_out (u32[B]) can be handed to zk_prove_batch_device /
+ * zk_prove_batch_rings_device as d_which as it is (replace ZK_WHICH_NONE first, or skip those witnesses: the prover answers it with ZK_E_ARG).
+ * The call changes no prover or verifier state and may be issued between prove calls; it works in chunks of 16 384 witnesses on one scratch buffer of about
+ * 23 MB whatever B is, and does not need the prover's workspaces.  The scratch holds u1 = z / s and u2 = r / s: witness-derived, so zk_ctx_wipe,
+ * zk_ctx_destroy and a failed screen call zero it.  zk_last_timing afterwards reports the call's two phases, "screen_lookup" and "screen_ecdsa" (under the
+ * rules of zk_ctx_set_timing).  ZK_E_BUFFER before zk_ctx_set_params (the comb of G is built there) and, for the plain forms, without an active ring;
+ * ZK_E_ARG for NULL pointers other than `which` and while streamed jobs are queued; B = 0 is ZK_OK.
+ * How: find mode runs blocks of 256 witnesses against tiles of the ring's lowest limb in LDS, compares at full width where that limb matches and keeps the
+ * lowest index; the ECDSA part is one lane per witness -- one inversion (of s), u1 G by the comb of G (13 additions), u2 pk through the key's table where the
+ * looked-up entry has one (33 additions; zk_ctx_set_key_tables) and by the prover's 65-window walk otherwise, and the comparison X == r Z, X == (r + n) Z
+ * without a field inversion.  A _rings call makes one pass per resident ring.
+ * Not provided: a cooperative form for calls of a few witnesses (the one-lane kernels serve B = 1), streamed (submit / wait) variants, zk_pool_* variants. */
+#define ZK_WHICH_NONE 0xFFFFFFFFu
+enum {
+    ZK_SCREEN_KEY_NOT_ON_CURVE = 1,
+    ZK_SCREEN_SIG_RANGE = 2,
+    ZK_SCREEN_SIG_INVALID = 4,
+    ZK_SCREEN_NOT_IN_RING = 8,
+    ZK_SCREEN_RING_NOT_RESIDENT = 16
+};
+zk_status zk_screen_batch(zk_ctx *ctx, uint64_t B, const uint8_t *msg_hash /*Bx32*/, const uint8_t *sig /*Bx64*/, const uint8_t *pk_xy /*Bx64*/,
+                          const uint32_t *which /*B or NULL*/, uint32_t *which_out /*B*/, uint32_t *flags /*B*/);
+zk_status zk_screen_batch_device(zk_ctx *ctx, uint64_t B, const void *d_msg_hash, const void *d_sig, const void *d_pk_xy, const void *d_which /*u32[B] or NULL*/,
+                                 void *d_which_out /*u32[B]*/, void *d_flags /*u32[B]*/);
+zk_status zk_screen_batch_rings(zk_ctx *ctx, uint64_t B, const uint8_t *msg_hash /*Bx32*/, const uint8_t *sig /*Bx64*/, const uint8_t *pk_xy /*Bx64*/,
+                                const uint32_t *which /*B or NULL*/, const uint32_t *ring_ids /*B*/, uint32_t *which_out /*B*/, uint32_t *flags /*B*/);
+zk_status zk_screen_batch_rings_device(zk_ctx *ctx, uint64_t B, const void *d_msg_hash, const void *d_sig, const void *d_pk_xy,
+                                       const void *d_which /*u32[B] or NULL*/, const void *d_ring_ids /*u32[B]*/, void *d_which_out /*u32[B]*/,
+                                       void *d_flags /*u32[B]*/);
+
 /* ---- two (or more) batches in flight on one context.  zk_prove_batch / zk_verify_batch are synchronous: each call pays its own head
  * (no byte of a chunk exists before its stage 1 is over) and its own tail (the copies of the last slices, with nothing left to
  * hide them).  The submit / wait pair splits a call so that the pipeline keeps running ACROSS calls: submit stages the inputs and

@@ -26,6 +26,7 @@ SYMBOLS = [
     'zk_pool_add_ring', 'zk_pool_use_ring', 'zk_pool_drop_ring', 'zk_pool_verify_batch_rings',
     'zk_ctx_update_ring', 'zk_pool_update_ring',
     'zk_prove_batch_rings', 'zk_prove_batch_rings_device', 'zk_pool_prove_batch_rings', 'zk_ring_proof_max_size',
+    'zk_screen_batch', 'zk_screen_batch_device', 'zk_screen_batch_rings', 'zk_screen_batch_rings_device',
     'zk_test_field_op', 'zk_test_tom_commit', 'zk_test_p256_fixed_mul', 'zk_test_sha256', 'zk_test_rng_draws',
 ]
 
@@ -122,6 +123,10 @@ def lib():
         L.zk_prove_batch_rings_device.argtypes = [vp, u64, vp, vp, vp, vp, vp, C.POINTER(ZkRng), vp, u64, vp, vp]
         L.zk_pool_prove_batch_rings.argtypes = [vp, u64, C.c_char_p, C.c_char_p, C.c_char_p, vp, vp, C.POINTER(ZkRng), vp, u64, vp, vp, vp]
         L.zk_ring_proof_max_size.argtypes = [vp, u32]
+        L.zk_screen_batch.argtypes = [vp, u64, C.c_char_p, C.c_char_p, C.c_char_p, vp, vp, vp]
+        L.zk_screen_batch_device.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp]
+        L.zk_screen_batch_rings.argtypes = [vp, u64, C.c_char_p, C.c_char_p, C.c_char_p, vp, vp, vp, vp]
+        L.zk_screen_batch_rings_device.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp, vp]
         L.zk_ring_proof_max_size.restype = u64
         L.zk_ring_digest.argtypes = [vp, vp]
         L.zk_hardened_h.argtypes = [C.c_char_p, u64, vp, vp]
@@ -218,6 +223,9 @@ class ZkError(RuntimeError):
 
 MODE_REFERENCE, MODE_HARDENED = 0, 1
 RING_TABLE_E, RING_DIGIT_PLANES, RING_TABLE_E_DIGITS, RING_KEY_TABLES, RING_ACTIVE = 1, 2, 4, 8, 16   # zk_ring_info flags
+# zk_screen_batch: the bits of flags[b] (0 = prove this witness) and the index of a key that is not in the ring
+SCREEN_KEY_NOT_ON_CURVE, SCREEN_SIG_RANGE, SCREEN_SIG_INVALID, SCREEN_NOT_IN_RING, SCREEN_RING_NOT_RESIDENT = 1, 2, 4, 8, 16
+WHICH_NONE = 0xFFFFFFFF
 
 
 def hardened_h(tag=b''):
@@ -555,6 +563,32 @@ class Engine:
         """zk_prove_batch_rings_device: every pointer a device address"""
         rng = ZkRng(mode, d_seeds, stride_blocks)
         self._chk(self.L.zk_prove_batch_rings_device(self.h, B, d_msg, d_sig, d_pk, d_which, d_ring_ids, C.byref(rng), d_out, out_cap, d_off, d_status))
+
+    def screen_batch(self, msg, sig, pk, which=None, ring_ids=None):
+        """zk_screen_batch / zk_screen_batch_rings: is each witness worth a proof?  Returns (which_out list, flags list): flags[b] is a set of SCREEN_*
+        bits, 0 = the signature verifies and the key is in the ring at which_out[b].  which=None finds the lowest index of pk.x among the ring's keys
+        (WHICH_NONE and SCREEN_NOT_IN_RING when absent), a list is checked entry by entry.  ring_ids: one resident ring id per witness instead of the
+        active ring.  SCREEN_SIG_RANGE is stricter than the prover, which reduces r and s mod n."""
+        B = len(bytes(msg)) // 32
+        if len(sig) != 64 * B or len(pk) != 64 * B or (which is not None and len(which) != B) or (ring_ids is not None and len(ring_ids) != B):
+            raise ValueError('32 bytes of hash, 64 of signature and 64 of key per witness, one index and one ring id each where given')
+        w = (C.c_uint32 * max(B, 1))(*which) if which is not None else None
+        wo = (C.c_uint32 * max(B, 1))()
+        fl = (C.c_uint32 * max(B, 1))()
+        if ring_ids is None:
+            self._chk(self.L.zk_screen_batch(self.h, B, bytes(msg), bytes(sig), bytes(pk), w, wo, fl))
+        else:
+            ids = (C.c_uint32 * max(B, 1))(*ring_ids)
+            self._chk(self.L.zk_screen_batch_rings(self.h, B, bytes(msg), bytes(sig), bytes(pk), w, ids, wo, fl))
+        return list(wo)[:B], list(fl)[:B]
+
+    def screen_batch_device(self, B, d_msg, d_sig, d_pk, d_which, d_which_out, d_flags, d_ring_ids=None):
+        """zk_screen_batch_device / zk_screen_batch_rings_device: every pointer a device address (d_which may be None: find mode); d_which_out is what
+        prove_batch_device takes as d_which"""
+        if d_ring_ids is None:
+            self._chk(self.L.zk_screen_batch_device(self.h, B, d_msg, d_sig, d_pk, d_which, d_which_out, d_flags))
+        else:
+            self._chk(self.L.zk_screen_batch_rings_device(self.h, B, d_msg, d_sig, d_pk, d_which, d_ring_ids, d_which_out, d_flags))
 
     def test_set_prove_segment(self, proofs):
         """test build only (lib/libzkattest_hip_testhooks.so through ZKATTEST_LIB): proofs per segment of the mixed-ring prove calls; 0 = the default"""

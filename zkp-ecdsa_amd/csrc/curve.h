@@ -216,6 +216,21 @@ ZK_DEV bool p256_on_curve(const P256Aff& a) {
     return fe_eq(y2, rhs);
 }
 
+// ECDSA's last step without a field inversion: is x(R) mod n == r for R = (X : Y : Z) and a canonical r in [1, n)?  x = X / Z lies in [0, p) and
+// n < p < 2 n, so x mod n == r exactly when x == r or -- only where r + n < p, the wrap case R.x in [n, p) -- x == r + n: X == r Z or X == (r + n) Z mod p.
+// The identity (Z == 0) has no x-coordinate: false.  Device and host (tests/host_arith/host_screen.cpp).
+ZK_DEV bool p256_x_is_r_mod_n(const P256Pt& R, const Fe<ModN, 1>& r) {
+    Fe<ModQ, 1> r0;
+    Fe<ModQ, 2> r1;   // r + n as a plain integer < 2 n < 2^257
+#pragma unroll
+    for (int i = 0; i < NLIMB; i++) r0.l[i] = r.l[i], r1.l[i] = r.l[i] + ModN::mod[i];
+    limbs_normalize(r1.l);
+    const bool wrap = !limbs_geq_mod<ModQ>(r1.l);   // r + n < p
+    const Fq2 z = fe_reduce(R.z);
+    const bool eq0 = fe_eq(R.x, fe_to_mont(r0) * z), eq1 = fe_eq(R.x, fe_to_mont(r1) * z);
+    return !fe_is_zero(z) && (eq0 || (wrap && eq1));
+}
+
 // ---------------------------------------------------------------- Tom-256 on the a = 1 image
 struct TomPt {  // extended (X:Y:T:Z), Montgomery
     Ft2 x, y, t, z;

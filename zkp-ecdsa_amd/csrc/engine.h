@@ -376,6 +376,31 @@ struct ChunkIn {
     uint32_t count;   // proofs in this chunk
 };
 
+// witness screen (k_screen.hip; include/zkattest.h: zk_screen_batch): a chunk of witnesses (device pointers, already offset to the chunk's first one), the
+// view of one resident ring, and the per-witness scratch area the three ECDSA kernels hand their values on in
+#define SCR_AREA_WORDS 312   // nine rtab.h entries (1..8 times pk, u1 * G), u2's digits, u1, u2, pk, the key table's address, the path
+#define SCR_TILE 2048        // ring keys per LDS tile of the lookup
+struct ScreenIn {
+    const uint8_t* msg;
+    const uint8_t* sig;
+    const uint8_t* pk;
+    const uint32_t* which;   // nullptr: find mode
+    const uint32_t* ids;     // nullptr: every witness is on the one ring of the call
+    uint32_t* which_out;
+    uint32_t* flags;
+    uint32_t count;
+};
+struct ScreenRing {
+    Soa ring;                // [N] plain canonical limbs
+    uint32_t N, nkeys, id;
+    const uint32_t* ktab;    // per-key tables or nullptr
+    const uint8_t* ktab_ok;
+};
+void launch_screen_init(hipStream_t s, const ScreenIn& in, uint32_t* scratch);
+void launch_screen_lookup(hipStream_t s, const ScreenRing& G, const ScreenIn& in);   // find mode only: the lowest matching index of ring G's witnesses
+void launch_screen_front(hipStream_t s, const ScreenRing& G, const ScreenIn& in, uint32_t* scratch);
+void launch_screen_ecdsa(hipStream_t s, const DevParams& P, const ScreenIn& in, uint32_t* scratch);
+
 // buffers of the batched Tom-256 check (k_msm.hip), one set per verifier lane
 struct MsmBuf {
     uint32_t cap;          // term ids

@@ -10,32 +10,8 @@
 #include "rtab.h"   // engine.h (and with it ktab.h), the projective table entries of rtab.h
 #include "coop_dev.h"   // the table sums of a call of a few proofs on cooperating waves (k_front_co, k_exp_commit_kt_co)
 
-// k * B for a fixed base with a PFIX_WIN_BITS-bit comb table; k given as 8 little-endian words (clobbered)
-ZK_DEV P256Pt p256_fixed_mul(const uint32_t* __restrict__ tab, uint32_t kw[8]) {
-    P256Pt acc;
-    {   // first window: identity + entry = the entry
-        uint32_t d = kw[0] & (PFIX_WIN_SIZE - 1);
-        shr256<PFIX_WIN_BITS>(kw);
-        acc = p256_select(d != 0, p256_from_affine(ld_pfix(tab + (size_t)PFIX_ENTRY_WORDS * d)), p256_identity());
-    }
-#pragma unroll 1
-    for (int w = 1; w < PFIX_NWIN; w++) {
-        uint32_t d = kw[0] & (PFIX_WIN_SIZE - 1);
-        shr256<PFIX_WIN_BITS>(kw);
-        ZK_ADD_IF(d != 0, acc, p256_add_mixed(acc, ld_pfix(tab + (size_t)PFIX_ENTRY_WORDS * (w * PFIX_WIN_SIZE + (d ? d : 1)))));   // a zero digit (2^-20) idles its lane (rtab.h: ZK_UNIFORM_CF)
-    }
-    return acc;
-}
-// acc + k * B: the comb's additions go straight onto a running point (one complete addition less than summing two results)
-ZK_DEV P256Pt p256_fixed_mul_acc(P256Pt acc, const uint32_t* __restrict__ tab, uint32_t kw[8]) {
-#pragma unroll 1
-    for (int w = 0; w < PFIX_NWIN; w++) {
-        uint32_t d = kw[0] & (PFIX_WIN_SIZE - 1);
-        shr256<PFIX_WIN_BITS>(kw);
-        ZK_ADD_IF(d != 0, acc, p256_add_mixed(acc, ld_pfix(tab + (size_t)PFIX_ENTRY_WORDS * (w * PFIX_WIN_SIZE + (d ? d : 1)))));   // a zero digit (2^-20) idles its lane (rtab.h: ZK_UNIFORM_CF)
-    }
-    return acc;
-}
+// (k * B through a fixed base's comb -- p256_fixed_mul, p256_fixed_mul_acc -- and the pieces of the front end's walk live in rtab.h: the witness
+// screen, k_screen.hip, takes them too)
 ZK_DEV void st_proj(const Soa3& a, uint32_t e, const P256Pt& p) {
     soa_st(a.x, e, p.x), soa_st(a.y, e, p.y), soa_st(a.z, e, p.z);
 }
@@ -53,7 +29,6 @@ ZK_DEV P256Pt ld_proj(const Soa3& a, uint32_t e) {
 //                    bit-serial ladder), R = u1*G + u2*pk, R affine
 // Between the kernels the values live in the proof's R-table area, which k_rtab_* only writes afterwards: entries 0..7 = d * pk,
 // entry 8 = u1*G, words of entry 9: u2's digits (65 bytes), entry 10: u1, z1.
-#define FRONT_NW 65   // signed 4-bit digits of a 256-bit scalar
 ZK_DEV uint32_t* front_area(const Workspace& W, uint32_t p) { return W.rtab + (size_t)p * rtab_words(RTAB_PROVE_BITS); }
 static_assert(FRONT_NW <= 4 * RTAB_ENTRY_WORDS && 2 * NLIMB <= RTAB_ENTRY_WORDS, "front-end scratch inside R-table entries");
 __global__ void __launch_bounds__(64, 2) k_front(DevParams P, Workspace W, ChunkIn in) {
@@ -110,17 +85,9 @@ __global__ void __launch_bounds__(64, 2) k_front(DevParams P, Workspace W, Chunk
     uint32_t* area = front_area(W, p);
     {
         uint8_t* dig = (uint8_t*)(area + 9 * RTAB_ENTRY_WORDS);
-        uint32_t u2w[8], carry = 0;
+        uint32_t u2w[8];
         words_from_limbs<8>(u2w, u2.l);
-#pragma unroll 1
-        for (uint32_t w = 0; w < FRONT_NW; w++) {
-            uint32_t d = (u2w[0] & 15) + carry;
-            shr256<4>(u2w);
-            bool neg = d > 8;
-            carry = neg ? 1 : 0;
-            if (neg) d = 16 - d;
-            dig[w] = (uint8_t)(d | (neg ? 0x80u : 0u));
-        }
+        front_recode(u2w, dig);
         uint32_t* sc = area + 10 * RTAB_ENTRY_WORDS;
 #pragma unroll
         for (int l = 0; l < NLIMB; l++) sc[l] = u1.l[l], sc[NLIMB + l] = z1.l[l];
@@ -170,15 +137,7 @@ __global__ void __launch_bounds__(64, 2) k_front_table(DevParams P, Workspace W,
     if (!W.kt_use[p]) {
         P256Aff pk;
         pk.x = soa_ld<ModQ, 2>(W.pkxm, p), pk.y = soa_ld<ModQ, 2>(W.pkym, p);
-        P256Pt base = p256_from_affine(pk), m = base;
-        st_rtab(area, m);
-        m = p256_dbl(base);
-        st_rtab(area + RTAB_ENTRY_WORDS, m);
-#pragma unroll 1
-        for (uint32_t d = 2; d < 8; d++) {
-            m = p256_add(m, base);
-            st_rtab(area + d * RTAB_ENTRY_WORDS, m);
-        }
+        front_pk_multiples(area, pk);
     }
     const uint32_t* sc = area + 10 * RTAB_ENTRY_WORDS;
     Fe<ModN, 1> u1, z1;
@@ -203,17 +162,7 @@ __global__ void __launch_bounds__(64, 2) k_front_walk(Workspace W, uint32_t coun
         words_from_limbs<8>(kw, fe_from_mont(soa_ld<ModN, 1>(W.u2m, p).as<2>()).l);
         R = p256_ktab_mul_acc(ld_rtab(area + 8 * RTAB_ENTRY_WORDS), W.ktab + (size_t)W.kt_key[p] * KTAB_KEY_WORDS, kw, use == 2);
     } else {
-        P256Pt acc = p256_identity();
-#pragma unroll 1
-        for (int w = FRONT_NW - 1; w >= 0; w--) {
-#pragma unroll 1
-            for (int i = 0; i < 4; i++) acc = p256_dbl(acc);
-            uint32_t db = dig[w], d = db & 15;
-            P256Pt e = ld_rtab(area + (d ? d - 1 : 0) * RTAB_ENTRY_WORDS);
-            e.y = fe_select((db & 0x80u) != 0, fq8_neg(e.y), e.y);
-            P256Pt s = p256_add(acc, e);
-            acc = p256_select(d != 0, s, acc);
-        }
+        const P256Pt acc = front_walk(area, dig);
         R = p256_add(ld_rtab(area + 8 * RTAB_ENTRY_WORDS), acc);
     }
     // R affine (output + base of the per-proof table).  R = identity makes every T_i the identity: exp.ts:151.

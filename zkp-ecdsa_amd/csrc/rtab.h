@@ -114,6 +114,72 @@ ZK_DEV P256Aff ld_pfix(const uint32_t* e) {
     for (int l = 0; l < 9; l++) a.x.l[l] = w[l], a.y.l[l] = w[9 + l];
     return a;
 }
+// k * B for a fixed base with a PFIX_WIN_BITS-bit comb table; k given as 8 little-endian words (clobbered)
+ZK_DEV P256Pt p256_fixed_mul(const uint32_t* __restrict__ tab, uint32_t kw[8]) {
+    P256Pt acc;
+    {   // first window: identity + entry = the entry
+        uint32_t d = kw[0] & (PFIX_WIN_SIZE - 1);
+        shr256<PFIX_WIN_BITS>(kw);
+        acc = p256_select(d != 0, p256_from_affine(ld_pfix(tab + (size_t)PFIX_ENTRY_WORDS * d)), p256_identity());
+    }
+#pragma unroll 1
+    for (int w = 1; w < PFIX_NWIN; w++) {
+        uint32_t d = kw[0] & (PFIX_WIN_SIZE - 1);
+        shr256<PFIX_WIN_BITS>(kw);
+        ZK_ADD_IF(d != 0, acc, p256_add_mixed(acc, ld_pfix(tab + (size_t)PFIX_ENTRY_WORDS * (w * PFIX_WIN_SIZE + (d ? d : 1)))));   // a zero digit (2^-20) idles its lane (rtab.h: ZK_UNIFORM_CF)
+    }
+    return acc;
+}
+// acc + k * B: the comb's additions go straight onto a running point (one complete addition less than summing two results)
+ZK_DEV P256Pt p256_fixed_mul_acc(P256Pt acc, const uint32_t* __restrict__ tab, uint32_t kw[8]) {
+#pragma unroll 1
+    for (int w = 0; w < PFIX_NWIN; w++) {
+        uint32_t d = kw[0] & (PFIX_WIN_SIZE - 1);
+        shr256<PFIX_WIN_BITS>(kw);
+        ZK_ADD_IF(d != 0, acc, p256_add_mixed(acc, ld_pfix(tab + (size_t)PFIX_ENTRY_WORDS * (w * PFIX_WIN_SIZE + (d ? d : 1)))));   // a zero digit (2^-20) idles its lane (rtab.h: ZK_UNIFORM_CF)
+    }
+    return acc;
+}
+// ---- k * P for a point without a table of its own, as the ECDSA front ends take u2 * pk (k_p256.hip: k_front*; k_screen.hip): signed 4-bit digits, the
+// multiples 1..8 of P in the first eight entries of a scratch area (rtab.h entry format), 65 windows of four doublings and one addition
+#define FRONT_NW 65   // signed 4-bit digits of a 256-bit scalar
+ZK_DEV void front_recode(uint32_t kw[8] /*clobbered*/, uint8_t* dig /*[FRONT_NW]: |d| in 0..8, bit 7 = negative*/) {
+    uint32_t carry = 0;
+#pragma unroll 1
+    for (uint32_t w = 0; w < FRONT_NW; w++) {
+        uint32_t d = (kw[0] & 15) + carry;
+        shr256<4>(kw);
+        bool neg = d > 8;
+        carry = neg ? 1 : 0;
+        if (neg) d = 16 - d;
+        dig[w] = (uint8_t)(d | (neg ? 0x80u : 0u));
+    }
+}
+ZK_DEV void front_pk_multiples(uint32_t* area, const P256Aff& pk) {
+    P256Pt base = p256_from_affine(pk), m = base;
+    st_rtab(area, m);
+    m = p256_dbl(base);
+    st_rtab(area + RTAB_ENTRY_WORDS, m);
+#pragma unroll 1
+    for (uint32_t d = 2; d < 8; d++) {
+        m = p256_add(m, base);
+        st_rtab(area + d * RTAB_ENTRY_WORDS, m);
+    }
+}
+ZK_DEV P256Pt front_walk(const uint32_t* area, const uint8_t* dig) {
+    P256Pt acc = p256_identity();
+#pragma unroll 1
+    for (int w = FRONT_NW - 1; w >= 0; w--) {
+#pragma unroll 1
+        for (int i = 0; i < 4; i++) acc = p256_dbl(acc);
+        uint32_t db = dig[w], d = db & 15;
+        P256Pt e = ld_rtab(area + (d ? d - 1 : 0) * RTAB_ENTRY_WORDS);
+        e.y = fe_select((db & 0x80u) != 0, fq8_neg(e.y), e.y);
+        P256Pt s = p256_add(acc, e);
+        acc = p256_select(d != 0, s, acc);
+    }
+    return acc;
+}
 // acc + (the comb's windows [w0, w0 + per) of k) * B: one lane's share when four lanes split a fixed-base multiplication (k_p256.hip: k_exp_commit_kt_wide, k_front_wide; k_verify.hip: k_v_p256_total_wide)
 ZK_DEV P256Pt p256_fixed_mul_range(P256Pt acc, const uint32_t* __restrict__ tab, uint32_t kw[8], uint32_t w0, uint32_t per) {
 #pragma unroll 1
