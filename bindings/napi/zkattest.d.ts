@@ -54,6 +54,22 @@ export const WHICH_NONE: number
 export function screenSignatureLists(params: SystemParametersList, statements: ScreenStatement[]): Promise<ScreenVerdict[]>
 /** the lookup alone: the lowest index of the key's x-coordinate among keys, or -1; params default to those the facade used last */
 export function findKey(publicKey: PublicKey, keys: bigint[] | Buffer, params?: SystemParametersList): Promise<number>
+/** ring membership of a committed value on its own (src/proofGK/gk.ts:94-262): ZKM1 proofs over the engine's resident rings */
+export class Commitment { p: Point; r: Scalar; constructor(p: Point, r: Scalar) }
+export class GKProof {
+    readonly bytes: Buffer; readonly n: number
+    readonly cl: Point[]; readonly ca: Point[]; readonly cb: Point[]; readonly cd: Point[]
+    readonly f: Scalar[]; readonly za: Scalar[]; readonly zb: Scalar[]; readonly zd: Scalar
+    constructor(bytes: Buffer); eq(o: GKProof): boolean
+}
+/** pedersen.ts:53-58: value * g + r * h with a fresh blinder r */
+export function commit(params: PedersenParams, value: bigint): Commitment
+/** com.r is the blinder; throws unless com.p commits to keys[index] under it */
+export function proveMembership(params: PedersenParams | SystemParametersList, com: Commitment, index: number, keys: bigint[] | Buffer): Promise<GKProof>
+export function verifyMembership(params: PedersenParams | SystemParametersList, com: Point, keys: bigint[] | Buffer, proof: GKProof): Promise<boolean>
+/** batched over one key list */
+export function proveMemberships(params: PedersenParams | SystemParametersList, coms: Commitment[], indices: number[], keys: bigint[] | Buffer): Promise<GKProof[]>
+export function verifyMemberships(params: PedersenParams | SystemParametersList, coms: Point[], keys: bigint[] | Buffer, proofs: GKProof[]): Promise<boolean[]>
 type Newable<T> = new (...args: any[]) => T
 export function writeJson<T>(type: Newable<T>, object: T): string
 export function readJson<T>(type: Newable<T>, text: string): T

@@ -388,6 +388,18 @@ class Engine {
         const u32 = (b) => Array.from({ length: b.length / 4 }, (_, i) => b.readUInt32LE(4 * i))
         return { which: u32(r.which), flags: u32(r.flags) }
     }
+    // ring membership on its own (zk_member_*), on the ACTIVE ring: -> { proofs: Buffer[] | null per entry, coms: Buffer[] (72 B), blinders: Buffer[] (32 B), status: Int32Array }
+    memberProofSize() { return native.memberProofSize(this.h) }
+    memberProveBatch(which, blinders, seeds) {
+        const B = which.length, size = this.memberProofSize()
+        const r = native.memberProveBatch(this.h, Buffer.from(Uint32Array.from(which).buffer), blinders || null, seeds || crypto.randomBytes(32 * B))   // one fresh seed per proof
+        const st = i32(r.status), cut = (b, w) => Array.from({ length: B }, (_, i) => b.slice(w * i, w * i + w))
+        return { proofs: cut(r.proofs, size).map((p, i) => (st[i] === 0 ? p : null)), coms: cut(r.coms, 72), blinders: cut(r.blinders, 32), status: st }
+    }
+    memberVerifyBatch(coms, proofs) {   // -> { ok: boolean[], status: Int32Array }
+        const r = native.memberVerifyBatch(this.h, Buffer.concat(coms), Buffer.concat(proofs))
+        return { ok: Array.from(r.ok, (v) => v === 1), status: i32(r.status) }
+    }
     proveBatchRingsAsync(msg, sig, pk, which, ringIds, seeds) { return this._chain(() => this._proveRingsNow(msg, sig, pk, which, ringIds, seeds)) }
     verifyBatchRingsAsync(msg, proofs, ringIds, seeds) { return this._chain(() => this._verifyRingsNow(msg, proofs, ringIds, seeds)) }
     proveBatchAsync(msg, sig, pk, which, seeds) { return this._chain(() => this._proveNow(msg, sig, pk, which, seeds)) }
@@ -729,6 +741,80 @@ async function findKey(publicKey, keys, params = lastParams) {
     return r.flags & SCREEN.NOT_IN_RING ? -1 : r.which
 }
 
-module.exports = { screenSignatureLists, findKey, SCREEN, WHICH_NONE, verifySignatureLists, proveSignatureLists, _ringGenerations, setVerifyLevel, getVerifyLevel, generateParamsList, generateParamsListHardened, keyToInt, proveSignatureList, verifySignatureList, proveSignatureListBatch, verifySignatureListBatch,
+// ---------------------------------------------------------------- ring membership on its own (src/proofGK/gk.ts:31-262, src/commit/pedersen.ts:21-58)
+class Commitment { // src/commit/pedersen.ts:21-36: the point and its blinder
+    constructor(p, r) { this.p = p; this.r = r }
+}
+// A GKProof keeps the engine's ZKM1 bytes (include/zkattest.h) and materialises the reference's members (cl, ca, cb, cd: Points; f, za, zb: Scalars; zd) on demand.
+class GKProof { // src/proofGK/gk.ts:31-73
+    constructor(bytes) {
+        if (!(Buffer.isBuffer(bytes) && bytes.length >= 16 && bytes.slice(0, 4).toString('latin1') === 'ZKM1' && bytes.readUInt32BE(4) === bytes.length &&
+            bytes.length === 16 + 384 * bytes.readUInt32BE(8) + 32)) throw new Error('error deserializing GKProof')
+        this.bytes = bytes
+    }
+    get n() { return this.bytes.readUInt32BE(8) }
+    _pts(k) { const n = this.n; return Array.from({ length: n }, (_, i) => { const o = 16 + 72 * (k * n + i); return new Point(tomEdwards256, fromBE(this.bytes.slice(o, o + 36)), fromBE(this.bytes.slice(o + 36, o + 72))) }) }
+    _scs(k) { const n = this.n; return Array.from({ length: n }, (_, i) => { const o = 16 + 288 * n + 32 * (k * n + i); return new Scalar(tomEdwards256, fromBE(this.bytes.slice(o, o + 32))) }) }
+    get cl() { return this._pts(0) }
+    get ca() { return this._pts(1) }
+    get cb() { return this._pts(2) }
+    get cd() { return this._pts(3) }
+    get f() { return this._scs(0) }
+    get za() { return this._scs(1) }
+    get zb() { return this._scs(2) }
+    get zd() { const o = this.bytes.length - 32; return new Scalar(tomEdwards256, fromBE(this.bytes.slice(o))) }
+    eq(o) { return o instanceof GKProof && this.bytes.equals(o.bytes) }
+}
+// pedersen.ts:53-58 -- commit(value): a fresh blinder from crypto.getRandomValues (a one-time host call, like generateParamsList)
+function commit(pedersenParams, value) {
+    const c = pedersenParams.c, r = c.randomScalar(), v = new Scalar(c, value)
+    return new Commitment(pedersenParams.h.mul(r).add(pedersenParams.g.mul(v)), r)
+}
+// The engine holds whole parameter sets: a bare Tom-256 PedersenParams rides in a SystemParametersList whose P-256 half plays no part in these calls.
+const memberParams = new WeakMap()
+function paramsOf(pedersenParams) {
+    if (pedersenParams instanceof SystemParametersList) return pedersenParams
+    if (!(pedersenParams instanceof PedersenParams) || !pedersenParams.c.eq(tomEdwards256)) throw new TypeError('params: PedersenParams on tomEdwards256')
+    let sp = memberParams.get(pedersenParams)
+    if (!sp) {
+        sp = new SystemParametersList(new PedersenParams(p256, p256.generator(), p256.generator()), pedersenParams, 80)
+        memberParams.set(pedersenParams, sp)
+    }
+    return sp
+}
+const tomBytes = (pt) => Buffer.concat([toBE(pt.x, 36), toBE(pt.y, 36)])
+// proveMembership(params, com, index, keys) (gk.ts:94-195): com.r is the blinder; the engine's commitment to keys[index] under it must be com.p
+async function proveMembership(pedersenParams, com, index, keys) { return (await proveMemberships(pedersenParams, [com], [index], keys))[0] }
+// verifyMembership(params, comPoint, keys, proof) (gk.ts:197-262) -> boolean; what does not deserialise throws
+async function verifyMembership(pedersenParams, comPoint, keys, proof) { return (await verifyMemberships(pedersenParams, [comPoint], keys, [proof]))[0] }
+// batched: one ring, B commitments and indices -> GKProof[]
+async function proveMemberships(pedersenParams, coms, indices, keys) {
+    if (coms.length !== indices.length) throw new RangeError('proveMemberships: one index per commitment')
+    checkRingSize(Buffer.isBuffer(keys) ? keys.length / 32 : keys.length, true)
+    if (!coms.length) return []
+    const { withRing } = engineFor(paramsOf(pedersenParams), keys)
+    const r = await withRing((engine) => engine.memberProveBatch(indices, Buffer.concat(coms.map((c) => toBE(c.r.k, 32)))))
+    return r.proofs.map((p, i) => {
+        if (r.status[i] !== 0) throw statusError(r.status[i])
+        if (!r.coms[i].equals(tomBytes(coms[i].p))) throw new Error('proveMembership: com does not commit to keys[index] with blinder com.r')
+        return new GKProof(p)
+    })
+}
+async function verifyMemberships(pedersenParams, comPoints, keys, proofs) {
+    if (comPoints.length !== proofs.length) throw new RangeError('verifyMemberships: one proof per commitment')
+    checkRingSize(Buffer.isBuffer(keys) ? keys.length / 32 : keys.length, false)
+    if (!proofs.length) return []
+    const { withRing } = engineFor(paramsOf(pedersenParams), keys)
+    return withRing((engine) => {
+        const size = engine.memberProofSize()
+        // a GKProof of another ring's length: the reference's length check returns false (gk.ts:208-218); the engine sees fixed-size slots
+        const fit = proofs.map((p) => { const b = p.bytes; return b.length === size ? b : b.length > size ? b.slice(0, size) : Buffer.concat([b, Buffer.alloc(size - b.length)]) })
+        const r = engine.memberVerifyBatch(comPoints.map(tomBytes), fit)
+        r.status.forEach((st) => { if (st !== 0) throw statusError(st) })
+        return r.ok
+    })
+}
+
+module.exports = { proveMembership, verifyMembership, proveMemberships, verifyMemberships, GKProof, Commitment, commit, screenSignatureLists, findKey, SCREEN, WHICH_NONE, verifySignatureLists, proveSignatureLists, _ringGenerations, setVerifyLevel, getVerifyLevel, generateParamsList, generateParamsListHardened, keyToInt, proveSignatureList, verifySignatureList, proveSignatureListBatch, verifySignatureListBatch,
     writeJson, readJson, writeJsonBatch, readJsonBatch, SignatureProofList, SystemParametersList, PedersenParams, generatePedersenParams, p256, tomEdwards256, ALL_GROUPS,
     Group, Point, Scalar, Engine, shutdown, setWireLayout, getWireLayout, setOption, native }

@@ -1038,6 +1038,76 @@ static napi_value ScreenBatchRings(napi_env env, napi_callback_info info) {
     return v;
 }
 
+/* Ring membership on its own (include/zkattest.h: zk_member_*), on the pool's first context like the screen (no pool form); the active ring is the facade's.
+ * (h) -> bytes of one ZKM1 proof over the active ring */
+static napi_value MemberProofSize(napi_env env, napi_callback_info info) {
+    napi_value argv[1], v = NULL;
+    if (!get_args(env, info, 1, argv)) return NULL;
+    Handle *h = get_handle(env, argv[0], 0);
+    if (!h) return NULL;
+    napi_create_double(env, (double)zk_member_proof_size(zk_pool_ctx(h->pool, 0)), &v);
+    return v;
+}
+/* (h, which: B u32 LE, blinders: B x 32 or null, seeds: B x 32) -> {proofs: B x size (zeros where status != 0), coms: B x 72, blinders: B x 32, status: B i32 LE} */
+static napi_value MemberProveBatch(napi_env env, napi_callback_info info) {
+    napi_value argv[4];
+    if (!get_args(env, info, 4, argv)) return NULL;
+    Handle *h = get_handle(env, argv[0], 0);
+    uint8_t *wb, *bl, *seeds;
+    size_t lw, lb, ls;
+    if (!h || !get_bytes(env, argv[1], &wb, &lw) || !get_bytes(env, argv[2], &bl, &lb) || !get_bytes(env, argv[3], &seeds, &ls)) return NULL;
+    const size_t B = lw / 4;
+    if (lw % 4 || (bl && lb != 32 * B) || ls != 32 * B) {
+        napi_throw_range_error(env, NULL, "memberProveBatch: one u32 index and 32 seed bytes per proof (and 32 blinder bytes each, or null)");
+        return NULL;
+    }
+    zk_ctx *c = zk_pool_ctx(h->pool, 0);
+    const uint64_t size = zk_member_proof_size(c);
+    uint8_t *buf = (uint8_t *)xmalloc(env, (size + 72 + 32 + 8) * B + 8);   /* (a Buffer's bytes need not be 4-byte aligned: the indices are copied) */
+    if (!buf) return NULL;
+    uint32_t *which = (uint32_t *)buf;
+    int32_t *status = (int32_t *)(buf + 4 * B);
+    uint8_t *out = buf + 8 * B, *com = out + size * B, *bo = com + 72 * B;
+    if (B) memcpy(which, wb, 4 * B);
+    zk_rng rng = {ZK_RNG_SEED, seeds, 0};
+    zk_status st = zk_member_prove_batch(c, B, which, bl, &rng, com, bo, out, size * B, status);
+    napi_value v = NULL;
+    if (st != ZK_OK) throw_text(env, st, zk_last_error(c));
+    else if (napi_create_object(env, &v) == napi_ok) {
+        set_prop(env, v, "proofs", new_buffer(env, out, size * B)), set_prop(env, v, "coms", new_buffer(env, com, 72 * B));
+        set_prop(env, v, "blinders", new_buffer(env, bo, 32 * B)), set_prop(env, v, "status", new_buffer(env, status, 4 * B));
+    }
+    memset(buf, 0, (size + 72 + 32 + 8) * B + 8);   /* the blinders */
+    free(buf);
+    return v;
+}
+/* (h, coms: B x 72, proofs: B x size) -> {ok: B bytes, status: B i32 LE} */
+static napi_value MemberVerifyBatch(napi_env env, napi_callback_info info) {
+    napi_value argv[3];
+    if (!get_args(env, info, 3, argv)) return NULL;
+    Handle *h = get_handle(env, argv[0], 0);
+    uint8_t *com, *proofs;
+    size_t lc, lp;
+    if (!h || !get_bytes(env, argv[1], &com, &lc) || !get_bytes(env, argv[2], &proofs, &lp)) return NULL;
+    zk_ctx *c = zk_pool_ctx(h->pool, 0);
+    const uint64_t size = zk_member_proof_size(c);
+    const size_t B = lc / 72;
+    if (lc % 72 || !size || lp != size * B) {
+        napi_throw_range_error(env, NULL, "memberVerifyBatch: one 72-byte commitment and one proof of the active ring's size per entry");
+        return NULL;
+    }
+    uint8_t *buf = (uint8_t *)xmalloc(env, 5 * B + 8);
+    if (!buf) return NULL;
+    int32_t *status = (int32_t *)buf;
+    uint8_t *ok = buf + 4 * B;
+    zk_status st = zk_member_verify_batch(c, B, com, proofs, NULL, ok, status);
+    napi_value v = NULL;
+    if (st != ZK_OK) throw_text(env, st, zk_last_error(c));
+    else if (napi_create_object(env, &v) == napi_ok) set_prop(env, v, "ok", new_buffer(env, ok, B)), set_prop(env, v, "status", new_buffer(env, status, 4 * B));
+    free(buf);
+    return v;
+}
+
 static napi_value Init(napi_env env, napi_value exports) {
     static const struct {
         const char *name;
@@ -1052,7 +1122,8 @@ static napi_value Init(napi_env env, napi_value exports) {
                {"addRing", AddRing},             {"useRing", UseRing},               {"dropRing", DropRing},           {"updateRing", UpdateRing},       {"ringInfo", RingInfo},
                {"verifyBatchRings", VerifyBatchRings}, {"verifyBatchRingsAsync", VerifyBatchRingsAsync},
                {"proveBatchRings", ProveBatchRings},   {"proveBatchRingsAsync", ProveBatchRingsAsync},
-               {"screenBatchRings", ScreenBatchRings}};
+               {"screenBatchRings", ScreenBatchRings},
+               {"memberProofSize", MemberProofSize},   {"memberProveBatch", MemberProveBatch}, {"memberVerifyBatch", MemberVerifyBatch}};
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;
         if (napi_create_function(env, fns[i].name, NAPI_AUTO_LENGTH, fns[i].fn, NULL, &f) != napi_ok) return NULL;

@@ -25,6 +25,11 @@
  *        MultProof: C_4, A_x, A_y, A_z, A_4_1, A_4_2 (T), t_x, t_y, t_z, t_rx, t_ry, t_rz, t_r4   (src/commit/mult.ts:26-52)
  *        EqualityProof: A_1, A_2 (T), t_x, t_r1, t_r2                                              (src/commit/equality.ts:27-40)
  *     GKProof: cl[n], ca[n], cb[n], cd[n] (T), f[n], za[n], zb[n], zd                              (src/proofGK/gk.ts:31-58)
+ *   membership proof on its own  "ZKM1" layout, the binary equivalent of a bare GKProof (src/proofGK/gk.ts:31-58; zk_member_* below):
+ *     header 16 B : "ZKM1" | total_len u32 | n = log2(padded ring) u32 | 0 u32
+ *     GKProof: cl[n], ca[n], cb[n], cd[n] (T), f[n], za[n], zb[n], zd      -- byte for byte the GKProof section of a ZKA1 proof
+ *     total_len = 16 + 288 n + 32 (3 n + 1): fixed per ring (6 192 B at n = 16).  Always 36-byte coordinates (zk_ctx_set_wire plays no part).  The commitment
+ *     the proof is about is not part of it: it travels beside the proof as one Tom-256 point.
  *
  * Randomness contract (replaces crypto.getRandomValues in src/bignum/big.ts:171-181): the k-th 32-byte fill
  * of proof b is SHA-256(seed_b || be64(k)) (ZK_RNG_SEED) or block k of a caller-supplied stream
@@ -401,6 +406,41 @@ zk_status zk_screen_batch_rings(zk_ctx *ctx, uint64_t B, const uint8_t *msg_hash
 zk_status zk_screen_batch_rings_device(zk_ctx *ctx, uint64_t B, const void *d_msg_hash, const void *d_sig, const void *d_pk_xy,
                                        const void *d_which /*u32[B] or NULL*/, const void *d_ring_ids /*u32[B]*/, void *d_which_out /*u32[B]*/,
                                        void *d_flags /*u32[B]*/);
+
+/* ---- ring membership of a committed value on its own.  Replaces B calls of proveMembership(params, com, index, values) /
+ * verifyMembership(params, com, values, proof) (src/proofGK/gk.ts:94-262, with com = params.commit(values[index]), src/commit/pedersen.ts:53-58): a proof
+ * that a Pedersen commitment on Tom-256 opens to one entry of the ACTIVE ring, without revealing which -- the one-of-many part of a ZKAttest proof without
+ * its 80 cut-and-choose repetitions (4 n commitments and one ring fold per proof).  Proofs are "ZKM1" (byte formats above): proof b of a batch lies at
+ * b * zk_member_proof_size(ctx).
+ * Prover: the committed value is entry which[b] of the padded ring (padding indices allowed, as in zk_prove_batch); which[b] >= N gives per-proof ZK_E_ARG.
+ * Randomness, per proof: with blinder_be32 == NULL fill 0 is commit()'s randomScalar and the 5 n draws of proveMembership follow in the reference's order
+ * (r_i, a_i, s_i, t_i, rho_i for i = 0 .. n-1), every draw mod q with the contract's rejection sampling; the blinder comes back in blinder_out if that is
+ * given.  With a caller's blinders (B x 32 bytes, reduced mod q as newScalar does) the 5 n draws start at fill 0.  com_xy72[b] = v g + r h is always
+ * written; out[b * size ..] is the proof, or zeros where per_proof_status[b] != 0 (ZK_E_ARG, ZK_E_RNG_EXHAUSTED; ZK_E_INTERPOLATION cannot occur, as in
+ * the full prover).  out_cap < B * size: ZK_E_BUFFER.
+ * Verifier, per proof and in this order: ZK_E_BAD_ENCODING for a wrong magic, a total_len that is not the one the header's n announces (or, where n is the
+ * ring's, not the slot's size), a nonzero reserved word, n > 63, com or a point of the announced structure off its curve or non-canonical (exactly what
+ * zk_verify_batch checks on the same bytes inside ZKA1; of a structure longer than its slot, the points that lie inside the slot -- no byte outside a slot
+ * is read); ok = 0 with status 0 where the header's n is not the ring's (the reference's length check returns false) or the summed relations are not the
+ * identity; otherwise ok = 1.  verifier_seeds follow zk_verify_batch's contract (2 n + 1 fills per proof; the engine draws its own 128-bit randomisers
+ * from the same seed); NULL: fresh OS randomness.
+ * Both run in chunks (zk_ctx_set_chunk) on the context's lanes, on workspaces of their own sized for what a membership proof holds; the ring fold, the
+ * commitments, the challenge hash and the verifier's sums are the kernels of the full proof, so zk_ctx_set_ring_fold, zk_ctx_set_comb_bits and the uniform
+ * build apply, and the bytes depend on none of them.  Blinders, nonces and RNG fills are wiped as the prover's are (zk_ctx_wipe, zk_ctx_destroy, a failed
+ * call).  zk_last_timing reports the families "rng_prepass", "gk_fold", "tom_commit", "tom_normalize", "hash", "respond_write" (prover) and
+ * "v_parse_validate", "v_gk_total", "v_sums" (verifier).  ZK_E_BUFFER before zk_ctx_set_params or without an active ring; ZK_E_ARG for NULL pointers
+ * (other than the optional ones), while streamed jobs are queued, and in ZK_MODE_HARDENED (there is no statement to bind).  B = 0 is ZK_OK.
+ * Not provided: _rings forms, submit / wait forms, zk_pool_* forms, JSON, a packed layout. */
+uint64_t zk_member_proof_size(const zk_ctx *ctx);   /* active ring; 0 without one */
+zk_status zk_member_prove_batch(zk_ctx *ctx, uint64_t B, const uint32_t *which /*B*/, const uint8_t *blinder_be32 /*Bx32 or NULL*/, const zk_rng *rng,
+                                uint8_t *com_xy72 /*Bx72 out*/, uint8_t *blinder_out /*Bx32 or NULL*/, uint8_t *out, uint64_t out_cap,
+                                int32_t *per_proof_status /*B*/);
+zk_status zk_member_prove_batch_device(zk_ctx *ctx, uint64_t B, const void *d_which, const void *d_blinder_be32, const zk_rng *rng /* rng->data in HBM */,
+                                       void *d_com_xy72, void *d_blinder_out, void *d_out, uint64_t out_cap, void *d_per_proof_status);
+zk_status zk_member_verify_batch(zk_ctx *ctx, uint64_t B, const uint8_t *com_xy72 /*Bx72*/, const uint8_t *proofs /*B x size*/,
+                                 const uint8_t *verifier_seeds /*Bx32 or NULL*/, uint8_t *ok /*B*/, int32_t *per_proof_status /*B*/);
+zk_status zk_member_verify_batch_device(zk_ctx *ctx, uint64_t B, const void *d_com_xy72, const void *d_proofs, const void *d_verifier_seeds, void *d_ok,
+                                        void *d_per_proof_status);
 
 /* ---- two (or more) batches in flight on one context.  zk_prove_batch / zk_verify_batch are synchronous: each call pays its own head
  * (no byte of a chunk exists before its stage 1 is over) and its own tail (the copies of the last slices, with nothing left to

@@ -27,6 +27,7 @@ SYMBOLS = [
     'zk_ctx_update_ring', 'zk_pool_update_ring',
     'zk_prove_batch_rings', 'zk_prove_batch_rings_device', 'zk_pool_prove_batch_rings', 'zk_ring_proof_max_size',
     'zk_screen_batch', 'zk_screen_batch_device', 'zk_screen_batch_rings', 'zk_screen_batch_rings_device',
+    'zk_member_proof_size', 'zk_member_prove_batch', 'zk_member_prove_batch_device', 'zk_member_verify_batch', 'zk_member_verify_batch_device',
     'zk_test_field_op', 'zk_test_tom_commit', 'zk_test_p256_fixed_mul', 'zk_test_sha256', 'zk_test_rng_draws',
 ]
 
@@ -128,6 +129,12 @@ def lib():
         L.zk_screen_batch_rings.argtypes = [vp, u64, C.c_char_p, C.c_char_p, C.c_char_p, vp, vp, vp, vp]
         L.zk_screen_batch_rings_device.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp, vp]
         L.zk_ring_proof_max_size.restype = u64
+        L.zk_member_proof_size.argtypes = [vp]
+        L.zk_member_proof_size.restype = u64
+        L.zk_member_prove_batch.argtypes = [vp, u64, vp, C.c_char_p, C.POINTER(ZkRng), vp, vp, vp, u64, vp]
+        L.zk_member_prove_batch_device.argtypes = [vp, u64, vp, vp, C.POINTER(ZkRng), vp, vp, vp, u64, vp]
+        L.zk_member_verify_batch.argtypes = [vp, u64, C.c_char_p, C.c_char_p, C.c_char_p, vp, vp]
+        L.zk_member_verify_batch_device.argtypes = [vp, u64, vp, vp, vp, vp, vp]
         L.zk_ring_digest.argtypes = [vp, vp]
         L.zk_hardened_h.argtypes = [C.c_char_p, u64, vp, vp]
         L.zk_pool_create.argtypes = [C.POINTER(C.c_int), i32, C.POINTER(vp)]
@@ -693,6 +700,59 @@ class Engine:
 
     def verify_batch_device(self, B, d_msg, d_proofs, d_off, d_vseeds, d_ok, d_status):
         self._chk(self.L.zk_verify_batch_device(self.h, B, d_msg, d_proofs, d_off, d_vseeds, d_ok, d_status))
+
+    # ---- ring membership of a committed value on its own (zk_member_*): proveMembership / verifyMembership on the active ring, "ZKM1" proofs
+    def member_proof_size(self):
+        """bytes of one ZKM1 proof over the active ring: 16 + 288 n + 32 (3 n + 1); 0 without a ring"""
+        return int(self.L.zk_member_proof_size(self.h))
+
+    def member_prove_batch(self, which, blinders=None, seeds=None, streams=None, stream_blocks=0, want_blinders=True):
+        """One membership proof per entry of `which` (indices into the padded active ring).  blinders: B x 32 bytes, the openings' blinders (reduced mod
+        q), or None: the engine draws each from fill 0 of the proof's RNG.  Returns (proofs: list of bytes or None, coms: list of 72-byte Tom-256 points,
+        blinders: list of 32-byte scalars or None, statuses).  seeds: as in prove_batch -- fresh, secret, one per proof."""
+        B = len(which)
+        if seeds is None and streams is None:
+            seeds = os.urandom(32 * B)
+        if streams is None and len(seeds) != 32 * B:
+            raise ValueError('seeds must hold 32 bytes per proof')
+        if blinders is not None and len(blinders) != 32 * B:
+            raise ValueError('blinders must hold 32 bytes per proof')
+        size = self.member_proof_size()
+        out = C.create_string_buffer(max(size * B, 1))
+        com = C.create_string_buffer(max(72 * B, 1))
+        bo = C.create_string_buffer(max(32 * B, 1)) if want_blinders else None
+        st = (C.c_int32 * max(B, 1))()
+        w = (C.c_uint32 * max(B, 1))(*which)
+        if streams is None:
+            data = C.create_string_buffer(bytes(seeds), max(32 * B, 1))
+            rng = ZkRng(0, C.cast(data, C.c_void_p), 0)
+        else:
+            data = C.create_string_buffer(bytes(streams), max(32 * B * stream_blocks, 1))
+            rng = ZkRng(1, C.cast(data, C.c_void_p), stream_blocks)
+        self._chk(self.L.zk_member_prove_batch(self.h, B, w, bytes(blinders) if blinders is not None else None, C.byref(rng), com, bo, out, size * B, st))
+        raw, craw = out.raw, com.raw
+        proofs = [raw[size * b:size * (b + 1)] if st[b] == 0 else None for b in range(B)]
+        self.member_last_raw = raw[:size * B]   # the B slots as written (a slot whose status is not 0 is zero-filled)
+        return (proofs, [craw[72 * b:72 * (b + 1)] for b in range(B)], [bo.raw[32 * b:32 * (b + 1)] for b in range(B)] if want_blinders else None,
+                list(st)[:B])
+
+    def member_prove_batch_device(self, B, d_which, d_blinders, d_rng, d_com, d_blinders_out, d_out, out_cap, d_status, mode=0, stride_blocks=0):
+        rng = ZkRng(mode, d_rng, stride_blocks)
+        self._chk(self.L.zk_member_prove_batch_device(self.h, B, d_which, d_blinders, C.byref(rng), d_com, d_blinders_out, d_out, out_cap, d_status))
+
+    def member_verify_batch(self, coms, proofs, vseeds=None):
+        """verifyMembership for B (com, proof) pairs on the active ring; every proof is member_proof_size() bytes.  Returns (ok list, status list)."""
+        B = len(proofs)
+        size = self.member_proof_size()
+        if len(coms) != B or any(len(p) != size for p in proofs) or any(len(cm) != 72 for cm in coms):
+            raise ValueError('one 72-byte commitment and one proof of member_proof_size() bytes per entry')
+        ok = (C.c_uint8 * max(B, 1))()
+        st = (C.c_int32 * max(B, 1))()
+        self._chk(self.L.zk_member_verify_batch(self.h, B, b''.join(coms), b''.join(proofs), bytes(vseeds) if vseeds is not None else None, ok, st))
+        return list(ok)[:B], list(st)[:B]
+
+    def member_verify_batch_device(self, B, d_com, d_proofs, d_vseeds, d_ok, d_status):
+        self._chk(self.L.zk_member_verify_batch_device(self.h, B, d_com, d_proofs, d_vseeds, d_ok, d_status))
 
     def synth_params(self, seed):
         a, b, c = C.create_string_buffer(64), C.create_string_buffer(72), C.create_string_buffer(72)

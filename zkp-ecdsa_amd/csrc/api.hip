@@ -141,7 +141,7 @@ void stream_abandon_jobs(zk_ctx* c);
 // responses before they are written out) and the staging buffer of the host-pointer calls (signatures, seeds).  Zeroed when the context is destroyed, when a
 // prove call fails, and on request (zk_ctx_wipe); a successful call leaves them as they are -- the next call overwrites them, and wiping 2.5 GB of RNG
 // stream per 22 016-proof chunk would cost ~0.5 ms of every call.  (The reference leaves its BigInts to the garbage collector.)  Nothing may be in flight.
-static void wipe_witness(zk_ctx* c) {
+void wipe_witness(zk_ctx* c) {
     // every stream a prove call puts work on is drained first: a kernel still running on a lane's side stream, or a gather of a mixed-ring call on the
     // main stream, would write witness-derived data behind the memsets
     for (int l = 0; l < ZK_MAX_LANES; l++)
@@ -149,6 +149,8 @@ static void wipe_witness(zk_ctx* c) {
             if (st) (void)hipStreamSynchronize(st);
     for (int l = 0; l < ZK_MAX_LANES; l++)
         if (c->pl[l].arena && c->pl[l].stream) (void)hipMemsetAsync(c->pl[l].arena, 0, c->pl[l].arena_bytes, c->pl[l].stream);
+    for (int l = 0; l < ZK_MAX_LANES; l++)   // membership proofs on their own (api_member.hip): blinders, nonces, RNG fills
+        if (c->ml[l].arena && c->pl[l].stream) (void)hipMemsetAsync(c->ml[l].arena, 0, c->ml[l].arena_bytes, c->pl[l].stream);
     if (c->in_buf && c->stream) (void)hipMemsetAsync(c->in_buf, 0, c->in_bytes, c->stream);
     if (c->pw_buf && c->stream) (void)hipMemsetAsync(c->pw_buf, 0, c->pw_bytes, c->stream);   // mixed-ring prove calls: the gathered signatures, seeds and RNG streams
     if (c->scr_buf && c->stream) (void)hipMemsetAsync(c->scr_buf, 0, c->scr_bytes, c->stream);   // witness screen: u1 = z / s, u2 = r / s, staged signatures
@@ -185,13 +187,13 @@ extern "C" void zk_ctx_destroy(zk_ctx* c) {
     if (c->h_rg) hipHostFree(c->h_rg);
     hipFree(c->io_buf), hipFree(c->in_buf), hipFree(c->unp_buf), hipFree(c->unp_off), hipFree(c->seed_buf), hipFree(c->lv_buf), hipFree(c->lw_buf), hipFree(c->lb_buf);
     if (c->h_lv) hipHostFree(c->h_lv);
-    hipFree(c->pr_buf), hipFree(c->pw_buf), hipFree(c->ps_buf), hipFree(c->scr_buf);
+    hipFree(c->pr_buf), hipFree(c->pw_buf), hipFree(c->ps_buf), hipFree(c->scr_buf), hipFree(c->m_off);
     if (c->h_pr) hipHostFree(c->h_pr);
     if (c->pr_ready) hipEventDestroy(c->pr_ready);
     if (c->h_stage) hipHostFree(c->h_stage);
     if (c->in_ready) hipEventDestroy(c->in_ready);
     for (int l = 0; l < ZK_MAX_LANES; l++) {
-        hipFree(c->pl[l].arena), hipFree(c->pl[l].d_totals), hipFree(c->vl[l].arena);
+        hipFree(c->pl[l].arena), hipFree(c->pl[l].d_totals), hipFree(c->vl[l].arena), hipFree(c->ml[l].arena);
         if (c->pl[l].h_scan) hipHostFree(c->pl[l].h_scan);
         if (c->vl[l].h_msm) hipHostFree(c->vl[l].h_msm);
         if (c->vl[l].aux_fork) hipEventDestroy(c->vl[l].aux_fork);
@@ -749,6 +751,7 @@ static size_t carve(zk_ctx* c, Workspace& W, Soa& gk_am, uint8_t* base, uint32_t
     W.lb = k.list(items_cap * LB_SLOTS);
     const size_t lb_bytes = k.off - lb_off0;
     W.lc = k.list((size_t)C * 4 * n);
+    W.gk_fill0 = 3 + 4 * sec, W.gk_blind = Soa{nullptr, 0};
     W.gk_x = (uint32_t*)k.take(12 * (size_t)C);
     W.gk_coef = k.soa((size_t)(n + 1) * C);
     gk_am = k.soa((size_t)n * C);

@@ -7,6 +7,7 @@ static size_t vcarve(VWork& V, Soa& res, Soa& res2, MsmBuf& M, PMsmBuf& PM, uint
                      uint32_t want_groups) {
     Carver k(base);
     V.C = C, V.sec = sec, V.n = n;
+    V.gk_fixed = ZK_FIXED, V.com = nullptr;
     V.st = (int32_t*)k.take(4 * (size_t)C);
     V.exp_st = (int32_t*)k.take(4 * (size_t)C);
     V.exp_jm = (uint32_t*)k.take(4 * (size_t)C), V.exp_jz = (uint32_t*)k.take(4 * (size_t)C);

@@ -127,6 +127,21 @@ struct zk_ctx {
         bool released_by_host = false;   // ... or the host waits for it in stage2b and launches their kernels then (VerifyJob::host_release)
         bool ready = false;
     } vl[ZK_MAX_LANES];
+    // membership proofs on their own (api_member.hip): a lane holds what a chunk's GK phase needs and nothing of the repetitions -- the prover's view W (list C with
+    // one more slot per proof for com, the fold's buffers, the RNG fills, the blinders) and the verifier's view V (the GK terms and sums).  Lane l runs on pl[l].stream.
+    struct MemberLane {
+        Workspace W{};
+        VWork V{};
+        Soa gk_am{}, res{}, res2{};
+        uint32_t* which_s = nullptr;   // [C] the indices the fold kernels read (0 for one outside the ring)
+        void* arena = nullptr;         // witness-derived (blinders, nonces, the RNG stream): wiped with the prover lanes' (api.hip: wipe_witness)
+        size_t arena_bytes = 0;
+        bool ready = false;
+    } ml[ZK_MAX_LANES];
+    uint32_t ms_C = 0, ms_n = 0;
+    bool ms_etab = false, ms_edig = false;
+    uint64_t* m_off = nullptr;         // offsets of a verify call's equally long proofs (grow-only)
+    size_t m_off_entries = 0;
     uint32_t vs_C = 0, vs_sec = 0, vs_n = 0;
     uint32_t p256_batch_min = 8192;   // chunks of at least this many proofs sum their P-256 relations across proofs too (ZKATTEST_P256_BATCH; 0 = never)
     uint32_t verify_groups = 8;   // groups per chunk of the batched Tom check: 8 (16-bit windows) or 64 (13-bit windows); zk_ctx_set_verify_groups
@@ -258,6 +273,7 @@ struct DevBuf {
     template <class T>
     T* as() const { return (T*)p; }
 };
+void wipe_witness(zk_ctx* c);   // api.hip: zeroes every witness-derived buffer of the context (nothing may be in flight)
 zk_status ensure_workspace(zk_ctx* c, uint32_t C, uint32_t nlanes = 1);   // api.hip: prover workspaces of lanes 0..nlanes-1
 hipError_t malloc_or_shed(zk_ctx* c, void** p, size_t bytes);   // api.hip: a workspace allocation that sheds the optional per-ring tables first
 zk_status ensure_in_buf(zk_ctx* c, size_t bytes);  // api.hip: c->in_buf of at least `bytes`

@@ -147,6 +147,8 @@ struct Workspace {
     uint32_t* padd_c;            // [items_cap][6][3] challenges of pi8, pi10, pi11, pix, pi13, piy
     TomList la, lb, lc;
     // GK
+    uint32_t gk_fill0;           // first draw of the membership proof of a proof without zero-bit repetitions: 3 + 4 sec inside a ZKAttest proof, 0 / 1 on its own
+    Soa gk_blind;                // [C] blinder of the commitment the membership proof is about, plain mod q (k_member.hip); p == nullptr: draw 1, keyXcom's
     uint32_t* gk_x;              // [C][3]
     Soa gk_coef;                 // [(n+1)*C] final polynomial coefficients, index k*C + proof
     uint32_t gk_group;           // proofs per fold pass
@@ -227,6 +229,10 @@ struct VWork {
     uint32_t C, sec, n;
     uint32_t hardened;           // as in Workspace
     const uint32_t* ring_digest;
+    // where a proof's GKProof and the commitment it is about lie: ZK_FIXED bytes, the repetitions, then the GKProof, keyXcom at byte 160 (ZKA1); or 16 header
+    // bytes, then the GKProof, the commitments in an array of their own (ZKM1, k_member.hip: sec = 0, zcnt = 0)
+    uint32_t gk_fixed;
+    const uint8_t* com;   // [B][72] indexed like the proofs, or nullptr: keyXcom inside the proof
     int32_t* st;          // [C] structural status (deserialisation)
     int32_t* exp_st;      // [C] exceptions of verifyExp (k_v_exp_status; k_v_final folds exp_jm in)
     uint32_t* exp_jm;     // [C] first sampled slot whose response type differs from the recomputed challenge bit, VK: none (k_v_sample_check)

@@ -503,7 +503,10 @@ void launch_write_padd_points(hipStream_t s, const Workspace& W, uint32_t items,
 // P is obtained EXACTLY (same coefficients, deg d <= n-1) by folding the ring along the index bits with
 // polynomial-valued entries:  new = w * (l_j ? odd : even) + a_j * (odd - even)   -- (j+1) modmuls per output,
 // 2N in total.  The self-check of interpolate.ts:63-67 holds by construction.
-ZK_DEV uint32_t gk_g0(const Workspace& W, uint32_t p) { return 3 + 4 * W.sec + 40 * W.zcnt[p]; }
+// first draw of the membership proof, and the blinder of the commitment it is about: both come from the workspace (inside a ZKAttest proof 3 + 4 sec and
+// draw 1, keyXcom's; on its own -- k_member.hip -- fill 0 or 1 and the array its front end wrote)
+ZK_DEV uint32_t gk_g0(const Workspace& W, uint32_t p) { return W.gk_fill0 + 40 * W.zcnt[p]; }
+ZK_DEV Sq gk_blinder(const Workspace& W, uint32_t p) { return W.gk_blind.p ? soa_ld<ModQ, 1>(W.gk_blind, p) : drawq(W, p, 1); }
 __global__ void __launch_bounds__(256) k_gk_scalars(Workspace W, ChunkIn in, Soa am) {
     uint32_t t = gtid();
     if (t >= in.count * W.n) return;
@@ -566,7 +569,7 @@ __global__ void __launch_bounds__(64) k_gk_respond(Workspace W, ChunkIn in, uint
     uint8_t* sc = gk + 8 * W.wire.tc * n;
     Sq x = chal_scalar(W.gk_x + 3 * p);
     auto xm = fe_to_mont(x);
-    Sq rcom = drawq(W, p, 1);                                    // blinder of keyXcom
+    Sq rcom = gk_blinder(W, p);                                  // blinder of keyXcom
     Fe<ModQ, 2> xpow = fe_one_mont<ModQ>().as<2>();              // x^i (Montgomery)
     Sq acc = fe_zero<ModQ>();                                    // sum rho_i x^i
     for (uint32_t i = 0; i < n; i++) {

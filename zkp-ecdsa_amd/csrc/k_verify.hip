@@ -62,8 +62,10 @@ ZK_DEV uint64_t v_proof_size(uint32_t sec, uint32_t n, uint32_t z) {
     return (uint64_t)ZK_FIXED + (uint64_t)ZK_REP_HEAD * sec + (uint64_t)ZK_PADD_SZ * z + (uint64_t)n * (4 * 72 + 3 * 32) + 32;
 }
 ZK_DEV const uint8_t* v_gk_base(const VWork& V, const uint8_t* pr, uint32_t p) {
-    return pr + ZK_FIXED + (uint64_t)ZK_REP_HEAD * V.sec + (uint64_t)ZK_PADD_SZ * V.zcnt[p];
+    return pr + V.gk_fixed + (uint64_t)ZK_REP_HEAD * V.sec + (uint64_t)ZK_PADD_SZ * V.zcnt[p];
 }
+// the commitment the membership proof is about: keyXcom of a ZKA1 proof, or entry gp of the array a ZKM1 call brings (engine.h: VWork::com)
+ZK_DEV const uint8_t* v_gk_com(const VWork& V, const uint8_t* pr, uint64_t gp) { return V.com ? V.com + 72 * gp : pr + 160; }
 
 // ------------------------------------------------------------------ header + structural validation
 __global__ void __launch_bounds__(256) k_v_header(VWork V, uint32_t count, const uint8_t* proofs, const uint64_t* off, uint64_t first) {
@@ -1328,7 +1330,7 @@ __global__ void __launch_bounds__(256) k_v_proof_points(VWork V, uint32_t count,
     } else {
         uint32_t u = t - ngl * 8, k = u / count, p = u % count;
         bool good = V.st[p] == ZK_OK && !(V.okflags[p] & 8);
-        if (good && (k == 0 || V.exp_st[p] == ZK_OK)) src = proofs + off[first + p] + (k == 2 ? 232 : 160);
+        if (good && (k == 0 || V.exp_st[p] == ZK_OK)) src = k == 0 ? v_gk_com(V, proofs + off[first + p], first + p) : proofs + off[first + p] + (k == 2 ? 232 : 160);
         idx = k * nm + p;
     }
     Ft2 x, y, dt;

@@ -14,7 +14,7 @@ struct RngCtx {
     const uint8_t* stream;   // mode 1: B x stride x 32
     uint64_t stride_blocks;
     int mode;
-    int sec;                 // secLevel (draw layout)
+    int sec;                 // secLevel (draw layout); negative: every draw is mod q (a membership proof on its own, k_member.hip)
     uint32_t* exc_idx;       // [C][RNG_MAX_EXC] fill indices whose first word is 0xffffffff
     uint32_t* exc_flags;     // bit0: value >= n, bit1: value >= q
     uint32_t* exc_cnt;       // [C]
@@ -42,7 +42,7 @@ ZK_DEV void rng_block(const RngCtx& g, uint32_t proof, uint32_t blk, uint32_t w[
     }
 }
 // modulus of logical draw j inside proveSignatureList: true = n, false = q
-ZK_DEV bool rng_draw_is_n(const RngCtx& g, uint32_t j) { return j == 0 || (j >= 3 && j < 3 + 4 * (uint32_t)g.sec && ((j - 3) & 3) < 2); }
+ZK_DEV bool rng_draw_is_n(const RngCtx& g, uint32_t j) { return g.sec >= 0 && (j == 0 || (j >= 3 && j < 3 + 4 * (uint32_t)g.sec && ((j - 3) & 3) < 2)); }
 
 ZK_DEV uint32_t rng_map(const RngCtx& g, uint32_t proof, uint32_t k) {
     uint32_t cnt = g.exc_cnt[proof];

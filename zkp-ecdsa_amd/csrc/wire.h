@@ -39,6 +39,11 @@ ZK_HD static inline Wire wire_make(bool packed) {
 ZK_HD static inline uint64_t wire_proof_size(const Wire& w, uint32_t sec, uint32_t n, uint32_t z) {
     return (uint64_t)w.fixed + (uint64_t)w.rep_head * sec + (uint64_t)w.padd * z + (uint64_t)w.gk_n * n + 32;
 }
+// "ZKM1" (include/zkattest.h: zk_member_*): a GKProof on its own -- 16 header bytes ("ZKM1" | total_len | n | 0), then the GKProof section of a ZKA1 proof as it is
+// (4 n Tom points of 72 bytes, 3 n + 1 scalars).  Fixed per ring.
+#define ZKM1_HDR 16
+#define ZK_MAGIC_ZKM1 0x314d4b5au
+ZK_HD static inline uint64_t zkm1_size(uint32_t n) { return (uint64_t)ZKM1_HDR + 288ull * n + 32ull * (3ull * n + 1); }
 // Per-proof verify levels (zk_ctx_set_verify_level): the level a proof of o1 - o0 bytes at `pr` announces, 0..ZK_MAXSEC, or ZK_LV_BAD where the
 // header alone already makes it ZK_E_BAD_ENCODING in the pipeline at ANY level (short, misaligned, wrong magic, a length that is not the header's,
 // secLevel above 128, n above 63, or more bytes than the largest well-formed proof of that level) -- which also bounds the bytes a level's
