@@ -265,6 +265,37 @@ def test_gk_table_path_on_the_matrix_cores_equals_the_vector_form(nkeys, B0, mon
     eng.close(), vec.close()
 
 
+def test_gk_table_path_on_the_matrix_cores_with_keys_at_the_digit_extremes(monkeypatch):
+    """The prover's matrix-core table path on a ring whose non-signer keys follow the byte patterns of tests/extreme_rings.py (digits of all -128 / all +127, carries
+    through every digit, whole 256-key blocks of one pattern): the same bytes as the all-VALU table path (ZKATTEST_GK_MFMA_PROVE=0) on every proof, the oracle's
+    bytes on the first ones."""
+    import coracle as CO
+    import zkp_ecdsa_amd as Z
+    from extreme_rings import extreme_ring
+    S, nkeys, B = 4413, 4096, 37
+    eng = Z.Engine(0)
+    nh, tg, th = eng.synth_params(S)
+    eng.set_params(nh, tg, th, 80)
+    ring, msg, sig, pk, which, seeds = eng.synth_workload(S, nkeys, B)
+    ring = extreme_ring(ring, which)
+    eng.set_ring(ring, nkeys)
+    got, st = eng.prove_batch(msg, sig, pk, which, seeds=seeds)
+    assert st == [0] * B
+    monkeypatch.setenv('ZKATTEST_GK_MFMA_PROVE', '0')
+    vec = Z.Engine(0)
+    vec.set_params(nh, tg, th, 80)
+    vec.set_ring(ring, nkeys)
+    ref, st2 = vec.prove_batch(msg, sig, pk, which, seeds=seeds)
+    assert st2 == [0] * B
+    assert [hashlib.sha256(g).hexdigest() for g in got] == [hashlib.sha256(r).hexdigest() for r in ref]
+    octx = CO.OracleCtx(nh, tg, th, 80)
+    octx.set_ring(ring, nkeys)
+    exp, est = octx.prove_batch(msg[:32 * 2], sig[:64 * 2], pk[:64 * 2], which[:2], seeds=seeds[:32 * 2], nthreads=2)
+    assert est == [0, 0] and got[:2] == exp
+    assert eng.verify_batch(msg, got) == ([1] * B, [0] * B)
+    eng.close(), vec.close()
+
+
 @pytest.mark.parametrize('sec,nkeys,B', [(1, 4, 3), (7, 5, 4), (33, 12, 3), (128, 9, 2), (96, 300, 2)])
 def test_security_levels_other_than_80(sec, nkeys, B):
     """secLevel is a run-time parameter of the reference (SystemParametersList.SecLevel): repetition counts that are not a

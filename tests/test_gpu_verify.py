@@ -342,6 +342,46 @@ def test_ring_fold_on_the_matrix_pipe_equals_the_vector_form(nkeys, B):
     eng.close()
 
 
+def test_ring_fold_on_the_matrix_pipe_with_keys_at_the_digit_extremes():
+    """The balanced base-256 recoding of k_gk_mfma.hip (gkm_digits) where a synthetic ring never takes it: every key that no proof signs with follows a byte pattern
+    (tests/extreme_rings.py) -- digit planes of all -128 and all +127, a carry that ripples through the 32 digits into digit 32, the carry digit on every key of a
+    256-key block, whole blocks of one pattern.  Matrix pipe and 64-bit multiply-add form give the same verdicts and statuses on honest proofs and on the three
+    forged responses; the oracle agrees on the first proofs."""
+    import coracle as CO
+    import zkp_ecdsa_amd as Z
+    from extreme_rings import extreme_ring
+    nkeys, B = 4096, 37
+    eng = Z.Engine(0)
+    eng.set_comb_bits(16)
+    params = eng.synth_params(1213)
+    eng.set_params(*params, 80)
+    ring, msg, sig, pk, which, seeds = eng.synth_workload(1213, nkeys, B)
+    ring = extreme_ring(ring, which)
+    eng.set_ring(ring, nkeys)
+    eng.set_chunk(512)
+    proofs, st = eng.prove_batch(msg, sig, pk, which, seeds=seeds)
+    assert st == [0] * B
+    bad = list(proofs)
+    for b, pos in ((1, -9), (B // 2, -40), (B - 1, -9 - 32 * 3)):     # zd, a zb / za / f response of the GK proof
+        f = bytearray(proofs[b])
+        f[pos] ^= 0x20
+        bad[b] = bytes(f)
+    vs = _vseeds(B)
+    got = {}
+    for pipe in (0, 1):
+        eng.set_ring_fold(pipe)
+        got[pipe] = (eng.verify_batch(msg, proofs, vseeds=vs), eng.verify_batch(msg, bad, vseeds=vs))
+    assert got[0] == got[1]
+    assert got[1][0] == ([1] * B, [0] * B)
+    assert [b for b in range(B) if not got[1][1][0][b]] == sorted({1, B // 2, B - 1})
+    octx = CO.OracleCtx(*params, 80)
+    octx.set_ring(ring, nkeys)
+    k = 3
+    o = octx.verify_batch(msg[:32 * k], bad[:k], nthreads=k, vseeds=vs[:32 * k])
+    assert (list(o[0]), list(o[1])) == (got[1][1][0][:k], got[1][1][1][:k]) and list(o[0]) == [1, 0, 1]
+    eng.close()
+
+
 def test_sixty_four_groups_give_the_same_verdicts_and_a_finer_fallback():
     """zk_ctx_set_verify_groups(64): the chunk-wide check with 64 groups and 13-bit windows instead of 8 groups and 16-bit windows.
     Same verdicts and statuses for honest, forged and malformed proofs; a forged proof sends a 64th of its chunk (not an eighth) to

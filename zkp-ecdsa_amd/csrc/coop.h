@@ -178,7 +178,8 @@ ZK_DEV CoFe<M, Ka + Kb> co_add(const CoFe<M, Ka>& a, const CoFe<M, Kb>& b) {
     return r;
 }
 // C * M in the redundant form of field.h's fe_sub2 (every limb below the top lends 2^30 twice): limbs 0..7 >= 2^31 - 2 >= any nearly normalised
-// subtrahend limb, top limb >= the top limb of any value < (C - 1) * M; a + S < 2^32 for every constant of consts_gen.h (checked below).
+// subtrahend limb, top limb >= the top limb of any value < (C - 1) * M; a + S < 2^32 for every constant of consts_gen.h (checked below, the top limb
+// included; tests/test_coop_bounds.py has the exact interval form).
 template <class M, int C>
 ZK_DEV CoU32 co_sub_const() {
     CoU32 s;
@@ -196,9 +197,15 @@ ZK_DEV CoU32 co_sub_const() {
 template <class M>
 constexpr bool co_sub_consts_fit() {
     const uint32_t* all[7] = {M::sub4, M::sub8, M::sub16, M::sub32, M::sub64, M::sub128, M::sub256};
-    for (int c = 0; c < 7; c++)
+    for (int c = 0; c < 7; c++) {
         for (int i = 0; i < NLIMB - 1; i++)
             if ((uint64_t)all[c][i] + (i == 0 ? (1u << LIMB_BITS) : LIMB_MASK) + LIMB_MASK + CO_NEAR >= (1ull << 32)) return false;
+        // top limb (it lends one: S_8 - 1): at least that of any subtrahend < (C - 1) * M, and the top limb of a minuend < KCAP * M and the carry fit beside it;
+        // the top limb of a value < K * M is at most K * (M_8 + 1)
+        const uint64_t C = 4ull << c, m8 = (uint64_t)M::mod[NLIMB - 1] + 1;
+        if ((uint64_t)all[c][NLIMB - 1] < 1 + (C - 1) * m8) return false;
+        if ((uint64_t)all[c][NLIMB - 1] + KCAP * m8 + CO_NEAR >= (1ull << 32)) return false;
+    }
     return true;
 }
 static_assert(co_sub_consts_fit<ModT>() && co_sub_consts_fit<ModQ>() && co_sub_consts_fit<ModN>(), "a + C*M overflows a limb");

@@ -119,13 +119,13 @@ ZK_DEV Fe<M, Ka + SubC<Kb + Kc>::value> fe_sub2(const Fe<M, Ka>& a, const Fe<M, 
     limbs_normalize(r.l);
     return r;
 }
+// C*M - a with C the subtraction constant of a's magnitude.  The bound is C + 1, not C: -0 comes out as C*M itself, which is not BELOW C*M (a zero typed
+// Fe<M, 0> would promise a value below 0; tests/test_raw_limbs.py found fe_neg(0) outside its type).  The same instructions either way.
+template <class M>
+ZK_DEV Fe<M, 1> fe_zero();
 template <class M, int Ka>
-ZK_DEV Fe<M, SubC<Ka>::value> fe_neg(const Fe<M, Ka>& a) {
-    Fe<M, 0> z;
-#pragma unroll
-    for (int i = 0; i < NLIMB; i++) z.l[i] = 0;
-    auto r = z - a;
-    return r;
+ZK_DEV Fe<M, SubC<Ka>::value + 1> fe_neg(const Fe<M, Ka>& a) {
+    return fe_zero<M>() - a;
 }
 template <class M, int Ka>
 ZK_DEV Fe<M, 2 * Ka> fe_dbl(const Fe<M, Ka>& a) {
