@@ -657,6 +657,11 @@ zk_status zk_test_tom_commit(zk_ctx *ctx, uint64_t count, const uint8_t *v_be32,
 zk_status zk_test_tom_commit_shape(zk_ctx *ctx, uint32_t shape, uint64_t count, const uint8_t *v_be32, const uint8_t *r_be32, uint8_t *out_xy72);
 /* out[i] = k[i]*G (base_sel 0) or k[i]*h_NIST (base_sel 1) on P-256 (64-byte affine; all-zero for the identity) */
 zk_status zk_test_p256_fixed_mul(zk_ctx *ctx, int base_sel, uint64_t count, const uint8_t *k_be32, uint8_t *out_xy64);
+/* the table sums of the Exp commit phase on given scalars, key-table path of the active ring: T = g * G + k * (+- ring key `key`), A = T + b * h_NIST for count
+ * triples gkb[i] = g || k || b (3 x 32 bytes big-endian, reduced mod n); neg != 0: the key is the negative of its table's base point.  out: 4 x count points of 64
+ * bytes (affine; all-zero for the identity) -- T[0..count), A[0..count) through the device functions the prover's kernel runs, then T, A through the complete-law
+ * walks alone.  fell[i]: bit 0 / bit 1 = the first T / A was recomputed with the complete law.  ZK_E_BUFFER without parameters or key tables. */
+zk_status zk_test_exp_sum(zk_ctx *ctx, uint32_t key, int neg, uint64_t count, const uint8_t *gkb_be96, uint8_t *out_xy64, uint32_t *fell);
 /* digest[i] = SHA-256(msg[i]) for count messages of identical length len */
 zk_status zk_test_sha256(zk_ctx *ctx, uint64_t count, uint64_t len, const uint8_t *msgs, uint8_t *digests32);
 /* logical RNG draw k of each proof (after rejection mapping), 32 bytes BE */

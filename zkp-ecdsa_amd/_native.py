@@ -28,7 +28,7 @@ SYMBOLS = [
     'zk_prove_batch_rings', 'zk_prove_batch_rings_device', 'zk_pool_prove_batch_rings', 'zk_ring_proof_max_size',
     'zk_screen_batch', 'zk_screen_batch_device', 'zk_screen_batch_rings', 'zk_screen_batch_rings_device',
     'zk_member_proof_size', 'zk_member_prove_batch', 'zk_member_prove_batch_device', 'zk_member_verify_batch', 'zk_member_verify_batch_device',
-    'zk_test_field_op', 'zk_test_tom_commit', 'zk_test_p256_fixed_mul', 'zk_test_sha256', 'zk_test_rng_draws',
+    'zk_test_field_op', 'zk_test_tom_commit', 'zk_test_p256_fixed_mul', 'zk_test_sha256', 'zk_test_rng_draws', 'zk_test_exp_sum',
 ]
 
 STATUS_TEXT = {
@@ -191,6 +191,7 @@ def lib():
         L.zk_test_tom_commit.argtypes = [vp, u64, C.c_char_p, C.c_char_p, vp]
         L.zk_test_tom_commit_shape.argtypes = [vp, u32, u64, C.c_char_p, C.c_char_p, vp]
         L.zk_test_p256_fixed_mul.argtypes = [vp, i32, u64, C.c_char_p, vp]
+        L.zk_test_exp_sum.argtypes = [vp, C.c_uint32, i32, u64, C.c_char_p, vp, vp]
         L.zk_test_sha256.argtypes = [vp, u64, u64, C.c_char_p, vp]
         L.zk_test_rng_draws.argtypes = [vp, u64, C.POINTER(ZkRng), u32, u32, vp]
         _lib = L
@@ -815,6 +816,16 @@ class Engine:
         out = C.create_string_buffer(64 * n)
         self._chk(self.L.zk_test_p256_fixed_mul(self.h, base_sel, n, b''.join(x.to_bytes(32, 'big') for x in k_list), out))
         return [out.raw[64 * i:64 * i + 64] for i in range(n)]
+
+    def test_exp_sum(self, key, neg, gkb_list):
+        """zk_test_exp_sum: for every (g, k, b) the sums T = g G + k (+- ring key `key`), A = T + b h of the Exp commit phase's key-table kernel.  Returns
+        (T, A, T_complete, A_complete, fell): four lists of 64-byte affine points (zero bytes: the identity) and the fallback flags (bit 0: T, bit 1: A)."""
+        n = len(gkb_list)
+        out = C.create_string_buffer(256 * n)
+        fell = (C.c_uint32 * n)()
+        self._chk(self.L.zk_test_exp_sum(self.h, key, 1 if neg else 0, n, b''.join(x.to_bytes(32, 'big') for t in gkb_list for x in t), out, fell))
+        cols = [[out.raw[64 * (c * n + i):64 * (c * n + i) + 64] for i in range(n)] for c in range(4)]
+        return cols[0], cols[1], cols[2], cols[3], list(fell)
 
     def test_sha256(self, msgs):
         n, ln = len(msgs), len(msgs[0])

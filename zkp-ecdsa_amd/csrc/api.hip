@@ -1935,6 +1935,34 @@ extern "C" zk_status zk_test_p256_fixed_mul(zk_ctx* c, int base_sel, uint64_t co
     HIPCHK(c, hipMemcpy(out, dout.p, 64 * count, hipMemcpyDeviceToHost));
     return ZK_OK;
 }
+extern "C" zk_status zk_test_exp_sum(zk_ctx* c, uint32_t key, int neg, uint64_t count, const uint8_t* gkb, uint8_t* out, uint32_t* fell) {
+    if (!c || !gkb || !out || !fell || !count || count > 65536) return ZK_E_ARG;
+    if (!c->params_set || !c->ring->ktab) return ZK_E_BUFFER;
+    if (key >= c->ring->N) return ZK_E_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    uint8_t has = 0;
+    HIPCHK(c, hipMemcpy(&has, c->ring->ktab_ok + key, 1, hipMemcpyDeviceToHost));
+    if (!has) return ZK_E_ARG;   // the ring value is no x-coordinate: it has no table
+    const uint32_t n = (uint32_t)count, np = 4 * n;   // points: T, A of the sums under test, then T, A of the complete law
+    DevBuf dk, dlimbs, dout, df, dst;
+    HIPCHK(c, hipMalloc(&dk.p, 96 * count)); HIPCHK(c, hipMalloc(&dlimbs.p, sizeof(uint32_t) * NLIMB * 5 * np));
+    HIPCHK(c, hipMalloc(&dout.p, 64 * (size_t)np)); HIPCHK(c, hipMalloc(&df.p, 4 * count)); HIPCHK(c, hipMalloc(&dst.p, 4 * (size_t)np));
+    HIPCHK(c, hipMemsetAsync(dst.p, 0, 4 * (size_t)np, c->stream));
+    HIPCHK(c, hipMemcpy(dk.p, gkb, 96 * count, hipMemcpyHostToDevice));
+    auto col = [&](uint32_t i) { return Soa{dlimbs.as<uint32_t>() + (size_t)i * NLIMB * np, np}; };
+    const Soa3 proj{col(0), col(1), col(2)};
+    launch_test_exp_sum(c->stream, c->P, c->ring->ktab + (size_t)key * KTAB_KEY_WORDS, neg ? 1 : 0, n, dk.as<uint8_t>(), proj, df.as<uint32_t>());
+    launch_p256_normalize(c->stream, proj, np, col(3), col(4), dst.as<int32_t>(), 1, ZK_E_T_INF, nullptr);   // st[i] != 0: point i is the identity
+    launch_affine_to_bytes(c->stream, col(3), col(4), np, 0, dout.as<uint8_t>());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out, dout.p, 64 * (size_t)np, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(fell, df.p, 4 * count, hipMemcpyDeviceToHost));
+    std::vector<int32_t> inf(np);
+    HIPCHK(c, hipMemcpy(inf.data(), dst.p, 4 * (size_t)np, hipMemcpyDeviceToHost));
+    for (uint32_t i = 0; i < np; i++)
+        if (inf[i]) memset(out + 64 * (size_t)i, 0, 64);
+    return ZK_OK;
+}
 extern "C" zk_status zk_test_sha256(zk_ctx* c, uint64_t count, uint64_t len, const uint8_t* msgs, uint8_t* digests) {
     if (!c || !digests || !count || (len && !msgs)) return ZK_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));

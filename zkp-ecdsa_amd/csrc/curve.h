@@ -206,6 +206,101 @@ ZK_DEV P256Pt p256_select(bool c, const P256Pt& a, const P256Pt& b) {
     } while (0)
 #endif
 
+// XYZZ coordinates (x = X / ZZ, y = Y / ZZZ, ZZ^3 = ZZZ^2) for the SUMS OF AFFINE TABLE ENTRIES of k_exp_commit_kt (rtab.h / ktab.h: the *_xyzz walks): the
+// generic mixed addition "madd-2008-s" costs 8 products and 2 squarings against the 13 products of p256_add_mixed.  It is NOT complete: it is wrong when the
+// running point is the identity and when the entry has the running point's x (P = 0 below: a doubling, or a sum that is the identity).  The walks never test
+// for either per step:
+//   * a sum starts EMPTY (P256XyzzSum::empty) and its first entry is copied, so the law never sees the identity as an operand;
+//   * ZZ' = ZZ P^2 and ZZZ' = ZZZ P^3: one step with P = 0 leaves ZZ = 0 for the rest of the sum, whatever is added afterwards.  A final ZZ != 0 therefore proves
+//     that every step was a generic addition of two points with different x, and ONE zero test of ZZ per stored point decides whether the lane recomputes the sum
+//     with the complete law (never on honest inputs; a prover who knows the discrete log of its key can craft scalars that get there).
+// Magnitudes: the lazy subtractions leave X < 10 q and Y < 6 q; as operands of the next addition (P = U2 - X < 18 q, R = S2 - Y < 10 q, Q - X' < 18 q) every
+// product stays far inside ModQ::kmax (18 * 18, 10 * 18), so a chain of additions needs no reduction of its own.
+struct P256Xyzz {
+    Fe<ModQ, 10> x;
+    Fe<ModQ, 6> y;
+    Fq2 zz, zzz;
+};
+ZK_DEV P256Xyzz p256_xyzz_from_affine(const P256Aff& a) {
+    P256Xyzz r;
+    r.x = a.x.as<10>(), r.y = a.y.as<6>();
+    r.zz = fe_one_mont<ModQ>().as<2>(), r.zzz = fe_one_mont<ModQ>().as<2>();
+    return r;
+}
+// the two squarings of the addition below: the squaring form (45 + 81 multiply-adds) where the translation unit computes its products one after the other,
+// the lock-step pair (field.h: limbs_mont_mul_n) where it batches them
+template <int Ka, int Kb>
+ZK_DEV void p256_sqr2(Fq2& r0, Fq2& r1, const Fe<ModQ, Ka>& a, const Fe<ModQ, Kb>& b) {
+#if ZK_BATCH_P256 && !defined(ZK_HOST_BUILD)
+    fe_mul2<true>(r0, r1, a, a, b, b);
+#else
+    r0 = fe_sqr(a), r1 = fe_sqr(b);
+#endif
+}
+// p + q, q affine and not the identity, p not the identity, x(p) != x(q): four lock-step groups, 2 + 2 + 3 + 3 products
+ZK_DEV P256Xyzz p256_xyzz_madd(const P256Xyzz& p, const P256Aff& q) {
+    Fq2 u2, s2;
+    fe_mul2<ZK_BATCH_P256 != 0>(u2, s2, q.x, p.zz, q.y, p.zzz);
+    auto P = u2 - p.x;
+    auto R = s2 - p.y;
+    Fq2 pp, rr;
+    Fq2 ppp, Q;
+    P256Xyzz r;
+    p256_sqr2(pp, rr, P, R);
+    fe_mul3<ZK_BATCH_P256 != 0>(ppp, Q, r.zz, P, pp, p.x, pp, p.zz, pp);
+    auto x3 = fe_sub2(rr, ppp, Q + Q);
+    Fq2 m1, m2;
+    fe_mul3<ZK_BATCH_P256 != 0>(m1, m2, r.zzz, R, Q - x3, p.y, ppp, p.zzz, ppp);
+    r.x = x3;
+    r.y = m1 - m2;
+    return r;
+}
+// (X : Y : ZZ : ZZZ) -> (X ZZZ : Y ZZ : ZZ ZZZ) homogeneous, the form the stores, the normaliser and k_t1 take: 3 products
+ZK_DEV P256Pt p256_from_xyzz(const P256Xyzz& p) {
+    Fq2 x, y, z;
+    fe_mul3<ZK_BATCH_P256 != 0>(x, y, z, p.x, p.zzz, p.y, p.zz, p.zz, p.zzz);
+    P256Pt r;
+    r.x = x.as<8>(), r.y = y.as<8>(), r.z = z.as<8>();
+    return r;
+}
+ZK_DEV P256Xyzz p256_xyzz_select(bool c, const P256Xyzz& a, const P256Xyzz& b) {
+    P256Xyzz r;
+    r.x = fe_select(c, a.x, b.x), r.y = fe_select(c, a.y, b.y);
+    r.zz = fe_select(c, a.zz, b.zz), r.zzz = fe_select(c, a.zzz, b.zzz);
+    return r;
+}
+// A sum of table entries under way.  empty: nothing added yet (p is then all zeros and never read as a point).
+struct P256XyzzSum {
+    P256Xyzz p;
+    bool empty;
+};
+ZK_DEV P256XyzzSum p256_xyzz_sum_empty() {
+    P256XyzzSum s;
+    s.p.x = fe_zero<ModQ>().as<10>(), s.p.y = fe_zero<ModQ>().as<6>();
+    s.p.zz = fe_zero<ModQ>().as<2>(), s.p.zzz = fe_zero<ModQ>().as<2>();
+    s.empty = true;
+    return s;
+}
+// one step of a table walk: the entry e of a NON-ZERO digit (nz) joins the sum -- copied into an empty sum, added otherwise; a zero digit changes nothing.
+// Default build: the caller branches on nz (and loads e inside the branch); -DZK_UNIFORM_CF=1: computed on a valid entry and discarded by select, like ZK_ADD_IF.
+ZK_DEV void p256_xyzz_sum_step(P256XyzzSum& s, bool nz, const P256Aff& e) {
+#if ZK_UNIFORM_CF
+    const P256Xyzz a = p256_xyzz_madd(s.p, e), c = p256_xyzz_from_affine(e);
+    s.p = p256_xyzz_select(nz, p256_xyzz_select(s.empty, c, a), s.p);
+    s.empty = s.empty && !nz;
+#else
+    if (nz) {
+        if (s.empty) s.p = p256_xyzz_from_affine(e);
+        else s.p = p256_xyzz_madd(s.p, e);
+        s.empty = false;
+    }
+#endif
+}
+// did the sum meet an exceptional pair?  (the canonical zero test of ZZ, once per stored point)
+ZK_DEV bool p256_xyzz_sum_degenerate(const P256XyzzSum& s) { return !s.empty && fe_is_zero(s.p.zz); }
+// the sum as a homogeneous point; an empty sum is the identity (0 : 1 : 0).  Meaningless where p256_xyzz_sum_degenerate.
+ZK_DEV P256Pt p256_xyzz_sum_point(const P256XyzzSum& s) { return p256_select(s.empty, p256_identity(), p256_from_xyzz(s.p)); }
+
 // y^2 == x^3 - 3x + b  (weier.ts:56-70 with Z = 1)
 ZK_DEV bool p256_on_curve(const P256Aff& a) {
     const auto b = fe_const<ModQ, 1>(P256_B_M);

@@ -56,14 +56,7 @@ static inline size_t tom_tab_words(uint32_t bits) { return (size_t)tom_nwin(bits
 #ifndef ZK_NORM_MIN_THREADS
 #define ZK_NORM_MIN_THREADS 131072
 #endif
-#ifndef PFIX_WIN_BITS
-#define PFIX_WIN_BITS 20
-#endif
-#define PFIX_NWIN ((256 + PFIX_WIN_BITS - 1) / PFIX_WIN_BITS)
-#define PFIX_WIN_SIZE (1u << PFIX_WIN_BITS)
-#define PFIX_ENTRY_WORDS 20
-#define PFIX_TAB_WORDS ((size_t)PFIX_NWIN * PFIX_WIN_SIZE * PFIX_ENTRY_WORDS)
-#include "ktab.h"   // layout of the per-key tables of the ring (KTAB_*) and the multiplication through them
+#include "ktab.h"   // layout of the per-key tables of the ring (KTAB_*) and the multiplication through them; geometry of the fixed-base combs (PFIX_*)
 size_t ktab_temp_bytes(uint64_t N, uint32_t slab_keys);
 void launch_ktab_build(hipStream_t s, const Soa& ring, uint64_t N, uint32_t* ktab, uint8_t* ok, void* temp, uint32_t slab_keys);
 // the same kernels over a list of ring entries (zk_ctx_update_ring); temp: ktab_temp_bytes(count, slab_keys), indexed by position in the list
@@ -495,6 +488,7 @@ void launch_exp_commit(hipStream_t s, const DevParams& P, const Workspace& W, ui
 void launch_p256_normalize(hipStream_t s, const Soa3& proj, uint32_t count, const Soa& ox, const Soa& oy, int32_t* st, uint32_t per_proof, int32_t err_code, const uint32_t* owner /*nullable: item->proof*/);
 void launch_t1(hipStream_t s, const Workspace& W, uint32_t items);
 void launch_test_pfix(hipStream_t s, const uint32_t* tab, uint64_t count, const uint8_t* k_be, uint8_t* out);
+void launch_test_exp_sum(hipStream_t s, const DevParams& P, const uint32_t* kt, uint32_t neg, uint32_t count, const uint8_t* gkb_be, const Soa3& proj /*4 * count points*/, uint32_t* fell);
 // k_hash.hip
 void launch_rng_prepass(hipStream_t s, const Workspace& W, uint32_t count, uint32_t blk0, uint32_t blk1, uint32_t stride, uint32_t* fill, bool by_zcnt);
 void launch_exp_challenge(hipStream_t s, const Workspace& W, uint32_t count);
@@ -684,13 +678,6 @@ ZK_DEV void store_tomcoord_be(uint8_t* p, const Fe<ModT, 1>& a) {  // canonical 
     uint32_t w[9];
     words_from_limbs<9>(w, a.l);
     store_be<9>(p, w);
-}
-// shift a 256-bit little-endian word array right by SH bits
-template <int SH>
-ZK_DEV void shr256(uint32_t w[8]) {
-#pragma unroll
-    for (int i = 0; i < 7; i++) w[i] = (w[i] >> SH) | (w[i + 1] << (32 - SH));
-    w[7] >>= SH;
 }
 // offset of rep i inside a proof, given the challenge (bit = 1 -> short response)
 ZK_DEV uint32_t zeros_below(const uint32_t* chal, uint32_t i) {  // number of 0 bits among challenge bits [0, i)

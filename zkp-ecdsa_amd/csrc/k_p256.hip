@@ -257,6 +257,39 @@ __global__ void __launch_bounds__(256) k_exp_commit(DevParams P, Workspace W, ui
     st_proj(W.Tproj, t, T);
     st_proj(W.Aproj, t, A);
 }
+// The sums of one lane of k_exp_commit_kt: T = g * G + k * (+- key) and A = T + b * h over the three tables, in XYZZ coordinates (curve.h: p256_xyzz_madd, 8 products
+// and 2 squarings per gathered entry instead of the 13 products of the complete mixed addition), as ONE chain: h's entries go straight onto T's sum.  The generic law
+// has exceptional pairs, so each of the two stored points gets ONE zero test of ZZ (curve.h has the argument why that is enough, and why a T that fails sends A after
+// it).  A lane whose test fires computes BOTH points again with the complete law -- the walks this kernel consisted of before -- inline, in a wave-divergent branch behind
+// the fast path, where nothing of the fast path is live any more: the kernel's registers are the maximum of the two paths.  Expected never to run on honest inputs, but
+// a prover knows the discrete log of its key and can make a multiple of G meet a multiple of the key.  Same group elements either way, hence the same affine
+// coordinates and the same bytes (a T that was fine is stored a second time, in the complete law's representation).
+//   scal_gk(gw, kw), scal_b(bw): (re)fill the scalars, 8 little-endian words each -- the walks clobber them;  st_t(T), st_a(A): store the points.
+// Returns 0, or which point sent the lane to the complete law: 1 = T (and with it A: 3), 2 = A alone.
+template <class ScalGK, class ScalB, class StT, class StA>
+ZK_DEV uint32_t exp_kt_sums(const DevParams& P, const uint32_t* __restrict__ kt, bool neg, const ScalGK& scal_gk, const ScalB& scal_b, const StT& st_t, const StA& st_a) {
+    uint32_t gw[8], kw[8], bw[8], fell = 0;
+    {
+        P256XyzzSum s = p256_xyzz_sum_empty();
+        scal_gk(gw, kw);
+        p256_fixed_mul_acc_xyzz(s, P.pfix_G, gw);
+        p256_ktab_mul_acc_xyzz(s, kt, kw, neg);
+        if (p256_xyzz_sum_degenerate(s)) fell = 1;
+        else st_t(p256_xyzz_sum_point(s));
+        scal_b(bw);
+        p256_fixed_mul_acc_xyzz(s, P.pfix_H, bw);
+        if (p256_xyzz_sum_degenerate(s)) fell |= 2;
+        else st_a(p256_xyzz_sum_point(s));
+    }
+    if (fell) {
+        scal_gk(gw, kw);
+        scal_b(bw);
+        const P256Pt T = p256_ktab_mul_acc(p256_fixed_mul(P.pfix_G, gw), kt, kw, neg);
+        st_t(T);
+        st_a(p256_fixed_mul_acc(T, P.pfix_H, bw));   // A = T + r * h, the comb's additions straight onto T
+    }
+    return fell;
+}
 __global__ void __launch_bounds__(256) k_exp_commit_kt(DevParams P, Workspace W, uint32_t count) {
     uint32_t t = gtid();
     uint32_t per = W.sec + 1;
@@ -264,15 +297,17 @@ __global__ void __launch_bounds__(256) k_exp_commit_kt(DevParams P, Workspace W,
     uint32_t p = t / per, j = t % per;
     const uint32_t use = W.kt_use[p];
     if (!use) return;
-    uint32_t aw[8], bw[8], gw[8], kw[8];
-    exp_scalars(W, p, j, aw, bw, true, true);
-    Fe<ModN, 1> al;
-    limbs_from_words<8>(al.l, aw);
-    words_from_limbs<8>(gw, fe_canon(al.as<2>() * soa_ld<ModN, 1>(W.u1m, p).as<2>()).l);   // plain x Montgomery = plain
-    words_from_limbs<8>(kw, fe_canon(al.as<2>() * soa_ld<ModN, 1>(W.u2m, p).as<2>()).l);
-    P256Pt T = p256_ktab_mul_acc(p256_fixed_mul(P.pfix_G, gw), W.ktab + (size_t)W.kt_key[p] * KTAB_KEY_WORDS, kw, use == 2);
-    st_proj(W.Tproj, t, T);
-    st_proj(W.Aproj, t, p256_fixed_mul_acc(T, P.pfix_H, bw));   // A = T + r * h, the comb's additions straight onto T
+    exp_kt_sums(
+        P, W.ktab + (size_t)W.kt_key[p] * KTAB_KEY_WORDS, use == 2,
+        [&](uint32_t gw[8], uint32_t kw[8]) {
+            uint32_t aw[8];
+            exp_scalars(W, p, j, aw, nullptr, true, false);
+            Fe<ModN, 1> al;
+            limbs_from_words<8>(al.l, aw);
+            words_from_limbs<8>(gw, fe_canon(al.as<2>() * soa_ld<ModN, 1>(W.u1m, p).as<2>()).l);   // plain x Montgomery = plain
+            words_from_limbs<8>(kw, fe_canon(al.as<2>() * soa_ld<ModN, 1>(W.u2m, p).as<2>()).l);
+        },
+        [&](uint32_t bw[8]) { exp_scalars(W, p, j, nullptr, bw, false, true); }, [&](const P256Pt& T) { st_proj(W.Tproj, t, T); }, [&](const P256Pt& A) { st_proj(W.Aproj, t, A); });
 }
 // The same for a small chunk, FOUR lanes per (proof, repetition): each takes a quarter of the windows of G's comb, of the key's table and of h's comb
 // (4 + 9 + 4 gathered additions in a row instead of 13 + 33 + 13), the partial sums meet through the wave's cross-lane moves.  Same group elements,
@@ -598,6 +633,30 @@ __global__ void __launch_bounds__(64) k_test_pfix(const uint32_t* tab, uint64_t 
     }
     store_be<8>(out + 64 * (size_t)t, xw);
     store_be<8>(out + 64 * (size_t)t + 32, yw);
+}
+// ---------------------------------------------------------------- unit-test hook: the sums of k_exp_commit_kt on given scalars
+// Sum i: T = g_i * G + k_i * (+- key), A = T + b_i * h through exp_kt_sums (what the kernel runs) and through the complete-law walks alone.  proj: 4 * count points --
+// T at i and A at count + i from the first, T at 2 count + i and A at 3 count + i from the second; fell[i]: exp_kt_sums' return value.
+__global__ void __launch_bounds__(64) k_test_exp_sum(DevParams P, const uint32_t* kt, uint32_t neg, uint32_t count, const uint8_t* gkb_be, Soa3 proj, uint32_t* fell) {
+    const uint32_t t = gtid();
+    if (t >= count) return;
+    const uint8_t* sc = gkb_be + 96 * (size_t)t;
+    auto scal = [&](uint32_t w[8], uint32_t which) {
+        load_be32(sc + 32 * which, w);
+        Fe<ModN, 1> k = fe_from_words256_reduce<ModN>(w);
+        words_from_limbs<8>(w, k.l);
+    };
+    fell[t] = exp_kt_sums(
+        P, kt, neg != 0, [&](uint32_t gw[8], uint32_t kw[8]) { scal(gw, 0), scal(kw, 1); }, [&](uint32_t bw[8]) { scal(bw, 2); },
+        [&](const P256Pt& T) { st_proj(proj, t, T); }, [&](const P256Pt& A) { st_proj(proj, count + t, A); });
+    uint32_t gw[8], kw[8], bw[8];
+    scal(gw, 0), scal(kw, 1), scal(bw, 2);
+    const P256Pt T = p256_ktab_mul_acc(p256_fixed_mul(P.pfix_G, gw), kt, kw, neg != 0);
+    st_proj(proj, 2 * count + t, T);
+    st_proj(proj, 3 * count + t, p256_fixed_mul_acc(T, P.pfix_H, bw));
+}
+void launch_test_exp_sum(hipStream_t s, const DevParams& P, const uint32_t* kt, uint32_t neg, uint32_t count, const uint8_t* gkb_be, const Soa3& proj, uint32_t* fell) {
+    hipLaunchKernelGGL(k_test_exp_sum, dim3((count + 63) / 64), dim3(64), 0, s, P, kt, neg, count, gkb_be, proj, fell);
 }
 void launch_test_pfix(hipStream_t s, const uint32_t* tab, uint64_t count, const uint8_t* k_be, uint8_t* out) {
     hipLaunchKernelGGL(k_test_pfix, dim3((count + 63) / 64), dim3(64), 0, s, tab, count, k_be, out);

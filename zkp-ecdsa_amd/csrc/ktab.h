@@ -4,6 +4,23 @@
 #include "comb_digits.h"
 #include "curve.h"
 
+// geometry of the fixed-base combs of G and h_NIST (engine.h has their description; rtab.h walks them -- here so that tests/host_arith can compile the walks
+// for the host with a narrow comb, -DPFIX_WIN_BITS=...)
+#ifndef PFIX_WIN_BITS
+#define PFIX_WIN_BITS 20
+#endif
+#define PFIX_NWIN ((256 + PFIX_WIN_BITS - 1) / PFIX_WIN_BITS)
+#define PFIX_WIN_SIZE (1u << PFIX_WIN_BITS)
+#define PFIX_ENTRY_WORDS 20
+#define PFIX_TAB_WORDS ((size_t)PFIX_NWIN * PFIX_WIN_SIZE * PFIX_ENTRY_WORDS)
+// shift a 256-bit little-endian word array right by SH bits
+template <int SH>
+ZK_DEV void shr256(uint32_t w[8]) {
+#pragma unroll
+    for (int i = 0; i < 7; i++) w[i] = (w[i] >> SH) | (w[i + 1] << (32 - SH));
+    w[7] >>= SH;
+}
+
 // per-KEY tables (k_ktab.hip): every ring key P gets d * 2^(8 w) * P, d = 1..128, w = 0..32, affine, 64 bytes per entry (slot d - 1 of
 // window w): 264 KB per key, 17.7 GB for a ring of 2^16 keys.  A scalar is recoded into signed 8-bit digits in [-127, 128] (a negative
 // digit negates the entry on load), so a prover's k * pk is 33 mixed additions of gathered entries, and alpha_i * R of proveExp
@@ -67,6 +84,26 @@ ZK_DEV P256Pt p256_ktab_mul_acc(P256Pt acc, const uint32_t* __restrict__ kt, uin
         ZK_ADD_IF(d != 0, acc, p256_add_mixed(acc, ld_ktab(kt + ((size_t)w * KTAB_ENT + (d ? d - 1 : 0)) * KTAB_ENTRY_WORDS, neg != dn)));   // a zero digit (2^-8) idles its lane (curve.h: ZK_UNIFORM_CF)
     }
     return acc;
+}
+// The same sum in XYZZ coordinates (curve.h: p256_xyzz_madd, 8 products and 2 squarings per entry instead of 13 products) onto a sum under way: k_exp_commit_kt.
+// Same digits, same entries, a negative digit still negates y on load.  The caller tests the sum once where it stores it (p256_xyzz_sum_degenerate) and falls
+// back to p256_ktab_mul_acc above.
+ZK_DEV void p256_ktab_mul_acc_xyzz(P256XyzzSum& s, const uint32_t* __restrict__ kt, const uint32_t kw[8], bool neg) {
+    KeyDigits kd;
+    kd.init();
+#pragma unroll
+    for (int i = 0; i < 8; i++) kd.w[i] = kw[i];
+#pragma unroll 1
+    for (uint32_t w = 0; w < KTAB_NWIN; w++) {
+        uint32_t d;
+        bool dn;
+        kd.next(d, dn);
+#if ZK_UNIFORM_CF
+        p256_xyzz_sum_step(s, d != 0, ld_ktab(kt + ((size_t)w * KTAB_ENT + (d ? d - 1 : 0)) * KTAB_ENTRY_WORDS, neg != dn));
+#else
+        if (d != 0) p256_xyzz_sum_step(s, true, ld_ktab(kt + ((size_t)w * KTAB_ENT + d - 1) * KTAB_ENTRY_WORDS, neg != dn));   // a zero digit (2^-8) idles its lane
+#endif
+    }
 }
 // The same sum restricted to windows [w0, w0 + per): the table holds every window multiple, so several lanes can take a range each (rtab.h:
 // p256_rtab_mul_range has the reasoning behind the two loops: the carries below w0 are integer work with a per-lane trip count, the additions have one

@@ -6,8 +6,73 @@
 // width; a negative digit negates Y on load.  Prover: bits = 6 (43 windows x 32 entries, 43 additions per multiple,
 // 80 multiples per proof); verifier: bits = 4 (65 x 8, 21 multiples per proof).  Projective entries (X, Y, Z), 28 words.
 #pragma once
+#ifdef ZK_HOST_BUILD
+#include "ktab.h"   // tests/host_arith: the fixed-base comb walks below, nothing else of this file
+#else
 #include "engine.h"
+#endif
 
+// ---- fixed-base combs of G and h_NIST (ktab.h: PFIX_*): entry = affine (x, y) Montgomery limbs, digit 0 unused
+ZK_DEV P256Aff ld_pfix(const uint32_t* e) {
+    uint32_t w[20];
+#ifdef ZK_HOST_BUILD
+    for (int i = 0; i < 20; i++) w[i] = e[i];
+#else
+    const uint4* q = (const uint4*)e;
+#pragma unroll
+    for (int i = 0; i < 5; i++) {
+        uint4 v = q[i];
+        w[4 * i] = v.x, w[4 * i + 1] = v.y, w[4 * i + 2] = v.z, w[4 * i + 3] = v.w;
+    }
+#endif
+    P256Aff a;
+#pragma unroll
+    for (int l = 0; l < 9; l++) a.x.l[l] = w[l], a.y.l[l] = w[9 + l];
+    return a;
+}
+// k * B for a fixed base with a PFIX_WIN_BITS-bit comb table; k given as 8 little-endian words (clobbered)
+ZK_DEV P256Pt p256_fixed_mul(const uint32_t* __restrict__ tab, uint32_t kw[8]) {
+    P256Pt acc;
+    {   // first window: identity + entry = the entry
+        uint32_t d = kw[0] & (PFIX_WIN_SIZE - 1);
+        shr256<PFIX_WIN_BITS>(kw);
+        acc = p256_select(d != 0, p256_from_affine(ld_pfix(tab + (size_t)PFIX_ENTRY_WORDS * d)), p256_identity());
+    }
+#pragma unroll 1
+    for (int w = 1; w < PFIX_NWIN; w++) {
+        uint32_t d = kw[0] & (PFIX_WIN_SIZE - 1);
+        shr256<PFIX_WIN_BITS>(kw);
+        ZK_ADD_IF(d != 0, acc, p256_add_mixed(acc, ld_pfix(tab + (size_t)PFIX_ENTRY_WORDS * (w * PFIX_WIN_SIZE + (d ? d : 1)))));   // a zero digit (2^-20) idles its lane (rtab.h: ZK_UNIFORM_CF)
+    }
+    return acc;
+}
+// acc + k * B: the comb's additions go straight onto a running point (one complete addition less than summing two results)
+ZK_DEV P256Pt p256_fixed_mul_acc(P256Pt acc, const uint32_t* __restrict__ tab, uint32_t kw[8]) {
+#pragma unroll 1
+    for (int w = 0; w < PFIX_NWIN; w++) {
+        uint32_t d = kw[0] & (PFIX_WIN_SIZE - 1);
+        shr256<PFIX_WIN_BITS>(kw);
+        ZK_ADD_IF(d != 0, acc, p256_add_mixed(acc, ld_pfix(tab + (size_t)PFIX_ENTRY_WORDS * (w * PFIX_WIN_SIZE + (d ? d : 1)))));   // a zero digit (2^-20) idles its lane (rtab.h: ZK_UNIFORM_CF)
+    }
+    return acc;
+}
+// sum + k * B in XYZZ coordinates (curve.h: p256_xyzz_madd), the comb's entries straight onto a sum under way -- G's comb from an empty sum, h's onto T:
+// k_exp_commit_kt.  k as 8 little-endian words (clobbered).  The caller tests the sum once where it stores it (p256_xyzz_sum_degenerate) and falls back to
+// p256_fixed_mul / p256_fixed_mul_acc above.
+ZK_DEV void p256_fixed_mul_acc_xyzz(P256XyzzSum& s, const uint32_t* __restrict__ tab, uint32_t kw[8]) {
+#pragma unroll 1
+    for (int w = 0; w < PFIX_NWIN; w++) {
+        uint32_t d = kw[0] & (PFIX_WIN_SIZE - 1);
+        shr256<PFIX_WIN_BITS>(kw);
+#if ZK_UNIFORM_CF
+        p256_xyzz_sum_step(s, d != 0, ld_pfix(tab + (size_t)PFIX_ENTRY_WORDS * (w * PFIX_WIN_SIZE + (d ? d : 1))));
+#else
+        if (d != 0) p256_xyzz_sum_step(s, true, ld_pfix(tab + (size_t)PFIX_ENTRY_WORDS * (w * PFIX_WIN_SIZE + d)));   // a zero digit (2^-20) idles its lane
+#endif
+    }
+}
+
+#if !defined(ZK_HOST_BUILD)
 ZK_DEV P256Pt ld_rtab(const uint32_t* e) {
     const uint4* q = (const uint4*)e;
     uint32_t w[28];
@@ -92,7 +157,6 @@ ZK_DEV P256Pt p256_rtab_mul_range(const uint32_t* __restrict__ rtab, uint32_t kw
 
 // ---- sums over tables that hold EVERY window multiple need no doubling, so several lanes can take a range of windows each and add their partial sums through
 // the wave's cross-lane moves (round 4: k_v_exp_points; round 5: the prover's table sums of a small chunk, k_p256.hip / k_tom.hip "wide" kernels).
-#if !defined(ZK_HOST_BUILD)
 ZK_DEV P256Pt p256_shfl_xor(const P256Pt& a, int m) {
     P256Pt r;
 #pragma unroll
@@ -100,45 +164,6 @@ ZK_DEV P256Pt p256_shfl_xor(const P256Pt& a, int m) {
         r.x.l[l] = (uint32_t)__shfl_xor((int)a.x.l[l], m), r.y.l[l] = (uint32_t)__shfl_xor((int)a.y.l[l], m), r.z.l[l] = (uint32_t)__shfl_xor((int)a.z.l[l], m);
     }
     return r;
-}
-ZK_DEV P256Aff ld_pfix(const uint32_t* e) {
-    const uint4* q = (const uint4*)e;
-    uint32_t w[20];
-#pragma unroll
-    for (int i = 0; i < 5; i++) {
-        uint4 v = q[i];
-        w[4 * i] = v.x, w[4 * i + 1] = v.y, w[4 * i + 2] = v.z, w[4 * i + 3] = v.w;
-    }
-    P256Aff a;
-#pragma unroll
-    for (int l = 0; l < 9; l++) a.x.l[l] = w[l], a.y.l[l] = w[9 + l];
-    return a;
-}
-// k * B for a fixed base with a PFIX_WIN_BITS-bit comb table; k given as 8 little-endian words (clobbered)
-ZK_DEV P256Pt p256_fixed_mul(const uint32_t* __restrict__ tab, uint32_t kw[8]) {
-    P256Pt acc;
-    {   // first window: identity + entry = the entry
-        uint32_t d = kw[0] & (PFIX_WIN_SIZE - 1);
-        shr256<PFIX_WIN_BITS>(kw);
-        acc = p256_select(d != 0, p256_from_affine(ld_pfix(tab + (size_t)PFIX_ENTRY_WORDS * d)), p256_identity());
-    }
-#pragma unroll 1
-    for (int w = 1; w < PFIX_NWIN; w++) {
-        uint32_t d = kw[0] & (PFIX_WIN_SIZE - 1);
-        shr256<PFIX_WIN_BITS>(kw);
-        ZK_ADD_IF(d != 0, acc, p256_add_mixed(acc, ld_pfix(tab + (size_t)PFIX_ENTRY_WORDS * (w * PFIX_WIN_SIZE + (d ? d : 1)))));   // a zero digit (2^-20) idles its lane (rtab.h: ZK_UNIFORM_CF)
-    }
-    return acc;
-}
-// acc + k * B: the comb's additions go straight onto a running point (one complete addition less than summing two results)
-ZK_DEV P256Pt p256_fixed_mul_acc(P256Pt acc, const uint32_t* __restrict__ tab, uint32_t kw[8]) {
-#pragma unroll 1
-    for (int w = 0; w < PFIX_NWIN; w++) {
-        uint32_t d = kw[0] & (PFIX_WIN_SIZE - 1);
-        shr256<PFIX_WIN_BITS>(kw);
-        ZK_ADD_IF(d != 0, acc, p256_add_mixed(acc, ld_pfix(tab + (size_t)PFIX_ENTRY_WORDS * (w * PFIX_WIN_SIZE + (d ? d : 1)))));   // a zero digit (2^-20) idles its lane (rtab.h: ZK_UNIFORM_CF)
-    }
-    return acc;
 }
 // ---- k * P for a point without a table of its own, as the ECDSA front ends take u2 * pk (k_p256.hip: k_front*; k_screen.hip): signed 4-bit digits, the
 // multiples 1..8 of P in the first eight entries of a scratch area (rtab.h entry format), 65 windows of four doublings and one addition
