@@ -387,8 +387,12 @@ zk_status zk_prove_batch_rings_device(zk_ctx *ctx, uint64_t B, const void *d_msg
  * How: find mode runs blocks of 256 witnesses against tiles of the ring's lowest limb in LDS, compares at full width where that limb matches and keeps the
  * lowest index; the ECDSA part is one lane per witness -- one inversion (of s), u1 G by the comb of G (13 additions), u2 pk through the key's table where the
  * looked-up entry has one (33 additions; zk_ctx_set_key_tables) and by the prover's 65-window walk otherwise, and the comparison X == r Z, X == (r + n) Z
- * without a field inversion.  A _rings call makes one pass per resident ring.
- * Not provided: a cooperative form for calls of a few witnesses (the one-lane kernels serve B = 1), streamed (submit / wait) variants, zk_pool_* variants. */
+ * without a field inversion.  A _rings call makes one pass per resident ring.  A chunk of at most 4 096 witnesses (ZK_SCREEN_CO_MAX; the decision is taken per
+ * chunk, so a call of 16 384 + 3 runs its last three that way) takes the point arithmetic on cooperating waves instead, one workgroup of four waves per witness:
+ * on the key-table path a quarter of the comb's and of the table's windows per wave, on the walk one wave for the 65 windows while the others sum u1 G.  Same
+ * which_out and flags bit for bit; ZKATTEST_ONE_LANE_CHAINS (any value) keeps every chunk on the one-lane kernels; zk_test_counter 4 counts four chains per
+ * witness of a cooperative chunk.
+ * Not provided: streamed (submit / wait) variants, zk_pool_* variants. */
 #define ZK_WHICH_NONE 0xFFFFFFFFu
 enum {
     ZK_SCREEN_KEY_NOT_ON_CURVE = 1,
@@ -626,7 +630,8 @@ int zk_pool_test_locality(const char *pci_bus_id, int *numa_node, int *cpus, int
  * 2 = live terms that went through the verifier's batched Tom-256 check (bucket pass) since the context was created;
  * 3 = proofs whose P-256 relation was accepted by the cross-proof P-256 pass (chunks of at least ZKATTEST_P256_BATCH proofs, default 8192): every GROUP
  *     without a failing proof counts (a failing group, not its chunk, goes through the per-proof sums);
- * 4 = dependent chains of small calls handed to cooperating waves so far (k_coop.hip: Straus sums, the table of R), process-wide;
+ * 4 = dependent chains of small calls handed to cooperating waves so far (k_coop.hip: Straus sums, the table of R; k_p256.hip: the prover's table sums;
+ *     k_screen.hip: four per witness of a screen chunk of at most ZK_SCREEN_CO_MAX witnesses, whatever paths they take), process-wide;
  * 5 = per-key tables COMPUTED by the ring builder since the context was created (a full build computes one per padded entry; the tables zk_ctx_update_ring
  *     copies from entry 0 for padding entries do not count);
  * 6 = 256-key blocks whose table E was built since the context was created;

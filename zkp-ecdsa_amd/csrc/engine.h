@@ -314,8 +314,12 @@ void launch_v_acc_tree(hipStream_t s, const Soa4& src, uint32_t nouter, uint32_t
 #ifndef ZK_COOP_MAX_CHAINS
 #define ZK_COOP_MAX_CHAINS 16384u
 #endif
+// ... and the witness screen's point arithmetic (k_screen.hip: four waves per witness) for a chunk of at most ZK_SCREEN_CO_MAX witnesses: ZK_COOP_MAX_CHAINS / 4
+#ifndef ZK_SCREEN_CO_MAX
+#define ZK_SCREEN_CO_MAX 4096u
+#endif
 // ZKATTEST_ONE_LANE_CHAINS (any value): every dependent chain stays in one lane (the kernels of round 5) -- the A/B switch behind profiles/r06_ab_variants.txt
-extern std::atomic<uint64_t> g_coop_chains;   // k_coop.hip: chains handed to cooperating waves by this process so far (zk_test_counter 4; tests only)
+extern std::atomic<uint64_t> g_coop_chains;   // k_coop.hip: chains handed to cooperating waves by this process so far, four per witness of a cooperative screen chunk (zk_test_counter 4; tests only)
 static inline bool zk_one_lane_chains() {
     static const bool v = getenv("ZKATTEST_ONE_LANE_CHAINS") != nullptr;
     return v;

@@ -8,7 +8,7 @@
 // per-proof signed-digit table of R (rtab.h), shared by the sec + 1 multiplications by R of one proof (43 complete additions each).
 // All additions are the complete RCB formulas the reference uses.
 #include "rtab.h"   // engine.h (and with it ktab.h), the projective table entries of rtab.h
-#include "coop_dev.h"   // the table sums of a call of a few proofs on cooperating waves (k_front_co, k_exp_commit_kt_co)
+#include "coop_sums.h"   // coop_dev.h and the table sums of a call of a few proofs on cooperating waves (k_front_co, k_exp_commit_kt_co)
 
 // (k * B through a fixed base's comb -- p256_fixed_mul, p256_fixed_mul_acc -- and the pieces of the front end's walk live in rtab.h: the witness
 // screen, k_screen.hip, takes them too)
@@ -334,66 +334,8 @@ __global__ void __launch_bounds__(256) k_exp_commit_kt_wide(DevParams P, Workspa
     st_proj(W.Tproj, t, T);
     st_proj(W.Aproj, t, p256_add(T, U));
 }
-// ---------------------------------------------------------------- a call of a few proofs: the table sums on cooperating waves (coop.h)
-// One sum = one workgroup of four waves: wave q adds the entries of a quarter of the comb's windows (and of the key table's) at 1.2 us an addition instead of
-// one lane's 5.4-8, the four partial sums meet in LDS.  Same group elements as the one-lane kernels, hence the same affine coordinates and the same bytes
-// (tests/test_gpu_prove.py: one-lane against cooperative chains, byte for byte).  ZK_UNIFORM_CF: a zero digit's addition is computed and discarded here too.
-ZK_DEV CoP256 co_add_if(bool cond, const CoP256& acc, const CoFe<ModQ, 8>& ent, const CoU32& mj) {
-    CoP256 e;
-    e.v = ent;
-#if ZK_UNIFORM_CF
-    const CoP256 s = co_p256_add(acc, e, mj);
-    CoP256 r;
-    r.v = co_pick((uint32_t)cond, s.v, acc.v);
-    return r;
-#else
-    return cond ? co_p256_add(acc, e, mj) : acc;
-#endif
-}
-// acc + (windows [w0, w0 + per) of k) * B through B's comb (rtab.h: p256_fixed_mul_range)
-ZK_DEV CoP256 co_fixed_mul_range(CoP256 acc, const uint32_t* __restrict__ tab, uint32_t kw[8], uint32_t w0, uint32_t per, const CoU32& mj) {
-#pragma unroll 1
-    for (uint32_t w = 0; w < w0; w++) shr256<PFIX_WIN_BITS>(kw);
-#pragma unroll 1
-    for (uint32_t w = w0; w < w0 + per && w < PFIX_NWIN; w++) {
-        const uint32_t d = kw[0] & (PFIX_WIN_SIZE - 1);
-        shr256<PFIX_WIN_BITS>(kw);
-        acc = co_add_if(d != 0, acc, co_load_pfix(tab + (size_t)PFIX_ENTRY_WORDS * (w * PFIX_WIN_SIZE + (d ? d : 1))), mj);
-    }
-    return acc;
-}
-// ... and through a ring key's table (ktab.h: p256_ktab_mul_range)
-ZK_DEV CoP256 co_ktab_mul_range(CoP256 acc, const uint32_t* __restrict__ kt, const uint32_t kw[8], bool neg, uint32_t w0, uint32_t per, const CoU32& mj) {
-    KeyDigits kd;
-    kd.init();
-#pragma unroll
-    for (int i = 0; i < 8; i++) kd.w[i] = kw[i];
-    uint32_t d;
-    bool dn;
-#pragma unroll 1
-    for (uint32_t w = 0; w < w0; w++) kd.next(d, dn);
-#pragma unroll 1
-    for (uint32_t w = w0; w < w0 + per && w < KTAB_NWIN; w++) {
-        kd.next(d, dn);
-        acc = co_add_if(d != 0, acc, co_load_ktab(kt + ((size_t)w * KTAB_ENT + (d ? d - 1 : 0)) * KTAB_ENTRY_WORDS, neg != dn), mj);
-    }
-    return acc;
-}
-// the sum of the four waves' points: waves 1..3 park theirs in LDS, wave 0 returns the total (the others return their own)
-ZK_DEV CoP256 co_wg4_sum(CoP256 acc, uint32_t (*part)[64], uint32_t q, const CoU32& mj) {
-    const uint32_t lane = threadIdx.x & 63u;
-    __syncthreads();   // (the buffer may still be read from the sum before)
-    if (q) part[q - 1][lane] = acc.v.v;
-    __syncthreads();
-    if (q) return acc;
-#pragma unroll 1
-    for (uint32_t k = 0; k < 3; k++) {
-        CoP256 o;
-        o.v.v = part[k][lane];
-        acc = co_p256_add(acc, o, mj);
-    }
-    return acc;
-}
+// ---------------------------------------------------------------- a call of a few proofs: the table sums on cooperating waves (coop_sums.h: co_add_if,
+// co_fixed_mul_range, co_ktab_mul_range, co_wg4_sum -- the witness screen, k_screen.hip, takes them too)
 // k_exp_commit_kt_wide's sums: workgroup t = (proof, repetition)
 __global__ void __launch_bounds__(256) k_exp_commit_kt_co(DevParams P, Workspace W, uint32_t count) {
     __shared__ uint32_t part[3][64];

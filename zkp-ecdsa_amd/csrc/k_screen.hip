@@ -11,8 +11,13 @@
 // The three ECDSA kernels are split like k_front / k_front_table / k_front_walk so that no live set exceeds 256 registers; between them the values live in
 // the witness's scratch area.  The table sums and the walk are the prover's own device functions (rtab.h, ktab.h): ZK_ADD_IF / p256_select, so the uniform
 // build has no digit-dependent skip here either.  Branches below depend on the public key, the ring and the range of (r, s) only.
+// A chunk of at most ZK_SCREEN_CO_MAX witnesses (engine.h) takes the last two on cooperating waves instead, one workgroup per witness:
+//   k_screen_table_co key-table path: four waves sum a quarter of the windows of G's comb and of the key's table each
+//   k_screen_walk_co  walk path: wave 0 builds 1..8 times pk in LDS and walks u2's digits while waves 1..3 sum u1 * G from the comb
+// Both end with the verdict of k_screen_walk, taken by one lane on the normalised rows of R.
 #include <algorithm>
 #include "rtab.h"
+#include "coop_sums.h"   // the sums and the walk of a chunk of a few witnesses on cooperating waves (k_screen_table_co, k_screen_walk_co)
 
 // a witness's scratch area: entries 0..7 = d * pk, entry 8 = u1 * G (rtab.h format), then the words below
 #define SCR_DIG (9 * RTAB_ENTRY_WORDS)   // u2's signed 4-bit digits (65 bytes)
@@ -174,6 +179,88 @@ __global__ void __launch_bounds__(64, 2) k_screen_walk(ScreenIn in, uint32_t* sc
     if (!p256_x_is_r_mod_n(R, r)) in.flags[b] |= ZK_SCREEN_SIG_INVALID;
 }
 
+// ---------------------------------------------------------------- a chunk of a few witnesses: the point arithmetic on cooperating waves (coop.h, coop_sums.h)
+// One workgroup of four waves per witness; k_screen_init / lookup / front have run as for any chunk and the workgroup reads their results from the witness's
+// area.  Same group element R as the one-lane kernels (other projective coordinates), hence the same verdict; nothing witness-derived leaves the area and LDS.
+// the verdict both paths end with (k_screen_walk's last lines): wave 0 hands the exact limbs of R's rows to its lane 0
+ZK_DEV void scr_co_verdict(const CoP256& R, uint32_t* rsum /* LDS, 64 words */, const ScreenIn& in, uint32_t b) {
+    const uint32_t lane = threadIdx.x & 63u;
+    rsum[lane] = co_normalize(R.v).v;
+    __builtin_amdgcn_wave_barrier();
+    __threadfence_block();
+    if (lane) return;
+    P256Pt Rp;
+#pragma unroll
+    for (int l = 0; l < NLIMB; l++) Rp.x.l[l] = rsum[l], Rp.y.l[l] = rsum[16 + l], Rp.z.l[l] = rsum[32 + l];
+    uint32_t rw[8];
+    load_be32(in.sig + 64 * (size_t)b, rw);
+    Fe<ModN, 1> r;   // in [1, n): k_screen_front checked the range
+    limbs_from_words<8>(r.l, rw);
+    if (!p256_x_is_r_mod_n(Rp, r)) in.flags[b] |= ZK_SCREEN_SIG_INVALID;   // R = identity: Z reduces to zero, no x-coordinate
+}
+// use 1 / 2: R = u1 G + u2 pk, wave q takes windows [4 q, 4 q + 4) of G's comb and [9 q, 9 q + 9) of the key's table (k_front_co's waves 0..3)
+__global__ void __launch_bounds__(256) k_screen_table_co(DevParams P, ScreenIn in, uint32_t* scratch) {
+    __shared__ uint32_t part[3][64];
+    __shared__ uint32_t rsum[64];
+    const uint32_t b = blockIdx.x, q = threadIdx.x >> 6;
+    const uint32_t* area = scr_area(scratch, b);
+    const uint32_t use = area[SCR_USE];
+    if (use != 1 && use != 2) return;   // (uniform for the workgroup)
+    const CoU32 mj = co_limbs(ModQ::mod);
+    uint32_t kw[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) kw[i] = area[SCR_U1 + i];
+    constexpr uint32_t gper = (PFIX_NWIN + 3) / 4, kper = (KTAB_NWIN + 3) / 4;
+    CoP256 acc = co_fixed_mul_range(co_p256_identity(), P.pfix_G, kw, q * gper, gper, mj);
+#pragma unroll
+    for (int i = 0; i < 8; i++) kw[i] = area[SCR_U2 + i];
+    acc = co_ktab_mul_range(acc, *(const uint32_t* const*)(area + SCR_KT), kw, use == 2, q * kper, kper, mj);
+    acc = co_wg4_sum(acc, part, q, mj);
+    if (q) return;
+    scr_co_verdict(acc, rsum, in, b);
+}
+// use 0: wave 0 owns the chain -- 1..8 times pk (LDS), the 65 digits of u2 --; waves 1..3 sum u1 * G from the comb meanwhile (five windows each), wave 1
+// adds the three parts up, and ONE addition joins the two behind the walk
+__global__ void __launch_bounds__(256) k_screen_walk_co(DevParams P, ScreenIn in, uint32_t* scratch) {
+    __shared__ uint32_t mult[CO_WALK_MULT_WORDS];
+    __shared__ uint32_t part[2][64];
+    __shared__ uint32_t u1g[64];
+    __shared__ uint32_t rsum[64];
+    const uint32_t b = blockIdx.x, q = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t* area = scr_area(scratch, b);
+    if (area[SCR_USE] != 0) return;   // (uniform for the workgroup)
+    const CoU32 mj = co_limbs(ModQ::mod);
+    CoP256 acc;
+    if (!q) {
+        CoP256 pk;
+        pk.v = co_load_pfix(area + SCR_PK);   // the comb entries' format: nine Montgomery limbs of x, nine of y
+        co_front_pk_multiples(mult, pk, mj);
+    } else {
+        uint32_t kw[8];
+#pragma unroll
+        for (int i = 0; i < 8; i++) kw[i] = area[SCR_U1 + i];
+        constexpr uint32_t gper = (PFIX_NWIN + 2) / 3;
+        acc = co_fixed_mul_range(co_p256_identity(), P.pfix_G, kw, (q - 1) * gper, gper, mj);
+        if (q > 1) part[q - 2][lane] = acc.v.v;
+    }
+    __syncthreads();
+    if (!q) acc = co_front_walk(mult, (const uint8_t*)(area + SCR_DIG), mj);
+    else if (q == 1) {
+#pragma unroll 1
+        for (uint32_t k = 0; k < 2; k++) {
+            CoP256 o;
+            o.v.v = part[k][lane];
+            acc = co_p256_add(acc, o, mj);
+        }
+        u1g[lane] = acc.v.v;
+    }
+    __syncthreads();
+    if (q) return;
+    CoP256 g;
+    g.v.v = u1g[lane];
+    scr_co_verdict(co_p256_add(g, acc, mj), rsum, in, b);
+}
+
 void launch_screen_init(hipStream_t s, const ScreenIn& in, uint32_t* scratch) {
     hipLaunchKernelGGL(k_screen_init, dim3((in.count + 255) / 256), dim3(256), 0, s, in, scratch);
 }
@@ -191,8 +278,14 @@ void launch_screen_lookup(hipStream_t s, const ScreenRing& G, const ScreenIn& in
 void launch_screen_front(hipStream_t s, const ScreenRing& G, const ScreenIn& in, uint32_t* scratch) {
     hipLaunchKernelGGL(k_screen_front, dim3((in.count + 63) / 64), dim3(64), 0, s, G, in, scratch);
 }
-// the point arithmetic of the whole chunk, after every ring's pass
+// the point arithmetic of the whole chunk, after every ring's pass: a chunk of a few witnesses on cooperating waves, four per witness whatever its path
 void launch_screen_ecdsa(hipStream_t s, const DevParams& P, const ScreenIn& in, uint32_t* scratch) {
+    if (in.count <= ZK_SCREEN_CO_MAX && !zk_one_lane_chains()) {
+        g_coop_chains.fetch_add((uint64_t)in.count * 4, std::memory_order_relaxed);
+        hipLaunchKernelGGL(k_screen_table_co, dim3(in.count), dim3(256), 0, s, P, in, scratch);
+        hipLaunchKernelGGL(k_screen_walk_co, dim3(in.count), dim3(256), 0, s, P, in, scratch);
+        return;
+    }
     hipLaunchKernelGGL(k_screen_table, dim3((in.count + 63) / 64), dim3(64), 0, s, P, in.count, scratch);
     hipLaunchKernelGGL(k_screen_walk, dim3((in.count + 63) / 64), dim3(64), 0, s, in, scratch);
 }

@@ -72,6 +72,21 @@ ZK_DEV void p256_fixed_mul_acc_xyzz(P256XyzzSum& s, const uint32_t* __restrict__
     }
 }
 
+// ---- the signed 4-bit digits of the ECDSA front ends' walk (below; coop_sums.h has the walk on a cooperating wave, which tests/host_arith builds for the host)
+#define FRONT_NW 65   // signed 4-bit digits of a 256-bit scalar
+ZK_DEV void front_recode(uint32_t kw[8] /*clobbered*/, uint8_t* dig /*[FRONT_NW]: |d| in 0..8, bit 7 = negative*/) {
+    uint32_t carry = 0;
+#pragma unroll 1
+    for (uint32_t w = 0; w < FRONT_NW; w++) {
+        uint32_t d = (kw[0] & 15) + carry;
+        shr256<4>(kw);
+        bool neg = d > 8;
+        carry = neg ? 1 : 0;
+        if (neg) d = 16 - d;
+        dig[w] = (uint8_t)(d | (neg ? 0x80u : 0u));
+    }
+}
+
 #if !defined(ZK_HOST_BUILD)
 ZK_DEV P256Pt ld_rtab(const uint32_t* e) {
     const uint4* q = (const uint4*)e;
@@ -167,19 +182,6 @@ ZK_DEV P256Pt p256_shfl_xor(const P256Pt& a, int m) {
 }
 // ---- k * P for a point without a table of its own, as the ECDSA front ends take u2 * pk (k_p256.hip: k_front*; k_screen.hip): signed 4-bit digits, the
 // multiples 1..8 of P in the first eight entries of a scratch area (rtab.h entry format), 65 windows of four doublings and one addition
-#define FRONT_NW 65   // signed 4-bit digits of a 256-bit scalar
-ZK_DEV void front_recode(uint32_t kw[8] /*clobbered*/, uint8_t* dig /*[FRONT_NW]: |d| in 0..8, bit 7 = negative*/) {
-    uint32_t carry = 0;
-#pragma unroll 1
-    for (uint32_t w = 0; w < FRONT_NW; w++) {
-        uint32_t d = (kw[0] & 15) + carry;
-        shr256<4>(kw);
-        bool neg = d > 8;
-        carry = neg ? 1 : 0;
-        if (neg) d = 16 - d;
-        dig[w] = (uint8_t)(d | (neg ? 0x80u : 0u));
-    }
-}
 ZK_DEV void front_pk_multiples(uint32_t* area, const P256Aff& pk) {
     P256Pt base = p256_from_affine(pk), m = base;
     st_rtab(area, m);
