@@ -76,6 +76,39 @@ column_table(30, 2 * n30, 2 * n30, 'both operands raw sums')
 column_table(29, n29, n29, 'both normalised')
 column_table(29, 2 * n29, 2 * n29, 'both operands raw sums')
 column_table(29, 3 * n29, 2 * n29, 'raw a + C t - b  x  raw sum')
+print('(1q) the same column budget for the P-256 field prime q, whose reduction multiplies by the limbs of q + 1 (field.h: redc_limbs): fewer terms, smaller columns')
+q = int(F['groups']['p256']['constants'][0], 16) if 'p256' in F['groups'] else 0xffffffff00000001000000000000000000000000ffffffffffffffffffffffff
+assert q == 2 ** 256 - 2 ** 224 + 2 ** 192 + 2 ** 96 - 1
+
+
+def column_q(red, note):
+    """worst column of a ModQ product, operands with limbs 0..7 full and the top limbs of 512 q and 32 q (kmax = 16384), every quotient digit 2^30 - 1;
+    red: the limbs the digits are multiplied by (q: the generic reduction; q + 1: the digit is dropped from its own column, which only clears bits)"""
+    n, bits = 9, 30
+    full = (1 << bits) - 1
+    a = [full] * (n - 1) + [(512 * q) >> (bits * (n - 1))]
+    b = [full] * (n - 1) + [(32 * q) >> (bits * (n - 1))]
+    worst, where, carry, terms = 0, 0, 0, 0
+    for k in range(2 * n - 1):
+        s = carry
+        for i in range(n):
+            j = k - i
+            if 0 <= j < n:
+                s += a[i] * b[j]
+                if red[j]:
+                    s += full * red[j]
+                    terms += 1
+        if s > worst:
+            worst, where = s, k
+        carry = s >> bits
+    print('  radix 2^30, reduction by %-24s %2d multiply-adds, worst column %2d: 2^%.3f  -> %s'
+          % (note + ':', terms, where, __import__('math').log2(worst), 'fits 64 bits' if worst < (1 << 64) else 'OVERFLOWS'))
+    return worst
+
+
+w_old = column_q(limbs(q, 30, 9), 'q (7 limbs not zero)')
+w_new = column_q(limbs(q + 1, 30, 9), 'q + 1 (4 limbs not zero)')
+assert w_new <= w_old < 1 << 64
 print('(2) magnitude budget kappa = R / t')
 for bits in (30, 29):
     R = 1 << (bits * 9)

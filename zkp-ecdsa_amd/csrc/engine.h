@@ -597,34 +597,7 @@ ZK_DEV void limbs_repack(uint32_t* out, const uint32_t* in) {
             buf >>= OUT_BITS;
         }
 }
-// Montgomery reduction of an 18-limb radix-2^30 integer T < q * 2^270: returns T / 2^270 mod q, < 2q.
-ZK_DEV Fe<ModQ, 2> redc_wide(const uint32_t T[2 * NLIMB]) {
-    uint64_t acc = 0;
-    uint32_t m[NLIMB];
-    Fe<ModQ, 2> r;
-#pragma unroll
-    for (int k = 0; k < NLIMB; k++) {
-        acc += T[k];
-#pragma unroll
-        for (int i = 0; i < k; i++) acc = mad64(m[i], ModQ::mod[k - i], acc);
-        m[k] = ((uint32_t)acc * ModQ::n0) & LIMB_MASK;
-        acc = mad64(m[k], ModQ::mod[0], acc);
-        acc >>= LIMB_BITS;
-    }
-#pragma unroll
-    for (int k = NLIMB; k < 2 * NLIMB; k++) {
-        acc += T[k];
-#pragma unroll
-        for (int i = k - (NLIMB - 1); i < NLIMB; i++) acc = mad64(m[i], ModQ::mod[k - i], acc);
-        if (k < 2 * NLIMB - 1) {
-            r.l[k - NLIMB] = (uint32_t)acc & LIMB_MASK;
-            acc >>= LIMB_BITS;
-        } else {
-            r.l[NLIMB - 1] = (uint32_t)acc;
-        }
-    }
-    return r;
-}
+// (redc_wide, the Montgomery reduction of such an 18-limb integer: field.h)
 
 // list B is item-fastest: slot k of item i lives at k * items_cap + i (coalesced for every per-item kernel)
 ZK_DEV uint32_t lbi(const Workspace& W, uint32_t item, uint32_t k) { return k * W.items_cap + item; }

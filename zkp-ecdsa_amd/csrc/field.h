@@ -138,14 +138,52 @@ ZK_DEV Fe<M, 2 * Ka> fe_dbl(const Fe<M, Ka>& a) {
 #ifndef ZK_LAUNDER_MOD
 #define ZK_LAUNDER_MOD 1
 #endif
+//
+// What a reduction multiplies the quotient digits by.  Generic modulus: the limbs of M.  A modulus whose low limb is all ones (M::low_ones, i.e. n0 = 1: the P-256
+// field prime q = 2^96 - 1 mod 2^120): m_k * M = m_k * (M + 1) - m_k, and m_k IS the low 30 bits of column k, so subtracting it there just clears them -- the column's
+// carry is acc >> 30 whether they were cleared or not, no instruction.  What is left to add is m_k times the limbs of M + 1, of which q + 1 has four that are not zero
+// ({0, 0, 0, 2^6, 0, 0, 2^12, 2^30 - 2^14, 2^16 - 1}): 36 multiply-adds per product instead of 63.  Same quotient digits, same integer a b + m M, so the same result
+// limbs (limbs 0..7 of the result are masked to 30 bits and the top limb is the rest: the integer fixes them); every column only loses terms, so the 64-bit column bound
+// of tools/radix_budget.py holds as before.  The limbs stay opaque v_mad_u64_u32 operands: this drops terms, it does not rewrite a multiply-add as shifts.
 template <class M>
-ZK_DEV void mod_limbs(uint32_t md[NLIMB]) {
+ZK_DEV constexpr uint32_t redc_limb(int j) {
+    if constexpr (M::low_ones) return M::modp1[j];
+    else return M::mod[j];
+}
+// term j of a reduction is there at all?  (Generic moduli keep every term, zero limbs too, exactly as they were compiled before.)
+template <class M>
+ZK_DEV constexpr bool redc_term(int j) {
+    if constexpr (M::low_ones) return M::modp1[j] != 0;
+    else return true;
+}
+template <class M>
+ZK_DEV void redc_limbs(uint32_t md[NLIMB]) {
 #pragma unroll
     for (int i = 0; i < NLIMB; i++) {
-        md[i] = M::mod[i];
+        md[i] = redc_limb<M>(i);
 #if ZK_LAUNDER_MOD
-        if (M::mod[i] != 0) asm("" : "+s"(md[i]));
+        if (redc_limb<M>(i) != 0) asm("" : "+s"(md[i]));
 #endif
+    }
+}
+// the quotient digit of column k, and the column without its low limb
+template <class M>
+ZK_DEV uint32_t redc_digit(uint64_t& acc, const uint32_t md[NLIMB]) {
+    if constexpr (M::low_ones) {
+        uint32_t m = (uint32_t)acc & LIMB_MASK;
+        acc >>= LIMB_BITS;
+#if !defined(ZK_HOST_BUILD)
+        // Digit and carry opaque (empty asm, no instruction).  The generic form hides them behind the m * M_0 multiply-add; seen through, the optimiser starts the
+        // columns of a product computed alone side by side and small kernels grow by ~28 VGPRs (k_keys_to_ints 52 -> 80, k_v_validate 44 -> 72: a wave per SIMD
+        // or two), for 3 VALU instructions fewer per kernel.  With the pin they keep the registers they had.
+        asm("" : "+v"(acc), "+v"(m));
+#endif
+        return m;
+    } else {
+        const uint32_t m = ((uint32_t)acc * M::n0) & LIMB_MASK;
+        acc = mad64(m, md[0], acc);
+        acc >>= LIMB_BITS;
+        return m;
     }
 }
 #ifndef ZK_PIN_LIMBS32
@@ -185,23 +223,23 @@ template <class M>
 ZK_DEV void limbs_mont_mul(uint32_t out[NLIMB], const uint32_t a[NLIMB], const uint32_t b[NLIMB]) {
     uint64_t acc = 0;
     uint32_t m[NLIMB], md[NLIMB];
-    mod_limbs<M>(md);
+    redc_limbs<M>(md);
 #pragma unroll
     for (int k = 0; k < NLIMB; k++) {
 #pragma unroll
         for (int i = 0; i <= k; i++) acc = mad64(a[i], b[k - i], acc);
 #pragma unroll
-        for (int i = 0; i < k; i++) acc = mad64(m[i], md[k - i], acc);
-        m[k] = ((uint32_t)acc * M::n0) & LIMB_MASK;
-        acc = mad64(m[k], md[0], acc);
-        acc >>= LIMB_BITS;
+        for (int i = 0; i < k; i++)
+            if (redc_term<M>(k - i)) acc = mad64(m[i], md[k - i], acc);
+        m[k] = redc_digit<M>(acc, md);
     }
 #pragma unroll
     for (int k = NLIMB; k < 2 * NLIMB - 1; k++) {
 #pragma unroll
         for (int i = k - (NLIMB - 1); i < NLIMB; i++) acc = mad64(a[i], b[k - i], acc);
 #pragma unroll
-        for (int i = k - (NLIMB - 1); i < NLIMB; i++) acc = mad64(m[i], md[k - i], acc);
+        for (int i = k - (NLIMB - 1); i < NLIMB; i++)
+            if (redc_term<M>(k - i)) acc = mad64(m[i], md[k - i], acc);
         out[k - NLIMB] = (uint32_t)acc & LIMB_MASK;
         acc >>= LIMB_BITS;
     }
@@ -221,7 +259,7 @@ template <class M, int NP>
 ZK_DEV void limbs_mont_mul_n(uint32_t (&out)[NP][NLIMB], const uint32_t (&a)[NP][NLIMB], const uint32_t (&b)[NP][NLIMB]) {
     uint64_t acc[NP];
     uint32_t m[NP][NLIMB], md[NLIMB];
-    mod_limbs<M>(md);
+    redc_limbs<M>(md);
 #pragma unroll
     for (int p = 0; p < NP; p++) acc[p] = 0;
 #pragma unroll
@@ -233,11 +271,17 @@ ZK_DEV void limbs_mont_mul_n(uint32_t (&out)[NP][NLIMB], const uint32_t (&a)[NP]
 #pragma unroll
         for (int i = 0; i < k; i++)
 #pragma unroll
-            for (int p = 0; p < NP; p++) acc[p] = mad64c(m[p][i], md[k - i], acc[p]);
+            for (int p = 0; p < NP; p++)
+                if (redc_term<M>(k - i)) acc[p] = mad64c(m[p][i], md[k - i], acc[p]);
+        if constexpr (M::low_ones) {
 #pragma unroll
-        for (int p = 0; p < NP; p++) m[p][k] = ((uint32_t)acc[p] * M::n0) & LIMB_MASK;
+            for (int p = 0; p < NP; p++) m[p][k] = (uint32_t)acc[p] & LIMB_MASK;
+        } else {
 #pragma unroll
-        for (int p = 0; p < NP; p++) acc[p] = mad64c(m[p][k], md[0], acc[p]);
+            for (int p = 0; p < NP; p++) m[p][k] = ((uint32_t)acc[p] * M::n0) & LIMB_MASK;
+#pragma unroll
+            for (int p = 0; p < NP; p++) acc[p] = mad64c(m[p][k], md[0], acc[p]);
+        }
 #pragma unroll
         for (int p = 0; p < NP; p++) acc[p] >>= LIMB_BITS;
     }
@@ -250,7 +294,8 @@ ZK_DEV void limbs_mont_mul_n(uint32_t (&out)[NP][NLIMB], const uint32_t (&a)[NP]
 #pragma unroll
         for (int i = k - (NLIMB - 1); i < NLIMB; i++)
 #pragma unroll
-            for (int p = 0; p < NP; p++) acc[p] = mad64c(m[p][i], md[k - i], acc[p]);
+            for (int p = 0; p < NP; p++)
+                if (redc_term<M>(k - i)) acc[p] = mad64c(m[p][i], md[k - i], acc[p]);
 #pragma unroll
         for (int p = 0; p < NP; p++) out[p][k - NLIMB] = (uint32_t)acc[p] & LIMB_MASK;
 #pragma unroll
@@ -282,7 +327,7 @@ template <class M>
 ZK_DEV void limbs_mont_sqr(uint32_t out[NLIMB], const uint32_t a[NLIMB]) {
     uint64_t acc = 0;
     uint32_t m[NLIMB], md[NLIMB], a2[NLIMB];
-    mod_limbs<M>(md);
+    redc_limbs<M>(md);
 #pragma unroll
     for (int i = 0; i < NLIMB; i++) a2[i] = a[i] << 1;
 #pragma unroll
@@ -291,10 +336,9 @@ ZK_DEV void limbs_mont_sqr(uint32_t out[NLIMB], const uint32_t a[NLIMB]) {
         for (int i = 0; 2 * i < k; i++) acc = mad64(a2[i], a[k - i], acc);
         if (k % 2 == 0) acc = mad64(a[k / 2], a[k / 2], acc);
 #pragma unroll
-        for (int i = 0; i < k; i++) acc = mad64(m[i], md[k - i], acc);
-        m[k] = ((uint32_t)acc * M::n0) & LIMB_MASK;
-        acc = mad64(m[k], md[0], acc);
-        acc >>= LIMB_BITS;
+        for (int i = 0; i < k; i++)
+            if (redc_term<M>(k - i)) acc = mad64(m[i], md[k - i], acc);
+        m[k] = redc_digit<M>(acc, md);
     }
 #pragma unroll
     for (int k = NLIMB; k < 2 * NLIMB - 1; k++) {
@@ -302,7 +346,8 @@ ZK_DEV void limbs_mont_sqr(uint32_t out[NLIMB], const uint32_t a[NLIMB]) {
         for (int i = k - (NLIMB - 1); 2 * i < k; i++) acc = mad64(a2[i], a[k - i], acc);
         if (k % 2 == 0) acc = mad64(a[k / 2], a[k / 2], acc);
 #pragma unroll
-        for (int i = k - (NLIMB - 1); i < NLIMB; i++) acc = mad64(m[i], md[k - i], acc);
+        for (int i = k - (NLIMB - 1); i < NLIMB; i++)
+            if (redc_term<M>(k - i)) acc = mad64(m[i], md[k - i], acc);
         out[k - NLIMB] = (uint32_t)acc & LIMB_MASK;
         acc >>= LIMB_BITS;
     }
@@ -321,6 +366,50 @@ ZK_DEV Fe<M, 2> fe_sqr(const Fe<M, Ka>& a) {
 #pragma unroll
     for (int i = 0; i < NLIMB; i++) r.l[i] = o[i];
     return r;
+}
+// Montgomery reduction of NJ 18-limb radix-2^30 integers T < M * 2^270 in lock-step (the ring fold's exact column sums, k_gk.hip / k_gk_mfma.hip): T / 2^270 mod M, < 2M.
+// The reduction half of limbs_mont_mul with the limbs of T in place of the partial products.
+template <int NJ, class M = ModQ>
+ZK_DEV void redc_wide_n(const uint32_t (&T)[NJ][2 * NLIMB], Fe<M, 2> (&r)[NJ]) {
+    uint64_t a[NJ] = {};
+    uint32_t m[NJ][NLIMB], md[NLIMB];
+    redc_limbs<M>(md);
+#pragma unroll
+    for (int k = 0; k < NLIMB; k++) {
+#pragma unroll
+        for (int j = 0; j < NJ; j++) a[j] += T[j][k];
+#pragma unroll
+        for (int i = 0; i < k; i++)
+#pragma unroll
+            for (int j = 0; j < NJ; j++)
+                if (redc_term<M>(k - i)) a[j] = mad64(m[j][i], md[k - i], a[j]);
+#pragma unroll
+        for (int j = 0; j < NJ; j++) m[j][k] = redc_digit<M>(a[j], md);
+    }
+#pragma unroll
+    for (int k = NLIMB; k < 2 * NLIMB; k++) {
+#pragma unroll
+        for (int j = 0; j < NJ; j++) a[j] += T[j][k];
+#pragma unroll
+        for (int i = k - (NLIMB - 1); i < NLIMB; i++)
+#pragma unroll
+            for (int j = 0; j < NJ; j++)
+                if (redc_term<M>(k - i)) a[j] = mad64(m[j][i], md[k - i], a[j]);
+#pragma unroll
+        for (int j = 0; j < NJ; j++) {
+            if (k < 2 * NLIMB - 1) r[j].l[k - NLIMB] = (uint32_t)a[j] & LIMB_MASK, a[j] >>= LIMB_BITS;
+            else r[j].l[NLIMB - 1] = (uint32_t)a[j];
+        }
+    }
+}
+template <class M = ModQ>
+ZK_DEV Fe<M, 2> redc_wide(const uint32_t T[2 * NLIMB]) {
+    uint32_t t[1][2 * NLIMB];
+    Fe<M, 2> r[1];
+#pragma unroll
+    for (int k = 0; k < 2 * NLIMB; k++) t[0][k] = T[k];
+    redc_wide_n<1, M>(t, r);
+    return r[0];
 }
 // r_i = a_i * b_i for independent products: BATCH = true computes them in lock-step (limbs_mont_mul_n: fewer instructions, more
 // live registers), false one after the other.  A translation unit picks per curve (ZK_BATCH_TOM / ZK_BATCH_P256, curve.h): the
@@ -508,7 +597,7 @@ template <class M>
 ZK_DEV void limbs_mont_mul_rows(uint32_t out[NLIMB], const uint32_t a[NLIMB], const uint32_t b[NLIMB]) {
     uint64_t T[2 * NLIMB];
     uint32_t md[NLIMB];
-    mod_limbs<M>(md);
+    redc_limbs<M>(md);
 #pragma unroll
     for (int k = 0; k < 2 * NLIMB; k++) T[k] = 0;
 #pragma unroll
@@ -516,9 +605,10 @@ ZK_DEV void limbs_mont_mul_rows(uint32_t out[NLIMB], const uint32_t a[NLIMB], co
 #pragma unroll
         for (int j = 0; j < NLIMB; j++) T[i + j] = mad64(a[i], b[j], T[i + j]);
         if (i > 0) T[i] += T[i - 1] >> LIMB_BITS;   // column i is complete now: every a_r b_(i-r), every m_r M_(i-r) with r < i, the carry
-        const uint32_t m = ((uint32_t)T[i] * M::n0) & LIMB_MASK;
+        const uint32_t m = ((uint32_t)T[i] * M::n0) & LIMB_MASK;   // n0 = 1 with M::low_ones: no multiplication
 #pragma unroll
-        for (int j = 0; j < NLIMB; j++) T[i + j] = mad64(m, md[j], T[i + j]);
+        for (int j = 0; j < NLIMB; j++)   // M::low_ones: no term 0 -- only T[i] >> 30 is read from column i again
+            if (redc_term<M>(j)) T[i + j] = mad64(m, md[j], T[i + j]);
     }
     uint64_t carry = T[NLIMB - 1] >> LIMB_BITS;
 #pragma unroll

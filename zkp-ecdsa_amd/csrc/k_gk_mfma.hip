@@ -193,40 +193,6 @@ ZK_DEV void gkm_recombine_n(const int32_t (&D)[NJ][GKM_NDIAG], uint32_t (&t30)[N
             for (int j = 0; j < NJ; j++) t30[j][kk] = (uint32_t)buf[j] & LIMB_MASK, buf[j] >>= 30;
         }
 }
-template <int NJ>
-ZK_DEV void redc_wide_n(const uint32_t (&T)[NJ][18], Fe<ModQ, 2> (&r)[NJ]) {   // redc_wide (engine.h), NJ values in lock step
-    uint64_t a[NJ] = {};
-    uint32_t m[NJ][NLIMB];
-#pragma unroll
-    for (int k = 0; k < NLIMB; k++) {
-#pragma unroll
-        for (int j = 0; j < NJ; j++) a[j] += T[j][k];
-#pragma unroll
-        for (int i = 0; i < k; i++)
-#pragma unroll
-            for (int j = 0; j < NJ; j++) a[j] = mad64(m[j][i], ModQ::mod[k - i], a[j]);
-#pragma unroll
-        for (int j = 0; j < NJ; j++) {
-            m[j][k] = ((uint32_t)a[j] * ModQ::n0) & LIMB_MASK;
-            a[j] = mad64(m[j][k], ModQ::mod[0], a[j]);
-            a[j] >>= LIMB_BITS;
-        }
-    }
-#pragma unroll
-    for (int k = NLIMB; k < 2 * NLIMB; k++) {
-#pragma unroll
-        for (int j = 0; j < NJ; j++) a[j] += T[j][k];
-#pragma unroll
-        for (int i = k - (NLIMB - 1); i < NLIMB; i++)
-#pragma unroll
-            for (int j = 0; j < NJ; j++) a[j] = mad64(m[j][i], ModQ::mod[k - i], a[j]);
-#pragma unroll
-        for (int j = 0; j < NJ; j++) {
-            if (k < 2 * NLIMB - 1) r[j].l[k - NLIMB] = (uint32_t)a[j] & LIMB_MASK, a[j] >>= LIMB_BITS;
-            else r[j].l[NLIMB - 1] = (uint32_t)a[j];
-        }
-    }
-}
 __global__ void __launch_bounds__(256, 1) k_v_gk_block_mfma(uint32_t count, const int8_t* __restrict__ afrag, const int8_t* __restrict__ bfrag, uint32_t nblocks, uint32_t nkc, Soa res) {
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t tiles_p = (count + 15) >> 4, tiles_b = nblocks >> 4;
