@@ -20,7 +20,7 @@
 //   sub2     T0..T3 (Kb, Kc) = (1,1) (2,1) (3,4) (127,128) with Ka = KCAP - C(Kb + Kc)
 //   unary    U0..U7 K = 1, 2, 4, 16, 64, 128, 256, 512
 // One-lane ops: 0 a * b   1 fe_sqr(x), x = a if Ka^2 <= kmax else b   2/3 fe_mul2<false/true> (a b, a c)   4/5 fe_mul3 (+ c b)   6/7 fe_mul4 (+ b a)
-//   8 fe_mul_rows (class P1)   9 limbs_mont_mul_rows on the raw limbs   10 a + b (sum)   11 a - b (sub)   12 fe_sub2(a, b, c) (sub2)   13 fe_neg(b) (sub)
+//   8 a * b on Fe<M, 2> (class P1)   9 limbs_mont_mul_rows on the raw limbs   10 a + b (sum)   11 a - b (sub)   12 fe_sub2(a, b, c) (sub2)   13 fe_neg(b) (sub)
 //   14 fe_dbl (unary, K <= 256)   15 fe_reduce (unary)   16 fe_canon (U0..U2)   17 fe_is_zero (unary)   18 fe_eq(a, b) (sub)
 //   19/20 fe_inv_gcd<M, false/true> (U1)   21 fe_inv_fermat (U1)
 // Cooperative ops: 0 co_mul (product)   1 co_add (sum)   2 co_sub (sub)   3 co_addsub, a - b in rows 1, 2 (sub)   4 co_addsub, a - b in rows 0, 3 (sub)
@@ -72,7 +72,7 @@ ZK_DEV void rl_one(const uint32_t* in, uint32_t* out) {
         fe_mul4<BATCH>(r0, r1, r2, r3, rl_ld<M, Ka>(pa), rl_ld<M, Kb>(pb), rl_ld<M, Ka>(pa), rl_ld<M, Kc>(pc), rl_ld<M, Kc>(pc), rl_ld<M, Kb>(pb), rl_ld<M, Kb>(pb),
                        rl_ld<M, Ka>(pa));
         rl_st(out, r0), rl_st(out + NLIMB, r1), rl_st(out + 2 * NLIMB, r2), rl_st(out + 3 * NLIMB, r3);
-    } else if constexpr (OP == 8) rl_st(out, fe_mul_rows(rl_ld<M, 2>(pa), rl_ld<M, 2>(pb)));
+    } else if constexpr (OP == 8) rl_st(out, rl_ld<M, 2>(pa) * rl_ld<M, 2>(pb));
     else if constexpr (OP == 9) {
         static_assert((long)Ka * Kb <= M::kmax, "Montgomery input magnitudes too large");
         Fe<M, 2> r;

@@ -23,9 +23,6 @@ struct CombDigits {
         neg = sgn && d > half;
         carry = neg ? 1u : 0u;
         idx = neg ? (mask + 1) - d : d;
-#ifdef ZK_DEBUG_IDX_MASK  // timing experiments only (wrong results): confine the gathers to the first entries of each window
-        idx &= ZK_DEBUG_IDX_MASK;
-#endif
     }
 };
 

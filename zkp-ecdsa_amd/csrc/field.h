@@ -38,27 +38,13 @@ struct Fe {
     }
 };
 
-// ZK_PAR_CARRY=1 (experiment, per translation unit): ONE parallel carry step instead of the ripple -- every limb hands its excess
-// to its neighbour at once, so the eight steps do not depend on each other.  The result is "nearly normalised" (limbs <= 2^30 + 2
-// after a difference of three operands): fine as a product operand (the column bound of tools/radix_budget.py moves by 2^-28) and as
-// an operand of another sum, NOT for fe_canon / comparisons -- only translation units that canonicalise product outputs may use it.
-#ifndef ZK_PAR_CARRY
-#define ZK_PAR_CARRY 0
-#endif
+// The carry sweep of every sum: a ripple, so every limb below the top one comes out < 2^30 (fe_canon and the comparisons need exactly that).
 ZK_DEV void limbs_normalize(uint32_t r[NLIMB]) {
-#if ZK_PAR_CARRY
-    uint32_t c[NLIMB - 1];
-#pragma unroll
-    for (int i = 0; i < NLIMB - 1; i++) c[i] = r[i] >> LIMB_BITS, r[i] &= LIMB_MASK;
-#pragma unroll
-    for (int i = 0; i < NLIMB - 1; i++) r[i + 1] += c[i];
-#else
 #pragma unroll
     for (int i = 0; i < NLIMB - 1; i++) {
         r[i + 1] += r[i] >> LIMB_BITS;
         r[i] &= LIMB_MASK;
     }
-#endif
 }
 
 template <class M, int Ka, int Kb>
@@ -134,10 +120,7 @@ ZK_DEV Fe<M, 2 * Ka> fe_dbl(const Fe<M, Ka>& a) {
 
 // Modulus limb i as an SGPR operand the optimiser cannot see through: left to itself the compiler strength-reduces
 // m * (2^a - 2^b) into 64-bit shift/add/sub sequences that cost more VALU issue slots than the one v_mad_u64_u32
-// they replace (ZK_LAUNDER_MOD=0 keeps the compiler's choice).  Zero limbs stay compile-time zeros (no instruction).
-#ifndef ZK_LAUNDER_MOD
-#define ZK_LAUNDER_MOD 1
-#endif
+// they replace.  Zero limbs stay compile-time zeros (no instruction).
 //
 // What a reduction multiplies the quotient digits by.  Generic modulus: the limbs of M.  A modulus whose low limb is all ones (M::low_ones, i.e. n0 = 1: the P-256
 // field prime q = 2^96 - 1 mod 2^120): m_k * M = m_k * (M + 1) - m_k, and m_k IS the low 30 bits of column k, so subtracting it there just clears them -- the column's
@@ -161,9 +144,7 @@ ZK_DEV void redc_limbs(uint32_t md[NLIMB]) {
 #pragma unroll
     for (int i = 0; i < NLIMB; i++) {
         md[i] = redc_limb<M>(i);
-#if ZK_LAUNDER_MOD
-        if (redc_limb<M>(i) != 0) asm("" : "+s"(md[i]));
-#endif
+        if (redc_limb<M>(i) != 0) zk_opaque_s(md[i]);
     }
 }
 // the quotient digit of column k, and the column without its low limb
@@ -172,12 +153,10 @@ ZK_DEV uint32_t redc_digit(uint64_t& acc, const uint32_t md[NLIMB]) {
     if constexpr (M::low_ones) {
         uint32_t m = (uint32_t)acc & LIMB_MASK;
         acc >>= LIMB_BITS;
-#if !defined(ZK_HOST_BUILD)
-        // Digit and carry opaque (empty asm, no instruction).  The generic form hides them behind the m * M_0 multiply-add; seen through, the optimiser starts the
+        // Digit and carry opaque (no instruction).  The generic form hides them behind the m * M_0 multiply-add; seen through, the optimiser starts the
         // columns of a product computed alone side by side and small kernels grow by ~28 VGPRs (k_keys_to_ints 52 -> 80, k_v_validate 44 -> 72: a wave per SIMD
         // or two), for 3 VALU instructions fewer per kernel.  With the pin they keep the registers they had.
-        asm("" : "+v"(acc), "+v"(m));
-#endif
+        zk_opaque_v(acc, m);
         return m;
     } else {
         const uint32_t m = ((uint32_t)acc * M::n0) & LIMB_MASK;
@@ -186,9 +165,6 @@ ZK_DEV uint32_t redc_digit(uint64_t& acc, const uint32_t md[NLIMB]) {
         return m;
     }
 }
-#ifndef ZK_PIN_LIMBS32
-#define ZK_PIN_LIMBS32 1
-#endif
 // A product computed ALONE: the optimiser starts every column in a fresh accumulator while the previous column is being
 // finished (m_k * M_0, shift) and joins the two with a 64-bit add -- it shortens the dependent chain (a dependent
 // v_mad_u64_u32 issues every 15.6 cycles, an independent one every 4.2) at the price of 16 extra VALU instructions per product,
@@ -196,26 +172,10 @@ ZK_DEV uint32_t redc_digit(uint64_t& acc, const uint32_t md[NLIMB]) {
 // and second half, the pairs of the P-256 laws) limbs_mont_mul_n below runs them in lock-step instead: every product is ONE
 // dependent chain (mad64c hides the sums from the reassociation pass), consecutive instructions belong to different products,
 // so the latency is covered by the other chains and the joins disappear: 212 -> 196 VALU instructions per product.
-#ifndef ZK_SINGLE_CHAIN
-#define ZK_SINGLE_CHAIN 1
-#endif
-// ZK_MAD_VOLATILE=1 (experiment, per translation unit): the empty asm statements of mad64c are volatile, so the machine scheduler may not move one chain's multiply-adds
-// past another's.  Without it the scheduler sometimes strings a product's whole chain together to get registers back: the FIRST table walk of k_exp_commit_kt has 1 046
-// hazard nops per loop body against ~200 in the two walks behind it, k_msm_bucket 592 at 96 VGPRs against 153 at 128.  Measured, same box (profiles/r06_ab_variants.txt (8)):
-// no gain -- at three to five waves per SIMD the other waves cover a serialised chain (p256_exp_commit 29.2 -> 29.2 ms, bucket sums 17.6 -> 16.9 ms but the P-256 pass beside
-// them 9.5 -> 10.7).  Default off.
-#ifndef ZK_MAD_VOLATILE
-#define ZK_MAD_VOLATILE 0
-#endif
+// The statement is not volatile: the machine scheduler may still move one chain's multiply-adds past another's, and the other waves cover what that costs.
 ZK_DEV uint64_t mad64c(uint32_t a, uint32_t b, uint64_t c) {
     uint64_t r = (uint64_t)a * b + c;
-#if ZK_SINGLE_CHAIN && !defined(ZK_HOST_BUILD)
-#if ZK_MAD_VOLATILE
-    asm volatile("" : "+v"(r));   // ... and, volatile, it keeps its place among the other chains' sums: the lock-step order of the source IS the schedule
-#else
-    asm("" : "+v"(r));   // no instruction: the sum is opaque to the reassociation pass
-#endif
-#endif
+    zk_opaque_v(r);   // no instruction: the sum is opaque to the reassociation pass
     return r;
 }
 // Montgomery product, product-scanning with a single 64-bit accumulator (no carry flags).
@@ -244,14 +204,12 @@ ZK_DEV void limbs_mont_mul(uint32_t out[NLIMB], const uint32_t a[NLIMB], const u
         acc >>= LIMB_BITS;
     }
     out[NLIMB - 1] = (uint32_t)acc;
-#if ZK_PIN_LIMBS32
-    // Keep every result limb a 32-bit VGPR value (empty asm, no instruction).  Without this the optimiser carries some
+    // Keep every result limb a 32-bit VGPR value (no instruction).  Without this the optimiser carries some
     // products across basic blocks as the 64-bit (acc & mask) they were truncated from; instruction selection works per
     // block, cannot prove the high halves zero there, and multiplies them as 64 x 32 bits: +72 v_mad_u64_u32 and
-    // +144 v_mov_b32 per table addition in k_tom_commit's loop (ISA inspection; ZK_PIN_LIMBS32=0 shows the old code).
+    // +144 v_mov_b32 per table addition in k_tom_commit's loop (ISA inspection).
 #pragma unroll
-    for (int i = 0; i < NLIMB; i++) asm("" : "+v"(out[i]));
-#endif
+    for (int i = 0; i < NLIMB; i++) zk_opaque_v(out[i]);
 }
 // NP independent Montgomery products in lock-step (see the note above mad64c).  Row-interleaved: column k of every product
 // advances by one multiply-add per row, so a product's own chain is touched every NP-th instruction.
@@ -303,12 +261,10 @@ ZK_DEV void limbs_mont_mul_n(uint32_t (&out)[NP][NLIMB], const uint32_t (&a)[NP]
     }
 #pragma unroll
     for (int p = 0; p < NP; p++) out[p][NLIMB - 1] = (uint32_t)acc[p];
-#if ZK_PIN_LIMBS32
 #pragma unroll
     for (int p = 0; p < NP; p++)
 #pragma unroll
-        for (int i = 0; i < NLIMB; i++) asm("" : "+v"(out[p][i]));
-#endif
+        for (int i = 0; i < NLIMB; i++) zk_opaque_v(out[p][i]);   // 32-bit result limbs, as in limbs_mont_mul
 }
 template <class M, int Ka, int Kb>
 ZK_DEV Fe<M, 2> operator*(const Fe<M, Ka>& a, const Fe<M, Kb>& b) {
@@ -352,10 +308,8 @@ ZK_DEV void limbs_mont_sqr(uint32_t out[NLIMB], const uint32_t a[NLIMB]) {
         acc >>= LIMB_BITS;
     }
     out[NLIMB - 1] = (uint32_t)acc;
-#if ZK_PIN_LIMBS32
 #pragma unroll
-    for (int i = 0; i < NLIMB; i++) asm("" : "+v"(out[i]));
-#endif
+    for (int i = 0; i < NLIMB; i++) zk_opaque_v(out[i]);   // 32-bit result limbs, as in limbs_mont_mul
 }
 template <class M, int Ka>
 ZK_DEV Fe<M, 2> fe_sqr(const Fe<M, Ka>& a) {
@@ -588,11 +542,9 @@ ZK_DEV Fe<M, K> fe_select(bool c, const Fe<M, K>& a, const Fe<M, K>& b) {  // c 
     return r;
 }
 
-// Montgomery product for the places where ONE thread multiplies while everybody else waits for it (the Fermat inversions: thread 0 of a
-// normaliser workgroup, the front end's one thread per proof): operand-scanning, one 64-bit accumulator PER COLUMN, so the nine
-// multiply-adds of a row are independent of each other and issue back to back (4.2 cycles each) instead of one behind the other
-// (15.8 cycles, profiles/r03_valu_peak_microbench.txt).  The column sums are those of limbs_mont_mul -- the same partial products and
-// carries, added in another order -- so the result limbs are identical.  Eighteen live accumulators: not for kernels short of registers.
+// Montgomery product, operand-scanning: one 64-bit accumulator PER COLUMN, a row of nine independent multiply-adds at a time.  The column sums are those
+// of limbs_mont_mul -- the same partial products and carries, added in another order -- so the result limbs are identical.  No kernel of the engine
+// calls it: it is the cross-check that tests/raw_limbs (op 9) and tests/modq_redc hold the product-scanning forms above against.
 template <class M>
 ZK_DEV void limbs_mont_mul_rows(uint32_t out[NLIMB], const uint32_t a[NLIMB], const uint32_t b[NLIMB]) {
     uint64_t T[2 * NLIMB];
@@ -619,21 +571,6 @@ ZK_DEV void limbs_mont_mul_rows(uint32_t out[NLIMB], const uint32_t a[NLIMB], co
     }
     out[NLIMB - 1] = (uint32_t)carry;
 }
-// Measured (profiles/r04_ab_variants.txt, same box): no effect -- tom_normalize 10.82 -> 10.96 ms, p256_front 3.16 -> 3.26 ms per step, proofs/s
-// unchanged: the inversions are not what those kernels wait for.  Default off; kept as the record of the experiment.
-#ifndef ZK_POW_ROWS
-#define ZK_POW_ROWS 0
-#endif
-template <class M>
-ZK_DEV Fe<M, 2> fe_mul_rows(const Fe<M, 2>& a, const Fe<M, 2>& b) {
-#if ZK_POW_ROWS
-    Fe<M, 2> r;
-    limbs_mont_mul_rows<M>(r.l, a.l, b.l);
-    return r;
-#else
-    return a * b;
-#endif
-}
 // a^e for a public exponent e given as 9 little-endian 32-bit words (right-to-left binary), Montgomery domain
 template <class M>
 ZK_DEV_NOINLINE Fe<M, 2> fe_pow_words(Fe<M, 2> a, const uint32_t e[NLIMB]) {
@@ -644,12 +581,8 @@ ZK_DEV_NOINLINE Fe<M, 2> fe_pow_words(Fe<M, 2> a, const uint32_t e[NLIMB]) {
         int nb = M::bits - 32 * w;
         if (nb > 32) nb = 32;
         for (int b = 0; b < nb; b++) {
-            if ((ew >> b) & 1) acc = fe_mul_rows(acc, base);
-#if ZK_POW_ROWS
-            base = fe_mul_rows(base, base);
-#else
+            if ((ew >> b) & 1) acc = acc * base;
             base = fe_sqr(base);
-#endif
         }
     }
     return acc;
@@ -762,17 +695,9 @@ ZK_DEV_NOINLINE Fe<M, 2> fe_inv_gcd(const Fe<M, 2> a) {
 }
 
 // Montgomery-domain inverse, inv(0) = 0: what every caller uses (block_inverse, the front ends, the table builders).
-// (-DZK_INV_FERMAT=1 builds round 5's Fermat inversions back in: the A/B library of profiles/r06_ab_variants.txt.)
-#ifndef ZK_INV_FERMAT
-#define ZK_INV_FERMAT 0
-#endif
 template <class M, bool LOCKSTEP = false>
 ZK_DEV Fe<M, 2> fe_inv(const Fe<M, 2>& a) {
-#if ZK_INV_FERMAT
-    return fe_inv_fermat<M>(a);
-#else
     return fe_inv_gcd<M, LOCKSTEP>(a);
-#endif
 }
 
 // ---- plain 32-bit-word <-> 30-bit-limb conversions ----

@@ -205,28 +205,16 @@ __global__ void __launch_bounds__(256) k_padd_inv(Workspace W, uint32_t items, u
 // i8 itself (at most two extra products), so no part holds more than a few scalars.
 #define PADD_PARTS 6
 // The six parts of an item read overlapping draws (the item's blinders d0 + 0..5, the repetition's and the proof's) and their neighbours in the same cache
-// lines.  ZK_PADD_TILED = 1 (default since round 4): a workgroup is six waves over the SAME 64 items, wave w = part w, so those lines are fetched once per
-// CU instead of once per part of a grid-wide sweep (part = t / items: the parts of an item ran a whole grid apart).  0 = the old mapping, for A/Bs.
-#ifndef ZK_PADD_TILED
-#define ZK_PADD_TILED 1
-#endif
+// lines.  A workgroup is six waves over the SAME 64 items, wave w = part w, so those lines are fetched once per CU instead of once per part of a
+// grid-wide sweep (part = t / items: the parts of an item a whole grid apart).
 #ifndef ZK_PADD_RESPOND_WAVES
 #define ZK_PADD_RESPOND_WAVES 3   // waves per SIMD k_padd_respond is compiled for (168 VGPRs)
 #endif
-#if ZK_PADD_TILED
 #define PADD_BLOCK (64 * PADD_PARTS)
 #define PADD_GRID(items) dim3(((items) + 63) / 64)
 #define PADD_MAP(items, part, it)                                                                   \
     const uint32_t part = threadIdx.x >> 6, it = blockIdx.x * 64 + (threadIdx.x & 63);             \
     if (it >= (items)) return
-#else
-#define PADD_BLOCK 256
-#define PADD_GRID(items) dim3(((items) * PADD_PARTS + 255) / 256)
-#define PADD_MAP(items, part, it)                                                                   \
-    const uint32_t t_ = gtid();                                                                     \
-    if (t_ >= (items) * PADD_PARTS) return;                                                         \
-    const uint32_t part = t_ / (items), it = t_ % (items)
-#endif
 struct PaddIn {
     uint32_t p, i, d0;
     Sq x1, y1;
@@ -361,13 +349,8 @@ __global__ void __launch_bounds__(PADD_BLOCK, ZK_PADD_RESPOND_WAVES) k_padd_resp
         }
     }
 }
-// Limit study (profiles/r04_ab_variants.txt (6)): -DZK_AB_SKIP_RESPOND=1 leaves the response / serialisation kernels out altogether -- the proofs are then
-// garbage -- to measure what the whole family costs the OVERLAPPED step, i.e. the most any rewrite of these kernels could win.  Never set in a product build.
-#ifndef ZK_AB_SKIP_RESPOND
-#define ZK_AB_SKIP_RESPOND 0
-#endif
 void launch_padd_respond(hipStream_t s, const Workspace& W, uint32_t items, uint8_t* out) {
-    if (!items || ZK_AB_SKIP_RESPOND) return;
+    if (!items) return;
     hipLaunchKernelGGL(k_padd_respond, PADD_GRID(items), dim3(PADD_BLOCK), 0, s, W, items, out);
 }
 
@@ -424,7 +407,6 @@ __global__ void __launch_bounds__(256) k_write_fixed(Workspace W, uint32_t count
     }
 }
 void launch_write_fixed(hipStream_t s, const Workspace& W, uint32_t count, uint8_t* out) {
-    if (ZK_AB_SKIP_RESPOND) return;
     uint32_t n = count * (W.sec + 1);
     hipLaunchKernelGGL(k_write_fixed, dim3((n + 255) / 256), dim3(256), 0, s, W, count, out);
 }
@@ -493,7 +475,7 @@ __global__ void __launch_bounds__(256) k_write_padd_points(Workspace W, uint32_t
     }
 }
 void launch_write_padd_points(hipStream_t s, const Workspace& W, uint32_t items, uint8_t* out) {
-    if (!items || ZK_AB_SKIP_RESPOND) return;
+    if (!items) return;
     hipLaunchKernelGGL(k_write_padd_points, dim3((items + WP_ITEMS - 1) / WP_ITEMS), dim3(256), 0, s, W, items, out);
 }
 
@@ -597,7 +579,6 @@ __global__ void __launch_bounds__(256) k_write_gk_points(Workspace W, uint32_t c
     put_tom_pair(W.wire, gk + 4 * W.wire.tc * k, W.lc, p * 4 * W.n + 2 * k, p * 4 * W.n + 2 * k + 1);
 }
 void launch_gk_respond(hipStream_t s, const Workspace& W, const ChunkIn& in, uint8_t* out) {
-    if (ZK_AB_SKIP_RESPOND) return;
     hipLaunchKernelGGL(k_gk_respond, dim3((in.count + 63) / 64), dim3(64), 0, s, W, in, out);
     uint32_t n = in.count * 2 * W.n;
     hipLaunchKernelGGL(k_write_gk_points, dim3((n + 255) / 256), dim3(256), 0, s, W, in.count, out);

@@ -1,7 +1,7 @@
 // Function qualifiers of the per-lane device code.  The product compiles these headers with hipcc for gfx950 only.
 // tests/host_arith defines ZK_HOST_BUILD and compiles the SAME headers (field.h, curve.h, sha256.h, rng.h) with g++ for the host
-// CPU, so that the CPU test tier exercises this source against the oracle; the opaque-operand asm statements of field.h and the
-// AMDGPU builtins are switched off / replaced by their portable definitions there.  One product unit is built that way too: h2c_host.cpp, the
+// CPU, so that the CPU test tier exercises this source against the oracle; the opaque-operand statements (zk_opaque_v / zk_opaque_s below) are
+// nothing and the AMDGPU builtins are replaced by their portable definitions there.  One product unit is built that way too: h2c_host.cpp, the
 // one-time host-side derivation of the hardened mode's generators (no kernel involved).
 #pragma once
 #include <stdint.h>
@@ -9,8 +9,11 @@
 #define ZK_DEV inline
 #define ZK_DEV_NOINLINE
 #define ZK_CONSTANT static const
-#define ZK_LAUNDER_MOD 0
-#define ZK_PIN_LIMBS32 0
+// zk_opaque_v / zk_opaque_s (see the device definitions below): registers of the GPU, nothing here
+template <class... T>
+ZK_DEV void zk_opaque_v(T&...) {}
+template <class T>
+ZK_DEV void zk_opaque_s(T&) {}
 ZK_DEV uint32_t zk_rotr32(uint32_t x, int n) { return (x >> n) | (x << (32 - n)); }
 ZK_DEV uint32_t zk_funnelshift_r(uint32_t lo, uint32_t hi, uint32_t sh) { return (uint32_t)((((uint64_t)hi << 32) | lo) >> (sh & 31)); }
 ZK_DEV uint32_t zk_xor3(uint32_t a, uint32_t b, uint32_t c) { return a ^ b ^ c; }
@@ -21,6 +24,17 @@ ZK_DEV uint32_t zk_maj(uint32_t a, uint32_t b, uint32_t c) { return (a & b) | (c
 #define ZK_DEV __device__ __forceinline__
 #define ZK_DEV_NOINLINE __device__ __noinline__
 #define ZK_CONSTANT __constant__
+// Opaque to the optimiser, no instruction: the values pass through an empty asm statement as VGPR (_v) or SGPR (_s) operands, so no pass sees what they
+// were computed from or reshapes the code around them.  Every use says what it keeps the compiler from doing.  Several values in one call are ONE
+// statement, pinned at the same point: not the same code as one call each.
+template <class A>
+ZK_DEV void zk_opaque_v(A& a) { asm("" : "+v"(a)); }
+template <class A, class B>
+ZK_DEV void zk_opaque_v(A& a, B& b) { asm("" : "+v"(a), "+v"(b)); }
+template <class A, class B, class C>
+ZK_DEV void zk_opaque_v(A& a, B& b, C& c) { asm("" : "+v"(a), "+v"(b), "+v"(c)); }
+template <class T>
+ZK_DEV void zk_opaque_s(T& x) { asm("" : "+s"(x)); }
 ZK_DEV uint32_t zk_rotr32(uint32_t x, int n) { return __builtin_amdgcn_alignbit(x, x, n); }
 ZK_DEV uint32_t zk_funnelshift_r(uint32_t lo, uint32_t hi, uint32_t sh) { return __funnelshift_r(lo, hi, sh); }
 // Three-input boolean functions in ONE instruction: gfx950 has no v_xor3_b32 (the assembler refuses it) but it has v_bitop3_b32 -- any function of three
