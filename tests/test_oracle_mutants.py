@@ -4,9 +4,11 @@ restatement's verifier must reach every outcome the sweep claims to cover, the P
 prover's planted-fill / out-of-range cases must give the statuses the reference's throws map to."""
 import hashlib
 
+import pytest
+
 import coracle as CO
 import zkattest_ref as R
-from zka1_mutants import P256_N, Layout, mutants
+from zka1_mutants import DILUTED_RINGS, DILUTED_TAGS, P256_N, SUBSET_MORE, SUBSET_PER_STRATUM, Layout, diluted_signers, mutants, stratum, subset
 
 
 def _xy(pt, w):
@@ -101,6 +103,35 @@ def test_the_sweep_reaches_every_verifier_outcome_and_both_restatements_agree():
     for i in picked:
         got = _py_verify(params, ring, msgs[32 * i:32 * i + 32], plist[i], vs[32 * i:32 * i + 32])
         assert got == (ok[i], vst[i]), (names[i], got, (ok[i], vst[i]))
+
+
+@pytest.mark.parametrize('nkeys,S', DILUTED_RINGS)
+def test_the_stratified_subset_is_still_a_sweep(nkeys, S):
+    """tests/test_gpu_mutants_batched.py dilutes subset(mutants) among honest proofs; this is the condition on its inputs, judged by the oracle alone on the proofs
+    of the oracle's prover (the engine's bytes, RNG contract): every stratum of the full sweep is in the subset, and under each of the two verifier tags the
+    oracle's verdicts over the subset reach all six outcomes.  The workload is the GPU tier's: min(16, keys) signers in the ring, mutants of proofs 0 and 1."""
+    W = diluted_signers(nkeys)
+    params, ring, c, msg, sig, pk, which, seeds = _case(S, nkeys, W)
+    proofs, st = c.prove_batch(msg[:64], sig[:128], pk[:128], which[:2], seeds=seeds[:64], nthreads=2)
+    assert st == [0, 0]
+    muts = mutants(proofs, (nkeys - 1).bit_length(), S, S)
+    sub = subset(muts, SUBSET_PER_STRATUM, SUBSET_MORE)
+    assert sub == subset(muts, SUBSET_PER_STRATUM, SUBSET_MORE)                # deterministic
+    pos = {id(m): i for i, m in enumerate(muts)}
+    assert [pos[id(m)] for m in sub] == sorted(pos[id(m)] for m in sub)        # the original order
+    strata = [stratum(m[0]) for m in muts]
+    assert {stratum(m[0]) for m in sub} == set(strata) and len(set(strata)) >= 70, sorted(set(strata))
+    for s in set(strata):
+        want = min(strata.count(s), SUBSET_MORE.get(s, SUBSET_PER_STRATUM))
+        assert [m for m in sub if stratum(m[0]) == s] == [m for m in muts if stratum(m[0]) == s][:want], s
+    assert {'rep-point', 'rep-padd-scalar', 'gk-scalar', 'cut-len', 'alpha=zero-rep', 'T1inf', 'R=(0,sqrt b)', 'swap-Tx-Ty'} <= set(strata)
+    assert len(sub) < len(muts) // 2
+    msgs = b''.join(msg[32 * m[1]:32 * m[1] + 32] for m in sub)
+    plist = [m[2] for m in sub]
+    for tag in DILUTED_TAGS:
+        ok, vst = c.verify_batch(msgs, plist, nthreads=16, vseeds=_vseeds(len(plist), tag))
+        seen = set(zip(ok, vst))
+        assert seen == {(1, 0), (0, 0), (0, 3), (0, 4), (0, 8), (0, 10)}, (tag, sorted(seen))
 
 
 def test_planted_fills_and_which_out_of_range_in_the_oracle():

@@ -1,6 +1,7 @@
 """Seeded, stratified mutants of honest ZKA1 proofs (include/zkattest.h layout) for the differential tests of the verifier:
 tests/test_gpu_mutants.py (-m gpu: engine vs oracle) and tests/test_oracle_mutants.py (CPU tier: the sweep reaches every outcome)."""
 import random
+import re
 
 P256_N = 0xffffffff00000000ffffffffffffffffbce6faada7179e84f3b9cac2fc632551
 TOM_Q = 0xffffffff00000001000000000000000000000000ffffffffffffffffffffffff   # Tom-256 scalar field = the P-256 base field
@@ -269,4 +270,55 @@ def mutants(proofs, n, S, synth_S):
         add('other-message', 1, proofs[0])
     return out
 
+
+# ---- a stratified subset for the diluted sweeps (tests/test_gpu_mutants_batched.py; tests/test_oracle_mutants.py holds it to its claims on the CPU)
+_STRATUM_RULES = [(re.compile(a), b) for a, b in (
+    (r'/p\d+$', ''),                           # the proof the mutant was made from
+    (r'^T1inf\([+-]\d\)-rep\d+$', 'T1inf'),    # either sign of R = +-k G, whichever repetition
+    (r'\(0,[+-]sqrt b\)', '(0,sqrt b)'),
+    (r'rep\d+', 'rep'),                        # repetition indices
+    (r'(point|scalar)\d+', r'\1'),             # point and scalar indices
+    (r'^A\d+=', 'A='), (r'T([xy])\d+', r'T\1'),
+    (r'^top@\d+', 'top'), (r'^hdr-byte\d+', 'hdr-byte'), (r'^(cut|ext)\d+', r'\1'))]
+
+
+def stratum(name):
+    """The mutant's name up to the /p<j> suffix with repetition, point and scalar indices, offsets and lengths stripped: 'rep17-padd-scalar3/p1' -> 'rep-padd-scalar',
+    'cut336-len/p0' -> 'cut-len', 'alpha=zero-rep5/p1' -> 'alpha=zero-rep', 'T1inf(-1)-rep9/p0' -> 'T1inf', 'R=(0,+sqrt b)/p0' -> 'R=(0,sqrt b)'.  VALUES stay: 'hdr-n=63',
+    'gk-of-n=4-badpoint' and 'bits-0to1' are strata of their own."""
+    for rx, to in _STRATUM_RULES:
+        name = rx.sub(to, name)
+    return name
+
+
+def subset(muts, per_stratum, more=None):
+    """The first `per_stratum` mutants of every stratum (`more`: {stratum: count} for the strata that need another count), in the order of `muts`."""
+    more = more or {}
+    assert all(isinstance(v, int) and v > 0 for v in list(more.values()) + [per_stratum])
+    taken, out = {}, []
+    for m in muts:
+        s = stratum(m[0])
+        if taken.get(s, 0) < more.get(s, per_stratum):
+            taken[s] = taken.get(s, 0) + 1
+            out.append(m)
+    assert not set(more) - set(taken), sorted(set(more) - set(taken))    # a misspelt stratum would silently count for nothing
+    return out
+
+
+# The diluted sweeps' inputs, shared by both tiers: (keys, synthetic seed) of the two rings, the tags of the two verifier seeds -- mutant k of the subset is verified
+# under SHA-256(tag || be32(k)) wherever a layout puts it, so the oracle judges the subset once per tag -- and the subset's size.  Two per stratum, except:
+#   T1inf             all 12: R = +k G or -k G (one sign per proof is live) and the verifier must SAMPLE the repetition for status 4 to show
+#   alpha0-rep+Ty=Tx  proof 0's 8 carriers: which of 'T is at infinity' and 'params not found' comes first depends on the sampled order
+# Chosen on the CPU (tests/test_oracle_mutants.py::test_the_stratified_subset_is_still_a_sweep): with these counts the oracle's verdicts reach all six outcomes
+# for both tags on both rings; with 2 everywhere status 4 is missing under b'd0' on the ring of 8 keys.
+DILUTED_RINGS = ((8, 9001), (1024, 9002))
+DILUTED_TAGS = (b'd0', b'd1')
+SUBSET_PER_STRATUM = 2
+SUBSET_MORE = {'T1inf': 12, 'alpha0-rep+Ty=Tx': 8}
+
+
+def diluted_signers(nkeys):
+    """Signers of the diluted sweeps' synthetic workload: signer b owns ring entry b % nkeys, so a ring of 8 keys holds 8 of them (a ninth would overwrite the first one's
+    key) -- its 16 honest proofs are two per signer, under different prover seeds."""
+    return min(16, nkeys)
 
