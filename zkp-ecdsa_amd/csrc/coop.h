@@ -55,6 +55,11 @@ inline CoU32 co_eq(CoU32 a, uint32_t b) {
     CO_LANES r.v[i_] = a.v[i_] == b ? 1u : 0u;
     return r;
 }
+inline CoU32 co_eq(CoU32 a, CoU32 b) {
+    CoU32 r;
+    CO_LANES r.v[i_] = a.v[i_] == b.v[i_] ? 1u : 0u;
+    return r;
+}
 inline CoU32 co_lt(CoU32 a, uint32_t b) {
     CoU32 r;
     CO_LANES r.v[i_] = a.v[i_] < b ? 1u : 0u;
@@ -111,6 +116,12 @@ inline CoU32 co_gather(CoU32 src, CoU32 a) {   // lane i <- lane src[i]
     CO_LANES r.v[i_] = a.v[src.v[i_] & 63];
     return r;
 }
+template <int R>
+inline bool co_row_all(CoU32 c) {   // is c set in every lane of row R?
+    for (int i = 16 * R; i < 16 * R + 16; i++)
+        if (!c.v[i]) return false;
+    return true;
+}
 #undef CO_LANES
 #else
 // ---- the device: a "register" is a VGPR
@@ -135,6 +146,10 @@ ZK_DEV CoU32 co_bcast(CoU32 a) { return co_dpp<0x150 + N>(a); }   // row_newbcas
 ZK_DEV CoU32 co_from_above(CoU32 a) { return co_dpp<0x101>(a); }  // row_shl:1
 ZK_DEV CoU32 co_from_below(CoU32 a) { return co_dpp<0x111>(a); }  // row_shr:1
 ZK_DEV CoU32 co_gather(CoU32 src, CoU32 a) { return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(src << 2), (int)a); }
+// is c set in every lane of row R?  A wave-wide __ballot, unlike the helpers above: ALL 64 lanes must reach the call, under wave-uniform control flow -- a lane that
+// is masked off reads as "not set" and a row with such a lane never answers true.  The verdict is wave-uniform.
+template <int R>
+ZK_DEV bool co_row_all(CoU32 c) { return ((uint32_t)(__ballot(c) >> (16 * R)) & 0xffffu) == 0xffffu; }
 #endif
 
 // A CoFe limb is at most 2^30 - 1 + CO_NEAR ("nearly normalised"): a parallel carry step adds at most 3 (its input is below 2^32) to a 30-bit low part, and a
@@ -422,6 +437,23 @@ ZK_DEV CoTom co_tom_m1_to_a1(const CoTom& p, const CoU32& mj) {
     return r;
 }
 
+// addition of a Straus table entry (X2, Y2, d'T2, Z2 -- k_verify.hip: st_tab), negated when `neg` (-X2, -d'T2; wave-uniform): curve.h's tom_add_tab, nine products
+// in three passes
+ZK_DEV CoTom co_tom_add_tab(const CoTom& p, const CoFe<ModT, 2>& ent, bool neg, const CoU32& mj) {
+    CoFe<ModT, 0> zero;
+    zero.v = co_splat(0);
+    const auto e = co_pick(neg ? co_eq(co_row_index() & 1u, 0u) : co_splat(0), co_sub(zero, ent), ent);  // rows 0 and 2 negated
+    const auto m1 = co_mul(p.v, e, mj);                                                          // A, B, C, D
+    const auto m2 = co_mul(co_add(p.v, co_rows<1, 4, 4, 4>(p.v)), co_add(e, co_rows<1, 4, 4, 4>(e)), mj);   // row 0: (x1 + y1)(x2 + y2)
+    // E = P4 - (A + B), F = D - C, G = D + C, H = B - A
+    const auto x1 = co_pick(co_row_is(0), m2, co_rows<4, 3, 3, 1>(m1));
+    const auto y1 = co_pick(co_row_is(0), co_add(m1, co_rows<1, 4, 4, 4>(m1)), co_rows<4, 2, 2, 0>(m1));
+    const auto w = co_addsub(x1, y1, co_eq(co_row_index(), 2) ^ 1u);
+    CoTom r;
+    r.v = co_mul(co_rows<0, 2, 0, 1>(w), co_rows<1, 3, 3, 2>(w), mj);                            // E F, G H, E H, F G
+    return r;
+}
+
 // ---- P-256, homogeneous (X : Y : Z) in rows 0, 1, 2 (row 3 of a point register is ignored), the complete Renes-Costello-Batina laws of curve.h
 // (weier.ts:133-230) with their 14 / 13 products dealt to FOUR passes of at most four rows.
 struct CoP256 {
@@ -526,4 +558,10 @@ ZK_DEV CoP256 co_p256_from_jac(const CoP256J& p, const CoU32& mj) {
     r.v = co_mul(a, b, mj).template as<8>();
     return r;
 }
-
+// Is Z (row 2) of a homogeneous point 0 mod q -- the point at infinity?  co_p256_add's Z is the SUM of two products, each below 2 q: a Z that is 0 mod q may be
+// 0, q, 2 q or 3 q (adding two identities: both products are q, Z = 2 q).  One more product, with one, brings it below 2 q: Z = 0 or q.  The same verdict in every lane;
+// the whole wave must call it, under wave-uniform control flow (co_row_all).
+ZK_DEV bool co_p256_z_is_zero(const CoP256& acc, const CoU32& mj) {
+    const CoU32 z = co_normalize(co_mul(acc.v, co_const<ModQ>(ModQ::one), mj)).v;
+    return co_row_all<2>(co_eq(z, 0u)) || co_row_all<2>(co_eq(z, mj));
+}

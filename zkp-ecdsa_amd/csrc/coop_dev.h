@@ -71,18 +71,4 @@ ZK_DEV CoP256 co_p256_identity() {   // (0 : 1 : 0)
     r.v.v = co_row_index() == 1 ? co_limbs(ModQ::one) : 0u;
     return r;
 }
-// addition of a Straus table entry (X2, Y2, d'T2, Z2 -- k_verify.hip: st_tab), negated when `neg` (-X2, -d'T2): curve.h's tom_add_tab, nine products in three passes
-ZK_DEV CoTom co_tom_add_tab(const CoTom& p, const CoFe<ModT, 2>& ent, bool neg, const CoU32& mj) {
-    CoFe<ModT, 0> zero;
-    zero.v = 0;
-    const auto e = co_pick((uint32_t)(neg && !(co_row_index() & 1u)), co_sub(zero, ent), ent);  // rows 0 and 2 negated
-    const auto m1 = co_mul(p.v, e, mj);                                                          // A, B, C, D
-    const auto m2 = co_mul(co_add(p.v, co_rows<1, 4, 4, 4>(p.v)), co_add(e, co_rows<1, 4, 4, 4>(e)), mj);   // row 0: (x1 + y1)(x2 + y2)
-    // E = P4 - (A + B), F = D - C, G = D + C, H = B - A
-    const auto x1 = co_pick(co_row_is(0), m2, co_rows<4, 3, 3, 1>(m1));
-    const auto y1 = co_pick(co_row_is(0), co_add(m1, co_rows<1, 4, 4, 4>(m1)), co_rows<4, 2, 2, 0>(m1));
-    const auto w = co_addsub(x1, y1, (uint32_t)(co_row_index() != 2));
-    CoTom r;
-    r.v = co_mul(co_rows<0, 2, 0, 1>(w), co_rows<1, 3, 3, 2>(w), mj);                            // E F, G H, E H, F G
-    return r;
-}
+// (the addition of a Straus table entry, co_tom_add_tab, is in coop.h: the host tier runs it too)

@@ -411,6 +411,29 @@ ZK_DEV TomPt tom_add(const TomPt& p, const TomPt& q) {
     fe_mul4<ZK_BATCH_TOM != 0>(r.x, r.y, r.t, r.z, E, F, G, H, E, H, F, G);
     return r;
 }
+// addition with an entry (X2, Y2, d'T2, Z2) of the verifier's Straus tables (k_verify.hip: st_tab, k_v_straus): 9 modmuls
+template <int KX>
+ZK_DEV TomPt tom_add_tab(const TomPt& p, const Fe<ModT, KX>& x2, const Ft2& y2, const Fe<ModT, KX>& dt2, const Ft2& z2) {
+    auto A = p.x * x2;
+    auto B = p.y * y2;
+    auto C = p.t * dt2;
+    auto D = p.z * z2;
+    auto E = ((p.x + p.y) * (x2 + y2) - A) - B;
+    auto F = D - C;
+    auto G = D + C;
+    auto H = B - A;
+    TomPt r;
+    r.x = E * F, r.y = G * H, r.t = E * H, r.z = F * G;
+    return r;
+}
+// -v for a coordinate < 2t: 4t - v < 4t ... kept below 4t, which the products of tom_add_tab accept (2 * 4 <= kmax)
+ZK_DEV Fe<ModT, 4> ft_neg_sel(const Ft2& v, bool neg) {
+    Fe<ModT, 4> r;
+#pragma unroll
+    for (int i = 0; i < NLIMB; i++) r.l[i] = neg ? ModT::sub4[i] - v.l[i] : v.l[i];
+    limbs_normalize(r.l);
+    return r;
+}
 // edwards.ts:141-160 with a = 1: 4S + 4M
 ZK_DEV TomPt tom_dbl(const TomPt& p) {
     Ft2 A, B, Cz, S;

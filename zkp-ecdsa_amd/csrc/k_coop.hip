@@ -143,12 +143,8 @@ __global__ void __launch_bounds__(256) k_v_exp_points_co(Workspace W, VWork V, u
             qq.v = co_load_soa<ModQ, 8>(p, W.Q.x, W.Q.y, W.Q.z, Soa{nullptr, 0});
             acc = co_p256_add(acc, qq, mj);
         }
-        // 'T is at infinity' / 'T1 is at infinity' (exp.ts:274,312).  co_p256_add's Z is the SUM of two products, each below 2 q: a Z that is 0 mod q may be
-        // 0, q, 2 q or 3 q (alpha = 0 adds identities: both products are q, Z = 2 q).  One more product, with one, brings it below 2 q: Z = 0 or q; the first such
-        // slot counts
-        const uint32_t z = co_normalize(co_mul(acc.v, co_const<ModQ>(ModQ::one), mj)).v;
-        const uint32_t is0 = (uint32_t)(__ballot(z == 0u) >> 32) & 0xffffu, isq = (uint32_t)(__ballot(z == mj) >> 32) & 0xffffu;
-        if (lane == 0 && (is0 == 0xffffu || isq == 0xffffu)) atomicMin(V.exp_jz + p, t % VK);
+        // 'T is at infinity' / 'T1 is at infinity' (exp.ts:274,312): Z == 0 mod q in any of its representations (coop.h); the first such slot counts
+        if (co_p256_z_is_zero(acc, mj) && lane == 0) atomicMin(V.exp_jz + p, t % VK);
     } else {   // keep later kernels on defined data: G
         const uint32_t row = co_row_index();
         acc.v.v = row == 0 ? co_limbs(P256_GX_M) : row == 1 ? co_limbs(P256_GY_M) : row == 2 ? co_limbs(ModQ::one) : 0u;

@@ -1463,29 +1463,7 @@ __global__ void __launch_bounds__(256, 2) k_v_term_tables(VTerms L, uint32_t ngr
         st_tab(L, e, idx, m);
     }
 }
-// addition with a table entry (X2, Y2, d'T2, Z2): 9 modmuls
-template <int KX>
-ZK_DEV TomPt tom_add_tab(const TomPt& p, const Fe<ModT, KX>& x2, const Ft2& y2, const Fe<ModT, KX>& dt2, const Ft2& z2) {
-    auto A = p.x * x2;
-    auto B = p.y * y2;
-    auto C = p.t * dt2;
-    auto D = p.z * z2;
-    auto E = ((p.x + p.y) * (x2 + y2) - A) - B;
-    auto F = D - C;
-    auto G = D + C;
-    auto H = B - A;
-    TomPt r;
-    r.x = E * F, r.y = G * H, r.t = E * H, r.z = F * G;
-    return r;
-}
-// -v for a coordinate < 2t: 4t - v < 4t ... kept below 4t, which the products of tom_add_tab accept (2 * 4 <= kmax)
-ZK_DEV Fe<ModT, 4> ft_neg_sel(const Ft2& v, bool neg) {
-    Fe<ModT, 4> r;
-#pragma unroll
-    for (int i = 0; i < NLIMB; i++) r.l[i] = neg ? ModT::sub4[i] - v.l[i] : v.l[i];
-    limbs_normalize(r.l);
-    return r;
-}
+// (the addition of a table entry: curve.h, tom_add_tab / ft_neg_sel)
 // Lane i works on group perm[i] (identity without perm).  Lanes below cnt[0] are full groups: terms [0, n256) have 256-bit
 // scalars (windows 64..0), terms [n256, n256 + n128) 128-bit scalars (windows 32..0).  The remaining lanes (slots of
 // one-bit repetitions or of rejected proofs) only own the last two 128-bit terms, so they start at window 32 and add
