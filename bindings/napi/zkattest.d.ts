@@ -54,6 +54,14 @@ export const WHICH_NONE: number
 export function screenSignatureLists(params: SystemParametersList, statements: ScreenStatement[]): Promise<ScreenVerdict[]>
 /** the lookup alone: the lowest index of the key's x-coordinate among keys, or -1; params default to those the facade used last */
 export function findKey(publicKey: PublicKey, keys: bigint[] | Buffer, params?: SystemParametersList): Promise<number>
+/** Key recovery (zk_recover_batch_rings): the signer's key from (msgHash, sigBytes) alone and its lowest index among `keys`.  flags is a set of RECOVER bits; with
+ *  flags === 0 publicKey is the raw 65-byte uncompressed point, which proveSignatureList(s) takes as its publicKey as it is (or import it:
+ *  subtle.importKey('raw', publicKey, { name: 'ECDSA', namedCurve: 'P-256' }, true, ['verify'])); otherwise publicKey is null and which is WHICH_NONE. */
+export interface RecoverStatement { msgHash: Uint8Array; sigBytes: Uint8Array; keys: bigint[] | Buffer }
+export interface RecoveredKey { publicKey: Buffer | null; which: number; flags: number }
+export const RECOVER: { readonly SIG_RANGE: 2; readonly NOT_IN_RING: 8; readonly RING_NOT_RESIDENT: 16; readonly NO_POINT: 32 }
+export function recoverSignatureLists(params: SystemParametersList, statements: RecoverStatement[]): Promise<RecoveredKey[]>
+export function recoverKey(msgHash: Uint8Array, sigBytes: Uint8Array, keys: bigint[] | Buffer, params?: SystemParametersList): Promise<RecoveredKey>
 /** ring membership of a committed value on its own (src/proofGK/gk.ts:94-262): ZKM1 proofs over the engine's resident rings */
 export class Commitment { p: Point; r: Scalar; constructor(p: Point, r: Scalar) }
 export class GKProof {

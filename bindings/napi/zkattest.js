@@ -388,6 +388,12 @@ class Engine {
         const u32 = (b) => Array.from({ length: b.length / 4 }, (_, i) => b.readUInt32LE(4 * i))
         return { which: u32(r.which), flags: u32(r.flags) }
     }
+    // zk_recover_batch_rings: -> { pk: Buffer (64 B per witness, zeros where flags != 0), which, flags }
+    recoverBatchRings(msg, sig, ringIds) {
+        const r = native.recoverBatchRings(this.h, msg, sig, Buffer.from(Uint32Array.from(ringIds).buffer))
+        const u32 = (b) => Array.from({ length: b.length / 4 }, (_, i) => b.readUInt32LE(4 * i))
+        return { pk: r.pk, which: u32(r.which), flags: u32(r.flags) }
+    }
     // ring membership on its own (zk_member_*), on the ACTIVE ring: -> { proofs: Buffer[] | null per entry, coms: Buffer[] (72 B), blinders: Buffer[] (32 B), status: Int32Array }
     memberProofSize() { return native.memberProofSize(this.h) }
     memberProveBatch(which, blinders, seeds) {
@@ -732,6 +738,43 @@ async function screenSignatureLists(params, statements) {
     }
     return out
 }
+// Key recovery (include/zkattest.h: zk_recover_batch_rings) behind the facade: from { msgHash, sigBytes, keys } alone -- no public key -- the signer's key and
+// where it stands in `keys`.  -> [{ publicKey, which, flags }] in the order given: flags is a set of RECOVER bits; with flags === 0 publicKey is the raw 65-byte
+// uncompressed point (0x04 || x || y) and which its lowest index; otherwise publicKey is null and which WHICH_NONE.  proveSignatureList(s) takes that raw
+// point as its publicKey as it is (rawPublicKey accepts a Buffer); a caller that wants a CryptoKey imports it:
+//   crypto.webcrypto.subtle.importKey('raw', publicKey, { name: 'ECDSA', namedCurve: 'P-256' }, true, ['verify']).
+// Uses the engine and the resident rings of the prove / verify / screen calls.  The reference has no counterpart (src/zkpAttestList.ts:104-118 takes the key).
+const RECOVER = Object.freeze({ SIG_RANGE: 2, NOT_IN_RING: 8, RING_NOT_RESIDENT: 16, NO_POINT: 32 })
+async function recoverSignatureLists(params, statements) {
+    const B = statements.length
+    if (!B) return []
+    const rings = [], ringOfSt = new Array(B), byTag = new Map()
+    statements.forEach((s, i) => {
+        checkRingSize(Buffer.isBuffer(s.keys) ? s.keys.length / 32 : s.keys.length, true)
+        const r = ringOf(s.keys)
+        if (!byTag.has(r.tag)) { byTag.set(r.tag, rings.length); rings.push(r) }
+        ringOfSt[i] = byTag.get(r.tag)
+    })
+    const { withRings, capacity } = engineFor(params, statements[0].keys)
+    const out = new Array(B), per = capacity()
+    for (let g = 0; g < rings.length; g += per) {   // groups of at most residentRings rings: one group unless the call names more
+        const sel = []
+        for (let i = 0; i < B; i++) if (ringOfSt[i] >= g && ringOfSt[i] < g + per) sel.push(i)
+        const cat = (f) => Buffer.concat(sel.map(f))
+        const r = await withRings(rings.slice(g, g + per), (engine, ids) =>
+            engine.recoverBatchRings(cat((i) => Buffer.from(statements[i].msgHash)), cat((i) => Buffer.from(statements[i].sigBytes)), sel.map((i) => ids[ringOfSt[i] - g])))
+        sel.forEach((i, k) => {
+            const ok = r.flags[k] === 0
+            out[i] = { publicKey: ok ? Buffer.concat([Buffer.from([4]), r.pk.slice(64 * k, 64 * k + 64)]) : null, which: r.which[k], flags: r.flags[k] }
+        })
+    }
+    return out
+}
+// the one-statement form
+async function recoverKey(msgHash, sigBytes, keys, params = lastParams) {
+    if (!params) throw new Error('recoverKey: no params given and none used yet')
+    return (await recoverSignatureLists(params, [{ msgHash, sigBytes, keys }]))[0]
+}
 // the lookup alone: the lowest index of publicKey's x-coordinate among keys, or -1 (the engine compares integers: a key off the curve is looked up like any
 // other).  The ring lives on the engine of a SystemParametersList: `params`, or by default the one the facade used last.
 let lastParams = null
@@ -815,6 +858,6 @@ async function verifyMemberships(pedersenParams, comPoints, keys, proofs) {
     })
 }
 
-module.exports = { proveMembership, verifyMembership, proveMemberships, verifyMemberships, GKProof, Commitment, commit, screenSignatureLists, findKey, SCREEN, WHICH_NONE, verifySignatureLists, proveSignatureLists, _ringGenerations, setVerifyLevel, getVerifyLevel, generateParamsList, generateParamsListHardened, keyToInt, proveSignatureList, verifySignatureList, proveSignatureListBatch, verifySignatureListBatch,
+module.exports = { proveMembership, verifyMembership, proveMemberships, verifyMemberships, GKProof, Commitment, commit, screenSignatureLists, findKey, SCREEN, WHICH_NONE, recoverSignatureLists, recoverKey, RECOVER, verifySignatureLists, proveSignatureLists, _ringGenerations, setVerifyLevel, getVerifyLevel, generateParamsList, generateParamsListHardened, keyToInt, proveSignatureList, verifySignatureList, proveSignatureListBatch, verifySignatureListBatch,
     writeJson, readJson, writeJsonBatch, readJsonBatch, SignatureProofList, SystemParametersList, PedersenParams, generatePedersenParams, p256, tomEdwards256, ALL_GROUPS,
     Group, Point, Scalar, Engine, shutdown, setWireLayout, getWireLayout, setOption, native }

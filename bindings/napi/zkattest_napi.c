@@ -1038,6 +1038,35 @@ static napi_value ScreenBatchRings(napi_env env, napi_callback_info info) {
     return v;
 }
 
+/* (h, msg, sig, ringIds: B u32 LE) -> {pk: B x 64 (zeros where flags != 0), which: B u32 LE, flags: B u32 LE}: zk_recover_batch_rings on the pool's first
+ * context, like the screen (no pool form) */
+static napi_value RecoverBatchRings(napi_env env, napi_callback_info info) {
+    napi_value argv[4];
+    if (!get_args(env, info, 4, argv)) return NULL;
+    Handle *h = get_handle(env, argv[0], 0);
+    uint8_t *msg, *sig, *ib;
+    size_t lm, ls, li;
+    if (!h || !get_bytes(env, argv[1], &msg, &lm) || !get_bytes(env, argv[2], &sig, &ls) || !get_bytes(env, argv[3], &ib, &li)) return NULL;
+    const size_t B = lm / 32;
+    if (lm % 32 || ls != 64 * B || li != 4 * B) {
+        napi_throw_range_error(env, NULL, "recoverBatchRings: 32 bytes of hash, 64 of signature and one ring id per witness");
+        return NULL;
+    }
+    /* (a Buffer's bytes need not be 4-byte aligned) */
+    uint32_t *buf = (uint32_t *)xmalloc(env, 12 * B + 64 * B + 4);
+    if (!buf) return NULL;
+    uint32_t *ids = buf, *wo = buf + B, *fl = buf + 2 * B;
+    uint8_t *pk = (uint8_t *)(buf + 3 * B);
+    if (B) memcpy(ids, ib, 4 * B);
+    zk_status st = zk_recover_batch_rings(zk_pool_ctx(h->pool, 0), B, msg, sig, ids, pk, wo, fl);
+    napi_value v = NULL;
+    if (st != ZK_OK) throw_text(env, st, zk_last_error(zk_pool_ctx(h->pool, 0)));
+    else if (napi_create_object(env, &v) == napi_ok)
+        set_prop(env, v, "pk", new_buffer(env, pk, 64 * B)), set_prop(env, v, "which", new_buffer(env, wo, 4 * B)), set_prop(env, v, "flags", new_buffer(env, fl, 4 * B));
+    free(buf);
+    return v;
+}
+
 /* Ring membership on its own (include/zkattest.h: zk_member_*), on the pool's first context like the screen (no pool form); the active ring is the facade's.
  * (h) -> bytes of one ZKM1 proof over the active ring */
 static napi_value MemberProofSize(napi_env env, napi_callback_info info) {
@@ -1123,6 +1152,7 @@ static napi_value Init(napi_env env, napi_value exports) {
                {"verifyBatchRings", VerifyBatchRings}, {"verifyBatchRingsAsync", VerifyBatchRingsAsync},
                {"proveBatchRings", ProveBatchRings},   {"proveBatchRingsAsync", ProveBatchRingsAsync},
                {"screenBatchRings", ScreenBatchRings},
+               {"recoverBatchRings", RecoverBatchRings},
                {"memberProofSize", MemberProofSize},   {"memberProveBatch", MemberProveBatch}, {"memberVerifyBatch", MemberVerifyBatch}};
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;

@@ -411,6 +411,54 @@ zk_status zk_screen_batch_rings_device(zk_ctx *ctx, uint64_t B, const void *d_ms
                                        const void *d_which /*u32[B] or NULL*/, const void *d_ring_ids /*u32[B]*/, void *d_which_out /*u32[B]*/,
                                        void *d_flags /*u32[B]*/);
 
+/* Key recovery: the signer's key from (msg_hash, signature) alone, and its place in the ring.  A witness of zk_prove_batch is (msg_hash, sig, pk, which)
+ * and zk_screen_batch can drop `which`, but a P-256 signature already determines its signer up to four points Q = (s R - z G) / r, and only the ring can say
+ * which of them is a member.  zk_recover_batch computes them and looks them up in the ring's resident limbs; its outputs are laid out as
+ * zk_prove_batch_device takes its inputs, so recover -> prove is device-resident from (msg, sig) alone.  The reference has no counterpart: its prover takes
+ * the key from the caller (src/zkpAttestList.ts:104-118).  Per witness:
+ *   Range.       r or s outside [1, n - 1] as a 256-bit integer: flags = ZK_RECOVER_SIG_RANGE, which_out = ZK_WHICH_NONE, pk_xy_out = 64 zero bytes; nothing else
+ *                is evaluated.
+ *   Candidates.  At most four, in this order: c = 0: R = (r, even y), 1: R = (r, odd y), 2: R = (r + n, even y), 3: R = (r + n, odd y).  Candidates 2 and 3 exist
+ *                only when r + n < p.  An x-candidate exists only when v = x^3 - 3x + b is a square mod p (y = v^((p+1)/4), tested by y^2 == v).  If no
+ *                x-candidate lifts: flags = ZK_RECOVER_NO_POINT | ZK_RECOVER_NOT_IN_RING.
+ *   Keys.        Q_c = u1 G + u2 R_c with u1 = -z / r, u2 = s / r mod n and z = truncateToN(msg_hash) as the prover and the screen compute it
+ *                (zkpAttestList.ts:80-86).  A Q_c that is the identity is not a key and is skipped; its sibling of the other parity is still exact.
+ *   Lookup.      x(Q_c) among the caller's keys [0, n_keys) -- never the padding --: the lowest matching index, as in the screen's find mode.
+ *   Winner.      The candidate with the lowest index; ties (z = 0 mod n makes Q_0 = -Q_1: one x) go to the lowest c.  With a winner pk_xy_out is its canonical
+ *                affine x || y, big-endian, which_out its index, flags = 0; without one ZK_RECOVER_NOT_IN_RING, ZK_WHICH_NONE and zero bytes.
+ *   _rings.      One resident ring id per witness, as in zk_screen_batch_rings; an id that is not resident gives ZK_RECOVER_RING_NOT_RESIDENT alone (ZK_WHICH_NONE,
+ *                zero bytes, nothing else evaluated).  These forms neither read nor change the active ring.
+ * Guarantee: flags[b] == 0 implies that zk_screen_batch in find mode on (msg, sig, pk_xy_out) returns (which_out[b], 0), hence that zk_prove_batch with these
+ * values gives a proof that verifies.
+ * Call-level rules are the screen's: ZK_E_BUFFER before zk_ctx_set_params and, for the plain forms, without an active ring; ZK_E_ARG for NULL pointers and
+ * while streamed jobs are queued; B = 0 is ZK_OK; chunks of 16 384 witnesses on the context's main stream; a call issued after zk_ctx_update_ring sees the
+ * updated ring; prover, verifier and screen state is untouched.  The _device forms take every pointer in this context's HBM (4-byte aligned).  zk_last_timing
+ * reports three families, "recover_lift", "recover_points" and "recover_lookup".  Memory: one buffer of about 26 MB of its own, allocated by the first call
+ * (the screen's scratch keeps its documented size); it holds u1, u2, the lifted R and the candidate keys, all witness-derived, so zk_ctx_wipe, zk_ctx_destroy
+ * and a failed call zero it.
+ * How: one lane per witness; per pass (x = r, then x = r + n, whose workgroups leave at once outside adversarial inputs) a front end (the lift, ONE inversion
+ * of r, u2's digits), u1 G by the comb of G and 1..8 R, then ONE 65-window walk u2 R that serves both parities (Q_0 = A + Bp, Q_1 = A - Bp) and one shared
+ * field inversion; the screen's LDS-tiled lookup over the candidates ("recover_lookup" times the lookup alone), and the selection.  A chunk of at most
+ * 4 096 witnesses (ZK_SCREEN_CO_MAX; decided per chunk, like the screen) takes the square root and the point arithmetic on cooperating waves instead: one
+ * wave per witness raises v to (p+1)/4, then one workgroup of four waves per witness -- wave 0 holds 1..8 R in LDS and owns the walk, waves 1..3 sum u1 G
+ * from the comb -- ends with A +- Bp and the same shared inversion.  Same pk_xy_out, which_out and flags bit for bit; ZKATTEST_ONE_LANE_CHAINS (any value)
+ * keeps every chunk on the one-lane kernels; zk_test_counter 4 counts four chains per witness and pass (two passes) of a cooperative chunk.
+ * Not provided: streamed (submit / wait) variants, zk_pool_* variants. */
+enum {                                   /* values shared with ZK_SCREEN_* where the meaning is the same */
+    ZK_RECOVER_SIG_RANGE = 2,
+    ZK_RECOVER_NOT_IN_RING = 8,
+    ZK_RECOVER_RING_NOT_RESIDENT = 16,
+    ZK_RECOVER_NO_POINT = 32
+};
+zk_status zk_recover_batch(zk_ctx *ctx, uint64_t B, const uint8_t *msg_hash /*Bx32*/, const uint8_t *sig /*Bx64*/, uint8_t *pk_xy_out /*Bx64*/,
+                           uint32_t *which_out /*B*/, uint32_t *flags /*B*/);
+zk_status zk_recover_batch_device(zk_ctx *ctx, uint64_t B, const void *d_msg_hash, const void *d_sig, void *d_pk_xy_out /*Bx64*/, void *d_which_out /*u32[B]*/,
+                                  void *d_flags /*u32[B]*/);
+zk_status zk_recover_batch_rings(zk_ctx *ctx, uint64_t B, const uint8_t *msg_hash /*Bx32*/, const uint8_t *sig /*Bx64*/, const uint32_t *ring_ids /*B*/,
+                                 uint8_t *pk_xy_out /*Bx64*/, uint32_t *which_out /*B*/, uint32_t *flags /*B*/);
+zk_status zk_recover_batch_rings_device(zk_ctx *ctx, uint64_t B, const void *d_msg_hash, const void *d_sig, const void *d_ring_ids /*u32[B]*/,
+                                        void *d_pk_xy_out /*Bx64*/, void *d_which_out /*u32[B]*/, void *d_flags /*u32[B]*/);
+
 /* ---- ring membership of a committed value on its own.  Replaces B calls of proveMembership(params, com, index, values) /
  * verifyMembership(params, com, values, proof) (src/proofGK/gk.ts:94-262, with com = params.commit(values[index]), src/commit/pedersen.ts:53-58): a proof
  * that a Pedersen commitment on Tom-256 opens to one entry of the ACTIVE ring, without revealing which -- the one-of-many part of a ZKAttest proof without

@@ -27,6 +27,7 @@ SYMBOLS = [
     'zk_ctx_update_ring', 'zk_pool_update_ring',
     'zk_prove_batch_rings', 'zk_prove_batch_rings_device', 'zk_pool_prove_batch_rings', 'zk_ring_proof_max_size',
     'zk_screen_batch', 'zk_screen_batch_device', 'zk_screen_batch_rings', 'zk_screen_batch_rings_device',
+    'zk_recover_batch', 'zk_recover_batch_device', 'zk_recover_batch_rings', 'zk_recover_batch_rings_device',
     'zk_member_proof_size', 'zk_member_prove_batch', 'zk_member_prove_batch_device', 'zk_member_verify_batch', 'zk_member_verify_batch_device',
     'zk_test_field_op', 'zk_test_tom_commit', 'zk_test_p256_fixed_mul', 'zk_test_sha256', 'zk_test_rng_draws', 'zk_test_exp_sum',
 ]
@@ -128,6 +129,10 @@ def lib():
         L.zk_screen_batch_device.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp]
         L.zk_screen_batch_rings.argtypes = [vp, u64, C.c_char_p, C.c_char_p, C.c_char_p, vp, vp, vp, vp]
         L.zk_screen_batch_rings_device.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp, vp]
+        L.zk_recover_batch.argtypes = [vp, u64, C.c_char_p, C.c_char_p, vp, vp, vp]
+        L.zk_recover_batch_device.argtypes = [vp, u64, vp, vp, vp, vp, vp]
+        L.zk_recover_batch_rings.argtypes = [vp, u64, C.c_char_p, C.c_char_p, vp, vp, vp, vp]
+        L.zk_recover_batch_rings_device.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp]
         L.zk_ring_proof_max_size.restype = u64
         L.zk_member_proof_size.argtypes = [vp]
         L.zk_member_proof_size.restype = u64
@@ -234,6 +239,8 @@ RING_TABLE_E, RING_DIGIT_PLANES, RING_TABLE_E_DIGITS, RING_KEY_TABLES, RING_ACTI
 # zk_screen_batch: the bits of flags[b] (0 = prove this witness) and the index of a key that is not in the ring
 SCREEN_KEY_NOT_ON_CURVE, SCREEN_SIG_RANGE, SCREEN_SIG_INVALID, SCREEN_NOT_IN_RING, SCREEN_RING_NOT_RESIDENT = 1, 2, 4, 8, 16
 WHICH_NONE = 0xFFFFFFFF
+# zk_recover_batch: the bits of flags[b] (0 = the key was recovered and is in the ring at which_out[b]); shared values mean what they mean for the screen
+RECOVER_SIG_RANGE, RECOVER_NOT_IN_RING, RECOVER_RING_NOT_RESIDENT, RECOVER_NO_POINT = 2, 8, 16, 32
 
 
 def hardened_h(tag=b''):
@@ -597,6 +604,33 @@ class Engine:
             self._chk(self.L.zk_screen_batch_device(self.h, B, d_msg, d_sig, d_pk, d_which, d_which_out, d_flags))
         else:
             self._chk(self.L.zk_screen_batch_rings_device(self.h, B, d_msg, d_sig, d_pk, d_which, d_ring_ids, d_which_out, d_flags))
+
+    def recover_batch(self, msg, sig, ring_ids=None):
+        """zk_recover_batch / zk_recover_batch_rings: the signer's key from (msgHash, signature) alone and its index in the ring.  Returns (pk list, which_out
+        list, flags list): flags[b] is a set of RECOVER_* bits; 0 = pk[b] (64 bytes x || y) is the key at which_out[b] and the witness (msg, sig, pk[b],
+        which_out[b]) is what prove_batch takes; otherwise pk[b] is None and which_out[b] is WHICH_NONE.  ring_ids: one resident ring id per witness instead
+        of the active ring."""
+        B = len(bytes(msg)) // 32
+        if len(msg) != 32 * B or len(sig) != 64 * B or (ring_ids is not None and len(ring_ids) != B):
+            raise ValueError('32 bytes of hash and 64 of signature per witness, one ring id each where given')
+        pk = (C.c_uint8 * max(64 * B, 1))()
+        wo = (C.c_uint32 * max(B, 1))()
+        fl = (C.c_uint32 * max(B, 1))()
+        if ring_ids is None:
+            self._chk(self.L.zk_recover_batch(self.h, B, bytes(msg), bytes(sig), pk, wo, fl))
+        else:
+            ids = (C.c_uint32 * max(B, 1))(*ring_ids)
+            self._chk(self.L.zk_recover_batch_rings(self.h, B, bytes(msg), bytes(sig), ids, pk, wo, fl))
+        raw = bytes(pk)
+        return [raw[64 * b:64 * b + 64] if fl[b] == 0 else None for b in range(B)], list(wo)[:B], list(fl)[:B]
+
+    def recover_batch_device(self, B, d_msg, d_sig, d_pk_out, d_which_out, d_flags, d_ring_ids=None):
+        """zk_recover_batch_device / zk_recover_batch_rings_device: every pointer a device address; d_pk_out (64 B bytes) and d_which_out are what
+        prove_batch_device takes as d_pk and d_which"""
+        if d_ring_ids is None:
+            self._chk(self.L.zk_recover_batch_device(self.h, B, d_msg, d_sig, d_pk_out, d_which_out, d_flags))
+        else:
+            self._chk(self.L.zk_recover_batch_rings_device(self.h, B, d_msg, d_sig, d_ring_ids, d_pk_out, d_which_out, d_flags))
 
     def test_set_prove_segment(self, proofs):
         """test build only (lib/libzkattest_hip_testhooks.so through ZKATTEST_LIB): proofs per segment of the mixed-ring prove calls; 0 = the default"""

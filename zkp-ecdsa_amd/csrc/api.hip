@@ -154,6 +154,7 @@ void wipe_witness(zk_ctx* c) {
     if (c->in_buf && c->stream) (void)hipMemsetAsync(c->in_buf, 0, c->in_bytes, c->stream);
     if (c->pw_buf && c->stream) (void)hipMemsetAsync(c->pw_buf, 0, c->pw_bytes, c->stream);   // mixed-ring prove calls: the gathered signatures, seeds and RNG streams
     if (c->scr_buf && c->stream) (void)hipMemsetAsync(c->scr_buf, 0, c->scr_bytes, c->stream);   // witness screen: u1 = z / s, u2 = r / s, staged signatures
+    if (c->rec_buf && c->stream) (void)hipMemsetAsync(c->rec_buf, 0, c->rec_bytes, c->stream);   // key recovery: u1 = -z / r, u2 = s / r, the lifted R, the candidate keys
     if (c->h_stage) {   // the page-locked mirror of the inputs (signatures, RNG blocks)
         volatile uint8_t* h = c->h_stage;
         for (size_t i = 0; i < c->h_stage_bytes; i++) h[i] = 0;
@@ -187,7 +188,7 @@ extern "C" void zk_ctx_destroy(zk_ctx* c) {
     if (c->h_rg) hipHostFree(c->h_rg);
     hipFree(c->io_buf), hipFree(c->in_buf), hipFree(c->unp_buf), hipFree(c->unp_off), hipFree(c->seed_buf), hipFree(c->lv_buf), hipFree(c->lw_buf), hipFree(c->lb_buf);
     if (c->h_lv) hipHostFree(c->h_lv);
-    hipFree(c->pr_buf), hipFree(c->pw_buf), hipFree(c->ps_buf), hipFree(c->scr_buf), hipFree(c->m_off);
+    hipFree(c->pr_buf), hipFree(c->pw_buf), hipFree(c->ps_buf), hipFree(c->scr_buf), hipFree(c->rec_buf), hipFree(c->m_off);
     if (c->h_pr) hipHostFree(c->h_pr);
     if (c->pr_ready) hipEventDestroy(c->pr_ready);
     if (c->h_stage) hipHostFree(c->h_stage);

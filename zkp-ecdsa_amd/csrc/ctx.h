@@ -70,6 +70,8 @@ struct zk_ctx {
     uint32_t pr_seg_force = 0;     // test build only (zk_test_set_prove_segment): proofs per segment instead of what ZK_PR_STAGE_BYTES holds; 0 = off
     void* scr_buf = nullptr;       // witness screen (api_screen.hip): one chunk's scratch areas (u1, u2: witness-derived, wiped with the workspaces) and, for the
     size_t scr_bytes = 0;          // host-pointer forms, the chunk's inputs and results; allocated by the first screen call, its size does not depend on B
+    void* rec_buf = nullptr;       // key recovery (api_recover.hip): one chunk's scratch areas, lifted R, candidate keys (all witness-derived, wiped with the workspaces)
+    size_t rec_bytes = 0;          // and, for the host-pointer forms, the chunk's inputs and results; allocated by the first recover call, its size does not depend on B
     uint32_t mode = 0;                 // zk_ctx_set_mode: ZK_MODE_REFERENCE / ZK_MODE_HARDENED
     uint32_t verify_level = 0;         // zk_ctx_set_verify_level: ZK_VERIFY_LEVEL_CONTEXT / ZK_VERIFY_LEVEL_PER_PROOF
     // per-proof mode: the repetition count the verifier's workspaces are planned for during one call (or while streamed verify jobs are queued); the

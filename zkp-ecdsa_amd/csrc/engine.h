@@ -399,10 +399,51 @@ struct ScreenRing {
     const uint32_t* ktab;    // per-key tables or nullptr
     const uint8_t* ktab_ok;
 };
+// (the layout is shared with the key recovery, k_recover.hip, whose front end fills an area with R for pk so that the same walk runs on it)
+// a witness's scratch area: entries 0..7 = d * pk, entry 8 = u1 * G (rtab.h format), then the words below
+#define SCR_DIG (9 * RTAB_ENTRY_WORDS)   // u2's signed 4-bit digits (65 bytes)
+#define SCR_U1 (SCR_DIG + 20)            // u1, 8 words
+#define SCR_U2 (SCR_U1 + 8)              // u2, 8 words
+#define SCR_PK (SCR_U2 + 8)              // pk in Montgomery form, 2 x 9 limbs
+#define SCR_KT (SCR_PK + 2 * NLIMB)      // address of the key's table (2 words)
+#define SCR_USE (SCR_KT + 2)             // 0: walk, 1 / 2: pk = + / - the key table's base point, SCR_SKIP: no ECDSA for this witness
+#define SCR_SKIP 3u
+static_assert(SCR_USE < SCR_AREA_WORDS && SCR_AREA_WORDS % 4 == 0 && SCR_KT % 2 == 0, "scratch area layout");
+#define SCR_NO_X 0xffffffffu     // limb 0 of a lane without a witness: no 30-bit limb equals it
+#define SCR_PAD 0xfffffffeu      // ... and of a tile slot past the ring's keys
+
+ZK_DEV uint32_t* scr_area(uint32_t* scratch, uint32_t b) { return scratch + (size_t)b * SCR_AREA_WORDS; }
 void launch_screen_init(hipStream_t s, const ScreenIn& in, uint32_t* scratch);
 void launch_screen_lookup(hipStream_t s, const ScreenRing& G, const ScreenIn& in);   // find mode only: the lowest matching index of ring G's witnesses
 void launch_screen_front(hipStream_t s, const ScreenRing& G, const ScreenIn& in, uint32_t* scratch);
 void launch_screen_ecdsa(hipStream_t s, const DevParams& P, const ScreenIn& in, uint32_t* scratch);
+
+// key recovery (k_recover.hip; include/zkattest.h: zk_recover_batch): a chunk of (msgHash, sig) pairs, its results, and the chunk's buffers in c->rec_buf
+#define REC_NO_RING 0xFFFFFFFFu   // the ring id of a candidate that does not exist: ids count up from 0 and are never reused, so no ring carries it
+#define REC_ST_RANGE 1u           // state word of a witness: r or s out of range,
+#define REC_ST_NORING 2u          // ... its ring id is not resident (nothing else is evaluated),
+#define REC_ST_LIFT0 4u           // ... x = r,
+#define REC_ST_LIFT1 8u           // ... x = r + n lifts to a curve point
+struct RecoverIn {
+    const uint8_t* msg;
+    const uint8_t* sig;
+    const uint32_t* ids;     // nullptr: every witness is on ring `plain_id`
+    uint32_t plain_id;
+    uint8_t* pk_out;
+    uint32_t* which_out;
+    uint32_t* flags;
+    uint32_t count;
+};
+struct RecoverBuf {
+    uint32_t* scratch;       // [count] areas in the screen's layout
+    uint8_t* cand;           // [4 count][64] candidate keys x || y, candidate-major: candidate c of witness b at c * count + b
+    uint32_t* cand_ids;      // [4 count] the witness's ring id where the candidate exists, REC_NO_RING otherwise: the ids[] of the lookup's pseudo-witnesses
+    uint32_t* cand_which;    // [4 count] the lookup's answers
+    uint32_t* state;         // [count] REC_ST_*
+};
+void launch_recover_lift(hipStream_t s, const RecoverIn& in, const RecoverBuf& buf, const RingSlots& rs, uint32_t pass);   // pass 0 also initialises the chunk
+void launch_recover_points(hipStream_t s, const DevParams& P, const RecoverIn& in, const RecoverBuf& buf, uint32_t pass);
+void launch_recover_select(hipStream_t s, const RecoverIn& in, const RecoverBuf& buf);
 
 // buffers of the batched Tom-256 check (k_msm.hip), one set per verifier lane
 struct MsmBuf {

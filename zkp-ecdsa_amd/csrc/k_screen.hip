@@ -19,19 +19,6 @@
 #include "rtab.h"
 #include "coop_sums.h"   // the sums and the walk of a chunk of a few witnesses on cooperating waves (k_screen_table_co, k_screen_walk_co)
 
-// a witness's scratch area: entries 0..7 = d * pk, entry 8 = u1 * G (rtab.h format), then the words below
-#define SCR_DIG (9 * RTAB_ENTRY_WORDS)   // u2's signed 4-bit digits (65 bytes)
-#define SCR_U1 (SCR_DIG + 20)            // u1, 8 words
-#define SCR_U2 (SCR_U1 + 8)              // u2, 8 words
-#define SCR_PK (SCR_U2 + 8)              // pk in Montgomery form, 2 x 9 limbs
-#define SCR_KT (SCR_PK + 2 * NLIMB)      // address of the key's table (2 words)
-#define SCR_USE (SCR_KT + 2)             // 0: walk, 1 / 2: pk = + / - the key table's base point, SCR_SKIP: no ECDSA for this witness
-#define SCR_SKIP 3u
-static_assert(SCR_USE < SCR_AREA_WORDS && SCR_AREA_WORDS % 4 == 0 && SCR_KT % 2 == 0, "scratch area layout");
-#define SCR_NO_X 0xffffffffu     // limb 0 of a lane without a witness: no 30-bit limb equals it
-#define SCR_PAD 0xfffffffeu      // ... and of a tile slot past the ring's keys
-
-ZK_DEV uint32_t* scr_area(uint32_t* scratch, uint32_t b) { return scratch + (size_t)b * SCR_AREA_WORDS; }
 ZK_DEV bool scr_mine(const ScreenIn& in, const ScreenRing& G, uint32_t b) { return b < in.count && (!in.ids || in.ids[b] == G.id); }
 ZK_DEV bool scr_ring_is(const ScreenRing& G, uint32_t i, const Fe<ModQ, 1>& x) {
     bool same = true;
