@@ -474,3 +474,39 @@ def test_wipe_zeroes_the_workspaces_and_changes_nothing_else():
     c, st = eng.prove_batch(msg, sig, pk, which, seeds=seeds)
     assert c == a
     eng.close()
+
+
+def test_wipe_leaves_no_nonzero_word_in_any_witness_buffer():
+    """zk_test_counter 11 reads back what zk_ctx_wipe has to zero -- the context's witness-flagged buffers (staged inputs, the mixed-ring window, the
+    screen's and the recovery's chunk buffers) and the prover's and member lanes' arenas -- and counts the nonzero 32-bit words.  One context, two
+    resident rings of 64 and 32 keys, host-pointer calls of 6 that reach every one of them: nonzero afterwards, zero after wipe(), zero again after a
+    prove call that fails, and the same proofs from the same inputs at the end."""
+    import ctypes as C
+    import zkp_ecdsa_amd as Z
+    eng = Z.Engine(0)
+    nh, tg, th = eng.synth_params(517)
+    eng.set_params(nh, tg, th, 80)
+    ring_a, msg, sig, pk, which, seeds = eng.synth_workload(517, 64, 6)
+    ring_b, msg_b, sig_b, pk_b, which_b, seeds_b = eng.synth_workload(518, 32, 3)
+    a, b = eng.add_ring(ring_a, 64), eng.add_ring(ring_b, 32)
+    eng.use_ring(a)
+    assert eng.test_counter(11) == 0   # nothing allocated yet
+    first, st = eng.prove_batch(msg, sig, pk, which, seeds=seeds)
+    assert st == [0] * 6
+    # three proofs per ring
+    mixed = eng.prove_batch_rings(msg[:96] + msg_b, sig[:192] + sig_b, pk[:192] + pk_b, which[:3] + which_b, [a] * 3 + [b] * 3, seeds=seeds[:96] + seeds_b)
+    assert mixed[1] == [0] * 6
+    assert eng.screen_batch(msg, sig, pk)[1] == [0] * 6
+    assert eng.recover_batch(msg, sig)[2] == [0] * 6
+    assert eng.member_prove_batch(which, seeds=seeds)[3] == [0] * 6
+    n = eng.test_counter(11)
+    print('nonzero words in the witness buffers after the five calls: %d' % n)
+    assert 0 < n < 1 << 63   # (~0: a copy failed)
+    eng.wipe()
+    assert eng.test_counter(11) == 0
+    with pytest.raises(Z.ZkError):   # output buffer too small: the call wipes by itself
+        eng.prove_batch_host_raw(msg, sig, pk, which, seeds, out=(C.c_uint8 * 1000)())
+    assert eng.test_counter(11) == 0
+    again, st = eng.prove_batch(msg, sig, pk, which, seeds=seeds)
+    assert st == [0] * 6 and again == first
+    eng.close()

@@ -1,4 +1,5 @@
-// C ABI of libzkattest_hip.so (include/zkattest.h) and the host-side phase pipeline of the prover.
+// C ABI of libzkattest_hip.so (include/zkattest.h): the context and its buffers (reserve, wipe_witness), ring management, and the host-side phase pipeline of
+// the prover with its host-pointer and mixed-ring forms.
 // One context = one GPU = one HIP stream.  A batch is processed in chunks of `chunk` proofs; every phase of a chunk
 // is one kernel over all proofs (or all zero-bit reps) of the chunk -- see DESIGN.md for the phase list.
 #include <algorithm>
@@ -123,11 +124,6 @@ static zk_status ctx_init(zk_ctx* c, int device_id) {
     HIPCHK(c, hipFree(d_xy));
     return ZK_OK;
 }
-// settings a queued streamed job was planned with (its lane rotation, chunk size, workspaces, mode) stay frozen until it is waited for
-static zk_status busy_refusal(zk_ctx* c) {
-    c->err = "streamed jobs are in flight on this context (zk_prove_wait / zk_verify_wait them first)";
-    return ZK_E_ARG;
-}
 extern "C" zk_status zk_ctx_set_comb_bits(zk_ctx* c, uint32_t bits) {
     if (!c || bits < 8 || bits > TOM_MAX_BITS) return ZK_E_ARG;
     if (c->stream_busy) return busy_refusal(c);
@@ -147,14 +143,11 @@ void wipe_witness(zk_ctx* c) {
     for (int l = 0; l < ZK_MAX_LANES; l++)
         for (hipStream_t st : {c->pl[l].stream, c->pl[l].side, c->pl[l].copy_stream})
             if (st) (void)hipStreamSynchronize(st);
-    for (int l = 0; l < ZK_MAX_LANES; l++)
-        if (c->pl[l].arena && c->pl[l].stream) (void)hipMemsetAsync(c->pl[l].arena, 0, c->pl[l].arena_bytes, c->pl[l].stream);
-    for (int l = 0; l < ZK_MAX_LANES; l++)   // membership proofs on their own (api_member.hip): blinders, nonces, RNG fills
-        if (c->ml[l].arena && c->pl[l].stream) (void)hipMemsetAsync(c->ml[l].arena, 0, c->ml[l].arena_bytes, c->pl[l].stream);
-    if (c->in_buf && c->stream) (void)hipMemsetAsync(c->in_buf, 0, c->in_bytes, c->stream);
-    if (c->pw_buf && c->stream) (void)hipMemsetAsync(c->pw_buf, 0, c->pw_bytes, c->stream);   // mixed-ring prove calls: the gathered signatures, seeds and RNG streams
-    if (c->scr_buf && c->stream) (void)hipMemsetAsync(c->scr_buf, 0, c->scr_bytes, c->stream);   // witness screen: u1 = z / s, u2 = r / s, staged signatures
-    if (c->rec_buf && c->stream) (void)hipMemsetAsync(c->rec_buf, 0, c->rec_bytes, c->stream);   // key recovery: u1 = -z / r, u2 = s / r, the lifted R, the candidate keys
+    for (int l = 0; l < ZK_MAX_LANES; l++)   // the prover's lanes, and the membership proofs' on their own (api_member.hip), each on its lane's stream
+        for (const GrowBuf* a : {&c->pl[l].arena, &c->ml[l].arena})
+            if (a->p && c->pl[l].stream) (void)hipMemsetAsync(a->p, 0, a->bytes, c->pl[l].stream);
+    for (const GrowBuf& b : c->buf)   // the witness-flagged buffers of ZK_CTX_BUFS (ctx.h)
+        if (b.witness && b.p && c->stream) (void)hipMemsetAsync(b.p, 0, b.bytes, c->stream);
     if (c->h_stage) {   // the page-locked mirror of the inputs (signatures, RNG blocks)
         volatile uint8_t* h = c->h_stage;
         for (size_t i = 0; i < c->h_stage_bytes; i++) h[i] = 0;
@@ -165,10 +158,7 @@ void wipe_witness(zk_ctx* c) {
 }
 extern "C" zk_status zk_ctx_wipe(zk_ctx* c) {
     if (!c) return ZK_E_ARG;
-    if (c->stream_busy) {
-        c->err = "streamed jobs are in flight on this context (zk_prove_wait / zk_verify_wait them first)";
-        return ZK_E_ARG;
-    }
+    if (c->stream_busy) return busy_refusal(c);
     HIPCHK(c, hipSetDevice(c->device));
     wipe_witness(c);
     return ZK_OK;
@@ -184,17 +174,17 @@ extern "C" void zk_ctx_destroy(zk_ctx* c) {
     for (auto e : c->epool) hipEventDestroy(e);
     hipFree(c->P.tom_tab_g), hipFree(c->P.tom_tab_h), hipFree(c->tom_tab_gen), hipFree(c->P.pfix_G), hipFree(c->P.pfix_H);
     for (auto& R : c->rings) free_ring(R);
-    hipFree(c->tab_scratch), hipFree(c->d_flag), hipFree(c->rg_buf);
+    hipFree(c->tab_scratch), hipFree(c->d_flag);
+    for (GrowBuf& b : c->buf) hipFree(b.p);
     if (c->h_rg) hipHostFree(c->h_rg);
-    hipFree(c->io_buf), hipFree(c->in_buf), hipFree(c->unp_buf), hipFree(c->unp_off), hipFree(c->seed_buf), hipFree(c->lv_buf), hipFree(c->lw_buf), hipFree(c->lb_buf);
     if (c->h_lv) hipHostFree(c->h_lv);
-    hipFree(c->pr_buf), hipFree(c->pw_buf), hipFree(c->ps_buf), hipFree(c->scr_buf), hipFree(c->rec_buf), hipFree(c->m_off);
     if (c->h_pr) hipHostFree(c->h_pr);
     if (c->pr_ready) hipEventDestroy(c->pr_ready);
     if (c->h_stage) hipHostFree(c->h_stage);
     if (c->in_ready) hipEventDestroy(c->in_ready);
     for (int l = 0; l < ZK_MAX_LANES; l++) {
-        hipFree(c->pl[l].arena), hipFree(c->pl[l].d_totals), hipFree(c->vl[l].arena), hipFree(c->ml[l].arena);
+        for (const GrowBuf* a : {&c->pl[l].arena, &c->vl[l].arena, &c->ml[l].arena}) hipFree(a->p);
+        hipFree(c->pl[l].d_totals);
         if (c->pl[l].h_scan) hipHostFree(c->pl[l].h_scan);
         if (c->vl[l].h_msm) hipHostFree(c->vl[l].h_msm);
         if (c->vl[l].aux_fork) hipEventDestroy(c->vl[l].aux_fork);
@@ -234,10 +224,7 @@ static void words_to_limbs30(const uint32_t* w, int nw, uint32_t* l) {
 extern "C" zk_status zk_ctx_set_params(zk_ctx* c, const uint8_t nist_h[64], const uint8_t tom_g[72], const uint8_t tom_h[72], uint32_t sec) {
     if (!c || !nist_h || !tom_g || !tom_h) return ZK_E_ARG;
     if (sec == 0 || sec > ZK_MAXSEC) return ZK_E_SECLEVEL;
-    if (c->stream_busy) {
-        c->err = "streamed jobs are in flight on this context (zk_prove_wait / zk_verify_wait them first)";
-        return ZK_E_ARG;
-    }
+    if (c->stream_busy) return busy_refusal(c);
     HIPCHK(c, hipSetDevice(c->device));
     uint32_t hw[16], gw[18], hw2[18];
     be_to_words(nist_h, 32, hw, 8), be_to_words(nist_h + 32, 32, hw + 8, 8);
@@ -367,10 +354,7 @@ static Ring* free_slot(zk_ctx* c) {
 }
 // zk_ctx_set_ring: (re)builds the active ring in place (its id stays); a context without an active ring gets a new one and makes it active
 static zk_status set_ring_common(zk_ctx* c, const uint8_t* d_keys, uint64_t nkeys) {
-    if (c->stream_busy) {   // the queued jobs read the ring, table E and the key tables this call would free
-        c->err = "streamed jobs are in flight on this context (zk_prove_wait / zk_verify_wait them first)";
-        return ZK_E_ARG;
-    }
+    if (c->stream_busy) return busy_refusal(c);   // the queued jobs read the ring, table E and the key tables this call would free
     uint32_t n = 0;
     while (((uint64_t)1 << n) < nkeys) n++;
     if (n < 1 || n > ZK_MAXN - 4) return ZK_E_ARG;
@@ -723,7 +707,7 @@ extern "C" uint64_t zk_proof_max_size(const zk_ctx* c) {
 
 // ------------------------------------------------------------------ workspace arena
 static size_t carve(zk_ctx* c, Workspace& W, Soa& gk_am, uint8_t* base, uint32_t C, uint32_t sec, uint32_t n, uint64_t N) {
-    Carver k(base);
+    SoaCarver k(base);
     uint64_t cs = (uint64_t)C * sec;
     uint64_t items_cap = std::min<uint64_t>(cs, cs / 2 + (uint64_t)(4.0 * std::sqrt((double)cs)) + 64);
     W.C = C, W.sec = sec, W.n = n, W.N = (uint32_t)N, W.items_cap = (uint32_t)items_cap;
@@ -822,14 +806,7 @@ zk_status ensure_workspace(zk_ctx* c, uint32_t C, uint32_t nlanes) {
     for (uint32_t l = 0; l < nlanes && l < ZK_MAX_LANES; l++) {
         auto& L = c->pl[l];
         if (!L.ready) {
-            size_t need = carve(c, L.W, L.gk_am, nullptr, C, sec, n, c->ring->N);
-            if (need > L.arena_bytes) {
-                if (L.arena) HIPCHK(c, hipFree(L.arena));
-                L.arena = nullptr, L.arena_bytes = 0;
-                HIPCHK(c, malloc_or_shed(c, &L.arena, need));
-                L.arena_bytes = need;
-            }
-            carve(c, L.W, L.gk_am, (uint8_t*)L.arena, C, sec, n, c->ring->N);
+            if (zk_status zs = lay_out(c, L.arena, GROW_SHED, [&](uint8_t* base) { return carve(c, L.W, L.gk_am, base, C, sec, n, c->ring->N); })) return zs;
             if (!L.d_totals) HIPCHK(c, hipMalloc(&L.d_totals, 64));
             const size_t hs = 64 + 16 * ((size_t)C + 2);
             if (hs > L.h_scan_bytes) {
@@ -992,26 +969,16 @@ bool host_ptr_is_pinned(const void* p) {
     return a.type == hipMemoryTypeHost;
 }
 void* stream_take_spare_dev(zk_ctx* c, size_t bytes, size_t* got);   // api_stream.hip: staging buffers of finished streamed jobs
-zk_status ensure_io_buf(zk_ctx* c, size_t bytes) {
-    if (bytes <= c->io_bytes) return ZK_OK;
-    if (c->io_buf) hipFree(c->io_buf);
-    c->io_buf = nullptr, c->io_bytes = 0;
-    size_t got = 0;
-    if (void* p = stream_take_spare_dev(c, bytes, &got)) {
-        c->io_buf = p, c->io_bytes = got;
-        return ZK_OK;
-    }
-    HIPCHK(c, hipMalloc(&c->io_buf, bytes));
-    c->io_bytes = bytes;
-    return ZK_OK;
-}
-zk_status ensure_in_buf(zk_ctx* c, size_t bytes) {
-    if (bytes <= c->in_bytes) return ZK_OK;
-    if (c->in_buf) hipFree(c->in_buf);
-    c->in_buf = nullptr, c->in_bytes = 0;
-    bytes += bytes / 4 + 4096;
-    HIPCHK(c, hipMalloc(&c->in_buf, bytes));
-    c->in_bytes = bytes;
+// The one "make it at least this big" of the context's device buffers (ctx.h: GrowBuf, GrowPolicy).  A buffer that is too small is freed before its successor is
+// allocated: the two never stand in HBM together.
+zk_status reserve(zk_ctx* c, GrowBuf& b, size_t need, GrowPolicy policy) {
+    if (policy == GROW_ONCE ? b.p != nullptr : need <= b.bytes) return ZK_OK;
+    if (b.p) HIPCHK(c, hipFree(b.p));
+    b.p = nullptr, b.bytes = 0;
+    if (policy == GROW_SPARE && (b.p = stream_take_spare_dev(c, need, &b.bytes))) return ZK_OK;
+    if (policy == GROW_SLACK) need += need / 4 + 4096;
+    HIPCHK(c, policy == GROW_SHED ? malloc_or_shed(c, &b.p, need) : hipMalloc(&b.p, need));
+    b.bytes = need;
     return ZK_OK;
 }
 zk_status ensure_h_stage(zk_ctx* c, size_t bytes) {
@@ -1343,10 +1310,7 @@ static zk_status prove_device(zk_ctx* c, uint64_t B, const uint8_t* d_msg, const
                               int32_t* d_status, uint8_t* host_sink = nullptr, hipEvent_t inputs_ready = nullptr, uint64_t* total_bytes = nullptr) {
     if (!c->params_set || !c->ring->N) return ZK_E_BUFFER;
     if (rng_mode != ZK_RNG_SEED && rng_mode != ZK_RNG_STREAM) return ZK_E_ARG;
-    if (c->stream_busy) {
-        c->err = "streamed jobs are in flight on this context (zk_prove_wait / zk_verify_wait them first)";
-        return ZK_E_ARG;
-    }
+    if (c->stream_busy) return busy_refusal(c);
     ProveJob J;
     J.c = c, J.B = B, J.d_msg = d_msg, J.d_sig = d_sig, J.d_pk = d_pk, J.d_which = d_which, J.rng_mode = rng_mode, J.d_rng = d_rng, J.stride = stride;
     J.d_out = d_out, J.out_cap = out_cap, J.d_out_off = d_out_off, J.d_status = d_status, J.host_sink = host_sink, J.timed = zk_timed(c, B), J.inputs_ready = inputs_ready;
@@ -1411,6 +1375,20 @@ extern "C" zk_status zk_prove_batch_device(zk_ctx* c, uint64_t B, const void* d_
                         rng->stride_blocks, (uint8_t*)d_out, out_cap, (uint64_t*)d_out_off, (int32_t*)d_status);
 }
 
+// c->buf[B_in] of the host-pointer prove calls: the inputs, then offsets and statuses next to each other (prove_host reads both back in one copy)
+struct ProveIn {
+    uint8_t *msg, *sig, *pk, *rng;
+    uint32_t *which, *ids;   // ids: zk_prove_batch_rings only
+    uint64_t* off;
+    int32_t* st;
+};
+static size_t prove_in_layout(ProveIn& I, uint8_t* base, size_t B, size_t rng_bytes, bool ids) {
+    Carver k(base);
+    I.msg = (uint8_t*)k.take(32 * B), I.sig = (uint8_t*)k.take(64 * B), I.pk = (uint8_t*)k.take(64 * B), I.which = (uint32_t*)k.take(4 * B);
+    I.ids = ids ? (uint32_t*)k.take(4 * B) : nullptr;
+    I.rng = (uint8_t*)k.take(rng_bytes ? rng_bytes : 32), I.off = (uint64_t*)k.take(8 * (B + 1)), I.st = (int32_t*)k.take(4 * B);
+    return k.off + ZK_LAYOUT_TAIL;
+}
 static zk_status prove_host(zk_ctx* c, uint64_t B, const uint8_t* msg, const uint8_t* sig, const uint8_t* pk, const uint32_t* which, const zk_rng* rng, uint8_t* out,
                             uint64_t out_cap, uint64_t* out_off, int32_t* status);
 extern "C" zk_status zk_prove_batch(zk_ctx* c, uint64_t B, const uint8_t* msg, const uint8_t* sig, const uint8_t* pk, const uint32_t* which,
@@ -1423,28 +1401,15 @@ extern "C" zk_status zk_prove_batch(zk_ctx* c, uint64_t B, const uint8_t* msg, c
 static zk_status prove_host(zk_ctx* c, uint64_t B, const uint8_t* msg, const uint8_t* sig, const uint8_t* pk, const uint32_t* which, const zk_rng* rng, uint8_t* out,
                             uint64_t out_cap, uint64_t* out_off, int32_t* status) {
     if (!c->params_set || !c->ring->N) return ZK_E_BUFFER;
-    if (c->stream_busy) {
-        c->err = "streamed jobs are in flight on this context (zk_prove_wait / zk_verify_wait them first)";
-        return ZK_E_ARG;
-    }
+    if (c->stream_busy) return busy_refusal(c);
     size_t rng_bytes = rng->mode == ZK_RNG_SEED ? 32 * B : 32 * B * rng->stride_blocks;
     size_t bb = B ? B : 1;
     uint64_t cap_dev = std::min<uint64_t>(out_cap, zk_proof_max_size(c) * bb);
     // the small per-proof arrays live in the context's grow-only input buffer (no hipMalloc / hipFree per call)
-    Carver k(nullptr);
-    auto carve_in = [&](Carver& kk, uint8_t*& m, uint8_t*& sg, uint8_t*& p, uint32_t*& w, uint8_t*& r, uint64_t*& o, int32_t*& st_) {
-        m = (uint8_t*)kk.take(32 * bb), sg = (uint8_t*)kk.take(64 * bb), p = (uint8_t*)kk.take(64 * bb), w = (uint32_t*)kk.take(4 * bb);
-        r = (uint8_t*)kk.take(rng_bytes ? rng_bytes : 32), o = (uint64_t*)kk.take(8 * (bb + 1)), st_ = (int32_t*)kk.take(4 * bb);
-    };
-    uint8_t *d_msg, *d_sig, *d_pk, *d_rng;
-    uint32_t* d_which;
-    uint64_t* d_off;
-    int32_t* d_st;
-    carve_in(k, d_msg, d_sig, d_pk, d_which, d_rng, d_off, d_st);
-    zk_status zs = ensure_in_buf(c, k.off + 256);
+    ProveIn I;
+    zk_status zs = lay_out(c, B_in, [&](uint8_t* base) { return prove_in_layout(I, base, bb, rng_bytes, false); });
     if (zs) return zs;
-    Carver k2((uint8_t*)c->in_buf);
-    carve_in(k2, d_msg, d_sig, d_pk, d_which, d_rng, d_off, d_st);
+    uint8_t* const in_buf = (uint8_t*)c->buf[B_in].p;
     // `out` may itself lie in this GPU's HBM (hipMalloc'ed by the caller): the proofs are written there and never cross the link --
     // host inputs, device-resident output (zk_pool_prove_batch_device is this, per shard)
     bool out_on_device = false;
@@ -1458,24 +1423,24 @@ static zk_status prove_host(zk_ctx* c, uint64_t B, const uint8_t* msg, const uin
         }
     }
     if (out_on_device) cap_dev = out_cap;
-    else if ((zs = ensure_io_buf(c, cap_dev ? cap_dev : 32))) return zs;  // proof bytes: the context's grow-only staging buffer
-    uint8_t* d_out = out_on_device ? out : (uint8_t*)c->io_buf;
+    else if ((zs = reserve(c, B_io, cap_dev ? cap_dev : 32))) return zs;  // proof bytes: the context's grow-only staging buffer
+    uint8_t* d_out = out_on_device ? out : (uint8_t*)c->buf[B_io].p;
     // A call of a few proofs: the five input arrays cross in ONE copy out of the context's page-locked mirror of in_buf and the lanes wait for its event -- five
     // pageable copies and a host wait cost a one-proof call 0.1 ms before its first kernel (profiles/r06_ab_variants.txt (15)).
-    const size_t in_end = (size_t)((uint8_t*)d_off - (uint8_t*)c->in_buf), res_end = (size_t)((uint8_t*)(d_st + bb) - (uint8_t*)c->in_buf);
+    const size_t in_end = (size_t)((uint8_t*)I.off - in_buf), res_end = (size_t)((uint8_t*)(I.st + bb) - in_buf);
     const bool staged = B && res_end <= ZK_STAGE_MAX;
     if (staged) {
         if ((zs = ensure_h_stage(c, res_end))) return zs;
-        auto at = [&](const void* d) { return c->h_stage + ((const uint8_t*)d - (const uint8_t*)c->in_buf); };
-        memcpy(at(d_msg), msg, 32 * B), memcpy(at(d_sig), sig, 64 * B), memcpy(at(d_pk), pk, 64 * B), memcpy(at(d_which), which, 4 * B), memcpy(at(d_rng), rng->data, rng_bytes);
-        HIPCHK(c, hipMemcpyAsync(c->in_buf, c->h_stage, in_end, hipMemcpyHostToDevice, c->stream));
+        auto at = [&](const void* d) { return c->h_stage + ((const uint8_t*)d - in_buf); };
+        memcpy(at(I.msg), msg, 32 * B), memcpy(at(I.sig), sig, 64 * B), memcpy(at(I.pk), pk, 64 * B), memcpy(at(I.which), which, 4 * B), memcpy(at(I.rng), rng->data, rng_bytes);
+        HIPCHK(c, hipMemcpyAsync(in_buf, c->h_stage, in_end, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipEventRecord(c->in_ready, c->stream));
     } else if (B) {
-        HIPCHK(c, hipMemcpyAsync(d_msg, msg, 32 * B, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_sig, sig, 64 * B, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_pk, pk, 64 * B, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_which, which, 4 * B, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_rng, rng->data, rng_bytes, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(I.msg, msg, 32 * B, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(I.sig, sig, 64 * B, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(I.pk, pk, 64 * B, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(I.which, which, 4 * B, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(I.rng, rng->data, rng_bytes, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));   // both lanes read these arrays
     }
     // a page-locked `out` (zk_host_alloc) receives each chunk by DMA while the next chunks are proved
@@ -1484,18 +1449,18 @@ static zk_status prove_host(zk_ctx* c, uint64_t B, const uint8_t* msg, const uin
         zs = ensure_copy_stream(c);
         if (zs) return zs;
     }
-    zs = prove_device(c, B, d_msg, d_sig, d_pk, d_which, rng->mode, d_rng, rng->stride_blocks, d_out, cap_dev, d_off, d_st, sink, staged ? c->in_ready : nullptr);
+    zs = prove_device(c, B, I.msg, I.sig, I.pk, I.which, rng->mode, I.rng, rng->stride_blocks, d_out, cap_dev, I.off, I.st, sink, staged ? c->in_ready : nullptr);
     if (zs) {
         if (staged) (void)hipStreamSynchronize(c->stream);   // the mirror is reused by the next call
         return zs;
     }
     if (staged) {   // offsets and statuses lie next to each other in in_buf: one copy
-        HIPCHK(c, hipMemcpy(c->h_stage + in_end, d_off, res_end - in_end, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(c->h_stage + in_end, I.off, res_end - in_end, hipMemcpyDeviceToHost));
         memcpy(out_off, c->h_stage + in_end, 8 * (B + 1));
-        memcpy(status, c->h_stage + ((uint8_t*)d_st - (uint8_t*)c->in_buf), 4 * B);
+        memcpy(status, c->h_stage + ((uint8_t*)I.st - in_buf), 4 * B);
     } else {
-        HIPCHK(c, hipMemcpy(out_off, d_off, 8 * (B + 1), hipMemcpyDeviceToHost));
-        if (B) HIPCHK(c, hipMemcpy(status, d_st, 4 * B, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(out_off, I.off, 8 * (B + 1), hipMemcpyDeviceToHost));
+        if (B) HIPCHK(c, hipMemcpy(status, I.st, 4 * B, hipMemcpyDeviceToHost));
     }
     if (!sink && !out_on_device && out_off[B]) HIPCHK(c, hipMemcpy(out, d_out, out_off[B], hipMemcpyDeviceToHost));
     return ZK_OK;
@@ -1507,21 +1472,37 @@ static zk_status prove_host(zk_ctx* c, uint64_t B, const uint8_t* msg, const uin
 // proofs of each ring lie in any index range that starts and ends at a multiple of PR_BLOCK, and where those proofs stand in the one stable
 // permutation by ring (k_part_perm) -- so a call needs no further census however it is cut.
 //   One ring, no unknown id: the usual pipeline on the caller's buffers with that ring bound.  Nothing else is launched.
-//   Otherwise the batch is cut into index-contiguous SEGMENTS whose proofs fit the staging buffer (c->ps_buf: ZK_PR_STAGE_BYTES, or one PR_BLOCK of the
-//   largest proofs if that is more).  Per segment and ring, WINDOWS of at most 2 x chunk x lanes proofs: the inputs are gathered into c->pw_buf, the
+//   Otherwise the batch is cut into index-contiguous SEGMENTS whose proofs fit the staging buffer (c->buf[B_ps]: ZK_PR_STAGE_BYTES, or one PR_BLOCK of the
+//   largest proofs if that is more).  Per segment and ring, WINDOWS of at most 2 x chunk x lanes proofs: the inputs are gathered into c->buf[B_pw], the
 //   window is proved with its ring bound (ensure_workspace re-binds, and re-carves only when n or the tables change) into the staging buffer behind the
 //   windows before it, and (staging offset, length, status) are recorded at every proof's own index.  A proof's size depends on its Exp challenge and its
 //   ring's n, so the final offsets exist only now: one scan over the segment's lengths in index order writes out_off, one byte mover (a workgroup
 //   per proof) writes `out` behind the previous segment's bytes.  A segment is finished before the next one starts; with a page-locked `out` its bytes
 //   cross the link on lane 0's copy stream under the next segment's kernels.
 #define ZK_PR_STAGE_BYTES (8ull << 30)
-static zk_status grow_dev(zk_ctx* c, void** buf, size_t* have, size_t need, bool shed) {   // grow-only device buffer
-    if (need <= *have) return ZK_OK;
-    if (*buf) HIPCHK(c, hipFree(*buf));
-    *buf = nullptr, *have = 0;
-    HIPCHK(c, shed ? malloc_or_shed(c, buf, need) : hipMalloc(buf, need));
-    *have = need;
-    return ZK_OK;
+// c->buf[B_pr]: the census and what the segments record; c->buf[B_pw]: the window one ring's inputs are gathered into
+struct ProveCensus {
+    uint8_t* cls;
+    uint32_t *cnts, *perm;
+    uint64_t *rec_off, *rec_len;
+};
+static size_t prove_census_layout(ProveCensus& X, uint8_t* base, uint64_t B, size_t ncnt, uint64_t seg_max) {
+    Carver k(base);
+    X.cls = (uint8_t*)k.take(B), X.cnts = (uint32_t*)k.take(4 * ncnt), X.perm = (uint32_t*)k.take(4 * B);
+    X.rec_off = (uint64_t*)k.take(8 * seg_max), X.rec_len = (uint64_t*)k.take(8 * seg_max);
+    return k.off + ZK_LAYOUT_TAIL;
+}
+struct ProveWindow {
+    uint8_t *msg, *sig, *pk, *rng;
+    uint32_t* which;
+    uint64_t* off;
+    int32_t* st;
+};
+static size_t prove_window_layout(ProveWindow& W, uint8_t* base, size_t Wp, size_t rng_row) {
+    Carver k(base);
+    W.msg = (uint8_t*)k.take(32 * Wp), W.sig = (uint8_t*)k.take(64 * Wp), W.pk = (uint8_t*)k.take(64 * Wp), W.which = (uint32_t*)k.take(4 * Wp);
+    W.rng = (uint8_t*)k.take(rng_row * Wp + 32), W.off = (uint64_t*)k.take(8 * (Wp + 1)), W.st = (int32_t*)k.take(4 * Wp);
+    return k.off + ZK_LAYOUT_TAIL;
 }
 static uint64_t ring_proof_max_size(const zk_ctx* c, const Ring* R) { return wire_proof_size(wire_make(c->wire == ZK_WIRE_ZKA1P), c->P.sec, R->n, c->P.sec); }
 static zk_status prove_rings_device(zk_ctx* c, uint64_t B, const uint8_t* d_msg, const uint8_t* d_sig, const uint8_t* d_pk, const uint32_t* d_which, const uint32_t* d_ids,
@@ -1537,28 +1518,18 @@ static zk_status prove_rings_device(zk_ctx* c, uint64_t B, const uint8_t* d_msg,
         HIPCHK(c, hipStreamSynchronize(s));
         return ZK_OK;
     }
-    RingSlots rs{};
+    RingSlots rs;
     Ring* slot[ZK_MAX_RINGS] = {};
     uint64_t max_any = 0;
-    for (auto& R : c->rings)
-        if (R.live && R.N) slot[rs.count] = &R, rs.id[rs.count++] = R.id, max_any = std::max(max_any, ring_proof_max_size(c, &R));
+    ring_slots(c, rs, slot);
+    for (uint32_t r = 0; r < rs.count; r++) max_any = std::max(max_any, ring_proof_max_size(c, slot[r]));
     // proofs per segment: what the staging buffer holds of the largest proof any resident ring can give, a multiple of PR_BLOCK
     uint64_t seg = c->pr_seg_force ? c->pr_seg_force : ZK_PR_STAGE_BYTES / (max_any ? max_any : 1);
     seg = std::max<uint64_t>(PR_BLOCK, seg & ~(uint64_t)(PR_BLOCK - 1));
     const uint64_t nblk = (B + PR_BLOCK - 1) / PR_BLOCK, seg_max = std::min<uint64_t>(seg, nblk * PR_BLOCK);
     const size_t ncnt = (size_t)(2 + nblk) * PR_CLASSES;
-    auto carve_pr = [&](Carver& k, uint8_t*& cls, uint32_t*& cnts, uint32_t*& perm, uint64_t*& rec_off, uint64_t*& rec_len) {
-        cls = (uint8_t*)k.take(B), cnts = (uint32_t*)k.take(4 * ncnt), perm = (uint32_t*)k.take(4 * B);
-        rec_off = (uint64_t*)k.take(8 * seg_max), rec_len = (uint64_t*)k.take(8 * seg_max);
-    };
-    uint8_t* cls;
-    uint32_t *cnts, *perm;
-    uint64_t *rec_off, *rec_len;
-    Carver k0(nullptr);
-    carve_pr(k0, cls, cnts, perm, rec_off, rec_len);
-    if (zk_status zs = grow_dev(c, &c->pr_buf, &c->pr_bytes, k0.off + 256, false)) return zs;
-    Carver k1((uint8_t*)c->pr_buf);
-    carve_pr(k1, cls, cnts, perm, rec_off, rec_len);
+    ProveCensus X;
+    if (zk_status zs = lay_out(c, B_pr, [&](uint8_t* base) { return prove_census_layout(X, base, B, ncnt, seg_max); })) return zs;
     if (4 * ncnt > c->h_pr_bytes) {
         if (c->h_pr) HIPCHK(c, hipHostFree(c->h_pr));
         c->h_pr = nullptr, c->h_pr_bytes = 0;
@@ -1566,9 +1537,9 @@ static zk_status prove_rings_device(zk_ctx* c, uint64_t B, const uint8_t* d_msg,
         c->h_pr_bytes = 8 * ncnt;
     }
     if (!c->pr_ready) HIPCHK(c, hipEventCreateWithFlags(&c->pr_ready, hipEventDisableTiming));
-    uint32_t *out = cnts, *blk = cnts + 2 * PR_CLASSES;   // totals and class starts, then the per-workgroup prefix sums
-    launch_pr_census(s, B, d_ids, rs, cls, blk, out);
-    HIPCHK(c, hipMemcpyAsync(c->h_pr, cnts, 4 * ncnt, hipMemcpyDeviceToHost, s));
+    uint32_t *out = X.cnts, *blk = X.cnts + 2 * PR_CLASSES;   // totals and class starts, then the per-workgroup prefix sums
+    launch_pr_census(s, B, d_ids, rs, X.cls, blk, out);
+    HIPCHK(c, hipMemcpyAsync(c->h_pr, X.cnts, 4 * ncnt, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     const uint32_t *cnt = c->h_pr, *start = c->h_pr + PR_CLASSES;
     auto before = [&](uint64_t b, uint32_t k) { return b < nblk ? c->h_pr[(2 + b) * PR_CLASSES + k] : cnt[k]; };   // proofs of class k in workgroups [0, b)
@@ -1580,24 +1551,13 @@ static zk_status prove_rings_device(zk_ctx* c, uint64_t B, const uint8_t* d_msg,
         RingBind rb(c, slot[last]);
         return prove_device(c, B, d_msg, d_sig, d_pk, d_which, rng_mode, d_rng, stride, d_out, out_cap, d_out_off, d_status, host_sink);
     }
-    launch_pr_perm(s, B, cls, blk, out, perm);
+    launch_pr_perm(s, B, X.cls, blk, out, X.perm);
     const uint32_t Wp = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(most, 2ull * c->chunk * c->lanes));
     const size_t rng_row = rng_mode == ZK_RNG_SEED ? 32 : 32 * (size_t)stride;
-    auto carve_pw = [&](Carver& k, uint8_t*& w_msg, uint8_t*& w_sig, uint8_t*& w_pk, uint32_t*& w_which, uint8_t*& w_rng, uint64_t*& w_off, int32_t*& w_st) {
-        w_msg = (uint8_t*)k.take(32 * (size_t)Wp), w_sig = (uint8_t*)k.take(64 * (size_t)Wp), w_pk = (uint8_t*)k.take(64 * (size_t)Wp), w_which = (uint32_t*)k.take(4 * (size_t)Wp);
-        w_rng = (uint8_t*)k.take(rng_row * Wp + 32), w_off = (uint64_t*)k.take(8 * ((size_t)Wp + 1)), w_st = (int32_t*)k.take(4 * (size_t)Wp);
-    };
-    uint8_t *w_msg, *w_sig, *w_pk, *w_rng;
-    uint32_t* w_which;
-    uint64_t* w_off;
-    int32_t* w_st;
-    Carver p0(nullptr);
-    carve_pw(p0, w_msg, w_sig, w_pk, w_which, w_rng, w_off, w_st);
-    if (zk_status zs = grow_dev(c, &c->pw_buf, &c->pw_bytes, p0.off + 256, true)) return zs;
-    Carver p1((uint8_t*)c->pw_buf);
-    carve_pw(p1, w_msg, w_sig, w_pk, w_which, w_rng, w_off, w_st);
-    if (zk_status zs = grow_dev(c, &c->ps_buf, &c->ps_bytes, (size_t)(std::min<uint64_t>(seg, B) * max_used + 256), true)) return zs;
-    uint8_t* stage = (uint8_t*)c->ps_buf;
+    ProveWindow W;
+    if (zk_status zs = lay_out(c, B_pw, [&](uint8_t* base) { return prove_window_layout(W, base, Wp, rng_row); })) return zs;
+    if (zk_status zs = reserve(c, B_ps, (size_t)(std::min<uint64_t>(seg, B) * max_used + 256))) return zs;
+    uint8_t* stage = (uint8_t*)c->buf[B_ps].p;
     zk_status zs = ZK_OK;
     hipError_t he = hipSuccess;
     auto hip = [&](hipError_t e) {
@@ -1615,30 +1575,30 @@ static zk_status prove_rings_device(zk_ctx* c, uint64_t B, const uint8_t* d_msg,
             RingBind rb(c, slot[r]);
             for (uint32_t w = 0; w < n_r && !zs && he == hipSuccess; w += Wp) {
                 const uint32_t n = std::min<uint32_t>(Wp, n_r - w);
-                const uint32_t* sel = perm + start[r] + first + w;
+                const uint32_t* sel = X.perm + start[r] + first + w;
                 c->dbg_pr_windows++;
-                launch_pr_gather(s, n, sel, d_msg, d_sig, d_pk, d_which, rng_mode == ZK_RNG_SEED ? d_rng : nullptr, w_msg, w_sig, w_pk, w_which, w_rng);
-                if (rng_mode == ZK_RNG_STREAM) launch_pr_gather_rows(s, n, sel, d_rng, rng_row, w_rng);
+                launch_pr_gather(s, n, sel, d_msg, d_sig, d_pk, d_which, rng_mode == ZK_RNG_SEED ? d_rng : nullptr, W.msg, W.sig, W.pk, W.which, W.rng);
+                if (rng_mode == ZK_RNG_STREAM) launch_pr_gather_rows(s, n, sel, d_rng, rng_row, W.rng);
                 if (!hip(hipEventRecord(c->pr_ready, s))) break;
                 uint64_t bytes = 0;
-                zs = prove_device(c, n, w_msg, w_sig, w_pk, w_which, rng_mode, w_rng, stride, stage + staged, c->ps_bytes - staged, w_off, w_st, nullptr, c->pr_ready, &bytes);
+                zs = prove_device(c, n, W.msg, W.sig, W.pk, W.which, rng_mode, W.rng, stride, stage + staged, c->buf[B_ps].bytes - staged, W.off, W.st, nullptr, c->pr_ready, &bytes);
                 if (zs) break;
-                launch_pr_record(s, n, sel, seg0, w_off, w_st, staged, rec_off, rec_len, d_status, 0);
+                launch_pr_record(s, n, sel, seg0, W.off, W.st, staged, X.rec_off, X.rec_len, d_status, 0);
                 staged += bytes;
             }
         }
         if (zs || he != hipSuccess) break;
         {   // ids that are not resident: empty proofs, ZK_E_ARG
             const uint32_t first = before(b0, PR_UNKNOWN), n_u = before(b1, PR_UNKNOWN) - first;
-            launch_pr_record(s, n_u, perm + start[PR_UNKNOWN] + first, seg0, nullptr, nullptr, 0, rec_off, rec_len, d_status, ZK_E_ARG);
+            launch_pr_record(s, n_u, X.perm + start[PR_UNKNOWN] + first, seg0, nullptr, nullptr, 0, X.rec_off, X.rec_len, d_status, ZK_E_ARG);
         }
         if (base + staged > out_cap) {
             c->err = "output buffer too small";
             zs = ZK_E_BUFFER;
             break;
         }
-        launch_pr_offsets(s, (uint32_t)(seg1 - seg0), rec_len, base, d_out_off + seg0);
-        launch_pr_move(s, (uint32_t)(seg1 - seg0), rec_off, rec_len, stage, d_out_off + seg0, d_out);
+        launch_pr_offsets(s, (uint32_t)(seg1 - seg0), X.rec_len, base, d_out_off + seg0);
+        launch_pr_move(s, (uint32_t)(seg1 - seg0), X.rec_off, X.rec_len, stage, d_out_off + seg0, d_out);
         if (host_sink && staged) {   // this segment's bytes are final: DMA them out behind the next segment's kernels
             if (!hip(hipEventRecord(c->pl[0].copy_ev, s)) || !hip(hipStreamWaitEvent(cs, c->pl[0].copy_ev, 0))) break;
             const uint64_t piece = 512ull << 20;   // one DMA command moves at most this much
@@ -1696,19 +1656,8 @@ extern "C" zk_status zk_prove_batch_rings(zk_ctx* c, uint64_t B, const uint8_t* 
     uint64_t bound = 0;   // no proof of the batch is larger than the largest resident ring's
     for (auto& R : c->rings)
         if (R.live && R.N) bound = std::max(bound, ring_proof_max_size(c, &R));
-    auto carve_in = [&](Carver& kk, uint8_t*& m, uint8_t*& sg, uint8_t*& p, uint32_t*& w, uint32_t*& ids, uint8_t*& r, uint64_t*& o, int32_t*& st_) {
-        m = (uint8_t*)kk.take(32 * B), sg = (uint8_t*)kk.take(64 * B), p = (uint8_t*)kk.take(64 * B), w = (uint32_t*)kk.take(4 * B), ids = (uint32_t*)kk.take(4 * B);
-        r = (uint8_t*)kk.take(rng_bytes ? rng_bytes : 32), o = (uint64_t*)kk.take(8 * (B + 1)), st_ = (int32_t*)kk.take(4 * B);
-    };
-    uint8_t *d_msg, *d_sig, *d_pk, *d_rng;
-    uint32_t *d_which, *d_ids;
-    uint64_t* d_off;
-    int32_t* d_st;
-    Carver k0(nullptr);
-    carve_in(k0, d_msg, d_sig, d_pk, d_which, d_ids, d_rng, d_off, d_st);
-    if (zk_status zs = ensure_in_buf(c, k0.off + 256)) return zs;
-    Carver k1((uint8_t*)c->in_buf);
-    carve_in(k1, d_msg, d_sig, d_pk, d_which, d_ids, d_rng, d_off, d_st);
+    ProveIn I;
+    if (zk_status zs = lay_out(c, B_in, [&](uint8_t* base) { return prove_in_layout(I, base, B, rng_bytes, true); })) return zs;
     bool out_on_device = false;
     hipPointerAttribute_t a;
     if (hipPointerGetAttributes(&a, out) == hipSuccess) out_on_device = a.type == hipMemoryTypeDevice;
@@ -1719,14 +1668,14 @@ extern "C" zk_status zk_prove_batch_rings(zk_ctx* c, uint64_t B, const uint8_t* 
     }
     const uint64_t cap_dev = out_on_device ? out_cap : std::min<uint64_t>(out_cap, bound * B);
     if (!out_on_device)
-        if (zk_status zs = ensure_io_buf(c, cap_dev ? cap_dev : 32)) return zs;
-    uint8_t* d_out = out_on_device ? out : (uint8_t*)c->io_buf;
+        if (zk_status zs = reserve(c, B_io, cap_dev ? cap_dev : 32)) return zs;
+    uint8_t* d_out = out_on_device ? out : (uint8_t*)c->buf[B_io].p;
     uint8_t* sink = !out_on_device && host_ptr_is_pinned(out) ? out : nullptr;
     if (sink)
         if (zk_status zs = ensure_copy_stream(c)) return zs;
     // from the first upload on, signatures and seeds lie in in_buf: every failure below zeroes them (prove_rings_device does so itself)
-    const struct { void* d; const void* h; size_t n; } up[] = {{d_msg, msg, 32 * B}, {d_sig, sig, 64 * B}, {d_pk, pk, 64 * B}, {d_which, which, 4 * B},
-                                                               {d_ids, ring_ids, 4 * B}, {d_rng, rng->data, rng_bytes}};
+    const struct { void* d; const void* h; size_t n; } up[] = {{I.msg, msg, 32 * B}, {I.sig, sig, 64 * B}, {I.pk, pk, 64 * B}, {I.which, which, 4 * B},
+                                                               {I.ids, ring_ids, 4 * B}, {I.rng, rng->data, rng_bytes}};
     for (auto& u : up)
         if (hipMemcpy(u.d, u.h, u.n, hipMemcpyHostToDevice) != hipSuccess) {
             c->err = "upload of the inputs failed";
@@ -1734,9 +1683,9 @@ extern "C" zk_status zk_prove_batch_rings(zk_ctx* c, uint64_t B, const uint8_t* 
             wipe_witness(c);
             return ZK_E_DEVICE;
         }
-    if (zk_status zs = prove_rings_device(c, B, d_msg, d_sig, d_pk, d_which, d_ids, rng->mode, d_rng, rng->stride_blocks, d_out, cap_dev, d_off, d_st, sink)) return zs;
-    hipError_t e = hipMemcpy(out_off, d_off, 8 * (B + 1), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(status, d_st, 4 * B, hipMemcpyDeviceToHost);
+    if (zk_status zs = prove_rings_device(c, B, I.msg, I.sig, I.pk, I.which, I.ids, rng->mode, I.rng, rng->stride_blocks, d_out, cap_dev, I.off, I.st, sink)) return zs;
+    hipError_t e = hipMemcpy(out_off, I.off, 8 * (B + 1), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(status, I.st, 4 * B, hipMemcpyDeviceToHost);
     if (e == hipSuccess && !sink && !out_on_device && out_off[B]) e = hipMemcpy(out, d_out, out_off[B], hipMemcpyDeviceToHost);
     if (e != hipSuccess) wipe_witness(c);
     HIPCHK(c, e);
@@ -1852,7 +1801,7 @@ static zk_status tom_commit_generic(zk_ctx* c, const uint32_t* tab_g, const uint
     void* mem;
     size_t per = 36 * 7;
     HIPCHK(c, hipMalloc(&mem, per * count + 4096 + 4 * (count + 1)));
-    Carver k((uint8_t*)mem);
+    SoaCarver k((uint8_t*)mem);
     L = k.list(count);
     uint32_t* d_list = (uint32_t*)((uint8_t*)mem + (per * count + 4096) / 4 * 4);   // shape 5 (k_tom_commit_list): the slots in reverse order, then their number
     launch_bytes_to_scalars(c->stream, d_v, count, L.v);

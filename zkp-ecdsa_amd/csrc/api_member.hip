@@ -10,7 +10,7 @@ zk_status make_default_vseeds(zk_ctx* c, uint64_t B, uint8_t* d_seeds, hipStream
 // W.sec only sizes the challenge hash's message buffers here (k_hash.hip: launch_gk_hash compares against the Exp challenge's block count): the GK message of
 // 4 n points fits the buffers of 2 n repetitions; the layout's repetition terms are zero (wire.rep_head = wire.padd = 0), so it moves no byte of the output.
 static size_t mcarve(zk_ctx* c, zk_ctx::MemberLane& L, uint8_t* base, uint32_t C, uint32_t n, uint64_t N) {
-    Carver k(base);
+    SoaCarver k(base);
     Workspace& W = L.W;
     W = Workspace{};
     W.C = C, W.sec = 2 * n, W.n = n, W.N = (uint32_t)N;
@@ -81,14 +81,7 @@ static zk_status ensure_member_lanes(zk_ctx* c, uint32_t C, uint32_t nlanes) {
     for (uint32_t l = 0; l < nlanes && l < ZK_MAX_LANES; l++) {
         auto& L = c->ml[l];
         if (!L.ready) {
-            const size_t need = mcarve(c, L, nullptr, C, n, c->ring->N);
-            if (need > L.arena_bytes) {
-                if (L.arena) HIPCHK(c, hipFree(L.arena));
-                L.arena = nullptr, L.arena_bytes = 0;
-                HIPCHK(c, malloc_or_shed(c, &L.arena, need));
-                L.arena_bytes = need;
-            }
-            mcarve(c, L, (uint8_t*)L.arena, C, n, c->ring->N);
+            if (zk_status zs = lay_out(c, L.arena, GROW_SHED, [&](uint8_t* base) { return mcarve(c, L, base, C, n, c->ring->N); })) return zs;
             L.ready = true;
         }
         // the ring's pointers are bound on every call (zk_ctx_use_ring, zk_ctx_update_ring, zk_ctx_set_ring_fold)
@@ -101,10 +94,7 @@ static zk_status ensure_member_lanes(zk_ctx* c, uint32_t C, uint32_t nlanes) {
 }
 static zk_status member_refusal(zk_ctx* c) {
     if (!c->params_set || !c->ring->N) return ZK_E_BUFFER;
-    if (c->stream_busy) {
-        c->err = "streamed jobs are in flight on this context (zk_prove_wait / zk_verify_wait them first)";
-        return ZK_E_ARG;
-    }
+    if (c->stream_busy) return busy_refusal(c);
     if (c->mode == ZK_MODE_HARDENED) {
         c->err = "membership proofs on their own have no statement to bind: not available in ZK_MODE_HARDENED";
         return ZK_E_ARG;
@@ -199,6 +189,17 @@ extern "C" zk_status zk_member_prove_batch_device(zk_ctx* c, uint64_t B, const v
                                (uint8_t*)d_out, out_cap, (int32_t*)d_status);
 }
 // Host pointers: the small arrays through the context's input buffer (witness-derived: wiped with it), the proofs through its output staging buffer.
+struct MemberProveIn {
+    uint32_t* which;
+    uint8_t *blinder, *rng, *com, *blinder_out;
+    int32_t* st;
+};
+static size_t member_prove_in_layout(MemberProveIn& I, uint8_t* base, size_t B, size_t rng_bytes) {
+    Carver k(base);
+    I.which = (uint32_t*)k.take(4 * B), I.blinder = (uint8_t*)k.take(32 * B), I.rng = (uint8_t*)k.take(rng_bytes ? rng_bytes : 32), I.com = (uint8_t*)k.take(72 * B);
+    I.blinder_out = (uint8_t*)k.take(32 * B), I.st = (int32_t*)k.take(4 * B);
+    return k.off + ZK_LAYOUT_TAIL;
+}
 extern "C" zk_status zk_member_prove_batch(zk_ctx* c, uint64_t B, const uint32_t* which, const uint8_t* blinder, const zk_rng* rng, uint8_t* com, uint8_t* blinder_out,
                                            uint8_t* out, uint64_t out_cap, int32_t* status) {
     if (!c || !rng || (B && (!which || !rng->data || !com || !out || !status))) return ZK_E_ARG;
@@ -212,31 +213,22 @@ extern "C" zk_status zk_member_prove_batch(zk_ctx* c, uint64_t B, const uint32_t
     }
     if (B == 0) return ZK_OK;
     const size_t rng_bytes = rng->mode == ZK_RNG_SEED ? 32 * B : 32 * B * rng->stride_blocks;
-    Carver k(nullptr);
-    auto carve_in = [&](Carver& kk, uint32_t*& w, uint8_t*& bl, uint8_t*& r, uint8_t*& cm, uint8_t*& bo, int32_t*& st) {
-        w = (uint32_t*)kk.take(4 * B), bl = (uint8_t*)kk.take(32 * B), r = (uint8_t*)kk.take(rng_bytes ? rng_bytes : 32), cm = (uint8_t*)kk.take(72 * B);
-        bo = (uint8_t*)kk.take(32 * B), st = (int32_t*)kk.take(4 * B);
-    };
-    uint32_t* d_which;
-    uint8_t *d_bl, *d_rng, *d_com, *d_bo;
-    int32_t* d_st;
-    carve_in(k, d_which, d_bl, d_rng, d_com, d_bo, d_st);
-    if (zk_status zs = ensure_in_buf(c, k.off + 256)) return zs;
-    if (zk_status zs = ensure_io_buf(c, B * size)) return zs;
-    Carver k2((uint8_t*)c->in_buf);
-    carve_in(k2, d_which, d_bl, d_rng, d_com, d_bo, d_st);
+    MemberProveIn I;
+    if (zk_status zs = lay_out(c, B_in, [&](uint8_t* base) { return member_prove_in_layout(I, base, B, rng_bytes); })) return zs;
+    if (zk_status zs = reserve(c, B_io, B * size)) return zs;
+    uint8_t* const d_out = (uint8_t*)c->buf[B_io].p;
     hipStream_t s = c->stream;
-    HIPCHK(c, hipMemcpyAsync(d_which, which, 4 * B, hipMemcpyHostToDevice, s));
-    if (blinder) HIPCHK(c, hipMemcpyAsync(d_bl, blinder, 32 * B, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_rng, rng->data, rng_bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(I.which, which, 4 * B, hipMemcpyHostToDevice, s));
+    if (blinder) HIPCHK(c, hipMemcpyAsync(I.blinder, blinder, 32 * B, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(I.rng, rng->data, rng_bytes, hipMemcpyHostToDevice, s));
     HIPCHK(c, hipStreamSynchronize(s));   // the lanes' streams start behind the inputs
-    zk_status zs = member_prove_device(c, B, d_which, blinder ? d_bl : nullptr, rng->mode, d_rng, rng->stride_blocks, d_com, blinder_out ? d_bo : nullptr, (uint8_t*)c->io_buf,
-                                       B * size, d_st);
+    zk_status zs = member_prove_device(c, B, I.which, blinder ? I.blinder : nullptr, rng->mode, I.rng, rng->stride_blocks, I.com, blinder_out ? I.blinder_out : nullptr, d_out,
+                                       B * size, I.st);
     if (zs) return zs;
-    HIPCHK(c, hipMemcpyAsync(out, c->io_buf, B * size, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(com, d_com, 72 * B, hipMemcpyDeviceToHost, s));
-    if (blinder_out) HIPCHK(c, hipMemcpyAsync(blinder_out, d_bo, 32 * B, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(status, d_st, 4 * B, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(out, d_out, B * size, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(com, I.com, 72 * B, hipMemcpyDeviceToHost, s));
+    if (blinder_out) HIPCHK(c, hipMemcpyAsync(blinder_out, I.blinder_out, 32 * B, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(status, I.st, 4 * B, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     return ZK_OK;
 }
@@ -252,27 +244,16 @@ static zk_status member_verify_device(zk_ctx* c, uint64_t B, const uint8_t* d_co
     const std::vector<ChunkPlan> plan = make_chunk_plan(B, C, 1, false);
     const uint32_t NL = (uint32_t)std::min<size_t>(c->lanes, plan.size());
     if (zk_status zs = ensure_member_lanes(c, C, NL)) return zs;
-    if (c->m_off_entries < B + 1) {
-        if (c->m_off) HIPCHK(c, hipFree(c->m_off));
-        c->m_off = nullptr, c->m_off_entries = 0;
-        const size_t want = B + 1 + B / 4 + 512;
-        HIPCHK(c, hipMalloc((void**)&c->m_off, 8 * want));
-        c->m_off_entries = want;
-    }
-    launch_mv_offsets(c->stream, c->m_off, B, size);
+    if (zk_status zs = reserve(c, B_m_off, 8 * (B + 1))) return zs;
+    uint64_t* const d_off = (uint64_t*)c->buf[B_m_off].p;
+    launch_mv_offsets(c->stream, d_off, B, size);
     if (!d_vseeds) {   // the verifier's own seeds (api_verify.hip): fresh OS randomness per call
-        if (c->seed_bytes < 32 * B) {
-            if (c->seed_buf) HIPCHK(c, hipFree(c->seed_buf));
-            c->seed_buf = nullptr, c->seed_bytes = 0;
-            HIPCHK(c, hipMalloc(&c->seed_buf, 32 * B + 32 * B / 4 + 4096));
-            c->seed_bytes = 32 * B + 32 * B / 4 + 4096;
-        }
-        if (zk_status zs = make_default_vseeds(c, B, (uint8_t*)c->seed_buf, c->stream)) return zs;
-        d_vseeds = (const uint8_t*)c->seed_buf;
+        if (zk_status zs = reserve(c, B_seed, 32 * B)) return zs;
+        if (zk_status zs = make_default_vseeds(c, B, (uint8_t*)c->buf[B_seed].p, c->stream)) return zs;
+        d_vseeds = (const uint8_t*)c->buf[B_seed].p;
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));   // offsets and seeds are there before any lane reads them
     const bool timed = zk_timed(c, B);
-    const uint64_t* d_off = c->m_off;
     for (uint64_t k = 0; k < plan.size(); k++) {
         const uint32_t lane = (uint32_t)(k % NL), cnt = plan[k].cnt;
         const uint64_t first = plan[k].first;
@@ -316,31 +297,33 @@ extern "C" zk_status zk_member_verify_batch_device(zk_ctx* c, uint64_t B, const 
     HIPCHK(c, hipSetDevice(c->device));
     return member_verify_device(c, B, (const uint8_t*)d_com, (const uint8_t*)d_proofs, (const uint8_t*)d_vseeds, (uint8_t*)d_ok, (int32_t*)d_status);
 }
+struct MemberVerifyIn {
+    uint8_t *com, *seeds, *ok;
+    int32_t* st;
+};
+static size_t member_verify_in_layout(MemberVerifyIn& I, uint8_t* base, size_t B) {
+    Carver k(base);
+    I.com = (uint8_t*)k.take(72 * B), I.seeds = (uint8_t*)k.take(32 * B), I.ok = (uint8_t*)k.take(B), I.st = (int32_t*)k.take(4 * B);
+    return k.off + ZK_LAYOUT_TAIL;
+}
 extern "C" zk_status zk_member_verify_batch(zk_ctx* c, uint64_t B, const uint8_t* com, const uint8_t* proofs, const uint8_t* vseeds, uint8_t* ok, int32_t* status) {
     if (!c || (B && (!com || !proofs || !ok || !status))) return ZK_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     if (zk_status zs = member_refusal(c)) return zs;
     if (B == 0) return ZK_OK;
     const uint64_t size = zkm1_size(c->ring->n);
-    Carver k(nullptr);
-    auto carve_in = [&](Carver& kk, uint8_t*& cm, uint8_t*& vs, uint8_t*& o, int32_t*& st) {
-        cm = (uint8_t*)kk.take(72 * B), vs = (uint8_t*)kk.take(32 * B), o = (uint8_t*)kk.take(B), st = (int32_t*)kk.take(4 * B);
-    };
-    uint8_t *d_com, *d_vs, *d_ok;
-    int32_t* d_st;
-    carve_in(k, d_com, d_vs, d_ok, d_st);
-    if (zk_status zs = ensure_in_buf(c, k.off + 256)) return zs;
-    if (zk_status zs = ensure_io_buf(c, B * size)) return zs;
-    Carver k2((uint8_t*)c->in_buf);
-    carve_in(k2, d_com, d_vs, d_ok, d_st);
+    MemberVerifyIn I;
+    if (zk_status zs = lay_out(c, B_in, [&](uint8_t* base) { return member_verify_in_layout(I, base, B); })) return zs;
+    if (zk_status zs = reserve(c, B_io, B * size)) return zs;
+    uint8_t* const d_proofs = (uint8_t*)c->buf[B_io].p;
     hipStream_t s = c->stream;
-    HIPCHK(c, hipMemcpyAsync(d_com, com, 72 * B, hipMemcpyHostToDevice, s));
-    if (vseeds) HIPCHK(c, hipMemcpyAsync(d_vs, vseeds, 32 * B, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(c->io_buf, proofs, B * size, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(I.com, com, 72 * B, hipMemcpyHostToDevice, s));
+    if (vseeds) HIPCHK(c, hipMemcpyAsync(I.seeds, vseeds, 32 * B, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_proofs, proofs, B * size, hipMemcpyHostToDevice, s));
     HIPCHK(c, hipStreamSynchronize(s));
-    if (zk_status zs = member_verify_device(c, B, d_com, (const uint8_t*)c->io_buf, vseeds ? d_vs : nullptr, d_ok, d_st)) return zs;
-    HIPCHK(c, hipMemcpyAsync(ok, d_ok, B, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(status, d_st, 4 * B, hipMemcpyDeviceToHost, s));
+    if (zk_status zs = member_verify_device(c, B, I.com, d_proofs, vseeds ? I.seeds : nullptr, I.ok, I.st)) return zs;
+    HIPCHK(c, hipMemcpyAsync(ok, I.ok, B, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(status, I.st, 4 * B, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     return ZK_OK;
 }

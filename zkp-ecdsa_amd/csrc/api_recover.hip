@@ -3,12 +3,12 @@
 // A call runs in chunks of ZK_RECOVER_CHUNK witnesses on the context's main stream, like the screen.  Per chunk: two passes of lift -> points (x = r, then
 // x = r + n, whose workgroups leave at once outside adversarial inputs; nothing is read back to decide), the screen's lookup over the candidate buffer as
 // up to 4 x count pseudo-witnesses -- once for the active ring, or once per resident ring for the _rings forms --, and the selection.  Nothing of the
-// prover's, the verifier's or the screen's state is touched: the only memory is c->rec_buf, allocated by the first call.
+// prover's, the verifier's or the screen's state is touched: the only memory is c->buf[B_rec], allocated by the first call.
 #include "jobs.h"   // ctx.h, MaybeScope
 #include "recover.h"   // REC_NCAND
 
 #define ZK_RECOVER_CHUNK 16384u
-// c->rec_buf: the chunk's buffers, then (host-pointer forms) its inputs and results
+// c->buf[B_rec]: the chunk's buffers, then (host-pointer forms) its inputs and results
 struct RecoverStage {
     RecoverBuf buf;
     uint8_t *msg, *sig, *pk_out;
@@ -26,17 +26,8 @@ static size_t recover_carve(RecoverStage& S, uint8_t* base) {
 }
 static zk_status recover_prepare(zk_ctx* c, bool rings, RecoverStage& S) {
     if (!c->params_set || (!rings && !c->ring->N)) return ZK_E_BUFFER;
-    if (c->stream_busy) {
-        c->err = "streamed jobs are in flight on this context (zk_prove_wait / zk_verify_wait them first)";
-        return ZK_E_ARG;
-    }
-    const size_t need = recover_carve(S, nullptr);
-    if (!c->rec_buf) {
-        HIPCHK(c, hipMalloc(&c->rec_buf, need));
-        c->rec_bytes = need;
-    }
-    recover_carve(S, (uint8_t*)c->rec_buf);
-    return ZK_OK;
+    if (c->stream_busy) return busy_refusal(c);
+    return lay_out(c, B_rec, [&](uint8_t* base) { return recover_carve(S, base); });
 }
 static ScreenRing recover_ring(const Ring& R) {   // (the lookup reads the limbs only)
     ScreenRing G;
@@ -74,7 +65,7 @@ static zk_status recover_fail(zk_ctx* c, hipError_t e, const char* what) {
     snprintf(buf, sizeof buf, "%s failed: %s (api_recover.hip)", what, hipGetErrorString(e));
     c->err = buf;
     (void)hipStreamSynchronize(c->stream);
-    (void)hipMemset(c->rec_buf, 0, c->rec_bytes);
+    (void)hipMemset(c->buf[B_rec].p, 0, c->buf[B_rec].bytes);
     (void)hipGetLastError();
     return ZK_E_DEVICE;
 }

@@ -4,11 +4,11 @@
 // ring of the call makes one pass (the lookup in find mode, then the front end of the ring's witnesses: checks, scalars, the choice of the path), and the
 // point arithmetic runs once over the whole chunk.  The plain forms have one ring, the active one; the _rings forms pass over every resident ring -- at
 // most ZK_MAX_RINGS -- with the witnesses of the other rings idle (a workgroup without a witness of the ring leaves at once), which needs no census of
-// the ids and no read-back.  Nothing of the prover's or verifier's state is touched: the only memory is c->scr_buf, allocated by the first call.
+// the ids and no read-back.  Nothing of the prover's or verifier's state is touched: the only memory is c->buf[B_scr], allocated by the first call.
 #include "jobs.h"   // ctx.h, MaybeScope
 
 #define ZK_SCREEN_CHUNK 16384u
-// c->scr_buf: the scratch areas, then (host-pointer forms) the chunk's inputs and results
+// c->buf[B_scr]: the scratch areas, then (host-pointer forms) the chunk's inputs and results
 struct ScreenStage {
     uint32_t* scratch;
     uint8_t *msg, *sig, *pk;
@@ -24,17 +24,8 @@ static size_t screen_carve(ScreenStage& S, uint8_t* base) {
 }
 static zk_status screen_prepare(zk_ctx* c, bool rings, ScreenStage& S) {
     if (!c->params_set || (!rings && !c->ring->N)) return ZK_E_BUFFER;
-    if (c->stream_busy) {
-        c->err = "streamed jobs are in flight on this context (zk_prove_wait / zk_verify_wait them first)";
-        return ZK_E_ARG;
-    }
-    const size_t need = screen_carve(S, nullptr);
-    if (!c->scr_buf) {
-        HIPCHK(c, hipMalloc(&c->scr_buf, need));
-        c->scr_bytes = need;
-    }
-    screen_carve(S, (uint8_t*)c->scr_buf);
-    return ZK_OK;
+    if (c->stream_busy) return busy_refusal(c);
+    return lay_out(c, B_scr, [&](uint8_t* base) { return screen_carve(S, base); });
 }
 static ScreenRing screen_ring(const Ring& R) {
     ScreenRing G;
@@ -64,7 +55,7 @@ static zk_status screen_fail(zk_ctx* c, hipError_t e, const char* what) {
     snprintf(buf, sizeof buf, "%s failed: %s (api_screen.hip)", what, hipGetErrorString(e));
     c->err = buf;
     (void)hipStreamSynchronize(c->stream);
-    (void)hipMemset(c->scr_buf, 0, c->scr_bytes);
+    (void)hipMemset(c->buf[B_scr].p, 0, c->buf[B_scr].bytes);
     (void)hipGetLastError();
     return ZK_E_DEVICE;
 }

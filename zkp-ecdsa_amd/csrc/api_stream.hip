@@ -86,7 +86,7 @@ static zk_status get_pinned(zk_ctx* c, size_t bytes, void** p, size_t* got) {
     *got = bytes;
     return ZK_OK;
 }
-void* stream_take_spare_dev(zk_ctx* c, size_t bytes, size_t* got) { return take_spare(c->spare_dev, bytes, got); }   // ensure_io_buf (api.hip)
+void* stream_take_spare_dev(zk_ctx* c, size_t bytes, size_t* got) { return take_spare(c->spare_dev, bytes, got); }   // reserve, GROW_SPARE (api.hip)
 void stream_release_spares(zk_ctx* c) {   // zk_ctx_destroy: the jobs' staged inputs (signatures, seeds) are zeroed before the memory goes back
     for (auto& s : c->spare_dev) (void)hipMemset(s.p, 0, s.bytes), hipFree(s.p);
     for (auto& s : c->spare_pinned) memset(s.p, 0, s.bytes), hipHostFree(s.p);
@@ -162,9 +162,9 @@ static zk_status stream_common(zk_ctx* c, int kind) {
     // order and the context already owns eight (api.hip, zk_ctx_create) -- a ninth stream would share lane 0's queue, and the
     // finisher's "wait for every lane" would stall the kernels of the next job queued behind it there.
     if (!c->fin_stream) c->fin_stream = c->pl[ZK_MAX_LANES - 1].copy_stream;
-    if (c->io_buf) {   // the synchronous calls' staging buffer serves as a job's (it comes back through the pool: ensure_io_buf)
-        c->spare_dev.push_back({c->io_buf, c->io_bytes});
-        c->io_buf = nullptr, c->io_bytes = 0;
+    if (GrowBuf& io = c->buf[B_io]; io.p) {   // the synchronous calls' staging buffer serves as a job's (it comes back through the pool: reserve, GROW_SPARE)
+        c->spare_dev.push_back({io.p, io.bytes});
+        io.p = nullptr, io.bytes = 0;
     }
     zk_status zs = ensure_copy_stream(c);
     if (zs) return zs;
@@ -567,7 +567,24 @@ extern "C" uint64_t zk_test_counter(const zk_ctx* c, int which) {
     if (which == 6) return c->dbg_etab_blocks;   // 256-key blocks whose table E was built
     if (which == 7) return c->dbg_pr_segments;   // segments staged by mixed-ring prove calls
     if (which == 8) return c->dbg_pr_windows;    // windows proved by mixed-ring prove calls
-    if (which == 9) return c->ps_bytes;          // bytes of the staging buffer mixed-ring prove calls have grown so far
+    if (which == 9) return c->buf[B_ps].bytes;         // bytes of the staging buffer mixed-ring prove calls have grown so far
+    if (which == 11) {   // nonzero 32-bit words in what wipe_witness zeroes -- the witness-flagged buffers, the prover's and the member lanes' arenas -- with nothing in flight
+        std::vector<const GrowBuf*> bufs;
+        for (const GrowBuf& b : c->buf)
+            if (b.witness) bufs.push_back(&b);
+        for (int l = 0; l < ZK_MAX_LANES; l++) bufs.push_back(&c->pl[l].arena), bufs.push_back(&c->ml[l].arena);
+        if (hipSetDevice(c->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return ~0ull;
+        std::vector<uint32_t> piece((size_t)4 << 20);   // 16 MiB per copy
+        uint64_t n = 0;
+        for (const GrowBuf* b : bufs)
+            for (size_t o = 0; o < b->bytes; o += 4 * piece.size()) {
+                const size_t len = std::min(b->bytes - o, 4 * piece.size());
+                piece[(len - 1) / 4] = 0;   // (a buffer's last word may be a partial one)
+                if (hipMemcpy(piece.data(), (const uint8_t*)b->p + o, len, hipMemcpyDeviceToHost) != hipSuccess) return ~0ull;
+                for (size_t i = 0; i < (len + 3) / 4; i++) n += piece[i] != 0;
+            }
+        return n;
+    }
     if (which == 10) return c->params_set ? c->P.tom_model : ~0ull;   // form of the comb tables of g and h (curve.h): 1 = the a = -1 model (both bases of odd order), 0 = the a = 1 image
     return which == 0 ? c->dbg_recheck_proofs : which == 2 ? c->dbg_msm_terms : which == 3 ? c->dbg_p256_batched : 0;
 }

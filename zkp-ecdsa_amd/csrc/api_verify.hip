@@ -1,11 +1,12 @@
-// zk_verify_batch / zk_verify_batch_device: host-side phase pipeline of the verifier (kernels in k_verify.hip).
+// zk_verify_batch / zk_verify_batch_device: host-side phase pipeline of the verifier (kernels in k_verify.hip), and the partitioned batches on top of it:
+// per-proof levels (verify_per_proof) and mixed rings (verify_rings_device), which run their own census and hand its classes to one window driver (WindowRun).
 #include "ctx.h"
 #include "jobs.h"
 #include <optional>
 
 static size_t vcarve(VWork& V, Soa& res, Soa& res2, MsmBuf& M, PMsmBuf& PM, uint8_t* base, uint32_t C, uint32_t sec, uint32_t n, uint64_t N, bool want_msm, bool want_pm,
                      uint32_t want_groups) {
-    Carver k(base);
+    SoaCarver k(base);
     V.C = C, V.sec = sec, V.n = n;
     V.gk_fixed = ZK_FIXED, V.com = nullptr;
     V.st = (int32_t*)k.take(4 * (size_t)C);
@@ -98,14 +99,10 @@ zk_status ensure_vworkspace(zk_ctx* c, uint32_t C, uint32_t nlanes) {
     for (uint32_t l = 0; l < nlanes && l < ZK_MAX_LANES; l++) {
         auto& L = c->vl[l];
         if (L.ready) continue;
-        size_t need = vcarve(L.V, L.res, L.res2, L.M, L.PM, nullptr, C, sec, n, c->ring->N, want_msm, want_pm, c->verify_groups);
-        if (need > L.arena_bytes) {
-            if (L.arena) HIPCHK(c, hipFree(L.arena));
-            L.arena = nullptr, L.arena_bytes = 0;
-            HIPCHK(c, malloc_or_shed(c, &L.arena, need));
-            L.arena_bytes = need;
-        }
-        vcarve(L.V, L.res, L.res2, L.M, L.PM, (uint8_t*)L.arena, C, sec, n, c->ring->N, want_msm, want_pm, c->verify_groups);
+        if (zk_status zs = lay_out(c, L.arena, GROW_SHED, [&](uint8_t* base) {
+                return vcarve(L.V, L.res, L.res2, L.M, L.PM, base, C, sec, n, c->ring->N, want_msm, want_pm, c->verify_groups);
+            }))
+            return zs;
         if (!L.h_msm) HIPCHK(c, hipHostMalloc((void**)&L.h_msm, 1024, hipHostMallocMapped | hipHostMallocCoherent));
         if (!L.aux_fork) HIPCHK(c, hipEventCreateWithFlags(&L.aux_fork, hipEventDisableTiming));
         for (int i = 0; i < V_AUX_STREAMS; i++) {
@@ -655,10 +652,7 @@ static zk_status verify_device(zk_ctx* c, uint64_t B, const uint8_t* d_msg, cons
     if (!c->params_set || !c->ring->N) return ZK_E_BUFFER;
     if (plan_sec(c) < VK && !c->v_sec_on) return ZK_E_SECLEVEL;   // (a per-proof-mode call at a level below VK verifies membership only)
     if (B == 0) return ZK_OK;
-    if (c->stream_busy) {
-        c->err = "streamed jobs are in flight on this context (zk_prove_wait / zk_verify_wait them first)";
-        return ZK_E_ARG;
-    }
+    if (c->stream_busy) return busy_refusal(c);
     VerifyJob J;
     J.c = c, J.B = B, J.d_msg = d_msg, J.d_proofs = d_proofs, J.d_off = d_off, J.d_ok = d_ok, J.d_status = d_status, J.host_src = host_src, J.host_off = host_off;
     J.timed = zk_timed(c, B);
@@ -674,20 +668,9 @@ static zk_status verify_device(zk_ctx* c, uint64_t B, const uint8_t* d_msg, cons
         uint64_t total = 0;
         if (host_off) total = host_off[B];
         else HIPCHK(c, hipMemcpy(&total, d_off + B, 8, hipMemcpyDeviceToHost));
-        const size_t need = unpack_stage_bytes(B, total, J.C), ents = unpack_off_entries(B, J.C);
-        if (need > c->unp_bytes) {
-            if (c->unp_buf) HIPCHK(c, hipFree(c->unp_buf));
-            c->unp_buf = nullptr, c->unp_bytes = 0;
-            HIPCHK(c, hipMalloc(&c->unp_buf, need));
-            c->unp_bytes = need;
-        }
-        if (ents > c->unp_off_entries) {
-            if (c->unp_off) HIPCHK(c, hipFree(c->unp_off));
-            c->unp_off = nullptr, c->unp_off_entries = 0;
-            HIPCHK(c, hipMalloc((void**)&c->unp_off, 8 * ents));
-            c->unp_off_entries = ents;
-        }
-        J.d_packed = d_proofs, J.d_poff = d_off, J.d_proofs = (const uint8_t*)c->unp_buf, J.d_uoff = c->unp_off;
+        if (zk_status zs = reserve(c, B_unp, unpack_stage_bytes(B, total, J.C))) return zs;
+        if (zk_status zs = reserve(c, B_unp_off, 8 * unpack_off_entries(B, J.C))) return zs;
+        J.d_packed = d_proofs, J.d_poff = d_off, J.d_proofs = (const uint8_t*)c->buf[B_unp].p, J.d_uoff = (uint64_t*)c->buf[B_unp_off].p;
         zk_status zp = J.plan_unpack();
         if (zp) return zp;
     }
@@ -697,15 +680,10 @@ static zk_status verify_device(zk_ctx* c, uint64_t B, const uint8_t* d_msg, cons
     if (zs) return zs;
     timing_begin(c);
     if (!d_vseeds) {   // the verifier's own seeds: the context's grow-only buffer, derived on c->stream (no allocation, copy or host wait per call)
-        if (c->seed_bytes < 32 * B) {
-            if (c->seed_buf) HIPCHK(c, hipFree(c->seed_buf));
-            c->seed_buf = nullptr, c->seed_bytes = 0;
-            HIPCHK(c, hipMalloc(&c->seed_buf, 32 * B + 32 * B / 4 + 4096));
-            c->seed_bytes = 32 * B + 32 * B / 4 + 4096;
-        }
-        zs = make_default_vseeds(c, B, (uint8_t*)c->seed_buf, c->stream);
+        if ((zs = reserve(c, B_seed, 32 * B))) return zs;
+        d_vseeds = (const uint8_t*)c->buf[B_seed].p;
+        zs = make_default_vseeds(c, B, (uint8_t*)c->buf[B_seed].p, c->stream);
         if (zs) return zs;
-        d_vseeds = (const uint8_t*)c->seed_buf;
         inputs_on_stream = true;
     }
     J.d_vseeds = d_vseeds;
@@ -769,313 +747,265 @@ uint32_t host_level_census(const zk_ctx* c, uint64_t B, const uint8_t* proofs, c
     }
     return lvl;
 }
-static zk_status grow(zk_ctx* c, void** buf, size_t* have, size_t need) {   // grow-only device buffer
-    if (need <= *have) return ZK_OK;
-    if (*buf) HIPCHK(c, hipFree(*buf));
-    *buf = nullptr, *have = 0;
-    HIPCHK(c, hipMalloc(buf, need));
-    *have = need;
-    return ZK_OK;
+// ------------------------------------------------------------------ partitioned verification: what the per-proof levels and the mixed rings share
+// What a census leaves in c->buf[B_lv] / c->buf[B_rg]: every proof's class (one or two bytes), the per-workgroup counts, the totals and class starts, and
+// the stable permutation by class
+namespace {   // (nothing of the driver is another unit's business)
+struct Census {
+    void* cls;
+    uint32_t *blk, *out, *perm;
+};
+static size_t census_layout(Census& X, uint8_t* base, uint64_t B, size_t cls_bytes, size_t classes) {
+    Carver k(base);
+    const uint64_t nblk = (B + LV_BLOCK - 1) / LV_BLOCK;
+    X.cls = k.take(cls_bytes * B), X.blk = (uint32_t*)k.take(4 * nblk * classes), X.out = (uint32_t*)k.take(8 * classes), X.perm = (uint32_t*)k.take(4 * B);
+    return k.off + ZK_LAYOUT_TAIL;
 }
-// One window of a partitioned batch: the n proofs sel[0 .. n) gathered into the window buffers (c->lb_buf for the bytes), verified as a batch of their
-// own with whatever ring and level the caller bound, their verdicts scattered back.  The partition's kernels are timed into *part_ms, the window's
-// families summed into *fam.
+// c->buf[B_lw]: the window a class's proofs are gathered into -- offsets, message hashes, seeds, verdicts, statuses (the bytes go to c->buf[B_lb])
+struct Window {
+    uint64_t* off;
+    uint8_t *msg, *seeds, *ok;
+    int32_t* st;
+};
+static size_t window_layout(Window& W, uint8_t* base, size_t Wp) {
+    Carver k(base);
+    W.off = (uint64_t*)k.take(8 * (Wp + 1)), W.msg = (uint8_t*)k.take(32 * Wp), W.seeds = (uint8_t*)k.take(32 * Wp);
+    W.ok = (uint8_t*)k.take(Wp), W.st = (int32_t*)k.take(4 * Wp);
+    return k.off + ZK_LAYOUT_TAIL;
+}
+struct WindowClass {   // one class of the partition: perm[start .. start + count) are its proofs
+    Ring* ring;        // bound while they are verified; nullptr: the ring that is bound already
+    int level;         // planned while they are verified; -1: the context's
+    uint32_t start, count;
+};
+// The driver of a partitioned batch.  Its caller runs the census, takes its common-case shortcut on the caller's buffers, scatters the statuses that need no
+// verification (both inside part(), which times the partition's own kernels) and hands run() the classes.  run() cuts each class into windows of at most
+// 2 x chunk x lanes proofs: a window's proofs are gathered into c->buf[B_lw] / c->buf[B_lb], verified as a batch of their own with the class's ring bound and
+// its level planned, their verdicts scattered back.  zk_last_timing then reports the windows' families, summed, and the partition's kernels (census,
+// permutation, gathers, scatters) as the family `family`.
 struct WindowRun {
     zk_ctx* c;
+    const char* family;
     hipStream_t s;
-    bool timed;
-    hipEvent_t* ev;
-    float* part_ms;
-    std::vector<std::pair<const char*, float>>* fam;
-    const uint8_t *d_msg, *d_proofs;
-    const uint64_t* d_off;
-    const uint8_t* d_vseeds;
-    uint8_t* d_ok;
-    int32_t* d_st;
-    uint64_t* w_off;
-    uint8_t *w_msg, *w_seeds, *w_ok;
-    int32_t* w_st;
-    uint64_t* h_total;   // page-locked
-    void lap() {
-        float ms = 0;
-        if (timed && hipEventElapsedTime(&ms, ev[2], ev[3]) == hipSuccess) *part_ms += ms;
+    const bool timed;
+    const int timing_mode;   // the context's: the windows run with the call's (run), and it is put back on every path
+    hipEvent_t ev[4] = {};   // part(): 0, 1; a window's gather and scatter: 2, 3
+    float part_ms = 0;
+    std::vector<std::pair<const char*, float>> fam;
+    WindowRun(zk_ctx* c_, uint64_t B, const char* family_) : c(c_), family(family_), s(c_->stream), timed(zk_timed(c_, B)), timing_mode(c_->timing_mode) {}
+    WindowRun(const WindowRun&) = delete;
+    ~WindowRun() {
+        c->timing_mode = timing_mode;
+        for (hipEvent_t e : ev)
+            if (e) hipEventDestroy(e);
     }
-    zk_status run(const uint32_t* sel, uint32_t n) {
-        if (timed) HIPCHK(c, hipEventRecord(ev[2], s));
-        launch_lv_gather_meta(s, n, sel, d_off, d_msg, d_vseeds, w_off, w_msg, w_seeds);
-        HIPCHK(c, hipMemcpyAsync(h_total, w_off + n, 8, hipMemcpyDeviceToHost, s));
+    zk_status open() {   // the events, and the page-locked words a census and a window's byte count come back through
+        if (!c->h_lv) HIPCHK(c, hipHostMalloc((void**)&c->h_lv, 4096, hipHostMallocDefault));
+        if (timed)
+            for (auto& e : ev) HIPCHK(c, hipEventCreate(&e));
+        return ZK_OK;
+    }
+    zk_status mark(int i) {
+        if (timed) HIPCHK(c, hipEventRecord(ev[i], s));
+        return ZK_OK;
+    }
+    void lap(int i) {   // the partition's kernels between ev[i] and ev[i + 1] (the stream has been synchronised behind them)
+        float ms = 0;
+        if (timed && hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess) part_ms += ms;
+    }
+    template <class Launch>
+    zk_status part(Launch&& launch) {   // kernels of the partition itself; lap(0) once the host has waited for them
+        if (zk_status zs = mark(0)) return zs;
+        launch();
+        return mark(1);
+    }
+    // the verifier's own seeds for the whole batch, gathered with the proofs (the window calls must not draw their own)
+    zk_status own_seeds(uint64_t B, const uint8_t*& d_vseeds) {
+        if (d_vseeds) return ZK_OK;
+        GrowBuf& sd = c->buf[B_seed];   // (asked for with its slack: a partitioned batch has always regrown it for every larger B)
+        if (zk_status zs = reserve(c, sd, 32 * B + 32 * B / 4 + 4096, GROW_EXACT)) return zs;
+        if (zk_status zs = make_default_vseeds(c, B, (uint8_t*)sd.p, s)) return zs;
+        d_vseeds = (const uint8_t*)sd.p;
+        return ZK_OK;
+    }
+    zk_status window(const uint8_t* d_msg, const uint8_t* d_proofs, const uint64_t* d_off, const uint8_t* d_vseeds, uint8_t* d_ok, int32_t* d_st, const Window& W,
+                     const uint32_t* sel, uint32_t n) {
+        uint64_t* h_total = (uint64_t*)(c->h_lv + 2 * ZK_LV_CLASSES);
+        GrowBuf& lb = c->buf[B_lb];
+        if (zk_status zs = mark(2)) return zs;
+        launch_lv_gather_meta(s, n, sel, d_off, d_msg, d_vseeds, W.off, W.msg, W.seeds);
+        HIPCHK(c, hipMemcpyAsync(h_total, W.off + n, 8, hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipStreamSynchronize(s));   // the window's bytes: every length is bounded by its level (wire_level_class)
-        if (zk_status zs = grow(c, &c->lb_buf, &c->lb_bytes, *h_total + 64)) return zs;
-        launch_lv_gather_bytes(s, n, sel, d_off, d_proofs, w_off, (uint8_t*)c->lb_buf);
-        if (timed) HIPCHK(c, hipEventRecord(ev[3], s));
-        if (zk_status zs = verify_device(c, n, w_msg, (const uint8_t*)c->lb_buf, w_off, w_seeds, w_ok, w_st, nullptr, nullptr, true)) return zs;
-        lap();
+        if (zk_status zs = reserve(c, B_lb, *h_total + 64)) return zs;
+        launch_lv_gather_bytes(s, n, sel, d_off, d_proofs, W.off, (uint8_t*)lb.p);
+        if (zk_status zs = mark(3)) return zs;
+        if (zk_status zs = verify_device(c, n, W.msg, (const uint8_t*)lb.p, W.off, W.seeds, W.ok, W.st, nullptr, nullptr, true)) return zs;
+        lap(2);
         for (auto& f : c->last_timing) {
             bool found = false;
-            for (auto& g : *fam)
+            for (auto& g : fam)
                 if (g.first == f.first) g.second += f.second, found = true;
-            if (!found) fam->push_back(f);
+            if (!found) fam.push_back(f);
         }
-        if (timed) HIPCHK(c, hipEventRecord(ev[2], s));
-        launch_lv_scatter(s, n, sel, w_ok, w_st, d_ok, d_st, 0);
-        if (timed) HIPCHK(c, hipEventRecord(ev[3], s));
+        if (zk_status zs = mark(2)) return zs;
+        launch_lv_scatter(s, n, sel, W.ok, W.st, d_ok, d_st, 0);
+        if (zk_status zs = mark(3)) return zs;
         HIPCHK(c, hipStreamSynchronize(s));
-        lap();
+        lap(2);
+        return ZK_OK;
+    }
+    zk_status run(const uint8_t* d_msg, const uint8_t* d_proofs, const uint64_t* d_off, const uint8_t* d_vseeds, uint8_t* d_ok, int32_t* d_st, const uint32_t* perm,
+                  const std::vector<WindowClass>& classes) {
+        uint32_t most = 0;
+        for (const WindowClass& k : classes) most = std::max(most, k.count);
+        const uint32_t Wp = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(most, 2ull * c->chunk * c->lanes));
+        Window W;   // (one window buffer for both partitions: neither runs inside a window of the other)
+        if (zk_status zs = lay_out(c, B_lw, [&](uint8_t* base) { return window_layout(W, base, Wp); })) return zs;
+        // the windows' own calls record their families into the call's timing (the mode is the call's, whatever the window's size)
+        c->timing_mode = timed ? ZK_TIMING_ON : ZK_TIMING_OFF;
+        zk_status zs = ZK_OK;
+        for (const WindowClass& k : classes) {
+            RingBind rb(c, k.ring ? k.ring : c->ring);
+            std::optional<VLevel> level;
+            if (k.level >= 0) level.emplace(c, (uint32_t)k.level);
+            for (uint32_t w = 0; w < k.count && !zs; w += Wp) zs = window(d_msg, d_proofs, d_off, d_vseeds, d_ok, d_st, W, perm + k.start + w, std::min<uint32_t>(Wp, k.count - w));
+            if (zs) break;
+        }
+        c->timing_mode = timing_mode;
+        if (zs) {
+            (void)hipStreamSynchronize(s);
+            return zs;
+        }
+        HIPCHK(c, hipStreamSynchronize(s));
+        lap(0);
+        c->last_timing.clear(), c->last_total_ms = 0, c->last_wall_ms = 0;
+        if (timed) {
+            c->last_timing = fam;
+            c->last_timing.push_back({family, part_ms});
+            for (auto& f : c->last_timing)
+                if (f.first[0] != '+') c->last_total_ms += f.second;
+            c->last_wall_ms = c->last_total_ms;
+        }
         return ZK_OK;
     }
 };
+}   // namespace
 // A batch of device-resident proofs in per-proof mode.  The census (k_lv_census) classifies every proof and counts the classes; the host reads the
 // 130 counters back (the one read-back the mode adds to a call).  One level: the usual pipeline on the caller's buffers, planned at that level.
-// Several: a stable permutation by level, then per level windows of at most 2 x chunk x lanes proofs gathered into HBM (k_lv_gather_*), verified
-// like a batch of their own, their verdicts scattered back (k_lv_scatter); a proof whose header is malformed gets ZK_E_BAD_ENCODING directly.
+// Several: a stable permutation by level, then the windows of every level (WindowRun); a proof whose header is malformed gets ZK_E_BAD_ENCODING directly.
 static zk_status verify_per_proof(zk_ctx* c, uint64_t B, const uint8_t* d_msg, const uint8_t* d_proofs, const uint64_t* d_off, const uint8_t* d_vseeds, uint8_t* d_ok,
                                   int32_t* d_st, bool inputs_on_stream) {
     if (!c->params_set || !c->ring->N) return ZK_E_BUFFER;
     if (B == 0) return ZK_OK;
-    if (c->stream_busy) {
-        c->err = "streamed jobs are in flight on this context (zk_prove_wait / zk_verify_wait them first)";
-        return ZK_E_ARG;
-    }
+    if (c->stream_busy) return busy_refusal(c);
     if (B > 0xffffffffull) return ZK_E_ARG;
-    const uint64_t nblk = (B + 1023) / 1024;
-    Carver k0(nullptr);
-    auto carve = [&](Carver& k, uint8_t*& cls, uint32_t*& blk, uint32_t*& out, uint32_t*& perm) {
-        cls = (uint8_t*)k.take(B), blk = (uint32_t*)k.take(4 * nblk * ZK_LV_CLASSES), out = (uint32_t*)k.take(8 * ZK_LV_CLASSES), perm = (uint32_t*)k.take(4 * B);
-    };
-    uint8_t* cls;
-    uint32_t *blk, *out, *perm;
-    carve(k0, cls, blk, out, perm);
-    if (zk_status zs = grow(c, &c->lv_buf, &c->lv_bytes, k0.off + 256)) return zs;
-    Carver k1((uint8_t*)c->lv_buf);
-    carve(k1, cls, blk, out, perm);
-    if (!c->h_lv) HIPCHK(c, hipHostMalloc((void**)&c->h_lv, 4096, hipHostMallocDefault));
+    Census X;
+    if (zk_status zs = lay_out(c, B_lv, [&](uint8_t* base) { return census_layout(X, base, B, 1, ZK_LV_CLASSES); })) return zs;
+    WindowRun R(c, B, "v_levels");
+    if (zk_status zs = R.open()) return zs;
     hipStream_t s = c->stream;
-    const bool timed = zk_timed(c, B);
-    hipEvent_t ev[4] = {};
-    float lv_ms = 0;
-    auto lap = [&](int i, int j) {   // partition kernels between ev[i] and ev[j] (the stream has been synchronised behind ev[j])
-        float ms = 0;
-        if (timed && hipEventElapsedTime(&ms, ev[i], ev[j]) == hipSuccess) lv_ms += ms;
-    };
-    struct Events {
-        hipEvent_t* e;
-        ~Events() {
-            for (int i = 0; i < 4; i++)
-                if (e[i]) hipEventDestroy(e[i]);
-        }
-    } ev_guard{ev};
-    if (timed)
-        for (auto& e : ev) HIPCHK(c, hipEventCreate(&e));
-    if (timed) HIPCHK(c, hipEventRecord(ev[0], s));
-    launch_lv_census(s, B, d_proofs, d_off, c->wire == ZK_WIRE_ZKA1P, cls, blk, out);
-    if (timed) HIPCHK(c, hipEventRecord(ev[1], s));
-    HIPCHK(c, hipMemcpyAsync(c->h_lv, out, 8 * ZK_LV_CLASSES, hipMemcpyDeviceToHost, s));
+    if (zk_status zs = R.part([&] { launch_lv_census(s, B, d_proofs, d_off, c->wire == ZK_WIRE_ZKA1P, (uint8_t*)X.cls, X.blk, X.out); })) return zs;
+    HIPCHK(c, hipMemcpyAsync(c->h_lv, X.out, 8 * ZK_LV_CLASSES, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
-    lap(0, 1);
-    const uint32_t* cnt = c->h_lv;
-    uint32_t levels = 0, single = c->P.sec, most = 0;
-    uint32_t start[ZK_LV_CLASSES];
-    for (uint32_t l = 0; l < ZK_LV_CLASSES; l++) start[l] = c->h_lv[ZK_LV_CLASSES + l];
+    R.lap(0);
+    const uint32_t *cnt = c->h_lv, *start = c->h_lv + ZK_LV_CLASSES;
+    uint32_t single = c->P.sec;
+    std::vector<WindowClass> classes;
     for (uint32_t l = 0; l <= ZK_MAXSEC; l++)
-        if (cnt[l]) levels++, single = l, most = std::max(most, cnt[l]);
-    if (levels <= 1) {   // the common case: the caller's buffers as they are (malformed headers get ZK_E_BAD_ENCODING from k_v_header at any level)
+        if (cnt[l]) single = l, classes.push_back({nullptr, (int)l, start[l], cnt[l]});
+    if (classes.size() <= 1) {   // the common case: the caller's buffers as they are (malformed headers get ZK_E_BAD_ENCODING from k_v_header at any level)
         VLevel g(c, single);
         return verify_device(c, B, d_msg, d_proofs, d_off, d_vseeds, d_ok, d_st, nullptr, nullptr, inputs_on_stream);
     }
-    if (!d_vseeds) {   // the verifier's own seeds for the whole batch, gathered with the proofs (the window calls must not draw their own)
-        if (zk_status zs = grow(c, &c->seed_buf, &c->seed_bytes, 32 * B + 32 * B / 4 + 4096)) return zs;
-        if (zk_status zs = make_default_vseeds(c, B, (uint8_t*)c->seed_buf, s)) return zs;
-        d_vseeds = (const uint8_t*)c->seed_buf;
-    }
-    if (timed) HIPCHK(c, hipEventRecord(ev[0], s));
-    launch_lv_perm(s, B, cls, blk, out, perm);
-    launch_lv_scatter(s, cnt[ZK_LV_BAD], perm + start[ZK_LV_BAD], nullptr, nullptr, d_ok, d_st, ZK_E_BAD_ENCODING);
-    if (timed) HIPCHK(c, hipEventRecord(ev[1], s));
-    const uint32_t Wp = (uint32_t)std::min<uint64_t>(most, 2ull * c->chunk * c->lanes);
-    Carver w0(nullptr);
-    auto wcarve = [&](Carver& k, uint64_t*& w_off, uint8_t*& w_msg, uint8_t*& w_seeds, uint8_t*& w_ok, int32_t*& w_st) {
-        w_off = (uint64_t*)k.take(8 * ((size_t)Wp + 1)), w_msg = (uint8_t*)k.take(32 * (size_t)Wp), w_seeds = (uint8_t*)k.take(32 * (size_t)Wp);
-        w_ok = (uint8_t*)k.take(Wp), w_st = (int32_t*)k.take(4 * (size_t)Wp);
-    };
-    uint64_t* w_off;
-    uint8_t *w_msg, *w_seeds, *w_ok;
-    int32_t* w_st;
-    wcarve(w0, w_off, w_msg, w_seeds, w_ok, w_st);
-    if (zk_status zs = grow(c, &c->lw_buf, &c->lw_bytes, w0.off + 256)) return zs;
-    Carver w1((uint8_t*)c->lw_buf);
-    wcarve(w1, w_off, w_msg, w_seeds, w_ok, w_st);
-    // the windows' own calls record their families into the call's timing (the mode is the call's, whatever the window's size)
-    const int timing_mode = c->timing_mode;
-    c->timing_mode = timed ? ZK_TIMING_ON : ZK_TIMING_OFF;
-    std::vector<std::pair<const char*, float>> fam;
-    zk_status zs = ZK_OK;
-    WindowRun R{c, s, timed, ev, &lv_ms, &fam, d_msg, d_proofs, d_off, d_vseeds, d_ok, d_st, w_off, w_msg, w_seeds, w_ok, w_st, (uint64_t*)(c->h_lv + 2 * ZK_LV_CLASSES)};
-    for (uint32_t l = 0; l <= ZK_MAXSEC && !zs; l++) {
-        for (uint32_t w = 0; w < cnt[l] && !zs; w += Wp) {
-            VLevel g(c, l);
-            zs = R.run(perm + start[l] + w, std::min<uint32_t>(Wp, cnt[l] - w));
-        }
-    }
-    c->timing_mode = timing_mode;
-    if (zs) {
-        (void)hipStreamSynchronize(s);
+    if (zk_status zs = R.own_seeds(B, d_vseeds)) return zs;
+    const uint32_t bad_start = start[ZK_LV_BAD], bad_cnt = cnt[ZK_LV_BAD];
+    if (zk_status zs = R.part([&] {
+            launch_lv_perm(s, B, (const uint8_t*)X.cls, X.blk, X.out, X.perm);
+            launch_lv_scatter(s, bad_cnt, X.perm + bad_start, nullptr, nullptr, d_ok, d_st, ZK_E_BAD_ENCODING);
+        }))
         return zs;
-    }
-    HIPCHK(c, hipStreamSynchronize(s));
-    lap(0, 1);
-    c->last_timing.clear(), c->last_total_ms = 0, c->last_wall_ms = 0;
-    if (timed) {   // the windows' families, summed, and the partition's kernels (census, permutation, gathers, scatters) as one family
-        c->last_timing = fam;
-        c->last_timing.push_back({"v_levels", lv_ms});
-        for (auto& f : c->last_timing)
-            if (f.first[0] != '+') c->last_total_ms += f.second;
-        c->last_wall_ms = c->last_total_ms;
-    }
-    return ZK_OK;
+    return R.run(d_msg, d_proofs, d_off, d_vseeds, d_ok, d_st, X.perm, classes);
 }
 
 // ------------------------------------------------------------------ mixed-ring verification (include/zkattest.h: zk_verify_batch_rings)
 Ring* zk_resident_ring(zk_ctx* c, uint32_t id);   // api.hip
-// The resident rings in slot order: the census classes a proof by the place of its id in rs.id
-static uint32_t ring_slots(zk_ctx* c, RingSlots& rs, Ring** slot) {
-    rs = RingSlots{};
-    for (auto& R : c->rings)
-        if (R.live && R.N) slot[rs.count] = &R, rs.id[rs.count++] = R.id;
-    return rs.count;
-}
 // Device-resident proofs and ring ids.  The census (k_rg_census) classes every proof by (ring slot, level class) and counts the classes; the host reads
 // RG_CLASSES counters back (the one read-back the call adds).  One ring and one level: the usual pipeline on the caller's buffers with that ring
-// bound (and, per-proof mode, planned at that level).  Otherwise a stable permutation by class, then per class windows of at most 2 x chunk x lanes
-// proofs gathered into HBM, verified with the class's ring bound and its level planned, and their verdicts scattered back; a proof whose id is not
-// resident gets ZK_E_ARG and a malformed header ZK_E_BAD_ENCODING directly.  The level split of verify_per_proof never runs inside a window: one
-// census of (ring, level) gives one permutation and one gather per class.
+// bound (and, per-proof mode, planned at that level).  Otherwise a stable permutation by class, then the windows of every class with its ring bound and
+// its level planned (WindowRun); a proof whose id is not resident gets ZK_E_ARG and a malformed header ZK_E_BAD_ENCODING directly.  The level split of
+// verify_per_proof never runs inside a window: one census of (ring, level) gives one permutation and one gather per class.
 static zk_status verify_rings_device(zk_ctx* c, uint64_t B, const uint8_t* d_msg, const uint8_t* d_proofs, const uint64_t* d_off, const uint32_t* d_ids,
                                      const uint8_t* d_vseeds, uint8_t* d_ok, int32_t* d_st, bool inputs_on_stream) {
     if (!c->params_set) return ZK_E_BUFFER;
     if (B == 0) return ZK_OK;
-    if (c->stream_busy) {
-        c->err = "streamed jobs are in flight on this context (zk_prove_wait / zk_verify_wait them first)";
-        return ZK_E_ARG;
-    }
+    if (c->stream_busy) return busy_refusal(c);
     if (B > 0xffffffffull) return ZK_E_ARG;
     const bool per_proof = c->verify_level == ZK_VERIFY_LEVEL_PER_PROOF;
     RingSlots rs;
     Ring* slot[ZK_MAX_RINGS] = {};
     ring_slots(c, rs, slot);
-    const uint64_t nblk = (B + LV_BLOCK - 1) / LV_BLOCK;
-    auto carve = [&](Carver& k, uint16_t*& cls, uint32_t*& blk, uint32_t*& out, uint32_t*& perm) {
-        cls = (uint16_t*)k.take(2 * B), blk = (uint32_t*)k.take(4 * nblk * RG_CLASSES), out = (uint32_t*)k.take(8 * RG_CLASSES), perm = (uint32_t*)k.take(4 * B);
-    };
-    uint16_t* cls;
-    uint32_t *blk, *out, *perm;
-    Carver k0(nullptr);
-    carve(k0, cls, blk, out, perm);
-    if (zk_status zs = grow(c, &c->rg_buf, &c->rg_bytes, k0.off + 256)) return zs;
-    Carver k1((uint8_t*)c->rg_buf);
-    carve(k1, cls, blk, out, perm);
+    Census X;
+    if (zk_status zs = lay_out(c, B_rg, [&](uint8_t* base) { return census_layout(X, base, B, 2, RG_CLASSES); })) return zs;
     if (!c->h_rg) HIPCHK(c, hipHostMalloc((void**)&c->h_rg, 4 * RG_CLASSES + 64, hipHostMallocDefault));
-    if (!c->h_lv) HIPCHK(c, hipHostMalloc((void**)&c->h_lv, 4096, hipHostMallocDefault));
+    WindowRun R(c, B, "v_rings");
+    if (zk_status zs = R.open()) return zs;
     hipStream_t s = c->stream;
-    const bool timed = zk_timed(c, B);
-    hipEvent_t ev[4] = {};
-    struct Events {
-        hipEvent_t* e;
-        ~Events() {
-            for (int i = 0; i < 4; i++)
-                if (e[i]) hipEventDestroy(e[i]);
-        }
-    } ev_guard{ev};
-    if (timed)
-        for (auto& e : ev) HIPCHK(c, hipEventCreate(&e));
-    float part_ms = 0;
-    auto lap = [&](int i, int j) {
-        float ms = 0;
-        if (timed && hipEventElapsedTime(&ms, ev[i], ev[j]) == hipSuccess) part_ms += ms;
-    };
-    if (timed) HIPCHK(c, hipEventRecord(ev[0], s));
-    launch_rg_census(s, B, d_ids, rs, d_proofs, d_off, c->wire == ZK_WIRE_ZKA1P, per_proof, cls, blk, out);
-    if (timed) HIPCHK(c, hipEventRecord(ev[1], s));
-    HIPCHK(c, hipMemcpyAsync(c->h_rg, out, 4 * RG_CLASSES, hipMemcpyDeviceToHost, s));
+    if (zk_status zs = R.part([&] { launch_rg_census(s, B, d_ids, rs, d_proofs, d_off, c->wire == ZK_WIRE_ZKA1P, per_proof, (uint16_t*)X.cls, X.blk, X.out); })) return zs;
+    HIPCHK(c, hipMemcpyAsync(c->h_rg, X.out, 4 * RG_CLASSES, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
-    lap(0, 1);
-    uint32_t cnt[RG_CLASSES], start[RG_CLASSES];
-    memcpy(cnt, c->h_rg, sizeof cnt);
-    uint32_t most = 0, used_slots = 0, last_slot = 0, levels_last = 0, level_last = c->P.sec;
+    R.lap(0);
+    const uint32_t* cnt = c->h_rg;
+    uint32_t start[RG_CLASSES];
     for (uint32_t k = 0, run = 0; k < RG_CLASSES; k++) start[k] = run, run += cnt[k];
+    uint32_t used_slots = 0, last_slot = 0;
+    std::vector<WindowClass> classes;
     for (uint32_t r = 0; r < rs.count; r++) {
-        uint32_t any = 0, lv = 0, lvl = c->P.sec;
-        for (uint32_t l = 0; l < ZK_LV_CLASSES; l++) {
-            const uint32_t n = cnt[r * ZK_LV_CLASSES + l];
-            any += n;
-            if (n && l != ZK_LV_BAD) lv++, lvl = l, most = std::max(most, n);
+        uint32_t any = cnt[r * ZK_LV_CLASSES + ZK_LV_BAD];
+        for (uint32_t l = 0; l <= ZK_MAXSEC; l++) {
+            const uint32_t k = r * ZK_LV_CLASSES + l;
+            any += cnt[k];
+            if (cnt[k]) classes.push_back({slot[r], per_proof ? (int)l : -1, start[k], cnt[k]});
         }
-        if (any) used_slots++, last_slot = r, levels_last = lv, level_last = lvl;
+        if (any) used_slots++, last_slot = r;
     }
-    if (!cnt[RG_UNKNOWN] && used_slots == 1 && levels_last <= 1) {   // the common case: one ring, one level -- the caller's buffers as they are
-        RingBind rb(c, slot[last_slot]);
+    if (!cnt[RG_UNKNOWN] && used_slots == 1 && classes.size() <= 1) {   // the common case: one ring, one level -- the caller's buffers as they are
+        RingBind rb(c, slot[last_slot]);   // (its proofs may all be malformed: then it has no class to verify, and k_v_header says so)
         std::optional<VLevel> level;
-        if (per_proof) level.emplace(c, level_last);
+        if (per_proof) level.emplace(c, classes.empty() ? c->P.sec : (uint32_t)(classes[0].level));
         return verify_device(c, B, d_msg, d_proofs, d_off, d_vseeds, d_ok, d_st, nullptr, nullptr, inputs_on_stream);
     }
-    if (!d_vseeds) {   // the verifier's own seeds for the whole batch, gathered with the proofs (the window calls must not draw their own)
-        if (zk_status zs = grow(c, &c->seed_buf, &c->seed_bytes, 32 * B + 32 * B / 4 + 4096)) return zs;
-        if (zk_status zs = make_default_vseeds(c, B, (uint8_t*)c->seed_buf, s)) return zs;
-        d_vseeds = (const uint8_t*)c->seed_buf;
-    }
-    if (timed) HIPCHK(c, hipEventRecord(ev[0], s));
-    launch_rg_perm(s, B, cls, blk, out, perm);
-    launch_lv_scatter(s, cnt[RG_UNKNOWN], perm + start[RG_UNKNOWN], nullptr, nullptr, d_ok, d_st, ZK_E_ARG);
-    for (uint32_t r = 0; r < rs.count; r++) {
-        const uint32_t k = r * ZK_LV_CLASSES + ZK_LV_BAD;
-        launch_lv_scatter(s, cnt[k], perm + start[k], nullptr, nullptr, d_ok, d_st, ZK_E_BAD_ENCODING);
-    }
-    if (timed) HIPCHK(c, hipEventRecord(ev[1], s));
-    const uint32_t Wp = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(most, 2ull * c->chunk * c->lanes));
-    auto wcarve = [&](Carver& k, uint64_t*& w_off, uint8_t*& w_msg, uint8_t*& w_seeds, uint8_t*& w_ok, int32_t*& w_st) {
-        w_off = (uint64_t*)k.take(8 * ((size_t)Wp + 1)), w_msg = (uint8_t*)k.take(32 * (size_t)Wp), w_seeds = (uint8_t*)k.take(32 * (size_t)Wp);
-        w_ok = (uint8_t*)k.take(Wp), w_st = (int32_t*)k.take(4 * (size_t)Wp);
-    };
-    uint64_t* w_off;
-    uint8_t *w_msg, *w_seeds, *w_ok;
-    int32_t* w_st;
-    Carver w0(nullptr);
-    wcarve(w0, w_off, w_msg, w_seeds, w_ok, w_st);
-    // (the ring windows share lw_buf / lb_buf with the level windows: nothing below runs verify_per_proof, which would reuse them while they hold a window)
-    if (zk_status zs = grow(c, &c->lw_buf, &c->lw_bytes, w0.off + 256)) return zs;
-    Carver w1((uint8_t*)c->lw_buf);
-    wcarve(w1, w_off, w_msg, w_seeds, w_ok, w_st);
-    const int timing_mode = c->timing_mode;
-    c->timing_mode = timed ? ZK_TIMING_ON : ZK_TIMING_OFF;
-    std::vector<std::pair<const char*, float>> fam;
-    WindowRun R{c, s, timed, ev, &part_ms, &fam, d_msg, d_proofs, d_off, d_vseeds, d_ok, d_st, w_off, w_msg, w_seeds, w_ok, w_st, (uint64_t*)(c->h_lv + 2 * ZK_LV_CLASSES)};
-    zk_status zs = ZK_OK;
-    for (uint32_t r = 0; r < rs.count && !zs; r++) {
-        RingBind rb(c, slot[r]);
-        for (uint32_t l = 0; l <= ZK_MAXSEC && !zs; l++) {
-            const uint32_t k = r * ZK_LV_CLASSES + l;
-            for (uint32_t w = 0; w < cnt[k] && !zs; w += Wp) {
-                std::optional<VLevel> level;
-                if (per_proof) level.emplace(c, l);
-                zs = R.run(perm + start[k] + w, std::min<uint32_t>(Wp, cnt[k] - w));
+    if (zk_status zs = R.own_seeds(B, d_vseeds)) return zs;
+    if (zk_status zs = R.part([&] {
+            launch_rg_perm(s, B, (const uint16_t*)X.cls, X.blk, X.out, X.perm);
+            launch_lv_scatter(s, cnt[RG_UNKNOWN], X.perm + start[RG_UNKNOWN], nullptr, nullptr, d_ok, d_st, ZK_E_ARG);
+            for (uint32_t r = 0; r < rs.count; r++) {
+                const uint32_t k = r * ZK_LV_CLASSES + ZK_LV_BAD;
+                launch_lv_scatter(s, cnt[k], X.perm + start[k], nullptr, nullptr, d_ok, d_st, ZK_E_BAD_ENCODING);
             }
-        }
-    }
-    c->timing_mode = timing_mode;
-    if (zs) {
-        (void)hipStreamSynchronize(s);
+        }))
         return zs;
-    }
-    HIPCHK(c, hipStreamSynchronize(s));
-    lap(0, 1);
-    c->last_timing.clear(), c->last_total_ms = 0, c->last_wall_ms = 0;
-    if (timed) {   // the windows' families, summed, and the partition's kernels (census, permutation, gathers, scatters) as one family
-        c->last_timing = fam;
-        c->last_timing.push_back({"v_rings", part_ms});
-        for (auto& f : c->last_timing)
-            if (f.first[0] != '+') c->last_total_ms += f.second;
-        c->last_wall_ms = c->last_total_ms;
-    }
-    return ZK_OK;
+    return R.run(d_msg, d_proofs, d_off, d_vseeds, d_ok, d_st, X.perm, classes);
+}
+// c->buf[B_in] of the host-pointer verify calls.  zk_verify_batch: messages and offsets, verdicts and statuses next to each other (read back in one copy),
+// then the seeds; the mixed-ring form keeps its own order, ids included.  `end`: the bytes in use (verify_host sizes the page-locked mirror by it).
+struct VerifyIn {
+    uint8_t *msg, *seeds, *ok;
+    uint64_t* off;
+    uint32_t* ids;
+    int32_t* st;
+    size_t end;
+};
+static size_t verify_in_layout(VerifyIn& I, uint8_t* base, size_t B, bool seeds) {
+    Carver k(base);
+    I.msg = (uint8_t*)k.take(32 * B), I.off = (uint64_t*)k.take(8 * (B + 1)), I.ok = (uint8_t*)k.take(B), I.st = (int32_t*)k.take(4 * B);
+    I.seeds = (uint8_t*)k.take(seeds ? 32 * B : 32), I.ids = nullptr;
+    return (I.end = k.off) + ZK_LAYOUT_TAIL;
+}
+static size_t verify_rings_in_layout(VerifyIn& I, uint8_t* base, size_t B, bool seeds) {
+    Carver k(base);
+    I.msg = (uint8_t*)k.take(32 * B), I.off = (uint64_t*)k.take(8 * (B + 1)), I.ids = (uint32_t*)k.take(4 * B), I.seeds = (uint8_t*)k.take(seeds ? 32 * B : 32);
+    I.ok = (uint8_t*)k.take(B), I.st = (int32_t*)k.take(4 * B);
+    return (I.end = k.off) + ZK_LAYOUT_TAIL;
 }
 extern "C" zk_status zk_verify_batch_rings_device(zk_ctx* c, uint64_t B, const void* d_msg, const void* d_proofs, const void* d_off, const void* d_ids,
                                                   const void* d_vseeds, void* d_ok, void* d_status) {
@@ -1092,10 +1022,7 @@ extern "C" zk_status zk_verify_batch_rings(zk_ctx* c, uint64_t B, const uint8_t*
     HIPCHK(c, hipSetDevice(c->device));
     if (!c->params_set) return ZK_E_BUFFER;
     if (B == 0) return ZK_OK;
-    if (c->stream_busy) {
-        c->err = "streamed jobs are in flight on this context (zk_prove_wait / zk_verify_wait them first)";
-        return ZK_E_ARG;
-    }
+    if (c->stream_busy) return busy_refusal(c);
     Ring* one = zk_resident_ring(c, ring_ids[0]);
     for (uint64_t b = 1; b < B && one; b++)
         if (ring_ids[b] != ring_ids[0]) one = nullptr;
@@ -1106,29 +1033,19 @@ extern "C" zk_status zk_verify_batch_rings(zk_ctx* c, uint64_t B, const uint8_t*
     if (off[0] != 0) return ZK_E_ARG;
     for (uint64_t b = 0; b < B; b++)
         if (off[b + 1] < off[b]) return ZK_E_ARG;  // every proof lies inside [0, off[B])
-    Carver k0(nullptr);
-    auto carve_in = [&](Carver& kk, uint8_t*& m, uint64_t*& o, uint32_t*& ids, uint8_t*& sd, uint8_t*& okp, int32_t*& st_) {
-        m = (uint8_t*)kk.take(32 * B), o = (uint64_t*)kk.take(8 * (B + 1)), ids = (uint32_t*)kk.take(4 * B), sd = (uint8_t*)kk.take(vseeds ? 32 * B : 32);
-        okp = (uint8_t*)kk.take(B), st_ = (int32_t*)kk.take(4 * B);
-    };
-    uint8_t *d_msg, *d_seeds, *d_ok;
-    uint64_t* d_off;
-    uint32_t* d_ids;
-    int32_t* d_st;
-    carve_in(k0, d_msg, d_off, d_ids, d_seeds, d_ok, d_st);
-    if (zk_status zs = ensure_in_buf(c, k0.off + 256)) return zs;
-    Carver k1((uint8_t*)c->in_buf);
-    carve_in(k1, d_msg, d_off, d_ids, d_seeds, d_ok, d_st);
-    if (zk_status zs = ensure_io_buf(c, off[B] + 64)) return zs;
-    HIPCHK(c, hipMemcpy(c->io_buf, proofs, off[B], hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(d_msg, msg, 32 * B, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(d_off, off, 8 * (B + 1), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(d_ids, ring_ids, 4 * B, hipMemcpyHostToDevice));
-    if (vseeds) HIPCHK(c, hipMemcpy(d_seeds, vseeds, 32 * B, hipMemcpyHostToDevice));
-    zk_status zs = verify_rings_device(c, B, d_msg, (const uint8_t*)c->io_buf, d_off, d_ids, vseeds ? d_seeds : nullptr, d_ok, d_st, false);
+    VerifyIn I;
+    if (zk_status zs = lay_out(c, B_in, [&](uint8_t* base) { return verify_rings_in_layout(I, base, B, vseeds != nullptr); })) return zs;
+    if (zk_status zs = reserve(c, B_io, off[B] + 64)) return zs;
+    uint8_t* const d_proofs = (uint8_t*)c->buf[B_io].p;
+    HIPCHK(c, hipMemcpy(d_proofs, proofs, off[B], hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(I.msg, msg, 32 * B, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(I.off, off, 8 * (B + 1), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(I.ids, ring_ids, 4 * B, hipMemcpyHostToDevice));
+    if (vseeds) HIPCHK(c, hipMemcpy(I.seeds, vseeds, 32 * B, hipMemcpyHostToDevice));
+    zk_status zs = verify_rings_device(c, B, I.msg, d_proofs, I.off, I.ids, vseeds ? I.seeds : nullptr, I.ok, I.st, false);
     if (zs) return zs;
-    HIPCHK(c, hipMemcpy(ok, d_ok, B, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(status, d_st, 4 * B, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(ok, I.ok, B, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(status, I.st, 4 * B, hipMemcpyDeviceToHost));
     return ZK_OK;
 }
 
@@ -1147,10 +1064,7 @@ extern "C" zk_status zk_verify_batch(zk_ctx* c, uint64_t B, const uint8_t* msg, 
     HIPCHK(c, hipSetDevice(c->device));
     if (!c->params_set || !c->ring->N) return ZK_E_BUFFER;
     if (B == 0) return ZK_OK;
-    if (c->stream_busy) {
-        c->err = "streamed jobs are in flight on this context (zk_prove_wait / zk_verify_wait them first)";
-        return ZK_E_ARG;
-    }
+    if (c->stream_busy) return busy_refusal(c);
     return verify_host(c, B, msg, proofs, off, vseeds, ok, status);
 }
 zk_status verify_host(zk_ctx* c, uint64_t B, const uint8_t* msg, const uint8_t* proofs, const uint64_t* off, const uint8_t* vseeds, uint8_t* ok, int32_t* status) {
@@ -1169,22 +1083,13 @@ zk_status verify_host(zk_ctx* c, uint64_t B, const uint8_t* msg, const uint8_t* 
     std::optional<VLevel> level;
     if (per_proof && !mixed) level.emplace(c, lvl == LV_NONE ? c->P.sec : lvl);
     // the small per-proof arrays live in the context's grow-only input buffer (no hipMalloc / hipFree per call)
-    Carver k0(nullptr);
-    auto carve_in = [&](Carver& kk, uint8_t*& m, uint64_t*& o, uint8_t*& okp, int32_t*& st_, uint8_t*& sd) {
-        m = (uint8_t*)kk.take(32 * B), o = (uint64_t*)kk.take(8 * (B + 1)), okp = (uint8_t*)kk.take(B), st_ = (int32_t*)kk.take(4 * B);
-        sd = (uint8_t*)kk.take(vseeds ? 32 * B : 32);
-    };
-    uint8_t *d_msg, *d_ok, *d_seeds;
-    uint64_t* d_off;
-    int32_t* d_st;
-    carve_in(k0, d_msg, d_off, d_ok, d_st, d_seeds);
-    zk_status zs = ensure_in_buf(c, k0.off + 256);
+    VerifyIn I;
+    zk_status zs = lay_out(c, B_in, [&](uint8_t* base) { return verify_in_layout(I, base, B, vseeds != nullptr); });
     if (zs) return zs;
-    Carver k1((uint8_t*)c->in_buf);
-    carve_in(k1, d_msg, d_off, d_ok, d_st, d_seeds);
-    zs = ensure_io_buf(c, total + 64);  // proof bytes: the context's grow-only staging buffer
+    uint8_t* const in_buf = (uint8_t*)c->buf[B_in].p;
+    zs = reserve(c, B_io, total + 64);  // proof bytes: the context's grow-only staging buffer
     if (zs) return zs;
-    uint8_t* d_proofs = (uint8_t*)c->io_buf;
+    uint8_t* d_proofs = (uint8_t*)c->buf[B_io].p;
     // page-locked `proofs` (zk_host_alloc): chunk-wise DMA under the kernels of the earlier chunks; pageable: one blocking copy
     const bool pinned = !mixed && host_ptr_is_pinned(proofs);
     if (pinned) {
@@ -1195,36 +1100,36 @@ zk_status verify_host(zk_ctx* c, uint64_t B, const uint8_t* msg, const uint8_t* 
     }
     // A call of a few proofs: messages, offsets and seeds cross in ONE copy out of the context's page-locked mirror of in_buf, and the lanes wait for its event
     // instead of the host (api.hip: zk_prove_batch does the same); verdicts and statuses come back in one.
-    const size_t in_end = (size_t)(d_ok - (uint8_t*)c->in_buf), res_end = (size_t)((uint8_t*)(d_st + B) - (uint8_t*)c->in_buf);
-    const bool staged = k1.off <= ZK_STAGE_MAX;
+    const size_t in_end = (size_t)(I.ok - in_buf), res_end = (size_t)((uint8_t*)(I.st + B) - in_buf);
+    const bool staged = I.end <= ZK_STAGE_MAX;
     if (staged) {
-        if ((zs = ensure_h_stage(c, k1.off))) return zs;
-        auto at = [&](const void* d) { return c->h_stage + ((const uint8_t*)d - (const uint8_t*)c->in_buf); };
-        memcpy(at(d_msg), msg, 32 * B), memcpy(at(d_off), off, 8 * (B + 1));
-        HIPCHK(c, hipMemcpyAsync(c->in_buf, c->h_stage, in_end, hipMemcpyHostToDevice, c->stream));
+        if ((zs = ensure_h_stage(c, I.end))) return zs;
+        auto at = [&](const void* d) { return c->h_stage + ((const uint8_t*)d - in_buf); };
+        memcpy(at(I.msg), msg, 32 * B), memcpy(at(I.off), off, 8 * (B + 1));
+        HIPCHK(c, hipMemcpyAsync(in_buf, c->h_stage, in_end, hipMemcpyHostToDevice, c->stream));
         if (vseeds) {
-            memcpy(at(d_seeds), vseeds, 32 * B);
-            HIPCHK(c, hipMemcpyAsync(d_seeds, at(d_seeds), 32 * B, hipMemcpyHostToDevice, c->stream));
+            memcpy(at(I.seeds), vseeds, 32 * B);
+            HIPCHK(c, hipMemcpyAsync(I.seeds, at(I.seeds), 32 * B, hipMemcpyHostToDevice, c->stream));
         }
     } else {
-        HIPCHK(c, hipMemcpyAsync(d_msg, msg, 32 * B, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_off, off, 8 * (B + 1), hipMemcpyHostToDevice, c->stream));
-        if (vseeds) HIPCHK(c, hipMemcpyAsync(d_seeds, vseeds, 32 * B, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(I.msg, msg, 32 * B, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(I.off, off, 8 * (B + 1), hipMemcpyHostToDevice, c->stream));
+        if (vseeds) HIPCHK(c, hipMemcpyAsync(I.seeds, vseeds, 32 * B, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));   // both lanes read these arrays
     }
-    zs = mixed ? verify_per_proof(c, B, d_msg, d_proofs, d_off, vseeds ? d_seeds : nullptr, d_ok, d_st, staged)
-               : verify_device(c, B, d_msg, d_proofs, d_off, vseeds ? d_seeds : nullptr, d_ok, d_st, pinned ? proofs : nullptr, pinned ? off : nullptr, staged);
+    zs = mixed ? verify_per_proof(c, B, I.msg, d_proofs, I.off, vseeds ? I.seeds : nullptr, I.ok, I.st, staged)
+               : verify_device(c, B, I.msg, d_proofs, I.off, vseeds ? I.seeds : nullptr, I.ok, I.st, pinned ? proofs : nullptr, pinned ? off : nullptr, staged);
     if (zs) {
         if (staged) (void)hipStreamSynchronize(c->stream);   // the mirror is reused by the next call
         return zs;
     }
     if (staged) {   // verdicts and statuses lie next to each other in in_buf
-        HIPCHK(c, hipMemcpy(c->h_stage + in_end, d_ok, res_end - in_end, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(c->h_stage + in_end, I.ok, res_end - in_end, hipMemcpyDeviceToHost));
         memcpy(ok, c->h_stage + in_end, B);
-        memcpy(status, c->h_stage + ((uint8_t*)d_st - (uint8_t*)c->in_buf), 4 * B);
+        memcpy(status, c->h_stage + ((uint8_t*)I.st - in_buf), 4 * B);
     } else {
-        HIPCHK(c, hipMemcpy(ok, d_ok, B, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(status, d_st, 4 * B, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(ok, I.ok, B, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(status, I.st, 4 * B, hipMemcpyDeviceToHost));
     }
     return ZK_OK;
 }

@@ -1,4 +1,5 @@
-// Shared host-side context of libzkattest_hip.so (api.hip: prover pipeline; api_verify.hip: verifier pipeline).
+// Shared host-side context of libzkattest_hip.so (api.hip: prover pipeline; api_verify.hip: verifier pipeline): the context itself, its grow-only device
+// buffers (GrowBuf, reserve, lay_out), the refusal while streamed jobs are queued, the timed scopes and the chunk plan.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -8,12 +9,49 @@
 #include <string>
 #include <vector>
 #include "engine.h"
+#include "layout.h"
 
 struct TimerRec {
     const char* name;
     hipEvent_t e0, e1;
 };
 #define ZK_MAX_LANES 4
+// A grow-only device buffer: a call that needs more frees it and allocates anew, nothing shrinks it before the context goes.
+struct GrowBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+    bool witness = false;   // holds signatures, seeds, nonces or candidate keys: zeroed by wipe_witness
+};
+enum GrowPolicy {
+    GROW_EXACT,   // hipMalloc of what is needed
+    GROW_SHED,    // ... through malloc_or_shed: the optional per-ring tables go first
+    GROW_SLACK,   // need + need / 4 + 4096: buffers that follow B call by call
+    GROW_SPARE,   // a staging buffer of a finished streamed job where one is large enough (stream_take_spare_dev), else exact
+    GROW_ONCE,    // allocated by the first call; its size does not depend on the call
+};
+// The context's device buffers: name, policy, witness-derived?  One line here is all a new buffer takes -- zk_ctx_destroy frees and wipe_witness zeroes by this table.
+#define ZK_CTX_BUFS(X)                                                                                                                                             \
+    X(rg, GROW_EXACT, false)      /* mixed-ring verify calls (api_verify.hip): census, permutation and counters */                                                \
+    X(pr, GROW_EXACT, false)      /* mixed-ring prove calls (api.hip): classes, per-workgroup counters, permutation, the segment's (staging offset, length) */   \
+    X(pw, GROW_SHED, true)        /* ... the window one ring's inputs are gathered into: signatures, seeds or RNG streams */                                      \
+    X(ps, GROW_SHED, false)       /* ... staging of a segment's proofs until their final offsets are known */                                                     \
+    X(scr, GROW_ONCE, true)       /* witness screen (api_screen.hip): a chunk's scratch areas (u1, u2) and, host-pointer forms, its inputs and results */         \
+    X(rec, GROW_ONCE, true)       /* key recovery (api_recover.hip): a chunk's scratch areas, lifted R, candidate keys and, host-pointer forms, its inputs */     \
+    X(lv, GROW_EXACT, false)      /* per-proof verify levels: census, permutation and counters of a mixed batch */                                                \
+    X(lw, GROW_EXACT, false)      /* partitioned verification: offsets, message hashes, seeds and verdicts of the window one class's proofs are gathered into */ \
+    X(lb, GROW_EXACT, false)      /* ... and the window's proof bytes */                                                                                          \
+    X(io, GROW_SPARE, false)      /* host-pointer entry points: staging of the proof bytes (a multi-GB hipMalloc / hipFree per call costs as much as the copy) */ \
+    X(seed, GROW_SLACK, false)    /* the verifier's own seeds when the caller gives none (32 B bytes) */                                                          \
+    X(in, GROW_SLACK, true)       /* host-pointer entry points: the small per-proof arrays (inputs, offsets, statuses, verdicts) */                               \
+    X(unp, GROW_EXACT, false)     /* ZKA1P input of the synchronous verify calls: staging of the expanded proofs */                                               \
+    X(unp_off, GROW_EXACT, false) /* ... and their per-chunk offsets */                                                                                           \
+    X(m_off, GROW_SLACK, false)   /* membership proofs on their own: offsets of a verify call's equally long proofs */
+enum BufId {
+#define X(name, policy, witness) B_##name,
+    ZK_CTX_BUFS(X)
+#undef X
+        B_COUNT
+};
 // One resident ring of a context: the padded ring's limbs and the tables built from it.  Every table but the limbs and the digest is optional.
 struct Ring {
     uint32_t id = 0;
@@ -53,38 +91,19 @@ struct zk_ctx {
     bool key_tables = true;        // ZKATTEST_KEYTAB=0 / zk_ctx_set_key_tables(ctx, 0): per-proof tables of R for every proof (read when a ring is built)
     bool gk_mfma_prove = true;     // build gk_edig with the ring (ZKATTEST_GK_MFMA_PROVE; read when a ring is built)
     bool gk_mfma = true;           // verifier's ring fold on the matrix pipe where gk_kdig exists (zk_ctx_set_ring_fold, ZKATTEST_GK_MFMA)
-    void* rg_buf = nullptr;        // mixed-ring verify calls (api_verify.hip): census, permutation and counters (grow-only)
-    size_t rg_bytes = 0;
-    uint32_t* h_rg = nullptr;      // ... page-locked read-back of the per-class counters
-    size_t h_rg_bytes = 0;
-    // mixed-ring prove calls (api.hip: prove_rings_device), all grow-only
-    void* pr_buf = nullptr;        // classes, per-workgroup counters, permutation and the running segment's (staging offset, length) records
-    size_t pr_bytes = 0;
-    uint32_t* h_pr = nullptr;      // page-locked read-back of the counters
+    GrowBuf buf[B_COUNT];          // the device buffers of ZK_CTX_BUFS, policy and witness flag as listed there (zk_ctx's constructor)
+    uint32_t* h_rg = nullptr;      // mixed-ring verify calls: page-locked read-back of the per-class counters
+    uint32_t* h_pr = nullptr;      // mixed-ring prove calls (api.hip: prove_rings_device): page-locked read-back of the counters
     size_t h_pr_bytes = 0;
-    void* pw_buf = nullptr;        // the window one ring's inputs are gathered into: signatures, seeds or RNG streams -- witness-derived, wiped with the workspaces
-    size_t pw_bytes = 0;
-    void* ps_buf = nullptr;        // staging of a segment's proofs until their final offsets are known (malloc_or_shed)
-    size_t ps_bytes = 0;
     hipEvent_t pr_ready = nullptr; // "the window is gathered": the lanes' stage 1 waits for it
     uint32_t pr_seg_force = 0;     // test build only (zk_test_set_prove_segment): proofs per segment instead of what ZK_PR_STAGE_BYTES holds; 0 = off
-    void* scr_buf = nullptr;       // witness screen (api_screen.hip): one chunk's scratch areas (u1, u2: witness-derived, wiped with the workspaces) and, for the
-    size_t scr_bytes = 0;          // host-pointer forms, the chunk's inputs and results; allocated by the first screen call, its size does not depend on B
-    void* rec_buf = nullptr;       // key recovery (api_recover.hip): one chunk's scratch areas, lifted R, candidate keys (all witness-derived, wiped with the workspaces)
-    size_t rec_bytes = 0;          // and, for the host-pointer forms, the chunk's inputs and results; allocated by the first recover call, its size does not depend on B
     uint32_t mode = 0;                 // zk_ctx_set_mode: ZK_MODE_REFERENCE / ZK_MODE_HARDENED
     uint32_t verify_level = 0;         // zk_ctx_set_verify_level: ZK_VERIFY_LEVEL_CONTEXT / ZK_VERIFY_LEVEL_PER_PROOF
     // per-proof mode: the repetition count the verifier's workspaces are planned for during one call (or while streamed verify jobs are queued); the
     // context's own P.sec otherwise (plan_sec below), so that the next prove call plans at the context's level again
     uint32_t v_sec = 0;
     bool v_sec_on = false;
-    void* lv_buf = nullptr;            // per-proof mode: census, permutation and counters of a mixed batch (grow-only)
-    size_t lv_bytes = 0;
-    void* lw_buf = nullptr;            // ... the offsets, message hashes, seeds and verdicts of the window one level's proofs are gathered into
-    size_t lw_bytes = 0;
-    void* lb_buf = nullptr;            // ... and the window's proof bytes (grow-only)
-    size_t lb_bytes = 0;
-    uint32_t* h_lv = nullptr;          // page-locked read-back of the per-level counters
+    uint32_t* h_lv = nullptr;          // per-proof mode: page-locked read-back of the per-level counters; partitioned verification: of a window's byte count
     // workspace: up to ZK_MAX_LANES pipeline lanes, each with its own HIP stream and prover / verifier workspace; consecutive
     // chunks go to consecutive lanes, so the low-occupancy per-proof kernels, the scans the host waits for and (host-pointer
     // calls) the output phases of different chunks fall into each other's heavy phases.  Lane 0 runs on `stream`.
@@ -96,8 +115,7 @@ struct zk_ctx {
         Workspace W{};
         Soa gk_am{};
         uint32_t* d_totals = nullptr;
-        void* arena = nullptr;
-        size_t arena_bytes = 0;
+        GrowBuf arena{nullptr, 0, true};   // witness-derived (the RNG stream of every proof, nonces, s1 = s / r, blinders): wiped by wipe_witness
         bool ready = false;
         uint32_t last_cnt = 0;          // proofs of the last chunk this lane started (zk_test_counter)
         hipStream_t side = nullptr;     // small chunks: the membership phase of stage 2 runs beside the PointAdd phase (api.hip: ProveJob::stage2)
@@ -113,8 +131,7 @@ struct zk_ctx {
     // verifier workspace
     struct VerifyLane {
         VWork V{};
-        void* arena = nullptr;
-        size_t arena_bytes = 0;
+        GrowBuf arena;
         Soa res{}, res2{};
         MsmBuf M{};               // batched Tom check buffers (k_msm.hip), carved with V
         uint32_t* h_msm = nullptr;   // page-locked read-back words of run_msm
@@ -136,14 +153,11 @@ struct zk_ctx {
         VWork V{};
         Soa gk_am{}, res{}, res2{};
         uint32_t* which_s = nullptr;   // [C] the indices the fold kernels read (0 for one outside the ring)
-        void* arena = nullptr;         // witness-derived (blinders, nonces, the RNG stream): wiped with the prover lanes' (api.hip: wipe_witness)
-        size_t arena_bytes = 0;
+        GrowBuf arena{nullptr, 0, true};   // witness-derived (blinders, nonces, the RNG stream): wiped with the prover lanes' (api.hip: wipe_witness)
         bool ready = false;
     } ml[ZK_MAX_LANES];
     uint32_t ms_C = 0, ms_n = 0;
     bool ms_etab = false, ms_edig = false;
-    uint64_t* m_off = nullptr;         // offsets of a verify call's equally long proofs (grow-only)
-    size_t m_off_entries = 0;
     uint32_t vs_C = 0, vs_sec = 0, vs_n = 0;
     uint32_t p256_batch_min = 8192;   // chunks of at least this many proofs sum their P-256 relations across proofs too (ZKATTEST_P256_BATCH; 0 = never)
     uint32_t verify_groups = 8;   // groups per chunk of the batched Tom check: 8 (16-bit windows) or 64 (13-bit windows); zk_ctx_set_verify_groups
@@ -153,20 +167,10 @@ struct zk_ctx {
     uint32_t verify_batch_min = 256;   // zk_ctx_set_batch_verify: chunks of at least this many proofs get the batched check (0 = never)
     // host-buffer entry points: DMA stream for page-locked caller buffers (zk_host_alloc), one event per lane
     hipStream_t copy_stream = nullptr;
-    void* io_buf = nullptr;        // device staging of the proof bytes for the host-pointer entry points (grow-only: a
-    size_t io_bytes = 0;           // multi-GB hipMalloc/hipFree per call costs as much as the transfer itself)
     uint8_t* h_stage = nullptr;    // page-locked mirror of in_buf's head for calls of a few proofs: the input arrays cross in ONE copy that no host thread waits for, and
     size_t h_stage_bytes = 0;      // the offsets / statuses / verdicts come back in one (api.hip: ensure_h_stage; wiped with the witness)
     hipEvent_t in_ready = nullptr; // ... the lanes wait for this event instead (the job's inputs_ready)
-    void* seed_buf = nullptr;      // the verifier's own seeds when the caller gives none (32 B + 32 bytes, grow-only)
-    size_t seed_bytes = 0;
-    void* in_buf = nullptr;        // device copies of the small per-proof arrays of the host-pointer entry points (inputs,
-    size_t in_bytes = 0;           // offsets, statuses, verdicts), grow-only for the same reason
     uint32_t wire = 0;             // zk_ctx_set_wire: 0 = ZKA1 (36-byte Tom coordinates), 1 = ZKA1P (33-byte): what the prover emits and the verifier is handed
-    void* unp_buf = nullptr;       // ZKA1P input of the synchronous verify calls: staging of the expanded proofs and their per-chunk offsets (grow-only)
-    size_t unp_bytes = 0;
-    uint64_t* unp_off = nullptr;
-    size_t unp_off_entries = 0;
     uint32_t host_taper = 1;       // host-pointer calls on page-locked buffers: tapered chunk plan (zk_ctx_set_host_taper)
     uint32_t slice = 0;            // proofs per PointAdd slice of the prover (zk_ctx_set_slice): 0 = 4096 with a page-locked sink, else none
     // streamed calls (api_stream.hip): jobs submitted and not yet waited for, in submission order
@@ -195,6 +199,16 @@ struct zk_ctx {
     float last_total_ms = 0, last_wall_ms = 0;   // sum of the timed scopes ('+' parts excluded); first start -> last end of the same call
     int timing_mode = ZK_TIMING_AUTO;   // zk_ctx_set_timing
     bool timing_forked = false;   // this call put timed scopes on forked streams (small one-chunk calls): its scopes overlap, the total is first start -> last end
+    zk_ctx() {
+#define X(name, policy, w) buf[B_##name].witness = w;
+        ZK_CTX_BUFS(X)
+#undef X
+    }
+};
+static const GrowPolicy zk_buf_policy[B_COUNT] = {
+#define X(name, policy, witness) policy,
+    ZK_CTX_BUFS(X)
+#undef X
 };
 
 #define HIPCHK(ctx, x)                                                                                      \
@@ -278,7 +292,31 @@ struct DevBuf {
 void wipe_witness(zk_ctx* c);   // api.hip: zeroes every witness-derived buffer of the context (nothing may be in flight)
 zk_status ensure_workspace(zk_ctx* c, uint32_t C, uint32_t nlanes = 1);   // api.hip: prover workspaces of lanes 0..nlanes-1
 hipError_t malloc_or_shed(zk_ctx* c, void** p, size_t bytes);   // api.hip: a workspace allocation that sheds the optional per-ring tables first
-zk_status ensure_in_buf(zk_ctx* c, size_t bytes);  // api.hip: c->in_buf of at least `bytes`
+// settings a queued streamed job was planned with (its lane rotation, chunk size, workspaces, mode) and the buffers it reads stay frozen until it is waited for
+static inline zk_status busy_refusal(zk_ctx* c) {
+    c->err = "streamed jobs are in flight on this context (zk_prove_wait / zk_verify_wait them first)";
+    return ZK_E_ARG;
+}
+zk_status reserve(zk_ctx* c, GrowBuf& b, size_t need, GrowPolicy policy);   // api.hip: `b` of at least `need` bytes
+static inline zk_status reserve(zk_ctx* c, BufId id, size_t need) { return reserve(c, c->buf[id], need, zk_buf_policy[id]); }
+// sizes `layout` (base -> bytes), reserves the buffer, carves it for real
+template <class Layout>
+static inline zk_status lay_out(zk_ctx* c, GrowBuf& b, GrowPolicy policy, Layout&& layout) {
+    return lay_out(layout, [&](size_t need, uint8_t** base) {
+        const zk_status zs = reserve(c, b, need, policy);
+        *base = (uint8_t*)b.p;
+        return zs;
+    });
+}
+template <class Layout>
+static inline zk_status lay_out(zk_ctx* c, BufId id, Layout&& layout) { return lay_out(c, c->buf[id], zk_buf_policy[id], layout); }
+// The resident rings in slot order: the censuses class a proof by the place of its id in rs.id
+static inline uint32_t ring_slots(zk_ctx* c, RingSlots& rs, Ring** slot) {
+    rs = RingSlots{};
+    for (auto& R : c->rings)
+        if (R.live && R.N) slot[rs.count] = &R, rs.id[rs.count++] = R.id;
+    return rs.count;
+}
 #define ZK_STAGE_MAX (1u << 20)   // input arrays up to this size take the page-locked mirror
 zk_status ensure_h_stage(zk_ctx* c, size_t bytes);  // api.hip: c->h_stage of at least `bytes`, c->in_ready
 
@@ -327,22 +365,13 @@ static inline std::vector<ChunkPlan> make_chunk_plan(uint64_t B, uint32_t C, uin
     for (uint32_t s : sizes) plan.push_back({f, s}), f += s;
     return plan;
 }
-zk_status ensure_io_buf(zk_ctx* c, size_t bytes);  // api.hip: c->io_buf of at least `bytes`
 float pinned_d2h_rate(void* p, size_t bytes);   // api.hip: slowest D2H rate over three windows of a page-locked range (the "slow pages" check)
 void* alloc_fast_pinned(size_t bytes, const std::function<void*()>& alloc, const std::function<void(void*)>& release);   // api.hip: the fastest of up to three candidates
 bool host_ptr_is_pinned(const void* p);     // api.hip: page-locked (zk_host_alloc / hipHostMalloc / hipHostRegister) host memory?
 zk_status ensure_copy_stream(zk_ctx* c);    // api.hip: c->copy_stream and the lanes' copy events
 
-struct Carver {
-    uint8_t* base;
-    size_t off = 0;
-    explicit Carver(uint8_t* b) : base(b) {}
-    void* take(size_t bytes) {
-        off = (off + 255) & ~(size_t)255;
-        void* p = base ? base + off : nullptr;
-        off += bytes;
-        return p;
-    }
+struct SoaCarver : Carver {   // the workspace arenas' conveniences on top of layout.h
+    using Carver::Carver;
     Soa soa(size_t elems) { return Soa{(uint32_t*)take(elems * 36), (uint32_t)elems}; }
     Soa3 soa3(size_t elems) { return Soa3{soa(elems), soa(elems), soa(elems)}; }
     TomList list(size_t cap) {
