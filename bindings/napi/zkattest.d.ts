@@ -94,7 +94,7 @@ export class Engine {
     /** residentRings (1..16, default 4): key rings the facade's context cache keeps built on this engine, least recently used dropped first;
      *  ringDelta (default 0 = off): a key list that misses the cache but differs from a resident ring of the same length in at most this many 32-byte entries
      *  updates that ring in place (updateRing) instead of building a new one */
-    setOption(name: 'chunk' | 'lanes' | 'combBits' | 'hostTaper' | 'batchVerify' | 'mode' | 'slice' | 'ringFold' | 'verifyGroups' | 'wire' | 'verifyLevel' | 'inflight' | 'residentRings' | 'ringDelta', value: number): void
+    setOption(name: 'chunk' | 'lanes' | 'combBits' | 'hostTaper' | 'batchVerify' | 'mode' | 'slice' | 'ringFold' | 'verifyGroups' | 'wire' | 'verifyLevel' | 'verifyReps' | 'inflight' | 'residentRings' | 'ringDelta', value: number): void
     /** zero the witness-derived device memory (prover workspaces, staged signatures and seeds) of every device now; close() and a failed prove do it by themselves */
     wipe(): void
     setParams(p: EngineParams): void
@@ -131,3 +131,5 @@ export function getWireLayout(): 'zka1' | 'zka1p'
  *  or 'proof' (the proof's own repetition count, as the reference's verifier does).  Applies to every engine, cached ones included. */
 export function setVerifyLevel(name: 'context' | 'proof'): void
 export function getVerifyLevel(): 'context' | 'proof'
+export function setVerifyReps(name: 'sample' | 'all'): void
+export function getVerifyReps(): 'sample' | 'all'

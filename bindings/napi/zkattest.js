@@ -304,7 +304,7 @@ class Engine {
     }
     close() { if (this.h) native.destroyPool(this.h); this.h = null }
     info() { return native.poolInfo(this.h) }
-    // chunk, lanes, combBits (before setParams), hostTaper, batchVerify, mode, slice, ringFold, verifyGroups, wire (0 ZKA1, 1 ZKA1P), verifyLevel (0 context, 1 per proof), inflight;
+    // chunk, lanes, combBits (before setParams), hostTaper, batchVerify, mode, slice, ringFold, verifyGroups, wire (0 ZKA1, 1 ZKA1P), verifyLevel (0 context, 1 per proof), verifyReps (0 sampled, 1 all), inflight;
     // residentRings (default 4): how many key rings the facade's context cache keeps built on this engine (engineFor: LRU by ring)
     setOption(name, value) {
         if (name === 'residentRings') {
@@ -581,6 +581,17 @@ function getVerifyLevel() { return verifyLevel ? 'proof' : 'context' }
 function useVerifyLevel(slotEngine, level) {   // inside a queued unit of the engine (nothing of it is in flight)
     if ((slotEngine._verifyLevel || 0) !== level) { slotEngine.setOption('verifyLevel', level); slotEngine._verifyLevel = level }
 }
+// The repetitions verifySignatureList checks: 'sample' (default) = the 20 that generateIndices draws, as the reference's verifier does, or 'all' = every
+// repetition of the proof (include/zkattest.h zk_ctx_set_verify_reps: stricter than the reference).  Applies to every engine, cached ones included.
+let verifyReps = 0
+function setVerifyReps(name) {
+    if (name !== 'sample' && name !== 'all') throw new TypeError("verify reps: 'sample' or 'all'")
+    verifyReps = name === 'all' ? 1 : 0
+}
+function getVerifyReps() { return verifyReps ? 'all' : 'sample' }
+function useVerifyReps(slotEngine, reps) {   // inside a queued unit of the engine (nothing of it is in flight)
+    if ((slotEngine._verifyReps || 0) !== reps) { slotEngine.setOption('verifyReps', reps); slotEngine._verifyReps = reps }
+}
 const isPacked = (b) => Buffer.isBuffer(b) && b.length >= 4 && b.slice(0, 4).toString('latin1') === 'ZK1P'
 
 // ---------------------------------------------------------------- the reference's API
@@ -629,8 +640,8 @@ async function verifySignatureListBatch(params, msgHashes, keys, proofs) {
         const sel = idx[wire]
         if (!sel.length) continue
         const m = sel.length === raw.length ? msg : Buffer.concat(sel.map((i) => msg.slice(32 * i, 32 * i + 32)))
-        const level = verifyLevel
-        const r = await engineFor(params, keys).withRing((engine) => { useWire(engine, wire); useVerifyLevel(engine, level); return engine._verifyNow(m, sel.map((i) => raw[i])) })
+        const level = verifyLevel, reps = verifyReps
+        const r = await engineFor(params, keys).withRing((engine) => { useWire(engine, wire); useVerifyLevel(engine, level); useVerifyReps(engine, reps); return engine._verifyNow(m, sel.map((i) => raw[i])) })
         sel.forEach((i, k) => { out[i] = r[k]; errors[i] = r.errors[k] })
     }
     Object.defineProperty(out, 'errors', { value: errors })
@@ -683,7 +694,7 @@ async function verifySignatureLists(params, msgHashes, keyLists, proofs) {
         ringOfProof[i] = byTag.get(r.tag)
     })
     const { withRings, capacity } = engineFor(params, keyLists[0] || [])
-    const out = new Array(raw.length), errors = new Array(raw.length), level = verifyLevel
+    const out = new Array(raw.length), errors = new Array(raw.length), level = verifyLevel, reps = verifyReps
     const per = capacity()
     for (let g = 0; g < rings.length; g += per) {   // groups of at most residentRings rings
         const group = rings.slice(g, g + per)
@@ -695,6 +706,7 @@ async function verifySignatureLists(params, msgHashes, keyLists, proofs) {
             const r = await withRings(group, (engine, ids) => {
                 useWire(engine, wire)
                 useVerifyLevel(engine, level)
+                useVerifyReps(engine, reps)
                 return engine._verifyRingsNow(m, sel.map((i) => raw[i]), sel.map((i) => ids[ringOfProof[i] - g]))
             })
             sel.forEach((i, k) => { out[i] = r[k]; errors[i] = r.errors[k] })
@@ -858,6 +870,6 @@ async function verifyMemberships(pedersenParams, comPoints, keys, proofs) {
     })
 }
 
-module.exports = { proveMembership, verifyMembership, proveMemberships, verifyMemberships, GKProof, Commitment, commit, screenSignatureLists, findKey, SCREEN, WHICH_NONE, recoverSignatureLists, recoverKey, RECOVER, verifySignatureLists, proveSignatureLists, _ringGenerations, setVerifyLevel, getVerifyLevel, generateParamsList, generateParamsListHardened, keyToInt, proveSignatureList, verifySignatureList, proveSignatureListBatch, verifySignatureListBatch,
+module.exports = { proveMembership, verifyMembership, proveMemberships, verifyMemberships, GKProof, Commitment, commit, screenSignatureLists, findKey, SCREEN, WHICH_NONE, recoverSignatureLists, recoverKey, RECOVER, verifySignatureLists, proveSignatureLists, _ringGenerations, setVerifyLevel, getVerifyLevel, setVerifyReps, getVerifyReps, generateParamsList, generateParamsListHardened, keyToInt, proveSignatureList, verifySignatureList, proveSignatureListBatch, verifySignatureListBatch,
     writeJson, readJson, writeJsonBatch, readJsonBatch, SignatureProofList, SystemParametersList, PedersenParams, generatePedersenParams, p256, tomEdwards256, ALL_GROUPS,
     Group, Point, Scalar, Engine, shutdown, setWireLayout, getWireLayout, setOption, native }

@@ -248,6 +248,7 @@ static napi_value SetOption(napi_env env, napi_callback_info info) {
                        : !strcmp(name, "verifyGroups") ? zk_ctx_set_verify_groups(c, val)
                        : !strcmp(name, "wire")        ? zk_ctx_set_wire(c, val)
                        : !strcmp(name, "verifyLevel") ? zk_ctx_set_verify_level(c, val) /* 0: the context's secLevel, 1: every proof's own */
+                       : !strcmp(name, "verifyReps")  ? zk_ctx_set_verify_reps(c, val) /* 0: the 20 sampled repetitions, 1: every repetition of every proof */
                        : !strcmp(name, "wipe")        ? zk_ctx_wipe(c) /* value ignored: zero the witness-derived device memory of every context now */
                                                       : ZK_E_ARG;
         if (st != ZK_OK) return throw_text(env, st, name);

@@ -264,6 +264,30 @@ zk_status zk_verify_batch_device(zk_ctx *ctx, uint64_t B, const void *d_msg_hash
 enum { ZK_VERIFY_LEVEL_CONTEXT = 0, ZK_VERIFY_LEVEL_PER_PROOF = 1 };
 zk_status zk_ctx_set_verify_level(zk_ctx *ctx, uint32_t mode);
 
+/* Verified repetitions.  ZK_VERIFY_REPS_SAMPLE (default): the 20-subset above -- generateIndices(20, count) from the verifier's seed, as
+ * verifySignatureList does (src/zkpAttestList.ts:177, `// TODO: raise!`); one broken repetition out of 80 is then missed with probability
+ * 60/80.  ZK_VERIFY_REPS_ALL: every repetition the proof holds is checked.  The semantics are verifySignatureList with
+ * verifyExp(..., secparam = pi.length, Q) and the repetitions walked in ascending index order in place of a random permutation.  Per proof,
+ * in order: ZK_E_BAD_ENCODING for a structural error (exactly the default mode's); ok 0 / status 0 where membership fails; ZK_E_SECLEVEL
+ * below 20 repetitions (the context's level, or the header's in ZK_VERIFY_LEVEL_PER_PROOF -- as in the default mode); otherwise the
+ * exception of the LOWEST-index repetition that throws -- ZK_E_PARAMS_NOT_FOUND where its header bit disagrees with the recomputed
+ * challenge bit, ZK_E_T_INF / ZK_E_T1_INF where its point is the identity, the type looked at before the point --; otherwise ok = 1 if and
+ * only if every relation of every repetition holds.  This is STRICTER than the reference: a proof it accepts under some seed may be
+ * rejected here.  The verifier-seed contract keeps its 2n+1 membership fills; generateIndices draws nothing; the engine's 128-bit
+ * randomisers still come from the seed, and the passes below reuse them.
+ * How: P = ceil(count / 20) passes over the sampled verifier's pipeline at the level the call is planned for.  Pass r < P - 1 checks
+ * repetitions 20 r .. 20 r + 19, the last pass count - 20 .. count - 1 (it overlaps the one before it where 20 does not divide count); the
+ * verdicts are merged as ok &= ok_r, status = status ? status : status_r.  Each pass repeats the challenge hashes, R's table and the
+ * membership check, so a call costs about P sampled calls.  Independent of zk_ctx_set_verify_level (each level's window runs its own P),
+ * of the wire layout (ZKA1P input is expanded once) and of the protocol mode.  Every blocking verify entry point follows it
+ * (zk_verify_batch, zk_verify_batch_device, the _rings forms, the pool's blocking calls); a host-pointer call of more than one pass first
+ * copies its proofs to HBM in one transfer.  zk_last_timing reports the families summed over the passes, plus "v_merge".
+ * Not provided: streamed variants -- zk_verify_submit returns ZK_E_ARG in this mode.
+ * The setter follows the rules of zk_ctx_set_verify_level (takes effect with the next call; ZK_E_ARG while streamed jobs are queued, or for
+ * an unknown mode).  zk_pool_set_verify_reps sets the mode of every shard context. */
+enum { ZK_VERIFY_REPS_SAMPLE = 0, ZK_VERIFY_REPS_ALL = 1 };
+zk_status zk_ctx_set_verify_reps(zk_ctx *ctx, uint32_t mode);
+
 /* Resident rings.  The reference takes the ring as an argument of every call (proveSignatureList / verifySignatureList,
  * src/zkpAttestList.ts:104-184); a context keeps up to ZK_MAX_RINGS rings built at once, so that a verifier serving several key sets
  * never rebuilds one (a rebuild costs tens of milliseconds at 2^16 keys, a verification ~1.5 ms).  Exactly one of them, or none, is ACTIVE:
@@ -553,6 +577,7 @@ void zk_pool_shard(const zk_pool *pool, uint64_t B, int i, uint64_t *first, uint
 zk_status zk_pool_set_params(zk_pool *pool, const uint8_t nist_h[64], const uint8_t tom_g[72], const uint8_t tom_h[72], uint32_t sec_level);
 zk_status zk_pool_set_ring(zk_pool *pool, const uint8_t *keys_be32, uint64_t n_keys);
 zk_status zk_pool_set_verify_level(zk_pool *pool, uint32_t mode);   /* zk_ctx_set_verify_level on every shard context */
+zk_status zk_pool_set_verify_reps(zk_pool *pool, uint32_t mode);    /* zk_ctx_set_verify_reps on every shard context */
 zk_status zk_pool_add_ring(zk_pool *pool, const uint8_t *keys_be32, uint64_t n_keys, uint32_t *ring);   /* resident rings: see zk_ctx_add_ring */
 zk_status zk_pool_use_ring(zk_pool *pool, uint32_t ring);
 zk_status zk_pool_drop_ring(zk_pool *pool, uint32_t ring);
@@ -687,7 +712,10 @@ int zk_pool_test_locality(const char *pci_bus_id, int *numa_node, int *cpus, int
  * 8 = windows those calls proved;
  * 9 = bytes of the staging buffer those calls have grown so far (grow-only);
  * 10 = form of the context's comb tables of g and h: 1 = the a = -1 model (7 products per table addition; chosen by zk_ctx_set_params when q * g = q * h =
- *     identity), 0 = the a = 1 image (any other pair of curve points); ~0 before zk_ctx_set_params.  Bytes and verdicts are the same. */
+ *     identity), 0 = the a = 1 image (any other pair of curve points); ~0 before zk_ctx_set_params.  Bytes and verdicts are the same;
+ * 11 = nonzero 32-bit words in the buffers a witness wipe zeroes, with nothing in flight;
+ * 12 = passes of the verifier's pipeline run by blocking calls since the context was created: one per call (or per window of a split batch), ceil(count / 20)
+ *     in ZK_VERIFY_REPS_ALL. */
 uint64_t zk_test_counter(const zk_ctx *ctx, int which);
 /* Only in the test build (lib/libzkattest_hip_testhooks.so, csrc/api_pool.hip under ZK_TEST_HOOKS); the product library exports neither:
  *   void zk_test_pool_fail_next_submit, arguments (zk_pool *pool, int slot):

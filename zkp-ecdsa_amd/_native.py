@@ -21,7 +21,7 @@ SYMBOLS = [
     'zk_prove_submit', 'zk_prove_submit_device', 'zk_prove_wait', 'zk_verify_submit', 'zk_verify_wait', 'zk_test_counter', 'zk_test_tom_commit_shape', 'zk_ctx_set_key_tables',
     'zk_proofs_to_json_batch', 'zk_proofs_from_json_batch', 'zk_ctx_set_ring_fold',
     'zk_pool_prove_submit', 'zk_pool_prove_wait', 'zk_pool_verify_submit', 'zk_pool_verify_wait', 'zk_ctx_set_verify_groups',
-    'zk_ctx_set_verify_level', 'zk_pool_set_verify_level',
+    'zk_ctx_set_verify_level', 'zk_pool_set_verify_level', 'zk_ctx_set_verify_reps', 'zk_pool_set_verify_reps',
     'zk_ctx_add_ring', 'zk_ctx_add_ring_device', 'zk_ctx_use_ring', 'zk_ctx_drop_ring', 'zk_ring_info', 'zk_verify_batch_rings', 'zk_verify_batch_rings_device',
     'zk_pool_add_ring', 'zk_pool_use_ring', 'zk_pool_drop_ring', 'zk_pool_verify_batch_rings',
     'zk_ctx_update_ring', 'zk_pool_update_ring',
@@ -108,6 +108,8 @@ def lib():
         L.zk_ctx_set_mode.argtypes = [vp, u32]
         L.zk_ctx_set_verify_level.argtypes = [vp, u32]
         L.zk_pool_set_verify_level.argtypes = [vp, u32]
+        L.zk_ctx_set_verify_reps.argtypes = [vp, u32]
+        L.zk_pool_set_verify_reps.argtypes = [vp, u32]
         L.zk_ctx_add_ring.argtypes = [vp, C.c_char_p, u64, C.POINTER(u32)]
         L.zk_ctx_add_ring_device.argtypes = [vp, vp, u64, C.POINTER(u32)]
         L.zk_ctx_use_ring.argtypes = [vp, u32]
@@ -415,6 +417,11 @@ class Engine:
         """zk_ctx_set_verify_level: False / 0 = every proof at the context's secLevel (default), True / 1 = every proof at its own header's
         secLevel, as the reference's verifySignatureList does."""
         self._chk(self.L.zk_ctx_set_verify_level(self.h, 1 if per_proof else 0))
+
+    def set_verify_reps(self, all):
+        """zk_ctx_set_verify_reps: False / 0 = the 20 repetitions generateIndices samples (default, the reference's verifier), True / 1 = every
+        repetition of every proof, in ceil(secLevel / 20) passes (stricter than the reference; blocking calls only)."""
+        self._chk(self.L.zk_ctx_set_verify_reps(self.h, 1 if all else 0))
 
     def ring_digest(self):
         d = C.create_string_buffer(32)
@@ -939,6 +946,10 @@ class Pool:
     def set_verify_level(self, per_proof):
         """zk_pool_set_verify_level: Engine.set_verify_level on every shard context."""
         self._chk(self.L.zk_pool_set_verify_level(self.h, 1 if per_proof else 0))
+
+    def set_verify_reps(self, all):
+        """zk_pool_set_verify_reps: Engine.set_verify_reps on every shard context."""
+        self._chk(self.L.zk_pool_set_verify_reps(self.h, 1 if all else 0))
 
     def set_ring(self, keys_be32, nkeys=None):
         keys_be32 = bytes(keys_be32)

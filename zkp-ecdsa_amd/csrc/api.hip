@@ -665,6 +665,12 @@ extern "C" zk_status zk_ctx_set_verify_level(zk_ctx* c, uint32_t mode) {
     c->verify_level = mode;
     return ZK_OK;
 }
+extern "C" zk_status zk_ctx_set_verify_reps(zk_ctx* c, uint32_t mode) {
+    if (!c || (mode != ZK_VERIFY_REPS_SAMPLE && mode != ZK_VERIFY_REPS_ALL)) return ZK_E_ARG;
+    if (c->stream_busy) return busy_refusal(c);
+    c->verify_reps = mode;
+    return ZK_OK;
+}
 extern "C" zk_status zk_ring_digest(zk_ctx* c, uint8_t digest[32]) {
     if (!c || !digest) return ZK_E_ARG;
     if (!c->ring->N || !c->ring->ring_digest) return ZK_E_BUFFER;

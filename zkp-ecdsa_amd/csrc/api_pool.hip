@@ -405,6 +405,16 @@ extern "C" zk_status zk_pool_set_verify_level(zk_pool* p, uint32_t mode) {
         if (zk_status zs = zk_ctx_set_verify_level(p->ctx[i], mode)) return zs;
     return ZK_OK;
 }
+// exhaustive verify mode on every shard context (zk_ctx_set_verify_reps: ZK_E_ARG while a shard has streamed jobs queued)
+extern "C" zk_status zk_pool_set_verify_reps(zk_pool* p, uint32_t mode) {
+    if (!p) return ZK_E_ARG;
+    if (mode != ZK_VERIFY_REPS_SAMPLE && mode != ZK_VERIFY_REPS_ALL) return ZK_E_ARG;
+    for (size_t i = 0; i < p->ctx.size(); i++)
+        if (p->ctx[i]->stream_busy) return ZK_E_ARG;
+    for (size_t i = 0; i < p->ctx.size(); i++)
+        if (zk_status zs = zk_ctx_set_verify_reps(p->ctx[i], mode)) return zs;
+    return ZK_OK;
+}
 
 // The ring's keys on every shard device: one PCIe upload to device 0, then an RCCL broadcast or peer copies.  f(i, d_keys_i) runs on every shard
 // (pool_each) and the staging buffers are freed behind it; the calling thread's current device is restored on every exit path.

@@ -435,6 +435,10 @@ extern "C" zk_status zk_verify_submit(zk_ctx* c, uint64_t B, const uint8_t* msg,
     if (!c || !job || !B || !msg || !proofs || !off || !ok || !status) return ZK_E_ARG;
     *job = nullptr;
     HIPCHK(c, hipSetDevice(c->device));
+    if (c->verify_reps == ZK_VERIFY_REPS_ALL) {
+        c->err = "the exhaustive verify mode (zk_ctx_set_verify_reps) has no streamed variant";
+        return ZK_E_ARG;
+    }
     const bool per_proof = c->verify_level == ZK_VERIFY_LEVEL_PER_PROOF;
     if (!per_proof && c->params_set && c->P.sec < VK) return ZK_E_SECLEVEL;
     if (off[0] != 0) return ZK_E_ARG;
@@ -585,6 +589,7 @@ extern "C" uint64_t zk_test_counter(const zk_ctx* c, int which) {
             }
         return n;
     }
+    if (which == 12) return c->dbg_v_passes;     // passes of the verifier's pipeline run by blocking calls (ceil(sec / VK) per call or window in ZK_VERIFY_REPS_ALL)
     if (which == 10) return c->params_set ? c->P.tom_model : ~0ull;   // form of the comb tables of g and h (curve.h): 1 = the a = -1 model (both bases of odd order), 0 = the a = 1 image
     return which == 0 ? c->dbg_recheck_proofs : which == 2 ? c->dbg_msm_terms : which == 3 ? c->dbg_p256_batched : 0;
 }

@@ -203,7 +203,7 @@ zk_status VerifyJob::stage1(uint64_t chunk_no) {
     const uint64_t* d_off = off_of(chunk_no);   // shadows the member: the chunk's own offsets when the input is packed
     {
         MaybeScope t(timed, c, "v_parse_validate", s);
-        if (d_packed) launch_v_unpack(s, V.sec, cnt, d_packed, d_poff, first, ubase[chunk_no], (uint8_t*)d_proofs, d_uoff + first + chunk_no);
+        if (d_packed && !unpacked) launch_v_unpack(s, V.sec, cnt, d_packed, d_poff, first, ubase[chunk_no], (uint8_t*)d_proofs, d_uoff + first + chunk_no);
         launch_v_header_validate(s, V, cnt, d_proofs, d_off, first);
     }
     if (memb_only) {   // a level below VK: the membership proof's challenge, total and terms (stage 2b sums them per proof)
@@ -239,7 +239,7 @@ zk_status VerifyJob::stage1(uint64_t chunk_no) {
         }
         {
             MaybeScope t(timed, c, "v_hash", sq);
-            launch_v_sample(sq, V, cnt, d_vseeds, first);
+            launch_v_sample(sq, V, cnt, d_vseeds, first, pass);
         }
         HIPCHK(c, hipEventRecord(A.aux_done[2], sq));
         {   // aux 0: the Exp challenge (three kernels where the schedule buffer holds the chunk): 0.45 ms in one lane, needed only to CHECK the header's bits
@@ -273,7 +273,7 @@ zk_status VerifyJob::stage1(uint64_t chunk_no) {
         // (a chunk of this size keeps one wave per SIMD busy with one lane per proof already: the three-kernel path of the small chunks measured 1.9 ms per
         // 32 768 proofs against this kernel's 1.86, profiles/r05_ab_variants.txt)
         launch_v_challenges(s, V, cnt, d_proofs, d_off, d_msg, first, 3);
-        launch_v_sample(s, V, cnt, d_vseeds, first);
+        launch_v_sample(s, V, cnt, d_vseeds, first, pass);
         launch_v_sample_check(s, V, cnt);
     }
     {
@@ -664,6 +664,20 @@ static zk_status verify_device(zk_ctx* c, uint64_t B, const uint8_t* d_msg, cons
         J.memb_only = plan_sec(c) < VK;
         J.host_release = J.plan.size() == 1 && B <= V_WIDE_MAXP && !no_release && !zk_one_lane_chains() && !J.memb_only;
     }
+    // exhaustive mode: ceil(sec / VK) passes at the level the call is planned for (a level below VK checks membership only: one pass)
+    const bool all = c->verify_reps == ZK_VERIFY_REPS_ALL && !J.memb_only;
+    const uint32_t passes = all ? (plan_sec(c) + VK - 1) / VK : 1;
+    uint8_t* pass_ok = nullptr;
+    int32_t* pass_st = nullptr;
+    if (passes > 1) {
+        if (zk_status zs = lay_out(c, B_vp, [&](uint8_t* base) {
+                Carver k(base);
+                pass_st = (int32_t*)k.take(4 * B), pass_ok = (uint8_t*)k.take(B);
+                return k.off + ZK_LAYOUT_TAIL;
+            }))
+            return zs;
+        if (zk_status zs = ensure_h_stage(c, 0)) return zs;   // c->in_ready
+    }
     if (c->wire == ZK_WIRE_ZKA1P) {   // the proofs handed in are packed: every chunk is expanded into the context's staging first
         uint64_t total = 0;
         if (host_off) total = host_off[B];
@@ -710,16 +724,35 @@ static zk_status verify_device(zk_ctx* c, uint64_t B, const uint8_t* d_msg, cons
     // stage 1 of the next NL - 1 chunks is enqueued on the other lanes before the host blocks on this chunk's batched check
     // ... and so are the batched passes of those chunks (stage2a: no host round trip), so that the reductions that end one chunk's pass -- dependent chains, 3 ms with
     // the GPU nearly idle -- run beside the next chunk's bucket sums; the host blocks in stage2b of the oldest chunk only
-    for (uint64_t k = 0; k < nchunks && !zs; k++) {
-        while (!zs && J.next_s1 < nchunks && J.next_s1 < k + J.NL) zs = J.stage1(J.next_s1++);
-        while (!zs && J.next_s2a < J.next_s1) zs = J.stage2a(J.next_s2a++);
-        if (!zs) zs = J.stage2b(k);
-    }
+    // ZK_VERIFY_REPS_ALL: the chunks run once per pass, every pass over VK repetitions of its own (k_verify_all.hip); only the sampler is told which.  Pass 0
+    // writes the caller's verdicts, a later one the context's scratch, merged into the caller's on c->stream (= lane 0's) once the pass's lanes are done;
+    // the lanes of the next pass, which writes the scratch again, start behind the merge (inputs_ready).
     hipError_t e1 = hipSuccess;
-    for (uint32_t l = 0; l < J.NL; l++) {
-        hipError_t e = hipStreamSynchronize(c->pl[l].stream);
-        if (e1 == hipSuccess) e1 = e;
+    for (uint32_t r = 0; r < passes && !zs && e1 == hipSuccess; r++) {
+        if (all) J.pass = (int)r;
+        J.unpacked = r > 0;
+        J.next_s1 = J.next_s2a = 0;
+        if (r) J.d_ok = pass_ok, J.d_status = pass_st;
+        for (uint64_t k = 0; k < nchunks && !zs; k++) {
+            while (!zs && J.next_s1 < nchunks && J.next_s1 < k + J.NL) zs = J.stage1(J.next_s1++);
+            while (!zs && J.next_s2a < J.next_s1) zs = J.stage2a(J.next_s2a++);
+            if (!zs) zs = J.stage2b(k);
+        }
+        for (uint32_t l = 0; l < J.NL; l++) {
+            hipError_t e = hipStreamSynchronize(c->pl[l].stream);
+            if (e1 == hipSuccess) e1 = e;
+        }
+        c->dbg_v_passes++;
+        if (r && !zs && e1 == hipSuccess) {
+            MaybeScope t(J.timed, c, "v_merge", c->stream);
+            launch_v_merge_pass(c->stream, B, pass_ok, pass_st, d_ok, d_status);
+            if (r + 1 < passes) {
+                e1 = hipEventRecord(c->in_ready, c->stream);
+                J.inputs_ready = c->in_ready;
+            }
+        }
     }
+    if (passes > 1 && !zs && e1 == hipSuccess) e1 = hipStreamSynchronize(c->stream);
     hipError_t e3 = host_src ? hipStreamSynchronize(c->copy_stream) : hipSuccess;
     if (zs || e1 != hipSuccess) drain();   // an error between a fork and its join may have left kernels on an auxiliary stream: they finish before the buffers go
     if (zs) return zs;
@@ -1091,7 +1124,9 @@ zk_status verify_host(zk_ctx* c, uint64_t B, const uint8_t* msg, const uint8_t* 
     if (zs) return zs;
     uint8_t* d_proofs = (uint8_t*)c->buf[B_io].p;
     // page-locked `proofs` (zk_host_alloc): chunk-wise DMA under the kernels of the earlier chunks; pageable: one blocking copy
-    const bool pinned = !mixed && host_ptr_is_pinned(proofs);
+    // (exhaustive mode, several passes: every pass reads all of the bytes -- they cross first, in one transfer, like a mixed-level batch's)
+    const bool multipass = c->verify_reps == ZK_VERIFY_REPS_ALL && plan_sec(c) > VK;
+    const bool pinned = !mixed && !multipass && host_ptr_is_pinned(proofs);
     if (pinned) {
         zs = ensure_copy_stream(c);
         if (zs) return zs;

@@ -45,7 +45,8 @@ enum GrowPolicy {
     X(in, GROW_SLACK, true)       /* host-pointer entry points: the small per-proof arrays (inputs, offsets, statuses, verdicts) */                               \
     X(unp, GROW_EXACT, false)     /* ZKA1P input of the synchronous verify calls: staging of the expanded proofs */                                               \
     X(unp_off, GROW_EXACT, false) /* ... and their per-chunk offsets */                                                                                           \
-    X(m_off, GROW_SLACK, false)   /* membership proofs on their own: offsets of a verify call's equally long proofs */
+    X(m_off, GROW_SLACK, false)   /* membership proofs on their own: offsets of a verify call's equally long proofs */                                            \
+    X(vp, GROW_SLACK, false)      /* exhaustive verify mode: verdicts and statuses of a pass behind the first (5 B bytes), until they are merged */
 enum BufId {
 #define X(name, policy, witness) B_##name,
     ZK_CTX_BUFS(X)
@@ -99,6 +100,7 @@ struct zk_ctx {
     uint32_t pr_seg_force = 0;     // test build only (zk_test_set_prove_segment): proofs per segment instead of what ZK_PR_STAGE_BYTES holds; 0 = off
     uint32_t mode = 0;                 // zk_ctx_set_mode: ZK_MODE_REFERENCE / ZK_MODE_HARDENED
     uint32_t verify_level = 0;         // zk_ctx_set_verify_level: ZK_VERIFY_LEVEL_CONTEXT / ZK_VERIFY_LEVEL_PER_PROOF
+    uint32_t verify_reps = 0;          // zk_ctx_set_verify_reps: ZK_VERIFY_REPS_SAMPLE / ZK_VERIFY_REPS_ALL
     // per-proof mode: the repetition count the verifier's workspaces are planned for during one call (or while streamed verify jobs are queued); the
     // context's own P.sec otherwise (plan_sec below), so that the next prove call plans at the context's level again
     uint32_t v_sec = 0;
@@ -191,6 +193,7 @@ struct zk_ctx {
     uint64_t dbg_etab_blocks = 0;      // 256-key blocks whose table E was built (k_gk.hip) since the context was created
     uint64_t dbg_pr_segments = 0;      // segments that mixed-ring prove calls staged since the context was created (a one-ring call stages none)
     uint64_t dbg_pr_windows = 0;       // ... and the windows they proved
+    uint64_t dbg_v_passes = 0;         // passes of the verifier's pipeline since the context was created: one per blocking call or window, ceil(sec / VK) in ZK_VERIFY_REPS_ALL
     // timing
     std::vector<TimerRec> trecs;
     std::vector<hipEvent_t> epool;

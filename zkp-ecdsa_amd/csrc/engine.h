@@ -275,7 +275,10 @@ void launch_v_front_q(hipStream_t s, const DevParams& P, const Workspace& W, con
 // through the three-kernel path (message from the proof bytes, then launch_exph_hash into V.chal)
 void launch_v_challenges(hipStream_t s, const VWork& V, uint32_t count, const uint8_t* proofs, const uint64_t* off, const uint8_t* msg, uint64_t first, uint32_t parts);
 void launch_v_exp_challenge_small(hipStream_t s, const Workspace& W, const VWork& V, uint32_t count, const uint8_t* proofs, const uint64_t* off, uint64_t first);
-void launch_v_sample(hipStream_t s, const VWork& V, uint32_t count, const uint8_t* vseeds, uint64_t first);
+// pass < 0: generateIndices' subset from the verifier's seed; pass >= 0 (ZK_VERIFY_REPS_ALL): the VK repetitions of that pass in ascending order (k_verify_all.hip)
+void launch_v_sample(hipStream_t s, const VWork& V, uint32_t count, const uint8_t* vseeds, uint64_t first, int pass = -1);
+void launch_v_sample_all(hipStream_t s, const VWork& V, uint32_t count, uint32_t pass);
+void launch_v_merge_pass(hipStream_t s, uint64_t B, const uint8_t* ok_r, const int32_t* st_r, uint8_t* ok, int32_t* status);   // ok &= ok_r, status = status ? status : st_r
 void launch_v_sample_check(hipStream_t s, const VWork& V, uint32_t count);
 void launch_v_exp_status(hipStream_t s, const Workspace& W, const VWork& V, uint32_t count, bool have_jm);
 #define V_PH_MAXP 64      // proofs per call whose PointAdd challenges go through the message / schedule / two-lane rounds kernels

@@ -99,6 +99,10 @@ struct VerifyJob {
     // per-proof verify levels (zk_ctx_set_verify_level): proofs of fewer than VK repetitions -- header, validation and the membership proof only, then
     // 'security level not achieved' where membership holds (k_v_final_memb)
     bool memb_only = false;
+    // exhaustive verify mode (zk_ctx_set_verify_reps): the pass this run of the chunks is (handed to the sampler alone), -1 = the sampled subset; passes behind
+    // the first find ZKA1P input expanded already
+    int pass = -1;
+    bool unpacked = false;
     hipEvent_t inputs_ready = nullptr;
     std::vector<ChunkPlan> plan;
     std::vector<hipEvent_t> arrived;     // host_src: one event per chunk, recorded on the copy stream behind the chunk's bytes

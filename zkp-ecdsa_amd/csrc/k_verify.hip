@@ -1819,7 +1819,8 @@ void launch_v_exp_challenge_small(hipStream_t s, const Workspace& W, const VWork
     L1(k_v_exph_msg, count * (2 + 3 * V.sec + 1), 256, W, V, count, proofs, off, first);
     launch_exph_hash(s, W, count, V.chal);
 }
-void launch_v_sample(hipStream_t s, const VWork& V, uint32_t count, const uint8_t* vseeds, uint64_t first) {   // needs the header only
+void launch_v_sample(hipStream_t s, const VWork& V, uint32_t count, const uint8_t* vseeds, uint64_t first, int pass) {   // needs the header only
+    if (pass >= 0) return launch_v_sample_all(s, V, count, (uint32_t)pass);   // every repetition, VK per pass: nothing is drawn
     L1(k_v_sample_fills, count * VS_KMAX, 256, V, count, vseeds, first);
     L1(k_v_sample, count, 64, V, count, vseeds, first);
 }
