@@ -78,6 +78,9 @@ export function verifyMembership(params: PedersenParams | SystemParametersList, 
 /** batched over one key list */
 export function proveMemberships(params: PedersenParams | SystemParametersList, coms: Commitment[], indices: number[], keys: bigint[] | Buffer): Promise<GKProof[]>
 export function verifyMemberships(params: PedersenParams | SystemParametersList, coms: Point[], keys: bigint[] | Buffer, proofs: GKProof[]): Promise<boolean[]>
+/** batched with one key list per entry: keysList[i] is the ring of commitment i (resolved to the engine's resident rings like proveSignatureLists' key lists) */
+export function proveMembershipLists(params: PedersenParams | SystemParametersList, coms: Commitment[], indices: number[], keysList: (bigint[] | Buffer)[]): Promise<GKProof[]>
+export function verifyMembershipLists(params: PedersenParams | SystemParametersList, coms: Point[], keysList: (bigint[] | Buffer)[], proofs: GKProof[]): Promise<boolean[]>
 type Newable<T> = new (...args: any[]) => T
 export function writeJson<T>(type: Newable<T>, object: T): string
 export function readJson<T>(type: Newable<T>, text: string): T

@@ -406,6 +406,22 @@ class Engine {
         const r = native.memberVerifyBatch(this.h, Buffer.concat(coms), Buffer.concat(proofs))
         return { ok: Array.from(r.ok, (v) => v === 1), status: i32(r.status) }
     }
+    // ... with one resident ring id per entry (zk_member_*_batch_rings): the active ring plays no part; an id that is not resident gives status 14 and no proof
+    memberProofSizeRing(ringId) { return native.memberProofSizeRing(this.h, ringId) }
+    memberProveBatchRings(which, ringIds, blinders, seeds) {
+        const B = which.length, u32 = (a) => Buffer.from(Uint32Array.from(a).buffer)
+        const r = native.memberProveBatchRings(this.h, u32(which), u32(ringIds), blinders || null, seeds || crypto.randomBytes(32 * B))   // one fresh seed per proof
+        const st = i32(r.status), cut = (b, w) => Array.from({ length: B }, (_, i) => b.slice(w * i, w * i + w))
+        const off = Array.from({ length: B + 1 }, (_, i) => Number(r.off.readBigUInt64LE(8 * i)))
+        return { proofs: st.length ? Array.from(st, (s, i) => (s === 0 ? r.proofs.slice(off[i], off[i + 1]) : null)) : [], coms: cut(r.coms, 72), blinders: cut(r.blinders, 32), status: st, off, raw: r.proofs }
+    }
+    memberVerifyBatchRings(coms, proofs, ringIds) {   // proofs: one Buffer per entry, laid back to back -> { ok: boolean[], status: Int32Array }
+        const off = Buffer.alloc(8 * (proofs.length + 1))
+        let run = 0
+        proofs.forEach((p, i) => { run += p.length; off.writeBigUInt64LE(BigInt(run), 8 * (i + 1)) })
+        const r = native.memberVerifyBatchRings(this.h, Buffer.concat(coms), Buffer.concat(proofs), off, Buffer.from(Uint32Array.from(ringIds).buffer))
+        return { ok: Array.from(r.ok, (v) => v === 1), status: i32(r.status) }
+    }
     proveBatchRingsAsync(msg, sig, pk, which, ringIds, seeds) { return this._chain(() => this._proveRingsNow(msg, sig, pk, which, ringIds, seeds)) }
     verifyBatchRingsAsync(msg, proofs, ringIds, seeds) { return this._chain(() => this._verifyRingsNow(msg, proofs, ringIds, seeds)) }
     proveBatchAsync(msg, sig, pk, which, seeds) { return this._chain(() => this._proveNow(msg, sig, pk, which, seeds)) }
@@ -869,7 +885,64 @@ async function verifyMemberships(pedersenParams, comPoints, keys, proofs) {
         return r.ok
     })
 }
+// One key list per entry: keysList[i] is the ring of commitment i and indices[i] indexes it -- the reference takes `keys` with every proveMembership /
+// verifyMembership call, this is that interface over a batch.  The key lists are resolved to resident rings the way proveSignatureLists / verifySignatureLists
+// resolve theirs; a call is split only when it names more rings than residentRings, and each part is ONE zk_member_prove_batch_rings /
+// zk_member_verify_batch_rings.  -> GKProof[] / boolean[] in the order given.
+function memberRingsOf(keysList, prove) {
+    const rings = [], ringOf_ = new Array(keysList.length), byTag = new Map()
+    keysList.forEach((keys, i) => {
+        checkRingSize(Buffer.isBuffer(keys) ? keys.length / 32 : keys.length, prove)
+        const r = ringOf(keys)
+        if (!byTag.has(r.tag)) { byTag.set(r.tag, rings.length); rings.push(r) }
+        ringOf_[i] = byTag.get(r.tag)
+    })
+    return { rings, ringOfEntry: ringOf_ }
+}
+async function proveMembershipLists(pedersenParams, coms, indices, keysList) {
+    const B = coms.length
+    if (indices.length !== B || keysList.length !== B) throw new RangeError('proveMembershipLists: one index and one key list per commitment')
+    const { rings, ringOfEntry } = memberRingsOf(keysList, true)
+    if (!B) return []
+    const { withRings, capacity } = engineFor(paramsOf(pedersenParams), keysList[0])
+    const out = new Array(B), per = capacity()
+    for (let g = 0; g < rings.length; g += per) {   // groups of at most residentRings rings: one group unless the call names more
+        const sel = []
+        for (let i = 0; i < B; i++) if (ringOfEntry[i] >= g && ringOfEntry[i] < g + per) sel.push(i)
+        const r = await withRings(rings.slice(g, g + per), (engine, ids) =>
+            engine.memberProveBatchRings(sel.map((i) => indices[i]), sel.map((i) => ids[ringOfEntry[i] - g]), Buffer.concat(sel.map((i) => toBE(coms[i].r.k, 32)))))
+        sel.forEach((i, k) => {
+            if (r.status[k] !== 0) throw statusError(r.status[k])
+            if (!r.coms[k].equals(tomBytes(coms[i].p))) throw new Error('proveMembership: com does not commit to keys[index] with blinder com.r')
+            out[i] = new GKProof(r.proofs[k])
+        })
+    }
+    return out
+}
+async function verifyMembershipLists(pedersenParams, comPoints, keysList, proofs) {
+    const B = proofs.length
+    if (comPoints.length !== B || keysList.length !== B) throw new RangeError('verifyMembershipLists: one commitment and one key list per proof')
+    const { rings, ringOfEntry } = memberRingsOf(keysList, false)
+    if (!B) return []
+    const { withRings, capacity } = engineFor(paramsOf(pedersenParams), keysList[0])
+    const out = new Array(B), per = capacity()
+    for (let g = 0; g < rings.length; g += per) {
+        const sel = []
+        for (let i = 0; i < B; i++) if (ringOfEntry[i] >= g && ringOfEntry[i] < g + per) sel.push(i)
+        const r = await withRings(rings.slice(g, g + per), (engine, ids) => {
+            const rid = sel.map((i) => ids[ringOfEntry[i] - g])
+            // a GKProof of another ring's length: the reference's length check returns false (gk.ts:208-218); the engine sees slots of the ring's size
+            const fit = sel.map((i, k) => { const b = proofs[i].bytes, size = engine.memberProofSizeRing(rid[k]); return b.length === size ? b : b.length > size ? b.slice(0, size) : Buffer.concat([b, Buffer.alloc(size - b.length)]) })
+            return engine.memberVerifyBatchRings(sel.map((i) => tomBytes(comPoints[i])), fit, rid)
+        })
+        sel.forEach((i, k) => {
+            if (r.status[k] !== 0) throw statusError(r.status[k])
+            out[i] = r.ok[k]
+        })
+    }
+    return out
+}
 
-module.exports = { proveMembership, verifyMembership, proveMemberships, verifyMemberships, GKProof, Commitment, commit, screenSignatureLists, findKey, SCREEN, WHICH_NONE, recoverSignatureLists, recoverKey, RECOVER, verifySignatureLists, proveSignatureLists, _ringGenerations, setVerifyLevel, getVerifyLevel, setVerifyReps, getVerifyReps, generateParamsList, generateParamsListHardened, keyToInt, proveSignatureList, verifySignatureList, proveSignatureListBatch, verifySignatureListBatch,
+module.exports = { proveMembership, verifyMembership, proveMemberships, verifyMemberships, proveMembershipLists, verifyMembershipLists, GKProof, Commitment, commit, screenSignatureLists, findKey, SCREEN, WHICH_NONE, recoverSignatureLists, recoverKey, RECOVER, verifySignatureLists, proveSignatureLists, _ringGenerations, setVerifyLevel, getVerifyLevel, setVerifyReps, getVerifyReps, generateParamsList, generateParamsListHardened, keyToInt, proveSignatureList, verifySignatureList, proveSignatureListBatch, verifySignatureListBatch,
     writeJson, readJson, writeJsonBatch, readJsonBatch, SignatureProofList, SystemParametersList, PedersenParams, generatePedersenParams, p256, tomEdwards256, ALL_GROUPS,
     Group, Point, Scalar, Engine, shutdown, setWireLayout, getWireLayout, setOption, native }

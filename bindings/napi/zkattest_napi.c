@@ -1138,6 +1138,91 @@ static napi_value MemberVerifyBatch(napi_env env, napi_callback_info info) {
     return v;
 }
 
+/* ... with one resident ring id per entry (zk_member_*_batch_rings); the active ring plays no part.
+ * (h, ring id) -> bytes of one ZKM1 proof over that resident ring, 0 for an id that is not resident */
+static napi_value MemberProofSizeRing(napi_env env, napi_callback_info info) {
+    napi_value argv[2], v = NULL;
+    if (!get_args(env, info, 2, argv)) return NULL;
+    Handle *h = get_handle(env, argv[0], 0);
+    uint32_t id = 0;
+    if (!h || napi_get_value_uint32(env, argv[1], &id) != napi_ok) return NULL;
+    napi_create_double(env, (double)zk_member_proof_size_ring(zk_pool_ctx(h->pool, 0), id), &v);
+    return v;
+}
+/* (h, which: B u32 LE, ring ids: B u32 LE, blinders: B x 32 or null, seeds: B x 32) -> {proofs: the batch's bytes back to back, off: B+1 u64 LE, coms: B x 72,
+ * blinders: B x 32, status: B i32 LE} */
+static napi_value MemberProveBatchRings(napi_env env, napi_callback_info info) {
+    napi_value argv[5];
+    if (!get_args(env, info, 5, argv)) return NULL;
+    Handle *h = get_handle(env, argv[0], 0);
+    uint8_t *wb, *ib, *bl, *seeds;
+    size_t lw, li, lb, ls;
+    if (!h || !get_bytes(env, argv[1], &wb, &lw) || !get_bytes(env, argv[2], &ib, &li) || !get_bytes(env, argv[3], &bl, &lb) || !get_bytes(env, argv[4], &seeds, &ls)) return NULL;
+    const size_t B = lw / 4;
+    if (lw % 4 || li != lw || (bl && lb != 32 * B) || ls != 32 * B) {
+        napi_throw_range_error(env, NULL, "memberProveBatchRings: one u32 index, one u32 ring id and 32 seed bytes per proof (and 32 blinder bytes each, or null)");
+        return NULL;
+    }
+    zk_ctx *c = zk_pool_ctx(h->pool, 0);
+    uint64_t total = 0;   /* (a Buffer's bytes need not be 4-byte aligned: indices and ids are copied) */
+    for (size_t b = 0; b < B; b++) {
+        uint32_t id;
+        memcpy(&id, ib + 4 * b, 4);
+        total += zk_member_proof_size_ring(c, id);
+    }
+    const size_t bytes = 8 * (B + 1) + (72 + 32 + 12) * B + total + 8;
+    uint8_t *buf = (uint8_t *)xmalloc(env, bytes);
+    if (!buf) return NULL;
+    uint64_t *off = (uint64_t *)buf;
+    uint32_t *which = (uint32_t *)(buf + 8 * (B + 1)), *ids = which + B;
+    int32_t *status = (int32_t *)(ids + B);
+    uint8_t *com = (uint8_t *)(status + B), *bo = com + 72 * B, *out = bo + 32 * B;
+    if (B) memcpy(which, wb, 4 * B), memcpy(ids, ib, 4 * B);
+    zk_rng rng = {ZK_RNG_SEED, seeds, 0};
+    zk_status st = zk_member_prove_batch_rings(c, B, which, ids, bl, &rng, com, bo, out, total, off, status);
+    napi_value v = NULL;
+    if (st != ZK_OK) throw_text(env, st, zk_last_error(c));
+    else if (napi_create_object(env, &v) == napi_ok) {
+        set_prop(env, v, "proofs", new_buffer(env, out, off[B])), set_prop(env, v, "off", new_buffer(env, off, 8 * (B + 1))), set_prop(env, v, "coms", new_buffer(env, com, 72 * B));
+        set_prop(env, v, "blinders", new_buffer(env, bo, 32 * B)), set_prop(env, v, "status", new_buffer(env, status, 4 * B));
+    }
+    memset(buf, 0, bytes);   /* the blinders */
+    free(buf);
+    return v;
+}
+/* (h, coms: B x 72, proofs: the batch's bytes, off: B+1 u64 LE, ring ids: B u32 LE) -> {ok: B bytes, status: B i32 LE} */
+static napi_value MemberVerifyBatchRings(napi_env env, napi_callback_info info) {
+    napi_value argv[5];
+    if (!get_args(env, info, 5, argv)) return NULL;
+    Handle *h = get_handle(env, argv[0], 0);
+    uint8_t *com, *proofs, *ob, *ib;
+    size_t lc, lp, lo, li;
+    if (!h || !get_bytes(env, argv[1], &com, &lc) || !get_bytes(env, argv[2], &proofs, &lp) || !get_bytes(env, argv[3], &ob, &lo) || !get_bytes(env, argv[4], &ib, &li)) return NULL;
+    const size_t B = lc / 72;
+    uint64_t last = 0;
+    if (lo == 8 * (B + 1)) memcpy(&last, ob + 8 * B, 8);
+    if (lc % 72 || lo != 8 * (B + 1) || li != 4 * B || last != lp) {
+        napi_throw_range_error(env, NULL, "memberVerifyBatchRings: one 72-byte commitment and one ring id per entry, B + 1 offsets that end at the proofs' length");
+        return NULL;
+    }
+    uint8_t *buf = (uint8_t *)xmalloc(env, 8 * (B + 1) + 9 * B + lp + 8);
+    if (!buf) return NULL;
+    uint64_t *off = (uint64_t *)buf;
+    uint32_t *ids = (uint32_t *)(buf + 8 * (B + 1));
+    int32_t *status = (int32_t *)(ids + B);
+    uint8_t *ok = (uint8_t *)(status + B), *pr = ok + B + (4 - B % 4) % 4;   /* (the slots' alignment is judged from offset 0: a copy that starts on a word) */
+    memcpy(off, ob, 8 * (B + 1));
+    if (B) memcpy(ids, ib, 4 * B);
+    if (lp) memcpy(pr, proofs, lp);
+    zk_ctx *c = zk_pool_ctx(h->pool, 0);
+    zk_status st = zk_member_verify_batch_rings(c, B, com, pr, off, ids, NULL, ok, status);
+    napi_value v = NULL;
+    if (st != ZK_OK) throw_text(env, st, zk_last_error(c));
+    else if (napi_create_object(env, &v) == napi_ok) set_prop(env, v, "ok", new_buffer(env, ok, B)), set_prop(env, v, "status", new_buffer(env, status, 4 * B));
+    free(buf);
+    return v;
+}
+
 static napi_value Init(napi_env env, napi_value exports) {
     static const struct {
         const char *name;
@@ -1154,7 +1239,8 @@ static napi_value Init(napi_env env, napi_value exports) {
                {"proveBatchRings", ProveBatchRings},   {"proveBatchRingsAsync", ProveBatchRingsAsync},
                {"screenBatchRings", ScreenBatchRings},
                {"recoverBatchRings", RecoverBatchRings},
-               {"memberProofSize", MemberProofSize},   {"memberProveBatch", MemberProveBatch}, {"memberVerifyBatch", MemberVerifyBatch}};
+               {"memberProofSize", MemberProofSize},   {"memberProveBatch", MemberProveBatch}, {"memberVerifyBatch", MemberVerifyBatch},
+               {"memberProofSizeRing", MemberProofSizeRing}, {"memberProveBatchRings", MemberProveBatchRings}, {"memberVerifyBatchRings", MemberVerifyBatchRings}};
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;
         if (napi_create_function(env, fns[i].name, NAPI_AUTO_LENGTH, fns[i].fn, NULL, &f) != napi_ok) return NULL;

@@ -506,7 +506,7 @@ zk_status zk_recover_batch_rings_device(zk_ctx *ctx, uint64_t B, const void *d_m
  * call).  zk_last_timing reports the families "rng_prepass", "gk_fold", "tom_commit", "tom_normalize", "hash", "respond_write" (prover) and
  * "v_parse_validate", "v_gk_total", "v_sums" (verifier).  ZK_E_BUFFER before zk_ctx_set_params or without an active ring; ZK_E_ARG for NULL pointers
  * (other than the optional ones), while streamed jobs are queued, and in ZK_MODE_HARDENED (there is no statement to bind).  B = 0 is ZK_OK.
- * Not provided: _rings forms, submit / wait forms, zk_pool_* forms, JSON, a packed layout. */
+ * Not provided: submit / wait forms, zk_pool_* forms, JSON, a packed layout. */
 uint64_t zk_member_proof_size(const zk_ctx *ctx);   /* active ring; 0 without one */
 zk_status zk_member_prove_batch(zk_ctx *ctx, uint64_t B, const uint32_t *which /*B*/, const uint8_t *blinder_be32 /*Bx32 or NULL*/, const zk_rng *rng,
                                 uint8_t *com_xy72 /*Bx72 out*/, uint8_t *blinder_out /*Bx32 or NULL*/, uint8_t *out, uint64_t out_cap,
@@ -517,6 +517,40 @@ zk_status zk_member_verify_batch(zk_ctx *ctx, uint64_t B, const uint8_t *com_xy7
                                  const uint8_t *verifier_seeds /*Bx32 or NULL*/, uint8_t *ok /*B*/, int32_t *per_proof_status /*B*/);
 zk_status zk_member_verify_batch_device(zk_ctx *ctx, uint64_t B, const void *d_com_xy72, const void *d_proofs, const void *d_verifier_seeds, void *d_ok,
                                         void *d_per_proof_status);
+/* One resident ring id per proof (zk_ctx_add_ring): the reference takes `values` with every call, so a batch over several key sets is its own interface.
+ * Neither form reads or changes the active ring -- a context whose rings are all inactive can prove and verify -- and a proof's size follows from its
+ * ring alone: zk_member_proof_size_ring(ctx, ring) = 16 + 288 n + 32 (3 n + 1) for a resident id, 0 otherwise.
+ * Prover: proof b, com_xy72[b], blinder_out[b] and per_proof_status[b] are byte for byte what zk_member_prove_batch returns for input b with ring
+ * ring_ids[b] active -- the same randomness contract (the fills of proof b depend on b's own seed or stream row alone), engine-drawn or caller blinders,
+ * which[b] indexing THAT ring's padded size (which[b] >= its N: ZK_E_ARG and a zeroed slot).  out_off[0] = 0, out_off[b + 1] = out_off[b] +
+ * zk_member_proof_size_ring(ctx, ring_ids[b]): the proofs lie back to back in index order, and the result can be handed to zk_member_verify_batch_rings
+ * with the same ring_ids as it is.  An id that is not resident: ZK_E_ARG, a zero-length slot, 72 zero bytes of com (32 of blinder_out).  out_cap <
+ * out_off[B]: ZK_E_BUFFER, decided before a byte of any output is written.
+ * Verifier, per proof and in this order: an id that is not resident: ok 0, ZK_E_ARG; a slot whose length proof_off[b + 1] - proof_off[b] is not
+ * zk_member_proof_size_ring(ctx, ring_ids[b]), whose offset is no multiple of 4, or with proof_off[b + 1] < proof_off[b] or > proof_off[B]: ok 0,
+ * ZK_E_BAD_ENCODING, and no byte of the slot is read; otherwise exactly the (ok, status) zk_member_verify_batch gives these 72 + size bytes with that
+ * ring active (a header whose n is not the ring's: ok 0, status 0).  No byte outside a proof's slot is read; verifier_seeds as above.
+ * How: the ids are classed (host pointers: on the host; device pointers: by one kernel and ONE read-back of the per-class counters).  A batch of one
+ * resident ring runs the one-ring pipeline on the caller's buffers with that ring bound.  Otherwise, per ring, windows of at most 2 x chunk x lanes
+ * proofs: one gather collects the window's small inputs (whole stream rows in ZK_RNG_STREAM mode), and the window's kernels write every proof, com,
+ * blinder, status and verdict once, at its final place; the verifier reads the proof bytes where they lie.  zk_test_counter 13 counts the windows.
+ * zk_last_timing reports the one-ring families summed over the windows, plus "m_class" and "m_gather".  The gathered inputs are witness-derived: a failed
+ * call, zk_ctx_wipe and zk_ctx_destroy zero them.  ZK_E_BUFFER before zk_ctx_set_params; ZK_E_ARG for NULL pointers (other than the optional ones), while
+ * streamed jobs are queued, and in ZK_MODE_HARDENED; B = 0 is ZK_OK (out_off[0] = 0).  The _device forms take every pointer in this context's HBM (4-byte
+ * aligned; offsets 8-byte aligned), rng->data too. */
+uint64_t zk_member_proof_size_ring(const zk_ctx *ctx, uint32_t ring);   /* 0 for an id that is not resident */
+zk_status zk_member_prove_batch_rings(zk_ctx *ctx, uint64_t B, const uint32_t *which /*B*/, const uint32_t *ring_ids /*B*/,
+                                      const uint8_t *blinder_be32 /*Bx32 or NULL*/, const zk_rng *rng, uint8_t *com_xy72 /*Bx72 out*/,
+                                      uint8_t *blinder_out /*Bx32 or NULL*/, uint8_t *out, uint64_t out_cap, uint64_t *out_off /*B+1*/,
+                                      int32_t *per_proof_status /*B*/);
+zk_status zk_member_prove_batch_rings_device(zk_ctx *ctx, uint64_t B, const void *d_which, const void *d_ring_ids, const void *d_blinder_be32,
+                                             const zk_rng *rng /* rng->data in HBM */, void *d_com_xy72, void *d_blinder_out, void *d_out, uint64_t out_cap,
+                                             void *d_out_off /*u64[B+1]*/, void *d_per_proof_status);
+zk_status zk_member_verify_batch_rings(zk_ctx *ctx, uint64_t B, const uint8_t *com_xy72 /*Bx72*/, const uint8_t *proofs, const uint64_t *proof_off /*B+1*/,
+                                       const uint32_t *ring_ids /*B*/, const uint8_t *verifier_seeds /*Bx32 or NULL*/, uint8_t *ok /*B*/,
+                                       int32_t *per_proof_status /*B*/);
+zk_status zk_member_verify_batch_rings_device(zk_ctx *ctx, uint64_t B, const void *d_com_xy72, const void *d_proofs, const void *d_proof_off /*u64[B+1]*/,
+                                              const void *d_ring_ids, const void *d_verifier_seeds, void *d_ok, void *d_per_proof_status);
 
 /* ---- two (or more) batches in flight on one context.  zk_prove_batch / zk_verify_batch are synchronous: each call pays its own head
  * (no byte of a chunk exists before its stage 1 is over) and its own tail (the copies of the last slices, with nothing left to
@@ -715,7 +749,8 @@ int zk_pool_test_locality(const char *pci_bus_id, int *numa_node, int *cpus, int
  *     identity), 0 = the a = 1 image (any other pair of curve points); ~0 before zk_ctx_set_params.  Bytes and verdicts are the same;
  * 11 = nonzero 32-bit words in the buffers a witness wipe zeroes, with nothing in flight;
  * 12 = passes of the verifier's pipeline run by blocking calls since the context was created: one per call (or per window of a split batch), ceil(count / 20)
- *     in ZK_VERIFY_REPS_ALL. */
+ *     in ZK_VERIFY_REPS_ALL;
+ * 13 = windows that mixed-ring membership calls (zk_member_*_batch_rings) proved or verified since the context was created -- a batch of one ring runs none. */
 uint64_t zk_test_counter(const zk_ctx *ctx, int which);
 /* Only in the test build (lib/libzkattest_hip_testhooks.so, csrc/api_pool.hip under ZK_TEST_HOOKS); the product library exports neither:
  *   void zk_test_pool_fail_next_submit, arguments (zk_pool *pool, int slot):

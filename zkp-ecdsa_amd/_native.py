@@ -29,6 +29,7 @@ SYMBOLS = [
     'zk_screen_batch', 'zk_screen_batch_device', 'zk_screen_batch_rings', 'zk_screen_batch_rings_device',
     'zk_recover_batch', 'zk_recover_batch_device', 'zk_recover_batch_rings', 'zk_recover_batch_rings_device',
     'zk_member_proof_size', 'zk_member_prove_batch', 'zk_member_prove_batch_device', 'zk_member_verify_batch', 'zk_member_verify_batch_device',
+    'zk_member_proof_size_ring', 'zk_member_prove_batch_rings', 'zk_member_prove_batch_rings_device', 'zk_member_verify_batch_rings', 'zk_member_verify_batch_rings_device',
     'zk_test_field_op', 'zk_test_tom_commit', 'zk_test_p256_fixed_mul', 'zk_test_sha256', 'zk_test_rng_draws', 'zk_test_exp_sum',
 ]
 
@@ -142,6 +143,12 @@ def lib():
         L.zk_member_prove_batch_device.argtypes = [vp, u64, vp, vp, C.POINTER(ZkRng), vp, vp, vp, u64, vp]
         L.zk_member_verify_batch.argtypes = [vp, u64, C.c_char_p, C.c_char_p, C.c_char_p, vp, vp]
         L.zk_member_verify_batch_device.argtypes = [vp, u64, vp, vp, vp, vp, vp]
+        L.zk_member_proof_size_ring.argtypes = [vp, C.c_uint32]
+        L.zk_member_proof_size_ring.restype = u64
+        L.zk_member_prove_batch_rings.argtypes = [vp, u64, vp, vp, C.c_char_p, C.POINTER(ZkRng), vp, vp, vp, u64, vp, vp]
+        L.zk_member_prove_batch_rings_device.argtypes = [vp, u64, vp, vp, vp, C.POINTER(ZkRng), vp, vp, vp, u64, vp, vp]
+        L.zk_member_verify_batch_rings.argtypes = [vp, u64, C.c_char_p, C.c_char_p, vp, vp, C.c_char_p, vp, vp]
+        L.zk_member_verify_batch_rings_device.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp, vp]
         L.zk_ring_digest.argtypes = [vp, vp]
         L.zk_hardened_h.argtypes = [C.c_char_p, u64, vp, vp]
         L.zk_pool_create.argtypes = [C.POINTER(C.c_int), i32, C.POINTER(vp)]
@@ -744,8 +751,11 @@ class Engine:
         self._chk(self.L.zk_verify_batch_device(self.h, B, d_msg, d_proofs, d_off, d_vseeds, d_ok, d_status))
 
     # ---- ring membership of a committed value on its own (zk_member_*): proveMembership / verifyMembership on the active ring, "ZKM1" proofs
-    def member_proof_size(self):
-        """bytes of one ZKM1 proof over the active ring: 16 + 288 n + 32 (3 n + 1); 0 without a ring"""
+    def member_proof_size(self, ring=None):
+        """bytes of one ZKM1 proof over the active ring (ring=None; 0 without one) or over the resident ring `ring` (0 for an id that is not resident):
+        16 + 288 n + 32 (3 n + 1)"""
+        if ring is not None:
+            return int(self.L.zk_member_proof_size_ring(self.h, int(ring)))
         return int(self.L.zk_member_proof_size(self.h))
 
     def member_prove_batch(self, which, blinders=None, seeds=None, streams=None, stream_blocks=0, want_blinders=True):
@@ -795,6 +805,76 @@ class Engine:
 
     def member_verify_batch_device(self, B, d_com, d_proofs, d_vseeds, d_ok, d_status):
         self._chk(self.L.zk_member_verify_batch_device(self.h, B, d_com, d_proofs, d_vseeds, d_ok, d_status))
+
+    # ---- ... with one resident ring id per proof (zk_member_*_batch_rings): the active ring plays no part
+    def member_prove_batch_rings(self, which, ring_ids, blinders=None, seeds=None, streams=None, stream_blocks=0, want_blinders=True, cap=None):
+        """member_prove_batch with one resident ring id per proof (which[b] indexes ring ring_ids[b]).  Returns (proofs: list of bytes or None, coms,
+        blinders or None, statuses); the proofs lie back to back in index order: member_last_off holds the B + 1 offsets, member_last_raw the bytes.
+        An id that is not resident gives status 14, no proof and 72 zero bytes of com.  cap: the out_cap handed to the call (default: what the batch takes)."""
+        B = len(which)
+        if len(ring_ids) != B:
+            raise ValueError('one ring id per proof')
+        if seeds is None and streams is None:
+            seeds = os.urandom(32 * B)
+        if streams is None and len(seeds) != 32 * B:
+            raise ValueError('seeds must hold 32 bytes per proof')
+        if blinders is not None and len(blinders) != 32 * B:
+            raise ValueError('blinders must hold 32 bytes per proof')
+        if cap is None:
+            sizes = {r: self.member_proof_size(r) for r in set(ring_ids)}
+            cap = sum(sizes[r] for r in ring_ids)
+        out = C.create_string_buffer(max(cap, 1))
+        com = C.create_string_buffer(max(72 * B, 1))
+        bo = C.create_string_buffer(max(32 * B, 1)) if want_blinders else None
+        st = (C.c_int32 * max(B, 1))()
+        off = (C.c_uint64 * (B + 1))()
+        w = (C.c_uint32 * max(B, 1))(*which)
+        ids = (C.c_uint32 * max(B, 1))(*ring_ids)
+        if streams is None:
+            data = C.create_string_buffer(bytes(seeds), max(32 * B, 1))
+            rng = ZkRng(0, C.cast(data, C.c_void_p), 0)
+        else:
+            data = C.create_string_buffer(bytes(streams), max(32 * B * stream_blocks, 1))
+            rng = ZkRng(1, C.cast(data, C.c_void_p), stream_blocks)
+        self._chk(self.L.zk_member_prove_batch_rings(self.h, B, w, ids, bytes(blinders) if blinders is not None else None, C.byref(rng), com, bo, out, cap, off, st))
+        raw, craw = out.raw, com.raw
+        self.member_last_off = list(off)
+        self.member_last_raw = raw[:off[B]]
+        proofs = [raw[off[b]:off[b + 1]] if st[b] == 0 else None for b in range(B)]
+        return (proofs, [craw[72 * b:72 * (b + 1)] for b in range(B)], [bo.raw[32 * b:32 * (b + 1)] for b in range(B)] if want_blinders else None,
+                list(st)[:B])
+
+    def member_prove_batch_rings_device(self, B, d_which, d_ring_ids, d_blinders, d_rng, d_com, d_blinders_out, d_out, out_cap, d_off, d_status, mode=0, stride_blocks=0):
+        """zk_member_prove_batch_rings_device: every pointer a device address"""
+        rng = ZkRng(mode, d_rng, stride_blocks)
+        self._chk(self.L.zk_member_prove_batch_rings_device(self.h, B, d_which, d_ring_ids, d_blinders, C.byref(rng), d_com, d_blinders_out, d_out, out_cap, d_off, d_status))
+
+    def member_verify_batch_rings(self, coms, proofs, ring_ids, vseeds=None, offsets=None):
+        """verifyMembership for B (com, proof) pairs, proof b under the resident ring ring_ids[b].  proofs: a list of byte strings laid back to back, or
+        (offsets given) the bytes of the whole batch with its B + 1 offsets.  Returns (ok list, status list)."""
+        B = len(coms)
+        if len(ring_ids) != B or any(len(cm) != 72 for cm in coms):
+            raise ValueError('one 72-byte commitment and one ring id per entry')
+        if offsets is None:
+            if len(proofs) != B:
+                raise ValueError('one proof per entry')
+            offsets, run = [0], 0
+            for p in proofs:
+                run += len(p)
+                offsets.append(run)
+            proofs = b''.join(proofs)
+        elif len(offsets) != B + 1:
+            raise ValueError('B + 1 offsets')
+        ok = (C.c_uint8 * max(B, 1))()
+        st = (C.c_int32 * max(B, 1))()
+        off = (C.c_uint64 * (B + 1))(*offsets)
+        ids = (C.c_uint32 * max(B, 1))(*ring_ids)
+        self._chk(self.L.zk_member_verify_batch_rings(self.h, B, b''.join(coms), bytes(proofs), off, ids, bytes(vseeds) if vseeds is not None else None, ok, st))
+        return list(ok)[:B], list(st)[:B]
+
+    def member_verify_batch_rings_device(self, B, d_com, d_proofs, d_off, d_ring_ids, d_vseeds, d_ok, d_status):
+        """zk_member_verify_batch_rings_device: every pointer a device address"""
+        self._chk(self.L.zk_member_verify_batch_rings_device(self.h, B, d_com, d_proofs, d_off, d_ring_ids, d_vseeds, d_ok, d_status))
 
     def synth_params(self, seed):
         a, b, c = C.create_string_buffer(64), C.create_string_buffer(72), C.create_string_buffer(72)

@@ -180,6 +180,8 @@ extern "C" void zk_ctx_destroy(zk_ctx* c) {
     if (c->h_lv) hipHostFree(c->h_lv);
     if (c->h_pr) hipHostFree(c->h_pr);
     if (c->pr_ready) hipEventDestroy(c->pr_ready);
+    if (c->h_mr) hipHostFree(c->h_mr);
+    if (c->mr_ready) hipEventDestroy(c->mr_ready);
     if (c->h_stage) hipHostFree(c->h_stage);
     if (c->in_ready) hipEventDestroy(c->in_ready);
     for (int l = 0; l < ZK_MAX_LANES; l++) {

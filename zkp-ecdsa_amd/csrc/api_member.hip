@@ -1,5 +1,6 @@
 // zk_member_prove_batch / zk_member_verify_batch (include/zkattest.h): proveMembership / verifyMembership (gk.ts:94-262) on the active ring, without a ZKAttest
-// proof around them.  Host-side pipeline; the kernels of its own are in k_member.hip, everything heavy is the GK phase of the full prover and verifier.
+// proof around them, and their _rings forms with one resident ring id per proof.  Host-side pipeline; the kernels of its own are in k_member.hip and
+// k_member_rings.hip, everything heavy is the GK phase of the full prover and verifier.
 #include "ctx.h"
 #include "jobs.h"
 #include "member.h"
@@ -92,8 +93,8 @@ static zk_status ensure_member_lanes(zk_ctx* c, uint32_t C, uint32_t nlanes) {
     }
     return ZK_OK;
 }
-static zk_status member_refusal(zk_ctx* c) {
-    if (!c->params_set || !c->ring->N) return ZK_E_BUFFER;
+static zk_status member_refusal(zk_ctx* c, bool need_ring = true) {   // (the mixed-ring forms read no active ring)
+    if (!c->params_set || (need_ring && !c->ring->N)) return ZK_E_BUFFER;
     if (c->stream_busy) return busy_refusal(c);
     if (c->mode == ZK_MODE_HARDENED) {
         c->err = "membership proofs on their own have no statement to bind: not available in ZK_MODE_HARDENED";
@@ -107,23 +108,19 @@ extern "C" uint64_t zk_member_proof_size(const zk_ctx* c) {
 }
 
 // ------------------------------------------------------------------ prover
-static zk_status member_prove_device(zk_ctx* c, uint64_t B, const uint32_t* d_which, const uint8_t* d_blinder, int rng_mode, const uint8_t* d_rng, uint64_t stride,
-                                     uint8_t* d_com, uint8_t* d_blinder_out, uint8_t* d_out, uint64_t out_cap, int32_t* d_status) {
-    if (zk_status zs = member_refusal(c)) return zs;
-    if (rng_mode != ZK_RNG_SEED && rng_mode != ZK_RNG_STREAM) return ZK_E_ARG;
+// The chunks of B proofs over the bound ring on the lanes: a one-ring call, or (S.sel) one window of a mixed-ring call, whose inputs lie gathered in the window's
+// arrays and whose results go through S to their final places in the batch's buffers; the lanes then start behind `ready`.  C: the chunk size the lanes are
+// carved for.  Every lane is drained before it returns; *e_sync is what draining them gave.  Wipes nothing and leaves the call's timing to its caller.
+static zk_status member_prove_run(zk_ctx* c, uint64_t B, const uint32_t* d_which, const uint8_t* d_blinder, int rng_mode, const uint8_t* d_rng, uint64_t stride,
+                                  uint8_t* d_com, uint8_t* d_blinder_out, uint8_t* d_out, int32_t* d_status, uint32_t C, bool timed, const MemberSel& S, hipEvent_t ready,
+                                  hipError_t* e_sync) {
     const uint32_t size = (uint32_t)zkm1_size(c->ring->n);
-    if (B > out_cap / size) {
-        c->err = "output buffer too small";
-        return ZK_E_BUFFER;
-    }
-    timing_begin(c);
-    if (B == 0) return ZK_OK;
     const DevParams& P = c->P;
-    const uint32_t C = (uint32_t)std::min<uint64_t>(c->chunk, B);
     const std::vector<ChunkPlan> plan = make_chunk_plan(B, C, 1, false);
     const uint32_t NL = (uint32_t)std::min<size_t>(c->lanes, plan.size());
     if (zk_status zs = ensure_member_lanes(c, C, NL)) return zs;
-    const bool timed = zk_timed(c, B);
+    if (ready)
+        for (uint32_t l = 0; l < NL; l++) HIPCHK(c, hipStreamWaitEvent(c->pl[l].stream, ready, 0));
     zk_status zs = ZK_OK;
     auto chunk = [&](uint64_t k) -> zk_status {
         const uint32_t lane = (uint32_t)(k % NL), cnt = plan[k].cnt;
@@ -162,18 +159,33 @@ static zk_status member_prove_device(zk_ctx* c, uint64_t B, const uint32_t* d_wh
         }
         {
             MaybeScope t(timed, c, "respond_write", s);
-            uint8_t* out = d_out + first * size;
-            launch_m_write_head(s, W, cnt, first, size, out, d_com, d_blinder_out, d_status);
+            uint8_t* out = S.sel ? d_out : d_out + first * size;   // (a window's proofs lie where the batch's offsets say: W.out_base)
+            launch_m_write_head(s, W, cnt, first, size, out, d_com, d_blinder_out, d_status, S);
             launch_gk_respond(s, W, in, out);
         }
         return ZK_OK;
     };
     for (uint64_t k = 0; k < plan.size() && !zs; k++) zs = chunk(k);
-    hipError_t e_sync = hipSuccess;
     for (uint32_t l = 0; l < NL; l++) {
         const hipError_t e = hipStreamSynchronize(c->pl[l].stream);
-        if (e_sync == hipSuccess) e_sync = e;
+        if (*e_sync == hipSuccess) *e_sync = e;
     }
+    return zs;
+}
+static zk_status member_prove_device(zk_ctx* c, uint64_t B, const uint32_t* d_which, const uint8_t* d_blinder, int rng_mode, const uint8_t* d_rng, uint64_t stride,
+                                     uint8_t* d_com, uint8_t* d_blinder_out, uint8_t* d_out, uint64_t out_cap, int32_t* d_status) {
+    if (zk_status zs = member_refusal(c)) return zs;
+    if (rng_mode != ZK_RNG_SEED && rng_mode != ZK_RNG_STREAM) return ZK_E_ARG;
+    const uint32_t size = (uint32_t)zkm1_size(c->ring->n);
+    if (B > out_cap / size) {
+        c->err = "output buffer too small";
+        return ZK_E_BUFFER;
+    }
+    timing_begin(c);
+    if (B == 0) return ZK_OK;
+    hipError_t e_sync = hipSuccess;
+    const zk_status zs = member_prove_run(c, B, d_which, d_blinder, rng_mode, d_rng, stride, d_com, d_blinder_out, d_out, d_status, (uint32_t)std::min<uint64_t>(c->chunk, B),
+                                          zk_timed(c, B), MemberSel{}, nullptr, &e_sync);
     if (zs || e_sync != hipSuccess) wipe_witness(c);   // a failed call leaves no nonce, blinder or RNG block behind
     if (zs) return zs;
     HIPCHK(c, e_sync);
@@ -200,10 +212,17 @@ static size_t member_prove_in_layout(MemberProveIn& I, uint8_t* base, size_t B, 
     I.blinder_out = (uint8_t*)k.take(32 * B), I.st = (int32_t*)k.take(4 * B);
     return k.off + ZK_LAYOUT_TAIL;
 }
+// zk_member_prove_batch on the ring the context is bound to: the active one, or the one ring of a zk_member_prove_batch_rings call (RingBind)
+static zk_status member_prove_host(zk_ctx* c, uint64_t B, const uint32_t* which, const uint8_t* blinder, const zk_rng* rng, uint8_t* com, uint8_t* blinder_out, uint8_t* out,
+                                   uint64_t out_cap, int32_t* status);
 extern "C" zk_status zk_member_prove_batch(zk_ctx* c, uint64_t B, const uint32_t* which, const uint8_t* blinder, const zk_rng* rng, uint8_t* com, uint8_t* blinder_out,
                                            uint8_t* out, uint64_t out_cap, int32_t* status) {
     if (!c || !rng || (B && (!which || !rng->data || !com || !out || !status))) return ZK_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
+    return member_prove_host(c, B, which, blinder, rng, com, blinder_out, out, out_cap, status);
+}
+static zk_status member_prove_host(zk_ctx* c, uint64_t B, const uint32_t* which, const uint8_t* blinder, const zk_rng* rng, uint8_t* com, uint8_t* blinder_out, uint8_t* out,
+                                   uint64_t out_cap, int32_t* status) {
     if (zk_status zs = member_refusal(c)) return zs;
     if (rng->mode != ZK_RNG_SEED && rng->mode != ZK_RNG_STREAM) return ZK_E_ARG;
     const uint64_t size = zkm1_size(c->ring->n);
@@ -234,26 +253,17 @@ extern "C" zk_status zk_member_prove_batch(zk_ctx* c, uint64_t B, const uint32_t
 }
 
 // ------------------------------------------------------------------ verifier
-static zk_status member_verify_device(zk_ctx* c, uint64_t B, const uint8_t* d_com, const uint8_t* d_proofs, const uint8_t* d_vseeds, uint8_t* d_ok, int32_t* d_status) {
-    if (zk_status zs = member_refusal(c)) return zs;
-    timing_begin(c);
-    if (B == 0) return ZK_OK;
+// The chunks of B proofs over the bound ring on the lanes, read in place through d_off: a one-ring call (proof first + p starts at d_off[first + p] and ends
+// where the next one starts), or (S.sel) one window of a mixed-ring call -- d_com, d_off and d_vseeds are the window's gathered arrays, every slot is `slot`
+// bytes long, the verdicts go through S to their places in the batch's arrays, and the lanes start behind `ready`.  Every lane is drained before it returns.
+static zk_status member_verify_run(zk_ctx* c, uint64_t B, const uint8_t* d_com, const uint8_t* d_proofs, const uint64_t* d_off, const uint8_t* d_vseeds, uint8_t* d_ok,
+                                   int32_t* d_status, uint32_t C, bool timed, uint32_t slot, const MemberSel& S, hipEvent_t ready) {
     const DevParams& P = c->P;
-    const uint64_t size = zkm1_size(c->ring->n);
-    const uint32_t C = (uint32_t)std::min<uint64_t>(c->chunk, B);
     const std::vector<ChunkPlan> plan = make_chunk_plan(B, C, 1, false);
     const uint32_t NL = (uint32_t)std::min<size_t>(c->lanes, plan.size());
     if (zk_status zs = ensure_member_lanes(c, C, NL)) return zs;
-    if (zk_status zs = reserve(c, B_m_off, 8 * (B + 1))) return zs;
-    uint64_t* const d_off = (uint64_t*)c->buf[B_m_off].p;
-    launch_mv_offsets(c->stream, d_off, B, size);
-    if (!d_vseeds) {   // the verifier's own seeds (api_verify.hip): fresh OS randomness per call
-        if (zk_status zs = reserve(c, B_seed, 32 * B)) return zs;
-        if (zk_status zs = make_default_vseeds(c, B, (uint8_t*)c->buf[B_seed].p, c->stream)) return zs;
-        d_vseeds = (const uint8_t*)c->buf[B_seed].p;
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));   // offsets and seeds are there before any lane reads them
-    const bool timed = zk_timed(c, B);
+    if (ready)
+        for (uint32_t l = 0; l < NL; l++) HIPCHK(c, hipStreamWaitEvent(c->pl[l].stream, ready, 0));
     for (uint64_t k = 0; k < plan.size(); k++) {
         const uint32_t lane = (uint32_t)(k % NL), cnt = plan[k].cnt;
         const uint64_t first = plan[k].first;
@@ -265,7 +275,7 @@ static zk_status member_verify_device(zk_ctx* c, uint64_t B, const uint8_t* d_co
         const uint32_t nq = (V.n + 1) / 2;
         {
             MaybeScope t(timed, c, "v_parse_validate", s);
-            launch_mv_header_validate(s, V, cnt, d_proofs, d_off, first);
+            launch_mv_header_validate(s, V, cnt, d_proofs, d_off, first, slot);
         }
         {
             MaybeScope t(timed, c, "v_gk_total", s);
@@ -279,7 +289,7 @@ static zk_status member_verify_device(zk_ctx* c, uint64_t B, const uint8_t* d_co
             launch_v_straus(s, V.gk_terms, cnt * nq, V.C * nq, 4, 4, V.gk_acc, nullptr, nullptr);
             launch_v_straus(s, V.misc_terms, cnt, 3 * V.C, 1, 0, V.misc_acc, nullptr, nullptr);
             launch_tom_commit(s, P, W.lc, cnt, 1, 4 * W.n);
-            launch_mv_final(s, W, V, cnt, d_ok, d_status, first);
+            launch_mv_final(s, W, V, cnt, d_ok, d_status, first, S);
         }
     }
     hipError_t e_sync = hipSuccess;
@@ -289,6 +299,26 @@ static zk_status member_verify_device(zk_ctx* c, uint64_t B, const uint8_t* d_co
     }
     HIPCHK(c, e_sync);
     HIPCHK(c, hipGetLastError());
+    return ZK_OK;
+}
+static zk_status member_default_vseeds(zk_ctx* c, uint64_t B, const uint8_t** d_vseeds) {   // the verifier's own seeds (api_verify.hip): fresh OS randomness per call
+    if (*d_vseeds) return ZK_OK;
+    if (zk_status zs = reserve(c, B_seed, 32 * B)) return zs;
+    if (zk_status zs = make_default_vseeds(c, B, (uint8_t*)c->buf[B_seed].p, c->stream)) return zs;
+    *d_vseeds = (const uint8_t*)c->buf[B_seed].p;
+    return ZK_OK;
+}
+static zk_status member_verify_device(zk_ctx* c, uint64_t B, const uint8_t* d_com, const uint8_t* d_proofs, const uint8_t* d_vseeds, uint8_t* d_ok, int32_t* d_status) {
+    if (zk_status zs = member_refusal(c)) return zs;
+    timing_begin(c);
+    if (B == 0) return ZK_OK;
+    const uint32_t C = (uint32_t)std::min<uint64_t>(c->chunk, B);
+    if (zk_status zs = reserve(c, B_m_off, 8 * (B + 1))) return zs;
+    uint64_t* const d_off = (uint64_t*)c->buf[B_m_off].p;
+    launch_mv_offsets(c->stream, d_off, B, zkm1_size(c->ring->n));
+    if (zk_status zs = member_default_vseeds(c, B, &d_vseeds)) return zs;
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // offsets and seeds are there before any lane reads them
+    if (zk_status zs = member_verify_run(c, B, d_com, d_proofs, d_off, d_vseeds, d_ok, d_status, C, zk_timed(c, B), 0, MemberSel{}, nullptr)) return zs;
     timing_end(c);
     return ZK_OK;
 }
@@ -306,9 +336,13 @@ static size_t member_verify_in_layout(MemberVerifyIn& I, uint8_t* base, size_t B
     I.com = (uint8_t*)k.take(72 * B), I.seeds = (uint8_t*)k.take(32 * B), I.ok = (uint8_t*)k.take(B), I.st = (int32_t*)k.take(4 * B);
     return k.off + ZK_LAYOUT_TAIL;
 }
+static zk_status member_verify_host(zk_ctx* c, uint64_t B, const uint8_t* com, const uint8_t* proofs, const uint8_t* vseeds, uint8_t* ok, int32_t* status);
 extern "C" zk_status zk_member_verify_batch(zk_ctx* c, uint64_t B, const uint8_t* com, const uint8_t* proofs, const uint8_t* vseeds, uint8_t* ok, int32_t* status) {
     if (!c || (B && (!com || !proofs || !ok || !status))) return ZK_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
+    return member_verify_host(c, B, com, proofs, vseeds, ok, status);
+}
+static zk_status member_verify_host(zk_ctx* c, uint64_t B, const uint8_t* com, const uint8_t* proofs, const uint8_t* vseeds, uint8_t* ok, int32_t* status) {
     if (zk_status zs = member_refusal(c)) return zs;
     if (B == 0) return ZK_OK;
     const uint64_t size = zkm1_size(c->ring->n);
@@ -322,6 +356,331 @@ extern "C" zk_status zk_member_verify_batch(zk_ctx* c, uint64_t B, const uint8_t
     HIPCHK(c, hipMemcpyAsync(d_proofs, proofs, B * size, hipMemcpyHostToDevice, s));
     HIPCHK(c, hipStreamSynchronize(s));
     if (zk_status zs = member_verify_device(c, B, I.com, d_proofs, vseeds ? I.seeds : nullptr, I.ok, I.st)) return zs;
+    HIPCHK(c, hipMemcpyAsync(ok, I.ok, B, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(status, I.st, 4 * B, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    return ZK_OK;
+}
+
+// ------------------------------------------------------------------ one resident ring id per proof (include/zkattest.h: zk_member_*_batch_rings)
+// The classing kernel (k_mr_class) classes every proof by its ring's slot -- the verifier's also by its slot's geometry -- and counts the classes per workgroup
+// of MR_BLOCK proofs; the scan (partition.h) turns the counts into prefix sums over the workgroups, and the host reads the per-class totals and starts back
+// ONCE.  A ZKM1 proof's size follows from its ring's n, so the prover's offsets exist before anything is proved (k_mr_offsets: the workgroup's prefix counts
+// times the classes' sizes, then a scan inside the workgroup) and out_cap is decided there.
+//   One resident ring and nothing else: the one-ring pipeline on the caller's buffers with that ring bound.  No permutation, no gather.
+//   Otherwise, per ring, WINDOWS of at most 2 x chunk x lanes proofs through the stable permutation by class (k_part_perm): one gather collects the window's small
+//   inputs into c->buf[B_mw] (whole stream rows in ZK_RNG_STREAM mode), the window runs with its ring bound (ensure_member_lanes re-binds, and re-carves only
+//   when n or the tables change), and its writers put every proof, com, blinder, status and verdict at its final place through the window's `sel` list: no
+//   staging buffer, no byte written twice.  The verifier reads the proof bytes in place through the window's gathered offsets.
+struct MemberCensus {
+    uint8_t* cls;
+    uint32_t *cnts, *perm;
+};
+static size_t member_census_layout(MemberCensus& X, uint8_t* base, uint64_t B, size_t ncnt) {
+    Carver k(base);
+    X.cls = (uint8_t*)k.take(B), X.cnts = (uint32_t*)k.take(4 * ncnt), X.perm = (uint32_t*)k.take(4 * B);
+    return k.off + ZK_LAYOUT_TAIL;
+}
+struct MemberProveWindow {
+    uint32_t* which;
+    uint8_t *blinder, *rng;
+};
+static size_t member_prove_window_layout(MemberProveWindow& W, uint8_t* base, size_t Wp, size_t rng_row) {
+    Carver k(base);
+    W.which = (uint32_t*)k.take(4 * Wp), W.blinder = (uint8_t*)k.take(32 * Wp), W.rng = (uint8_t*)k.take(rng_row * Wp + 32);
+    return k.off + ZK_LAYOUT_TAIL;
+}
+struct MemberVerifyWindow {
+    uint64_t* off;
+    uint8_t *com, *seeds;
+};
+static size_t member_verify_window_layout(MemberVerifyWindow& W, uint8_t* base, size_t Wp) {
+    Carver k(base);
+    W.off = (uint64_t*)k.take(8 * Wp), W.com = (uint8_t*)k.take(72 * Wp), W.seeds = (uint8_t*)k.take(32 * Wp);
+    return k.off + ZK_LAYOUT_TAIL;
+}
+static void member_rings(zk_ctx* c, MrRings& R, Ring** slot) {   // the resident rings in slot order, with their proofs' sizes
+    RingSlots rs;
+    ring_slots(c, rs, slot);
+    mr_rings_clear(R);
+    for (uint32_t r = 0; r < rs.count; r++) mr_rings_add(R, rs.id[r], slot[r]->n);
+}
+// classes, per-workgroup counts and their scan on the device; c->h_mr[0 .. MR_CLASSES) = proofs per class, [MR_CLASSES ..) = where each class starts in the permutation
+static zk_status member_class(zk_ctx* c, uint64_t B, const uint32_t* d_ids, const MrRings& R, const uint64_t* d_proof_off, uint8_t* d_ok, int32_t* d_status, MemberCensus& X,
+                              bool timed) {
+    const uint64_t nblk = (B + MR_BLOCK - 1) / MR_BLOCK;
+    const size_t ncnt = (size_t)(2 + nblk) * MR_CLASSES;
+    if (zk_status zs = lay_out(c, B_mr, [&](uint8_t* base) { return member_census_layout(X, base, B, ncnt); })) return zs;
+    if (!c->h_mr) HIPCHK(c, hipHostMalloc((void**)&c->h_mr, 4 * 2 * MR_CLASSES, hipHostMallocDefault));
+    if (!c->mr_ready) HIPCHK(c, hipEventCreateWithFlags(&c->mr_ready, hipEventDisableTiming));
+    {
+        MaybeScope t(timed, c, "m_class", c->stream);
+        launch_mr_class(c->stream, B, d_ids, R, d_proof_off, X.cls, X.cnts + 2 * MR_CLASSES, X.cnts, d_ok, d_status);
+    }
+    HIPCHK(c, hipMemcpyAsync(c->h_mr, X.cnts, 4 * 2 * MR_CLASSES, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ZK_OK;
+}
+static zk_status member_prove_rings_device(zk_ctx* c, uint64_t B, const uint32_t* d_which, const uint32_t* d_ids, const uint8_t* d_blinder, int rng_mode, const uint8_t* d_rng,
+                                           uint64_t stride, uint8_t* d_com, uint8_t* d_blinder_out, uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_off, int32_t* d_status) {
+    if (zk_status zs = member_refusal(c, false)) return zs;
+    if (rng_mode != ZK_RNG_SEED && rng_mode != ZK_RNG_STREAM) return ZK_E_ARG;
+    if (B > 0xffffffffull) return ZK_E_ARG;
+    hipStream_t s = c->stream;
+    timing_begin(c);
+    if (B == 0) {
+        HIPCHK(c, hipMemsetAsync(d_out_off, 0, 8, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        return ZK_OK;
+    }
+    MrRings R;
+    Ring* slot[ZK_MAX_RINGS] = {};
+    member_rings(c, R, slot);
+    const bool timed = zk_timed(c, B);
+    MemberCensus X;
+    if (zk_status zs = member_class(c, B, d_ids, R, nullptr, nullptr, nullptr, X, timed)) return zs;
+    const uint32_t *cnt = c->h_mr, *start = c->h_mr + MR_CLASSES;
+    if (!mr_fits(mr_bytes(cnt, R), out_cap)) {   // before a byte of any output is written
+        c->err = "output buffer too small";
+        return ZK_E_BUFFER;
+    }
+    {
+        MaybeScope t(timed, c, "m_class", s);
+        launch_mr_offsets(s, B, X.cls, X.cnts + 2 * MR_CLASSES, R, d_out_off, d_com, d_blinder_out, d_status);
+    }
+    zk_status zs = ZK_OK;
+    hipError_t he = hipSuccess;
+    const uint32_t one = mr_single_class(cnt, R);
+    if (one < MR_CLASSES) {   // the common case: one ring -- the caller's buffers as they are
+        RingBind rb(c, slot[one]);
+        he = hipStreamSynchronize(s);
+        if (he == hipSuccess)
+            zs = member_prove_run(c, B, d_which, d_blinder, rng_mode, d_rng, stride, d_com, d_blinder_out, d_out, d_status, (uint32_t)std::min<uint64_t>(c->chunk, B), timed,
+                                  MemberSel{}, nullptr, &he);
+    } else {
+        launch_mr_perm(s, B, X.cls, X.cnts + 2 * MR_CLASSES, X.cnts, X.perm);
+        const uint32_t Wp = mr_window_cap(c->chunk, c->lanes, cnt, R), C = std::min<uint32_t>(c->chunk, Wp);
+        const size_t rng_row = rng_mode == ZK_RNG_SEED ? 32 : 32 * (size_t)stride;
+        MemberProveWindow W;
+        zs = lay_out(c, B_mw, [&](uint8_t* base) { return member_prove_window_layout(W, base, Wp, rng_row); });
+        for (uint32_t r = 0; r < R.count && !zs && he == hipSuccess; r++) {
+            RingBind rb(c, slot[r]);
+            for (uint32_t w = 0; w < mr_window_count(cnt[r], Wp) && !zs && he == hipSuccess; w++) {
+                uint32_t first, n;
+                mr_window(cnt[r], Wp, w, &first, &n);
+                const uint32_t* sel = X.perm + start[r] + first;
+                c->dbg_mr_windows++;
+                {
+                    MaybeScope t(timed, c, "m_gather", s);
+                    launch_mr_pgather(s, n, B, sel, d_which, d_blinder, rng_mode == ZK_RNG_SEED ? d_rng : nullptr, W.which, W.blinder, W.rng);
+                    if (rng_mode == ZK_RNG_STREAM) launch_pr_gather_rows(s, n, sel, d_rng, rng_row, W.rng);
+                }
+                if ((he = hipEventRecord(c->mr_ready, s)) != hipSuccess) break;
+                zs = member_prove_run(c, n, W.which, d_blinder ? W.blinder : nullptr, rng_mode, W.rng, stride, d_com, d_blinder_out, d_out, d_status, C, timed,
+                                      MemberSel{sel, d_out_off, B}, c->mr_ready, &he);
+            }
+        }
+    }
+    {   // nothing of this call may still be running (or writing into the caller's buffers) when it returns
+        const hipError_t e = hipStreamSynchronize(s);
+        if (he == hipSuccess) he = e;
+    }
+    if (zs || he != hipSuccess) wipe_witness(c);   // a failed call leaves no gathered blinder, seed or stream row, no nonce and no RNG block behind
+    if (zs) return zs;
+    HIPCHK(c, he);
+    HIPCHK(c, hipGetLastError());
+    timing_end(c);
+    return ZK_OK;
+}
+static Ring* member_resident(zk_ctx* c, uint32_t id) {
+    for (auto& R : c->rings)
+        if (R.live && R.id == id && R.N) return &R;
+    return nullptr;
+}
+extern "C" uint64_t zk_member_proof_size_ring(const zk_ctx* c, uint32_t ring) {
+    if (!c) return 0;
+    const Ring* R = member_resident(const_cast<zk_ctx*>(c), ring);
+    return R ? zkm1_size(R->n) : 0;
+}
+extern "C" zk_status zk_member_prove_batch_rings_device(zk_ctx* c, uint64_t B, const void* d_which, const void* d_ids, const void* d_blinder, const zk_rng* rng, void* d_com,
+                                                        void* d_blinder_out, void* d_out, uint64_t out_cap, void* d_out_off, void* d_status) {
+    if (!c || !rng || !d_out_off || (B && (!d_which || !d_ids || !rng->data || !d_com || !d_out || !d_status))) return ZK_E_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    return member_prove_rings_device(c, B, (const uint32_t*)d_which, (const uint32_t*)d_ids, (const uint8_t*)d_blinder, rng->mode, rng->data, rng->stride_blocks, (uint8_t*)d_com,
+                                     (uint8_t*)d_blinder_out, (uint8_t*)d_out, out_cap, (uint64_t*)d_out_off, (int32_t*)d_status);
+}
+// Host pointers: the ids are classed here, and with them the offsets and the out_cap decision.  All of one resident ring: zk_member_prove_batch with that ring
+// bound.  Anything else: the inputs cross to HBM and take the device path; the proofs lie in order in the context's staging copy of `out` and cross the link in
+// one copy.
+struct MemberProveRingsIn {
+    uint32_t *which, *ids;
+    uint8_t *blinder, *rng, *com, *blinder_out;
+    int32_t* st;
+    uint64_t* off;
+};
+static size_t member_prove_rings_in_layout(MemberProveRingsIn& I, uint8_t* base, size_t B, size_t rng_bytes) {
+    Carver k(base);
+    I.which = (uint32_t*)k.take(4 * B), I.ids = (uint32_t*)k.take(4 * B), I.blinder = (uint8_t*)k.take(32 * B), I.rng = (uint8_t*)k.take(rng_bytes ? rng_bytes : 32);
+    I.com = (uint8_t*)k.take(72 * B), I.blinder_out = (uint8_t*)k.take(32 * B), I.st = (int32_t*)k.take(4 * B), I.off = (uint64_t*)k.take(8 * (B + 1));
+    return k.off + ZK_LAYOUT_TAIL;
+}
+extern "C" zk_status zk_member_prove_batch_rings(zk_ctx* c, uint64_t B, const uint32_t* which, const uint32_t* ring_ids, const uint8_t* blinder, const zk_rng* rng, uint8_t* com,
+                                                 uint8_t* blinder_out, uint8_t* out, uint64_t out_cap, uint64_t* out_off, int32_t* status) {
+    if (!c || !rng || !out_off || (B && (!which || !ring_ids || !rng->data || !com || !out || !status))) return ZK_E_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (zk_status zs = member_refusal(c, false)) return zs;
+    if (rng->mode != ZK_RNG_SEED && rng->mode != ZK_RNG_STREAM) return ZK_E_ARG;
+    if (B > 0xffffffffull) return ZK_E_ARG;
+    if (B == 0) {
+        out_off[0] = 0;
+        return ZK_OK;
+    }
+    MrRings R;
+    Ring* slot[ZK_MAX_RINGS] = {};
+    member_rings(c, R, slot);
+    uint32_t cnt[MR_CLASSES];
+    std::vector<uint64_t> off(B + 1);
+    mr_plan_host(R, B, ring_ids, nullptr, cnt, off.data());
+    const uint64_t total = off[B];
+    if (!mr_fits(total, out_cap)) {   // before a byte of any output is written
+        c->err = "output buffer too small";
+        return ZK_E_BUFFER;
+    }
+    const uint32_t one = mr_single_class(cnt, R);
+    if (one < MR_CLASSES) {
+        RingBind rb(c, slot[one]);
+        if (zk_status zs = member_prove_host(c, B, which, blinder, rng, com, blinder_out, out, total, status)) return zs;
+        memcpy(out_off, off.data(), 8 * (B + 1));
+        return ZK_OK;
+    }
+    const size_t rng_bytes = rng->mode == ZK_RNG_SEED ? 32 * B : 32 * B * rng->stride_blocks;
+    MemberProveRingsIn I;
+    if (zk_status zs = lay_out(c, B_in, [&](uint8_t* base) { return member_prove_rings_in_layout(I, base, B, rng_bytes); })) return zs;
+    if (zk_status zs = reserve(c, B_io, total ? total : 32)) return zs;
+    uint8_t* const d_out = (uint8_t*)c->buf[B_io].p;
+    // from the first upload on, blinders and seeds lie in the input buffer: every failure below zeroes them (member_prove_rings_device does so itself)
+    const struct { void* d; const void* h; size_t n; } up[] = {{I.which, which, 4 * B}, {I.ids, ring_ids, 4 * B}, {I.blinder, blinder, blinder ? 32 * B : 0}, {I.rng, rng->data, rng_bytes}};
+    for (auto& u : up)
+        if (u.n && hipMemcpy(u.d, u.h, u.n, hipMemcpyHostToDevice) != hipSuccess) {
+            c->err = "upload of the inputs failed";
+            (void)hipGetLastError();
+            wipe_witness(c);
+            return ZK_E_DEVICE;
+        }
+    if (zk_status zs = member_prove_rings_device(c, B, I.which, I.ids, blinder ? I.blinder : nullptr, rng->mode, I.rng, rng->stride_blocks, I.com, blinder_out ? I.blinder_out : nullptr,
+                                                 d_out, total, I.off, I.st))
+        return zs;
+    hipError_t e = total ? hipMemcpy(out, d_out, total, hipMemcpyDeviceToHost) : hipSuccess;
+    if (e == hipSuccess) e = hipMemcpy(com, I.com, 72 * B, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && blinder_out) e = hipMemcpy(blinder_out, I.blinder_out, 32 * B, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(status, I.st, 4 * B, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(out_off, I.off, 8 * (B + 1), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) wipe_witness(c);
+    HIPCHK(c, e);
+    return ZK_OK;
+}
+
+static zk_status member_verify_rings_device(zk_ctx* c, uint64_t B, const uint8_t* d_com, const uint8_t* d_proofs, const uint64_t* d_proof_off, const uint32_t* d_ids,
+                                            const uint8_t* d_vseeds, uint8_t* d_ok, int32_t* d_status) {
+    if (zk_status zs = member_refusal(c, false)) return zs;
+    if (B > 0xffffffffull || ((uintptr_t)d_proofs & 3)) return ZK_E_ARG;
+    timing_begin(c);
+    if (B == 0) return ZK_OK;
+    hipStream_t s = c->stream;
+    MrRings R;
+    Ring* slot[ZK_MAX_RINGS] = {};
+    member_rings(c, R, slot);
+    const bool timed = zk_timed(c, B);
+    if (zk_status zs = member_default_vseeds(c, B, &d_vseeds)) return zs;
+    MemberCensus X;
+    if (zk_status zs = member_class(c, B, d_ids, R, d_proof_off, d_ok, d_status, X, timed)) return zs;   // (the seeds are there too when it returns)
+    const uint32_t *cnt = c->h_mr, *start = c->h_mr + MR_CLASSES;
+    const uint32_t one = mr_single_class(cnt, R);
+    if (one < MR_CLASSES) {   // one ring, every slot as long as its proofs: the caller's buffers and offsets as they are
+        RingBind rb(c, slot[one]);
+        if (zk_status zs = member_verify_run(c, B, d_com, d_proofs, d_proof_off, d_vseeds, d_ok, d_status, (uint32_t)std::min<uint64_t>(c->chunk, B), timed, 0, MemberSel{}, nullptr))
+            return zs;
+    } else {
+        launch_mr_perm(s, B, X.cls, X.cnts + 2 * MR_CLASSES, X.cnts, X.perm);
+        const uint32_t Wp = mr_window_cap(c->chunk, c->lanes, cnt, R), C = std::min<uint32_t>(c->chunk, Wp);
+        MemberVerifyWindow W;
+        if (zk_status zs = lay_out(c, B_mw, [&](uint8_t* base) { return member_verify_window_layout(W, base, Wp); })) return zs;
+        for (uint32_t r = 0; r < R.count; r++) {
+            RingBind rb(c, slot[r]);
+            for (uint32_t w = 0; w < mr_window_count(cnt[r], Wp); w++) {
+                uint32_t first, n;
+                mr_window(cnt[r], Wp, w, &first, &n);
+                const uint32_t* sel = X.perm + start[r] + first;
+                c->dbg_mr_windows++;
+                {
+                    MaybeScope t(timed, c, "m_gather", s);
+                    launch_mr_vgather(s, n, B, sel, d_proof_off, d_com, d_vseeds, W.off, W.com, W.seeds);
+                }
+                HIPCHK(c, hipEventRecord(c->mr_ready, s));
+                if (zk_status zs = member_verify_run(c, n, W.com, d_proofs, W.off, W.seeds, d_ok, d_status, C, timed, R.size[r], MemberSel{sel, nullptr, B}, c->mr_ready)) return zs;
+            }
+        }
+    }
+    HIPCHK(c, hipStreamSynchronize(s));
+    HIPCHK(c, hipGetLastError());
+    timing_end(c);
+    return ZK_OK;
+}
+extern "C" zk_status zk_member_verify_batch_rings_device(zk_ctx* c, uint64_t B, const void* d_com, const void* d_proofs, const void* d_proof_off, const void* d_ids,
+                                                         const void* d_vseeds, void* d_ok, void* d_status) {
+    if (!c || (B && (!d_com || !d_proofs || !d_proof_off || !d_ids || !d_ok || !d_status))) return ZK_E_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    return member_verify_rings_device(c, B, (const uint8_t*)d_com, (const uint8_t*)d_proofs, (const uint64_t*)d_proof_off, (const uint32_t*)d_ids, (const uint8_t*)d_vseeds,
+                                      (uint8_t*)d_ok, (int32_t*)d_status);
+}
+// Host pointers: classed here as the classing kernel does.  One resident ring and every slot in order: zk_member_verify_batch on the bytes from the first slot
+// on, with that ring bound.  Anything else: everything crosses to HBM and takes the device path (which classes again; bytes behind proof_off[B] do not cross).
+struct MemberVerifyRingsIn {
+    uint8_t *com, *seeds, *ok;
+    uint32_t* ids;
+    uint64_t* off;
+    int32_t* st;
+};
+static size_t member_verify_rings_in_layout(MemberVerifyRingsIn& I, uint8_t* base, size_t B) {
+    Carver k(base);
+    I.com = (uint8_t*)k.take(72 * B), I.seeds = (uint8_t*)k.take(32 * B), I.ok = (uint8_t*)k.take(B), I.ids = (uint32_t*)k.take(4 * B), I.off = (uint64_t*)k.take(8 * (B + 1));
+    I.st = (int32_t*)k.take(4 * B);
+    return k.off + ZK_LAYOUT_TAIL;
+}
+extern "C" zk_status zk_member_verify_batch_rings(zk_ctx* c, uint64_t B, const uint8_t* com, const uint8_t* proofs, const uint64_t* proof_off, const uint32_t* ring_ids,
+                                                  const uint8_t* vseeds, uint8_t* ok, int32_t* status) {
+    if (!c || (B && (!com || !proofs || !proof_off || !ring_ids || !ok || !status))) return ZK_E_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (zk_status zs = member_refusal(c, false)) return zs;
+    if (B > 0xffffffffull) return ZK_E_ARG;
+    if (B == 0) return ZK_OK;
+    MrRings R;
+    Ring* slot[ZK_MAX_RINGS] = {};
+    member_rings(c, R, slot);
+    uint32_t cnt[MR_CLASSES] = {};
+    for (uint64_t b = 0; b < B; b++) {
+        uint32_t k = mr_class_of_id(R, ring_ids[b]);
+        if (k < MR_SLOTS && !mr_slot_ok(proof_off[b], proof_off[b + 1], proof_off[B], R.size[k])) k = MR_BAD;
+        cnt[k]++;
+    }
+    const uint32_t one = mr_single_class(cnt, R);
+    if (one < MR_CLASSES) {
+        RingBind rb(c, slot[one]);
+        return member_verify_host(c, B, com, proofs + proof_off[0], vseeds, ok, status);
+    }
+    const uint64_t bytes = proof_off[B];
+    MemberVerifyRingsIn I;
+    if (zk_status zs = lay_out(c, B_in, [&](uint8_t* base) { return member_verify_rings_in_layout(I, base, B); })) return zs;
+    if (zk_status zs = reserve(c, B_io, bytes ? bytes : 32)) return zs;
+    uint8_t* const d_proofs = (uint8_t*)c->buf[B_io].p;
+    hipStream_t s = c->stream;
+    HIPCHK(c, hipMemcpyAsync(I.com, com, 72 * B, hipMemcpyHostToDevice, s));
+    if (vseeds) HIPCHK(c, hipMemcpyAsync(I.seeds, vseeds, 32 * B, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(I.ids, ring_ids, 4 * B, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(I.off, proof_off, 8 * (B + 1), hipMemcpyHostToDevice, s));
+    if (bytes) HIPCHK(c, hipMemcpyAsync(d_proofs, proofs, bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (zk_status zs = member_verify_rings_device(c, B, I.com, d_proofs, I.off, I.ids, vseeds ? I.seeds : nullptr, I.ok, I.st)) return zs;
     HIPCHK(c, hipMemcpyAsync(ok, I.ok, B, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipMemcpyAsync(status, I.st, 4 * B, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));

@@ -590,6 +590,7 @@ extern "C" uint64_t zk_test_counter(const zk_ctx* c, int which) {
         return n;
     }
     if (which == 12) return c->dbg_v_passes;     // passes of the verifier's pipeline run by blocking calls (ceil(sec / VK) per call or window in ZK_VERIFY_REPS_ALL)
+    if (which == 13) return c->dbg_mr_windows;   // windows of mixed-ring membership calls (0 for a batch of one ring: the one-ring pipeline on the caller's buffers)
     if (which == 10) return c->params_set ? c->P.tom_model : ~0ull;   // form of the comb tables of g and h (curve.h): 1 = the a = -1 model (both bases of odd order), 0 = the a = 1 image
     return which == 0 ? c->dbg_recheck_proofs : which == 2 ? c->dbg_msm_terms : which == 3 ? c->dbg_p256_batched : 0;
 }

@@ -46,7 +46,9 @@ enum GrowPolicy {
     X(unp, GROW_EXACT, false)     /* ZKA1P input of the synchronous verify calls: staging of the expanded proofs */                                               \
     X(unp_off, GROW_EXACT, false) /* ... and their per-chunk offsets */                                                                                           \
     X(m_off, GROW_SLACK, false)   /* membership proofs on their own: offsets of a verify call's equally long proofs */                                            \
-    X(vp, GROW_SLACK, false)      /* exhaustive verify mode: verdicts and statuses of a pass behind the first (5 B bytes), until they are merged */
+    X(vp, GROW_SLACK, false)      /* exhaustive verify mode: verdicts and statuses of a pass behind the first (5 B bytes), until they are merged */           \
+    X(mr, GROW_EXACT, false)      /* mixed-ring membership calls (api_member.hip): classes, per-workgroup counters, permutation */                                \
+    X(mw, GROW_SHED, true)        /* ... the window one ring's inputs are gathered into: indices, blinders, seeds or RNG streams; coms, offsets, verifier seeds */
 enum BufId {
 #define X(name, policy, witness) B_##name,
     ZK_CTX_BUFS(X)
@@ -97,6 +99,8 @@ struct zk_ctx {
     uint32_t* h_pr = nullptr;      // mixed-ring prove calls (api.hip: prove_rings_device): page-locked read-back of the counters
     size_t h_pr_bytes = 0;
     hipEvent_t pr_ready = nullptr; // "the window is gathered": the lanes' stage 1 waits for it
+    uint32_t* h_mr = nullptr;      // mixed-ring membership calls (api_member.hip): page-locked read-back of the per-class counters
+    hipEvent_t mr_ready = nullptr; // ... "the window is gathered": the lanes wait for it
     uint32_t pr_seg_force = 0;     // test build only (zk_test_set_prove_segment): proofs per segment instead of what ZK_PR_STAGE_BYTES holds; 0 = off
     uint32_t mode = 0;                 // zk_ctx_set_mode: ZK_MODE_REFERENCE / ZK_MODE_HARDENED
     uint32_t verify_level = 0;         // zk_ctx_set_verify_level: ZK_VERIFY_LEVEL_CONTEXT / ZK_VERIFY_LEVEL_PER_PROOF
@@ -193,6 +197,7 @@ struct zk_ctx {
     uint64_t dbg_etab_blocks = 0;      // 256-key blocks whose table E was built (k_gk.hip) since the context was created
     uint64_t dbg_pr_segments = 0;      // segments that mixed-ring prove calls staged since the context was created (a one-ring call stages none)
     uint64_t dbg_pr_windows = 0;       // ... and the windows they proved
+    uint64_t dbg_mr_windows = 0;       // windows that mixed-ring membership calls proved or verified since the context was created (a one-ring call runs none)
     uint64_t dbg_v_passes = 0;         // passes of the verifier's pipeline since the context was created: one per blocking call or window, ceil(sec / VK) in ZK_VERIFY_REPS_ALL
     // timing
     std::vector<TimerRec> trecs;

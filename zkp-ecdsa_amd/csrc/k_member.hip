@@ -42,27 +42,40 @@ void launch_m_front(hipStream_t s, const Workspace& W, uint32_t count, const uin
 }
 // Everything of a proof's slot that k_gk_respond / k_write_gk_points do not write: the 16 header bytes (or zeros over the whole slot where the status is
 // not 0), the commitment, the blinder, the status.  One workgroup per proof.  W.out_base[p] = p * size is written here too, before the GKProof's writers run.
+// A window of a mixed-ring call (S.sel): entry first + p of the window is proof S.sel[first + p] of the batch -- its slot starts at that proof's place in the
+// batch's offsets (out = the batch's buffer), com, blinder and status go to that index: every byte is written once, at its final place.  An entry that is
+// not an index of the batch writes nothing, and its status keeps the GKProof's writers from writing too.
 __global__ void __launch_bounds__(64) k_m_write_head(Workspace W, uint32_t count, uint64_t first, uint32_t size, uint8_t* out, uint8_t* com, uint8_t* blinder_out,
-                                                     int32_t* status) {
+                                                     int32_t* status, MemberSel S) {
     const uint32_t p = blockIdx.x, t = threadIdx.x;
     const int32_t st = W.st[p];
-    uint32_t* slot = (uint32_t*)(out + (uint64_t)p * size);
+    uint64_t idx = first + p, base = (uint64_t)p * size;
+    if (S.sel) {
+        idx = S.sel[first + p];
+        if (idx >= S.B) {
+            if (t == 0) W.st[p] = ZK_E_ARG, W.out_base[p] = 0;
+            return;
+        }
+        base = S.off[idx];
+    }
+    uint32_t* slot = (uint32_t*)(out + base);
     if (st != ZK_OK) {
         for (uint32_t i = t; i < size / 4; i += 64) slot[i] = 0;
     } else if (t < 4) {
         slot[t] = t == 0 ? ZK_MAGIC_ZKM1 : t == 1 ? bswap32(size) : t == 2 ? bswap32(W.n) : 0;
     }
     if (t == 0) {
-        W.out_base[p] = (uint64_t)p * size;
-        status[first + p] = st;
+        W.out_base[p] = base;
+        status[idx] = st;
         const uint32_t e = 4 * W.n * count + p;
-        store_tomcoord_be(com + 72 * (first + p), soa_ld<ModT, 1>(W.lc.ax, e));
-        store_tomcoord_be(com + 72 * (first + p) + 36, soa_ld<ModT, 1>(W.lc.ay, e));
-        if (blinder_out) store_scalar_be(blinder_out + 32 * (first + p), soa_ld<ModQ, 1>(W.gk_blind, p));
+        store_tomcoord_be(com + 72 * idx, soa_ld<ModT, 1>(W.lc.ax, e));
+        store_tomcoord_be(com + 72 * idx + 36, soa_ld<ModT, 1>(W.lc.ay, e));
+        if (blinder_out) store_scalar_be(blinder_out + 32 * idx, soa_ld<ModQ, 1>(W.gk_blind, p));
     }
 }
-void launch_m_write_head(hipStream_t s, const Workspace& W, uint32_t count, uint64_t first, uint32_t size, uint8_t* out, uint8_t* com, uint8_t* blinder_out, int32_t* status) {
-    hipLaunchKernelGGL(k_m_write_head, dim3(count), dim3(64), 0, s, W, count, first, size, out, com, blinder_out, status);
+void launch_m_write_head(hipStream_t s, const Workspace& W, uint32_t count, uint64_t first, uint32_t size, uint8_t* out, uint8_t* com, uint8_t* blinder_out, int32_t* status,
+                         const MemberSel& S) {
+    hipLaunchKernelGGL(k_m_write_head, dim3(count), dim3(64), 0, s, W, count, first, size, out, com, blinder_out, status, S);
 }
 
 // ------------------------------------------------------------------ verifier
@@ -75,10 +88,11 @@ ZK_DEV bool m_tom_bytes_valid(const uint8_t* p) {  // edwards.ts:204-209 afterJs
 }
 // The ZKM1 header (one thread per proof): proofs are `size` bytes apart.  Fills the fields the GK kernels of k_verify.hip read: st, okflags (bit 3: the header's n
 // is not the ring's -- verifyMembership returns false, gk.ts:208-218 --, the header's n above it), zcnt = 0.  total_len must be the length n announces.
-__global__ void __launch_bounds__(256) k_mv_header(VWork V, uint32_t count, const uint8_t* proofs, const uint64_t* off, uint64_t first) {
+// (slot != 0: a window of a mixed-ring call -- off holds the gathered starts of slots that the classing kernel found `slot` bytes long)
+__global__ void __launch_bounds__(256) k_mv_header(VWork V, uint32_t count, const uint8_t* proofs, const uint64_t* off, uint64_t first, uint32_t slot) {
     const uint32_t p = gtid();
     if (p >= count) return;
-    const uint64_t o0 = off[first + p], o1 = off[first + p + 1];
+    const uint64_t o0 = off[first + p], o1 = slot ? o0 + slot : off[first + p + 1];
     const uint32_t* h = (const uint32_t*)(proofs + o0);
     const uint32_t total = bswap32(h[1]), n = bswap32(h[2]);
     int32_t st = ZK_OK;
@@ -90,7 +104,7 @@ __global__ void __launch_bounds__(256) k_mv_header(VWork V, uint32_t count, cons
 }
 // One thread per point that exists: com, then the 4 n commitments of the announced structure (a proof whose n is not the ring's has its 4 n' points walked by
 // the thread of com, as k_v_validate does; the call's slots have the active ring's size, so of a longer proof only what lies inside its slot).
-__global__ void __launch_bounds__(256) k_mv_validate(VWork V, uint32_t count, const uint8_t* proofs, const uint64_t* off, uint64_t first) {
+__global__ void __launch_bounds__(256) k_mv_validate(VWork V, uint32_t count, const uint8_t* proofs, const uint64_t* off, uint64_t first, uint32_t slot) {
     const uint32_t per = 1 + 4 * V.n, t = gtid();
     if (t >= count * per) return;
     const uint32_t p = t / per, u = t % per;
@@ -101,17 +115,17 @@ __global__ void __launch_bounds__(256) k_mv_validate(VWork V, uint32_t count, co
     if (u == 0) {
         ok = m_tom_bytes_valid(V.com + 72 * (first + p));
         if (other) {   // no byte outside the proof's slot is read: of a longer structure, the points that lie inside it
-            const uint64_t room = (off[first + p + 1] - off[first + p] - ZKM1_HDR) / 72;
+            const uint64_t room = ((slot ? slot : off[first + p + 1] - off[first + p]) - ZKM1_HDR) / 72;
             const uint32_t np = 4 * (V.okflags[p] >> 16);
             for (uint32_t k = 0; k < (np < room ? np : (uint32_t)room); k++) ok = ok && m_tom_bytes_valid(gk + 72 * k);
         }
     } else if (!other) ok = m_tom_bytes_valid(gk + 72 * (u - 1));
     if (!ok) atomicCAS(&V.st[p], ZK_OK, ZK_E_BAD_ENCODING);
 }
-void launch_mv_header_validate(hipStream_t s, const VWork& V, uint32_t count, const uint8_t* proofs, const uint64_t* off, uint64_t first) {
-    hipLaunchKernelGGL(k_mv_header, dim3((count + 255) / 256), dim3(256), 0, s, V, count, proofs, off, first);
+void launch_mv_header_validate(hipStream_t s, const VWork& V, uint32_t count, const uint8_t* proofs, const uint64_t* off, uint64_t first, uint32_t slot) {
+    hipLaunchKernelGGL(k_mv_header, dim3((count + 255) / 256), dim3(256), 0, s, V, count, proofs, off, first, slot);
     const uint32_t n = count * (1 + 4 * V.n);
-    hipLaunchKernelGGL(k_mv_validate, dim3((n + 255) / 256), dim3(256), 0, s, V, count, proofs, off, first);
+    hipLaunchKernelGGL(k_mv_validate, dim3((n + 255) / 256), dim3(256), 0, s, V, count, proofs, off, first, slot);
 }
 // offsets of a batch of equally long proofs (the GK kernels take an offset array)
 __global__ void __launch_bounds__(256) k_mv_offsets(uint64_t* off, uint64_t B, uint64_t size) {
@@ -128,9 +142,13 @@ ZK_DEV TomPt m_ld_tom4(const Soa4& a, uint32_t e) {
     r.x = soa_ld<ModT, 2>(a.x, e), r.y = soa_ld<ModT, 2>(a.y, e), r.z = soa_ld<ModT, 2>(a.z, e), r.t = soa_ld<ModT, 2>(a.t, e);
     return r;
 }
-__global__ void __launch_bounds__(64, 2) k_mv_final(Workspace W, VWork V, uint32_t count, uint8_t* ok_out, int32_t* status_out, uint64_t first) {
+// (S.sel: a window of a mixed-ring call -- the verdict of entry first + p goes to index S.sel[first + p] of the batch, k_lv_scatter's pattern; an entry that is
+// no index of the batch writes nothing)
+__global__ void __launch_bounds__(64, 2) k_mv_final(Workspace W, VWork V, uint32_t count, uint8_t* ok_out, int32_t* status_out, uint64_t first, MemberSel S) {
     const uint32_t p = gtid();
     if (p >= count) return;
+    const uint64_t idx = S.sel ? S.sel[first + p] : first + p;
+    if (S.sel && idx >= S.B) return;
     const int32_t st = V.st[p];
     uint8_t ok = 0;
     if (st == ZK_OK && !(V.okflags[p] & 8)) {
@@ -144,9 +162,9 @@ __global__ void __launch_bounds__(64, 2) k_mv_final(Workspace W, VWork V, uint32
         m = tom_add(m, m_ld_tom4(V.misc_acc, p));
         ok = fe_is_zero(m.x) && fe_eq(m.y, m.z) && !fe_is_zero(m.z);   // edwards.ts:117-125 on the a = 1 image
     }
-    ok_out[first + p] = ok;
-    status_out[first + p] = st;
+    ok_out[idx] = ok;
+    status_out[idx] = st;
 }
-void launch_mv_final(hipStream_t s, const Workspace& W, const VWork& V, uint32_t count, uint8_t* ok, int32_t* status, uint64_t first) {
-    hipLaunchKernelGGL(k_mv_final, dim3((count + 63) / 64), dim3(64), 0, s, W, V, count, ok, status, first);
+void launch_mv_final(hipStream_t s, const Workspace& W, const VWork& V, uint32_t count, uint8_t* ok, int32_t* status, uint64_t first, const MemberSel& S) {
+    hipLaunchKernelGGL(k_mv_final, dim3((count + 63) / 64), dim3(64), 0, s, W, V, count, ok, status, first, S);
 }

@@ -1,8 +1,29 @@
-// Ring membership on its own (k_member.hip, api_member.hip): the launch wrappers (the ZKM1 layout is in wire.h) of the kernels around the shared GK machinery.
+// Ring membership on its own (k_member.hip, api_member.hip): the launch wrappers (the ZKM1 layout is in wire.h) of the kernels around the shared GK machinery,
+// and of the classing, offsets and gather kernels of the mixed-ring forms (k_member_rings.hip; the plan's arithmetic is member_plan.h's).
 #pragma once
 #include "engine.h"
+#include "member_plan.h"
+// Where a window of a mixed-ring call puts its results: window entry j is proof sel[j] of a batch of B, whose slot starts at off[sel[j]] (prover).
+// sel == nullptr: a one-ring call -- entry j is proof first + j, slots are `size` bytes apart.
+struct MemberSel {
+    const uint32_t* sel = nullptr;
+    const uint64_t* off = nullptr;
+    uint64_t B = 0;
+};
 void launch_m_front(hipStream_t s, const Workspace& W, uint32_t count, const uint32_t* which, const uint8_t* blinder, uint64_t first, uint32_t* which_s);
-void launch_m_write_head(hipStream_t s, const Workspace& W, uint32_t count, uint64_t first, uint32_t size, uint8_t* out, uint8_t* com, uint8_t* blinder_out, int32_t* status);
-void launch_mv_header_validate(hipStream_t s, const VWork& V, uint32_t count, const uint8_t* proofs, const uint64_t* off, uint64_t first);
+void launch_m_write_head(hipStream_t s, const Workspace& W, uint32_t count, uint64_t first, uint32_t size, uint8_t* out, uint8_t* com, uint8_t* blinder_out, int32_t* status,
+                         const MemberSel& S = MemberSel{});
+// slot != 0: every slot is `slot` bytes long (a window's gathered offsets have no successor to measure against)
+void launch_mv_header_validate(hipStream_t s, const VWork& V, uint32_t count, const uint8_t* proofs, const uint64_t* off, uint64_t first, uint32_t slot = 0);
 void launch_mv_offsets(hipStream_t s, uint64_t* off, uint64_t B, uint64_t size);
-void launch_mv_final(hipStream_t s, const Workspace& W, const VWork& V, uint32_t count, uint8_t* ok, int32_t* status, uint64_t first);
+void launch_mv_final(hipStream_t s, const Workspace& W, const VWork& V, uint32_t count, uint8_t* ok, int32_t* status, uint64_t first, const MemberSel& S = MemberSel{});
+// k_member_rings.hip
+void launch_mr_class(hipStream_t s, uint64_t B, const uint32_t* ring_ids, const MrRings& R, const uint64_t* proof_off, uint8_t* cls, uint32_t* blk_cnt, uint32_t* out,
+                     uint8_t* ok, int32_t* status);
+void launch_mr_perm(hipStream_t s, uint64_t B, const uint8_t* cls, const uint32_t* blk_base, const uint32_t* out, uint32_t* perm);
+void launch_mr_offsets(hipStream_t s, uint64_t B, const uint8_t* cls, const uint32_t* blk_base, const MrRings& R, uint64_t* out_off, uint8_t* com, uint8_t* blinder_out,
+                       int32_t* status);
+void launch_mr_pgather(hipStream_t s, uint32_t n, uint64_t B, const uint32_t* sel, const uint32_t* which, const uint8_t* blinder, const uint8_t* seeds, uint32_t* w_which,
+                       uint8_t* w_blinder, uint8_t* w_seeds);
+void launch_mr_vgather(hipStream_t s, uint32_t n, uint64_t B, const uint32_t* sel, const uint64_t* proof_off, const uint8_t* com, const uint8_t* seeds, uint64_t* w_off,
+                       uint8_t* w_com, uint8_t* w_seeds);
