@@ -62,25 +62,38 @@ export interface RecoveredKey { publicKey: Buffer | null; which: number; flags: 
 export const RECOVER: { readonly SIG_RANGE: 2; readonly NOT_IN_RING: 8; readonly RING_NOT_RESIDENT: 16; readonly NO_POINT: 32 }
 export function recoverSignatureLists(params: SystemParametersList, statements: RecoverStatement[]): Promise<RecoveredKey[]>
 export function recoverKey(msgHash: Uint8Array, sigBytes: Uint8Array, keys: bigint[] | Buffer, params?: SystemParametersList): Promise<RecoveredKey>
-/** ring membership of a committed value on its own (src/proofGK/gk.ts:94-262): ZKM1 proofs over the engine's resident rings */
+/** ring membership of a committed value on its own (src/proofGK/gk.ts:94-262): ZKM1 proofs (ZKMB with a context: MemberOptions) over the engine's resident rings */
 export class Commitment { p: Point; r: Scalar; constructor(p: Point, r: Scalar) }
 export class GKProof {
     readonly bytes: Buffer; readonly n: number
+    /** true for a "ZKMB" proof: made with a context, verifies only with it */
+    readonly bound: boolean
     readonly cl: Point[]; readonly ca: Point[]; readonly cb: Point[]; readonly cd: Point[]
     readonly f: Scalar[]; readonly za: Scalar[]; readonly zb: Scalar[]; readonly zd: Scalar
     constructor(bytes: Buffer); eq(o: GKProof): boolean
 }
 /** pedersen.ts:53-58: value * g + r * h with a fresh blinder r */
 export function commit(params: PedersenParams, value: bigint): Commitment
+/** bound proofs ("ZKMB", include/zkattest.h: zk_member_*_bound): `context` -- 32 caller bytes per proof (a session nonce, a message hash, a verifier's id) -- is hashed
+ *  into the challenge with the ring's digest and the commitment; the verifier must be given the same context.  One Uint8Array(32) for the single calls, an array of
+ *  them (one per entry) for the batched and Lists calls.  No counterpart in the reference beyond the TODO at src/proofGK/gk.ts:178. */
+export interface MemberOptions { context?: Uint8Array }
+export interface MemberBatchOptions { context?: Uint8Array[] }
 /** com.r is the blinder; throws unless com.p commits to keys[index] under it */
 export function proveMembership(params: PedersenParams | SystemParametersList, com: Commitment, index: number, keys: bigint[] | Buffer): Promise<GKProof>
+export function proveMembership(params: PedersenParams | SystemParametersList, com: Commitment, index: number, keys: bigint[] | Buffer, options: MemberOptions): Promise<GKProof>
 export function verifyMembership(params: PedersenParams | SystemParametersList, com: Point, keys: bigint[] | Buffer, proof: GKProof): Promise<boolean>
+export function verifyMembership(params: PedersenParams | SystemParametersList, com: Point, keys: bigint[] | Buffer, proof: GKProof, options: MemberOptions): Promise<boolean>
 /** batched over one key list */
 export function proveMemberships(params: PedersenParams | SystemParametersList, coms: Commitment[], indices: number[], keys: bigint[] | Buffer): Promise<GKProof[]>
+export function proveMemberships(params: PedersenParams | SystemParametersList, coms: Commitment[], indices: number[], keys: bigint[] | Buffer, options: MemberBatchOptions): Promise<GKProof[]>
 export function verifyMemberships(params: PedersenParams | SystemParametersList, coms: Point[], keys: bigint[] | Buffer, proofs: GKProof[]): Promise<boolean[]>
+export function verifyMemberships(params: PedersenParams | SystemParametersList, coms: Point[], keys: bigint[] | Buffer, proofs: GKProof[], options: MemberBatchOptions): Promise<boolean[]>
 /** batched with one key list per entry: keysList[i] is the ring of commitment i (resolved to the engine's resident rings like proveSignatureLists' key lists) */
 export function proveMembershipLists(params: PedersenParams | SystemParametersList, coms: Commitment[], indices: number[], keysList: (bigint[] | Buffer)[]): Promise<GKProof[]>
+export function proveMembershipLists(params: PedersenParams | SystemParametersList, coms: Commitment[], indices: number[], keysList: (bigint[] | Buffer)[], options: MemberBatchOptions): Promise<GKProof[]>
 export function verifyMembershipLists(params: PedersenParams | SystemParametersList, coms: Point[], keysList: (bigint[] | Buffer)[], proofs: GKProof[]): Promise<boolean[]>
+export function verifyMembershipLists(params: PedersenParams | SystemParametersList, coms: Point[], keysList: (bigint[] | Buffer)[], proofs: GKProof[], options: MemberBatchOptions): Promise<boolean[]>
 type Newable<T> = new (...args: any[]) => T
 export function writeJson<T>(type: Newable<T>, object: T): string
 export function readJson<T>(type: Newable<T>, text: string): T

@@ -396,30 +396,32 @@ class Engine {
     }
     // ring membership on its own (zk_member_*), on the ACTIVE ring: -> { proofs: Buffer[] | null per entry, coms: Buffer[] (72 B), blinders: Buffer[] (32 B), status: Int32Array }
     memberProofSize() { return native.memberProofSize(this.h) }
-    memberProveBatch(which, blinders, seeds) {
-        const B = which.length, size = this.memberProofSize()
-        const r = native.memberProveBatch(this.h, Buffer.from(Uint32Array.from(which).buffer), blinders || null, seeds || crypto.randomBytes(32 * B))   // one fresh seed per proof
+    // context (B x 32 bytes, or null): the bound forms, "ZKMB" (zk_member_*_bound)
+    memberProveBatch(which, blinders, seeds, context) {
+        const B = which.length, size = this.memberProofSize(), w = Buffer.from(Uint32Array.from(which).buffer), sd = seeds || crypto.randomBytes(32 * B)   // one fresh seed per proof
+        const r = context ? native.memberProveBatchBound(this.h, w, blinders || null, sd, context) : native.memberProveBatch(this.h, w, blinders || null, sd)
         const st = i32(r.status), cut = (b, w) => Array.from({ length: B }, (_, i) => b.slice(w * i, w * i + w))
         return { proofs: cut(r.proofs, size).map((p, i) => (st[i] === 0 ? p : null)), coms: cut(r.coms, 72), blinders: cut(r.blinders, 32), status: st }
     }
-    memberVerifyBatch(coms, proofs) {   // -> { ok: boolean[], status: Int32Array }
-        const r = native.memberVerifyBatch(this.h, Buffer.concat(coms), Buffer.concat(proofs))
+    memberVerifyBatch(coms, proofs, context) {   // -> { ok: boolean[], status: Int32Array }
+        const r = context ? native.memberVerifyBatchBound(this.h, Buffer.concat(coms), Buffer.concat(proofs), context) : native.memberVerifyBatch(this.h, Buffer.concat(coms), Buffer.concat(proofs))
         return { ok: Array.from(r.ok, (v) => v === 1), status: i32(r.status) }
     }
     // ... with one resident ring id per entry (zk_member_*_batch_rings): the active ring plays no part; an id that is not resident gives status 14 and no proof
     memberProofSizeRing(ringId) { return native.memberProofSizeRing(this.h, ringId) }
-    memberProveBatchRings(which, ringIds, blinders, seeds) {
-        const B = which.length, u32 = (a) => Buffer.from(Uint32Array.from(a).buffer)
-        const r = native.memberProveBatchRings(this.h, u32(which), u32(ringIds), blinders || null, seeds || crypto.randomBytes(32 * B))   // one fresh seed per proof
+    memberProveBatchRings(which, ringIds, blinders, seeds, context) {
+        const B = which.length, u32 = (a) => Buffer.from(Uint32Array.from(a).buffer), sd = seeds || crypto.randomBytes(32 * B)   // one fresh seed per proof
+        const r = context ? native.memberProveBatchRingsBound(this.h, u32(which), u32(ringIds), blinders || null, sd, context) : native.memberProveBatchRings(this.h, u32(which), u32(ringIds), blinders || null, sd)
         const st = i32(r.status), cut = (b, w) => Array.from({ length: B }, (_, i) => b.slice(w * i, w * i + w))
         const off = Array.from({ length: B + 1 }, (_, i) => Number(r.off.readBigUInt64LE(8 * i)))
         return { proofs: st.length ? Array.from(st, (s, i) => (s === 0 ? r.proofs.slice(off[i], off[i + 1]) : null)) : [], coms: cut(r.coms, 72), blinders: cut(r.blinders, 32), status: st, off, raw: r.proofs }
     }
-    memberVerifyBatchRings(coms, proofs, ringIds) {   // proofs: one Buffer per entry, laid back to back -> { ok: boolean[], status: Int32Array }
+    memberVerifyBatchRings(coms, proofs, ringIds, context) {   // proofs: one Buffer per entry, laid back to back -> { ok: boolean[], status: Int32Array }
         const off = Buffer.alloc(8 * (proofs.length + 1))
         let run = 0
         proofs.forEach((p, i) => { run += p.length; off.writeBigUInt64LE(BigInt(run), 8 * (i + 1)) })
-        const r = native.memberVerifyBatchRings(this.h, Buffer.concat(coms), Buffer.concat(proofs), off, Buffer.from(Uint32Array.from(ringIds).buffer))
+        const ids = Buffer.from(Uint32Array.from(ringIds).buffer)
+        const r = context ? native.memberVerifyBatchRingsBound(this.h, Buffer.concat(coms), Buffer.concat(proofs), off, ids, context) : native.memberVerifyBatchRings(this.h, Buffer.concat(coms), Buffer.concat(proofs), off, ids)
         return { ok: Array.from(r.ok, (v) => v === 1), status: i32(r.status) }
     }
     proveBatchRingsAsync(msg, sig, pk, which, ringIds, seeds) { return this._chain(() => this._proveRingsNow(msg, sig, pk, which, ringIds, seeds)) }
@@ -816,14 +818,15 @@ async function findKey(publicKey, keys, params = lastParams) {
 class Commitment { // src/commit/pedersen.ts:21-36: the point and its blinder
     constructor(p, r) { this.p = p; this.r = r }
 }
-// A GKProof keeps the engine's ZKM1 bytes (include/zkattest.h) and materialises the reference's members (cl, ca, cb, cd: Points; f, za, zb: Scalars; zd) on demand.
+// A GKProof keeps the engine's ZKM1 bytes (include/zkattest.h; "ZKMB" for a proof made with a context: `bound`) and materialises the reference's members (cl, ca, cb, cd: Points; f, za, zb: Scalars; zd) on demand.
 class GKProof { // src/proofGK/gk.ts:31-73
     constructor(bytes) {
-        if (!(Buffer.isBuffer(bytes) && bytes.length >= 16 && bytes.slice(0, 4).toString('latin1') === 'ZKM1' && bytes.readUInt32BE(4) === bytes.length &&
+        if (!(Buffer.isBuffer(bytes) && bytes.length >= 16 && ['ZKM1', 'ZKMB'].includes(bytes.slice(0, 4).toString('latin1')) && bytes.readUInt32BE(4) === bytes.length &&
             bytes.length === 16 + 384 * bytes.readUInt32BE(8) + 32)) throw new Error('error deserializing GKProof')
         this.bytes = bytes
     }
     get n() { return this.bytes.readUInt32BE(8) }
+    get bound() { return this.bytes[3] === 0x42 }   // "ZKMB": verifies only with the context, the commitment and the ring it was made with
     _pts(k) { const n = this.n; return Array.from({ length: n }, (_, i) => { const o = 16 + 72 * (k * n + i); return new Point(tomEdwards256, fromBE(this.bytes.slice(o, o + 36)), fromBE(this.bytes.slice(o + 36, o + 72))) }) }
     _scs(k) { const n = this.n; return Array.from({ length: n }, (_, i) => { const o = 16 + 288 * n + 32 * (k * n + i); return new Scalar(tomEdwards256, fromBE(this.bytes.slice(o, o + 32))) }) }
     get cl() { return this._pts(0) }
@@ -854,17 +857,37 @@ function paramsOf(pedersenParams) {
     return sp
 }
 const tomBytes = (pt) => Buffer.concat([toBE(pt.x, 36), toBE(pt.y, 36)])
+// Bound proofs ("ZKMB", include/zkattest.h: zk_member_*_bound): every call below takes one more argument than the reference's list, `options`, and
+// options.context binds the proof -- 32 bytes of the caller's (a session nonce, a message hash, a verifier's id) that the challenge hashes together with the
+// ring's digest and the commitment.  The single calls take one Uint8Array(32), the batched and Lists calls an array of them, one per entry.  The same context
+// must be given to the verifier; a proof made without one does not deserialise there, and a bound proof does not deserialise in a call without one.
+// The declared parameter lists stay the reference's (Function.length and the call shape are what callers of gk.ts know): the fifth argument is read here.
+function memberContexts(args, at, B, name) {
+    const options = args[at]
+    if (options === undefined || options === null || options.context === undefined || options.context === null) return null
+    const list = B === null ? [options.context] : options.context
+    if (!Array.isArray(list) || list.length !== (B === null ? 1 : B)) throw new RangeError(name + ': options.context holds one Uint8Array(32) per entry')
+    list.forEach((c) => { if (!(c instanceof Uint8Array) || c.length !== 32) throw new TypeError(name + ': a context is a Uint8Array(32)') })
+    return list.map((c) => Buffer.from(c.buffer, c.byteOffset, 32))
+}
 // proveMembership(params, com, index, keys) (gk.ts:94-195): com.r is the blinder; the engine's commitment to keys[index] under it must be com.p
-async function proveMembership(pedersenParams, com, index, keys) { return (await proveMemberships(pedersenParams, [com], [index], keys))[0] }
+async function proveMembership(pedersenParams, com, index, keys) {   // (+ options: { context: Uint8Array(32) })
+    const ctx = memberContexts(arguments, 4, null, 'proveMembership')
+    return (await proveMemberships(pedersenParams, [com], [index], keys, ctx ? { context: ctx } : undefined))[0]
+}
 // verifyMembership(params, comPoint, keys, proof) (gk.ts:197-262) -> boolean; what does not deserialise throws
-async function verifyMembership(pedersenParams, comPoint, keys, proof) { return (await verifyMemberships(pedersenParams, [comPoint], keys, [proof]))[0] }
+async function verifyMembership(pedersenParams, comPoint, keys, proof) {   // (+ options: { context: Uint8Array(32) })
+    const ctx = memberContexts(arguments, 4, null, 'verifyMembership')
+    return (await verifyMemberships(pedersenParams, [comPoint], keys, [proof], ctx ? { context: ctx } : undefined))[0]
+}
 // batched: one ring, B commitments and indices -> GKProof[]
 async function proveMemberships(pedersenParams, coms, indices, keys) {
     if (coms.length !== indices.length) throw new RangeError('proveMemberships: one index per commitment')
+    const ctx = memberContexts(arguments, 4, coms.length, 'proveMemberships')   // (+ options: { context: Uint8Array(32)[] })
     checkRingSize(Buffer.isBuffer(keys) ? keys.length / 32 : keys.length, true)
     if (!coms.length) return []
     const { withRing } = engineFor(paramsOf(pedersenParams), keys)
-    const r = await withRing((engine) => engine.memberProveBatch(indices, Buffer.concat(coms.map((c) => toBE(c.r.k, 32)))))
+    const r = await withRing((engine) => engine.memberProveBatch(indices, Buffer.concat(coms.map((c) => toBE(c.r.k, 32))), null, ctx && Buffer.concat(ctx)))
     return r.proofs.map((p, i) => {
         if (r.status[i] !== 0) throw statusError(r.status[i])
         if (!r.coms[i].equals(tomBytes(coms[i].p))) throw new Error('proveMembership: com does not commit to keys[index] with blinder com.r')
@@ -873,6 +896,7 @@ async function proveMemberships(pedersenParams, coms, indices, keys) {
 }
 async function verifyMemberships(pedersenParams, comPoints, keys, proofs) {
     if (comPoints.length !== proofs.length) throw new RangeError('verifyMemberships: one proof per commitment')
+    const ctx = memberContexts(arguments, 4, proofs.length, 'verifyMemberships')   // (+ options: { context: Uint8Array(32)[] })
     checkRingSize(Buffer.isBuffer(keys) ? keys.length / 32 : keys.length, false)
     if (!proofs.length) return []
     const { withRing } = engineFor(paramsOf(pedersenParams), keys)
@@ -880,7 +904,7 @@ async function verifyMemberships(pedersenParams, comPoints, keys, proofs) {
         const size = engine.memberProofSize()
         // a GKProof of another ring's length: the reference's length check returns false (gk.ts:208-218); the engine sees fixed-size slots
         const fit = proofs.map((p) => { const b = p.bytes; return b.length === size ? b : b.length > size ? b.slice(0, size) : Buffer.concat([b, Buffer.alloc(size - b.length)]) })
-        const r = engine.memberVerifyBatch(comPoints.map(tomBytes), fit)
+        const r = engine.memberVerifyBatch(comPoints.map(tomBytes), fit, ctx && Buffer.concat(ctx))
         r.status.forEach((st) => { if (st !== 0) throw statusError(st) })
         return r.ok
     })
@@ -902,6 +926,7 @@ function memberRingsOf(keysList, prove) {
 async function proveMembershipLists(pedersenParams, coms, indices, keysList) {
     const B = coms.length
     if (indices.length !== B || keysList.length !== B) throw new RangeError('proveMembershipLists: one index and one key list per commitment')
+    const ctx = memberContexts(arguments, 4, B, 'proveMembershipLists')   // (+ options: { context: Uint8Array(32)[] }: entry i's proof hashes ITS ring's digest and context[i])
     const { rings, ringOfEntry } = memberRingsOf(keysList, true)
     if (!B) return []
     const { withRings, capacity } = engineFor(paramsOf(pedersenParams), keysList[0])
@@ -910,7 +935,8 @@ async function proveMembershipLists(pedersenParams, coms, indices, keysList) {
         const sel = []
         for (let i = 0; i < B; i++) if (ringOfEntry[i] >= g && ringOfEntry[i] < g + per) sel.push(i)
         const r = await withRings(rings.slice(g, g + per), (engine, ids) =>
-            engine.memberProveBatchRings(sel.map((i) => indices[i]), sel.map((i) => ids[ringOfEntry[i] - g]), Buffer.concat(sel.map((i) => toBE(coms[i].r.k, 32)))))
+            engine.memberProveBatchRings(sel.map((i) => indices[i]), sel.map((i) => ids[ringOfEntry[i] - g]), Buffer.concat(sel.map((i) => toBE(coms[i].r.k, 32))), null,
+                ctx && Buffer.concat(sel.map((i) => ctx[i]))))
         sel.forEach((i, k) => {
             if (r.status[k] !== 0) throw statusError(r.status[k])
             if (!r.coms[k].equals(tomBytes(coms[i].p))) throw new Error('proveMembership: com does not commit to keys[index] with blinder com.r')
@@ -922,6 +948,7 @@ async function proveMembershipLists(pedersenParams, coms, indices, keysList) {
 async function verifyMembershipLists(pedersenParams, comPoints, keysList, proofs) {
     const B = proofs.length
     if (comPoints.length !== B || keysList.length !== B) throw new RangeError('verifyMembershipLists: one commitment and one key list per proof')
+    const ctx = memberContexts(arguments, 4, B, 'verifyMembershipLists')   // (+ options: { context: Uint8Array(32)[] })
     const { rings, ringOfEntry } = memberRingsOf(keysList, false)
     if (!B) return []
     const { withRings, capacity } = engineFor(paramsOf(pedersenParams), keysList[0])
@@ -933,7 +960,7 @@ async function verifyMembershipLists(pedersenParams, comPoints, keysList, proofs
             const rid = sel.map((i) => ids[ringOfEntry[i] - g])
             // a GKProof of another ring's length: the reference's length check returns false (gk.ts:208-218); the engine sees slots of the ring's size
             const fit = sel.map((i, k) => { const b = proofs[i].bytes, size = engine.memberProofSizeRing(rid[k]); return b.length === size ? b : b.length > size ? b.slice(0, size) : Buffer.concat([b, Buffer.alloc(size - b.length)]) })
-            return engine.memberVerifyBatchRings(sel.map((i) => tomBytes(comPoints[i])), fit, rid)
+            return engine.memberVerifyBatchRings(sel.map((i) => tomBytes(comPoints[i])), fit, rid, ctx && Buffer.concat(sel.map((i) => ctx[i])))
         })
         sel.forEach((i, k) => {
             if (r.status[k] !== 0) throw statusError(r.status[k])

@@ -1078,12 +1078,26 @@ static napi_value MemberProofSize(napi_env env, napi_callback_info info) {
     napi_create_double(env, (double)zk_member_proof_size(zk_pool_ctx(h->pool, 0)), &v);
     return v;
 }
-/* (h, which: B u32 LE, blinders: B x 32 or null, seeds: B x 32) -> {proofs: B x size (zeros where status != 0), coms: B x 72, blinders: B x 32, status: B i32 LE} */
-static napi_value MemberProveBatch(napi_env env, napi_callback_info info) {
-    napi_value argv[4];
-    if (!get_args(env, info, 4, argv)) return NULL;
+/* The bound forms ("ZKMB", zk_member_*_bound) take one more argument behind the unbound call's: context, B x 32 bytes.  A missing or misfitting context is a
+ * RangeError here; the C ABI never sees a NULL context from this addon. */
+static int get_context(napi_env env, napi_value v, size_t B, uint8_t **ctx, const char *what) {
+    static uint8_t none[32];   /* B = 0: an empty Buffer may have no address; the call reads no byte of it */
+    size_t lc;
+    if (!get_bytes(env, v, ctx, &lc)) return 0;
+    if (lc != 32 * B || (B && !*ctx)) {
+        napi_throw_range_error(env, NULL, what);
+        return 0;
+    }
+    if (!*ctx) *ctx = none;
+    return 1;
+}
+/* (h, which: B u32 LE, blinders: B x 32 or null, seeds: B x 32[, context: B x 32]) -> {proofs: B x size (zeros where status != 0), coms: B x 72, blinders: B x 32,
+ * status: B i32 LE} */
+static napi_value member_prove(napi_env env, napi_callback_info info, int bound) {
+    napi_value argv[5];
+    if (!get_args(env, info, bound ? 5 : 4, argv)) return NULL;
     Handle *h = get_handle(env, argv[0], 0);
-    uint8_t *wb, *bl, *seeds;
+    uint8_t *wb, *bl, *seeds, *ctx = NULL;
     size_t lw, lb, ls;
     if (!h || !get_bytes(env, argv[1], &wb, &lw) || !get_bytes(env, argv[2], &bl, &lb) || !get_bytes(env, argv[3], &seeds, &ls)) return NULL;
     const size_t B = lw / 4;
@@ -1091,6 +1105,7 @@ static napi_value MemberProveBatch(napi_env env, napi_callback_info info) {
         napi_throw_range_error(env, NULL, "memberProveBatch: one u32 index and 32 seed bytes per proof (and 32 blinder bytes each, or null)");
         return NULL;
     }
+    if (bound && !get_context(env, argv[4], B, &ctx, "memberProveBatchBound: 32 context bytes per proof")) return NULL;
     zk_ctx *c = zk_pool_ctx(h->pool, 0);
     const uint64_t size = zk_member_proof_size(c);
     uint8_t *buf = (uint8_t *)xmalloc(env, (size + 72 + 32 + 8) * B + 8);   /* (a Buffer's bytes need not be 4-byte aligned: the indices are copied) */
@@ -1100,7 +1115,8 @@ static napi_value MemberProveBatch(napi_env env, napi_callback_info info) {
     uint8_t *out = buf + 8 * B, *com = out + size * B, *bo = com + 72 * B;
     if (B) memcpy(which, wb, 4 * B);
     zk_rng rng = {ZK_RNG_SEED, seeds, 0};
-    zk_status st = zk_member_prove_batch(c, B, which, bl, &rng, com, bo, out, size * B, status);
+    zk_status st = bound ? zk_member_prove_batch_bound(c, B, which, ctx, bl, &rng, com, bo, out, size * B, status)
+                         : zk_member_prove_batch(c, B, which, bl, &rng, com, bo, out, size * B, status);
     napi_value v = NULL;
     if (st != ZK_OK) throw_text(env, st, zk_last_error(c));
     else if (napi_create_object(env, &v) == napi_ok) {
@@ -1111,12 +1127,14 @@ static napi_value MemberProveBatch(napi_env env, napi_callback_info info) {
     free(buf);
     return v;
 }
-/* (h, coms: B x 72, proofs: B x size) -> {ok: B bytes, status: B i32 LE} */
-static napi_value MemberVerifyBatch(napi_env env, napi_callback_info info) {
-    napi_value argv[3];
-    if (!get_args(env, info, 3, argv)) return NULL;
+static napi_value MemberProveBatch(napi_env env, napi_callback_info info) { return member_prove(env, info, 0); }
+static napi_value MemberProveBatchBound(napi_env env, napi_callback_info info) { return member_prove(env, info, 1); }
+/* (h, coms: B x 72, proofs: B x size[, context: B x 32]) -> {ok: B bytes, status: B i32 LE} */
+static napi_value member_verify(napi_env env, napi_callback_info info, int bound) {
+    napi_value argv[4];
+    if (!get_args(env, info, bound ? 4 : 3, argv)) return NULL;
     Handle *h = get_handle(env, argv[0], 0);
-    uint8_t *com, *proofs;
+    uint8_t *com, *proofs, *ctx = NULL;
     size_t lc, lp;
     if (!h || !get_bytes(env, argv[1], &com, &lc) || !get_bytes(env, argv[2], &proofs, &lp)) return NULL;
     zk_ctx *c = zk_pool_ctx(h->pool, 0);
@@ -1126,17 +1144,20 @@ static napi_value MemberVerifyBatch(napi_env env, napi_callback_info info) {
         napi_throw_range_error(env, NULL, "memberVerifyBatch: one 72-byte commitment and one proof of the active ring's size per entry");
         return NULL;
     }
+    if (bound && !get_context(env, argv[3], B, &ctx, "memberVerifyBatchBound: 32 context bytes per proof")) return NULL;
     uint8_t *buf = (uint8_t *)xmalloc(env, 5 * B + 8);
     if (!buf) return NULL;
     int32_t *status = (int32_t *)buf;
     uint8_t *ok = buf + 4 * B;
-    zk_status st = zk_member_verify_batch(c, B, com, proofs, NULL, ok, status);
+    zk_status st = bound ? zk_member_verify_batch_bound(c, B, com, ctx, proofs, NULL, ok, status) : zk_member_verify_batch(c, B, com, proofs, NULL, ok, status);
     napi_value v = NULL;
     if (st != ZK_OK) throw_text(env, st, zk_last_error(c));
     else if (napi_create_object(env, &v) == napi_ok) set_prop(env, v, "ok", new_buffer(env, ok, B)), set_prop(env, v, "status", new_buffer(env, status, 4 * B));
     free(buf);
     return v;
 }
+static napi_value MemberVerifyBatch(napi_env env, napi_callback_info info) { return member_verify(env, info, 0); }
+static napi_value MemberVerifyBatchBound(napi_env env, napi_callback_info info) { return member_verify(env, info, 1); }
 
 /* ... with one resident ring id per entry (zk_member_*_batch_rings); the active ring plays no part.
  * (h, ring id) -> bytes of one ZKM1 proof over that resident ring, 0 for an id that is not resident */
@@ -1149,13 +1170,13 @@ static napi_value MemberProofSizeRing(napi_env env, napi_callback_info info) {
     napi_create_double(env, (double)zk_member_proof_size_ring(zk_pool_ctx(h->pool, 0), id), &v);
     return v;
 }
-/* (h, which: B u32 LE, ring ids: B u32 LE, blinders: B x 32 or null, seeds: B x 32) -> {proofs: the batch's bytes back to back, off: B+1 u64 LE, coms: B x 72,
- * blinders: B x 32, status: B i32 LE} */
-static napi_value MemberProveBatchRings(napi_env env, napi_callback_info info) {
-    napi_value argv[5];
-    if (!get_args(env, info, 5, argv)) return NULL;
+/* (h, which: B u32 LE, ring ids: B u32 LE, blinders: B x 32 or null, seeds: B x 32[, context: B x 32]) -> {proofs: the batch's bytes back to back, off: B+1 u64 LE,
+ * coms: B x 72, blinders: B x 32, status: B i32 LE} */
+static napi_value member_prove_rings(napi_env env, napi_callback_info info, int bound) {
+    napi_value argv[6];
+    if (!get_args(env, info, bound ? 6 : 5, argv)) return NULL;
     Handle *h = get_handle(env, argv[0], 0);
-    uint8_t *wb, *ib, *bl, *seeds;
+    uint8_t *wb, *ib, *bl, *seeds, *ctx = NULL;
     size_t lw, li, lb, ls;
     if (!h || !get_bytes(env, argv[1], &wb, &lw) || !get_bytes(env, argv[2], &ib, &li) || !get_bytes(env, argv[3], &bl, &lb) || !get_bytes(env, argv[4], &seeds, &ls)) return NULL;
     const size_t B = lw / 4;
@@ -1163,6 +1184,7 @@ static napi_value MemberProveBatchRings(napi_env env, napi_callback_info info) {
         napi_throw_range_error(env, NULL, "memberProveBatchRings: one u32 index, one u32 ring id and 32 seed bytes per proof (and 32 blinder bytes each, or null)");
         return NULL;
     }
+    if (bound && !get_context(env, argv[5], B, &ctx, "memberProveBatchRingsBound: 32 context bytes per proof")) return NULL;
     zk_ctx *c = zk_pool_ctx(h->pool, 0);
     uint64_t total = 0;   /* (a Buffer's bytes need not be 4-byte aligned: indices and ids are copied) */
     for (size_t b = 0; b < B; b++) {
@@ -1179,7 +1201,8 @@ static napi_value MemberProveBatchRings(napi_env env, napi_callback_info info) {
     uint8_t *com = (uint8_t *)(status + B), *bo = com + 72 * B, *out = bo + 32 * B;
     if (B) memcpy(which, wb, 4 * B), memcpy(ids, ib, 4 * B);
     zk_rng rng = {ZK_RNG_SEED, seeds, 0};
-    zk_status st = zk_member_prove_batch_rings(c, B, which, ids, bl, &rng, com, bo, out, total, off, status);
+    zk_status st = bound ? zk_member_prove_batch_rings_bound(c, B, which, ctx, ids, bl, &rng, com, bo, out, total, off, status)
+                         : zk_member_prove_batch_rings(c, B, which, ids, bl, &rng, com, bo, out, total, off, status);
     napi_value v = NULL;
     if (st != ZK_OK) throw_text(env, st, zk_last_error(c));
     else if (napi_create_object(env, &v) == napi_ok) {
@@ -1190,12 +1213,14 @@ static napi_value MemberProveBatchRings(napi_env env, napi_callback_info info) {
     free(buf);
     return v;
 }
-/* (h, coms: B x 72, proofs: the batch's bytes, off: B+1 u64 LE, ring ids: B u32 LE) -> {ok: B bytes, status: B i32 LE} */
-static napi_value MemberVerifyBatchRings(napi_env env, napi_callback_info info) {
-    napi_value argv[5];
-    if (!get_args(env, info, 5, argv)) return NULL;
+static napi_value MemberProveBatchRings(napi_env env, napi_callback_info info) { return member_prove_rings(env, info, 0); }
+static napi_value MemberProveBatchRingsBound(napi_env env, napi_callback_info info) { return member_prove_rings(env, info, 1); }
+/* (h, coms: B x 72, proofs: the batch's bytes, off: B+1 u64 LE, ring ids: B u32 LE[, context: B x 32]) -> {ok: B bytes, status: B i32 LE} */
+static napi_value member_verify_rings(napi_env env, napi_callback_info info, int bound) {
+    napi_value argv[6];
+    if (!get_args(env, info, bound ? 6 : 5, argv)) return NULL;
     Handle *h = get_handle(env, argv[0], 0);
-    uint8_t *com, *proofs, *ob, *ib;
+    uint8_t *com, *proofs, *ob, *ib, *ctx = NULL;
     size_t lc, lp, lo, li;
     if (!h || !get_bytes(env, argv[1], &com, &lc) || !get_bytes(env, argv[2], &proofs, &lp) || !get_bytes(env, argv[3], &ob, &lo) || !get_bytes(env, argv[4], &ib, &li)) return NULL;
     const size_t B = lc / 72;
@@ -1205,6 +1230,7 @@ static napi_value MemberVerifyBatchRings(napi_env env, napi_callback_info info) 
         napi_throw_range_error(env, NULL, "memberVerifyBatchRings: one 72-byte commitment and one ring id per entry, B + 1 offsets that end at the proofs' length");
         return NULL;
     }
+    if (bound && !get_context(env, argv[5], B, &ctx, "memberVerifyBatchRingsBound: 32 context bytes per proof")) return NULL;
     uint8_t *buf = (uint8_t *)xmalloc(env, 8 * (B + 1) + 9 * B + lp + 8);
     if (!buf) return NULL;
     uint64_t *off = (uint64_t *)buf;
@@ -1215,13 +1241,16 @@ static napi_value MemberVerifyBatchRings(napi_env env, napi_callback_info info) 
     if (B) memcpy(ids, ib, 4 * B);
     if (lp) memcpy(pr, proofs, lp);
     zk_ctx *c = zk_pool_ctx(h->pool, 0);
-    zk_status st = zk_member_verify_batch_rings(c, B, com, pr, off, ids, NULL, ok, status);
+    zk_status st = bound ? zk_member_verify_batch_rings_bound(c, B, com, ctx, pr, off, ids, NULL, ok, status)
+                         : zk_member_verify_batch_rings(c, B, com, pr, off, ids, NULL, ok, status);
     napi_value v = NULL;
     if (st != ZK_OK) throw_text(env, st, zk_last_error(c));
     else if (napi_create_object(env, &v) == napi_ok) set_prop(env, v, "ok", new_buffer(env, ok, B)), set_prop(env, v, "status", new_buffer(env, status, 4 * B));
     free(buf);
     return v;
 }
+static napi_value MemberVerifyBatchRings(napi_env env, napi_callback_info info) { return member_verify_rings(env, info, 0); }
+static napi_value MemberVerifyBatchRingsBound(napi_env env, napi_callback_info info) { return member_verify_rings(env, info, 1); }
 
 static napi_value Init(napi_env env, napi_value exports) {
     static const struct {
@@ -1240,7 +1269,9 @@ static napi_value Init(napi_env env, napi_value exports) {
                {"screenBatchRings", ScreenBatchRings},
                {"recoverBatchRings", RecoverBatchRings},
                {"memberProofSize", MemberProofSize},   {"memberProveBatch", MemberProveBatch}, {"memberVerifyBatch", MemberVerifyBatch},
-               {"memberProofSizeRing", MemberProofSizeRing}, {"memberProveBatchRings", MemberProveBatchRings}, {"memberVerifyBatchRings", MemberVerifyBatchRings}};
+               {"memberProofSizeRing", MemberProofSizeRing}, {"memberProveBatchRings", MemberProveBatchRings}, {"memberVerifyBatchRings", MemberVerifyBatchRings},
+               {"memberProveBatchBound", MemberProveBatchBound}, {"memberVerifyBatchBound", MemberVerifyBatchBound},
+               {"memberProveBatchRingsBound", MemberProveBatchRingsBound}, {"memberVerifyBatchRingsBound", MemberVerifyBatchRingsBound}};
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;
         if (napi_create_function(env, fns[i].name, NAPI_AUTO_LENGTH, fns[i].fn, NULL, &f) != napi_ok) return NULL;

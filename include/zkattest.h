@@ -30,6 +30,7 @@
  *     GKProof: cl[n], ca[n], cb[n], cd[n] (T), f[n], za[n], zb[n], zd      -- byte for byte the GKProof section of a ZKA1 proof
  *     total_len = 16 + 288 n + 32 (3 n + 1): fixed per ring (6 192 B at n = 16).  Always 36-byte coordinates (zk_ctx_set_wire plays no part).  The commitment
  *     the proof is about is not part of it: it travels beside the proof as one Tom-256 point.
+ *   bound membership proof  "ZKMB": the ZKM1 layout and size under the magic "ZKMB"; its challenge also hashes a statement (zk_member_*_bound below).
  *
  * Randomness contract (replaces crypto.getRandomValues in src/bignum/big.ts:171-181): the k-th 32-byte fill
  * of proof b is SHA-256(seed_b || be64(k)) (ZK_RNG_SEED) or block k of a caller-supplied stream
@@ -505,8 +506,9 @@ zk_status zk_recover_batch_rings_device(zk_ctx *ctx, uint64_t B, const void *d_m
  * build apply, and the bytes depend on none of them.  Blinders, nonces and RNG fills are wiped as the prover's are (zk_ctx_wipe, zk_ctx_destroy, a failed
  * call).  zk_last_timing reports the families "rng_prepass", "gk_fold", "tom_commit", "tom_normalize", "hash", "respond_write" (prover) and
  * "v_parse_validate", "v_gk_total", "v_sums" (verifier).  ZK_E_BUFFER before zk_ctx_set_params or without an active ring; ZK_E_ARG for NULL pointers
- * (other than the optional ones), while streamed jobs are queued, and in ZK_MODE_HARDENED (there is no statement to bind).  B = 0 is ZK_OK.
- * Not provided: submit / wait forms, zk_pool_* forms, JSON, a packed layout. */
+ * (other than the optional ones), while streamed jobs are queued, and in ZK_MODE_HARDENED (an unbound proof hashes no statement; the _bound forms below
+ * name theirs in the call and run in either mode).  B = 0 is ZK_OK.
+ * Not provided: submit / wait forms, zk_pool_* forms, JSON, a packed layout -- of these calls and of their _bound forms. */
 uint64_t zk_member_proof_size(const zk_ctx *ctx);   /* active ring; 0 without one */
 zk_status zk_member_prove_batch(zk_ctx *ctx, uint64_t B, const uint32_t *which /*B*/, const uint8_t *blinder_be32 /*Bx32 or NULL*/, const zk_rng *rng,
                                 uint8_t *com_xy72 /*Bx72 out*/, uint8_t *blinder_out /*Bx32 or NULL*/, uint8_t *out, uint64_t out_cap,
@@ -551,6 +553,48 @@ zk_status zk_member_verify_batch_rings(zk_ctx *ctx, uint64_t B, const uint8_t *c
                                        int32_t *per_proof_status /*B*/);
 zk_status zk_member_verify_batch_rings_device(zk_ctx *ctx, uint64_t B, const void *d_com_xy72, const void *d_proofs, const void *d_proof_off /*u64[B+1]*/,
                                               const void *d_ring_ids, const void *d_verifier_seeds, void *d_ok, void *d_per_proof_status);
+/* Bound membership proofs, "ZKMB".  A ZKM1 proof is a bare Groth-Kohlweiss transcript -- its challenge hashes the 4 n commitment points and nothing else
+ * (gk.ts:178-180, under the TODO "we should hash in the statement") --, so whoever sees one (com, proof) pair can present it again to any verifier, in any
+ * session, even for another ring of the same size that holds the value.  The _bound forms close that: the eight calls above with `context`, 32 bytes per
+ * proof chosen by the caller (a session nonce, a message hash, a verifier's id; the engine does not interpret them), after `which` (prove) or after
+ * com_xy72 (verify), and the challenge becomes
+ *     x = first 10 bytes of SHA-256( cl || ca || cb || cd  ||  S_b ),   the 4 n points in their hashPoints encodings (04 || x(33) || y(33)) as before,
+ *     S_b = "ZKAttest-GK-member-v1" (21 bytes, no terminator) || ring digest (32: zk_ring_digest of the proof's ring, padded) || context_b (32)
+ *           || 04 || com_b.x (33, big-endian) || com_b.y (33)                                                            -- 152 bytes.
+ * Everything else is the unbound call's: draws and their order, blinder rules, responses, sizes (zk_member_proof_size[_ring]), the verifier's order of
+ * checks, its status codes and its seeds, chunks, lanes, windows, timing families, wiping.  The proof's first four bytes are "ZKMB".  The bound verifier
+ * accepts exactly "ZKMB" and the unbound one exactly "ZKM1": the other magic is ZK_E_BAD_ENCODING, like any wrong magic.  A proof verifies only with the
+ * context and the com it was made with, against the ring it was made for: another context, another proof's com or another ring give ok = 0, status 0.
+ * The ring digest is read when the call runs: after zk_ctx_update_ring a bound call hashes the updated ring's digest, so a proof made before the update
+ * no longer verifies (ok = 0, status 0) even where the key it is about was not touched -- re-prove after an update.  In the _rings forms proof b hashes
+ * the digest of ring ring_ids[b].  The binding is in the call, not in a mode: the _bound forms run in ZK_MODE_REFERENCE and ZK_MODE_HARDENED alike and give
+ * the same bytes in both.  Contexts are not secret: they are not wiped.  context == NULL: ZK_E_ARG (also for B = 0); otherwise the call-level rules above.
+ * No counterpart in the reference beyond its TODO; oracle/zkattest_ref.py states it as proveMembership / verifyMembership(..., statement = S_b). */
+zk_status zk_member_prove_batch_bound(zk_ctx *ctx, uint64_t B, const uint32_t *which /*B*/, const uint8_t *context /*Bx32*/,
+                                      const uint8_t *blinder_be32 /*Bx32 or NULL*/, const zk_rng *rng, uint8_t *com_xy72 /*Bx72 out*/,
+                                      uint8_t *blinder_out /*Bx32 or NULL*/, uint8_t *out, uint64_t out_cap, int32_t *per_proof_status /*B*/);
+zk_status zk_member_prove_batch_bound_device(zk_ctx *ctx, uint64_t B, const void *d_which, const void *d_context, const void *d_blinder_be32,
+                                             const zk_rng *rng /* rng->data in HBM */, void *d_com_xy72, void *d_blinder_out, void *d_out, uint64_t out_cap,
+                                             void *d_per_proof_status);
+zk_status zk_member_verify_batch_bound(zk_ctx *ctx, uint64_t B, const uint8_t *com_xy72 /*Bx72*/, const uint8_t *context /*Bx32*/,
+                                       const uint8_t *proofs /*B x size*/, const uint8_t *verifier_seeds /*Bx32 or NULL*/, uint8_t *ok /*B*/,
+                                       int32_t *per_proof_status /*B*/);
+zk_status zk_member_verify_batch_bound_device(zk_ctx *ctx, uint64_t B, const void *d_com_xy72, const void *d_context, const void *d_proofs,
+                                              const void *d_verifier_seeds, void *d_ok, void *d_per_proof_status);
+zk_status zk_member_prove_batch_rings_bound(zk_ctx *ctx, uint64_t B, const uint32_t *which /*B*/, const uint8_t *context /*Bx32*/,
+                                            const uint32_t *ring_ids /*B*/, const uint8_t *blinder_be32 /*Bx32 or NULL*/, const zk_rng *rng,
+                                            uint8_t *com_xy72 /*Bx72 out*/, uint8_t *blinder_out /*Bx32 or NULL*/, uint8_t *out, uint64_t out_cap,
+                                            uint64_t *out_off /*B+1*/, int32_t *per_proof_status /*B*/);
+zk_status zk_member_prove_batch_rings_bound_device(zk_ctx *ctx, uint64_t B, const void *d_which, const void *d_context, const void *d_ring_ids,
+                                                   const void *d_blinder_be32, const zk_rng *rng /* rng->data in HBM */, void *d_com_xy72,
+                                                   void *d_blinder_out, void *d_out, uint64_t out_cap, void *d_out_off /*u64[B+1]*/,
+                                                   void *d_per_proof_status);
+zk_status zk_member_verify_batch_rings_bound(zk_ctx *ctx, uint64_t B, const uint8_t *com_xy72 /*Bx72*/, const uint8_t *context /*Bx32*/,
+                                             const uint8_t *proofs, const uint64_t *proof_off /*B+1*/, const uint32_t *ring_ids /*B*/,
+                                             const uint8_t *verifier_seeds /*Bx32 or NULL*/, uint8_t *ok /*B*/, int32_t *per_proof_status /*B*/);
+zk_status zk_member_verify_batch_rings_bound_device(zk_ctx *ctx, uint64_t B, const void *d_com_xy72, const void *d_context, const void *d_proofs,
+                                                    const void *d_proof_off /*u64[B+1]*/, const void *d_ring_ids, const void *d_verifier_seeds, void *d_ok,
+                                                    void *d_per_proof_status);
 
 /* ---- two (or more) batches in flight on one context.  zk_prove_batch / zk_verify_batch are synchronous: each call pays its own head
  * (no byte of a chunk exists before its stage 1 is over) and its own tail (the copies of the last slices, with nothing left to

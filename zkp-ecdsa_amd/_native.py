@@ -30,6 +30,8 @@ SYMBOLS = [
     'zk_recover_batch', 'zk_recover_batch_device', 'zk_recover_batch_rings', 'zk_recover_batch_rings_device',
     'zk_member_proof_size', 'zk_member_prove_batch', 'zk_member_prove_batch_device', 'zk_member_verify_batch', 'zk_member_verify_batch_device',
     'zk_member_proof_size_ring', 'zk_member_prove_batch_rings', 'zk_member_prove_batch_rings_device', 'zk_member_verify_batch_rings', 'zk_member_verify_batch_rings_device',
+    'zk_member_prove_batch_bound', 'zk_member_prove_batch_bound_device', 'zk_member_verify_batch_bound', 'zk_member_verify_batch_bound_device',
+    'zk_member_prove_batch_rings_bound', 'zk_member_prove_batch_rings_bound_device', 'zk_member_verify_batch_rings_bound', 'zk_member_verify_batch_rings_bound_device',
     'zk_test_field_op', 'zk_test_tom_commit', 'zk_test_p256_fixed_mul', 'zk_test_sha256', 'zk_test_rng_draws', 'zk_test_exp_sum',
 ]
 
@@ -149,6 +151,15 @@ def lib():
         L.zk_member_prove_batch_rings_device.argtypes = [vp, u64, vp, vp, vp, C.POINTER(ZkRng), vp, vp, vp, u64, vp, vp]
         L.zk_member_verify_batch_rings.argtypes = [vp, u64, C.c_char_p, C.c_char_p, vp, vp, C.c_char_p, vp, vp]
         L.zk_member_verify_batch_rings_device.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp, vp]
+        # the bound forms ("ZKMB"): 32 context bytes per proof after `which` (prove) / after the commitments (verify)
+        L.zk_member_prove_batch_bound.argtypes = [vp, u64, vp, C.c_char_p, C.c_char_p, C.POINTER(ZkRng), vp, vp, vp, u64, vp]
+        L.zk_member_prove_batch_bound_device.argtypes = [vp, u64, vp, vp, vp, C.POINTER(ZkRng), vp, vp, vp, u64, vp]
+        L.zk_member_verify_batch_bound.argtypes = [vp, u64, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, vp, vp]
+        L.zk_member_verify_batch_bound_device.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp]
+        L.zk_member_prove_batch_rings_bound.argtypes = [vp, u64, vp, C.c_char_p, vp, C.c_char_p, C.POINTER(ZkRng), vp, vp, vp, u64, vp, vp]
+        L.zk_member_prove_batch_rings_bound_device.argtypes = [vp, u64, vp, vp, vp, vp, C.POINTER(ZkRng), vp, vp, vp, u64, vp, vp]
+        L.zk_member_verify_batch_rings_bound.argtypes = [vp, u64, C.c_char_p, C.c_char_p, C.c_char_p, vp, vp, C.c_char_p, vp, vp]
+        L.zk_member_verify_batch_rings_bound_device.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp, vp, vp]
         L.zk_ring_digest.argtypes = [vp, vp]
         L.zk_hardened_h.argtypes = [C.c_char_p, u64, vp, vp]
         L.zk_pool_create.argtypes = [C.POINTER(C.c_int), i32, C.POINTER(vp)]
@@ -758,8 +769,18 @@ class Engine:
             return int(self.L.zk_member_proof_size_ring(self.h, int(ring)))
         return int(self.L.zk_member_proof_size(self.h))
 
-    def member_prove_batch(self, which, blinders=None, seeds=None, streams=None, stream_blocks=0, want_blinders=True):
-        """One membership proof per entry of `which` (indices into the padded active ring).  blinders: B x 32 bytes, the openings' blinders (reduced mod
+    @staticmethod
+    def _member_context(context, B):
+        """context of a bound membership call: B x 32 bytes, or a list of B 32-byte strings -> bytes (never empty: NULL means 'no context' to the C ABI)"""
+        if not isinstance(context, (bytes, bytearray, memoryview)):
+            context = b''.join(bytes(x) for x in context)
+        if len(context) != 32 * B:
+            raise ValueError('context must hold 32 bytes per proof')
+        return bytes(context) if B else bytes(32)
+
+    def member_prove_batch(self, which, blinders=None, seeds=None, streams=None, stream_blocks=0, want_blinders=True, context=None):
+        """One membership proof per entry of `which` (indices into the padded active ring).  context (B x 32 bytes, or a list of 32-byte strings): bound
+        proofs, "ZKMB" -- the challenge also hashes the ring's digest, context[b] and com[b] (zk_member_prove_batch_bound); None: "ZKM1".  blinders: B x 32 bytes, the openings' blinders (reduced mod
         q), or None: the engine draws each from fill 0 of the proof's RNG.  Returns (proofs: list of bytes or None, coms: list of 72-byte Tom-256 points,
         blinders: list of 32-byte scalars or None, statuses).  seeds: as in prove_batch -- fresh, secret, one per proof."""
         B = len(which)
@@ -781,34 +802,49 @@ class Engine:
         else:
             data = C.create_string_buffer(bytes(streams), max(32 * B * stream_blocks, 1))
             rng = ZkRng(1, C.cast(data, C.c_void_p), stream_blocks)
-        self._chk(self.L.zk_member_prove_batch(self.h, B, w, bytes(blinders) if blinders is not None else None, C.byref(rng), com, bo, out, size * B, st))
+        bl = bytes(blinders) if blinders is not None else None
+        if context is None:
+            self._chk(self.L.zk_member_prove_batch(self.h, B, w, bl, C.byref(rng), com, bo, out, size * B, st))
+        else:
+            self._chk(self.L.zk_member_prove_batch_bound(self.h, B, w, self._member_context(context, B), bl, C.byref(rng), com, bo, out, size * B, st))
         raw, craw = out.raw, com.raw
         proofs = [raw[size * b:size * (b + 1)] if st[b] == 0 else None for b in range(B)]
         self.member_last_raw = raw[:size * B]   # the B slots as written (a slot whose status is not 0 is zero-filled)
         return (proofs, [craw[72 * b:72 * (b + 1)] for b in range(B)], [bo.raw[32 * b:32 * (b + 1)] for b in range(B)] if want_blinders else None,
                 list(st)[:B])
 
-    def member_prove_batch_device(self, B, d_which, d_blinders, d_rng, d_com, d_blinders_out, d_out, out_cap, d_status, mode=0, stride_blocks=0):
+    def member_prove_batch_device(self, B, d_which, d_blinders, d_rng, d_com, d_blinders_out, d_out, out_cap, d_status, mode=0, stride_blocks=0, d_context=None):
         rng = ZkRng(mode, d_rng, stride_blocks)
-        self._chk(self.L.zk_member_prove_batch_device(self.h, B, d_which, d_blinders, C.byref(rng), d_com, d_blinders_out, d_out, out_cap, d_status))
+        if d_context is None:
+            self._chk(self.L.zk_member_prove_batch_device(self.h, B, d_which, d_blinders, C.byref(rng), d_com, d_blinders_out, d_out, out_cap, d_status))
+        else:
+            self._chk(self.L.zk_member_prove_batch_bound_device(self.h, B, d_which, d_context, d_blinders, C.byref(rng), d_com, d_blinders_out, d_out, out_cap, d_status))
 
-    def member_verify_batch(self, coms, proofs, vseeds=None):
-        """verifyMembership for B (com, proof) pairs on the active ring; every proof is member_proof_size() bytes.  Returns (ok list, status list)."""
+    def member_verify_batch(self, coms, proofs, vseeds=None, context=None):
+        """verifyMembership for B (com, proof) pairs on the active ring; every proof is member_proof_size() bytes.  context: as in member_prove_batch --
+        the bound verifier (zk_member_verify_batch_bound), which takes "ZKMB" proofs only.  Returns (ok list, status list)."""
         B = len(proofs)
         size = self.member_proof_size()
         if len(coms) != B or any(len(p) != size for p in proofs) or any(len(cm) != 72 for cm in coms):
             raise ValueError('one 72-byte commitment and one proof of member_proof_size() bytes per entry')
         ok = (C.c_uint8 * max(B, 1))()
         st = (C.c_int32 * max(B, 1))()
-        self._chk(self.L.zk_member_verify_batch(self.h, B, b''.join(coms), b''.join(proofs), bytes(vseeds) if vseeds is not None else None, ok, st))
+        vs = bytes(vseeds) if vseeds is not None else None
+        if context is None:
+            self._chk(self.L.zk_member_verify_batch(self.h, B, b''.join(coms), b''.join(proofs), vs, ok, st))
+        else:
+            self._chk(self.L.zk_member_verify_batch_bound(self.h, B, b''.join(coms), self._member_context(context, B), b''.join(proofs), vs, ok, st))
         return list(ok)[:B], list(st)[:B]
 
-    def member_verify_batch_device(self, B, d_com, d_proofs, d_vseeds, d_ok, d_status):
-        self._chk(self.L.zk_member_verify_batch_device(self.h, B, d_com, d_proofs, d_vseeds, d_ok, d_status))
+    def member_verify_batch_device(self, B, d_com, d_proofs, d_vseeds, d_ok, d_status, d_context=None):
+        if d_context is None:
+            self._chk(self.L.zk_member_verify_batch_device(self.h, B, d_com, d_proofs, d_vseeds, d_ok, d_status))
+        else:
+            self._chk(self.L.zk_member_verify_batch_bound_device(self.h, B, d_com, d_context, d_proofs, d_vseeds, d_ok, d_status))
 
     # ---- ... with one resident ring id per proof (zk_member_*_batch_rings): the active ring plays no part
-    def member_prove_batch_rings(self, which, ring_ids, blinders=None, seeds=None, streams=None, stream_blocks=0, want_blinders=True, cap=None):
-        """member_prove_batch with one resident ring id per proof (which[b] indexes ring ring_ids[b]).  Returns (proofs: list of bytes or None, coms,
+    def member_prove_batch_rings(self, which, ring_ids, blinders=None, seeds=None, streams=None, stream_blocks=0, want_blinders=True, cap=None, context=None):
+        """member_prove_batch with one resident ring id per proof (which[b] indexes ring ring_ids[b]; context: bound proofs, each over ITS ring's digest).  Returns (proofs: list of bytes or None, coms,
         blinders or None, statuses); the proofs lie back to back in index order: member_last_off holds the B + 1 offsets, member_last_raw the bytes.
         An id that is not resident gives status 14, no proof and 72 zero bytes of com.  cap: the out_cap handed to the call (default: what the batch takes)."""
         B = len(which)
@@ -836,7 +872,11 @@ class Engine:
         else:
             data = C.create_string_buffer(bytes(streams), max(32 * B * stream_blocks, 1))
             rng = ZkRng(1, C.cast(data, C.c_void_p), stream_blocks)
-        self._chk(self.L.zk_member_prove_batch_rings(self.h, B, w, ids, bytes(blinders) if blinders is not None else None, C.byref(rng), com, bo, out, cap, off, st))
+        bl = bytes(blinders) if blinders is not None else None
+        if context is None:
+            self._chk(self.L.zk_member_prove_batch_rings(self.h, B, w, ids, bl, C.byref(rng), com, bo, out, cap, off, st))
+        else:
+            self._chk(self.L.zk_member_prove_batch_rings_bound(self.h, B, w, self._member_context(context, B), ids, bl, C.byref(rng), com, bo, out, cap, off, st))
         raw, craw = out.raw, com.raw
         self.member_last_off = list(off)
         self.member_last_raw = raw[:off[B]]
@@ -844,14 +884,20 @@ class Engine:
         return (proofs, [craw[72 * b:72 * (b + 1)] for b in range(B)], [bo.raw[32 * b:32 * (b + 1)] for b in range(B)] if want_blinders else None,
                 list(st)[:B])
 
-    def member_prove_batch_rings_device(self, B, d_which, d_ring_ids, d_blinders, d_rng, d_com, d_blinders_out, d_out, out_cap, d_off, d_status, mode=0, stride_blocks=0):
-        """zk_member_prove_batch_rings_device: every pointer a device address"""
+    def member_prove_batch_rings_device(self, B, d_which, d_ring_ids, d_blinders, d_rng, d_com, d_blinders_out, d_out, out_cap, d_off, d_status, mode=0, stride_blocks=0,
+                                        d_context=None):
+        """zk_member_prove_batch_rings_device (d_context: zk_member_prove_batch_rings_bound_device): every pointer a device address"""
         rng = ZkRng(mode, d_rng, stride_blocks)
-        self._chk(self.L.zk_member_prove_batch_rings_device(self.h, B, d_which, d_ring_ids, d_blinders, C.byref(rng), d_com, d_blinders_out, d_out, out_cap, d_off, d_status))
+        if d_context is None:
+            self._chk(self.L.zk_member_prove_batch_rings_device(self.h, B, d_which, d_ring_ids, d_blinders, C.byref(rng), d_com, d_blinders_out, d_out, out_cap, d_off, d_status))
+        else:
+            self._chk(self.L.zk_member_prove_batch_rings_bound_device(self.h, B, d_which, d_context, d_ring_ids, d_blinders, C.byref(rng), d_com, d_blinders_out, d_out, out_cap,
+                                                                      d_off, d_status))
 
-    def member_verify_batch_rings(self, coms, proofs, ring_ids, vseeds=None, offsets=None):
+    def member_verify_batch_rings(self, coms, proofs, ring_ids, vseeds=None, offsets=None, context=None):
         """verifyMembership for B (com, proof) pairs, proof b under the resident ring ring_ids[b].  proofs: a list of byte strings laid back to back, or
-        (offsets given) the bytes of the whole batch with its B + 1 offsets.  Returns (ok list, status list)."""
+        (offsets given) the bytes of the whole batch with its B + 1 offsets.  context: as in member_prove_batch -- the bound verifier
+        (zk_member_verify_batch_rings_bound): "ZKMB" proofs only, proof b against the digest of ring ring_ids[b] and context[b].  Returns (ok list, status list)."""
         B = len(coms)
         if len(ring_ids) != B or any(len(cm) != 72 for cm in coms):
             raise ValueError('one 72-byte commitment and one ring id per entry')
@@ -869,12 +915,19 @@ class Engine:
         st = (C.c_int32 * max(B, 1))()
         off = (C.c_uint64 * (B + 1))(*offsets)
         ids = (C.c_uint32 * max(B, 1))(*ring_ids)
-        self._chk(self.L.zk_member_verify_batch_rings(self.h, B, b''.join(coms), bytes(proofs), off, ids, bytes(vseeds) if vseeds is not None else None, ok, st))
+        vs = bytes(vseeds) if vseeds is not None else None
+        if context is None:
+            self._chk(self.L.zk_member_verify_batch_rings(self.h, B, b''.join(coms), bytes(proofs), off, ids, vs, ok, st))
+        else:
+            self._chk(self.L.zk_member_verify_batch_rings_bound(self.h, B, b''.join(coms), self._member_context(context, B), bytes(proofs), off, ids, vs, ok, st))
         return list(ok)[:B], list(st)[:B]
 
-    def member_verify_batch_rings_device(self, B, d_com, d_proofs, d_off, d_ring_ids, d_vseeds, d_ok, d_status):
-        """zk_member_verify_batch_rings_device: every pointer a device address"""
-        self._chk(self.L.zk_member_verify_batch_rings_device(self.h, B, d_com, d_proofs, d_off, d_ring_ids, d_vseeds, d_ok, d_status))
+    def member_verify_batch_rings_device(self, B, d_com, d_proofs, d_off, d_ring_ids, d_vseeds, d_ok, d_status, d_context=None):
+        """zk_member_verify_batch_rings_device (d_context: zk_member_verify_batch_rings_bound_device): every pointer a device address"""
+        if d_context is None:
+            self._chk(self.L.zk_member_verify_batch_rings_device(self.h, B, d_com, d_proofs, d_off, d_ring_ids, d_vseeds, d_ok, d_status))
+        else:
+            self._chk(self.L.zk_member_verify_batch_rings_bound_device(self.h, B, d_com, d_context, d_proofs, d_off, d_ring_ids, d_vseeds, d_ok, d_status))
 
     def synth_params(self, seed):
         a, b, c = C.create_string_buffer(64), C.create_string_buffer(72), C.create_string_buffer(72)

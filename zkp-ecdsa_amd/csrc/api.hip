@@ -826,7 +826,7 @@ zk_status ensure_workspace(zk_ctx* c, uint32_t C, uint32_t nlanes) {
             L.ready = true;
         }
         L.W.ring = Soa{c->ring->ring_mem, (uint32_t)c->ring->N};
-        L.W.hardened = c->mode == ZK_MODE_HARDENED, L.W.ring_digest = c->ring->ring_digest;
+        L.W.gk_stmt = c->mode == ZK_MODE_HARDENED ? GK_STMT_FULL : GK_STMT_NONE, L.W.ring_digest = c->ring->ring_digest;
         L.W.wire = wire_make(c->wire == ZK_WIRE_ZKA1P);
         L.W.ktab = c->ring->ktab, L.W.ktab_ok = c->ring->ktab_ok;
         L.W.gk_etab = c->ring->gk_etab;

@@ -1,5 +1,6 @@
 // zk_member_prove_batch / zk_member_verify_batch (include/zkattest.h): proveMembership / verifyMembership (gk.ts:94-262) on the active ring, without a ZKAttest
-// proof around them, and their _rings forms with one resident ring id per proof.  Host-side pipeline; the kernels of its own are in k_member.hip and
+// proof around them, their _rings forms with one resident ring id per proof, and the _bound forms of all of them ("ZKMB": the challenge also hashes the ring's
+// digest, 32 context bytes of the caller's and the commitment -- d_ctx below; nullptr = the unbound call).  Host-side pipeline; the kernels of its own are in k_member.hip and
 // k_member_rings.hip, everything heavy is the GK phase of the full prover and verifier.
 #include "ctx.h"
 #include "jobs.h"
@@ -93,11 +94,11 @@ static zk_status ensure_member_lanes(zk_ctx* c, uint32_t C, uint32_t nlanes) {
     }
     return ZK_OK;
 }
-static zk_status member_refusal(zk_ctx* c, bool need_ring = true) {   // (the mixed-ring forms read no active ring)
+static zk_status member_refusal(zk_ctx* c, bool bound, bool need_ring = true) {   // (the mixed-ring forms read no active ring)
     if (!c->params_set || (need_ring && !c->ring->N)) return ZK_E_BUFFER;
     if (c->stream_busy) return busy_refusal(c);
-    if (c->mode == ZK_MODE_HARDENED) {
-        c->err = "membership proofs on their own have no statement to bind: not available in ZK_MODE_HARDENED";
+    if (c->mode == ZK_MODE_HARDENED && !bound) {   // a bound call names its statement itself, in either mode
+        c->err = "an unbound membership proof hashes no statement: not available in ZK_MODE_HARDENED (use the _bound calls)";
         return ZK_E_ARG;
     }
     return ZK_OK;
@@ -113,7 +114,7 @@ extern "C" uint64_t zk_member_proof_size(const zk_ctx* c) {
 // carved for.  Every lane is drained before it returns; *e_sync is what draining them gave.  Wipes nothing and leaves the call's timing to its caller.
 static zk_status member_prove_run(zk_ctx* c, uint64_t B, const uint32_t* d_which, const uint8_t* d_blinder, int rng_mode, const uint8_t* d_rng, uint64_t stride,
                                   uint8_t* d_com, uint8_t* d_blinder_out, uint8_t* d_out, int32_t* d_status, uint32_t C, bool timed, const MemberSel& S, hipEvent_t ready,
-                                  hipError_t* e_sync) {
+                                  hipError_t* e_sync, const uint8_t* d_ctx) {
     const uint32_t size = (uint32_t)zkm1_size(c->ring->n);
     const DevParams& P = c->P;
     const std::vector<ChunkPlan> plan = make_chunk_plan(B, C, 1, false);
@@ -129,6 +130,8 @@ static zk_status member_prove_run(zk_ctx* c, uint64_t B, const uint32_t* d_which
         Workspace& W = L.W;
         hipStream_t s = c->pl[lane].stream;
         W.gk_fill0 = d_blinder ? 0 : 1;
+        // bound: the challenge hashes the bound ring's digest, the proof's context (indexed like d_which) and its com; the header says so
+        W.gk_stmt = d_ctx ? GK_STMT_MEMBER : GK_STMT_NONE, W.ring_digest = c->ring->ring_digest, W.wire.magic = d_ctx ? ZK_MAGIC_ZKMB : ZK_MAGIC_ZKM1;
         const uint32_t nblk = W.gk_fill0 + 5 * W.n + RNG_MAX_EXC;   // + margin: rejected fills shift later draws
         W.rng.seeds = d_rng, W.rng.stream = d_rng, W.rng.stride_blocks = stride, W.rng.mode = rng_mode, W.rng.sec = -1, W.rng.proof_base = (uint32_t)first;
         {
@@ -155,7 +158,7 @@ static zk_status member_prove_run(zk_ctx* c, uint64_t B, const uint32_t* d_which
         }
         {
             MaybeScope t(timed, c, "hash", s);
-            launch_gk_hash(s, W, cnt, nullptr);
+            launch_gk_hash(s, W, cnt, d_ctx ? d_ctx + 32 * first : nullptr);   // behind the normaliser: com's affine coordinates are the ones k_m_write_head writes out
         }
         {
             MaybeScope t(timed, c, "respond_write", s);
@@ -173,8 +176,8 @@ static zk_status member_prove_run(zk_ctx* c, uint64_t B, const uint32_t* d_which
     return zs;
 }
 static zk_status member_prove_device(zk_ctx* c, uint64_t B, const uint32_t* d_which, const uint8_t* d_blinder, int rng_mode, const uint8_t* d_rng, uint64_t stride,
-                                     uint8_t* d_com, uint8_t* d_blinder_out, uint8_t* d_out, uint64_t out_cap, int32_t* d_status) {
-    if (zk_status zs = member_refusal(c)) return zs;
+                                     uint8_t* d_com, uint8_t* d_blinder_out, uint8_t* d_out, uint64_t out_cap, int32_t* d_status, const uint8_t* d_ctx) {
+    if (zk_status zs = member_refusal(c, d_ctx != nullptr)) return zs;
     if (rng_mode != ZK_RNG_SEED && rng_mode != ZK_RNG_STREAM) return ZK_E_ARG;
     const uint32_t size = (uint32_t)zkm1_size(c->ring->n);
     if (B > out_cap / size) {
@@ -185,7 +188,7 @@ static zk_status member_prove_device(zk_ctx* c, uint64_t B, const uint32_t* d_wh
     if (B == 0) return ZK_OK;
     hipError_t e_sync = hipSuccess;
     const zk_status zs = member_prove_run(c, B, d_which, d_blinder, rng_mode, d_rng, stride, d_com, d_blinder_out, d_out, d_status, (uint32_t)std::min<uint64_t>(c->chunk, B),
-                                          zk_timed(c, B), MemberSel{}, nullptr, &e_sync);
+                                          zk_timed(c, B), MemberSel{}, nullptr, &e_sync, d_ctx);
     if (zs || e_sync != hipSuccess) wipe_witness(c);   // a failed call leaves no nonce, blinder or RNG block behind
     if (zs) return zs;
     HIPCHK(c, e_sync);
@@ -198,32 +201,45 @@ extern "C" zk_status zk_member_prove_batch_device(zk_ctx* c, uint64_t B, const v
     if (!c || !rng || (B && (!d_which || !rng->data || !d_com || !d_out || !d_status))) return ZK_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     return member_prove_device(c, B, (const uint32_t*)d_which, (const uint8_t*)d_blinder, rng->mode, rng->data, rng->stride_blocks, (uint8_t*)d_com, (uint8_t*)d_blinder_out,
-                               (uint8_t*)d_out, out_cap, (int32_t*)d_status);
+                               (uint8_t*)d_out, out_cap, (int32_t*)d_status, nullptr);
+}
+extern "C" zk_status zk_member_prove_batch_bound_device(zk_ctx* c, uint64_t B, const void* d_which, const void* d_context, const void* d_blinder, const zk_rng* rng, void* d_com,
+                                                        void* d_blinder_out, void* d_out, uint64_t out_cap, void* d_status) {
+    if (!c || !rng || !d_context || (B && (!d_which || !rng->data || !d_com || !d_out || !d_status))) return ZK_E_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    return member_prove_device(c, B, (const uint32_t*)d_which, (const uint8_t*)d_blinder, rng->mode, rng->data, rng->stride_blocks, (uint8_t*)d_com, (uint8_t*)d_blinder_out,
+                               (uint8_t*)d_out, out_cap, (int32_t*)d_status, (const uint8_t*)d_context);
 }
 // Host pointers: the small arrays through the context's input buffer (witness-derived: wiped with it), the proofs through its output staging buffer.
 struct MemberProveIn {
     uint32_t* which;
-    uint8_t *blinder, *rng, *com, *blinder_out;
+    uint8_t *blinder, *rng, *com, *blinder_out, *ctx;
     int32_t* st;
 };
 static size_t member_prove_in_layout(MemberProveIn& I, uint8_t* base, size_t B, size_t rng_bytes) {
     Carver k(base);
     I.which = (uint32_t*)k.take(4 * B), I.blinder = (uint8_t*)k.take(32 * B), I.rng = (uint8_t*)k.take(rng_bytes ? rng_bytes : 32), I.com = (uint8_t*)k.take(72 * B);
-    I.blinder_out = (uint8_t*)k.take(32 * B), I.st = (int32_t*)k.take(4 * B);
+    I.blinder_out = (uint8_t*)k.take(32 * B), I.st = (int32_t*)k.take(4 * B), I.ctx = (uint8_t*)k.take(32 * B);
     return k.off + ZK_LAYOUT_TAIL;
 }
 // zk_member_prove_batch on the ring the context is bound to: the active one, or the one ring of a zk_member_prove_batch_rings call (RingBind)
 static zk_status member_prove_host(zk_ctx* c, uint64_t B, const uint32_t* which, const uint8_t* blinder, const zk_rng* rng, uint8_t* com, uint8_t* blinder_out, uint8_t* out,
-                                   uint64_t out_cap, int32_t* status);
+                                   uint64_t out_cap, int32_t* status, const uint8_t* context);
 extern "C" zk_status zk_member_prove_batch(zk_ctx* c, uint64_t B, const uint32_t* which, const uint8_t* blinder, const zk_rng* rng, uint8_t* com, uint8_t* blinder_out,
                                            uint8_t* out, uint64_t out_cap, int32_t* status) {
     if (!c || !rng || (B && (!which || !rng->data || !com || !out || !status))) return ZK_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    return member_prove_host(c, B, which, blinder, rng, com, blinder_out, out, out_cap, status);
+    return member_prove_host(c, B, which, blinder, rng, com, blinder_out, out, out_cap, status, nullptr);
+}
+extern "C" zk_status zk_member_prove_batch_bound(zk_ctx* c, uint64_t B, const uint32_t* which, const uint8_t* context, const uint8_t* blinder, const zk_rng* rng, uint8_t* com,
+                                                 uint8_t* blinder_out, uint8_t* out, uint64_t out_cap, int32_t* status) {
+    if (!c || !rng || !context || (B && (!which || !rng->data || !com || !out || !status))) return ZK_E_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    return member_prove_host(c, B, which, blinder, rng, com, blinder_out, out, out_cap, status, context);
 }
 static zk_status member_prove_host(zk_ctx* c, uint64_t B, const uint32_t* which, const uint8_t* blinder, const zk_rng* rng, uint8_t* com, uint8_t* blinder_out, uint8_t* out,
-                                   uint64_t out_cap, int32_t* status) {
-    if (zk_status zs = member_refusal(c)) return zs;
+                                   uint64_t out_cap, int32_t* status, const uint8_t* context) {
+    if (zk_status zs = member_refusal(c, context != nullptr)) return zs;
     if (rng->mode != ZK_RNG_SEED && rng->mode != ZK_RNG_STREAM) return ZK_E_ARG;
     const uint64_t size = zkm1_size(c->ring->n);
     if (B > out_cap / size) {
@@ -240,9 +256,10 @@ static zk_status member_prove_host(zk_ctx* c, uint64_t B, const uint32_t* which,
     HIPCHK(c, hipMemcpyAsync(I.which, which, 4 * B, hipMemcpyHostToDevice, s));
     if (blinder) HIPCHK(c, hipMemcpyAsync(I.blinder, blinder, 32 * B, hipMemcpyHostToDevice, s));
     HIPCHK(c, hipMemcpyAsync(I.rng, rng->data, rng_bytes, hipMemcpyHostToDevice, s));
+    if (context) HIPCHK(c, hipMemcpyAsync(I.ctx, context, 32 * B, hipMemcpyHostToDevice, s));
     HIPCHK(c, hipStreamSynchronize(s));   // the lanes' streams start behind the inputs
     zk_status zs = member_prove_device(c, B, I.which, blinder ? I.blinder : nullptr, rng->mode, I.rng, rng->stride_blocks, I.com, blinder_out ? I.blinder_out : nullptr, d_out,
-                                       B * size, I.st);
+                                       B * size, I.st, context ? I.ctx : nullptr);
     if (zs) return zs;
     HIPCHK(c, hipMemcpyAsync(out, d_out, B * size, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipMemcpyAsync(com, I.com, 72 * B, hipMemcpyDeviceToHost, s));
@@ -257,7 +274,7 @@ static zk_status member_prove_host(zk_ctx* c, uint64_t B, const uint32_t* which,
 // where the next one starts), or (S.sel) one window of a mixed-ring call -- d_com, d_off and d_vseeds are the window's gathered arrays, every slot is `slot`
 // bytes long, the verdicts go through S to their places in the batch's arrays, and the lanes start behind `ready`.  Every lane is drained before it returns.
 static zk_status member_verify_run(zk_ctx* c, uint64_t B, const uint8_t* d_com, const uint8_t* d_proofs, const uint64_t* d_off, const uint8_t* d_vseeds, uint8_t* d_ok,
-                                   int32_t* d_status, uint32_t C, bool timed, uint32_t slot, const MemberSel& S, hipEvent_t ready) {
+                                   int32_t* d_status, uint32_t C, bool timed, uint32_t slot, const MemberSel& S, hipEvent_t ready, const uint8_t* d_ctx) {
     const DevParams& P = c->P;
     const std::vector<ChunkPlan> plan = make_chunk_plan(B, C, 1, false);
     const uint32_t NL = (uint32_t)std::min<size_t>(c->lanes, plan.size());
@@ -271,6 +288,7 @@ static zk_status member_verify_run(zk_ctx* c, uint64_t B, const uint8_t* d_com, 
         Workspace& W = L.W;
         VWork& V = L.V;
         V.com = d_com;
+        V.gk_stmt = d_ctx ? GK_STMT_MEMBER : GK_STMT_NONE, V.ring_digest = c->ring->ring_digest;   // bound (d_ctx is indexed like d_com): "ZKMB" and its statement, else "ZKM1"
         hipStream_t s = c->pl[lane].stream;
         const uint32_t nq = (V.n + 1) / 2;
         {
@@ -279,7 +297,7 @@ static zk_status member_verify_run(zk_ctx* c, uint64_t B, const uint8_t* d_com, 
         }
         {
             MaybeScope t(timed, c, "v_gk_total", s);
-            launch_v_challenges(s, V, cnt, d_proofs, d_off, nullptr, first, 2);
+            launch_v_challenges(s, V, cnt, d_proofs, d_off, d_ctx, first, 2);
             launch_v_gk_total(s, V, W.ring, W.gk_etab, W.gk_kdig, cnt, W.N, d_proofs, d_off, first, L.res, L.res2);
             launch_v_proof_points(s, V, cnt, d_proofs, d_off, first, 1);
             launch_v_proof_terms(s, W, V, cnt, d_proofs, d_off, d_vseeds, first);
@@ -308,8 +326,9 @@ static zk_status member_default_vseeds(zk_ctx* c, uint64_t B, const uint8_t** d_
     *d_vseeds = (const uint8_t*)c->buf[B_seed].p;
     return ZK_OK;
 }
-static zk_status member_verify_device(zk_ctx* c, uint64_t B, const uint8_t* d_com, const uint8_t* d_proofs, const uint8_t* d_vseeds, uint8_t* d_ok, int32_t* d_status) {
-    if (zk_status zs = member_refusal(c)) return zs;
+static zk_status member_verify_device(zk_ctx* c, uint64_t B, const uint8_t* d_com, const uint8_t* d_proofs, const uint8_t* d_vseeds, uint8_t* d_ok, int32_t* d_status,
+                                      const uint8_t* d_ctx) {
+    if (zk_status zs = member_refusal(c, d_ctx != nullptr)) return zs;
     timing_begin(c);
     if (B == 0) return ZK_OK;
     const uint32_t C = (uint32_t)std::min<uint64_t>(c->chunk, B);
@@ -318,32 +337,46 @@ static zk_status member_verify_device(zk_ctx* c, uint64_t B, const uint8_t* d_co
     launch_mv_offsets(c->stream, d_off, B, zkm1_size(c->ring->n));
     if (zk_status zs = member_default_vseeds(c, B, &d_vseeds)) return zs;
     HIPCHK(c, hipStreamSynchronize(c->stream));   // offsets and seeds are there before any lane reads them
-    if (zk_status zs = member_verify_run(c, B, d_com, d_proofs, d_off, d_vseeds, d_ok, d_status, C, zk_timed(c, B), 0, MemberSel{}, nullptr)) return zs;
+    if (zk_status zs = member_verify_run(c, B, d_com, d_proofs, d_off, d_vseeds, d_ok, d_status, C, zk_timed(c, B), 0, MemberSel{}, nullptr, d_ctx)) return zs;
     timing_end(c);
     return ZK_OK;
 }
 extern "C" zk_status zk_member_verify_batch_device(zk_ctx* c, uint64_t B, const void* d_com, const void* d_proofs, const void* d_vseeds, void* d_ok, void* d_status) {
     if (!c || (B && (!d_com || !d_proofs || !d_ok || !d_status))) return ZK_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    return member_verify_device(c, B, (const uint8_t*)d_com, (const uint8_t*)d_proofs, (const uint8_t*)d_vseeds, (uint8_t*)d_ok, (int32_t*)d_status);
+    return member_verify_device(c, B, (const uint8_t*)d_com, (const uint8_t*)d_proofs, (const uint8_t*)d_vseeds, (uint8_t*)d_ok, (int32_t*)d_status, nullptr);
+}
+extern "C" zk_status zk_member_verify_batch_bound_device(zk_ctx* c, uint64_t B, const void* d_com, const void* d_context, const void* d_proofs, const void* d_vseeds, void* d_ok,
+                                                         void* d_status) {
+    if (!c || !d_context || (B && (!d_com || !d_proofs || !d_ok || !d_status))) return ZK_E_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    return member_verify_device(c, B, (const uint8_t*)d_com, (const uint8_t*)d_proofs, (const uint8_t*)d_vseeds, (uint8_t*)d_ok, (int32_t*)d_status, (const uint8_t*)d_context);
 }
 struct MemberVerifyIn {
-    uint8_t *com, *seeds, *ok;
+    uint8_t *com, *seeds, *ok, *ctx;
     int32_t* st;
 };
 static size_t member_verify_in_layout(MemberVerifyIn& I, uint8_t* base, size_t B) {
     Carver k(base);
-    I.com = (uint8_t*)k.take(72 * B), I.seeds = (uint8_t*)k.take(32 * B), I.ok = (uint8_t*)k.take(B), I.st = (int32_t*)k.take(4 * B);
+    I.com = (uint8_t*)k.take(72 * B), I.seeds = (uint8_t*)k.take(32 * B), I.ok = (uint8_t*)k.take(B), I.st = (int32_t*)k.take(4 * B), I.ctx = (uint8_t*)k.take(32 * B);
     return k.off + ZK_LAYOUT_TAIL;
 }
-static zk_status member_verify_host(zk_ctx* c, uint64_t B, const uint8_t* com, const uint8_t* proofs, const uint8_t* vseeds, uint8_t* ok, int32_t* status);
+static zk_status member_verify_host(zk_ctx* c, uint64_t B, const uint8_t* com, const uint8_t* proofs, const uint8_t* vseeds, uint8_t* ok, int32_t* status,
+                                    const uint8_t* context);
 extern "C" zk_status zk_member_verify_batch(zk_ctx* c, uint64_t B, const uint8_t* com, const uint8_t* proofs, const uint8_t* vseeds, uint8_t* ok, int32_t* status) {
     if (!c || (B && (!com || !proofs || !ok || !status))) return ZK_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    return member_verify_host(c, B, com, proofs, vseeds, ok, status);
+    return member_verify_host(c, B, com, proofs, vseeds, ok, status, nullptr);
 }
-static zk_status member_verify_host(zk_ctx* c, uint64_t B, const uint8_t* com, const uint8_t* proofs, const uint8_t* vseeds, uint8_t* ok, int32_t* status) {
-    if (zk_status zs = member_refusal(c)) return zs;
+extern "C" zk_status zk_member_verify_batch_bound(zk_ctx* c, uint64_t B, const uint8_t* com, const uint8_t* context, const uint8_t* proofs, const uint8_t* vseeds, uint8_t* ok,
+                                                  int32_t* status) {
+    if (!c || !context || (B && (!com || !proofs || !ok || !status))) return ZK_E_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    return member_verify_host(c, B, com, proofs, vseeds, ok, status, context);
+}
+static zk_status member_verify_host(zk_ctx* c, uint64_t B, const uint8_t* com, const uint8_t* proofs, const uint8_t* vseeds, uint8_t* ok, int32_t* status,
+                                    const uint8_t* context) {
+    if (zk_status zs = member_refusal(c, context != nullptr)) return zs;
     if (B == 0) return ZK_OK;
     const uint64_t size = zkm1_size(c->ring->n);
     MemberVerifyIn I;
@@ -354,8 +387,9 @@ static zk_status member_verify_host(zk_ctx* c, uint64_t B, const uint8_t* com, c
     HIPCHK(c, hipMemcpyAsync(I.com, com, 72 * B, hipMemcpyHostToDevice, s));
     if (vseeds) HIPCHK(c, hipMemcpyAsync(I.seeds, vseeds, 32 * B, hipMemcpyHostToDevice, s));
     HIPCHK(c, hipMemcpyAsync(d_proofs, proofs, B * size, hipMemcpyHostToDevice, s));
+    if (context) HIPCHK(c, hipMemcpyAsync(I.ctx, context, 32 * B, hipMemcpyHostToDevice, s));
     HIPCHK(c, hipStreamSynchronize(s));
-    if (zk_status zs = member_verify_device(c, B, I.com, d_proofs, vseeds ? I.seeds : nullptr, I.ok, I.st)) return zs;
+    if (zk_status zs = member_verify_device(c, B, I.com, d_proofs, vseeds ? I.seeds : nullptr, I.ok, I.st, context ? I.ctx : nullptr)) return zs;
     HIPCHK(c, hipMemcpyAsync(ok, I.ok, B, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipMemcpyAsync(status, I.st, 4 * B, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
@@ -370,7 +404,7 @@ static zk_status member_verify_host(zk_ctx* c, uint64_t B, const uint8_t* com, c
 //   One resident ring and nothing else: the one-ring pipeline on the caller's buffers with that ring bound.  No permutation, no gather.
 //   Otherwise, per ring, WINDOWS of at most 2 x chunk x lanes proofs through the stable permutation by class (k_part_perm): one gather collects the window's small
 //   inputs into c->buf[B_mw] (whole stream rows in ZK_RNG_STREAM mode), the window runs with its ring bound (ensure_member_lanes re-binds, and re-carves only
-//   when n or the tables change), and its writers put every proof, com, blinder, status and verdict at its final place through the window's `sel` list: no
+//   when n or the tables change, and hands a bound call that ring's digest), and its writers put every proof, com, blinder, status and verdict at its final place through the window's `sel` list: no
 //   staging buffer, no byte written twice.  The verifier reads the proof bytes in place through the window's gathered offsets.
 struct MemberCensus {
     uint8_t* cls;
@@ -383,20 +417,20 @@ static size_t member_census_layout(MemberCensus& X, uint8_t* base, uint64_t B, s
 }
 struct MemberProveWindow {
     uint32_t* which;
-    uint8_t *blinder, *rng;
+    uint8_t *blinder, *rng, *ctx;
 };
 static size_t member_prove_window_layout(MemberProveWindow& W, uint8_t* base, size_t Wp, size_t rng_row) {
     Carver k(base);
-    W.which = (uint32_t*)k.take(4 * Wp), W.blinder = (uint8_t*)k.take(32 * Wp), W.rng = (uint8_t*)k.take(rng_row * Wp + 32);
+    W.which = (uint32_t*)k.take(4 * Wp), W.blinder = (uint8_t*)k.take(32 * Wp), W.rng = (uint8_t*)k.take(rng_row * Wp + 32), W.ctx = (uint8_t*)k.take(32 * Wp);
     return k.off + ZK_LAYOUT_TAIL;
 }
 struct MemberVerifyWindow {
     uint64_t* off;
-    uint8_t *com, *seeds;
+    uint8_t *com, *seeds, *ctx;
 };
 static size_t member_verify_window_layout(MemberVerifyWindow& W, uint8_t* base, size_t Wp) {
     Carver k(base);
-    W.off = (uint64_t*)k.take(8 * Wp), W.com = (uint8_t*)k.take(72 * Wp), W.seeds = (uint8_t*)k.take(32 * Wp);
+    W.off = (uint64_t*)k.take(8 * Wp), W.com = (uint8_t*)k.take(72 * Wp), W.seeds = (uint8_t*)k.take(32 * Wp), W.ctx = (uint8_t*)k.take(32 * Wp);
     return k.off + ZK_LAYOUT_TAIL;
 }
 static void member_rings(zk_ctx* c, MrRings& R, Ring** slot) {   // the resident rings in slot order, with their proofs' sizes
@@ -422,8 +456,9 @@ static zk_status member_class(zk_ctx* c, uint64_t B, const uint32_t* d_ids, cons
     return ZK_OK;
 }
 static zk_status member_prove_rings_device(zk_ctx* c, uint64_t B, const uint32_t* d_which, const uint32_t* d_ids, const uint8_t* d_blinder, int rng_mode, const uint8_t* d_rng,
-                                           uint64_t stride, uint8_t* d_com, uint8_t* d_blinder_out, uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_off, int32_t* d_status) {
-    if (zk_status zs = member_refusal(c, false)) return zs;
+                                           uint64_t stride, uint8_t* d_com, uint8_t* d_blinder_out, uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_off, int32_t* d_status,
+                                           const uint8_t* d_ctx) {
+    if (zk_status zs = member_refusal(c, d_ctx != nullptr, false)) return zs;
     if (rng_mode != ZK_RNG_SEED && rng_mode != ZK_RNG_STREAM) return ZK_E_ARG;
     if (B > 0xffffffffull) return ZK_E_ARG;
     hipStream_t s = c->stream;
@@ -456,7 +491,7 @@ static zk_status member_prove_rings_device(zk_ctx* c, uint64_t B, const uint32_t
         he = hipStreamSynchronize(s);
         if (he == hipSuccess)
             zs = member_prove_run(c, B, d_which, d_blinder, rng_mode, d_rng, stride, d_com, d_blinder_out, d_out, d_status, (uint32_t)std::min<uint64_t>(c->chunk, B), timed,
-                                  MemberSel{}, nullptr, &he);
+                                  MemberSel{}, nullptr, &he, d_ctx);
     } else {
         launch_mr_perm(s, B, X.cls, X.cnts + 2 * MR_CLASSES, X.cnts, X.perm);
         const uint32_t Wp = mr_window_cap(c->chunk, c->lanes, cnt, R), C = std::min<uint32_t>(c->chunk, Wp);
@@ -472,12 +507,12 @@ static zk_status member_prove_rings_device(zk_ctx* c, uint64_t B, const uint32_t
                 c->dbg_mr_windows++;
                 {
                     MaybeScope t(timed, c, "m_gather", s);
-                    launch_mr_pgather(s, n, B, sel, d_which, d_blinder, rng_mode == ZK_RNG_SEED ? d_rng : nullptr, W.which, W.blinder, W.rng);
+                    launch_mr_pgather(s, n, B, sel, d_which, d_blinder, rng_mode == ZK_RNG_SEED ? d_rng : nullptr, d_ctx, W.which, W.blinder, W.rng, W.ctx);
                     if (rng_mode == ZK_RNG_STREAM) launch_pr_gather_rows(s, n, sel, d_rng, rng_row, W.rng);
                 }
                 if ((he = hipEventRecord(c->mr_ready, s)) != hipSuccess) break;
                 zs = member_prove_run(c, n, W.which, d_blinder ? W.blinder : nullptr, rng_mode, W.rng, stride, d_com, d_blinder_out, d_out, d_status, C, timed,
-                                      MemberSel{sel, d_out_off, B}, c->mr_ready, &he);
+                                      MemberSel{sel, d_out_off, B}, c->mr_ready, &he, d_ctx ? W.ctx : nullptr);
             }
         }
     }
@@ -507,14 +542,21 @@ extern "C" zk_status zk_member_prove_batch_rings_device(zk_ctx* c, uint64_t B, c
     if (!c || !rng || !d_out_off || (B && (!d_which || !d_ids || !rng->data || !d_com || !d_out || !d_status))) return ZK_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     return member_prove_rings_device(c, B, (const uint32_t*)d_which, (const uint32_t*)d_ids, (const uint8_t*)d_blinder, rng->mode, rng->data, rng->stride_blocks, (uint8_t*)d_com,
-                                     (uint8_t*)d_blinder_out, (uint8_t*)d_out, out_cap, (uint64_t*)d_out_off, (int32_t*)d_status);
+                                     (uint8_t*)d_blinder_out, (uint8_t*)d_out, out_cap, (uint64_t*)d_out_off, (int32_t*)d_status, nullptr);
+}
+extern "C" zk_status zk_member_prove_batch_rings_bound_device(zk_ctx* c, uint64_t B, const void* d_which, const void* d_context, const void* d_ids, const void* d_blinder,
+                                                              const zk_rng* rng, void* d_com, void* d_blinder_out, void* d_out, uint64_t out_cap, void* d_out_off, void* d_status) {
+    if (!c || !rng || !d_context || !d_out_off || (B && (!d_which || !d_ids || !rng->data || !d_com || !d_out || !d_status))) return ZK_E_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    return member_prove_rings_device(c, B, (const uint32_t*)d_which, (const uint32_t*)d_ids, (const uint8_t*)d_blinder, rng->mode, rng->data, rng->stride_blocks, (uint8_t*)d_com,
+                                     (uint8_t*)d_blinder_out, (uint8_t*)d_out, out_cap, (uint64_t*)d_out_off, (int32_t*)d_status, (const uint8_t*)d_context);
 }
 // Host pointers: the ids are classed here, and with them the offsets and the out_cap decision.  All of one resident ring: zk_member_prove_batch with that ring
 // bound.  Anything else: the inputs cross to HBM and take the device path; the proofs lie in order in the context's staging copy of `out` and cross the link in
 // one copy.
 struct MemberProveRingsIn {
     uint32_t *which, *ids;
-    uint8_t *blinder, *rng, *com, *blinder_out;
+    uint8_t *blinder, *rng, *com, *blinder_out, *ctx;
     int32_t* st;
     uint64_t* off;
 };
@@ -522,13 +564,26 @@ static size_t member_prove_rings_in_layout(MemberProveRingsIn& I, uint8_t* base,
     Carver k(base);
     I.which = (uint32_t*)k.take(4 * B), I.ids = (uint32_t*)k.take(4 * B), I.blinder = (uint8_t*)k.take(32 * B), I.rng = (uint8_t*)k.take(rng_bytes ? rng_bytes : 32);
     I.com = (uint8_t*)k.take(72 * B), I.blinder_out = (uint8_t*)k.take(32 * B), I.st = (int32_t*)k.take(4 * B), I.off = (uint64_t*)k.take(8 * (B + 1));
+    I.ctx = (uint8_t*)k.take(32 * B);
     return k.off + ZK_LAYOUT_TAIL;
 }
+static zk_status member_prove_rings_host(zk_ctx* c, uint64_t B, const uint32_t* which, const uint32_t* ring_ids, const uint8_t* blinder, const zk_rng* rng, uint8_t* com,
+                                         uint8_t* blinder_out, uint8_t* out, uint64_t out_cap, uint64_t* out_off, int32_t* status, const uint8_t* context);
 extern "C" zk_status zk_member_prove_batch_rings(zk_ctx* c, uint64_t B, const uint32_t* which, const uint32_t* ring_ids, const uint8_t* blinder, const zk_rng* rng, uint8_t* com,
                                                  uint8_t* blinder_out, uint8_t* out, uint64_t out_cap, uint64_t* out_off, int32_t* status) {
     if (!c || !rng || !out_off || (B && (!which || !ring_ids || !rng->data || !com || !out || !status))) return ZK_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    if (zk_status zs = member_refusal(c, false)) return zs;
+    return member_prove_rings_host(c, B, which, ring_ids, blinder, rng, com, blinder_out, out, out_cap, out_off, status, nullptr);
+}
+extern "C" zk_status zk_member_prove_batch_rings_bound(zk_ctx* c, uint64_t B, const uint32_t* which, const uint8_t* context, const uint32_t* ring_ids, const uint8_t* blinder,
+                                                       const zk_rng* rng, uint8_t* com, uint8_t* blinder_out, uint8_t* out, uint64_t out_cap, uint64_t* out_off, int32_t* status) {
+    if (!c || !rng || !context || !out_off || (B && (!which || !ring_ids || !rng->data || !com || !out || !status))) return ZK_E_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    return member_prove_rings_host(c, B, which, ring_ids, blinder, rng, com, blinder_out, out, out_cap, out_off, status, context);
+}
+static zk_status member_prove_rings_host(zk_ctx* c, uint64_t B, const uint32_t* which, const uint32_t* ring_ids, const uint8_t* blinder, const zk_rng* rng, uint8_t* com,
+                                         uint8_t* blinder_out, uint8_t* out, uint64_t out_cap, uint64_t* out_off, int32_t* status, const uint8_t* context) {
+    if (zk_status zs = member_refusal(c, context != nullptr, false)) return zs;
     if (rng->mode != ZK_RNG_SEED && rng->mode != ZK_RNG_STREAM) return ZK_E_ARG;
     if (B > 0xffffffffull) return ZK_E_ARG;
     if (B == 0) {
@@ -549,7 +604,7 @@ extern "C" zk_status zk_member_prove_batch_rings(zk_ctx* c, uint64_t B, const ui
     const uint32_t one = mr_single_class(cnt, R);
     if (one < MR_CLASSES) {
         RingBind rb(c, slot[one]);
-        if (zk_status zs = member_prove_host(c, B, which, blinder, rng, com, blinder_out, out, total, status)) return zs;
+        if (zk_status zs = member_prove_host(c, B, which, blinder, rng, com, blinder_out, out, total, status, context)) return zs;
         memcpy(out_off, off.data(), 8 * (B + 1));
         return ZK_OK;
     }
@@ -559,7 +614,7 @@ extern "C" zk_status zk_member_prove_batch_rings(zk_ctx* c, uint64_t B, const ui
     if (zk_status zs = reserve(c, B_io, total ? total : 32)) return zs;
     uint8_t* const d_out = (uint8_t*)c->buf[B_io].p;
     // from the first upload on, blinders and seeds lie in the input buffer: every failure below zeroes them (member_prove_rings_device does so itself)
-    const struct { void* d; const void* h; size_t n; } up[] = {{I.which, which, 4 * B}, {I.ids, ring_ids, 4 * B}, {I.blinder, blinder, blinder ? 32 * B : 0}, {I.rng, rng->data, rng_bytes}};
+    const struct { void* d; const void* h; size_t n; } up[] = {{I.which, which, 4 * B}, {I.ids, ring_ids, 4 * B}, {I.blinder, blinder, blinder ? 32 * B : 0}, {I.rng, rng->data, rng_bytes}, {I.ctx, context, context ? 32 * B : 0}};
     for (auto& u : up)
         if (u.n && hipMemcpy(u.d, u.h, u.n, hipMemcpyHostToDevice) != hipSuccess) {
             c->err = "upload of the inputs failed";
@@ -568,7 +623,7 @@ extern "C" zk_status zk_member_prove_batch_rings(zk_ctx* c, uint64_t B, const ui
             return ZK_E_DEVICE;
         }
     if (zk_status zs = member_prove_rings_device(c, B, I.which, I.ids, blinder ? I.blinder : nullptr, rng->mode, I.rng, rng->stride_blocks, I.com, blinder_out ? I.blinder_out : nullptr,
-                                                 d_out, total, I.off, I.st))
+                                                 d_out, total, I.off, I.st, context ? I.ctx : nullptr))
         return zs;
     hipError_t e = total ? hipMemcpy(out, d_out, total, hipMemcpyDeviceToHost) : hipSuccess;
     if (e == hipSuccess) e = hipMemcpy(com, I.com, 72 * B, hipMemcpyDeviceToHost);
@@ -581,8 +636,8 @@ extern "C" zk_status zk_member_prove_batch_rings(zk_ctx* c, uint64_t B, const ui
 }
 
 static zk_status member_verify_rings_device(zk_ctx* c, uint64_t B, const uint8_t* d_com, const uint8_t* d_proofs, const uint64_t* d_proof_off, const uint32_t* d_ids,
-                                            const uint8_t* d_vseeds, uint8_t* d_ok, int32_t* d_status) {
-    if (zk_status zs = member_refusal(c, false)) return zs;
+                                            const uint8_t* d_vseeds, uint8_t* d_ok, int32_t* d_status, const uint8_t* d_ctx) {
+    if (zk_status zs = member_refusal(c, d_ctx != nullptr, false)) return zs;
     if (B > 0xffffffffull || ((uintptr_t)d_proofs & 3)) return ZK_E_ARG;
     timing_begin(c);
     if (B == 0) return ZK_OK;
@@ -598,7 +653,8 @@ static zk_status member_verify_rings_device(zk_ctx* c, uint64_t B, const uint8_t
     const uint32_t one = mr_single_class(cnt, R);
     if (one < MR_CLASSES) {   // one ring, every slot as long as its proofs: the caller's buffers and offsets as they are
         RingBind rb(c, slot[one]);
-        if (zk_status zs = member_verify_run(c, B, d_com, d_proofs, d_proof_off, d_vseeds, d_ok, d_status, (uint32_t)std::min<uint64_t>(c->chunk, B), timed, 0, MemberSel{}, nullptr))
+        if (zk_status zs = member_verify_run(c, B, d_com, d_proofs, d_proof_off, d_vseeds, d_ok, d_status, (uint32_t)std::min<uint64_t>(c->chunk, B), timed, 0, MemberSel{}, nullptr,
+                                             d_ctx))
             return zs;
     } else {
         launch_mr_perm(s, B, X.cls, X.cnts + 2 * MR_CLASSES, X.cnts, X.perm);
@@ -614,10 +670,12 @@ static zk_status member_verify_rings_device(zk_ctx* c, uint64_t B, const uint8_t
                 c->dbg_mr_windows++;
                 {
                     MaybeScope t(timed, c, "m_gather", s);
-                    launch_mr_vgather(s, n, B, sel, d_proof_off, d_com, d_vseeds, W.off, W.com, W.seeds);
+                    launch_mr_vgather(s, n, B, sel, d_proof_off, d_com, d_vseeds, d_ctx, W.off, W.com, W.seeds, W.ctx);
                 }
                 HIPCHK(c, hipEventRecord(c->mr_ready, s));
-                if (zk_status zs = member_verify_run(c, n, W.com, d_proofs, W.off, W.seeds, d_ok, d_status, C, timed, R.size[r], MemberSel{sel, nullptr, B}, c->mr_ready)) return zs;
+                if (zk_status zs = member_verify_run(c, n, W.com, d_proofs, W.off, W.seeds, d_ok, d_status, C, timed, R.size[r], MemberSel{sel, nullptr, B}, c->mr_ready,
+                                                     d_ctx ? W.ctx : nullptr))
+                    return zs;
             }
         }
     }
@@ -631,12 +689,19 @@ extern "C" zk_status zk_member_verify_batch_rings_device(zk_ctx* c, uint64_t B, 
     if (!c || (B && (!d_com || !d_proofs || !d_proof_off || !d_ids || !d_ok || !d_status))) return ZK_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     return member_verify_rings_device(c, B, (const uint8_t*)d_com, (const uint8_t*)d_proofs, (const uint64_t*)d_proof_off, (const uint32_t*)d_ids, (const uint8_t*)d_vseeds,
-                                      (uint8_t*)d_ok, (int32_t*)d_status);
+                                      (uint8_t*)d_ok, (int32_t*)d_status, nullptr);
+}
+extern "C" zk_status zk_member_verify_batch_rings_bound_device(zk_ctx* c, uint64_t B, const void* d_com, const void* d_context, const void* d_proofs, const void* d_proof_off,
+                                                               const void* d_ids, const void* d_vseeds, void* d_ok, void* d_status) {
+    if (!c || !d_context || (B && (!d_com || !d_proofs || !d_proof_off || !d_ids || !d_ok || !d_status))) return ZK_E_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    return member_verify_rings_device(c, B, (const uint8_t*)d_com, (const uint8_t*)d_proofs, (const uint64_t*)d_proof_off, (const uint32_t*)d_ids, (const uint8_t*)d_vseeds,
+                                      (uint8_t*)d_ok, (int32_t*)d_status, (const uint8_t*)d_context);
 }
 // Host pointers: classed here as the classing kernel does.  One resident ring and every slot in order: zk_member_verify_batch on the bytes from the first slot
 // on, with that ring bound.  Anything else: everything crosses to HBM and takes the device path (which classes again; bytes behind proof_off[B] do not cross).
 struct MemberVerifyRingsIn {
-    uint8_t *com, *seeds, *ok;
+    uint8_t *com, *seeds, *ok, *ctx;
     uint32_t* ids;
     uint64_t* off;
     int32_t* st;
@@ -644,14 +709,26 @@ struct MemberVerifyRingsIn {
 static size_t member_verify_rings_in_layout(MemberVerifyRingsIn& I, uint8_t* base, size_t B) {
     Carver k(base);
     I.com = (uint8_t*)k.take(72 * B), I.seeds = (uint8_t*)k.take(32 * B), I.ok = (uint8_t*)k.take(B), I.ids = (uint32_t*)k.take(4 * B), I.off = (uint64_t*)k.take(8 * (B + 1));
-    I.st = (int32_t*)k.take(4 * B);
+    I.st = (int32_t*)k.take(4 * B), I.ctx = (uint8_t*)k.take(32 * B);
     return k.off + ZK_LAYOUT_TAIL;
 }
+static zk_status member_verify_rings_host(zk_ctx* c, uint64_t B, const uint8_t* com, const uint8_t* proofs, const uint64_t* proof_off, const uint32_t* ring_ids,
+                                          const uint8_t* vseeds, uint8_t* ok, int32_t* status, const uint8_t* context);
 extern "C" zk_status zk_member_verify_batch_rings(zk_ctx* c, uint64_t B, const uint8_t* com, const uint8_t* proofs, const uint64_t* proof_off, const uint32_t* ring_ids,
                                                   const uint8_t* vseeds, uint8_t* ok, int32_t* status) {
     if (!c || (B && (!com || !proofs || !proof_off || !ring_ids || !ok || !status))) return ZK_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    if (zk_status zs = member_refusal(c, false)) return zs;
+    return member_verify_rings_host(c, B, com, proofs, proof_off, ring_ids, vseeds, ok, status, nullptr);
+}
+extern "C" zk_status zk_member_verify_batch_rings_bound(zk_ctx* c, uint64_t B, const uint8_t* com, const uint8_t* context, const uint8_t* proofs, const uint64_t* proof_off,
+                                                        const uint32_t* ring_ids, const uint8_t* vseeds, uint8_t* ok, int32_t* status) {
+    if (!c || !context || (B && (!com || !proofs || !proof_off || !ring_ids || !ok || !status))) return ZK_E_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    return member_verify_rings_host(c, B, com, proofs, proof_off, ring_ids, vseeds, ok, status, context);
+}
+static zk_status member_verify_rings_host(zk_ctx* c, uint64_t B, const uint8_t* com, const uint8_t* proofs, const uint64_t* proof_off, const uint32_t* ring_ids,
+                                          const uint8_t* vseeds, uint8_t* ok, int32_t* status, const uint8_t* context) {
+    if (zk_status zs = member_refusal(c, context != nullptr, false)) return zs;
     if (B > 0xffffffffull) return ZK_E_ARG;
     if (B == 0) return ZK_OK;
     MrRings R;
@@ -666,7 +743,7 @@ extern "C" zk_status zk_member_verify_batch_rings(zk_ctx* c, uint64_t B, const u
     const uint32_t one = mr_single_class(cnt, R);
     if (one < MR_CLASSES) {
         RingBind rb(c, slot[one]);
-        return member_verify_host(c, B, com, proofs + proof_off[0], vseeds, ok, status);
+        return member_verify_host(c, B, com, proofs + proof_off[0], vseeds, ok, status, context);
     }
     const uint64_t bytes = proof_off[B];
     MemberVerifyRingsIn I;
@@ -679,8 +756,9 @@ extern "C" zk_status zk_member_verify_batch_rings(zk_ctx* c, uint64_t B, const u
     HIPCHK(c, hipMemcpyAsync(I.ids, ring_ids, 4 * B, hipMemcpyHostToDevice, s));
     HIPCHK(c, hipMemcpyAsync(I.off, proof_off, 8 * (B + 1), hipMemcpyHostToDevice, s));
     if (bytes) HIPCHK(c, hipMemcpyAsync(d_proofs, proofs, bytes, hipMemcpyHostToDevice, s));
+    if (context) HIPCHK(c, hipMemcpyAsync(I.ctx, context, 32 * B, hipMemcpyHostToDevice, s));
     HIPCHK(c, hipStreamSynchronize(s));
-    if (zk_status zs = member_verify_rings_device(c, B, I.com, d_proofs, I.off, I.ids, vseeds ? I.seeds : nullptr, I.ok, I.st)) return zs;
+    if (zk_status zs = member_verify_rings_device(c, B, I.com, d_proofs, I.off, I.ids, vseeds ? I.seeds : nullptr, I.ok, I.st, context ? I.ctx : nullptr)) return zs;
     HIPCHK(c, hipMemcpyAsync(ok, I.ok, B, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipMemcpyAsync(status, I.st, 4 * B, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));

@@ -112,7 +112,7 @@ zk_status ensure_vworkspace(zk_ctx* c, uint32_t C, uint32_t nlanes) {
         L.M.host = L.h_msm;
         L.ready = true;
     }
-    for (uint32_t l = 0; l < nlanes && l < ZK_MAX_LANES; l++) c->vl[l].V.hardened = c->mode == ZK_MODE_HARDENED, c->vl[l].V.ring_digest = c->ring->ring_digest;
+    for (uint32_t l = 0; l < nlanes && l < ZK_MAX_LANES; l++) c->vl[l].V.gk_stmt = c->mode == ZK_MODE_HARDENED ? GK_STMT_FULL : GK_STMT_NONE, c->vl[l].V.ring_digest = c->ring->ring_digest;
     return ZK_OK;
 }
 

@@ -166,7 +166,7 @@ struct Workspace {
     uint32_t* gk_goff;           // [257] group offsets of that order
     Soa ring;                    // [N] plain canonical limbs (shared, owned by ctx)
     uint32_t N;
-    uint32_t hardened;           // zk_ctx_set_mode: the GK challenge also hashes the statement (ring digest, msgHash, R, keyXcom)
+    uint32_t gk_stmt;            // GK_STMT_* (sha256.h): the GK challenge also hashes a statement -- zk_ctx_set_mode's (ring digest, msgHash, R, keyXcom), or a bound membership proof's
     const uint32_t* ring_digest; // [8] SHA-256 words of the padded ring (k_hash.hip: launch_ring_digest), owned by ctx
     Wire wire;                   // layout the prover's writers emit (zk_ctx_set_wire)
     RngCtx rng;
@@ -220,7 +220,7 @@ struct VTerms {           // terms of the "sum s_i P_i = identity" checks: niels
 };
 struct VWork {
     uint32_t C, sec, n;
-    uint32_t hardened;           // as in Workspace
+    uint32_t gk_stmt;            // as in Workspace
     const uint32_t* ring_digest;
     // where a proof's GKProof and the commitment it is about lie: ZK_FIXED bytes, the repetitions, then the GKProof, keyXcom at byte 160 (ZKA1); or 16 header
     // bytes, then the GKProof, the commitments in an array of their own (ZKM1, k_member.hip: sec = 0, zcnt = 0)

@@ -341,10 +341,13 @@ __global__ void __launch_bounds__(64) k_gk_hash(Workspace W, uint32_t count, con
     ShaStream s;
     s.init(lds, threadIdx.x, 64);
     for (uint32_t k = 0; k < 4 * W.n; k++) absorb_tom(s, W.lc.ax, W.lc.ay, p * 4 * W.n + k);
-    if (W.hardened) {   // the statement: which ring, which message, which R, which committed key (gk.ts:178 TODO)
+    if (W.gk_stmt == GK_STMT_FULL) {   // the statement: which ring, which message, which R, which committed key (gk.ts:178 TODO)
         sha_put_gk_statement_head(s, W.ring_digest, msg + 32 * (size_t)p);
         absorb_p256(s, W.Rx, W.Ry, p);
         absorb_tom(s, W.la.ax, W.la.ay, p * (2 + 2 * W.sec));
+    } else if (W.gk_stmt == GK_STMT_MEMBER) {   // a bound membership proof: which ring, which context (msg), which com -- the affine one k_m_write_head writes out
+        sha_put_member_statement_head(s, W.ring_digest, msg + 32 * (size_t)p);
+        absorb_tom(s, W.lc.ax, W.lc.ay, 4 * W.n * count + p);
     }
     uint32_t h[8], c[4];
     s.finish(h);
@@ -352,7 +355,7 @@ __global__ void __launch_bounds__(64) k_gk_hash(Workspace W, uint32_t count, con
     if (live) W.gk_x[3 * p] = c[0], W.gk_x[3 * p + 1] = c[1], W.gk_x[3 * p + 2] = c[2];
 }
 // The same digest for a call of a few proofs through the Exp challenge's three kernels (its buffers are free in stage 2): one lane per point writes the message
-// (4 n points of 67 bytes; hardened: the statement behind them), one lane per block expands the schedule, a pair of lanes per proof runs the rounds --
+// (4 n points of 67 bytes; the statement in force behind them), one lane per block expands the schedule, a pair of lanes per proof runs the rounds --
 // 68 blocks at 1.5 us instead of 2.5, and nobody absorbs 4 KB byte by byte in one lane.
 __global__ void __launch_bounds__(256) k_gk_msg(Workspace W, uint32_t count, const uint8_t* __restrict__ msg, uint32_t nblk) {
     const uint32_t ne = 4 * W.n + 1, t = gtid();
@@ -370,7 +373,17 @@ __global__ void __launch_bounds__(256) k_gk_msg(Workspace W, uint32_t count, con
         return;
     }
     uint32_t len = 67 * 4 * W.n;
-    if (W.hardened) {   // the statement: which ring, which message, which R, which committed key (sha256.h: sha_put_gk_statement_head, then R and keyXcom as points)
+    if (W.gk_stmt == GK_STMT_MEMBER) {   // sha256.h: sha_put_member_statement_head, then com (list slot 4 n count + p) as a point
+        ShaBytes sink{m + len};
+        sha_put_member_statement_head(sink, W.ring_digest, msg + 32 * (size_t)p);
+        len += 21 + 32 + 32;
+        m[len] = 4;
+        words_from_limbs<9>(w, soa_ld<ModT, 1>(W.lc.ax, 4 * W.n * count + p).l);
+        exph_put_coord<9>(m + len + 1, w);
+        words_from_limbs<9>(w, soa_ld<ModT, 1>(W.lc.ay, 4 * W.n * count + p).l);
+        exph_put_coord<9>(m + len + 34, w);
+        len += 67;
+    } else if (W.gk_stmt == GK_STMT_FULL) {   // the statement: which ring, which message, which R, which committed key (sha256.h: sha_put_gk_statement_head, then R and keyXcom as points)
         const char tag[] = "ZKAttest-GK-statement-v1";
         for (int i = 0; i < 24; i++) m[len + i] = (uint8_t)tag[i];
         len += 24;
@@ -394,14 +407,11 @@ __global__ void __launch_bounds__(256) k_gk_msg(Workspace W, uint32_t count, con
         exph_put_coord<9>(m + len + 34, w);
         len += 67;
     }
-    m[len] = 0x80;   // padding: 0x80, zeros, the bit length in eight bytes
-    for (uint32_t i = len + 1; i < nblk * 64 - 8; i++) m[i] = 0;
-    const uint64_t bits = (uint64_t)len * 8;
-    for (int i = 0; i < 8; i++) m[nblk * 64 - 1 - i] = (uint8_t)(bits >> (8 * i));
+    sha_put_padding(m, len, nblk);   // 0x80, zeros, the bit length in eight bytes
 }
 void launch_gk_hash(hipStream_t s, const Workspace& W, uint32_t count, const uint8_t* msg) {
     if (count <= W.exph_cap && W.exph_wk && count <= 512 && !getenv_exph_one_lane()) {
-        const uint32_t len = 67 * 4 * W.n + (W.hardened ? 24 + 32 + 32 + 65 + 67 : 0), nblk = (len + 9 + 63) / 64;
+        const uint32_t nblk = gk_hash_blocks(W.n, W.gk_stmt);   // (sha256.h: 67 * 4 n bytes, + 220 in hardened mode, + 152 for a bound membership proof)
         if (nblk <= (2 * 67 + W.sec * (65 + 2 * 67) + 9 + 63) / 64) {   // (the buffers were carved for the Exp challenge's blocks)
             hipLaunchKernelGGL(k_gk_msg, dim3((count * (4 * W.n + 1) + 255) / 256), dim3(256), 0, s, W, count, msg, nblk);
             launch_sha_msgs(s, W, count, W.gk_x, nblk, 3);

@@ -40,7 +40,7 @@ __global__ void __launch_bounds__(64) k_m_front(Workspace W, uint32_t count, con
 void launch_m_front(hipStream_t s, const Workspace& W, uint32_t count, const uint32_t* which, const uint8_t* blinder, uint64_t first, uint32_t* which_s) {
     hipLaunchKernelGGL(k_m_front, dim3((count + 63) / 64), dim3(64), 0, s, W, count, which, blinder, first, which_s);
 }
-// Everything of a proof's slot that k_gk_respond / k_write_gk_points do not write: the 16 header bytes (or zeros over the whole slot where the status is
+// Everything of a proof's slot that k_gk_respond / k_write_gk_points do not write: the 16 header bytes (W.wire.magic: "ZKM1", or "ZKMB" in a bound call; or zeros over the whole slot where the status is
 // not 0), the commitment, the blinder, the status.  One workgroup per proof.  W.out_base[p] = p * size is written here too, before the GKProof's writers run.
 // A window of a mixed-ring call (S.sel): entry first + p of the window is proof S.sel[first + p] of the batch -- its slot starts at that proof's place in the
 // batch's offsets (out = the batch's buffer), com, blinder and status go to that index: every byte is written once, at its final place.  An entry that is
@@ -62,7 +62,7 @@ __global__ void __launch_bounds__(64) k_m_write_head(Workspace W, uint32_t count
     if (st != ZK_OK) {
         for (uint32_t i = t; i < size / 4; i += 64) slot[i] = 0;
     } else if (t < 4) {
-        slot[t] = t == 0 ? ZK_MAGIC_ZKM1 : t == 1 ? bswap32(size) : t == 2 ? bswap32(W.n) : 0;
+        slot[t] = t == 0 ? W.wire.magic : t == 1 ? bswap32(size) : t == 2 ? bswap32(W.n) : 0;
     }
     if (t == 0) {
         W.out_base[p] = base;
@@ -88,6 +88,7 @@ ZK_DEV bool m_tom_bytes_valid(const uint8_t* p) {  // edwards.ts:204-209 afterJs
 }
 // The ZKM1 header (one thread per proof): proofs are `size` bytes apart.  Fills the fields the GK kernels of k_verify.hip read: st, okflags (bit 3: the header's n
 // is not the ring's -- verifyMembership returns false, gk.ts:208-218 --, the header's n above it), zcnt = 0.  total_len must be the length n announces.
+// The magic is exactly the call's: "ZKMB" in a bound call (V.gk_stmt), "ZKM1" in an unbound one.
 // (slot != 0: a window of a mixed-ring call -- off holds the gathered starts of slots that the classing kernel found `slot` bytes long)
 __global__ void __launch_bounds__(256) k_mv_header(VWork V, uint32_t count, const uint8_t* proofs, const uint64_t* off, uint64_t first, uint32_t slot) {
     const uint32_t p = gtid();
@@ -97,7 +98,7 @@ __global__ void __launch_bounds__(256) k_mv_header(VWork V, uint32_t count, cons
     const uint32_t total = bswap32(h[1]), n = bswap32(h[2]);
     int32_t st = ZK_OK;
     uint32_t flags = 0;
-    if (h[0] != ZK_MAGIC_ZKM1 || h[3] != 0 || n > 63 || total != zkm1_size(n)) st = ZK_E_BAD_ENCODING;
+    if (h[0] != (V.gk_stmt == GK_STMT_MEMBER ? ZK_MAGIC_ZKMB : ZK_MAGIC_ZKM1) || h[3] != 0 || n > 63 || total != zkm1_size(n)) st = ZK_E_BAD_ENCODING;
     else if (n != V.n) flags = 8 | (n << 16);   // (its total_len is the one ITS n announces; the slot is the ring's size)
     else if (total != o1 - o0) st = ZK_E_BAD_ENCODING;
     V.st[p] = st, V.okflags[p] = flags, V.zcnt[p] = 0;

@@ -88,10 +88,12 @@ ZK_DEV uint2 mr_load8(const uint8_t* __restrict__ s, bool al) {
     return make_uint2(w[0], w[1]);
 }
 // prover: window entry j = proof sel[j].  8 threads per entry: `which`, two 16-byte pieces of the blinder (blinder == nullptr: the engine draws it), two
-// of the seed (seeds == nullptr in stream mode: k_pr_gather_rows moves the rows).  Consecutive threads write consecutive pieces of the window's arrays.
+// of the seed (seeds == nullptr in stream mode: k_pr_gather_rows moves the rows), two of the context (a bound call).  Consecutive threads write consecutive
+// pieces of the window's arrays.
 __global__ void __launch_bounds__(256) k_mr_pgather(uint32_t n, uint64_t B, const uint32_t* __restrict__ sel, const uint32_t* __restrict__ which,
-                                                    const uint8_t* __restrict__ blinder, const uint8_t* __restrict__ seeds, uint32_t al, uint32_t* __restrict__ w_which,
-                                                    uint8_t* __restrict__ w_blinder, uint8_t* __restrict__ w_seeds) {
+                                                    const uint8_t* __restrict__ blinder, const uint8_t* __restrict__ seeds, const uint8_t* __restrict__ context, uint32_t al,
+                                                    uint32_t* __restrict__ w_which, uint8_t* __restrict__ w_blinder, uint8_t* __restrict__ w_seeds,
+                                                    uint8_t* __restrict__ w_context) {
     const uint32_t t = gtid();
     if (t >= 8 * n) return;
     const uint32_t j = t >> 3, q = t & 7;
@@ -102,13 +104,16 @@ __global__ void __launch_bounds__(256) k_mr_pgather(uint32_t n, uint64_t B, cons
         if (blinder) ((uint4*)(w_blinder + 32 * (size_t)j))[q - 1] = mr_load16(blinder + 32 * b + 16 * (q - 1), al & 1);
     } else if (q < 5) {
         if (seeds) ((uint4*)(w_seeds + 32 * (size_t)j))[q - 3] = mr_load16(seeds + 32 * b + 16 * (q - 3), al & 2);
+    } else if (q < 7) {
+        if (context) ((uint4*)(w_context + 32 * (size_t)j))[q - 5] = mr_load16(context + 32 * b + 16 * (q - 5), al & 4);
     }
 }
 // verifier: 16 threads per entry -- nine 8-byte pieces of com (72 bytes: an entry of the window starts on a multiple of 8), two 16-byte pieces of the
-// verifier's seed, the slot's offset.  The proof bytes stay where they are: the GK kernels read them through the window's offsets.
+// verifier's seed, the slot's offset, two 16-byte pieces of the context (a bound call).  The proof bytes stay where they are: the GK kernels read them through
+// the window's offsets.
 __global__ void __launch_bounds__(256) k_mr_vgather(uint32_t n, uint64_t B, const uint32_t* __restrict__ sel, const uint64_t* __restrict__ proof_off,
-                                                    const uint8_t* __restrict__ com, const uint8_t* __restrict__ seeds, uint32_t al, uint64_t* __restrict__ w_off,
-                                                    uint8_t* __restrict__ w_com, uint8_t* __restrict__ w_seeds) {
+                                                    const uint8_t* __restrict__ com, const uint8_t* __restrict__ seeds, const uint8_t* __restrict__ context, uint32_t al,
+                                                    uint64_t* __restrict__ w_off, uint8_t* __restrict__ w_com, uint8_t* __restrict__ w_seeds, uint8_t* __restrict__ w_context) {
     const uint32_t t = gtid();
     if (t >= 16 * n) return;
     const uint32_t j = t >> 4, q = t & 15;
@@ -117,6 +122,9 @@ __global__ void __launch_bounds__(256) k_mr_vgather(uint32_t n, uint64_t B, cons
     if (q < 9) ((uint2*)(w_com + 72 * (size_t)j))[q] = mr_load8(com + 72 * b + 8 * q, al & 1);
     else if (q < 11) ((uint4*)(w_seeds + 32 * (size_t)j))[q - 9] = mr_load16(seeds + 32 * b + 16 * (q - 9), al & 2);
     else if (q == 11) w_off[j] = proof_off[b];
+    else if (q < 14) {
+        if (context) ((uint4*)(w_context + 32 * (size_t)j))[q - 12] = mr_load16(context + 32 * b + 16 * (q - 12), al & 4);
+    }
 }
 
 void launch_mr_class(hipStream_t s, uint64_t B, const uint32_t* ring_ids, const MrRings& R, const uint64_t* proof_off, uint8_t* cls, uint32_t* blk_cnt, uint32_t* out,
@@ -133,13 +141,13 @@ void launch_mr_offsets(hipStream_t s, uint64_t B, const uint8_t* cls, const uint
     hipLaunchKernelGGL(k_mr_offsets, dim3((uint32_t)((B + MR_BLOCK - 1) / MR_BLOCK)), dim3(MR_BLOCK), 0, s, B, cls, blk_base, R, out_off, com, blinder_out, status);
 }
 static uint32_t mr_aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-void launch_mr_pgather(hipStream_t s, uint32_t n, uint64_t B, const uint32_t* sel, const uint32_t* which, const uint8_t* blinder, const uint8_t* seeds, uint32_t* w_which,
-                       uint8_t* w_blinder, uint8_t* w_seeds) {
-    const uint32_t al = mr_aligned(blinder, 16) | mr_aligned(seeds, 16) << 1;
-    if (n) hipLaunchKernelGGL(k_mr_pgather, dim3((8 * n + 255) / 256), dim3(256), 0, s, n, B, sel, which, blinder, seeds, al, w_which, w_blinder, w_seeds);
+void launch_mr_pgather(hipStream_t s, uint32_t n, uint64_t B, const uint32_t* sel, const uint32_t* which, const uint8_t* blinder, const uint8_t* seeds, const uint8_t* context,
+                       uint32_t* w_which, uint8_t* w_blinder, uint8_t* w_seeds, uint8_t* w_context) {
+    const uint32_t al = mr_aligned(blinder, 16) | mr_aligned(seeds, 16) << 1 | mr_aligned(context, 16) << 2;
+    if (n) hipLaunchKernelGGL(k_mr_pgather, dim3((8 * n + 255) / 256), dim3(256), 0, s, n, B, sel, which, blinder, seeds, context, al, w_which, w_blinder, w_seeds, w_context);
 }
-void launch_mr_vgather(hipStream_t s, uint32_t n, uint64_t B, const uint32_t* sel, const uint64_t* proof_off, const uint8_t* com, const uint8_t* seeds, uint64_t* w_off,
-                       uint8_t* w_com, uint8_t* w_seeds) {
-    const uint32_t al = mr_aligned(com, 8) | mr_aligned(seeds, 16) << 1;
-    if (n) hipLaunchKernelGGL(k_mr_vgather, dim3((16 * n + 255) / 256), dim3(256), 0, s, n, B, sel, proof_off, com, seeds, al, w_off, w_com, w_seeds);
+void launch_mr_vgather(hipStream_t s, uint32_t n, uint64_t B, const uint32_t* sel, const uint64_t* proof_off, const uint8_t* com, const uint8_t* seeds, const uint8_t* context,
+                       uint64_t* w_off, uint8_t* w_com, uint8_t* w_seeds, uint8_t* w_context) {
+    const uint32_t al = mr_aligned(com, 8) | mr_aligned(seeds, 16) << 1 | mr_aligned(context, 16) << 2;
+    if (n) hipLaunchKernelGGL(k_mr_vgather, dim3((16 * n + 255) / 256), dim3(256), 0, s, n, B, sel, proof_off, com, seeds, context, al, w_off, w_com, w_seeds, w_context);
 }

@@ -433,10 +433,13 @@ __global__ void __launch_bounds__(64) k_v_challenges(VWork V, uint32_t count, co
     if (good) {
         const uint8_t* gk = v_gk_base(V, pr, p);
         for (uint32_t k = 0; k < 4 * V.n; k++) absorb_tom_bytes(s, gk + 72 * k);
-        if (V.hardened) {   // the statement binds the challenge (k_hash.hip: k_gk_hash)
+        if (V.gk_stmt == GK_STMT_FULL) {   // the statement binds the challenge (k_hash.hip: k_gk_hash)
             sha_put_gk_statement_head(s, V.ring_digest, msg + 32 * (first + p));
             absorb_p256_bytes(s, pr + 32);
             absorb_tom_bytes(s, pr + 160);
+        } else if (V.gk_stmt == GK_STMT_MEMBER) {   // a "ZKMB" proof: its ring's digest, the caller's context (msg), the commitment it is shown with
+            sha_put_member_statement_head(s, V.ring_digest, msg + 32 * (first + p));
+            absorb_tom_bytes(s, V.com + 72 * (first + p));
         }
     }
     s.finish(h);

@@ -23,7 +23,8 @@ void launch_mr_class(hipStream_t s, uint64_t B, const uint32_t* ring_ids, const 
 void launch_mr_perm(hipStream_t s, uint64_t B, const uint8_t* cls, const uint32_t* blk_base, const uint32_t* out, uint32_t* perm);
 void launch_mr_offsets(hipStream_t s, uint64_t B, const uint8_t* cls, const uint32_t* blk_base, const MrRings& R, uint64_t* out_off, uint8_t* com, uint8_t* blinder_out,
                        int32_t* status);
-void launch_mr_pgather(hipStream_t s, uint32_t n, uint64_t B, const uint32_t* sel, const uint32_t* which, const uint8_t* blinder, const uint8_t* seeds, uint32_t* w_which,
-                       uint8_t* w_blinder, uint8_t* w_seeds);
-void launch_mr_vgather(hipStream_t s, uint32_t n, uint64_t B, const uint32_t* sel, const uint64_t* proof_off, const uint8_t* com, const uint8_t* seeds, uint64_t* w_off,
-                       uint8_t* w_com, uint8_t* w_seeds);
+// context != nullptr (a bound call): the window also collects its proofs' 32 context bytes, entry j = context of proof sel[j]
+void launch_mr_pgather(hipStream_t s, uint32_t n, uint64_t B, const uint32_t* sel, const uint32_t* which, const uint8_t* blinder, const uint8_t* seeds, const uint8_t* context,
+                       uint32_t* w_which, uint8_t* w_blinder, uint8_t* w_seeds, uint8_t* w_context);
+void launch_mr_vgather(hipStream_t s, uint32_t n, uint64_t B, const uint32_t* sel, const uint64_t* proof_off, const uint8_t* com, const uint8_t* seeds, const uint8_t* context,
+                       uint64_t* w_off, uint8_t* w_com, uint8_t* w_seeds, uint8_t* w_context);

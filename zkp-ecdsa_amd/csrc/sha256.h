@@ -131,3 +131,40 @@ ZK_DEV void sha_put_gk_statement_head(ShaStream& s, const uint32_t* ring_digest8
     for (int i = 0; i < 32; i++) s.put_byte(msg32[i]);
 }
 
+// Which statement the Groth-Kohlweiss challenge hashes behind its 4 n points (Workspace / VWork: gk_stmt): none (the reference, gk.ts:178-180), the full
+// proof's in hardened mode (above), or a bound membership proof's ("ZKMB", include/zkattest.h: zk_member_*_bound) --
+//   "ZKAttest-GK-member-v1" (21) || ring digest (32) || context (32) || com in its hashPoints encoding (67): 152 bytes.
+#define GK_STMT_NONE 0u
+#define GK_STMT_FULL 1u
+#define GK_STMT_MEMBER 2u
+#define GK_MEMBER_TAG "ZKAttest-GK-member-v1"
+ZK_HOSTDEV uint32_t gk_stmt_bytes(uint32_t stmt) { return stmt == GK_STMT_FULL ? 24 + 32 + 32 + 65 + 67 : stmt == GK_STMT_MEMBER ? 21 + 32 + 32 + 67 : 0; }
+// the hashed message of a ring of 2^n keys and how many 64-byte blocks it pads to (0x80, zeros, eight length bytes)
+ZK_HOSTDEV uint32_t gk_hash_len(uint32_t n, uint32_t stmt) { return 67 * 4 * n + gk_stmt_bytes(stmt); }
+ZK_HOSTDEV uint32_t gk_hash_blocks(uint32_t n, uint32_t stmt) { return (gk_hash_len(n, stmt) + 9 + 63) / 64; }
+// The bound membership statement up to the commitment -- tag || ring digest || the caller's 32 context bytes --, into anything that takes bytes (a ShaStream,
+// or k_gk_msg's message buffer through ShaBytes); the caller then puts com as a point.
+struct ShaBytes {
+    uint8_t* p;
+    ZK_DEV void put_byte(uint32_t b) { *p++ = (uint8_t)b; }
+};
+template <class Sink>
+ZK_DEV void sha_put_member_statement_head(Sink& s, const uint32_t* ring_digest8, const uint8_t* context32) {
+    const char tag[] = GK_MEMBER_TAG;
+#pragma unroll 1
+    for (int i = 0; i < 21; i++) s.put_byte((uint8_t)tag[i]);
+#pragma unroll 1
+    for (int i = 0; i < 8; i++) {
+        uint32_t w = ring_digest8[i];
+        s.put_byte(w >> 24), s.put_byte(w >> 16), s.put_byte(w >> 8), s.put_byte(w);
+    }
+#pragma unroll 1
+    for (int i = 0; i < 32; i++) s.put_byte(context32[i]);
+}
+// padding of a message of len bytes written out in nblk blocks
+ZK_DEV void sha_put_padding(uint8_t* m, uint32_t len, uint32_t nblk) {
+    m[len] = 0x80;
+    for (uint32_t i = len + 1; i < nblk * 64 - 8; i++) m[i] = 0;
+    const uint64_t bits = (uint64_t)len * 8;
+    for (int i = 0; i < 8; i++) m[nblk * 64 - 1 - i] = (uint8_t)(bits >> (8 * i));
+}

@@ -43,6 +43,8 @@ ZK_HD static inline uint64_t wire_proof_size(const Wire& w, uint32_t sec, uint32
 // (4 n Tom points of 72 bytes, 3 n + 1 scalars).  Fixed per ring.
 #define ZKM1_HDR 16
 #define ZK_MAGIC_ZKM1 0x314d4b5au
+// "ZKMB": the same bytes under the magic of a BOUND membership proof, whose challenge also hashes ring digest, caller context and com (sha256.h: GK_STMT_MEMBER)
+#define ZK_MAGIC_ZKMB 0x424d4b5au
 ZK_HD static inline uint64_t zkm1_size(uint32_t n) { return (uint64_t)ZKM1_HDR + 288ull * n + 32ull * (3ull * n + 1); }
 // Per-proof verify levels (zk_ctx_set_verify_level): the level a proof of o1 - o0 bytes at `pr` announces, 0..ZK_MAXSEC, or ZK_LV_BAD where the
 // header alone already makes it ZK_E_BAD_ENCODING in the pipeline at ANY level (short, misaligned, wrong magic, a length that is not the header's,

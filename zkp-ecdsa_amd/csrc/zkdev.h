@@ -7,6 +7,7 @@
 #include <stdint.h>
 #ifdef ZK_HOST_BUILD
 #define ZK_DEV inline
+#define ZK_HOSTDEV inline
 #define ZK_DEV_NOINLINE
 #define ZK_CONSTANT static const
 // zk_opaque_v / zk_opaque_s (see the device definitions below): registers of the GPU, nothing here
@@ -22,6 +23,7 @@ ZK_DEV uint32_t zk_maj(uint32_t a, uint32_t b, uint32_t c) { return (a & b) | (c
 #else
 #include <hip/hip_runtime.h>
 #define ZK_DEV __device__ __forceinline__
+#define ZK_HOSTDEV __host__ __device__ inline   // sizes that a launch wrapper and its kernel must agree on
 #define ZK_DEV_NOINLINE __device__ __noinline__
 #define ZK_CONSTANT __constant__
 // Opaque to the optimiser, no instruction: the values pass through an empty asm statement as VGPR (_v) or SGPR (_s) operands, so no pass sees what they
