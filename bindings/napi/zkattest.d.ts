@@ -44,6 +44,12 @@ export function verifySignatureLists(params: SystemParametersList, msgHashes: Ui
 /** B statements over several rings in one call, proved: keyLists[i] is the ring of proof i and whichs[i] indexes it (zk_prove_batch_rings).  The rings stay resident
  *  through the cache verifySignatureLists uses; a call is split only when it names more rings than residentRings. */
 export function proveSignatureLists(params: SystemParametersList, msgHashes: Uint8Array[], sigs: Uint8Array[], publicKeys: PublicKey[], whichs: number[], keyLists: (bigint[] | Buffer)[]): Promise<SignatureProofList[]>
+/** re-ring (zk_proof_rering_batch): proofs made for any ring become proofs for `keys` with their signature part untouched -- only the GKProof section is made anew,
+ *  over the same keyXcom.  whichNew[i]: the index of proof i's key in `keys`; keyBlinders[i]: the blinder of its keyXcom (keyBlinders).  Throws for the first proof
+ *  that fails.  Two GKProofs over one keyXcom place the key in the intersection of the two rings. */
+export function reringSignatureLists(params: SystemParametersList, msgHashes: Uint8Array[], proofs: (SignatureProofList | Buffer)[], whichNew: number[], keyBlinders: Uint8Array[], keys: bigint[] | Buffer): Promise<SignatureProofList[]>
+/** zk_prove_key_blinders: the blinders of keyXcom in the proofs made from `seeds` (B x 32 bytes, or one Uint8Array(32) per proof); as secret as the seeds */
+export function keyBlinders(seeds: Buffer | Uint8Array[], params?: SystemParametersList): Promise<Buffer[]>
 /** the witness screen (zk_screen_batch_rings): before a proof is paid for, where the signer's key stands in `keys` (`which` absent: the lowest index is found; given: that
  *  index is checked) and whether the ECDSA signature verifies.  flags is a set of SCREEN bits; ok = (flags === 0) means proveSignatureList with `which` gives a proof that
  *  verifies.  SCREEN.SIG_RANGE (r or s outside [1, n - 1]) is stricter than the prover, which reduces them mod n. */
@@ -129,6 +135,10 @@ export class Engine {
     /** zk_prove_batch_rings: which[b] indexes resident ring ringIds[b]; the active ring plays no part */
     proveBatchRings(msg: Buffer, sig: Buffer, pk: Buffer, which: number[] | Buffer, ringIds: number[] | Uint32Array, seeds?: Buffer): Buffer[]
     proveBatchRingsAsync(msg: Buffer, sig: Buffer, pk: Buffer, which: number[] | Buffer, ringIds: number[] | Uint32Array, seeds?: Buffer): Promise<Buffer[]>
+    /** zk_prove_key_blinders: keyXcom's blinder of the proof made from each 32-byte seed */
+    keyBlinders(seeds: Buffer): Buffer[]
+    /** zk_proof_rering_batch: proofs moved to the ACTIVE ring; seeds must be fresh (default: crypto.randomBytes).  status 16: the index and blinder do not open keyXcom */
+    reringBatch(msg: Buffer, proofs: Buffer[], whichNew: number[] | Uint32Array, blinders: Buffer, seeds?: Buffer): { proofs: (Buffer | null)[]; status: Int32Array }
     keysToInts(pkxy: Buffer): { keys: Buffer; status: Buffer }
     proveBatch(msg: Buffer, sig: Buffer, pk: Buffer, which: number[] | Buffer, seeds?: Buffer): Buffer[]
     verifyBatch(msg: Buffer, proofs: Buffer[], seeds?: Buffer): Verdicts

@@ -20,7 +20,8 @@ const path = require('path')
 const native = require(process.env.ZKATTEST_NODE || path.join(__dirname, 'zkattest.node'))
 
 const STATUS_TEXT = { 1: 'point not in group', 2: 'invalid public key', 3: 'T[i] is at infinity', 4: 'T1 is at infinity', 5: 'P/Q/R is at infinity',
-    6: "Points don't add up!", 7: 'R is at infinity', 8: 'params not found', 9: 'security level not achieved', 10: 'error deserializing' }
+    6: "Points don't add up!", 7: 'R is at infinity', 8: 'params not found', 9: 'security level not achieved', 10: 'error deserializing',
+    11: 'randomness stream exhausted', 16: "the index and blinder do not open the proof's key commitment" }
 // The two places where the reference dies with a TypeError of the JavaScript runtime instead of one of its own errors (include/zkattest.h):
 // `which` past the padded ring reads values[index].k of undefined (src/proofGK/gk.ts:162, engine status 14), and a ring of ONE key pads to
 // length 1, n = 0, where interpolate([], []) evaluates -x[0] % m with x[0] undefined (src/proofGK/interpolate.ts:40).
@@ -424,6 +425,21 @@ class Engine {
         const r = context ? native.memberVerifyBatchRingsBound(this.h, Buffer.concat(coms), Buffer.concat(proofs), off, ids, context) : native.memberVerifyBatchRings(this.h, Buffer.concat(coms), Buffer.concat(proofs), off, ids)
         return { ok: Array.from(r.ok, (v) => v === 1), status: i32(r.status) }
     }
+    // re-ring (zk_prove_key_blinders, zk_proof_rering_batch).  keyBlinders: seeds (B x 32 bytes) -> Buffer[] of keyXcom's blinders, as secret as the seeds.
+    keyBlinders(seeds) {
+        const r = native.keyBlinders(this.h, seeds)
+        return Array.from({ length: seeds.length / 32 }, (_, i) => r.slice(32 * i, 32 * i + 32))
+    }
+    // proofs (Buffers in the engine's wire layout) moved to the ACTIVE ring: -> { proofs: Buffer | null per entry, status: Int32Array }.  seeds must be FRESH:
+    // never the ones the proofs were made with (default: crypto.randomBytes)
+    reringBatch(msg, proofs, whichNew, blinders, seeds) {
+        const B = proofs.length, off = Buffer.alloc(8 * (B + 1))
+        let run = 0
+        proofs.forEach((p, i) => { run += p.length; off.writeBigUInt64LE(BigInt(run), 8 * (i + 1)) })
+        const r = native.reringBatch(this.h, msg, Buffer.concat(proofs), off, Buffer.from(Uint32Array.from(whichNew).buffer), blinders, seeds || crypto.randomBytes(32 * B))
+        const st = i32(r.status), o = u64(r.off)
+        return { proofs: Array.from(st, (s, i) => (s === 0 ? r.proofs.slice(Number(o[i]), Number(o[i + 1])) : null)), status: st }
+    }
     proveBatchRingsAsync(msg, sig, pk, which, ringIds, seeds) { return this._chain(() => this._proveRingsNow(msg, sig, pk, which, ringIds, seeds)) }
     verifyBatchRingsAsync(msg, proofs, ringIds, seeds) { return this._chain(() => this._verifyRingsNow(msg, proofs, ringIds, seeds)) }
     proveBatchAsync(msg, sig, pk, which, seeds) { return this._chain(() => this._proveNow(msg, sig, pk, which, seeds)) }
@@ -482,6 +498,7 @@ function engineFor(params, keys) {
         slot = { engine, rings: new Map(), active: null, bufs: new Map() }   // rings: ring tag -> resident ring id, least recently used first; bufs: ring tag -> key bytes (ringDelta)
         engines.set(key, slot)
     }
+    if (keys === null) return { engine: slot.engine, run: (job) => slot.engine.run(() => job(slot.engine)) }   // a call that reads no ring (keyBlinders)
     const ring = ringOf(keys)
     // one queued unit per call: make the ring resident and active (table E and the rest: once per key ring while it stays among the engine's
     // `residentRings` most recently used), then run the batch; units of one engine run strictly one after the other, so interleaved callers with
@@ -664,6 +681,38 @@ async function verifySignatureListBatch(params, msgHashes, keys, proofs) {
     }
     Object.defineProperty(out, 'errors', { value: errors })
     return out
+}
+// Re-ring (include/zkattest.h: zk_proof_rering_batch): proofs made for any ring become proofs for `keys` -- after a registry update, for a second registry, for
+// a larger ring -- without their signature part being touched: only the GKProof section is made anew, over the same keyXcom.  whichNew[i]: the index of proof
+// i's key in `keys`; keyBlinders[i]: the blinder of its keyXcom (keyBlinders below, 32 bytes).  The signature is not needed.  -> SignatureProofList[] in the order
+// given, in each proof's own wire layout; throws for the first proof that fails: 'error deserializing', the reference's TypeError for an index past the padded
+// ring, or "the index and blinder do not open the proof's key commitment".  The engine draws fresh seeds (crypto.randomBytes).  Two GKProofs over one keyXcom
+// tell a verifier who sees both that the key lies in the intersection of the two rings (INTEGRATION.md).
+async function reringSignatureLists(params, msgHashes, proofs, whichNew, keyBlinders, keys) {
+    const B = msgHashes.length
+    if (proofs.length !== B || whichNew.length !== B || keyBlinders.length !== B) throw new RangeError('reringSignatureLists: one proof, one index and one blinder per message hash')
+    const raw = proofs.map((p) => (p instanceof SignatureProofList ? p.bytes : p))
+    for (const b of raw) if (!wellFormedProof(b)) throw new Error('error deserializing')
+    for (const k of keyBlinders) if (!((Buffer.isBuffer(k) || k instanceof Uint8Array) && k.length === 32)) throw new TypeError('a key blinder is a Uint8Array(32)')
+    checkRingSize(Buffer.isBuffer(keys) ? keys.length / 32 : keys.length, true)
+    const idx = [[], []], out = new Array(B)   // a context works in ONE layout at a time: split by the proofs' magic like the verifier
+    raw.forEach((b, i) => idx[isPacked(b) ? 1 : 0].push(i))
+    for (const wire of [0, 1]) {
+        const sel = idx[wire]
+        if (!sel.length) continue
+        const msg = Buffer.concat(sel.map((i) => Buffer.from(msgHashes[i]))), bl = Buffer.concat(sel.map((i) => Buffer.from(keyBlinders[i])))
+        const r = await engineFor(params, keys).withRing((engine) => { useWire(engine, wire); return engine.reringBatch(msg, sel.map((i) => raw[i]), sel.map((i) => whichNew[i]), bl) })
+        sel.forEach((i, k) => { if (r.status[k] !== 0) throw statusError(r.status[k]); out[i] = new SignatureProofList(r.proofs[k]) })
+    }
+    return out
+}
+// The blinders of keyXcom in the proofs made from `seeds` (a Buffer of B x 32 bytes, or an array of 32-byte seeds): what reringSignatureLists needs later.  A
+// prover that wants to re-ring keeps its seeds (Engine.proveBatch takes them) or these blinders beside the proofs; they are as secret as the seeds.  -> Buffer[]
+async function keyBlinders(seeds, params = lastParams) {
+    const buf = Buffer.isBuffer(seeds) ? seeds : Buffer.concat(Array.from(seeds, (s) => Buffer.from(s)))
+    if (buf.length % 32) throw new RangeError('keyBlinders: 32 bytes per seed')
+    if (!params) throw new Error('keyBlinders: no parameters yet (pass a SystemParametersList)')
+    return engineFor(params, null).run((engine) => engine.keyBlinders(buf))
 }
 // B statements over several rings in one call, proved: keyLists[i] is the ring of proof i and whichs[i] indexes it -- the reference's proveSignatureList takes
 // `keys` with every call (src/zkpAttestList.ts:104-145), this is that interface over a batch.  The rings are kept resident through the cache
@@ -970,6 +1019,6 @@ async function verifyMembershipLists(pedersenParams, comPoints, keysList, proofs
     return out
 }
 
-module.exports = { proveMembership, verifyMembership, proveMemberships, verifyMemberships, proveMembershipLists, verifyMembershipLists, GKProof, Commitment, commit, screenSignatureLists, findKey, SCREEN, WHICH_NONE, recoverSignatureLists, recoverKey, RECOVER, verifySignatureLists, proveSignatureLists, _ringGenerations, setVerifyLevel, getVerifyLevel, setVerifyReps, getVerifyReps, generateParamsList, generateParamsListHardened, keyToInt, proveSignatureList, verifySignatureList, proveSignatureListBatch, verifySignatureListBatch,
+module.exports = { reringSignatureLists, keyBlinders, proveMembership, verifyMembership, proveMemberships, verifyMemberships, proveMembershipLists, verifyMembershipLists, GKProof, Commitment, commit, screenSignatureLists, findKey, SCREEN, WHICH_NONE, recoverSignatureLists, recoverKey, RECOVER, verifySignatureLists, proveSignatureLists, _ringGenerations, setVerifyLevel, getVerifyLevel, setVerifyReps, getVerifyReps, generateParamsList, generateParamsListHardened, keyToInt, proveSignatureList, verifySignatureList, proveSignatureListBatch, verifySignatureListBatch,
     writeJson, readJson, writeJsonBatch, readJsonBatch, SignatureProofList, SystemParametersList, PedersenParams, generatePedersenParams, p256, tomEdwards256, ALL_GROUPS,
     Group, Point, Scalar, Engine, shutdown, setWireLayout, getWireLayout, setOption, native }

@@ -1252,6 +1252,71 @@ static napi_value member_verify_rings(napi_env env, napi_callback_info info, int
 static napi_value MemberVerifyBatchRings(napi_env env, napi_callback_info info) { return member_verify_rings(env, info, 0); }
 static napi_value MemberVerifyBatchRingsBound(napi_env env, napi_callback_info info) { return member_verify_rings(env, info, 1); }
 
+/* Re-ring (include/zkattest.h: zk_prove_key_blinders, zk_proof_rering_batch), on the pool's first context like the member calls; the target is the ACTIVE ring,
+ * which the facade made so.  (h, seeds: B x 32) -> blinders: B x 32, keyXcom's blinder of the proof made from each seed */
+static napi_value KeyBlinders(napi_env env, napi_callback_info info) {
+    napi_value argv[2];
+    if (!get_args(env, info, 2, argv)) return NULL;
+    Handle *h = get_handle(env, argv[0], 0);
+    uint8_t *seeds;
+    size_t ls;
+    if (!h || !get_bytes(env, argv[1], &seeds, &ls)) return NULL;
+    const size_t B = ls / 32;
+    if (ls % 32) {
+        napi_throw_range_error(env, NULL, "keyBlinders: 32 seed bytes per proof");
+        return NULL;
+    }
+    zk_ctx *c = zk_pool_ctx(h->pool, 0);
+    uint8_t *out = (uint8_t *)xmalloc(env, 32 * B + 8);
+    if (!out) return NULL;
+    zk_rng rng = {ZK_RNG_SEED, seeds, 0};
+    zk_status st = zk_prove_key_blinders(c, B, &rng, out);
+    napi_value v = NULL;
+    if (st != ZK_OK) throw_text(env, st, zk_last_error(c));
+    else v = new_buffer(env, out, 32 * B);
+    memset(out, 0, 32 * B + 8);
+    free(out);
+    return v;
+}
+/* (h, msg: B x 32, proofs: the B proofs back to back, off: (B + 1) u64 LE, whichNew: B u32 LE, blinders: B x 32, seeds: B x 32 -- FRESH) ->
+ * {proofs: the re-ringed proofs back to back, off: (B + 1) u64 LE, status: B i32 LE} */
+static napi_value ReringBatch(napi_env env, napi_callback_info info) {
+    napi_value argv[7];
+    if (!get_args(env, info, 7, argv)) return NULL;
+    Handle *h = get_handle(env, argv[0], 0);
+    uint8_t *msg, *blob, *ob, *wb, *bl, *seeds;
+    size_t lm, lp, lo, lw, lb, ls;
+    if (!h || !get_bytes(env, argv[1], &msg, &lm) || !get_bytes(env, argv[2], &blob, &lp) || !get_bytes(env, argv[3], &ob, &lo) || !get_bytes(env, argv[4], &wb, &lw) ||
+        !get_bytes(env, argv[5], &bl, &lb) || !get_bytes(env, argv[6], &seeds, &ls))
+        return NULL;
+    const size_t B = lw / 4;
+    if (lw % 4 || lm != 32 * B || lb != 32 * B || ls != 32 * B || lo != 8 * (B + 1)) {
+        napi_throw_range_error(env, NULL, "reringBatch: per proof 32 message bytes, one u32 index, 32 blinder bytes and 32 seed bytes; B + 1 offsets");
+        return NULL;
+    }
+    zk_ctx *c = zk_pool_ctx(h->pool, 0);
+    const uint64_t cap = lp + B * zk_member_proof_size(c);   /* every head as it is plus a new GKProof section */
+    const size_t small = 8 * (B + 1) * 2 + 8 * B;
+    uint8_t *buf = (uint8_t *)xmalloc(env, small + cap + 8);   /* (a Buffer's bytes need not be aligned: offsets and indices are copied) */
+    if (!buf) return NULL;
+    uint64_t *off = (uint64_t *)buf, *out_off = off + (B + 1);
+    uint32_t *which = (uint32_t *)(out_off + (B + 1));
+    int32_t *status = (int32_t *)(which + B);
+    uint8_t *out = buf + small;
+    memcpy(off, ob, 8 * (B + 1));
+    if (B) memcpy(which, wb, 4 * B);
+    zk_rng rng = {ZK_RNG_SEED, seeds, 0};
+    zk_status st = zk_proof_rering_batch(c, B, msg, blob, off, which, bl, &rng, out, cap, out_off, status);
+    napi_value v = NULL;
+    if (st != ZK_OK) throw_text(env, st, zk_last_error(c));
+    else if (napi_create_object(env, &v) == napi_ok) {
+        set_prop(env, v, "proofs", new_buffer(env, out, (size_t)out_off[B])), set_prop(env, v, "off", new_buffer(env, out_off, 8 * (B + 1)));
+        set_prop(env, v, "status", new_buffer(env, status, 4 * B));
+    }
+    free(buf);
+    return v;
+}
+
 static napi_value Init(napi_env env, napi_value exports) {
     static const struct {
         const char *name;
@@ -1271,7 +1336,8 @@ static napi_value Init(napi_env env, napi_value exports) {
                {"memberProofSize", MemberProofSize},   {"memberProveBatch", MemberProveBatch}, {"memberVerifyBatch", MemberVerifyBatch},
                {"memberProofSizeRing", MemberProofSizeRing}, {"memberProveBatchRings", MemberProveBatchRings}, {"memberVerifyBatchRings", MemberVerifyBatchRings},
                {"memberProveBatchBound", MemberProveBatchBound}, {"memberVerifyBatchBound", MemberVerifyBatchBound},
-               {"memberProveBatchRingsBound", MemberProveBatchRingsBound}, {"memberVerifyBatchRingsBound", MemberVerifyBatchRingsBound}};
+               {"memberProveBatchRingsBound", MemberProveBatchRingsBound}, {"memberVerifyBatchRingsBound", MemberVerifyBatchRingsBound},
+               {"keyBlinders", KeyBlinders},     {"reringBatch", ReringBatch}};
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;
         if (napi_create_function(env, fns[i].name, NAPI_AUTO_LENGTH, fns[i].fn, NULL, &f) != napi_ok) return NULL;

@@ -64,7 +64,8 @@ enum {
     ZK_E_BUFFER = 12,            /* output buffer too small, or context not configured */
     ZK_E_INTERPOLATION = 13,     /* 'incorrect interpolation'       src/proofGK/interpolate.ts:65 */
     ZK_E_ARG = 14,               /* invalid argument */
-    ZK_E_DEVICE = 15             /* HIP runtime failure (zk_last_error has the text) */
+    ZK_E_DEVICE = 15,            /* HIP runtime failure (zk_last_error has the text) */
+    ZK_E_OPENING = 16            /* zk_proof_rering_batch: ring[which_new] and the blinder do not open the proof's keyXcom */
 };
 
 enum { ZK_RNG_SEED = 0, ZK_RNG_STREAM = 1 };
@@ -595,6 +596,63 @@ zk_status zk_member_verify_batch_rings_bound(zk_ctx *ctx, uint64_t B, const uint
 zk_status zk_member_verify_batch_rings_bound_device(zk_ctx *ctx, uint64_t B, const void *d_com_xy72, const void *d_context, const void *d_proofs,
                                                     const void *d_proof_off /*u64[B+1]*/, const void *d_ring_ids, const void *d_verifier_seeds, void *d_ok,
                                                     void *d_per_proof_status);
+
+/* ---- re-ring: a ZKA1 proof moved to another ring, its signature part untouched.  A proof is R, comS1, keyXcom, keyYcom, expProof[secLevel] followed by a GKProof,
+ * and only the GKProof depends on the ring (src/zkpAttestList.ts:104-145: proveMembership(params.ProofGroup, pkX, which, keys) runs last, on the commitment
+ * keyXcom); the rest -- about 96 % of the bytes and 87 % of a proof's time (profiles/rering_rate.json) -- stays valid for any ring that holds the key.  So after zk_ctx_update_ring, for a second
+ * registry or for a larger ring, a proof for the new ring is the old head plus a fresh GKProof over the same keyXcom: what zk_member_prove_batch computes when
+ * it is given keyXcom's blinder.  The signature witness is not needed again, the blinder is.
+ * zk_prove_key_blinders: the blinder of keyXcom of the proof zk_prove_batch makes from the same rng -- logical draw 1 of each proof under the randomness
+ *   contract (draw 0 is comS1's, mod n; draw 1 mod q), 32 bytes big-endian per proof.  A prover that wants to re-ring later keeps it (or the seed) with the
+ *   proof; it is as secret as the seed.  ZK_E_BUFFER before zk_ctx_set_params, ZK_E_ARG for NULL pointers, B >= 2^32 and while streamed jobs are queued, B = 0
+ *   is ZK_OK.  ZK_RNG_STREAM: a proof whose stream does not hold the draw (fewer than two blocks, or rejected fills in front of it) gets 32 zero bytes and the
+ *   call returns ZK_E_RNG_EXHAUSTED; the other proofs' blinders are written.  Works in chunks of 2^18 proofs on one scratch buffer of 18 MB, wiped with the rest.
+ * zk_proof_rering_batch: the target is the ACTIVE ring.  Nothing of the ring a proof was made for is read: it need not be resident or exist any more.
+ *   Output proof b is input proof b with its GKProof section (the last 288 n_old + 32 (3 n_old + 1) bytes, 264 n_old + ... in ZKA1P) replaced by a new one for
+ *   the active ring and the header's n and total_len updated; every other byte -- magic, secLevel, challenge bits, R, comS1, keyXcom, keyYcom, every
+ *   repetition -- is copied unchanged.  In ZK_MODE_REFERENCE the new section is byte for byte bytes [16, size) of the proof zk_member_prove_batch(which_new,
+ *   key_blinder, rng) returns with this ring active, under that call's caller-blinder contract: the 5 n draws start at fill 0, all mod q.  In
+ *   ZK_MODE_HARDENED its challenge hashes the full proof's statement (ring digest, msgHash, R, keyXcom: zk_ctx_set_mode), R and keyXcom read from the proof,
+ *   as zk_prove_batch does in that mode.  msg_hash is required in both modes.  Input and output are in the context's wire layout (zk_ctx_set_wire).
+ *   Per proof, in this order; a failed proof gets an empty output slot and touches no neighbour:
+ *     ZK_E_BAD_ENCODING   a wrong magic (the other layout's included), a header total_len that is not the slot's length, a header n > 63, a total_len smaller
+ *                         than the fixed head plus the GKProof its n announces, a slot offset or a slot length that is not a multiple of 4, offsets that do
+ *                         not ascend.  No
+ *                         curve check is made -- this is not a verifier -- and no byte outside a slot is read.
+ *     ZK_E_ARG            which_new[b] >= N of the active ring.
+ *     ZK_E_OPENING        ring[which_new[b]] g + key_blinder[b] h is not the proof's keyXcom (the blinder reduced mod q as newScalar does; one comb commitment
+ *                         per proof, compared as canonical bytes): a wrong blinder, or a key that is not at which_new -- caught before a proof that cannot
+ *                         verify is written.
+ *     ZK_E_RNG_EXHAUSTED  as in zk_member_prove_batch.
+ *   out_off[0] = 0 and the proofs lie back to back in index order, ready for zk_verify_batch.  ZK_E_BUFFER when out_cap is too small, decided before a byte is
+ *   written, from the headers alone: out_cap must hold the new proofs of all inputs that pass the first two checks (what the output is unless a proof fails
+ *   its opening or its RNG stream; those slots are then empty and the proofs behind them close up).
+ *   In place: out == proofs is allowed in the _device form when every well-formed proof's n equals the ring's.  Only the GKProof sections are rewritten,
+ *   out_off is a copy of proof_off, a failed proof keeps its bytes and gets its status, no byte of any repetition is read or written, and out_cap must be
+ *   at least proof_off[B].  If some well-formed proof has another n the call returns ZK_E_ARG and writes nothing.  The _device form decides both rules with
+ *   one census kernel and ONE read-back of its counters.  The host-pointer form stages the batch in HBM; out == proofs is in place there too, by the same rules
+ *   (the staged copy is re-ringed in place and copied back).  Any other overlap of out and proofs is refused with ZK_E_ARG, nothing written.
+ *   Call-level rules are the member calls': ZK_E_BUFFER without params or without an active ring; ZK_E_ARG for NULL pointers and while streamed jobs are
+ *   queued; B = 0 is ZK_OK (out_off[0] = 0); chunks (zk_ctx_set_chunk) on the context's lanes; both protocol modes.  The _device form takes every pointer and
+ *   rng->data in this context's HBM (proofs and out 4-byte aligned, offsets 8-byte aligned).  zk_last_timing reports the member prover's families plus
+ *   "rr_census", "rr_offsets" and "rr_move".  The staged blinders and RNG fills are witness-derived: zk_ctx_wipe, zk_ctx_destroy and a failed call zero them.
+ *   Not provided: _rings, streamed and zk_pool_* forms.
+ * Two warnings.  (1) Two GKProofs over one keyXcom tell a verifier who sees both that the key lies in the INTERSECTION of the two rings: re-ringing to a ring
+ *   that shares few keys with the old one gives most of the anonymity away to whoever holds both proofs.  (2) rng must be fresh and independent of the rng the
+ *   proof was made with: with the original seeds, fill 0 and fill 1 of the new call are comS1's and keyXcom's blinders reused as GK nonces, and the responses
+ *   za, zb then reveal them.
+ * How: one lane per proof reads the header, keyXcom (and R in hardened mode) and gathers ring[which_new] from the ring's resident limbs; the claimed opening
+ *   rides in the same commitment launch as the proof's 4 n membership commitments and is compared behind the normaliser; an exclusive scan of the new lengths
+ *   gives the offsets; one kernel moves the heads, 16 bytes per lane with the work divided by bytes; the membership prover's fold, hash, responses and point
+ *   writers run unchanged, pointed at each proof's own GKProof section. */
+zk_status zk_prove_key_blinders(zk_ctx *ctx, uint64_t B, const zk_rng *rng, uint8_t *blinder_be32 /*Bx32*/);   /* host pointers */
+zk_status zk_prove_key_blinders_device(zk_ctx *ctx, uint64_t B, const zk_rng *rng_device, void *d_blinder_be32);
+zk_status zk_proof_rering_batch(zk_ctx *ctx, uint64_t B, const uint8_t *msg_hash /*Bx32*/, const uint8_t *proofs, const uint64_t *proof_off /*B+1*/,
+                                const uint32_t *which_new /*B*/, const uint8_t *key_blinder_be32 /*Bx32*/, const zk_rng *rng, uint8_t *out, uint64_t out_cap,
+                                uint64_t *out_off /*B+1*/, int32_t *per_proof_status /*B*/);
+zk_status zk_proof_rering_batch_device(zk_ctx *ctx, uint64_t B, const void *d_msg_hash, const void *d_proofs, const void *d_proof_off /*u64[B+1]*/,
+                                       const void *d_which_new /*u32[B]*/, const void *d_key_blinder_be32, const zk_rng *rng_device, void *d_out,
+                                       uint64_t out_cap, void *d_out_off /*u64[B+1]*/, void *d_per_proof_status /*i32[B]*/);
 
 /* ---- two (or more) batches in flight on one context.  zk_prove_batch / zk_verify_batch are synchronous: each call pays its own head
  * (no byte of a chunk exists before its stage 1 is over) and its own tail (the copies of the last slices, with nothing left to

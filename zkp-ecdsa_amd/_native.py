@@ -32,6 +32,7 @@ SYMBOLS = [
     'zk_member_proof_size_ring', 'zk_member_prove_batch_rings', 'zk_member_prove_batch_rings_device', 'zk_member_verify_batch_rings', 'zk_member_verify_batch_rings_device',
     'zk_member_prove_batch_bound', 'zk_member_prove_batch_bound_device', 'zk_member_verify_batch_bound', 'zk_member_verify_batch_bound_device',
     'zk_member_prove_batch_rings_bound', 'zk_member_prove_batch_rings_bound_device', 'zk_member_verify_batch_rings_bound', 'zk_member_verify_batch_rings_bound_device',
+    'zk_prove_key_blinders', 'zk_prove_key_blinders_device', 'zk_proof_rering_batch', 'zk_proof_rering_batch_device',
     'zk_test_field_op', 'zk_test_tom_commit', 'zk_test_p256_fixed_mul', 'zk_test_sha256', 'zk_test_rng_draws', 'zk_test_exp_sum',
 ]
 
@@ -40,8 +41,9 @@ STATUS_TEXT = {
     5: 'P/Q/R is at infinity', 6: "Points don't add up!", 7: 'R is at infinity', 8: 'params not found',
     9: 'security level not achieved', 10: 'error deserializing', 11: 'randomness stream exhausted',
     12: 'buffer too small or context not configured', 13: 'incorrect interpolation', 14: 'invalid argument',
-    15: 'HIP runtime failure',
+    15: 'HIP runtime failure', 16: "the index and blinder do not open the proof's key commitment",
 }
+E_OPENING = 16
 
 
 def _ring_changes(changes):
@@ -160,6 +162,11 @@ def lib():
         L.zk_member_prove_batch_rings_bound_device.argtypes = [vp, u64, vp, vp, vp, vp, C.POINTER(ZkRng), vp, vp, vp, u64, vp, vp]
         L.zk_member_verify_batch_rings_bound.argtypes = [vp, u64, C.c_char_p, C.c_char_p, C.c_char_p, vp, vp, C.c_char_p, vp, vp]
         L.zk_member_verify_batch_rings_bound_device.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp, vp, vp]
+        # re-ring: keyXcom's blinders, and a proof's GKProof section replaced by one for the active ring
+        L.zk_prove_key_blinders.argtypes = [vp, u64, C.POINTER(ZkRng), vp]
+        L.zk_prove_key_blinders_device.argtypes = [vp, u64, C.POINTER(ZkRng), vp]
+        L.zk_proof_rering_batch.argtypes = [vp, u64, C.c_char_p, vp, vp, vp, C.c_char_p, C.POINTER(ZkRng), vp, u64, vp, vp]
+        L.zk_proof_rering_batch_device.argtypes = [vp, u64, vp, vp, vp, vp, vp, C.POINTER(ZkRng), vp, u64, vp, vp]
         L.zk_ring_digest.argtypes = [vp, vp]
         L.zk_hardened_h.argtypes = [C.c_char_p, u64, vp, vp]
         L.zk_pool_create.argtypes = [C.POINTER(C.c_int), i32, C.POINTER(vp)]
@@ -928,6 +935,76 @@ class Engine:
             self._chk(self.L.zk_member_verify_batch_rings_device(self.h, B, d_com, d_proofs, d_off, d_ring_ids, d_vseeds, d_ok, d_status))
         else:
             self._chk(self.L.zk_member_verify_batch_rings_bound_device(self.h, B, d_com, d_context, d_proofs, d_off, d_ring_ids, d_vseeds, d_ok, d_status))
+
+    # ---- re-ring (zk_prove_key_blinders, zk_proof_rering_batch): a ZKA1 proof moved to the active ring, its signature part untouched
+    @staticmethod
+    def _rng(B, seeds, streams, stream_blocks):
+        if streams is None:
+            if len(seeds) != 32 * B:
+                raise ValueError('seeds must hold 32 bytes per proof')
+            data = C.create_string_buffer(bytes(seeds), max(32 * B, 1))
+            return ZkRng(0, C.cast(data, C.c_void_p), 0), data
+        data = C.create_string_buffer(bytes(streams), max(32 * B * stream_blocks, 1))
+        return ZkRng(1, C.cast(data, C.c_void_p), stream_blocks), data
+
+    def prove_key_blinders(self, seeds=None, streams=None, stream_blocks=0):
+        """zk_prove_key_blinders: the blinder of keyXcom in the proof prove_batch makes from the same seeds / streams (draw 1 of each proof), a list of
+        32-byte scalars -- what rering_batch needs later.  As secret as the seeds."""
+        B = (len(seeds) // 32) if streams is None else len(streams) // (32 * stream_blocks)
+        rng, _keep = self._rng(B, seeds, streams, stream_blocks)
+        out = C.create_string_buffer(max(32 * B, 1))
+        self._chk(self.L.zk_prove_key_blinders(self.h, B, C.byref(rng), out))
+        return [out.raw[32 * b:32 * b + 32] for b in range(B)]
+
+    def prove_key_blinders_device(self, B, d_rng, d_out, mode=0, stride_blocks=0):
+        rng = ZkRng(mode, d_rng, stride_blocks)
+        self._chk(self.L.zk_prove_key_blinders_device(self.h, B, C.byref(rng), d_out))
+
+    def rering_batch(self, msg, proofs, which_new, key_blinders, seeds=None, streams=None, stream_blocks=0, in_place=False, cap=None):
+        """zk_proof_rering_batch: every proof (bytes, in the context's wire layout) with its GKProof section replaced by one for the ACTIVE ring, where
+        ring[which_new[b]] is the proof's key and key_blinders[b] (32 bytes each, or B x 32 bytes) keyXcom's blinder (prove_key_blinders).  seeds / streams
+        must be FRESH: never the ones the proofs were made with.  Returns (proofs: list of bytes, None where the status is not 0; statuses); the offsets the
+        call wrote are kept in self.rering_last_off.  in_place: out == proofs, one buffer: allowed when every
+        proof's n is the ring's (ZkError 14 otherwise); a failed proof then keeps its bytes and is returned as they are.  cap: the out_cap handed to the call."""
+        B = len(proofs)
+        if len(which_new) != B:
+            raise ValueError('one index per proof')
+        if not isinstance(key_blinders, (bytes, bytearray, memoryview)):
+            key_blinders = b''.join(bytes(x) for x in key_blinders)
+        if len(key_blinders) != 32 * B or len(msg) != 32 * B:
+            raise ValueError('msg and key_blinders must hold 32 bytes per proof')
+        if seeds is None and streams is None:
+            seeds = os.urandom(32 * B)
+        rng, data = self._rng(B, seeds, streams, stream_blocks)
+        blob = b''.join(proofs)
+        off = (C.c_uint64 * (B + 1))()
+        o = 0
+        for b, p in enumerate(proofs):
+            off[b] = o
+            o += len(p)
+        off[B] = o
+        w = (C.c_uint32 * max(B, 1))(*which_new)
+        st = (C.c_int32 * max(B, 1))()
+        out_off = (C.c_uint64 * (B + 1))()
+        if in_place:   # one buffer for proofs and out: only the GKProof sections are rewritten, a failed proof keeps its bytes
+            buf = C.create_string_buffer(blob, max(len(blob), 1))
+            self._chk(self.L.zk_proof_rering_batch(self.h, B, bytes(msg), buf, off, w, bytes(key_blinders), C.byref(rng), buf, len(blob) if cap is None else cap, out_off, st))
+            raw = buf.raw[:len(blob)]
+            self.rering_last_off = list(out_off)
+            return [raw[out_off[b]:out_off[b + 1]] for b in range(B)], list(st)[:B]
+        if cap is None:
+            cap = len(blob) + B * self.member_proof_size()   # every head as it is plus a new GKProof section (16 bytes to spare per proof)
+        out = C.create_string_buffer(max(cap, 1))
+        self._chk(self.L.zk_proof_rering_batch(self.h, B, bytes(msg), blob, off, w, bytes(key_blinders), C.byref(rng), out, cap, out_off, st))
+        assert out_off[0] == 0 and all(out_off[b] <= out_off[b + 1] for b in range(B))
+        raw = out.raw[:out_off[B]]
+        self.rering_last_off = list(out_off)
+        return [raw[out_off[b]:out_off[b + 1]] if st[b] == 0 else None for b in range(B)], list(st)[:B]
+
+    def rering_batch_device(self, B, d_msg, d_proofs, d_off, d_which_new, d_key_blinders, d_rng, d_out, out_cap, d_out_off, d_status, mode=0, stride_blocks=0):
+        """zk_proof_rering_batch_device: every pointer a device address; d_out == d_proofs re-rings in place"""
+        rng = ZkRng(mode, d_rng, stride_blocks)
+        self._chk(self.L.zk_proof_rering_batch_device(self.h, B, d_msg, d_proofs, d_off, d_which_new, d_key_blinders, C.byref(rng), d_out, out_cap, d_out_off, d_status))
 
     def synth_params(self, seed):
         a, b, c = C.create_string_buffer(64), C.create_string_buffer(72), C.create_string_buffer(72)

@@ -43,6 +43,7 @@ extern "C" const char* zk_strerror(zk_status s) {
     case ZK_E_INTERPOLATION: return "incorrect interpolation";
     case ZK_E_ARG: return "invalid argument";
     case ZK_E_DEVICE: return "HIP runtime failure";
+    case ZK_E_OPENING: return "the index and blinder do not open the proof's key commitment";
     }
     return "unknown status";
 }
@@ -182,6 +183,9 @@ extern "C" void zk_ctx_destroy(zk_ctx* c) {
     if (c->pr_ready) hipEventDestroy(c->pr_ready);
     if (c->h_mr) hipHostFree(c->h_mr);
     if (c->mr_ready) hipEventDestroy(c->mr_ready);
+    if (c->h_rr) hipHostFree(c->h_rr);
+    for (hipEvent_t e : c->rr_scan)
+        if (e) hipEventDestroy(e);
     if (c->h_stage) hipHostFree(c->h_stage);
     if (c->in_ready) hipEventDestroy(c->in_ready);
     for (int l = 0; l < ZK_MAX_LANES; l++) {

@@ -73,7 +73,7 @@ static size_t mcarve(zk_ctx* c, zk_ctx::MemberLane& L, uint8_t* base, uint32_t C
     L.res2 = k.soa((size_t)C * std::max<uint64_t>(1, (N >> VT) / 512));
     return k.off + 256;
 }
-static zk_status ensure_member_lanes(zk_ctx* c, uint32_t C, uint32_t nlanes) {
+zk_status ensure_member_lanes(zk_ctx* c, uint32_t C, uint32_t nlanes) {   // (also api_rering.hip)
     const uint32_t n = c->ring->n;
     const bool etab = c->ring->gk_etab != nullptr, edig = c->ring->gk_edig != nullptr;
     if (!(c->ms_C == C && c->ms_n == n && c->ms_etab == etab && c->ms_edig == edig)) {
