@@ -300,7 +300,7 @@ static zk_status build_ring(zk_ctx* c, Ring& R, const uint8_t* d_keys, uint64_t 
     HIPCHK(c, hipMalloc(&R.ring_mem, sizeof(uint32_t) * 9 * N));
     Soa ring = {R.ring_mem, (uint32_t)N};
     launch_ring_load(c->stream, d_keys, nkeys, N, ring);
-    if (c->gk_table && n >= GK_ETAB_MINN && n <= GK_ETAB_MAXN) {  // per-ring table of the 8 low fold levels (k_gk.hip)
+    if (c->gk_table && gk_etab_range(n)) {  // per-ring table of the 8 low fold levels (k_gk.hip)
         if (strict) HIPCHK(c, hipMalloc(&R.gk_etab, sizeof(uint32_t) * gk_etab_words(N)));
         else if (hipMalloc(&R.gk_etab, sizeof(uint32_t) * gk_etab_words(N)) != hipSuccess) (void)hipGetLastError(), R.gk_etab = nullptr;   // plain fold for this ring
         if (R.gk_etab) launch_gk_etab(c->stream, ring, (uint32_t)(N >> 8), R.gk_etab), c->dbg_etab_blocks += N >> 8;
@@ -749,41 +749,20 @@ static size_t carve(zk_ctx* c, Workspace& W, Soa& gk_am, uint8_t* base, uint32_t
     const size_t lb_bytes = k.off - lb_off0;
     W.lc = k.list((size_t)C * 4 * n);
     W.gk_fill0 = 3 + 4 * sec, W.gk_blind = Soa{nullptr, 0};
-    W.gk_x = (uint32_t*)k.take(12 * (size_t)C);
-    W.gk_coef = k.soa((size_t)(n + 1) * C);
-    gk_am = k.soa((size_t)n * C);
-    // fused fold (n >= 3): gk_bufA holds the tile polynomials, (T+1) coefs x N/2^T tiles per proof; the per-level
-    // fallback for tiny rings ping-pongs G*N elements between gk_bufA and gk_bufB
-    uint64_t g = std::max<uint64_t>(1, std::min<uint64_t>(C, ((uint64_t)1 << 16) / N));
-    W.gk_group = (uint32_t)g;
-    uint32_t T = c->ring->gk_etab ? 8 : std::min<uint32_t>(n, 12);
-    uint64_t tile_elems = (uint64_t)(T + 1) * C * (N >> T);
-    W.gk_etab = c->ring->gk_etab;
-    W.gk_kdig = c->gk_mfma ? c->ring->gk_kdig : nullptr;
-    W.gk_edig = c->gk_mfma ? c->ring->gk_edig : nullptr;
-    W.gk_adig = c->ring->gk_edig ? (int8_t*)k.take(gkm_asub_frag_bytes(C)) : nullptr;
-    W.gk_toff = (uint32_t*)k.take(4 * 264);
-    W.gk_asub = c->ring->gk_etab ? (uint32_t*)k.take(36 * 256 * (size_t)C) : nullptr;
-    W.gk_order = (uint32_t*)k.take(4 * (size_t)C);
-    W.gk_goff = (uint32_t*)k.take(4 * 264);
-    W.gk_bufA = (uint32_t*)k.take(36 * std::max<uint64_t>(g * N, tile_elems));
-    W.gk_bufB = (uint32_t*)k.take(36 * std::max<uint64_t>(g * N, (uint64_t)(n + 1) * C * std::max<uint64_t>(1, (N >> T) / gk_finish_gsz(T, (uint32_t)(N >> T)))));
-    W.rng.exc_idx = (uint32_t*)k.take(4 * RNG_MAX_EXC * (size_t)C);
-    W.rng.exc_flags = (uint32_t*)k.take(4 * RNG_MAX_EXC * (size_t)C);
-    W.rng.exc_cnt = (uint32_t*)k.take(4 * (size_t)C);
-    W.rng_fill = (uint32_t*)k.take(32 * (size_t)(3 + 44 * sec + 5 * n + RNG_MAX_EXC) * C);
+    carve_gk_scalars(k, W, gk_am);
+    carve_gk_fold(k, W, *c->ring, N);
+    carve_rng(k, W, 3 + 44 * (size_t)sec + 5 * n + RNG_MAX_EXC);
     {
         // the Exp challenge's message and schedule buffers (k_hash.hip: k_exph_*): their own memory for chunks of up to EXPH_MAXP proofs (the verifier's
         // small chunks use them while list B may be live); a prover chunk of any size borrows LIST B, which nothing touches before stage 2 -- 80 KB of
         // the 397 KB a proof's list B takes, so the three-kernel path costs no HBM
-        const size_t blocks = (2 * 67 + (size_t)sec * (65 + 2 * 67) + 9 + 63) / 64, np = std::min<size_t>(C, EXPH_MAXP);
-        W.exph_msg = (uint8_t*)k.take(np * blocks * 64), W.exph_wk = (uint32_t*)k.take(np * blocks * 256), W.exph_cap = (uint32_t)np;
+        carve_exph(k, W);
+        const size_t blocks = exph_blocks(sec);
         const size_t big_msg = ((size_t)C * blocks * 64 + 255) & ~(size_t)255;
         if (lb_bytes >= big_msg + (size_t)C * blocks * 256) W.exph_big_msg = lb_begin, W.exph_big_wk = (uint32_t*)(lb_begin ? lb_begin + big_msg : nullptr), W.exph_big_cap = C;
         else W.exph_big_msg = nullptr, W.exph_big_wk = nullptr, W.exph_big_cap = 0;
     }
-    W.ring = Soa{c->ring->ring_mem, (uint32_t)N};
-    return k.off + 256;
+    return k.off + 256;   // (the ring's pointers: ensure_workspace binds them on every call)
 }
 // hipMalloc for a workspace that gives up the OPTIONAL per-ring tables before it gives up itself: the per-key tables (35 GB at 2^17 keys)
 // are taken when a ring is built, before anybody knows how large the chunks will be; if a lane's arena no longer fits, the tables go and
@@ -829,13 +808,10 @@ zk_status ensure_workspace(zk_ctx* c, uint32_t C, uint32_t nlanes) {
             }
             L.ready = true;
         }
-        L.W.ring = Soa{c->ring->ring_mem, (uint32_t)c->ring->N};
+        bind_ring(L.W, c);
         L.W.gk_stmt = c->mode == ZK_MODE_HARDENED ? GK_STMT_FULL : GK_STMT_NONE, L.W.ring_digest = c->ring->ring_digest;
         L.W.wire = wire_make(c->wire == ZK_WIRE_ZKA1P);
         L.W.ktab = c->ring->ktab, L.W.ktab_ok = c->ring->ktab_ok;
-        L.W.gk_etab = c->ring->gk_etab;
-        L.W.gk_kdig = c->gk_mfma ? c->ring->gk_kdig : nullptr;
-        L.W.gk_edig = c->gk_mfma && L.W.gk_adig ? c->ring->gk_edig : nullptr;
     }
     return ZK_OK;
 }

@@ -21,30 +21,11 @@ static size_t mcarve(zk_ctx* c, zk_ctx::MemberLane& L, uint8_t* base, uint32_t C
     W.out_base = (uint64_t*)k.take(8 * ((size_t)C + 1));
     W.lc = k.list((size_t)C * (4 * n + 1));
     W.gk_blind = k.soa(C);
-    W.gk_x = (uint32_t*)k.take(12 * (size_t)C);
-    W.gk_coef = k.soa((size_t)(n + 1) * C);
-    L.gk_am = k.soa((size_t)n * C);
+    carve_gk_scalars(k, W, L.gk_am);
     L.which_s = (uint32_t*)k.take(4 * (size_t)C);
-    // the fold's buffers, as the full prover's workspace sizes them (api.hip: carve)
-    const uint64_t g = std::max<uint64_t>(1, std::min<uint64_t>(C, ((uint64_t)1 << 16) / N));
-    W.gk_group = (uint32_t)g;
-    const uint32_t T = c->ring->gk_etab ? 8 : std::min<uint32_t>(n, 12);
-    const uint64_t tile_elems = (uint64_t)(T + 1) * C * (N >> T);
-    W.gk_adig = c->ring->gk_edig ? (int8_t*)k.take(gkm_asub_frag_bytes(C)) : nullptr;
-    W.gk_toff = (uint32_t*)k.take(4 * 264);
-    W.gk_asub = c->ring->gk_etab ? (uint32_t*)k.take(36 * 256 * (size_t)C) : nullptr;
-    W.gk_order = (uint32_t*)k.take(4 * (size_t)C);
-    W.gk_goff = (uint32_t*)k.take(4 * 264);
-    W.gk_bufA = (uint32_t*)k.take(36 * std::max<uint64_t>(g * N, tile_elems));
-    W.gk_bufB = (uint32_t*)k.take(36 * std::max<uint64_t>(g * N, (uint64_t)(n + 1) * C * std::max<uint64_t>(1, (N >> T) / gk_finish_gsz(T, (uint32_t)(N >> T)))));
-    W.rng.exc_idx = (uint32_t*)k.take(4 * RNG_MAX_EXC * (size_t)C);
-    W.rng.exc_flags = (uint32_t*)k.take(4 * RNG_MAX_EXC * (size_t)C);
-    W.rng.exc_cnt = (uint32_t*)k.take(4 * (size_t)C);
-    W.rng_fill = (uint32_t*)k.take(32 * (size_t)(1 + 5 * n + RNG_MAX_EXC) * C);
-    {
-        const size_t blocks = (2 * 67 + (size_t)W.sec * (65 + 2 * 67) + 9 + 63) / 64, np = std::min<size_t>(C, EXPH_MAXP);
-        W.exph_msg = (uint8_t*)k.take(np * blocks * 64), W.exph_wk = (uint32_t*)k.take(np * blocks * 256), W.exph_cap = (uint32_t)np;
-    }
+    carve_gk_fold(k, W, *c->ring, N);
+    carve_rng(k, W, 1 + 5 * (size_t)n + RNG_MAX_EXC);
+    carve_exph(k, W);
     W.wire = wire_make(false);
     W.wire.fixed = ZKM1_HDR, W.wire.rep_head = 0, W.wire.padd = 0, W.wire.magic = ZK_MAGIC_ZKM1;
     // the verifier's view
@@ -56,10 +37,7 @@ static size_t mcarve(zk_ctx* c, zk_ctx::MemberLane& L, uint8_t* base, uint32_t C
     V.okflags = (uint32_t*)k.take(4 * (size_t)C);
     V.zcnt = (uint32_t*)k.take(4 * (size_t)C);
     V.gkx = (uint32_t*)k.take(12 * (size_t)C);
-    V.gk_f = k.soa((size_t)n * C), V.gk_g = k.soa((size_t)n * C);
-    V.gk_total = k.soa(C);
-    V.gk_csub = (uint32_t*)k.take(n >= GK_ETAB_MINN && n <= GK_ETAB_MAXN ? std::max<size_t>(36 * 256 * (size_t)C, n >= GKM_MINN ? gkm_coef_frag_bytes(C) : 0) : 16);
-    V.gk_swap = (uint32_t*)k.take(4 * (size_t)n * C);
+    carve_v_gk_scalars(k, V);
     const size_t nq = (n + 1) / 2;
     auto terms = [&](size_t cnt) {
         return VTerms{(uint32_t*)k.take(cnt * VT_ENTRY_WORDS * 4), k.soa(cnt), (uint32_t*)k.take(cnt * 8 * 36 * 4), (uint8_t*)k.take(cnt * 65), (uint32_t)cnt};
@@ -68,9 +46,7 @@ static size_t mcarve(zk_ctx* c, zk_ctx::MemberLane& L, uint8_t* base, uint32_t C
     V.gk_terms = terms((size_t)C * nq * 8);
     V.misc_terms = terms((size_t)C * 3);
     V.gk_acc = soa4((size_t)C * nq), V.misc_acc = soa4((size_t)C * 3);
-    const uint32_t VT = n >= GK_ETAB_MINN && n <= GK_ETAB_MAXN ? 8 : std::min<uint32_t>(n, 13);
-    L.res = k.soa((size_t)C * (N >> VT));
-    L.res2 = k.soa((size_t)C * std::max<uint64_t>(1, (N >> VT) / 512));
+    carve_v_gk_fold(k, L.res, L.res2, C, n, N);
     return k.off + 256;
 }
 zk_status ensure_member_lanes(zk_ctx* c, uint32_t C, uint32_t nlanes) {   // (also api_rering.hip)
@@ -86,11 +62,7 @@ zk_status ensure_member_lanes(zk_ctx* c, uint32_t C, uint32_t nlanes) {   // (al
             if (zk_status zs = lay_out(c, L.arena, GROW_SHED, [&](uint8_t* base) { return mcarve(c, L, base, C, n, c->ring->N); })) return zs;
             L.ready = true;
         }
-        // the ring's pointers are bound on every call (zk_ctx_use_ring, zk_ctx_update_ring, zk_ctx_set_ring_fold)
-        L.W.ring = Soa{c->ring->ring_mem, (uint32_t)c->ring->N};
-        L.W.gk_etab = c->ring->gk_etab;
-        L.W.gk_kdig = c->gk_mfma ? c->ring->gk_kdig : nullptr;
-        L.W.gk_edig = c->gk_mfma && L.W.gk_adig ? c->ring->gk_edig : nullptr;
+        bind_ring(L.W, c);
     }
     return ZK_OK;
 }

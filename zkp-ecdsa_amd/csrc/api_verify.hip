@@ -27,10 +27,7 @@ static size_t vcarve(VWork& V, Soa& res, Soa& res2, MsmBuf& M, PMsmBuf& PM, uint
         V.ph_msg = (uint8_t*)k.take(nm * V_PH_BLOCKS * 64), V.ph_wk = (uint32_t*)k.take(nm * V_PH_BLOCKS * 256), V.ph_nblk = (uint8_t*)k.take(nm);
     }
     V.vd = k.list(ns * 5);
-    V.gk_f = k.soa((size_t)n * C), V.gk_g = k.soa((size_t)n * C);
-    V.gk_total = k.soa(C);
-    V.gk_csub = (uint32_t*)k.take(n >= GK_ETAB_MINN && n <= GK_ETAB_MAXN ? std::max<size_t>(36 * 256 * (size_t)C, n >= GKM_MINN ? gkm_coef_frag_bytes(C) : 0) : 16);
-    V.gk_swap = (uint32_t*)k.take(4 * (size_t)n * C);
+    carve_v_gk_scalars(k, V);
     size_t nq = (n + 1) / 2;
     // the points of the three term lists are ONE array of 128-byte entries (slot terms, membership terms, the three per proof): a term's number in it is
     // its id in the bucket pass (k_msm.hip), which gathers these entries as they are
@@ -83,9 +80,7 @@ static size_t vcarve(VWork& V, Soa& res, Soa& res2, MsmBuf& M, PMsmBuf& PM, uint
         M.sort_tmp = k.take(M.sort_tmp_bytes);
         M.one = k.list(MSM_G_MAX);
     }
-    uint32_t T = n >= GK_ETAB_MINN && n <= GK_ETAB_MAXN ? 8 : std::min<uint32_t>(n, 13);  // block path: one value per 256 keys
-    res = k.soa((size_t)C * (N >> T));
-    res2 = k.soa((size_t)C * std::max<uint64_t>(1, (N >> T) / 512));
+    carve_v_gk_fold(k, res, res2, C, n, N);
     return k.off + 256;
 }
 zk_status ensure_vworkspace(zk_ctx* c, uint32_t C, uint32_t nlanes) {

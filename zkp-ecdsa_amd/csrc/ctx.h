@@ -393,3 +393,52 @@ struct SoaCarver : Carver {   // the workspace arenas' conveniences on top of la
         return L;
     }
 };
+// The GK (ring membership) sections of a lane's arena.  The prover's, the verifier's and the member lanes' arenas (api.hip: carve; api_verify.hip: vcarve;
+// api_member.hip: mcarve) take them from here, each run at its own place in the arena, every size from gk_plan.h.  W.C, W.sec, W.n (V.C, V.n) are set before.
+static inline void carve_gk_scalars(SoaCarver& k, Workspace& W, Soa& gk_am) {
+    W.gk_x = (uint32_t*)k.take(12 * (size_t)W.C);
+    W.gk_coef = k.soa((size_t)(W.n + 1) * W.C);
+    gk_am = k.soa((size_t)W.n * W.C);
+}
+// the prover's fold of a ring of N keys: what the table path adds where R has the tables, then the two ping-pong buffers
+static inline void carve_gk_fold(SoaCarver& k, Workspace& W, const Ring& R, uint64_t N) {
+    const GkProvePlan p = gk_prove_plan(W.C, W.n, N, R.gk_etab != nullptr);
+    W.gk_group = p.group;
+    W.gk_adig = R.gk_edig ? (int8_t*)k.take(gkm_asub_frag_bytes(W.C)) : nullptr;
+    W.gk_toff = (uint32_t*)k.take(4 * 264);
+    W.gk_asub = R.gk_etab ? (uint32_t*)k.take(36 * 256 * (size_t)W.C) : nullptr;
+    W.gk_order = (uint32_t*)k.take(4 * (size_t)W.C);
+    W.gk_goff = (uint32_t*)k.take(4 * 264);
+    W.gk_bufA = (uint32_t*)k.take(36 * p.bufA);
+    W.gk_bufB = (uint32_t*)k.take(36 * p.bufB);
+}
+// the RNG prepass's rejection lists and the chunk's fills, `blocks` 32-byte blocks per proof
+static inline void carve_rng(SoaCarver& k, Workspace& W, size_t blocks) {
+    W.rng.exc_idx = (uint32_t*)k.take(4 * RNG_MAX_EXC * (size_t)W.C);
+    W.rng.exc_flags = (uint32_t*)k.take(4 * RNG_MAX_EXC * (size_t)W.C);
+    W.rng.exc_cnt = (uint32_t*)k.take(4 * (size_t)W.C);
+    W.rng_fill = (uint32_t*)k.take(32 * blocks * W.C);
+}
+// message and schedule buffers of the challenge hash of a chunk of up to EXPH_MAXP proofs (k_hash.hip: k_exph_*), exph_blocks(W.sec) blocks per proof
+static inline void carve_exph(SoaCarver& k, Workspace& W) {
+    const size_t blocks = exph_blocks(W.sec), np = std::min<size_t>(W.C, EXPH_MAXP);
+    W.exph_msg = (uint8_t*)k.take(np * blocks * 64), W.exph_wk = (uint32_t*)k.take(np * blocks * 256), W.exph_cap = (uint32_t)np;
+}
+static inline void carve_v_gk_scalars(SoaCarver& k, VWork& V) {
+    const size_t C = V.C, n = V.n;
+    V.gk_f = k.soa(n * C), V.gk_g = k.soa(n * C);
+    V.gk_total = k.soa(C);
+    V.gk_csub = (uint32_t*)k.take(gk_etab_range(V.n) ? std::max<size_t>(36 * 256 * C, V.n >= GKM_MINN ? gkm_coef_frag_bytes(V.C) : 0) : 16);
+    V.gk_swap = (uint32_t*)k.take(4 * n * C);
+}
+static inline void carve_v_gk_fold(SoaCarver& k, Soa& res, Soa& res2, uint32_t C, uint32_t n, uint64_t N) {
+    const GkVerifyPlan p = gk_verify_plan(C, n, N);
+    res = k.soa(p.res), res2 = k.soa(p.res2);
+}
+// the ring's pointers of a prover workspace, bound on every call (zk_ctx_use_ring, zk_ctx_update_ring, zk_ctx_set_ring_fold, RingBind)
+static inline void bind_ring(Workspace& W, const zk_ctx* c) {
+    W.ring = Soa{c->ring->ring_mem, (uint32_t)c->ring->N};
+    W.gk_etab = c->ring->gk_etab;
+    W.gk_kdig = c->gk_mfma ? c->ring->gk_kdig : nullptr;
+    W.gk_edig = c->gk_mfma && W.gk_adig ? c->ring->gk_edig : nullptr;
+}

@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include "../../include/zkattest.h"
 #include "curve.h"
+#include "gk_plan.h"   // geometry of the ring fold (GK_*, VGK_*, gk_prove_plan, gk_verify_plan) and the Exp challenge message's length (exph_blocks)
 #include "rng.h"
 
 // ------------------------------------------------------------------ SoA views (limb l of element e at p[l*stride+e])
@@ -291,8 +292,7 @@ void launch_v_t1_scalars(hipStream_t s, const Workspace& W, const VWork& V, uint
 void launch_v_derived(hipStream_t s, const Workspace& W, const VWork& V, uint32_t count, const uint8_t* proofs, const uint64_t* off, uint64_t first);
 void launch_v_padd_hash(hipStream_t s, const DevParams& P, const Workspace& W, const VWork& V, uint32_t count, const uint8_t* proofs, const uint64_t* off, uint64_t first);
 void launch_v_gk_total(hipStream_t s, const VWork& V, const Soa& ring, const uint32_t* etab, const int8_t* kdig, uint32_t count, uint32_t N, const uint8_t* proofs, const uint64_t* off, uint64_t first, const Soa& res, const Soa& res2);
-// k_gk_mfma.hip: the 8 low index bits of the verifier's ring fold as int8 matrix products (rings of at least 2^12 keys)
-#define GKM_MINN 12
+// k_gk_mfma.hip: the 8 low index bits of the verifier's ring fold as int8 matrix products (rings of at least 2^GKM_MINN keys)
 size_t gkm_ring_frag_bytes(uint64_t N);
 size_t gkm_coef_frag_bytes(uint32_t C);
 void launch_gkm_ring_digits(hipStream_t s, const Soa& ring, uint32_t nblocks, int8_t* frag);
@@ -499,16 +499,7 @@ hipError_t run_msm(hipStream_t s, const DevParams& P, const Workspace& W, const 
                    uint32_t* gsz, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr /* recorded around k_msm_bucket */,
                    hipEvent_t ev2 = nullptr, hipEvent_t ev3 = nullptr /* ... around the grouping of the keys */);
 void msm_read_flags(const MsmBuf& M, uint32_t groups, uint32_t* host_flags /*[groups]*/);
-// group size of one k_gk_finish pass over `ntiles` polynomials of T+1 coefficients: <= 64, dynamic LDS below 60 KB
-static inline size_t gk_finish_lds(uint32_t T, uint32_t g) { return sizeof(uint32_t) * 9 * ((size_t)g * (T + 1) + (size_t)(g / 2) * (T + 2)); }
-static inline uint32_t gk_finish_gsz(uint32_t T, uint32_t ntiles) {
-    uint32_t g = ntiles < 64 ? ntiles : 64;
-    while (g > 2 && gk_finish_lds(T, g) > 60 * 1024) g >>= 1;
-    return g;
-}
 // k_gk.hip
-#define GK_ETAB_MINN 9
-#define GK_ETAB_MAXN 20
 size_t gk_etab_words(uint64_t N);
 void launch_gk_etab(hipStream_t s, const Soa& ring, uint32_t nblocks, uint32_t* E);
 void launch_gk_etab_list(hipStream_t s, const Soa& ring, uint32_t nblocks, const uint32_t* d_blocks, uint32_t nb, uint32_t* E);   // only the listed blocks' columns (zk_ctx_update_ring)
@@ -714,10 +705,7 @@ ZK_DEV uint32_t zeros_below(const uint32_t* chal, uint32_t i) {  // number of 0 
     }
     return i - ones;
 }
-// Exp challenge of a small chunk in three kernels (k_hash.hip: k_exph_*): the padded message of hashPoints(Px, Py, A_0, Tx_0, Ty_0, ...) -- two Tom
-// points (67 bytes each), then per repetition a P-256 point (65) and two Tom points -- and its length in 64-byte blocks
-ZK_DEV uint32_t exph_msg_bytes(uint32_t sec) { return 2 * 67 + sec * (65 + 2 * 67); }
-ZK_DEV uint32_t exph_blocks(uint32_t sec) { return (exph_msg_bytes(sec) + 9 + 63) / 64; }
+// Exp challenge of a small chunk in three kernels (k_hash.hip: k_exph_*): where element e of the message lies (gk_plan.h: exph_msg_bytes, exph_blocks) and its padding
 ZK_DEV uint32_t exph_elem_offset(uint32_t e) { return e < 2 ? 67 * e : 134 + 199 * ((e - 2) / 3) + ((e - 2) % 3 == 0 ? 0 : (e - 2) % 3 == 1 ? 65 : 132); }
 ZK_DEV void exph_put_padding(uint8_t* m, uint32_t sec) {   // 0x80, zeros, the bit length in eight bytes
     const uint32_t len = exph_msg_bytes(sec), end = exph_blocks(sec) * 64;

@@ -585,8 +585,7 @@ void launch_gk_respond(hipStream_t s, const Workspace& W, const ChunkIn& in, uin
 }
 // ---- plain fold (rings without table E, see k_gk.hip for the table path): a tile of 2^T ring elements per workgroup.
 // RL levels run depth-first in registers (2^RL elements per lane), the others coefficient-parallel through LDS (one output coefficient = one modmul per lane), so a whole
-// tile costs ~20 modmul latencies instead of one kernel launch per level.  LDS planes are limb-major (conflict-free).
-#define GK_TMAX 12   // 256 lanes x 16 elements
+// tile costs ~20 modmul latencies instead of one kernel launch per level.  LDS planes are limb-major (conflict-free).  T <= GK_TMAX (gk_plan.h).
 struct LdsPlane {
     uint32_t* p;
     uint32_t stride;
@@ -730,9 +729,9 @@ void launch_gk_scalars_fold(hipStream_t s, const Workspace& W, const ChunkIn& in
     hipLaunchKernelGGL(k_gk_scalars, dim3((nt + 255) / 256), dim3(256), 0, s, W, in, am);
     if (W.n >= 3) {
         const uint32_t RL = W.n >= 4 ? 4 : 3;
-        uint32_t T = W.gk_etab ? 8 : W.n < GK_TMAX ? W.n : GK_TMAX;
-        uint32_t ntiles = W.N >> T;
-        // tile results: (T+1) coefs x ntiles per proof, kept in gk_bufA (capacity checked by the workspace carver)
+        const GkProvePlan plan = gk_prove_plan(W.C, W.n, W.N, W.gk_etab != nullptr);   // the plan gk_bufA and gk_bufB were carved by (ctx.h: carve_gk_fold)
+        uint32_t T = plan.T, ntiles = plan.ntiles;
+        // tile results: (T+1) coefs x ntiles per proof, kept in gk_bufA
         Soa res = {W.gk_bufA, (uint32_t)((T + 1) * W.C * ntiles)};
         if (W.gk_etab) launch_gk_block_stage(s, W, in, am, res);  // 8 low index bits through the per-ring table (k_gk.hip)
         else if (RL == 4) hipLaunchKernelGGL(k_gk_tile<4>, dim3(in.count * ntiles), dim3(256), 0, s, W, in, am, T, ntiles, res);

@@ -887,8 +887,7 @@ __global__ void __launch_bounds__(256) k_v_padd_msg(DevParams P, Workspace W, VW
 }
 
 // ------------------------------------------------------------------ GK total (gk.ts:239-250), fold form:
-// layer' [i] = (x - f_j) * layer[2i] + f_j * layer[2i+1]; tile of 2^T ring elements per workgroup, levels through LDS
-#define VGK_T 13   // 256 lanes x 32 elements per tile
+// layer' [i] = (x - f_j) * layer[2i] + f_j * layer[2i+1]; tile of 2^T ring elements per workgroup (T <= VGK_T, gk_plan.h), levels through LDS
 __global__ void __launch_bounds__(256) k_v_gk_fg(VWork V, uint32_t count, const uint8_t* proofs, const uint64_t* off, uint64_t first) {
     uint32_t t = gtid();
     if (t >= count * V.n) return;
@@ -980,8 +979,7 @@ __global__ void __launch_bounds__(256) k_v_gk_tile(VWork V, Soa ring, uint32_t T
         else soa_st(res, p * ntiles + tile, fe_canon(fe_reduce(r)));
     }
 }
-// finish pass: workgroup (proof, group) folds gsz <= 512 consecutive tile values through log2(gsz) levels (dynamic LDS)
-#define VGK_FIN 512u
+// finish pass: workgroup (proof, group) folds gsz <= VGK_FIN consecutive tile values through log2(gsz) levels (dynamic LDS)
 __global__ void __launch_bounds__(256) k_v_gk_finish(VWork V, uint32_t Tin, uint32_t npoly, uint32_t gsz, Soa src, Soa dst) {
     extern __shared__ uint32_t v_lds_dyn[];  // two planes of gsz elements (9 limbs each): sized by the launch
     uint32_t* bufA = v_lds_dyn;
@@ -1025,14 +1023,14 @@ void launch_v_gk_total(hipStream_t s, const VWork& V, const Soa& ring, const uin
         hipLaunchKernelGGL(k_v_gk_small, dim3((count + 63) / 64), dim3(64), 0, s, V, ring, count);
         return;
     }
-    uint32_t T = etab ? 8 : V.n < VGK_T ? V.n : VGK_T, ntiles = N >> T;
+    uint32_t T = vgk_tile(V.n, etab != nullptr), ntiles = N >> T;   // res and res2 hold this or more (gk_plan.h: gk_verify_plan)
     if (etab && kdig && V.n >= GKM_MINN) launch_v_gk_block_mfma(s, V, kdig, ntiles, count, (int8_t*)V.gk_csub, res);   // the same sums as int8 matrix products (k_gk_mfma.hip)
     else if (etab) launch_v_gk_block_stage(s, V, etab, ntiles, count, V.gk_csub, res);  // 8 low index bits through table E (k_gk.hip)
     else if (V.n >= 5) hipLaunchKernelGGL(k_v_gk_tile<5>, dim3(count * ntiles), dim3(256), 0, s, V, ring, T, ntiles, res);
     else hipLaunchKernelGGL(k_v_gk_tile<3>, dim3(count * ntiles), dim3(256), 0, s, V, ring, T, ntiles, res);
     Soa src = res, dst = res2;
     while (ntiles > 1) {
-        uint32_t gsz = ntiles < VGK_FIN ? ntiles : VGK_FIN, ngroups = ntiles / gsz, lv = 0;
+        uint32_t gsz = vgk_finish_gsz(ntiles), ngroups = ntiles / gsz, lv = 0;
         while ((1u << lv) < gsz) lv++;
         hipLaunchKernelGGL(k_v_gk_finish, dim3(count * ngroups), dim3(256), sizeof(uint32_t) * 2 * NLIMB * gsz, s, V, T, ntiles, gsz, src, dst);
         Soa tmp = src;
