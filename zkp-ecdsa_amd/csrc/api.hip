@@ -1390,7 +1390,7 @@ static zk_status prove_host(zk_ctx* c, uint64_t B, const uint8_t* msg, const uin
                             uint64_t out_cap, uint64_t* out_off, int32_t* status) {
     if (!c->params_set || !c->ring->N) return ZK_E_BUFFER;
     if (c->stream_busy) return busy_refusal(c);
-    size_t rng_bytes = rng->mode == ZK_RNG_SEED ? 32 * B : 32 * B * rng->stride_blocks;
+    size_t rng_bytes = ::rng_bytes(rng, B);
     size_t bb = B ? B : 1;
     uint64_t cap_dev = std::min<uint64_t>(out_cap, zk_proof_max_size(c) * bb);
     // the small per-proof arrays live in the context's grow-only input buffer (no hipMalloc / hipFree per call)
@@ -1627,7 +1627,7 @@ extern "C" zk_status zk_prove_batch_rings(zk_ctx* c, uint64_t B, const uint8_t* 
     if (!c || !rng || !out_off || !status || (B && (!msg || !sig || !pk || !which || !ring_ids || !rng->data || !out))) return ZK_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     if (!c->params_set) return ZK_E_BUFFER;
-    if (rng->mode != ZK_RNG_SEED && rng->mode != ZK_RNG_STREAM) return ZK_E_ARG;
+    if (!rng_mode_ok(rng)) return ZK_E_ARG;
     if (c->stream_busy) return busy_refusal(c);
     if (B == 0) {
         out_off[0] = 0;
@@ -1640,7 +1640,7 @@ extern "C" zk_status zk_prove_batch_rings(zk_ctx* c, uint64_t B, const uint8_t* 
         RingBind rb(c, one);
         return prove_host(c, B, msg, sig, pk, which, rng, out, out_cap, out_off, status);
     }
-    const size_t rng_bytes = rng->mode == ZK_RNG_SEED ? 32 * B : 32 * B * rng->stride_blocks;
+    const size_t rng_bytes = ::rng_bytes(rng, B);
     uint64_t bound = 0;   // no proof of the batch is larger than the largest resident ring's
     for (auto& R : c->rings)
         if (R.live && R.N) bound = std::max(bound, ring_proof_max_size(c, &R));
@@ -1662,22 +1662,11 @@ extern "C" zk_status zk_prove_batch_rings(zk_ctx* c, uint64_t B, const uint8_t* 
     if (sink)
         if (zk_status zs = ensure_copy_stream(c)) return zs;
     // from the first upload on, signatures and seeds lie in in_buf: every failure below zeroes them (prove_rings_device does so itself)
-    const struct { void* d; const void* h; size_t n; } up[] = {{I.msg, msg, 32 * B}, {I.sig, sig, 64 * B}, {I.pk, pk, 64 * B}, {I.which, which, 4 * B},
-                                                               {I.ids, ring_ids, 4 * B}, {I.rng, rng->data, rng_bytes}};
-    for (auto& u : up)
-        if (hipMemcpy(u.d, u.h, u.n, hipMemcpyHostToDevice) != hipSuccess) {
-            c->err = "upload of the inputs failed";
-            (void)hipGetLastError();
-            wipe_witness(c);
-            return ZK_E_DEVICE;
-        }
+    if (zk_status zs = upload_or_wipe(c, {{I.msg, msg, 32 * B}, {I.sig, sig, 64 * B}, {I.pk, pk, 64 * B}, {I.which, which, 4 * B}, {I.ids, ring_ids, 4 * B}, {I.rng, rng->data, rng_bytes}}))
+        return zs;
     if (zk_status zs = prove_rings_device(c, B, I.msg, I.sig, I.pk, I.which, I.ids, rng->mode, I.rng, rng->stride_blocks, d_out, cap_dev, I.off, I.st, sink)) return zs;
-    hipError_t e = hipMemcpy(out_off, I.off, 8 * (B + 1), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(status, I.st, 4 * B, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && !sink && !out_on_device && out_off[B]) e = hipMemcpy(out, d_out, out_off[B], hipMemcpyDeviceToHost);
-    if (e != hipSuccess) wipe_witness(c);
-    HIPCHK(c, e);
-    return ZK_OK;
+    if (zk_status zs = download_or_wipe(c, {{I.off, out_off, 8 * (B + 1)}, {I.st, status, 4 * B}})) return zs;
+    return download_or_wipe(c, {{d_out, out, !sink && !out_on_device ? out_off[B] : 0}});   // (out_off[B] has arrived)
 }
 
 // Diagnostic: what a page-locked copy of `bytes` reaches on lane `lane`'s copy stream, in both directions (GB/s), measured with HIP
@@ -1916,7 +1905,7 @@ extern "C" zk_status zk_test_rng_draws(zk_ctx* c, uint64_t B, const zk_rng* rng,
     if (!c || !rng || !rng->data || !out || !B || !n_k) return ZK_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     uint32_t sec = c->params_set ? c->P.sec : 80;
-    size_t rng_bytes = rng->mode == ZK_RNG_SEED ? 32 * B : 32 * B * rng->stride_blocks;
+    size_t rng_bytes = ::rng_bytes(rng, B);
     DevBuf dr, dout, dexc;
     HIPCHK(c, hipMalloc(&dr.p, rng_bytes)); HIPCHK(c, hipMalloc(&dout.p, 32 * B * n_k)); HIPCHK(c, hipMalloc(&dexc.p, 4 * B * (2 * RNG_MAX_EXC + 1)));
     HIPCHK(c, hipMemcpy(dr.p, rng->data, rng_bytes, hipMemcpyHostToDevice));

@@ -6,17 +6,15 @@
 #include "member.h"
 #include "rering.h"
 
-zk_status ensure_member_lanes(zk_ctx* c, uint32_t C, uint32_t nlanes);   // api_member.hip
-
 // ------------------------------------------------------------------ the blinder of keyXcom
 // Logical draw 1 of every proof under the randomness contract (draw 0 is comS1's, mod n; draw 1 mod q): the prepass and the draw mapping behind
 // zk_test_rng_draws on the caller's device buffers, in chunks of KB_CHUNK proofs on one scratch buffer of the context (the rejection lists are derived from
 // the seeds: it is witness-flagged and wiped with the rest).  A proof whose stream does not hold the draw gets 32 zero bytes and the call ZK_E_RNG_EXHAUSTED.
 #define KB_CHUNK (1u << 18)
-static zk_status key_blinders_device(zk_ctx* c, uint64_t B, int rng_mode, const uint8_t* d_rng, uint64_t stride, uint8_t* d_out) {
+static zk_status key_blinders_device(zk_ctx* c, uint64_t B, const zk_rng& rng, uint8_t* d_out) {   // (rng.data: a device pointer)
     if (!c->params_set) return ZK_E_BUFFER;
     if (c->stream_busy) return busy_refusal(c);
-    if ((rng_mode != ZK_RNG_SEED && rng_mode != ZK_RNG_STREAM) || B > 0xffffffffull) return ZK_E_ARG;
+    if (!rng_mode_ok(&rng) || B > 0xffffffffull) return ZK_E_ARG;
     if (B == 0) return ZK_OK;
     if (zk_status zs = reserve(c, B_kb, 4 * (size_t)KB_CHUNK * (2 * RNG_MAX_EXC + 1) + 256)) return zs;
     uint32_t* const flag = (uint32_t*)c->buf[B_kb].p;
@@ -24,7 +22,7 @@ static zk_status key_blinders_device(zk_ctx* c, uint64_t B, int rng_mode, const 
     HIPCHK(c, hipMemsetAsync(flag, 0, 4, s));
     Workspace W{};
     W.sec = c->P.sec;
-    W.rng.seeds = d_rng, W.rng.stream = d_rng, W.rng.stride_blocks = stride, W.rng.mode = rng_mode, W.rng.sec = (int)c->P.sec;
+    W.rng.seeds = rng.data, W.rng.stream = rng.data, W.rng.stride_blocks = rng.stride_blocks, W.rng.mode = rng.mode, W.rng.sec = (int)c->P.sec;
     W.rng.exc_idx = flag + 64, W.rng.exc_flags = W.rng.exc_idx + RNG_MAX_EXC * (size_t)KB_CHUNK, W.rng.exc_cnt = W.rng.exc_flags + RNG_MAX_EXC * (size_t)KB_CHUNK;
     for (uint64_t first = 0; first < B; first += KB_CHUNK) {
         const uint32_t cnt = (uint32_t)std::min<uint64_t>(KB_CHUNK, B - first);
@@ -45,7 +43,7 @@ static zk_status key_blinders_device(zk_ctx* c, uint64_t B, int rng_mode, const 
 extern "C" zk_status zk_prove_key_blinders_device(zk_ctx* c, uint64_t B, const zk_rng* rng, void* d_blinder) {
     if (!c || !rng || (B && (!rng->data || !d_blinder))) return ZK_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    return key_blinders_device(c, B, rng->mode, rng->data, rng->stride_blocks, (uint8_t*)d_blinder);
+    return key_blinders_device(c, B, *rng, (uint8_t*)d_blinder);
 }
 struct KeyBlindersIn {
     uint8_t *rng, *out;
@@ -60,19 +58,16 @@ extern "C" zk_status zk_prove_key_blinders(zk_ctx* c, uint64_t B, const zk_rng* 
     HIPCHK(c, hipSetDevice(c->device));
     if (!c->params_set) return ZK_E_BUFFER;
     if (c->stream_busy) return busy_refusal(c);
-    if (rng->mode != ZK_RNG_SEED && rng->mode != ZK_RNG_STREAM) return ZK_E_ARG;
+    if (!rng_mode_ok(rng)) return ZK_E_ARG;
     if (B == 0) return ZK_OK;
-    const size_t rng_bytes = rng->mode == ZK_RNG_SEED ? 32 * B : 32 * B * rng->stride_blocks;
-    KeyBlindersIn I;   // seeds and blinders lie in the witness-flagged input buffer
-    if (zk_status zs = lay_out(c, B_in, [&](uint8_t* base) { return key_blinders_in_layout(I, base, B, rng_bytes); })) return zs;
-    hipError_t e = hipMemcpy(I.rng, rng->data, rng_bytes, hipMemcpyHostToDevice);
-    zk_status zs = ZK_OK;
-    if (e == hipSuccess) zs = key_blinders_device(c, B, rng->mode, I.rng, rng->stride_blocks, I.out);
-    if (e == hipSuccess && !zs) e = hipMemcpy(blinder, I.out, 32 * B, hipMemcpyDeviceToHost);
-    if (zs || e != hipSuccess) wipe_witness(c);
-    if (zs) return zs;
-    HIPCHK(c, e);
-    return ZK_OK;
+    KeyBlindersIn I;   // seeds and blinders lie in the witness-flagged input buffer: every failure below zeroes them
+    if (zk_status zs = lay_out(c, B_in, [&](uint8_t* base) { return key_blinders_in_layout(I, base, B, rng_bytes(rng, B)); })) return zs;
+    if (zk_status zs = upload_or_wipe(c, {{I.rng, rng->data, rng_bytes(rng, B)}})) return zs;
+    if (zk_status zs = key_blinders_device(c, B, zk_rng{rng->mode, I.rng, rng->stride_blocks}, I.out)) {
+        wipe_witness(c);
+        return zs;
+    }
+    return download_or_wipe(c, {{I.out, blinder, 32 * B}});
 }
 
 // ------------------------------------------------------------------ re-ring
@@ -103,9 +98,9 @@ static size_t rering_layout(RrBufs& R, uint8_t* base, uint32_t C, uint32_t nlane
 // slot, the comparison (final statuses, new lengths), the offsets -- a chunk's proofs start where the chunk before ended, so its scan waits for that chunk's,
 // and for nothing else of it --, the challenge hash, then the heads' mover and the member prover's writers, into disjoint bytes.
 static zk_status rering_device(zk_ctx* c, uint64_t B, const uint8_t* d_msg, const uint8_t* d_proofs, const uint64_t* d_off, const uint32_t* d_which, const uint8_t* d_blinder,
-                               int rng_mode, const uint8_t* d_rng, uint64_t stride, uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_off, int32_t* d_status) {
+                               const zk_rng& rng, uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_off, int32_t* d_status) {   // (rng.data: a device pointer)
     if (zk_status zs = rering_refusal(c)) return zs;
-    if ((rng_mode != ZK_RNG_SEED && rng_mode != ZK_RNG_STREAM) || B > 0xffffffffull || ((uintptr_t)d_proofs & 3) || ((uintptr_t)d_out & 3)) return ZK_E_ARG;
+    if (!rng_mode_ok(&rng) || B > 0xffffffffull || ((uintptr_t)d_proofs & 3) || ((uintptr_t)d_out & 3)) return ZK_E_ARG;
     hipStream_t s0 = c->stream;
     timing_begin(c);
     if (B == 0) {
@@ -155,29 +150,8 @@ static zk_status rering_device(zk_ctx* c, uint64_t B, const uint8_t* d_msg, cons
         W.gk_fill0 = 0;   // the caller-blinder contract of zk_member_prove_batch: the 5 n draws start at fill 0
         W.gk_stmt = full ? GK_STMT_FULL : GK_STMT_NONE, W.ring_digest = c->ring->ring_digest, W.wire = wire_make(c->wire != 0);
         W.Rx = X.Rx, W.Ry = X.Ry, W.la.ax = X.kax, W.la.ay = X.kay;
-        const uint32_t nblk = 5 * W.n + RNG_MAX_EXC;
-        W.rng.seeds = d_rng, W.rng.stream = d_rng, W.rng.stride_blocks = stride, W.rng.mode = rng_mode, W.rng.sec = -1, W.rng.proof_base = (uint32_t)first;
-        {
-            MaybeScope t(timed, c, "rng_prepass", s);
-            launch_rng_prepass(s, W, cnt, 0, nblk, nblk, rng_mode == 0 ? W.rng_fill : nullptr, false);
-        }
-        if (rng_mode == 0) W.rng.mode = 1, W.rng.stream = (const uint8_t*)W.rng_fill, W.rng.stride_blocks = nblk, W.rng.proof_base = 0;
-        const ChunkIn in{nullptr, nullptr, nullptr, L.which_s, cnt};
-        const uint32_t nc = cnt * (4 * W.n + 1);
-        {
-            MaybeScope t(timed, c, "gk_fold", s);
-            launch_rr_front(s, W, X, cnt, first, d_proofs, d_off, d_which, d_blinder, L.which_s);
-            launch_gk_scalars_fold(s, W, in, L.gk_am);
-            launch_gk_cd_scalars(s, W, cnt);
-        }
-        {
-            MaybeScope t(timed, c, "tom_commit", s);
-            launch_tom_commit(s, c->P, W.lc, nc, 1, 1);
-        }
-        {
-            MaybeScope t(timed, c, "tom_normalize", s);
-            launch_tom_normalize(s, W.lc, nc, 0, 1, 1);
-        }
+        member_chunk_rng(c, timed, s, W, rng, first, cnt);
+        const ChunkIn in = member_chunk_commit(c, timed, s, W, L, cnt, [&] { launch_rr_front(s, W, X, cnt, first, d_proofs, d_off, d_which, d_blinder, L.which_s); });
         {
             MaybeScope t(timed, c, "rr_offsets", s);
             launch_rr_compare(s, W, X, cnt, first, d_status);
@@ -204,10 +178,7 @@ static zk_status rering_device(zk_ctx* c, uint64_t B, const uint8_t* d_msg, cons
             launch_gk_respond(s, W, in, d_out);
         }
     }
-    for (uint32_t l = 0; l < NL; l++) {
-        const hipError_t e = hipStreamSynchronize(c->pl[l].stream);
-        if (he == hipSuccess) he = e;
-    }
+    if (const hipError_t e = drain_lanes(c, NL); he == hipSuccess) he = e;
     if (he != hipSuccess) wipe_witness(c);   // a failed call leaves no blinder, nonce or RNG block behind
     HIPCHK(c, he);
     HIPCHK(c, hipGetLastError());
@@ -218,8 +189,8 @@ extern "C" zk_status zk_proof_rering_batch_device(zk_ctx* c, uint64_t B, const v
                                                   const zk_rng* rng, void* d_out, uint64_t out_cap, void* d_out_off, void* d_status) {
     if (!c || !rng || !d_out_off || (B && (!d_msg || !d_proofs || !d_off || !d_which || !d_blinder || !rng->data || !d_out || !d_status))) return ZK_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    return rering_device(c, B, (const uint8_t*)d_msg, (const uint8_t*)d_proofs, (const uint64_t*)d_off, (const uint32_t*)d_which, (const uint8_t*)d_blinder, rng->mode,
-                         rng->data, rng->stride_blocks, (uint8_t*)d_out, out_cap, (uint64_t*)d_out_off, (int32_t*)d_status);
+    return rering_device(c, B, (const uint8_t*)d_msg, (const uint8_t*)d_proofs, (const uint64_t*)d_off, (const uint32_t*)d_which, (const uint8_t*)d_blinder, *rng,
+                         (uint8_t*)d_out, out_cap, (uint64_t*)d_out_off, (int32_t*)d_status);
 }
 // Host pointers: the batch is staged in HBM -- the small arrays in the context's input buffer (blinders and seeds: wiped with it), the proofs in its staging
 // buffers -- and takes the device path.  The headers are read here first, so out_cap is decided (by the census' rule) and the output staged at its size.
@@ -240,7 +211,7 @@ extern "C" zk_status zk_proof_rering_batch(zk_ctx* c, uint64_t B, const uint8_t*
     if (!c || !rng || !out_off || !off || (B && (!msg || !proofs || !which || !blinder || !rng->data || !out || !status))) return ZK_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     if (zk_status zs = rering_refusal(c)) return zs;
-    if ((rng->mode != ZK_RNG_SEED && rng->mode != ZK_RNG_STREAM) || B > 0xffffffffull) return ZK_E_ARG;
+    if (!rng_mode_ok(rng) || B > 0xffffffffull) return ZK_E_ARG;
     if (B == 0) {
         out_off[0] = 0;
         return ZK_OK;
@@ -259,31 +230,20 @@ extern "C" zk_status zk_proof_rering_batch(zk_ctx* c, uint64_t B, const uint8_t*
         c->err = "output buffer too small";
         return ZK_E_BUFFER;
     }
-    const size_t rng_bytes = rng->mode == ZK_RNG_SEED ? 32 * B : 32 * B * rng->stride_blocks;
     RrIn I;
-    if (zk_status zs = lay_out(c, B_in, [&](uint8_t* base) { return rering_in_layout(I, base, B, rng_bytes); })) return zs;
+    if (zk_status zs = lay_out(c, B_in, [&](uint8_t* base) { return rering_in_layout(I, base, B, rng_bytes(rng, B)); })) return zs;
     if (zk_status zs = reserve(c, B_io, in_bytes + 32)) return zs;
     if (!in_place)
         if (zk_status zs = reserve(c, B_ro, need + 32)) return zs;
     uint8_t *const d_proofs = (uint8_t*)c->buf[B_io].p, *const d_out = in_place ? d_proofs : (uint8_t*)c->buf[B_ro].p;
     // from the first upload on, blinders and seeds lie in the input buffer: every failure below zeroes them
-    const struct { void* d; const void* h; size_t n; } up[] = {{I.msg, msg, 32 * B}, {I.blinder, blinder, 32 * B}, {I.rng, rng->data, rng_bytes}, {I.which, which, 4 * B},
-                                                                {I.off, off, 8 * (B + 1)}, {d_proofs, proofs, in_bytes}};
-    for (auto& u : up)
-        if (u.n && hipMemcpy(u.d, u.h, u.n, hipMemcpyHostToDevice) != hipSuccess) {
-            c->err = "upload of the inputs failed";
-            (void)hipGetLastError();
-            wipe_witness(c);
-            return ZK_E_DEVICE;
-        }
-    if (zk_status zs = rering_device(c, B, I.msg, d_proofs, I.off, I.which, I.blinder, rng->mode, I.rng, rng->stride_blocks, d_out, need, I.out_off, I.st)) {
+    if (zk_status zs = upload_or_wipe(c, {{I.msg, msg, 32 * B}, {I.blinder, blinder, 32 * B}, {I.rng, rng->data, rng_bytes(rng, B)}, {I.which, which, 4 * B},
+                                          {I.off, off, 8 * (B + 1)}, {d_proofs, proofs, in_bytes}}))
+        return zs;
+    if (zk_status zs = rering_device(c, B, I.msg, d_proofs, I.off, I.which, I.blinder, zk_rng{rng->mode, I.rng, rng->stride_blocks}, d_out, need, I.out_off, I.st)) {
         wipe_witness(c);
         return zs;
     }
-    hipError_t e = hipMemcpy(out_off, I.out_off, 8 * (B + 1), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(status, I.st, 4 * B, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && (in_place ? need : out_off[B])) e = hipMemcpy(out, d_out, in_place ? need : out_off[B], hipMemcpyDeviceToHost);
-    if (e != hipSuccess) wipe_witness(c);
-    HIPCHK(c, e);
-    return ZK_OK;
+    if (zk_status zs = download_or_wipe(c, {{I.out_off, out_off, 8 * (B + 1)}, {I.st, status, 4 * B}})) return zs;
+    return download_or_wipe(c, {{d_out, out, in_place ? need : out_off[B]}});   // (out_off[B] has arrived)
 }

@@ -303,6 +303,47 @@ struct DevBuf {
     T* as() const { return (T*)p; }
 };
 void wipe_witness(zk_ctx* c);   // api.hip: zeroes every witness-derived buffer of the context (nothing may be in flight)
+// lanes 0 .. NL-1 drained: the first error one of their streams gave
+static inline hipError_t drain_lanes(zk_ctx* c, uint32_t NL) {
+    hipError_t first = hipSuccess;
+    for (uint32_t l = 0; l < NL; l++) {
+        const hipError_t e = hipStreamSynchronize(c->pl[l].stream);
+        if (first == hipSuccess) first = e;
+    }
+    return first;
+}
+static inline bool rng_mode_ok(const zk_rng* rng) { return rng->mode == ZK_RNG_SEED || rng->mode == ZK_RNG_STREAM; }
+static inline size_t rng_bytes(const zk_rng* rng, uint64_t B) { return rng->mode == ZK_RNG_SEED ? 32 * B : 32 * B * rng->stride_blocks; }   // what rng->data holds for B proofs
+// The blocking copies of a host-pointer call whose staged inputs are witness-derived (signatures, blinders, seeds in c->buf[B_in]): rows of no bytes are
+// skipped, and a failed copy zeroes every witness-derived buffer before the call returns.
+struct UploadRow {
+    void* dev;
+    const void* host;
+    size_t bytes;
+};
+struct DownloadRow {
+    const void* dev;
+    void* host;
+    size_t bytes;
+};
+static inline zk_status upload_or_wipe(zk_ctx* c, std::initializer_list<UploadRow> rows) {
+    for (auto& r : rows)
+        if (r.bytes && hipMemcpy(r.dev, r.host, r.bytes, hipMemcpyHostToDevice) != hipSuccess) {
+            c->err = "upload of the inputs failed";
+            (void)hipGetLastError();
+            wipe_witness(c);
+            return ZK_E_DEVICE;
+        }
+    return ZK_OK;
+}
+static inline zk_status download_or_wipe(zk_ctx* c, std::initializer_list<DownloadRow> rows) {
+    hipError_t e = hipSuccess;
+    for (auto& r : rows)
+        if (e == hipSuccess && r.bytes) e = hipMemcpy(r.host, r.dev, r.bytes, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) wipe_witness(c);
+    HIPCHK(c, e);
+    return ZK_OK;
+}
 zk_status ensure_workspace(zk_ctx* c, uint32_t C, uint32_t nlanes = 1);   // api.hip: prover workspaces of lanes 0..nlanes-1
 hipError_t malloc_or_shed(zk_ctx* c, void** p, size_t bytes);   // api.hip: a workspace allocation that sheds the optional per-ring tables first
 // settings a queued streamed job was planned with (its lane rotation, chunk size, workspaces, mode) and the buffers it reads stay frozen until it is waited for

@@ -48,14 +48,7 @@ struct ProveJob {
     static double host_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
     uint32_t lane_of(uint64_t k) const { return (uint32_t)((lane_base + k) % NL); }
-    hipError_t sync_lanes() {
-        hipError_t r = hipSuccess;
-        for (uint32_t l = 0; l < NL; l++) {
-            hipError_t e = hipStreamSynchronize(c->pl[l].stream);
-            if (r == hipSuccess) r = e;
-        }
-        return r;
-    }
+    hipError_t sync_lanes() { return drain_lanes(c, NL); }
     zk_status stage1(uint64_t chunk_no);
     zk_status stage2(uint64_t chunk_no);
 };
