@@ -48,6 +48,9 @@ export function proveSignatureLists(params: SystemParametersList, msgHashes: Uin
  *  over the same keyXcom.  whichNew[i]: the index of proof i's key in `keys`; keyBlinders[i]: the blinder of its keyXcom (keyBlinders).  Throws for the first proof
  *  that fails.  Two GKProofs over one keyXcom place the key in the intersection of the two rings. */
 export function reringSignatureLists(params: SystemParametersList, msgHashes: Uint8Array[], proofs: (SignatureProofList | Buffer)[], whichNew: number[], keyBlinders: Uint8Array[], keys: bigint[] | Buffer): Promise<SignatureProofList[]>
+/** ... with one key list per proof (zk_proof_rering_batch_rings; rings named as in proveSignatureLists / verifySignatureLists): proof i moves to keyLists[i],
+ *  whichNew[i] indexes that list; the lists are made resident, the active ring is not touched. */
+export function reringSignatureLists(params: SystemParametersList, msgHashes: Uint8Array[], proofs: (SignatureProofList | Buffer)[], whichNew: number[], keyBlinders: Uint8Array[], keyLists: (bigint[] | Buffer)[]): Promise<SignatureProofList[]>
 /** zk_prove_key_blinders: the blinders of keyXcom in the proofs made from `seeds` (B x 32 bytes, or one Uint8Array(32) per proof); as secret as the seeds */
 export function keyBlinders(seeds: Buffer | Uint8Array[], params?: SystemParametersList): Promise<Buffer[]>
 /** the witness screen (zk_screen_batch_rings): before a proof is paid for, where the signer's key stands in `keys` (`which` absent: the lowest index is found; given: that
@@ -139,6 +142,8 @@ export class Engine {
     keyBlinders(seeds: Buffer): Buffer[]
     /** zk_proof_rering_batch: proofs moved to the ACTIVE ring; seeds must be fresh (default: crypto.randomBytes).  status 16: the index and blinder do not open keyXcom */
     reringBatch(msg: Buffer, proofs: Buffer[], whichNew: number[] | Uint32Array, blinders: Buffer, seeds?: Buffer): { proofs: (Buffer | null)[]; status: Int32Array }
+    /** zk_proof_rering_batch_rings: proof i moved to the RESIDENT ring ringIds[i], the active ring neither read nor changed; a proof whose status is not 0 is null */
+    reringBatchRings(msg: Buffer, proofs: Buffer[], whichNew: number[] | Uint32Array, ringIds: number[] | Uint32Array, blinders: Buffer, seeds?: Buffer): { proofs: (Buffer | null)[]; status: Int32Array }
     keysToInts(pkxy: Buffer): { keys: Buffer; status: Buffer }
     proveBatch(msg: Buffer, sig: Buffer, pk: Buffer, which: number[] | Buffer, seeds?: Buffer): Buffer[]
     verifyBatch(msg: Buffer, proofs: Buffer[], seeds?: Buffer): Verdicts

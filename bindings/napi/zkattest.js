@@ -440,6 +440,17 @@ class Engine {
         const st = i32(r.status), o = u64(r.off)
         return { proofs: Array.from(st, (s, i) => (s === 0 ? r.proofs.slice(Number(o[i]), Number(o[i + 1])) : null)), status: st }
     }
+    // zk_proof_rering_batch_rings: proof i moved to the RESIDENT ring ringIds[i]; the active ring is neither read nor changed.  A proof whose status is not 0
+    // comes back as null (its slot in the call's output is empty or zero-filled).  seeds must be FRESH (default: crypto.randomBytes)
+    reringBatchRings(msg, proofs, whichNew, ringIds, blinders, seeds) {
+        const B = proofs.length, off = Buffer.alloc(8 * (B + 1))
+        let run = 0
+        proofs.forEach((p, i) => { run += p.length; off.writeBigUInt64LE(BigInt(run), 8 * (i + 1)) })
+        const r = native.reringBatchRings(this.h, msg, Buffer.concat(proofs), off, Buffer.from(Uint32Array.from(whichNew).buffer), Buffer.from(Uint32Array.from(ringIds).buffer), blinders,
+            seeds || crypto.randomBytes(32 * B))
+        const st = i32(r.status), o = u64(r.off)
+        return { proofs: Array.from(st, (s, i) => (s === 0 ? r.proofs.slice(Number(o[i]), Number(o[i + 1])) : null)), status: st }
+    }
     proveBatchRingsAsync(msg, sig, pk, which, ringIds, seeds) { return this._chain(() => this._proveRingsNow(msg, sig, pk, which, ringIds, seeds)) }
     verifyBatchRingsAsync(msg, proofs, ringIds, seeds) { return this._chain(() => this._verifyRingsNow(msg, proofs, ringIds, seeds)) }
     proveBatchAsync(msg, sig, pk, which, seeds) { return this._chain(() => this._proveNow(msg, sig, pk, which, seeds)) }
@@ -694,6 +705,7 @@ async function reringSignatureLists(params, msgHashes, proofs, whichNew, keyBlin
     const raw = proofs.map((p) => (p instanceof SignatureProofList ? p.bytes : p))
     for (const b of raw) if (!wellFormedProof(b)) throw new Error('error deserializing')
     for (const k of keyBlinders) if (!((Buffer.isBuffer(k) || k instanceof Uint8Array) && k.length === 32)) throw new TypeError('a key blinder is a Uint8Array(32)')
+    if (isKeyLists(keys)) return reringToLists(params, msgHashes, raw, whichNew, keyBlinders, keys)
     checkRingSize(Buffer.isBuffer(keys) ? keys.length / 32 : keys.length, true)
     const idx = [[], []], out = new Array(B)   // a context works in ONE layout at a time: split by the proofs' magic like the verifier
     raw.forEach((b, i) => idx[isPacked(b) ? 1 : 0].push(i))
@@ -703,6 +715,37 @@ async function reringSignatureLists(params, msgHashes, proofs, whichNew, keyBlin
         const msg = Buffer.concat(sel.map((i) => Buffer.from(msgHashes[i]))), bl = Buffer.concat(sel.map((i) => Buffer.from(keyBlinders[i])))
         const r = await engineFor(params, keys).withRing((engine) => { useWire(engine, wire); return engine.reringBatch(msg, sel.map((i) => raw[i]), sel.map((i) => whichNew[i]), bl) })
         sel.forEach((i, k) => { if (r.status[k] !== 0) throw statusError(r.status[k]); out[i] = new SignatureProofList(r.proofs[k]) })
+    }
+    return out
+}
+// `keys` of reringSignatureLists as one key list PER PROOF (an array of bigint[] / Buffer, as proveSignatureLists and verifySignatureLists name rings): proof i
+// moves to keys[i] and whichNew[i] indexes that list.  The lists are made resident through the same cache (residentRings at a time: a call that names more is
+// split by ring) and every layout's proofs of a group go through ONE zk_proof_rering_batch_rings; the active ring is not touched.
+const isKeyLists = (keys) => Array.isArray(keys) && keys.length > 0 && (Array.isArray(keys[0]) || Buffer.isBuffer(keys[0]))
+async function reringToLists(params, msgHashes, raw, whichNew, keyBlinders, keyLists) {
+    const B = raw.length
+    if (keyLists.length !== B) throw new RangeError('reringSignatureLists: one key list per proof')
+    const rings = [], ringOfProof = new Array(B), byTag = new Map()
+    keyLists.forEach((keys, i) => {
+        checkRingSize(Buffer.isBuffer(keys) ? keys.length / 32 : keys.length, true)
+        const r = ringOf(keys)
+        if (!byTag.has(r.tag)) { byTag.set(r.tag, rings.length); rings.push(r) }
+        ringOfProof[i] = byTag.get(r.tag)
+    })
+    const { withRings, capacity } = engineFor(params, keyLists[0])
+    const out = new Array(B), per = capacity()
+    for (let g = 0; g < rings.length; g += per) {   // groups of at most residentRings rings
+        for (const wire of [0, 1]) {
+            const sel = []
+            raw.forEach((b, i) => { if (ringOfProof[i] >= g && ringOfProof[i] < g + per && (isPacked(b) ? 1 : 0) === wire) sel.push(i) })
+            if (!sel.length) continue
+            const msg = Buffer.concat(sel.map((i) => Buffer.from(msgHashes[i]))), bl = Buffer.concat(sel.map((i) => Buffer.from(keyBlinders[i])))
+            const r = await withRings(rings.slice(g, g + per), (engine, ids) => {
+                useWire(engine, wire)
+                return engine.reringBatchRings(msg, sel.map((i) => raw[i]), sel.map((i) => whichNew[i]), sel.map((i) => ids[ringOfProof[i] - g]), bl)
+            })
+            sel.forEach((i, k) => { if (r.status[k] !== 0) throw statusError(r.status[k]); out[i] = new SignatureProofList(r.proofs[k]) })
+        }
     }
     return out
 }

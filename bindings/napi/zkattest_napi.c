@@ -1317,6 +1317,54 @@ static napi_value ReringBatch(napi_env env, napi_callback_info info) {
     return v;
 }
 
+/* zk_proof_rering_batch_rings: (h, msg: B x 32, proofs: the B proofs back to back, off: (B + 1) u64 LE, whichNew: B u32 LE, ringIds: B u32 LE -- resident rings,
+ * blinders: B x 32, seeds: B x 32 -- FRESH) -> {proofs: every slot back to back (a proof that failed behind the header checks keeps a slot of zero bytes),
+ * off: (B + 1) u64 LE, status: B i32 LE}.  The active ring is neither read nor changed. */
+static napi_value ReringBatchRings(napi_env env, napi_callback_info info) {
+    napi_value argv[8];
+    if (!get_args(env, info, 8, argv)) return NULL;
+    Handle *h = get_handle(env, argv[0], 0);
+    uint8_t *msg, *blob, *ob, *wb, *ib, *bl, *seeds;
+    size_t lm, lp, lo, lw, li, lb, ls;
+    if (!h || !get_bytes(env, argv[1], &msg, &lm) || !get_bytes(env, argv[2], &blob, &lp) || !get_bytes(env, argv[3], &ob, &lo) || !get_bytes(env, argv[4], &wb, &lw) ||
+        !get_bytes(env, argv[5], &ib, &li) || !get_bytes(env, argv[6], &bl, &lb) || !get_bytes(env, argv[7], &seeds, &ls))
+        return NULL;
+    const size_t B = lw / 4;
+    if (lw % 4 || li != 4 * B || lm != 32 * B || lb != 32 * B || ls != 32 * B || lo != 8 * (B + 1)) {
+        napi_throw_range_error(env, NULL, "reringBatchRings: per proof 32 message bytes, one u32 index, one u32 ring id, 32 blinder bytes and 32 seed bytes; B + 1 offsets");
+        return NULL;
+    }
+    zk_ctx *c = zk_pool_ctx(h->pool, 0);
+    const size_t small = 8 * (B + 1) * 2 + 12 * B;
+    uint32_t *ids_tmp = (uint32_t *)xmalloc(env, 4 * B + 8);
+    if (!ids_tmp) return NULL;
+    if (B) memcpy(ids_tmp, ib, 4 * B);
+    uint64_t cap = lp;   /* every head as it is plus a new GKProof section of its destination ring's size */
+    for (size_t b = 0; b < B; b++) cap += zk_member_proof_size_ring(c, ids_tmp[b]);
+    uint8_t *buf = (uint8_t *)xmalloc(env, small + cap + 8);   /* (a Buffer's bytes need not be aligned: offsets, indices and ids are copied) */
+    if (!buf) {
+        free(ids_tmp);
+        return NULL;
+    }
+    uint64_t *off = (uint64_t *)buf, *out_off = off + (B + 1);
+    uint32_t *which = (uint32_t *)(out_off + (B + 1)), *ids = which + B;
+    int32_t *status = (int32_t *)(ids + B);
+    uint8_t *out = buf + small;
+    memcpy(off, ob, 8 * (B + 1));
+    if (B) memcpy(which, wb, 4 * B), memcpy(ids, ids_tmp, 4 * B);
+    free(ids_tmp);
+    zk_rng rng = {ZK_RNG_SEED, seeds, 0};
+    zk_status st = zk_proof_rering_batch_rings(c, B, msg, blob, off, which, ids, bl, &rng, out, cap, out_off, status);
+    napi_value v = NULL;
+    if (st != ZK_OK) throw_text(env, st, zk_last_error(c));
+    else if (napi_create_object(env, &v) == napi_ok) {
+        set_prop(env, v, "proofs", new_buffer(env, out, (size_t)out_off[B])), set_prop(env, v, "off", new_buffer(env, out_off, 8 * (B + 1)));
+        set_prop(env, v, "status", new_buffer(env, status, 4 * B));
+    }
+    free(buf);
+    return v;
+}
+
 static napi_value Init(napi_env env, napi_value exports) {
     static const struct {
         const char *name;
@@ -1337,7 +1385,7 @@ static napi_value Init(napi_env env, napi_value exports) {
                {"memberProofSizeRing", MemberProofSizeRing}, {"memberProveBatchRings", MemberProveBatchRings}, {"memberVerifyBatchRings", MemberVerifyBatchRings},
                {"memberProveBatchBound", MemberProveBatchBound}, {"memberVerifyBatchBound", MemberVerifyBatchBound},
                {"memberProveBatchRingsBound", MemberProveBatchRingsBound}, {"memberVerifyBatchRingsBound", MemberVerifyBatchRingsBound},
-               {"keyBlinders", KeyBlinders},     {"reringBatch", ReringBatch}};
+               {"keyBlinders", KeyBlinders},     {"reringBatch", ReringBatch},     {"reringBatchRings", ReringBatchRings}};
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;
         if (napi_create_function(env, fns[i].name, NAPI_AUTO_LENGTH, fns[i].fn, NULL, &f) != napi_ok) return NULL;

@@ -636,7 +636,30 @@ zk_status zk_member_verify_batch_rings_bound_device(zk_ctx *ctx, uint64_t B, con
  *   queued; B = 0 is ZK_OK (out_off[0] = 0); chunks (zk_ctx_set_chunk) on the context's lanes; both protocol modes.  The _device form takes every pointer and
  *   rng->data in this context's HBM (proofs and out 4-byte aligned, offsets 8-byte aligned).  zk_last_timing reports the member prover's families plus
  *   "rr_census", "rr_offsets" and "rr_move".  The staged blinders and RNG fills are witness-derived: zk_ctx_wipe, zk_ctx_destroy and a failed call zero them.
- *   Not provided: _rings, streamed and zk_pool_* forms.
+ *   Not provided: streamed and zk_pool_* forms.
+ * zk_proof_rering_batch_rings: one resident ring id per proof.  Proof b is moved to resident ring ring_ids[b]; the active ring is neither read nor changed,
+ *   so a context without an active ring can make the call.  Where proof b succeeds, its output bytes are byte for byte what zk_proof_rering_batch writes for
+ *   input b alone with that ring active, under the same rng row or seed -- in both protocol modes (in ZK_MODE_HARDENED the statement hashes the digest of
+ *   ring ring_ids[b]) and both wire layouts.  Per proof, the first rule that matches:
+ *     1. ring_ids[b] is not resident                      ZK_E_ARG, a zero-length slot (no byte of the proof is read)
+ *     2. the header or slot rules above fail              ZK_E_BAD_ENCODING, a zero-length slot (no byte beyond the header is read)
+ *     3. which_new[b] >= N of ITS ring                    ZK_E_ARG, a zero-length slot
+ *     4. the opening fails                                ZK_E_OPENING
+ *     5. the RNG stream is too short                      ZK_E_RNG_EXHAUSTED
+ *   The one difference from the one-ring call: the layout is fixed by ids and headers alone -- out_off[b + 1] - out_off[b] = head_b + gk(n of ring_ids[b])
+ *   for every proof that passes rules 1-3 and 0 otherwise, and a proof that then fails rule 4 or 5 KEEPS its slot, filled with zero bytes (ZK_E_BAD_ENCODING
+ *   to every verifier), instead of the slots behind it closing up.  A batch whose ids all name one ring follows the same rule: it belongs to the call, not
+ *   to the mix.  So every proof's place is known before anything is proved, and out_cap is decided exactly: ZK_E_BUFFER when out_cap < out_off[B], before a
+ *   byte of out, out_off or the statuses is written.
+ *   In place: out == proofs is allowed in both forms when every proof that passes rules 1-3 has the n of its destination ring; otherwise ZK_E_ARG, nothing
+ *   written.  Then only GKProof sections are rewritten, out_off is a copy of proof_off, a failed proof keeps its bytes and gets its status, no byte of a
+ *   repetition is read or written, and out_cap >= proof_off[B].  Any other overlap of out and proofs is ZK_E_ARG.
+ *   Call-level rules are zk_proof_rering_batch's, except that "no active ring" is no refusal: a context with params but no resident ring gives every proof
+ *   rule 1.  The _device form makes ONE read-back, of the census counters.  zk_last_timing reports the member prover's families plus "rr_census",
+ *   "rr_offsets", "rr_move" and "m_gather"; zk_test_counter 13 counts the windows (none for a batch of one ring without refusals, which runs on the caller's
+ *   arrays).  The gathered blinders, seeds and stream rows are witness-derived: a failed call, zk_ctx_wipe and zk_ctx_destroy zero them.
+ *   The host-pointer form stages proofs[0, end of the last slot it reads) in HBM as one copy: rules 1 and 2 say which bytes are PARSED, not which cross the link.
+ *   How: DESIGN.md section 5d'.
  * Two warnings.  (1) Two GKProofs over one keyXcom tell a verifier who sees both that the key lies in the INTERSECTION of the two rings: re-ringing to a ring
  *   that shares few keys with the old one gives most of the anonymity away to whoever holds both proofs.  (2) rng must be fresh and independent of the rng the
  *   proof was made with: with the original seeds, fill 0 and fill 1 of the new call are comS1's and keyXcom's blinders reused as GK nonces, and the responses
@@ -653,6 +676,13 @@ zk_status zk_proof_rering_batch(zk_ctx *ctx, uint64_t B, const uint8_t *msg_hash
 zk_status zk_proof_rering_batch_device(zk_ctx *ctx, uint64_t B, const void *d_msg_hash, const void *d_proofs, const void *d_proof_off /*u64[B+1]*/,
                                        const void *d_which_new /*u32[B]*/, const void *d_key_blinder_be32, const zk_rng *rng_device, void *d_out,
                                        uint64_t out_cap, void *d_out_off /*u64[B+1]*/, void *d_per_proof_status /*i32[B]*/);
+zk_status zk_proof_rering_batch_rings(zk_ctx *ctx, uint64_t B, const uint8_t *msg_hash /*Bx32*/, const uint8_t *proofs, const uint64_t *proof_off /*B+1*/,
+                                      const uint32_t *which_new /*B*/, const uint32_t *ring_ids /*B*/, const uint8_t *key_blinder_be32 /*Bx32*/, const zk_rng *rng,
+                                      uint8_t *out, uint64_t out_cap, uint64_t *out_off /*B+1*/, int32_t *per_proof_status /*B*/);
+zk_status zk_proof_rering_batch_rings_device(zk_ctx *ctx, uint64_t B, const void *d_msg_hash, const void *d_proofs, const void *d_proof_off /*u64[B+1]*/,
+                                             const void *d_which_new /*u32[B]*/, const void *d_ring_ids /*u32[B]*/, const void *d_key_blinder_be32,
+                                             const zk_rng *rng_device, void *d_out, uint64_t out_cap, void *d_out_off /*u64[B+1]*/,
+                                             void *d_per_proof_status /*i32[B]*/);
 
 /* ---- two (or more) batches in flight on one context.  zk_prove_batch / zk_verify_batch are synchronous: each call pays its own head
  * (no byte of a chunk exists before its stage 1 is over) and its own tail (the copies of the last slices, with nothing left to

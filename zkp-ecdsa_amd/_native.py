@@ -33,6 +33,7 @@ SYMBOLS = [
     'zk_member_prove_batch_bound', 'zk_member_prove_batch_bound_device', 'zk_member_verify_batch_bound', 'zk_member_verify_batch_bound_device',
     'zk_member_prove_batch_rings_bound', 'zk_member_prove_batch_rings_bound_device', 'zk_member_verify_batch_rings_bound', 'zk_member_verify_batch_rings_bound_device',
     'zk_prove_key_blinders', 'zk_prove_key_blinders_device', 'zk_proof_rering_batch', 'zk_proof_rering_batch_device',
+    'zk_proof_rering_batch_rings', 'zk_proof_rering_batch_rings_device',
     'zk_test_field_op', 'zk_test_tom_commit', 'zk_test_p256_fixed_mul', 'zk_test_sha256', 'zk_test_rng_draws', 'zk_test_exp_sum',
 ]
 
@@ -167,6 +168,8 @@ def lib():
         L.zk_prove_key_blinders_device.argtypes = [vp, u64, C.POINTER(ZkRng), vp]
         L.zk_proof_rering_batch.argtypes = [vp, u64, C.c_char_p, vp, vp, vp, C.c_char_p, C.POINTER(ZkRng), vp, u64, vp, vp]
         L.zk_proof_rering_batch_device.argtypes = [vp, u64, vp, vp, vp, vp, vp, C.POINTER(ZkRng), vp, u64, vp, vp]
+        L.zk_proof_rering_batch_rings.argtypes = [vp, u64, C.c_char_p, vp, vp, vp, vp, C.c_char_p, C.POINTER(ZkRng), vp, u64, vp, vp]
+        L.zk_proof_rering_batch_rings_device.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp, C.POINTER(ZkRng), vp, u64, vp, vp]
         L.zk_ring_digest.argtypes = [vp, vp]
         L.zk_hardened_h.argtypes = [C.c_char_p, u64, vp, vp]
         L.zk_pool_create.argtypes = [C.POINTER(C.c_int), i32, C.POINTER(vp)]
@@ -1005,6 +1008,54 @@ class Engine:
         """zk_proof_rering_batch_device: every pointer a device address; d_out == d_proofs re-rings in place"""
         rng = ZkRng(mode, d_rng, stride_blocks)
         self._chk(self.L.zk_proof_rering_batch_device(self.h, B, d_msg, d_proofs, d_off, d_which_new, d_key_blinders, C.byref(rng), d_out, out_cap, d_out_off, d_status))
+
+    def rering_batch_rings(self, msg, proofs, which_new, ring_ids, key_blinders, seeds=None, streams=None, stream_blocks=0, in_place=False, cap=None):
+        """zk_proof_rering_batch_rings: rering_batch with one resident ring id per proof -- proof b is moved to ring ring_ids[b], the active ring is neither
+        read nor changed.  Every proof that passes the id, header and index checks has a slot of its own: a proof that then fails (opening, RNG stream) is
+        returned as None and its slot holds zero bytes.  The offsets and the raw output are kept in self.rering_last_off / self.rering_last_raw.
+        in_place: as in rering_batch, when every proof's n is its destination ring's."""
+        B = len(proofs)
+        if len(which_new) != B or len(ring_ids) != B:
+            raise ValueError('one index and one ring id per proof')
+        if not isinstance(key_blinders, (bytes, bytearray, memoryview)):
+            key_blinders = b''.join(bytes(x) for x in key_blinders)
+        if len(key_blinders) != 32 * B or len(msg) != 32 * B:
+            raise ValueError('msg and key_blinders must hold 32 bytes per proof')
+        if seeds is None and streams is None:
+            seeds = os.urandom(32 * B)
+        rng, data = self._rng(B, seeds, streams, stream_blocks)
+        blob = b''.join(proofs)
+        off = (C.c_uint64 * (B + 1))()
+        o = 0
+        for b, p in enumerate(proofs):
+            off[b] = o
+            o += len(p)
+        off[B] = o
+        w = (C.c_uint32 * max(B, 1))(*which_new)
+        ids = (C.c_uint32 * max(B, 1))(*ring_ids)
+        st = (C.c_int32 * max(B, 1))()
+        out_off = (C.c_uint64 * (B + 1))()
+        if in_place:
+            buf = C.create_string_buffer(blob, max(len(blob), 1))
+            self._chk(self.L.zk_proof_rering_batch_rings(self.h, B, bytes(msg), buf, off, w, ids, bytes(key_blinders), C.byref(rng), buf, len(blob) if cap is None else cap,
+                                                         out_off, st))
+            raw = buf.raw[:len(blob)]
+            self.rering_last_off, self.rering_last_raw = list(out_off), raw
+            return [raw[out_off[b]:out_off[b + 1]] for b in range(B)], list(st)[:B]
+        if cap is None:   # every head as it is plus a GKProof section of the largest resident ring's size (n <= 63)
+            cap = len(blob) + B * max([self.member_proof_size(r) for r in set(ring_ids)] + [0])
+        out = C.create_string_buffer(max(cap, 1))
+        self._chk(self.L.zk_proof_rering_batch_rings(self.h, B, bytes(msg), blob, off, w, ids, bytes(key_blinders), C.byref(rng), out, cap, out_off, st))
+        assert out_off[0] == 0 and all(out_off[b] <= out_off[b + 1] for b in range(B))
+        raw = out.raw[:out_off[B]]
+        self.rering_last_off, self.rering_last_raw = list(out_off), raw
+        return [raw[out_off[b]:out_off[b + 1]] if st[b] == 0 else None for b in range(B)], list(st)[:B]
+
+    def rering_batch_rings_device(self, B, d_msg, d_proofs, d_off, d_which_new, d_ring_ids, d_key_blinders, d_rng, d_out, out_cap, d_out_off, d_status, mode=0, stride_blocks=0):
+        """zk_proof_rering_batch_rings_device: every pointer a device address; d_out == d_proofs re-rings in place"""
+        rng = ZkRng(mode, d_rng, stride_blocks)
+        self._chk(self.L.zk_proof_rering_batch_rings_device(self.h, B, d_msg, d_proofs, d_off, d_which_new, d_ring_ids, d_key_blinders, C.byref(rng), d_out, out_cap,
+                                                            d_out_off, d_status))
 
     def synth_params(self, seed):
         a, b, c = C.create_string_buffer(64), C.create_string_buffer(72), C.create_string_buffer(72)

@@ -184,6 +184,7 @@ extern "C" void zk_ctx_destroy(zk_ctx* c) {
     if (c->h_mr) hipHostFree(c->h_mr);
     if (c->mr_ready) hipEventDestroy(c->mr_ready);
     if (c->h_rr) hipHostFree(c->h_rr);
+    if (c->h_rrr) hipHostFree(c->h_rrr);
     for (hipEvent_t e : c->rr_scan)
         if (e) hipEventDestroy(e);
     if (c->h_stage) hipHostFree(c->h_stage);

@@ -47,8 +47,8 @@ enum GrowPolicy {
     X(unp_off, GROW_EXACT, false) /* ... and their per-chunk offsets */                                                                                           \
     X(m_off, GROW_SLACK, false)   /* membership proofs on their own: offsets of a verify call's equally long proofs */                                            \
     X(vp, GROW_SLACK, false)      /* exhaustive verify mode: verdicts and statuses of a pass behind the first (5 B bytes), until they are merged */           \
-    X(mr, GROW_EXACT, false)      /* mixed-ring membership calls (api_member.hip): classes, per-workgroup counters, permutation */                                \
-    X(mw, GROW_SHED, true)        /* ... the window one ring's inputs are gathered into: indices, blinders, seeds or RNG streams; coms, offsets, verifier seeds */ \
+    X(mr, GROW_EXACT, false)      /* mixed-ring membership and re-ring calls (api_member.hip, api_rering.hip): classes, per-workgroup counters, permutation */    \
+    X(mw, GROW_SHED, true)        /* ... the window one ring's inputs are gathered into: indices, blinders, seeds or RNG streams; coms, offsets, verifier seeds; message hashes */ \
     X(rr, GROW_EXACT, false)      /* re-ring calls (api_rering.hip): the census counters and every lane's per-proof arrays (head lengths, keyXcom, R: public) */ \
     X(ro, GROW_SPARE, false)      /* ... host-pointer form: staging of the re-ringed proofs (the input proofs lie in io) */ \
     X(kb, GROW_ONCE, true)        /* zk_prove_key_blinders: a chunk's rejection lists (derived from the seeds) and the call's exhaustion flag */
@@ -105,6 +105,7 @@ struct zk_ctx {
     uint32_t* h_mr = nullptr;      // mixed-ring membership calls (api_member.hip): page-locked read-back of the per-class counters
     hipEvent_t mr_ready = nullptr; // ... "the window is gathered": the lanes wait for it
     unsigned long long* h_rr = nullptr;   // re-ring calls (api_rering.hip): page-locked read-back of the census counters
+    uint8_t* h_rrr = nullptr;             // ... their mixed-ring form: of the census counters and the per-class totals (RRR_READBACK bytes)
     hipEvent_t rr_scan[ZK_MAX_LANES] = {};   // ... "this lane's chunk has written its offsets": the next chunk's scan, on another lane, starts behind it
     uint32_t pr_seg_force = 0;     // test build only (zk_test_set_prove_segment): proofs per segment instead of what ZK_PR_STAGE_BYTES holds; 0 = off
     uint32_t mode = 0;                 // zk_ctx_set_mode: ZK_MODE_REFERENCE / ZK_MODE_HARDENED

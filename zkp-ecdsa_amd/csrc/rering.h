@@ -3,28 +3,8 @@
 // header has what is new: the rule that says where a proof's GKProof section lies, a lane's per-proof arrays and the launch wrappers of the kernels around it.
 #pragma once
 #include "engine.h"
+#include "rering_plan.h"   // RrHead, rr_head: what a proof's header says; the plan of the mixed-ring form
 
-// What the header of the proof in slot [o0, o1) says, read from its first 16 bytes alone: the bytes in front of its GKProof section (`head`) and its n, or
-// ok = false where the slot is ZK_E_BAD_ENCODING for this call -- offsets that do not ascend or are not 4-byte aligned, a slot whose length is no multiple of 4 (no proof of either layout has one) or too short for a header, a
-// wrong magic, a total_len that is not the slot's length, n > 63, a total_len smaller than the fixed head plus the GKProof its n announces.
-struct RrHead {
-    bool ok;
-    uint32_t n, total, head;
-};
-ZK_HD static inline bool rr_slot_readable(uint64_t o0, uint64_t o1) { return o1 >= o0 && !(o0 & 3) && !((o1 - o0) & 3) && o1 - o0 >= ZK_HDR && o1 - o0 <= 0xffffffffull; }   // else no byte of it is read
-ZK_HD static inline RrHead rr_head(const uint8_t* proofs, uint64_t o0, uint64_t o1, const Wire& w) {
-    RrHead h{false, 0, 0, 0};
-    if (!rr_slot_readable(o0, o1)) return h;
-    uint32_t hw[4];
-    __builtin_memcpy(hw, proofs + o0, 16);
-    h.total = __builtin_bswap32(hw[1]), h.n = __builtin_bswap32(hw[3]);
-    if (hw[0] != w.magic || h.total != o1 - o0 || h.n > 63) return h;
-    const uint32_t gk = w.gk_n * h.n + 32;
-    if (h.total < w.fixed + gk) return h;
-    h.head = h.total - gk;
-    h.ok = true;
-    return h;
-}
 // a lane's per-proof arrays beside its member workspace; nothing here is witness-derived (keyXcom and R are public parts of the proofs)
 struct RrLane {
     uint32_t* kx;      // [C][18] keyXcom as the proof states it: x, then y, nine little-endian words each
@@ -48,3 +28,34 @@ void launch_rr_scan(hipStream_t s, const Workspace& W, const RrLane& X, uint32_t
 void launch_rr_place(hipStream_t s, const Workspace& W, const RrLane& X, uint32_t count, uint64_t first, uint64_t B, const uint64_t* off, uint64_t* out_off);
 void launch_rr_move(hipStream_t s, const RrLane& X, uint32_t count, uint64_t first, const uint8_t* proofs, const uint64_t* off, const uint64_t* out_off, uint32_t n_new,
                     uint8_t* out);
+
+// ------------------------------------------------------------------ one destination ring id per proof (k_rering_rings.hip; the plan is rering_plan.h's)
+// The census' arrays over the whole batch, and what the host reads back in ONE copy: RRR_HEAD_BYTES of counters followed by k_part_scan's 2 x MR_CLASSES words
+// (proofs per class, where each class starts in the permutation).
+struct RrCensus {
+    uint64_t* cnt;        // [4] the slots' bytes (= out_off[B]), proofs that pass rules 1-3 with another n than their ring's, proof_off[B], 0
+    uint32_t* cls_tot;    // [2 x MR_CLASSES] directly behind cnt
+    uint8_t* cls;         // [B]
+    uint32_t *len, *head; // [B] the output slot's length and the bytes in front of the GKProof section, 0 for a refusal
+    uint32_t* blk_cnt;    // [blocks][MR_CLASSES] per workgroup of MR_BLOCK proofs: proofs per class, then (k_part_scan) those of the workgroups before it
+    uint64_t* blk_bytes;  // [blocks + 1] ... the bytes of its slots, then (k_rrr_totals) of the workgroups before it
+    uint64_t* blk_other;  // [blocks] ... its proofs of another n
+    uint32_t* perm;       // [B]
+};
+#define RRR_HEAD_BYTES 32
+#define RRR_READBACK (RRR_HEAD_BYTES + 4 * 2 * MR_CLASSES)
+void launch_rrr_census(hipStream_t s, uint64_t B, const uint8_t* proofs, const uint64_t* off, const uint32_t* which, const uint32_t* ids, const Wire& wire, const RrRings& R,
+                       const RrCensus& X);
+// out_off (in place: a copy of proof_off) and the statuses of rules 1-3
+void launch_rrr_offsets(hipStream_t s, uint64_t B, const RrCensus& X, const uint64_t* proof_off, bool in_place, uint64_t* out_off, int32_t* status);
+void launch_rrr_perm(hipStream_t s, uint64_t B, const RrCensus& X);
+// every head of the batch to its place in one launch over [0, out_off[B]): k_rr_move's method with the per-proof n of the destination ring
+void launch_rrr_move(hipStream_t s, uint64_t B, const RrCensus& X, const RrRings& R, const uint8_t* proofs, const uint64_t* off, const uint64_t* out_off, uint8_t* out);
+// behind the windows: zero bytes in the slot of every proof whose final status is not ZK_OK (rules 4 and 5; the slots of rules 1-3 are empty)
+void launch_rrr_blank(hipStream_t s, uint64_t B, const uint64_t* out_off, const int32_t* status, uint8_t* out);
+// The sel-indexed forms of launch_rr_front / _compare / _place: window entry first + p is proof sel[first + p] of a batch of B (sel == nullptr: proof first + p).
+// which / blinder are the window's gathered arrays (entry first + p), proofs / off / out_off / status the batch's.
+void launch_rrr_front(hipStream_t s, const Workspace& W, const RrLane& X, uint32_t count, uint64_t first, const uint32_t* sel, uint64_t B, const uint8_t* proofs,
+                      const uint64_t* off, const uint32_t* which, const uint8_t* blinder, uint32_t* which_s);
+void launch_rrr_compare(hipStream_t s, const Workspace& W, const RrLane& X, uint32_t count, uint64_t first, const uint32_t* sel, uint64_t B, int32_t* status);
+void launch_rrr_place(hipStream_t s, const Workspace& W, const RrLane& X, uint32_t count, uint64_t first, const uint32_t* sel, uint64_t B, const uint64_t* out_off);
