@@ -103,6 +103,27 @@ export function proveMembershipLists(params: PedersenParams | SystemParametersLi
 export function proveMembershipLists(params: PedersenParams | SystemParametersList, coms: Commitment[], indices: number[], keysList: (bigint[] | Buffer)[], options: MemberBatchOptions): Promise<GKProof[]>
 export function verifyMembershipLists(params: PedersenParams | SystemParametersList, coms: Point[], keysList: (bigint[] | Buffer)[], proofs: GKProof[]): Promise<boolean[]>
 export function verifyMembershipLists(params: PedersenParams | SystemParametersList, coms: Point[], keysList: (bigint[] | Buffer)[], proofs: GKProof[], options: MemberBatchOptions): Promise<boolean[]>
+/** Link proofs ("ZKL1", zk_link_*): comA = key g + blinderA h and comB = key g + blinderB h hide the same key (src/commit/equality.ts).  A link proof
+ *  deliberately makes the two proofs linkable to anyone who sees it; the engine draws fresh seeds. */
+export class LinkProof {
+    constructor(bytes: Buffer)
+    readonly bytes: Buffer
+    readonly A_1: Point
+    readonly A_2: Point
+    readonly t_x: Scalar
+    readonly t_r1: Scalar
+    readonly t_r2: Scalar
+    eq(o: LinkProof): boolean
+}
+type LinkCom = Point | Commitment | Buffer
+type LinkScalar = Scalar | bigint | Uint8Array
+export function proveSameKey(params: PedersenParams | SystemParametersList, key: LinkScalar, comA: LinkCom, blinderA: LinkScalar, comB: LinkCom, blinderB: LinkScalar): Promise<LinkProof>
+export function verifySameKey(params: PedersenParams | SystemParametersList, comA: LinkCom, comB: LinkCom, link: LinkProof | Buffer): Promise<boolean>
+export function proveSameKeys(params: PedersenParams | SystemParametersList, keys: LinkScalar[], comsA: LinkCom[], blindersA: LinkScalar[], comsB: LinkCom[], blindersB: LinkScalar[]): Promise<LinkProof[]>
+export function verifySameKeys(params: PedersenParams | SystemParametersList, comsA: LinkCom[], comsB: LinkCom[], links: (LinkProof | Buffer)[]): Promise<boolean[]>
+/** keyXcom of a proof (either wire layout; zk_proof_key_commitments) */
+export function keyCommitment(proof: SignatureProofList | Buffer, params?: SystemParametersList): Promise<Point>
+export function keyCommitments(proofs: (SignatureProofList | Buffer)[], params?: SystemParametersList): Promise<Point[]>
 type Newable<T> = new (...args: any[]) => T
 export function writeJson<T>(type: Newable<T>, object: T): string
 export function readJson<T>(type: Newable<T>, text: string): T
@@ -144,6 +165,12 @@ export class Engine {
     reringBatch(msg: Buffer, proofs: Buffer[], whichNew: number[] | Uint32Array, blinders: Buffer, seeds?: Buffer): { proofs: (Buffer | null)[]; status: Int32Array }
     /** zk_proof_rering_batch_rings: proof i moved to the RESIDENT ring ringIds[i], the active ring neither read nor changed; a proof whose status is not 0 is null */
     reringBatchRings(msg: Buffer, proofs: Buffer[], whichNew: number[] | Uint32Array, ringIds: number[] | Uint32Array, blinders: Buffer, seeds?: Buffer): { proofs: (Buffer | null)[]; status: Int32Array }
+    /** zk_link_prove_batch: per entry a 32-byte key, two 72-byte commitments and their 32-byte blinders; seeds must be fresh (default: crypto.randomBytes).  status 16: the key and a blinder do not open a commitment */
+    linkProveBatch(keys: Buffer[], com1: Buffer[], blinder1: Buffer[], com2: Buffer[], blinder2: Buffer[], seeds?: Buffer): { proofs: (Buffer | null)[]; status: Int32Array }
+    /** zk_link_verify_batch */
+    linkVerifyBatch(com1: Buffer[], com2: Buffer[], proofs: Buffer[]): { ok: boolean[]; status: Int32Array }
+    /** zk_proof_key_commitments: keyXcom of proofs in the engine's wire layout, 72 bytes each; null where the status is not 0 */
+    keyCommitments(proofs: Buffer[]): { coms: (Buffer | null)[]; status: Int32Array }
     keysToInts(pkxy: Buffer): { keys: Buffer; status: Buffer }
     proveBatch(msg: Buffer, sig: Buffer, pk: Buffer, which: number[] | Buffer, seeds?: Buffer): Buffer[]
     verifyBatch(msg: Buffer, proofs: Buffer[], seeds?: Buffer): Verdicts

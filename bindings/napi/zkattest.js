@@ -451,6 +451,27 @@ class Engine {
         const st = i32(r.status), o = u64(r.off)
         return { proofs: Array.from(st, (s, i) => (s === 0 ? r.proofs.slice(Number(o[i]), Number(o[i + 1])) : null)), status: st }
     }
+    // link proofs (zk_link_*): "ZKL1", 256 bytes -- com1[i] and com2[i] (72-byte Tom-256 points) open to keys[i] under blinder1[i] / blinder2[i].  Arrays of Buffers
+    // -> { proofs: Buffer | null per entry, status: Int32Array }.  seeds must be FRESH: never the ones either commitment's proof was made with (default: crypto.randomBytes)
+    linkProveBatch(keys, com1, blinder1, com2, blinder2, seeds) {
+        const B = keys.length, cat = (a) => Buffer.concat(a.map((v) => Buffer.from(v)))
+        const r = native.linkProveBatch(this.h, cat(keys), cat(com1), cat(blinder1), cat(com2), cat(blinder2), seeds || crypto.randomBytes(32 * B))
+        const st = i32(r.status)
+        return { proofs: Array.from(st, (s, i) => (s === 0 ? r.proofs.slice(256 * i, 256 * i + 256) : null)), status: st }
+    }
+    linkVerifyBatch(com1, com2, proofs) {   // -> { ok: boolean[], status: Int32Array }
+        const r = native.linkVerifyBatch(this.h, Buffer.concat(com1), Buffer.concat(com2), Buffer.concat(proofs))
+        return { ok: Array.from(r.ok, (v) => v === 1), status: i32(r.status) }
+    }
+    // zk_proof_key_commitments: keyXcom of every proof (Buffers in the engine's wire layout) as a 72-byte point -> { coms: Buffer | null per entry, status: Int32Array }
+    keyCommitments(proofs) {
+        const B = proofs.length, off = Buffer.alloc(8 * (B + 1))
+        let run = 0
+        proofs.forEach((p, i) => { run += p.length; off.writeBigUInt64LE(BigInt(run), 8 * (i + 1)) })
+        const r = native.keyCommitments(this.h, Buffer.concat(proofs), off)
+        const st = i32(r.status)
+        return { coms: Array.from(st, (s, i) => (s === 0 ? r.coms.slice(72 * i, 72 * i + 72) : null)), status: st }
+    }
     proveBatchRingsAsync(msg, sig, pk, which, ringIds, seeds) { return this._chain(() => this._proveRingsNow(msg, sig, pk, which, ringIds, seeds)) }
     verifyBatchRingsAsync(msg, proofs, ringIds, seeds) { return this._chain(() => this._verifyRingsNow(msg, proofs, ringIds, seeds)) }
     proveBatchAsync(msg, sig, pk, which, seeds) { return this._chain(() => this._proveNow(msg, sig, pk, which, seeds)) }
@@ -1062,6 +1083,68 @@ async function verifyMembershipLists(pedersenParams, comPoints, keysList, proofs
     return out
 }
 
-module.exports = { reringSignatureLists, keyBlinders, proveMembership, verifyMembership, proveMemberships, verifyMemberships, proveMembershipLists, verifyMembershipLists, GKProof, Commitment, commit, screenSignatureLists, findKey, SCREEN, WHICH_NONE, recoverSignatureLists, recoverKey, RECOVER, verifySignatureLists, proveSignatureLists, _ringGenerations, setVerifyLevel, getVerifyLevel, setVerifyReps, getVerifyReps, generateParamsList, generateParamsListHardened, keyToInt, proveSignatureList, verifySignatureList, proveSignatureListBatch, verifySignatureListBatch,
+// ---------------------------------------------------------------- link proofs: two key commitments hide the same key (src/commit/equality.ts:27-116)
+// A LinkProof keeps the engine's ZKL1 bytes (include/zkattest.h) and materialises the reference's EqualityProof members (A_1, A_2: Points; t_x, t_r1, t_r2: Scalars).
+class LinkProof {
+    constructor(bytes) {
+        if (!(Buffer.isBuffer(bytes) && bytes.length === 256 && bytes.slice(0, 4).toString('latin1') === 'ZKL1' && bytes.readUInt32BE(4) === 256 && bytes.readUInt32BE(8) === 0 &&
+            bytes.readUInt32BE(12) === 0)) throw new Error('error deserializing LinkProof')
+        this.bytes = bytes
+    }
+    _pt(o) { return new Point(tomEdwards256, fromBE(this.bytes.slice(o, o + 36)), fromBE(this.bytes.slice(o + 36, o + 72))) }
+    _sc(o) { return new Scalar(tomEdwards256, fromBE(this.bytes.slice(o, o + 32))) }
+    get A_1() { return this._pt(16) }
+    get A_2() { return this._pt(88) }
+    get t_x() { return this._sc(160) }
+    get t_r1() { return this._sc(192) }
+    get t_r2() { return this._sc(224) }
+    eq(o) { return o instanceof LinkProof && this.bytes.equals(o.bytes) }
+}
+const scalarBytes = (v) => (v instanceof Scalar ? toBE(v.k, 32) : (Buffer.isBuffer(v) || v instanceof Uint8Array) ? Buffer.from(v) : toBE(mod(BigInt(v), tomEdwards256.order), 32))
+const comBytes = (c) => (Buffer.isBuffer(c) ? c : tomBytes(c instanceof Commitment ? c.p : c))
+// proveSameKey(params, key, comA, blinderA, comB, blinderB): comA = key g + blinderA h and comB = key g + blinderB h (Points, Commitments or 72-byte Buffers; the
+// key a bigint, the blinders Scalars, bigints or 32-byte Buffers -- keyBlinders gives a keyXcom's) -> LinkProof.  The engine draws fresh seeds.  A link proof
+// deliberately makes the two proofs linkable to anyone who sees it.  Throws 'error deserializing' for a commitment off the curve and "... do not open ..." when the
+// key and a blinder do not open a commitment.
+async function proveSameKey(params, key, comA, blinderA, comB, blinderB) {
+    return (await proveSameKeys(params, [key], [comA], [blinderA], [comB], [blinderB]))[0]
+}
+async function verifySameKey(params, comA, comB, link) {   // -> boolean; what does not deserialise throws
+    return (await verifySameKeys(params, [comA], [comB], [link]))[0]
+}
+// batched: arrays of equal length
+async function proveSameKeys(params, keys, comsA, blindersA, comsB, blindersB) {
+    const B = keys.length
+    if ([comsA, blindersA, comsB, blindersB].some((a) => a.length !== B)) throw new RangeError('proveSameKeys: one key, two commitments and two blinders per entry')
+    if (!B) return []
+    const r = await engineFor(paramsOf(params), null).run((engine) => engine.linkProveBatch(keys.map(scalarBytes), comsA.map(comBytes), blindersA.map(scalarBytes), comsB.map(comBytes),
+        blindersB.map(scalarBytes)))
+    return r.proofs.map((p, i) => { if (r.status[i] !== 0) throw statusError(r.status[i]); return new LinkProof(p) })
+}
+async function verifySameKeys(params, comsA, comsB, links) {
+    const B = links.length
+    if (comsA.length !== B || comsB.length !== B) throw new RangeError('verifySameKeys: two commitments per link proof')
+    if (!B) return []
+    const r = await engineFor(paramsOf(params), null).run((engine) => engine.linkVerifyBatch(comsA.map(comBytes), comsB.map(comBytes), links.map((l) => (l instanceof LinkProof ? l.bytes : new LinkProof(l).bytes))))
+    r.status.forEach((st) => { if (st !== 0) throw statusError(st) })
+    return r.ok
+}
+// keyXcom of a proof (a SignatureProofList or its bytes, either wire layout) as a Point: what takes a verifier from two attestations to verifySameKey
+async function keyCommitment(proof, params = lastParams) { return (await keyCommitments([proof], params))[0] }
+async function keyCommitments(proofs, params = lastParams) {
+    if (!params) throw new Error('keyCommitment: no parameters yet (pass a SystemParametersList)')
+    const raw = proofs.map((p) => (p instanceof SignatureProofList ? p.bytes : p)), out = new Array(raw.length)
+    for (const b of raw) if (!wellFormedProof(b)) throw new Error('error deserializing')
+    for (const wire of [0, 1]) {   // a context works in ONE layout at a time
+        const sel = []
+        raw.forEach((b, i) => { if ((isPacked(b) ? 1 : 0) === wire) sel.push(i) })
+        if (!sel.length) continue
+        const r = await engineFor(params, null).run((engine) => { useWire(engine, wire); return engine.keyCommitments(sel.map((i) => raw[i])) })
+        sel.forEach((i, k) => { if (r.status[k] !== 0) throw statusError(r.status[k]); out[i] = new Point(tomEdwards256, fromBE(r.coms[k].slice(0, 36)), fromBE(r.coms[k].slice(36))) })
+    }
+    return out
+}
+
+module.exports = { proveSameKey, verifySameKey, proveSameKeys, verifySameKeys, keyCommitment, keyCommitments, LinkProof, reringSignatureLists, keyBlinders, proveMembership, verifyMembership, proveMemberships, verifyMemberships, proveMembershipLists, verifyMembershipLists, GKProof, Commitment, commit, screenSignatureLists, findKey, SCREEN, WHICH_NONE, recoverSignatureLists, recoverKey, RECOVER, verifySignatureLists, proveSignatureLists, _ringGenerations, setVerifyLevel, getVerifyLevel, setVerifyReps, getVerifyReps, generateParamsList, generateParamsListHardened, keyToInt, proveSignatureList, verifySignatureList, proveSignatureListBatch, verifySignatureListBatch,
     writeJson, readJson, writeJsonBatch, readJsonBatch, SignatureProofList, SystemParametersList, PedersenParams, generatePedersenParams, p256, tomEdwards256, ALL_GROUPS,
     Group, Point, Scalar, Engine, shutdown, setWireLayout, getWireLayout, setOption, native }

@@ -1365,6 +1365,98 @@ static napi_value ReringBatchRings(napi_env env, napi_callback_info info) {
     return v;
 }
 
+/* Link proofs (include/zkattest.h: zk_link_*, zk_proof_key_commitments), on the pool's first context like the member calls; no ring takes part.
+ * (h, keys: B x 32, com1: B x 72, blinder1: B x 32, com2: B x 72, blinder2: B x 32, seeds: B x 32 -- FRESH) -> {proofs: B x 256 (zeros where status != 0),
+ * status: B i32 LE} */
+static napi_value LinkProveBatch(napi_env env, napi_callback_info info) {
+    napi_value argv[7];
+    if (!get_args(env, info, 7, argv)) return NULL;
+    Handle *h = get_handle(env, argv[0], 0);
+    uint8_t *key, *c1, *b1, *c2, *b2, *seeds;
+    size_t lk, lc1, lb1, lc2, lb2, ls;
+    if (!h || !get_bytes(env, argv[1], &key, &lk) || !get_bytes(env, argv[2], &c1, &lc1) || !get_bytes(env, argv[3], &b1, &lb1) || !get_bytes(env, argv[4], &c2, &lc2) ||
+        !get_bytes(env, argv[5], &b2, &lb2) || !get_bytes(env, argv[6], &seeds, &ls))
+        return NULL;
+    const size_t B = lk / 32;
+    if (lk % 32 || lc1 != 72 * B || lb1 != 32 * B || lc2 != 72 * B || lb2 != 32 * B || ls != 32 * B) {
+        napi_throw_range_error(env, NULL, "linkProveBatch: per proof a 32-byte key, two 72-byte commitments, two 32-byte blinders and 32 seed bytes");
+        return NULL;
+    }
+    zk_ctx *c = zk_pool_ctx(h->pool, 0);
+    const uint64_t size = zk_link_proof_size();
+    uint8_t *buf = (uint8_t *)xmalloc(env, (size + 4) * B + 8);
+    if (!buf) return NULL;
+    int32_t *status = (int32_t *)buf;
+    uint8_t *out = buf + 4 * B;
+    zk_rng rng = {ZK_RNG_SEED, seeds, 0};
+    zk_status st = zk_link_prove_batch(c, B, key, c1, b1, c2, b2, &rng, out, size * B, status);
+    napi_value v = NULL;
+    if (st != ZK_OK) throw_text(env, st, zk_last_error(c));
+    else if (napi_create_object(env, &v) == napi_ok) set_prop(env, v, "proofs", new_buffer(env, out, size * B)), set_prop(env, v, "status", new_buffer(env, status, 4 * B));
+    free(buf);
+    return v;
+}
+/* (h, com1: B x 72, com2: B x 72, proofs: B x 256) -> {ok: B bytes, status: B i32 LE} */
+static napi_value LinkVerifyBatch(napi_env env, napi_callback_info info) {
+    napi_value argv[4];
+    if (!get_args(env, info, 4, argv)) return NULL;
+    Handle *h = get_handle(env, argv[0], 0);
+    uint8_t *c1, *c2, *proofs;
+    size_t lc1, lc2, lp;
+    if (!h || !get_bytes(env, argv[1], &c1, &lc1) || !get_bytes(env, argv[2], &c2, &lc2) || !get_bytes(env, argv[3], &proofs, &lp)) return NULL;
+    const size_t B = lc1 / 72;
+    if (lc1 % 72 || lc2 != 72 * B || lp != zk_link_proof_size() * B) {
+        napi_throw_range_error(env, NULL, "linkVerifyBatch: two 72-byte commitments and one 256-byte proof per entry");
+        return NULL;
+    }
+    zk_ctx *c = zk_pool_ctx(h->pool, 0);
+    uint8_t *buf = (uint8_t *)xmalloc(env, 5 * B + 8);
+    if (!buf) return NULL;
+    int32_t *status = (int32_t *)buf;
+    uint8_t *ok = buf + 4 * B;
+    zk_status st = zk_link_verify_batch(c, B, c1, c2, proofs, ok, status);
+    napi_value v = NULL;
+    if (st != ZK_OK) throw_text(env, st, zk_last_error(c));
+    else if (napi_create_object(env, &v) == napi_ok) set_prop(env, v, "ok", new_buffer(env, ok, B)), set_prop(env, v, "status", new_buffer(env, status, 4 * B));
+    free(buf);
+    return v;
+}
+/* zk_proof_key_commitments: (h, proofs: the B proofs back to back in the context's wire layout, off: (B + 1) u64 LE) -> {coms: B x 72 (zeros where status != 0),
+ * status: B i32 LE} */
+static napi_value KeyCommitments(napi_env env, napi_callback_info info) {
+    napi_value argv[3];
+    if (!get_args(env, info, 3, argv)) return NULL;
+    Handle *h = get_handle(env, argv[0], 0);
+    uint8_t *blob, *ob;
+    size_t lp, lo;
+    if (!h || !get_bytes(env, argv[1], &blob, &lp) || !get_bytes(env, argv[2], &ob, &lo)) return NULL;
+    if (lo < 8 || lo % 8) {
+        napi_throw_range_error(env, NULL, "keyCommitments: B + 1 offsets of 8 bytes");
+        return NULL;
+    }
+    const size_t B = lo / 8 - 1;
+    uint8_t *buf = (uint8_t *)xmalloc(env, 8 * (B + 1) + (72 + 4) * B + lp + 8);   /* (a Buffer's bytes need not be aligned: offsets and proofs are copied) */
+    if (!buf) return NULL;
+    uint64_t *off = (uint64_t *)buf;
+    int32_t *status = (int32_t *)(off + (B + 1));
+    uint8_t *com = (uint8_t *)(status + B), *pr = com + 72 * B;
+    memcpy(off, ob, 8 * (B + 1));
+    if (lp) memcpy(pr, blob, lp);
+    for (size_t b = 0; b <= B; b++)
+        if (off[b] > lp) {   /* no slot may reach past the bytes that were handed over */
+            free(buf);
+            napi_throw_range_error(env, NULL, "keyCommitments: an offset lies behind the proofs' bytes");
+            return NULL;
+        }
+    zk_ctx *c = zk_pool_ctx(h->pool, 0);
+    zk_status st = zk_proof_key_commitments(c, B, pr, off, com, status);
+    napi_value v = NULL;
+    if (st != ZK_OK) throw_text(env, st, zk_last_error(c));
+    else if (napi_create_object(env, &v) == napi_ok) set_prop(env, v, "coms", new_buffer(env, com, 72 * B)), set_prop(env, v, "status", new_buffer(env, status, 4 * B));
+    free(buf);
+    return v;
+}
+
 static napi_value Init(napi_env env, napi_value exports) {
     static const struct {
         const char *name;
@@ -1385,7 +1477,8 @@ static napi_value Init(napi_env env, napi_value exports) {
                {"memberProofSizeRing", MemberProofSizeRing}, {"memberProveBatchRings", MemberProveBatchRings}, {"memberVerifyBatchRings", MemberVerifyBatchRings},
                {"memberProveBatchBound", MemberProveBatchBound}, {"memberVerifyBatchBound", MemberVerifyBatchBound},
                {"memberProveBatchRingsBound", MemberProveBatchRingsBound}, {"memberVerifyBatchRingsBound", MemberVerifyBatchRingsBound},
-               {"keyBlinders", KeyBlinders},     {"reringBatch", ReringBatch},     {"reringBatchRings", ReringBatchRings}};
+               {"keyBlinders", KeyBlinders},     {"reringBatch", ReringBatch},     {"reringBatchRings", ReringBatchRings},
+               {"linkProveBatch", LinkProveBatch}, {"linkVerifyBatch", LinkVerifyBatch}, {"keyCommitments", KeyCommitments}};
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;
         if (napi_create_function(env, fns[i].name, NAPI_AUTO_LENGTH, fns[i].fn, NULL, &f) != napi_ok) return NULL;

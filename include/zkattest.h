@@ -65,7 +65,8 @@ enum {
     ZK_E_INTERPOLATION = 13,     /* 'incorrect interpolation'       src/proofGK/interpolate.ts:65 */
     ZK_E_ARG = 14,               /* invalid argument */
     ZK_E_DEVICE = 15,            /* HIP runtime failure (zk_last_error has the text) */
-    ZK_E_OPENING = 16            /* zk_proof_rering_batch: ring[which_new] and the blinder do not open the proof's keyXcom */
+    ZK_E_OPENING = 16            /* zk_proof_rering_batch: ring[which_new] and the blinder do not open the proof's keyXcom; zk_link_prove_batch: the key and a
+                                    blinder do not open com1 or com2 */
 };
 
 enum { ZK_RNG_SEED = 0, ZK_RNG_STREAM = 1 };
@@ -683,6 +684,63 @@ zk_status zk_proof_rering_batch_rings_device(zk_ctx *ctx, uint64_t B, const void
                                              const void *d_which_new /*u32[B]*/, const void *d_ring_ids /*u32[B]*/, const void *d_key_blinder_be32,
                                              const zk_rng *rng_device, void *d_out, uint64_t out_cap, void *d_out_off /*u64[B+1]*/,
                                              void *d_per_proof_status /*i32[B]*/);
+
+/* ---- link proofs: two key commitments hide the same key.  The engine hands out Tom-256 commitments to a signer's key in three places -- keyXcom of every
+ * ZKA1 proof (its blinder: zk_prove_key_blinders), com of zk_member_prove_batch, and the keyXcom a re-ringed proof keeps -- and a link proof is the one statement
+ * that ties two of them together: ZK(x, r1, r2 : C1 = x g + r1 h  and  C2 = x g + r2 h), the reference's proveEquality / verifyEquality
+ * (src/commit/equality.ts:60-116) on its own, outside any PointAddProof.  With it the signer of attestation A shows that they also signed attestation B (two
+ * different proofs, two unrelated keyXcoms), or that they are a member of a second registry (keyXcom and a ZKM1 commitment), without re-ringing.  No signature,
+ * no P-256, no ring: the calls need zk_ctx_set_params only.
+ * Wire format "ZKL1", 256 bytes:
+ *     header 16 B : "ZKL1" | total_len u32 big-endian (= 256) | 0 u32 | 0 u32
+ *     EqualityProof 240 B : A_1, A_2 (Tom-256 points, 72 bytes each), t_x, t_r1, t_r2 (32 bytes big-endian each)
+ *   the body exactly as an EqualityProof lies inside ZKA1, always with 36-byte coordinates: zk_ctx_set_wire plays no part, as for ZKM1.  The two commitments
+ *   travel beside the proof as 72-byte Tom-256 points, as com does for ZKM1.
+ * zk_link_prove_batch: proof b is byte for byte proveEquality(params.ProofGroup, x, Commitment(C1, r1), Commitment(C2, r2)) under the randomness contract:
+ *   fill 0 is k = rnd(q), fills 1 and 2 the randomScalars s1, s2 of the two commit(k), all mod q with the contract's rejection sampling; key and both blinders
+ *   are reduced mod q as newScalar does; c = hashPoints([C1, C2, A_1, A_2]) (80 bits); t_x = k - c x, t_r1 = s1 - c r1, t_r2 = s2 - c r2.
+ *   Per proof, in this order; a failed proof gets 256 zero bytes and touches no neighbour:
+ *     ZK_E_BAD_ENCODING   com1 or com2 has a coordinate that is not below the field prime (padding bytes set included) or is off the curve: the rule
+ *                         zk_member_verify_batch applies to com.
+ *     ZK_E_OPENING        x g + r1 h is not com1, or x g + r2 h is not com2 (compared as canonical bytes, as the re-ring opening check): caught before a proof
+ *                         that cannot verify is written.
+ *     ZK_E_RNG_EXHAUSTED  as in zk_member_prove_batch: ZK_RNG_STREAM with fewer blocks than the three draws and their rejected fills need.
+ *   ZK_E_BUFFER when out_cap < 256 B, before a byte of out or the statuses is written.  The bytes depend neither on zk_ctx_set_comb_bits nor on the uniform
+ *   build, and both protocol modes work: the challenge binds both commitments, and ZK_MODE_HARDENED only changes h.
+ * zk_link_verify_batch: per proof, in this order:
+ *     ZK_E_BAD_ENCODING   a wrong magic, total_len != 256, a nonzero reserved word, or com1, com2, A_1 or A_2 non-canonical or off the curve.
+ *   Scalars >= q are REDUCED mod q, exactly as zk_verify_batch treats the scalars of an EqualityProof inside ZKA1 (the reference's Scalar constructor reduces):
+ *   they are no encoding error.  Otherwise ok = 1 iff both relations hold exactly,
+ *     t_x g + t_r1 h + c C1 - A_1 = O   and   t_x g + t_r2 h + c C2 - A_2 = O,
+ *   and the status is 0 either way.  The reference sums the two relations under random multipliers (multimult.ts:168-173); checking each one exactly gives the
+ *   same boolean without any verifier randomness, so there is no verifier_seeds argument.
+ * zk_proof_key_commitments: keyXcom of each ZKA1 / ZK1P proof (the context's wire layout, zk_ctx_set_wire), packed coordinates widened to 36 bytes -- what takes
+ *   a verifier from two attestations to zk_link_verify_batch.  Header and slot rules, and ZK_E_BAD_ENCODING, are zk_proof_rering_batch's; no curve check is made,
+ *   no byte outside a slot is read, no ring is needed.  A failed slot gets 72 zero bytes.
+ * Call-level rules are the member calls': ZK_E_BUFFER before zk_ctx_set_params; ZK_E_ARG for NULL pointers, B >= 2^32 and while streamed jobs are queued; B = 0
+ *   is ZK_OK; chunks (zk_ctx_set_chunk) on the context's lanes.  The _device forms take every pointer and rng->data in this context's HBM, 4-byte aligned
+ *   (proof_off 8-byte aligned), else ZK_E_ARG.  The staged keys, blinders and RNG fills and the nonces are witness-derived: zk_ctx_wipe, zk_ctx_destroy and a failed
+ *   call zero them.  zk_last_timing reports "rng_prepass", "tom_commit", "tom_normalize", "hash", "link_respond" (prover) and "link_parse", "tom_commit",
+ *   "link_ladder" (verifier).  Not provided: submit / wait, zk_pool_*, JSON, a caller-context binding.
+ * Two warnings.  (1) A link proof deliberately makes the two proofs linkable to anyone who sees it: that is its statement.  Show it only to whom the link is
+ *   meant for.  (2) rng must be independent of the seeds either commitment's proof was made with.  With a ZKA1 proof's own seed, fills 0 and 1 are comS1's and
+ *   keyXcom's blinders; reused as k and s1, the responses t_x and t_r1 reveal them.
+ * How: the four commitments of a proof are two pair launches that share the g-part, (k g + s1 h, k g + s2 h) and (x g + r1 h, x g + r2 h); the verifier's
+ *   c C_j is a left-to-right double-and-add over the 80 challenge bits, one lane per (proof, relation).  DESIGN.md section 5e. */
+uint64_t zk_link_proof_size(void);   /* 256 */
+zk_status zk_link_prove_batch(zk_ctx *ctx, uint64_t B, const uint8_t *key_be32 /*Bx32*/, const uint8_t *com1_xy72 /*Bx72*/, const uint8_t *blinder1_be32 /*Bx32*/,
+                              const uint8_t *com2_xy72 /*Bx72*/, const uint8_t *blinder2_be32 /*Bx32*/, const zk_rng *rng, uint8_t *out, uint64_t out_cap,
+                              int32_t *per_proof_status /*B*/);
+zk_status zk_link_prove_batch_device(zk_ctx *ctx, uint64_t B, const void *d_key_be32, const void *d_com1_xy72, const void *d_blinder1_be32, const void *d_com2_xy72,
+                                     const void *d_blinder2_be32, const zk_rng *rng_device, void *d_out, uint64_t out_cap, void *d_per_proof_status /*i32[B]*/);
+zk_status zk_link_verify_batch(zk_ctx *ctx, uint64_t B, const uint8_t *com1_xy72 /*Bx72*/, const uint8_t *com2_xy72 /*Bx72*/, const uint8_t *proofs /*Bx256*/,
+                               uint8_t *ok /*B*/, int32_t *per_proof_status /*B*/);
+zk_status zk_link_verify_batch_device(zk_ctx *ctx, uint64_t B, const void *d_com1_xy72, const void *d_com2_xy72, const void *d_proofs, void *d_ok,
+                                      void *d_per_proof_status /*i32[B]*/);
+zk_status zk_proof_key_commitments(zk_ctx *ctx, uint64_t B, const uint8_t *proofs, const uint64_t *proof_off /*B+1*/, uint8_t *com_xy72 /*Bx72*/,
+                                   int32_t *per_proof_status /*B*/);
+zk_status zk_proof_key_commitments_device(zk_ctx *ctx, uint64_t B, const void *d_proofs, const void *d_proof_off /*u64[B+1]*/, void *d_com_xy72,
+                                          void *d_per_proof_status /*i32[B]*/);
 
 /* ---- two (or more) batches in flight on one context.  zk_prove_batch / zk_verify_batch are synchronous: each call pays its own head
  * (no byte of a chunk exists before its stage 1 is over) and its own tail (the copies of the last slices, with nothing left to

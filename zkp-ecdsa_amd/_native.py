@@ -34,6 +34,8 @@ SYMBOLS = [
     'zk_member_prove_batch_rings_bound', 'zk_member_prove_batch_rings_bound_device', 'zk_member_verify_batch_rings_bound', 'zk_member_verify_batch_rings_bound_device',
     'zk_prove_key_blinders', 'zk_prove_key_blinders_device', 'zk_proof_rering_batch', 'zk_proof_rering_batch_device',
     'zk_proof_rering_batch_rings', 'zk_proof_rering_batch_rings_device',
+    'zk_link_proof_size', 'zk_link_prove_batch', 'zk_link_prove_batch_device', 'zk_link_verify_batch', 'zk_link_verify_batch_device',
+    'zk_proof_key_commitments', 'zk_proof_key_commitments_device',
     'zk_test_field_op', 'zk_test_tom_commit', 'zk_test_p256_fixed_mul', 'zk_test_sha256', 'zk_test_rng_draws', 'zk_test_exp_sum',
 ]
 
@@ -42,7 +44,7 @@ STATUS_TEXT = {
     5: 'P/Q/R is at infinity', 6: "Points don't add up!", 7: 'R is at infinity', 8: 'params not found',
     9: 'security level not achieved', 10: 'error deserializing', 11: 'randomness stream exhausted',
     12: 'buffer too small or context not configured', 13: 'incorrect interpolation', 14: 'invalid argument',
-    15: 'HIP runtime failure', 16: "the index and blinder do not open the proof's key commitment",
+    15: 'HIP runtime failure', 16: "the index and blinder do not open the proof's key commitment",   # (link proofs: the key and a blinder do not open com1 / com2)
 }
 E_OPENING = 16
 
@@ -170,6 +172,15 @@ def lib():
         L.zk_proof_rering_batch_device.argtypes = [vp, u64, vp, vp, vp, vp, vp, C.POINTER(ZkRng), vp, u64, vp, vp]
         L.zk_proof_rering_batch_rings.argtypes = [vp, u64, C.c_char_p, vp, vp, vp, vp, C.c_char_p, C.POINTER(ZkRng), vp, u64, vp, vp]
         L.zk_proof_rering_batch_rings_device.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp, C.POINTER(ZkRng), vp, u64, vp, vp]
+        # link proofs ("ZKL1"): two commitments hide the same key; keyXcom of ZKA1 / ZK1P proofs
+        L.zk_link_proof_size.argtypes = []
+        L.zk_link_proof_size.restype = u64
+        L.zk_link_prove_batch.argtypes = [vp, u64, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(ZkRng), vp, u64, vp]
+        L.zk_link_prove_batch_device.argtypes = [vp, u64, vp, vp, vp, vp, vp, C.POINTER(ZkRng), vp, u64, vp]
+        L.zk_link_verify_batch.argtypes = [vp, u64, C.c_char_p, C.c_char_p, C.c_char_p, vp, vp]
+        L.zk_link_verify_batch_device.argtypes = [vp, u64, vp, vp, vp, vp, vp]
+        L.zk_proof_key_commitments.argtypes = [vp, u64, C.c_char_p, vp, vp, vp]
+        L.zk_proof_key_commitments_device.argtypes = [vp, u64, vp, vp, vp, vp]
         L.zk_ring_digest.argtypes = [vp, vp]
         L.zk_hardened_h.argtypes = [C.c_char_p, u64, vp, vp]
         L.zk_pool_create.argtypes = [C.POINTER(C.c_int), i32, C.POINTER(vp)]
@@ -1056,6 +1067,77 @@ class Engine:
         rng = ZkRng(mode, d_rng, stride_blocks)
         self._chk(self.L.zk_proof_rering_batch_rings_device(self.h, B, d_msg, d_proofs, d_off, d_which_new, d_ring_ids, d_key_blinders, C.byref(rng), d_out, out_cap,
                                                             d_out_off, d_status))
+
+    # ---- link proofs (zk_link_*, zk_proof_key_commitments): two Tom-256 commitments hide the same key ("ZKL1", 256 bytes)
+    def link_proof_size(self):
+        return int(self.L.zk_link_proof_size())
+
+    @staticmethod
+    def _rows(x, width, B, what):
+        if not isinstance(x, (bytes, bytearray, memoryview)):
+            x = b''.join(bytes(v) for v in x)
+        if len(x) != width * B:
+            raise ValueError('%s must hold %d bytes per proof' % (what, width))
+        return bytes(x) if B else bytes(width)
+
+    def link_prove_batch(self, keys, com1, blinder1, com2, blinder2, seeds=None, streams=None, stream_blocks=0, cap=None):
+        """zk_link_prove_batch: proof b shows that com1[b] = keys[b] g + blinder1[b] h and com2[b] = keys[b] g + blinder2[b] h hide one key.  keys, blinders:
+        32-byte big-endian scalars (a list, or B x 32 bytes), coms: 72-byte Tom-256 points.  seeds / streams must be FRESH: never the ones either commitment's
+        proof was made with.  Returns (proofs: list of 256-byte strings, None where the status is not 0; statuses).  Two debugging aids, as
+        rering_batch and member_prove_batch have them: self.link_last_raw keeps the B slots as the call wrote them (a slot whose status is not 0 is zero-filled),
+        and cap overrides the out_cap handed to the call (default 256 B; a smaller one makes the call refuse with ZK_E_BUFFER)."""
+        B = len(keys) // 32 if isinstance(keys, (bytes, bytearray, memoryview)) else len(keys)
+        k, c1, b1, c2, b2 = (self._rows(keys, 32, B, 'keys'), self._rows(com1, 72, B, 'com1'), self._rows(blinder1, 32, B, 'blinder1'),
+                             self._rows(com2, 72, B, 'com2'), self._rows(blinder2, 32, B, 'blinder2'))
+        if seeds is None and streams is None:
+            seeds = os.urandom(32 * B)
+        rng, _keep = self._rng(B, seeds, streams, stream_blocks)
+        size = self.link_proof_size()
+        out = C.create_string_buffer(max(size * B, 1))
+        st = (C.c_int32 * max(B, 1))()
+        self._chk(self.L.zk_link_prove_batch(self.h, B, k, c1, b1, c2, b2, C.byref(rng), out, size * B if cap is None else cap, st))
+        raw = out.raw
+        self.link_last_raw = raw[:size * B]
+        return [raw[size * b:size * (b + 1)] if st[b] == 0 else None for b in range(B)], list(st)[:B]
+
+    def link_prove_batch_device(self, B, d_keys, d_com1, d_blinder1, d_com2, d_blinder2, d_rng, d_out, out_cap, d_status, mode=0, stride_blocks=0):
+        rng = ZkRng(mode, d_rng, stride_blocks)
+        self._chk(self.L.zk_link_prove_batch_device(self.h, B, d_keys, d_com1, d_blinder1, d_com2, d_blinder2, C.byref(rng), d_out, out_cap, d_status))
+
+    def link_verify_batch(self, com1, com2, proofs):
+        """zk_link_verify_batch for B (com1, com2, proof) triples, every proof 256 bytes.  Returns (ok list, status list)."""
+        B = len(proofs)
+        size = self.link_proof_size()
+        if any(len(p) != size for p in proofs):
+            raise ValueError('a link proof is %d bytes' % size)
+        ok = (C.c_uint8 * max(B, 1))()
+        st = (C.c_int32 * max(B, 1))()
+        self._chk(self.L.zk_link_verify_batch(self.h, B, self._rows(com1, 72, B, 'com1'), self._rows(com2, 72, B, 'com2'), b''.join(proofs) if B else bytes(size), ok, st))
+        return list(ok)[:B], list(st)[:B]
+
+    def link_verify_batch_device(self, B, d_com1, d_com2, d_proofs, d_ok, d_status):
+        self._chk(self.L.zk_link_verify_batch_device(self.h, B, d_com1, d_com2, d_proofs, d_ok, d_status))
+
+    def proof_key_commitments(self, proofs, offsets=None):
+        """zk_proof_key_commitments: keyXcom of every ZKA1 / ZK1P proof (the context's wire layout) as a 72-byte Tom-256 point.  proofs: a list of byte strings,
+        or one blob with `offsets` (B + 1 entries).  Returns (coms, statuses); a refused slot gives 72 zero bytes and status 10."""
+        if offsets is None:
+            blob, offsets, o = b''.join(proofs), [], 0
+            for p in proofs:
+                offsets.append(o)
+                o += len(p)
+            offsets.append(o)
+        else:
+            blob = bytes(proofs)
+        B = len(offsets) - 1
+        off = (C.c_uint64 * (B + 1))(*offsets)
+        com = C.create_string_buffer(max(72 * B, 1))
+        st = (C.c_int32 * max(B, 1))()
+        self._chk(self.L.zk_proof_key_commitments(self.h, B, blob if blob else bytes(4), off, com, st))
+        return [com.raw[72 * b:72 * b + 72] for b in range(B)], list(st)[:B]
+
+    def proof_key_commitments_device(self, B, d_proofs, d_off, d_com, d_status):
+        self._chk(self.L.zk_proof_key_commitments_device(self.h, B, d_proofs, d_off, d_com, d_status))
 
     def synth_params(self, seed):
         a, b, c = C.create_string_buffer(64), C.create_string_buffer(72), C.create_string_buffer(72)

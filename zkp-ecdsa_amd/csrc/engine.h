@@ -518,6 +518,7 @@ void launch_tom_commit(hipStream_t s, const DevParams& P, const TomList& L, uint
 void launch_tom_commit_list(hipStream_t s, const DevParams& P, const TomList& L, const uint32_t* list, const uint32_t* count_dev, uint32_t max_count);
 bool launch_tom_commit_shape(hipStream_t s, const DevParams& P, const TomList& L, uint32_t count, uint32_t shape, const uint32_t* list, const uint32_t* count_dev);   // test hook
 void launch_tom_commit_listb(hipStream_t s, const DevParams& P, const TomList& L, uint32_t items, uint32_t kstride);  // the 34 commitments of every PointAdd item
+void launch_tom_commit_pair_slots(hipStream_t s, const DevParams& P, const TomList& L, uint32_t units);   // slots 2 u, 2 u + 1: L.v[2 u] under L.r[2 u] and L.r[2 u + 1]
 void launch_tom_normalize(hipStream_t s, const TomList& L, uint32_t count, uint32_t first, uint32_t per_group, uint32_t slots_per_group, uint32_t kstride = 0);
 void launch_padd_derived(hipStream_t s, const Workspace& W, uint32_t items);
 // k_p256.hip

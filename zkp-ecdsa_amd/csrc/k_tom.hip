@@ -140,12 +140,9 @@ ZK_DEV typename TomModel<MODEL>::Pt tom_comb_acc(typename TomModel<MODEL>::Pt ac
     }
     return acc;
 }
+// one pair: L.v[slot0] * g once, then both h-parts
 template <bool SGN, int MODEL>
-__global__ void __launch_bounds__(256, 2) k_tom_commit_pairs(const uint32_t* __restrict__ tab_g, const uint32_t* __restrict__ tab_h, TomList L,
-                                                             uint32_t items, uint32_t kstride, uint32_t bits, uint32_t nwin) {
-    uint32_t c = gtid();
-    if (c >= items * LB_UNITS_PAIR) return;
-    uint32_t slot0 = LB_PAIR_K0[c / items] * kstride + c % items, slot1 = LB_PAIR_K1[c / items] * kstride + c % items;
+ZK_DEV void tom_commit_pair(const uint32_t* __restrict__ tab_g, const uint32_t* __restrict__ tab_h, const TomList& L, uint32_t slot0, uint32_t slot1, uint32_t bits, uint32_t nwin) {
     uint32_t w8[8];
     words_from_limbs<8>(w8, soa_ld<ModQ, 1>(L.v, slot0).l);
     typedef typename TomModel<MODEL>::Pt Pt;
@@ -156,6 +153,34 @@ __global__ void __launch_bounds__(256, 2) k_tom_commit_pairs(const uint32_t* __r
     words_from_limbs<8>(w8, soa_ld<ModQ, 1>(L.r, slot1).l);
     A = tom_comb_acc<false, true, SGN, MODEL>(G, tab_h, w8, bits, nwin);
     soa_st(L.proj.x, slot1, A.x), soa_st(L.proj.y, slot1, A.y), soa_st(L.proj.z, slot1, A.z);
+}
+template <bool SGN, int MODEL>
+__global__ void __launch_bounds__(256, 2) k_tom_commit_pairs(const uint32_t* __restrict__ tab_g, const uint32_t* __restrict__ tab_h, TomList L,
+                                                             uint32_t items, uint32_t kstride, uint32_t bits, uint32_t nwin) {
+    uint32_t c = gtid();
+    if (c >= items * LB_UNITS_PAIR) return;
+    tom_commit_pair<SGN, MODEL>(tab_g, tab_h, L, LB_PAIR_K0[c / items] * kstride + c % items, LB_PAIR_K1[c / items] * kstride + c % items, bits, nwin);
+}
+// The pair form over a list of its own: slots 2 u and 2 u + 1 commit to L.v[2 u] under L.r[2 u] and L.r[2 u + 1] (k_link.hip: A_1 / A_2 of a link proof, the
+// openings the prover claims, the verifier's t_x g + t_r1 h / t_x g + t_r2 h).  No digit is looked at before its table entry is added, so the uniform build
+// (curve.h: ZK_UNIFORM_CF) runs the same code.
+template <bool SGN, int MODEL>
+__global__ void __launch_bounds__(256, 2) k_tom_commit_pair_slots(const uint32_t* __restrict__ tab_g, const uint32_t* __restrict__ tab_h, TomList L, uint32_t units,
+                                                                  uint32_t bits, uint32_t nwin) {
+    const uint32_t u = gtid();
+    if (u >= units) return;
+    tom_commit_pair<SGN, MODEL>(tab_g, tab_h, L, 2 * u, 2 * u + 1, bits, nwin);
+}
+template <int MODEL>
+static void launch_tom_commit_pair_slots_m(hipStream_t s, const DevParams& P, const TomList& L, uint32_t units) {
+    const dim3 g((units + 255) / 256), b(256);
+    if (tom_signed(P.tom_bits)) hipLaunchKernelGGL((k_tom_commit_pair_slots<true, MODEL>), g, b, 0, s, P.tom_tab_g, P.tom_tab_h, L, units, P.tom_bits, tom_nwin(P.tom_bits));
+    else hipLaunchKernelGGL((k_tom_commit_pair_slots<false, MODEL>), g, b, 0, s, P.tom_tab_g, P.tom_tab_h, L, units, P.tom_bits, tom_nwin(P.tom_bits));
+}
+void launch_tom_commit_pair_slots(hipStream_t s, const DevParams& P, const TomList& L, uint32_t units) {
+    if (!units) return;
+    if (P.tom_model == TOM_MODEL_M1) launch_tom_commit_pair_slots_m<TOM_MODEL_M1>(s, P, L, units);
+    else launch_tom_commit_pair_slots_m<TOM_MODEL_A1>(s, P, L, units);
 }
 // ---- the same commitments for a SMALL launch, four lanes each (engine.h: ZK_WIDE_MAX_UNITS).  The comb tables hold every window multiple, so lane `part`
 // takes windows [part * per, part * per + per) of v's g-part and r's h-part -- 3 + 3 table additions at 24 bits instead of 11 + 11 in a row -- and the four
