@@ -121,6 +121,33 @@ export function proveSameKey(params: PedersenParams | SystemParametersList, key:
 export function verifySameKey(params: PedersenParams | SystemParametersList, comA: LinkCom, comB: LinkCom, link: LinkProof | Buffer): Promise<boolean>
 export function proveSameKeys(params: PedersenParams | SystemParametersList, keys: LinkScalar[], comsA: LinkCom[], blindersA: LinkScalar[], comsB: LinkCom[], blindersB: LinkScalar[]): Promise<LinkProof[]>
 export function verifySameKeys(params: PedersenParams | SystemParametersList, comsA: LinkCom[], comsB: LinkCom[], links: (LinkProof | Buffer)[]): Promise<boolean[]>
+/** Distinct-key proofs ("ZKD1", zk_distinct_*): comA = keyA g + blinderA h and comB = keyB g + blinderB h hide DIFFERENT keys: one MultProof (src/commit/mult.ts)
+ *  for (keyA - keyB) * w = 1.  A proof verifies for (comA, comB) in this order only; equal keys throw '... hide the same key ...'; the engine draws fresh seeds. */
+export class DistinctProof {
+    constructor(bytes: Buffer)
+    readonly bytes: Buffer
+    readonly C_w: Point
+    readonly C_4: Point
+    readonly A_x: Point
+    readonly A_y: Point
+    readonly A_z: Point
+    readonly A_4_1: Point
+    readonly A_4_2: Point
+    readonly t_x: Scalar
+    readonly t_y: Scalar
+    readonly t_z: Scalar
+    readonly t_rx: Scalar
+    readonly t_ry: Scalar
+    readonly t_rz: Scalar
+    readonly t_r4: Scalar
+    eq(o: DistinctProof): boolean
+}
+export function proveDifferentKeys(params: PedersenParams | SystemParametersList, keyA: LinkScalar, comA: LinkCom, blinderA: LinkScalar, keyB: LinkScalar, comB: LinkCom, blinderB: LinkScalar): Promise<DistinctProof>
+export function verifyDifferentKeys(params: PedersenParams | SystemParametersList, comA: LinkCom, comB: LinkCom, proof: DistinctProof | Buffer): Promise<boolean>
+export function proveDifferentKeysBatch(params: PedersenParams | SystemParametersList, keysA: LinkScalar[], comsA: LinkCom[], blindersA: LinkScalar[], keysB: LinkScalar[], comsB: LinkCom[], blindersB: LinkScalar[]): Promise<DistinctProof[]>
+export function verifyDifferentKeysBatch(params: PedersenParams | SystemParametersList, comsA: LinkCom[], comsB: LinkCom[], proofs: (DistinctProof | Buffer)[]): Promise<boolean[]>
+/** the k (k - 1) / 2 pairs [i, j], i < j, of k commitments in lexicographic order: one distinct-key proof per pair shows k different signers */
+export function distinctPairs(k: number): [number, number][]
 /** keyXcom of a proof (either wire layout; zk_proof_key_commitments) */
 export function keyCommitment(proof: SignatureProofList | Buffer, params?: SystemParametersList): Promise<Point>
 export function keyCommitments(proofs: (SignatureProofList | Buffer)[], params?: SystemParametersList): Promise<Point[]>
@@ -167,6 +194,10 @@ export class Engine {
     reringBatchRings(msg: Buffer, proofs: Buffer[], whichNew: number[] | Uint32Array, ringIds: number[] | Uint32Array, blinders: Buffer, seeds?: Buffer): { proofs: (Buffer | null)[]; status: Int32Array }
     /** zk_link_prove_batch: per entry a 32-byte key, two 72-byte commitments and their 32-byte blinders; seeds must be fresh (default: crypto.randomBytes).  status 16: the key and a blinder do not open a commitment */
     linkProveBatch(keys: Buffer[], com1: Buffer[], blinder1: Buffer[], com2: Buffer[], blinder2: Buffer[], seeds?: Buffer): { proofs: (Buffer | null)[]; status: Int32Array }
+    /** zk_distinct_prove_batch: per entry two 32-byte keys, two 72-byte commitments and their 32-byte blinders; seeds must be fresh (default: crypto.randomBytes).  status 14: equal keys; 16: a key and its blinder do not open their commitment */
+    distinctProveBatch(key1: Buffer[], com1: Buffer[], blinder1: Buffer[], key2: Buffer[], com2: Buffer[], blinder2: Buffer[], seeds?: Buffer): { proofs: (Buffer | null)[]; status: Int32Array }
+    /** zk_distinct_verify_batch */
+    distinctVerifyBatch(com1: Buffer[], com2: Buffer[], proofs: Buffer[]): { ok: boolean[]; status: Int32Array }
     /** zk_link_verify_batch */
     linkVerifyBatch(com1: Buffer[], com2: Buffer[], proofs: Buffer[]): { ok: boolean[]; status: Int32Array }
     /** zk_proof_key_commitments: keyXcom of proofs in the engine's wire layout, 72 bytes each; null where the status is not 0 */

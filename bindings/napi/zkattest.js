@@ -463,6 +463,19 @@ class Engine {
         const r = native.linkVerifyBatch(this.h, Buffer.concat(com1), Buffer.concat(com2), Buffer.concat(proofs))
         return { ok: Array.from(r.ok, (v) => v === 1), status: i32(r.status) }
     }
+    // distinct-key proofs (zk_distinct_*): "ZKD1", 744 bytes -- com1[i] opens to key1[i] under blinder1[i], com2[i] to key2[i] under blinder2[i], and the keys differ;
+    // the proof verifies for (com1, com2) in this order only.  Arrays of Buffers -> { proofs: Buffer | null per entry, status: Int32Array } (status 14: equal keys).
+    // seeds must be FRESH: never the ones either commitment's proof was made with (default: crypto.randomBytes)
+    distinctProveBatch(key1, com1, blinder1, key2, com2, blinder2, seeds) {
+        const B = key1.length, cat = (a) => Buffer.concat(a.map((v) => Buffer.from(v)))
+        const r = native.distinctProveBatch(this.h, cat(key1), cat(com1), cat(blinder1), cat(key2), cat(com2), cat(blinder2), seeds || crypto.randomBytes(32 * B))
+        const st = i32(r.status)
+        return { proofs: Array.from(st, (s, i) => (s === 0 ? r.proofs.slice(744 * i, 744 * i + 744) : null)), status: st }
+    }
+    distinctVerifyBatch(com1, com2, proofs) {   // -> { ok: boolean[], status: Int32Array }
+        const r = native.distinctVerifyBatch(this.h, Buffer.concat(com1), Buffer.concat(com2), Buffer.concat(proofs))
+        return { ok: Array.from(r.ok, (v) => v === 1), status: i32(r.status) }
+    }
     // zk_proof_key_commitments: keyXcom of every proof (Buffers in the engine's wire layout) as a 72-byte point -> { coms: Buffer | null per entry, status: Int32Array }
     keyCommitments(proofs) {
         const B = proofs.length, off = Buffer.alloc(8 * (B + 1))
@@ -1145,6 +1158,71 @@ async function keyCommitments(proofs, params = lastParams) {
     return out
 }
 
-module.exports = { proveSameKey, verifySameKey, proveSameKeys, verifySameKeys, keyCommitment, keyCommitments, LinkProof, reringSignatureLists, keyBlinders, proveMembership, verifyMembership, proveMemberships, verifyMemberships, proveMembershipLists, verifyMembershipLists, GKProof, Commitment, commit, screenSignatureLists, findKey, SCREEN, WHICH_NONE, recoverSignatureLists, recoverKey, RECOVER, verifySignatureLists, proveSignatureLists, _ringGenerations, setVerifyLevel, getVerifyLevel, setVerifyReps, getVerifyReps, generateParamsList, generateParamsListHardened, keyToInt, proveSignatureList, verifySignatureList, proveSignatureListBatch, verifySignatureListBatch,
+// ---------------------------------------------------------------- distinct-key proofs: two key commitments hide different keys (src/commit/mult.ts:26-175)
+// A DistinctProof keeps the engine's ZKD1 bytes (include/zkattest.h) and materialises C_w and the reference's MultProof members (six Points, seven Scalars).
+class DistinctProof {
+    constructor(bytes) {
+        if (!(Buffer.isBuffer(bytes) && bytes.length === 744 && bytes.slice(0, 4).toString('latin1') === 'ZKD1' && bytes.readUInt32BE(4) === 744 && bytes.readUInt32BE(8) === 0 &&
+            bytes.readUInt32BE(12) === 0)) throw new Error('error deserializing DistinctProof')
+        this.bytes = bytes
+    }
+    _pt(o) { return new Point(tomEdwards256, fromBE(this.bytes.slice(o, o + 36)), fromBE(this.bytes.slice(o + 36, o + 72))) }
+    _sc(o) { return new Scalar(tomEdwards256, fromBE(this.bytes.slice(o, o + 32))) }
+    get C_w() { return this._pt(16) }
+    get C_4() { return this._pt(88) }
+    get A_x() { return this._pt(160) }
+    get A_y() { return this._pt(232) }
+    get A_z() { return this._pt(304) }
+    get A_4_1() { return this._pt(376) }
+    get A_4_2() { return this._pt(448) }
+    get t_x() { return this._sc(520) }
+    get t_y() { return this._sc(552) }
+    get t_z() { return this._sc(584) }
+    get t_rx() { return this._sc(616) }
+    get t_ry() { return this._sc(648) }
+    get t_rz() { return this._sc(680) }
+    get t_r4() { return this._sc(712) }
+    eq(o) { return o instanceof DistinctProof && this.bytes.equals(o.bytes) }
+}
+// the k (k - 1) / 2 pairs [i, j], i < j, of k commitments in lexicographic order: one distinct-key proof per pair shows k different keys
+function distinctPairs(k) {
+    const out = []
+    for (let i = 0; i < k; i++) for (let j = i + 1; j < k; j++) out.push([i, j])
+    return out
+}
+// proveDifferentKeys(params, keyA, comA, blinderA, keyB, comB, blinderB): comA = keyA g + blinderA h and comB = keyB g + blinderB h (Points, Commitments or 72-byte
+// Buffers; keys and blinders Scalars, bigints or 32-byte Buffers -- keyBlinders gives a keyXcom's) hide different keys -> DistinctProof, which verifies for
+// (comA, comB) in this order only.  The engine draws fresh seeds.  Throws 'error deserializing' for a commitment off the curve, '... hide the same key ...' for equal
+// keys and "... do not open ..." when a key and its blinder do not open their commitment.
+async function proveDifferentKeys(params, keyA, comA, blinderA, keyB, comB, blinderB) {
+    return (await proveDifferentKeysBatch(params, [keyA], [comA], [blinderA], [keyB], [comB], [blinderB]))[0]
+}
+async function verifyDifferentKeys(params, comA, comB, proof) {   // -> boolean; what does not deserialise throws
+    return (await verifyDifferentKeysBatch(params, [comA], [comB], [proof]))[0]
+}
+// batched: arrays of equal length
+async function proveDifferentKeysBatch(params, keysA, comsA, blindersA, keysB, comsB, blindersB) {
+    const B = keysA.length
+    if ([comsA, blindersA, keysB, comsB, blindersB].some((a) => a.length !== B)) throw new RangeError('proveDifferentKeysBatch: two keys, two commitments and two blinders per entry')
+    if (!B) return []
+    const r = await engineFor(paramsOf(params), null).run((engine) => engine.distinctProveBatch(keysA.map(scalarBytes), comsA.map(comBytes), blindersA.map(scalarBytes),
+        keysB.map(scalarBytes), comsB.map(comBytes), blindersB.map(scalarBytes)))
+    return r.proofs.map((p, i) => {
+        if (r.status[i] === 14) throw new Error('the two commitments hide the same key: no distinct-key proof exists')
+        if (r.status[i] !== 0) throw statusError(r.status[i])
+        return new DistinctProof(p)
+    })
+}
+async function verifyDifferentKeysBatch(params, comsA, comsB, proofs) {
+    const B = proofs.length
+    if (comsA.length !== B || comsB.length !== B) throw new RangeError('verifyDifferentKeysBatch: two commitments per distinct-key proof')
+    if (!B) return []
+    const r = await engineFor(paramsOf(params), null).run((engine) => engine.distinctVerifyBatch(comsA.map(comBytes), comsB.map(comBytes),
+        proofs.map((l) => (l instanceof DistinctProof ? l.bytes : new DistinctProof(l).bytes))))
+    r.status.forEach((st) => { if (st !== 0) throw statusError(st) })
+    return r.ok
+}
+
+module.exports = { proveDifferentKeys, verifyDifferentKeys, proveDifferentKeysBatch, verifyDifferentKeysBatch, distinctPairs, DistinctProof, proveSameKey, verifySameKey, proveSameKeys, verifySameKeys, keyCommitment, keyCommitments, LinkProof, reringSignatureLists, keyBlinders, proveMembership, verifyMembership, proveMemberships, verifyMemberships, proveMembershipLists, verifyMembershipLists, GKProof, Commitment, commit, screenSignatureLists, findKey, SCREEN, WHICH_NONE, recoverSignatureLists, recoverKey, RECOVER, verifySignatureLists, proveSignatureLists, _ringGenerations, setVerifyLevel, getVerifyLevel, setVerifyReps, getVerifyReps, generateParamsList, generateParamsListHardened, keyToInt, proveSignatureList, verifySignatureList, proveSignatureListBatch, verifySignatureListBatch,
     writeJson, readJson, writeJsonBatch, readJsonBatch, SignatureProofList, SystemParametersList, PedersenParams, generatePedersenParams, p256, tomEdwards256, ALL_GROUPS,
     Group, Point, Scalar, Engine, shutdown, setWireLayout, getWireLayout, setOption, native }

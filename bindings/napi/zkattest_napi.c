@@ -1421,6 +1421,62 @@ static napi_value LinkVerifyBatch(napi_env env, napi_callback_info info) {
     free(buf);
     return v;
 }
+/* Distinct-key proofs (include/zkattest.h: zk_distinct_*), on the pool's first context like the link calls; no ring takes part.
+ * (h, key1: B x 32, com1: B x 72, blinder1: B x 32, key2: B x 32, com2: B x 72, blinder2: B x 32, seeds: B x 32 -- FRESH) -> {proofs: B x 744 (zeros where
+ * status != 0), status: B i32 LE} */
+static napi_value DistinctProveBatch(napi_env env, napi_callback_info info) {
+    napi_value argv[8];
+    if (!get_args(env, info, 8, argv)) return NULL;
+    Handle *h = get_handle(env, argv[0], 0);
+    uint8_t *k1, *c1, *b1, *k2, *c2, *b2, *seeds;
+    size_t lk1, lc1, lb1, lk2, lc2, lb2, ls;
+    if (!h || !get_bytes(env, argv[1], &k1, &lk1) || !get_bytes(env, argv[2], &c1, &lc1) || !get_bytes(env, argv[3], &b1, &lb1) || !get_bytes(env, argv[4], &k2, &lk2) ||
+        !get_bytes(env, argv[5], &c2, &lc2) || !get_bytes(env, argv[6], &b2, &lb2) || !get_bytes(env, argv[7], &seeds, &ls))
+        return NULL;
+    const size_t B = lk1 / 32;
+    if (lk1 % 32 || lc1 != 72 * B || lb1 != 32 * B || lk2 != 32 * B || lc2 != 72 * B || lb2 != 32 * B || ls != 32 * B) {
+        napi_throw_range_error(env, NULL, "distinctProveBatch: per proof two 32-byte keys, two 72-byte commitments, two 32-byte blinders and 32 seed bytes");
+        return NULL;
+    }
+    zk_ctx *c = zk_pool_ctx(h->pool, 0);
+    const uint64_t size = zk_distinct_proof_size();
+    uint8_t *buf = (uint8_t *)xmalloc(env, (size + 4) * B + 8);
+    if (!buf) return NULL;
+    int32_t *status = (int32_t *)buf;
+    uint8_t *out = buf + 4 * B;
+    zk_rng rng = {ZK_RNG_SEED, seeds, 0};
+    zk_status st = zk_distinct_prove_batch(c, B, k1, c1, b1, k2, c2, b2, &rng, out, size * B, status);
+    napi_value v = NULL;
+    if (st != ZK_OK) throw_text(env, st, zk_last_error(c));
+    else if (napi_create_object(env, &v) == napi_ok) set_prop(env, v, "proofs", new_buffer(env, out, size * B)), set_prop(env, v, "status", new_buffer(env, status, 4 * B));
+    free(buf);
+    return v;
+}
+/* (h, com1: B x 72, com2: B x 72, proofs: B x 744) -> {ok: B bytes, status: B i32 LE} */
+static napi_value DistinctVerifyBatch(napi_env env, napi_callback_info info) {
+    napi_value argv[4];
+    if (!get_args(env, info, 4, argv)) return NULL;
+    Handle *h = get_handle(env, argv[0], 0);
+    uint8_t *c1, *c2, *proofs;
+    size_t lc1, lc2, lp;
+    if (!h || !get_bytes(env, argv[1], &c1, &lc1) || !get_bytes(env, argv[2], &c2, &lc2) || !get_bytes(env, argv[3], &proofs, &lp)) return NULL;
+    const size_t B = lc1 / 72;
+    if (lc1 % 72 || lc2 != 72 * B || lp != zk_distinct_proof_size() * B) {
+        napi_throw_range_error(env, NULL, "distinctVerifyBatch: two 72-byte commitments and one 744-byte proof per entry");
+        return NULL;
+    }
+    zk_ctx *c = zk_pool_ctx(h->pool, 0);
+    uint8_t *buf = (uint8_t *)xmalloc(env, 5 * B + 8);
+    if (!buf) return NULL;
+    int32_t *status = (int32_t *)buf;
+    uint8_t *ok = buf + 4 * B;
+    zk_status st = zk_distinct_verify_batch(c, B, c1, c2, proofs, ok, status);
+    napi_value v = NULL;
+    if (st != ZK_OK) throw_text(env, st, zk_last_error(c));
+    else if (napi_create_object(env, &v) == napi_ok) set_prop(env, v, "ok", new_buffer(env, ok, B)), set_prop(env, v, "status", new_buffer(env, status, 4 * B));
+    free(buf);
+    return v;
+}
 /* zk_proof_key_commitments: (h, proofs: the B proofs back to back in the context's wire layout, off: (B + 1) u64 LE) -> {coms: B x 72 (zeros where status != 0),
  * status: B i32 LE} */
 static napi_value KeyCommitments(napi_env env, napi_callback_info info) {
@@ -1478,7 +1534,8 @@ static napi_value Init(napi_env env, napi_value exports) {
                {"memberProveBatchBound", MemberProveBatchBound}, {"memberVerifyBatchBound", MemberVerifyBatchBound},
                {"memberProveBatchRingsBound", MemberProveBatchRingsBound}, {"memberVerifyBatchRingsBound", MemberVerifyBatchRingsBound},
                {"keyBlinders", KeyBlinders},     {"reringBatch", ReringBatch},     {"reringBatchRings", ReringBatchRings},
-               {"linkProveBatch", LinkProveBatch}, {"linkVerifyBatch", LinkVerifyBatch}, {"keyCommitments", KeyCommitments}};
+               {"linkProveBatch", LinkProveBatch}, {"linkVerifyBatch", LinkVerifyBatch}, {"keyCommitments", KeyCommitments},
+               {"distinctProveBatch", DistinctProveBatch}, {"distinctVerifyBatch", DistinctVerifyBatch}};
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;
         if (napi_create_function(env, fns[i].name, NAPI_AUTO_LENGTH, fns[i].fn, NULL, &f) != napi_ok) return NULL;

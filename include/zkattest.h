@@ -742,6 +742,62 @@ zk_status zk_proof_key_commitments(zk_ctx *ctx, uint64_t B, const uint8_t *proof
 zk_status zk_proof_key_commitments_device(zk_ctx *ctx, uint64_t B, const void *d_proofs, const void *d_proof_off /*u64[B+1]*/, void *d_com_xy72,
                                           void *d_per_proof_status /*i32[B]*/);
 
+/* ---- distinct-key proofs: two key commitments hide DIFFERENT keys.  The opposite statement of a link proof, over the same commitments (a keyXcom from
+ * zk_proof_key_commitments with its blinder from zk_prove_key_blinders, or a com of the member calls): ZK(x1, r1, x2, r2 : C1 = x1 g + r1 h, C2 = x2 g + r2 h,
+ * x1 != x2 mod q).  q is P-256's field prime and a ring entry is a key's x-coordinate, so this means two different ring entries.  With one proof per pair, k
+ * attestations that zk_verify_batch[_rings] accepts become "k different members of the ring approved this" with no member identified: the quorum or threshold
+ * use (INTEGRATION.md "Counting signers").  A value is non-zero exactly when it has an inverse, so the proof is one MultProof of the reference
+ * (src/commit/mult.ts:93-175) for (x1 - x2) * w = 1 over Cx = C1 - C2, Cy = C_w = commit(w), Cz = g.  No signature, no P-256, no ring: zk_ctx_set_params only.
+ * Wire format "ZKD1", 744 bytes:
+ *     header 16 B : "ZKD1" | total_len u32 big-endian (= 744) | 0 u32 | 0 u32
+ *     C_w 72 B : the commitment to 1 / (x1 - x2), a Tom-256 point
+ *     MultProof 656 B : C_4, A_x, A_y, A_z, A_4_1, A_4_2 (72 bytes each), t_x, t_y, t_z, t_rx, t_ry, t_rz, t_r4 (32 bytes big-endian each)
+ *   the MultProof exactly as one lies inside ZKA1, always with 36-byte coordinates: zk_ctx_set_wire plays no part, as for ZKL1.  The two commitments travel
+ *   beside the proof as 72-byte Tom-256 points.
+ * The proof is DIRECTIONAL: (C1, C2, proof) does not verify as (C2, C1, proof).  Prover and verifier name the pair in the same order.
+ * zk_distinct_prove_batch: with d = x1 - x2, rd = r1 - r2, w = 1 / d (all mod q), proof b is byte for byte
+ *     Cw = params.commit(w);  proveMult(params, d, w, 1, Commitment(C1 - C2, rd), Cw, Commitment(g, 0))
+ *   under the randomness contract: fill 0 is r_w, fills 1..3 are k_x, k_y, k_z, fills 4..7 the blinders of A_x, A_y, A_z, A_4_1, all mod q with the contract's
+ *   rejection sampling (a stream needs 8 blocks plus one per rejected fill); keys and blinders are reduced mod q as newScalar does;
+ *   c = hashPoints([Cx, C_w, g, C_4, A_x, A_y, A_z, A_4_1, A_4_2]) (80 bits).  Per proof, in this order; a failed proof gets 744 zero bytes and touches no
+ *   neighbour:
+ *     ZK_E_BAD_ENCODING   com1 or com2 has a coordinate that is not below the field prime (padding bytes set included) or is off the curve: the link calls' rule.
+ *     ZK_E_ARG            x1 = x2 mod q: the statement is false and no proof exists.
+ *     ZK_E_OPENING        x1 g + r1 h is not com1, or x2 g + r2 h is not com2 (compared as canonical bytes), before anything is written.
+ *     ZK_E_RNG_EXHAUSTED  as in zk_link_prove_batch: ZK_RNG_STREAM with fewer blocks than the eight draws and their rejected fills need.
+ *   ZK_E_BUFFER when out_cap < 744 B, before a byte of out or the statuses is written.  The bytes depend neither on zk_ctx_set_comb_bits nor on the uniform
+ *   build, and both protocol modes work: ZK_MODE_HARDENED only changes h.
+ * zk_distinct_verify_batch: per proof, in this order:
+ *     ZK_E_BAD_ENCODING   a wrong magic, total_len != 744, a nonzero reserved word, or com1, com2, C_w or one of the six points non-canonical or off the curve.
+ *   Scalars >= q are REDUCED mod q, not refused.  Otherwise the status is 0 and ok = 1 iff the five relations of aggregateMult hold exactly, with Cx = C1 - C2
+ *   (the identity is a legal point here) and c as above:
+ *     t_x g + t_rx h + c Cx - A_x = O,   t_y g + t_ry h + c C_w - A_y = O,   t_z g + t_rz h + c g - A_z = O,
+ *     t_z g + t_r4 h + c C_4 - A_4_1 = O,   t_x C_w + c C_4 - A_4_2 = O.
+ *   The reference sums them under random multipliers (multimult.ts:168-173); checking each one exactly gives the same boolean without verifier randomness, so
+ *   there is no verifier_seeds argument.  There is no special case for C1 = C2: with Cx = O a forger would need z = 0 against Cz = g, which the relations refuse.
+ * Call-level rules are the link calls': ZK_E_BUFFER before zk_ctx_set_params; ZK_E_ARG for NULL pointers, B >= 2^32 and while streamed jobs are queued; B = 0
+ *   is ZK_OK; chunks (zk_ctx_set_chunk) on the context's lanes.  The _device forms take every pointer and rng->data in this context's HBM, 4-byte aligned, else
+ *   ZK_E_ARG.  The staged keys and blinders, d, w, r_w, the nonces and the RNG fills are witness-derived: zk_ctx_wipe, zk_ctx_destroy and a failed call zero
+ *   them.  zk_last_timing reports "rng_prepass", "tom_commit", "tom_normalize", "hash", "distinct_respond" (prover) and "distinct_parse", "tom_normalize",
+ *   "hash", "tom_commit", "distinct_short", "distinct_long" (verifier).  Not provided: submit / wait, zk_pool_*, JSON, a caller-context binding.
+ * Two warnings.  (1) A distinct-key proof tells whoever sees it that the two commitments belong to different signers; keep it for whom it is meant.  (2) rng
+ *   must be independent of the seeds either commitment's proof was made with: with a ZKA1 proof's own seed the fills that blinded comS1 and keyXcom would come
+ *   back as r_w and k_x, and the responses would be further equations in those blinders.
+ * How: every point the prover makes is a fixed-base commitment with a known opening -- C_4 = (1, d r_w), A_4_2 = (k_x w, k_x r_w), (A_z, A_4_1) one pair
+ *   launch -- so its side has no variable-base multiplication; the verifier's relation 5 is a joint left-to-right double-and-add over the 256 bits of t_x and
+ *   the 80 of c in a kernel of its own, relations 1, 2, 4 are the link verifier's 80-bit ladder, relation 3 folds c into its comb part.  DESIGN.md section 5f. */
+uint64_t zk_distinct_proof_size(void);   /* 744 */
+zk_status zk_distinct_prove_batch(zk_ctx *ctx, uint64_t B, const uint8_t *key1_be32 /*Bx32*/, const uint8_t *com1_xy72 /*Bx72*/, const uint8_t *blinder1_be32 /*Bx32*/,
+                                  const uint8_t *key2_be32 /*Bx32*/, const uint8_t *com2_xy72 /*Bx72*/, const uint8_t *blinder2_be32 /*Bx32*/, const zk_rng *rng,
+                                  uint8_t *out, uint64_t out_cap, int32_t *per_proof_status /*B*/);
+zk_status zk_distinct_prove_batch_device(zk_ctx *ctx, uint64_t B, const void *d_key1_be32, const void *d_com1_xy72, const void *d_blinder1_be32,
+                                         const void *d_key2_be32, const void *d_com2_xy72, const void *d_blinder2_be32, const zk_rng *rng_device, void *d_out,
+                                         uint64_t out_cap, void *d_per_proof_status /*i32[B]*/);
+zk_status zk_distinct_verify_batch(zk_ctx *ctx, uint64_t B, const uint8_t *com1_xy72 /*Bx72*/, const uint8_t *com2_xy72 /*Bx72*/, const uint8_t *proofs /*Bx744*/,
+                                   uint8_t *ok /*B*/, int32_t *per_proof_status /*B*/);
+zk_status zk_distinct_verify_batch_device(zk_ctx *ctx, uint64_t B, const void *d_com1_xy72, const void *d_com2_xy72, const void *d_proofs, void *d_ok,
+                                          void *d_per_proof_status /*i32[B]*/);
+
 /* ---- two (or more) batches in flight on one context.  zk_prove_batch / zk_verify_batch are synchronous: each call pays its own head
  * (no byte of a chunk exists before its stage 1 is over) and its own tail (the copies of the last slices, with nothing left to
  * hide them).  The submit / wait pair splits a call so that the pipeline keeps running ACROSS calls: submit stages the inputs and

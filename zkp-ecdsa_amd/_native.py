@@ -36,6 +36,7 @@ SYMBOLS = [
     'zk_proof_rering_batch_rings', 'zk_proof_rering_batch_rings_device',
     'zk_link_proof_size', 'zk_link_prove_batch', 'zk_link_prove_batch_device', 'zk_link_verify_batch', 'zk_link_verify_batch_device',
     'zk_proof_key_commitments', 'zk_proof_key_commitments_device',
+    'zk_distinct_proof_size', 'zk_distinct_prove_batch', 'zk_distinct_prove_batch_device', 'zk_distinct_verify_batch', 'zk_distinct_verify_batch_device',
     'zk_test_field_op', 'zk_test_tom_commit', 'zk_test_p256_fixed_mul', 'zk_test_sha256', 'zk_test_rng_draws', 'zk_test_exp_sum',
 ]
 
@@ -179,6 +180,13 @@ def lib():
         L.zk_link_prove_batch_device.argtypes = [vp, u64, vp, vp, vp, vp, vp, C.POINTER(ZkRng), vp, u64, vp]
         L.zk_link_verify_batch.argtypes = [vp, u64, C.c_char_p, C.c_char_p, C.c_char_p, vp, vp]
         L.zk_link_verify_batch_device.argtypes = [vp, u64, vp, vp, vp, vp, vp]
+        # distinct-key proofs ("ZKD1"): two commitments hide different keys
+        L.zk_distinct_proof_size.argtypes = []
+        L.zk_distinct_proof_size.restype = u64
+        L.zk_distinct_prove_batch.argtypes = [vp, u64, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(ZkRng), vp, u64, vp]
+        L.zk_distinct_prove_batch_device.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp, C.POINTER(ZkRng), vp, u64, vp]
+        L.zk_distinct_verify_batch.argtypes = [vp, u64, C.c_char_p, C.c_char_p, C.c_char_p, vp, vp]
+        L.zk_distinct_verify_batch_device.argtypes = [vp, u64, vp, vp, vp, vp, vp]
         L.zk_proof_key_commitments.argtypes = [vp, u64, C.c_char_p, vp, vp, vp]
         L.zk_proof_key_commitments_device.argtypes = [vp, u64, vp, vp, vp, vp]
         L.zk_ring_digest.argtypes = [vp, vp]
@@ -1138,6 +1146,53 @@ class Engine:
 
     def proof_key_commitments_device(self, B, d_proofs, d_off, d_com, d_status):
         self._chk(self.L.zk_proof_key_commitments_device(self.h, B, d_proofs, d_off, d_com, d_status))
+
+    # ---- distinct-key proofs (zk_distinct_*): two Tom-256 commitments hide DIFFERENT keys ("ZKD1", 744 bytes)
+    def distinct_proof_size(self):
+        return int(self.L.zk_distinct_proof_size())
+
+    @staticmethod
+    def distinct_pairs(k):
+        """the k (k - 1) / 2 pairs (i, j), i < j, of k commitments in lexicographic order: one distinct-key proof per pair shows k different keys"""
+        return [(i, j) for i in range(k) for j in range(i + 1, k)]
+
+    def distinct_prove_batch(self, key1, com1, blinder1, key2, com2, blinder2, seeds=None, streams=None, stream_blocks=0, cap=None):
+        """zk_distinct_prove_batch: proof b shows that com1[b] = key1[b] g + blinder1[b] h and com2[b] = key2[b] g + blinder2[b] h hide different keys; it
+        verifies for (com1, com2) in this order only.  keys, blinders: 32-byte big-endian scalars (a list, or B x 32 bytes), coms: 72-byte Tom-256 points.
+        seeds / streams must be FRESH: never the ones either commitment's proof was made with.  Returns (proofs: list of 744-byte strings, None where the
+        status is not 0; statuses); equal keys give status 14.  self.distinct_last_raw keeps the B slots as the call wrote them (a slot whose status is
+        not 0 is zero-filled), and cap overrides the out_cap handed to the call (default 744 B; a smaller one makes the call refuse with ZK_E_BUFFER)."""
+        B = len(key1) // 32 if isinstance(key1, (bytes, bytearray, memoryview)) else len(key1)
+        k1, c1, b1 = self._rows(key1, 32, B, 'key1'), self._rows(com1, 72, B, 'com1'), self._rows(blinder1, 32, B, 'blinder1')
+        k2, c2, b2 = self._rows(key2, 32, B, 'key2'), self._rows(com2, 72, B, 'com2'), self._rows(blinder2, 32, B, 'blinder2')
+        if seeds is None and streams is None:
+            seeds = os.urandom(32 * B)
+        rng, _keep = self._rng(B, seeds, streams, stream_blocks)
+        size = self.distinct_proof_size()
+        out = C.create_string_buffer(max(size * B, 1))
+        st = (C.c_int32 * max(B, 1))()
+        self._chk(self.L.zk_distinct_prove_batch(self.h, B, k1, c1, b1, k2, c2, b2, C.byref(rng), out, size * B if cap is None else cap, st))
+        raw = out.raw
+        self.distinct_last_raw = raw[:size * B]
+        return [raw[size * b:size * (b + 1)] if st[b] == 0 else None for b in range(B)], list(st)[:B]
+
+    def distinct_prove_batch_device(self, B, d_key1, d_com1, d_blinder1, d_key2, d_com2, d_blinder2, d_rng, d_out, out_cap, d_status, mode=0, stride_blocks=0):
+        rng = ZkRng(mode, d_rng, stride_blocks)
+        self._chk(self.L.zk_distinct_prove_batch_device(self.h, B, d_key1, d_com1, d_blinder1, d_key2, d_com2, d_blinder2, C.byref(rng), d_out, out_cap, d_status))
+
+    def distinct_verify_batch(self, com1, com2, proofs):
+        """zk_distinct_verify_batch for B (com1, com2, proof) triples, every proof 744 bytes.  Returns (ok list, status list)."""
+        B = len(proofs)
+        size = self.distinct_proof_size()
+        if any(len(p) != size for p in proofs):
+            raise ValueError('a distinct-key proof is %d bytes' % size)
+        ok = (C.c_uint8 * max(B, 1))()
+        st = (C.c_int32 * max(B, 1))()
+        self._chk(self.L.zk_distinct_verify_batch(self.h, B, self._rows(com1, 72, B, 'com1'), self._rows(com2, 72, B, 'com2'), b''.join(proofs) if B else bytes(size), ok, st))
+        return list(ok)[:B], list(st)[:B]
+
+    def distinct_verify_batch_device(self, B, d_com1, d_com2, d_proofs, d_ok, d_status):
+        self._chk(self.L.zk_distinct_verify_batch_device(self.h, B, d_com1, d_com2, d_proofs, d_ok, d_status))
 
     def synth_params(self, seed):
         a, b, c = C.create_string_buffer(64), C.create_string_buffer(72), C.create_string_buffer(72)

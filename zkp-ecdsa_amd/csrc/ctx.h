@@ -52,7 +52,8 @@ enum GrowPolicy {
     X(rr, GROW_EXACT, false)      /* re-ring calls (api_rering.hip): the census counters and every lane's per-proof arrays (head lengths, keyXcom, R: public) */ \
     X(ro, GROW_SPARE, false)      /* ... host-pointer form: staging of the re-ringed proofs (the input proofs lie in io) */ \
     X(kb, GROW_ONCE, true)        /* zk_prove_key_blinders: a chunk's rejection lists (derived from the seeds) and the call's exhaustion flag */ \
-    X(lk, GROW_SHED, true)        /* link proofs (api_link.hip): the lanes' arenas -- the staged key and blinders, the nonces k, s1, s2, the RNG fills, the challenge's message */
+    X(lk, GROW_SHED, true)        /* link proofs (api_link.hip): the lanes' arenas -- the staged key and blinders, the nonces k, s1, s2, the RNG fills, the challenge's message */ \
+    X(dk, GROW_SHED, true)        /* distinct-key proofs (api_distinct.hip): the lanes' arenas -- the staged keys and blinders, d, 1 / d, r_w, the nonces, the RNG fills, the challenge's message */
 enum BufId {
 #define X(name, policy, witness) B_##name,
     ZK_CTX_BUFS(X)

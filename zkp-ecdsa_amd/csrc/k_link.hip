@@ -8,34 +8,11 @@
 typedef Fe<ModQ, 1> Sq;
 typedef Fe<ModT, 1> St;
 
-// 72 bytes (two 36-byte big-endian coordinates, 4-byte aligned) -> 18 little-endian words; true where both are below the field prime and on the curve
-ZK_DEV bool lk_load_point(const uint8_t* p, uint32_t w[18]) {
-    const uint32_t* q = (const uint32_t*)p;
-#pragma unroll
-    for (int i = 0; i < 9; i++) w[i] = bswap32(q[8 - i]), w[9 + i] = bswap32(q[17 - i]);
-    return tom_words_on_curve(w, w + 9);
-}
-ZK_DEV Sq lk_load_scalar(const uint8_t* p) {   // newScalar reduces (group.ts:164-167)
-    uint32_t w[8];
-    load_be32(p, w);
-    return fe_from_words256_reduce<ModQ>(w);
-}
-// one point of the challenge's message: 04 || x (33 bytes) || y (33 bytes), from nine little-endian words per coordinate
-ZK_DEV void lk_put_point(uint8_t* m, const uint32_t* xw, const uint32_t* yw) {
-    m[0] = 4;
-#pragma unroll
-    for (int i = 0; i < 33; i++) m[1 + i] = (uint8_t)(xw[(32 - i) >> 2] >> (8 * ((32 - i) & 3))), m[34 + i] = (uint8_t)(yw[(32 - i) >> 2] >> (8 * ((32 - i) & 3)));
-}
 ZK_DEV void lk_put_padding(uint8_t* m) {   // behind the 268 message bytes: 0x80, zeros, the bit length
     m[268] = 0x80;
 #pragma unroll
     for (int i = 269; i < 318; i++) m[i] = 0;
     m[318] = (uint8_t)((268 * 8) >> 8), m[319] = (uint8_t)(268 * 8);
-}
-ZK_DEV TomPt lk_point_from_words(const uint32_t w[18]) {
-    TomPt r;
-    (void)tom_from_affine_words(r, w, w + 9);
-    return r;
 }
 
 // ------------------------------------------------------------------ prover

@@ -10,6 +10,7 @@
 //     pix: +27 k, +28 s1, +29 s2 | pi13: +30.. | piy: +37 k, +38 s1, +39 s2
 //   then g0 = 3 + 4 sec + 40 z:  g0+5i.. r_i, a_i, s_i, t_i, rho_i   (gk.ts:117-123)
 #include "engine.h"
+#include "distinct.h"   // mult_responses
 
 typedef Fe<ModQ, 1> Sq;  // canonical plain scalar mod q
 typedef Fe<ModN, 1> Sn;
@@ -281,17 +282,11 @@ void launch_padd_scalars(hipStream_t s, const DevParams&, const Workspace& W, ui
 // ---------------------------------------------------------------- PointAdd responses (mult.ts:122-130, equality.ts:73-77)
 ZK_DEV void mult_respond(const Workspace& W, uint32_t p, uint32_t dm, const uint32_t* c3, uint8_t* o, const Sq& x, const Sq& y, const Sq& z,
                          const Sq& rx, const Sq& ry, const Sq& rz) {
-    auto cm = fe_to_mont(chal_scalar(c3));
-    Sq kx = drawq(W, p, dm), ky = drawq(W, p, dm + 1), kz = drawq(W, p, dm + 2);
-    Sq sx = drawq(W, p, dm + 3), sy = drawq(W, p, dm + 4), sz = drawq(W, p, dm + 5), s4 = drawq(W, p, dm + 6);
-    Sq r4 = fe_mul_mod(x, ry);
-    store_scalar_be(o + 0, fe_sub_mod(kx, fe_canon(cm * x)));
-    store_scalar_be(o + 32, fe_sub_mod(ky, fe_canon(cm * y)));
-    store_scalar_be(o + 64, fe_sub_mod(kz, fe_canon(cm * z)));
-    store_scalar_be(o + 96, fe_sub_mod(sx, fe_canon(cm * rx)));
-    store_scalar_be(o + 128, fe_sub_mod(sy, fe_canon(cm * ry)));
-    store_scalar_be(o + 160, fe_sub_mod(sz, fe_canon(cm * rz)));
-    store_scalar_be(o + 192, fe_sub_mod(s4, fe_canon(cm * r4)));
+    const Sq k[7] = {drawq(W, p, dm), drawq(W, p, dm + 1), drawq(W, p, dm + 2), drawq(W, p, dm + 3), drawq(W, p, dm + 4), drawq(W, p, dm + 5), drawq(W, p, dm + 6)};
+    Sq t[7];
+    mult_responses(t, c3, k, x, y, z, rx, ry, rz);   // distinct.h: the distinct-key prover's responses are the same seven
+    store_scalar_be(o + 0, t[0]), store_scalar_be(o + 32, t[1]), store_scalar_be(o + 64, t[2]), store_scalar_be(o + 96, t[3]);
+    store_scalar_be(o + 128, t[4]), store_scalar_be(o + 160, t[5]), store_scalar_be(o + 192, t[6]);
 }
 ZK_DEV void eq_respond(const Workspace& W, uint32_t p, uint32_t de, const uint32_t* c3, uint8_t* o, const Sq& x, const Sq& rc1, const Sq& rc2) {
     auto cm = fe_to_mont(chal_scalar(c3));
