@@ -148,6 +148,20 @@ export function proveDifferentKeysBatch(params: PedersenParams | SystemParameter
 export function verifyDifferentKeysBatch(params: PedersenParams | SystemParametersList, comsA: LinkCom[], comsB: LinkCom[], proofs: (DistinctProof | Buffer)[]): Promise<boolean[]>
 /** the k (k - 1) / 2 pairs [i, j], i < j, of k commitments in lexicographic order: one distinct-key proof per pair shows k different signers */
 export function distinctPairs(k: number): [number, number][]
+/** Quorum proofs ("ZKQ1", zk_quorum_*): k attestations over one ring by k DIFFERENT members as one artifact -- a 16-byte header, the k attestations, the
+ *  k (k - 1) / 2 distinct-key proofs between their keyXcoms in distinctPairs(k)'s order.  It tells whoever sees it that its attestations come from different signers. */
+export class QuorumProof {
+    readonly bytes: Buffer
+    readonly k: number
+    constructor(zkq1: Buffer)
+    readonly attestations: SignatureProofList[]
+    readonly distinctProofs: DistinctProof[]
+    eq(o: QuorumProof): boolean
+}
+/** k = msgHashes.length attestations (2..16) signed by k different members of `keys`; throws when two signers are the same member */
+export function proveQuorum(params: SystemParametersList, msgHashes: Uint8Array[], sigs: Uint8Array[], publicKeys: PublicKey[], whichs: number[], keys: bigint[] | Buffer): Promise<QuorumProof>
+/** true iff every attestation verifies over `keys` for its message hash and every pair of them comes from different keys; what does not deserialise throws */
+export function verifyQuorum(params: SystemParametersList, msgHashes: Uint8Array[], keys: bigint[] | Buffer, proof: QuorumProof | Buffer): Promise<boolean>
 /** keyXcom of a proof (either wire layout; zk_proof_key_commitments) */
 export function keyCommitment(proof: SignatureProofList | Buffer, params?: SystemParametersList): Promise<Point>
 export function keyCommitments(proofs: (SignatureProofList | Buffer)[], params?: SystemParametersList): Promise<Point[]>
@@ -198,6 +212,10 @@ export class Engine {
     distinctProveBatch(key1: Buffer[], com1: Buffer[], blinder1: Buffer[], key2: Buffer[], com2: Buffer[], blinder2: Buffer[], seeds?: Buffer): { proofs: (Buffer | null)[]; status: Int32Array }
     /** zk_distinct_verify_batch */
     distinctVerifyBatch(com1: Buffer[], com2: Buffer[], proofs: Buffer[]): { ok: boolean[]; status: Int32Array }
+    /** zk_quorum_prove_batch over the active ring: Q quorums of k members, rows in member order (pk: 64-byte x | y per member); both seed sets must be fresh and independent (default: crypto.randomBytes).  status 14 with every memberStatus 0: two members have the same key */
+    quorumProveBatch(k: number, msg: Buffer, sig: Buffer, pk: Buffer, whichs: number[], seeds?: Buffer, pairSeeds?: Buffer): { bundles: (Buffer | null)[]; status: Int32Array; memberStatus: Int32Array }
+    /** zk_quorum_verify_batch: firstBad names the first member (< k) or pair (k + p) that failed, 0xFFFFFFFF where ok */
+    quorumVerifyBatch(k: number, msg: Buffer, bundles: Buffer[]): { ok: boolean[]; status: Int32Array; firstBad: Uint32Array }
     /** zk_link_verify_batch */
     linkVerifyBatch(com1: Buffer[], com2: Buffer[], proofs: Buffer[]): { ok: boolean[]; status: Int32Array }
     /** zk_proof_key_commitments: keyXcom of proofs in the engine's wire layout, 72 bytes each; null where the status is not 0 */

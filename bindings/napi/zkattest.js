@@ -476,6 +476,23 @@ class Engine {
         const r = native.distinctVerifyBatch(this.h, Buffer.concat(com1), Buffer.concat(com2), Buffer.concat(proofs))
         return { ok: Array.from(r.ok, (v) => v === 1), status: i32(r.status) }
     }
+    // quorum proofs (zk_quorum_*): "ZKQ1" bundles over the ACTIVE ring -- Q quorums of k members; member m = q k + i takes row m of msg, sig, pk (64-byte x | y),
+    // whichs and seeds, pair p of quorum q row q k (k - 1) / 2 + p of pairSeeds.  -> { bundles: Buffer | null per quorum, status: Int32Array, memberStatus: Int32Array }
+    // (status 14: two members of the quorum have the same key).  Both seed sets must be FRESH and independent of each other (default: crypto.randomBytes)
+    quorumProveBatch(k, msg, sig, pk, whichs, seeds, pairSeeds) {
+        const n = whichs.length, Q = n / k, P = k * (k - 1) / 2
+        const r = native.quorumProveBatch(this.h, k, msg, sig, pk, Buffer.from(Uint32Array.from(whichs).buffer), seeds || crypto.randomBytes(32 * n), pairSeeds || crypto.randomBytes(32 * Q * P))
+        const st = i32(r.status), o = u64(r.off)
+        return { bundles: Array.from(st, (s, q) => (s === 0 ? r.bundles.slice(Number(o[q]), Number(o[q + 1])) : null)), status: st, memberStatus: i32(r.memberStatus) }
+    }
+    // -> { ok: boolean[], status: Int32Array, firstBad: Uint32Array } -- firstBad names the first member (< k) or pair (k + p) that failed, 0xFFFFFFFF where ok
+    quorumVerifyBatch(k, msg, bundles) {
+        const Q = bundles.length, off = Buffer.alloc(8 * (Q + 1))
+        let run = 0
+        bundles.forEach((b, q) => { run += b.length; off.writeBigUInt64LE(BigInt(run), 8 * (q + 1)) })
+        const r = native.quorumVerifyBatch(this.h, k, msg, Buffer.concat(bundles), off)
+        return { ok: Array.from(r.ok, (v) => v === 1), status: i32(r.status), firstBad: new Uint32Array(Uint8Array.from(r.firstBad).buffer) }
+    }
     // zk_proof_key_commitments: keyXcom of every proof (Buffers in the engine's wire layout) as a 72-byte point -> { coms: Buffer | null per entry, status: Int32Array }
     keyCommitments(proofs) {
         const B = proofs.length, off = Buffer.alloc(8 * (B + 1))
@@ -1223,6 +1240,60 @@ async function verifyDifferentKeysBatch(params, comsA, comsB, proofs) {
     return r.ok
 }
 
-module.exports = { proveDifferentKeys, verifyDifferentKeys, proveDifferentKeysBatch, verifyDifferentKeysBatch, distinctPairs, DistinctProof, proveSameKey, verifySameKey, proveSameKeys, verifySameKeys, keyCommitment, keyCommitments, LinkProof, reringSignatureLists, keyBlinders, proveMembership, verifyMembership, proveMemberships, verifyMemberships, proveMembershipLists, verifyMembershipLists, GKProof, Commitment, commit, screenSignatureLists, findKey, SCREEN, WHICH_NONE, recoverSignatureLists, recoverKey, RECOVER, verifySignatureLists, proveSignatureLists, _ringGenerations, setVerifyLevel, getVerifyLevel, setVerifyReps, getVerifyReps, generateParamsList, generateParamsListHardened, keyToInt, proveSignatureList, verifySignatureList, proveSignatureListBatch, verifySignatureListBatch,
+// ---------------------------------------------------------------- quorum proofs: k attestations by k different ring members as one artifact
+// A QuorumProof keeps the engine's ZKQ1 bytes (include/zkattest.h): a 16-byte header, k attestations in one wire layout, k (k - 1) / 2 distinct-key proofs between
+// their keyXcoms in distinctPairs(k)'s order.  The key commitments are the ones inside the attestations: the distinct-key proofs cannot be checked against others.
+class QuorumProof {
+    constructor(bytes) {
+        const bad = () => new Error('error deserializing QuorumProof')
+        if (!(Buffer.isBuffer(bytes) && bytes.length >= 16 && bytes.slice(0, 4).toString('latin1') === 'ZKQ1' && bytes.readUInt32BE(4) === bytes.length && bytes.readUInt32BE(12) === 0)) throw bad()
+        const k = bytes.readUInt32BE(8)
+        if (k < 2 || k > 16) throw bad()
+        const end = bytes.length - 744 * (k * (k - 1) / 2)
+        let pos = 16
+        this.offsets = [pos]
+        for (let i = 0; i < k; i++) {
+            if (end - pos < 32) throw bad()
+            const len = bytes.readUInt32BE(pos + 4)
+            if (len < 32 || len % 4 || len > end - pos) throw bad()
+            pos += len
+            this.offsets.push(pos)
+        }
+        if (pos !== end) throw bad()
+        this.bytes = bytes
+        this.k = k
+    }
+    get attestations() { return Array.from({ length: this.k }, (_, i) => new SignatureProofList(this.bytes.slice(this.offsets[i], this.offsets[i + 1]))) }
+    get distinctProofs() { return distinctPairs(this.k).map((_, p) => new DistinctProof(this.bytes.slice(this.offsets[this.k] + 744 * p, this.offsets[this.k] + 744 * p + 744))) }
+    eq(o) { return o instanceof QuorumProof && this.bytes.equals(o.bytes) }
+}
+// proveQuorum(params, msgHashes, sigs, publicKeys, whichs, keys): k = msgHashes.length attestations over the ring `keys` (the arguments of proveSignatureListBatch),
+// signed by k DIFFERENT members -> QuorumProof.  Throws '... the same key ...' when two of the signers are the same member.  The engine draws both seed sets.
+async function proveQuorum(params, msgHashes, sigs, publicKeys, whichs, keys) {
+    const k = msgHashes.length
+    if (k < 2 || k > 16 || sigs.length !== k || publicKeys.length !== k || whichs.length !== k) throw new RangeError('proveQuorum: 2 to 16 members, one hash, signature, key and index each')
+    const raws = await Promise.all(publicKeys.map(rawPublicKey))
+    for (const r of raws) if (r.length !== 65 || r[0] !== 4) throw new Error('invalid public key')
+    const msg = Buffer.concat(msgHashes.map((m) => Buffer.from(m))), sig = Buffer.concat(sigs.map((s) => Buffer.from(s)))
+    checkRingSize(Buffer.isBuffer(keys) ? keys.length / 32 : keys.length, true)
+    const wire = wireLayout
+    const r = await engineFor(params, keys).withRing((engine) => { useWire(engine, wire); return engine.quorumProveBatch(k, msg, sig, Buffer.concat(raws.map((x) => x.slice(1))), whichs) })
+    if (r.status[0] === 14 && r.memberStatus.every((s) => s === 0)) throw new Error('two members of the quorum have the same key: no quorum proof exists')
+    if (r.status[0] !== 0) throw statusError(r.status[0])
+    return new QuorumProof(r.bundles[0])
+}
+// -> boolean: every attestation verifies over `keys` for its message hash and every pair of them comes from different keys.  What does not deserialise throws.
+async function verifyQuorum(params, msgHashes, keys, proof) {
+    const q = proof instanceof QuorumProof ? proof : new QuorumProof(proof)
+    if (msgHashes.length !== q.k) throw new RangeError('verifyQuorum: one message hash per member')
+    const msg = Buffer.concat(msgHashes.map((m) => Buffer.from(m)))
+    checkRingSize(Buffer.isBuffer(keys) ? keys.length / 32 : keys.length, false)
+    const wire = isPacked(q.bytes.slice(16)) ? 1 : 0, level = verifyLevel, reps = verifyReps
+    const r = await engineFor(params, keys).withRing((engine) => { useWire(engine, wire); useVerifyLevel(engine, level); useVerifyReps(engine, reps); return engine.quorumVerifyBatch(q.k, msg, [q.bytes]) })
+    if (r.status[0] !== 0) throw statusError(r.status[0])
+    return r.ok[0]
+}
+
+module.exports = { proveQuorum, verifyQuorum, QuorumProof, proveDifferentKeys, verifyDifferentKeys, proveDifferentKeysBatch, verifyDifferentKeysBatch, distinctPairs, DistinctProof, proveSameKey, verifySameKey, proveSameKeys, verifySameKeys, keyCommitment, keyCommitments, LinkProof, reringSignatureLists, keyBlinders, proveMembership, verifyMembership, proveMemberships, verifyMemberships, proveMembershipLists, verifyMembershipLists, GKProof, Commitment, commit, screenSignatureLists, findKey, SCREEN, WHICH_NONE, recoverSignatureLists, recoverKey, RECOVER, verifySignatureLists, proveSignatureLists, _ringGenerations, setVerifyLevel, getVerifyLevel, setVerifyReps, getVerifyReps, generateParamsList, generateParamsListHardened, keyToInt, proveSignatureList, verifySignatureList, proveSignatureListBatch, verifySignatureListBatch,
     writeJson, readJson, writeJsonBatch, readJsonBatch, SignatureProofList, SystemParametersList, PedersenParams, generatePedersenParams, p256, tomEdwards256, ALL_GROUPS,
     Group, Point, Scalar, Engine, shutdown, setWireLayout, getWireLayout, setOption, native }

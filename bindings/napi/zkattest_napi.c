@@ -1477,6 +1477,86 @@ static napi_value DistinctVerifyBatch(napi_env env, napi_callback_info info) {
     free(buf);
     return v;
 }
+/* Quorum proofs (include/zkattest.h: zk_quorum_*), on the pool's first context with its ACTIVE ring.
+ * (h, k, msg: Qk x 32, sig: Qk x 64, pk: Qk x 64, which: Qk u32 LE, seeds: Qk x 32, pairSeeds: Q k (k - 1) / 2 x 32 -- both FRESH and independent of each other)
+ * -> {bundles: the successful quorums' ZKQ1 bundles back to back, off: (Q + 1) u64 LE, status: Q i32 LE, memberStatus: Qk i32 LE} */
+static napi_value QuorumProveBatch(napi_env env, napi_callback_info info) {
+    napi_value argv[8];
+    if (!get_args(env, info, 8, argv)) return NULL;
+    Handle *h = get_handle(env, argv[0], 0);
+    uint32_t k = 0;
+    uint8_t *msg, *sig, *pk, *which, *seeds, *pseeds;
+    size_t lm, ls, lp, lw, lsd, lps;
+    if (!h || napi_get_value_uint32(env, argv[1], &k) != napi_ok || !get_bytes(env, argv[2], &msg, &lm) || !get_bytes(env, argv[3], &sig, &ls) || !get_bytes(env, argv[4], &pk, &lp) ||
+        !get_bytes(env, argv[5], &which, &lw) || !get_bytes(env, argv[6], &seeds, &lsd) || !get_bytes(env, argv[7], &pseeds, &lps))
+        return NULL;
+    const uint64_t P = zk_quorum_pair_count(k);
+    const size_t n = lm / 32, Q = P ? n / k : 0;
+    if (!P || lm % 32 || n != Q * k || ls != 64 * n || lp != 64 * n || lw != 4 * n || lsd != 32 * n || lps != 32 * Q * P) {
+        napi_throw_range_error(env, NULL, "quorumProveBatch: 2 <= k <= 16; per member a 32-byte hash, a 64-byte signature, a 64-byte key, a u32 index and 32 seed bytes; 32 seed bytes per pair");
+        return NULL;
+    }
+    zk_ctx *c = zk_pool_ctx(h->pool, 0);
+    const uint64_t cap = zk_quorum_proof_max_size(c, k) * Q;
+    uint8_t *buf = (uint8_t *)xmalloc(env, 8 * (Q + 1) + 4 * Q + 4 * n + cap + 8);
+    if (!buf) return NULL;
+    uint64_t *off = (uint64_t *)buf;
+    int32_t *status = (int32_t *)(buf + 8 * (Q + 1)), *mstatus = status + Q;
+    uint8_t *out = (uint8_t *)(mstatus + n);
+    uint32_t *w = (uint32_t *)xmalloc(env, 4 * n + 4);   /* (a Buffer's bytes need not be aligned) */
+    if (!w) {
+        free(buf);
+        return NULL;
+    }
+    memcpy(w, which, 4 * n);
+    zk_rng rng = {ZK_RNG_SEED, seeds, 0}, rng_pairs = {ZK_RNG_SEED, pseeds, 0};
+    zk_status st = zk_quorum_prove_batch(c, Q, k, msg, sig, pk, w, &rng, &rng_pairs, out, cap, off, status, mstatus);
+    napi_value v = NULL;
+    if (st != ZK_OK) throw_text(env, st, zk_last_error(c));
+    else if (napi_create_object(env, &v) == napi_ok)
+        set_prop(env, v, "bundles", new_buffer(env, out, off[Q])), set_prop(env, v, "off", new_buffer(env, off, 8 * (Q + 1))), set_prop(env, v, "status", new_buffer(env, status, 4 * Q)),
+            set_prop(env, v, "memberStatus", new_buffer(env, mstatus, 4 * n));
+    free(w);
+    free(buf);
+    return v;
+}
+/* (h, k, msg: Qk x 32, bundles: back to back, off: (Q + 1) u64 LE) -> {ok: Q bytes, status: Q i32 LE, firstBad: Q u32 LE} */
+static napi_value QuorumVerifyBatch(napi_env env, napi_callback_info info) {
+    napi_value argv[5];
+    if (!get_args(env, info, 5, argv)) return NULL;
+    Handle *h = get_handle(env, argv[0], 0);
+    uint32_t k = 0;
+    uint8_t *msg, *blob, *ob;
+    size_t lm, lb, lo;
+    if (!h || napi_get_value_uint32(env, argv[1], &k) != napi_ok || !get_bytes(env, argv[2], &msg, &lm) || !get_bytes(env, argv[3], &blob, &lb) || !get_bytes(env, argv[4], &ob, &lo))
+        return NULL;
+    const size_t Q = lo >= 8 ? lo / 8 - 1 : 0;
+    if (!zk_quorum_pair_count(k) || lo < 8 || lo % 8 || lm != 32 * Q * k) {
+        napi_throw_range_error(env, NULL, "quorumVerifyBatch: 2 <= k <= 16, (Q + 1) u64 offsets and k 32-byte hashes per bundle");
+        return NULL;
+    }
+    uint8_t *buf = (uint8_t *)xmalloc(env, 8 * (Q + 1) + 9 * Q + 8);
+    if (!buf) return NULL;
+    uint64_t *off = (uint64_t *)buf;
+    memcpy(off, ob, 8 * (Q + 1));
+    for (size_t q = 0; q <= Q; q++)
+        if (off[q] > lb) {   /* no slot may reach past the Buffer */
+            free(buf);
+            napi_throw_range_error(env, NULL, "quorumVerifyBatch: an offset lies behind the bundles");
+            return NULL;
+        }
+    int32_t *status = (int32_t *)(buf + 8 * (Q + 1));
+    uint32_t *bad = (uint32_t *)(status + Q);
+    uint8_t *ok = (uint8_t *)(bad + Q);
+    zk_ctx *c = zk_pool_ctx(h->pool, 0);
+    zk_status st = zk_quorum_verify_batch(c, Q, k, msg, blob, off, NULL, ok, status, bad);
+    napi_value v = NULL;
+    if (st != ZK_OK) throw_text(env, st, zk_last_error(c));
+    else if (napi_create_object(env, &v) == napi_ok)
+        set_prop(env, v, "ok", new_buffer(env, ok, Q)), set_prop(env, v, "status", new_buffer(env, status, 4 * Q)), set_prop(env, v, "firstBad", new_buffer(env, bad, 4 * Q));
+    free(buf);
+    return v;
+}
 /* zk_proof_key_commitments: (h, proofs: the B proofs back to back in the context's wire layout, off: (B + 1) u64 LE) -> {coms: B x 72 (zeros where status != 0),
  * status: B i32 LE} */
 static napi_value KeyCommitments(napi_env env, napi_callback_info info) {
@@ -1535,7 +1615,8 @@ static napi_value Init(napi_env env, napi_value exports) {
                {"memberProveBatchRingsBound", MemberProveBatchRingsBound}, {"memberVerifyBatchRingsBound", MemberVerifyBatchRingsBound},
                {"keyBlinders", KeyBlinders},     {"reringBatch", ReringBatch},     {"reringBatchRings", ReringBatchRings},
                {"linkProveBatch", LinkProveBatch}, {"linkVerifyBatch", LinkVerifyBatch}, {"keyCommitments", KeyCommitments},
-               {"distinctProveBatch", DistinctProveBatch}, {"distinctVerifyBatch", DistinctVerifyBatch}};
+               {"distinctProveBatch", DistinctProveBatch}, {"distinctVerifyBatch", DistinctVerifyBatch},
+               {"quorumProveBatch", QuorumProveBatch}, {"quorumVerifyBatch", QuorumVerifyBatch}};
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;
         if (napi_create_function(env, fns[i].name, NAPI_AUTO_LENGTH, fns[i].fn, NULL, &f) != napi_ok) return NULL;

@@ -798,6 +798,57 @@ zk_status zk_distinct_verify_batch(zk_ctx *ctx, uint64_t B, const uint8_t *com1_
 zk_status zk_distinct_verify_batch_device(zk_ctx *ctx, uint64_t B, const void *d_com1_xy72, const void *d_com2_xy72, const void *d_proofs, void *d_ok,
                                           void *d_per_proof_status /*i32[B]*/);
 
+/* ---- quorum proofs: k attestations by k DIFFERENT ring members, as one artifact.  The recipe of INTEGRATION.md "Counting signers" -- zk_prove_batch,
+ * zk_prove_key_blinders with the same seeds, zk_proof_key_commitments, zk_distinct_prove_batch over the pairs (and the mirror image for the verifier) -- as one
+ * prove call and one verify call with a wire format of its own; the pairs are expanded, gathered and judged on the device.  No existing call changes.
+ * Wire format "ZKQ1" (a bundle), 2 <= k <= 16, P = k (k - 1) / 2 <= 120:
+ *     header 16 B : "ZKQ1" | total_len u32 big-endian | k u32 big-endian | 0 u32
+ *     k attestations : ZKA1 / ZK1P proofs in the context's wire layout (zk_ctx_set_wire), back to back in member order, each exactly as zk_prove_batch writes
+ *                      it (each carries its own total_len, a multiple of 4)
+ *     P distinct-key proofs : ZKD1, 744 B each, in the order (0,1), (0,2), ..., (0,k-1), (1,2), ..., (k-2,k-1); pair (i, j) is proved for
+ *                      (com1, com2) = (keyXcom of member i, keyXcom of member j), in that direction
+ *   The key commitments are not repeated: they are the keyXcoms inside the k attestations, read by the rules of zk_proof_key_commitments, so the distinct-key
+ *   proofs can only be checked against the attestations they travel with.  Attestation lengths vary with the Exp challenge, so a bundle's length varies;
+ *   zk_quorum_proof_max_size(ctx, k) = 16 + k zk_proof_max_size(ctx) + 744 P.
+ * Member m = q k + i of quorum q uses row m of msg_hash, sig, pk_xy, which and rng; pair p of quorum q uses row q P + p of rng_pairs.
+ * zk_quorum_prove_batch: where quorum q succeeds its bundle is, byte for byte, the header, the k proofs zk_prove_batch makes for those members with the active
+ *   ring under rng's rows, and the P proofs zk_distinct_prove_batch makes under rng_pairs' rows with key = pk_xy[0:32], com = the member's keyXcom and blinder =
+ *   what zk_prove_key_blinders gives for the member's row: the bytes of the recipe, in both protocol modes and wire layouts, whatever the comb width or build.
+ *   A quorum's status is the first non-zero one of: its members' zk_prove_batch statuses in member order; ZK_E_ARG if two of its members have the same key mod
+ *   q (no distinct-key proof exists); its pairs' statuses in pair order (ZK_E_RNG_EXHAUSTED on a short pair stream).  A failed quorum gets an empty slot
+ *   (out_off[q + 1] = out_off[q]), the bundles behind it close up, no neighbour's byte changes.  per_member_status (may be NULL) receives the Q k member
+ *   statuses.  ZK_E_BUFFER when out_cap < Q zk_quorum_proof_max_size, decided before a byte of any output is written.
+ * zk_quorum_verify_batch: per quorum, the first rule that matches:
+ *     ZK_E_BAD_ENCODING with ok 0 and first_bad 0, no byte outside the slot read: a wrong magic, total_len != the slot's length, header k != the call's k, a
+ *       non-zero reserved word, a slot offset or length that is no multiple of 4 or offsets that do not ascend, or the k inner headers (magic of the context's
+ *       layout, total_len, the rules of zk_proof_rering_batch) not walking from byte 16 exactly to total_len - 744 P.
+ *   Otherwise the k members are verified exactly as zk_verify_batch verifies them (the active ring, zk_ctx_set_verify_level and zk_ctx_set_verify_reps,
+ *   verifier_seeds row m or the library's own) and the P pairs exactly as zk_distinct_verify_batch does over the members' keyXcoms.  ok = 1 iff all k + P
+ *   elements are ok; per_quorum_status is the first non-zero element status, members before pairs, in index order; first_bad (may be NULL) is the smallest
+ *   element index e whose ok is 0 or whose status is non-zero -- 0 <= e < k names a member, k <= e < k + P a pair -- and 0xFFFFFFFF where ok = 1.
+ * Call-level rules are the distinct calls' plus the prover's: ZK_E_BUFFER without params or without an active ring; ZK_E_ARG for NULL pointers other than the
+ *   two optional arrays, for k outside 2..16, for Q k or Q P >= 2^32 and while streamed jobs are queued; Q = 0 is ZK_OK with out_off[0] = 0.  The _device
+ *   forms take every pointer, both rng->data included, in this context's HBM, 4-byte aligned, else ZK_E_ARG.  A call runs in windows of whole quorums of at
+ *   most chunk x lanes members; what is witness-derived -- the gathered keys and blinders, both RNG fills, the distinct prover's arena, the staged inputs --
+ *   is zeroed by zk_ctx_wipe, zk_ctx_destroy and a failed call.  zk_last_timing reports the families of the calls above plus "quorum_blinders",
+ *   "quorum_gather", "quorum_layout" (prover) and "quorum_walk", "quorum_verdict" (verifier).
+ * Not provided: one ring id per member, submit / wait forms, zk_pool_* forms, JSON, a caller-context binding.
+ * Two warnings.  (1) rng_pairs must be independent of rng: with an attestation's own seed the fills that blinded comS1 and keyXcom would come back as a
+ *   distinct-key proof's r_w and k_x.  (2) A bundle tells whoever sees it that its attestations come from different signers; keep it for whom it is meant.
+ * DESIGN.md section 5g. */
+uint64_t zk_quorum_pair_count(uint32_t k);                         /* k (k - 1) / 2; 0 for k outside 2..16 */
+uint64_t zk_quorum_proof_max_size(const zk_ctx *ctx, uint32_t k);  /* 0 without params / an active ring, or k outside 2..16 */
+zk_status zk_quorum_prove_batch(zk_ctx *ctx, uint64_t Q, uint32_t k, const uint8_t *msg_hash /*Qkx32*/, const uint8_t *sig /*Qkx64*/, const uint8_t *pk_xy /*Qkx64*/,
+                                const uint32_t *which /*Qk*/, const zk_rng *rng /*Qk rows*/, const zk_rng *rng_pairs /*QP rows*/, uint8_t *out, uint64_t out_cap,
+                                uint64_t *out_off /*Q+1*/, int32_t *per_quorum_status /*Q*/, int32_t *per_member_status /*Qk or NULL*/);
+zk_status zk_quorum_prove_batch_device(zk_ctx *ctx, uint64_t Q, uint32_t k, const void *d_msg_hash, const void *d_sig, const void *d_pk_xy, const void *d_which,
+                                       const zk_rng *rng_device, const zk_rng *rng_pairs_device, void *d_out, uint64_t out_cap, void *d_out_off /*u64[Q+1]*/,
+                                       void *d_per_quorum_status /*i32[Q]*/, void *d_per_member_status /*i32[Qk] or NULL*/);
+zk_status zk_quorum_verify_batch(zk_ctx *ctx, uint64_t Q, uint32_t k, const uint8_t *msg_hash /*Qkx32*/, const uint8_t *bundles, const uint64_t *bundle_off /*Q+1*/,
+                                 const uint8_t *verifier_seeds /*Qkx32 or NULL*/, uint8_t *ok /*Q*/, int32_t *per_quorum_status /*Q*/, uint32_t *first_bad /*Q or NULL*/);
+zk_status zk_quorum_verify_batch_device(zk_ctx *ctx, uint64_t Q, uint32_t k, const void *d_msg_hash, const void *d_bundles, const void *d_bundle_off /*u64[Q+1]*/,
+                                        const void *d_verifier_seeds, void *d_ok, void *d_per_quorum_status /*i32[Q]*/, void *d_first_bad /*u32[Q] or NULL*/);
+
 /* ---- two (or more) batches in flight on one context.  zk_prove_batch / zk_verify_batch are synchronous: each call pays its own head
  * (no byte of a chunk exists before its stage 1 is over) and its own tail (the copies of the last slices, with nothing left to
  * hide them).  The submit / wait pair splits a call so that the pipeline keeps running ACROSS calls: submit stages the inputs and

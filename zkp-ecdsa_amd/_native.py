@@ -37,6 +37,7 @@ SYMBOLS = [
     'zk_link_proof_size', 'zk_link_prove_batch', 'zk_link_prove_batch_device', 'zk_link_verify_batch', 'zk_link_verify_batch_device',
     'zk_proof_key_commitments', 'zk_proof_key_commitments_device',
     'zk_distinct_proof_size', 'zk_distinct_prove_batch', 'zk_distinct_prove_batch_device', 'zk_distinct_verify_batch', 'zk_distinct_verify_batch_device',
+    'zk_quorum_pair_count', 'zk_quorum_proof_max_size', 'zk_quorum_prove_batch', 'zk_quorum_prove_batch_device', 'zk_quorum_verify_batch', 'zk_quorum_verify_batch_device',
     'zk_test_field_op', 'zk_test_tom_commit', 'zk_test_p256_fixed_mul', 'zk_test_sha256', 'zk_test_rng_draws', 'zk_test_exp_sum',
 ]
 
@@ -187,6 +188,15 @@ def lib():
         L.zk_distinct_prove_batch_device.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp, C.POINTER(ZkRng), vp, u64, vp]
         L.zk_distinct_verify_batch.argtypes = [vp, u64, C.c_char_p, C.c_char_p, C.c_char_p, vp, vp]
         L.zk_distinct_verify_batch_device.argtypes = [vp, u64, vp, vp, vp, vp, vp]
+        # quorum proofs ("ZKQ1"): k attestations and the distinct-key proofs between their keyXcoms as one bundle
+        L.zk_quorum_pair_count.argtypes = [C.c_uint32]
+        L.zk_quorum_pair_count.restype = u64
+        L.zk_quorum_proof_max_size.argtypes = [vp, C.c_uint32]
+        L.zk_quorum_proof_max_size.restype = u64
+        L.zk_quorum_prove_batch.argtypes = [vp, u64, C.c_uint32, C.c_char_p, C.c_char_p, C.c_char_p, vp, C.POINTER(ZkRng), C.POINTER(ZkRng), vp, u64, vp, vp, vp]
+        L.zk_quorum_prove_batch_device.argtypes = [vp, u64, C.c_uint32, vp, vp, vp, vp, C.POINTER(ZkRng), C.POINTER(ZkRng), vp, u64, vp, vp, vp]
+        L.zk_quorum_verify_batch.argtypes = [vp, u64, C.c_uint32, C.c_char_p, C.c_char_p, vp, C.c_char_p, vp, vp, vp]
+        L.zk_quorum_verify_batch_device.argtypes = [vp, u64, C.c_uint32, vp, vp, vp, vp, vp, vp, vp]
         L.zk_proof_key_commitments.argtypes = [vp, u64, C.c_char_p, vp, vp, vp]
         L.zk_proof_key_commitments_device.argtypes = [vp, u64, vp, vp, vp, vp]
         L.zk_ring_digest.argtypes = [vp, vp]
@@ -1193,6 +1203,65 @@ class Engine:
 
     def distinct_verify_batch_device(self, B, d_com1, d_com2, d_proofs, d_ok, d_status):
         self._chk(self.L.zk_distinct_verify_batch_device(self.h, B, d_com1, d_com2, d_proofs, d_ok, d_status))
+
+    # ---- quorum proofs (zk_quorum_*): k attestations by k different ring members as one "ZKQ1" bundle
+    def quorum_pair_count(self, k):
+        """zk_quorum_pair_count: k (k - 1) / 2, 0 for a k outside 2..16"""
+        return int(self.L.zk_quorum_pair_count(k))
+
+    def quorum_proof_max_size(self, k):
+        """zk_quorum_proof_max_size: upper bound of one bundle's size over the active ring (0 without params / ring or for a k outside 2..16)"""
+        return int(self.L.zk_quorum_proof_max_size(self.h, k))
+
+    def quorum_prove_batch(self, k, msg, sig, pk, which, seeds=None, pair_seeds=None, streams=None, stream_blocks=0, pair_streams=None, pair_stream_blocks=0,
+                           cap=None, want_member_status=True):
+        """zk_quorum_prove_batch: Q = len(which) // k quorums of k members each over the active ring; member m = q k + i uses row m of msg, sig, pk, which and
+        seeds, pair p of quorum q row q P + p of pair_seeds (P = k (k - 1) / 2).  Both seed sets come from os.urandom when absent; they must be independent of
+        each other.  Returns (bundles: list of byte strings, None where the quorum's status is not 0; quorum statuses; member statuses).  cap overrides the
+        out_cap handed to the call."""
+        n = len(which)
+        if k <= 0 or n % k:
+            raise ValueError('k members per quorum')
+        Q, P = n // k, k * (k - 1) // 2
+        if seeds is None and streams is None:
+            seeds = os.urandom(32 * n)
+        if pair_seeds is None and pair_streams is None:
+            pair_seeds = os.urandom(32 * Q * P)
+        rng, _keep = self._rng(n, seeds, streams, stream_blocks)
+        rng_pairs, _keep2 = self._rng(Q * P, pair_seeds, pair_streams, pair_stream_blocks)
+        size = max(self.quorum_proof_max_size(k) * Q, 16)
+        out = C.create_string_buffer(size)
+        off = (C.c_uint64 * (Q + 1))()
+        st = (C.c_int32 * max(Q, 1))()
+        mst = (C.c_int32 * max(n, 1))()
+        w = (C.c_uint32 * max(n, 1))(*which)
+        self._chk(self.L.zk_quorum_prove_batch(self.h, Q, k, bytes(msg), bytes(sig), bytes(pk), w, C.byref(rng), C.byref(rng_pairs), out, size if cap is None else cap, off, st,
+                                               mst if want_member_status else None))
+        raw = out.raw
+        return [raw[off[q]:off[q + 1]] if st[q] == 0 else None for q in range(Q)], list(st)[:Q], list(mst)[:n] if want_member_status else None
+
+    def quorum_prove_batch_device(self, Q, k, d_msg, d_sig, d_pk, d_which, d_rng, d_rng_pairs, d_out, out_cap, d_out_off, d_status, d_member_status=None, mode=0, stride_blocks=0,
+                                  pair_mode=0, pair_stride_blocks=0):
+        rng, rng_pairs = ZkRng(mode, d_rng, stride_blocks), ZkRng(pair_mode, d_rng_pairs, pair_stride_blocks)
+        self._chk(self.L.zk_quorum_prove_batch_device(self.h, Q, k, d_msg, d_sig, d_pk, d_which, C.byref(rng), C.byref(rng_pairs), d_out, out_cap, d_out_off, d_status,
+                                                      d_member_status))
+
+    def quorum_verify_batch(self, k, msg, bundles, vseeds=None, want_first_bad=True):
+        """zk_quorum_verify_batch: bundle q against rows q k .. q k + k - 1 of msg.  Returns (ok list, status list, first_bad list): first_bad names the first
+        element that failed -- a member (< k) or a pair (k + p) -- and is 0xFFFFFFFF where ok is 1."""
+        Q = len(bundles)
+        off = (C.c_uint64 * (Q + 1))()
+        for q, b in enumerate(bundles):
+            off[q + 1] = off[q] + len(b)
+        ok = (C.c_uint8 * max(Q, 1))()
+        st = (C.c_int32 * max(Q, 1))()
+        bad = (C.c_uint32 * max(Q, 1))()
+        self._chk(self.L.zk_quorum_verify_batch(self.h, Q, k, bytes(msg), b''.join(bundles) if Q else bytes(16), off, None if vseeds is None else bytes(vseeds), ok, st,
+                                                bad if want_first_bad else None))
+        return list(ok)[:Q], list(st)[:Q], list(bad)[:Q] if want_first_bad else None
+
+    def quorum_verify_batch_device(self, Q, k, d_msg, d_bundles, d_bundle_off, d_vseeds, d_ok, d_status, d_first_bad=None):
+        self._chk(self.L.zk_quorum_verify_batch_device(self.h, Q, k, d_msg, d_bundles, d_bundle_off, d_vseeds, d_ok, d_status, d_first_bad))
 
     def synth_params(self, seed):
         a, b, c = C.create_string_buffer(64), C.create_string_buffer(72), C.create_string_buffer(72)

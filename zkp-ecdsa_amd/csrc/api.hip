@@ -1356,6 +1356,11 @@ static zk_status prove_device(zk_ctx* c, uint64_t B, const uint8_t* d_msg, const
     return ZK_OK;
 }
 
+// zk_prove_batch_device's pipeline for api_quorum.hip (quorum.h)
+zk_status zkq_prove_members(zk_ctx* c, uint64_t B, const uint8_t* d_msg, const uint8_t* d_sig, const uint8_t* d_pk, const uint32_t* d_which, const zk_rng& rng, uint8_t* d_out,
+                            uint64_t out_cap, uint64_t* d_out_off, int32_t* d_status) {
+    return prove_device(c, B, d_msg, d_sig, d_pk, d_which, rng.mode, rng.data, rng.stride_blocks, d_out, out_cap, d_out_off, d_status);
+}
 extern "C" zk_status zk_prove_batch_device(zk_ctx* c, uint64_t B, const void* d_msg, const void* d_sig, const void* d_pk, const void* d_which,
                                            const zk_rng* rng, void* d_out, uint64_t out_cap, void* d_out_off, void* d_status) {
     if (!c || !rng || (B && (!d_msg || !d_sig || !d_pk || !d_which || !rng->data || !d_out)) || !d_out_off || !d_status) return ZK_E_ARG;

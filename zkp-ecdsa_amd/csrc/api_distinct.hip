@@ -236,3 +236,12 @@ extern "C" zk_status zk_distinct_verify_batch(zk_ctx* c, uint64_t B, const uint8
     HIPCHK(c, hipStreamSynchronize(s));
     return ZK_OK;
 }
+
+// ------------------------------------------------------------------ the two pipelines for api_quorum.hip (quorum.h), behind the entry points' argument checks
+zk_status zkq_distinct_prove(zk_ctx* c, uint64_t B, const uint8_t* key1, const uint8_t* com1, const uint8_t* blinder1, const uint8_t* key2, const uint8_t* com2,
+                             const uint8_t* blinder2, const zk_rng& rng, uint8_t* out, int32_t* status) {
+    return dist_prove_device(c, B, {key1, com1, blinder1, key2, com2, blinder2, out, status}, rng, B * ZKD1_SIZE);
+}
+zk_status zkq_distinct_verify(zk_ctx* c, uint64_t B, const uint8_t* com1, const uint8_t* com2, const uint8_t* proofs, uint8_t* ok, int32_t* status) {
+    return dist_verify_device(c, B, {com1, com2, proofs, ok, status});
+}

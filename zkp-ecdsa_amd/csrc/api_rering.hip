@@ -503,3 +503,6 @@ extern "C" zk_status zk_proof_rering_batch_rings(zk_ctx* c, uint64_t B, const ui
     }
     return download_or_wipe(c, {{I.one.out_off, out_off, 8 * (B + 1)}, {I.one.st, status, 4 * B}, {d_out, out, need}});
 }
+
+// zk_prove_key_blinders_device's pipeline for api_quorum.hip (quorum.h)
+zk_status zkq_key_blinders(zk_ctx* c, uint64_t B, const zk_rng& rng, uint8_t* d_out) { return key_blinders_device(c, B, rng, d_out); }

@@ -1086,6 +1086,12 @@ extern "C" zk_status zk_verify_batch_device(zk_ctx* c, uint64_t B, const void* d
                                 false);
     return verify_device(c, B, (const uint8_t*)d_msg, (const uint8_t*)d_proofs, (const uint64_t*)d_off, (const uint8_t*)d_vseeds, (uint8_t*)d_ok, (int32_t*)d_status);
 }
+// zk_verify_batch_device's pipeline for api_quorum.hip (quorum.h); the lanes order themselves behind what c->stream carries
+zk_status zkq_verify_members(zk_ctx* c, uint64_t B, const uint8_t* d_msg, const uint8_t* d_proofs, const uint64_t* d_off, const uint8_t* d_vseeds, uint8_t* d_ok,
+                             int32_t* d_status) {
+    if (c->verify_level == ZK_VERIFY_LEVEL_PER_PROOF) return verify_per_proof(c, B, d_msg, d_proofs, d_off, d_vseeds, d_ok, d_status, true);
+    return verify_device(c, B, d_msg, d_proofs, d_off, d_vseeds, d_ok, d_status, nullptr, nullptr, true);
+}
 extern "C" zk_status zk_verify_batch(zk_ctx* c, uint64_t B, const uint8_t* msg, const uint8_t* proofs, const uint64_t* off, const uint8_t* vseeds, uint8_t* ok,
                                      int32_t* status) {
     if (!c || (B && (!msg || !proofs || !off || !ok || !status))) return ZK_E_ARG;
