@@ -148,6 +148,10 @@ export function proveDifferentKeysBatch(params: PedersenParams | SystemParameter
 export function verifyDifferentKeysBatch(params: PedersenParams | SystemParametersList, comsA: LinkCom[], comsB: LinkCom[], proofs: (DistinctProof | Buffer)[]): Promise<boolean[]>
 /** the k (k - 1) / 2 pairs [i, j], i < j, of k commitments in lexicographic order: one distinct-key proof per pair shows k different signers */
 export function distinctPairs(k: number): [number, number][]
+/** `keys` of proveQuorum / verifyQuorum: one ring for all members, or one key list PER MEMBER (the convention of reringSignatureLists) for a registry sharded over
+ *  several rings -- then whichs[i] indexes list i, all lists of a quorum are resident at once (at most residentRings different ones), and a key enrolled in two
+ *  lists and used through both counts as the same key. */
+export type QuorumKeys = bigint[] | Buffer | Array<bigint[] | Buffer>
 /** Quorum proofs ("ZKQ1", zk_quorum_*): k attestations over one ring by k DIFFERENT members as one artifact -- a 16-byte header, the k attestations, the
  *  k (k - 1) / 2 distinct-key proofs between their keyXcoms in distinctPairs(k)'s order.  It tells whoever sees it that its attestations come from different signers. */
 export class QuorumProof {
@@ -159,9 +163,9 @@ export class QuorumProof {
     eq(o: QuorumProof): boolean
 }
 /** k = msgHashes.length attestations (2..16) signed by k different members of `keys`; throws when two signers are the same member */
-export function proveQuorum(params: SystemParametersList, msgHashes: Uint8Array[], sigs: Uint8Array[], publicKeys: PublicKey[], whichs: number[], keys: bigint[] | Buffer): Promise<QuorumProof>
+export function proveQuorum(params: SystemParametersList, msgHashes: Uint8Array[], sigs: Uint8Array[], publicKeys: PublicKey[], whichs: number[], keys: QuorumKeys): Promise<QuorumProof>
 /** true iff every attestation verifies over `keys` for its message hash and every pair of them comes from different keys; what does not deserialise throws */
-export function verifyQuorum(params: SystemParametersList, msgHashes: Uint8Array[], keys: bigint[] | Buffer, proof: QuorumProof | Buffer): Promise<boolean>
+export function verifyQuorum(params: SystemParametersList, msgHashes: Uint8Array[], keys: QuorumKeys, proof: QuorumProof | Buffer): Promise<boolean>
 /** keyXcom of a proof (either wire layout; zk_proof_key_commitments) */
 export function keyCommitment(proof: SignatureProofList | Buffer, params?: SystemParametersList): Promise<Point>
 export function keyCommitments(proofs: (SignatureProofList | Buffer)[], params?: SystemParametersList): Promise<Point[]>
@@ -216,6 +220,10 @@ export class Engine {
     quorumProveBatch(k: number, msg: Buffer, sig: Buffer, pk: Buffer, whichs: number[], seeds?: Buffer, pairSeeds?: Buffer): { bundles: (Buffer | null)[]; status: Int32Array; memberStatus: Int32Array }
     /** zk_quorum_verify_batch: firstBad names the first member (< k) or pair (k + p) that failed, 0xFFFFFFFF where ok */
     quorumVerifyBatch(k: number, msg: Buffer, bundles: Buffer[]): { ok: boolean[]; status: Int32Array; firstBad: Uint32Array }
+    /** zk_rings_quorum_prove_batch: quorumProveBatch with one RESIDENT ring id per member (whichs[m] indexes ring ringIds[m]); the active ring plays no part */
+    ringsQuorumProveBatch(k: number, msg: Buffer, sig: Buffer, pk: Buffer, whichs: number[], ringIds: number[], seeds?: Buffer, pairSeeds?: Buffer): { bundles: (Buffer | null)[]; status: Int32Array; memberStatus: Int32Array }
+    /** zk_rings_quorum_verify_batch: quorumVerifyBatch with one RESIDENT ring id per member; an id that is not resident fails its member with status 14 */
+    ringsQuorumVerifyBatch(k: number, msg: Buffer, bundles: Buffer[], ringIds: number[]): { ok: boolean[]; status: Int32Array; firstBad: Uint32Array }
     /** zk_link_verify_batch */
     linkVerifyBatch(com1: Buffer[], com2: Buffer[], proofs: Buffer[]): { ok: boolean[]; status: Int32Array }
     /** zk_proof_key_commitments: keyXcom of proofs in the engine's wire layout, 72 bytes each; null where the status is not 0 */

@@ -493,6 +493,22 @@ class Engine {
         const r = native.quorumVerifyBatch(this.h, k, msg, Buffer.concat(bundles), off)
         return { ok: Array.from(r.ok, (v) => v === 1), status: i32(r.status), firstBad: new Uint32Array(Uint8Array.from(r.firstBad).buffer) }
     }
+    // zk_rings_quorum_prove_batch / zk_rings_quorum_verify_batch: the same with one RESIDENT ring id per member (ringIds[m]; whichs[m] indexes that ring); the
+    // active ring plays no part.  A key enrolled in two rings and used through both is "the same key" (status 14)
+    ringsQuorumProveBatch(k, msg, sig, pk, whichs, ringIds, seeds, pairSeeds) {
+        const n = whichs.length, Q = n / k, P = k * (k - 1) / 2
+        const u32 = (a) => Buffer.from(Uint32Array.from(a).buffer)
+        const r = native.ringsQuorumProveBatch(this.h, k, msg, sig, pk, u32(whichs), u32(ringIds), seeds || crypto.randomBytes(32 * n), pairSeeds || crypto.randomBytes(32 * Q * P))
+        const st = i32(r.status), o = u64(r.off)
+        return { bundles: Array.from(st, (s, q) => (s === 0 ? r.bundles.slice(Number(o[q]), Number(o[q + 1])) : null)), status: st, memberStatus: i32(r.memberStatus) }
+    }
+    ringsQuorumVerifyBatch(k, msg, bundles, ringIds) {
+        const Q = bundles.length, off = Buffer.alloc(8 * (Q + 1))
+        let run = 0
+        bundles.forEach((b, q) => { run += b.length; off.writeBigUInt64LE(BigInt(run), 8 * (q + 1)) })
+        const r = native.ringsQuorumVerifyBatch(this.h, k, msg, Buffer.concat(bundles), off, Buffer.from(Uint32Array.from(ringIds).buffer))
+        return { ok: Array.from(r.ok, (v) => v === 1), status: i32(r.status), firstBad: new Uint32Array(Uint8Array.from(r.firstBad).buffer) }
+    }
     // zk_proof_key_commitments: keyXcom of every proof (Buffers in the engine's wire layout) as a 72-byte point -> { coms: Buffer | null per entry, status: Int32Array }
     keyCommitments(proofs) {
         const B = proofs.length, off = Buffer.alloc(8 * (B + 1))
@@ -1267,6 +1283,24 @@ class QuorumProof {
     get distinctProofs() { return distinctPairs(this.k).map((_, p) => new DistinctProof(this.bytes.slice(this.offsets[this.k] + 744 * p, this.offsets[this.k] + 744 * p + 744))) }
     eq(o) { return o instanceof QuorumProof && this.bytes.equals(o.bytes) }
 }
+// `keys` of proveQuorum / verifyQuorum as one key list PER MEMBER: the different rings among them, and each member's.  A quorum is one call: all its rings are
+// resident at once, so it may name at most residentRings of them.
+function quorumRings(keyLists, k, proving) {
+    if (keyLists.length !== k) throw new RangeError('one key list per member')
+    const rings = [], ringOfMember = new Array(k), byTag = new Map()
+    keyLists.forEach((keys, i) => {
+        checkRingSize(Buffer.isBuffer(keys) ? keys.length / 32 : keys.length, proving)
+        const r = ringOf(keys)
+        if (!byTag.has(r.tag)) { byTag.set(r.tag, rings.length); rings.push(r) }
+        ringOfMember[i] = byTag.get(r.tag)
+    })
+    return { rings, ringOfMember }
+}
+function quorumEngine(params, keyLists, rings) {
+    const e = engineFor(params, keyLists[0])
+    if (rings.length > e.capacity()) throw new RangeError('a quorum names more rings than residentRings')
+    return e
+}
 // proveQuorum(params, msgHashes, sigs, publicKeys, whichs, keys): k = msgHashes.length attestations over the ring `keys` (the arguments of proveSignatureListBatch),
 // signed by k DIFFERENT members -> QuorumProof.  Throws '... the same key ...' when two of the signers are the same member.  The engine draws both seed sets.
 async function proveQuorum(params, msgHashes, sigs, publicKeys, whichs, keys) {
@@ -1274,10 +1308,16 @@ async function proveQuorum(params, msgHashes, sigs, publicKeys, whichs, keys) {
     if (k < 2 || k > 16 || sigs.length !== k || publicKeys.length !== k || whichs.length !== k) throw new RangeError('proveQuorum: 2 to 16 members, one hash, signature, key and index each')
     const raws = await Promise.all(publicKeys.map(rawPublicKey))
     for (const r of raws) if (r.length !== 65 || r[0] !== 4) throw new Error('invalid public key')
-    const msg = Buffer.concat(msgHashes.map((m) => Buffer.from(m))), sig = Buffer.concat(sigs.map((s) => Buffer.from(s)))
-    checkRingSize(Buffer.isBuffer(keys) ? keys.length / 32 : keys.length, true)
+    const msg = Buffer.concat(msgHashes.map((m) => Buffer.from(m))), sig = Buffer.concat(sigs.map((s) => Buffer.from(s))), pk = Buffer.concat(raws.map((x) => x.slice(1)))
     const wire = wireLayout
-    const r = await engineFor(params, keys).withRing((engine) => { useWire(engine, wire); return engine.quorumProveBatch(k, msg, sig, Buffer.concat(raws.map((x) => x.slice(1))), whichs) })
+    let r
+    if (isKeyLists(keys)) {   // one key list per member (the convention of reringSignatureLists): ONE zk_rings_quorum_prove_batch, the active ring is not touched
+        const { rings, ringOfMember } = quorumRings(keys, k, true)
+        r = await quorumEngine(params, keys, rings).withRings(rings, (engine, ids) => { useWire(engine, wire); return engine.ringsQuorumProveBatch(k, msg, sig, pk, whichs, ringOfMember.map((i) => ids[i])) })
+    } else {
+        checkRingSize(Buffer.isBuffer(keys) ? keys.length / 32 : keys.length, true)
+        r = await engineFor(params, keys).withRing((engine) => { useWire(engine, wire); return engine.quorumProveBatch(k, msg, sig, pk, whichs) })
+    }
     if (r.status[0] === 14 && r.memberStatus.every((s) => s === 0)) throw new Error('two members of the quorum have the same key: no quorum proof exists')
     if (r.status[0] !== 0) throw statusError(r.status[0])
     return new QuorumProof(r.bundles[0])
@@ -1287,9 +1327,16 @@ async function verifyQuorum(params, msgHashes, keys, proof) {
     const q = proof instanceof QuorumProof ? proof : new QuorumProof(proof)
     if (msgHashes.length !== q.k) throw new RangeError('verifyQuorum: one message hash per member')
     const msg = Buffer.concat(msgHashes.map((m) => Buffer.from(m)))
-    checkRingSize(Buffer.isBuffer(keys) ? keys.length / 32 : keys.length, false)
     const wire = isPacked(q.bytes.slice(16)) ? 1 : 0, level = verifyLevel, reps = verifyReps
-    const r = await engineFor(params, keys).withRing((engine) => { useWire(engine, wire); useVerifyLevel(engine, level); useVerifyReps(engine, reps); return engine.quorumVerifyBatch(q.k, msg, [q.bytes]) })
+    const set = (engine) => { useWire(engine, wire); useVerifyLevel(engine, level); useVerifyReps(engine, reps) }
+    let r
+    if (isKeyLists(keys)) {
+        const { rings, ringOfMember } = quorumRings(keys, q.k, false)
+        r = await quorumEngine(params, keys, rings).withRings(rings, (engine, ids) => { set(engine); return engine.ringsQuorumVerifyBatch(q.k, msg, [q.bytes], ringOfMember.map((i) => ids[i])) })
+    } else {
+        checkRingSize(Buffer.isBuffer(keys) ? keys.length / 32 : keys.length, false)
+        r = await engineFor(params, keys).withRing((engine) => { set(engine); return engine.quorumVerifyBatch(q.k, msg, [q.bytes]) })
+    }
     if (r.status[0] !== 0) throw statusError(r.status[0])
     return r.ok[0]
 }

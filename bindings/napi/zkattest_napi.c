@@ -1480,62 +1480,82 @@ static napi_value DistinctVerifyBatch(napi_env env, napi_callback_info info) {
 /* Quorum proofs (include/zkattest.h: zk_quorum_*), on the pool's first context with its ACTIVE ring.
  * (h, k, msg: Qk x 32, sig: Qk x 64, pk: Qk x 64, which: Qk u32 LE, seeds: Qk x 32, pairSeeds: Q k (k - 1) / 2 x 32 -- both FRESH and independent of each other)
  * -> {bundles: the successful quorums' ZKQ1 bundles back to back, off: (Q + 1) u64 LE, status: Q i32 LE, memberStatus: Qk i32 LE} */
-static napi_value QuorumProveBatch(napi_env env, napi_callback_info info) {
-    napi_value argv[8];
-    if (!get_args(env, info, 8, argv)) return NULL;
+static napi_value quorum_prove(napi_env env, napi_callback_info info, int rings) {
+    napi_value argv[9];
+    if (!get_args(env, info, 8 + rings, argv)) return NULL;
     Handle *h = get_handle(env, argv[0], 0);
     uint32_t k = 0;
-    uint8_t *msg, *sig, *pk, *which, *seeds, *pseeds;
-    size_t lm, ls, lp, lw, lsd, lps;
+    uint8_t *msg, *sig, *pk, *which, *seeds, *pseeds, *idb = NULL;
+    size_t lm, ls, lp, lw, lsd, lps, li = 0;
     if (!h || napi_get_value_uint32(env, argv[1], &k) != napi_ok || !get_bytes(env, argv[2], &msg, &lm) || !get_bytes(env, argv[3], &sig, &ls) || !get_bytes(env, argv[4], &pk, &lp) ||
-        !get_bytes(env, argv[5], &which, &lw) || !get_bytes(env, argv[6], &seeds, &lsd) || !get_bytes(env, argv[7], &pseeds, &lps))
+        !get_bytes(env, argv[5], &which, &lw) || (rings && !get_bytes(env, argv[6], &idb, &li)) || !get_bytes(env, argv[6 + rings], &seeds, &lsd) ||
+        !get_bytes(env, argv[7 + rings], &pseeds, &lps))
         return NULL;
     const uint64_t P = zk_quorum_pair_count(k);
     const size_t n = lm / 32, Q = P ? n / k : 0;
-    if (!P || lm % 32 || n != Q * k || ls != 64 * n || lp != 64 * n || lw != 4 * n || lsd != 32 * n || lps != 32 * Q * P) {
-        napi_throw_range_error(env, NULL, "quorumProveBatch: 2 <= k <= 16; per member a 32-byte hash, a 64-byte signature, a 64-byte key, a u32 index and 32 seed bytes; 32 seed bytes per pair");
+    if (!P || lm % 32 || n != Q * k || ls != 64 * n || lp != 64 * n || lw != 4 * n || (rings && li != 4 * n) || lsd != 32 * n || lps != 32 * Q * P) {
+        napi_throw_range_error(env, NULL, rings ? "ringsQuorumProveBatch: 2 <= k <= 16; per member a 32-byte hash, a 64-byte signature, a 64-byte key, a u32 index, a u32 ring id and 32 seed bytes; 32 seed bytes per pair"
+                                                : "quorumProveBatch: 2 <= k <= 16; per member a 32-byte hash, a 64-byte signature, a 64-byte key, a u32 index and 32 seed bytes; 32 seed bytes per pair");
         return NULL;
     }
     zk_ctx *c = zk_pool_ctx(h->pool, 0);
-    const uint64_t cap = zk_quorum_proof_max_size(c, k) * Q;
+    uint32_t *ids = NULL;   /* (a Buffer's bytes need not be aligned) */
+    uint64_t cap = rings ? Q * (16 + 744 * P) : zk_quorum_proof_max_size(c, k) * Q;
+    if (rings) {
+        ids = (uint32_t *)xmalloc(env, 4 * n + 4);
+        if (!ids) return NULL;
+        memcpy(ids, idb, 4 * n);
+        for (size_t m = 0; m < n; m++) cap += zk_ring_proof_max_size(c, ids[m]);   /* the call's exact capacity rule */
+    }
     uint8_t *buf = (uint8_t *)xmalloc(env, 8 * (Q + 1) + 4 * Q + 4 * n + cap + 8);
-    if (!buf) return NULL;
+    if (!buf) {
+        free(ids);
+        return NULL;
+    }
     uint64_t *off = (uint64_t *)buf;
     int32_t *status = (int32_t *)(buf + 8 * (Q + 1)), *mstatus = status + Q;
     uint8_t *out = (uint8_t *)(mstatus + n);
     uint32_t *w = (uint32_t *)xmalloc(env, 4 * n + 4);   /* (a Buffer's bytes need not be aligned) */
     if (!w) {
         free(buf);
+        free(ids);
         return NULL;
     }
     memcpy(w, which, 4 * n);
     zk_rng rng = {ZK_RNG_SEED, seeds, 0}, rng_pairs = {ZK_RNG_SEED, pseeds, 0};
-    zk_status st = zk_quorum_prove_batch(c, Q, k, msg, sig, pk, w, &rng, &rng_pairs, out, cap, off, status, mstatus);
+    zk_status st = rings ? zk_rings_quorum_prove_batch(c, Q, k, msg, sig, pk, w, ids, &rng, &rng_pairs, out, cap, off, status, mstatus)
+                         : zk_quorum_prove_batch(c, Q, k, msg, sig, pk, w, &rng, &rng_pairs, out, cap, off, status, mstatus);
     napi_value v = NULL;
     if (st != ZK_OK) throw_text(env, st, zk_last_error(c));
     else if (napi_create_object(env, &v) == napi_ok)
         set_prop(env, v, "bundles", new_buffer(env, out, off[Q])), set_prop(env, v, "off", new_buffer(env, off, 8 * (Q + 1))), set_prop(env, v, "status", new_buffer(env, status, 4 * Q)),
             set_prop(env, v, "memberStatus", new_buffer(env, mstatus, 4 * n));
     free(w);
+    free(ids);
     free(buf);
     return v;
 }
+static napi_value QuorumProveBatch(napi_env env, napi_callback_info info) { return quorum_prove(env, info, 0); }
+/* zk_rings_quorum_prove_batch: the same with ids: Qk u32 LE (one RESIDENT ring id per member) behind which; the active ring plays no part */
+static napi_value QuorumProveBatchRings(napi_env env, napi_callback_info info) { return quorum_prove(env, info, 1); }
 /* (h, k, msg: Qk x 32, bundles: back to back, off: (Q + 1) u64 LE) -> {ok: Q bytes, status: Q i32 LE, firstBad: Q u32 LE} */
-static napi_value QuorumVerifyBatch(napi_env env, napi_callback_info info) {
-    napi_value argv[5];
-    if (!get_args(env, info, 5, argv)) return NULL;
+static napi_value quorum_verify(napi_env env, napi_callback_info info, int rings) {
+    napi_value argv[6];
+    if (!get_args(env, info, 5 + rings, argv)) return NULL;
     Handle *h = get_handle(env, argv[0], 0);
     uint32_t k = 0;
-    uint8_t *msg, *blob, *ob;
-    size_t lm, lb, lo;
-    if (!h || napi_get_value_uint32(env, argv[1], &k) != napi_ok || !get_bytes(env, argv[2], &msg, &lm) || !get_bytes(env, argv[3], &blob, &lb) || !get_bytes(env, argv[4], &ob, &lo))
+    uint8_t *msg, *blob, *ob, *idb = NULL;
+    size_t lm, lb, lo, li = 0;
+    if (!h || napi_get_value_uint32(env, argv[1], &k) != napi_ok || !get_bytes(env, argv[2], &msg, &lm) || !get_bytes(env, argv[3], &blob, &lb) || !get_bytes(env, argv[4], &ob, &lo) ||
+        (rings && !get_bytes(env, argv[5], &idb, &li)))
         return NULL;
     const size_t Q = lo >= 8 ? lo / 8 - 1 : 0;
-    if (!zk_quorum_pair_count(k) || lo < 8 || lo % 8 || lm != 32 * Q * k) {
-        napi_throw_range_error(env, NULL, "quorumVerifyBatch: 2 <= k <= 16, (Q + 1) u64 offsets and k 32-byte hashes per bundle");
+    if (!zk_quorum_pair_count(k) || lo < 8 || lo % 8 || lm != 32 * Q * k || (rings && li != 4 * Q * k)) {
+        napi_throw_range_error(env, NULL, rings ? "ringsQuorumVerifyBatch: 2 <= k <= 16, (Q + 1) u64 offsets, k 32-byte hashes and k u32 ring ids per bundle"
+                                                : "quorumVerifyBatch: 2 <= k <= 16, (Q + 1) u64 offsets and k 32-byte hashes per bundle");
         return NULL;
     }
-    uint8_t *buf = (uint8_t *)xmalloc(env, 8 * (Q + 1) + 9 * Q + 8);
+    uint8_t *buf = (uint8_t *)xmalloc(env, 8 * (Q + 1) + 9 * Q + 4 * Q * k + 8);
     if (!buf) return NULL;
     uint64_t *off = (uint64_t *)buf;
     memcpy(off, ob, 8 * (Q + 1));
@@ -1547,9 +1567,11 @@ static napi_value QuorumVerifyBatch(napi_env env, napi_callback_info info) {
         }
     int32_t *status = (int32_t *)(buf + 8 * (Q + 1));
     uint32_t *bad = (uint32_t *)(status + Q);
-    uint8_t *ok = (uint8_t *)(bad + Q);
+    uint32_t *ids = bad + Q;   /* (a Buffer's bytes need not be aligned) */
+    uint8_t *ok = (uint8_t *)(ids + Q * k);
+    if (rings) memcpy(ids, idb, 4 * Q * k);
     zk_ctx *c = zk_pool_ctx(h->pool, 0);
-    zk_status st = zk_quorum_verify_batch(c, Q, k, msg, blob, off, NULL, ok, status, bad);
+    zk_status st = rings ? zk_rings_quorum_verify_batch(c, Q, k, msg, blob, off, ids, NULL, ok, status, bad) : zk_quorum_verify_batch(c, Q, k, msg, blob, off, NULL, ok, status, bad);
     napi_value v = NULL;
     if (st != ZK_OK) throw_text(env, st, zk_last_error(c));
     else if (napi_create_object(env, &v) == napi_ok)
@@ -1557,6 +1579,9 @@ static napi_value QuorumVerifyBatch(napi_env env, napi_callback_info info) {
     free(buf);
     return v;
 }
+static napi_value QuorumVerifyBatch(napi_env env, napi_callback_info info) { return quorum_verify(env, info, 0); }
+/* zk_rings_quorum_verify_batch: the same with ids: Qk u32 LE (one RESIDENT ring id per member) behind off */
+static napi_value QuorumVerifyBatchRings(napi_env env, napi_callback_info info) { return quorum_verify(env, info, 1); }
 /* zk_proof_key_commitments: (h, proofs: the B proofs back to back in the context's wire layout, off: (B + 1) u64 LE) -> {coms: B x 72 (zeros where status != 0),
  * status: B i32 LE} */
 static napi_value KeyCommitments(napi_env env, napi_callback_info info) {
@@ -1616,7 +1641,8 @@ static napi_value Init(napi_env env, napi_value exports) {
                {"keyBlinders", KeyBlinders},     {"reringBatch", ReringBatch},     {"reringBatchRings", ReringBatchRings},
                {"linkProveBatch", LinkProveBatch}, {"linkVerifyBatch", LinkVerifyBatch}, {"keyCommitments", KeyCommitments},
                {"distinctProveBatch", DistinctProveBatch}, {"distinctVerifyBatch", DistinctVerifyBatch},
-               {"quorumProveBatch", QuorumProveBatch}, {"quorumVerifyBatch", QuorumVerifyBatch}};
+               {"quorumProveBatch", QuorumProveBatch}, {"quorumVerifyBatch", QuorumVerifyBatch},
+               {"ringsQuorumProveBatch", QuorumProveBatchRings}, {"ringsQuorumVerifyBatch", QuorumVerifyBatchRings}};
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;
         if (napi_create_function(env, fns[i].name, NAPI_AUTO_LENGTH, fns[i].fn, NULL, &f) != napi_ok) return NULL;

@@ -849,6 +849,48 @@ zk_status zk_quorum_verify_batch(zk_ctx *ctx, uint64_t Q, uint32_t k, const uint
 zk_status zk_quorum_verify_batch_device(zk_ctx *ctx, uint64_t Q, uint32_t k, const void *d_msg_hash, const void *d_bundles, const void *d_bundle_off /*u64[Q+1]*/,
                                         const void *d_verifier_seeds, void *d_ok, void *d_per_quorum_status /*i32[Q]*/, void *d_first_bad /*u32[Q] or NULL*/);
 
+/* ---- quorum proofs over several rings: one RESIDENT ring id per member (the sharded registry of zk_prove_batch_rings / zk_verify_batch_rings) -- what the
+ * zk_quorum_* calls above do not provide.  These calls are named zk_rings_quorum_*: the set of zk_quorum_* names stays the six above.  The wire format
+ * is ZKQ1, unchanged: a bundle does not name rings, the verifier is told them as zk_verify_batch_rings is.  Member m = q k + i uses row m of every per-member
+ * array, ring_ids included; which[m] indexes the padded size of ring ring_ids[m].  "k different members" means k different KEYS mod q, whatever ring each is
+ * shown to be in: a key enrolled in two rings and used through both is refused like a key used twice in one ring.
+ * Prover: where quorum q succeeds its bundle is, byte for byte, the 16-byte header, the k proofs zk_prove_batch_rings makes for those members under rng's rows (in
+ *   hardened mode each hashes the digest of its own ring), and the P proofs zk_distinct_prove_batch makes under rng_pairs' rows with key = pk_xy[0:32], com = the
+ *   member's keyXcom and blinder = what zk_prove_key_blinders gives for the member's row -- in both protocol modes and wire layouts, whatever the comb width or
+ *   build.  A quorum's status is the first non-zero one of: its members' zk_prove_batch_rings statuses in member order (ZK_E_ARG for an id that is not resident);
+ *   ZK_E_ARG if two of its members have the same key mod q, in the same ring or in different ones; its pairs' statuses in pair order.  A failed quorum gets an
+ *   empty slot and the bundles behind it close up.  per_member_status (may be NULL) receives the Q k statuses zk_prove_batch_rings would return.
+ * Verifier: the header and inner-header walk is zk_quorum_verify_batch's and needs no ring.  The k members are then verified exactly as zk_verify_batch_rings
+ *   verifies them with those ids (verify level, verify reps, seeds row m; ok 0 / ZK_E_ARG for an id that is not resident), the P pairs exactly as
+ *   zk_distinct_verify_batch does over the members' keyXcoms; ok, per_quorum_status and first_bad are folded by zk_quorum_verify_batch's rules.
+ * When all ring_ids name one ring, both calls return exactly what zk_quorum_prove_batch / zk_quorum_verify_batch return with that ring active.
+ * The active ring is neither read nor changed: a context whose rings are all inactive can make both calls (the "no active ring" refusal above does not apply;
+ *   ZK_E_BUFFER without params does).
+ * Buffer sizes: zk_rings_quorum_proof_max_size(ctx, k, ring_ids) = 16 + the sum of zk_ring_proof_max_size(ctx, ring_ids[i]) over the k members + 744 P, and 0 for
+ *   k outside 2..16 or an id that is not resident.  ZK_E_BUFFER when out_cap < the sum over the quorums of (16 + the members' rings' max sizes + 744 P), a member
+ *   whose id is not resident counting 0: exact, decided from the ids alone before a byte of any output is written (the _device form: one kernel, one read-back).
+ * Call-level rules are zk_quorum_prove_batch's / zk_quorum_verify_batch's: ZK_E_ARG for NULL pointers other than the optional arrays, for k outside 2..16, for
+ *   Q k or Q P >= 2^32 and while streamed jobs are queued; _device pointers (d_ring_ids included) in this context's HBM, 4-byte aligned, else ZK_E_ARG; Q = 0 is
+ *   ZK_OK with out_off[0] = 0.  A window's attestation staging follows the largest ring the call names.  What is witness-derived -- the gathered keys and
+ *   blinders, both RNG fills, the staged inputs, the windows the mixed-ring prover gathers per ring -- is zeroed by zk_ctx_wipe, zk_ctx_destroy and a failed call.
+ *   zk_last_timing reports what the inner calls report (zk_prove_batch_rings reports no families for a window that mixes rings), the "quorum_*" families above
+ *   and "quorum_caps" for the capacity kernel of the _device prover.
+ * Still not provided: submit / wait forms, zk_pool_* forms, JSON, a caller-context binding.  DESIGN.md section 5g'. */
+uint64_t zk_rings_quorum_proof_max_size(const zk_ctx *ctx, uint32_t k, const uint32_t *ring_ids /*k*/);
+zk_status zk_rings_quorum_prove_batch(zk_ctx *ctx, uint64_t Q, uint32_t k, const uint8_t *msg_hash /*Qkx32*/, const uint8_t *sig /*Qkx64*/, const uint8_t *pk_xy /*Qkx64*/,
+                                      const uint32_t *which /*Qk*/, const uint32_t *ring_ids /*Qk*/, const zk_rng *rng /*Qk rows*/, const zk_rng *rng_pairs /*QP rows*/,
+                                      uint8_t *out, uint64_t out_cap, uint64_t *out_off /*Q+1*/, int32_t *per_quorum_status /*Q*/,
+                                      int32_t *per_member_status /*Qk or NULL*/);
+zk_status zk_rings_quorum_prove_batch_device(zk_ctx *ctx, uint64_t Q, uint32_t k, const void *d_msg_hash, const void *d_sig, const void *d_pk_xy, const void *d_which,
+                                             const void *d_ring_ids /*u32[Qk]*/, const zk_rng *rng_device, const zk_rng *rng_pairs_device, void *d_out, uint64_t out_cap,
+                                             void *d_out_off /*u64[Q+1]*/, void *d_per_quorum_status /*i32[Q]*/, void *d_per_member_status /*i32[Qk] or NULL*/);
+zk_status zk_rings_quorum_verify_batch(zk_ctx *ctx, uint64_t Q, uint32_t k, const uint8_t *msg_hash /*Qkx32*/, const uint8_t *bundles, const uint64_t *bundle_off /*Q+1*/,
+                                       const uint32_t *ring_ids /*Qk*/, const uint8_t *verifier_seeds /*Qkx32 or NULL*/, uint8_t *ok /*Q*/,
+                                       int32_t *per_quorum_status /*Q*/, uint32_t *first_bad /*Q or NULL*/);
+zk_status zk_rings_quorum_verify_batch_device(zk_ctx *ctx, uint64_t Q, uint32_t k, const void *d_msg_hash, const void *d_bundles, const void *d_bundle_off /*u64[Q+1]*/,
+                                              const void *d_ring_ids /*u32[Qk]*/, const void *d_verifier_seeds, void *d_ok, void *d_per_quorum_status /*i32[Q]*/,
+                                              void *d_first_bad /*u32[Q] or NULL*/);
+
 /* ---- two (or more) batches in flight on one context.  zk_prove_batch / zk_verify_batch are synchronous: each call pays its own head
  * (no byte of a chunk exists before its stage 1 is over) and its own tail (the copies of the last slices, with nothing left to
  * hide them).  The submit / wait pair splits a call so that the pipeline keeps running ACROSS calls: submit stages the inputs and

@@ -38,6 +38,7 @@ SYMBOLS = [
     'zk_proof_key_commitments', 'zk_proof_key_commitments_device',
     'zk_distinct_proof_size', 'zk_distinct_prove_batch', 'zk_distinct_prove_batch_device', 'zk_distinct_verify_batch', 'zk_distinct_verify_batch_device',
     'zk_quorum_pair_count', 'zk_quorum_proof_max_size', 'zk_quorum_prove_batch', 'zk_quorum_prove_batch_device', 'zk_quorum_verify_batch', 'zk_quorum_verify_batch_device',
+    'zk_rings_quorum_proof_max_size', 'zk_rings_quorum_prove_batch', 'zk_rings_quorum_prove_batch_device', 'zk_rings_quorum_verify_batch', 'zk_rings_quorum_verify_batch_device',
     'zk_test_field_op', 'zk_test_tom_commit', 'zk_test_p256_fixed_mul', 'zk_test_sha256', 'zk_test_rng_draws', 'zk_test_exp_sum',
 ]
 
@@ -197,6 +198,13 @@ def lib():
         L.zk_quorum_prove_batch_device.argtypes = [vp, u64, C.c_uint32, vp, vp, vp, vp, C.POINTER(ZkRng), C.POINTER(ZkRng), vp, u64, vp, vp, vp]
         L.zk_quorum_verify_batch.argtypes = [vp, u64, C.c_uint32, C.c_char_p, C.c_char_p, vp, C.c_char_p, vp, vp, vp]
         L.zk_quorum_verify_batch_device.argtypes = [vp, u64, C.c_uint32, vp, vp, vp, vp, vp, vp, vp]
+        # ... with one resident ring id per member
+        L.zk_rings_quorum_proof_max_size.argtypes = [vp, C.c_uint32, vp]
+        L.zk_rings_quorum_proof_max_size.restype = u64
+        L.zk_rings_quorum_prove_batch.argtypes = [vp, u64, C.c_uint32, C.c_char_p, C.c_char_p, C.c_char_p, vp, vp, C.POINTER(ZkRng), C.POINTER(ZkRng), vp, u64, vp, vp, vp]
+        L.zk_rings_quorum_prove_batch_device.argtypes = [vp, u64, C.c_uint32, vp, vp, vp, vp, vp, C.POINTER(ZkRng), C.POINTER(ZkRng), vp, u64, vp, vp, vp]
+        L.zk_rings_quorum_verify_batch.argtypes = [vp, u64, C.c_uint32, C.c_char_p, C.c_char_p, vp, vp, C.c_char_p, vp, vp, vp]
+        L.zk_rings_quorum_verify_batch_device.argtypes = [vp, u64, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp]
         L.zk_proof_key_commitments.argtypes = [vp, u64, C.c_char_p, vp, vp, vp]
         L.zk_proof_key_commitments_device.argtypes = [vp, u64, vp, vp, vp, vp]
         L.zk_ring_digest.argtypes = [vp, vp]
@@ -1262,6 +1270,66 @@ class Engine:
 
     def quorum_verify_batch_device(self, Q, k, d_msg, d_bundles, d_bundle_off, d_vseeds, d_ok, d_status, d_first_bad=None):
         self._chk(self.L.zk_quorum_verify_batch_device(self.h, Q, k, d_msg, d_bundles, d_bundle_off, d_vseeds, d_ok, d_status, d_first_bad))
+
+    # ---- quorum proofs over several rings (zk_rings_quorum_*): one resident ring id per member; the wire format is ZKQ1 unchanged
+    def quorum_proof_max_size_rings(self, k, ring_ids):
+        """zk_rings_quorum_proof_max_size: upper bound of one bundle's size when member i proves over ring ring_ids[i] (0 for a k outside 2..16 or an id that is
+        not resident)"""
+        if len(ring_ids) != k:
+            raise ValueError('one ring id per member')
+        return int(self.L.zk_rings_quorum_proof_max_size(self.h, k, (C.c_uint32 * max(k, 1))(*ring_ids)))
+
+    def quorum_prove_batch_rings(self, k, msg, sig, pk, which, ring_ids, seeds=None, pair_seeds=None, streams=None, stream_blocks=0, pair_streams=None,
+                                 pair_stream_blocks=0, cap=None, want_member_status=True):
+        """zk_rings_quorum_prove_batch: quorum_prove_batch with member m proving over resident ring ring_ids[m] (which[m] indexes that ring); the active ring is
+        neither read nor changed.  Returns (bundles, quorum statuses, member statuses) like quorum_prove_batch."""
+        n = len(which)
+        if k <= 0 or n % k or len(ring_ids) != n:
+            raise ValueError('k members per quorum, one ring id per member')
+        Q, P = n // k, k * (k - 1) // 2
+        if seeds is None and streams is None:
+            seeds = os.urandom(32 * n)
+        if pair_seeds is None and pair_streams is None:
+            pair_seeds = os.urandom(32 * Q * P)
+        rng, _keep = self._rng(n, seeds, streams, stream_blocks)
+        rng_pairs, _keep2 = self._rng(Q * P, pair_seeds, pair_streams, pair_stream_blocks)
+        sizes = {r: self.ring_proof_max_size(r) for r in set(ring_ids)}
+        size = max(sum(sizes[r] for r in ring_ids) + Q * (16 + 744 * P), 16)   # the exact capacity rule: an id that is not resident counts 0
+        out = C.create_string_buffer(size)
+        off = (C.c_uint64 * (Q + 1))()
+        st = (C.c_int32 * max(Q, 1))()
+        mst = (C.c_int32 * max(n, 1))()
+        w = (C.c_uint32 * max(n, 1))(*which)
+        ids = (C.c_uint32 * max(n, 1))(*ring_ids)
+        self._chk(self.L.zk_rings_quorum_prove_batch(self.h, Q, k, bytes(msg), bytes(sig), bytes(pk), w, ids, C.byref(rng), C.byref(rng_pairs), out,
+                                                     size if cap is None else cap, off, st, mst if want_member_status else None))
+        raw = out.raw
+        return [raw[off[q]:off[q + 1]] if st[q] == 0 else None for q in range(Q)], list(st)[:Q], list(mst)[:n] if want_member_status else None
+
+    def quorum_prove_batch_rings_device(self, Q, k, d_msg, d_sig, d_pk, d_which, d_ids, d_rng, d_rng_pairs, d_out, out_cap, d_out_off, d_status, d_member_status=None, mode=0,
+                                        stride_blocks=0, pair_mode=0, pair_stride_blocks=0):
+        rng, rng_pairs = ZkRng(mode, d_rng, stride_blocks), ZkRng(pair_mode, d_rng_pairs, pair_stride_blocks)
+        self._chk(self.L.zk_rings_quorum_prove_batch_device(self.h, Q, k, d_msg, d_sig, d_pk, d_which, d_ids, C.byref(rng), C.byref(rng_pairs), d_out, out_cap, d_out_off,
+                                                            d_status, d_member_status))
+
+    def quorum_verify_batch_rings(self, k, msg, bundles, ring_ids, verifier_seeds=None, want_first_bad=True):
+        """zk_rings_quorum_verify_batch: quorum_verify_batch with member m verified over resident ring ring_ids[m].  Returns (ok, statuses, first_bad)."""
+        Q = len(bundles)
+        if len(ring_ids) != Q * k:
+            raise ValueError('one ring id per member')
+        off = (C.c_uint64 * (Q + 1))()
+        for q, b in enumerate(bundles):
+            off[q + 1] = off[q] + len(b)
+        ok = (C.c_uint8 * max(Q, 1))()
+        st = (C.c_int32 * max(Q, 1))()
+        bad = (C.c_uint32 * max(Q, 1))()
+        ids = (C.c_uint32 * max(Q * k, 1))(*ring_ids)
+        self._chk(self.L.zk_rings_quorum_verify_batch(self.h, Q, k, bytes(msg), b''.join(bundles) if Q else bytes(16), off, ids,
+                                                      None if verifier_seeds is None else bytes(verifier_seeds), ok, st, bad if want_first_bad else None))
+        return list(ok)[:Q], list(st)[:Q], list(bad)[:Q] if want_first_bad else None
+
+    def quorum_verify_batch_rings_device(self, Q, k, d_msg, d_bundles, d_bundle_off, d_ids, d_vseeds, d_ok, d_status, d_first_bad=None):
+        self._chk(self.L.zk_rings_quorum_verify_batch_device(self.h, Q, k, d_msg, d_bundles, d_bundle_off, d_ids, d_vseeds, d_ok, d_status, d_first_bad))
 
     def synth_params(self, seed):
         a, b, c = C.create_string_buffer(64), C.create_string_buffer(72), C.create_string_buffer(72)

@@ -1625,6 +1625,11 @@ extern "C" zk_status zk_prove_batch_rings_device(zk_ctx* c, uint64_t B, const vo
     return prove_rings_device(c, B, (const uint8_t*)d_msg, (const uint8_t*)d_sig, (const uint8_t*)d_pk, (const uint32_t*)d_which, (const uint32_t*)d_ids, rng->mode, rng->data,
                               rng->stride_blocks, (uint8_t*)d_out, out_cap, (uint64_t*)d_out_off, (int32_t*)d_status, nullptr);
 }
+// zk_prove_batch_rings_device's pipeline for api_quorum.hip (quorum.h)
+zk_status zkq_prove_members_rings(zk_ctx* c, uint64_t B, const uint8_t* d_msg, const uint8_t* d_sig, const uint8_t* d_pk, const uint32_t* d_which, const uint32_t* d_ids,
+                                  const zk_rng& rng, uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_off, int32_t* d_status) {
+    return prove_rings_device(c, B, d_msg, d_sig, d_pk, d_which, d_ids, rng.mode, rng.data, rng.stride_blocks, d_out, out_cap, d_out_off, d_status, nullptr);
+}
 // Host pointers: the ids are classed here.  All of one resident ring: zk_prove_batch with that ring bound (staging, page-locked DMA, slices: everything as
 // with that ring active).  Anything else: the inputs cross to HBM and take the device path; the proofs are put in order in the context's staging copy of
 // `out` (or in `out` itself where it lies in HBM) and cross the link segment by segment (page-locked `out`) or in one copy at the end.

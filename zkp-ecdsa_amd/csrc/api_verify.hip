@@ -1092,6 +1092,11 @@ zk_status zkq_verify_members(zk_ctx* c, uint64_t B, const uint8_t* d_msg, const 
     if (c->verify_level == ZK_VERIFY_LEVEL_PER_PROOF) return verify_per_proof(c, B, d_msg, d_proofs, d_off, d_vseeds, d_ok, d_status, true);
     return verify_device(c, B, d_msg, d_proofs, d_off, d_vseeds, d_ok, d_status, nullptr, nullptr, true);
 }
+// ... and zk_verify_batch_rings_device's
+zk_status zkq_verify_members_rings(zk_ctx* c, uint64_t B, const uint8_t* d_msg, const uint8_t* d_proofs, const uint64_t* d_off, const uint32_t* d_ids, const uint8_t* d_vseeds,
+                                   uint8_t* d_ok, int32_t* d_status) {
+    return verify_rings_device(c, B, d_msg, d_proofs, d_off, d_ids, d_vseeds, d_ok, d_status, true);
+}
 extern "C" zk_status zk_verify_batch(zk_ctx* c, uint64_t B, const uint8_t* msg, const uint8_t* proofs, const uint64_t* off, const uint8_t* vseeds, uint8_t* ok,
                                      int32_t* status) {
     if (!c || (B && (!msg || !proofs || !off || !ok || !status))) return ZK_E_ARG;

@@ -54,7 +54,8 @@ enum GrowPolicy {
     X(kb, GROW_ONCE, true)        /* zk_prove_key_blinders: a chunk's rejection lists (derived from the seeds) and the call's exhaustion flag */ \
     X(lk, GROW_SHED, true)        /* link proofs (api_link.hip): the lanes' arenas -- the staged key and blinders, the nonces k, s1, s2, the RNG fills, the challenge's message */ \
     X(dk, GROW_SHED, true)        /* distinct-key proofs (api_distinct.hip): the lanes' arenas -- the staged keys and blinders, d, 1 / d, r_w, the nonces, the RNG fills, the challenge's message */ \
-    X(qs, GROW_SHED, true)        /* quorum proofs (api_quorum.hip): a window's staging -- the gathered keys, keyXcoms and blinders of its pairs, its attestations and distinct-key proofs until they are in place; verifier: the walked offsets, the members' and pairs' bytes and verdicts */
+    X(qs, GROW_SHED, true)        /* quorum proofs (api_quorum.hip): a window's staging -- the gathered keys, keyXcoms and blinders of its pairs, its attestations and distinct-key proofs until they are in place; verifier: the walked offsets, the members' and pairs' bytes and verdicts */ \
+    X(qc, GROW_SLACK, false)      /* ... their `_rings` forms: every quorum's capacity, the call's total and the set of rings its ids name (from ring ids: public) */
 enum BufId {
 #define X(name, policy, witness) B_##name,
     ZK_CTX_BUFS(X)

@@ -68,6 +68,17 @@ __global__ void __launch_bounds__(256) k_q_place(QuorumShape W, const uint64_t* 
     uint32_t* o = (uint32_t*)(out + at);
     o[0] = hw[0], o[1] = hw[1], o[2] = hw[2], o[3] = hw[3];
 }
+// The `_rings` forms.  lane q: the capacity of quorum q's slot from its k ring ids (quorum_plan.h: zkq_capacity_rings; `R` lies in the kernel's arguments); a
+// wave adds its lanes' capacities and ors their ring sets, and its first lane adds the wave's into the call's two words.
+__global__ void __launch_bounds__(256) k_q_caps(uint32_t Q, uint32_t k, const uint32_t* __restrict__ ids, QuorumRings R, uint64_t* __restrict__ caps,
+                                                unsigned long long* __restrict__ total) {
+    const uint32_t q = gtid();
+    unsigned long long cap = 0;
+    uint32_t used = 0;
+    if (q < Q) caps[q] = cap = zkq_capacity_rings(R, k, ids + (size_t)q * k, &used);
+    for (int d = 32; d; d >>= 1) cap += __shfl_down(cap, d), used |= __shfl_down(used, d);
+    if ((threadIdx.x & 63) == 0 && (cap | used)) atomicAdd(total, cap), atomicOr(total + 1, (unsigned long long)used);
+}
 
 // ------------------------------------------------------------------ verifier
 // lane q: walk[q (k + 1) ..] receives the walk's offsets; a refused bundle's members and pairs get empty records (no byte of it is moved)
@@ -139,4 +150,7 @@ void launch_q_gather_verify(hipStream_t s, const QuorumShape& W, const uint8_t* 
 void launch_q_verdict(hipStream_t s, const QuorumShape& W, const uint8_t* good, const uint8_t* m_ok, const int32_t* m_st, const uint8_t* p_ok, const int32_t* p_st, uint8_t* ok,
                       int32_t* status, uint32_t* first_bad) {
     if (W.nq) hipLaunchKernelGGL(k_q_verdict, q_grid(W.nq), dim3(256), 0, s, W, good, m_ok, m_st, p_ok, p_st, ok, status, first_bad);
+}
+void launch_q_caps(hipStream_t s, uint32_t Q, uint32_t k, const uint32_t* ring_ids, const QuorumRings& R, uint64_t* caps, uint64_t* total) {
+    if (Q) hipLaunchKernelGGL(k_q_caps, q_grid(Q), dim3(256), 0, s, Q, k, ring_ids, R, caps, (unsigned long long*)total);
 }

@@ -26,6 +26,9 @@ void launch_q_gather_verify(hipStream_t s, const QuorumShape& W, const uint8_t* 
 // One lane per quorum folds its k + P (ok, status) pairs into ok, status and first_bad (nullptr: not wanted)
 void launch_q_verdict(hipStream_t s, const QuorumShape& W, const uint8_t* good, const uint8_t* m_ok, const int32_t* m_st, const uint8_t* p_ok, const int32_t* p_st, uint8_t* ok,
                       int32_t* status, uint32_t* first_bad);
+// The `_rings` forms.  One lane per quorum: caps[q] = its slot's capacity by quorum_plan.h's rule; total[0] += the capacities, total[1] |= the entries of `R` the
+// ids name (the caller zeroes both words).
+void launch_q_caps(hipStream_t s, uint32_t Q, uint32_t k, const uint32_t* ring_ids, const QuorumRings& R, uint64_t* caps, uint64_t* total /*2*/);
 
 #if !defined(ZK_QUORUM_KERNELS_ONLY)
 #include "ctx.h"
@@ -34,6 +37,10 @@ zk_status zkq_prove_members(zk_ctx* c, uint64_t B, const uint8_t* d_msg, const u
                             uint64_t out_cap, uint64_t* d_out_off, int32_t* d_status);                                                                  // api.hip: zk_prove_batch_device
 zk_status zkq_verify_members(zk_ctx* c, uint64_t B, const uint8_t* d_msg, const uint8_t* d_proofs, const uint64_t* d_off, const uint8_t* d_vseeds, uint8_t* d_ok,
                              int32_t* d_status);                                                                                                        // api_verify.hip: zk_verify_batch_device
+zk_status zkq_prove_members_rings(zk_ctx* c, uint64_t B, const uint8_t* d_msg, const uint8_t* d_sig, const uint8_t* d_pk, const uint32_t* d_which, const uint32_t* d_ids,
+                                  const zk_rng& rng, uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_off, int32_t* d_status);                         // api.hip: zk_prove_batch_rings_device
+zk_status zkq_verify_members_rings(zk_ctx* c, uint64_t B, const uint8_t* d_msg, const uint8_t* d_proofs, const uint64_t* d_off, const uint32_t* d_ids, const uint8_t* d_vseeds,
+                                   uint8_t* d_ok, int32_t* d_status);                                                                                   // api_verify.hip: zk_verify_batch_rings_device
 zk_status zkq_key_blinders(zk_ctx* c, uint64_t B, const zk_rng& rng, uint8_t* d_out);                                                                   // api_rering.hip: zk_prove_key_blinders_device
 zk_status zkq_distinct_prove(zk_ctx* c, uint64_t B, const uint8_t* key1, const uint8_t* com1, const uint8_t* blinder1, const uint8_t* key2, const uint8_t* com2,
                              const uint8_t* blinder2, const zk_rng& rng, uint8_t* out, int32_t* status);                                                // api_distinct.hip: zk_distinct_prove_batch_device

@@ -23,6 +23,39 @@ ZK_HD static inline void zkq_unrank(uint32_t k, uint32_t p, uint32_t& i, uint32_
 ZK_HD static inline uint64_t zkq_max_size(uint32_t k, uint64_t proof_max) {
     return zkq_k_ok(k) && proof_max ? ZKQ1_HDR + (uint64_t)k * proof_max + (uint64_t)zkq_pairs(k) * ZKQ_PAIR_BYTES : 0;
 }
+// The `_rings` forms (one resident ring id per member): what a call knows of the context's rings, and the capacity a quorum's slot needs.  At most ZKQ_RINGS
+// entries (ZK_MAX_RINGS); an entry with resident = 0, like an id that has no entry, names no ring.
+#define ZKQ_RINGS 16u
+struct QuorumRings {   // (a kernel argument)
+    uint32_t count;
+    uint32_t id[ZKQ_RINGS], resident[ZKQ_RINGS], proof_max[ZKQ_RINGS];   // proof_max: zk_ring_proof_max_size of the ring
+};
+// the entry of `id`, ZKQ_RINGS where it names no resident ring
+ZK_HD static inline uint32_t zkq_ring_entry(const QuorumRings& R, uint32_t id) {
+    for (uint32_t r = 0; r < R.count && r < ZKQ_RINGS; r++)
+        if (R.resident[r] && R.id[r] == id) return r;
+    return ZKQ_RINGS;
+}
+// The slot of a quorum whose member i proves over ring ids[i]: the header, every member's ring's largest proof (0 for an id that is not resident), the pairs'
+// proofs.  0 for a k outside 2..16.  `used` (may be NULL) collects the entries the ids name, as a bit set.  The sum cannot wrap: 16 proofs of < 2^32 bytes.
+ZK_HD static inline uint64_t zkq_capacity_rings(const QuorumRings& R, uint32_t k, const uint32_t* ids, uint32_t* used) {
+    if (!zkq_k_ok(k)) return 0;
+    uint64_t cap = ZKQ1_HDR + (uint64_t)zkq_pairs(k) * ZKQ_PAIR_BYTES;
+    for (uint32_t i = 0; i < k; i++) {
+        const uint32_t r = zkq_ring_entry(R, ids[i]);
+        if (r == ZKQ_RINGS) continue;
+        cap += R.proof_max[r];
+        if (used) *used |= 1u << r;
+    }
+    return cap;
+}
+// zk_rings_quorum_proof_max_size: the same sum, but 0 as soon as one id is not resident
+ZK_HD static inline uint64_t zkq_max_size_rings(const QuorumRings& R, uint32_t k, const uint32_t* ids) {
+    if (!zkq_k_ok(k)) return 0;
+    for (uint32_t i = 0; i < k; i++)
+        if (zkq_ring_entry(R, ids[i]) == ZKQ_RINGS || !R.proof_max[zkq_ring_entry(R, ids[i])]) return 0;
+    return zkq_capacity_rings(R, k, ids, nullptr);
+}
 // a bundle whose k attestations take att_bytes
 ZK_HD static inline uint64_t zkq_size(uint32_t k, uint64_t att_bytes) { return ZKQ1_HDR + att_bytes + (uint64_t)zkq_pairs(k) * ZKQ_PAIR_BYTES; }
 ZK_HD static inline void zkq_header(uint32_t hw[4], uint32_t total, uint32_t k) {   // the 16 header bytes as four words in memory order
