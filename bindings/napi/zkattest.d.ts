@@ -121,6 +121,29 @@ export function proveSameKey(params: PedersenParams | SystemParametersList, key:
 export function verifySameKey(params: PedersenParams | SystemParametersList, comA: LinkCom, comB: LinkCom, link: LinkProof | Buffer): Promise<boolean>
 export function proveSameKeys(params: PedersenParams | SystemParametersList, keys: LinkScalar[], comsA: LinkCom[], blindersA: LinkScalar[], comsB: LinkCom[], blindersB: LinkScalar[]): Promise<LinkProof[]>
 export function verifySameKeys(params: PedersenParams | SystemParametersList, comsA: LinkCom[], comsB: LinkCom[], links: (LinkProof | Buffer)[]): Promise<boolean[]>
+/** Escrow tags ("ZKT1", zk_ctx_set_auditor / zk_escrow_*): beside com = key g + blinder h, the key encrypted (exponential ElGamal) to the key A = a g of a designated
+ *  auditor with a proof that it is com's key.  Anyone verifies a tag; who holds a opens it to the ring member's index.  A tag is bound to com and A, not to a
+ *  message or a ring; opening does NOT verify; the engine draws fresh seeds; anyone who knows a can open every tag made for A. */
+export class EscrowTag {
+    constructor(bytes: Buffer)
+    readonly bytes: Buffer
+    readonly E1: Point
+    readonly E2: Point
+    readonly T1: Point
+    readonly T2: Point
+    readonly T3: Point
+    readonly t_x: Scalar
+    readonly t_r: Scalar
+    readonly t_rho: Scalar
+    eq(o: EscrowTag): boolean
+}
+export function escrowAuditorKey(params: PedersenParams | SystemParametersList, secret: LinkScalar): Promise<Point>
+export function proveEscrowTag(params: PedersenParams | SystemParametersList, auditor: Point | Buffer, key: LinkScalar, com: LinkCom, blinder: LinkScalar): Promise<EscrowTag>
+export function verifyEscrowTag(params: PedersenParams | SystemParametersList, auditor: Point | Buffer, com: LinkCom, tag: EscrowTag | Buffer): Promise<boolean>
+export function proveEscrowTags(params: PedersenParams | SystemParametersList, auditor: Point | Buffer, keys: LinkScalar[], coms: LinkCom[], blinders: LinkScalar[]): Promise<EscrowTag[]>
+export function verifyEscrowTags(params: PedersenParams | SystemParametersList, auditor: Point | Buffer, coms: LinkCom[], tags: (EscrowTag | Buffer)[]): Promise<boolean[]>
+/** the auditor's call: per tag the index in `keys` of the ring member whose key it carries (the lowest where a key occurs twice), null for nobody */
+export function openEscrowTags(params: PedersenParams | SystemParametersList, secret: LinkScalar, keys: bigint[] | Buffer, tags: (EscrowTag | Buffer)[]): Promise<(number | null)[]>
 /** Distinct-key proofs ("ZKD1", zk_distinct_*): comA = keyA g + blinderA h and comB = keyB g + blinderB h hide DIFFERENT keys: one MultProof (src/commit/mult.ts)
  *  for (keyA - keyB) * w = 1.  A proof verifies for (comA, comB) in this order only; equal keys throw '... hide the same key ...'; the engine draws fresh seeds. */
 export class DistinctProof {
@@ -226,6 +249,15 @@ export class Engine {
     ringsQuorumVerifyBatch(k: number, msg: Buffer, bundles: Buffer[], ringIds: number[]): { ok: boolean[]; status: Int32Array; firstBad: Uint32Array }
     /** zk_link_verify_batch */
     linkVerifyBatch(com1: Buffer[], com2: Buffer[], proofs: Buffer[]): { ok: boolean[]; status: Int32Array }
+    /** zk_ctx_set_auditor: the auditor's key as a 72-byte Tom-256 point, for the escrow calls; setParams drops it */
+    setAuditor(key72: Uint8Array): void
+    /** zk_escrow_keygen: A = a g (72 bytes) for a 32-byte big-endian secret */
+    escrowKeygen(secret32: Uint8Array): Buffer
+    /** zk_escrow_prove_batch: per entry a 32-byte key, a 72-byte commitment and its 32-byte blinder; seeds must be fresh (default: crypto.randomBytes).  status 16: key and blinder do not open the commitment */
+    escrowProveBatch(keys: Buffer[], com: Buffer[], blinder: Buffer[], seeds?: Buffer): { tags: (Buffer | null)[]; status: Int32Array }
+    escrowVerifyBatch(com: Buffer[], tags: Buffer[]): { ok: boolean[]; status: Int32Array }
+    /** zk_escrow_open_batch against the ACTIVE ring: index 0xffffffff = nobody; it does not verify */
+    escrowOpenBatch(secret32: Uint8Array, tags: Buffer[]): { index: number[]; status: Int32Array }
     /** zk_proof_key_commitments: keyXcom of proofs in the engine's wire layout, 72 bytes each; null where the status is not 0 */
     keyCommitments(proofs: Buffer[]): { coms: (Buffer | null)[]; status: Int32Array }
     keysToInts(pkxy: Buffer): { keys: Buffer; status: Buffer }

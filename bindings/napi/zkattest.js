@@ -322,7 +322,7 @@ class Engine {
     }
     wipe() { native.setOption(this.h, 'wipe', 0) }   // zk_ctx_wipe on every device: prover workspaces and staged inputs zeroed (also done by close() and after a failed prove)
     // params: { nistH: 64 B, tomG: 72 B, tomH: 72 B, secLevel } -- SystemParametersList as affine big-endian coordinates
-    setParams(p) { native.setParams(this.h, p.nistH, p.tomG, p.tomH, p.secLevel || 80); this.params = p }
+    setParams(p) { native.setParams(this.h, p.nistH, p.tomG, p.tomH, p.secLevel || 80); this.params = p; this.auditor = null }   // (zk_ctx_set_params drops the auditor's key)
     setRing(keys) { return native.setRing(this.h, Buffer.isBuffer(keys) ? keys : Buffer.concat(keys.map(be32))) }
     // resident rings (include/zkattest.h zk_ctx_add_ring): built once, switched by id without a rebuild
     addRing(keys) { return native.addRing(this.h, Buffer.isBuffer(keys) ? keys : Buffer.concat(keys.map(be32))) }   // -> ring id (not made active)
@@ -462,6 +462,26 @@ class Engine {
     linkVerifyBatch(com1, com2, proofs) {   // -> { ok: boolean[], status: Int32Array }
         const r = native.linkVerifyBatch(this.h, Buffer.concat(com1), Buffer.concat(com2), Buffer.concat(proofs))
         return { ok: Array.from(r.ok, (v) => v === 1), status: i32(r.status) }
+    }
+    // escrow tags (zk_ctx_set_auditor, zk_escrow_*): "ZKT1", 472 bytes -- ElGamal of keys[i] under the auditor's key with a proof that com[i] opens to it under
+    // blinder[i].  setAuditor: the key A as a 72-byte Tom-256 point, again after every setParams; escrowKeygen: A = a g for a 32-byte secret.  Arrays of Buffers
+    // -> { tags: Buffer | null per entry, status: Int32Array }.  seeds must be FRESH: never the ones the commitment's proof was made with (default: crypto.randomBytes)
+    setAuditor(key72) { native.setAuditor(this.h, Buffer.from(key72)); this.auditor = Buffer.from(key72).toString('hex') }
+    escrowKeygen(secret32) { return native.escrowKeygen(this.h, Buffer.from(secret32)) }
+    escrowProveBatch(keys, com, blinder, seeds) {
+        const B = keys.length, cat = (a) => Buffer.concat(a.map((v) => Buffer.from(v)))
+        const r = native.escrowProveBatch(this.h, cat(keys), cat(com), cat(blinder), seeds || crypto.randomBytes(32 * B))
+        const st = i32(r.status)
+        return { tags: Array.from(st, (s, i) => (s === 0 ? r.tags.slice(472 * i, 472 * i + 472) : null)), status: st }
+    }
+    escrowVerifyBatch(com, tags) {   // -> { ok: boolean[], status: Int32Array }
+        const r = native.escrowVerifyBatch(this.h, Buffer.concat(com), Buffer.concat(tags))
+        return { ok: Array.from(r.ok, (v) => v === 1), status: i32(r.status) }
+    }
+    // the auditor's call against the ACTIVE ring -> { index: number[] (0xffffffff: nobody), status: Int32Array }.  It does not verify.
+    escrowOpenBatch(secret32, tags) {
+        const r = native.escrowOpenBatch(this.h, Buffer.from(secret32), Buffer.concat(tags))
+        return { index: Array.from(tags, (_, i) => r.index.readUInt32LE(4 * i)), status: i32(r.status) }
     }
     // distinct-key proofs (zk_distinct_*): "ZKD1", 744 bytes -- com1[i] opens to key1[i] under blinder1[i], com2[i] to key2[i] under blinder2[i], and the keys differ;
     // the proof verifies for (com1, com2) in this order only.  Arrays of Buffers -> { proofs: Buffer | null per entry, status: Int32Array } (status 14: equal keys).
@@ -1191,6 +1211,71 @@ async function keyCommitments(proofs, params = lastParams) {
     return out
 }
 
+// ---------------------------------------------------------------- escrow tags: an auditor can open which ring member attested (include/zkattest.h: zk_escrow_*)
+// An EscrowTag keeps the engine's ZKT1 bytes and materialises its members (E1, E2, T1, T2, T3: Points; t_x, t_r, t_rho: Scalars).
+class EscrowTag {
+    constructor(bytes) {
+        if (!(Buffer.isBuffer(bytes) && bytes.length === 472 && bytes.slice(0, 4).toString('latin1') === 'ZKT1' && bytes.readUInt32BE(4) === 472 && bytes.readUInt32BE(8) === 0 &&
+            bytes.readUInt32BE(12) === 0)) throw new Error('error deserializing EscrowTag')
+        this.bytes = bytes
+    }
+    _pt(o) { return new Point(tomEdwards256, fromBE(this.bytes.slice(o, o + 36)), fromBE(this.bytes.slice(o + 36, o + 72))) }
+    _sc(o) { return new Scalar(tomEdwards256, fromBE(this.bytes.slice(o, o + 32))) }
+    get E1() { return this._pt(16) }
+    get E2() { return this._pt(88) }
+    get T1() { return this._pt(160) }
+    get T2() { return this._pt(232) }
+    get T3() { return this._pt(304) }
+    get t_x() { return this._sc(376) }
+    get t_r() { return this._sc(408) }
+    get t_rho() { return this._sc(440) }
+    eq(o) { return o instanceof EscrowTag && this.bytes.equals(o.bytes) }
+}
+// inside a queued unit of the engine: the auditor's key of this call (a Point or 72 bytes) is the one the engine holds -- its comb table is built once per key
+function useAuditor(engine, auditor) {
+    const key = comBytes(auditor)
+    if (engine.auditor !== key.toString('hex')) engine.setAuditor(key)
+}
+// escrowAuditorKey(params, secret): the auditor's public key A = a g (a Point) for a secret a (a bigint, a Scalar or 32 bytes).  Keep a where the court order is kept:
+// anyone who knows it opens every tag made for A.
+async function escrowAuditorKey(params, secret) {
+    const k = await engineFor(paramsOf(params), null).run((engine) => engine.escrowKeygen(scalarBytes(secret)))
+    return new Point(tomEdwards256, fromBE(k.slice(0, 36)), fromBE(k.slice(36)))
+}
+// proveEscrowTag(params, auditor, key, com, blinder): com = key g + blinder h (a Point, a Commitment or 72 bytes; keyXcom of an attestation with keyBlinders' blinder,
+// or a membership commitment) -> EscrowTag: the key encrypted to the auditor's key, tied to com.  The engine draws fresh seeds.  The tag is bound to com and the
+// auditor's key, not to a message or a ring.  Throws 'error deserializing' for a commitment off the curve and "... do not open ..." when key and blinder do not open com.
+async function proveEscrowTag(params, auditor, key, com, blinder) {
+    return (await proveEscrowTags(params, auditor, [key], [com], [blinder]))[0]
+}
+async function verifyEscrowTag(params, auditor, com, tag) {   // -> boolean; what does not deserialise throws
+    return (await verifyEscrowTags(params, auditor, [com], [tag]))[0]
+}
+async function proveEscrowTags(params, auditor, keys, coms, blinders) {
+    const B = keys.length
+    if (coms.length !== B || blinders.length !== B) throw new RangeError('proveEscrowTags: one key, one commitment and one blinder per entry')
+    if (!B) return []
+    const r = await engineFor(paramsOf(params), null).run((engine) => { useAuditor(engine, auditor); return engine.escrowProveBatch(keys.map(scalarBytes), coms.map(comBytes), blinders.map(scalarBytes)) })
+    return r.tags.map((t, i) => { if (r.status[i] !== 0) throw statusError(r.status[i]); return new EscrowTag(t) })
+}
+async function verifyEscrowTags(params, auditor, coms, tags) {
+    const B = tags.length
+    if (coms.length !== B) throw new RangeError('verifyEscrowTags: one commitment per tag')
+    if (!B) return []
+    const raw = tags.map((t) => (t instanceof EscrowTag ? t.bytes : new EscrowTag(t).bytes))
+    const r = await engineFor(paramsOf(params), null).run((engine) => { useAuditor(engine, auditor); return engine.escrowVerifyBatch(coms.map(comBytes), raw) })
+    r.status.forEach((st) => { if (st !== 0) throw statusError(st) })
+    return r.ok
+}
+// openEscrowTags(params, secret, keys, tags): the auditor's call -> per tag the index in `keys` of the ring member whose key it carries (the lowest, where a key
+// occurs twice) or null for nobody.  It does NOT verify: call verifyEscrowTag (and the attestation's verifier) first.  Throws when the secret is 0 mod q.
+async function openEscrowTags(params, secret, keys, tags) {
+    if (!tags.length) return []
+    const raw = tags.map((t) => (t instanceof EscrowTag ? t.bytes : new EscrowTag(t).bytes)), a = scalarBytes(secret)
+    const r = await engineFor(paramsOf(params), keys).withRing((engine) => { useAuditor(engine, engine.escrowKeygen(a)); return engine.escrowOpenBatch(a, raw) })
+    return r.index.map((w, i) => { if (r.status[i] !== 0) throw statusError(r.status[i]); return w === 0xffffffff ? null : w })
+}
+
 // ---------------------------------------------------------------- distinct-key proofs: two key commitments hide different keys (src/commit/mult.ts:26-175)
 // A DistinctProof keeps the engine's ZKD1 bytes (include/zkattest.h) and materialises C_w and the reference's MultProof members (six Points, seven Scalars).
 class DistinctProof {
@@ -1341,6 +1426,6 @@ async function verifyQuorum(params, msgHashes, keys, proof) {
     return r.ok[0]
 }
 
-module.exports = { proveQuorum, verifyQuorum, QuorumProof, proveDifferentKeys, verifyDifferentKeys, proveDifferentKeysBatch, verifyDifferentKeysBatch, distinctPairs, DistinctProof, proveSameKey, verifySameKey, proveSameKeys, verifySameKeys, keyCommitment, keyCommitments, LinkProof, reringSignatureLists, keyBlinders, proveMembership, verifyMembership, proveMemberships, verifyMemberships, proveMembershipLists, verifyMembershipLists, GKProof, Commitment, commit, screenSignatureLists, findKey, SCREEN, WHICH_NONE, recoverSignatureLists, recoverKey, RECOVER, verifySignatureLists, proveSignatureLists, _ringGenerations, setVerifyLevel, getVerifyLevel, setVerifyReps, getVerifyReps, generateParamsList, generateParamsListHardened, keyToInt, proveSignatureList, verifySignatureList, proveSignatureListBatch, verifySignatureListBatch,
+module.exports = { proveEscrowTag, verifyEscrowTag, proveEscrowTags, verifyEscrowTags, openEscrowTags, escrowAuditorKey, EscrowTag, proveQuorum, verifyQuorum, QuorumProof, proveDifferentKeys, verifyDifferentKeys, proveDifferentKeysBatch, verifyDifferentKeysBatch, distinctPairs, DistinctProof, proveSameKey, verifySameKey, proveSameKeys, verifySameKeys, keyCommitment, keyCommitments, LinkProof, reringSignatureLists, keyBlinders, proveMembership, verifyMembership, proveMemberships, verifyMemberships, proveMembershipLists, verifyMembershipLists, GKProof, Commitment, commit, screenSignatureLists, findKey, SCREEN, WHICH_NONE, recoverSignatureLists, recoverKey, RECOVER, verifySignatureLists, proveSignatureLists, _ringGenerations, setVerifyLevel, getVerifyLevel, setVerifyReps, getVerifyReps, generateParamsList, generateParamsListHardened, keyToInt, proveSignatureList, verifySignatureList, proveSignatureListBatch, verifySignatureListBatch,
     writeJson, readJson, writeJsonBatch, readJsonBatch, SignatureProofList, SystemParametersList, PedersenParams, generatePedersenParams, p256, tomEdwards256, ALL_GROUPS,
     Group, Point, Scalar, Engine, shutdown, setWireLayout, getWireLayout, setOption, native }

@@ -1421,6 +1421,121 @@ static napi_value LinkVerifyBatch(napi_env env, napi_callback_info info) {
     free(buf);
     return v;
 }
+/* Escrow tags (include/zkattest.h: zk_ctx_set_auditor, zk_escrow_*), on the pool's first context like the link calls; only the opening reads the active ring.
+ * (h, auditor: 72) -> undefined */
+static napi_value SetAuditor(napi_env env, napi_callback_info info) {
+    napi_value argv[2];
+    if (!get_args(env, info, 2, argv)) return NULL;
+    Handle *h = get_handle(env, argv[0], 0);
+    uint8_t *key;
+    size_t lk;
+    if (!h || !get_bytes(env, argv[1], &key, &lk)) return NULL;
+    if (lk != 72) {
+        napi_throw_range_error(env, NULL, "setAuditor: a 72-byte Tom-256 point");
+        return NULL;
+    }
+    zk_ctx *c = zk_pool_ctx(h->pool, 0);
+    zk_status st = zk_ctx_set_auditor(c, key);
+    if (st != ZK_OK) throw_text(env, st, zk_last_error(c));
+    return NULL;
+}
+/* (h, secret: 32) -> the auditor's key a g: 72 bytes */
+static napi_value EscrowKeygen(napi_env env, napi_callback_info info) {
+    napi_value argv[2];
+    if (!get_args(env, info, 2, argv)) return NULL;
+    Handle *h = get_handle(env, argv[0], 0);
+    uint8_t *secret, key[72];
+    size_t ls;
+    if (!h || !get_bytes(env, argv[1], &secret, &ls)) return NULL;
+    if (ls != 32) {
+        napi_throw_range_error(env, NULL, "escrowKeygen: a 32-byte secret");
+        return NULL;
+    }
+    zk_ctx *c = zk_pool_ctx(h->pool, 0);
+    zk_status st = zk_escrow_keygen(c, secret, key);
+    if (st != ZK_OK) {
+        throw_text(env, st, zk_last_error(c));
+        return NULL;
+    }
+    return new_buffer(env, key, 72);
+}
+/* (h, keys: B x 32, com: B x 72, blinder: B x 32, seeds: B x 32 -- FRESH) -> {tags: B x 472 (zeros where status != 0), status: B i32 LE} */
+static napi_value EscrowProveBatch(napi_env env, napi_callback_info info) {
+    napi_value argv[5];
+    if (!get_args(env, info, 5, argv)) return NULL;
+    Handle *h = get_handle(env, argv[0], 0);
+    uint8_t *key, *com, *bl, *seeds;
+    size_t lk, lc, lb, ls;
+    if (!h || !get_bytes(env, argv[1], &key, &lk) || !get_bytes(env, argv[2], &com, &lc) || !get_bytes(env, argv[3], &bl, &lb) || !get_bytes(env, argv[4], &seeds, &ls)) return NULL;
+    const size_t B = lk / 32;
+    if (lk % 32 || lc != 72 * B || lb != 32 * B || ls != 32 * B) {
+        napi_throw_range_error(env, NULL, "escrowProveBatch: per tag a 32-byte key, a 72-byte commitment, a 32-byte blinder and 32 seed bytes");
+        return NULL;
+    }
+    zk_ctx *c = zk_pool_ctx(h->pool, 0);
+    const uint64_t size = zk_escrow_tag_size();
+    uint8_t *buf = (uint8_t *)xmalloc(env, (size + 4) * B + 8);
+    if (!buf) return NULL;
+    int32_t *status = (int32_t *)buf;
+    uint8_t *out = buf + 4 * B;
+    zk_rng rng = {ZK_RNG_SEED, seeds, 0};
+    zk_status st = zk_escrow_prove_batch(c, B, key, com, bl, &rng, out, size * B, status);
+    napi_value v = NULL;
+    if (st != ZK_OK) throw_text(env, st, zk_last_error(c));
+    else if (napi_create_object(env, &v) == napi_ok) set_prop(env, v, "tags", new_buffer(env, out, size * B)), set_prop(env, v, "status", new_buffer(env, status, 4 * B));
+    free(buf);
+    return v;
+}
+/* (h, com: B x 72, tags: B x 472) -> {ok: B bytes, status: B i32 LE} */
+static napi_value EscrowVerifyBatch(napi_env env, napi_callback_info info) {
+    napi_value argv[3];
+    if (!get_args(env, info, 3, argv)) return NULL;
+    Handle *h = get_handle(env, argv[0], 0);
+    uint8_t *com, *tags;
+    size_t lc, lt;
+    if (!h || !get_bytes(env, argv[1], &com, &lc) || !get_bytes(env, argv[2], &tags, &lt)) return NULL;
+    const size_t B = lc / 72;
+    if (lc % 72 || lt != zk_escrow_tag_size() * B) {
+        napi_throw_range_error(env, NULL, "escrowVerifyBatch: one 72-byte commitment and one 472-byte tag per entry");
+        return NULL;
+    }
+    zk_ctx *c = zk_pool_ctx(h->pool, 0);
+    uint8_t *buf = (uint8_t *)xmalloc(env, 5 * B + 8);
+    if (!buf) return NULL;
+    int32_t *status = (int32_t *)buf;
+    uint8_t *ok = buf + 4 * B;
+    zk_status st = zk_escrow_verify_batch(c, B, com, tags, ok, status);
+    napi_value v = NULL;
+    if (st != ZK_OK) throw_text(env, st, zk_last_error(c));
+    else if (napi_create_object(env, &v) == napi_ok) set_prop(env, v, "ok", new_buffer(env, ok, B)), set_prop(env, v, "status", new_buffer(env, status, 4 * B));
+    free(buf);
+    return v;
+}
+/* (h, secret: 32, tags: B x 472) -> {index: B u32 LE (0xffffffff: nobody), status: B i32 LE}, against the ACTIVE ring */
+static napi_value EscrowOpenBatch(napi_env env, napi_callback_info info) {
+    napi_value argv[3];
+    if (!get_args(env, info, 3, argv)) return NULL;
+    Handle *h = get_handle(env, argv[0], 0);
+    uint8_t *secret, *tags;
+    size_t ls, lt;
+    if (!h || !get_bytes(env, argv[1], &secret, &ls) || !get_bytes(env, argv[2], &tags, &lt)) return NULL;
+    const size_t B = lt / zk_escrow_tag_size();
+    if (ls != 32 || lt != zk_escrow_tag_size() * B) {
+        napi_throw_range_error(env, NULL, "escrowOpenBatch: a 32-byte secret and 472-byte tags");
+        return NULL;
+    }
+    zk_ctx *c = zk_pool_ctx(h->pool, 0);
+    uint8_t *buf = (uint8_t *)xmalloc(env, 8 * B + 8);
+    if (!buf) return NULL;
+    int32_t *status = (int32_t *)buf;
+    uint32_t *index = (uint32_t *)(buf + 4 * B);
+    zk_status st = zk_escrow_open_batch(c, B, secret, tags, index, status);
+    napi_value v = NULL;
+    if (st != ZK_OK) throw_text(env, st, zk_last_error(c));
+    else if (napi_create_object(env, &v) == napi_ok) set_prop(env, v, "index", new_buffer(env, index, 4 * B)), set_prop(env, v, "status", new_buffer(env, status, 4 * B));
+    free(buf);
+    return v;
+}
 /* Distinct-key proofs (include/zkattest.h: zk_distinct_*), on the pool's first context like the link calls; no ring takes part.
  * (h, key1: B x 32, com1: B x 72, blinder1: B x 32, key2: B x 32, com2: B x 72, blinder2: B x 32, seeds: B x 32 -- FRESH) -> {proofs: B x 744 (zeros where
  * status != 0), status: B i32 LE} */
@@ -1641,6 +1756,8 @@ static napi_value Init(napi_env env, napi_value exports) {
                {"keyBlinders", KeyBlinders},     {"reringBatch", ReringBatch},     {"reringBatchRings", ReringBatchRings},
                {"linkProveBatch", LinkProveBatch}, {"linkVerifyBatch", LinkVerifyBatch}, {"keyCommitments", KeyCommitments},
                {"distinctProveBatch", DistinctProveBatch}, {"distinctVerifyBatch", DistinctVerifyBatch},
+               {"setAuditor", SetAuditor},       {"escrowKeygen", EscrowKeygen},   {"escrowProveBatch", EscrowProveBatch},
+               {"escrowVerifyBatch", EscrowVerifyBatch}, {"escrowOpenBatch", EscrowOpenBatch},
                {"quorumProveBatch", QuorumProveBatch}, {"quorumVerifyBatch", QuorumVerifyBatch},
                {"ringsQuorumProveBatch", QuorumProveBatchRings}, {"ringsQuorumVerifyBatch", QuorumVerifyBatchRings}};
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {

@@ -891,6 +891,70 @@ zk_status zk_rings_quorum_verify_batch_device(zk_ctx *ctx, uint64_t Q, uint32_t 
                                               const void *d_ring_ids /*u32[Qk]*/, const void *d_verifier_seeds, void *d_ok, void *d_per_quorum_status /*i32[Q]*/,
                                               void *d_first_bad /*u32[Q] or NULL*/);
 
+/* ---- escrow tags: let an auditor open which ring member attested.  Every statement above is about a committed key and never says which key it is.  An
+ * escrow tag adds the accountable path ("opening" in group signatures and DAA): beside a commitment C = x g + r h -- keyXcom of a ZKA1 proof (its blinder:
+ * zk_prove_key_blinders) or a ZKM1 commitment -- the prover puts an exponential ElGamal encryption of x under the key A = a g of a designated auditor and a
+ * sigma proof that the ciphertext carries the x of C.  Anyone verifies the tag; only who holds a learns which ring member it is.
+ *     E1 = rho g      E2 = x g + rho A      T1 = k_x g + k_r h      T2 = k_rho g      T3 = k_x g + k_rho A
+ *     c = hashPoints([C, E1, E2, A, T1, T2, T3])   (the ZKL1 challenge's hash and 80-bit truncation, seven points, this order)
+ *     t_x = k_x - c x      t_r = k_r - c r      t_rho = k_rho - c rho      (mod q)
+ * Wire format "ZKT1", 472 bytes:
+ *     header 16 B : "ZKT1" | total_len u32 big-endian (= 472) | 0 u32 | 0 u32
+ *     E1, E2, T1, T2, T3 : five Tom-256 points, 72 bytes each, as A_1 lies in ZKL1
+ *     t_x, t_r, t_rho    : 32 bytes big-endian each
+ *   always with 36-byte coordinates: zk_ctx_set_wire plays no part.  C travels beside the tag as com1 / com2 do for ZKL1; A is context state.
+ * zk_ctx_set_auditor: the auditor's public key as a 72-byte Tom-256 point.  In this order: ZK_E_BUFFER before zk_ctx_set_params; ZK_E_BAD_ENCODING for a
+ *   coordinate that is not below the field prime (padding bytes set included) or a point off the curve; ZK_E_ARG for the identity or a point with q A != O
+ *   (the curve has cofactor 4).  It builds the comb set of (g, A) on the device (16-bit combs of its own, about 0.13 GB per base; g's table is the context's
+ *   where the widths agree).  A second call replaces the key; zk_ctx_set_params drops it, and the escrow calls then give ZK_E_BUFFER until it is set again.
+ * zk_escrow_keygen: A = a g for a 32-byte big-endian secret, a REDUCED mod q; ZK_E_BUFFER before zk_ctx_set_params (g is the context's), ZK_E_ARG for
+ *   a = 0 mod q.  One comb walk; the staged secret is witness-flagged and zeroed before the call returns.  It needs no auditor key and sets none.
+ * zk_escrow_prove_batch: draws under the randomness contract, all mod q with the rejection handling of zk_link_prove_batch: fill 0 is rho, 1 k_x, 2 k_r,
+ *   3 k_rho; key and blinder are reduced mod q as newScalar does.  Per tag, in this order; a failed tag gets 472 zero bytes and touches no neighbour:
+ *     ZK_E_BAD_ENCODING   com has a coordinate that is not below the field prime (padding bytes set included) or is off the curve.
+ *     ZK_E_OPENING        x g + r h is not com (compared as canonical bytes): caught before a tag that cannot verify is written.
+ *     ZK_E_RNG_EXHAUSTED  ZK_RNG_STREAM with fewer blocks than the four draws and their rejected fills need.
+ *   ZK_E_BUFFER when out_cap < 472 B, or when no auditor is set, before a byte of out or the statuses is written.  The bytes depend neither on
+ *   zk_ctx_set_comb_bits, nor on the auditor set's width, nor on the uniform build; ZK_MODE_HARDENED only changes h, as for ZKL1.
+ * zk_escrow_verify_batch: per tag ZK_E_BAD_ENCODING for a wrong magic, total_len != 472, a nonzero reserved word, or any of the six points (com, E1, E2, T1,
+ *   T2, T3) non-canonical or off the curve.  Scalars >= q are REDUCED mod q, not refused, as in ZKL1.  Otherwise the status is 0 and ok = 1 iff all three
+ *   relations hold exactly,
+ *     (t_x g + t_r h) + c C - T1 = O      (t_rho g) + c E1 - T2 = O      (t_x g + t_rho A) + c E2 - T3 = O;
+ *   there is no verifier randomness and no verifier_seeds argument.  A tag made for auditor A gives ok = 0 under another key.
+ * zk_escrow_open_batch: the auditor's call, against the ACTIVE ring.  ZK_E_BUFFER when no auditor is set or no ring is active (before the secret is looked
+ *   at).  ZK_E_OPENING at call level, nothing written, when a g is not the context's auditor key; zk_last_timing then holds "escrow_open" alone.
+ *   Per tag ZK_E_BAD_ENCODING for the header, E1 or E2 (the index is then 0xffffffff); otherwise status 0 and the index is the lowest i below the ring's key
+ *   count with 4 y_i g = 4 E2 - a (4 E1), or 0xffffffff when there is none.  The factor 4 is part of the rule: E1 and E2 come out of a proof and may carry a
+ *   component of order 2 or 4 that a prover ground the challenge for until it cancelled in the relations; without the factor such a tag would verify and open
+ *   to nobody, with it the prime-order parts decide, and the relations force those to be rho g and x g + rho A with the x of C.  The _device form takes the
+ *   secret in HBM as well.  The table of the ring's points 4 y_i g is rebuilt by every call: its residency (and zk_ctx_update_ring's part in it) is left out.
+ * What a tag does and does not say.  It is bound to C and to A, not to a message or a ring: it stays valid after zk_proof_rering_batch, because keyXcom is
+ *   kept, and it can be copied together with its attestation -- that is the attestation's own replay property.  Opening does not verify: an auditor calls
+ *   zk_escrow_verify_batch (and the attestation's verifier) first.  rng must be independent of the seeds C's proof was made with: warning (2) of ZKL1, for
+ *   the same reason.  Anyone who knows a can open every tag made for A.
+ * Call-level rules are the link calls': ZK_E_ARG for NULL pointers, B >= 2^32 and while streamed jobs are queued; B = 0 is ZK_OK; chunks (zk_ctx_set_chunk) on
+ *   the context's lanes.  The _device forms take every pointer and rng->data in this context's HBM, 4-byte aligned, else ZK_E_ARG.  The staged keys, blinders,
+ *   draws and RNG fills, the staged secret a and a E1 are witness-derived: zk_ctx_wipe, zk_ctx_destroy and a failed call zero them.  zk_last_timing reports
+ *   "rng_prepass", "escrow_front", "tom_commit", "tom_normalize", "hash", "escrow_respond" (prover), "escrow_parse", "tom_commit", "escrow_ladder" (verifier)
+ *   and "escrow_open", "escrow_ladder", "tom_normalize", "escrow_ring_points", "escrow_match" (opening).  Not provided: submit / wait, zk_pool_*, JSON.
+ * How: six commitments per tag, four on the (g, h) combs and two on the (g, A) set; the verifier runs link_relation on one lane per (tag, relation); the
+ *   opening multiplies E1 by the 256-bit secret on one lane per tag, one doubling and one addition per bit, the addend chosen between the base and the
+ *   identity by a mask: no branch and no address depends on a bit of a, in every build.  DESIGN.md section 5h. */
+zk_status zk_ctx_set_auditor(zk_ctx *ctx, const uint8_t auditor_xy72[72]);
+zk_status zk_escrow_keygen(zk_ctx *ctx, const uint8_t secret_be32[32], uint8_t auditor_xy72[72]);
+uint64_t zk_escrow_tag_size(void);   /* 472 */
+zk_status zk_escrow_prove_batch(zk_ctx *ctx, uint64_t B, const uint8_t *key_be32 /*Bx32*/, const uint8_t *com_xy72 /*Bx72*/, const uint8_t *blinder_be32 /*Bx32*/,
+                                const zk_rng *rng, uint8_t *out, uint64_t out_cap, int32_t *per_tag_status /*B*/);
+zk_status zk_escrow_prove_batch_device(zk_ctx *ctx, uint64_t B, const void *d_key_be32, const void *d_com_xy72, const void *d_blinder_be32, const zk_rng *rng_device,
+                                       void *d_out, uint64_t out_cap, void *d_per_tag_status /*i32[B]*/);
+zk_status zk_escrow_verify_batch(zk_ctx *ctx, uint64_t B, const uint8_t *com_xy72 /*Bx72*/, const uint8_t *tags /*Bx472*/, uint8_t *ok /*B*/,
+                                 int32_t *per_tag_status /*B*/);
+zk_status zk_escrow_verify_batch_device(zk_ctx *ctx, uint64_t B, const void *d_com_xy72, const void *d_tags, void *d_ok, void *d_per_tag_status /*i32[B]*/);
+zk_status zk_escrow_open_batch(zk_ctx *ctx, uint64_t B, const uint8_t secret_be32[32], const uint8_t *tags /*Bx472*/, uint32_t *index_u32 /*B*/,
+                               int32_t *per_tag_status /*B*/);
+zk_status zk_escrow_open_batch_device(zk_ctx *ctx, uint64_t B, const void *d_secret_be32, const void *d_tags, void *d_index_u32 /*u32[B]*/,
+                                      void *d_per_tag_status /*i32[B]*/);
+
 /* ---- two (or more) batches in flight on one context.  zk_prove_batch / zk_verify_batch are synchronous: each call pays its own head
  * (no byte of a chunk exists before its stage 1 is over) and its own tail (the copies of the last slices, with nothing left to
  * hide them).  The submit / wait pair splits a call so that the pipeline keeps running ACROSS calls: submit stages the inputs and

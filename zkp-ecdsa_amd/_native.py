@@ -39,6 +39,8 @@ SYMBOLS = [
     'zk_distinct_proof_size', 'zk_distinct_prove_batch', 'zk_distinct_prove_batch_device', 'zk_distinct_verify_batch', 'zk_distinct_verify_batch_device',
     'zk_quorum_pair_count', 'zk_quorum_proof_max_size', 'zk_quorum_prove_batch', 'zk_quorum_prove_batch_device', 'zk_quorum_verify_batch', 'zk_quorum_verify_batch_device',
     'zk_rings_quorum_proof_max_size', 'zk_rings_quorum_prove_batch', 'zk_rings_quorum_prove_batch_device', 'zk_rings_quorum_verify_batch', 'zk_rings_quorum_verify_batch_device',
+    'zk_ctx_set_auditor', 'zk_escrow_keygen', 'zk_escrow_tag_size', 'zk_escrow_prove_batch', 'zk_escrow_prove_batch_device', 'zk_escrow_verify_batch',
+    'zk_escrow_verify_batch_device', 'zk_escrow_open_batch', 'zk_escrow_open_batch_device',
     'zk_test_field_op', 'zk_test_tom_commit', 'zk_test_p256_fixed_mul', 'zk_test_sha256', 'zk_test_rng_draws', 'zk_test_exp_sum',
 ]
 
@@ -205,6 +207,17 @@ def lib():
         L.zk_rings_quorum_prove_batch_device.argtypes = [vp, u64, C.c_uint32, vp, vp, vp, vp, vp, C.POINTER(ZkRng), C.POINTER(ZkRng), vp, u64, vp, vp, vp]
         L.zk_rings_quorum_verify_batch.argtypes = [vp, u64, C.c_uint32, C.c_char_p, C.c_char_p, vp, vp, C.c_char_p, vp, vp, vp]
         L.zk_rings_quorum_verify_batch_device.argtypes = [vp, u64, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp]
+        # escrow tags ("ZKT1"): ElGamal of a committed key under an auditor's key, and the auditor's opening
+        L.zk_ctx_set_auditor.argtypes = [vp, C.c_char_p]
+        L.zk_escrow_keygen.argtypes = [vp, C.c_char_p, vp]
+        L.zk_escrow_tag_size.argtypes = []
+        L.zk_escrow_tag_size.restype = u64
+        L.zk_escrow_prove_batch.argtypes = [vp, u64, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(ZkRng), vp, u64, vp]
+        L.zk_escrow_prove_batch_device.argtypes = [vp, u64, vp, vp, vp, C.POINTER(ZkRng), vp, u64, vp]
+        L.zk_escrow_verify_batch.argtypes = [vp, u64, C.c_char_p, C.c_char_p, vp, vp]
+        L.zk_escrow_verify_batch_device.argtypes = [vp, u64, vp, vp, vp, vp]
+        L.zk_escrow_open_batch.argtypes = [vp, u64, C.c_char_p, C.c_char_p, vp, vp]
+        L.zk_escrow_open_batch_device.argtypes = [vp, u64, vp, vp, vp, vp]
         L.zk_proof_key_commitments.argtypes = [vp, u64, C.c_char_p, vp, vp, vp]
         L.zk_proof_key_commitments_device.argtypes = [vp, u64, vp, vp, vp, vp]
         L.zk_ring_digest.argtypes = [vp, vp]
@@ -1330,6 +1343,75 @@ class Engine:
 
     def quorum_verify_batch_rings_device(self, Q, k, d_msg, d_bundles, d_bundle_off, d_ids, d_vseeds, d_ok, d_status, d_first_bad=None):
         self._chk(self.L.zk_rings_quorum_verify_batch_device(self.h, Q, k, d_msg, d_bundles, d_bundle_off, d_ids, d_vseeds, d_ok, d_status, d_first_bad))
+
+    # ---- escrow tags (zk_ctx_set_auditor, zk_escrow_*): ElGamal of a committed key under an auditor's key, tied to the commitment ("ZKT1", 472 bytes)
+    def set_auditor(self, auditor_xy72):
+        """zk_ctx_set_auditor: the auditor's public key A (72 bytes) for the escrow calls; zk_ctx_set_params drops it"""
+        if len(auditor_xy72) != 72:
+            raise ValueError('the auditor key is a 72-byte Tom-256 point')
+        self._chk(self.L.zk_ctx_set_auditor(self.h, bytes(auditor_xy72)))
+
+    def escrow_keygen(self, secret_be32):
+        """zk_escrow_keygen: A = a g for the 32-byte big-endian secret a (reduced mod q; 0 is refused)"""
+        if len(secret_be32) != 32:
+            raise ValueError('the secret is 32 bytes')
+        out = C.create_string_buffer(72)
+        self._chk(self.L.zk_escrow_keygen(self.h, bytes(secret_be32), out))
+        return out.raw
+
+    def escrow_tag_size(self):
+        return int(self.L.zk_escrow_tag_size())
+
+    def escrow_prove_batch(self, keys, com, blinder, seeds=None, streams=None, stream_blocks=0, cap=None):
+        """zk_escrow_prove_batch: tag b encrypts keys[b] under the context's auditor key and shows that it is the key of com[b] = keys[b] g + blinder[b] h.
+        keys, blinders: 32-byte big-endian scalars (a list, or B x 32 bytes), com: 72-byte Tom-256 points.  seeds / streams must be FRESH: never the ones
+        the commitment's proof was made with.  Returns (tags: list of 472-byte strings, None where the status is not 0; statuses).  self.escrow_last_raw keeps
+        the B slots as the call wrote them, and cap overrides the out_cap handed to the call, as link_prove_batch has them."""
+        B = len(keys) // 32 if isinstance(keys, (bytes, bytearray, memoryview)) else len(keys)
+        k, c1, b1 = self._rows(keys, 32, B, 'keys'), self._rows(com, 72, B, 'com'), self._rows(blinder, 32, B, 'blinder')
+        if seeds is None and streams is None:
+            seeds = os.urandom(32 * B)
+        rng, _keep = self._rng(B, seeds, streams, stream_blocks)
+        size = self.escrow_tag_size()
+        out = C.create_string_buffer(max(size * B, 1))
+        st = (C.c_int32 * max(B, 1))()
+        self._chk(self.L.zk_escrow_prove_batch(self.h, B, k, c1, b1, C.byref(rng), out, size * B if cap is None else cap, st))
+        raw = out.raw
+        self.escrow_last_raw = raw[:size * B]
+        return [raw[size * b:size * (b + 1)] if st[b] == 0 else None for b in range(B)], list(st)[:B]
+
+    def escrow_prove_batch_device(self, B, d_keys, d_com, d_blinder, d_rng, d_out, out_cap, d_status, mode=0, stride_blocks=0):
+        rng = ZkRng(mode, d_rng, stride_blocks)
+        self._chk(self.L.zk_escrow_prove_batch_device(self.h, B, d_keys, d_com, d_blinder, C.byref(rng), d_out, out_cap, d_status))
+
+    def escrow_verify_batch(self, com, tags):
+        """zk_escrow_verify_batch for B (com, tag) pairs, every tag 472 bytes.  Returns (ok list, status list)."""
+        B = len(tags)
+        size = self.escrow_tag_size()
+        if any(len(t) != size for t in tags):
+            raise ValueError('an escrow tag is %d bytes' % size)
+        ok = (C.c_uint8 * max(B, 1))()
+        st = (C.c_int32 * max(B, 1))()
+        self._chk(self.L.zk_escrow_verify_batch(self.h, B, self._rows(com, 72, B, 'com'), b''.join(tags) if B else bytes(size), ok, st))
+        return list(ok)[:B], list(st)[:B]
+
+    def escrow_verify_batch_device(self, B, d_com, d_tags, d_ok, d_status):
+        self._chk(self.L.zk_escrow_verify_batch_device(self.h, B, d_com, d_tags, d_ok, d_status))
+
+    def escrow_open_batch(self, secret_be32, tags):
+        """zk_escrow_open_batch: the auditor's call against the active ring.  Returns (indices: the lowest ring index whose key the tag carries, 0xffffffff
+        for none; statuses).  It does not verify: call escrow_verify_batch first."""
+        B = len(tags)
+        size = self.escrow_tag_size()
+        if len(secret_be32) != 32 or any(len(t) != size for t in tags):
+            raise ValueError('the secret is 32 bytes and an escrow tag %d' % size)
+        idx = (C.c_uint32 * max(B, 1))()
+        st = (C.c_int32 * max(B, 1))()
+        self._chk(self.L.zk_escrow_open_batch(self.h, B, bytes(secret_be32), b''.join(tags) if B else bytes(size), idx, st))
+        return list(idx)[:B], list(st)[:B]
+
+    def escrow_open_batch_device(self, B, d_secret, d_tags, d_index, d_status):
+        self._chk(self.L.zk_escrow_open_batch_device(self.h, B, d_secret, d_tags, d_index, d_status))
 
     def synth_params(self, seed):
         a, b, c = C.create_string_buffer(64), C.create_string_buffer(72), C.create_string_buffer(72)

@@ -173,6 +173,7 @@ extern "C" void zk_ctx_destroy(zk_ctx* c) {
     stream_release_spares(c);
     wipe_witness(c);
     for (auto e : c->epool) hipEventDestroy(e);
+    escrow_drop_auditor(c);
     hipFree(c->P.tom_tab_g), hipFree(c->P.tom_tab_h), hipFree(c->tom_tab_gen), hipFree(c->P.pfix_G), hipFree(c->P.pfix_H);
     for (auto& R : c->rings) free_ring(R);
     hipFree(c->tab_scratch), hipFree(c->d_flag);
@@ -233,6 +234,8 @@ extern "C" zk_status zk_ctx_set_params(zk_ctx* c, const uint8_t nist_h[64], cons
     if (sec == 0 || sec > ZK_MAXSEC) return ZK_E_SECLEVEL;
     if (c->stream_busy) return busy_refusal(c);
     HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    escrow_drop_auditor(c);   // the auditor's set shares g's table and was built for these bases
     uint32_t hw[16], gw[18], hw2[18];
     be_to_words(nist_h, 32, hw, 8), be_to_words(nist_h + 32, 32, hw + 8, 8);
     be_to_words(tom_g, 36, gw, 9), be_to_words(tom_g + 36, 36, gw + 9, 9);
@@ -275,6 +278,7 @@ extern "C" zk_status zk_ctx_set_params(zk_ctx* c, const uint8_t nist_h[64], cons
         return ZK_E_POINT_NOT_IN_GROUP;
     }
     words_to_limbs30(gw, 9, c->P.tom_g_aff), words_to_limbs30(gw + 9, 9, c->P.tom_g_aff + 9);
+    memcpy(c->tom_g_w, gw, sizeof gw);
     c->P.sec = sec;
     c->params_set = true;
     return ZK_OK;

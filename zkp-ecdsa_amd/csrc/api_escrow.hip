@@ -1,0 +1,449 @@
+// zk_ctx_set_auditor / zk_escrow_keygen / zk_escrow_prove_batch / zk_escrow_verify_batch / zk_escrow_open_batch (include/zkattest.h): escrow tags "ZKT1" --
+// exponential ElGamal of a committed key under an auditor's key with a sigma proof that ties it to the commitment, and the auditor's opening against the
+// active ring.  Host-side pipeline; the kernels of its own are in k_escrow.hip, the commitments are k_tom.hip's over the context's (g, h) combs and the
+// auditor's (g, A) set, the challenge hash k_hash.hip's message path.  The chunks run on the context's lanes (their streams are the prover lanes'), every
+// lane's arena carved from one witness-flagged buffer.
+#include "ctx.h"
+#include "jobs.h"
+#include "escrow.h"
+
+#define ZK_AUDITOR_BITS 16   // comb width of the (g, A) set: 0.13 GB per base (24 bits: 23 GB); a tag's bytes do not depend on it
+
+// ------------------------------------------------------------------ the auditor's key
+void escrow_drop_auditor(zk_ctx* c) {
+    if (c->PA.tom_tab_h) (void)hipFree(c->PA.tom_tab_h);
+    if (c->aud_tab_g) (void)hipFree(c->aud_tab_g);
+    c->PA = DevParams{};
+    c->aud_tab_g = nullptr, c->auditor_set = false;
+}
+extern "C" zk_status zk_ctx_set_auditor(zk_ctx* c, const uint8_t auditor_xy72[72]) {
+    if (!c || !auditor_xy72) return ZK_E_ARG;
+    if (c->stream_busy) return busy_refusal(c);
+    if (!c->params_set) return ZK_E_BUFFER;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    DevBuf d;   // 72 bytes of the key, its 18 words, g's 18 words, the kernel's two verdicts, the order check's two
+    HIPCHK(c, hipMalloc(&d.p, 512));
+    uint8_t* const d_xy = d.as<uint8_t>();
+    uint32_t* const d_w = (uint32_t*)(d_xy + 128);
+    uint32_t* const d_g = d_w + 32;
+    int32_t* const d_res = (int32_t*)(d_g + 32);
+    HIPCHK(c, hipMemcpyAsync(d_xy, auditor_xy72, 72, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_g, c->tom_g_w, 72, hipMemcpyHostToDevice, s));
+    launch_escrow_check_key(s, d_xy, d_w, d_res);
+    launch_tom_order_check(s, d_w, d_w, d_res + 2);
+    int32_t res[4] = {0, 0, 0, 0};
+    uint32_t aw[18];
+    HIPCHK(c, hipMemcpyAsync(res, d_res, 16, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(aw, d_w, 72, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (!res[0]) return ZK_E_BAD_ENCODING;
+    if (res[1] || !res[2]) {
+        c->err = "the auditor's key is the identity or has a component outside the group of prime order";
+        return ZK_E_ARG;
+    }
+    // from here on the previous key is gone: a failure below leaves the context without an auditor
+    escrow_drop_auditor(c);
+    const bool share = c->tom_bits == ZK_AUDITOR_BITS;
+    HIPCHK(c, hipMalloc(&c->PA.tom_tab_h, sizeof(uint32_t) * tom_tab_words(ZK_AUDITOR_BITS)));
+    if (!share) HIPCHK(c, hipMalloc(&c->aud_tab_g, sizeof(uint32_t) * tom_tab_words(ZK_AUDITOR_BITS)));
+    c->PA.tom_tab_g = share ? c->P.tom_tab_g : c->aud_tab_g;
+    c->PA.tom_bits = ZK_AUDITOR_BITS;
+    c->PA.tom_model = c->P.tom_model;   // A has odd order, so it may live on whichever model g's table is on
+    c->PA.sec = c->P.sec;
+    memcpy(c->PA.tom_g_aff, c->P.tom_g_aff, sizeof c->PA.tom_g_aff);
+    int32_t one = 1, ok = 0;
+    HIPCHK(c, hipMemcpyAsync(c->d_flag, &one, 4, hipMemcpyHostToDevice, s));
+    if (!share) launch_build_tom_table(s, d_g, ZK_AUDITOR_BITS, c->PA.tom_model, c->aud_tab_g, c->tab_scratch, c->d_flag);
+    launch_build_tom_table(s, d_w, ZK_AUDITOR_BITS, c->PA.tom_model, c->PA.tom_tab_h, c->tab_scratch, c->d_flag);
+    hipError_t e = hipMemcpyAsync(&ok, c->d_flag, 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess || !ok) escrow_drop_auditor(c);
+    HIPCHK(c, e);
+    if (!ok) return ZK_E_POINT_NOT_IN_GROUP;
+    memcpy(c->aud_w, aw, sizeof aw), memcpy(c->aud_xy, auditor_xy72, 72);
+    c->auditor_set = true;
+    return ZK_OK;
+}
+
+static zk_status escrow_refusal(zk_ctx* c, uint64_t B, bool need_auditor) {
+    if (!c->params_set) return ZK_E_BUFFER;
+    if (c->stream_busy) return busy_refusal(c);
+    if (B > 0xffffffffull) return ZK_E_ARG;
+    if (need_auditor && !c->auditor_set) {
+        c->err = "no auditor key is set (zk_ctx_set_auditor)";
+        return ZK_E_BUFFER;
+    }
+    return ZK_OK;
+}
+static bool escrow_aligned(std::initializer_list<const void*> ps) {   // the kernels read and write 32-bit words
+    for (const void* p : ps)
+        if ((uintptr_t)p & 3) return false;
+    return true;
+}
+extern "C" uint64_t zk_escrow_tag_size(void) { return ZKT1_SIZE; }
+
+// a * g for the secret at d_secret through one comb walk: S[0] = (a, 0), its affine bytes at d_ag; a8 (nullable) receives a mod q as words
+static void escrow_secret_point(zk_ctx* c, hipStream_t s, const uint8_t* d_secret, const TomList& S, uint32_t* a8, uint8_t* d_ag) {
+    launch_escrow_stage_secret(s, d_secret, S, 0, a8);
+    launch_tom_commit(s, c->P, S, 1, 1, 1);
+    launch_tom_normalize(s, S, 1, 0, 1, 1);
+    launch_affine_to_bytes(s, S.ax, S.ay, 1, 1, d_ag);
+}
+struct EscrowKeygen {
+    uint8_t *secret, *ag;
+    TomList S;
+};
+static size_t escrow_keygen_layout(EscrowKeygen& G, uint8_t* base) {
+    SoaCarver k(base);
+    G.secret = (uint8_t*)k.take(32), G.ag = (uint8_t*)k.take(72), G.S = k.list(1);
+    return k.off + ZK_LAYOUT_TAIL;
+}
+extern "C" zk_status zk_escrow_keygen(zk_ctx* c, const uint8_t secret_be32[32], uint8_t auditor_xy72[72]) {
+    if (!c || !secret_be32 || !auditor_xy72) return ZK_E_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (zk_status zs = escrow_refusal(c, 1, false)) return zs;
+    EscrowKeygen G;
+    if (zk_status zs = lay_out(c, B_et, [&](uint8_t* base) { return escrow_keygen_layout(G, base); })) return zs;
+    if (zk_status zs = upload_or_wipe(c, {{G.secret, secret_be32, 32}})) return zs;   // the staged secret lies in a witness-flagged buffer
+    escrow_secret_point(c, c->stream, G.secret, G.S, nullptr, G.ag);
+    uint8_t ag[72];
+    if (zk_status zs = download_or_wipe(c, {{G.ag, ag, 72}})) return zs;
+    wipe_witness(c);   // one key per call: nothing of it stays behind
+    bool ident = ag[71] == 1;
+    for (int i = 0; i < 71; i++) ident = ident && ag[i] == 0;
+    if (ident) {
+        c->err = "the secret is 0 mod q";
+        return ZK_E_ARG;
+    }
+    memcpy(auditor_xy72, ag, 72);
+    return ZK_OK;
+}
+
+// ------------------------------------------------------------------ lanes
+static size_t escrow_carve(EscrowLane* K, uint32_t nlanes, uint8_t* base, uint32_t C) {
+    SoaCarver k(base);
+    for (uint32_t l = 0; l < nlanes; l++) {
+        EscrowLane& X = K[l];
+        X = EscrowLane{};
+        X.C = C;
+        X.L = k.list(ESC_SLOTS * (size_t)C);
+        X.rng.exc_idx = (uint32_t*)k.take(4 * RNG_MAX_EXC * (size_t)C);
+        X.rng.exc_flags = (uint32_t*)k.take(4 * RNG_MAX_EXC * (size_t)C);
+        X.rng.exc_cnt = (uint32_t*)k.take(4 * (size_t)C);
+        X.rng_fill = (uint32_t*)k.take(32 * (size_t)ESC_RNG_BLOCKS * C);
+        X.st = (int32_t*)k.take(4 * (size_t)C);
+        X.flags = (uint32_t*)k.take(4 * (size_t)C);
+        X.cw = (uint32_t*)k.take(4 * 18 * (size_t)C);
+        X.msg = (uint8_t*)k.take((size_t)ZKT1_MSG_BLOCKS * 64 * C);
+        X.wk = (uint32_t*)k.take((size_t)ZKT1_MSG_BLOCKS * 256 * C);
+        X.chal = (uint32_t*)k.take(16 * (size_t)C);
+        X.rel = (uint32_t*)k.take(12 * (size_t)C);
+    }
+    return k.off + ZK_LAYOUT_TAIL;
+}
+// The chunk plan of a call of B tags and its lanes' arenas
+struct EscrowRun {
+    std::vector<ChunkPlan> plan;
+    uint32_t NL = 0;
+    EscrowLane K[ZK_MAX_LANES];
+};
+static zk_status escrow_plan(zk_ctx* c, uint64_t B, EscrowRun& R) {
+    const uint32_t C = (uint32_t)std::min<uint64_t>(c->chunk, B);
+    R.plan = make_chunk_plan(B, C, 1, false);
+    R.NL = (uint32_t)std::min<size_t>(std::min<uint32_t>(c->lanes, ZK_MAX_LANES), R.plan.size());
+    return lay_out(c, B_et, [&](uint8_t* base) { return escrow_carve(R.K, R.NL, base, C); });
+}
+static EscrowKey escrow_key(const zk_ctx* c) {
+    EscrowKey A;
+    memcpy(A.w, c->aud_w, sizeof A.w);
+    return A;
+}
+
+// ------------------------------------------------------------------ prover
+static zk_status escrow_prove_device(zk_ctx* c, uint64_t B, const EscrowProveIo& io, const zk_rng& rng, uint64_t out_cap) {
+    if (zk_status zs = escrow_refusal(c, B, true)) return zs;
+    if (!rng_mode_ok(&rng)) return ZK_E_ARG;
+    if (B > out_cap / ZKT1_SIZE) {
+        c->err = "output buffer too small";
+        return ZK_E_BUFFER;
+    }
+    if (B == 0) return ZK_OK;
+    if (!escrow_aligned({io.com, io.key, io.blinder, io.out, io.status, rng.data})) return ZK_E_ARG;
+    timing_begin(c);   // (behind every refusal: a call that runs nothing leaves the last call's record as it is)
+    EscrowRun R;
+    if (zk_status zs = escrow_plan(c, B, R)) return zs;
+    const bool timed = zk_timed(c, B);
+    const EscrowKey A = escrow_key(c);
+    for (uint64_t k = 0; k < R.plan.size(); k++) {
+        const uint32_t lane = (uint32_t)(k % R.NL), cnt = R.plan[k].cnt;
+        const uint64_t first = R.plan[k].first;
+        EscrowLane& K = R.K[lane];
+        hipStream_t s = c->pl[lane].stream;
+        K.rng.seeds = rng.data, K.rng.stream = rng.data, K.rng.stride_blocks = rng.stride_blocks, K.rng.mode = rng.mode, K.rng.sec = -1, K.rng.proof_base = (uint32_t)first;
+        {
+            MaybeScope t(timed, c, "rng_prepass", s);
+            Workspace W{};   // the prepass reads a workspace's RNG view
+            W.rng = K.rng;
+            launch_rng_prepass(s, W, cnt, 0, ESC_RNG_BLOCKS, ESC_RNG_BLOCKS, rng.mode == ZK_RNG_SEED ? K.rng_fill : nullptr, false);
+        }
+        if (rng.mode == ZK_RNG_SEED) K.rng.mode = ZK_RNG_STREAM, K.rng.stream = (const uint8_t*)K.rng_fill, K.rng.stride_blocks = ESC_RNG_BLOCKS, K.rng.proof_base = 0;
+        {
+            MaybeScope t(timed, c, "escrow_front", s);
+            launch_escrow_front(s, K, cnt, first, io);
+        }
+        {
+            MaybeScope t(timed, c, "tom_commit", s);
+            launch_tom_commit(s, c->P, K.L, 4 * cnt, 1, 1);                          // E1, T1, T2 and the claimed opening on (g, h)
+            launch_tom_commit(s, c->PA, escrow_view(K.L, 4 * cnt), 2 * cnt, 1, 1);   // E2, T3 on (g, A)
+        }
+        {
+            MaybeScope t(timed, c, "tom_normalize", s);
+            launch_tom_normalize(s, K.L, ESC_SLOTS * cnt, 0, 1, 1);
+        }
+        {
+            MaybeScope t(timed, c, "hash", s);
+            launch_escrow_opening_msg(s, K, A, cnt);
+            launch_escrow_hash(s, K, cnt);
+        }
+        {
+            MaybeScope t(timed, c, "escrow_respond", s);
+            launch_escrow_respond(s, K, cnt, first, io);
+        }
+    }
+    const hipError_t e_sync = drain_lanes(c, R.NL);
+    if (e_sync != hipSuccess) wipe_witness(c);   // a failed call leaves no nonce, blinder or RNG block behind
+    HIPCHK(c, e_sync);
+    HIPCHK(c, hipGetLastError());
+    timing_end(c);
+    return ZK_OK;
+}
+extern "C" zk_status zk_escrow_prove_batch_device(zk_ctx* c, uint64_t B, const void* d_key, const void* d_com, const void* d_blinder, const zk_rng* rng, void* d_out,
+                                                  uint64_t out_cap, void* d_status) {
+    if (!c || !rng || (B && (!d_key || !d_com || !d_blinder || !rng->data || !d_out || !d_status))) return ZK_E_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    const zk_status zs = escrow_prove_device(c, B, {(const uint8_t*)d_key, (const uint8_t*)d_com, (const uint8_t*)d_blinder, (uint8_t*)d_out, (int32_t*)d_status}, *rng, out_cap);
+    if (zs && c->params_set && !c->stream_busy) wipe_witness(c);
+    return zs;
+}
+// Host pointers: key, blinder and seeds through the context's witness-flagged input buffer, the tags through its output staging buffer.
+struct EscrowProveIn {
+    uint8_t *key, *com, *blinder, *rng;
+    int32_t* st;
+};
+static size_t escrow_prove_in_layout(EscrowProveIn& I, uint8_t* base, size_t B, size_t rng_bytes) {
+    Carver k(base);
+    I.key = (uint8_t*)k.take(32 * B), I.com = (uint8_t*)k.take(72 * B), I.blinder = (uint8_t*)k.take(32 * B);
+    I.rng = (uint8_t*)k.take(rng_bytes ? rng_bytes : 32), I.st = (int32_t*)k.take(4 * B);
+    return k.off + ZK_LAYOUT_TAIL;
+}
+extern "C" zk_status zk_escrow_prove_batch(zk_ctx* c, uint64_t B, const uint8_t* key, const uint8_t* com, const uint8_t* blinder, const zk_rng* rng, uint8_t* out,
+                                           uint64_t out_cap, int32_t* status) {
+    if (!c || !rng || (B && (!key || !com || !blinder || !rng->data || !out || !status))) return ZK_E_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (zk_status zs = escrow_refusal(c, B, true)) return zs;
+    if (!rng_mode_ok(rng)) return ZK_E_ARG;
+    if (B > out_cap / ZKT1_SIZE) {
+        c->err = "output buffer too small";
+        return ZK_E_BUFFER;
+    }
+    if (B == 0) return ZK_OK;
+    EscrowProveIn I;
+    if (zk_status zs = lay_out(c, B_in, [&](uint8_t* base) { return escrow_prove_in_layout(I, base, B, rng_bytes(rng, B)); })) return zs;
+    if (zk_status zs = reserve(c, B_io, B * ZKT1_SIZE)) return zs;
+    uint8_t* const d_out = (uint8_t*)c->buf[B_io].p;
+    // from the first upload on, key, blinder and seeds lie in the input buffer: every failure below zeroes them
+    if (zk_status zs = upload_or_wipe(c, {{I.key, key, 32 * B}, {I.com, com, 72 * B}, {I.blinder, blinder, 32 * B}, {I.rng, rng->data, rng_bytes(rng, B)}})) return zs;
+    if (zk_status zs = escrow_prove_device(c, B, {I.key, I.com, I.blinder, d_out, I.st}, zk_rng{rng->mode, I.rng, rng->stride_blocks}, B * ZKT1_SIZE)) {
+        wipe_witness(c);
+        return zs;
+    }
+    return download_or_wipe(c, {{d_out, out, B * ZKT1_SIZE}, {I.st, status, 4 * B}});
+}
+
+// ------------------------------------------------------------------ verifier
+static zk_status escrow_verify_device(zk_ctx* c, uint64_t B, const EscrowVerifyIo& io) {
+    if (zk_status zs = escrow_refusal(c, B, true)) return zs;
+    if (B == 0) return ZK_OK;
+    if (!escrow_aligned({io.com, io.tags, io.status})) return ZK_E_ARG;
+    timing_begin(c);
+    EscrowRun R;
+    if (zk_status zs = escrow_plan(c, B, R)) return zs;
+    const bool timed = zk_timed(c, B);
+    const EscrowKey A = escrow_key(c);
+    for (uint64_t k = 0; k < R.plan.size(); k++) {
+        const uint32_t lane = (uint32_t)(k % R.NL), cnt = R.plan[k].cnt;
+        const uint64_t first = R.plan[k].first;
+        const EscrowLane& K = R.K[lane];
+        hipStream_t s = c->pl[lane].stream;
+        {
+            MaybeScope t(timed, c, "escrow_parse", s);
+            launch_escrow_parse(s, K, A, cnt, first, io);
+            launch_escrow_hash(s, K, cnt);
+        }
+        {
+            MaybeScope t(timed, c, "tom_commit", s);
+            launch_tom_commit(s, c->P, K.L, 2 * cnt, 1, 1);                      // t_x g + t_r h, t_rho g
+            launch_tom_commit(s, c->PA, escrow_view(K.L, 2 * cnt), cnt, 1, 1);   // t_x g + t_rho A
+        }
+        {
+            MaybeScope t(timed, c, "escrow_ladder", s);
+            launch_escrow_relations(s, K, cnt, first, io);
+            launch_escrow_verdict(s, K, cnt, first, io);
+        }
+    }
+    HIPCHK(c, drain_lanes(c, R.NL));
+    HIPCHK(c, hipGetLastError());
+    timing_end(c);
+    return ZK_OK;
+}
+extern "C" zk_status zk_escrow_verify_batch_device(zk_ctx* c, uint64_t B, const void* d_com, const void* d_tags, void* d_ok, void* d_status) {
+    if (!c || (B && (!d_com || !d_tags || !d_ok || !d_status))) return ZK_E_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    return escrow_verify_device(c, B, {(const uint8_t*)d_com, (const uint8_t*)d_tags, (uint8_t*)d_ok, (int32_t*)d_status});
+}
+struct EscrowVerifyIn {   // no witness is staged: a failing copy returns as it is
+    uint8_t *com, *ok;
+    int32_t* st;
+};
+static size_t escrow_verify_in_layout(EscrowVerifyIn& I, uint8_t* base, size_t B) {
+    Carver k(base);
+    I.com = (uint8_t*)k.take(72 * B), I.ok = (uint8_t*)k.take(B), I.st = (int32_t*)k.take(4 * B);
+    return k.off + ZK_LAYOUT_TAIL;
+}
+extern "C" zk_status zk_escrow_verify_batch(zk_ctx* c, uint64_t B, const uint8_t* com, const uint8_t* tags, uint8_t* ok, int32_t* status) {
+    if (!c || (B && (!com || !tags || !ok || !status))) return ZK_E_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (zk_status zs = escrow_refusal(c, B, true)) return zs;
+    if (B == 0) return ZK_OK;
+    EscrowVerifyIn I;
+    if (zk_status zs = lay_out(c, B_in, [&](uint8_t* base) { return escrow_verify_in_layout(I, base, B); })) return zs;
+    if (zk_status zs = reserve(c, B_io, B * ZKT1_SIZE)) return zs;
+    uint8_t* const d_tags = (uint8_t*)c->buf[B_io].p;
+    hipStream_t s = c->stream;
+    HIPCHK(c, hipMemcpyAsync(I.com, com, 72 * B, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_tags, tags, B * ZKT1_SIZE, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (zk_status zs = escrow_verify_device(c, B, {I.com, d_tags, I.ok, I.st})) return zs;
+    HIPCHK(c, hipMemcpyAsync(ok, I.ok, B, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(status, I.st, 4 * B, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    return ZK_OK;
+}
+
+// ------------------------------------------------------------------ opening
+static size_t escrow_open_carve(EscrowOpen& O, uint8_t* base, uint64_t B, uint32_t slab) {
+    SoaCarver k(base);
+    O = EscrowOpen{};
+    O.S = k.list(1);
+    O.a8 = (uint32_t*)k.take(32);
+    O.ag = (uint8_t*)k.take(72);
+    O.T = k.list(B);
+    O.st = (int32_t*)k.take(4 * B);
+    O.Rg = k.list(slab);
+    return k.off + ZK_LAYOUT_TAIL;
+}
+// The auditor's side.  1. a g against the context's key, once; 2. one lane per tag: 4 (E2 - a E1), normalised; 3. per slab of the active ring's real keys:
+// 4 y_i g through the comb, normalised; 4. the match.  The ring's point table is rebuilt by every call.
+static zk_status escrow_open_device(zk_ctx* c, uint64_t B, const uint8_t* d_secret, const uint8_t* d_tags, uint32_t* d_index, int32_t* d_status) {
+    if (zk_status zs = escrow_refusal(c, B, true)) return zs;
+    if (!c->ring->N) {
+        c->err = "no ring is active";
+        return ZK_E_BUFFER;
+    }
+    if (B == 0) return ZK_OK;
+    if (!escrow_aligned({d_secret, d_tags, d_index, d_status})) return ZK_E_ARG;
+    timing_begin(c);
+    const uint64_t nkeys = c->ring->nkeys;
+    const uint32_t slab = (uint32_t)std::min<uint64_t>(nkeys, ESC_RING_SLAB);
+    EscrowOpen O;
+    if (zk_status zs = lay_out(c, B_et, [&](uint8_t* base) { return escrow_open_carve(O, base, B, slab); })) return zs;
+    const bool timed = zk_timed(c, B);
+    hipStream_t s0 = c->stream;
+    {
+        MaybeScope t(timed, c, "escrow_open", s0);
+        escrow_secret_point(c, s0, d_secret, O.S, O.a8, O.ag);
+    }
+    uint8_t ag[72];
+    if (zk_status zs = download_or_wipe(c, {{O.ag, ag, 72}})) return zs;   // (a blocking copy: the staged secret is in place for every lane behind it)
+    if (memcmp(ag, c->aud_xy, 72) != 0) {
+        wipe_witness(c);
+        timing_end(c);   // the key check ran: the call's record is its "escrow_open" family alone
+        c->err = "the secret does not belong to the context's auditor key";
+        return ZK_E_OPENING;
+    }
+    const uint32_t C = (uint32_t)std::min<uint64_t>(c->chunk, B);
+    const std::vector<ChunkPlan> plan = make_chunk_plan(B, C, 1, false);
+    const uint32_t NL = (uint32_t)std::min<size_t>(std::min<uint32_t>(c->lanes, ZK_MAX_LANES), plan.size());
+    for (uint64_t k = 0; k < plan.size(); k++) {
+        hipStream_t s = c->pl[k % NL].stream;
+        MaybeScope t(timed, c, "escrow_ladder", s);
+        launch_escrow_open_points(s, O, plan[k].cnt, plan[k].first, d_tags, d_index, d_status);
+    }
+    hipError_t e = drain_lanes(c, NL);
+    if (e == hipSuccess) {
+        {
+            MaybeScope t(timed, c, "tom_normalize", s0);
+            launch_tom_normalize(s0, O.T, (uint32_t)B, 0, 1, 1);
+        }
+        const Soa ring = {c->ring->ring_mem, (uint32_t)c->ring->N};
+        for (uint64_t i0 = 0; i0 < nkeys; i0 += slab) {
+            const uint32_t n = (uint32_t)std::min<uint64_t>(slab, nkeys - i0);
+            {
+                MaybeScope t(timed, c, "escrow_ring_points", s0);
+                launch_escrow_ring_scalars(s0, ring, i0, n, O.Rg);
+                launch_tom_commit(s0, c->P, O.Rg, n, 1, 1);
+                launch_escrow_times4(s0, O.Rg, n);
+                launch_tom_normalize(s0, O.Rg, n, 0, 1, 1);
+            }
+            {
+                MaybeScope t(timed, c, "escrow_match", s0);
+                launch_escrow_match(s0, O, B, i0, n, d_index);
+            }
+        }
+        e = hipStreamSynchronize(s0);
+    }
+    if (e != hipSuccess) wipe_witness(c);   // a failed call leaves neither a nor a E1 behind
+    HIPCHK(c, e);
+    HIPCHK(c, hipGetLastError());
+    timing_end(c);
+    return ZK_OK;
+}
+extern "C" zk_status zk_escrow_open_batch_device(zk_ctx* c, uint64_t B, const void* d_secret, const void* d_tags, void* d_index, void* d_status) {
+    if (!c || !d_secret || (B && (!d_tags || !d_index || !d_status))) return ZK_E_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    const zk_status zs = escrow_open_device(c, B, (const uint8_t*)d_secret, (const uint8_t*)d_tags, (uint32_t*)d_index, (int32_t*)d_status);
+    if (zs && zs != ZK_E_OPENING && c->params_set && !c->stream_busy) wipe_witness(c);
+    return zs;
+}
+struct EscrowOpenIn {
+    uint8_t* secret;
+    uint32_t* index;
+    int32_t* st;
+};
+static size_t escrow_open_in_layout(EscrowOpenIn& I, uint8_t* base, size_t B) {
+    Carver k(base);
+    I.secret = (uint8_t*)k.take(32), I.index = (uint32_t*)k.take(4 * B), I.st = (int32_t*)k.take(4 * B);
+    return k.off + ZK_LAYOUT_TAIL;
+}
+extern "C" zk_status zk_escrow_open_batch(zk_ctx* c, uint64_t B, const uint8_t secret_be32[32], const uint8_t* tags, uint32_t* index_u32, int32_t* status) {
+    if (!c || !secret_be32 || (B && (!tags || !index_u32 || !status))) return ZK_E_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (zk_status zs = escrow_refusal(c, B, true)) return zs;
+    if (!c->ring->N) {
+        c->err = "no ring is active";
+        return ZK_E_BUFFER;
+    }
+    if (B == 0) return ZK_OK;
+    EscrowOpenIn I;
+    if (zk_status zs = lay_out(c, B_in, [&](uint8_t* base) { return escrow_open_in_layout(I, base, B); })) return zs;
+    if (zk_status zs = reserve(c, B_io, B * ZKT1_SIZE)) return zs;
+    uint8_t* const d_tags = (uint8_t*)c->buf[B_io].p;
+    // from the first upload on the secret lies in the input buffer: every failure below zeroes it
+    if (zk_status zs = upload_or_wipe(c, {{I.secret, secret_be32, 32}, {d_tags, tags, B * ZKT1_SIZE}})) return zs;
+    if (zk_status zs = escrow_open_device(c, B, I.secret, d_tags, I.index, I.st)) {
+        wipe_witness(c);
+        return zs;
+    }
+    return download_or_wipe(c, {{I.index, index_u32, 4 * B}, {I.st, status, 4 * B}});
+}

@@ -55,7 +55,8 @@ enum GrowPolicy {
     X(lk, GROW_SHED, true)        /* link proofs (api_link.hip): the lanes' arenas -- the staged key and blinders, the nonces k, s1, s2, the RNG fills, the challenge's message */ \
     X(dk, GROW_SHED, true)        /* distinct-key proofs (api_distinct.hip): the lanes' arenas -- the staged keys and blinders, d, 1 / d, r_w, the nonces, the RNG fills, the challenge's message */ \
     X(qs, GROW_SHED, true)        /* quorum proofs (api_quorum.hip): a window's staging -- the gathered keys, keyXcoms and blinders of its pairs, its attestations and distinct-key proofs until they are in place; verifier: the walked offsets, the members' and pairs' bytes and verdicts */ \
-    X(qc, GROW_SLACK, false)      /* ... their `_rings` forms: every quorum's capacity, the call's total and the set of rings its ids name (from ring ids: public) */
+    X(et, GROW_SHED, true)        /* escrow tags (api_escrow.hip): the lanes' arenas -- the staged key and blinder, rho and the nonces, the RNG fills, the challenge's message; an open call's staged secret a, the points 4 (E2 - a E1) and a slab of the ring's points */ \
+    X(qc, GROW_SLACK, false)      /* ... the quorum calls' `_rings` forms: every quorum's capacity, the call's total and the set of rings its ids name (from ring ids: public) */
 enum BufId {
 #define X(name, policy, witness) B_##name,
     ZK_CTX_BUFS(X)
@@ -85,6 +86,14 @@ struct zk_ctx {
     // params
     DevParams P{};
     bool params_set = false;
+    // the auditor's key of the escrow tags (zk_ctx_set_auditor, api_escrow.hip): a second comb set over (g, A) in the shape of P, so that the commitment
+    // kernels produce x g + rho A unchanged.  Its width is its own (ZK_AUDITOR_BITS); g's table is the context's where the widths agree, else aud_tab_g.
+    DevParams PA{};
+    bool auditor_set = false;
+    uint32_t* aud_tab_g = nullptr;    // g at the auditor set's width where the context's differs (owned; nullptr: PA.tom_tab_g is P.tom_tab_g)
+    uint32_t aud_w[18] = {};          // A as nine little-endian words per coordinate, and as the caller's bytes
+    uint8_t aud_xy[72] = {};
+    uint32_t tom_g_w[18] = {};        // g in the same form (zk_ctx_set_params)
     uint32_t* tom_tab_gen = nullptr;  // 8-bit comb table of the Tom generator (synthetic params only)
     uint32_t tom_bits = TOM_DEFAULT_BITS;  // comb width requested for g, h (zk_ctx_set_comb_bits)
     uint32_t tab_bits_alloc = 0;      // width the allocated P.tom_tab_g/h were sized for (0 = not allocated)
@@ -307,6 +316,7 @@ struct DevBuf {
     template <class T>
     T* as() const { return (T*)p; }
 };
+void escrow_drop_auditor(zk_ctx* c);   // api_escrow.hip: frees the (g, A) set (zk_ctx_set_params, zk_ctx_destroy; nothing may be in flight)
 void wipe_witness(zk_ctx* c);   // api.hip: zeroes every witness-derived buffer of the context (nothing may be in flight)
 // lanes 0 .. NL-1 drained: the first error one of their streams gave
 static inline hipError_t drain_lanes(zk_ctx* c, uint32_t NL) {
