@@ -144,6 +144,10 @@ export function proveEscrowTags(params: PedersenParams | SystemParametersList, a
 export function verifyEscrowTags(params: PedersenParams | SystemParametersList, auditor: Point | Buffer, coms: LinkCom[], tags: (EscrowTag | Buffer)[]): Promise<boolean[]>
 /** the auditor's call: per tag the index in `keys` of the ring member whose key it carries (the lowest where a key occurs twice), null for nobody */
 export function openEscrowTags(params: PedersenParams | SystemParametersList, secret: LinkScalar, keys: bigint[] | Buffer, tags: (EscrowTag | Buffer)[]): Promise<(number | null)[]>
+/** ... with ONE KEY LIST PER TAG in the place of `keys`: the tags of a registry sharded over several rings open in one zk_rings_escrow_open_batch (per group of at
+ *  most residentRings rings), through each ring's resident point index.  Per tag { ring, index } -- ring counts the distinct key lists in the order of their first
+ *  appearance, index is the member's (lowest) index in the tag's list -- or null for nobody. */
+export function openEscrowTags(params: PedersenParams | SystemParametersList, secret: LinkScalar, keys: (bigint[] | Buffer)[], tags: (EscrowTag | Buffer)[]): Promise<({ ring: number; index: number } | null)[]>
 /** Distinct-key proofs ("ZKD1", zk_distinct_*): comA = keyA g + blinderA h and comB = keyB g + blinderB h hide DIFFERENT keys: one MultProof (src/commit/mult.ts)
  *  for (keyA - keyB) * w = 1.  A proof verifies for (comA, comB) in this order only; equal keys throw '... hide the same key ...'; the engine draws fresh seeds. */
 export class DistinctProof {
@@ -258,6 +262,9 @@ export class Engine {
     escrowVerifyBatch(com: Buffer[], tags: Buffer[]): { ok: boolean[]; status: Int32Array }
     /** zk_escrow_open_batch against the ACTIVE ring: index 0xffffffff = nobody; it does not verify */
     escrowOpenBatch(secret32: Uint8Array, tags: Buffer[]): { index: number[]; status: Int32Array }
+    /** zk_rings_escrow_open_batch: one resident ring id per tag (0xffffffff: any resident ring, ascending ids), through the rings' resident point indexes; the
+     *  active ring is not involved.  ring / index 0xffffffff = nobody; it does not verify */
+    ringsEscrowOpenBatch(secret32: Uint8Array, tags: Buffer[], ringIds: number[]): { ring: number[]; index: number[]; status: Int32Array }
     /** zk_proof_key_commitments: keyXcom of proofs in the engine's wire layout, 72 bytes each; null where the status is not 0 */
     keyCommitments(proofs: Buffer[]): { coms: (Buffer | null)[]; status: Int32Array }
     keysToInts(pkxy: Buffer): { keys: Buffer; status: Buffer }

@@ -483,6 +483,11 @@ class Engine {
         const r = native.escrowOpenBatch(this.h, Buffer.from(secret32), Buffer.concat(tags))
         return { index: Array.from(tags, (_, i) => r.index.readUInt32LE(4 * i)), status: i32(r.status) }
     }
+    // zk_rings_escrow_open_batch: one resident ring id per tag (0xffffffff: any resident ring, ascending ids); the active ring is not involved
+    ringsEscrowOpenBatch(secret32, tags, ringIds) {
+        const r = native.ringsEscrowOpenBatch(this.h, Buffer.from(secret32), Buffer.concat(tags), Buffer.from(Uint32Array.from(ringIds).buffer))
+        return { ring: Array.from(tags, (_, i) => r.ring.readUInt32LE(4 * i)), index: Array.from(tags, (_, i) => r.index.readUInt32LE(4 * i)), status: i32(r.status) }
+    }
     // distinct-key proofs (zk_distinct_*): "ZKD1", 744 bytes -- com1[i] opens to key1[i] under blinder1[i], com2[i] to key2[i] under blinder2[i], and the keys differ;
     // the proof verifies for (com1, com2) in this order only.  Arrays of Buffers -> { proofs: Buffer | null per entry, status: Int32Array } (status 14: equal keys).
     // seeds must be FRESH: never the ones either commitment's proof was made with (default: crypto.randomBytes)
@@ -1269,9 +1274,31 @@ async function verifyEscrowTags(params, auditor, coms, tags) {
 }
 // openEscrowTags(params, secret, keys, tags): the auditor's call -> per tag the index in `keys` of the ring member whose key it carries (the lowest, where a key
 // occurs twice) or null for nobody.  It does NOT verify: call verifyEscrowTag (and the attestation's verifier) first.  Throws when the secret is 0 mod q.
+// With one key list per tag in the place of `keys` (the convention of reringSignatureLists) the tags of a sharded registry open in one zk_rings_escrow_open_batch
+// per group of at most residentRings rings, through the rings' resident point indexes: -> per tag { ring, index } -- ring counts the distinct key lists in the
+// order of their first appearance, index is the member's index in that list -- or null for nobody.
 async function openEscrowTags(params, secret, keys, tags) {
     if (!tags.length) return []
     const raw = tags.map((t) => (t instanceof EscrowTag ? t.bytes : new EscrowTag(t).bytes)), a = scalarBytes(secret)
+    if (isKeyLists(keys)) {
+        if (keys.length !== tags.length) throw new RangeError('openEscrowTags: one key list per tag')
+        const { rings, ringOfEntry } = memberRingsOf(keys, false)
+        const { withRings, capacity } = engineFor(paramsOf(params), keys[0])
+        const out = new Array(tags.length), per = capacity()
+        for (let g = 0; g < rings.length; g += per) {
+            const sel = []
+            for (let i = 0; i < tags.length; i++) if (ringOfEntry[i] >= g && ringOfEntry[i] < g + per) sel.push(i)
+            const r = await withRings(rings.slice(g, g + per), (engine, ids) => {
+                useAuditor(engine, engine.escrowKeygen(a))
+                return engine.ringsEscrowOpenBatch(a, sel.map((i) => raw[i]), sel.map((i) => ids[ringOfEntry[i] - g]))
+            })
+            sel.forEach((i, k) => {
+                if (r.status[k] !== 0) throw statusError(r.status[k])
+                out[i] = r.index[k] === 0xffffffff ? null : { ring: ringOfEntry[i], index: r.index[k] }
+            })
+        }
+        return out
+    }
     const r = await engineFor(paramsOf(params), keys).withRing((engine) => { useAuditor(engine, engine.escrowKeygen(a)); return engine.escrowOpenBatch(a, raw) })
     return r.index.map((w, i) => { if (r.status[i] !== 0) throw statusError(r.status[i]); return w === 0xffffffff ? null : w })
 }

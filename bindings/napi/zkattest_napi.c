@@ -1536,6 +1536,34 @@ static napi_value EscrowOpenBatch(napi_env env, napi_callback_info info) {
     free(buf);
     return v;
 }
+/* (h, secret: 32, tags: B x 472, ringIds: B u32 LE, 0xffffffff = any resident ring) -> {ring: B u32 LE, index: B u32 LE (0xffffffff: nobody), status: B i32 LE}:
+ * zk_rings_escrow_open_batch, through the rings' resident point indexes; the active ring is not involved */
+static napi_value EscrowOpenBatchRings(napi_env env, napi_callback_info info) {
+    napi_value argv[4];
+    if (!get_args(env, info, 4, argv)) return NULL;
+    Handle *h = get_handle(env, argv[0], 0);
+    uint8_t *secret, *tags, *ids;
+    size_t ls, lt, li;
+    if (!h || !get_bytes(env, argv[1], &secret, &ls) || !get_bytes(env, argv[2], &tags, &lt) || !get_bytes(env, argv[3], &ids, &li)) return NULL;
+    const size_t B = lt / zk_escrow_tag_size();
+    if (ls != 32 || lt != zk_escrow_tag_size() * B || li != 4 * B) {
+        napi_throw_range_error(env, NULL, "ringsEscrowOpenBatch: a 32-byte secret, 472-byte tags and one u32 ring id per tag");
+        return NULL;
+    }
+    zk_ctx *c = zk_pool_ctx(h->pool, 0);
+    uint8_t *buf = (uint8_t *)xmalloc(env, 16 * B + 8);
+    if (!buf) return NULL;
+    int32_t *status = (int32_t *)buf;
+    uint32_t *index = (uint32_t *)(buf + 4 * B), *ring = (uint32_t *)(buf + 8 * B), *idw = (uint32_t *)(buf + 12 * B);
+    memcpy(idw, ids, 4 * B);   /* (a Buffer's bytes need not be 4-byte aligned) */
+    zk_status st = zk_rings_escrow_open_batch(c, B, secret, tags, idw, ring, index, status);
+    napi_value v = NULL;
+    if (st != ZK_OK) throw_text(env, st, zk_last_error(c));
+    else if (napi_create_object(env, &v) == napi_ok)
+        set_prop(env, v, "ring", new_buffer(env, ring, 4 * B)), set_prop(env, v, "index", new_buffer(env, index, 4 * B)), set_prop(env, v, "status", new_buffer(env, status, 4 * B));
+    free(buf);
+    return v;
+}
 /* Distinct-key proofs (include/zkattest.h: zk_distinct_*), on the pool's first context like the link calls; no ring takes part.
  * (h, key1: B x 32, com1: B x 72, blinder1: B x 32, key2: B x 32, com2: B x 72, blinder2: B x 32, seeds: B x 32 -- FRESH) -> {proofs: B x 744 (zeros where
  * status != 0), status: B i32 LE} */
@@ -1759,7 +1787,8 @@ static napi_value Init(napi_env env, napi_value exports) {
                {"setAuditor", SetAuditor},       {"escrowKeygen", EscrowKeygen},   {"escrowProveBatch", EscrowProveBatch},
                {"escrowVerifyBatch", EscrowVerifyBatch}, {"escrowOpenBatch", EscrowOpenBatch},
                {"quorumProveBatch", QuorumProveBatch}, {"quorumVerifyBatch", QuorumVerifyBatch},
-               {"ringsQuorumProveBatch", QuorumProveBatchRings}, {"ringsQuorumVerifyBatch", QuorumVerifyBatchRings}};
+               {"ringsQuorumProveBatch", QuorumProveBatchRings}, {"ringsQuorumVerifyBatch", QuorumVerifyBatchRings},
+               {"ringsEscrowOpenBatch", EscrowOpenBatchRings}};
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;
         if (napi_create_function(env, fns[i].name, NAPI_AUTO_LENGTH, fns[i].fn, NULL, &f) != napi_ok) return NULL;

@@ -955,6 +955,35 @@ zk_status zk_escrow_open_batch(zk_ctx *ctx, uint64_t B, const uint8_t secret_be3
 zk_status zk_escrow_open_batch_device(zk_ctx *ctx, uint64_t B, const void *d_secret_be32, const void *d_tags, void *d_index_u32 /*u32[B]*/,
                                       void *d_per_tag_status /*i32[B]*/);
 
+/* ---- opening escrow tags against any resident ring: one resident ring id per tag, through a resident point index.  The auditor of a registry sharded over
+ * the resident rings (zk_ctx_add_ring; zk_prove_batch_rings -> tags -> zk_verify_batch_rings) opens a mixed batch in ONE call: the 256-bit ladder a E1, the
+ * largest part of an opening and independent of the ring, runs once per tag, and the tag's point is looked up in the ring its id names.
+ * ring_ids[b] is the id of a resident ring, or ZK_ESCROW_RING_ANY: the resident rings are then searched in ascending id order and the first one that holds the
+ *   key answers.  The ACTIVE ring is neither read nor changed, and "no active ring" is no refusal.
+ * Per tag, in this order: ZK_E_ARG when ring_ids[b] is neither resident nor ZK_ESCROW_RING_ANY (before the tag's bytes are judged); ZK_E_BAD_ENCODING for the
+ *   header, E1 or E2; otherwise 0.  ring_out and index are both 0xffffffff unless the status is 0 and a match exists; then index is the lowest i below that
+ *   ring's key count with 4 y_i g = 4 E2 - a (4 E1) -- the rule, its factor 4 and its warnings are zk_escrow_open_batch's -- and ring_out the ring's id.
+ * Call level: zk_escrow_open_batch's rules (ZK_E_BUFFER without parameters or an auditor key, ZK_E_OPENING with nothing written for a secret that is not the
+ *   auditor key's, B = 0 is ZK_OK, ZK_E_ARG for NULL pointers and while streamed jobs are queued; the staged secret, a E1 and the tags' points are
+ *   witness-derived and wiped as there).  The _device form takes every pointer and the secret in this context's HBM, 4-byte aligned, else ZK_E_ARG.
+ * The point index.  The call first builds the index of every resident ring that lacks one (a failed allocation is the call's failure, ZK_E_DEVICE, nothing
+ *   written): the ring's affine points 4 y_i g, 72 bytes per entry of the padded ring, and an open-addressed table of u32 key indices over them with twice as
+ *   many slots as the padded ring has entries (a power of two, at least twice the key count), 0xffffffff for an empty slot, linear probing with wrap-around.
+ *   The home slot of a point is a function of the two low 32-bit words w0, w1 of its canonical x:
+ *       h = w0 * 0x9e3779b1 + w1 * 0x85ebca6b;  h ^= h >> 16;  h *= 0xc2b2ae35;  h ^= h >> 13  (mod 2^32);  slot = h & (slots - 1)
+ *   (csrc/escrow_index.h is its one definition).  Every distinct point owns one slot, which holds its lowest index; a crafted ring whose points share a home
+ *   slot lengthens probes -- bounded by the slot count -- and changes no answer.  The index depends on g and the ring only: it is public, not wiped, and is
+ *   kept from call to call.  zk_ctx_update_ring patches it where the padded size stays (the touched keys' points are recomputed and the slots refilled from
+ *   the resident points; no tombstones); every rebuild of a ring (a size change, zk_ctx_set_ring) and zk_ctx_set_params drop it, and the next call builds
+ *   it again.  A ring that no such call has named in a context costs nothing: zk_ctx_add_ring, zk_ctx_set_ring and zk_ring_info are unchanged.
+ * zk_last_timing: "escrow_index_build" (only in a call that built one), "escrow_open", "escrow_ladder", "tom_normalize", "escrow_lookup".
+ * Not provided: pool, streamed and JSON forms.  DESIGN.md section 5h'. */
+#define ZK_ESCROW_RING_ANY 0xffffffffu
+zk_status zk_rings_escrow_open_batch(zk_ctx *ctx, uint64_t B, const uint8_t secret_be32[32], const uint8_t *tags /*Bx472*/, const uint32_t *ring_ids /*B*/,
+                                     uint32_t *ring_out_u32 /*B*/, uint32_t *index_u32 /*B*/, int32_t *per_tag_status /*B*/);
+zk_status zk_rings_escrow_open_batch_device(zk_ctx *ctx, uint64_t B, const void *d_secret_be32, const void *d_tags, const void *d_ring_ids /*u32[B]*/,
+                                            void *d_ring_out_u32 /*u32[B]*/, void *d_index_u32 /*u32[B]*/, void *d_per_tag_status /*i32[B]*/);
+
 /* ---- two (or more) batches in flight on one context.  zk_prove_batch / zk_verify_batch are synchronous: each call pays its own head
  * (no byte of a chunk exists before its stage 1 is over) and its own tail (the copies of the last slices, with nothing left to
  * hide them).  The submit / wait pair splits a call so that the pipeline keeps running ACROSS calls: submit stages the inputs and

@@ -41,6 +41,7 @@ SYMBOLS = [
     'zk_rings_quorum_proof_max_size', 'zk_rings_quorum_prove_batch', 'zk_rings_quorum_prove_batch_device', 'zk_rings_quorum_verify_batch', 'zk_rings_quorum_verify_batch_device',
     'zk_ctx_set_auditor', 'zk_escrow_keygen', 'zk_escrow_tag_size', 'zk_escrow_prove_batch', 'zk_escrow_prove_batch_device', 'zk_escrow_verify_batch',
     'zk_escrow_verify_batch_device', 'zk_escrow_open_batch', 'zk_escrow_open_batch_device',
+    'zk_rings_escrow_open_batch', 'zk_rings_escrow_open_batch_device',
     'zk_test_field_op', 'zk_test_tom_commit', 'zk_test_p256_fixed_mul', 'zk_test_sha256', 'zk_test_rng_draws', 'zk_test_exp_sum',
 ]
 
@@ -218,6 +219,9 @@ def lib():
         L.zk_escrow_verify_batch_device.argtypes = [vp, u64, vp, vp, vp, vp]
         L.zk_escrow_open_batch.argtypes = [vp, u64, C.c_char_p, C.c_char_p, vp, vp]
         L.zk_escrow_open_batch_device.argtypes = [vp, u64, vp, vp, vp, vp]
+        # ... against any resident ring, through the rings' resident point indexes: one ring id per tag
+        L.zk_rings_escrow_open_batch.argtypes = [vp, u64, C.c_char_p, C.c_char_p, vp, vp, vp, vp]
+        L.zk_rings_escrow_open_batch_device.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp]
         L.zk_proof_key_commitments.argtypes = [vp, u64, C.c_char_p, vp, vp, vp]
         L.zk_proof_key_commitments_device.argtypes = [vp, u64, vp, vp, vp, vp]
         L.zk_ring_digest.argtypes = [vp, vp]
@@ -319,6 +323,7 @@ RING_TABLE_E, RING_DIGIT_PLANES, RING_TABLE_E_DIGITS, RING_KEY_TABLES, RING_ACTI
 # zk_screen_batch: the bits of flags[b] (0 = prove this witness) and the index of a key that is not in the ring
 SCREEN_KEY_NOT_ON_CURVE, SCREEN_SIG_RANGE, SCREEN_SIG_INVALID, SCREEN_NOT_IN_RING, SCREEN_RING_NOT_RESIDENT = 1, 2, 4, 8, 16
 WHICH_NONE = 0xFFFFFFFF
+ESCROW_RING_ANY = 0xFFFFFFFF   # zk_rings_escrow_open_batch: search every resident ring, ascending ids
 # zk_recover_batch: the bits of flags[b] (0 = the key was recovered and is in the ring at which_out[b]); shared values mean what they mean for the screen
 RECOVER_SIG_RANGE, RECOVER_NOT_IN_RING, RECOVER_RING_NOT_RESIDENT, RECOVER_NO_POINT = 2, 8, 16, 32
 
@@ -1412,6 +1417,23 @@ class Engine:
 
     def escrow_open_batch_device(self, B, d_secret, d_tags, d_index, d_status):
         self._chk(self.L.zk_escrow_open_batch_device(self.h, B, d_secret, d_tags, d_index, d_status))
+
+    def escrow_open_batch_rings(self, secret_be32, tags, ring_ids):
+        """zk_rings_escrow_open_batch: the auditor's call with one resident ring id per tag (ESCROW_RING_ANY: every resident ring, ascending ids); the active
+        ring is not involved.  Returns (rings: the id of the ring that holds the tag's key, indices: its lowest index there -- both 0xffffffff for none --,
+        statuses).  It does not verify: call escrow_verify_batch first."""
+        B = len(tags)
+        size = self.escrow_tag_size()
+        if len(secret_be32) != 32 or any(len(t) != size for t in tags) or len(ring_ids) != B:
+            raise ValueError('the secret is 32 bytes, an escrow tag %d, and every tag has a ring id' % size)
+        ids = (C.c_uint32 * max(B, 1))(*ring_ids)
+        ring, idx = (C.c_uint32 * max(B, 1))(), (C.c_uint32 * max(B, 1))()
+        st = (C.c_int32 * max(B, 1))()
+        self._chk(self.L.zk_rings_escrow_open_batch(self.h, B, bytes(secret_be32), b''.join(tags) if B else bytes(size), ids, ring, idx, st))
+        return list(ring)[:B], list(idx)[:B], list(st)[:B]
+
+    def escrow_open_batch_rings_device(self, B, d_secret, d_tags, d_ring_ids, d_ring_out, d_index, d_status):
+        self._chk(self.L.zk_rings_escrow_open_batch_device(self.h, B, d_secret, d_tags, d_ring_ids, d_ring_out, d_index, d_status))
 
     def synth_params(self, seed):
         a, b, c = C.create_string_buffer(64), C.create_string_buffer(72), C.create_string_buffer(72)

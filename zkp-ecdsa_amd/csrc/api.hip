@@ -236,6 +236,7 @@ extern "C" zk_status zk_ctx_set_params(zk_ctx* c, const uint8_t nist_h[64], cons
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     escrow_drop_auditor(c);   // the auditor's set shares g's table and was built for these bases
+    for (auto& R : c->rings) escrow_index_drop(R);   // ... and so was every ring's point index
     uint32_t hw[16], gw[18], hw2[18];
     be_to_words(nist_h, 32, hw, 8), be_to_words(nist_h + 32, 32, hw + 8, 8);
     be_to_words(tom_g, 36, gw, 9), be_to_words(tom_g + 36, 36, gw + 9, 9);
@@ -286,6 +287,7 @@ extern "C" zk_status zk_ctx_set_params(zk_ctx* c, const uint8_t nist_h[64], cons
 
 static void free_ring(Ring& R) {   // (nothing in flight reads it: the callers synchronise or refuse while jobs are queued)
     hipFree(R.ring_mem), hipFree(R.gk_etab), hipFree(R.gk_kdig), hipFree(R.gk_edig), hipFree(R.ktab), hipFree(R.ktab_ok), hipFree(R.ring_digest), hipFree(R.leaves);
+    escrow_index_drop(R);
     const uint32_t id = R.id;
     const uint64_t gen = R.generation;
     const bool live = R.live;
@@ -521,7 +523,8 @@ static zk_status patch_ring(zk_ctx* c, Ring& R, const std::vector<uint32_t>& ent
         launch_ktab_copy_entry0(c->stream, d_ent + real, k - real, R.ktab, R.ktab_ok);   // behind the fill: entry 0's table is final
     }
     launch_ring_digest_list(c->stream, ring, R.N, R.N >= 256 ? d_blocks : nullptr, R.N >= 256 ? b : 1, R.leaves, R.ring_digest);
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
+    const hipError_t e_index = R.esc_pts ? escrow_index_patch(c, R, d_ent, real, new_nkeys) : hipSuccess;   // the point index follows the ring where one exists
+    if (e_index != hipSuccess || hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
         c->err = "zk_ctx_update_ring: a kernel of the update failed; the ring was dropped";
         return ZK_E_DEVICE;
     }

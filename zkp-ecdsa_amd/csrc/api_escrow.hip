@@ -447,3 +447,187 @@ extern "C" zk_status zk_escrow_open_batch(zk_ctx* c, uint64_t B, const uint8_t s
     }
     return download_or_wipe(c, {{I.index, index_u32, 4 * B}, {I.st, status, 4 * B}});
 }
+
+// ------------------------------------------------------------------ the resident point index and the opening against any resident ring
+// (escrow_index.h; kernels: k_escrow_index.hip).  A ring's points 4 y_i g and the table of key indices over them are public data of (g, the ring): not
+// witness-flagged, kept from one call to the next, patched by zk_ctx_update_ring's in-place path, dropped by every rebuild of the ring and by
+// zk_ctx_set_params.  A ring of nkeys >= 2 keys has esc_index_cap(nkeys) == N entries.
+static_assert(ESC_INDEX_MAX_RINGS >= ZK_MAX_RINGS, "one descriptor per resident ring");
+#define ESC_INDEX_SLAB (1u << 16)   // keys whose points are computed at a time: 252 bytes of temporary memory each
+void escrow_index_drop(Ring& R) {
+    hipFree(R.esc_pts), hipFree(R.esc_slots);
+    R.esc_pts = nullptr, R.esc_slots = nullptr;
+}
+static EscIndexRing escrow_index_desc(const Ring& R, uint64_t nkeys) {
+    EscIndexRing D{};
+    D.id = R.id, D.nkeys = (uint32_t)nkeys, D.mask = 2 * (uint32_t)R.N - 1, D.pts = R.esc_pts, D.slots = R.esc_slots;
+    return D;
+}
+static size_t escrow_index_tmp_layout(TomList& L, uint8_t* base, uint32_t slab) {
+    SoaCarver k(base);
+    L = k.list(slab);
+    return k.off + ZK_LAYOUT_TAIL;
+}
+static hipError_t escrow_index_tmp(DevBuf& d, TomList& L, uint32_t slab) {
+    const hipError_t e = hipMalloc(&d.p, escrow_index_tmp_layout(L, nullptr, slab));
+    if (e == hipSuccess) escrow_index_tmp_layout(L, d.as<uint8_t>(), slab);
+    return e;
+}
+static void escrow_index_refill(hipStream_t s, const Ring& R, uint64_t nkeys) {   // every slot empty, then one lane per key
+    (void)hipMemsetAsync(R.esc_slots, 0xff, 8 * R.N, s);
+    launch_escrow_index_insert(s, escrow_index_desc(R, nkeys));
+}
+// slots 0 .. n - 1 of L hold the openings (y, 0): their points 4 y g, normalised into L.ax, L.ay
+static void escrow_index_points(zk_ctx* c, hipStream_t s, const TomList& L, uint32_t n) {
+    launch_tom_commit(s, c->P, L, n, 1, 1);
+    launch_escrow_times4(s, L, n);
+    launch_tom_normalize(s, L, n, 0, 1, 1);
+}
+static zk_status escrow_index_build(zk_ctx* c, Ring& R) {
+    hipStream_t s = c->stream;
+    const uint32_t slab = (uint32_t)std::min<uint64_t>(R.nkeys, ESC_INDEX_SLAB), cap = (uint32_t)R.N;
+    DevBuf tmp;
+    TomList L;
+    if (hipMalloc(&R.esc_pts, 72 * R.N) != hipSuccess || hipMalloc(&R.esc_slots, 8 * R.N) != hipSuccess || escrow_index_tmp(tmp, L, slab) != hipSuccess) {
+        (void)hipGetLastError();
+        escrow_index_drop(R);
+        c->err = "the point index of a resident ring could not be allocated";
+        return ZK_E_DEVICE;
+    }
+    const Soa ring = {R.ring_mem, cap};
+    for (uint64_t i0 = 0; i0 < R.nkeys; i0 += slab) {   // the normaliser writes each slab where it stays
+        const uint32_t n = (uint32_t)std::min<uint64_t>(slab, R.nkeys - i0);
+        TomList V = L;
+        V.ax = Soa{R.esc_pts + i0, cap}, V.ay = Soa{R.esc_pts + 9 * (size_t)cap + i0, cap};
+        launch_escrow_ring_scalars(s, ring, i0, n, V);
+        escrow_index_points(c, s, V, n);
+    }
+    escrow_index_refill(s, R, R.nkeys);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) escrow_index_drop(R);
+    HIPCHK(c, e);
+    return ZK_OK;
+}
+hipError_t escrow_index_patch(zk_ctx* c, Ring& R, const uint32_t* d_ent, uint32_t real, uint64_t nkeys) {
+    hipStream_t s = c->stream;
+    DevBuf tmp;
+    TomList L;
+    const uint32_t slab = std::min<uint32_t>(real, ESC_INDEX_SLAB);
+    if (real && escrow_index_tmp(tmp, L, slab) != hipSuccess) {
+        (void)hipGetLastError();
+        escrow_index_drop(R);
+        return hipSuccess;
+    }
+    const Soa ring = {R.ring_mem, (uint32_t)R.N};
+    for (uint32_t j0 = 0; j0 < real; j0 += slab) {
+        const uint32_t n = std::min<uint32_t>(slab, real - j0);
+        launch_escrow_index_gather(s, ring, d_ent + j0, n, L);
+        escrow_index_points(c, s, L, n);
+        launch_escrow_index_scatter(s, L, d_ent + j0, n, R.esc_pts, (uint32_t)R.N);
+    }
+    escrow_index_refill(s, R, nkeys);
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? e : hipStreamSynchronize(s);   // (the temporary list goes with this scope)
+}
+
+// The auditor's side over the resident rings.  1. the index of every resident ring that lacks one; 2. a g against the context's key, once; 3. one lane per
+// tag: 4 (E2 - a E1), normalised (zk_escrow_open_batch's kernels); 4. one lane per tag: the lookup in the ring its id names.  The active ring is not read.
+static zk_status rings_escrow_open_device(zk_ctx* c, uint64_t B, const uint8_t* d_secret, const uint8_t* d_tags, const uint32_t* d_ids, uint32_t* d_ring_out, uint32_t* d_index,
+                                          int32_t* d_status) {
+    if (zk_status zs = escrow_refusal(c, B, true)) return zs;
+    if (B == 0) return ZK_OK;
+    if (!escrow_aligned({d_secret, d_tags, d_ids, d_ring_out, d_index, d_status})) return ZK_E_ARG;
+    timing_begin(c);
+    const bool timed = zk_timed(c, B);
+    hipStream_t s0 = c->stream;
+    Ring* rs[ZK_MAX_RINGS];
+    uint32_t nr = 0;
+    for (auto& R : c->rings)
+        if (R.live && R.N) rs[nr++] = &R;
+    std::sort(rs, rs + nr, [](const Ring* a, const Ring* b) { return a->id < b->id; });
+    EscIndexSet S{};
+    for (uint32_t k = 0; k < nr; k++) {
+        if (!rs[k]->esc_pts) {
+            MaybeScope t(timed, c, "escrow_index_build", s0);
+            if (zk_status zs = escrow_index_build(c, *rs[k])) return zs;
+        }
+        S.r[S.count++] = escrow_index_desc(*rs[k], rs[k]->nkeys);
+    }
+    EscrowOpen O;
+    if (zk_status zs = lay_out(c, B_et, [&](uint8_t* base) { return escrow_open_carve(O, base, B, 0); })) return zs;
+    {
+        MaybeScope t(timed, c, "escrow_open", s0);
+        escrow_secret_point(c, s0, d_secret, O.S, O.a8, O.ag);
+    }
+    uint8_t ag[72];
+    if (zk_status zs = download_or_wipe(c, {{O.ag, ag, 72}})) return zs;   // (a blocking copy: the staged secret is in place for every lane behind it)
+    if (memcmp(ag, c->aud_xy, 72) != 0) {
+        wipe_witness(c);
+        timing_end(c);
+        c->err = "the secret does not belong to the context's auditor key";
+        return ZK_E_OPENING;
+    }
+    const uint32_t C = (uint32_t)std::min<uint64_t>(c->chunk, B);
+    const std::vector<ChunkPlan> plan = make_chunk_plan(B, C, 1, false);
+    const uint32_t NL = (uint32_t)std::min<size_t>(std::min<uint32_t>(c->lanes, ZK_MAX_LANES), plan.size());
+    for (uint64_t k = 0; k < plan.size(); k++) {
+        hipStream_t s = c->pl[k % NL].stream;
+        MaybeScope t(timed, c, "escrow_ladder", s);
+        launch_escrow_open_points(s, O, plan[k].cnt, plan[k].first, d_tags, d_index, d_status);
+    }
+    hipError_t e = drain_lanes(c, NL);
+    if (e == hipSuccess) {
+        {
+            MaybeScope t(timed, c, "tom_normalize", s0);
+            launch_tom_normalize(s0, O.T, (uint32_t)B, 0, 1, 1);
+        }
+        {
+            MaybeScope t(timed, c, "escrow_lookup", s0);
+            launch_escrow_index_lookup(s0, S, O, B, d_ids, d_ring_out, d_index, d_status);
+        }
+        e = hipStreamSynchronize(s0);
+    }
+    if (e != hipSuccess) wipe_witness(c);   // a failed call leaves neither a nor a E1 behind
+    HIPCHK(c, e);
+    HIPCHK(c, hipGetLastError());
+    timing_end(c);
+    return ZK_OK;
+}
+extern "C" zk_status zk_rings_escrow_open_batch_device(zk_ctx* c, uint64_t B, const void* d_secret, const void* d_tags, const void* d_ring_ids, void* d_ring_out, void* d_index,
+                                                       void* d_status) {
+    if (!c || !d_secret || (B && (!d_tags || !d_ring_ids || !d_ring_out || !d_index || !d_status))) return ZK_E_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    const zk_status zs = rings_escrow_open_device(c, B, (const uint8_t*)d_secret, (const uint8_t*)d_tags, (const uint32_t*)d_ring_ids, (uint32_t*)d_ring_out, (uint32_t*)d_index,
+                                                  (int32_t*)d_status);
+    if (zs && zs != ZK_E_OPENING && c->params_set && !c->stream_busy) wipe_witness(c);
+    return zs;
+}
+struct RingsEscrowOpenIn {
+    uint8_t* secret;
+    uint32_t *ids, *ring, *index;
+    int32_t* st;
+};
+static size_t rings_escrow_open_in_layout(RingsEscrowOpenIn& I, uint8_t* base, size_t B) {
+    Carver k(base);
+    I.secret = (uint8_t*)k.take(32), I.ids = (uint32_t*)k.take(4 * B), I.ring = (uint32_t*)k.take(4 * B), I.index = (uint32_t*)k.take(4 * B), I.st = (int32_t*)k.take(4 * B);
+    return k.off + ZK_LAYOUT_TAIL;
+}
+extern "C" zk_status zk_rings_escrow_open_batch(zk_ctx* c, uint64_t B, const uint8_t secret_be32[32], const uint8_t* tags, const uint32_t* ring_ids, uint32_t* ring_out_u32,
+                                                uint32_t* index_u32, int32_t* status) {
+    if (!c || !secret_be32 || (B && (!tags || !ring_ids || !ring_out_u32 || !index_u32 || !status))) return ZK_E_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (zk_status zs = escrow_refusal(c, B, true)) return zs;
+    if (B == 0) return ZK_OK;
+    RingsEscrowOpenIn I;
+    if (zk_status zs = lay_out(c, B_in, [&](uint8_t* base) { return rings_escrow_open_in_layout(I, base, B); })) return zs;
+    if (zk_status zs = reserve(c, B_io, B * ZKT1_SIZE)) return zs;
+    uint8_t* const d_tags = (uint8_t*)c->buf[B_io].p;
+    // from the first upload on the secret lies in the input buffer: every failure below zeroes it
+    if (zk_status zs = upload_or_wipe(c, {{I.secret, secret_be32, 32}, {I.ids, ring_ids, 4 * B}, {d_tags, tags, B * ZKT1_SIZE}})) return zs;
+    if (zk_status zs = rings_escrow_open_device(c, B, I.secret, d_tags, I.ids, I.ring, I.index, I.st)) {
+        wipe_witness(c);
+        return zs;
+    }
+    return download_or_wipe(c, {{I.ring, ring_out_u32, 4 * B}, {I.index, index_u32, 4 * B}, {I.st, status, 4 * B}});
+}

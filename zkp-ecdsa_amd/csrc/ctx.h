@@ -78,6 +78,8 @@ struct Ring {
     uint32_t n = 0;
     uint32_t* ring_digest = nullptr;   // [8] SHA-256 words of the padded ring (hardened mode)
     uint32_t* leaves = nullptr;        // [8 x ceil(N / 256)] the digest's leaf hashes, kept so that zk_ctx_update_ring rehashes the touched leaves and the root only
+    uint32_t* esc_pts = nullptr;       // [18][N] the points 4 y_i g of the keys below nkeys (escrow_index.h), built by the first zk_rings_escrow_open_batch
+    uint32_t* esc_slots = nullptr;     // [2 N] ... and the open-addressed table of key indices over them; both or neither
 };
 struct zk_ctx {
     int device = 0;
@@ -316,6 +318,10 @@ struct DevBuf {
     template <class T>
     T* as() const { return (T*)p; }
 };
+void escrow_index_drop(Ring& R);   // api_escrow.hip: frees a ring's point index (free_ring; zk_ctx_set_params for every ring: it was built for g)
+// ... zk_ctx_update_ring's patch: the points of the touched real entries d_ent[0 .. real-1] recomputed, the slots refilled for nkeys keys.  Where the
+// temporary memory is not there the index is dropped instead (the next open call rebuilds it).  Runs on c->stream, behind the patch of the ring's limbs.
+hipError_t escrow_index_patch(zk_ctx* c, Ring& R, const uint32_t* d_ent, uint32_t real, uint64_t nkeys);
 void escrow_drop_auditor(zk_ctx* c);   // api_escrow.hip: frees the (g, A) set (zk_ctx_set_params, zk_ctx_destroy; nothing may be in flight)
 void wipe_witness(zk_ctx* c);   // api.hip: zeroes every witness-derived buffer of the context (nothing may be in flight)
 // lanes 0 .. NL-1 drained: the first error one of their streams gave

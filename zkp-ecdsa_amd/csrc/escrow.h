@@ -4,6 +4,7 @@
 // the host CPU under ZK_HOST_BUILD (tests/host_arith/host_escrow.cpp).
 #pragma once
 #include "link.h"
+#include "escrow_index.h"
 
 // "ZKT1": 16 header bytes ("ZKT1" | total_len = 472 | 0 | 0), E1, E2, T1, T2, T3 (72 bytes each), t_x, t_r, t_rho (32 bytes each)
 #define ZKT1_HDR 16
@@ -113,4 +114,10 @@ void launch_escrow_open_points(hipStream_t s, const EscrowOpen& O, uint32_t coun
 void launch_escrow_ring_scalars(hipStream_t s, const Soa& ring, uint64_t i0, uint32_t n, const TomList& L);
 void launch_escrow_times4(hipStream_t s, const TomList& L, uint32_t n);   // the projective triples of slots 0 .. n - 1, doubled twice in place
 void launch_escrow_match(hipStream_t s, const EscrowOpen& O, uint64_t B, uint64_t i0, uint32_t n, uint32_t* index);
+// k_escrow_index.hip: the resident point index (escrow_index.h)
+void launch_escrow_index_insert(hipStream_t s, const EscIndexRing& R);   // the slots hold ESC_INDEX_EMPTY, the points of the keys below R.nkeys are in place
+void launch_escrow_index_lookup(hipStream_t s, const EscIndexSet& S, const EscrowOpen& O, uint64_t B, const uint32_t* ring_ids, uint32_t* ring_out, uint32_t* index,
+                                int32_t* status);   // behind launch_escrow_open_points and the normaliser of O.T
+void launch_escrow_index_gather(hipStream_t s, const Soa& ring, const uint32_t* ent, uint32_t n, const TomList& L);
+void launch_escrow_index_scatter(hipStream_t s, const TomList& L, const uint32_t* ent, uint32_t n, uint32_t* pts, uint32_t cap);
 #endif
