@@ -148,6 +148,29 @@ export function openEscrowTags(params: PedersenParams | SystemParametersList, se
  *  most residentRings rings), through each ring's resident point index.  Per tag { ring, index } -- ring counts the distinct key lists in the order of their first
  *  appearance, index is the member's (lowest) index in the tag's list -- or null for nobody. */
 export function openEscrowTags(params: PedersenParams | SystemParametersList, secret: LinkScalar, keys: (bigint[] | Buffer)[], tags: (EscrowTag | Buffer)[]): Promise<({ ring: number; index: number } | null)[]>
+/** Threshold opening ("ZKS1", zk_auditors_* / zk_ctx_set_auditors): a dealer splits the auditor's secret into Shamir shares; each of t of n auditors turns a tag into
+ *  a 264-byte verifiable share (D = a_j E1 with a proof against A_j); anyone verifies shares and combines t of them into what openEscrowTags gives. */
+export class EscrowShare {
+    constructor(bytes: Buffer)
+    readonly bytes: Buffer
+    readonly j: number
+    readonly D: Point
+    readonly U1: Point
+    readonly U2: Point
+    readonly s: Scalar
+    eq(o: EscrowShare): boolean
+}
+/** a t-of-n set: the auditor's key A, the threshold and the share keys A_1 .. A_n */
+export interface AuditorSet { key: Point | Buffer; t: number; keys: (Point | Buffer)[] }
+/** the dealer's split (the dealer sees the secret): the set to publish, and one 32-byte share secret per auditor */
+export function splitAuditorKey(params: PedersenParams | SystemParametersList, secret: LinkScalar, t: number, n: number): Promise<{ key: Point; t: number; keys: Point[]; shares: Buffer[] }>
+/** auditor j's shares of the tags; throws when the share secret is not A_j's */
+export function shareEscrowTags(params: PedersenParams | SystemParametersList, auditors: AuditorSet, j: number, shareSecret: LinkScalar, tags: (EscrowTag | Buffer)[]): Promise<EscrowShare[]>
+/** one share per tag; run it on every share before combining */
+export function verifyEscrowShares(params: PedersenParams | SystemParametersList, auditors: AuditorSet, tags: (EscrowTag | Buffer)[], shares: (EscrowShare | Buffer)[]): Promise<boolean[]>
+/** shares[s][b]: one auditor's share of tags[b], t rows of different auditors.  The answer is openEscrowTags' for the undivided secret; it does not verify */
+export function combineEscrowShares(params: PedersenParams | SystemParametersList, auditors: AuditorSet, keys: bigint[] | Buffer, tags: (EscrowTag | Buffer)[], shares: (EscrowShare | Buffer)[][]): Promise<(number | null)[]>
+export function combineEscrowShares(params: PedersenParams | SystemParametersList, auditors: AuditorSet, keys: (bigint[] | Buffer)[], tags: (EscrowTag | Buffer)[], shares: (EscrowShare | Buffer)[][]): Promise<({ ring: number; index: number } | null)[]>
 /** Distinct-key proofs ("ZKD1", zk_distinct_*): comA = keyA g + blinderA h and comB = keyB g + blinderB h hide DIFFERENT keys: one MultProof (src/commit/mult.ts)
  *  for (keyA - keyB) * w = 1.  A proof verifies for (comA, comB) in this order only; equal keys throw '... hide the same key ...'; the engine draws fresh seeds. */
 export class DistinctProof {
@@ -265,6 +288,15 @@ export class Engine {
     /** zk_rings_escrow_open_batch: one resident ring id per tag (0xffffffff: any resident ring, ascending ids), through the rings' resident point indexes; the
      *  active ring is not involved.  ring / index 0xffffffff = nobody; it does not verify */
     ringsEscrowOpenBatch(secret32: Uint8Array, tags: Buffer[], ringIds: number[]): { ring: number[]; index: number[]; status: Int32Array }
+    /** zk_auditors_split_key: the dealer's Shamir split -> n 32-byte share secrets and n 72-byte share keys; the seed must be fresh (default: crypto.randomBytes) */
+    auditorsSplitKey(secret32: Uint8Array, t: number, n: number, seed?: Buffer): { shares: Buffer[]; keys: Buffer[] }
+    /** zk_ctx_set_auditors: the share keys of a t-of-n opening, checked against the auditor's key; setAuditor and setParams drop them */
+    auditorsSetKeys(t: number, keys: Uint8Array[]): void
+    /** zk_auditors_share_batch: auditor j's 264-byte shares of the tags; status 16 at call level: the share secret is not A_j's */
+    auditorsShareBatch(j: number, shareSecret32: Uint8Array, tags: Buffer[], seeds?: Buffer): { shares: (Buffer | null)[]; status: Int32Array }
+    auditorsShareVerifyBatch(tags: Buffer[], shares: Buffer[]): { ok: boolean[]; status: Int32Array }
+    /** zk_auditors_combine_batch: shares[s][b] is auditors[s]'s share of tags[b]; one resident ring id per tag (0xffffffff: any); it does not verify */
+    auditorsCombineBatch(auditors: number[], tags: Buffer[], shares: Buffer[][], ringIds: number[]): { ring: number[]; index: number[]; status: Int32Array }
     /** zk_proof_key_commitments: keyXcom of proofs in the engine's wire layout, 72 bytes each; null where the status is not 0 */
     keyCommitments(proofs: Buffer[]): { coms: (Buffer | null)[]; status: Int32Array }
     keysToInts(pkxy: Buffer): { keys: Buffer; status: Buffer }

@@ -322,7 +322,7 @@ class Engine {
     }
     wipe() { native.setOption(this.h, 'wipe', 0) }   // zk_ctx_wipe on every device: prover workspaces and staged inputs zeroed (also done by close() and after a failed prove)
     // params: { nistH: 64 B, tomG: 72 B, tomH: 72 B, secLevel } -- SystemParametersList as affine big-endian coordinates
-    setParams(p) { native.setParams(this.h, p.nistH, p.tomG, p.tomH, p.secLevel || 80); this.params = p; this.auditor = null }   // (zk_ctx_set_params drops the auditor's key)
+    setParams(p) { native.setParams(this.h, p.nistH, p.tomG, p.tomH, p.secLevel || 80); this.params = p; this.auditor = null; this.auditors = null }   // (zk_ctx_set_params drops the auditor's key)
     setRing(keys) { return native.setRing(this.h, Buffer.isBuffer(keys) ? keys : Buffer.concat(keys.map(be32))) }
     // resident rings (include/zkattest.h zk_ctx_add_ring): built once, switched by id without a rebuild
     addRing(keys) { return native.addRing(this.h, Buffer.isBuffer(keys) ? keys : Buffer.concat(keys.map(be32))) }   // -> ring id (not made active)
@@ -466,7 +466,7 @@ class Engine {
     // escrow tags (zk_ctx_set_auditor, zk_escrow_*): "ZKT1", 472 bytes -- ElGamal of keys[i] under the auditor's key with a proof that com[i] opens to it under
     // blinder[i].  setAuditor: the key A as a 72-byte Tom-256 point, again after every setParams; escrowKeygen: A = a g for a 32-byte secret.  Arrays of Buffers
     // -> { tags: Buffer | null per entry, status: Int32Array }.  seeds must be FRESH: never the ones the commitment's proof was made with (default: crypto.randomBytes)
-    setAuditor(key72) { native.setAuditor(this.h, Buffer.from(key72)); this.auditor = Buffer.from(key72).toString('hex') }
+    setAuditor(key72) { native.setAuditor(this.h, Buffer.from(key72)); this.auditor = Buffer.from(key72).toString('hex'); this.auditors = null }
     escrowKeygen(secret32) { return native.escrowKeygen(this.h, Buffer.from(secret32)) }
     escrowProveBatch(keys, com, blinder, seeds) {
         const B = keys.length, cat = (a) => Buffer.concat(a.map((v) => Buffer.from(v)))
@@ -486,6 +486,32 @@ class Engine {
     // zk_rings_escrow_open_batch: one resident ring id per tag (0xffffffff: any resident ring, ascending ids); the active ring is not involved
     ringsEscrowOpenBatch(secret32, tags, ringIds) {
         const r = native.ringsEscrowOpenBatch(this.h, Buffer.from(secret32), Buffer.concat(tags), Buffer.from(Uint32Array.from(ringIds).buffer))
+        return { ring: Array.from(tags, (_, i) => r.ring.readUInt32LE(4 * i)), index: Array.from(tags, (_, i) => r.index.readUInt32LE(4 * i)), status: i32(r.status) }
+    }
+    // threshold opening (zk_auditors_*, zk_ctx_set_auditors): t of n auditors open a tag through 264-byte shares "ZKS1".  auditorsSplitKey: the dealer's split
+    // -> { shares: n 32-byte Buffers, keys: n 72-byte Buffers }; auditorsSetKeys: the share keys, behind setAuditor (which drops them, as setParams does).
+    auditorsSplitKey(secret32, t, n, seed) {
+        const r = native.auditorsSplitKey(this.h, Buffer.from(secret32), t, n, seed || crypto.randomBytes(32))
+        return { shares: Array.from({ length: n }, (_, j) => r.shares.slice(32 * j, 32 * j + 32)), keys: Array.from({ length: n }, (_, j) => r.keys.slice(72 * j, 72 * j + 72)) }
+    }
+    auditorsSetKeys(t, keys) {
+        this.auditors = null
+        native.auditorsSetKeys(this.h, t, Buffer.concat(keys.map((k) => Buffer.from(k))))
+        this.auditors = t + ':' + keys.map((k) => Buffer.from(k).toString('hex')).join('')
+    }
+    auditorsShareBatch(j, shareSecret32, tags, seeds) {   // -> { shares: Buffer | null per tag, status: Int32Array }; seeds must be FRESH (default: crypto.randomBytes)
+        const r = native.auditorsShareBatch(this.h, j, Buffer.from(shareSecret32), Buffer.concat(tags), seeds || crypto.randomBytes(32 * tags.length))
+        const st = i32(r.status)
+        return { shares: Array.from(st, (s, i) => (s === 0 ? r.shares.slice(264 * i, 264 * i + 264) : null)), status: st }
+    }
+    auditorsShareVerifyBatch(tags, shares) {   // -> { ok: boolean[], status: Int32Array }; the auditor's index comes from each share's header
+        const r = native.auditorsShareVerifyBatch(this.h, Buffer.concat(tags), Buffer.concat(shares))
+        return { ok: Array.from(r.ok, (v) => v === 1), status: i32(r.status) }
+    }
+    // shares[s][b]: auditors[s]'s share of tags[b]; one resident ring id per tag (0xffffffff: any resident ring) -> ringsEscrowOpenBatch's result.  It does not verify.
+    auditorsCombineBatch(auditors, tags, shares, ringIds) {
+        const r = native.auditorsCombineBatch(this.h, Buffer.from(Uint32Array.from(auditors).buffer), Buffer.concat(tags), Buffer.concat(shares.map((row) => Buffer.concat(row))),
+            Buffer.from(Uint32Array.from(ringIds).buffer))
         return { ring: Array.from(tags, (_, i) => r.ring.readUInt32LE(4 * i)), index: Array.from(tags, (_, i) => r.index.readUInt32LE(4 * i)), status: i32(r.status) }
     }
     // distinct-key proofs (zk_distinct_*): "ZKD1", 744 bytes -- com1[i] opens to key1[i] under blinder1[i], com2[i] to key2[i] under blinder2[i], and the keys differ;
@@ -1303,6 +1329,82 @@ async function openEscrowTags(params, secret, keys, tags) {
     return r.index.map((w, i) => { if (r.status[i] !== 0) throw statusError(r.status[i]); return w === 0xffffffff ? null : w })
 }
 
+// ---------------------------------------------------------------- threshold opening: t of n auditors open a tag (include/zkattest.h: zk_auditors_*)
+// An EscrowShare keeps the engine's ZKS1 bytes and materialises its members (j: the auditor's index; D, U1, U2: Points; s: a Scalar).
+class EscrowShare {
+    constructor(bytes) {
+        if (!(Buffer.isBuffer(bytes) && bytes.length === 264 && bytes.slice(0, 4).toString('latin1') === 'ZKS1' && bytes.readUInt32BE(4) === 264 && bytes.readUInt32BE(12) === 0))
+            throw new Error('error deserializing EscrowShare')
+        this.bytes = bytes
+    }
+    _pt(o) { return new Point(tomEdwards256, fromBE(this.bytes.slice(o, o + 36)), fromBE(this.bytes.slice(o + 36, o + 72))) }
+    get j() { return this.bytes.readUInt32BE(8) }
+    get D() { return this._pt(16) }
+    get U1() { return this._pt(88) }
+    get U2() { return this._pt(160) }
+    get s() { return new Scalar(tomEdwards256, fromBE(this.bytes.slice(232, 264))) }
+    eq(o) { return o instanceof EscrowShare && this.bytes.equals(o.bytes) }
+}
+// `auditors` names a t-of-n set in every call below: { key: the auditor's key A, t, keys: the share keys A_1 .. A_n } (Points or 72 bytes).  Inside a queued
+// unit of the engine: the set is the one the engine holds -- it is checked against A once per set
+function useAuditors(engine, auditors) {
+    useAuditor(engine, auditors.key)
+    const keys = auditors.keys.map(comBytes)
+    if (engine.auditors !== auditors.t + ':' + keys.map((k) => k.toString('hex')).join('')) engine.auditorsSetKeys(auditors.t, keys)
+}
+const shareBytes = (s) => (s instanceof EscrowShare ? s.bytes : new EscrowShare(s).bytes)
+const tagBytes = (t) => (t instanceof EscrowTag ? t.bytes : new EscrowTag(t).bytes)
+// splitAuditorKey(params, secret, t, n): the dealer's Shamir split of the auditor's secret -> { key: A (a Point), t, keys: A_1 .. A_n (Points), shares: a_1 .. a_n
+// (32-byte Buffers, one per auditor) }; the first three members are the `auditors` of the other calls.  The dealer sees the secret: run it where that is acceptable.
+async function splitAuditorKey(params, secret, t, n) {
+    const a = scalarBytes(secret)
+    const r = await engineFor(paramsOf(params), null).run((engine) => ({ key: engine.escrowKeygen(a), split: engine.auditorsSplitKey(a, t, n) }))
+    const pt = (k) => new Point(tomEdwards256, fromBE(k.slice(0, 36)), fromBE(k.slice(36)))
+    return { key: pt(r.key), t, keys: r.split.keys.map(pt), shares: r.split.shares }
+}
+// shareEscrowTags(params, auditors, j, shareSecret, tags): auditor j's shares of the tags -> EscrowShare[].  Throws when the share secret is not A_j's.
+async function shareEscrowTags(params, auditors, j, shareSecret, tags) {
+    if (!tags.length) return []
+    const raw = tags.map(tagBytes)
+    const r = await engineFor(paramsOf(params), null).run((engine) => { useAuditors(engine, auditors); return engine.auditorsShareBatch(j, scalarBytes(shareSecret), raw) })
+    return r.shares.map((s, i) => { if (r.status[i] !== 0) throw statusError(r.status[i]); return new EscrowShare(s) })
+}
+// verifyEscrowShares(params, auditors, tags, shares): one share per tag -> boolean[]; what does not deserialise throws.  Call it on every share before combining.
+async function verifyEscrowShares(params, auditors, tags, shares) {
+    if (shares.length !== tags.length) throw new RangeError('verifyEscrowShares: one share per tag')
+    if (!tags.length) return []
+    const rawT = tags.map(tagBytes), rawS = shares.map(shareBytes)
+    const r = await engineFor(paramsOf(params), null).run((engine) => { useAuditors(engine, auditors); return engine.auditorsShareVerifyBatch(rawT, rawS) })
+    r.status.forEach((st) => { if (st !== 0) throw statusError(st) })
+    return r.ok
+}
+// combineEscrowShares(params, auditors, keys, tags, shares): shares[s][b] is one auditor's share of tags[b], t rows of different auditors (their indices come
+// from the shares) -> what openEscrowTags gives for the undivided secret: with one key list the index or null per tag, with one key list per tag
+// { ring, index } or null.  It does NOT verify: call verifyEscrowShares first.
+async function combineEscrowShares(params, auditors, keys, tags, shares) {
+    if (shares.length !== auditors.t || shares.some((row) => row.length !== tags.length)) throw new RangeError('combineEscrowShares: t rows of one share per tag')
+    if (!tags.length) return []
+    const raw = tags.map(tagBytes), rows = shares.map((row) => row.map(shareBytes)), who = rows.map((row) => row[0].readUInt32BE(8))
+    const lists = isKeyLists(keys), perTag = lists ? keys : tags.map(() => keys)
+    if (perTag.length !== tags.length) throw new RangeError('combineEscrowShares: one key list per tag')
+    const { rings, ringOfEntry } = memberRingsOf(perTag, false)
+    const { withRings, capacity } = engineFor(paramsOf(params), perTag[0])
+    const out = new Array(tags.length), per = capacity()
+    for (let g = 0; g < rings.length; g += per) {
+        const sel = []
+        for (let i = 0; i < tags.length; i++) if (ringOfEntry[i] >= g && ringOfEntry[i] < g + per) sel.push(i)
+        const r = await withRings(rings.slice(g, g + per), (engine, ids) => {
+            useAuditors(engine, auditors)
+            return engine.auditorsCombineBatch(who, sel.map((i) => raw[i]), rows.map((row) => sel.map((i) => row[i])), sel.map((i) => ids[ringOfEntry[i] - g]))
+        })
+        sel.forEach((i, k) => {
+            if (r.status[k] !== 0) throw statusError(r.status[k])
+            out[i] = r.index[k] === 0xffffffff ? null : lists ? { ring: ringOfEntry[i], index: r.index[k] } : r.index[k]
+        })
+    }
+    return out
+}
+
 // ---------------------------------------------------------------- distinct-key proofs: two key commitments hide different keys (src/commit/mult.ts:26-175)
 // A DistinctProof keeps the engine's ZKD1 bytes (include/zkattest.h) and materialises C_w and the reference's MultProof members (six Points, seven Scalars).
 class DistinctProof {
@@ -1453,6 +1555,6 @@ async function verifyQuorum(params, msgHashes, keys, proof) {
     return r.ok[0]
 }
 
-module.exports = { proveEscrowTag, verifyEscrowTag, proveEscrowTags, verifyEscrowTags, openEscrowTags, escrowAuditorKey, EscrowTag, proveQuorum, verifyQuorum, QuorumProof, proveDifferentKeys, verifyDifferentKeys, proveDifferentKeysBatch, verifyDifferentKeysBatch, distinctPairs, DistinctProof, proveSameKey, verifySameKey, proveSameKeys, verifySameKeys, keyCommitment, keyCommitments, LinkProof, reringSignatureLists, keyBlinders, proveMembership, verifyMembership, proveMemberships, verifyMemberships, proveMembershipLists, verifyMembershipLists, GKProof, Commitment, commit, screenSignatureLists, findKey, SCREEN, WHICH_NONE, recoverSignatureLists, recoverKey, RECOVER, verifySignatureLists, proveSignatureLists, _ringGenerations, setVerifyLevel, getVerifyLevel, setVerifyReps, getVerifyReps, generateParamsList, generateParamsListHardened, keyToInt, proveSignatureList, verifySignatureList, proveSignatureListBatch, verifySignatureListBatch,
+module.exports = { splitAuditorKey, shareEscrowTags, verifyEscrowShares, combineEscrowShares, EscrowShare, proveEscrowTag, verifyEscrowTag, proveEscrowTags, verifyEscrowTags, openEscrowTags, escrowAuditorKey, EscrowTag, proveQuorum, verifyQuorum, QuorumProof, proveDifferentKeys, verifyDifferentKeys, proveDifferentKeysBatch, verifyDifferentKeysBatch, distinctPairs, DistinctProof, proveSameKey, verifySameKey, proveSameKeys, verifySameKeys, keyCommitment, keyCommitments, LinkProof, reringSignatureLists, keyBlinders, proveMembership, verifyMembership, proveMemberships, verifyMemberships, proveMembershipLists, verifyMembershipLists, GKProof, Commitment, commit, screenSignatureLists, findKey, SCREEN, WHICH_NONE, recoverSignatureLists, recoverKey, RECOVER, verifySignatureLists, proveSignatureLists, _ringGenerations, setVerifyLevel, getVerifyLevel, setVerifyReps, getVerifyReps, generateParamsList, generateParamsListHardened, keyToInt, proveSignatureList, verifySignatureList, proveSignatureListBatch, verifySignatureListBatch,
     writeJson, readJson, writeJsonBatch, readJsonBatch, SignatureProofList, SystemParametersList, PedersenParams, generatePedersenParams, p256, tomEdwards256, ALL_GROUPS,
     Group, Point, Scalar, Engine, shutdown, setWireLayout, getWireLayout, setOption, native }

@@ -1564,6 +1564,134 @@ static napi_value EscrowOpenBatchRings(napi_env env, napi_callback_info info) {
     free(buf);
     return v;
 }
+/* Threshold opening (include/zkattest.h: zk_auditors_*, zk_ctx_set_auditors), on the pool's first context like the escrow calls.
+ * (h, secret: 32, t, n, seed: 32 -- FRESH) -> {shares: n x 32, keys: n x 72}: the dealer's split */
+static napi_value AuditorsSplitKey(napi_env env, napi_callback_info info) {
+    napi_value argv[5];
+    if (!get_args(env, info, 5, argv)) return NULL;
+    Handle *h = get_handle(env, argv[0], 0);
+    uint8_t *secret, *seed;
+    size_t ls, ld;
+    uint32_t t, n;
+    if (!h || !get_bytes(env, argv[1], &secret, &ls) || !get_bytes(env, argv[4], &seed, &ld)) return NULL;
+    NAPI_OK(napi_get_value_uint32(env, argv[2], &t));
+    NAPI_OK(napi_get_value_uint32(env, argv[3], &n));
+    if (ls != 32 || ld != 32 || n > 16) {
+        napi_throw_range_error(env, NULL, "auditorsSplitKey: a 32-byte secret, 1 <= t <= n <= 16 and a 32-byte seed");
+        return NULL;
+    }
+    zk_ctx *c = zk_pool_ctx(h->pool, 0);
+    uint8_t shares[32 * 16], keys[72 * 16];
+    zk_rng rng = {ZK_RNG_SEED, seed, 0};
+    zk_status st = zk_auditors_split_key(c, secret, t, n, &rng, shares, keys);
+    napi_value v = NULL;
+    if (st != ZK_OK) throw_text(env, st, zk_last_error(c));
+    else if (napi_create_object(env, &v) == napi_ok) set_prop(env, v, "shares", new_buffer(env, shares, 32 * (size_t)n)), set_prop(env, v, "keys", new_buffer(env, keys, 72 * (size_t)n));
+    for (volatile uint8_t *p = shares; p < shares + sizeof shares; p++) *p = 0;
+    return v;
+}
+/* (h, t, keys: n x 72) -> undefined: the share keys, checked against the auditor's key */
+static napi_value AuditorsSetKeys(napi_env env, napi_callback_info info) {
+    napi_value argv[3];
+    if (!get_args(env, info, 3, argv)) return NULL;
+    Handle *h = get_handle(env, argv[0], 0);
+    uint8_t *keys;
+    size_t lk;
+    uint32_t t;
+    if (!h || !get_bytes(env, argv[2], &keys, &lk)) return NULL;
+    NAPI_OK(napi_get_value_uint32(env, argv[1], &t));
+    if (lk % 72 || lk == 0 || lk > 72 * 16) {
+        napi_throw_range_error(env, NULL, "auditorsSetKeys: 1 to 16 Tom-256 points of 72 bytes");
+        return NULL;
+    }
+    zk_ctx *c = zk_pool_ctx(h->pool, 0);
+    zk_status st = zk_ctx_set_auditors(c, t, (uint32_t)(lk / 72), keys);
+    if (st != ZK_OK) throw_text(env, st, zk_last_error(c));
+    return NULL;
+}
+/* (h, j, shareSecret: 32, tags: B x 472, seeds: B x 32 -- FRESH) -> {shares: B x 264 (zeros where status != 0), status: B i32 LE} */
+static napi_value AuditorsShareBatch(napi_env env, napi_callback_info info) {
+    napi_value argv[5];
+    if (!get_args(env, info, 5, argv)) return NULL;
+    Handle *h = get_handle(env, argv[0], 0);
+    uint8_t *secret, *tags, *seeds;
+    size_t ls, lt, ld;
+    uint32_t j;
+    if (!h || !get_bytes(env, argv[2], &secret, &ls) || !get_bytes(env, argv[3], &tags, &lt) || !get_bytes(env, argv[4], &seeds, &ld)) return NULL;
+    NAPI_OK(napi_get_value_uint32(env, argv[1], &j));
+    const size_t B = lt / zk_escrow_tag_size();
+    if (ls != 32 || lt != zk_escrow_tag_size() * B || ld != 32 * B) {
+        napi_throw_range_error(env, NULL, "auditorsShareBatch: a 32-byte share secret, 472-byte tags and 32 seed bytes per tag");
+        return NULL;
+    }
+    zk_ctx *c = zk_pool_ctx(h->pool, 0);
+    const uint64_t size = zk_auditors_share_size();
+    uint8_t *buf = (uint8_t *)xmalloc(env, (size + 4) * B + 8);
+    if (!buf) return NULL;
+    int32_t *status = (int32_t *)buf;
+    uint8_t *out = buf + 4 * B;
+    zk_rng rng = {ZK_RNG_SEED, seeds, 0};
+    zk_status st = zk_auditors_share_batch(c, B, j, secret, tags, &rng, out, size * B, status);
+    napi_value v = NULL;
+    if (st != ZK_OK) throw_text(env, st, zk_last_error(c));
+    else if (napi_create_object(env, &v) == napi_ok) set_prop(env, v, "shares", new_buffer(env, out, size * B)), set_prop(env, v, "status", new_buffer(env, status, 4 * B));
+    free(buf);
+    return v;
+}
+/* (h, tags: B x 472, shares: B x 264) -> {ok: B bytes, status: B i32 LE} */
+static napi_value AuditorsShareVerifyBatch(napi_env env, napi_callback_info info) {
+    napi_value argv[3];
+    if (!get_args(env, info, 3, argv)) return NULL;
+    Handle *h = get_handle(env, argv[0], 0);
+    uint8_t *tags, *shares;
+    size_t lt, ls;
+    if (!h || !get_bytes(env, argv[1], &tags, &lt) || !get_bytes(env, argv[2], &shares, &ls)) return NULL;
+    const size_t B = lt / zk_escrow_tag_size();
+    if (lt != zk_escrow_tag_size() * B || ls != zk_auditors_share_size() * B) {
+        napi_throw_range_error(env, NULL, "auditorsShareVerifyBatch: one 472-byte tag and one 264-byte share per entry");
+        return NULL;
+    }
+    zk_ctx *c = zk_pool_ctx(h->pool, 0);
+    uint8_t *buf = (uint8_t *)xmalloc(env, 5 * B + 8);
+    if (!buf) return NULL;
+    int32_t *status = (int32_t *)buf;
+    uint8_t *ok = buf + 4 * B;
+    zk_status st = zk_auditors_share_verify_batch(c, B, tags, shares, ok, status);
+    napi_value v = NULL;
+    if (st != ZK_OK) throw_text(env, st, zk_last_error(c));
+    else if (napi_create_object(env, &v) == napi_ok) set_prop(env, v, "ok", new_buffer(env, ok, B)), set_prop(env, v, "status", new_buffer(env, status, 4 * B));
+    free(buf);
+    return v;
+}
+/* (h, auditors: t u32 LE, tags: B x 472, shares: t x B x 264 slot-major, ringIds: B u32 LE, 0xffffffff = any resident ring) -> {ring: B u32 LE, index: B u32 LE
+ * (0xffffffff: nobody), status: B i32 LE}; the active ring is not involved */
+static napi_value AuditorsCombineBatch(napi_env env, napi_callback_info info) {
+    napi_value argv[5];
+    if (!get_args(env, info, 5, argv)) return NULL;
+    Handle *h = get_handle(env, argv[0], 0);
+    uint8_t *aud, *tags, *shares, *ids;
+    size_t la, lt, ls, li;
+    if (!h || !get_bytes(env, argv[1], &aud, &la) || !get_bytes(env, argv[2], &tags, &lt) || !get_bytes(env, argv[3], &shares, &ls) || !get_bytes(env, argv[4], &ids, &li)) return NULL;
+    const size_t B = lt / zk_escrow_tag_size(), t = la / 4;
+    if (la % 4 || t < 1 || t > 16 || lt != zk_escrow_tag_size() * B || ls != zk_auditors_share_size() * B * t || li != 4 * B) {
+        napi_throw_range_error(env, NULL, "auditorsCombineBatch: 1 to 16 u32 auditors, 472-byte tags, one 264-byte share per auditor and tag, one u32 ring id per tag");
+        return NULL;
+    }
+    zk_ctx *c = zk_pool_ctx(h->pool, 0);
+    uint8_t *buf = (uint8_t *)xmalloc(env, 16 * B + 64 + 8);
+    if (!buf) return NULL;
+    uint32_t *audw = (uint32_t *)buf;   /* (a Buffer's bytes need not be 4-byte aligned) */
+    int32_t *status = (int32_t *)(buf + 64);
+    uint32_t *index = (uint32_t *)(buf + 64 + 4 * B), *ring = (uint32_t *)(buf + 64 + 8 * B), *idw = (uint32_t *)(buf + 64 + 12 * B);
+    memcpy(audw, aud, la), memcpy(idw, ids, 4 * B);
+    zk_status st = zk_auditors_combine_batch(c, B, (uint32_t)t, audw, tags, shares, idw, ring, index, status);
+    napi_value v = NULL;
+    if (st != ZK_OK) throw_text(env, st, zk_last_error(c));
+    else if (napi_create_object(env, &v) == napi_ok)
+        set_prop(env, v, "ring", new_buffer(env, ring, 4 * B)), set_prop(env, v, "index", new_buffer(env, index, 4 * B)), set_prop(env, v, "status", new_buffer(env, status, 4 * B));
+    free(buf);
+    return v;
+}
 /* Distinct-key proofs (include/zkattest.h: zk_distinct_*), on the pool's first context like the link calls; no ring takes part.
  * (h, key1: B x 32, com1: B x 72, blinder1: B x 32, key2: B x 32, com2: B x 72, blinder2: B x 32, seeds: B x 32 -- FRESH) -> {proofs: B x 744 (zeros where
  * status != 0), status: B i32 LE} */
@@ -1788,7 +1916,9 @@ static napi_value Init(napi_env env, napi_value exports) {
                {"escrowVerifyBatch", EscrowVerifyBatch}, {"escrowOpenBatch", EscrowOpenBatch},
                {"quorumProveBatch", QuorumProveBatch}, {"quorumVerifyBatch", QuorumVerifyBatch},
                {"ringsQuorumProveBatch", QuorumProveBatchRings}, {"ringsQuorumVerifyBatch", QuorumVerifyBatchRings},
-               {"ringsEscrowOpenBatch", EscrowOpenBatchRings}};
+               {"ringsEscrowOpenBatch", EscrowOpenBatchRings},
+               {"auditorsSplitKey", AuditorsSplitKey}, {"auditorsSetKeys", AuditorsSetKeys}, {"auditorsShareBatch", AuditorsShareBatch},
+               {"auditorsShareVerifyBatch", AuditorsShareVerifyBatch}, {"auditorsCombineBatch", AuditorsCombineBatch}};
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;
         if (napi_create_function(env, fns[i].name, NAPI_AUTO_LENGTH, fns[i].fn, NULL, &f) != napi_ok) return NULL;

@@ -984,6 +984,74 @@ zk_status zk_rings_escrow_open_batch(zk_ctx *ctx, uint64_t B, const uint8_t secr
 zk_status zk_rings_escrow_open_batch_device(zk_ctx *ctx, uint64_t B, const void *d_secret_be32, const void *d_tags, const void *d_ring_ids /*u32[B]*/,
                                             void *d_ring_out_u32 /*u32[B]*/, void *d_index_u32 /*u32[B]*/, void *d_per_tag_status /*i32[B]*/);
 
+/* ---- threshold escrow opening: t of n auditors open a tag.  Anyone who knows a can open every tag made for A (above); here a is split once, by a dealer,
+ * into Shamir shares a_1 .. a_n, and opening takes t of the n auditors.  From a tag, auditor j makes a partial opening D_j = a_j E1 and a Chaum-Pedersen proof
+ * (a share, "ZKS1") that D_j was made with the secret behind the published key A_j = a_j g.  Anyone can verify a share; anyone who holds t verified shares of a
+ * tag can combine them into the ring and index zk_rings_escrow_open_batch gives.  Provers, tags, verifiers and the single-auditor calls do not change: a ZKT1
+ * tag made for A is opened either way.  With q the group order and 1 <= t <= n <= 16:
+ *     split:    f(X) = a + c_1 X + ... + c_{t-1} X^{t-1};  a_j = f(j) mod q,  A_j = a_j g,  j = 1..n
+ *     share:    D = a_j E1    U1 = k g    U2 = k E1    c = hashPoints([A_j, E1, D, U1, U2])    s = k - c a_j  (mod q)
+ *               (the ZKL1 challenge's hash and 80-bit truncation, five points, this order)
+ *     verify:   s g + c A_j - U1 = O   and   s E1 + c D - U2 = O
+ *     combine:  lambda_j = prod_{m in S, m != j} m / (m - j)  (mod q);   M = 4 (E2 - sum_{j in S} lambda_j D_j)   for a set S of exactly t different auditors
+ * Wire format "ZKS1", 264 bytes:
+ *     header 16 B : "ZKS1" | total_len u32 big-endian (= 264) | j u32 big-endian | 0 u32
+ *     D, U1, U2   : three Tom-256 points, 72 bytes each, as the points lie in ZKT1
+ *     s           : 32 bytes big-endian
+ * zk_auditors_split_key: the dealer's call; it works as zk_escrow_keygen does and needs parameters only (ZK_E_BUFFER before zk_ctx_set_params).  a is REDUCED
+ *   mod q; the coefficients c_1 .. c_{t-1} are rnd(q) draws, fills 0 .. t-2 of the call's rng under the randomness contract (rng->data: one 32-byte seed, or
+ *   one stream of stride_blocks blocks), rejection handled as in zk_link_prove_batch; ZK_E_RNG_EXHAUSTED, nothing written, for a stream that does not hold
+ *   them; ZK_E_ARG unless 1 <= t <= n <= 16.  A share a_j = 0 is possible only with negligible probability: it is returned as it is, and
+ *   zk_ctx_set_auditors refuses its key.  Everything the call stages is witness-flagged and zeroed before it returns.  The dealer sees a: distributed key
+ *   generation is not provided.
+ * zk_ctx_set_auditors: the n share keys.  It needs an auditor key (zk_ctx_set_auditor), else ZK_E_BUFFER; ZK_E_ARG unless 1 <= t <= n <= 16.  Every A_j is
+ *   checked as zk_ctx_set_auditor checks A (ZK_E_BAD_ENCODING; ZK_E_ARG for the identity or q A_j != O), and the keys must lie on one polynomial of degree
+ *   t - 1 through A: interpolating A_1 .. A_t at 0 gives A and at every m > t gives A_m -- n - t + 1 sums through the combine's ladder, compared as canonical
+ *   bytes.  A mismatch is ZK_E_OPENING, and nothing is kept: a call that fails behind its argument checks leaves the context without a set.
+ *   zk_ctx_set_auditor and zk_ctx_set_params drop the set.
+ * zk_auditors_share_batch: auditor j's shares of B tags.  Call level, in this order: ZK_E_BUFFER without an auditor set; ZK_E_ARG for j outside 1..n;
+ *   ZK_E_OPENING with nothing written when a_j g is not A_j; ZK_E_BUFFER for out_cap < 264 B.  Per tag, in this order: ZK_E_BAD_ENCODING for the tag's header
+ *   or E1; ZK_E_RNG_EXHAUSTED.  k = rnd(q) is fill 0 of the tag's rng.  A failed share is 264 zero bytes and touches no neighbour.  Both a_j E1 and k E1 go
+ *   through the masked ladder of the single-auditor opening: no branch and no address depends on a bit of a_j or k, in every build; a refused tag walks the
+ *   identity.  U1 comes from the (g, h) comb with r = 0.  The bytes depend on neither the comb widths, nor the mode (h plays no part), nor the uniform build.
+ * zk_auditors_share_verify_batch: a share against the tag it belongs to and the context's A_j, j from the share's header.  Per share ZK_E_BAD_ENCODING for the
+ *   share's header (magic, total_len != 264, a nonzero reserved word, j outside 1..n), the tag's header, or any of the points E1, D, U1, U2 non-canonical or
+ *   off the curve.  A scalar s >= q is REDUCED, not refused.  Otherwise the status is 0 and ok = 1 iff both relations hold exactly; there is no verifier
+ *   randomness.  Relation 1 is one comb opening plus the link verifier's short ladder on A_j, relation 2 the two-base ladder of the distinct-key verifier.
+ * zk_auditors_combine_batch: shares holds t slots of B shares, slot-major: share b of slot s lies at (s B + b) x 264 and belongs to auditors[s].  Call level:
+ *   ZK_E_ARG when t is not the context's threshold, or when auditors holds a 0, a value above n, or a duplicate; the rest of the call-level rules are
+ *   zk_rings_escrow_open_batch's: the ACTIVE ring is neither read nor changed, and missing point indexes are built first.  Per tag, in this order: ZK_E_ARG
+ *   for a ring id that is neither resident nor ZK_ESCROW_RING_ANY; ZK_E_BAD_ENCODING for the tag's header, E1 or E2, for any slot's share header (j !=
+ *   auditors[s] included), or for a D that is non-canonical or off the curve; else 0.  M is looked up exactly as zk_rings_escrow_open_batch looks up its
+ *   point: lowest index, both outputs 0xffffffff where there is none.  The lambda_j are computed once per call; they are public.  One lane per tag walks
+ *   sum lambda_j D_j as one joint left-to-right ladder that shares the 256 doublings; its branches on the bits of lambda are wave-uniform.  The factor 4 is
+ *   part of the rule for the reason it is in the single-auditor rule: E1, and a D_j that a dishonest auditor adjusted, may carry a component of order 2 or 4.
+ * Combining does not verify, as opening does not: run zk_auditors_share_verify_batch first.  A wrong D_j then shows as "no member" or, for a party that
+ *   already knows the key, as whatever member it chooses.  A share reveals a_j E1 for that tag only.
+ * Call-level rules are the link calls': ZK_E_ARG for NULL pointers, B >= 2^32 and while streamed jobs are queued; B = 0 is ZK_OK; chunks on the context's
+ *   lanes; the _device forms take every pointer (auditors and rng->data included) in this context's HBM, 4-byte aligned, else ZK_E_ARG.  The staged a_j, k and
+ *   the RNG fills are witness-derived: zk_ctx_wipe, zk_ctx_destroy and a failed call zero them.  zk_last_timing reports "rng_prepass", "escrow_open",
+ *   "share_front", "tom_commit", "share_ladder", "tom_normalize", "hash", "share_respond" (share), "share_parse", "tom_commit", "share_relations" (verify)
+ *   and "escrow_index_build", "combine_ladder", "tom_normalize", "escrow_lookup" (combine).
+ * Not provided: distributed key generation, resharing, pool, streamed and JSON forms.  DESIGN.md section 5h''. */
+uint64_t zk_auditors_share_size(void);   /* 264 */
+zk_status zk_auditors_split_key(zk_ctx *ctx, const uint8_t secret_be32[32], uint32_t t, uint32_t n, const zk_rng *rng, uint8_t *shares_be32 /*nx32*/,
+                                uint8_t *share_keys_xy72 /*nx72*/);
+zk_status zk_ctx_set_auditors(zk_ctx *ctx, uint32_t t, uint32_t n, const uint8_t *share_keys_xy72 /*nx72*/);
+zk_status zk_auditors_share_batch(zk_ctx *ctx, uint64_t B, uint32_t j, const uint8_t share_secret_be32[32], const uint8_t *tags /*Bx472*/, const zk_rng *rng,
+                                  uint8_t *out /*Bx264*/, uint64_t out_cap, int32_t *per_tag_status /*B*/);
+zk_status zk_auditors_share_batch_device(zk_ctx *ctx, uint64_t B, uint32_t j, const void *d_share_secret_be32, const void *d_tags, const zk_rng *rng_device,
+                                         void *d_out, uint64_t out_cap, void *d_per_tag_status /*i32[B]*/);
+zk_status zk_auditors_share_verify_batch(zk_ctx *ctx, uint64_t B, const uint8_t *tags /*Bx472*/, const uint8_t *shares /*Bx264*/, uint8_t *ok /*B*/,
+                                         int32_t *per_share_status /*B*/);
+zk_status zk_auditors_share_verify_batch_device(zk_ctx *ctx, uint64_t B, const void *d_tags, const void *d_shares, void *d_ok, void *d_per_share_status /*i32[B]*/);
+zk_status zk_auditors_combine_batch(zk_ctx *ctx, uint64_t B, uint32_t t, const uint32_t *auditors_u32 /*t*/, const uint8_t *tags /*Bx472*/,
+                                    const uint8_t *shares /*txBx264*/, const uint32_t *ring_ids /*B*/, uint32_t *ring_out_u32 /*B*/, uint32_t *index_u32 /*B*/,
+                                    int32_t *per_tag_status /*B*/);
+zk_status zk_auditors_combine_batch_device(zk_ctx *ctx, uint64_t B, uint32_t t, const void *d_auditors_u32 /*u32[t]*/, const void *d_tags, const void *d_shares,
+                                           const void *d_ring_ids /*u32[B]*/, void *d_ring_out_u32 /*u32[B]*/, void *d_index_u32 /*u32[B]*/,
+                                           void *d_per_tag_status /*i32[B]*/);
+
 /* ---- two (or more) batches in flight on one context.  zk_prove_batch / zk_verify_batch are synchronous: each call pays its own head
  * (no byte of a chunk exists before its stage 1 is over) and its own tail (the copies of the last slices, with nothing left to
  * hide them).  The submit / wait pair splits a call so that the pipeline keeps running ACROSS calls: submit stages the inputs and

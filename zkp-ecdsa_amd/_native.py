@@ -42,6 +42,8 @@ SYMBOLS = [
     'zk_ctx_set_auditor', 'zk_escrow_keygen', 'zk_escrow_tag_size', 'zk_escrow_prove_batch', 'zk_escrow_prove_batch_device', 'zk_escrow_verify_batch',
     'zk_escrow_verify_batch_device', 'zk_escrow_open_batch', 'zk_escrow_open_batch_device',
     'zk_rings_escrow_open_batch', 'zk_rings_escrow_open_batch_device',
+    'zk_auditors_share_size', 'zk_auditors_split_key', 'zk_ctx_set_auditors', 'zk_auditors_share_batch', 'zk_auditors_share_batch_device',
+    'zk_auditors_share_verify_batch', 'zk_auditors_share_verify_batch_device', 'zk_auditors_combine_batch', 'zk_auditors_combine_batch_device',
     'zk_test_field_op', 'zk_test_tom_commit', 'zk_test_p256_fixed_mul', 'zk_test_sha256', 'zk_test_rng_draws', 'zk_test_exp_sum',
 ]
 
@@ -222,6 +224,17 @@ def lib():
         # ... against any resident ring, through the rings' resident point indexes: one ring id per tag
         L.zk_rings_escrow_open_batch.argtypes = [vp, u64, C.c_char_p, C.c_char_p, vp, vp, vp, vp]
         L.zk_rings_escrow_open_batch_device.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp]
+        # threshold opening ("ZKS1"): t of n auditors open a tag through verifiable shares
+        L.zk_auditors_share_size.argtypes = []
+        L.zk_auditors_share_size.restype = u64
+        L.zk_auditors_split_key.argtypes = [vp, C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(ZkRng), vp, vp]
+        L.zk_ctx_set_auditors.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_char_p]
+        L.zk_auditors_share_batch.argtypes = [vp, u64, C.c_uint32, C.c_char_p, C.c_char_p, C.POINTER(ZkRng), vp, u64, vp]
+        L.zk_auditors_share_batch_device.argtypes = [vp, u64, C.c_uint32, vp, vp, C.POINTER(ZkRng), vp, u64, vp]
+        L.zk_auditors_share_verify_batch.argtypes = [vp, u64, C.c_char_p, C.c_char_p, vp, vp]
+        L.zk_auditors_share_verify_batch_device.argtypes = [vp, u64, vp, vp, vp, vp]
+        L.zk_auditors_combine_batch.argtypes = [vp, u64, C.c_uint32, vp, C.c_char_p, C.c_char_p, vp, vp, vp, vp]
+        L.zk_auditors_combine_batch_device.argtypes = [vp, u64, C.c_uint32, vp, vp, vp, vp, vp, vp, vp]
         L.zk_proof_key_commitments.argtypes = [vp, u64, C.c_char_p, vp, vp, vp]
         L.zk_proof_key_commitments_device.argtypes = [vp, u64, vp, vp, vp, vp]
         L.zk_ring_digest.argtypes = [vp, vp]
@@ -1434,6 +1447,88 @@ class Engine:
 
     def escrow_open_batch_rings_device(self, B, d_secret, d_tags, d_ring_ids, d_ring_out, d_index, d_status):
         self._chk(self.L.zk_rings_escrow_open_batch_device(self.h, B, d_secret, d_tags, d_ring_ids, d_ring_out, d_index, d_status))
+
+    # ---- threshold opening (zk_ctx_set_auditors, zk_auditors_*): t of n auditors open a tag through verifiable shares ("ZKS1", 264 bytes)
+    def auditors_share_size(self):
+        return int(self.L.zk_auditors_share_size())
+
+    def auditors_split_key(self, secret_be32, t, n, seed=None, stream=None, stream_blocks=0):
+        """zk_auditors_split_key: the dealer's Shamir split of the auditor secret a.  Returns (shares: n 32-byte scalars a_j = f(j); keys: n 72-byte points
+        A_j = a_j g).  seed: 32 bytes (fresh; os.urandom where neither is given), or stream: stream_blocks 32-byte blocks."""
+        if len(secret_be32) != 32:
+            raise ValueError('the secret is 32 bytes')
+        if seed is None and stream is None:
+            seed = os.urandom(32)
+        rng, _keep = self._rng(1, seed, stream, stream_blocks)
+        shares, keys = C.create_string_buffer(32 * 16), C.create_string_buffer(72 * 16)
+        self._chk(self.L.zk_auditors_split_key(self.h, bytes(secret_be32), t, n, C.byref(rng), shares, keys))
+        return [shares.raw[32 * j:32 * j + 32] for j in range(n)], [keys.raw[72 * j:72 * j + 72] for j in range(n)]
+
+    def set_auditors(self, t, keys):
+        """zk_ctx_set_auditors: the share keys A_1 .. A_n (72 bytes each) of a t-of-n opening; they must interpolate to the context's auditor key"""
+        n = len(keys)
+        if any(len(k) != 72 for k in keys):
+            raise ValueError('a share key is a 72-byte Tom-256 point')
+        self._chk(self.L.zk_ctx_set_auditors(self.h, t, n, b''.join(bytes(k) for k in keys) if n else bytes(72)))
+
+    def _escrow_tags_blob(self, tags):
+        size = self.escrow_tag_size()
+        if any(len(t) != size for t in tags):
+            raise ValueError('an escrow tag is %d bytes' % size)
+        return b''.join(tags) if tags else bytes(size)
+
+    def auditors_share_batch(self, j, share_secret_be32, tags, seeds=None, streams=None, stream_blocks=0, cap=None):
+        """zk_auditors_share_batch: auditor j's shares of the tags.  Returns (shares: list of 264-byte strings, None where the status is not 0; statuses).
+        self.share_last_raw keeps the B slots as the call wrote them, and cap overrides the out_cap handed to the call, as escrow_prove_batch has them."""
+        B = len(tags)
+        if len(share_secret_be32) != 32:
+            raise ValueError('the share secret is 32 bytes')
+        if seeds is None and streams is None:
+            seeds = os.urandom(32 * B)
+        rng, _keep = self._rng(B, seeds, streams, stream_blocks)
+        size = self.auditors_share_size()
+        out = C.create_string_buffer(max(size * B, 1))
+        st = (C.c_int32 * max(B, 1))()
+        self._chk(self.L.zk_auditors_share_batch(self.h, B, j, bytes(share_secret_be32), self._escrow_tags_blob(tags), C.byref(rng), out, size * B if cap is None else cap, st))
+        raw = out.raw
+        self.share_last_raw = raw[:size * B]
+        return [raw[size * b:size * (b + 1)] if st[b] == 0 else None for b in range(B)], list(st)[:B]
+
+    def auditors_share_batch_device(self, B, j, d_share_secret, d_tags, d_rng, d_out, out_cap, d_status, mode=0, stride_blocks=0):
+        rng = ZkRng(mode, d_rng, stride_blocks)
+        self._chk(self.L.zk_auditors_share_batch_device(self.h, B, j, d_share_secret, d_tags, C.byref(rng), d_out, out_cap, d_status))
+
+    def auditors_share_verify_batch(self, tags, shares):
+        """zk_auditors_share_verify_batch for B (tag, share) pairs; the auditor's index comes from each share's header.  Returns (ok list, status list)."""
+        B = len(tags)
+        size = self.auditors_share_size()
+        if len(shares) != B or any(len(s) != size for s in shares):
+            raise ValueError('every tag has one share of %d bytes' % size)
+        ok = (C.c_uint8 * max(B, 1))()
+        st = (C.c_int32 * max(B, 1))()
+        self._chk(self.L.zk_auditors_share_verify_batch(self.h, B, self._escrow_tags_blob(tags), b''.join(shares) if B else bytes(size), ok, st))
+        return list(ok)[:B], list(st)[:B]
+
+    def auditors_share_verify_batch_device(self, B, d_tags, d_shares, d_ok, d_status):
+        self._chk(self.L.zk_auditors_share_verify_batch_device(self.h, B, d_tags, d_shares, d_ok, d_status))
+
+    def auditors_combine_batch(self, auditors, tags, shares, ring_ids, t=None):
+        """zk_auditors_combine_batch: shares[s][b] is auditor auditors[s]'s share of tags[b]; one resident ring id (or ESCROW_RING_ANY) per tag.  Returns
+        (rings, indices -- both 0xffffffff for none --, statuses) as escrow_open_batch_rings does.  It does not verify: call auditors_share_verify_batch first."""
+        B = len(tags)
+        t = len(auditors) if t is None else t
+        size = self.auditors_share_size()
+        if len(shares) != len(auditors) or any(len(row) != B or any(len(s) != size for s in row) for row in shares) or len(ring_ids) != B:
+            raise ValueError('one row of B %d-byte shares per auditor, and every tag has a ring id' % size)
+        aud = (C.c_uint32 * max(len(auditors), 1))(*auditors)
+        ids = (C.c_uint32 * max(B, 1))(*ring_ids)
+        ring, idx = (C.c_uint32 * max(B, 1))(), (C.c_uint32 * max(B, 1))()
+        st = (C.c_int32 * max(B, 1))()
+        self._chk(self.L.zk_auditors_combine_batch(self.h, B, t, aud, self._escrow_tags_blob(tags), b''.join(b''.join(row) for row in shares) if B else bytes(size), ids, ring, idx, st))
+        return list(ring)[:B], list(idx)[:B], list(st)[:B]
+
+    def auditors_combine_batch_device(self, B, t, d_auditors, d_tags, d_shares, d_ring_ids, d_ring_out, d_index, d_status):
+        self._chk(self.L.zk_auditors_combine_batch_device(self.h, B, t, d_auditors, d_tags, d_shares, d_ring_ids, d_ring_out, d_index, d_status))
 
     def synth_params(self, seed):
         a, b, c = C.create_string_buffer(64), C.create_string_buffer(72), C.create_string_buffer(72)

@@ -176,7 +176,7 @@ extern "C" void zk_ctx_destroy(zk_ctx* c) {
     escrow_drop_auditor(c);
     hipFree(c->P.tom_tab_g), hipFree(c->P.tom_tab_h), hipFree(c->tom_tab_gen), hipFree(c->P.pfix_G), hipFree(c->P.pfix_H);
     for (auto& R : c->rings) free_ring(R);
-    hipFree(c->tab_scratch), hipFree(c->d_flag);
+    hipFree(c->tab_scratch), hipFree(c->d_flag), hipFree(c->auditors_w);
     for (GrowBuf& b : c->buf) hipFree(b.p);
     if (c->h_rg) hipHostFree(c->h_rg);
     if (c->h_lv) hipHostFree(c->h_lv);

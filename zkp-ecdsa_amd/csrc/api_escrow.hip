@@ -5,7 +5,7 @@
 // lane's arena carved from one witness-flagged buffer.
 #include "ctx.h"
 #include "jobs.h"
-#include "escrow.h"
+#include "escrow_share.h"
 
 #define ZK_AUDITOR_BITS 16   // comb width of the (g, A) set: 0.13 GB per base (24 bits: 23 GB); a tag's bytes do not depend on it
 
@@ -15,6 +15,7 @@ void escrow_drop_auditor(zk_ctx* c) {
     if (c->aud_tab_g) (void)hipFree(c->aud_tab_g);
     c->PA = DevParams{};
     c->aud_tab_g = nullptr, c->auditor_set = false;
+    c->auditors_t = 0, c->auditors_n = 0;   // the share keys were checked against this key (zk_ctx_set_auditors)
 }
 extern "C" zk_status zk_ctx_set_auditor(zk_ctx* c, const uint8_t auditor_xy72[72]) {
     if (!c || !auditor_xy72) return ZK_E_ARG;
@@ -84,7 +85,7 @@ static bool escrow_aligned(std::initializer_list<const void*> ps) {   // the ker
 extern "C" uint64_t zk_escrow_tag_size(void) { return ZKT1_SIZE; }
 
 // a * g for the secret at d_secret through one comb walk: S[0] = (a, 0), its affine bytes at d_ag; a8 (nullable) receives a mod q as words
-static void escrow_secret_point(zk_ctx* c, hipStream_t s, const uint8_t* d_secret, const TomList& S, uint32_t* a8, uint8_t* d_ag) {
+void escrow_secret_point(zk_ctx* c, hipStream_t s, const uint8_t* d_secret, const TomList& S, uint32_t* a8, uint8_t* d_ag) {
     launch_escrow_stage_secret(s, d_secret, S, 0, a8);
     launch_tom_commit(s, c->P, S, 1, 1, 1);
     launch_tom_normalize(s, S, 1, 0, 1, 1);
@@ -332,7 +333,7 @@ extern "C" zk_status zk_escrow_verify_batch(zk_ctx* c, uint64_t B, const uint8_t
 }
 
 // ------------------------------------------------------------------ opening
-static size_t escrow_open_carve(EscrowOpen& O, uint8_t* base, uint64_t B, uint32_t slab) {
+size_t escrow_open_carve(EscrowOpen& O, uint8_t* base, uint64_t B, uint32_t slab) {
     SoaCarver k(base);
     O = EscrowOpen{};
     O.S = k.list(1);
@@ -458,7 +459,7 @@ void escrow_index_drop(Ring& R) {
     hipFree(R.esc_pts), hipFree(R.esc_slots);
     R.esc_pts = nullptr, R.esc_slots = nullptr;
 }
-static EscIndexRing escrow_index_desc(const Ring& R, uint64_t nkeys) {
+EscIndexRing escrow_index_desc(const Ring& R, uint64_t nkeys) {
     EscIndexRing D{};
     D.id = R.id, D.nkeys = (uint32_t)nkeys, D.mask = 2 * (uint32_t)R.N - 1, D.pts = R.esc_pts, D.slots = R.esc_slots;
     return D;
@@ -483,7 +484,7 @@ static void escrow_index_points(zk_ctx* c, hipStream_t s, const TomList& L, uint
     launch_escrow_times4(s, L, n);
     launch_tom_normalize(s, L, n, 0, 1, 1);
 }
-static zk_status escrow_index_build(zk_ctx* c, Ring& R) {
+zk_status escrow_index_build(zk_ctx* c, Ring& R) {
     hipStream_t s = c->stream;
     const uint32_t slab = (uint32_t)std::min<uint64_t>(R.nkeys, ESC_INDEX_SLAB), cap = (uint32_t)R.N;
     DevBuf tmp;

@@ -95,7 +95,11 @@ struct zk_ctx {
     uint32_t* aud_tab_g = nullptr;    // g at the auditor set's width where the context's differs (owned; nullptr: PA.tom_tab_g is P.tom_tab_g)
     uint32_t aud_w[18] = {};          // A as nine little-endian words per coordinate, and as the caller's bytes
     uint8_t aud_xy[72] = {};
-    uint32_t tom_g_w[18] = {};        // g in the same form (zk_ctx_set_params)
+    // the share keys A_1 .. A_n of a t-of-n opening (zk_ctx_set_auditors, api_escrow_share.hip): public, checked against the auditor's key and dropped with it
+    uint32_t auditors_t = 0, auditors_n = 0;   // n = 0: no set
+    uint8_t auditors_xy[16][72] = {};
+    uint32_t* auditors_w = nullptr;   // [16][18] on the device: nine little-endian words per coordinate (allocated by the first set, freed by zk_ctx_destroy)
+    uint32_t tom_g_w[18] = {};       // g in the same form (zk_ctx_set_params)
     uint32_t* tom_tab_gen = nullptr;  // 8-bit comb table of the Tom generator (synthetic params only)
     uint32_t tom_bits = TOM_DEFAULT_BITS;  // comb width requested for g, h (zk_ctx_set_comb_bits)
     uint32_t tab_bits_alloc = 0;      // width the allocated P.tom_tab_g/h were sized for (0 = not allocated)
