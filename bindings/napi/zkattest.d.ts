@@ -216,6 +216,24 @@ export class QuorumProof {
 export function proveQuorum(params: SystemParametersList, msgHashes: Uint8Array[], sigs: Uint8Array[], publicKeys: PublicKey[], whichs: number[], keys: QuorumKeys): Promise<QuorumProof>
 /** true iff every attestation verifies over `keys` for its message hash and every pair of them comes from different keys; what does not deserialise throws */
 export function verifyQuorum(params: SystemParametersList, msgHashes: Uint8Array[], keys: QuorumKeys, proof: QuorumProof | Buffer): Promise<boolean>
+/** Accountable attestations ("ZKC1", zk_accountable_*): one attestation and the escrow tag of the keyXcom inside it as one artifact -- a 16-byte header, the
+ *  attestation, the 472-byte ZKT1 tag.  The commitment is not repeated, so the tag can only be checked against the attestation it travels with. */
+export class AccountableProof {
+    readonly bytes: Buffer
+    constructor(zkc1: Buffer)
+    readonly attestation: SignatureProofList
+    readonly tag: EscrowTag
+    eq(o: AccountableProof): boolean
+}
+/** an attestation over `keys` with the escrow tag of its keyXcom under the auditor's key; the engine draws both seed sets */
+export function proveAccountable(params: SystemParametersList, auditor: LinkCom, msgHash: Uint8Array, sig: Uint8Array, publicKey: PublicKey, which: number, keys: bigint[] | Buffer): Promise<AccountableProof>
+export function proveAccountables(params: SystemParametersList, auditor: LinkCom, msgHashes: Uint8Array[], sigs: Uint8Array[], publicKeys: PublicKey[], whichs: number[], keys: bigint[] | Buffer): Promise<AccountableProof[]>
+/** true iff the attestation verifies over `keys` for its message hash and its tag verifies against the keyXcom inside it under the auditor's key; what does not deserialise throws */
+export function verifyAccountable(params: SystemParametersList, auditor: LinkCom, msgHash: Uint8Array, keys: bigint[] | Buffer, proof: AccountableProof | Buffer): Promise<boolean>
+export function verifyAccountables(params: SystemParametersList, auditor: LinkCom, msgHashes: Uint8Array[], keys: bigint[] | Buffer, proofs: (AccountableProof | Buffer)[]): Promise<boolean[]>
+/** pure layout: the attestations for verifySignatureLists / reringSignatureLists, the tags for the auditor's calls; joinAccountable is the inverse (split, re-ring, join keeps the tag) */
+export function splitAccountable(params: PedersenParams | SystemParametersList, proofs: (AccountableProof | Buffer)[]): Promise<{ attestation: SignatureProofList; tag: EscrowTag }[]>
+export function joinAccountable(params: PedersenParams | SystemParametersList, attestations: (SignatureProofList | Buffer)[], tags: (EscrowTag | Buffer)[]): Promise<AccountableProof[]>
 /** keyXcom of a proof (either wire layout; zk_proof_key_commitments) */
 export function keyCommitment(proof: SignatureProofList | Buffer, params?: SystemParametersList): Promise<Point>
 export function keyCommitments(proofs: (SignatureProofList | Buffer)[], params?: SystemParametersList): Promise<Point[]>
@@ -270,6 +288,14 @@ export class Engine {
     quorumProveBatch(k: number, msg: Buffer, sig: Buffer, pk: Buffer, whichs: number[], seeds?: Buffer, pairSeeds?: Buffer): { bundles: (Buffer | null)[]; status: Int32Array; memberStatus: Int32Array }
     /** zk_quorum_verify_batch: firstBad names the first member (< k) or pair (k + p) that failed, 0xFFFFFFFF where ok */
     quorumVerifyBatch(k: number, msg: Buffer, bundles: Buffer[]): { ok: boolean[]; status: Int32Array; firstBad: Uint32Array }
+    /** zk_accountable_prove_batch over the active ring under the engine's auditor key: rows in bundle order (pk: 64-byte x | y); both seed sets must be fresh and independent (default: crypto.randomBytes); partStatus: (attestation, tag) per bundle */
+    accountableProveBatch(msg: Buffer, sig: Buffer, pk: Buffer, whichs: number[], seeds?: Buffer, tagSeeds?: Buffer): { bundles: (Buffer | null)[]; status: Int32Array; partStatus: Int32Array }
+    /** zk_accountable_verify_batch: firstBad is 0 for the attestation, 1 for the tag, 0xFFFFFFFF where ok */
+    accountableVerifyBatch(msg: Buffer, bundles: Buffer[]): { ok: boolean[]; status: Int32Array; firstBad: Uint32Array }
+    /** zk_accountable_split_batch, pure layout: a refused bundle gives an empty attestation, 472 zero bytes and status 10 */
+    accountableSplitBatch(bundles: Buffer[]): { attestations: Buffer[]; tags: Buffer[]; status: Int32Array }
+    /** zk_accountable_join_batch, pure layout: null and status 10 where the proof's header or the tag's header is refused */
+    accountableJoinBatch(proofs: Buffer[], tags: Buffer[]): { bundles: (Buffer | null)[]; status: Int32Array }
     /** zk_rings_quorum_prove_batch: quorumProveBatch with one RESIDENT ring id per member (whichs[m] indexes ring ringIds[m]); the active ring plays no part */
     ringsQuorumProveBatch(k: number, msg: Buffer, sig: Buffer, pk: Buffer, whichs: number[], ringIds: number[], seeds?: Buffer, pairSeeds?: Buffer): { bundles: (Buffer | null)[]; status: Int32Array; memberStatus: Int32Array }
     /** zk_rings_quorum_verify_batch: quorumVerifyBatch with one RESIDENT ring id per member; an id that is not resident fails its member with status 14 */

@@ -544,6 +544,31 @@ class Engine {
         const r = native.quorumVerifyBatch(this.h, k, msg, Buffer.concat(bundles), off)
         return { ok: Array.from(r.ok, (v) => v === 1), status: i32(r.status), firstBad: new Uint32Array(Uint8Array.from(r.firstBad).buffer) }
     }
+    // accountable attestations (zk_accountable_*): "ZKC1" bundles over the ACTIVE ring under the engine's auditor key -- bundle b takes row b of msg, sig, pk (64-byte
+    // x | y), whichs, seeds and tagSeeds.  -> { bundles: Buffer | null per bundle, status: Int32Array, partStatus: Int32Array (attestation, tag per bundle) }.  Both
+    // seed sets must be FRESH and independent of each other (default: crypto.randomBytes)
+    accountableProveBatch(msg, sig, pk, whichs, seeds, tagSeeds) {
+        const B = whichs.length
+        const r = native.accountableProveBatch(this.h, msg, sig, pk, Buffer.from(Uint32Array.from(whichs).buffer), seeds || crypto.randomBytes(32 * B), tagSeeds || crypto.randomBytes(32 * B))
+        const st = i32(r.status), o = u64(r.off)
+        return { bundles: Array.from(st, (s, b) => (s === 0 ? r.bundles.slice(Number(o[b]), Number(o[b + 1])) : null)), status: st, partStatus: i32(r.partStatus) }
+    }
+    // -> { ok: boolean[], status: Int32Array, firstBad: Uint32Array } -- firstBad is 0 for the attestation, 1 for the tag, 0xFFFFFFFF where ok
+    accountableVerifyBatch(msg, bundles) {
+        const r = native.accountableVerifyBatch(this.h, msg, Buffer.concat(bundles), slotOffsets(bundles))
+        return { ok: Array.from(r.ok, (v) => v === 1), status: i32(r.status), firstBad: new Uint32Array(Uint8Array.from(r.firstBad).buffer) }
+    }
+    // zk_accountable_split_batch, pure layout: -> { attestations: Buffer[] (empty for a refused bundle), tags: Buffer[] (472 bytes each, zero for a refused bundle), status }
+    accountableSplitBatch(bundles) {
+        const B = bundles.length, r = native.accountableSplitBatch(this.h, Buffer.concat(bundles), slotOffsets(bundles)), o = u64(r.off)
+        return { attestations: Array.from({ length: B }, (_, b) => r.attestations.slice(Number(o[b]), Number(o[b + 1]))),
+            tags: Array.from({ length: B }, (_, b) => r.tags.slice(472 * b, 472 * b + 472)), status: i32(r.status) }
+    }
+    // zk_accountable_join_batch, pure layout: -> { bundles: Buffer | null per proof, status }
+    accountableJoinBatch(proofs, tags) {
+        const r = native.accountableJoinBatch(this.h, Buffer.concat(proofs), slotOffsets(proofs), Buffer.concat(tags)), st = i32(r.status), o = u64(r.off)
+        return { bundles: Array.from(st, (s, b) => (s === 0 ? r.bundles.slice(Number(o[b]), Number(o[b + 1])) : null)), status: st }
+    }
     // zk_rings_quorum_prove_batch / zk_rings_quorum_verify_batch: the same with one RESIDENT ring id per member (ringIds[m]; whichs[m] indexes that ring); the
     // active ring plays no part.  A key enrolled in two rings and used through both is "the same key" (status 14)
     ringsQuorumProveBatch(k, msg, sig, pk, whichs, ringIds, seeds, pairSeeds) {
@@ -607,6 +632,13 @@ function ringOf(keys) {
         if (frozen) ringCache.set(keys, c)
     }
     return c
+}
+// (B + 1) u64 LE offsets of byte strings laid back to back
+function slotOffsets(blobs) {
+    const off = Buffer.alloc(8 * (blobs.length + 1))
+    let run = 0
+    blobs.forEach((b, i) => { run += b.length; off.writeBigUInt64LE(BigInt(run), 8 * (i + 1)) })
+    return off
 }
 function engineFor(params, keys) {
     if (!(params instanceof SystemParametersList)) throw new TypeError('params: a SystemParametersList (generateParamsList / readJson)')
@@ -1555,6 +1587,74 @@ async function verifyQuorum(params, msgHashes, keys, proof) {
     return r.ok[0]
 }
 
-module.exports = { splitAuditorKey, shareEscrowTags, verifyEscrowShares, combineEscrowShares, EscrowShare, proveEscrowTag, verifyEscrowTag, proveEscrowTags, verifyEscrowTags, openEscrowTags, escrowAuditorKey, EscrowTag, proveQuorum, verifyQuorum, QuorumProof, proveDifferentKeys, verifyDifferentKeys, proveDifferentKeysBatch, verifyDifferentKeysBatch, distinctPairs, DistinctProof, proveSameKey, verifySameKey, proveSameKeys, verifySameKeys, keyCommitment, keyCommitments, LinkProof, reringSignatureLists, keyBlinders, proveMembership, verifyMembership, proveMemberships, verifyMemberships, proveMembershipLists, verifyMembershipLists, GKProof, Commitment, commit, screenSignatureLists, findKey, SCREEN, WHICH_NONE, recoverSignatureLists, recoverKey, RECOVER, verifySignatureLists, proveSignatureLists, _ringGenerations, setVerifyLevel, getVerifyLevel, setVerifyReps, getVerifyReps, generateParamsList, generateParamsListHardened, keyToInt, proveSignatureList, verifySignatureList, proveSignatureListBatch, verifySignatureListBatch,
+// ---------------------------------------------------------------- accountable attestations: an attestation that carries its escrow tag
+// An AccountableProof keeps the engine's ZKC1 bytes (include/zkattest.h): a 16-byte header, one attestation in one wire layout, the 472-byte ZKT1 tag of the keyXcom
+// inside that attestation.  The commitment is not repeated: the tag cannot be checked against another attestation.
+class AccountableProof {
+    constructor(bytes) {
+        const bad = () => new Error('error deserializing AccountableProof')
+        if (!(Buffer.isBuffer(bytes) && bytes.length >= 16 + 32 + 472 && bytes.length % 4 === 0 && bytes.slice(0, 4).toString('latin1') === 'ZKC1' && bytes.readUInt32BE(4) === bytes.length &&
+            bytes.readUInt32BE(8) === 0 && bytes.readUInt32BE(12) === 0)) throw bad()
+        if (bytes.readUInt32BE(20) !== bytes.length - 16 - 472) throw bad()   // the inner total_len walks exactly to the tag
+        this.bytes = bytes
+    }
+    get attestation() { return new SignatureProofList(this.bytes.slice(16, this.bytes.length - 472)) }
+    get tag() { return new EscrowTag(this.bytes.slice(this.bytes.length - 472)) }
+    eq(o) { return o instanceof AccountableProof && this.bytes.equals(o.bytes) }
+}
+const accountableBytes = (p) => (p instanceof AccountableProof ? p.bytes : new AccountableProof(p).bytes)
+// proveAccountables(params, auditor, msgHashes, sigs, publicKeys, whichs, keys): one attestation per row over the ring `keys` (the arguments of
+// proveSignatureListBatch), each with the escrow tag of its keyXcom under the auditor's key (a Point or 72 bytes) -> AccountableProof[].  The engine draws both seed sets.
+async function proveAccountables(params, auditor, msgHashes, sigs, publicKeys, whichs, keys) {
+    const B = msgHashes.length
+    if (sigs.length !== B || publicKeys.length !== B || whichs.length !== B) throw new RangeError('proveAccountables: one hash, signature, key and index per attestation')
+    if (!B) return []
+    const raws = await Promise.all(publicKeys.map(rawPublicKey))
+    for (const r of raws) if (r.length !== 65 || r[0] !== 4) throw new Error('invalid public key')
+    const msg = Buffer.concat(msgHashes.map((m) => Buffer.from(m))), sig = Buffer.concat(sigs.map((x) => Buffer.from(x))), pk = Buffer.concat(raws.map((x) => x.slice(1)))
+    const wire = wireLayout
+    checkRingSize(Buffer.isBuffer(keys) ? keys.length / 32 : keys.length, true)
+    const r = await engineFor(params, keys).withRing((engine) => { useWire(engine, wire); useAuditor(engine, auditor); return engine.accountableProveBatch(msg, sig, pk, whichs) })
+    return r.bundles.map((b, i) => { if (r.status[i] !== 0) throw statusError(r.status[i]); return new AccountableProof(b) })
+}
+async function proveAccountable(params, auditor, msgHash, sig, publicKey, which, keys) {
+    return (await proveAccountables(params, auditor, [msgHash], [sig], [publicKey], [which], keys))[0]
+}
+// -> boolean[]: the attestation verifies over `keys` for its message hash AND its tag verifies against the keyXcom inside it under the auditor's key.  What does not
+// deserialise throws.  All proofs of a call are in one wire layout.
+async function verifyAccountables(params, auditor, msgHashes, keys, proofs) {
+    const B = proofs.length
+    if (msgHashes.length !== B) throw new RangeError('verifyAccountables: one message hash per proof')
+    if (!B) return []
+    const raw = proofs.map(accountableBytes), msg = Buffer.concat(msgHashes.map((m) => Buffer.from(m)))
+    const wire = isPacked(raw[0].slice(16)) ? 1 : 0, level = verifyLevel, reps = verifyReps
+    checkRingSize(Buffer.isBuffer(keys) ? keys.length / 32 : keys.length, false)
+    const r = await engineFor(params, keys).withRing((engine) => { useWire(engine, wire); useVerifyLevel(engine, level); useVerifyReps(engine, reps); useAuditor(engine, auditor)
+        return engine.accountableVerifyBatch(msg, raw) })
+    r.status.forEach((st) => { if (st !== 0) throw statusError(st) })
+    return r.ok
+}
+async function verifyAccountable(params, auditor, msgHash, keys, proof) {
+    return (await verifyAccountables(params, auditor, [msgHash], keys, [proof]))[0]
+}
+// splitAccountable(params, proofs) -> [{ attestation: SignatureProofList, tag: EscrowTag }]: pure layout, for verifySignatureLists, reringSignatureLists and the
+// auditor's calls (openEscrowTags, shareEscrowTags, combineEscrowShares).  joinAccountable(params, attestations, tags) -> AccountableProof[] is its inverse: a tag is
+// bound to keyXcom and the auditor's key, not to the ring, so split -> reringSignatureLists -> join keeps it.
+async function splitAccountable(params, proofs) {
+    if (!proofs.length) return []
+    const raw = proofs.map(accountableBytes), wire = isPacked(raw[0].slice(16)) ? 1 : 0
+    const r = await engineFor(paramsOf(params), null).run((engine) => { useWire(engine, wire); return engine.accountableSplitBatch(raw) })
+    return raw.map((_, i) => { if (r.status[i] !== 0) throw statusError(r.status[i]); return { attestation: new SignatureProofList(r.attestations[i]), tag: new EscrowTag(r.tags[i]) } })
+}
+async function joinAccountable(params, attestations, tags) {
+    if (tags.length !== attestations.length) throw new RangeError('joinAccountable: one tag per attestation')
+    if (!tags.length) return []
+    const pr = attestations.map((a) => (Buffer.isBuffer(a) ? a : a.bytes)), tg = tags.map((t) => (t instanceof EscrowTag ? t.bytes : new EscrowTag(t).bytes))
+    const wire = isPacked(pr[0]) ? 1 : 0
+    const r = await engineFor(paramsOf(params), null).run((engine) => { useWire(engine, wire); return engine.accountableJoinBatch(pr, tg) })
+    return r.bundles.map((b, i) => { if (r.status[i] !== 0) throw statusError(r.status[i]); return new AccountableProof(b) })
+}
+
+module.exports = { proveAccountable, proveAccountables, verifyAccountable, verifyAccountables, splitAccountable, joinAccountable, AccountableProof, splitAuditorKey, shareEscrowTags, verifyEscrowShares, combineEscrowShares, EscrowShare, proveEscrowTag, verifyEscrowTag, proveEscrowTags, verifyEscrowTags, openEscrowTags, escrowAuditorKey, EscrowTag, proveQuorum, verifyQuorum, QuorumProof, proveDifferentKeys, verifyDifferentKeys, proveDifferentKeysBatch, verifyDifferentKeysBatch, distinctPairs, DistinctProof, proveSameKey, verifySameKey, proveSameKeys, verifySameKeys, keyCommitment, keyCommitments, LinkProof, reringSignatureLists, keyBlinders, proveMembership, verifyMembership, proveMemberships, verifyMemberships, proveMembershipLists, verifyMembershipLists, GKProof, Commitment, commit, screenSignatureLists, findKey, SCREEN, WHICH_NONE, recoverSignatureLists, recoverKey, RECOVER, verifySignatureLists, proveSignatureLists, _ringGenerations, setVerifyLevel, getVerifyLevel, setVerifyReps, getVerifyReps, generateParamsList, generateParamsListHardened, keyToInt, proveSignatureList, verifySignatureList, proveSignatureListBatch, verifySignatureListBatch,
     writeJson, readJson, writeJsonBatch, readJsonBatch, SignatureProofList, SystemParametersList, PedersenParams, generatePedersenParams, p256, tomEdwards256, ALL_GROUPS,
     Group, Point, Scalar, Engine, shutdown, setWireLayout, getWireLayout, setOption, native }

@@ -1853,6 +1853,148 @@ static napi_value quorum_verify(napi_env env, napi_callback_info info, int rings
 static napi_value QuorumVerifyBatch(napi_env env, napi_callback_info info) { return quorum_verify(env, info, 0); }
 /* zk_rings_quorum_verify_batch: the same with ids: Qk u32 LE (one RESIDENT ring id per member) behind off */
 static napi_value QuorumVerifyBatchRings(napi_env env, napi_callback_info info) { return quorum_verify(env, info, 1); }
+/* Accountable attestations (include/zkattest.h: zk_accountable_*), on the pool's first context with its ACTIVE ring and its auditor key.
+ * (h, msg: B x 32, sig: B x 64, pk: B x 64, which: B u32 LE, seeds: B x 32, tagSeeds: B x 32 -- both FRESH and independent of each other)
+ * -> {bundles: the successful ZKC1 bundles back to back, off: (B + 1) u64 LE, status: B i32 LE, partStatus: 2B i32 LE (attestation, tag)} */
+static napi_value AccountableProveBatch(napi_env env, napi_callback_info info) {
+    napi_value argv[7];
+    if (!get_args(env, info, 7, argv)) return NULL;
+    Handle *h = get_handle(env, argv[0], 0);
+    uint8_t *msg, *sig, *pk, *which, *seeds, *tseeds;
+    size_t lm, ls, lp, lw, lsd, lts;
+    if (!h || !get_bytes(env, argv[1], &msg, &lm) || !get_bytes(env, argv[2], &sig, &ls) || !get_bytes(env, argv[3], &pk, &lp) || !get_bytes(env, argv[4], &which, &lw) ||
+        !get_bytes(env, argv[5], &seeds, &lsd) || !get_bytes(env, argv[6], &tseeds, &lts))
+        return NULL;
+    const size_t B = lm / 32;
+    if (lm % 32 || ls != 64 * B || lp != 64 * B || lw != 4 * B || lsd != 32 * B || lts != 32 * B) {
+        napi_throw_range_error(env, NULL, "accountableProveBatch: per bundle a 32-byte hash, a 64-byte signature, a 64-byte key, a u32 index, 32 seed bytes and 32 tag seed bytes");
+        return NULL;
+    }
+    zk_ctx *c = zk_pool_ctx(h->pool, 0);
+    const uint64_t cap = zk_accountable_proof_max_size(c) * B;
+    uint8_t *buf = (uint8_t *)xmalloc(env, 8 * (B + 1) + 16 * B + cap + 8);
+    if (!buf) return NULL;
+    uint64_t *off = (uint64_t *)buf;
+    int32_t *status = (int32_t *)(buf + 8 * (B + 1)), *pstatus = status + B;
+    uint32_t *w = (uint32_t *)(pstatus + 2 * B);   /* (a Buffer's bytes need not be aligned) */
+    uint8_t *out = (uint8_t *)(w + B);
+    memcpy(w, which, 4 * B);
+    zk_rng rng = {ZK_RNG_SEED, seeds, 0}, rng_tags = {ZK_RNG_SEED, tseeds, 0};
+    zk_status st = zk_accountable_prove_batch(c, B, msg, sig, pk, w, &rng, &rng_tags, out, cap, off, status, pstatus);
+    napi_value v = NULL;
+    if (st != ZK_OK) throw_text(env, st, zk_last_error(c));
+    else if (napi_create_object(env, &v) == napi_ok)
+        set_prop(env, v, "bundles", new_buffer(env, out, off[B])), set_prop(env, v, "off", new_buffer(env, off, 8 * (B + 1))), set_prop(env, v, "status", new_buffer(env, status, 4 * B)),
+            set_prop(env, v, "partStatus", new_buffer(env, pstatus, 8 * B));
+    free(buf);
+    return v;
+}
+/* (B + 1) u64 LE offsets out of a Buffer into aligned memory; no slot may reach past `limit` bytes.  -> 0 after a thrown RangeError */
+static int accountable_offsets(napi_env env, const uint8_t *ob, size_t B, size_t limit, uint64_t *off, const char *what) {
+    memcpy(off, ob, 8 * (B + 1));
+    for (size_t b = 0; b <= B; b++)
+        if (off[b] > limit) {
+            napi_throw_range_error(env, NULL, what);
+            return 0;
+        }
+    return 1;
+}
+/* (h, msg: B x 32, bundles: back to back, off: (B + 1) u64 LE) -> {ok: B bytes, status: B i32 LE, firstBad: B u32 LE (0 attestation, 1 tag, 0xFFFFFFFF ok)} */
+static napi_value AccountableVerifyBatch(napi_env env, napi_callback_info info) {
+    napi_value argv[4];
+    if (!get_args(env, info, 4, argv)) return NULL;
+    Handle *h = get_handle(env, argv[0], 0);
+    uint8_t *msg, *blob, *ob;
+    size_t lm, lb, lo;
+    if (!h || !get_bytes(env, argv[1], &msg, &lm) || !get_bytes(env, argv[2], &blob, &lb) || !get_bytes(env, argv[3], &ob, &lo)) return NULL;
+    const size_t B = lo >= 8 ? lo / 8 - 1 : 0;
+    if (lo < 8 || lo % 8 || lm != 32 * B) {
+        napi_throw_range_error(env, NULL, "accountableVerifyBatch: (B + 1) u64 offsets and one 32-byte hash per bundle");
+        return NULL;
+    }
+    uint8_t *buf = (uint8_t *)xmalloc(env, 8 * (B + 1) + 9 * B + 8);
+    if (!buf) return NULL;
+    uint64_t *off = (uint64_t *)buf;
+    if (!accountable_offsets(env, ob, B, lb, off, "accountableVerifyBatch: an offset lies behind the bundles")) {
+        free(buf);
+        return NULL;
+    }
+    int32_t *status = (int32_t *)(buf + 8 * (B + 1));
+    uint32_t *bad = (uint32_t *)(status + B);
+    uint8_t *ok = (uint8_t *)(bad + B);
+    zk_ctx *c = zk_pool_ctx(h->pool, 0);
+    zk_status st = zk_accountable_verify_batch(c, B, msg, blob, off, NULL, ok, status, bad);
+    napi_value v = NULL;
+    if (st != ZK_OK) throw_text(env, st, zk_last_error(c));
+    else if (napi_create_object(env, &v) == napi_ok)
+        set_prop(env, v, "ok", new_buffer(env, ok, B)), set_prop(env, v, "status", new_buffer(env, status, 4 * B)), set_prop(env, v, "firstBad", new_buffer(env, bad, 4 * B));
+    free(buf);
+    return v;
+}
+/* zk_accountable_split_batch: (h, bundles: back to back, off: (B + 1) u64 LE) -> {attestations: back to back, off: (B + 1) u64 LE, tags: B x 472, status: B i32 LE} */
+static napi_value AccountableSplitBatch(napi_env env, napi_callback_info info) {
+    napi_value argv[3];
+    if (!get_args(env, info, 3, argv)) return NULL;
+    Handle *h = get_handle(env, argv[0], 0);
+    uint8_t *blob, *ob;
+    size_t lb, lo;
+    if (!h || !get_bytes(env, argv[1], &blob, &lb) || !get_bytes(env, argv[2], &ob, &lo)) return NULL;
+    if (lo < 8 || lo % 8) {
+        napi_throw_range_error(env, NULL, "accountableSplitBatch: B + 1 offsets of 8 bytes");
+        return NULL;
+    }
+    const size_t B = lo / 8 - 1;
+    uint8_t *buf = (uint8_t *)xmalloc(env, 16 * (B + 1) + 4 * B + 472 * B + lb + 8);
+    if (!buf) return NULL;
+    uint64_t *off = (uint64_t *)buf, *aoff = off + (B + 1);
+    if (!accountable_offsets(env, ob, B, lb, off, "accountableSplitBatch: an offset lies behind the bundles")) {
+        free(buf);
+        return NULL;
+    }
+    int32_t *status = (int32_t *)(aoff + (B + 1));
+    uint8_t *tags = (uint8_t *)(status + B), *att = tags + 472 * B;
+    zk_ctx *c = zk_pool_ctx(h->pool, 0);
+    zk_status st = zk_accountable_split_batch(c, B, blob, off, att, lb, aoff, tags, status);
+    napi_value v = NULL;
+    if (st != ZK_OK) throw_text(env, st, zk_last_error(c));
+    else if (napi_create_object(env, &v) == napi_ok)
+        set_prop(env, v, "attestations", new_buffer(env, att, aoff[B])), set_prop(env, v, "off", new_buffer(env, aoff, 8 * (B + 1))), set_prop(env, v, "tags", new_buffer(env, tags, 472 * B)),
+            set_prop(env, v, "status", new_buffer(env, status, 4 * B));
+    free(buf);
+    return v;
+}
+/* zk_accountable_join_batch: (h, proofs: back to back, off: (B + 1) u64 LE, tags: B x 472) -> {bundles: the accepted ones back to back, off: (B + 1) u64 LE, status: B i32 LE} */
+static napi_value AccountableJoinBatch(napi_env env, napi_callback_info info) {
+    napi_value argv[4];
+    if (!get_args(env, info, 4, argv)) return NULL;
+    Handle *h = get_handle(env, argv[0], 0);
+    uint8_t *blob, *ob, *tags;
+    size_t lb, lo, lt;
+    if (!h || !get_bytes(env, argv[1], &blob, &lb) || !get_bytes(env, argv[2], &ob, &lo) || !get_bytes(env, argv[3], &tags, &lt)) return NULL;
+    const size_t B = lo >= 8 ? lo / 8 - 1 : 0;
+    if (lo < 8 || lo % 8 || lt != 472 * B) {
+        napi_throw_range_error(env, NULL, "accountableJoinBatch: (B + 1) u64 offsets and one 472-byte tag per proof");
+        return NULL;
+    }
+    const uint64_t cap = lb + 488 * B;
+    uint8_t *buf = (uint8_t *)xmalloc(env, 16 * (B + 1) + 4 * B + cap + 8);
+    if (!buf) return NULL;
+    uint64_t *off = (uint64_t *)buf, *ooff = off + (B + 1);
+    if (!accountable_offsets(env, ob, B, lb, off, "accountableJoinBatch: an offset lies behind the proofs' bytes")) {
+        free(buf);
+        return NULL;
+    }
+    int32_t *status = (int32_t *)(ooff + (B + 1));
+    uint8_t *out = (uint8_t *)(status + B);
+    zk_ctx *c = zk_pool_ctx(h->pool, 0);
+    zk_status st = zk_accountable_join_batch(c, B, blob, off, tags, out, cap, ooff, status);
+    napi_value v = NULL;
+    if (st != ZK_OK) throw_text(env, st, zk_last_error(c));
+    else if (napi_create_object(env, &v) == napi_ok)
+        set_prop(env, v, "bundles", new_buffer(env, out, ooff[B])), set_prop(env, v, "off", new_buffer(env, ooff, 8 * (B + 1))), set_prop(env, v, "status", new_buffer(env, status, 4 * B));
+    free(buf);
+    return v;
+}
 /* zk_proof_key_commitments: (h, proofs: the B proofs back to back in the context's wire layout, off: (B + 1) u64 LE) -> {coms: B x 72 (zeros where status != 0),
  * status: B i32 LE} */
 static napi_value KeyCommitments(napi_env env, napi_callback_info info) {
@@ -1918,7 +2060,9 @@ static napi_value Init(napi_env env, napi_value exports) {
                {"ringsQuorumProveBatch", QuorumProveBatchRings}, {"ringsQuorumVerifyBatch", QuorumVerifyBatchRings},
                {"ringsEscrowOpenBatch", EscrowOpenBatchRings},
                {"auditorsSplitKey", AuditorsSplitKey}, {"auditorsSetKeys", AuditorsSetKeys}, {"auditorsShareBatch", AuditorsShareBatch},
-               {"auditorsShareVerifyBatch", AuditorsShareVerifyBatch}, {"auditorsCombineBatch", AuditorsCombineBatch}};
+               {"auditorsShareVerifyBatch", AuditorsShareVerifyBatch}, {"auditorsCombineBatch", AuditorsCombineBatch},
+               {"accountableProveBatch", AccountableProveBatch}, {"accountableVerifyBatch", AccountableVerifyBatch},
+               {"accountableSplitBatch", AccountableSplitBatch}, {"accountableJoinBatch", AccountableJoinBatch}};
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;
         if (napi_create_function(env, fns[i].name, NAPI_AUTO_LENGTH, fns[i].fn, NULL, &f) != napi_ok) return NULL;

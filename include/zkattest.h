@@ -1052,6 +1052,75 @@ zk_status zk_auditors_combine_batch_device(zk_ctx *ctx, uint64_t B, uint32_t t, 
                                            const void *d_ring_ids /*u32[B]*/, void *d_ring_out_u32 /*u32[B]*/, void *d_index_u32 /*u32[B]*/,
                                            void *d_per_tag_status /*i32[B]*/);
 
+/* ---- accountable attestations: an attestation that CARRIES its escrow tag, as one artifact.  The recipe of INTEGRATION.md "Accountable attestations" --
+ * zk_prove_batch, zk_prove_key_blinders with the same seeds, zk_proof_key_commitments, zk_escrow_prove_batch with key = pk_xy[0:32] (and zk_verify_batch,
+ * zk_proof_key_commitments, zk_escrow_verify_batch for the verifier) -- as one prove call and one verify call with a wire format of its own; keys, blinders
+ * and keyXcoms are gathered and the two verdicts folded on the device.  No existing call changes, a ZKT1 tag stays byte for byte what it is, and every
+ * auditor call (zk_escrow_open_batch, zk_rings_escrow_open_batch, zk_auditors_share_batch, zk_auditors_share_verify_batch, zk_auditors_combine_batch) works
+ * on the tags zk_accountable_split_batch takes out of bundles.
+ * Wire format "ZKC1" (a bundle):
+ *     header 16 B : "ZKC1" | total_len u32 big-endian | 0 u32 | 0 u32
+ *     attestation : one ZKA1 / ZK1P proof in the context's wire layout (zk_ctx_set_wire), exactly as zk_prove_batch writes it (its own total_len, a multiple
+ *                   of 4)
+ *     tag 472 B   : one ZKT1 tag, exactly as zk_escrow_prove_batch writes it, for C = the keyXcom inside that attestation (read by the rules of
+ *                   zk_proof_key_commitments) and the context's auditor key A
+ *   C is not repeated, so a tag can only be checked against the attestation it travels with.  An attestation's length varies with the Exp challenge, so a
+ *   bundle's length varies; zk_accountable_proof_max_size(ctx) = 16 + zk_proof_max_size(ctx) + 472.
+ * Bundle b uses row b of msg_hash, sig, pk_xy, which, rng and rng_tags.
+ * zk_accountable_prove_batch: where proof b succeeds its bundle is, byte for byte, the header, the proof zk_prove_batch makes for row b of rng with the
+ *   active ring, and the tag zk_escrow_prove_batch makes under row b of rng_tags with key = pk_xy[64 b : 64 b + 32], com = that proof's keyXcom and blinder =
+ *   what zk_prove_key_blinders gives for row b: the bytes of the recipe, in both protocol modes and wire layouts, whatever the comb width or build.
+ *   per_proof_status is the first non-zero one of the attestation's status, then the tag's (ZK_E_RNG_EXHAUSTED on a short rng_tags stream).  A failed bundle
+ *   gets an empty slot (out_off[b + 1] = out_off[b]), the bundles behind it close up, no neighbour's byte changes.  per_part_status (may be NULL) receives
+ *   both statuses: 2 b the attestation's, 2 b + 1 the tag's as zk_escrow_prove_batch reports it (for the all-zero commitment of a failed attestation too).
+ *   ZK_E_BUFFER, before a byte of any output is written: out_cap < B zk_accountable_proof_max_size, no params, no active ring, no auditor key.
+ * zk_accountable_verify_batch: per bundle, the first rule that matches:
+ *     ZK_E_BAD_ENCODING with ok 0 and first_bad 0, no byte outside the slot read: a wrong magic, total_len != the slot's length, a non-zero reserved word, a
+ *       slot offset or length that is no multiple of 4 or offsets that do not ascend, or an inner header (magic of the context's layout, total_len, the rules
+ *       of zk_proof_rering_batch) that does not walk from byte 16 exactly to total_len - 472.
+ *   Otherwise the attestation is verified exactly as zk_verify_batch verifies it (the active ring, zk_ctx_set_verify_level and zk_ctx_set_verify_reps,
+ *   verifier_seeds row b or the library's own) and the tag exactly as zk_escrow_verify_batch does against the attestation's keyXcom.  ok = 1 iff both parts
+ *   are ok; per_proof_status is the first non-zero one, attestation before tag; first_bad (may be NULL) is 0 for the attestation, 1 for the tag and
+ *   0xFFFFFFFF where ok = 1.  ZK_E_BUFFER without params, an active ring or an auditor key.
+ * zk_accountable_split_batch and zk_accountable_join_batch are pure layout: they prove nothing and check no curve, and need neither params nor a ring nor
+ *   an auditor key -- only the context's wire layout.  Split applies the verifier's walk: the attestations come out back to back (att_off, B + 1 entries),
+ *   ready for zk_verify_batch, zk_verify_batch_rings and zk_proof_rering_batch, the tags dense at 472 b, ready for every auditor call; a refused bundle is
+ *   ZK_E_BAD_ENCODING, an empty attestation slot and 472 zero bytes.  ZK_E_BUFFER, before a byte is written, when att_cap is less than the sum of
+ *   (slot length - 488) over the slots of at least 520 bytes: what the offsets alone allow.  Join checks the proof's header by the rules of
+ *   zk_proof_rering_batch and the tag's 16 header bytes ("ZKT1" | 472 | 0 | 0); it refuses with ZK_E_BAD_ENCODING and an empty slot.  ZK_E_BUFFER when
+ *   out_cap is less than the sum of (slot length + 488) over the readable slots.  join(split(x)) = x and split(join(p, t)) = (p, t).  A tag is bound to
+ *   keyXcom and A, not to the ring: split, zk_proof_rering_batch, join moves an accountable attestation to another ring with its tag intact, and split /
+ *   join are how a sharded registry (zk_prove_batch_rings, zk_verify_batch_rings) uses ZKC1.  Input and output buffers must not overlap.
+ * Call-level rules are the quorum prover's: ZK_E_ARG for NULL pointers other than the optional arrays, for B >= 2^32 and while streamed jobs are queued; B = 0
+ *   is ZK_OK with out_off[0] = 0 (att_off[0] = 0).  The _device forms take every pointer, both rng->data included, in this context's HBM, 4-byte aligned, else
+ *   ZK_E_ARG.  A call runs in windows of at most chunk x lanes bundles; what is witness-derived -- the staged keys and blinders, both RNG fills, the tag
+ *   prover's arena, the staged inputs -- is zeroed by zk_ctx_wipe, zk_ctx_destroy and a failed call.  zk_last_timing reports the families of the calls above
+ *   plus "accountable_blinders", "accountable_layout" (prover, join) and "accountable_walk", "accountable_verdict" (verifier, split, join).
+ * Not provided: one ring id per proof, tags inside ZKQ1 bundles, submit / wait, zk_pool_* and JSON forms, opening straight from bundles (split first), a
+ *   caller-context binding.
+ * Warning (2) of ZKL1 applies: rng_tags must be independent of rng -- with an attestation's own seed the fills that blinded it would come back as a tag's
+ *   rho and nonces.  A bundle tells the auditor, and nobody else, which ring member attested.  DESIGN.md section 5h'''. */
+uint64_t zk_accountable_proof_max_size(const zk_ctx *ctx);   /* 0 without params / an active ring */
+zk_status zk_accountable_prove_batch(zk_ctx *ctx, uint64_t B, const uint8_t *msg_hash /*Bx32*/, const uint8_t *sig /*Bx64*/, const uint8_t *pk_xy /*Bx64*/,
+                                     const uint32_t *which /*B*/, const zk_rng *rng, const zk_rng *rng_tags, uint8_t *out, uint64_t out_cap,
+                                     uint64_t *out_off /*B+1*/, int32_t *per_proof_status /*B*/, int32_t *per_part_status /*2B or NULL*/);
+zk_status zk_accountable_prove_batch_device(zk_ctx *ctx, uint64_t B, const void *d_msg_hash, const void *d_sig, const void *d_pk_xy, const void *d_which,
+                                            const zk_rng *rng_device, const zk_rng *rng_tags_device, void *d_out, uint64_t out_cap,
+                                            void *d_out_off /*u64[B+1]*/, void *d_per_proof_status /*i32[B]*/, void *d_per_part_status /*i32[2B] or NULL*/);
+zk_status zk_accountable_verify_batch(zk_ctx *ctx, uint64_t B, const uint8_t *msg_hash /*Bx32*/, const uint8_t *bundles, const uint64_t *bundle_off /*B+1*/,
+                                      const uint8_t *verifier_seeds /*Bx32 or NULL*/, uint8_t *ok /*B*/, int32_t *per_proof_status /*B*/,
+                                      uint32_t *first_bad /*B or NULL*/);
+zk_status zk_accountable_verify_batch_device(zk_ctx *ctx, uint64_t B, const void *d_msg_hash, const void *d_bundles, const void *d_bundle_off /*u64[B+1]*/,
+                                             const void *d_verifier_seeds, void *d_ok, void *d_per_proof_status /*i32[B]*/, void *d_first_bad /*u32[B] or NULL*/);
+zk_status zk_accountable_split_batch(zk_ctx *ctx, uint64_t B, const uint8_t *bundles, const uint64_t *bundle_off /*B+1*/, uint8_t *att_out, uint64_t att_cap,
+                                     uint64_t *att_off /*B+1*/, uint8_t *tags_out /*Bx472*/, int32_t *per_proof_status /*B*/);
+zk_status zk_accountable_split_batch_device(zk_ctx *ctx, uint64_t B, const void *d_bundles, const void *d_bundle_off /*u64[B+1]*/, void *d_att_out,
+                                            uint64_t att_cap, void *d_att_off /*u64[B+1]*/, void *d_tags_out, void *d_per_proof_status /*i32[B]*/);
+zk_status zk_accountable_join_batch(zk_ctx *ctx, uint64_t B, const uint8_t *proofs, const uint64_t *proof_off /*B+1*/, const uint8_t *tags /*Bx472*/,
+                                    uint8_t *out, uint64_t out_cap, uint64_t *out_off /*B+1*/, int32_t *per_proof_status /*B*/);
+zk_status zk_accountable_join_batch_device(zk_ctx *ctx, uint64_t B, const void *d_proofs, const void *d_proof_off /*u64[B+1]*/, const void *d_tags, void *d_out,
+                                           uint64_t out_cap, void *d_out_off /*u64[B+1]*/, void *d_per_proof_status /*i32[B]*/);
+
 /* ---- two (or more) batches in flight on one context.  zk_prove_batch / zk_verify_batch are synchronous: each call pays its own head
  * (no byte of a chunk exists before its stage 1 is over) and its own tail (the copies of the last slices, with nothing left to
  * hide them).  The submit / wait pair splits a call so that the pipeline keeps running ACROSS calls: submit stages the inputs and

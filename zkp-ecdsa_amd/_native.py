@@ -44,6 +44,9 @@ SYMBOLS = [
     'zk_rings_escrow_open_batch', 'zk_rings_escrow_open_batch_device',
     'zk_auditors_share_size', 'zk_auditors_split_key', 'zk_ctx_set_auditors', 'zk_auditors_share_batch', 'zk_auditors_share_batch_device',
     'zk_auditors_share_verify_batch', 'zk_auditors_share_verify_batch_device', 'zk_auditors_combine_batch', 'zk_auditors_combine_batch_device',
+    'zk_accountable_proof_max_size', 'zk_accountable_prove_batch', 'zk_accountable_prove_batch_device', 'zk_accountable_verify_batch',
+    'zk_accountable_verify_batch_device', 'zk_accountable_split_batch', 'zk_accountable_split_batch_device', 'zk_accountable_join_batch',
+    'zk_accountable_join_batch_device',
     'zk_test_field_op', 'zk_test_tom_commit', 'zk_test_p256_fixed_mul', 'zk_test_sha256', 'zk_test_rng_draws', 'zk_test_exp_sum',
 ]
 
@@ -235,6 +238,17 @@ def lib():
         L.zk_auditors_share_verify_batch_device.argtypes = [vp, u64, vp, vp, vp, vp]
         L.zk_auditors_combine_batch.argtypes = [vp, u64, C.c_uint32, vp, C.c_char_p, C.c_char_p, vp, vp, vp, vp]
         L.zk_auditors_combine_batch_device.argtypes = [vp, u64, C.c_uint32, vp, vp, vp, vp, vp, vp, vp]
+        # accountable attestations ("ZKC1"): an attestation and the escrow tag of its keyXcom as one bundle
+        L.zk_accountable_proof_max_size.argtypes = [vp]
+        L.zk_accountable_proof_max_size.restype = u64
+        L.zk_accountable_prove_batch.argtypes = [vp, u64, C.c_char_p, C.c_char_p, C.c_char_p, vp, C.POINTER(ZkRng), C.POINTER(ZkRng), vp, u64, vp, vp, vp]
+        L.zk_accountable_prove_batch_device.argtypes = [vp, u64, vp, vp, vp, vp, C.POINTER(ZkRng), C.POINTER(ZkRng), vp, u64, vp, vp, vp]
+        L.zk_accountable_verify_batch.argtypes = [vp, u64, C.c_char_p, C.c_char_p, vp, C.c_char_p, vp, vp, vp]
+        L.zk_accountable_verify_batch_device.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp, vp]
+        L.zk_accountable_split_batch.argtypes = [vp, u64, C.c_char_p, vp, vp, u64, vp, vp, vp]
+        L.zk_accountable_split_batch_device.argtypes = [vp, u64, vp, vp, vp, u64, vp, vp, vp]
+        L.zk_accountable_join_batch.argtypes = [vp, u64, C.c_char_p, vp, C.c_char_p, vp, u64, vp, vp]
+        L.zk_accountable_join_batch_device.argtypes = [vp, u64, vp, vp, vp, vp, u64, vp, vp]
         L.zk_proof_key_commitments.argtypes = [vp, u64, C.c_char_p, vp, vp, vp]
         L.zk_proof_key_commitments_device.argtypes = [vp, u64, vp, vp, vp, vp]
         L.zk_ring_digest.argtypes = [vp, vp]
@@ -1447,6 +1461,108 @@ class Engine:
 
     def escrow_open_batch_rings_device(self, B, d_secret, d_tags, d_ring_ids, d_ring_out, d_index, d_status):
         self._chk(self.L.zk_rings_escrow_open_batch_device(self.h, B, d_secret, d_tags, d_ring_ids, d_ring_out, d_index, d_status))
+
+    # ---- accountable attestations (zk_accountable_*): an attestation and the escrow tag of its keyXcom as one "ZKC1" bundle
+    def accountable_proof_max_size(self):
+        """zk_accountable_proof_max_size: 16 + proof_max_size + 472 (0 without params / an active ring)"""
+        return int(self.L.zk_accountable_proof_max_size(self.h))
+
+    @staticmethod
+    def _slots(blobs):
+        off = (C.c_uint64 * (len(blobs) + 1))()
+        for b, x in enumerate(blobs):
+            off[b + 1] = off[b] + len(x)
+        return off
+
+    def accountable_prove_batch(self, msg, sig, pk, which, seeds=None, tag_seeds=None, streams=None, stream_blocks=0, tag_streams=None, tag_stream_blocks=0, cap=None,
+                                want_part_status=True):
+        """zk_accountable_prove_batch: B = len(which) bundles over the active ring under the context's auditor key; bundle b uses row b of every array.  Both
+        seed sets come from os.urandom when absent; they must be independent of each other.  Returns (bundles: list of byte strings, None where the status is
+        not 0; statuses; part statuses: B (attestation, tag) pairs).  self.accountable_last_raw keeps (bytes, offsets) as the call wrote them; cap overrides the
+        out_cap handed to the call."""
+        B = len(which)
+        if seeds is None and streams is None:
+            seeds = os.urandom(32 * B)
+        if tag_seeds is None and tag_streams is None:
+            tag_seeds = os.urandom(32 * B)
+        rng, _keep = self._rng(B, seeds, streams, stream_blocks)
+        rng_tags, _keep2 = self._rng(B, tag_seeds, tag_streams, tag_stream_blocks)
+        size = max(self.accountable_proof_max_size() * B, 16)
+        out = C.create_string_buffer(size)
+        off = (C.c_uint64 * (B + 1))()
+        st = (C.c_int32 * max(B, 1))()
+        pst = (C.c_int32 * max(2 * B, 1))()
+        w = (C.c_uint32 * max(B, 1))(*which)
+        self._chk(self.L.zk_accountable_prove_batch(self.h, B, bytes(msg), bytes(sig), bytes(pk), w, C.byref(rng), C.byref(rng_tags), out, size if cap is None else cap, off, st,
+                                                    pst if want_part_status else None))
+        raw = out.raw
+        self.accountable_last_raw = (raw[:off[B]], list(off))
+        return ([raw[off[b]:off[b + 1]] if st[b] == 0 else None for b in range(B)], list(st)[:B],
+                [(pst[2 * b], pst[2 * b + 1]) for b in range(B)] if want_part_status else None)
+
+    def accountable_prove_batch_device(self, B, d_msg, d_sig, d_pk, d_which, d_rng, d_rng_tags, d_out, out_cap, d_out_off, d_status, d_part_status=None, mode=0, stride_blocks=0,
+                                       tag_mode=0, tag_stride_blocks=0):
+        rng, rng_tags = ZkRng(mode, d_rng, stride_blocks), ZkRng(tag_mode, d_rng_tags, tag_stride_blocks)
+        self._chk(self.L.zk_accountable_prove_batch_device(self.h, B, d_msg, d_sig, d_pk, d_which, C.byref(rng), C.byref(rng_tags), d_out, out_cap, d_out_off, d_status,
+                                                           d_part_status))
+
+    def accountable_verify_batch(self, msg, bundles, vseeds=None, want_first_bad=True, blob=None, offsets=None):
+        """zk_accountable_verify_batch: bundle b against row b of msg.  bundles: a list of byte strings, or one blob with offsets (B + 1 entries).  Returns (ok
+        list, status list, first_bad list): first_bad is 0 for the attestation, 1 for the tag and 0xFFFFFFFF where ok is 1."""
+        if blob is None:
+            blob, off = b''.join(bundles), self._slots(bundles)
+        else:
+            off = (C.c_uint64 * len(offsets))(*offsets)
+        B = len(off) - 1
+        ok = (C.c_uint8 * max(B, 1))()
+        st = (C.c_int32 * max(B, 1))()
+        bad = (C.c_uint32 * max(B, 1))()
+        self._chk(self.L.zk_accountable_verify_batch(self.h, B, bytes(msg), bytes(blob) if len(blob) else bytes(16), off, None if vseeds is None else bytes(vseeds), ok, st,
+                                                     bad if want_first_bad else None))
+        return list(ok)[:B], list(st)[:B], list(bad)[:B] if want_first_bad else None
+
+    def accountable_verify_batch_device(self, B, d_msg, d_bundles, d_bundle_off, d_vseeds, d_ok, d_status, d_first_bad=None):
+        self._chk(self.L.zk_accountable_verify_batch_device(self.h, B, d_msg, d_bundles, d_bundle_off, d_vseeds, d_ok, d_status, d_first_bad))
+
+    def accountable_split(self, bundles, cap=None, blob=None, offsets=None):
+        """zk_accountable_split_batch: pure layout.  Returns (attestations: list of byte strings, b'' for a refused bundle; tags: list of 472-byte strings, zero
+        bytes for a refused bundle; statuses).  self.accountable_last_raw keeps the attestations' (bytes, offsets) as the call wrote them."""
+        if blob is None:
+            blob, off = b''.join(bundles), self._slots(bundles)
+        else:
+            off = (C.c_uint64 * len(offsets))(*offsets)
+        B = len(off) - 1
+        size = max(len(blob), 16)
+        att = C.create_string_buffer(size)
+        aoff = (C.c_uint64 * (B + 1))()
+        tags = C.create_string_buffer(max(472 * B, 1))
+        st = (C.c_int32 * max(B, 1))()
+        self._chk(self.L.zk_accountable_split_batch(self.h, B, bytes(blob) if len(blob) else bytes(16), off, att, size if cap is None else cap, aoff, tags, st))
+        raw, traw = att.raw, tags.raw
+        self.accountable_last_raw = (raw[:aoff[B]], list(aoff))
+        return [raw[aoff[b]:aoff[b + 1]] for b in range(B)], [traw[472 * b:472 * b + 472] for b in range(B)], list(st)[:B]
+
+    def accountable_split_device(self, B, d_bundles, d_bundle_off, d_att_out, att_cap, d_att_off, d_tags_out, d_status):
+        self._chk(self.L.zk_accountable_split_batch_device(self.h, B, d_bundles, d_bundle_off, d_att_out, att_cap, d_att_off, d_tags_out, d_status))
+
+    def accountable_join(self, proofs, tags, cap=None):
+        """zk_accountable_join_batch: pure layout.  Returns (bundles: list of byte strings, None where join refuses; statuses)."""
+        B = len(proofs)
+        if len(tags) != B or any(len(t) != 472 for t in tags):
+            raise ValueError('one 472-byte tag per proof')
+        off = self._slots(proofs)
+        size = max(off[B] + 488 * B, 16)
+        out = C.create_string_buffer(size)
+        ooff = (C.c_uint64 * (B + 1))()
+        st = (C.c_int32 * max(B, 1))()
+        self._chk(self.L.zk_accountable_join_batch(self.h, B, b''.join(proofs) if off[B] else bytes(16), off, b''.join(tags) if B else bytes(472), out, size if cap is None else cap,
+                                                   ooff, st))
+        raw = out.raw
+        self.accountable_last_raw = (raw[:ooff[B]], list(ooff))
+        return [raw[ooff[b]:ooff[b + 1]] if st[b] == 0 else None for b in range(B)], list(st)[:B]
+
+    def accountable_join_device(self, B, d_proofs, d_proof_off, d_tags, d_out, out_cap, d_out_off, d_status):
+        self._chk(self.L.zk_accountable_join_batch_device(self.h, B, d_proofs, d_proof_off, d_tags, d_out, out_cap, d_out_off, d_status))
 
     # ---- threshold opening (zk_ctx_set_auditors, zk_auditors_*): t of n auditors open a tag through verifiable shares ("ZKS1", 264 bytes)
     def auditors_share_size(self):

@@ -6,6 +6,7 @@
 #include "ctx.h"
 #include "jobs.h"
 #include "escrow_share.h"
+#include "accountable.h"
 
 #define ZK_AUDITOR_BITS 16   // comb width of the (g, A) set: 0.13 GB per base (24 bits: 23 GB); a tag's bytes do not depend on it
 
@@ -227,6 +228,10 @@ extern "C" zk_status zk_escrow_prove_batch_device(zk_ctx* c, uint64_t B, const v
     if (zs && c->params_set && !c->stream_busy) wipe_witness(c);
     return zs;
 }
+// zk_escrow_prove_batch_device's pipeline for api_accountable.hip (accountable.h)
+zk_status zkc_escrow_prove(zk_ctx* c, uint64_t B, const uint8_t* key, const uint8_t* com, const uint8_t* blinder, const zk_rng& rng, uint8_t* out, int32_t* status) {
+    return escrow_prove_device(c, B, {key, com, blinder, out, status}, rng, B * ZKT1_SIZE);
+}
 // Host pointers: key, blinder and seeds through the context's witness-flagged input buffer, the tags through its output staging buffer.
 struct EscrowProveIn {
     uint8_t *key, *com, *blinder, *rng;
@@ -302,6 +307,10 @@ extern "C" zk_status zk_escrow_verify_batch_device(zk_ctx* c, uint64_t B, const 
     if (!c || (B && (!d_com || !d_tags || !d_ok || !d_status))) return ZK_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     return escrow_verify_device(c, B, {(const uint8_t*)d_com, (const uint8_t*)d_tags, (uint8_t*)d_ok, (int32_t*)d_status});
+}
+// zk_escrow_verify_batch_device's pipeline for api_accountable.hip (accountable.h)
+zk_status zkc_escrow_verify(zk_ctx* c, uint64_t B, const uint8_t* com, const uint8_t* tags, uint8_t* ok, int32_t* status) {
+    return escrow_verify_device(c, B, {com, tags, ok, status});
 }
 struct EscrowVerifyIn {   // no witness is staged: a failing copy returns as it is
     uint8_t *com, *ok;

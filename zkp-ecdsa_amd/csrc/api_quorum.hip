@@ -23,11 +23,7 @@ static zk_status quorum_refusal(zk_ctx* c, uint64_t Q, uint32_t k, bool rings) {
     if (c->stream_busy) return busy_refusal(c);
     return ZK_OK;
 }
-static bool quorum_aligned(std::initializer_list<const void*> ps) {   // the kernels read and write 32-bit words
-    for (const void* p : ps)
-        if ((uintptr_t)p & 3) return false;
-    return true;
-}
+static bool quorum_aligned(std::initializer_list<const void*> ps) { return words_aligned(ps); }
 // The `_rings` forms: the context's rings as the capacity rule sees them (quorum_plan.h), and what a call's ids come to
 static void quorum_rings_table(const zk_ctx* c, QuorumRings& R) {
     R = QuorumRings{};
@@ -78,42 +74,10 @@ extern "C" uint64_t zk_rings_quorum_proof_max_size(const zk_ctx* c, uint32_t k, 
     quorum_rings_table(c, R);
     return zkq_max_size_rings(R, k, ring_ids);
 }
-static uint32_t quorum_window(const zk_ctx* c, uint32_t k) { return std::max<uint32_t>(1, c->chunk * std::min<uint32_t>(c->lanes, ZK_MAX_LANES) / k); }   // quorums per window
-static size_t rng_row(const zk_rng& r) { return r.mode == ZK_RNG_SEED ? 32 : 32 * (size_t)r.stride_blocks; }
+static uint32_t quorum_window(const zk_ctx* c, uint32_t k) { return window_rows(c, k); }   // quorums per window
+static size_t rng_row(const zk_rng& r) { return rng_row_bytes(r); }
 
-// zk_last_timing of a call that runs other calls' pipelines window by window: every pipeline leaves its own record, which is added up here by family name;
-// the kernels of this file run in scopes of their own between them.
-struct QuorumTiming {
-    zk_ctx* c;
-    bool timed;
-    std::vector<std::pair<const char*, float>> acc;
-    float total = 0, wall = 0;
-    void absorb() {
-        for (auto& p : c->last_timing) {
-            bool found = false;
-            for (auto& a : acc)
-                if (!strcmp(a.first, p.first)) a.second += p.second, found = true;
-            if (!found) acc.push_back(p);
-        }
-        total += c->last_total_ms, wall += c->last_wall_ms;
-    }
-    template <class F>
-    zk_status phase(const char* name, F&& f) {   // f enqueues on c->stream; the stream is drained behind it (the next pipeline's lanes do not wait for c->stream)
-        if (timed) timing_begin(c);
-        zk_status zs;
-        {
-            MaybeScope t(timed, c, name, c->stream);
-            zs = f();
-        }
-        const hipError_t e = hipStreamSynchronize(c->stream);
-        if (zs) return zs;
-        HIPCHK(c, e);
-        HIPCHK(c, hipGetLastError());
-        if (timed) timing_end(c), absorb();
-        return ZK_OK;
-    }
-    void publish() { c->last_timing = acc, c->last_total_ms = total, c->last_wall_ms = wall; }
-};
+using QuorumTiming = PipelineTiming;   // (jobs.h)
 
 // ------------------------------------------------------------------ prover
 struct QuorumProveWin {

@@ -56,7 +56,8 @@ enum GrowPolicy {
     X(dk, GROW_SHED, true)        /* distinct-key proofs (api_distinct.hip): the lanes' arenas -- the staged keys and blinders, d, 1 / d, r_w, the nonces, the RNG fills, the challenge's message */ \
     X(qs, GROW_SHED, true)        /* quorum proofs (api_quorum.hip): a window's staging -- the gathered keys, keyXcoms and blinders of its pairs, its attestations and distinct-key proofs until they are in place; verifier: the walked offsets, the members' and pairs' bytes and verdicts */ \
     X(et, GROW_SHED, true)        /* escrow tags (api_escrow.hip): the lanes' arenas -- the staged key and blinder, rho and the nonces, the RNG fills, the challenge's message; an open call's staged secret a, the points 4 (E2 - a E1) and a slab of the ring's points */ \
-    X(qc, GROW_SLACK, false)      /* ... the quorum calls' `_rings` forms: every quorum's capacity, the call's total and the set of rings its ids name (from ring ids: public) */
+    X(qc, GROW_SLACK, false)      /* ... the quorum calls' `_rings` forms: every quorum's capacity, the call's total and the set of rings its ids name (from ring ids: public) */ \
+    X(as, GROW_SHED, true)        /* accountable attestations (api_accountable.hip): a window's staging -- the gathered keys, blinders and keyXcoms, its attestations and tags until they are in place; verifier, split and join: the walk's records, the attestations' and tags' bytes and verdicts */
 enum BufId {
 #define X(name, policy, witness) B_##name,
     ZK_CTX_BUFS(X)

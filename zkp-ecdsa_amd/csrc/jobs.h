@@ -137,3 +137,45 @@ zk_status verify_host(zk_ctx* c, uint64_t B, const uint8_t* msg, const uint8_t* 
 // bytes of the expansion staging and entries of the offset array for a ZKA1P batch of B proofs, `total` packed bytes, chunks of C proofs
 static inline size_t unpack_stage_bytes(uint64_t B, uint64_t total, uint32_t C) { return (size_t)((total * 12 + 10) / 11 + 32 * B + 256 * (B / (C ? C : 1) + 2) + 64); }
 static inline size_t unpack_off_entries(uint64_t B, uint32_t C) { return (size_t)(B + B / (C ? C : 1) + 4); }
+
+// Shared by the calls that run other calls' pipelines window by window (api_quorum.hip, api_accountable.hip)
+static inline bool words_aligned(std::initializer_list<const void*> ps) {   // the kernels read and write 32-bit words
+    for (const void* p : ps)
+        if ((uintptr_t)p & 3) return false;
+    return true;
+}
+static inline size_t rng_row_bytes(const zk_rng& r) { return r.mode == ZK_RNG_SEED ? 32 : 32 * (size_t)r.stride_blocks; }   // one proof's row of rng->data
+static inline uint32_t window_rows(const zk_ctx* c, uint32_t per) { return std::max<uint32_t>(1, c->chunk * std::min<uint32_t>(c->lanes, ZK_MAX_LANES) / per); }   // units of `per` proofs per window
+// zk_last_timing of a call that runs other calls' pipelines window by window: every pipeline leaves its own record, which is added up here by family name;
+// the caller's own kernels run in scopes of their own between them (api_quorum.hip, api_accountable.hip).
+struct PipelineTiming {
+    zk_ctx* c;
+    bool timed;
+    std::vector<std::pair<const char*, float>> acc;
+    float total = 0, wall = 0;
+    void absorb() {
+        for (auto& p : c->last_timing) {
+            bool found = false;
+            for (auto& a : acc)
+                if (!strcmp(a.first, p.first)) a.second += p.second, found = true;
+            if (!found) acc.push_back(p);
+        }
+        total += c->last_total_ms, wall += c->last_wall_ms;
+    }
+    template <class F>
+    zk_status phase(const char* name, F&& f) {   // f enqueues on c->stream; the stream is drained behind it (the next pipeline's lanes do not wait for c->stream)
+        if (timed) timing_begin(c);
+        zk_status zs;
+        {
+            MaybeScope t(timed, c, name, c->stream);
+            zs = f();
+        }
+        const hipError_t e = hipStreamSynchronize(c->stream);
+        if (zs) return zs;
+        HIPCHK(c, e);
+        HIPCHK(c, hipGetLastError());
+        if (timed) timing_end(c), absorb();
+        return ZK_OK;
+    }
+    void publish() { c->last_timing = acc, c->last_total_ms = total, c->last_wall_ms = wall; }
+};
