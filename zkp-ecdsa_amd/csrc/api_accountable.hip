@@ -25,7 +25,6 @@ static zk_status acc_refusal(zk_ctx* c, uint64_t B, bool proving) {
     if (c->stream_busy) return busy_refusal(c);
     return ZK_OK;
 }
-static bool acc_aligned(std::initializer_list<const void*> ps) { return words_aligned(ps); }
 static uint32_t acc_window(const zk_ctx* c) { return window_rows(c, 1); }   // bundles per window
 static size_t acc_rng_row(const zk_rng& r) { return rng_row_bytes(r); }
 using AccTiming = PipelineTiming;   // (jobs.h)
@@ -67,7 +66,7 @@ static zk_status acc_prove_device(zk_ctx* c, uint64_t B, const AccProveIo& io, c
     if (!rng_mode_ok(&rng) || !rng_mode_ok(&rng_tags)) return ZK_E_ARG;
     hipStream_t s = c->stream;
     if (B == 0) {
-        if (!acc_aligned({io.out_off})) return ZK_E_ARG;
+        if (!words_aligned({io.out_off})) return ZK_E_ARG;
         HIPCHK(c, hipMemsetAsync(io.out_off, 0, 8, s));
         HIPCHK(c, hipStreamSynchronize(s));
         return ZK_OK;
@@ -77,7 +76,7 @@ static zk_status acc_prove_device(zk_ctx* c, uint64_t B, const AccProveIo& io, c
         c->err = "output buffer too small";
         return ZK_E_BUFFER;
     }
-    if (!acc_aligned({io.msg, io.sig, io.pk, io.which, io.out, io.out_off, io.status, io.part_status, rng.data, rng_tags.data})) return ZK_E_ARG;
+    if (!words_aligned({io.msg, io.sig, io.pk, io.which, io.out, io.out_off, io.status, io.part_status, rng.data, rng_tags.data})) return ZK_E_ARG;
     const uint32_t Wn = (uint32_t)std::min<uint64_t>(B, acc_window(c));
     AccProveWin W;
     if (zk_status zs = lay_out(c, B_as, [&](uint8_t* base) { return acc_prove_layout(W, base, Wn, proof_max); })) return zs;
@@ -220,7 +219,7 @@ struct AccVerifyIo {   // device pointers
 static zk_status acc_verify_device(zk_ctx* c, uint64_t B, const AccVerifyIo& io, const uint64_t* h_off) {
     if (zk_status zs = acc_refusal(c, B, true)) return zs;
     if (B == 0) return ZK_OK;
-    if (!acc_aligned({io.msg, io.bundles, io.off, io.vseeds, io.ok, io.status, io.first_bad})) return ZK_E_ARG;
+    if (!words_aligned({io.msg, io.bundles, io.off, io.vseeds, io.ok, io.status, io.first_bad})) return ZK_E_ARG;
     hipStream_t s = c->stream;
     std::vector<uint64_t> off_copy;
     if (zk_status zs = acc_offsets(c, B, io.off, off_copy, h_off)) return zs;
@@ -314,12 +313,12 @@ static zk_status acc_split_device(zk_ctx* c, uint64_t B, const uint8_t* bundles,
     if (zk_status zs = acc_refusal(c, B, false)) return zs;
     hipStream_t s = c->stream;
     if (B == 0) {
-        if (!acc_aligned({att_off})) return ZK_E_ARG;
+        if (!words_aligned({att_off})) return ZK_E_ARG;
         HIPCHK(c, hipMemsetAsync(att_off, 0, 8, s));
         HIPCHK(c, hipStreamSynchronize(s));
         return ZK_OK;
     }
-    if (!acc_aligned({bundles, off, att_out, att_off, tags_out, status})) return ZK_E_ARG;
+    if (!words_aligned({bundles, off, att_out, att_off, tags_out, status})) return ZK_E_ARG;
     std::vector<uint64_t> off_copy;
     if (zk_status zs = acc_offsets(c, B, off, off_copy, h_off)) return zs;
     uint64_t need = 0;   // what the attestations can come to, from the offsets alone: before a byte of any output is written
@@ -410,12 +409,12 @@ static zk_status acc_join_device(zk_ctx* c, uint64_t B, const uint8_t* proofs, c
     if (zk_status zs = acc_refusal(c, B, false)) return zs;
     hipStream_t s = c->stream;
     if (B == 0) {
-        if (!acc_aligned({out_off})) return ZK_E_ARG;
+        if (!words_aligned({out_off})) return ZK_E_ARG;
         HIPCHK(c, hipMemsetAsync(out_off, 0, 8, s));
         HIPCHK(c, hipStreamSynchronize(s));
         return ZK_OK;
     }
-    if (!acc_aligned({proofs, off, tags, out, out_off, status})) return ZK_E_ARG;
+    if (!words_aligned({proofs, off, tags, out, out_off, status})) return ZK_E_ARG;
     std::vector<uint64_t> off_copy;
     if (zk_status zs = acc_offsets(c, B, off, off_copy, h_off)) return zs;
     if (out_cap < acc_join_need(B, h_off)) {   // before a byte of any output is written

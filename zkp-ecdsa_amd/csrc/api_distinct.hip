@@ -3,90 +3,36 @@
 // are k_tom.hip's comb kernels, the challenge hash k_hash.hip's message path.  No ring takes part.  The chunks run on the context's lanes (their streams are
 // the prover lanes'), every lane's arena carved from one witness-flagged buffer.
 #include "ctx.h"
-#include "jobs.h"
+#include "sigma.h"
 #include "distinct.h"
 
-static size_t dist_carve(DistLane* K, uint32_t nlanes, uint8_t* base, uint32_t C) {
-    SoaCarver k(base);
-    for (uint32_t l = 0; l < nlanes; l++) {
-        DistLane& X = K[l];
-        X = DistLane{};
-        X.C = C;
-        X.L = k.list(DIST_SLOTS * (size_t)C);
-        X.rng.exc_idx = (uint32_t*)k.take(4 * RNG_MAX_EXC * (size_t)C);
-        X.rng.exc_flags = (uint32_t*)k.take(4 * RNG_MAX_EXC * (size_t)C);
-        X.rng.exc_cnt = (uint32_t*)k.take(4 * (size_t)C);
-        X.rng_fill = (uint32_t*)k.take(32 * (size_t)DIST_RNG_BLOCKS * C);
-        X.st = (int32_t*)k.take(4 * (size_t)C);
-        X.flags = (uint32_t*)k.take(4 * (size_t)C);
-        X.cw = (uint32_t*)k.take(4 * 36 * (size_t)C);
-        X.msg = (uint8_t*)k.take((size_t)ZKD1_MSG_BLOCKS * 64 * C);
-        X.wk = (uint32_t*)k.take((size_t)ZKD1_MSG_BLOCKS * 256 * C);
-        X.chal = (uint32_t*)k.take(16 * (size_t)C);
-        X.tw = (uint32_t*)k.take(32 * (size_t)C);
-        X.tab = (DistQuad*)k.take(sizeof(DistQuad) * DIST_TAB_QUADS * (size_t)C);
-        X.rel = (uint32_t*)k.take(12 * (size_t)C);
-    }
-    return k.off + ZK_LAYOUT_TAIL;
-}
-static zk_status dist_refusal(zk_ctx* c, uint64_t B) {
-    if (!c->params_set) return ZK_E_BUFFER;
-    if (c->stream_busy) return busy_refusal(c);
-    if (B > 0xffffffffull) return ZK_E_ARG;
-    return ZK_OK;
-}
-static bool dist_aligned(std::initializer_list<const void*> ps) {   // the kernels read and write 32-bit words
-    for (const void* p : ps)
-        if ((uintptr_t)p & 3) return false;
-    return true;
+static void dist_carve(SoaCarver& k, DistLane& X, uint32_t C) {
+    X = DistLane{};
+    sigma_carve_core(k, X, C, DIST_SLOTS, DIST_RNG_BLOCKS, ZKD1_MSG_BLOCKS);
+    X.cw = (uint32_t*)k.take(4 * 36 * (size_t)C);
+    X.tw = (uint32_t*)k.take(32 * (size_t)C);
+    X.tab = (DistQuad*)k.take(sizeof(DistQuad) * DIST_TAB_QUADS * (size_t)C);
+    X.rel = (uint32_t*)k.take(12 * (size_t)C);
 }
 extern "C" uint64_t zk_distinct_proof_size(void) { return ZKD1_SIZE; }
-
-// The chunk plan of a call of B proofs and its lanes' arenas
-struct DistRun {
-    std::vector<ChunkPlan> plan;
-    uint32_t NL = 0;
-    DistLane K[ZK_MAX_LANES];
-};
-static zk_status dist_plan(zk_ctx* c, uint64_t B, DistRun& R) {
-    const uint32_t C = (uint32_t)std::min<uint64_t>(c->chunk, B);
-    R.plan = make_chunk_plan(B, C, 1, false);
-    R.NL = (uint32_t)std::min<size_t>(std::min<uint32_t>(c->lanes, ZK_MAX_LANES), R.plan.size());
-    return lay_out(c, B_dk, [&](uint8_t* base) { return dist_carve(R.K, R.NL, base, C); });
-}
+typedef SigmaRun<DistLane> DistRun;
 
 // ------------------------------------------------------------------ prover
 static zk_status dist_prove_device(zk_ctx* c, uint64_t B, const DistProveIo& io, const zk_rng& rng, uint64_t out_cap) {
-    if (zk_status zs = dist_refusal(c, B)) return zs;
-    if (!rng_mode_ok(&rng)) return ZK_E_ARG;
-    if (B > out_cap / ZKD1_SIZE) {
-        c->err = "output buffer too small";
-        return ZK_E_BUFFER;
-    }
-    if (B == 0) return ZK_OK;
-    if (!dist_aligned({io.key1, io.com1, io.blinder1, io.key2, io.com2, io.blinder2, io.out, io.status, rng.data})) return ZK_E_ARG;
+    zk_status gate;
+    if (sigma_prove_gate(c, B, rng, out_cap, ZKD1_SIZE, gate)) return gate;
+    if (!words_aligned({io.key1, io.com1, io.blinder1, io.key2, io.com2, io.blinder2, io.out, io.status, rng.data})) return ZK_E_ARG;
     timing_begin(c);   // (behind every refusal: a call that runs nothing leaves the last call's record as it is)
     DistRun R;
-    if (zk_status zs = dist_plan(c, B, R)) return zs;
+    if (zk_status zs = sigma_plan(c, B, B_dk, R, dist_carve)) return zs;
     const bool timed = zk_timed(c, B);
-    for (uint64_t k = 0; k < R.plan.size(); k++) {
-        const uint32_t lane = (uint32_t)(k % R.NL), cnt = R.plan[k].cnt;
-        const uint64_t first = R.plan[k].first;
-        DistLane& K = R.K[lane];
-        hipStream_t s = c->pl[lane].stream;
-        K.rng.seeds = rng.data, K.rng.stream = rng.data, K.rng.stride_blocks = rng.stride_blocks, K.rng.mode = rng.mode, K.rng.sec = -1, K.rng.proof_base = (uint32_t)first;
-        {
-            MaybeScope t(timed, c, "rng_prepass", s);
-            Workspace W{};   // the prepass reads a workspace's RNG view
-            W.rng = K.rng;
-            launch_rng_prepass(s, W, cnt, 0, DIST_RNG_BLOCKS, DIST_RNG_BLOCKS, rng.mode == ZK_RNG_SEED ? K.rng_fill : nullptr, false);
-        }
-        if (rng.mode == ZK_RNG_SEED) K.rng.mode = ZK_RNG_STREAM, K.rng.stream = (const uint8_t*)K.rng_fill, K.rng.stride_blocks = DIST_RNG_BLOCKS, K.rng.proof_base = 0;
+    return sigma_run_chunks(c, R, true, [&](DistLane& K, hipStream_t s, uint32_t cnt, uint64_t first) {
+        sigma_chunk_rng(c, timed, s, K.rng, K.rng_fill, rng, first, cnt, DIST_RNG_BLOCKS);
         {
             MaybeScope t(timed, c, "tom_commit", s);
             launch_dist_front(s, K, cnt, first, io);
             launch_tom_commit_pair_slots(s, c->P, K.L, cnt);                                    // (A_z, A_4_1): k_z g once
-            launch_tom_commit(s, c->P, dist_view(K.L, 2 * cnt), DIST_SINGLES * cnt, 1, 1);      // C_w, C_4, A_x, A_y, A_4_2 and the two claimed openings
+            launch_tom_commit(s, c->P, tom_list_from(K.L, 2 * cnt), DIST_SINGLES * cnt, 1, 1);  // C_w, C_4, A_x, A_y, A_4_2 and the two claimed openings
         }
         {
             MaybeScope t(timed, c, "tom_normalize", s);
@@ -95,19 +41,13 @@ static zk_status dist_prove_device(zk_ctx* c, uint64_t B, const DistProveIo& io,
         {
             MaybeScope t(timed, c, "hash", s);
             launch_dist_opening_msg(s, c->P, K, cnt);
-            launch_dist_hash(s, K, cnt);
+            launch_sigma_hash(s, K, cnt, ZKD1_MSG_BLOCKS);
         }
         {
             MaybeScope t(timed, c, "distinct_respond", s);
             launch_dist_respond(s, K, cnt, first, io);
         }
-    }
-    const hipError_t e_sync = drain_lanes(c, R.NL);
-    if (e_sync != hipSuccess) wipe_witness(c);   // a failed call leaves no key, inverse, nonce, blinder or RNG block behind
-    HIPCHK(c, e_sync);
-    HIPCHK(c, hipGetLastError());
-    timing_end(c);
-    return ZK_OK;
+    });   // (a failed call leaves no key, inverse, nonce, blinder or RNG block behind)
 }
 extern "C" zk_status zk_distinct_prove_batch_device(zk_ctx* c, uint64_t B, const void* d_key1, const void* d_com1, const void* d_blinder1, const void* d_key2, const void* d_com2,
                                                     const void* d_blinder2, const zk_rng* rng, void* d_out, uint64_t out_cap, void* d_status) {
@@ -134,13 +74,8 @@ extern "C" zk_status zk_distinct_prove_batch(zk_ctx* c, uint64_t B, const uint8_
                                              const uint8_t* blinder2, const zk_rng* rng, uint8_t* out, uint64_t out_cap, int32_t* status) {
     if (!c || !rng || (B && (!key1 || !com1 || !blinder1 || !key2 || !com2 || !blinder2 || !rng->data || !out || !status))) return ZK_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    if (zk_status zs = dist_refusal(c, B)) return zs;
-    if (!rng_mode_ok(rng)) return ZK_E_ARG;
-    if (B > out_cap / ZKD1_SIZE) {
-        c->err = "output buffer too small";
-        return ZK_E_BUFFER;
-    }
-    if (B == 0) return ZK_OK;
+    zk_status gate;
+    if (sigma_prove_gate(c, B, *rng, out_cap, ZKD1_SIZE, gate)) return gate;
     DistProveIn I;
     if (zk_status zs = lay_out(c, B_in, [&](uint8_t* base) { return dist_prove_in_layout(I, base, B, rng_bytes(rng, B)); })) return zs;
     if (zk_status zs = reserve(c, B_io, B * ZKD1_SIZE)) return zs;
@@ -158,18 +93,14 @@ extern "C" zk_status zk_distinct_prove_batch(zk_ctx* c, uint64_t B, const uint8_
 
 // ------------------------------------------------------------------ verifier
 static zk_status dist_verify_device(zk_ctx* c, uint64_t B, const DistVerifyIo& io) {
-    if (zk_status zs = dist_refusal(c, B)) return zs;
+    if (zk_status zs = sigma_refusal(c, B)) return zs;
     if (B == 0) return ZK_OK;
-    if (!dist_aligned({io.com1, io.com2, io.proofs, io.status})) return ZK_E_ARG;
+    if (!words_aligned({io.com1, io.com2, io.proofs, io.status})) return ZK_E_ARG;
     timing_begin(c);
     DistRun R;
-    if (zk_status zs = dist_plan(c, B, R)) return zs;
+    if (zk_status zs = sigma_plan(c, B, B_dk, R, dist_carve)) return zs;
     const bool timed = zk_timed(c, B);
-    for (uint64_t k = 0; k < R.plan.size(); k++) {
-        const uint32_t lane = (uint32_t)(k % R.NL), cnt = R.plan[k].cnt;
-        const uint64_t first = R.plan[k].first;
-        const DistLane& K = R.K[lane];
-        hipStream_t s = c->pl[lane].stream;
+    return sigma_run_chunks(c, R, false, [&](const DistLane& K, hipStream_t s, uint32_t cnt, uint64_t first) {
         {
             MaybeScope t(timed, c, "distinct_parse", s);
             launch_dist_parse(s, c->P, K, cnt, first, io);
@@ -181,7 +112,7 @@ static zk_status dist_verify_device(zk_ctx* c, uint64_t B, const DistVerifyIo& i
         {
             MaybeScope t(timed, c, "hash", s);
             launch_dist_cx_msg(s, K, cnt);
-            launch_dist_hash(s, K, cnt);
+            launch_sigma_hash(s, K, cnt, ZKD1_MSG_BLOCKS);
         }
         {
             MaybeScope t(timed, c, "tom_commit", s);
@@ -196,11 +127,7 @@ static zk_status dist_verify_device(zk_ctx* c, uint64_t B, const DistVerifyIo& i
             MaybeScope t(timed, c, "distinct_long", s);
             launch_dist_long(s, K, cnt, first, io);
         }
-    }
-    HIPCHK(c, drain_lanes(c, R.NL));
-    HIPCHK(c, hipGetLastError());
-    timing_end(c);
-    return ZK_OK;
+    });
 }
 extern "C" zk_status zk_distinct_verify_batch_device(zk_ctx* c, uint64_t B, const void* d_com1, const void* d_com2, const void* d_proofs, void* d_ok, void* d_status) {
     if (!c || (B && (!d_com1 || !d_com2 || !d_proofs || !d_ok || !d_status))) return ZK_E_ARG;
@@ -219,22 +146,15 @@ static size_t dist_verify_in_layout(DistVerifyIn& I, uint8_t* base, size_t B) {
 extern "C" zk_status zk_distinct_verify_batch(zk_ctx* c, uint64_t B, const uint8_t* com1, const uint8_t* com2, const uint8_t* proofs, uint8_t* ok, int32_t* status) {
     if (!c || (B && (!com1 || !com2 || !proofs || !ok || !status))) return ZK_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    if (zk_status zs = dist_refusal(c, B)) return zs;
+    if (zk_status zs = sigma_refusal(c, B)) return zs;
     if (B == 0) return ZK_OK;
     DistVerifyIn I;
     if (zk_status zs = lay_out(c, B_in, [&](uint8_t* base) { return dist_verify_in_layout(I, base, B); })) return zs;
     if (zk_status zs = reserve(c, B_io, B * ZKD1_SIZE)) return zs;
     uint8_t* const d_proofs = (uint8_t*)c->buf[B_io].p;
-    hipStream_t s = c->stream;
-    HIPCHK(c, hipMemcpyAsync(I.com1, com1, 72 * B, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(I.com2, com2, 72 * B, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_proofs, proofs, B * ZKD1_SIZE, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipStreamSynchronize(s));
+    if (zk_status zs = upload_rows(c, {{I.com1, com1, 72 * B}, {I.com2, com2, 72 * B}, {d_proofs, proofs, B * ZKD1_SIZE}})) return zs;
     if (zk_status zs = dist_verify_device(c, B, {I.com1, I.com2, d_proofs, I.ok, I.st})) return zs;
-    HIPCHK(c, hipMemcpyAsync(ok, I.ok, B, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(status, I.st, 4 * B, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    return ZK_OK;
+    return download_rows(c, {{I.ok, ok, B}, {I.st, status, 4 * B}});
 }
 
 // ------------------------------------------------------------------ the two pipelines for api_quorum.hip (quorum.h), behind the entry points' argument checks

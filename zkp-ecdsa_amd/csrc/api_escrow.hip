@@ -4,7 +4,7 @@
 // auditor's (g, A) set, the challenge hash k_hash.hip's message path.  The chunks run on the context's lanes (their streams are the prover lanes'), every
 // lane's arena carved from one witness-flagged buffer.
 #include "ctx.h"
-#include "jobs.h"
+#include "sigma.h"
 #include "escrow_share.h"
 #include "accountable.h"
 
@@ -68,20 +68,13 @@ extern "C" zk_status zk_ctx_set_auditor(zk_ctx* c, const uint8_t auditor_xy72[72
     return ZK_OK;
 }
 
-static zk_status escrow_refusal(zk_ctx* c, uint64_t B, bool need_auditor) {
-    if (!c->params_set) return ZK_E_BUFFER;
-    if (c->stream_busy) return busy_refusal(c);
-    if (B > 0xffffffffull) return ZK_E_ARG;
-    if (need_auditor && !c->auditor_set) {
+static zk_status escrow_refusal(zk_ctx* c, uint64_t B) {   // of every call that needs the auditor's key
+    if (zk_status zs = sigma_refusal(c, B)) return zs;
+    if (!c->auditor_set) {
         c->err = "no auditor key is set (zk_ctx_set_auditor)";
         return ZK_E_BUFFER;
     }
     return ZK_OK;
-}
-static bool escrow_aligned(std::initializer_list<const void*> ps) {   // the kernels read and write 32-bit words
-    for (const void* p : ps)
-        if ((uintptr_t)p & 3) return false;
-    return true;
 }
 extern "C" uint64_t zk_escrow_tag_size(void) { return ZKT1_SIZE; }
 
@@ -104,7 +97,7 @@ static size_t escrow_keygen_layout(EscrowKeygen& G, uint8_t* base) {
 extern "C" zk_status zk_escrow_keygen(zk_ctx* c, const uint8_t secret_be32[32], uint8_t auditor_xy72[72]) {
     if (!c || !secret_be32 || !auditor_xy72) return ZK_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    if (zk_status zs = escrow_refusal(c, 1, false)) return zs;
+    if (zk_status zs = sigma_refusal(c, 1)) return zs;
     EscrowKeygen G;
     if (zk_status zs = lay_out(c, B_et, [&](uint8_t* base) { return escrow_keygen_layout(G, base); })) return zs;
     if (zk_status zs = upload_or_wipe(c, {{G.secret, secret_be32, 32}})) return zs;   // the staged secret lies in a witness-flagged buffer
@@ -123,39 +116,13 @@ extern "C" zk_status zk_escrow_keygen(zk_ctx* c, const uint8_t secret_be32[32], 
 }
 
 // ------------------------------------------------------------------ lanes
-static size_t escrow_carve(EscrowLane* K, uint32_t nlanes, uint8_t* base, uint32_t C) {
-    SoaCarver k(base);
-    for (uint32_t l = 0; l < nlanes; l++) {
-        EscrowLane& X = K[l];
-        X = EscrowLane{};
-        X.C = C;
-        X.L = k.list(ESC_SLOTS * (size_t)C);
-        X.rng.exc_idx = (uint32_t*)k.take(4 * RNG_MAX_EXC * (size_t)C);
-        X.rng.exc_flags = (uint32_t*)k.take(4 * RNG_MAX_EXC * (size_t)C);
-        X.rng.exc_cnt = (uint32_t*)k.take(4 * (size_t)C);
-        X.rng_fill = (uint32_t*)k.take(32 * (size_t)ESC_RNG_BLOCKS * C);
-        X.st = (int32_t*)k.take(4 * (size_t)C);
-        X.flags = (uint32_t*)k.take(4 * (size_t)C);
-        X.cw = (uint32_t*)k.take(4 * 18 * (size_t)C);
-        X.msg = (uint8_t*)k.take((size_t)ZKT1_MSG_BLOCKS * 64 * C);
-        X.wk = (uint32_t*)k.take((size_t)ZKT1_MSG_BLOCKS * 256 * C);
-        X.chal = (uint32_t*)k.take(16 * (size_t)C);
-        X.rel = (uint32_t*)k.take(12 * (size_t)C);
-    }
-    return k.off + ZK_LAYOUT_TAIL;
+static void escrow_carve(SoaCarver& k, EscrowLane& X, uint32_t C) {
+    X = EscrowLane{};
+    sigma_carve_core(k, X, C, ESC_SLOTS, ESC_RNG_BLOCKS, ZKT1_MSG_BLOCKS);
+    X.cw = (uint32_t*)k.take(4 * 18 * (size_t)C);
+    X.rel = (uint32_t*)k.take(12 * (size_t)C);
 }
-// The chunk plan of a call of B tags and its lanes' arenas
-struct EscrowRun {
-    std::vector<ChunkPlan> plan;
-    uint32_t NL = 0;
-    EscrowLane K[ZK_MAX_LANES];
-};
-static zk_status escrow_plan(zk_ctx* c, uint64_t B, EscrowRun& R) {
-    const uint32_t C = (uint32_t)std::min<uint64_t>(c->chunk, B);
-    R.plan = make_chunk_plan(B, C, 1, false);
-    R.NL = (uint32_t)std::min<size_t>(std::min<uint32_t>(c->lanes, ZK_MAX_LANES), R.plan.size());
-    return lay_out(c, B_et, [&](uint8_t* base) { return escrow_carve(R.K, R.NL, base, C); });
-}
+typedef SigmaRun<EscrowLane> EscrowRun;
 static EscrowKey escrow_key(const zk_ctx* c) {
     EscrowKey A;
     memcpy(A.w, c->aud_w, sizeof A.w);
@@ -164,32 +131,16 @@ static EscrowKey escrow_key(const zk_ctx* c) {
 
 // ------------------------------------------------------------------ prover
 static zk_status escrow_prove_device(zk_ctx* c, uint64_t B, const EscrowProveIo& io, const zk_rng& rng, uint64_t out_cap) {
-    if (zk_status zs = escrow_refusal(c, B, true)) return zs;
-    if (!rng_mode_ok(&rng)) return ZK_E_ARG;
-    if (B > out_cap / ZKT1_SIZE) {
-        c->err = "output buffer too small";
-        return ZK_E_BUFFER;
-    }
-    if (B == 0) return ZK_OK;
-    if (!escrow_aligned({io.com, io.key, io.blinder, io.out, io.status, rng.data})) return ZK_E_ARG;
+    zk_status gate;
+    if (sigma_prove_gate(c, B, rng, out_cap, ZKT1_SIZE, gate, escrow_refusal)) return gate;
+    if (!words_aligned({io.com, io.key, io.blinder, io.out, io.status, rng.data})) return ZK_E_ARG;
     timing_begin(c);   // (behind every refusal: a call that runs nothing leaves the last call's record as it is)
     EscrowRun R;
-    if (zk_status zs = escrow_plan(c, B, R)) return zs;
+    if (zk_status zs = sigma_plan(c, B, B_et, R, escrow_carve)) return zs;
     const bool timed = zk_timed(c, B);
     const EscrowKey A = escrow_key(c);
-    for (uint64_t k = 0; k < R.plan.size(); k++) {
-        const uint32_t lane = (uint32_t)(k % R.NL), cnt = R.plan[k].cnt;
-        const uint64_t first = R.plan[k].first;
-        EscrowLane& K = R.K[lane];
-        hipStream_t s = c->pl[lane].stream;
-        K.rng.seeds = rng.data, K.rng.stream = rng.data, K.rng.stride_blocks = rng.stride_blocks, K.rng.mode = rng.mode, K.rng.sec = -1, K.rng.proof_base = (uint32_t)first;
-        {
-            MaybeScope t(timed, c, "rng_prepass", s);
-            Workspace W{};   // the prepass reads a workspace's RNG view
-            W.rng = K.rng;
-            launch_rng_prepass(s, W, cnt, 0, ESC_RNG_BLOCKS, ESC_RNG_BLOCKS, rng.mode == ZK_RNG_SEED ? K.rng_fill : nullptr, false);
-        }
-        if (rng.mode == ZK_RNG_SEED) K.rng.mode = ZK_RNG_STREAM, K.rng.stream = (const uint8_t*)K.rng_fill, K.rng.stride_blocks = ESC_RNG_BLOCKS, K.rng.proof_base = 0;
+    return sigma_run_chunks(c, R, true, [&](EscrowLane& K, hipStream_t s, uint32_t cnt, uint64_t first) {
+        sigma_chunk_rng(c, timed, s, K.rng, K.rng_fill, rng, first, cnt, ESC_RNG_BLOCKS);
         {
             MaybeScope t(timed, c, "escrow_front", s);
             launch_escrow_front(s, K, cnt, first, io);
@@ -197,7 +148,7 @@ static zk_status escrow_prove_device(zk_ctx* c, uint64_t B, const EscrowProveIo&
         {
             MaybeScope t(timed, c, "tom_commit", s);
             launch_tom_commit(s, c->P, K.L, 4 * cnt, 1, 1);                          // E1, T1, T2 and the claimed opening on (g, h)
-            launch_tom_commit(s, c->PA, escrow_view(K.L, 4 * cnt), 2 * cnt, 1, 1);   // E2, T3 on (g, A)
+            launch_tom_commit(s, c->PA, tom_list_from(K.L, 4 * cnt), 2 * cnt, 1, 1);   // E2, T3 on (g, A)
         }
         {
             MaybeScope t(timed, c, "tom_normalize", s);
@@ -206,19 +157,13 @@ static zk_status escrow_prove_device(zk_ctx* c, uint64_t B, const EscrowProveIo&
         {
             MaybeScope t(timed, c, "hash", s);
             launch_escrow_opening_msg(s, K, A, cnt);
-            launch_escrow_hash(s, K, cnt);
+            launch_sigma_hash(s, K, cnt, ZKT1_MSG_BLOCKS);
         }
         {
             MaybeScope t(timed, c, "escrow_respond", s);
             launch_escrow_respond(s, K, cnt, first, io);
         }
-    }
-    const hipError_t e_sync = drain_lanes(c, R.NL);
-    if (e_sync != hipSuccess) wipe_witness(c);   // a failed call leaves no nonce, blinder or RNG block behind
-    HIPCHK(c, e_sync);
-    HIPCHK(c, hipGetLastError());
-    timing_end(c);
-    return ZK_OK;
+    });
 }
 extern "C" zk_status zk_escrow_prove_batch_device(zk_ctx* c, uint64_t B, const void* d_key, const void* d_com, const void* d_blinder, const zk_rng* rng, void* d_out,
                                                   uint64_t out_cap, void* d_status) {
@@ -247,13 +192,8 @@ extern "C" zk_status zk_escrow_prove_batch(zk_ctx* c, uint64_t B, const uint8_t*
                                            uint64_t out_cap, int32_t* status) {
     if (!c || !rng || (B && (!key || !com || !blinder || !rng->data || !out || !status))) return ZK_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    if (zk_status zs = escrow_refusal(c, B, true)) return zs;
-    if (!rng_mode_ok(rng)) return ZK_E_ARG;
-    if (B > out_cap / ZKT1_SIZE) {
-        c->err = "output buffer too small";
-        return ZK_E_BUFFER;
-    }
-    if (B == 0) return ZK_OK;
+    zk_status gate;
+    if (sigma_prove_gate(c, B, *rng, out_cap, ZKT1_SIZE, gate, escrow_refusal)) return gate;
     EscrowProveIn I;
     if (zk_status zs = lay_out(c, B_in, [&](uint8_t* base) { return escrow_prove_in_layout(I, base, B, rng_bytes(rng, B)); })) return zs;
     if (zk_status zs = reserve(c, B_io, B * ZKT1_SIZE)) return zs;
@@ -269,39 +209,31 @@ extern "C" zk_status zk_escrow_prove_batch(zk_ctx* c, uint64_t B, const uint8_t*
 
 // ------------------------------------------------------------------ verifier
 static zk_status escrow_verify_device(zk_ctx* c, uint64_t B, const EscrowVerifyIo& io) {
-    if (zk_status zs = escrow_refusal(c, B, true)) return zs;
+    if (zk_status zs = escrow_refusal(c, B)) return zs;
     if (B == 0) return ZK_OK;
-    if (!escrow_aligned({io.com, io.tags, io.status})) return ZK_E_ARG;
+    if (!words_aligned({io.com, io.tags, io.status})) return ZK_E_ARG;
     timing_begin(c);
     EscrowRun R;
-    if (zk_status zs = escrow_plan(c, B, R)) return zs;
+    if (zk_status zs = sigma_plan(c, B, B_et, R, escrow_carve)) return zs;
     const bool timed = zk_timed(c, B);
     const EscrowKey A = escrow_key(c);
-    for (uint64_t k = 0; k < R.plan.size(); k++) {
-        const uint32_t lane = (uint32_t)(k % R.NL), cnt = R.plan[k].cnt;
-        const uint64_t first = R.plan[k].first;
-        const EscrowLane& K = R.K[lane];
-        hipStream_t s = c->pl[lane].stream;
+    return sigma_run_chunks(c, R, false, [&](const EscrowLane& K, hipStream_t s, uint32_t cnt, uint64_t first) {
         {
             MaybeScope t(timed, c, "escrow_parse", s);
             launch_escrow_parse(s, K, A, cnt, first, io);
-            launch_escrow_hash(s, K, cnt);
+            launch_sigma_hash(s, K, cnt, ZKT1_MSG_BLOCKS);
         }
         {
             MaybeScope t(timed, c, "tom_commit", s);
             launch_tom_commit(s, c->P, K.L, 2 * cnt, 1, 1);                      // t_x g + t_r h, t_rho g
-            launch_tom_commit(s, c->PA, escrow_view(K.L, 2 * cnt), cnt, 1, 1);   // t_x g + t_rho A
+            launch_tom_commit(s, c->PA, tom_list_from(K.L, 2 * cnt), cnt, 1, 1);   // t_x g + t_rho A
         }
         {
             MaybeScope t(timed, c, "escrow_ladder", s);
             launch_escrow_relations(s, K, cnt, first, io);
             launch_escrow_verdict(s, K, cnt, first, io);
         }
-    }
-    HIPCHK(c, drain_lanes(c, R.NL));
-    HIPCHK(c, hipGetLastError());
-    timing_end(c);
-    return ZK_OK;
+    });
 }
 extern "C" zk_status zk_escrow_verify_batch_device(zk_ctx* c, uint64_t B, const void* d_com, const void* d_tags, void* d_ok, void* d_status) {
     if (!c || (B && (!d_com || !d_tags || !d_ok || !d_status))) return ZK_E_ARG;
@@ -324,21 +256,15 @@ static size_t escrow_verify_in_layout(EscrowVerifyIn& I, uint8_t* base, size_t B
 extern "C" zk_status zk_escrow_verify_batch(zk_ctx* c, uint64_t B, const uint8_t* com, const uint8_t* tags, uint8_t* ok, int32_t* status) {
     if (!c || (B && (!com || !tags || !ok || !status))) return ZK_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    if (zk_status zs = escrow_refusal(c, B, true)) return zs;
+    if (zk_status zs = escrow_refusal(c, B)) return zs;
     if (B == 0) return ZK_OK;
     EscrowVerifyIn I;
     if (zk_status zs = lay_out(c, B_in, [&](uint8_t* base) { return escrow_verify_in_layout(I, base, B); })) return zs;
     if (zk_status zs = reserve(c, B_io, B * ZKT1_SIZE)) return zs;
     uint8_t* const d_tags = (uint8_t*)c->buf[B_io].p;
-    hipStream_t s = c->stream;
-    HIPCHK(c, hipMemcpyAsync(I.com, com, 72 * B, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_tags, tags, B * ZKT1_SIZE, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipStreamSynchronize(s));
+    if (zk_status zs = upload_rows(c, {{I.com, com, 72 * B}, {d_tags, tags, B * ZKT1_SIZE}})) return zs;
     if (zk_status zs = escrow_verify_device(c, B, {I.com, d_tags, I.ok, I.st})) return zs;
-    HIPCHK(c, hipMemcpyAsync(ok, I.ok, B, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(status, I.st, 4 * B, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    return ZK_OK;
+    return download_rows(c, {{I.ok, ok, B}, {I.st, status, 4 * B}});
 }
 
 // ------------------------------------------------------------------ opening
@@ -356,13 +282,13 @@ size_t escrow_open_carve(EscrowOpen& O, uint8_t* base, uint64_t B, uint32_t slab
 // The auditor's side.  1. a g against the context's key, once; 2. one lane per tag: 4 (E2 - a E1), normalised; 3. per slab of the active ring's real keys:
 // 4 y_i g through the comb, normalised; 4. the match.  The ring's point table is rebuilt by every call.
 static zk_status escrow_open_device(zk_ctx* c, uint64_t B, const uint8_t* d_secret, const uint8_t* d_tags, uint32_t* d_index, int32_t* d_status) {
-    if (zk_status zs = escrow_refusal(c, B, true)) return zs;
+    if (zk_status zs = escrow_refusal(c, B)) return zs;
     if (!c->ring->N) {
         c->err = "no ring is active";
         return ZK_E_BUFFER;
     }
     if (B == 0) return ZK_OK;
-    if (!escrow_aligned({d_secret, d_tags, d_index, d_status})) return ZK_E_ARG;
+    if (!words_aligned({d_secret, d_tags, d_index, d_status})) return ZK_E_ARG;
     timing_begin(c);
     const uint64_t nkeys = c->ring->nkeys;
     const uint32_t slab = (uint32_t)std::min<uint64_t>(nkeys, ESC_RING_SLAB);
@@ -439,7 +365,7 @@ static size_t escrow_open_in_layout(EscrowOpenIn& I, uint8_t* base, size_t B) {
 extern "C" zk_status zk_escrow_open_batch(zk_ctx* c, uint64_t B, const uint8_t secret_be32[32], const uint8_t* tags, uint32_t* index_u32, int32_t* status) {
     if (!c || !secret_be32 || (B && (!tags || !index_u32 || !status))) return ZK_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    if (zk_status zs = escrow_refusal(c, B, true)) return zs;
+    if (zk_status zs = escrow_refusal(c, B)) return zs;
     if (!c->ring->N) {
         c->err = "no ring is active";
         return ZK_E_BUFFER;
@@ -545,9 +471,9 @@ hipError_t escrow_index_patch(zk_ctx* c, Ring& R, const uint32_t* d_ent, uint32_
 // tag: 4 (E2 - a E1), normalised (zk_escrow_open_batch's kernels); 4. one lane per tag: the lookup in the ring its id names.  The active ring is not read.
 static zk_status rings_escrow_open_device(zk_ctx* c, uint64_t B, const uint8_t* d_secret, const uint8_t* d_tags, const uint32_t* d_ids, uint32_t* d_ring_out, uint32_t* d_index,
                                           int32_t* d_status) {
-    if (zk_status zs = escrow_refusal(c, B, true)) return zs;
+    if (zk_status zs = escrow_refusal(c, B)) return zs;
     if (B == 0) return ZK_OK;
-    if (!escrow_aligned({d_secret, d_tags, d_ids, d_ring_out, d_index, d_status})) return ZK_E_ARG;
+    if (!words_aligned({d_secret, d_tags, d_ids, d_ring_out, d_index, d_status})) return ZK_E_ARG;
     timing_begin(c);
     const bool timed = zk_timed(c, B);
     hipStream_t s0 = c->stream;
@@ -627,7 +553,7 @@ extern "C" zk_status zk_rings_escrow_open_batch(zk_ctx* c, uint64_t B, const uin
                                                 uint32_t* index_u32, int32_t* status) {
     if (!c || !secret_be32 || (B && (!tags || !ring_ids || !ring_out_u32 || !index_u32 || !status))) return ZK_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    if (zk_status zs = escrow_refusal(c, B, true)) return zs;
+    if (zk_status zs = escrow_refusal(c, B)) return zs;
     if (B == 0) return ZK_OK;
     RingsEscrowOpenIn I;
     if (zk_status zs = lay_out(c, B_in, [&](uint8_t* base) { return rings_escrow_open_in_layout(I, base, B); })) return zs;

@@ -3,25 +3,18 @@
 // k_tom.hip's over the context's (g, h) combs, the challenge hash k_hash.hip's message path, the normaliser and the lookup in the resident point indexes the
 // single-auditor opening's (api_escrow.hip).  The chunks run on the context's lanes, every lane's arena carved from the escrow calls' witness-flagged buffer.
 #include "ctx.h"
-#include "jobs.h"
+#include "sigma.h"
 #include "escrow_share.h"
 
 extern "C" uint64_t zk_auditors_share_size(void) { return ZKS1_SIZE; }
 
-static zk_status share_refusal(zk_ctx* c, uint64_t B, bool need_set) {
-    if (!c->params_set) return ZK_E_BUFFER;
-    if (c->stream_busy) return busy_refusal(c);
-    if (B > 0xffffffffull) return ZK_E_ARG;
-    if (need_set && (!c->auditor_set || !c->auditors_n)) {
+static zk_status share_refusal(zk_ctx* c, uint64_t B) {   // of every call that needs the set of share keys
+    if (zk_status zs = sigma_refusal(c, B)) return zs;
+    if (!c->auditor_set || !c->auditors_n) {
         c->err = "no set of share keys is in place (zk_ctx_set_auditor, then zk_ctx_set_auditors)";
         return ZK_E_BUFFER;
     }
     return ZK_OK;
-}
-static bool share_aligned(std::initializer_list<const void*> ps) {   // the kernels read and write 32-bit words
-    for (const void* p : ps)
-        if ((uintptr_t)p & 3) return false;
-    return true;
 }
 
 // ------------------------------------------------------------------ the share keys
@@ -117,7 +110,7 @@ static size_t share_split_layout(ShareSplit& G, uint8_t* base, size_t rng_bytes)
 extern "C" zk_status zk_auditors_split_key(zk_ctx* c, const uint8_t secret_be32[32], uint32_t t, uint32_t n, const zk_rng* rng, uint8_t* shares_be32, uint8_t* share_keys_xy72) {
     if (!c || !secret_be32 || !rng || !rng->data || !shares_be32 || !share_keys_xy72) return ZK_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    if (zk_status zs = share_refusal(c, 1, false)) return zs;
+    if (zk_status zs = sigma_refusal(c, 1)) return zs;
     if (t < 1 || t > n || n > ZK_AUDITORS_MAX || !rng_mode_ok(rng)) return ZK_E_ARG;
     ShareSplit G;
     if (zk_status zs = lay_out(c, B_et, [&](uint8_t* base) { return share_split_layout(G, base, rng_bytes(rng, 1)); })) return zs;
@@ -125,12 +118,8 @@ extern "C" zk_status zk_auditors_split_key(zk_ctx* c, const uint8_t secret_be32[
     if (zk_status zs = upload_or_wipe(c, {{G.secret, secret_be32, 32}, {G.rng, rng->data, rng_bytes(rng, 1)}})) return zs;
     hipStream_t s = c->stream;
     RngCtx R{};
-    R.seeds = G.rng, R.stream = G.rng, R.stride_blocks = rng->stride_blocks, R.mode = rng->mode, R.sec = -1, R.proof_base = 0;
     R.exc_idx = G.exc_idx, R.exc_flags = G.exc_flags, R.exc_cnt = G.exc_cnt;
-    Workspace W{};   // the prepass reads a workspace's RNG view
-    W.rng = R;
-    launch_rng_prepass(s, W, 1, 0, SPLIT_RNG_BLOCKS, SPLIT_RNG_BLOCKS, rng->mode == ZK_RNG_SEED ? G.fill : nullptr, false);
-    if (rng->mode == ZK_RNG_SEED) R.mode = ZK_RNG_STREAM, R.stream = (const uint8_t*)G.fill, R.stride_blocks = SPLIT_RNG_BLOCKS;
+    sigma_chunk_rng(c, false, s, R, G.fill, zk_rng{rng->mode, G.rng, rng->stride_blocks}, 0, 1, SPLIT_RNG_BLOCKS);   // one "proof", in no timed scope
     launch_share_split(s, R, G.secret, t, n, G.L, G.shares, G.flag);
     launch_tom_commit(s, c->P, G.L, n, 1, 1);
     launch_tom_normalize(s, G.L, n, 0, 1, 1);
@@ -144,53 +133,29 @@ extern "C" zk_status zk_auditors_split_key(zk_ctx* c, const uint8_t secret_be32[
 }
 
 // ------------------------------------------------------------------ lanes
-static void share_carve_lanes(SoaCarver& k, ShareLane* K, uint32_t nlanes, uint32_t C) {
-    for (uint32_t l = 0; l < nlanes; l++) {
-        ShareLane& X = K[l];
-        X = ShareLane{};
-        X.C = C;
-        X.L = k.list(SHR_SLOTS * (size_t)C);
-        X.rng.exc_idx = (uint32_t*)k.take(4 * RNG_MAX_EXC * (size_t)C);
-        X.rng.exc_flags = (uint32_t*)k.take(4 * RNG_MAX_EXC * (size_t)C);
-        X.rng.exc_cnt = (uint32_t*)k.take(4 * (size_t)C);
-        X.rng_fill = (uint32_t*)k.take(32 * (size_t)SHR_RNG_BLOCKS * C);
-        X.st = (int32_t*)k.take(4 * (size_t)C);
-        X.flags = (uint32_t*)k.take(4 * (size_t)C);
-        X.kw = (uint32_t*)k.take(32 * (size_t)C);
-        X.msg = (uint8_t*)k.take((size_t)ZKS1_MSG_BLOCKS * 64 * C);
-        X.wk = (uint32_t*)k.take((size_t)ZKS1_MSG_BLOCKS * 256 * C);
-        X.chal = (uint32_t*)k.take(16 * (size_t)C);
-        X.tab = (DistQuad*)k.take(sizeof(DistQuad) * DIST_TAB_QUADS * (size_t)C);
-        X.rel = (uint32_t*)k.take(8 * (size_t)C);
-    }
+static void share_carve(SoaCarver& k, ShareLane& X, uint32_t C) {
+    X = ShareLane{};
+    sigma_carve_core(k, X, C, SHR_SLOTS, SHR_RNG_BLOCKS, ZKS1_MSG_BLOCKS);
+    X.kw = (uint32_t*)k.take(32 * (size_t)C);
+    X.tab = (DistQuad*)k.take(sizeof(DistQuad) * DIST_TAB_QUADS * (size_t)C);
+    X.rel = (uint32_t*)k.take(8 * (size_t)C);
 }
-// The chunk plan of a call of B tags, its lanes' arenas and, for an auditor's call, the staged secret
-struct ShareRun {
-    std::vector<ChunkPlan> plan;
-    uint32_t NL = 0;
-    ShareLane K[ZK_MAX_LANES];
+// ... and, in front of the lanes, an auditor's call's staged secret
+struct ShareRun : SigmaRun<ShareLane> {
     TomList S;            // [1] (a_j, 0), whose commitment is compared with A_j
     uint32_t* a8 = nullptr;
     uint8_t* ag = nullptr;
 };
 static zk_status share_plan(zk_ctx* c, uint64_t B, ShareRun& R) {
-    const uint32_t C = (uint32_t)std::min<uint64_t>(c->chunk, B);
-    R.plan = make_chunk_plan(B, C, 1, false);
-    R.NL = (uint32_t)std::min<size_t>(std::min<uint32_t>(c->lanes, ZK_MAX_LANES), R.plan.size());
-    return lay_out(c, B_et, [&](uint8_t* base) {
-        SoaCarver k(base);
-        R.S = k.list(1), R.a8 = (uint32_t*)k.take(32), R.ag = (uint8_t*)k.take(72);
-        share_carve_lanes(k, R.K, R.NL, C);
-        return k.off + ZK_LAYOUT_TAIL;
-    });
+    return sigma_plan(c, B, B_et, R, share_carve, [&](SoaCarver& k) { R.S = k.list(1), R.a8 = (uint32_t*)k.take(32), R.ag = (uint8_t*)k.take(72); });
 }
 
 // ------------------------------------------------------------------ an auditor's shares
 static zk_status share_device(zk_ctx* c, uint64_t B, uint32_t j, const uint8_t* d_secret, const ShareProveIo& io, const zk_rng& rng, uint64_t out_cap) {
-    if (zk_status zs = share_refusal(c, B, true)) return zs;
+    if (zk_status zs = share_refusal(c, B)) return zs;
     if (j < 1 || j > c->auditors_n || !rng_mode_ok(&rng)) return ZK_E_ARG;
     if (B == 0) return ZK_OK;
-    if (!share_aligned({d_secret, io.tags, io.out, io.status, rng.data})) return ZK_E_ARG;
+    if (!words_aligned({d_secret, io.tags, io.out, io.status, rng.data})) return ZK_E_ARG;
     ShareRun R;
     if (zk_status zs = share_plan(c, B, R)) return zs;
     timing_begin(c);   // (behind every refusal and the arenas: a call that runs nothing leaves the last call's record as it is)
@@ -217,19 +182,8 @@ static zk_status share_device(zk_ctx* c, uint64_t B, uint32_t j, const uint8_t* 
         return ZK_E_BUFFER;
     }
     const ShareSecret A{R.a8, j};
-    for (uint64_t k = 0; k < R.plan.size(); k++) {
-        const uint32_t lane = (uint32_t)(k % R.NL), cnt = R.plan[k].cnt;
-        const uint64_t first = R.plan[k].first;
-        ShareLane& K = R.K[lane];
-        hipStream_t s = c->pl[lane].stream;
-        K.rng.seeds = rng.data, K.rng.stream = rng.data, K.rng.stride_blocks = rng.stride_blocks, K.rng.mode = rng.mode, K.rng.sec = -1, K.rng.proof_base = (uint32_t)first;
-        {
-            MaybeScope t(timed, c, "rng_prepass", s);
-            Workspace W{};   // the prepass reads a workspace's RNG view
-            W.rng = K.rng;
-            launch_rng_prepass(s, W, cnt, 0, SHR_RNG_BLOCKS, SHR_RNG_BLOCKS, rng.mode == ZK_RNG_SEED ? K.rng_fill : nullptr, false);
-        }
-        if (rng.mode == ZK_RNG_SEED) K.rng.mode = ZK_RNG_STREAM, K.rng.stream = (const uint8_t*)K.rng_fill, K.rng.stride_blocks = SHR_RNG_BLOCKS, K.rng.proof_base = 0;
+    return sigma_run_chunks(c, R, true, [&](ShareLane& K, hipStream_t s, uint32_t cnt, uint64_t first) {
+        sigma_chunk_rng(c, timed, s, K.rng, K.rng_fill, rng, first, cnt, SHR_RNG_BLOCKS);
         {
             MaybeScope t(timed, c, "share_front", s);
             launch_share_front(s, K, cnt, first, io);
@@ -249,19 +203,13 @@ static zk_status share_device(zk_ctx* c, uint64_t B, uint32_t j, const uint8_t* 
         {
             MaybeScope t(timed, c, "hash", s);
             launch_share_msg(s, K, c->auditors_w, j, cnt, first, io);
-            launch_share_hash(s, K, cnt);
+            launch_sigma_hash(s, K, cnt, ZKS1_MSG_BLOCKS);
         }
         {
             MaybeScope t(timed, c, "share_respond", s);
             launch_share_respond(s, K, A, cnt, first, io);
         }
-    }
-    const hipError_t e_sync = drain_lanes(c, R.NL);
-    if (e_sync != hipSuccess) wipe_witness(c);   // a failed call leaves neither a_j nor a nonce or RNG block behind
-    HIPCHK(c, e_sync);
-    HIPCHK(c, hipGetLastError());
-    timing_end(c);
-    return ZK_OK;
+    });   // (a failed call leaves neither a_j nor a nonce or RNG block behind)
 }
 extern "C" zk_status zk_auditors_share_batch_device(zk_ctx* c, uint64_t B, uint32_t j, const void* d_share_secret, const void* d_tags, const zk_rng* rng, void* d_out,
                                                     uint64_t out_cap, void* d_status) {
@@ -284,7 +232,7 @@ extern "C" zk_status zk_auditors_share_batch(zk_ctx* c, uint64_t B, uint32_t j, 
                                              uint64_t out_cap, int32_t* status) {
     if (!c || !rng || !share_secret_be32 || (B && (!tags || !rng->data || !out || !status))) return ZK_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    if (zk_status zs = share_refusal(c, B, true)) return zs;
+    if (zk_status zs = share_refusal(c, B)) return zs;
     if (j < 1 || j > c->auditors_n || !rng_mode_ok(rng)) return ZK_E_ARG;
     if (B == 0) return ZK_OK;
     ShareProveIn I;
@@ -304,22 +252,18 @@ extern "C" zk_status zk_auditors_share_batch(zk_ctx* c, uint64_t B, uint32_t j, 
 
 // ------------------------------------------------------------------ the share verifier
 static zk_status share_verify_device(zk_ctx* c, uint64_t B, const ShareVerifyIo& io) {
-    if (zk_status zs = share_refusal(c, B, true)) return zs;
+    if (zk_status zs = share_refusal(c, B)) return zs;
     if (B == 0) return ZK_OK;
-    if (!share_aligned({io.tags, io.shares, io.status})) return ZK_E_ARG;
+    if (!words_aligned({io.tags, io.shares, io.status})) return ZK_E_ARG;
     ShareRun R;
     if (zk_status zs = share_plan(c, B, R)) return zs;
     timing_begin(c);
     const bool timed = zk_timed(c, B);
-    for (uint64_t k = 0; k < R.plan.size(); k++) {
-        const uint32_t lane = (uint32_t)(k % R.NL), cnt = R.plan[k].cnt;
-        const uint64_t first = R.plan[k].first;
-        const ShareLane& K = R.K[lane];
-        hipStream_t s = c->pl[lane].stream;
+    return sigma_run_chunks(c, R, false, [&](const ShareLane& K, hipStream_t s, uint32_t cnt, uint64_t first) {
         {
             MaybeScope t(timed, c, "share_parse", s);
             launch_share_parse(s, K, c->auditors_w, c->auditors_n, cnt, first, io);
-            launch_share_hash(s, K, cnt);
+            launch_sigma_hash(s, K, cnt, ZKS1_MSG_BLOCKS);
         }
         {
             MaybeScope t(timed, c, "tom_commit", s);
@@ -330,11 +274,7 @@ static zk_status share_verify_device(zk_ctx* c, uint64_t B, const ShareVerifyIo&
             launch_share_relations(s, K, c->auditors_w, cnt, first, io);
             launch_share_verdict(s, K, cnt, first, io);
         }
-    }
-    HIPCHK(c, drain_lanes(c, R.NL));
-    HIPCHK(c, hipGetLastError());
-    timing_end(c);
-    return ZK_OK;
+    });
 }
 extern "C" zk_status zk_auditors_share_verify_batch_device(zk_ctx* c, uint64_t B, const void* d_tags, const void* d_shares, void* d_ok, void* d_status) {
     if (!c || (B && (!d_tags || !d_shares || !d_ok || !d_status))) return ZK_E_ARG;
@@ -353,28 +293,22 @@ static size_t share_verify_in_layout(ShareVerifyIn& I, uint8_t* base, size_t B) 
 extern "C" zk_status zk_auditors_share_verify_batch(zk_ctx* c, uint64_t B, const uint8_t* tags, const uint8_t* shares, uint8_t* ok, int32_t* status) {
     if (!c || (B && (!tags || !shares || !ok || !status))) return ZK_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    if (zk_status zs = share_refusal(c, B, true)) return zs;
+    if (zk_status zs = share_refusal(c, B)) return zs;
     if (B == 0) return ZK_OK;
     ShareVerifyIn I;
     if (zk_status zs = lay_out(c, B_in, [&](uint8_t* base) { return share_verify_in_layout(I, base, B); })) return zs;
     if (zk_status zs = reserve(c, B_io, B * (ZKT1_SIZE + ZKS1_SIZE))) return zs;
     uint8_t* const d_tags = (uint8_t*)c->buf[B_io].p;
     uint8_t* const d_shares = d_tags + B * ZKT1_SIZE;
-    hipStream_t s = c->stream;
-    HIPCHK(c, hipMemcpyAsync(d_tags, tags, B * ZKT1_SIZE, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_shares, shares, B * ZKS1_SIZE, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipStreamSynchronize(s));
+    if (zk_status zs = upload_rows(c, {{d_tags, tags, B * ZKT1_SIZE}, {d_shares, shares, B * ZKS1_SIZE}})) return zs;
     if (zk_status zs = share_verify_device(c, B, {d_tags, d_shares, I.ok, I.st})) return zs;
-    HIPCHK(c, hipMemcpyAsync(ok, I.ok, B, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(status, I.st, 4 * B, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    return ZK_OK;
+    return download_rows(c, {{I.ok, ok, B}, {I.st, status, 4 * B}});
 }
 
 // ------------------------------------------------------------------ combine
 // call level: t is the context's threshold and `auditors` holds t different indices in 1..n
 static zk_status combine_refusal(zk_ctx* c, uint64_t B, uint32_t t, const uint32_t* auditors) {
-    if (zk_status zs = share_refusal(c, B, true)) return zs;
+    if (zk_status zs = share_refusal(c, B)) return zs;
     if (t != c->auditors_t) {
         c->err = "t is not the threshold of the context's set of share keys";
         return ZK_E_ARG;
@@ -394,7 +328,7 @@ static zk_status combine_refusal(zk_ctx* c, uint64_t B, uint32_t t, const uint32
 static zk_status combine_device(zk_ctx* c, uint64_t B, uint32_t t, const uint32_t* d_auditors, const uint8_t* d_tags, const uint8_t* d_shares, const uint32_t* d_ids,
                                 uint32_t* d_ring_out, uint32_t* d_index, int32_t* d_status) {
     if (B == 0) return ZK_OK;
-    if (!share_aligned({d_auditors, d_tags, d_shares, d_ids, d_ring_out, d_index, d_status})) return ZK_E_ARG;
+    if (!words_aligned({d_auditors, d_tags, d_shares, d_ids, d_ring_out, d_index, d_status})) return ZK_E_ARG;
     timing_begin(c);
     const bool timed = zk_timed(c, B);
     hipStream_t s0 = c->stream;
@@ -465,7 +399,7 @@ extern "C" zk_status zk_auditors_combine_batch_device(zk_ctx* c, uint64_t B, uin
     if (!c || !d_auditors || (B && (!d_tags || !d_shares || !d_ring_ids || !d_ring_out || !d_index || !d_status))) return ZK_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     if (t < 1 || t > ZK_AUDITORS_MAX || ((uintptr_t)d_auditors & 3)) return ZK_E_ARG;
-    if (zk_status zs = share_refusal(c, B, true)) return zs;
+    if (zk_status zs = share_refusal(c, B)) return zs;
     uint32_t auditors[ZK_AUDITORS_MAX];
     HIPCHK(c, hipMemcpy(auditors, d_auditors, 4 * (size_t)t, hipMemcpyDeviceToHost));   // the call-level rules read them; they are public
     if (zk_status zs = combine_refusal(c, B, t, auditors)) return zs;

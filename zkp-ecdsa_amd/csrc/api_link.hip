@@ -3,83 +3,29 @@
 // Host-side pipeline; the kernels of its own are in k_link.hip, the commitments are k_tom.hip's pair form, the challenge hash k_hash.hip's message path.
 // No ring takes part.  The chunks run on the context's lanes (their streams are the prover lanes'), every lane's arena carved from one witness-flagged buffer.
 #include "ctx.h"
-#include "jobs.h"
+#include "sigma.h"
 #include "link.h"
 #include "rering_plan.h"   // rr_head: the header and slot rules of zk_proof_rering_batch
 
-static size_t link_carve(LinkLane* K, uint32_t nlanes, uint8_t* base, uint32_t C) {
-    SoaCarver k(base);
-    for (uint32_t l = 0; l < nlanes; l++) {
-        LinkLane& X = K[l];
-        X = LinkLane{};
-        X.C = C;
-        X.L = k.list(4 * (size_t)C);
-        X.rng.exc_idx = (uint32_t*)k.take(4 * RNG_MAX_EXC * (size_t)C);
-        X.rng.exc_flags = (uint32_t*)k.take(4 * RNG_MAX_EXC * (size_t)C);
-        X.rng.exc_cnt = (uint32_t*)k.take(4 * (size_t)C);
-        X.rng_fill = (uint32_t*)k.take(32 * (size_t)LINK_RNG_BLOCKS * C);
-        X.st = (int32_t*)k.take(4 * (size_t)C);
-        X.flags = (uint32_t*)k.take(4 * (size_t)C);
-        X.cw = (uint32_t*)k.take(4 * 36 * (size_t)C);
-        X.msg = (uint8_t*)k.take((size_t)ZKL1_MSG_BLOCKS * 64 * C);
-        X.wk = (uint32_t*)k.take((size_t)ZKL1_MSG_BLOCKS * 256 * C);
-        X.chal = (uint32_t*)k.take(16 * (size_t)C);
-    }
-    return k.off + ZK_LAYOUT_TAIL;
-}
-static zk_status link_refusal(zk_ctx* c, uint64_t B) {
-    if (!c->params_set) return ZK_E_BUFFER;
-    if (c->stream_busy) return busy_refusal(c);
-    if (B > 0xffffffffull) return ZK_E_ARG;
-    return ZK_OK;
-}
-static bool link_aligned(std::initializer_list<const void*> ps) {   // the kernels read and write 32-bit words
-    for (const void* p : ps)
-        if ((uintptr_t)p & 3) return false;
-    return true;
+static void link_carve(SoaCarver& k, LinkLane& X, uint32_t C) {
+    X = LinkLane{};
+    sigma_carve_core(k, X, C, LINK_SLOTS, LINK_RNG_BLOCKS, ZKL1_MSG_BLOCKS);
+    X.cw = (uint32_t*)k.take(4 * 36 * (size_t)C);
 }
 extern "C" uint64_t zk_link_proof_size(void) { return ZKL1_SIZE; }
-
-// The chunk plan of a call of B proofs and its lanes' arenas
-struct LinkRun {
-    std::vector<ChunkPlan> plan;
-    uint32_t NL = 0;
-    LinkLane K[ZK_MAX_LANES];
-};
-static zk_status link_plan(zk_ctx* c, uint64_t B, LinkRun& R) {
-    const uint32_t C = (uint32_t)std::min<uint64_t>(c->chunk, B);
-    R.plan = make_chunk_plan(B, C, 1, false);
-    R.NL = (uint32_t)std::min<size_t>(std::min<uint32_t>(c->lanes, ZK_MAX_LANES), R.plan.size());
-    return lay_out(c, B_lk, [&](uint8_t* base) { return link_carve(R.K, R.NL, base, C); });
-}
+typedef SigmaRun<LinkLane> LinkRun;
 
 // ------------------------------------------------------------------ prover
 static zk_status link_prove_device(zk_ctx* c, uint64_t B, const LinkProveIo& io, const zk_rng& rng, uint64_t out_cap) {
-    if (zk_status zs = link_refusal(c, B)) return zs;
-    if (!rng_mode_ok(&rng)) return ZK_E_ARG;
-    if (B > out_cap / ZKL1_SIZE) {
-        c->err = "output buffer too small";
-        return ZK_E_BUFFER;
-    }
-    if (B == 0) return ZK_OK;
-    if (!link_aligned({io.com1, io.com2, io.key, io.blinder1, io.blinder2, io.out, io.status, rng.data})) return ZK_E_ARG;
+    zk_status gate;
+    if (sigma_prove_gate(c, B, rng, out_cap, ZKL1_SIZE, gate)) return gate;
+    if (!words_aligned({io.com1, io.com2, io.key, io.blinder1, io.blinder2, io.out, io.status, rng.data})) return ZK_E_ARG;
     timing_begin(c);   // (behind every refusal: a call that runs nothing leaves the last call's record as it is)
     LinkRun R;
-    if (zk_status zs = link_plan(c, B, R)) return zs;
+    if (zk_status zs = sigma_plan(c, B, B_lk, R, link_carve)) return zs;
     const bool timed = zk_timed(c, B);
-    for (uint64_t k = 0; k < R.plan.size(); k++) {
-        const uint32_t lane = (uint32_t)(k % R.NL), cnt = R.plan[k].cnt;
-        const uint64_t first = R.plan[k].first;
-        LinkLane& K = R.K[lane];
-        hipStream_t s = c->pl[lane].stream;
-        K.rng.seeds = rng.data, K.rng.stream = rng.data, K.rng.stride_blocks = rng.stride_blocks, K.rng.mode = rng.mode, K.rng.sec = -1, K.rng.proof_base = (uint32_t)first;
-        {
-            MaybeScope t(timed, c, "rng_prepass", s);
-            Workspace W{};   // the prepass reads a workspace's RNG view
-            W.rng = K.rng;
-            launch_rng_prepass(s, W, cnt, 0, LINK_RNG_BLOCKS, LINK_RNG_BLOCKS, rng.mode == ZK_RNG_SEED ? K.rng_fill : nullptr, false);
-        }
-        if (rng.mode == ZK_RNG_SEED) K.rng.mode = ZK_RNG_STREAM, K.rng.stream = (const uint8_t*)K.rng_fill, K.rng.stride_blocks = LINK_RNG_BLOCKS, K.rng.proof_base = 0;
+    return sigma_run_chunks(c, R, true, [&](LinkLane& K, hipStream_t s, uint32_t cnt, uint64_t first) {
+        sigma_chunk_rng(c, timed, s, K.rng, K.rng_fill, rng, first, cnt, LINK_RNG_BLOCKS);
         {
             MaybeScope t(timed, c, "tom_commit", s);
             launch_link_front(s, K, cnt, first, io);
@@ -87,24 +33,18 @@ static zk_status link_prove_device(zk_ctx* c, uint64_t B, const LinkProveIo& io,
         }
         {
             MaybeScope t(timed, c, "tom_normalize", s);
-            launch_tom_normalize(s, K.L, 4 * cnt, 0, 1, 1);
+            launch_tom_normalize(s, K.L, LINK_SLOTS * cnt, 0, 1, 1);
         }
         {
             MaybeScope t(timed, c, "hash", s);
             launch_link_opening_msg(s, K, cnt);
-            launch_link_hash(s, K, cnt);
+            launch_sigma_hash(s, K, cnt, ZKL1_MSG_BLOCKS);
         }
         {
             MaybeScope t(timed, c, "link_respond", s);
             launch_link_respond(s, K, cnt, first, io);
         }
-    }
-    const hipError_t e_sync = drain_lanes(c, R.NL);
-    if (e_sync != hipSuccess) wipe_witness(c);   // a failed call leaves no nonce, blinder or RNG block behind
-    HIPCHK(c, e_sync);
-    HIPCHK(c, hipGetLastError());
-    timing_end(c);
-    return ZK_OK;
+    });
 }
 extern "C" zk_status zk_link_prove_batch_device(zk_ctx* c, uint64_t B, const void* d_key, const void* d_com1, const void* d_blinder1, const void* d_com2, const void* d_blinder2,
                                                 const zk_rng* rng, void* d_out, uint64_t out_cap, void* d_status) {
@@ -130,13 +70,8 @@ extern "C" zk_status zk_link_prove_batch(zk_ctx* c, uint64_t B, const uint8_t* k
                                          const zk_rng* rng, uint8_t* out, uint64_t out_cap, int32_t* status) {
     if (!c || !rng || (B && (!key || !com1 || !blinder1 || !com2 || !blinder2 || !rng->data || !out || !status))) return ZK_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    if (zk_status zs = link_refusal(c, B)) return zs;
-    if (!rng_mode_ok(rng)) return ZK_E_ARG;
-    if (B > out_cap / ZKL1_SIZE) {
-        c->err = "output buffer too small";
-        return ZK_E_BUFFER;
-    }
-    if (B == 0) return ZK_OK;
+    zk_status gate;
+    if (sigma_prove_gate(c, B, *rng, out_cap, ZKL1_SIZE, gate)) return gate;
     LinkProveIn I;
     if (zk_status zs = lay_out(c, B_in, [&](uint8_t* base) { return link_prove_in_layout(I, base, B, rng_bytes(rng, B)); })) return zs;
     if (zk_status zs = reserve(c, B_io, B * ZKL1_SIZE)) return zs;
@@ -154,22 +89,18 @@ extern "C" zk_status zk_link_prove_batch(zk_ctx* c, uint64_t B, const uint8_t* k
 
 // ------------------------------------------------------------------ verifier
 static zk_status link_verify_device(zk_ctx* c, uint64_t B, const LinkVerifyIo& io) {
-    if (zk_status zs = link_refusal(c, B)) return zs;
+    if (zk_status zs = sigma_refusal(c, B)) return zs;
     if (B == 0) return ZK_OK;
-    if (!link_aligned({io.com1, io.com2, io.proofs, io.status})) return ZK_E_ARG;
+    if (!words_aligned({io.com1, io.com2, io.proofs, io.status})) return ZK_E_ARG;
     timing_begin(c);
     LinkRun R;
-    if (zk_status zs = link_plan(c, B, R)) return zs;
+    if (zk_status zs = sigma_plan(c, B, B_lk, R, link_carve)) return zs;
     const bool timed = zk_timed(c, B);
-    for (uint64_t k = 0; k < R.plan.size(); k++) {
-        const uint32_t lane = (uint32_t)(k % R.NL), cnt = R.plan[k].cnt;
-        const uint64_t first = R.plan[k].first;
-        const LinkLane& K = R.K[lane];
-        hipStream_t s = c->pl[lane].stream;
+    return sigma_run_chunks(c, R, false, [&](const LinkLane& K, hipStream_t s, uint32_t cnt, uint64_t first) {
         {
             MaybeScope t(timed, c, "link_parse", s);
             launch_link_parse(s, K, cnt, first, io);
-            launch_link_hash(s, K, cnt);
+            launch_sigma_hash(s, K, cnt, ZKL1_MSG_BLOCKS);
         }
         {
             MaybeScope t(timed, c, "tom_commit", s);
@@ -179,11 +110,7 @@ static zk_status link_verify_device(zk_ctx* c, uint64_t B, const LinkVerifyIo& i
             MaybeScope t(timed, c, "link_ladder", s);
             launch_link_ladder(s, K, cnt, first, io);
         }
-    }
-    HIPCHK(c, drain_lanes(c, R.NL));
-    HIPCHK(c, hipGetLastError());
-    timing_end(c);
-    return ZK_OK;
+    });
 }
 extern "C" zk_status zk_link_verify_batch_device(zk_ctx* c, uint64_t B, const void* d_com1, const void* d_com2, const void* d_proofs, void* d_ok, void* d_status) {
     if (!c || (B && (!d_com1 || !d_com2 || !d_proofs || !d_ok || !d_status))) return ZK_E_ARG;
@@ -202,29 +129,22 @@ static size_t link_verify_in_layout(LinkVerifyIn& I, uint8_t* base, size_t B) {
 extern "C" zk_status zk_link_verify_batch(zk_ctx* c, uint64_t B, const uint8_t* com1, const uint8_t* com2, const uint8_t* proofs, uint8_t* ok, int32_t* status) {
     if (!c || (B && (!com1 || !com2 || !proofs || !ok || !status))) return ZK_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    if (zk_status zs = link_refusal(c, B)) return zs;
+    if (zk_status zs = sigma_refusal(c, B)) return zs;
     if (B == 0) return ZK_OK;
     LinkVerifyIn I;
     if (zk_status zs = lay_out(c, B_in, [&](uint8_t* base) { return link_verify_in_layout(I, base, B); })) return zs;
     if (zk_status zs = reserve(c, B_io, B * ZKL1_SIZE)) return zs;
     uint8_t* const d_proofs = (uint8_t*)c->buf[B_io].p;
-    hipStream_t s = c->stream;
-    HIPCHK(c, hipMemcpyAsync(I.com1, com1, 72 * B, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(I.com2, com2, 72 * B, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_proofs, proofs, B * ZKL1_SIZE, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipStreamSynchronize(s));
+    if (zk_status zs = upload_rows(c, {{I.com1, com1, 72 * B}, {I.com2, com2, 72 * B}, {d_proofs, proofs, B * ZKL1_SIZE}})) return zs;
     if (zk_status zs = link_verify_device(c, B, {I.com1, I.com2, d_proofs, I.ok, I.st})) return zs;
-    HIPCHK(c, hipMemcpyAsync(ok, I.ok, B, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(status, I.st, 4 * B, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    return ZK_OK;
+    return download_rows(c, {{I.ok, ok, B}, {I.st, status, 4 * B}});
 }
 
 // ------------------------------------------------------------------ keyXcom of ZKA1 / ZK1P proofs
 static zk_status key_commitments_device(zk_ctx* c, uint64_t B, const uint8_t* d_proofs, const uint64_t* d_off, uint8_t* d_com, int32_t* d_status) {
-    if (zk_status zs = link_refusal(c, B)) return zs;
+    if (zk_status zs = sigma_refusal(c, B)) return zs;
     if (B == 0) return ZK_OK;
-    if (!link_aligned({d_proofs, d_off, d_com, d_status}) || ((uintptr_t)d_off & 7)) return ZK_E_ARG;
+    if (!words_aligned({d_proofs, d_off, d_com, d_status}) || ((uintptr_t)d_off & 7)) return ZK_E_ARG;
     launch_link_keycoms(c->stream, B, d_proofs, d_off, wire_make(c->wire != 0), d_com, d_status);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipGetLastError());
@@ -238,7 +158,7 @@ extern "C" zk_status zk_proof_key_commitments_device(zk_ctx* c, uint64_t B, cons
 // Host pointers: nothing but the header and the two coordinates of a slot is looked at, so the work stays on the host (rr_head is the device's rule, compiled here)
 extern "C" zk_status zk_proof_key_commitments(zk_ctx* c, uint64_t B, const uint8_t* proofs, const uint64_t* proof_off, uint8_t* com, int32_t* status) {
     if (!c || (B && (!proofs || !proof_off || !com || !status))) return ZK_E_ARG;
-    if (zk_status zs = link_refusal(c, B)) return zs;
+    if (zk_status zs = sigma_refusal(c, B)) return zs;
     const Wire w = wire_make(c->wire != 0);
     for (uint64_t b = 0; b < B; b++) {
         uint8_t* o = com + 72 * b;

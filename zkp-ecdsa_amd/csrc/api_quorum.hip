@@ -23,7 +23,6 @@ static zk_status quorum_refusal(zk_ctx* c, uint64_t Q, uint32_t k, bool rings) {
     if (c->stream_busy) return busy_refusal(c);
     return ZK_OK;
 }
-static bool quorum_aligned(std::initializer_list<const void*> ps) { return words_aligned(ps); }
 // The `_rings` forms: the context's rings as the capacity rule sees them (quorum_plan.h), and what a call's ids come to
 static void quorum_rings_table(const zk_ctx* c, QuorumRings& R) {
     R = QuorumRings{};
@@ -123,7 +122,7 @@ static zk_status quorum_prove_device(zk_ctx* c, uint64_t Q, uint32_t k, const Qu
     QuorumTiming T{c, zk_timed(c, Q * k)};
     if (known) caps = *known;
     else if (io.ids) {   // from the ids alone, before a byte of any output is written
-        if (!quorum_aligned({io.ids})) return ZK_E_ARG;
+        if (!words_aligned({io.ids})) return ZK_E_ARG;
         if (zk_status zs = T.phase("quorum_caps", [&] { return quorum_caps_device(c, Q, k, io.ids, caps); })) return zs;
     }
     const uint64_t proof_max = caps.proof_max;
@@ -131,7 +130,7 @@ static zk_status quorum_prove_device(zk_ctx* c, uint64_t Q, uint32_t k, const Qu
         c->err = "output buffer too small";
         return ZK_E_BUFFER;
     }
-    if (!quorum_aligned({io.msg, io.sig, io.pk, io.which, io.out, io.out_off, io.status, io.member_status, rng.data, rng_pairs.data})) return ZK_E_ARG;
+    if (!words_aligned({io.msg, io.sig, io.pk, io.which, io.out, io.out_off, io.status, io.member_status, rng.data, rng_pairs.data})) return ZK_E_ARG;
     const uint32_t Wq = (uint32_t)std::min<uint64_t>(Q, quorum_window(c, k));
     QuorumProveWin W;
     if (zk_status zs = lay_out(c, B_qs, [&](uint8_t* base) { return quorum_prove_layout(W, base, Wq, k, proof_max); })) return zs;
@@ -288,7 +287,7 @@ struct QuorumVerifyIo {   // device pointers
 static zk_status quorum_verify_device(zk_ctx* c, uint64_t Q, uint32_t k, const QuorumVerifyIo& io, const uint64_t* h_off) {
     if (zk_status zs = quorum_refusal(c, Q, k, io.ids != nullptr)) return zs;
     if (Q == 0) return ZK_OK;
-    if (!quorum_aligned({io.msg, io.bundles, io.off, io.vseeds, io.ok, io.status, io.first_bad, io.ids})) return ZK_E_ARG;
+    if (!words_aligned({io.msg, io.bundles, io.off, io.vseeds, io.ok, io.status, io.first_bad, io.ids})) return ZK_E_ARG;
     hipStream_t s = c->stream;
     std::vector<uint64_t> off_copy;
     if (!h_off) {

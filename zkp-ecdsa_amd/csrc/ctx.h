@@ -370,6 +370,19 @@ static inline zk_status download_or_wipe(zk_ctx* c, std::initializer_list<Downlo
     HIPCHK(c, e);
     return ZK_OK;
 }
+// The same rows where nothing staged is witness-derived (the host-pointer verify calls): copies on c->stream and one wait; a failing copy returns as it is
+static inline zk_status upload_rows(zk_ctx* c, std::initializer_list<UploadRow> rows) {
+    for (auto& r : rows)
+        if (r.bytes) HIPCHK(c, hipMemcpyAsync(r.dev, r.host, r.bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ZK_OK;
+}
+static inline zk_status download_rows(zk_ctx* c, std::initializer_list<DownloadRow> rows) {
+    for (auto& r : rows)
+        if (r.bytes) HIPCHK(c, hipMemcpyAsync(r.host, r.dev, r.bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ZK_OK;
+}
 zk_status ensure_workspace(zk_ctx* c, uint32_t C, uint32_t nlanes = 1);   // api.hip: prover workspaces of lanes 0..nlanes-1
 hipError_t malloc_or_shed(zk_ctx* c, void** p, size_t bytes);   // api.hip: a workspace allocation that sheds the optional per-ring tables first
 // settings a queued streamed job was planned with (its lane rotation, chunk size, workspaces, mode) and the buffers it reads stay frozen until it is waited for

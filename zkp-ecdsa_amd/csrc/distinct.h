@@ -106,18 +106,9 @@ ZK_DEV bool dist_relation3(const TomPt& D, const TomPt& az) { return link_is_ide
 // Verifier: 4 p + k = (t_x, t_rx), (t_y, t_ry), (t_z + c, t_rz), (t_z, t_r4); 4 count + p = Cx.
 #define DIST_SLOTS 10
 #define DIST_SINGLES 7
-struct DistLane {
-    uint32_t C;
-    TomList L;            // [DIST_SLOTS C]
-    RngCtx rng;           // the rejection lists of the chunk's eight draws
-    uint32_t* rng_fill;   // [C][DIST_RNG_BLOCKS][8] seed mode: the fills as a stream
-    int32_t* st;          // [C]
-    uint32_t* flags;      // [C] bit 0: the RNG does not hold the eight draws
+struct DistLane : SigmaLane {   // L [DIST_SLOTS C], eight draws, ZKD1_MSG_BLOCKS message blocks
     uint32_t* cw;         // [C][36] com1 (x, y), com2 (x, y) as the caller states them, nine little-endian words each
-    uint8_t* msg;         // [C][ZKD1_MSG_BLOCKS * 64] the challenge's padded message ...
-    uint32_t* wk;         // ... its expanded schedule (k_hash.hip: launch_sha_msgs)
-    uint32_t* chal;       // [C][4]
-    uint32_t* tw;         // [C][8] verifier: t_x reduced, as words (dist_ladder2 reads them from memory)
+    uint32_t* tw;        // [C][8] verifier: t_x reduced, as words (dist_ladder2 reads them from memory)
     DistQuad* tab;        // [C][DIST_TAB_QUADS] verifier: the addends of relation 5's chain
     uint32_t* rel;        // [C][3] verifier: relations 1, 2 and 4 as the short ladders found them
 };
@@ -128,14 +119,8 @@ struct DistProveIo {      // device pointers of a prove call, indexed by the pro
     int32_t* status;
 };
 typedef LinkVerifyIo DistVerifyIo;   // com1, com2, proofs, ok, status
-static inline TomList dist_view(const TomList& L, uint32_t off) {   // the list from slot `off` on, for the launches that count slots from 0
-    TomList V = L;
-    V.v.p += off, V.r.p += off, V.proj.x.p += off, V.proj.y.p += off, V.proj.z.p += off, V.ax.p += off, V.ay.p += off, V.cap -= off;
-    return V;
-}
 void launch_dist_front(hipStream_t s, const DistLane& K, uint32_t count, uint64_t first, const DistProveIo& io);
 void launch_dist_opening_msg(hipStream_t s, const DevParams& P, const DistLane& K, uint32_t count);   // behind the normaliser: the opening compare, the challenge's message
-void launch_dist_hash(hipStream_t s, const DistLane& K, uint32_t count);
 void launch_dist_respond(hipStream_t s, const DistLane& K, uint32_t count, uint64_t first, const DistProveIo& io);
 void launch_dist_parse(hipStream_t s, const DevParams& P, const DistLane& K, uint32_t count, uint64_t first, const DistVerifyIo& io);
 void launch_dist_cx_msg(hipStream_t s, const DistLane& K, uint32_t count);   // behind the normaliser: Cx into the challenge's message

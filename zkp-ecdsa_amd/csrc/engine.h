@@ -93,6 +93,11 @@ struct TomList {   // a list of Pedersen commitments to compute: (v, r) -> proje
     Soa ax, ay;    // affine, original curve, plain canonical
     uint32_t cap;
 };
+static inline TomList tom_list_from(const TomList& L, uint32_t off) {   // the list from slot `off` on, for the launches that count slots from 0
+    TomList V = L;
+    V.v.p += off, V.r.p += off, V.proj.x.p += off, V.proj.y.p += off, V.proj.z.p += off, V.ax.p += off, V.ay.p += off, V.cap -= off;
+    return V;
+}
 
 struct DevParams {            // device-resident, built by zk_ctx_set_params
     uint32_t* tom_tab_g;      // tom_tab_words(tom_bits)
@@ -286,6 +291,20 @@ void launch_v_exp_status(hipStream_t s, const Workspace& W, const VWork& V, uint
 #define V_PH_BLOCKS 10    // 9 points of 67 bytes + padding
 // k_hash.hip: `count` messages of up to nblk 64-byte blocks at W.exph_msg (message p at p * nblk * 64; nblk_of[p] blocks if given) -> challenge words chal[ostride p ..]
 void launch_sha_msgs(hipStream_t s, const Workspace& W, uint32_t count, uint32_t* chal, uint32_t nblk, uint32_t ostride, const uint8_t* nblk_of = nullptr);
+// What every sigma proof's lane holds (link.h, distinct.h, escrow.h, escrow_share.h derive their lanes from it; sigma.h carves and runs them): a chunk of C
+// proofs' commitment list, the RNG's rejection lists and fills, the statuses, and the challenge's message, schedule and words.  A kernel argument.
+struct SigmaLane {
+    uint32_t C;
+    TomList L;            // [slots C]
+    RngCtx rng;           // the rejection lists of the chunk's draws
+    uint32_t* rng_fill;   // [C][rng blocks][8] seed mode: the fills as a stream
+    uint8_t* msg;         // [C][msg blocks * 64] the challenge's padded message ...
+    uint32_t* wk;         // ... its expanded schedule (k_hash.hip: launch_sha_msgs)
+    uint32_t* chal;       // [C][4]
+    int32_t* st;          // [C] (the last two: a lane's own words follow them, as the front ends load them together)
+    uint32_t* flags;      // [C] bit 0: the RNG does not hold the proof's draws
+};
+void launch_sigma_hash(hipStream_t s, const SigmaLane& K, uint32_t count, uint32_t msg_blocks);   // k_hash.hip: K.msg -> K.chal through launch_sha_msgs
 void launch_exph_hash(hipStream_t s, const Workspace& W, uint32_t count, uint32_t* chal);   // k_hash.hip: schedule per block, rounds per proof -> chal[4 p ..]
 void launch_v_exp_points(hipStream_t s, const Workspace& W, const VWork& V, uint32_t count, const uint8_t* proofs, const uint64_t* off, uint64_t first, uint32_t split = 1);   // split: 1, or 4 lanes per checked repetition (small chunks)
 void launch_v_t1_scalars(hipStream_t s, const Workspace& W, const VWork& V, uint32_t count, const uint8_t* proofs, const uint64_t* off, uint64_t first);

@@ -59,18 +59,9 @@ ZK_DEV TomPt escrow_open_point(const TomPt& e1, const TomPt& e2, const uint32_t*
 // Prover: 4 p + k on (g, h) = E1 (rho, 0), T1 (k_x, k_r), T2 (k_rho, 0), the opening the caller claims (x, r); 4 count + 2 p + k on (g, A) = E2 (x, rho),
 // T3 (k_x, k_rho).  Verifier: 2 p + k on (g, h) = (t_x, t_r), (t_rho, 0); 2 count + p on (g, A) = (t_x, t_rho).
 #define ESC_SLOTS 6
-struct EscrowLane {
-    uint32_t C;
-    TomList L;            // [ESC_SLOTS C]
-    RngCtx rng;           // the rejection lists of the chunk's four draws
-    uint32_t* rng_fill;   // [C][ESC_RNG_BLOCKS][8] seed mode: the fills as a stream
-    int32_t* st;          // [C]
-    uint32_t* flags;      // [C] bit 0: the RNG does not hold the four draws
+struct EscrowLane : SigmaLane {   // L [ESC_SLOTS C], four draws, ZKT1_MSG_BLOCKS message blocks
     uint32_t* cw;         // [C][18] com (x, y) as the caller states it, nine little-endian words each
-    uint8_t* msg;         // [C][ZKT1_MSG_BLOCKS * 64] the challenge's padded message ...
-    uint32_t* wk;         // ... its expanded schedule (k_hash.hip: launch_sha_msgs)
-    uint32_t* chal;       // [C][4]
-    uint32_t* rel;        // [C][3] verifier: the three relations as their lanes found them
+    uint32_t* rel;       // [C][3] verifier: the three relations as their lanes found them
 };
 #define ESC_RNG_BLOCKS (4 + RNG_MAX_EXC)   // rho, k_x, k_r, k_rho and a margin: rejected fills shift later draws
 struct EscrowKey {        // (a kernel argument) the auditor's key as the caller stated it, nine little-endian words per coordinate
@@ -96,15 +87,9 @@ struct EscrowOpen {
     uint8_t* ag;          // [72] a g as bytes
 };
 #define ESC_RING_SLAB (1u << 18)
-static inline TomList escrow_view(const TomList& L, uint32_t off) {   // the list from slot `off` on, for the launches that count slots from 0
-    TomList V = L;
-    V.v.p += off, V.r.p += off, V.proj.x.p += off, V.proj.y.p += off, V.proj.z.p += off, V.ax.p += off, V.ay.p += off, V.cap -= off;
-    return V;
-}
 void launch_escrow_check_key(hipStream_t s, const uint8_t* d_xy72, uint32_t* d_words18, int32_t* d_res /* [2]: encoding sound, identity */);
 void launch_escrow_front(hipStream_t s, const EscrowLane& K, uint32_t count, uint64_t first, const EscrowProveIo& io);
 void launch_escrow_opening_msg(hipStream_t s, const EscrowLane& K, const EscrowKey& A, uint32_t count);   // behind the normaliser: the opening compare, the challenge's message
-void launch_escrow_hash(hipStream_t s, const EscrowLane& K, uint32_t count);
 void launch_escrow_respond(hipStream_t s, const EscrowLane& K, uint32_t count, uint64_t first, const EscrowProveIo& io);
 void launch_escrow_parse(hipStream_t s, const EscrowLane& K, const EscrowKey& A, uint32_t count, uint64_t first, const EscrowVerifyIo& io);
 void launch_escrow_relations(hipStream_t s, const EscrowLane& K, uint32_t count, uint64_t first, const EscrowVerifyIo& io);

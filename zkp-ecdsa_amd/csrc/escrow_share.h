@@ -94,18 +94,9 @@ ZK_DEV TomPt share_combine_point(const TomPt& e2, const TomPt& sum) { return tom
 // The list's slots for a chunk of `count` tags.  Share: p = U1 (k, 0) on the (g, h) combs; count + p = D, 2 count + p = U2, projective from the ladder.
 // Verifier: p = (s, 0) on the combs.
 #define SHR_SLOTS 3
-struct ShareLane {
-    uint32_t C;
-    TomList L;            // [SHR_SLOTS C]
-    RngCtx rng;           // the rejection list of the chunk's one draw
-    uint32_t* rng_fill;   // [C][SHR_RNG_BLOCKS][8] seed mode: the fills as a stream
-    int32_t* st;          // [C]
-    uint32_t* flags;      // [C] bit 0: the RNG does not hold the draw
+struct ShareLane : SigmaLane {   // L [SHR_SLOTS C], one draw, ZKS1_MSG_BLOCKS message blocks
     uint32_t* kw;         // [C][8] share: k as words (the masked ladder reads them); verifier: s reduced (dist_ladder2 reads them)
-    uint8_t* msg;         // [C][ZKS1_MSG_BLOCKS * 64] the challenge's padded message ...
-    uint32_t* wk;         // ... its expanded schedule (k_hash.hip: launch_sha_msgs)
-    uint32_t* chal;       // [C][4]
-    DistQuad* tab;        // [C][DIST_TAB_QUADS] verifier: the addends of relation 2's chain
+    DistQuad* tab;       // [C][DIST_TAB_QUADS] verifier: the addends of relation 2's chain
     uint32_t* rel;        // [C][2] verifier: the two relations as their lanes found them
 };
 #define SHR_RNG_BLOCKS (1 + RNG_MAX_EXC)
@@ -133,7 +124,6 @@ struct ShareCombineIo {   // a combine call: slot s of `shares` (B shares) belon
 void launch_share_front(hipStream_t s, const ShareLane& K, uint32_t count, uint64_t first, const ShareProveIo& io);
 void launch_share_ladder(hipStream_t s, const ShareLane& K, const ShareSecret& A, uint32_t count, uint64_t first, const ShareProveIo& io);
 void launch_share_msg(hipStream_t s, const ShareLane& K, const uint32_t* keys_w /*[n][18]*/, uint32_t j, uint32_t count, uint64_t first, const ShareProveIo& io);
-void launch_share_hash(hipStream_t s, const ShareLane& K, uint32_t count);
 void launch_share_respond(hipStream_t s, const ShareLane& K, const ShareSecret& A, uint32_t count, uint64_t first, const ShareProveIo& io);
 void launch_share_parse(hipStream_t s, const ShareLane& K, const uint32_t* keys_w, uint32_t n, uint32_t count, uint64_t first, const ShareVerifyIo& io);
 void launch_share_relations(hipStream_t s, const ShareLane& K, const uint32_t* keys_w, uint32_t count, uint64_t first, const ShareVerifyIo& io);

@@ -138,12 +138,12 @@ zk_status verify_host(zk_ctx* c, uint64_t B, const uint8_t* msg, const uint8_t* 
 static inline size_t unpack_stage_bytes(uint64_t B, uint64_t total, uint32_t C) { return (size_t)((total * 12 + 10) / 11 + 32 * B + 256 * (B / (C ? C : 1) + 2) + 64); }
 static inline size_t unpack_off_entries(uint64_t B, uint32_t C) { return (size_t)(B + B / (C ? C : 1) + 4); }
 
-// Shared by the calls that run other calls' pipelines window by window (api_quorum.hip, api_accountable.hip)
 static inline bool words_aligned(std::initializer_list<const void*> ps) {   // the kernels read and write 32-bit words
     for (const void* p : ps)
         if ((uintptr_t)p & 3) return false;
     return true;
 }
+// Shared by the calls that run other calls' pipelines window by window (api_quorum.hip, api_accountable.hip)
 static inline size_t rng_row_bytes(const zk_rng& r) { return r.mode == ZK_RNG_SEED ? 32 : 32 * (size_t)r.stride_blocks; }   // one proof's row of rng->data
 static inline uint32_t window_rows(const zk_ctx* c, uint32_t per) { return std::max<uint32_t>(1, c->chunk * std::min<uint32_t>(c->lanes, ZK_MAX_LANES) / per); }   // units of `per` proofs per window
 // zk_last_timing of a call that runs other calls' pipelines window by window: every pipeline leaves its own record, which is added up here by family name;

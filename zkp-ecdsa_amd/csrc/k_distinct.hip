@@ -106,11 +106,6 @@ __global__ void __launch_bounds__(64) k_dist_opening_msg(DevParams P, DistLane K
 void launch_dist_opening_msg(hipStream_t s, const DevParams& P, const DistLane& K, uint32_t count) {
     hipLaunchKernelGGL(k_dist_opening_msg, dim3((count + 63) / 64), dim3(64), 0, s, P, K, count);
 }
-void launch_dist_hash(hipStream_t s, const DistLane& K, uint32_t count) {   // k_hash.hip's message path reads these two fields of a workspace and nothing else
-    Workspace W{};
-    W.exph_msg = K.msg, W.exph_wk = K.wk;
-    launch_sha_msgs(s, W, count, K.chal, ZKD1_MSG_BLOCKS, 4);
-}
 // One workgroup of 64 threads per proof builds the slot's 186 words in LDS: lanes 0..13 a coordinate of the seven points each, lane 14 the seven responses
 // (distinct.h: mult_responses with x = d, y = w, z = 1 under the blinders r1 - r2, r_w, 0), lane 15 the header.  Then every lane writes three words (two for the
 // last lanes).  A failed proof's slot is 186 zero words.  Every byte of the slot is written once.

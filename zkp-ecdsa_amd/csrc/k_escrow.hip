@@ -81,11 +81,6 @@ __global__ void __launch_bounds__(64) k_escrow_opening_msg(EscrowLane K, EscrowK
 void launch_escrow_opening_msg(hipStream_t s, const EscrowLane& K, const EscrowKey& A, uint32_t count) {
     hipLaunchKernelGGL(k_escrow_opening_msg, dim3((count + 63) / 64), dim3(64), 0, s, K, A, count);
 }
-void launch_escrow_hash(hipStream_t s, const EscrowLane& K, uint32_t count) {   // k_hash.hip's message path reads these two fields of a workspace and nothing else
-    Workspace W{};
-    W.exph_msg = K.msg, W.exph_wk = K.wk;
-    launch_sha_msgs(s, W, count, K.chal, ZKT1_MSG_BLOCKS, 4);
-}
 // One workgroup of 128 threads per tag, one 32-bit word of the slot each (118 of them): the header, the five points (lanes 1..10 make a coordinate each), the
 // responses (lanes 11..13 one each).  A failed tag's slot is 118 zero words.  Every byte of the slot is written once.
 __global__ void __launch_bounds__(128) k_escrow_respond(EscrowLane K, uint32_t count, uint64_t first, EscrowProveIo io) {

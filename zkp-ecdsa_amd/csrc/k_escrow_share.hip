@@ -83,11 +83,6 @@ __global__ void __launch_bounds__(64) k_share_msg(ShareLane K, const uint32_t* k
 void launch_share_msg(hipStream_t s, const ShareLane& K, const uint32_t* keys_w, uint32_t j, uint32_t count, uint64_t first, const ShareProveIo& io) {
     hipLaunchKernelGGL(k_share_msg, dim3((count + 63) / 64), dim3(64), 0, s, K, keys_w, j, count, first, io);
 }
-void launch_share_hash(hipStream_t s, const ShareLane& K, uint32_t count) {   // k_hash.hip's message path reads these two fields of a workspace and nothing else
-    Workspace W{};
-    W.exph_msg = K.msg, W.exph_wk = K.wk;
-    launch_sha_msgs(s, W, count, K.chal, ZKS1_MSG_BLOCKS, 4);
-}
 // One workgroup of 128 threads per tag, one 32-bit word of the slot each (66 of them): the header, the three points (lanes 1..6 make a coordinate each), the
 // response (lane 7).  A failed share's slot is 66 zero words.  Every byte of the slot is written once.
 __global__ void __launch_bounds__(128) k_share_respond(ShareLane K, ShareSecret A, uint32_t count, uint64_t first, ShareProveIo io) {

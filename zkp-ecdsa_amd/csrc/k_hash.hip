@@ -274,6 +274,11 @@ void launch_sha_msgs(hipStream_t s, const Workspace& W, uint32_t count, uint32_t
     else if (nblk_of) hipLaunchKernelGGL(k_exph_rounds<true>, grid, dim3(64), 0, s, W, count, chal, nblk, ostride, nblk_of);
     else hipLaunchKernelGGL(k_exph_rounds<false>, grid, dim3(64), 0, s, W, count, chal, nblk, ostride, nblk_of);
 }
+void launch_sigma_hash(hipStream_t s, const SigmaLane& K, uint32_t count, uint32_t msg_blocks) {   // the message path reads these two fields of a workspace and nothing else
+    Workspace W{};
+    W.exph_msg = K.msg, W.exph_wk = K.wk;
+    launch_sha_msgs(s, W, count, K.chal, msg_blocks, 4);
+}
 void launch_exph_hash(hipStream_t s, const Workspace& W, uint32_t count, uint32_t* chal) {
     launch_sha_msgs(s, W, count, chal, (2 * 67 + W.sec * (65 + 2 * 67) + 9 + 63) / 64, 4);
 }

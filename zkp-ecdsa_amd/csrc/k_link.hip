@@ -73,11 +73,6 @@ __global__ void __launch_bounds__(64) k_link_opening_msg(LinkLane K, uint32_t co
 void launch_link_opening_msg(hipStream_t s, const LinkLane& K, uint32_t count) {
     hipLaunchKernelGGL(k_link_opening_msg, dim3((count + 63) / 64), dim3(64), 0, s, K, count);
 }
-void launch_link_hash(hipStream_t s, const LinkLane& K, uint32_t count) {   // k_hash.hip's message path reads these two fields of a workspace and nothing else
-    Workspace W{};
-    W.exph_msg = K.msg, W.exph_wk = K.wk;
-    launch_sha_msgs(s, W, count, K.chal, ZKL1_MSG_BLOCKS, 4);
-}
 // One workgroup of 64 threads per proof, one 32-bit word of the slot each: the header, A_1, A_2 (lanes 1..4 make a coordinate each), the responses (lanes 5..7
 // one each).  A failed proof's slot is 64 zero words.  Every byte of the slot is written once.
 __global__ void __launch_bounds__(64) k_link_respond(LinkLane K, uint32_t count, uint64_t first, LinkProveIo io) {

@@ -93,17 +93,9 @@ ZK_DEV TomPt lk_point_from_words(const uint32_t w[18]) {
 // ------------------------------------------------------------------ a lane's arena (api_link.hip carves it, k_link.hip's kernels read it); C = proofs per chunk
 // The list's slots for a chunk of `count` proofs -- prover: 2 p, 2 p + 1 = (A_1, A_2) of proof p (k under s1, s2), 2 count + 2 p, + 1 = the openings the
 // caller claims (x under r1, r2); verifier: 2 p, 2 p + 1 = t_x g + t_r1 h, t_x g + t_r2 h.
-struct LinkLane {
-    uint32_t C;
-    TomList L;            // [4 C]
-    RngCtx rng;           // the rejection lists of the chunk's three draws
-    uint32_t* rng_fill;   // [C][LINK_RNG_BLOCKS][8] seed mode: the fills as a stream
-    int32_t* st;          // [C]
-    uint32_t* flags;      // [C] bit 0: the RNG does not hold the three draws
+#define LINK_SLOTS 4
+struct LinkLane : SigmaLane {   // L [LINK_SLOTS C], three draws, ZKL1_MSG_BLOCKS message blocks
     uint32_t* cw;         // [C][36] com1 (x, y), com2 (x, y) as the caller states them, nine little-endian words each
-    uint8_t* msg;         // [C][ZKL1_MSG_BLOCKS * 64] the challenge's padded message ...
-    uint32_t* wk;         // ... its expanded schedule (k_hash.hip: launch_sha_msgs)
-    uint32_t* chal;       // [C][4]
 };
 #define LINK_RNG_BLOCKS (3 + RNG_MAX_EXC)   // k, s1, s2 and a margin: rejected fills shift later draws
 struct LinkProveIo {      // device pointers of a prove call, indexed by the proof's place in the batch
@@ -118,7 +110,6 @@ struct LinkVerifyIo {
 };
 void launch_link_front(hipStream_t s, const LinkLane& K, uint32_t count, uint64_t first, const LinkProveIo& io);
 void launch_link_opening_msg(hipStream_t s, const LinkLane& K, uint32_t count);   // behind the normaliser: the opening compare, then the challenge's message
-void launch_link_hash(hipStream_t s, const LinkLane& K, uint32_t count);
 void launch_link_respond(hipStream_t s, const LinkLane& K, uint32_t count, uint64_t first, const LinkProveIo& io);
 void launch_link_parse(hipStream_t s, const LinkLane& K, uint32_t count, uint64_t first, const LinkVerifyIo& io);
 void launch_link_ladder(hipStream_t s, const LinkLane& K, uint32_t count, uint64_t first, const LinkVerifyIo& io);

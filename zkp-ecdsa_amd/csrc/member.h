@@ -1,7 +1,7 @@
 // Ring membership on its own (k_member.hip, api_member.hip): the launch wrappers (the ZKM1 layout is in wire.h) of the kernels around the shared GK machinery,
 // and of the classing, offsets and gather kernels of the mixed-ring forms (k_member_rings.hip; the plan's arithmetic is member_plan.h's).
 #pragma once
-#include "jobs.h"   // ctx.h (engine.h), MaybeScope: the member lanes' chunk front at the end
+#include "sigma.h"   // jobs.h (ctx.h, engine.h, MaybeScope) and the chunk RNG: the member lanes' chunk front at the end
 #include "member_plan.h"
 // Where a window of a mixed-ring call puts its results: window entry j is proof sel[j] of a batch of B, whose slot starts at off[sel[j]] (prover).
 // sel == nullptr: a one-ring call -- entry j is proof first + j, slots are `size` bytes apart.
@@ -36,13 +36,7 @@ static inline uint32_t member_rng_blocks(uint32_t n, uint32_t fill0) { return fi
 // A chunk's RNG on its lane (W.gk_fill0 is set): proofs first .. first + cnt of `rng`, whose data is a device pointer; the prepass; then, in seed mode, the
 // chunk reads the fills the prepass wrote.
 static inline void member_chunk_rng(zk_ctx* c, bool timed, hipStream_t s, Workspace& W, const zk_rng& rng, uint64_t first, uint32_t cnt) {
-    const uint32_t nblk = member_rng_blocks(W.n, W.gk_fill0);
-    W.rng.seeds = rng.data, W.rng.stream = rng.data, W.rng.stride_blocks = rng.stride_blocks, W.rng.mode = rng.mode, W.rng.sec = -1, W.rng.proof_base = (uint32_t)first;
-    {
-        MaybeScope t(timed, c, "rng_prepass", s);
-        launch_rng_prepass(s, W, cnt, 0, nblk, nblk, rng.mode == ZK_RNG_SEED ? W.rng_fill : nullptr, false);
-    }
-    if (rng.mode == ZK_RNG_SEED) W.rng.mode = ZK_RNG_STREAM, W.rng.stream = (const uint8_t*)W.rng_fill, W.rng.stride_blocks = nblk, W.rng.proof_base = 0;
+    sigma_chunk_rng(c, timed, s, W.rng, W.rng_fill, rng, first, cnt, member_rng_blocks(W.n, W.gk_fill0));
 }
 // A chunk's commitments: `front` (the caller's front end: launch_m_front / launch_rr_front) and the fold's scalars, then the 4 n membership commitments of
 // every proof and every proof's com -- list C -- committed and normalised.  Returns what the fold read, for launch_gk_respond.
