@@ -1347,6 +1347,23 @@ zk_status zk_test_p256_fixed_mul(zk_ctx *ctx, int base_sel, uint64_t count, cons
  * bytes (affine; all-zero for the identity) -- T[0..count), A[0..count) through the device functions the prover's kernel runs, then T, A through the complete-law
  * walks alone.  fell[i]: bit 0 / bit 1 = the first T / A was recomputed with the complete law.  ZK_E_BUFFER without parameters or key tables. */
 zk_status zk_test_exp_sum(zk_ctx *ctx, uint32_t key, int neg, uint64_t count, const uint8_t *gkb_be96, uint8_t *out_xy64, uint32_t *fell);
+/* The verifier's cross-proof Tom-256 bucket pass (the production launch sequence, on a workspace carved as the verifier carves a chunk of cap_proofs proofs)
+ * on caller-chosen terms, by value.  groups: 8 (16 windows of 16 bits) or 64 (20 windows of 13 bits); count <= cap_proofs live proofs; nq in 1..4 membership
+ * groups per proof.  A proof slot has T = 720 + 8 nq + 3 term slots; term ids as in the pass: k * (20 cap) + 20 p + j for term k < 36 of repetition j < 20 of
+ * proof slot p, then 720 cap + k * (nq cap) + nq p + i for term k < 8 of membership group i < nq, then (720 + 8 nq) cap + k * cap + p for k < 3.  Term id t
+ * is term_sc[t] (32 bytes big-endian, reduced mod q) times entry term_idx[t] of the table of ntab affine points (72 bytes each; an index >= ntab: the identity
+ * entry).  coef: per live proof the fixed-base coefficients mg, mh, eg, eh (4 x 32 bytes).  Out: tw_xy72[(w * groups + grp) * 72 ..] the window sums
+ * (sum_d d B_d) 2^(C w) as affine points (all-zero: the identity; all-0xff: a point with Z = 0), one_xy72[grp] the group's fixed-base point, flags[grp] the
+ * pass's verdict, counters[0] the live terms, counters[1] the oversized buckets seen.  ZK_E_BUFFER without parameters. */
+zk_status zk_test_msm_sum(zk_ctx *ctx, uint32_t groups, uint32_t cap_proofs, uint32_t count, uint32_t nq, uint32_t ntab, const uint8_t *table_xy72,
+                          const uint32_t *term_idx, const uint8_t *term_sc_be32, const uint8_t *coef_be32, uint8_t *tw_xy72, uint8_t *one_xy72, uint32_t *flags,
+                          uint32_t *counters);
+/* The same for the P-256 pass's pack, group, bucket and reduce kernels: groups 8 (11 windows of 13 bits) or 64 (14 windows of 10 bits).  Term ids: 20 p + j for
+ * A term j of proof slot p, then 20 cap + p for the Clambda term; table of 64-byte affine points (every index below ntab), scalars reduced mod n.  Out:
+ * tw_xy64[(w * groups + grp) * 64 ..] the window sums sum_d d B_d (NOT times 2^(C w); all-zero: the identity), flags[grp] the pass's verdict with identity R
+ * parts, counters[0] = 1 if a scalar reached beyond the windows, counters[1] the oversized buckets seen. */
+zk_status zk_test_pmsm_sum(zk_ctx *ctx, uint32_t groups, uint32_t cap_proofs, uint32_t count, uint32_t ntab, const uint8_t *table_xy64, const uint32_t *term_idx,
+                           const uint8_t *term_sc_be32, uint8_t *tw_xy64, uint32_t *flags, uint32_t *counters);
 /* digest[i] = SHA-256(msg[i]) for count messages of identical length len */
 zk_status zk_test_sha256(zk_ctx *ctx, uint64_t count, uint64_t len, const uint8_t *msgs, uint8_t *digests32);
 /* logical RNG draw k of each proof (after rejection mapping), 32 bytes BE */

@@ -1,7 +1,8 @@
 """Index arithmetic of the verifier's bucket reductions, restated over the integers (a "point" is an int, addition is +, doubling is * 2) and held against
 sum_d d * B_d computed directly.  No GPU, no library: this pins the SCHEMES of zkp-ecdsa_amd/csrc/k_msm.hip (k_msm_red1 / k_msm_redk / k_msm_red_last: four levels
 of sixteen with the plain sums of the lower levels' F carried along) and k_pmsm.hip (k_pm_reduce: per-thread running sums, then a tree of (F, G) segments whose
-joins double G_R log2(m) times) for both shapes of each pass; the kernels themselves are held to the oracle by tests/test_gpu_verify.py."""
+joins double G_R log2(m) times) for both shapes of each pass; the kernels themselves are held to the oracle by tests/test_gpu_verify.py (the verdicts) and
+tests/test_gpu_msm_value.py (every window sum, by value)."""
 import random
 
 import pytest

@@ -48,6 +48,7 @@ SYMBOLS = [
     'zk_accountable_verify_batch_device', 'zk_accountable_split_batch', 'zk_accountable_split_batch_device', 'zk_accountable_join_batch',
     'zk_accountable_join_batch_device',
     'zk_test_field_op', 'zk_test_tom_commit', 'zk_test_p256_fixed_mul', 'zk_test_sha256', 'zk_test_rng_draws', 'zk_test_exp_sum',
+    'zk_test_msm_sum', 'zk_test_pmsm_sum',
 ]
 
 STATUS_TEXT = {
@@ -308,6 +309,8 @@ def lib():
         L.zk_test_tom_commit_shape.argtypes = [vp, u32, u64, C.c_char_p, C.c_char_p, vp]
         L.zk_test_p256_fixed_mul.argtypes = [vp, i32, u64, C.c_char_p, vp]
         L.zk_test_exp_sum.argtypes = [vp, C.c_uint32, i32, u64, C.c_char_p, vp, vp]
+        L.zk_test_msm_sum.argtypes = [vp, u32, u32, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.zk_test_pmsm_sum.argtypes = [vp, u32, u32, u32, u32, vp, vp, vp, vp, vp, vp]
         L.zk_test_sha256.argtypes = [vp, u64, u64, C.c_char_p, vp]
         L.zk_test_rng_draws.argtypes = [vp, u64, C.POINTER(ZkRng), u32, u32, vp]
         _lib = L
@@ -1717,6 +1720,46 @@ class Engine:
         self._chk(self.L.zk_test_exp_sum(self.h, key, 1 if neg else 0, n, b''.join(x.to_bytes(32, 'big') for t in gkb_list for x in t), out, fell))
         cols = [[out.raw[64 * (c * n + i):64 * (c * n + i) + 64] for i in range(n)] for c in range(4)]
         return cols[0], cols[1], cols[2], cols[3], list(fell)
+
+    @staticmethod
+    def _in_ptr(buf, nbytes):
+        """bytes or a C-contiguous numpy array of exactly nbytes -> what a void * argument takes (the caller keeps `buf` alive)"""
+        if isinstance(buf, (bytes, bytearray)):
+            assert len(buf) == nbytes, (len(buf), nbytes)
+            return bytes(buf)
+        assert buf.flags['C_CONTIGUOUS'] and buf.nbytes == nbytes, (buf.nbytes, nbytes)
+        return buf.ctypes.data
+
+    def test_msm_sum(self, groups, cap_proofs, count, nq, table, term_idx, term_sc, coef):
+        """zk_test_msm_sum: the Tom-256 cross-proof bucket pass on caller-chosen terms.  table: 72-byte affine points; term_idx (uint32) and term_sc (32 bytes
+        big-endian each) per term id of the cap_proofs * (720 + 8 nq + 3) term slots (bytes or numpy arrays); coef: count x (mg, mh, eg, eh) as ints or 128 count
+        bytes.  Returns (tw, one, flags, live, oversized): tw[w][grp] and one[grp] 72-byte affine points (zero bytes: the identity)."""
+        nw = 20 if groups == 64 else 16
+        nt = cap_proofs * (720 + 8 * nq + 3)
+        tab = b''.join(table)
+        if not isinstance(coef, (bytes, bytearray)):
+            coef = b''.join(x.to_bytes(32, 'big') for t in coef for x in t)
+        assert len(tab) == 72 * len(table) and len(coef) == 128 * count
+        tw, one = C.create_string_buffer(72 * nw * groups), C.create_string_buffer(72 * groups)
+        flags, cnt = (C.c_uint32 * groups)(), (C.c_uint32 * 2)()
+        self._chk(self.L.zk_test_msm_sum(self.h, groups, cap_proofs, count, nq, len(table), tab, self._in_ptr(term_idx, 4 * nt), self._in_ptr(term_sc, 32 * nt),
+                                         bytes(coef) if count else None, tw, one, flags, cnt))
+        tw = [[tw.raw[72 * (w * groups + g):72 * (w * groups + g) + 72] for g in range(groups)] for w in range(nw)]
+        return tw, [one.raw[72 * g:72 * g + 72] for g in range(groups)], list(flags), cnt[0], cnt[1]
+
+    def test_pmsm_sum(self, groups, cap_proofs, count, table, term_idx, term_sc):
+        """zk_test_pmsm_sum: the P-256 cross-proof pass (pack, group, bucket, reduce) on caller-chosen terms.  table: 64-byte affine points; term ids 20 p + j
+        for the A terms, 20 cap_proofs + p for the Clambda terms.  Returns (tw, flags, beyond, oversized): tw[w][grp] = sum_d d B_d as 64-byte affine points
+        (zero bytes: the identity), the pass's verdicts, counters[1] and counters[2]."""
+        nw = 14 if groups == 64 else 11
+        nt = cap_proofs * 21
+        tab = b''.join(table)
+        assert len(tab) == 64 * len(table)
+        tw = C.create_string_buffer(64 * nw * groups)
+        flags, cnt = (C.c_uint32 * groups)(), (C.c_uint32 * 2)()
+        self._chk(self.L.zk_test_pmsm_sum(self.h, groups, cap_proofs, count, len(table), tab, self._in_ptr(term_idx, 4 * nt), self._in_ptr(term_sc, 32 * nt), tw, flags, cnt))
+        tw = [[tw.raw[64 * (w * groups + g):64 * (w * groups + g) + 64] for g in range(groups)] for w in range(nw)]
+        return tw, list(flags), cnt[0], cnt[1]
 
     def test_sha256(self, msgs):
         n, ln = len(msgs), len(msgs[0])

@@ -1908,6 +1908,155 @@ extern "C" zk_status zk_test_exp_sum(zk_ctx* c, uint32_t key, int neg, uint64_t 
         if (inf[i]) memset(out + 64 * (size_t)i, 0, 64);
     return ZK_OK;
 }
+// The cross-proof bucket passes by value (tests/test_gpu_msm_value.py): run_msm and pmsm_prepare / pmsm_sums as api_verify.hip launches them, on a scratch arena
+// carved by vcarve for a chunk of `cap` proofs, with terms the caller chose instead of terms parsed from proofs.
+struct BucketTestArena {
+    DevBuf mem, in, out;
+    VWork V{};
+    MsmBuf M{};
+    PMsmBuf PM{};
+    Soa res{}, res2{};
+    uint32_t* h_pinned = nullptr;
+    ~BucketTestArena() {
+        if (h_pinned) (void)hipHostFree(h_pinned);
+    }
+};
+static zk_status bucket_test_arena(zk_ctx* c, BucketTestArena& A, uint32_t cap, uint32_t nq, bool msm, uint32_t groups) {
+    const uint32_t n = 2 * nq;   // (n + 1) / 2 = nq membership groups per proof
+    const size_t need = vcarve(A.V, A.res, A.res2, A.M, A.PM, nullptr, cap, c->P.sec, n, (uint64_t)1 << n, msm, !msm, groups);
+    HIPCHK(c, hipMalloc(&A.mem.p, need));
+    (void)vcarve(A.V, A.res, A.res2, A.M, A.PM, (uint8_t*)A.mem.p, cap, c->P.sec, n, (uint64_t)1 << n, msm, !msm, groups);
+    HIPCHK(c, hipHostMalloc((void**)&A.h_pinned, 1024, hipHostMallocMapped | hipHostMallocCoherent));
+    memset(A.h_pinned, 0, 1024);
+    A.M.host = A.h_pinned;
+    return ZK_OK;
+}
+// `count` points of the passes' formats as affine bytes: all-zero for the identity, all-0xff where Z = 0
+static zk_status bucket_test_points(zk_ctx* c, const uint32_t* pts, uint32_t count, bool tom, uint8_t* out) {
+    const uint32_t pb = tom ? 72 : 64;
+    DevBuf limbs, bytes, bad, st;
+    HIPCHK(c, hipMalloc(&limbs.p, sizeof(uint32_t) * NLIMB * 5 * (size_t)count)); HIPCHK(c, hipMalloc(&bytes.p, (size_t)pb * count));
+    HIPCHK(c, hipMalloc(&bad.p, 4 * (size_t)count)); HIPCHK(c, hipMalloc(&st.p, 4 * (size_t)count));
+    HIPCHK(c, hipMemsetAsync(st.p, 0, 4 * (size_t)count, c->stream));
+    auto col = [&](uint32_t i) { return Soa{limbs.as<uint32_t>() + (size_t)i * NLIMB * count, count}; };
+    const Soa3 proj{col(0), col(1), col(2)};
+    if (tom) {   // extended (X, Y, T, Z) of 36 words
+        launch_test_unpack_points(c->stream, pts, count, 36, 0, 9, 27, proj, bad.as<uint32_t>());
+        TomList L{};
+        L.proj = proj, L.ax = col(3), L.ay = col(4), L.cap = count;
+        launch_tom_normalize(c->stream, L, count, 0, 1, 1);
+    } else {     // projective (X, Y, Z) of 28 words
+        launch_test_unpack_points(c->stream, pts, count, 28, 0, 9, 18, proj, bad.as<uint32_t>());
+        launch_p256_normalize(c->stream, proj, count, col(3), col(4), st.as<int32_t>(), 1, ZK_E_T_INF, nullptr);   // st[i] != 0: point i is the identity
+    }
+    launch_affine_to_bytes(c->stream, col(3), col(4), count, tom ? 1 : 0, bytes.as<uint8_t>());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::vector<uint32_t> hbad(count), hst(count);
+    HIPCHK(c, hipMemcpy(out, bytes.p, (size_t)pb * count, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(hbad.data(), bad.p, 4 * (size_t)count, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(hst.data(), st.p, 4 * (size_t)count, hipMemcpyDeviceToHost));
+    for (uint32_t i = 0; i < count; i++) {
+        uint8_t* o = out + (size_t)pb * i;
+        bool ident = false;
+        if (tom && !hbad[i]) {   // (0, 1)
+            ident = o[71] == 1;
+            for (int k = 0; k < 71; k++) ident = ident && o[k] == 0;
+        }
+        if (hbad[i] && (tom || !hst[i])) memset(o, 0xff, pb);
+        else if (ident || (!tom && hst[i])) memset(o, 0, pb);
+    }
+    return ZK_OK;
+}
+extern "C" zk_status zk_test_msm_sum(zk_ctx* c, uint32_t groups, uint32_t cap, uint32_t count, uint32_t nq, uint32_t ntab, const uint8_t* table, const uint32_t* term_idx,
+                                     const uint8_t* term_sc, const uint8_t* coef, uint8_t* tw, uint8_t* one, uint32_t* flags, uint32_t* counters) {
+    if (!c || !table || !term_idx || !term_sc || !tw || !one || !flags || !counters || (groups != 8 && groups != 64) || !cap || cap > (1u << 16) || count > cap || !ntab ||
+        nq < 1 || nq > 4 || (count && !coef))
+        return ZK_E_ARG;
+    if (!c->params_set) return ZK_E_BUFFER;
+    if (c->stream_busy) return busy_refusal(c);
+    HIPCHK(c, hipSetDevice(c->device));
+    BucketTestArena A;
+    if (zk_status zs = bucket_test_arena(c, A, cap, nq, true, groups)) return zs;
+    const size_t nterms = (size_t)cap * (VK * V_SLOT_TERMS + nq * 8 + 3), nlc = (size_t)cap * 4 * A.V.n;
+    if (nterms != A.M.cap) return ZK_E_ARG;
+    // inputs: table, indices, scalars, list C's (v, r) bytes
+    const size_t o_idx = ((size_t)72 * ntab + 255) & ~(size_t)255, o_sc = o_idx + 4 * nterms, o_v = o_sc + 32 * nterms, o_r = o_v + 32 * nlc;
+    HIPCHK(c, hipMalloc(&A.in.p, o_r + 32 * nlc));
+    uint8_t* in = A.in.as<uint8_t>();
+    std::vector<uint8_t> lcv(32 * nlc, 0), lcr(32 * nlc, 0);
+    for (uint32_t p = 0; p < count; p++) {   // list C slots p * 4n + {0, 1}: (mg, mh), (eg, eh)
+        const size_t s0 = (size_t)p * 4 * A.V.n;
+        memcpy(&lcv[32 * s0], coef + 128 * (size_t)p, 32), memcpy(&lcr[32 * s0], coef + 128 * (size_t)p + 32, 32);
+        memcpy(&lcv[32 * (s0 + 1)], coef + 128 * (size_t)p + 64, 32), memcpy(&lcr[32 * (s0 + 1)], coef + 128 * (size_t)p + 96, 32);
+    }
+    if (zk_status zs = upload_rows(c, {{in, table, (size_t)72 * ntab}, {in + o_idx, term_idx, 4 * nterms}, {in + o_sc, term_sc, 32 * nterms}, {in + o_v, lcv.data(), 32 * nlc},
+                                       {in + o_r, lcr.data(), 32 * nlc}}))
+        return zs;
+    // the one thing of the prover's workspace the pass reads: list C's coefficients (api.hip: carve)
+    Workspace W{};
+    W.C = cap, W.sec = c->P.sec, W.n = A.V.n;
+    DevBuf lc;
+    HIPCHK(c, hipMalloc(&lc.p, 36 * 7 * nlc + 4096));
+    SoaCarver k(lc.as<uint8_t>());
+    W.lc = k.list(nlc);
+    launch_bytes_to_scalars(c->stream, in + o_v, nlc, W.lc.v);
+    launch_bytes_to_scalars(c->stream, in + o_r, nlc, W.lc.r);
+    launch_test_msm_fill(c->stream, A.V, nq, in, ntab, (const uint32_t*)(in + o_idx), in + o_sc);
+    uint32_t gsz = 0;
+    HIPCHK(c, run_msm(c->stream, c->P, W, A.V, count, nq, A.M, groups, &gsz));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const uint32_t nw = groups == 64 ? 20 : 16;
+    if (zk_status zs = bucket_test_points(c, A.M.Tw, nw * groups, true, tw)) return zs;
+    launch_tom_normalize(c->stream, A.M.one, groups, 0, 1, 1);
+    HIPCHK(c, hipMalloc(&A.out.p, 72 * (size_t)groups));
+    launch_affine_to_bytes(c->stream, A.M.one.ax, A.M.one.ay, groups, 1, A.out.as<uint8_t>());
+    uint32_t cnt[64];
+    if (zk_status zs = download_rows(c, {{A.out.p, one, 72 * (size_t)groups}, {A.M.counters, cnt, sizeof cnt}})) return zs;
+    for (uint32_t g = 0; g < groups; g++) {   // the identity (0, 1) as all-zero
+        uint8_t* o = one + 72 * (size_t)g;
+        bool ident = o[71] == 1;
+        for (int i = 0; i < 71; i++) ident = ident && o[i] == 0;
+        if (ident) memset(o, 0, 72);
+    }
+    msm_read_flags(A.M, groups, flags);
+    counters[0] = cnt[0], counters[1] = cnt[32];
+    if (A.M.host[0] != cnt[0]) {
+        c->err = "the pass's read-back of the live terms differs from its counter";
+        return ZK_E_DEVICE;
+    }
+    return ZK_OK;
+}
+extern "C" zk_status zk_test_pmsm_sum(zk_ctx* c, uint32_t groups, uint32_t cap, uint32_t count, uint32_t ntab, const uint8_t* table, const uint32_t* term_idx, const uint8_t* term_sc,
+                                      uint8_t* tw, uint32_t* flags, uint32_t* counters) {
+    if (!c || !table || !term_idx || !term_sc || !tw || !flags || !counters || (groups != 8 && groups != 64) || !cap || cap > (1u << 16) || count > cap || !ntab) return ZK_E_ARG;
+    if (!c->params_set) return ZK_E_BUFFER;
+    if (c->stream_busy) return busy_refusal(c);
+    for (size_t t = 0; t < (size_t)cap * (VK + 1); t++)
+        if (term_idx[t] >= ntab) return ZK_E_ARG;   // (an affine table has no identity entry)
+    HIPCHK(c, hipSetDevice(c->device));
+    BucketTestArena A;
+    if (zk_status zs = bucket_test_arena(c, A, cap, 1, false, groups)) return zs;
+    if (!A.PM.aos) return ZK_E_BUFFER;
+    const size_t nterms = (size_t)cap * (VK + 1);
+    const size_t o_idx = ((size_t)64 * ntab + 255) & ~(size_t)255, o_sc = o_idx + 4 * nterms;
+    HIPCHK(c, hipMalloc(&A.in.p, o_sc + 32 * nterms));
+    uint8_t* in = A.in.as<uint8_t>();
+    if (zk_status zs = upload_rows(c, {{in, table, (size_t)64 * ntab}, {in + o_idx, term_idx, 4 * nterms}, {in + o_sc, term_sc, 32 * nterms}})) return zs;
+    launch_test_pmsm_fill(c->stream, A.V, in, ntab, (const uint32_t*)(in + o_idx), in + o_sc);
+    Workspace W{};   // (the R parts read the per-proof tables of good proofs only: the fill marks none)
+    W.C = cap, W.sec = c->P.sec, W.n = A.V.n;
+    uint32_t* pm_flags = A.h_pinned + 128;
+    pmsm_prepare(c->stream, W, A.V, count, A.PM, groups);
+    pmsm_sums(c->stream, c->P, count, A.PM, groups, pm_flags);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const uint32_t nw = groups == 64 ? 14 : 11;
+    if (zk_status zs = bucket_test_points(c, A.PM.Tw, nw * groups, false, tw)) return zs;
+    uint32_t cnt[4];
+    if (zk_status zs = download_rows(c, {{A.PM.counters, cnt, sizeof cnt}})) return zs;
+    for (uint32_t g = 0; g < groups; g++) flags[g] = pm_flags[g];
+    counters[0] = cnt[1], counters[1] = cnt[2];
+    return ZK_OK;
+}
 extern "C" zk_status zk_test_sha256(zk_ctx* c, uint64_t count, uint64_t len, const uint8_t* msgs, uint8_t* digests) {
     if (!c || !digests || !count || (len && !msgs)) return ZK_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));

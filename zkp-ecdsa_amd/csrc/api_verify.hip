@@ -4,8 +4,8 @@
 #include "jobs.h"
 #include <optional>
 
-static size_t vcarve(VWork& V, Soa& res, Soa& res2, MsmBuf& M, PMsmBuf& PM, uint8_t* base, uint32_t C, uint32_t sec, uint32_t n, uint64_t N, bool want_msm, bool want_pm,
-                     uint32_t want_groups) {
+size_t vcarve(VWork& V, Soa& res, Soa& res2, MsmBuf& M, PMsmBuf& PM, uint8_t* base, uint32_t C, uint32_t sec, uint32_t n, uint64_t N, bool want_msm, bool want_pm,
+              uint32_t want_groups) {
     SoaCarver k(base);
     V.C = C, V.sec = sec, V.n = n;
     V.gk_fixed = ZK_FIXED, V.com = nullptr;

@@ -383,6 +383,8 @@ static inline zk_status download_rows(zk_ctx* c, std::initializer_list<DownloadR
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return ZK_OK;
 }
+// api_verify.hip: a verifier lane's arena for chunks of C proofs (base == nullptr: the size only); ensure_vworkspace carves the lanes with it, the bucket passes' test hooks a scratch arena
+size_t vcarve(VWork& V, Soa& res, Soa& res2, MsmBuf& M, PMsmBuf& PM, uint8_t* base, uint32_t C, uint32_t sec, uint32_t n, uint64_t N, bool want_msm, bool want_pm, uint32_t want_groups);
 zk_status ensure_workspace(zk_ctx* c, uint32_t C, uint32_t nlanes = 1);   // api.hip: prover workspaces of lanes 0..nlanes-1
 hipError_t malloc_or_shed(zk_ctx* c, void** p, size_t bytes);   // api.hip: a workspace allocation that sheds the optional per-ring tables first
 // settings a queued streamed job was planned with (its lane rotation, chunk size, workspaces, mode) and the buffers it reads stay frozen until it is waited for

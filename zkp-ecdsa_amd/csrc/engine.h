@@ -509,6 +509,10 @@ size_t pmsm_carve(PMsmBuf* M, uint8_t* base, uint32_t Ccap, uint32_t groups);
 void pmsm_prepare(hipStream_t s, const Workspace& W, const VWork& V, uint32_t count, const PMsmBuf& M, uint32_t groups);
 void pmsm_sums(hipStream_t s, const DevParams& P, uint32_t count, const PMsmBuf& M, uint32_t groups, uint32_t* host_flags_pinned);
 void launch_pm_all_ok(hipStream_t s, const VWork& V, uint32_t count);
+// k_verify.hip, unit-test hooks (api.hip: zk_test_msm_sum, zk_test_pmsm_sum): caller-chosen terms in the layout the parsing kernels write, and the passes' points as a projective list
+void launch_test_msm_fill(hipStream_t s, const VWork& V, uint32_t nq, const uint8_t* table_xy72, uint32_t ntab, const uint32_t* idx, const uint8_t* sc_be32);
+void launch_test_pmsm_fill(hipStream_t s, const VWork& V, const uint8_t* table_xy64, uint32_t ntab, const uint32_t* idx, const uint8_t* sc_be32);
+void launch_test_unpack_points(hipStream_t s, const uint32_t* pts, uint32_t count, uint32_t stride, uint32_t ox, uint32_t oy, uint32_t oz, const Soa3& out, uint32_t* bad);
 // k_msm.hip
 size_t msm_workspace_bytes(uint32_t cap);
 size_t msm_red_words(uint32_t groups);

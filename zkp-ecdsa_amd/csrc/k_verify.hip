@@ -1890,3 +1890,55 @@ void launch_v_final(hipStream_t s, const Workspace& W, const VWork& V, uint32_t 
 void launch_v_final_memb(hipStream_t s, const Workspace& W, const VWork& V, uint32_t count, uint8_t* ok, int32_t* status, uint64_t first) {
     L1(k_v_final_memb, count, 64, W, V, count, ok, status, first);
 }
+
+// ------------------------------------------------------------------ unit-test hooks of the cross-proof bucket passes (api.hip: zk_test_msm_sum, zk_test_pmsm_sum)
+// Term id t of the Tom-256 pass (k_msm.hip: the slot terms, the membership terms, the three per proof, as carved for nproofs = V.C proof slots) gets entry
+// idx[t] of a table of 72-byte affine points (0xffffffff: the identity entry) and the scalar sc[32 t ..], through the stores the parsing kernels use.
+__global__ void __launch_bounds__(256) k_test_msm_fill(VWork V, uint32_t nq, const uint8_t* table, uint32_t ntab, const uint32_t* idx, const uint8_t* sc) {
+    const uint32_t t = gtid(), n0 = V.C * VK * V_SLOT_TERMS, n1 = V.C * nq * 8, n2 = V.C * 3;
+    if (t >= n0 + n1 + n2) return;
+    const VTerms& L = t < n0 ? V.slot_terms : t < n0 + n1 ? V.gk_terms : V.misc_terms;
+    const uint32_t e = t < n0 ? t : t < n0 + n1 ? t - n0 : t - n0 - n1, j = idx[t];
+    const Sq s = ld_scalar_q(sc + 32 * (size_t)t);
+    if (j < ntab) put_term_bytes(L, e, table + 72 * (size_t)j, false, s);
+    else vt_st_identity(L, e), soa_st(L.sc, e, s);
+}
+void launch_test_msm_fill(hipStream_t s, const VWork& V, uint32_t nq, const uint8_t* table, uint32_t ntab, const uint32_t* idx, const uint8_t* sc) {
+    L1(k_test_msm_fill, V.C * (VK * V_SLOT_TERMS + nq * 8 + 3), 256, V, nq, table, ntab, idx, sc);
+}
+// The P-256 pass's terms (k_pmsm.hip: k_pm_pack reads them): A term t < V.C * VK and the Clambda term of proof t - V.C * VK, from a table of 64-byte affine
+// points.  No proof is "good" (V.st), so the pass's R parts stay the identity and no per-proof table is read.
+__global__ void __launch_bounds__(256) k_test_pmsm_fill(VWork V, const uint8_t* table, uint32_t ntab, const uint32_t* idx, const uint8_t* sc) {
+    const uint32_t t = gtid(), na = V.C * VK;
+    if (t >= na + V.C) return;
+    const uint32_t j = idx[t] < ntab ? idx[t] : 0;
+    uint32_t xw[8], yw[8];
+    load_be32(table + 64 * (size_t)j, xw);
+    load_be32(table + 64 * (size_t)j + 32, yw);
+    const Fq2 x = fe_to_mont(fe_from_words256_reduce<ModQ>(xw)), y = fe_to_mont(fe_from_words256_reduce<ModQ>(yw));
+    const Sn k = ld_scalar_n(sc + 32 * (size_t)t);
+    if (t < na) soa_st(V.pa_x, t, x), soa_st(V.pa_y, t, y), soa_st(V.pa_sc, t, k);
+    else {
+        const uint32_t p = t - na;
+        soa_st(V.clx, p, x), soa_st(V.cly, p, y), soa_st(V.pSL, p, k);
+        V.st[p] = ZK_E_BAD_ENCODING, V.okflags[p] = 0;
+    }
+}
+void launch_test_pmsm_fill(hipStream_t s, const VWork& V, const uint8_t* table, uint32_t ntab, const uint32_t* idx, const uint8_t* sc) {
+    L1(k_test_pmsm_fill, V.C * (VK + 1), 256, V, table, ntab, idx, sc);
+}
+// count points of `stride` words (coordinates of nine limbs at word offsets ox, oy, oz) -> a projective list; bad[i] = 1 where Z = 0
+__global__ void __launch_bounds__(256) k_test_unpack_points(const uint32_t* pts, uint32_t count, uint32_t stride, uint32_t ox, uint32_t oy, uint32_t oz, Soa3 out, uint32_t* bad) {
+    const uint32_t i = gtid();
+    if (i >= count) return;
+    const uint32_t* p = pts + (size_t)i * stride;
+    uint32_t z = 0;
+    for (int l = 0; l < NLIMB; l++) {
+        out.x.p[(size_t)l * out.x.stride + i] = p[ox + l], out.y.p[(size_t)l * out.y.stride + i] = p[oy + l], out.z.p[(size_t)l * out.z.stride + i] = p[oz + l];
+        z |= p[oz + l];
+    }
+    bad[i] = z == 0;
+}
+void launch_test_unpack_points(hipStream_t s, const uint32_t* pts, uint32_t count, uint32_t stride, uint32_t ox, uint32_t oy, uint32_t oz, const Soa3& out, uint32_t* bad) {
+    L1(k_test_unpack_points, count, 256, pts, count, stride, ox, oy, oz, out, bad);
+}
