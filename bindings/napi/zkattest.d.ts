@@ -226,11 +226,15 @@ export class AccountableProof {
     eq(o: AccountableProof): boolean
 }
 /** an attestation over `keys` with the escrow tag of its keyXcom under the auditor's key; the engine draws both seed sets */
-export function proveAccountable(params: SystemParametersList, auditor: LinkCom, msgHash: Uint8Array, sig: Uint8Array, publicKey: PublicKey, which: number, keys: bigint[] | Buffer): Promise<AccountableProof>
-export function proveAccountables(params: SystemParametersList, auditor: LinkCom, msgHashes: Uint8Array[], sigs: Uint8Array[], publicKeys: PublicKey[], whichs: number[], keys: bigint[] | Buffer): Promise<AccountableProof[]>
+/** one ring for every proof, or one key list per proof (the convention of reringSignatureLists: the zk_rings_accountable_* calls, no active ring) */
+export type AccountableKeys = bigint[] | Buffer | Array<bigint[] | Buffer>
+export function proveAccountable(params: SystemParametersList, auditor: LinkCom, msgHash: Uint8Array, sig: Uint8Array, publicKey: PublicKey, which: number, keys: AccountableKeys): Promise<AccountableProof>
+export function proveAccountables(params: SystemParametersList, auditor: LinkCom, msgHashes: Uint8Array[], sigs: Uint8Array[], publicKeys: PublicKey[], whichs: number[], keys: AccountableKeys): Promise<AccountableProof[]>
 /** true iff the attestation verifies over `keys` for its message hash and its tag verifies against the keyXcom inside it under the auditor's key; what does not deserialise throws */
-export function verifyAccountable(params: SystemParametersList, auditor: LinkCom, msgHash: Uint8Array, keys: bigint[] | Buffer, proof: AccountableProof | Buffer): Promise<boolean>
-export function verifyAccountables(params: SystemParametersList, auditor: LinkCom, msgHashes: Uint8Array[], keys: bigint[] | Buffer, proofs: (AccountableProof | Buffer)[]): Promise<boolean[]>
+export function verifyAccountable(params: SystemParametersList, auditor: LinkCom, msgHash: Uint8Array, keys: AccountableKeys, proof: AccountableProof | Buffer): Promise<boolean>
+export function verifyAccountables(params: SystemParametersList, auditor: LinkCom, msgHashes: Uint8Array[], keys: AccountableKeys, proofs: (AccountableProof | Buffer)[]): Promise<boolean[]>
+/** the auditor's call straight on bundles (zk_rings_accountable_open_batch), one key list per proof: { ring, index } as openEscrowTags gives, null for nobody; it does NOT verify */
+export function openAccountables(params: PedersenParams | SystemParametersList, secret: bigint | Uint8Array, keyLists: Array<bigint[] | Buffer>, proofs: (AccountableProof | Buffer)[]): Promise<({ ring: number; index: number } | null)[]>
 /** pure layout: the attestations for verifySignatureLists / reringSignatureLists, the tags for the auditor's calls; joinAccountable is the inverse (split, re-ring, join keeps the tag) */
 export function splitAccountable(params: PedersenParams | SystemParametersList, proofs: (AccountableProof | Buffer)[]): Promise<{ attestation: SignatureProofList; tag: EscrowTag }[]>
 export function joinAccountable(params: PedersenParams | SystemParametersList, attestations: (SignatureProofList | Buffer)[], tags: (EscrowTag | Buffer)[]): Promise<AccountableProof[]>
@@ -292,6 +296,12 @@ export class Engine {
     accountableProveBatch(msg: Buffer, sig: Buffer, pk: Buffer, whichs: number[], seeds?: Buffer, tagSeeds?: Buffer): { bundles: (Buffer | null)[]; status: Int32Array; partStatus: Int32Array }
     /** zk_accountable_verify_batch: firstBad is 0 for the attestation, 1 for the tag, 0xFFFFFFFF where ok */
     accountableVerifyBatch(msg: Buffer, bundles: Buffer[]): { ok: boolean[]; status: Int32Array; firstBad: Uint32Array }
+    /** zk_rings_accountable_prove_batch: accountableProveBatch with one resident ring id per bundle (whichs[b] indexes ring ringIds[b]); no active ring is read */
+    accountableProveBatchRings(msg: Buffer, sig: Buffer, pk: Buffer, whichs: number[], ringIds: number[], seeds?: Buffer, tagSeeds?: Buffer): { bundles: (Buffer | null)[]; status: Int32Array; partStatus: Int32Array }
+    /** zk_rings_accountable_verify_batch */
+    accountableVerifyBatchRings(msg: Buffer, bundles: Buffer[], ringIds: number[]): { ok: boolean[]; status: Int32Array; firstBad: Uint32Array }
+    /** zk_rings_accountable_open_batch: the auditor's call straight on bundles (0xffffffff: any resident ring); it does NOT verify */
+    accountableOpenBatchRings(secret32: Uint8Array, bundles: Buffer[], ringIds: number[]): { ring: Uint32Array; index: Uint32Array; status: Int32Array }
     /** zk_accountable_split_batch, pure layout: a refused bundle gives an empty attestation, 472 zero bytes and status 10 */
     accountableSplitBatch(bundles: Buffer[]): { attestations: Buffer[]; tags: Buffer[]; status: Int32Array }
     /** zk_accountable_join_batch, pure layout: null and status 10 where the proof's header or the tag's header is refused */

@@ -569,6 +569,24 @@ class Engine {
         const r = native.accountableJoinBatch(this.h, Buffer.concat(proofs), slotOffsets(proofs), Buffer.concat(tags)), st = i32(r.status), o = u64(r.off)
         return { bundles: Array.from(st, (s, b) => (s === 0 ? r.bundles.slice(Number(o[b]), Number(o[b + 1])) : null)), status: st }
     }
+    // zk_rings_accountable_prove_batch / _verify_batch / _open_batch: the same with one RESIDENT ring id per bundle (ringIds[b]; whichs[b] indexes that ring); the
+    // active ring is neither read nor changed.  The open is the auditor's call straight on bundles (0xffffffff = any resident ring) -> { ring, index, status } as
+    // ringsEscrowOpenBatch; it does NOT verify
+    accountableProveBatchRings(msg, sig, pk, whichs, ringIds, seeds, tagSeeds) {
+        const B = whichs.length, u32 = (v) => Buffer.from(Uint32Array.from(v).buffer)
+        const r = native.accountableProveBatchRings(this.h, msg, sig, pk, u32(whichs), u32(ringIds), seeds || crypto.randomBytes(32 * B), tagSeeds || crypto.randomBytes(32 * B))
+        const st = i32(r.status), o = u64(r.off)
+        return { bundles: Array.from(st, (s, b) => (s === 0 ? r.bundles.slice(Number(o[b]), Number(o[b + 1])) : null)), status: st, partStatus: i32(r.partStatus) }
+    }
+    accountableVerifyBatchRings(msg, bundles, ringIds) {
+        const r = native.accountableVerifyBatchRings(this.h, msg, Buffer.concat(bundles), slotOffsets(bundles), Buffer.from(Uint32Array.from(ringIds).buffer))
+        return { ok: Array.from(r.ok, (v) => v === 1), status: i32(r.status), firstBad: new Uint32Array(Uint8Array.from(r.firstBad).buffer) }
+    }
+    accountableOpenBatchRings(secret32, bundles, ringIds) {
+        const r = native.accountableOpenBatchRings(this.h, Buffer.from(secret32), Buffer.concat(bundles), slotOffsets(bundles), Buffer.from(Uint32Array.from(ringIds).buffer))
+        const w = (b) => new Uint32Array(Uint8Array.from(b).buffer)
+        return { ring: w(r.ring), index: w(r.index), status: i32(r.status) }
+    }
     // zk_rings_quorum_prove_batch / zk_rings_quorum_verify_batch: the same with one RESIDENT ring id per member (ringIds[m]; whichs[m] indexes that ring); the
     // active ring plays no part.  A key enrolled in two rings and used through both is "the same key" (status 14)
     ringsQuorumProveBatch(k, msg, sig, pk, whichs, ringIds, seeds, pairSeeds) {
@@ -1603,6 +1621,19 @@ class AccountableProof {
     eq(o) { return o instanceof AccountableProof && this.bytes.equals(o.bytes) }
 }
 const accountableBytes = (p) => (p instanceof AccountableProof ? p.bytes : new AccountableProof(p).bytes)
+// One key list per entry in the place of `keys`: the distinct lists, in groups of at most residentRings, and per group the entries that belong to it.
+// job(withRings, the group's rings, the group's entries, entry -> position of its ring in the group)
+async function accountableGroups(params, keyLists, prove, job) {
+    const { rings, ringOfEntry } = memberRingsOf(keyLists, prove)
+    const { withRings, capacity } = engineFor(paramsOf(params), keyLists[0])
+    const per = capacity()
+    for (let g = 0; g < rings.length; g += per) {
+        const sel = []
+        for (let i = 0; i < keyLists.length; i++) if (ringOfEntry[i] >= g && ringOfEntry[i] < g + per) sel.push(i)
+        await job(withRings, rings.slice(g, g + per), sel, (i) => ringOfEntry[i] - g)
+    }
+    return ringOfEntry
+}
 // proveAccountables(params, auditor, msgHashes, sigs, publicKeys, whichs, keys): one attestation per row over the ring `keys` (the arguments of
 // proveSignatureListBatch), each with the escrow tag of its keyXcom under the auditor's key (a Point or 72 bytes) -> AccountableProof[].  The engine draws both seed sets.
 async function proveAccountables(params, auditor, msgHashes, sigs, publicKeys, whichs, keys) {
@@ -1613,6 +1644,16 @@ async function proveAccountables(params, auditor, msgHashes, sigs, publicKeys, w
     for (const r of raws) if (r.length !== 65 || r[0] !== 4) throw new Error('invalid public key')
     const msg = Buffer.concat(msgHashes.map((m) => Buffer.from(m))), sig = Buffer.concat(sigs.map((x) => Buffer.from(x))), pk = Buffer.concat(raws.map((x) => x.slice(1)))
     const wire = wireLayout
+    if (isKeyLists(keys)) {   // one key list per proof (the convention of reringSignatureLists): zk_rings_accountable_prove_batch per group of resident rings, no active ring
+        if (keys.length !== B) throw new RangeError('proveAccountables: one key list per attestation')
+        const out = new Array(B), cut = (a, w, sel) => Buffer.concat(sel.map((i) => a.slice(w * i, w * i + w)))
+        await accountableGroups(params, keys, true, async (withRings, rings, sel, idOf) => {
+            const r = await withRings(rings, (engine, ids) => { useWire(engine, wire); useAuditor(engine, auditor)
+                return engine.accountableProveBatchRings(cut(msg, 32, sel), cut(sig, 64, sel), cut(pk, 64, sel), sel.map((i) => whichs[i]), sel.map((i) => ids[idOf(i)])) })
+            sel.forEach((i, k) => { if (r.status[k] !== 0) throw statusError(r.status[k]); out[i] = new AccountableProof(r.bundles[k]) })
+        })
+        return out
+    }
     checkRingSize(Buffer.isBuffer(keys) ? keys.length / 32 : keys.length, true)
     const r = await engineFor(params, keys).withRing((engine) => { useWire(engine, wire); useAuditor(engine, auditor); return engine.accountableProveBatch(msg, sig, pk, whichs) })
     return r.bundles.map((b, i) => { if (r.status[i] !== 0) throw statusError(r.status[i]); return new AccountableProof(b) })
@@ -1628,6 +1669,16 @@ async function verifyAccountables(params, auditor, msgHashes, keys, proofs) {
     if (!B) return []
     const raw = proofs.map(accountableBytes), msg = Buffer.concat(msgHashes.map((m) => Buffer.from(m)))
     const wire = isPacked(raw[0].slice(16)) ? 1 : 0, level = verifyLevel, reps = verifyReps
+    if (isKeyLists(keys)) {   // one key list per proof: zk_rings_accountable_verify_batch
+        if (keys.length !== B) throw new RangeError('verifyAccountables: one key list per proof')
+        const out = new Array(B)
+        await accountableGroups(params, keys, false, async (withRings, rings, sel, idOf) => {
+            const r = await withRings(rings, (engine, ids) => { useWire(engine, wire); useVerifyLevel(engine, level); useVerifyReps(engine, reps); useAuditor(engine, auditor)
+                return engine.accountableVerifyBatchRings(Buffer.concat(sel.map((i) => msg.slice(32 * i, 32 * i + 32))), sel.map((i) => raw[i]), sel.map((i) => ids[idOf(i)])) })
+            sel.forEach((i, k) => { if (r.status[k] !== 0) throw statusError(r.status[k]); out[i] = r.ok[k] })
+        })
+        return out
+    }
     checkRingSize(Buffer.isBuffer(keys) ? keys.length / 32 : keys.length, false)
     const r = await engineFor(params, keys).withRing((engine) => { useWire(engine, wire); useVerifyLevel(engine, level); useVerifyReps(engine, reps); useAuditor(engine, auditor)
         return engine.accountableVerifyBatch(msg, raw) })
@@ -1636,6 +1687,21 @@ async function verifyAccountables(params, auditor, msgHashes, keys, proofs) {
 }
 async function verifyAccountable(params, auditor, msgHash, keys, proof) {
     return (await verifyAccountables(params, auditor, [msgHash], keys, [proof]))[0]
+}
+// openAccountables(params, secret, keyLists, proofs): the auditor's call straight on bundles, one key list per proof (zk_rings_accountable_open_batch: no split,
+// only the tags move) -> per proof { ring, index } -- ring counts the distinct key lists in the order of their first appearance, as openEscrowTags has it -- or
+// null for nobody.  It does NOT verify: call verifyAccountables first.
+async function openAccountables(params, secret, keyLists, proofs) {
+    const B = proofs.length
+    if (!isKeyLists(keyLists) || keyLists.length !== B) { if (!B) return []; throw new RangeError('openAccountables: one key list per proof') }
+    const raw = proofs.map(accountableBytes), a = scalarBytes(secret), out = new Array(B)
+    const wire = isPacked(raw[0].slice(16)) ? 1 : 0
+    const ringOfEntry = await accountableGroups(params, keyLists, false, async (withRings, rings, sel, idOf) => {
+        const r = await withRings(rings, (engine, ids) => { useWire(engine, wire); useAuditor(engine, engine.escrowKeygen(a))
+            return engine.accountableOpenBatchRings(a, sel.map((i) => raw[i]), sel.map((i) => ids[idOf(i)])) })
+        sel.forEach((i, k) => { if (r.status[k] !== 0) throw statusError(r.status[k]); out[i] = r.index[k] === 0xffffffff ? null : r.index[k] })
+    })
+    return out.map((w, i) => (w === null ? null : { ring: ringOfEntry[i], index: w }))
 }
 // splitAccountable(params, proofs) -> [{ attestation: SignatureProofList, tag: EscrowTag }]: pure layout, for verifySignatureLists, reringSignatureLists and the
 // auditor's calls (openEscrowTags, shareEscrowTags, combineEscrowShares).  joinAccountable(params, attestations, tags) -> AccountableProof[] is its inverse: a tag is
@@ -1655,6 +1721,6 @@ async function joinAccountable(params, attestations, tags) {
     return r.bundles.map((b, i) => { if (r.status[i] !== 0) throw statusError(r.status[i]); return new AccountableProof(b) })
 }
 
-module.exports = { proveAccountable, proveAccountables, verifyAccountable, verifyAccountables, splitAccountable, joinAccountable, AccountableProof, splitAuditorKey, shareEscrowTags, verifyEscrowShares, combineEscrowShares, EscrowShare, proveEscrowTag, verifyEscrowTag, proveEscrowTags, verifyEscrowTags, openEscrowTags, escrowAuditorKey, EscrowTag, proveQuorum, verifyQuorum, QuorumProof, proveDifferentKeys, verifyDifferentKeys, proveDifferentKeysBatch, verifyDifferentKeysBatch, distinctPairs, DistinctProof, proveSameKey, verifySameKey, proveSameKeys, verifySameKeys, keyCommitment, keyCommitments, LinkProof, reringSignatureLists, keyBlinders, proveMembership, verifyMembership, proveMemberships, verifyMemberships, proveMembershipLists, verifyMembershipLists, GKProof, Commitment, commit, screenSignatureLists, findKey, SCREEN, WHICH_NONE, recoverSignatureLists, recoverKey, RECOVER, verifySignatureLists, proveSignatureLists, _ringGenerations, setVerifyLevel, getVerifyLevel, setVerifyReps, getVerifyReps, generateParamsList, generateParamsListHardened, keyToInt, proveSignatureList, verifySignatureList, proveSignatureListBatch, verifySignatureListBatch,
+module.exports = { openAccountables, proveAccountable, proveAccountables, verifyAccountable, verifyAccountables, splitAccountable, joinAccountable, AccountableProof, splitAuditorKey, shareEscrowTags, verifyEscrowShares, combineEscrowShares, EscrowShare, proveEscrowTag, verifyEscrowTag, proveEscrowTags, verifyEscrowTags, openEscrowTags, escrowAuditorKey, EscrowTag, proveQuorum, verifyQuorum, QuorumProof, proveDifferentKeys, verifyDifferentKeys, proveDifferentKeysBatch, verifyDifferentKeysBatch, distinctPairs, DistinctProof, proveSameKey, verifySameKey, proveSameKeys, verifySameKeys, keyCommitment, keyCommitments, LinkProof, reringSignatureLists, keyBlinders, proveMembership, verifyMembership, proveMemberships, verifyMemberships, proveMembershipLists, verifyMembershipLists, GKProof, Commitment, commit, screenSignatureLists, findKey, SCREEN, WHICH_NONE, recoverSignatureLists, recoverKey, RECOVER, verifySignatureLists, proveSignatureLists, _ringGenerations, setVerifyLevel, getVerifyLevel, setVerifyReps, getVerifyReps, generateParamsList, generateParamsListHardened, keyToInt, proveSignatureList, verifySignatureList, proveSignatureListBatch, verifySignatureListBatch,
     writeJson, readJson, writeJsonBatch, readJsonBatch, SignatureProofList, SystemParametersList, PedersenParams, generatePedersenParams, p256, tomEdwards256, ALL_GROUPS,
     Group, Point, Scalar, Engine, shutdown, setWireLayout, getWireLayout, setOption, native }

@@ -1931,6 +1931,113 @@ static napi_value AccountableVerifyBatch(napi_env env, napi_callback_info info) 
     free(buf);
     return v;
 }
+/* Accountable attestations over several resident rings (include/zkattest_rings_accountable.h: zk_rings_accountable_*): one ring id per bundle, the pool's
+ * first context, no active ring involved.
+ * (h, msg, sig, pk, which: B u32 LE, ringIds: B u32 LE, seeds, tagSeeds) -> what accountableProveBatch returns */
+static napi_value AccountableProveBatchRings(napi_env env, napi_callback_info info) {
+    napi_value argv[8];
+    if (!get_args(env, info, 8, argv)) return NULL;
+    Handle *h = get_handle(env, argv[0], 0);
+    uint8_t *msg, *sig, *pk, *which, *ids, *seeds, *tseeds;
+    size_t lm, ls, lp, lw, li, lsd, lts;
+    if (!h || !get_bytes(env, argv[1], &msg, &lm) || !get_bytes(env, argv[2], &sig, &ls) || !get_bytes(env, argv[3], &pk, &lp) || !get_bytes(env, argv[4], &which, &lw) ||
+        !get_bytes(env, argv[5], &ids, &li) || !get_bytes(env, argv[6], &seeds, &lsd) || !get_bytes(env, argv[7], &tseeds, &lts))
+        return NULL;
+    const size_t B = lm / 32;
+    if (lm % 32 || ls != 64 * B || lp != 64 * B || lw != 4 * B || li != 4 * B || lsd != 32 * B || lts != 32 * B) {
+        napi_throw_range_error(env, NULL, "accountableProveBatchRings: per bundle a 32-byte hash, a 64-byte signature, a 64-byte key, a u32 index, a u32 ring id, 32 seed bytes and 32 tag seed bytes");
+        return NULL;
+    }
+    zk_ctx *c = zk_pool_ctx(h->pool, 0);
+    uint64_t cap = 0;   /* the call's own rule: the sum of the rings' maxima, 0 for an id that is not resident */
+    for (size_t b = 0; b < B; b++) {
+        uint32_t id;
+        memcpy(&id, ids + 4 * b, 4);
+        cap += zk_rings_accountable_proof_max_size(c, id);
+    }
+    uint8_t *buf = (uint8_t *)xmalloc(env, 8 * (B + 1) + 20 * B + cap + 8);
+    if (!buf) return NULL;
+    uint64_t *off = (uint64_t *)buf;
+    int32_t *status = (int32_t *)(buf + 8 * (B + 1)), *pstatus = status + B;
+    uint32_t *w = (uint32_t *)(pstatus + 2 * B), *idw = w + B;   /* (a Buffer's bytes need not be aligned) */
+    uint8_t *out = (uint8_t *)(idw + B);
+    memcpy(w, which, 4 * B), memcpy(idw, ids, 4 * B);
+    zk_rng rng = {ZK_RNG_SEED, seeds, 0}, rng_tags = {ZK_RNG_SEED, tseeds, 0};
+    zk_status st = zk_rings_accountable_prove_batch(c, B, msg, sig, pk, w, idw, &rng, &rng_tags, out, cap, off, status, pstatus);
+    napi_value v = NULL;
+    if (st != ZK_OK) throw_text(env, st, zk_last_error(c));
+    else if (napi_create_object(env, &v) == napi_ok)
+        set_prop(env, v, "bundles", new_buffer(env, out, off[B])), set_prop(env, v, "off", new_buffer(env, off, 8 * (B + 1))), set_prop(env, v, "status", new_buffer(env, status, 4 * B)),
+            set_prop(env, v, "partStatus", new_buffer(env, pstatus, 8 * B));
+    free(buf);
+    return v;
+}
+/* (h, msg: B x 32, bundles: back to back, off: (B + 1) u64 LE, ringIds: B u32 LE) -> what accountableVerifyBatch returns */
+static napi_value AccountableVerifyBatchRings(napi_env env, napi_callback_info info) {
+    napi_value argv[5];
+    if (!get_args(env, info, 5, argv)) return NULL;
+    Handle *h = get_handle(env, argv[0], 0);
+    uint8_t *msg, *blob, *ob, *ids;
+    size_t lm, lb, lo, li;
+    if (!h || !get_bytes(env, argv[1], &msg, &lm) || !get_bytes(env, argv[2], &blob, &lb) || !get_bytes(env, argv[3], &ob, &lo) || !get_bytes(env, argv[4], &ids, &li)) return NULL;
+    const size_t B = lo >= 8 ? lo / 8 - 1 : 0;
+    if (lo < 8 || lo % 8 || lm != 32 * B || li != 4 * B) {
+        napi_throw_range_error(env, NULL, "accountableVerifyBatchRings: (B + 1) u64 offsets, one 32-byte hash and one u32 ring id per bundle");
+        return NULL;
+    }
+    uint8_t *buf = (uint8_t *)xmalloc(env, 8 * (B + 1) + 13 * B + 8);
+    if (!buf) return NULL;
+    uint64_t *off = (uint64_t *)buf;
+    if (!accountable_offsets(env, ob, B, lb, off, "accountableVerifyBatchRings: an offset lies behind the bundles")) {
+        free(buf);
+        return NULL;
+    }
+    int32_t *status = (int32_t *)(buf + 8 * (B + 1));
+    uint32_t *bad = (uint32_t *)(status + B), *idw = bad + B;
+    uint8_t *ok = (uint8_t *)(idw + B);
+    memcpy(idw, ids, 4 * B);
+    zk_ctx *c = zk_pool_ctx(h->pool, 0);
+    zk_status st = zk_rings_accountable_verify_batch(c, B, msg, blob, off, idw, NULL, ok, status, bad);
+    napi_value v = NULL;
+    if (st != ZK_OK) throw_text(env, st, zk_last_error(c));
+    else if (napi_create_object(env, &v) == napi_ok)
+        set_prop(env, v, "ok", new_buffer(env, ok, B)), set_prop(env, v, "status", new_buffer(env, status, 4 * B)), set_prop(env, v, "firstBad", new_buffer(env, bad, 4 * B));
+    free(buf);
+    return v;
+}
+/* (h, secret: 32, bundles: back to back, off: (B + 1) u64 LE, ringIds: B u32 LE, 0xffffffff = any resident ring) -> what ringsEscrowOpenBatch returns: the
+ * auditor's call straight on bundles.  It does not verify. */
+static napi_value AccountableOpenBatchRings(napi_env env, napi_callback_info info) {
+    napi_value argv[5];
+    if (!get_args(env, info, 5, argv)) return NULL;
+    Handle *h = get_handle(env, argv[0], 0);
+    uint8_t *secret, *blob, *ob, *ids;
+    size_t ls, lb, lo, li;
+    if (!h || !get_bytes(env, argv[1], &secret, &ls) || !get_bytes(env, argv[2], &blob, &lb) || !get_bytes(env, argv[3], &ob, &lo) || !get_bytes(env, argv[4], &ids, &li)) return NULL;
+    const size_t B = lo >= 8 ? lo / 8 - 1 : 0;
+    if (ls != 32 || lo < 8 || lo % 8 || li != 4 * B) {
+        napi_throw_range_error(env, NULL, "accountableOpenBatchRings: a 32-byte secret, (B + 1) u64 offsets and one u32 ring id per bundle");
+        return NULL;
+    }
+    uint8_t *buf = (uint8_t *)xmalloc(env, 8 * (B + 1) + 16 * B + 8);
+    if (!buf) return NULL;
+    uint64_t *off = (uint64_t *)buf;
+    if (!accountable_offsets(env, ob, B, lb, off, "accountableOpenBatchRings: an offset lies behind the bundles")) {
+        free(buf);
+        return NULL;
+    }
+    int32_t *status = (int32_t *)(buf + 8 * (B + 1));
+    uint32_t *index = (uint32_t *)(status + B), *ring = index + B, *idw = ring + B;
+    memcpy(idw, ids, 4 * B);
+    zk_ctx *c = zk_pool_ctx(h->pool, 0);
+    zk_status st = zk_rings_accountable_open_batch(c, B, secret, blob, off, idw, ring, index, status);
+    napi_value v = NULL;
+    if (st != ZK_OK) throw_text(env, st, zk_last_error(c));
+    else if (napi_create_object(env, &v) == napi_ok)
+        set_prop(env, v, "ring", new_buffer(env, ring, 4 * B)), set_prop(env, v, "index", new_buffer(env, index, 4 * B)), set_prop(env, v, "status", new_buffer(env, status, 4 * B));
+    free(buf);
+    return v;
+}
 /* zk_accountable_split_batch: (h, bundles: back to back, off: (B + 1) u64 LE) -> {attestations: back to back, off: (B + 1) u64 LE, tags: B x 472, status: B i32 LE} */
 static napi_value AccountableSplitBatch(napi_env env, napi_callback_info info) {
     napi_value argv[3];
@@ -2062,7 +2169,9 @@ static napi_value Init(napi_env env, napi_value exports) {
                {"auditorsSplitKey", AuditorsSplitKey}, {"auditorsSetKeys", AuditorsSetKeys}, {"auditorsShareBatch", AuditorsShareBatch},
                {"auditorsShareVerifyBatch", AuditorsShareVerifyBatch}, {"auditorsCombineBatch", AuditorsCombineBatch},
                {"accountableProveBatch", AccountableProveBatch}, {"accountableVerifyBatch", AccountableVerifyBatch},
-               {"accountableSplitBatch", AccountableSplitBatch}, {"accountableJoinBatch", AccountableJoinBatch}};
+               {"accountableSplitBatch", AccountableSplitBatch}, {"accountableJoinBatch", AccountableJoinBatch},
+               {"accountableProveBatchRings", AccountableProveBatchRings}, {"accountableVerifyBatchRings", AccountableVerifyBatchRings},
+               {"accountableOpenBatchRings", AccountableOpenBatchRings}};
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;
         if (napi_create_function(env, fns[i].name, NAPI_AUTO_LENGTH, fns[i].fn, NULL, &f) != napi_ok) return NULL;

@@ -1120,6 +1120,9 @@ zk_status zk_accountable_join_batch(zk_ctx *ctx, uint64_t B, const uint8_t *proo
                                     uint8_t *out, uint64_t out_cap, uint64_t *out_off /*B+1*/, int32_t *per_proof_status /*B*/);
 zk_status zk_accountable_join_batch_device(zk_ctx *ctx, uint64_t B, const void *d_proofs, const void *d_proof_off /*u64[B+1]*/, const void *d_tags, void *d_out,
                                            uint64_t out_cap, void *d_out_off /*u64[B+1]*/, void *d_per_proof_status /*i32[B]*/);
+/* The `_rings` forms of the above -- one resident ring id per bundle, no active ring, and the auditor's opening straight from bundles -- are the
+ * zk_rings_accountable_* calls.  Their declarations and their contract are in zkattest_rings_accountable.h, which is part of this header. */
+#include "zkattest_rings_accountable.h"
 
 /* ---- two (or more) batches in flight on one context.  zk_prove_batch / zk_verify_batch are synchronous: each call pays its own head
  * (no byte of a chunk exists before its stage 1 is over) and its own tail (the copies of the last slices, with nothing left to

@@ -50,6 +50,11 @@ SYMBOLS = [
     'zk_test_field_op', 'zk_test_tom_commit', 'zk_test_p256_fixed_mul', 'zk_test_sha256', 'zk_test_rng_draws', 'zk_test_exp_sum',
     'zk_test_msm_sum', 'zk_test_pmsm_sum',
 ]
+# ... and what include/zkattest_rings_accountable.h, the part of it that is a file of its own, declares
+RINGS_ACCOUNTABLE_SYMBOLS = [
+    'zk_rings_accountable_proof_max_size', 'zk_rings_accountable_prove_batch', 'zk_rings_accountable_prove_batch_device', 'zk_rings_accountable_verify_batch',
+    'zk_rings_accountable_verify_batch_device', 'zk_rings_accountable_open_batch', 'zk_rings_accountable_open_batch_device',
+]
 
 STATUS_TEXT = {
     0: 'ok', 1: 'point not in group', 2: 'invalid public key', 3: 'T[i] is at infinity', 4: 'T1 is at infinity',
@@ -250,6 +255,15 @@ def lib():
         L.zk_accountable_split_batch_device.argtypes = [vp, u64, vp, vp, vp, u64, vp, vp, vp]
         L.zk_accountable_join_batch.argtypes = [vp, u64, C.c_char_p, vp, C.c_char_p, vp, u64, vp, vp]
         L.zk_accountable_join_batch_device.argtypes = [vp, u64, vp, vp, vp, vp, u64, vp, vp]
+        # ... over several rings: one resident ring id per bundle, and the auditor's opening straight from bundles
+        L.zk_rings_accountable_proof_max_size.argtypes = [vp, u32]
+        L.zk_rings_accountable_proof_max_size.restype = u64
+        L.zk_rings_accountable_prove_batch.argtypes = [vp, u64, C.c_char_p, C.c_char_p, C.c_char_p, vp, vp, C.POINTER(ZkRng), C.POINTER(ZkRng), vp, u64, vp, vp, vp]
+        L.zk_rings_accountable_prove_batch_device.argtypes = [vp, u64, vp, vp, vp, vp, vp, C.POINTER(ZkRng), C.POINTER(ZkRng), vp, u64, vp, vp, vp]
+        L.zk_rings_accountable_verify_batch.argtypes = [vp, u64, C.c_char_p, C.c_char_p, vp, vp, C.c_char_p, vp, vp, vp]
+        L.zk_rings_accountable_verify_batch_device.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.zk_rings_accountable_open_batch.argtypes = [vp, u64, C.c_char_p, C.c_char_p, vp, vp, vp, vp, vp]
+        L.zk_rings_accountable_open_batch_device.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp, vp]
         L.zk_proof_key_commitments.argtypes = [vp, u64, C.c_char_p, vp, vp, vp]
         L.zk_proof_key_commitments_device.argtypes = [vp, u64, vp, vp, vp, vp]
         L.zk_ring_digest.argtypes = [vp, vp]
@@ -1566,6 +1580,96 @@ class Engine:
 
     def accountable_join_device(self, B, d_proofs, d_proof_off, d_tags, d_out, out_cap, d_out_off, d_status):
         self._chk(self.L.zk_accountable_join_batch_device(self.h, B, d_proofs, d_proof_off, d_tags, d_out, out_cap, d_out_off, d_status))
+
+    # ---- accountable attestations over several rings (zk_rings_accountable_*): one resident ring id per bundle, no active ring; the wire format is ZKC1 unchanged
+    def ring_accountable_proof_max_size(self, ring):
+        """zk_rings_accountable_proof_max_size: 16 + ring_proof_max_size(ring) + 472 (0 for an id that is not resident / without params)"""
+        return int(self.L.zk_rings_accountable_proof_max_size(self.h, ring))
+
+    def accountable_prove_batch_rings(self, msg, sig, pk, which, ring_ids, seeds=None, tag_seeds=None, streams=None, stream_blocks=0, tag_streams=None, tag_stream_blocks=0,
+                                      cap=None, want_part_status=True, fill=None):
+        """zk_rings_accountable_prove_batch: accountable_prove_batch with bundle b proving over resident ring ring_ids[b] (which[b] indexes that ring); the active
+        ring is neither read nor changed.  The buffer handed to the call has exactly the capacity rule's size (an id that is not resident counts 0); cap
+        overrides the out_cap handed to the call; fill (one byte value) pre-fills every output, and self.accountable_last_outputs keeps them all as the call
+        left them (bytes, offsets, statuses, part statuses).  Returns (bundles, statuses, part statuses) like accountable_prove_batch."""
+        B = len(which)
+        if len(ring_ids) != B:
+            raise ValueError('one ring id per proof')
+        if seeds is None and streams is None:
+            seeds = os.urandom(32 * B)
+        if tag_seeds is None and tag_streams is None:
+            tag_seeds = os.urandom(32 * B)
+        rng, _keep = self._rng(B, seeds, streams, stream_blocks)
+        rng_tags, _keep2 = self._rng(B, tag_seeds, tag_streams, tag_stream_blocks)
+        sizes = {r: self.ring_accountable_proof_max_size(r) for r in set(ring_ids)}
+        exact = sum(sizes[r] for r in ring_ids)
+        out = C.create_string_buffer(max(exact, 16))
+        off = (C.c_uint64 * (B + 1))()
+        st = (C.c_int32 * max(B, 1))()
+        pst = (C.c_int32 * max(2 * B, 1))()
+        if fill is not None:
+            C.memset(out, fill, len(out)), C.memset(off, fill, C.sizeof(off)), C.memset(st, fill, C.sizeof(st)), C.memset(pst, fill, C.sizeof(pst))
+        w = (C.c_uint32 * max(B, 1))(*which)
+        ids = (C.c_uint32 * max(B, 1))(*ring_ids)
+        rc = self.L.zk_rings_accountable_prove_batch(self.h, B, bytes(msg), bytes(sig), bytes(pk), w, ids, C.byref(rng), C.byref(rng_tags), out, exact if cap is None else cap, off,
+                                                     st, pst if want_part_status else None)
+        self.accountable_last_outputs = (out.raw, list(off), list(st), list(pst))
+        self._chk(rc)
+        raw = out.raw
+        self.accountable_last_raw = (raw[:off[B]], list(off))
+        return ([raw[off[b]:off[b + 1]] if st[b] == 0 else None for b in range(B)], list(st)[:B],
+                [(pst[2 * b], pst[2 * b + 1]) for b in range(B)] if want_part_status else None)
+
+    def accountable_prove_batch_rings_device(self, B, d_msg, d_sig, d_pk, d_which, d_ring_ids, d_rng, d_rng_tags, d_out, out_cap, d_out_off, d_status, d_part_status=None, mode=0,
+                                             stride_blocks=0, tag_mode=0, tag_stride_blocks=0):
+        rng, rng_tags = ZkRng(mode, d_rng, stride_blocks), ZkRng(tag_mode, d_rng_tags, tag_stride_blocks)
+        self._chk(self.L.zk_rings_accountable_prove_batch_device(self.h, B, d_msg, d_sig, d_pk, d_which, d_ring_ids, C.byref(rng), C.byref(rng_tags), d_out, out_cap, d_out_off,
+                                                                 d_status, d_part_status))
+
+    def accountable_verify_batch_rings(self, msg, bundles, ring_ids, vseeds=None, want_first_bad=True, blob=None, offsets=None):
+        """zk_rings_accountable_verify_batch: accountable_verify_batch with bundle b's attestation verified over resident ring ring_ids[b].  Returns (ok list,
+        status list, first_bad list)."""
+        if blob is None:
+            blob, off = b''.join(bundles), self._slots(bundles)
+        else:
+            off = (C.c_uint64 * len(offsets))(*offsets)
+        B = len(off) - 1
+        if len(ring_ids) != B:
+            raise ValueError('one ring id per proof')
+        ok = (C.c_uint8 * max(B, 1))()
+        st = (C.c_int32 * max(B, 1))()
+        bad = (C.c_uint32 * max(B, 1))()
+        ids = (C.c_uint32 * max(B, 1))(*ring_ids)
+        self._chk(self.L.zk_rings_accountable_verify_batch(self.h, B, bytes(msg), bytes(blob) if len(blob) else bytes(16), off, ids, None if vseeds is None else bytes(vseeds),
+                                                           ok, st, bad if want_first_bad else None))
+        return list(ok)[:B], list(st)[:B], list(bad)[:B] if want_first_bad else None
+
+    def accountable_verify_batch_rings_device(self, B, d_msg, d_bundles, d_bundle_off, d_ring_ids, d_vseeds, d_ok, d_status, d_first_bad=None):
+        self._chk(self.L.zk_rings_accountable_verify_batch_device(self.h, B, d_msg, d_bundles, d_bundle_off, d_ring_ids, d_vseeds, d_ok, d_status, d_first_bad))
+
+    def accountable_open_batch_rings(self, secret_be32, bundles, ring_ids, fill=None, blob=None, offsets=None):
+        """zk_rings_accountable_open_batch: the auditor's call on bundles, one resident ring id per bundle (ESCROW_RING_ANY: every resident ring, ascending
+        ids).  Returns (rings, indices -- both 0xffffffff for none --, statuses) like escrow_open_batch_rings.  fill pre-fills the three outputs, and
+        self.accountable_last_outputs keeps them as the call left them.  It does not verify: call accountable_verify_batch_rings first."""
+        if blob is None:
+            blob, off = b''.join(bundles), self._slots(bundles)
+        else:
+            off = (C.c_uint64 * len(offsets))(*offsets)
+        B = len(off) - 1
+        if len(secret_be32) != 32 or len(ring_ids) != B:
+            raise ValueError('the secret is 32 bytes, and every bundle has a ring id')
+        ids = (C.c_uint32 * max(B, 1))(*ring_ids)
+        ring, idx = (C.c_uint32 * max(B, 1))(), (C.c_uint32 * max(B, 1))()
+        st = (C.c_int32 * max(B, 1))()
+        if fill is not None:
+            C.memset(ring, fill, C.sizeof(ring)), C.memset(idx, fill, C.sizeof(idx)), C.memset(st, fill, C.sizeof(st))
+        rc = self.L.zk_rings_accountable_open_batch(self.h, B, bytes(secret_be32), bytes(blob) if len(blob) else bytes(16), off, ids, ring, idx, st)
+        self.accountable_last_outputs = (list(ring), list(idx), list(st))
+        self._chk(rc)
+        return list(ring)[:B], list(idx)[:B], list(st)[:B]
+
+    def accountable_open_batch_rings_device(self, B, d_secret, d_bundles, d_bundle_off, d_ring_ids, d_ring_out, d_index, d_status):
+        self._chk(self.L.zk_rings_accountable_open_batch_device(self.h, B, d_secret, d_bundles, d_bundle_off, d_ring_ids, d_ring_out, d_index, d_status))
 
     # ---- threshold opening (zk_ctx_set_auditors, zk_auditors_*): t of n auditors open a tag through verifiable shares ("ZKS1", 264 bytes)
     def auditors_share_size(self):

@@ -22,10 +22,18 @@ void launch_acc_walk(hipStream_t s, uint32_t n, const uint8_t* bundles, const ui
 // One lane per bundle folds (good, attestation, tag) into ok, status and first_bad (nullptr: not wanted)
 void launch_acc_verdict(hipStream_t s, uint32_t n, const uint8_t* good, const uint8_t* a_ok, const int32_t* a_st, const uint8_t* t_ok, const int32_t* t_st, uint8_t* ok,
                         int32_t* status, uint32_t* first_bad);
+// The `_rings` forms.  One lane per bundle: total[0] += its slot by accountable_plan.h's rule (zkc_capacity_rings), total[1] |= the entries of `R` the ids
+// name (the caller zeroes both words and has checked zkc_capacity_fits)
+void launch_acc_caps(hipStream_t s, uint32_t n, const uint32_t* ring_ids, const QuorumRings& R, uint64_t* total /*2*/);
+// The open.  One lane per bundle merges the walk's refusal and the opener's id check with the opener's (status, ring, index) for the bundle's tag
+void launch_acc_fold_open(hipStream_t s, uint32_t n, const uint8_t* good, const int32_t* o_st, const uint32_t* o_ring, const uint32_t* o_index, uint32_t* ring_out,
+                          uint32_t* index, int32_t* status);
 
 #if !defined(ZK_ACCOUNTABLE_KERNELS_ONLY)
 #include "ctx.h"
 // The internal paths of the tag calls, behind their argument checks (api_escrow.hip); the attestations', the blinders' and the keyXcoms' are quorum.h's
 zk_status zkc_escrow_prove(zk_ctx* c, uint64_t B, const uint8_t* key, const uint8_t* com, const uint8_t* blinder, const zk_rng& rng, uint8_t* out, int32_t* status);   // zk_escrow_prove_batch_device
 zk_status zkc_escrow_verify(zk_ctx* c, uint64_t B, const uint8_t* com, const uint8_t* tags, uint8_t* ok, int32_t* status);                                            // zk_escrow_verify_batch_device
+zk_status zkc_rings_escrow_open(zk_ctx* c, uint64_t B, const uint8_t* secret, const uint8_t* tags, const uint32_t* ids, uint32_t* ring_out, uint32_t* index,
+                                int32_t* status);                                                                                                                     // zk_rings_escrow_open_batch_device
 #endif

@@ -3,6 +3,7 @@
 // (tests/host_arith/host_accountable.cpp).
 #pragma once
 #include "rering_plan.h"
+#include "quorum_plan.h"   // QuorumRings, zkq_ring_entry: what a `_rings` call knows of the context's rings
 
 #define ZKC1_HDR 16
 #define ZK_MAGIC_ZKC1 0x31434b5au   // "ZKC1" as a little-endian word
@@ -11,6 +12,30 @@
 
 // zk_accountable_proof_max_size: the header, one attestation of at most `proof_max` bytes (zk_proof_max_size), the tag
 ZK_HD static inline uint64_t zkc_max_size(uint64_t proof_max) { return proof_max ? ZKC1_HDR + proof_max + ZKC_TAG_BYTES : 0; }
+// The `_rings` forms (one resident ring id per bundle).  zkc_capacity_rings: the slot of a bundle that proves over ring `id` -- zk_rings_accountable_proof_max_size
+// of that ring, 0 for an id that names no resident ring (or one whose proof_max is 0: no params).  `used` (may be NULL) collects the entries the ids name, as a
+// bit set.  A call's out_cap is held against the sum of its bundles' slots; the sum is taken by zkc_capacity_add, which stays at 2^64 - 1 once it is passed:
+// a total that cannot be represented is refused as "too small", never wrapped into a small one.
+ZK_HD static inline uint64_t zkc_capacity_rings(const QuorumRings& R, uint32_t id, uint32_t* used) {
+    const uint32_t r = zkq_ring_entry(R, id);
+    if (r == ZKQ_RINGS || !R.proof_max[r]) return 0;
+    if (used) *used |= 1u << r;
+    return zkc_max_size(R.proof_max[r]);
+}
+ZK_HD static inline uint64_t zkc_capacity_add(uint64_t sum, uint64_t cap) { return sum + cap < sum ? ~0ull : sum + cap; }
+// the sum over a list of ids (the host form's loop; the kernel adds its lanes' slots with atomics, behind zkc_capacity_fits)
+ZK_HD static inline uint64_t zkc_capacity_total(const QuorumRings& R, uint64_t B, const uint32_t* ids, uint32_t* used) {
+    uint64_t total = 0;
+    for (uint64_t b = 0; b < B; b++) total = zkc_capacity_add(total, zkc_capacity_rings(R, ids[b], used));
+    return total;
+}
+// true where B slots of the largest resident ring still fit 64 bits: then no sum over B ids can pass 2^64 - 1, whatever they name
+ZK_HD static inline bool zkc_capacity_fits(const QuorumRings& R, uint64_t B) {
+    uint64_t most = 0;
+    for (uint32_t r = 0; r < R.count && r < ZKQ_RINGS; r++)
+        if (R.resident[r] && zkc_max_size(R.proof_max[r]) > most) most = zkc_max_size(R.proof_max[r]);
+    return !most || B <= ~0ull / most;
+}
 // a bundle whose attestation takes att_bytes
 ZK_HD static inline uint64_t zkc_size(uint64_t att_bytes) { return ZKC1_HDR + att_bytes + ZKC_TAG_BYTES; }
 ZK_HD static inline void zkc_header(uint32_t hw[4], uint32_t total) {   // the 16 header bytes as four words in memory order

@@ -539,6 +539,9 @@ extern "C" zk_status zk_rings_escrow_open_batch_device(zk_ctx* c, uint64_t B, co
     if (zs && zs != ZK_E_OPENING && c->params_set && !c->stream_busy) wipe_witness(c);
     return zs;
 }
+zk_status zkc_rings_escrow_open(zk_ctx* c, uint64_t B, const uint8_t* secret, const uint8_t* tags, const uint32_t* ids, uint32_t* ring_out, uint32_t* index, int32_t* status) {
+    return rings_escrow_open_device(c, B, secret, tags, ids, ring_out, index, status);
+}
 struct RingsEscrowOpenIn {
     uint8_t* secret;
     uint32_t *ids, *ring, *index;

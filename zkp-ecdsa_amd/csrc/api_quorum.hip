@@ -24,7 +24,7 @@ static zk_status quorum_refusal(zk_ctx* c, uint64_t Q, uint32_t k, bool rings) {
     return ZK_OK;
 }
 // The `_rings` forms: the context's rings as the capacity rule sees them (quorum_plan.h), and what a call's ids come to
-static void quorum_rings_table(const zk_ctx* c, QuorumRings& R) {
+void quorum_rings_table(const zk_ctx* c, QuorumRings& R) {
     R = QuorumRings{};
     for (auto& ring : c->rings)
         if (ring.live && R.count < ZKQ_RINGS) {
@@ -37,7 +37,7 @@ struct QuorumCaps {
     uint64_t total;       // the sum of the quorums' capacities: what out_cap is held against
     uint64_t proof_max;   // the largest proof of the rings the ids name: a window's attestation staging follows it
 };
-static uint64_t quorum_largest(const QuorumRings& R, uint32_t used) {
+uint64_t quorum_largest(const QuorumRings& R, uint32_t used) {
     uint64_t m = 0;
     for (uint32_t r = 0; r < R.count; r++)
         if (used >> r & 1) m = std::max<uint64_t>(m, R.proof_max[r]);

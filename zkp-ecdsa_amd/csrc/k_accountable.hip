@@ -86,7 +86,39 @@ __global__ void __launch_bounds__(256) k_acc_verdict(uint32_t n, const uint8_t* 
     if (first_bad) first_bad[b] = bad;
 }
 
+// ------------------------------------------------------------------ the `_rings` forms
+// lane b: its slot by accountable_plan.h's rule; every lane of a wave stays to the end (the shuffles read all 64), one pair of atomics per wave that has
+// anything to add.  The host has checked zkc_capacity_fits: the total cannot wrap.
+__global__ void __launch_bounds__(256) k_acc_caps(uint32_t n, const uint32_t* __restrict__ ids, QuorumRings R, unsigned long long* __restrict__ total) {
+    const uint32_t b = gtid();
+    unsigned long long cap = 0;
+    uint32_t used = 0;
+    if (b < n) cap = zkc_capacity_rings(R, ids[b], &used);
+    for (int d = 32; d; d >>= 1) cap += __shfl_down(cap, d), used |= __shfl_down(used, d);
+    if ((threadIdx.x & 63) == 0 && (cap | used)) atomicAdd(total, cap), atomicOr(total + 1, (unsigned long long)used);
+}
+// lane b of the open: the opener's answer for the tag of bundle b (a refused bundle's tag was 472 zero bytes).  Its ZK_E_ARG -- an id that is neither resident
+// nor ZK_ESCROW_RING_ANY -- comes first; then the walk's refusal; then what the opener found.  Both outputs are "none" under every non-zero status.
+__global__ void __launch_bounds__(256) k_acc_fold_open(uint32_t n, const uint8_t* __restrict__ good, const int32_t* __restrict__ o_st, const uint32_t* __restrict__ o_ring,
+                                                       const uint32_t* __restrict__ o_index, uint32_t* __restrict__ ring_out, uint32_t* __restrict__ index,
+                                                       int32_t* __restrict__ status) {
+    const uint32_t b = gtid();
+    if (b >= n) return;
+    const int32_t o = o_st[b];
+    const int32_t st = o == ZK_E_ARG ? ZK_E_ARG : !good[b] ? ZK_E_BAD_ENCODING : o;
+    status[b] = st;
+    ring_out[b] = st == ZK_OK ? o_ring[b] : 0xffffffffu;
+    index[b] = st == ZK_OK ? o_index[b] : 0xffffffffu;
+}
+
 static dim3 acc_grid(uint32_t n) { return dim3((n + 255) / 256); }
+void launch_acc_caps(hipStream_t s, uint32_t n, const uint32_t* ring_ids, const QuorumRings& R, uint64_t* total) {
+    if (n) hipLaunchKernelGGL(k_acc_caps, acc_grid(n), dim3(256), 0, s, n, ring_ids, R, (unsigned long long*)total);
+}
+void launch_acc_fold_open(hipStream_t s, uint32_t n, const uint8_t* good, const int32_t* o_st, const uint32_t* o_ring, const uint32_t* o_index, uint32_t* ring_out,
+                          uint32_t* index, int32_t* status) {
+    if (n) hipLaunchKernelGGL(k_acc_fold_open, acc_grid(n), dim3(256), 0, s, n, good, o_st, o_ring, o_index, ring_out, index, status);
+}
 void launch_acc_keys(hipStream_t s, uint32_t n, const uint8_t* pk, uint8_t* key) {
     if (n) hipLaunchKernelGGL(k_acc_keys, acc_grid(n), dim3(256), 0, s, n, pk, key);
 }

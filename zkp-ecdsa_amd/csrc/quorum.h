@@ -32,6 +32,10 @@ void launch_q_caps(hipStream_t s, uint32_t Q, uint32_t k, const uint32_t* ring_i
 
 #if !defined(ZK_QUORUM_KERNELS_ONLY)
 #include "ctx.h"
+// The `_rings` forms (api_quorum.hip; api_accountable.hip's share them): the context's rings as the capacity rules see them, and the largest proof among the
+// entries of the bit set `used`
+void quorum_rings_table(const zk_ctx* c, QuorumRings& R);
+uint64_t quorum_largest(const QuorumRings& R, uint32_t used);
 // The internal paths of the existing calls, behind their argument checks (each in the file of its call)
 zk_status zkq_prove_members(zk_ctx* c, uint64_t B, const uint8_t* d_msg, const uint8_t* d_sig, const uint8_t* d_pk, const uint32_t* d_which, const zk_rng& rng, uint8_t* d_out,
                             uint64_t out_cap, uint64_t* d_out_off, int32_t* d_status);                                                                  // api.hip: zk_prove_batch_device
